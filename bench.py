@@ -1,19 +1,26 @@
 #!/usr/bin/env python3
 """bench.py — hmult + key-switch throughput on MI355X (BASELINE.json metric), one JSON line on stdout.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
 
 A "step" is one full hmult (tensor -> hybrid key switch -> add -> rescale) at config_4.cfg, L=45, l=35,
 alpha=15 (BASELINE configs[2]) over synthetic limbs already resident in HBM.  The op runs through the same path
-as the CLI: C++ Operation/Driver -> C ABI -> HIP kernels.  `roofline` is measured live with HIP events on the
-backend's own stream; `cpu_baseline` times the CPU oracle ("port": the reference has no arithmetic to time,
-SURVEY.md §0) on a bounded sample, rank 0, N=1 only.
+as the CLI: C++ Operation/Driver -> C ABI -> HIP kernels.
+
+A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`) with the figures
+derived from it.  --full adds everything else, each from runs of its own: two more K-step regions, the sustained and
+one-op-at-a-time rates, per-launch stage times, `roofline` (measured live with HIP events on the backend's own
+stream), the hrotate / generic-chain / element-wise legs, `cpu_baseline` (times the CPU oracle, "port": the
+reference has no arithmetic to time, SURVEY.md §0, on a bounded sample, rank 0, N=1 only) and the reference model.
+--dump-outputs DIR writes the outputs of the last timed step (dump_outputs).
 """
 import argparse
 import json
 import os
 import sys
 import time
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -282,6 +289,64 @@ def pick_batch(steps, streams, default=DEFAULT_BATCH):
     return max(1, min(default, steps // max(1, streams)))
 
 
+OUTPUT_BUFFERS = ("out.c0", "out.c1")   # the ciphertext a caller of the op receives (hmult: l - 1 limbs after the rescale; hrotate: l)
+DUMP_LIMIT_BYTES = 60_000_000           # --dump-outputs writes at most this much array data (below 64 MB with the .npy headers)
+DUMP_SAMPLE_SEED = 0x44554D50           # fixed: every run and every build keeps the same coefficients
+
+
+def last_step(ops, tail_op, steps, batch, streams):
+    """(instance, batch copy) that computes the last of `steps` timed hmults: run() in main() deals full launches of `batch` ops
+    round-robin over the instances and gives the remainder to the one-op instance"""
+    if steps % batch:
+        return tail_op, 0
+    return ops[(steps // batch - 1) % streams], batch - 1
+
+
+def dump_columns(n_limbs, N, buffers=len(OUTPUT_BUFFERS)):
+    """coefficient indices written per limb: all N when the arrays fit DUMP_LIMIT_BYTES, else a fixed seeded sample (sorted),
+    halved until they fit.  Every residue is written as two float64 values (dump_outputs)."""
+    k = N
+    while buffers * n_limbs * k * 2 * 8 > DUMP_LIMIT_BYTES:
+        k //= 2
+    if k == N:
+        return np.arange(N)
+    return np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(N, k, replace=False))
+
+
+def read_output(inst, name, copy, dist, red_dev):
+    """buffer `name` of batch copy `copy` as [limbs][N] uint64; sharded (limb e on rank e % N): every rank contributes the limbs it
+    owns and rank 0 receives the whole buffer (None on the other ranks)"""
+    mine = inst.read(name, copy=copy)
+    if dist is None:
+        return mine
+    import torch
+    full = torch.zeros(mine.shape, dtype=torch.int64)
+    own = inst.owned(mine.shape[0])
+    full[own] = torch.from_numpy(mine[own].view(np.int64))
+    full = full.to(red_dev)
+    dist.reduce(full, dst=0, op=dist.ReduceOp.SUM)   # disjoint supports: the sum is the assembly
+    return full.cpu().numpy().view(np.uint64) if dist.get_rank() == 0 else None
+
+
+def dump_outputs(path, inst, copy, dist=None, red_dev="cpu"):
+    """--dump-outputs: the ciphertext the last timed step computed, as float64 .npy files under `path`.  A residue (below 2^60) does not
+    fit a float64 mantissa, so each is written exactly as its two 32-bit halves: <buffer>_hi.npy and <buffer>_lo.npy (out_c0_hi ...,
+    value = hi * 2^32 + lo), [limbs][k] over the coefficients of dump_columns.  The inputs are seeded, so the same arguments give the
+    same files in every run.  Returns the names written (rank 0) or []."""
+    arrays = [(name, read_output(inst, name, copy, dist, red_dev)) for name in OUTPUT_BUFFERS]
+    if arrays[0][1] is None:
+        return []
+    os.makedirs(path, exist_ok=True)
+    written = []
+    for name, a in arrays:
+        s = a[:, dump_columns(a.shape[0], a.shape[1])]
+        for half, v in (("hi", s >> np.uint64(32)), ("lo", s & np.uint64(0xFFFFFFFF))):
+            fn = f"{name.replace('.', '_')}_{half}"
+            np.save(os.path.join(path, fn + ".npy"), v.astype(np.float64))
+            written.append(fn)
+    return written
+
+
 def loaded_hip_library():
     """the backend build this process really mapped (an A/B build named by HOMULATOR_HIP_LIB must show up here, not beside the in-tree one)"""
     libs = sorted({ln.split()[-1] for ln in open("/proc/self/maps") if "libhomulator_hip" in ln or "/libhm_" in ln})
@@ -349,8 +414,16 @@ def main():
                     help="1 GPU: the throughput instances replay their launch plan as ONE captured HIP graph per enqueue (config key `graph`): "
                          "the host then takes ~20 us per launch set instead of ~0.3 ms of argument preparation, which matters for a 20-step "
                          "timed region (one launch set per instance); the one-op-at-a-time instance always enqueues directly")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle's leg")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, every other figure (each from runs of its own): two more timed regions, the sustained and "
+                         "one-op-at-a-time rates, per-launch stage times, the NTT-sweep roofline, the hrotate / generic-chain / element-wise "
+                         "legs, the CPU baseline, the reference model; N > 1 also the sharded sweep and independent replicas")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the ciphertext of the last timed step as DIR/<name>.npy (float64, see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:   # started plainly (`python bench.py --gpus N`): be the launcher
         raise SystemExit(self_launch(args.gpus))
 
@@ -463,95 +536,98 @@ def main():
     sync_all()
     barrier()
     dt = time.perf_counter() - t0
-    # two more regions of the same K steps, timed the same way: min / median / max of the three beside `value` (which stays the contract's
-    # single region above: K = 20 is one 3.7 ms graph launch per instance, and it moves by +-4 % from region to region)
+    if args.dump_outputs:   # outside the timed region: what its last step computed (every enqueue recomputes from the same seeded inputs)
+        inst, copy = last_step(ops, tail_op, args.steps, batch, streams)
+        names = dump_outputs(args.dump_outputs, inst, copy, dist, red_dev)
+        if names:
+            print(f"[bench] outputs of the last timed step -> {args.dump_outputs}: {', '.join(names)}", file=sys.stderr, flush=True)
     region_rates = [args.steps / dt]
-    for _ in range(2):
-        barrier()
-        t1 = time.perf_counter()
-        run(args.steps)
-        sync_all()
-        barrier()
-        d1 = time.perf_counter() - t1
-        if dist is not None:
-            tr = torch.tensor([d1], dtype=torch.float64, device=red_dev)
-            dist.all_reduce(tr, op=dist.ReduceOp.MAX)
-            d1 = float(tr.item())
-        region_rates.append(args.steps / d1)
-    # the same steady state over ten launches per instance (information: the contract's K = 20 is one launch per instance)
-    sustained = None
-    if world == 1:
-        n_sus = 10 * streams * batch
-        barrier()
-        t1 = time.perf_counter()
-        run(n_sus)
-        sync_all()
-        barrier()
-        sustained = n_sus / (time.perf_counter() - t1)
-    single = None
-    if world == 1 and (streams > 1 or batch > 1):   # latency mode beside it: one op at a time
-        lat_op = tail_op if tail_op is not None else op
-        lat_op.enqueue(max(2, args.warmup))   # untimed: this instance's key and tables back into the caches the batched instances have just swept
-        lat_op.sync()
-        barrier()
-        t1 = time.perf_counter()
-        lat_op.enqueue(args.steps)
-        lat_op.sync()
-        barrier()
-        single = args.steps / (time.perf_counter() - t1)
-    # N > 1, beside the sharded figure: what the same N GPUs do with INDEPENDENT ops (every rank runs its own two one-GPU instances of
-    # `rep_batch` hmults per launch, no exchange): the node's capacity for a stream of unrelated ops, where `value` is ONE op's limbs spread
-    # over the GPUs.  Information only; any failure here leaves the line without the field.
-    replicas = None
-    if world > 1:
-        rep_batch, rep_launches, reps, ok = 10, 4, [], 1.0
-        try:
-            reps = [host.Op(CFG, opn, L, ELL, ALPHA, device=local_rank, overrides={"seed": host.SEED + 31 * (i + 1), "batch": rep_batch, "graph": 1, "world": 1, "rank": 0}) for i in range(2)]
-            for _ in range(3):
-                for r_ in reps:
-                    r_.enqueue(1)
-            for r_ in reps:
-                r_.sync()
-        except Exception as e:  # noqa: BLE001
-            ok = 0.0
-            print("replicas leg skipped:", repr(e), file=sys.stderr, flush=True)
-        flag = torch.tensor([ok], dtype=torch.float64, device=red_dev)   # every rank takes the same branch: a rank that failed must not leave the others in a collective
-        dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-        if float(flag.item()) == 1.0:
+    sustained = single = replicas = stage_rows = batched_rows = sharded_sweep = None
+    if args.full:
+        # two more regions of the same K steps, timed the same way: min / median / max of the three beside `value` (which stays the contract's
+        # single region above: K = 20 is one 3.7 ms graph launch per instance, and it moves by +-4 % from region to region)
+        for _ in range(2):
             barrier()
             t1 = time.perf_counter()
+            run(args.steps)
+            sync_all()
+            barrier()
+            d1 = time.perf_counter() - t1
+            if dist is not None:
+                tr = torch.tensor([d1], dtype=torch.float64, device=red_dev)
+                dist.all_reduce(tr, op=dist.ReduceOp.MAX)
+                d1 = float(tr.item())
+            region_rates.append(args.steps / d1)
+        # the same steady state over ten launches per instance (information: the contract's K = 20 is one launch per instance)
+        if world == 1:
+            n_sus = 10 * streams * batch
+            barrier()
+            t1 = time.perf_counter()
+            run(n_sus)
+            sync_all()
+            barrier()
+            sustained = n_sus / (time.perf_counter() - t1)
+        if world == 1 and (streams > 1 or batch > 1):   # latency mode beside it: one op at a time
+            lat_op = tail_op if tail_op is not None else op
+            lat_op.enqueue(max(2, args.warmup))   # untimed: this instance's key and tables back into the caches the batched instances have just swept
+            lat_op.sync()
+            barrier()
+            t1 = time.perf_counter()
+            lat_op.enqueue(args.steps)
+            lat_op.sync()
+            barrier()
+            single = args.steps / (time.perf_counter() - t1)
+        # N > 1, beside the sharded figure: what the same N GPUs do with INDEPENDENT ops (every rank runs its own two one-GPU instances of
+        # `rep_batch` hmults per launch, no exchange): the node's capacity for a stream of unrelated ops, where `value` is ONE op's limbs spread
+        # over the GPUs.  Information only; any failure here leaves the line without the field.
+        if world > 1:
+            rep_batch, rep_launches, reps, ok = 10, 4, [], 1.0
             try:
-                for _ in range(rep_launches):
+                reps = [host.Op(CFG, opn, L, ELL, ALPHA, device=local_rank, overrides={"seed": host.SEED + 31 * (i + 1), "batch": rep_batch, "graph": 1, "world": 1, "rank": 0}) for i in range(2)]
+                for _ in range(3):
                     for r_ in reps:
                         r_.enqueue(1)
                 for r_ in reps:
                     r_.sync()
             except Exception as e:  # noqa: BLE001
                 ok = 0.0
-                print("replicas leg failed:", repr(e), file=sys.stderr, flush=True)
-            barrier()
-            res = torch.tensor([time.perf_counter() - t1, -ok], dtype=torch.float64, device=red_dev)
-            dist.all_reduce(res, op=dist.ReduceOp.MAX)
-            if float(res[1].item()) == -1.0:
-                replicas = {"ops_per_s": world * 2 * rep_launches * rep_batch / float(res[0].item()), "instances_per_gpu": 2, "batch": rep_batch,
-                            "note": "independent one-GPU instances on every rank, no exchange (weak scaling of unrelated ops); `value` is one op sharded over the GPUs"}
-        for r_ in reps:
-            try:
-                r_.close()
-            except Exception:  # noqa: BLE001
-                pass
-    # per-launch device time of one op, each launch bracketed by its own event pair (collective when sharded)
-    stage_rows = (tail_op if tail_op is not None else op).stage_times(5)   # sharded: of one batch
-    batched_rows = ops[0].stage_times(3) if world == 1 and batch > 1 else None   # per launch of `batch` ops
+                print("replicas leg skipped:", repr(e), file=sys.stderr, flush=True)
+            flag = torch.tensor([ok], dtype=torch.float64, device=red_dev)   # every rank takes the same branch: a rank that failed must not leave the others in a collective
+            dist.all_reduce(flag, op=dist.ReduceOp.MIN)
+            if float(flag.item()) == 1.0:
+                barrier()
+                t1 = time.perf_counter()
+                try:
+                    for _ in range(rep_launches):
+                        for r_ in reps:
+                            r_.enqueue(1)
+                    for r_ in reps:
+                        r_.sync()
+                except Exception as e:  # noqa: BLE001
+                    ok = 0.0
+                    print("replicas leg failed:", repr(e), file=sys.stderr, flush=True)
+                barrier()
+                res = torch.tensor([time.perf_counter() - t1, -ok], dtype=torch.float64, device=red_dev)
+                dist.all_reduce(res, op=dist.ReduceOp.MAX)
+                if float(res[1].item()) == -1.0:
+                    replicas = {"ops_per_s": world * 2 * rep_launches * rep_batch / float(res[0].item()), "instances_per_gpu": 2, "batch": rep_batch,
+                                "note": "independent one-GPU instances on every rank, no exchange (weak scaling of unrelated ops); `value` is one op sharded over the GPUs"}
+            for r_ in reps:
+                try:
+                    r_.close()
+                except Exception:  # noqa: BLE001
+                    pass
+        # per-launch device time of one op, each launch bracketed by its own event pair (collective when sharded)
+        stage_rows = (tail_op if tail_op is not None else op).stage_times(5)   # sharded: of one batch
+        batched_rows = ops[0].stage_times(3) if world == 1 and batch > 1 else None   # per launch of `batch` ops
     if dist is not None:
         t = torch.tensor([dt], dtype=torch.float64, device=red_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
 
-    # N > 1: the NTT sweep of the extended basis with its limbs sharded like the op's (limb e -> rank e % N), every rank on its own limbs at
-    # the same time (north_star: "HBM GB/s for the NTT sweep ... at 1/2/4/8 GPUs"); per-rank device times gathered on rank 0
-    sharded_sweep = None
-    if world > 1:
+    # N > 1, --full: the NTT sweep of the extended basis with its limbs sharded like the op's (limb e -> rank e % N), every rank on its own
+    # limbs at the same time (HBM GB/s of the sweep at N GPUs); per-rank device times gathered on rank 0
+    if args.full and world > 1:
         own = [e for e in range(ELL + ALPHA) if e % world == rank]
         barrier()
         ns_r, cross_r, one_r, ns_ip_r = measure_ntt_sweep(len(own), sets=max(6, 6 * world // 2), device=local_rank, which=own)
@@ -570,26 +646,12 @@ def main():
     if rank == 0:
         ms = dt / args.steps * 1e3
         value = args.steps / dt   # whole-job rate: the N GPUs complete `steps` sharded hmults together
-        sweep_limbs = ELL + ALPHA
-        if sharded_sweep is None:
-            ntt_ns, sweep_cross, sweep_one_launch, ntt_ns_inplace = measure_ntt_sweep(sweep_limbs)
-        else:   # this rank's own launch is the `roofline` kernel (per GPU); the aggregate over the ranks rides beside it
-            sweep_limbs = sharded_sweep["limbs"][0]
-            ntt_ns, sweep_cross, sweep_one_launch, ntt_ns_inplace = sharded_sweep["ns"][0], sharded_sweep["cross"], sharded_sweep["one_launch"], sharded_sweep["ns_inplace_rank0"]
-        # limb-polys of one-launch transforms that took the agent-scope path of the rendezvous in the op instances (timed region, warm-up, stage timings)
-        op_cross = sum(o.backend_counter("ntt_cross_xcd") for o in ops + ([tail_op] if tail_op is not None else []))
         arith = op.backend_counter("arith")
-        inop_ns, inop_limbs = measure_ntt_inop(batch) if world == 1 else (None, None)
-        achieved = NTT_ALG_BYTES * sweep_limbs / ntt_ns  # B/ns = GB/s
         rin = roofline_inputs()
-        # second ceiling (SURVEY.md §8d "measure and print both"): VALU issue.  One limb-NTT = N/2 * logN butterflies; a
-        # wave executes 64 at a time; `wave_butterfly_ns` is the measured full-chip time per wave-butterfly
-        wb_ns = rin.get("wave_butterfly_ns")
-        valu_floor_ns = wb_ns * BFLY_PER_LIMB_NTT / 64 * sweep_limbs if wb_ns else None
-        hbm_floor_ns = NTT_ALG_BYTES * sweep_limbs / HBM_PEAK_GBS
         out = {
             "metric": "hmult+key-switch ops/sec" if opn == "hmult" else "hrotate+key-switch ops/sec", "value": value, "unit": "ops/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": ms, "higher_is_better": True,
+            "full": args.full,
             "scaling": "strong", "vs_baseline": None, "dtype": "u64", "data": "synthetic",
             "config": {"workload": f"{CFG} {opn} L={L} l={ELL} alpha={ALPHA} (N=2^16, beta=3, " + ("full hybrid key switch + rescale)" if opn == "hmult" else "automorphism + full hybrid key switch)"),
                        "parallelism": "single GPU" if world == 1 else sharded_plan_note(op, world, batch),
@@ -601,19 +663,7 @@ def main():
             "hip_library": loaded_hip_library(),
             # N > 1: what the communicator of the HIP library itself reports (hm_get_counter comm_*): ranks_seen = ncclCommCount over RCCL
             "comm": comm_seen,
-            # one-launch transforms: limb-polys whose workgroups were spread over XCDs (the rendezvous' slow agent-scope path; 0 expected) after
-            # the sweep and in the op instances, and whether the form was in force (0 = off: the guard of hm_create or a time-out)
-            "ntt_cross_xcd": {"after_sweep": sweep_cross, "after_timed_region": op_cross, "ntt_fused_small": sweep_one_launch},
-            "value_min_median_max": None if world > 1 else [min(region_rates), sorted(region_rates)[1], max(region_rates)],   # three K-step regions; `value` is the first
-            "single_stream_ops_per_s": single,
-            "independent_replicas": replicas,
-            "sustained_ops_per_s": sustained,
             "launches_in_timed_region_per_instance": args.steps // (batch * streams),
-            "stage_us": [[kind, name, round(ns * 1e-3, 2)] for kind, name, ns in stage_rows],
-            "stage_us_per_op_batched": None if not batched_rows else [[kind, name, round(ns * 1e-3 / batch, 2)] for kind, name, ns in batched_rows],
-            "exchange_us_per_op": round(sum(ns for kind, _, ns in stage_rows if kind in EXCHANGE_KINDS) * 1e-3 / (batch if world > 1 else 1), 2),
-            "exchange_overlap": exchange_overlap(stage_rows, batch if world > 1 else 1, ms * 1e3, streams if world > 1 else 1,
-                                                 world > 1 and any(" mark=" in ln for ln in op.plan())),   # the op's own plan says whether its exchanges are pipelined
             "hmult_hbm_gbs_algorithmic": alg_bytes / (ms * 1e-3) / 1e9,
             "hmult_frac_of_hbm_peak": alg_bytes / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
             # the same with the evaluation key (2 beta E = 300 limb-polys) charged ONCE per launch of `batch` ops instead of once per
@@ -626,76 +676,106 @@ def main():
                 "frac_of_peak": rin["whole_op_bytes"] / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
                 "batch": rin["whole_op_batch"], "instances": rin["whole_op_instances"], "source": rin.get("whole_op_source"),
                 "note": "bytes from the committed rocprofv3 counter passes of the same launch shape, time from this run"},
-            # the op's dominant launch (ModUp conversion + transforms + key MAC in one C-ABI call): algorithmic bytes with the key charged once per
-            # launch of `batch` ops, HBM bytes of its kernels from the committed counter passes, time from this run's per-launch events
-            "roofline_op": roofline_op(batched_rows, batch, rin) if world == 1 and opn == "hmult" else None,
-            "roofline": {"bound": "valu" if valu_floor_ns and valu_floor_ns > hbm_floor_ns else "hbm",   # the ceiling with the larger floor for this launch, measured
-                         "contract_bound": "hbm",   # ... `achieved` / `peak` / `frac` / `traffic` are the HBM figures the task's contract asks for, whatever binds
-                         "binding_ceiling": "valu" if valu_floor_ns and valu_floor_ns > hbm_floor_ns else "hbm",
-                         "kernel": f"forward NTT sweep, {sweep_limbs} limbs = ONE launch, k_ntt_fused8<8, false, 0, 1, true> (COL pass on non-temporal input loads, per-limb rendezvous on XCD-local atomics, ROW pass)" + ("" if world == 1 else f": this rank's limbs of the 50-limb extended basis (limb e -> rank e % {world}), all ranks sweeping at once"),
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": rin.get("ntt_sweep50_traffic_bytes") if sweep_limbs == 50 and world == 1 else None, "us_per_launch": ntt_ns * 1e-3,
-                         "algorithmic_bytes_per_launch": NTT_ALG_BYTES * sweep_limbs,
-                         "working_set": "6 rotating buffer pairs, 315 MB: past the 256 MiB Infinity Cache",
-                         "hbm": {"floor_us": hbm_floor_ns * 1e-3, "frac": hbm_floor_ns / ntt_ns},
-                         "valu": None if valu_floor_ns is None else {
-                             "floor_us": valu_floor_ns * 1e-3, "frac": valu_floor_ns / ntt_ns, "unit": "wave-butterflies/ns",
-                             "achieved": BFLY_PER_LIMB_NTT / 64 * sweep_limbs / ntt_ns, "peak": 1.0 / wb_ns,
-                             "source": rin.get("wave_butterfly_source")},
-                         # N > 1: the whole 50-limb sweep over the N GPUs = every rank's launch at once; the slowest rank's time counts
-                         "sharded": None if sharded_sweep is None else {
-                             "limbs_per_rank": sharded_sweep["limbs"], "us_per_rank": [round(x * 1e-3, 2) for x in sharded_sweep["ns"]],
-                             "aggregate_gbs": NTT_ALG_BYTES * (ELL + ALPHA) / max(sharded_sweep["ns"]),
-                             "frac_per_gpu": [NTT_ALG_BYTES * n / t / HBM_PEAK_GBS for n, t in zip(sharded_sweep["limbs"], sharded_sweep["ns"])],
-                             "frac_of_aggregate_peak": NTT_ALG_BYTES * (ELL + ALPHA) / max(sharded_sweep["ns"]) / (HBM_PEAK_GBS * world)},
-                         # the OP-level figures to lead with (the sweep above is the contract's `kernel`): the timed region's bytes over its time,
-                         # with the evaluation key charged once per launch (the ops of a batch share it), and by the profiler's counters
-                         "op_frac_evk_once": (alg_bytes - EVK_BYTES * (1 - 1 / batch)) / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "op_measured_frac": None if opn != "hmult" or not rin.get("whole_op_bytes") or rin.get("whole_op_batch") != batch or rin.get("whole_op_instances") != streams
-                         else rin["whole_op_bytes"] / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "op_note": "op_frac_evk_once = (SURVEY.md 8(d) bytes of the op, key once per launch) / step time / 8 TB/s; op_measured_frac = (2 x FETCH_SIZE + WRITE_SIZE per op "
-                                    "from the committed counter passes of this launch shape) / step time / 8 TB/s; `achieved` / `frac` describe the kernel named in `kernel`",
-                         "in_place": {"us_per_launch": ntt_ns_inplace * 1e-3, "achieved": NTT_ALG_BYTES * sweep_limbs / ntt_ns_inplace,
-                                      "frac": NTT_ALG_BYTES * sweep_limbs / ntt_ns_inplace / HBM_PEAK_GBS,
-                                      "note": "the same 50-limb sweep with in == out (k_ntt_fused8<false, 0, 1, false>): the hand-off stays on L2 lines the input loads brought in; "
-                                              "the op's own transforms are out of place, which is what `achieved` / `frac` above describe"},
-                         "in_op": None if not inop_ns else {
-                             "kernel": "the ModUp forward transforms of one launch of the timed region (115 limb-polys per op x batch) as ONE hm_ntt call = k_ntt_col + k_ntt_row, timed alone with HIP events on the backend's stream",
-                             "limbs_per_launch_group": inop_limbs, "us": inop_ns * 1e-3, "us_per_limb": inop_ns * 1e-3 / inop_limbs,
-                             "achieved": NTT_ALG_BYTES * inop_limbs / inop_ns, "frac": NTT_ALG_BYTES * inop_limbs / inop_ns / HBM_PEAK_GBS,
-                             "valu_frac": None if not wb_ns else wb_ns * BFLY_PER_LIMB_NTT / 64 * inop_limbs / inop_ns},
-                         "real_traffic": {
-                             "floor_bytes_per_limb_ntt": 4 * LP,
-                             "note": "a limb-poly (512 KiB) does not fit one CU's LDS (160 KiB), so a transform is two passes through global memory with a hand-off between "
-                                     "them (4 limb-polys per limb-NTT + row twiddles = the floor above).  Since round 4 launches of up to 96 limb-polys run both passes in ONE kernel: the "
-                                     "workgroups of a limb-poly share an XCD, meet at a counter in that XCD's L2 (returning atomics without the agent-scope bit) and read the hand-off "
-                                     "from the L2 that holds it (write-back: profiles/r04_l2_handoff.txt); larger launches stay two kernels, where the rendezvous costs more than it saves"},
-                         "note": "`achieved`/`peak`/`frac`/`traffic` are the HBM figures of the task's contract (`contract_bound`); `bound` names the ceiling "
-                                 "with the larger floor for this launch (the 64-bit modular butterflies are integer VALU work)"},
         }
-        if world == 1 and opn == "hmult":   # configs[3] at the same launch shape, so that the driver's run times it too
-            out["hrotate"] = measure_second_op("hrotate", streams, batch, args.steps, local_rank)
-            # ... and the headline op on SURVEY.md 8(d)'s chain as written (largest primes = 1 mod 2N below 2^60): the generic arithmetic
-            # back-end behind the same ABI (`value` is the default chain of primes h 2^32 + 1: config.moduli)
-            if arith == 0:
-                g = measure_second_op("hmult", streams, batch, args.steps, local_rank, {"chain_bits": 60})
-                out["generic_chain"] = g
-                out["generic_chain_ops_per_s"] = g["ops_per_s"]
-                out["generic_chain_frac_evk_once"] = g["frac_evk_once"]
-        if world == 1 and opn == "hmult":   # the reference's other three ops (one element-wise stage each): rate and fraction of the HBM peak, same launch shape
-            # (50 launches per instance: a launch of ten element-wise ops is ~15 us)
-            out["elementwise"] = {o_: measure_second_op(o_, streams, batch, 50 * streams * batch, local_rank) for o_ in ("hadd", "pmult", "padd")}
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(opn)
-        try:  # the reference's own answer for the same command line, from the build's cycle model (backend = sim): host only
-            t0 = time.time()
-            sim_op = host.Op(CFG, opn, L, ELL, ALPHA, backend=host.BACKEND_SIM)
-            sim = sim_op.sim_run()
-            sim_op.close()
-            out["reference_model"] = {"cycles": sim["cycles"], "instructions": sim["retired"], "drained": sim["drained"], "host_seconds": round(time.time() - t0, 2),
-                                      "note": "simulated accelerator of the .cfg (4 clusters): what the reference simulator prints for this op (the reference's own run of this configuration with MALLOC_PERTURB_ set — its clean run: it reads uninitialised scoreboard operands, include/recodeboard.h:33-46 — took 3 h 18 min and gave the same cycles and counters: tests/golden/structural.json slow_points" + ("" if opn == "hmult" else "; for hrotate the stock binary can differ in a few counters for that reason") + "); not a GPU measurement"}
-        except Exception as e:  # never let the side figure take the bench line down
-            out["reference_model"] = {"error": str(e)[:200]}
+        if args.full:
+            sweep_limbs = ELL + ALPHA
+            if sharded_sweep is None:
+                ntt_ns, sweep_cross, sweep_one_launch, ntt_ns_inplace = measure_ntt_sweep(sweep_limbs)
+            else:   # this rank's own launch is the `roofline` kernel (per GPU); the aggregate over the ranks rides beside it
+                sweep_limbs = sharded_sweep["limbs"][0]
+                ntt_ns, sweep_cross, sweep_one_launch, ntt_ns_inplace = sharded_sweep["ns"][0], sharded_sweep["cross"], sharded_sweep["one_launch"], sharded_sweep["ns_inplace_rank0"]
+            # limb-polys of one-launch transforms that took the agent-scope path of the rendezvous in the op instances (timed region, warm-up, stage timings)
+            op_cross = sum(o.backend_counter("ntt_cross_xcd") for o in ops + ([tail_op] if tail_op is not None else []))
+            inop_ns, inop_limbs = measure_ntt_inop(batch) if world == 1 else (None, None)
+            achieved = NTT_ALG_BYTES * sweep_limbs / ntt_ns  # B/ns = GB/s
+            # second ceiling (SURVEY.md §8d "measure and print both"): VALU issue.  One limb-NTT = N/2 * logN butterflies; a
+            # wave executes 64 at a time; `wave_butterfly_ns` is the measured full-chip time per wave-butterfly
+            wb_ns = rin.get("wave_butterfly_ns")
+            valu_floor_ns = wb_ns * BFLY_PER_LIMB_NTT / 64 * sweep_limbs if wb_ns else None
+            hbm_floor_ns = NTT_ALG_BYTES * sweep_limbs / HBM_PEAK_GBS
+            out.update({
+                # one-launch transforms: limb-polys whose workgroups were spread over XCDs (the rendezvous' slow agent-scope path; 0 expected) after
+                # the sweep and in the op instances, and whether the form was in force (0 = off: the guard of hm_create or a time-out)
+                "ntt_cross_xcd": {"after_sweep": sweep_cross, "after_timed_region": op_cross, "ntt_fused_small": sweep_one_launch},
+                "value_min_median_max": None if world > 1 else [min(region_rates), sorted(region_rates)[1], max(region_rates)],   # three K-step regions; `value` is the first
+                "single_stream_ops_per_s": single,
+                "independent_replicas": replicas,
+                "sustained_ops_per_s": sustained,
+                "stage_us": [[kind, name, round(ns * 1e-3, 2)] for kind, name, ns in stage_rows],
+                "stage_us_per_op_batched": None if not batched_rows else [[kind, name, round(ns * 1e-3 / batch, 2)] for kind, name, ns in batched_rows],
+                "exchange_us_per_op": round(sum(ns for kind, _, ns in stage_rows if kind in EXCHANGE_KINDS) * 1e-3 / (batch if world > 1 else 1), 2),
+                "exchange_overlap": exchange_overlap(stage_rows, batch if world > 1 else 1, ms * 1e3, streams if world > 1 else 1,
+                                                     world > 1 and any(" mark=" in ln for ln in op.plan())),   # the op's own plan says whether its exchanges are pipelined
+                # the op's dominant launch (ModUp conversion + transforms + key MAC in one C-ABI call): algorithmic bytes with the key charged once per
+                # launch of `batch` ops, HBM bytes of its kernels from the committed counter passes, time from this run's per-launch events
+                "roofline_op": roofline_op(batched_rows, batch, rin) if world == 1 and opn == "hmult" else None,
+                "roofline": {"bound": "valu" if valu_floor_ns and valu_floor_ns > hbm_floor_ns else "hbm",   # the ceiling with the larger floor for this launch, measured
+                             "contract_bound": "hbm",   # ... `achieved` / `peak` / `frac` / `traffic` are the HBM figures the BASELINE.json contract asks for, whatever binds
+                             "binding_ceiling": "valu" if valu_floor_ns and valu_floor_ns > hbm_floor_ns else "hbm",
+                             "kernel": f"forward NTT sweep, {sweep_limbs} limbs = ONE launch, k_ntt_fused8<8, false, 0, 1, true> (COL pass on non-temporal input loads, per-limb rendezvous on XCD-local atomics, ROW pass)" + ("" if world == 1 else f": this rank's limbs of the 50-limb extended basis (limb e -> rank e % {world}), all ranks sweeping at once"),
+                             "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                             "traffic": rin.get("ntt_sweep50_traffic_bytes") if sweep_limbs == 50 and world == 1 else None, "us_per_launch": ntt_ns * 1e-3,
+                             "algorithmic_bytes_per_launch": NTT_ALG_BYTES * sweep_limbs,
+                             "working_set": "6 rotating buffer pairs, 315 MB: past the 256 MiB Infinity Cache",
+                             "hbm": {"floor_us": hbm_floor_ns * 1e-3, "frac": hbm_floor_ns / ntt_ns},
+                             "valu": None if valu_floor_ns is None else {
+                                 "floor_us": valu_floor_ns * 1e-3, "frac": valu_floor_ns / ntt_ns, "unit": "wave-butterflies/ns",
+                                 "achieved": BFLY_PER_LIMB_NTT / 64 * sweep_limbs / ntt_ns, "peak": 1.0 / wb_ns,
+                                 "source": rin.get("wave_butterfly_source")},
+                             # N > 1: the whole 50-limb sweep over the N GPUs = every rank's launch at once; the slowest rank's time counts
+                             "sharded": None if sharded_sweep is None else {
+                                 "limbs_per_rank": sharded_sweep["limbs"], "us_per_rank": [round(x * 1e-3, 2) for x in sharded_sweep["ns"]],
+                                 "aggregate_gbs": NTT_ALG_BYTES * (ELL + ALPHA) / max(sharded_sweep["ns"]),
+                                 "frac_per_gpu": [NTT_ALG_BYTES * n / t / HBM_PEAK_GBS for n, t in zip(sharded_sweep["limbs"], sharded_sweep["ns"])],
+                                 "frac_of_aggregate_peak": NTT_ALG_BYTES * (ELL + ALPHA) / max(sharded_sweep["ns"]) / (HBM_PEAK_GBS * world)},
+                             # the OP-level figures to lead with (the sweep above is the contract's `kernel`): the timed region's bytes over its time,
+                             # with the evaluation key charged once per launch (the ops of a batch share it), and by the profiler's counters
+                             "op_frac_evk_once": (alg_bytes - EVK_BYTES * (1 - 1 / batch)) / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                             "op_measured_frac": None if opn != "hmult" or not rin.get("whole_op_bytes") or rin.get("whole_op_batch") != batch or rin.get("whole_op_instances") != streams
+                             else rin["whole_op_bytes"] / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                             "op_note": "op_frac_evk_once = (SURVEY.md 8(d) bytes of the op, key once per launch) / step time / 8 TB/s; op_measured_frac = (2 x FETCH_SIZE + WRITE_SIZE per op "
+                                        "from the committed counter passes of this launch shape) / step time / 8 TB/s; `achieved` / `frac` describe the kernel named in `kernel`",
+                             "in_place": {"us_per_launch": ntt_ns_inplace * 1e-3, "achieved": NTT_ALG_BYTES * sweep_limbs / ntt_ns_inplace,
+                                          "frac": NTT_ALG_BYTES * sweep_limbs / ntt_ns_inplace / HBM_PEAK_GBS,
+                                          "note": "the same 50-limb sweep with in == out (k_ntt_fused8<false, 0, 1, false>): the hand-off stays on L2 lines the input loads brought in; "
+                                                  "the op's own transforms are out of place, which is what `achieved` / `frac` above describe"},
+                             "in_op": None if not inop_ns else {
+                                 "kernel": "the ModUp forward transforms of one launch of the timed region (115 limb-polys per op x batch) as ONE hm_ntt call = k_ntt_col + k_ntt_row, timed alone with HIP events on the backend's stream",
+                                 "limbs_per_launch_group": inop_limbs, "us": inop_ns * 1e-3, "us_per_limb": inop_ns * 1e-3 / inop_limbs,
+                                 "achieved": NTT_ALG_BYTES * inop_limbs / inop_ns, "frac": NTT_ALG_BYTES * inop_limbs / inop_ns / HBM_PEAK_GBS,
+                                 "valu_frac": None if not wb_ns else wb_ns * BFLY_PER_LIMB_NTT / 64 * inop_limbs / inop_ns},
+                             "real_traffic": {
+                                 "floor_bytes_per_limb_ntt": 4 * LP,
+                                 "note": "a limb-poly (512 KiB) does not fit one CU's LDS (160 KiB), so a transform is two passes through global memory with a hand-off between "
+                                         "them (4 limb-polys per limb-NTT + row twiddles = the floor above).  Since round 4 launches of up to 96 limb-polys run both passes in ONE kernel: the "
+                                         "workgroups of a limb-poly share an XCD, meet at a counter in that XCD's L2 (returning atomics without the agent-scope bit) and read the hand-off "
+                                         "from the L2 that holds it (write-back: profiles/r04_l2_handoff.txt); larger launches stay two kernels, where the rendezvous costs more than it saves"},
+                             "note": "`achieved`/`peak`/`frac`/`traffic` are the HBM figures of the BASELINE.json contract (`contract_bound`); `bound` names the ceiling "
+                                     "with the larger floor for this launch (the 64-bit modular butterflies are integer VALU work)"},
+            })
+            if world == 1 and opn == "hmult":   # configs[3] at the same launch shape
+                out["hrotate"] = measure_second_op("hrotate", streams, batch, args.steps, local_rank)
+                # ... and the headline op on SURVEY.md 8(d)'s chain as written (largest primes = 1 mod 2N below 2^60): the generic arithmetic
+                # back-end behind the same ABI (`value` is the default chain of primes h 2^32 + 1: config.moduli)
+                if arith == 0:
+                    g = measure_second_op("hmult", streams, batch, args.steps, local_rank, {"chain_bits": 60})
+                    out["generic_chain"] = g
+                    out["generic_chain_ops_per_s"] = g["ops_per_s"]
+                    out["generic_chain_frac_evk_once"] = g["frac_evk_once"]
+            if world == 1 and opn == "hmult":   # the reference's other three ops (one element-wise stage each): rate and fraction of the HBM peak, same launch shape
+                # (50 launches per instance: a launch of ten element-wise ops is ~15 us)
+                out["elementwise"] = {o_: measure_second_op(o_, streams, batch, 50 * streams * batch, local_rank) for o_ in ("hadd", "pmult", "padd")}
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(opn)
+            try:  # the reference's own answer for the same command line, from the build's cycle model (backend = sim): host only
+                t0 = time.time()
+                sim_op = host.Op(CFG, opn, L, ELL, ALPHA, backend=host.BACKEND_SIM)
+                sim = sim_op.sim_run()
+                sim_op.close()
+                out["reference_model"] = {"cycles": sim["cycles"], "instructions": sim["retired"], "drained": sim["drained"], "host_seconds": round(time.time() - t0, 2),
+                                          "note": "simulated accelerator of the .cfg (4 clusters): what the reference simulator prints for this op (the reference's own run of this configuration with MALLOC_PERTURB_ set — its clean run: it reads uninitialised scoreboard operands, include/recodeboard.h:33-46 — took 3 h 18 min and gave the same cycles and counters: tests/golden/structural.json slow_points" + ("" if opn == "hmult" else "; for hrotate the stock binary can differ in a few counters for that reason") + "); not a GPU measurement"}
+            except Exception as e:  # never let the side figure take the bench line down
+                out["reference_model"] = {"error": str(e)[:200]}
     for o in ops:
         o.close()
     if tail_op is not None:

@@ -113,7 +113,7 @@ def test_bench_flow_rehearsal_four_ranks():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, HOMULATOR_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
-                          "--master-port", "29533", os.path.join(root, "bench.py"), "--gpus", "4", "--steps", "8", "--warmup", "2"],
+                          "--master-port", "29533", os.path.join(root, "bench.py"), "--gpus", "4", "--steps", "8", "--warmup", "2", "--full"],
                          env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
@@ -138,7 +138,7 @@ def test_bench_flow_rehearsal_two_sharded_instances():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, HOMULATOR_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                          "--master-port", "29537", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "8", "--warmup", "2", "--sharded-streams", "2"],
+                          "--master-port", "29537", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "8", "--warmup", "2", "--sharded-streams", "2", "--full"],
                          env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])

@@ -15,7 +15,7 @@ export TMPDIR=/tmp
 cd /tmp
 $ROOT/tools/bflyrate > $OUT/${R}_bflyrate.txt 2>&1
 # 1. kernel trace + stats of the bench command at the driver's settings
-rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt --output-format csv -- python3 $ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/kt.log 2>&1
+rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt --output-format csv -- python3 $ROOT/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/kt.log 2>&1
 python3 $ROOT/tools/trace_summary.py $OUT/kt > $OUT/${R}_bench_kernel_trace_summary.txt 2>&1 || true
 find $OUT/kt -name "*kernel_stats.csv" -exec cp {} $OUT/${R}_bench_kernel_stats.csv \; 2>/dev/null || true
 # 2. HBM traffic of the roofline leg (50-limb forward sweep): FETCH_SIZE and WRITE_SIZE in separate passes

@@ -13,7 +13,7 @@ for r in $(seq 1 ${ROUNDS:-3}); do
   for v in default "$@"; do
     if [ ${OK[$v]} = 0 ] && [ "${TIME_WRONG:-0}" = 0 ]; then continue; fi
     if [ $v = default ]; then unset HOMULATOR_HIP_LIB; else export HOMULATOR_HIP_LIB=$ROOT/ab_builds/$v/libhomulator_hip.so; fi
-    timeout -k 10 200 python3 bench.py --steps 400 --warmup 20 --no-cpu-baseline > $OUT/b_${v}_$r.json 2>/dev/null
+    timeout -k 10 200 python3 bench.py --full --steps 400 --warmup 20 --no-cpu-baseline > $OUT/b_${v}_$r.json 2>/dev/null
     python3 -c "
 import json;d=json.load(open('$OUT/b_${v}_$r.json'));print('$v', round(d['value'],1), round(d['sustained_ops_per_s'],1), round(d['single_stream_ops_per_s'],1), d.get('hip_library'), {0: 'WRONG RESULTS', 1: 'parity ok', 2: 'parity not checked'}[${OK[$v]}])"
   done

@@ -6,8 +6,8 @@ export TMPDIR=/tmp
 bash tools/profile_round.sh r05 > $OUT/profile_round.log 2>&1; echo "profile_round rc=$?"
 bash tools/pmc_kernels.sh r05_pmc_kernels > $OUT/pmc_kernels.log 2>&1; echo "pmc_kernels rc=$?"
 bash tools/r05_trace1.sh > $OUT/trace1.txt 2>&1; echo "trace1 rc=$?"
-for r in 1 2; do timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 > $OUT/bench_k20_$r.json 2> $OUT/bench_k20_$r.err; echo "bench $r rc=$?"; done
-timeout -k 10 300 python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline > $OUT/bench_k200.json 2> $OUT/bench_k200.err
+for r in 1 2; do timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_k20_$r.json 2> $OUT/bench_k20_$r.err; echo "bench $r rc=$?"; done
+timeout -k 10 300 python3 bench.py --full --steps 200 --warmup 20 --no-cpu-baseline > $OUT/bench_k200.json 2> $OUT/bench_k200.err
 python3 - <<P
 import json
 for f in ("bench_k20_1", "bench_k20_2", "bench_k200"):

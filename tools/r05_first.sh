@@ -4,7 +4,7 @@ ROOT=$(pwd); OUT=$ROOT/gpurun_out/r05_first; mkdir -p $OUT
 export TMPDIR=/tmp
 timeout -k 10 600 python3 -m pytest tests -m gpu -x -q > $OUT/pytest.log 2>&1; echo "pytest rc=$?" | tee -a $OUT/pytest.log
 tail -3 $OUT/pytest.log
-timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 > $OUT/bench_k20.json 2> $OUT/bench_k20.err; echo "bench rc=$?"
+timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_k20.json 2> $OUT/bench_k20.err; echo "bench rc=$?"
 bash tools/pmc_kernels.sh r05_pmc_kernels > $OUT/pmc_kernels.log 2>&1; echo "pmc rc=$?"
 cp gpurun_out/r05_pmc_kernels/summary.txt $OUT/pmc_kernels_summary.txt 2>/dev/null
 python3 - <<P

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 timeout -k 10 900 python3 -m pytest tests/test_gpu_kernels.py tests/test_gpu_ops.py tests/test_gpu_ntt_fused.py -m gpu -x -q > $OUT/pytest.log 2>&1; echo "pytest rc=$?" | tee -a $OUT/pytest.log
 tail -5 $OUT/pytest.log
 for r in 1 2; do
-timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_k20_$r.json 2> $OUT/bench_k20.err; echo "bench rc=$?"
+timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_k20_$r.json 2> $OUT/bench_k20.err; echo "bench rc=$?"
 python3 - <<P
 import json
 d = json.load(open("$OUT/bench_k20_$r.json"))

@@ -4,7 +4,7 @@ ROOT=$(pwd); OUT=$ROOT/gpurun_out/r05_second; mkdir -p $OUT
 export TMPDIR=/tmp
 timeout -k 10 900 python3 -m pytest tests -m gpu -x -q > $OUT/pytest.log 2>&1; echo "pytest rc=$?" | tee -a $OUT/pytest.log
 tail -15 $OUT/pytest.log
-timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_k20.json 2> $OUT/bench_k20.err; echo "bench rc=$?"
+timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_k20.json 2> $OUT/bench_k20.err; echo "bench rc=$?"
 python3 - <<P
 import json
 d = json.load(open("$OUT/bench_k20.json"))

@@ -7,7 +7,7 @@ timeout -k 10 900 python3 -m pytest tests -m gpu -x -q -k "hrotate or rotate or 
 for v in 1 0; do timeout -k 10 200 python3 tools/stage_times_batch.py 10 hrotate config_4.cfg 45 35 15 fuse_auto=$v; done
 for r in 1 2 3; do
   for v in 1 0; do
-    HOMULATOR_FUSE_AUTO=$v timeout -k 10 200 python3 bench.py --steps 100 --warmup 10 --no-cpu-baseline > $OUT/b_${v}_$r.json 2> $OUT/b_${v}_$r.err
+    HOMULATOR_FUSE_AUTO=$v timeout -k 10 200 python3 bench.py --full --steps 100 --warmup 10 --no-cpu-baseline > $OUT/b_${v}_$r.json 2> $OUT/b_${v}_$r.err
     python3 -c "
 import json;d=json.load(open('$OUT/b_${v}_$r.json'));print('fuse_auto=$v', 'hrotate', round(d['hrotate']['ops_per_s'],1), [round(x,1) for x in d['hrotate']['ops_per_s_min_median_max']], 'value', round(d['value'],1))"
   done

@@ -1,5 +1,5 @@
 export TMPDIR=/tmp
-python3 bench.py --steps 4000 --warmup 20 --no-cpu-baseline > /tmp/b.json 2>/dev/null &
+python3 bench.py --full --steps 4000 --warmup 20 --no-cpu-baseline > /tmp/b.json 2>/dev/null &
 PID=$!
 sleep 6
 for i in 1 2 3 4 5 6; do rocm-smi --showclocks --showpower 2>/dev/null | grep -E "sclk|mclk|Power|fclk" | head -6; echo ---; sleep 0.7; done

@@ -7,7 +7,7 @@ timeout -k 10 600 python3 -m pytest tests/test_gpu_kernels.py tests/test_gpu_ops
 for r in 1 2 3; do
   for v in default head; do
     if [ $v = default ]; then unset HOMULATOR_HIP_LIB; else export HOMULATOR_HIP_LIB=$ROOT/ab_builds/$v/libhomulator_hip.so; fi
-    timeout -k 10 200 python3 bench.py --steps 200 --warmup 10 --no-cpu-baseline > $OUT/b_${v}_$r.json 2> $OUT/b_${v}_$r.err
+    timeout -k 10 200 python3 bench.py --full --steps 200 --warmup 10 --no-cpu-baseline > $OUT/b_${v}_$r.json 2> $OUT/b_${v}_$r.err
     python3 -c "
 import json;d=json.load(open('$OUT/b_${v}_$r.json'));print('$v', 'value', round(d['value'],1), 'generic', round(d['generic_chain_ops_per_s'],1), 'hrotate', round(d['hrotate']['ops_per_s'],1), 'one at a time', round(d['single_stream_ops_per_s'],1), 'sweep us', round(d['roofline']['us_per_launch'],2), 'in place', round(d['roofline']['in_place']['us_per_launch'],2), 'in op us/limb', round(d['roofline']['in_op']['us_per_limb'],4))"
   done
