@@ -1726,6 +1726,134 @@ extern "C" hm_status hm_inner_product_ex(hm_ctx *c, const hm_ip_desc *d) {
   return HM_OK;
 }
 
+// ---- K5 hoisted (hm_inner_product_hoisted): the key products of n_rot rotations of ONE ciphertext from its unrotated digits.  sigma_g takes the
+// aligned pair (off, off + 1) of a digit to the aligned pair at hm_auto_src(off, g^-1 mod 2N), in order or swapped (hm_ntt_core.h): a thread
+// loads its pair of every digit ONCE and, rotation by rotation, gathers the two keys and stores the two sums at that destination.  One record per
+// (rotation, entry) in a device table (16 rotations of 64 entries do not fit the kernel arguments).
+struct HmIpHoistRec {
+  uint16_t x[HM_IP_MAX_TERMS];
+  uint16_t y[2][HM_IP_MAX_TERMS];
+  uint16_t out[2];
+  uint16_t mod, pad;
+};
+struct HmIpHoistArgs {
+  const uint64_t *x, *y;
+  uint64_t *out;
+  const HmMod *mods;
+  const HmIpHoistRec *rec;   // [n_rot][n_limbs]
+  uint32_t logN, n_limbs, n_rot;
+  uint32_t dst_galois[HM_IP_HOISTED_MAX_ROT];   // g_r^-1 mod 2N: coefficient i of a digit lands at hm_auto_src(i, g_r^-1) of rotation r
+};
+
+template <int TERMS>
+__global__ void __launch_bounds__(256) k_inner_product_hoisted(HmIpHoistArgs a) {
+  const uint32_t N = 1u << a.logN;
+  const uint32_t per_limb = N / 512;
+  const uint32_t entry = blockIdx.x / per_limb, chunk = blockIdx.x % per_limb;
+  if (entry >= a.n_limbs) return;
+  const HmIpHoistRec &l0 = a.rec[entry];
+  const HmMod m = a.mods[l0.mod];
+  const uint32_t off = chunk * 512 + 2 * threadIdx.x;
+  ulonglong2 vx[TERMS];
+#pragma unroll
+  for (int j = 0; j < TERMS; ++j) vx[j] = *reinterpret_cast<const ulonglong2 *>(a.x + (size_t)l0.x[j] * N + off);
+#pragma unroll 1
+  for (uint32_t r = 0; r < a.n_rot; ++r) {
+    const HmIpHoistRec &lb = a.rec[(size_t)r * a.n_limbs + entry];
+    const uint32_t d = hm_auto_src(off, a.dst_galois[r], a.logN);
+    const size_t p = d & ~1u;
+    const bool swap = d & 1u;
+    ulonglong2 vy[2][TERMS];
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+#pragma unroll
+      for (int j = 0; j < TERMS; ++j) vy[k][j] = *reinterpret_cast<const ulonglong2 *>(a.y + (size_t)lb.y[k][j] * N + p);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      hm_u128 s0 = 0, s1 = 0;
+#pragma unroll
+      for (int j = 0; j < TERMS; ++j) {
+        const uint64_t x0 = swap ? vx[j].y : vx[j].x, x1 = swap ? vx[j].x : vx[j].y;
+        s0 += (hm_u128)x0 * vy[k][j].x;
+        s1 += (hm_u128)x1 * vy[k][j].y;
+      }
+      const ulonglong2 o = {hm_barrett(s0, m), hm_barrett(s1, m)};   // the same sums as k_inner_product's: bit-identical outputs
+      *reinterpret_cast<ulonglong2 *>(a.out + (size_t)lb.out[k] * N + p) = o;
+    }
+  }
+}
+
+// does a limb-poly of (ib, il[0..ni)) share an address with a limb-poly of (ob, ol[0..no))?  Compared as address RANGES (base + limb x N words),
+// so that different base pointers into one allocation are caught as well
+static bool limb_ranges_overlap(const uint64_t *ob, const uint32_t *ol, uint32_t no, const uint64_t *ib, const uint32_t *il, uint32_t ni, uint32_t N) {
+  uint32_t top = 0;
+  for (uint32_t i = 0; i < no; ++i) top = std::max(top, ol[i]);
+  std::vector<uint8_t> written((size_t)top + 1, 0);
+  for (uint32_t i = 0; i < no; ++i) written[ol[i]] = 1;
+  const int64_t lb = (int64_t)N * 8, base = (int64_t)(reinterpret_cast<intptr_t>(ib) - reinterpret_cast<intptr_t>(ob));
+  for (uint32_t i = 0; i < ni; ++i) {
+    const int64_t s = base + (int64_t)il[i] * lb;                   // bytes [s, s + lb) from the output base
+    const int64_t o0 = s >= 0 ? s / lb : -((-s + lb - 1) / lb);     // output limb-polys touched: o0, and o0 + 1 unless s is aligned to one
+    for (int64_t o = o0; o <= o0 + (s != o0 * lb ? 1 : 0); ++o)
+      if (o >= 0 && o <= (int64_t)top && written[(size_t)o]) return true;
+  }
+  return false;
+}
+
+extern "C" hm_status hm_inner_product_hoisted(hm_ctx *c, const hm_ip_hoisted_desc *d) {
+  if (!c) return HM_ERR_ARG;
+  if (!d || !d->x || !d->x_limbs || !d->y || !d->y_limbs || !d->out || !d->out_limbs || !d->mod_ids || !d->galois)
+    return fail(c, HM_ERR_ARG, "hm_inner_product_hoisted: null argument");
+  const uint32_t n = d->n, T = d->n_terms, R = d->n_rot, N = c->P.N;
+  if (T == 0 || T > HM_IP_MAX_TERMS || R == 0 || R > HM_IP_HOISTED_MAX_ROT)
+    return fail(c, HM_ERR_ARG, "hm_inner_product_hoisted: n_terms in [1,%d], n_rot in [1,%d]", HM_IP_MAX_TERMS, HM_IP_HOISTED_MAX_ROT);
+  for (uint32_t r = 0; r < R; ++r)
+    if (!(d->galois[r] & 1) || d->galois[r] >= 2 * N) return fail(c, HM_ERR_ARG, "hm_inner_product_hoisted: galois[%u] is not an odd number below 2N", r);
+  hm_status st;
+  if ((st = check_limbs(c, "hm_inner_product_hoisted", d->x_limbs, n * T)) || (st = check_limbs(c, "hm_inner_product_hoisted", d->y_limbs, R * n * 2 * T)) ||
+      (st = check_limbs(c, "hm_inner_product_hoisted", d->out_limbs, R * n * 2)) || (st = check_mods(c, "hm_inner_product_hoisted", d->mod_ids, n)))
+    return st;
+  // every output is stored at other positions than the ones its workgroup reads (the scatter of sigma_r): it may overlap no digit and no key
+  if (limb_ranges_overlap(d->out, d->out_limbs, R * n * 2, d->x, d->x_limbs, n * T, N))
+    return fail(c, HM_ERR_ARG, "hm_inner_product_hoisted: an output limb-poly overlaps a digit (x)");
+  if (limb_ranges_overlap(d->out, d->out_limbs, R * n * 2, d->y, d->y_limbs, R * n * 2 * T, N))
+    return fail(c, HM_ERR_ARG, "hm_inner_product_hoisted: an output limb-poly overlaps a key limb-poly (y)");
+  if (n == 0) return HM_OK;
+  std::vector<HmIpHoistRec> recs((size_t)R * n);
+  memset(recs.data(), 0, sizeof(HmIpHoistRec) * recs.size());
+  for (uint32_t r = 0; r < R; ++r)
+    for (uint32_t i = 0; i < n; ++i) {
+      HmIpHoistRec &l = recs[(size_t)r * n + i];
+      const size_t e = (size_t)r * n + i;
+      l.mod = (uint16_t)d->mod_ids[i];
+      for (uint32_t j = 0; j < T; ++j) l.x[j] = (uint16_t)d->x_limbs[(size_t)i * T + j];
+      for (uint32_t k = 0; k < 2; ++k) {
+        l.out[k] = (uint16_t)d->out_limbs[e * 2 + k];
+        for (uint32_t j = 0; j < T; ++j) l.y[k][j] = (uint16_t)d->y_limbs[(e * 2 + k) * T + j];
+      }
+    }
+  HM_HIP(c, hipSetDevice(c->device));
+  const void *dtab = nullptr;
+  if ((st = device_table(c, recs.data(), sizeof(HmIpHoistRec) * recs.size(), &dtab))) return st;
+  HmIpHoistArgs a;
+  a.x = d->x; a.y = d->y; a.out = d->out; a.mods = c->d_mods; a.rec = static_cast<const HmIpHoistRec *>(dtab);
+  a.logN = c->P.logN; a.n_limbs = n; a.n_rot = R;
+  for (uint32_t r = 0; r < HM_IP_HOISTED_MAX_ROT; ++r) {
+    const uint32_t g = r < R ? d->galois[r] : 1u;
+    uint32_t v = g;                                   // g^-1 mod 2^32 (g odd: Newton's iteration doubles the correct low bits), then mod 2N
+    for (int it = 0; it < 5; ++it) v *= 2u - g * v;
+    a.dst_galois[r] = v & (2 * N - 1);
+  }
+  const dim3 grid(n * (N / 512));
+  switch (T) {
+  case 1: hipLaunchKernelGGL(k_inner_product_hoisted<1>, grid, dim3(256), 0, c->stream, a); break;
+  case 2: hipLaunchKernelGGL(k_inner_product_hoisted<2>, grid, dim3(256), 0, c->stream, a); break;
+  case 3: hipLaunchKernelGGL(k_inner_product_hoisted<3>, grid, dim3(256), 0, c->stream, a); break;
+  case 4: hipLaunchKernelGGL(k_inner_product_hoisted<4>, grid, dim3(256), 0, c->stream, a); break;
+  }
+  HM_HIP(c, hipGetLastError());
+  return HM_OK;
+}
 
 // K1 x K5: out[i][k] = sum_j X_j[i] * y[i][k][j] with X_j[i] = NTT(x[i][j]) for the digits that go through
 // the transform (x_is_coeff) and x[i][j] itself for a digit's own limbs.  Two launches: the COL pass of every transformed

@@ -21,6 +21,7 @@ SYMBOLS = [
     "hm_capture_begin", "hm_capture_end", "hm_graph_launch", "hm_graph_destroy", "hm_comm_info", "hm_slice_rows", "hm_limbs_to_slices", "hm_slices_to_limbs", "hm_replicate_limbs",
     "hm_set_option", "hm_get_counter", "hm_ntt_inner_product", "hm_exchange_stream", "hm_exchange_mark", "hm_exchange_wait",
     "hm_bconv_col", "hm_limbs_to_colslices", "hm_colslices_to_limbs", "hm_ntt_second_pass", "hm_ntt_ex", "hm_capability", "hm_inner_product_ex",
+    "hm_inner_product_hoisted",
 ]
 
 
@@ -34,6 +35,11 @@ class hm_ntt_fused_desc(C.Structure):
 class hm_ip_desc(C.Structure):
     _fields_ = [("x", C.c_void_p), ("x_limbs", C.c_void_p), ("y", C.c_void_p), ("y_limbs", C.c_void_p), ("out", C.c_void_p), ("out_limbs", C.c_void_p),
                 ("mod_ids", C.c_void_p), ("n", C.c_uint32), ("n_terms", C.c_uint32), ("n_out", C.c_uint32), ("x_galois", C.c_uint32)]
+
+
+class hm_ip_hoisted_desc(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("x_limbs", C.c_void_p), ("y", C.c_void_p), ("y_limbs", C.c_void_p), ("out", C.c_void_p), ("out_limbs", C.c_void_p),
+                ("mod_ids", C.c_void_p), ("n", C.c_uint32), ("n_terms", C.c_uint32), ("n_rot", C.c_uint32), ("galois", C.c_void_p)]
 
 
 class hm_ntt_ip_desc(C.Structure):
@@ -94,6 +100,7 @@ def load():
     L.hm_ntt_second_pass.argtypes = [vp, vp, vp, vp, u32, i32, vp]
     L.hm_ntt_ex.argtypes = [vp, C.POINTER(hm_ntt_desc)]
     L.hm_inner_product_ex.argtypes = [vp, C.POINTER(hm_ip_desc)]
+    L.hm_inner_product_hoisted.argtypes = [vp, C.POINTER(hm_ip_hoisted_desc)]
     L.hm_ntt_sub_scale.argtypes = [vp] + [vp] * 9 + [u32, vp]
     L.hm_ntt_mix_sub_scale.argtypes = [vp, C.POINTER(hm_ntt_fused_desc)]
     L.hm_tensor.argtypes = [vp] + [vp] * 15 + [u32]
@@ -284,6 +291,14 @@ class Context:
             return
         self._ck(self.L.hm_inner_product(self.h, x.ptr, keep[0][1], y.ptr, keep[1][1], out.ptr, keep[2][1], keep[3][1], len(mod_ids),
                                          n_terms, n_out))
+
+    def inner_product_hoisted(self, x, x_limbs, y, y_limbs, out, out_limbs, mod_ids, n_terms, galois):
+        """out[r][i][k] = sum_j automorph_{galois[r]}(x[i][j]) * y[r][i][k][j], k < 2: the key products of len(galois) rotations of one
+        ciphertext from its unrotated digits, the digits read once (hm_inner_product_hoisted).  Limb lists: x_limbs [n][n_terms],
+        y_limbs [r][n][2][n_terms], out_limbs [r][n][2]; x / y / out: anything with a device address `.ptr`"""
+        keep = [_u32(v) for v in (x_limbs, y_limbs, out_limbs, mod_ids, galois)]
+        d = hm_ip_hoisted_desc(x.ptr, keep[0][1], y.ptr, keep[1][1], out.ptr, keep[2][1], keep[3][1], len(mod_ids), n_terms, len(galois), keep[4][1])
+        self._ck(self.L.hm_inner_product_hoisted(self.h, C.byref(d)))
 
     def ntt_second_pass(self, buf, mod_ids, inverse=False, limbs=None, scale=None):
         """the last pass of transforms whose first pass another call has already run into `buf` (in place)"""

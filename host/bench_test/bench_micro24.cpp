@@ -76,6 +76,15 @@ int main(int argc, char *argv[]) {
     HROTATE *hrotate = new HROTATE("test_hrotate", maxlevel, currentlevel, alpha, config, arch);
     if (arch->world() > 1) rcclRendezvous(arch, idFile);
     hrotate->simulate();
+  } else if (ops == "hrotate_hoisted") {   // build extension: R rotations of one ciphertext, one ModUp (config keys rotations, galois)
+    HROTATE_HOISTED *hoisted = nullptr;
+    try {
+      hoisted = new HROTATE_HOISTED("test_hrotate_hoisted", maxlevel, currentlevel, alpha, config, arch);
+    } catch (const std::exception &e) {
+      std::cerr << e.what() << std::endl;
+      return 1;
+    }
+    hoisted->simulate();
   } else if (ops == "hadd") {
     HADD *hadd = new HADD("test_hadd", maxlevel, currentlevel, alpha, config, arch);
     if (arch->world() > 1) rcclRendezvous(arch, idFile);

@@ -66,6 +66,9 @@ public:
   // input limbs, ipConvMods[j] their moduli (empty: digit j is not converted inside the kernel)
   std::vector<std::vector<AddrType>> ipConvIn;
   std::vector<std::vector<uint32_t>> ipConvMods;
+  // (6h) hoisted key product (hm_inner_product_hoisted): ipX = the UNROTATED digits, rotation r reads them through X -> X^ipHoistG[r] with keys
+  // ipY[2r + k]; its outputs are out_{r,k} = (OutputOperand, extraOutputs...)[2r + k].  Empty: not hoisted
+  std::vector<uint32_t> ipHoistG;
   std::vector<Instruction *> depsInsList;
 
   Instruction(std::string name, ins_ops op, uint32_t level) : ops(op), Name(std::move(name)), level_id(level) {}

@@ -16,6 +16,12 @@
 typedef std::map<std::string, std::vector<INSGROUP>> StageMap;  // stage key -> [level] -> instruction group
 
 class KeySwitch {
+public:
+  // FULL: the whole key switch of the input (upstream's constructor).  The hoisted rotations (HROTATE_HOISTED) build its parts separately:
+  // MODUP = the ModUp of the input alone (digits NTTOut_beta(j)); ROTATED_KEY_PRODUCT = for one rotation, the automorphism of every extended
+  // digit of an earlier MODUP, the key product with this rotation's key and the ModDown, every buffer and stage key carrying the suffix `rot`.
+  enum Part { FULL, MODUP, ROTATED_KEY_PRODUCT };
+
 private:
   std::vector<AddrType> *DataPool;
   std::map<AddrType, std::vector<Instruction *>> *DataInsMap;
@@ -25,18 +31,30 @@ private:
   AddrManage *memMange;
   Arch *arch;
   std::string baseName;
+  Part part_ = FULL;
+  std::string rot;   // "" except for ROTATED_KEY_PRODUCT: "_Rot<r>"
   StageMap KeySwicthInsMap;
   std::vector<std::string> KeySwitchInsMapName;
 
   uint32_t digitSize(uint32_t beta) const { return std::min(Alpha, Level - beta * Alpha); }
   uint32_t extMod(uint32_t t) const { return t < Level ? t : MaxLevel + (t - Level); }
+  // the evaluation-form digits the key product reads, and the stage that produces them
+  std::string digitBuffer(uint32_t j) const { return rot.empty() ? "NTTOut_beta(" + std::to_string(j) + ")" : "AUTOOut" + rot + "_beta(" + std::to_string(j) + ")"; }
+  std::string digitStage(uint32_t j) const { return rot.empty() ? "ModUp_NTT_(" + std::to_string(j) + ")" : "AUTO" + rot + "_beta(" + std::to_string(j) + ")"; }
 
 public:
   KeySwitch(std::string labelName, uint32_t maxlevel, uint32_t level, uint32_t alpha,
             const std::vector<AddrType> &inputPolynomialAddress, std::vector<AddrType> *pool,
             std::map<AddrType, std::vector<Instruction *>> *map, InsGen *insgen, AddrManage *memoryMange);
+  // any part; ROTATED_KEY_PRODUCT: galois = the rotation's element, keySeed = the synthetic stream of its key
+  KeySwitch(std::string labelName, uint32_t maxlevel, uint32_t level, uint32_t alpha,
+            const std::vector<AddrType> &inputPolynomialAddress, std::vector<AddrType> *pool,
+            std::map<AddrType, std::vector<Instruction *>> *map, InsGen *insgen, AddrManage *memoryMange,
+            Part part, const std::string &rotSuffix = "", uint32_t galois = 0, uint64_t keySeed = 0);
   std::pair<StageMap, std::vector<std::string>> getInsMap() { return {KeySwicthInsMap, KeySwitchInsMapName}; }
 
+  void ModUp();
+  void RotateDigits(uint32_t galois);
   void ModUpINTT();
   void ModUpDecompFusionBConvStep1(uint32_t beta);
   void ModUpBConvStep2(uint32_t beta);
@@ -145,6 +163,13 @@ class HROTATE : public OperationBase {
 public:
   HROTATE(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
 };
+// hrotate_hoisted (build extension; the reference has no such op): R rotations of ONE ciphertext with ONE ModUp (config keys `rotations` = R,
+// default 4, 1..16, and `galois` = g, default 5; rotation r = 1..R by g^r mod 2N).  Outputs out<r>.c0 / out<r>.c1, keys IP_Rot<r>_Key<k>_<j>.
+class HROTATE_HOISTED : public OperationBase {
+  Ciphertext *ciph;
+public:
+  HROTATE_HOISTED(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
+};
 class HADD : public OperationBase {
   Ciphertext *c1, *c2;
 public:
@@ -171,7 +196,8 @@ class OpChain {
   std::vector<Arch *> archs;
   std::vector<OperationBase *> ops;
 public:
-  // ops: comma-separated list of hmult | hrotate | hadd | pmult | padd, e.g. "hmult,hrotate,hadd,hmult"
+  // ops: comma-separated list of hmult | hrotate | hadd | pmult | padd, e.g. "hmult,hrotate,hadd,hmult"; hrotate_hoisted (R output
+  // ciphertexts) only as the last op
   OpChain(const std::string &cfgPath, const std::string &opList, uint32_t maxLevel, uint32_t curLevel, uint32_t alpha,
           const std::map<std::string, uint32_t> &overrides = {});
   ~OpChain();

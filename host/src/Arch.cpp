@@ -21,7 +21,9 @@ static uint32_t cap(uint32_t logN, const char *name) {
 // one C-ABI call, with its argument arrays prebuilt so that run() is a tight loop of calls
 struct Arch::Launch {
   enum Kind { L_NTT, L_INTT, L_EWE, L_BCONV, L_AUTO, L_NTT_SUBSCALE, L_TENSOR, L_EXCH_IN, L_EXCH_OUT, L_REPLICATE, L_IP, L_NTT_IP,
-              L_BCONV_COL, L_EXCH_IN_COL, L_EXCH_OUT_COL } kind;   // round 4: conversion + first pass on a rank's column slice, between the transposed-domain exchanges
+              L_BCONV_COL, L_EXCH_IN_COL, L_EXCH_OUT_COL,   // round 4: conversion + first pass on a rank's column slice, between the transposed-domain exchanges
+              L_IP_HOISTED } kind;                           // (6h) the key products of several rotations from one set of digits
+  std::vector<uint32_t> hoistG;   // L_IP_HOISTED: the Galois element of every rotation (a: digits [n][T], b: keys [r][n][2][T], out: [r][n][2])
   Launch *xin = nullptr, *xout = nullptr;   // sharded BCONV: the exchange launches around it (they share its slice buffers)
   int recordSlot = -1;            // exchange launches of a pipelined sharded plan: the mark set behind them (hm_exchange_mark)
   std::vector<int> waitSlots;     // marks the compute stream waits for before this launch (hm_exchange_wait)
@@ -117,6 +119,9 @@ Arch::Arch(Config *cfg) : config(cfg) {
   if (const char *e = getenv("HOMULATOR_FUSE_AUTO")) fuseAuto = std::string(e) != "0";
   fuseModDown = cfg->getValueOr("fuse_moddown", 0) != 0;
   if (const char *e = getenv("HOMULATOR_FUSE_MODDOWN")) fuseModDown = std::string(e) != "0";
+  // (6h) hrotate_hoisted: the R key products over automorphisms of the same digits become one hm_inner_product_hoisted launch.  Config key
+  // fuse_hoist (default 1).
+  fuseHoist = cfg->getValueOr("fuse_hoist", 1) != 0;
   // sharded runs: the exchanges of digit j+1 run on the context's exchange stream while digit j converts and transforms (SURVEY.md 7:
   // 2 beta + 2 all-to-alls per key switch instead of 4, same order on every rank).  The per-digit transforms must then stay separate
   // launches, so the fused NTT x key kernel (which needs all digits) is not used.
@@ -504,6 +509,78 @@ void Arch::fusePasses(std::vector<Stage> &st) {
       byX.erase(partner);
     }
   }
+  // (6h) hoisted rotations (hrotate_hoisted): two-key inner-product records whose digits are all automorphisms (one element per record) of the SAME
+  //      materialised digits, read by nothing else, merge into ONE record per (modulus, digit list): hm_inner_product_hoisted reads the digits once
+  //      for every rotation and gathers the key / scatters the output at the automorphism's destination; the automorphisms are never written.
+  //      The first record in stage order carries the merged one: every reader of any rotation's output comes after it.
+  if (fuseHoist) {
+    std::map<AddrType, std::vector<Instruction *>> readers;
+    for (auto &s : st)
+      for (Instruction *i : s.ins) {
+        if (dead.count(i)) continue;
+        if (i->ops == IP && !i->ipX.empty()) {
+          for (AddrType x : i->ipX) readers[x].push_back(i);
+          for (auto &y : i->ipY) for (AddrType yy : y) readers[yy].push_back(i);
+        } else {
+          for (AddrType a : operands(i)) readers[a].push_back(i);
+          if (i->fusedSubScale) { readers[i->fMinuend].push_back(i); if (i->fAddend) readers[i->fAddend].push_back(i); if (i->fMix) readers[i->fMix].push_back(i); }
+        }
+      }
+    typedef std::pair<uint32_t, std::vector<AddrType>> DigitsKey;   // (modulus, unrotated digits)
+    std::map<DigitsKey, std::vector<std::pair<Instruction *, std::vector<Instruction *>>>> groups;   // -> (record, its automorphisms) in stage order
+    std::vector<DigitsKey> groupOrder;
+    for (auto &s : st)
+      for (Instruction *ip : s.ins) {
+        if (ip->ops != IP || ip->ipX.empty() || dead.count(ip) || ip->ipY.size() != 2 || ip->ipXGalois || !ip->ipHoistG.empty() ||
+            std::find(ip->ipCoeff.begin(), ip->ipCoeff.end(), 1) != ip->ipCoeff.end())
+          continue;
+        std::vector<AddrType> src;
+        std::vector<Instruction *> autos;
+        for (AddrType x : ip->ipX) {
+          auto p = producer.find(x);
+          if (p == producer.end()) break;
+          Instruction *A = p->second;
+          const auto &rd = readers[x];
+          if (A->ops != AUTO || dead.count(A) || A->galois <= 1 || A->mod_id != ip->mod_id || (!autos.empty() && A->galois != autos[0]->galois) ||
+              rd.size() != 1 || rd[0] != ip)
+            break;
+          src.push_back(A->operandList[0]);
+          autos.push_back(A);
+        }
+        if (autos.size() != ip->ipX.size()) continue;
+        const DigitsKey key(ip->mod_id, src);
+        if (!groups.count(key)) groupOrder.push_back(key);
+        groups[key].push_back({ip, autos});
+      }
+    for (const DigitsKey &key : groupOrder) {
+      const auto &mem = groups[key];
+      for (size_t b = 0; b < mem.size(); b += HM_IP_HOISTED_MAX_ROT) {
+        const size_t e = std::min(mem.size(), b + (size_t)HM_IP_HOISTED_MAX_ROT);
+        std::set<uint32_t> distinct;
+        for (size_t m = b; m < e; ++m) distinct.insert(mem[m].second[0]->galois);
+        if (distinct.size() != e - b) continue;   // two records by one element are not rotations of one ciphertext
+        Instruction *c = mem[b].first;
+        std::vector<AddrType> outs;
+        std::vector<std::vector<AddrType>> ys;
+        std::vector<uint32_t> gs;
+        for (size_t m = b; m < e; ++m) {
+          Instruction *i = mem[m].first;
+          outs.push_back(i->OutputOperand);
+          outs.insert(outs.end(), i->extraOutputs.begin(), i->extraOutputs.end());
+          ys.insert(ys.end(), i->ipY.begin(), i->ipY.end());
+          gs.push_back(mem[m].second[0]->galois);
+          if (i != c) { c->refInstructions += i->refInstructions; dead.insert(i); }
+          for (Instruction *A : mem[m].second) { c->refInstructions += A->refInstructions; dead.insert(A); }
+        }
+        c->ipX = key.second;
+        c->ipY = ys;
+        c->ipHoistG = gs;
+        c->OutputOperand = outs[0];
+        c->extraOutputs.assign(outs.begin() + 1, outs.end());
+        for (AddrType o : outs) producer[o] = c;
+      }
+    }
+  }
   // (7) HPIP as SURVEY.md 8f-2 specifies it: a forward transform whose only reader is an inner-product record moves INTO that
   //     record (ModUp_NTT_(j) + InnerProOut: src/Operation.cpp:190-414).  The kernel runs the digit's ROW pass and multiplies
   //     its registers into both keys' accumulators; the extended digit (NTTOut_beta(j)) is never written or read back — its
@@ -523,7 +600,7 @@ void Arch::fusePasses(std::vector<Stage> &st) {
       }
     for (auto &s : st)
       for (Instruction *ip : s.ins) {
-        if (ip->ops != IP || ip->ipX.empty() || dead.count(ip)) continue;
+        if (ip->ops != IP || ip->ipX.empty() || dead.count(ip) || !ip->ipHoistG.empty()) continue;   // (6h): its digits stay materialised
         ip->ipSrc = ip->ipX;
         ip->ipCoeff.assign(ip->ipX.size(), 0);
         std::vector<Instruction *> conv(ip->ipX.size(), nullptr);
@@ -747,7 +824,7 @@ void Arch::fusePasses(std::vector<Stage> &st) {
         if (dead.count(i)) continue;
         if (i->ops == IP && !i->ipX.empty()) {
           // a transform x key record reads its own digits in evaluation form, a plain inner-product record (no digit transformed inside) all of them
-          const bool anyT = std::find(i->ipCoeff.begin(), i->ipCoeff.end(), 1) != i->ipCoeff.end(), can = !i->ipXGalois;   // (any plan: a limb-poly's key product runs on the rank that owns the limb, and so does the automorphism's source limb)
+          const bool anyT = std::find(i->ipCoeff.begin(), i->ipCoeff.end(), 1) != i->ipCoeff.end(), can = !i->ipXGalois && i->ipHoistG.empty();   // (any plan: a limb-poly's key product runs on the rank that owns the limb, and so does the automorphism's source limb)
           const auto &src = i->ipSrc.empty() ? i->ipX : i->ipSrc;
           for (size_t j = 0; j < src.size(); ++j) {
             const bool own = can && (!anyT || (!i->ipCoeff[j] && !(j < i->ipConvIn.size() && !i->ipConvIn[j].empty())));
@@ -857,7 +934,7 @@ void Arch::buildLaunches() {
     size_t first = parts.size();
     for (Instruction *i : s.ins) {
       const bool nip = i->ops == IP && std::find(i->ipCoeff.begin(), i->ipCoeff.end(), 1) != i->ipCoeff.end();
-      int key = nip ? 400 + (int)i->ipX.size() * 10 + (int)i->ipY.size() : i->ops == IP && !i->ipX.empty() ? 300 + (int)i->ipX.size() * 10 + (int)i->ipY.size() : i->fusedTensor ? 200 : i->fusedSubScale ? (i->fMix ? 203 : 201) + (i->fConvIn.empty() ? 0 : 4) : i->ops == MULT ? 100 + i->opcode : (i->ops == NTT && i->passthrough) ? 100 + EWE_COPY : i->ops == AUTO ? 1000 + (int)i->galois : (int)i->ops + (i->secondOnly ? 5000 : 0);
+      int key = !i->ipHoistG.empty() ? 6000 + (int)i->ipX.size() * 100 + (int)i->ipHoistG.size() : nip ? 400 +(int)i->ipX.size() * 10 + (int)i->ipY.size() : i->ops == IP && !i->ipX.empty() ? 300 + (int)i->ipX.size() * 10 + (int)i->ipY.size() : i->fusedTensor ? 200 : i->fusedSubScale ? (i->fMix ? 203 : 201) + (i->fConvIn.empty() ? 0 : 4) : i->ops == MULT ? 100 + i->opcode : (i->ops == NTT && i->passthrough) ? 100 + EWE_COPY : i->ops == AUTO ? 1000 + (int)i->galois : (int)i->ops + (i->secondOnly ? 5000 : 0);
       size_t p = first;
       for (; p < parts.size(); ++p)
         if (parts[p].key == key) break;
@@ -1108,7 +1185,27 @@ void Arch::buildLaunches() {
       size_t count = 0;
       for (const Part *g : group)
         for (Instruction *i : g->ins) { L->refInstructions += i->refInstructions * (i->ops == BCONV_STEP2 ? bconvPorts : 1ull) + i->refExtra; ++count; }
-      if (f->ops == IP && std::find(f->ipCoeff.begin(), f->ipCoeff.end(), 1) != f->ipCoeff.end()) {
+      if (f->ops == IP && !f->ipHoistG.empty()) {
+        // (6h) one hoisted key product: digits a [n][T], keys b [r][n][2][T], outputs out [r][n][2] (hm_ip_hoisted_desc)
+        L->kind = Launch::L_IP_HOISTED; L->statKey = "EWE";
+        L->ipTerms = (uint32_t)f->ipX.size(); L->ipOuts = 2; L->hoistG = f->ipHoistG;
+        const size_t R = f->ipHoistG.size();
+        std::vector<Instruction *> recs;
+        for (const Part *g : group) recs.insert(recs.end(), g->ins.begin(), g->ins.end());
+        for (Instruction *i : recs) {
+          if (i->ipHoistG != f->ipHoistG) { delete L; throw std::runtime_error("hoisted key product: the records of one launch rotate by different elements"); }
+          for (AddrType x : i->ipX) L->a.push_back(limbOf(x));
+          L->mods.push_back(i->mod_id);
+        }
+        for (size_t r = 0; r < R; ++r)
+          for (Instruction *i : recs)
+            for (size_t k = 0; k < 2; ++k) {
+              for (AddrType y : i->ipY[r * 2 + k]) L->b.push_back(limbOf(y));
+              L->out.push_back(limbOf(r == 0 && k == 0 ? i->OutputOperand : i->extraOutputs[r * 2 + k - 1]));
+            }
+        // digits read once, keys read and outputs written once per rotation
+        L->bytes = (unsigned long long)recs.size() * (L->ipTerms + 2 * R * L->ipTerms + 2 * R) * LP;
+      } else if (f->ops == IP && std::find(f->ipCoeff.begin(), f->ipCoeff.end(), 1) != f->ipCoeff.end()) {
         L->kind = Launch::L_NTT_IP; L->statKey = "NTT";
         L->ipTerms = (uint32_t)f->ipX.size(); L->ipOuts = (uint32_t)f->ipY.size();
         unsigned long long lp = 0;
@@ -1348,6 +1445,26 @@ void Arch::replicateForBatch() {
       l->bytes *= batch_;
       continue;
     }
+    if (l->kind == Launch::L_IP_HOISTED) {
+      // entry-major as the inner product below (the ops of a batch share the keys), inside every rotation's block of keys and outputs
+      const size_t n0 = l->mods.size();
+      auto inter = [&](std::vector<uint32_t> &v, size_t blocks, size_t width, bool isLimb) {
+        std::vector<uint32_t> o;
+        for (size_t r = 0; r < blocks; ++r)
+          for (size_t e = 0; e < n0; ++e)
+            for (uint32_t c = 0; c < batch_; ++c)
+              for (size_t w = 0; w < width; ++w) {
+                const uint32_t x = v[(r * n0 + e) * width + w];
+                o.push_back(isLimb && c && !sharedLimbs.count(x) ? x + c * per : x);
+              }
+        v.swap(o);
+      };
+      const size_t R = l->hoistG.size();
+      inter(l->a, 1, l->ipTerms, true); inter(l->b, R, 2 * (size_t)l->ipTerms, true); inter(l->out, R, 2, true); inter(l->mods, 1, 1, false);
+      l->refInstructions *= batch_;
+      l->bytes *= batch_;
+      continue;
+    }
     if (l->kind == Launch::L_IP || l->kind == Launch::L_NTT_IP) {
       // entry e: ipTerms x limbs, ipTerms * ipOuts y limbs, ipOuts outputs.  Entry-major order (entry e of every op
       // side by side): the ops share the key limbs, so the second and later readers of a key chunk find it in L2
@@ -1476,7 +1593,7 @@ void Arch::prepare() {
 }
 
 static const char *const kLaunchKindNames[] = {"NTT", "INTT", "EWE", "BCONV", "AUTO", "NTT_SUBSCALE", "TENSOR", "EXCH_IN", "EXCH_OUT", "REPLICATE", "IP", "NTT_IP",
-                                               "BCONV_COL", "EXCH_IN_COL", "EXCH_OUT_COL"};
+                                               "BCONV_COL", "EXCH_IN_COL", "EXCH_OUT_COL", "IP_HOISTED"};
 
 // Per-launch device time (SURVEY.md §8d "per-stage hipEvent times", exchange time at N > 1): every launch of the plan
 // bracketed by its own event pair, in plan order so that the data dependencies (and, sharded, the collectives) line up.
@@ -1505,7 +1622,7 @@ std::string Arch::planText() const {
   for (const Launch *l : launches) {
     size_t cnt = l->out.size();
     if (l->kind == Launch::L_BCONV || l->kind == Launch::L_BCONV_COL) { cnt = 0; for (auto &q : l->probs) cnt += q.out.size(); }
-    if (l->kind == Launch::L_IP || l->kind == Launch::L_NTT_IP) cnt = l->mods.size();
+    if (l->kind == Launch::L_IP || l->kind == Launch::L_NTT_IP || l->kind == Launch::L_IP_HOISTED) cnt = l->mods.size();
     out += std::string(names[l->kind]) + " " + l->name + " n=" + std::to_string(cnt) + " ref=" + std::to_string(l->refInstructions);
     // pass 11: limb-polys an inverse transform stores split-30 packed / conversions (separate or inside a transform's first pass) that read packed inputs
     const size_t po = (size_t)std::count(l->outPacked.begin(), l->outPacked.end(), 1), pi = (size_t)std::count_if(l->probs.begin(), l->probs.end(), [](const Launch::Prob &q) { return q.inPacked; });
@@ -1519,6 +1636,10 @@ std::string Arch::planText() const {
       if (cnt) out += std::string(gv == &l->inGalois ? " auto_in=" : " auto_addend=") + std::to_string(cnt) + "/g" + std::to_string(g);
     }
     if (l->xGalois) out += " auto_x=g" + std::to_string(l->xGalois);
+    if (!l->hoistG.empty()) {   // (6h): rotations of the hoisted key product and their elements
+      out += " rot=" + std::to_string(l->hoistG.size()) + " g=";
+      for (size_t r = 0; r < l->hoistG.size(); ++r) out += (r ? "," : "") + std::to_string(l->hoistG[r]);
+    }
     if (l->recordSlot >= 0) out += " mark=" + std::to_string(l->recordSlot);
     if (!l->waitSlots.empty()) { out += " wait="; for (int w : l->waitSlots) out += std::to_string(w) + ","; }
     if (!l->exLimbs.empty()) {
@@ -1568,6 +1689,12 @@ void Arch::enqueue(Launch &l) {
     } else
     st = hm_inner_product(ctx, pool, l.a.data(), pool, l.b.data(), pool, l.out.data(), l.mods.data(), (uint32_t)l.mods.size(), l.ipTerms, l.ipOuts);
     break;
+  case Launch::L_IP_HOISTED: {
+    const hm_ip_hoisted_desc d = {pool, l.a.data(), pool, l.b.data(), pool, l.out.data(), l.mods.data(), (uint32_t)l.mods.size(), l.ipTerms,
+                                  (uint32_t)l.hoistG.size(), l.hoistG.data()};
+    st = hm_inner_product_hoisted(ctx, &d);
+    break;
+  }
   case Launch::L_NTT_IP: {
     for (auto &q : l.probs)
       descs.push_back(hm_bconv_desc{pool, q.in.data(), q.inMods.data(), (uint32_t)q.in.size(), pool, q.out.data(), q.outMods.data(), (uint32_t)q.out.size(), 0,

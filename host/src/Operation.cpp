@@ -4,6 +4,7 @@
 #include "Operation.h"
 #include "SimProgram.h"
 
+#include <algorithm>
 #include <chrono>
 #include <sstream>
 
@@ -14,9 +15,15 @@ static std::string S(uint32_t v) { return std::to_string(v); }
 // =====================================================================================================
 KeySwitch::KeySwitch(std::string labelName, uint32_t maxlevel, uint32_t level, uint32_t alpha,
                      const std::vector<AddrType> &inputPolynomialAddress, std::vector<AddrType> *pool,
-                     std::map<AddrType, std::vector<Instruction *>> *map, InsGen *insgen, AddrManage *memoryMange) {
+                     std::map<AddrType, std::vector<Instruction *>> *map, InsGen *insgen, AddrManage *memoryMange)
+    : KeySwitch(labelName, maxlevel, level, alpha, inputPolynomialAddress, pool, map, insgen, memoryMange, FULL) {}
+
+KeySwitch::KeySwitch(std::string labelName, uint32_t maxlevel, uint32_t level, uint32_t alpha,
+                     const std::vector<AddrType> &inputPolynomialAddress, std::vector<AddrType> *pool,
+                     std::map<AddrType, std::vector<Instruction *>> *map, InsGen *insgen, AddrManage *memoryMange,
+                     Part part, const std::string &rotSuffix, uint32_t galois, uint64_t keySeed) {
   Arch *arch_ = insgen->backend();             // same signature as upstream (include/Operation.h:48-54): the backend
-  const uint64_t evkSeed = insgen->keySeed();  // and the key seed travel with the generator
+  const uint64_t evkSeed = part == ROTATED_KEY_PRODUCT ? keySeed : insgen->keySeed();  // and the key seed travel with the generator
   DataInsMap = map;
   DataPool = pool;
   MaxLevel = maxlevel;
@@ -28,16 +35,13 @@ KeySwitch::KeySwitch(std::string labelName, uint32_t maxlevel, uint32_t level, u
   memMange = memoryMange;
   arch = arch_;
   preAddr = inputPolynomialAddress;
-  baseName = labelName + "_KeySwitch";
+  part_ = part;
+  rot = part == ROTATED_KEY_PRODUCT ? rotSuffix : "";
+  baseName = labelName + "_KeySwitch" + rot;
 
-  ModUpINTT();
-  memMange->MallocMem("ModUpDecompOffset", 1);
-  memMange->MallocMem("ModUpDecompOut", Level);
-  for (uint32_t be = 0; be < Beta; be++) {
-    ModUpDecompFusionBConvStep1(be);
-    ModUpBConvStep2(be);
-    ModUpNTT(be);
-  }
+  if (part == ROTATED_KEY_PRODUCT) RotateDigits(galois);
+  else ModUp();
+  if (part == MODUP) return;
   InnerProduceOperation(evkSeed);
   ModDownINTT();
   ModDownBConvStep1();
@@ -46,14 +50,45 @@ KeySwitch::KeySwitch(std::string labelName, uint32_t maxlevel, uint32_t level, u
   ModDownSub();
 }
 
-// reference: KeySwitch::ModUpINTT :63-102 — one INTT per input limb; throws when the input has no producer
+// reference: KeySwitch::KeySwitch :33-40 — the ModUp: INTT of the input, then per digit scale, conversion and forward transforms
+void KeySwitch::ModUp() {
+  ModUpINTT();
+  memMange->MallocMem("ModUpDecompOffset", 1);
+  memMange->MallocMem("ModUpDecompOut", Level);
+  for (uint32_t be = 0; be < Beta; be++) {
+    ModUpDecompFusionBConvStep1(be);
+    ModUpBConvStep2(be);
+    ModUpNTT(be);
+  }
+}
+
+// hoisted rotations: sigma_g of every extended digit NTTOut_beta(j) of the shared ModUp, one AUTO per limb (InsGen::GenAUTO,
+// src/InsGen.cpp:46-71) into AUTOOut<rot>_beta(j): what the key product of this rotation reads instead of the digits themselves
+void KeySwitch::RotateDigits(uint32_t galois) {
+  const uint32_t E = Level + Alpha;
+  for (uint32_t be = 0; be < Beta; be++) {
+    memMange->MallocMem(digitBuffer(be), E);
+    const std::vector<AddrType> src = memMange->getAddr("NTTOut_beta(" + S(be) + ")"), dst = memMange->getAddr(digitBuffer(be));
+    std::vector<INSGROUP> out;
+    for (uint32_t t = 0; t < E; t++) {
+      auto prod = DataInsMap->find(src[t]);
+      out.push_back(insGenPointer->GenAUTO(t, baseName + "_AUTO_beta(" + S(be) + ")_Level(" + S(t) + ")_", prod == DataInsMap->end() ? nullptr : &prod->second,
+                                           src[t], dst[t], galois, extMod(t)));
+    }
+    KeySwicthInsMap[digitStage(be)] = out;
+    KeySwitchInsMapName.push_back(digitStage(be));
+  }
+}
+
+// reference: KeySwitch::ModUpINTT :63-102 — one INTT per input limb; throws when the input has no producer (the MODUP part of the hoisted
+// rotations reads the op's own input ciphertext)
 void KeySwitch::ModUpINTT() {
   memMange->MallocMem("ModUpINTTOut", Level);
   std::vector<INSGROUP> out;
   for (uint32_t l = 0; l < Level; l++) {
     auto prod = DataInsMap->find(preAddr[l]);
-    if (prod == DataInsMap->end()) throw std::runtime_error("Error! This dependece need exists!\n\n");
-    out.push_back(insGenPointer->GenNTT(l, baseName + "_ModUp_INTT(" + S(l) + ")_", &prod->second, false, preAddr[l],
+    if (prod == DataInsMap->end() && part_ == FULL) throw std::runtime_error("Error! This dependece need exists!\n\n");
+    out.push_back(insGenPointer->GenNTT(l, baseName + "_ModUp_INTT(" + S(l) + ")_", prod == DataInsMap->end() ? nullptr : &prod->second, false, preAddr[l],
                                         memMange->getAddr("ModUpINTTOut")[l], l));
   }
   KeySwicthInsMap["ModUp_INTT"] = out;
@@ -141,43 +176,44 @@ void KeySwitch::InnerProduceOperation(uint64_t evkSeed) {
   for (uint32_t t = 0; t < E; t++) extMods.push_back(extMod(t));
   for (uint32_t k = 0; k < 2; k++) {
     const std::string K = S(k);
-    memMange->MallocMem("InnerProduceOut_Key" + K, E);
+    memMange->MallocMem("InnerProduceOut" + rot + "_Key" + K, E);
     for (uint32_t be = 0; be < Beta; be++) {
-      memMange->MallocMem("IP_Key" + K + "_" + S(be), E);
+      memMange->MallocMem("IP" + rot + "_Key" + K + "_" + S(be), E);
       // evaluation key limbs are inputs: deterministic synthetic stream (same layout as the oracle's synth_evk)
-      arch->addInputFill(InputFill{memMange->getAddr("IP_Key" + K + "_" + S(be)), extMods, evkSeed + (be * 2 + k) * 1000ull, /*shared=*/true});
-      if (Beta != 1 && be <= Beta - 2) memMange->MallocMem("InnerProduceOut_temp(" + S(be) + ")_Key" + K, E);
+      arch->addInputFill(InputFill{memMange->getAddr("IP" + rot + "_Key" + K + "_" + S(be)), extMods, evkSeed + (be * 2 + k) * 1000ull, /*shared=*/true});
+      if (Beta != 1 && be <= Beta - 2) memMange->MallocMem("InnerProduceOut" + rot + "_temp(" + S(be) + ")_Key" + K, E);
     }
-    auto ext = [&](uint32_t j) { return memMange->getAddr("NTTOut_beta(" + S(j) + ")"); };
-    auto key = [&](uint32_t j) { return memMange->getAddr("IP_Key" + K + "_" + S(j)); };
+    auto ext = [&](uint32_t j) { return memMange->getAddr(digitBuffer(j)); };
+    auto key = [&](uint32_t j) { return memMange->getAddr("IP" + rot + "_Key" + K + "_" + S(j)); };
+    const std::string ipOut = "InnerProOut" + rot + "_(";
     if (Beta == 1) {
       std::vector<INSGROUP> g;
       for (uint32_t ml = 0; ml < E; ml++)
         g.push_back(insGenPointer->GenEWE(ml, baseName + "_InnerProducOperation(0)_Level(" + S(ml) + ")_Key(" + K + ")",
-                                          &KeySwicthInsMap["ModUp_NTT_(0)"][ml], nullptr, nullptr, nullptr, ext(0)[ml], key(0)[ml],
-                                          0, 0, memMange->getAddr("InnerProduceOut_Key" + K)[ml], EWE_MUL, extMods[ml]));
-      KeySwicthInsMap["InnerProOut_(0)_Key" + K] = g;
-      KeySwitchInsMapName.push_back("InnerProOut_(0)_Key" + K);
+                                          &KeySwicthInsMap[digitStage(0)][ml], nullptr, nullptr, nullptr, ext(0)[ml], key(0)[ml],
+                                          0, 0, memMange->getAddr("InnerProduceOut" + rot + "_Key" + K)[ml], EWE_MUL, extMods[ml]));
+      KeySwicthInsMap[ipOut + "0)_Key" + K] = g;
+      KeySwitchInsMapName.push_back(ipOut + "0)_Key" + K);
     } else {
       for (uint32_t be = 0; be < Beta - 1; be++) {
         std::vector<INSGROUP> g;
-        const std::string outKey = (be < Beta - 2) ? "InnerProduceOut_temp(" + S(be) + ")_Key" + K : "InnerProduceOut_Key" + K;
+        const std::string outKey = (be < Beta - 2) ? "InnerProduceOut" + rot + "_temp(" + S(be) + ")_Key" + K : "InnerProduceOut" + rot + "_Key" + K;
         for (uint32_t ml = 0; ml < E; ml++) {
           const std::string name = baseName + "_InnerProducOperation(" + S(be) + ")_Level(" + S(ml) + ")_Key(" + K + ")";
           const AddrType outaddr = memMange->getAddr(outKey)[ml];
           if (be == 0)
-            g.push_back(insGenPointer->GenEWE(ml, name, &KeySwicthInsMap["ModUp_NTT_(0)"][ml], nullptr,
-                                              &KeySwicthInsMap["ModUp_NTT_(1)"][ml], nullptr, ext(0)[ml], key(0)[ml], ext(1)[ml],
+            g.push_back(insGenPointer->GenEWE(ml, name, &KeySwicthInsMap[digitStage(0)][ml], nullptr,
+                                              &KeySwicthInsMap[digitStage(1)][ml], nullptr, ext(0)[ml], key(0)[ml], ext(1)[ml],
                                               key(1)[ml], outaddr, EWE_MAC2, extMods[ml]));
           else
-            g.push_back(insGenPointer->GenEWE(ml, name, &KeySwicthInsMap["ModUp_NTT_(" + S(be + 1) + ")"][ml], nullptr,
-                                              &KeySwicthInsMap["InnerProOut_(" + S(be - 1) + ")_Key" + K][ml], nullptr,
+            g.push_back(insGenPointer->GenEWE(ml, name, &KeySwicthInsMap[digitStage(be + 1)][ml], nullptr,
+                                              &KeySwicthInsMap[ipOut + S(be - 1) + ")_Key" + K][ml], nullptr,
                                               ext(be + 1)[ml], key(be + 1)[ml],
-                                              memMange->getAddr("InnerProduceOut_temp(" + S(be - 1) + ")_Key" + K)[ml], 0, outaddr,
+                                              memMange->getAddr("InnerProduceOut" + rot + "_temp(" + S(be - 1) + ")_Key" + K)[ml], 0, outaddr,
                                               EWE_MAC_ADD, extMods[ml]));
         }
-        KeySwicthInsMap["InnerProOut_(" + S(be) + ")_Key" + K] = g;
-        KeySwitchInsMapName.push_back("InnerProOut_(" + S(be) + ")_Key" + K);
+        KeySwicthInsMap[ipOut + S(be) + ")_Key" + K] = g;
+        KeySwitchInsMapName.push_back(ipOut + S(be) + ")_Key" + K);
       }
     }
   }
@@ -186,80 +222,80 @@ void KeySwitch::InnerProduceOperation(uint64_t evkSeed) {
 // reference: ModDownINTT :417-445 — INTT of the alpha special-prime limbs of each inner-product output
 // (extended limb order = Q limbs then P limbs: Appendix A (3))
 void KeySwitch::ModDownINTT() {
-  const std::string last = "InnerProOut_(" + S(Beta == 1 ? 0 : Beta - 2) + ")_Key";
+  const std::string last = "InnerProOut" + rot + "_(" + S(Beta == 1 ? 0 : Beta - 2) + ")_Key";
   for (uint32_t k = 0; k < 2; k++) {
-    memMange->MallocMem("INTTOut_ModDown_Key(" + S(k) + ")", Alpha);
+    memMange->MallocMem("INTTOut_ModDown" + rot + "_Key(" + S(k) + ")", Alpha);
     std::vector<INSGROUP> g;
     for (uint32_t l = 0; l < Alpha; l++)
       g.push_back(insGenPointer->GenNTT(l, baseName + "_ModDown_INTT(" + S(l) + ")_Key(" + S(k) + ")",
                                         &KeySwicthInsMap[last + S(k)][Level + l], false,
-                                        memMange->getAddr("InnerProduceOut_Key" + S(k))[Level + l],
-                                        memMange->getAddr("INTTOut_ModDown_Key(" + S(k) + ")")[l], MaxLevel + l));
-    KeySwicthInsMap["ModDownINTTOut_Key(" + S(k) + ")"] = g;
-    KeySwitchInsMapName.push_back("ModDownINTTOut_Key(" + S(k) + ")");
+                                        memMange->getAddr("InnerProduceOut" + rot + "_Key" + S(k))[Level + l],
+                                        memMange->getAddr("INTTOut_ModDown" + rot + "_Key(" + S(k) + ")")[l], MaxLevel + l));
+    KeySwicthInsMap["ModDownINTTOut" + rot + "_Key(" + S(k) + ")"] = g;
+    KeySwitchInsMapName.push_back("ModDownINTTOut" + rot + "_Key(" + S(k) + ")");
   }
 }
 
 // reference: ModDownBConvStep1 :447-487 — y_p = a_p * [(P/p)^-1]_p
 void KeySwitch::ModDownBConvStep1() {
-  memMange->MallocMem("ModDownBConvStep1_Ref", 2);
+  memMange->MallocMem("ModDownBConvStep1" + rot + "_Ref", 2);
   std::vector<uint32_t> pMods;
   for (uint32_t l = 0; l < Alpha; l++) pMods.push_back(MaxLevel + l);
   const std::vector<uint64_t> phatInv = arch->bconvScale(pMods);
   for (uint32_t k = 0; k < 2; k++) {
-    memMange->MallocMem("ModDownBConvStep1_Key(" + S(k) + ")", Alpha);
+    memMange->MallocMem("ModDownBConvStep1" + rot + "_Key(" + S(k) + ")", Alpha);
     std::vector<INSGROUP> g;
     for (uint32_t l = 0; l < Alpha; l++)
       g.push_back(insGenPointer->GenEWE(l, baseName + "_ModDownBConvStep1_Level(" + S(l) + ")_Key(" + S(k) + ")",
-                                        &KeySwicthInsMap["ModDownINTTOut_Key(" + S(k) + ")"][l], nullptr, nullptr, nullptr,
-                                        memMange->getAddr("INTTOut_ModDown_Key(" + S(k) + ")")[l],
-                                        memMange->getAddr("ModDownBConvStep1_Ref")[k], 0, 0,
-                                        memMange->getAddr("ModDownBConvStep1_Key(" + S(k) + ")")[l], EWE_MUL_CONST, MaxLevel + l,
+                                        &KeySwicthInsMap["ModDownINTTOut" + rot + "_Key(" + S(k) + ")"][l], nullptr, nullptr, nullptr,
+                                        memMange->getAddr("INTTOut_ModDown" + rot + "_Key(" + S(k) + ")")[l],
+                                        memMange->getAddr("ModDownBConvStep1" + rot + "_Ref")[k], 0, 0,
+                                        memMange->getAddr("ModDownBConvStep1" + rot + "_Key(" + S(k) + ")")[l], EWE_MUL_CONST, MaxLevel + l,
                                         true, phatInv[l]));
-    KeySwicthInsMap["ModDownBConvStep1_Key(" + S(k) + ")"] = g;
-    KeySwitchInsMapName.push_back("ModDownBConvStep1_Key(" + S(k) + ")");
+    KeySwicthInsMap["ModDownBConvStep1" + rot + "_Key(" + S(k) + ")"] = g;
+    KeySwitchInsMapName.push_back("ModDownBConvStep1" + rot + "_Key(" + S(k) + ")");
   }
 }
 
 // reference: ModDownBConvStep2 :489-519 — P -> Q conversion, alpha inputs per output limb
 void KeySwitch::ModDownBConvStep2() {
-  memMange->MallocMemOneBatch("ModdownBConvMap", 1);
+  memMange->MallocMemOneBatch("ModdownBConvMap" + rot, 1);
   std::vector<uint32_t> pMods;
   for (uint32_t l = 0; l < Alpha; l++) pMods.push_back(MaxLevel + l);
   for (uint32_t k = 0; k < 2; k++) {
-    memMange->MallocMem("ModdownBConvOut_Key" + S(k), Level);
+    memMange->MallocMem("ModdownBConvOut" + rot + "_Key" + S(k), Level);
     std::vector<INSGROUP> g;
     for (uint32_t ol = 0; ol < Level; ol++)
       g.push_back(insGenPointer->GenBCONV(ol, Alpha, baseName + "_ModDownBConv_outLevel(" + S(ol) + ")_Key(" + S(k) + ")",
-                                          KeySwicthInsMap["ModDownBConvStep1_Key(" + S(k) + ")"],
-                                          memMange->getAddr("ModDownBConvStep1_Key(" + S(k) + ")"), pMods,
-                                          memMange->getAddr("ModdownBConvMap")[0],
-                                          memMange->getAddr("ModdownBConvOut_Key" + S(k))[ol], ol));
-    KeySwicthInsMap["ModDown_BCONV_Key(" + S(k) + ")"] = g;
-    KeySwitchInsMapName.push_back("ModDown_BCONV_Key(" + S(k) + ")");
+                                          KeySwicthInsMap["ModDownBConvStep1" + rot + "_Key(" + S(k) + ")"],
+                                          memMange->getAddr("ModDownBConvStep1" + rot + "_Key(" + S(k) + ")"), pMods,
+                                          memMange->getAddr("ModdownBConvMap" + rot)[0],
+                                          memMange->getAddr("ModdownBConvOut" + rot + "_Key" + S(k))[ol], ol));
+    KeySwicthInsMap["ModDown_BCONV" + rot + "_Key(" + S(k) + ")"] = g;
+    KeySwitchInsMapName.push_back("ModDown_BCONV" + rot + "_Key(" + S(k) + ")");
   }
 }
 
 // reference: ModDowNTT :521-546 (passes ntt=false there: a labelling slip, Appendix C item 5)
 void KeySwitch::ModDowNTT() {
   for (uint32_t k = 0; k < 2; k++) {
-    memMange->MallocMem("NTTOut_ModDown_Key(" + S(k) + ")", Level);
+    memMange->MallocMem("NTTOut_ModDown" + rot + "_Key(" + S(k) + ")", Level);
     std::vector<INSGROUP> g;
     for (uint32_t l = 0; l < Level; l++)
       g.push_back(insGenPointer->GenNTT(l, baseName + "_ModDown_NTT(" + S(l) + ")_Key(" + S(k) + ")",
-                                        &KeySwicthInsMap["ModDown_BCONV_Key(" + S(k) + ")"][l], true,
-                                        memMange->getAddr("ModdownBConvOut_Key" + S(k))[l],
-                                        memMange->getAddr("NTTOut_ModDown_Key(" + S(k) + ")")[l], l));
-    KeySwicthInsMap["ModDownNTTOut_Key(" + S(k) + ")"] = g;
-    KeySwitchInsMapName.push_back("ModDownNTTOut_Key(" + S(k) + ")");
+                                        &KeySwicthInsMap["ModDown_BCONV" + rot + "_Key(" + S(k) + ")"][l], true,
+                                        memMange->getAddr("ModdownBConvOut" + rot + "_Key" + S(k))[l],
+                                        memMange->getAddr("NTTOut_ModDown" + rot + "_Key(" + S(k) + ")")[l], l));
+    KeySwicthInsMap["ModDownNTTOut" + rot + "_Key(" + S(k) + ")"] = g;
+    KeySwitchInsMapName.push_back("ModDownNTTOut" + rot + "_Key(" + S(k) + ")");
   }
 }
 
 // reference: ModDownSub :548-590 — ks_k,i = (acc_k,i - w_k,i) * [P^-1]_{q_i}
 void KeySwitch::ModDownSub() {
-  const std::string last = "InnerProOut_(" + S(Beta == 1 ? 0 : Beta - 2) + ")_Key";
+  const std::string last = "InnerProOut" + rot + "_(" + S(Beta == 1 ? 0 : Beta - 2) + ")_Key";
   for (uint32_t k = 0; k < 2; k++) {
-    memMange->MallocMem("KeySwitchFinalOutput_Key(" + S(k) + ")", Level);
+    memMange->MallocMem("KeySwitchFinalOutput" + rot + "_Key(" + S(k) + ")", Level);
     std::vector<INSGROUP> g;
     for (uint32_t l = 0; l < Level; l++) {
       const uint64_t q = arch->modulus(l);
@@ -272,14 +308,14 @@ void KeySwitch::ModDownSub() {
         base = (uint64_t)(((unsigned __int128)base * base) % q);
       }
       g.push_back(insGenPointer->GenEWE(l, baseName + "_ModDownSub_Level(" + S(l) + ")_Key(" + S(k) + ")",
-                                        &KeySwicthInsMap["ModDownNTTOut_Key(" + S(k) + ")"][l], nullptr,
+                                        &KeySwicthInsMap["ModDownNTTOut" + rot + "_Key(" + S(k) + ")"][l], nullptr,
                                         &KeySwicthInsMap[last + S(k)][l], nullptr,
-                                        memMange->getAddr("InnerProduceOut_Key" + S(k))[l], 0,
-                                        memMange->getAddr("NTTOut_ModDown_Key(" + S(k) + ")")[l], 0,
-                                        memMange->getAddr("KeySwitchFinalOutput_Key(" + S(k) + ")")[l], EWE_SUB_SCALE, l, true, r));
+                                        memMange->getAddr("InnerProduceOut" + rot + "_Key" + S(k))[l], 0,
+                                        memMange->getAddr("NTTOut_ModDown" + rot + "_Key(" + S(k) + ")")[l], 0,
+                                        memMange->getAddr("KeySwitchFinalOutput" + rot + "_Key(" + S(k) + ")")[l], EWE_SUB_SCALE, l, true, r));
     }
-    KeySwicthInsMap["KeySwitchFinalOutput_Key(" + S(k) + ")"] = g;
-    KeySwitchInsMapName.push_back("KeySwitchFinalOutput_Key(" + S(k) + ")");
+    KeySwicthInsMap["KeySwitchFinalOutput" + rot + "_Key(" + S(k) + ")"] = g;
+    KeySwitchInsMapName.push_back("KeySwitchFinalOutput" + rot + "_Key(" + S(k) + ")");
   }
 }
 
@@ -673,6 +709,60 @@ HROTATE::HROTATE(std::string labelName, uint32_t maxLevel, uint32_t currentLevel
   finishConstruction();
 }
 
+// hrotate_hoisted (build extension: the reference has no such op).  R rotations of one ciphertext by g_r = g^r mod 2N, r = 1..R, sharing ONE
+// ModUp of the UNROTATED c1 (KeySwitch MODUP): D_j = ModUp(c1).  Per rotation (KeySwitch ROTATED_KEY_PRODUCT, stage keys and buffers suffixed
+// _Rot<r>): AUTO of every extended digit, the key product with the rotation's own key, the ModDown, then out<r> = (sigma_r(c0) + ks0_r, ks1_r).
+// Not bit-identical to R hrotates: ModUp(sigma(c1)) and sigma(ModUp(c1)) differ by multiples of Q in the converted limbs; both key switches are
+// valid.  Unfused, the stages run one launch each; fused, pass (6h) of Arch::fusePasses turns the R key products into one hoisted launch.
+HROTATE_HOISTED::HROTATE_HOISTED(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch)
+    : OperationBase("HROTATE_HOISTED", cfg, _arch, maxLevel, currentLevel, alpha) {
+  label = labelName;
+  if (arch->backend() == Arch::BACKEND_SIM) throw std::runtime_error("hrotate_hoisted: backend = sim has no such op (the reference has no hoisted rotation)");
+  if (arch->world() > 1) throw std::runtime_error("hrotate_hoisted: world > 1 is not supported (sharded hoisting is not built)");
+  const uint32_t R = cfg->getValueOr("rotations", 4), galois = cfg->getValueOr("galois", 5), twoN = 2 * N;
+  if (R < 1 || R > 16) throw std::runtime_error("hrotate_hoisted: rotations = " + S(R) + ", must be in [1, 16]");
+  if (!(galois & 1) || galois >= twoN) throw std::runtime_error("hrotate_hoisted: galois = " + S(galois) + " must be odd and below 2N = " + S(twoN));
+  std::vector<uint32_t> gs;
+  uint64_t gr = 1;
+  for (uint32_t r = 1; r <= R; ++r) {
+    gr = gr * galois % twoN;
+    if (gr == 1 || std::find(gs.begin(), gs.end(), (uint32_t)gr) != gs.end())
+      throw std::runtime_error("hrotate_hoisted: galois^" + S(r) + " mod 2N repeats an element or is 1: the " + S(R) + " rotations are not distinct");
+    gs.push_back((uint32_t)gr);
+  }
+  ciph = new Ciphertext(currentLevel, N, Datapool, batchSize);
+  inputCiphertext("ct1", ciph, seed);
+  addrManager = new AddrManage(Datapool.back() + 1, batchSize);
+  addrManager->setGlobalDatapPoll(&Datapool);
+
+  KeySwitch up(labelName, maxLevel, currentLevel, alpha, ciph->getC1Addr(), &Datapool, &DataInsMap, insgener, addrManager, KeySwitch::MODUP);
+  dispatch(up.getInsMap());
+  const auto c0 = ciph->getC0Addr();
+  for (uint32_t r = 1; r <= R; ++r) {
+    const std::string rs = "_Rot" + S(r);
+    // rotation r's key: the synthetic stream seed + 10000 + 100000 r (+ (2 j + k) 1000 per digit and component, as IP_Key<k>_<j>)
+    KeySwitch ks(labelName, maxLevel, currentLevel, alpha, ciph->getC1Addr(), &Datapool, &DataInsMap, insgener, addrManager,
+                 KeySwitch::ROTATED_KEY_PRODUCT, rs, gs[r - 1], seed + 10000 + 100000ull * r);
+    dispatch(ks.getInsMap());
+    addrManager->MallocMem("AUTOOutput" + rs + "(0)", currentLevel);
+    std::vector<INSGROUP> a;
+    for (uint32_t l = 0; l < currentLevel; l++)
+      a.push_back(insgener->GenAUTO(l, labelName + "_AUTO" + rs + "_Level(" + S(l) + ")_k(0)", nullptr, c0[l],
+                                    addrManager->getAddr("AUTOOutput" + rs + "(0)")[l], gs[r - 1], l));
+    driver->dispatchInstructions("AUTO" + rs + "_Key(0)", a);
+    addrManager->MallocMem("HROTATEOutput" + rs + "(1)", currentLevel);
+    std::vector<INSGROUP> g;
+    for (uint32_t l = 0; l < currentLevel; l++)
+      g.push_back(insgener->GenEWE(l, labelName + "_HROTATEadd" + rs + "_Level(" + S(l) + ")", nullptr, nullptr, nullptr, nullptr,
+                                   addrManager->getAddr("KeySwitchFinalOutput" + rs + "_Key(0)")[l], 0, addrManager->getAddr("AUTOOutput" + rs + "(0)")[l], 0,
+                                   addrManager->getAddr("HROTATEOutput" + rs + "(1)")[l], EWE_ADD, l));
+    driver->dispatchInstructions("HROTATE_Hadd" + rs, g);
+    namedOutputs["out" + S(r) + ".c0"] = addrManager->getAddr("HROTATEOutput" + rs + "(1)");
+    namedOutputs["out" + S(r) + ".c1"] = addrManager->getAddr("KeySwitchFinalOutput" + rs + "_Key(1)");
+  }
+  finishConstruction();
+}
+
 // reference: HADD::HADD :1114-1176
 HADD::HADD(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch)
     : OperationBase("HADD", cfg, _arch, maxLevel, currentLevel, alpha) {
@@ -751,6 +841,7 @@ static OperationBase *makeOp(const std::string &o, uint32_t maxLevel, uint32_t l
   if (o == "hadd") return new HADD("test_hadd", maxLevel, level, alpha, cfg, arch);
   if (o == "pmult") return new PMULT("test_pmult", maxLevel, level, alpha, cfg, arch);
   if (o == "padd") return new PADD("test_ADD", maxLevel, level, alpha, cfg, arch);
+  if (o == "hrotate_hoisted") return new HROTATE_HOISTED("test_hrotate_hoisted", maxLevel, level, alpha, cfg, arch);
   throw std::runtime_error("Error operation requirement, please double confirm!");
 }
 
@@ -758,11 +849,16 @@ OpChain::OpChain(const std::string &cfgPath, const std::string &opList, uint32_t
                  const std::map<std::string, uint32_t> &overrides) {
   std::stringstream ss(opList);
   std::string name;
+  std::vector<std::string> names;
+  while (std::getline(ss, name, ','))
+    if (!name.empty()) names.push_back(name);
   uint32_t level = curLevel;
   try {
-    while (std::getline(ss, name, ',')) {
-      if (name.empty()) continue;
+    for (size_t i = 0; i < names.size(); ++i) {
+      name = names[i];
       if (level == 0) throw std::runtime_error("chain: no limbs left for " + name);
+      if (name == "hrotate_hoisted" && i + 1 < names.size())
+        throw std::runtime_error("chain: hrotate_hoisted has one output ciphertext per rotation and can only be the last op of a chain");
       Config *cfg = new Config(cfgPath);
       cfgs.push_back(cfg);
       cfg->getValue("N");
@@ -774,7 +870,7 @@ OpChain::OpChain(const std::string &cfgPath, const std::string &opList, uint32_t
       OperationBase *op = makeOp(name, maxLevel, level, alpha, cfg, arch);
       if (!ops.empty()) op->bindInput("ct1", ops.back());
       ops.push_back(op);
-      level = op->outputLevel();
+      if (i + 1 < names.size()) level = op->outputLevel();
     }
     if (ops.empty()) throw std::runtime_error("chain: empty op list");
   } catch (...) {

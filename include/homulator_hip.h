@@ -167,6 +167,25 @@ typedef struct hm_ip_desc {
   uint32_t x_galois;
 } hm_ip_desc;
 hm_status hm_inner_product_ex(hm_ctx *ctx, const hm_ip_desc *desc);
+/* Hoisted key product: ONE set of evaluation-form digits x, read once, multiplied with the keys of n_rot rotations, each through its own
+ * automorphism X -> X^galois[r]:
+ *   out[r][i][k] = sum_j automorph_{galois[r]}(x[i][j]) (.) y[r][i][k][j],   k < 2, j < n_terms <= 4, r < n_rot <= 16.
+ * Bit-identical to n_rot calls of hm_inner_product_ex with x_galois = galois[r] (residues are unique).  The digits are those of the UNROTATED
+ * ciphertext (the ModUp of src/Operation.cpp:31-188 run once); a digit's own Q limbs may point into c1 itself.  Limb lists are row-major:
+ * x_limbs[i * n_terms + j], y_limbs[((r * n + i) * 2 + k) * n_terms + j], out_limbs[(r * n + i) * 2 + k].  Every galois[r] is odd and below 2N.
+ * The kernel loads a tile of every digit once; for each rotation it gathers the key and scatters the output at the destination of the
+ * automorphism (aligned 16-byte pairs, swapped on odd: hm_automorph's index map).  No output limb-poly may overlap (by address range, not by
+ * base pointer) a digit or a key limb-poly: HM_ERR_ARG.  Safe under graph capture once it has run with the same limb lists. */
+#define HM_IP_HOISTED_MAX_ROT 16
+typedef struct hm_ip_hoisted_desc {
+  const uint64_t *x;  const uint32_t *x_limbs;    /* [n][n_terms] */
+  const uint64_t *y;  const uint32_t *y_limbs;    /* [n_rot][n][2][n_terms] */
+  uint64_t *out;      const uint32_t *out_limbs;  /* [n_rot][n][2] */
+  const uint32_t *mod_ids;                        /* [n] */
+  uint32_t n, n_terms, n_rot;
+  const uint32_t *galois;                         /* [n_rot] */
+} hm_ip_hoisted_desc;
+hm_status hm_inner_product_hoisted(hm_ctx *ctx, const hm_ip_hoisted_desc *desc);
 
 /* K1 x K5 — the HPIP unit as a fused NTT-epilogue x evaluation-key MAC: for extended limb i,
  *     out[i][k] = sum_{j < n_terms} X_j[i] * y[i][k][j],   X_j[i] = NTT(x[i][j]) if x_is_coeff[i][j] else x[i][j]
