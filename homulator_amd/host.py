@@ -49,6 +49,7 @@ def load():
         L.hh_op_N.restype = u32
         L.hh_op_N.argtypes = [vp]
         L.hh_op_plan.argtypes = [vp, C.c_char_p, u32]
+        L.hh_op_plan_full.argtypes = [vp, C.c_char_p, u32, C.POINTER(u32)]
         L.hh_op_stage_times.argtypes = [vp, u32, C.c_char_p, u32]
         L.hh_op_backend_counter.argtypes = [vp, C.c_char_p, u64p]
         L.hh_op_bind_input.argtypes = [vp, C.c_char_p, vp]
@@ -183,9 +184,16 @@ class Op:
         self._ck(self.L.hh_op_buffer_names(self.h, buf, len(buf)))
         return [s for s in buf.value.decode().split("\n") if s]
 
-    def plan(self):
-        buf = C.create_string_buffer(1 << 20)
-        self._ck(self.L.hh_op_plan(self.h, buf, len(buf)))
+    def plan(self, full=False):
+        """one line per launch; full=True: every field of every launch the execution consumes (operands included)"""
+        if full:
+            need = C.c_uint32()
+            self._ck(self.L.hh_op_plan_full(self.h, None, 0, C.byref(need)))
+            buf = C.create_string_buffer(need.value)
+            self._ck(self.L.hh_op_plan_full(self.h, buf, len(buf), None))
+        else:
+            buf = C.create_string_buffer(1 << 22)   # (batched sharded plans list every exchanged limb)
+            self._ck(self.L.hh_op_plan(self.h, buf, len(buf)))
         return [s for s in buf.value.decode().split("\n") if s]
 
     def backend_counter(self, name):

@@ -10,6 +10,8 @@
 // accelerator (include/SimModel.h) by one cycle, getCycle() returns CYCLES, shownStat() prints the reference's stat block.
 #ifndef HOMULATOR_ARCH_H
 #define HOMULATOR_ARCH_H
+#include <memory>
+
 #include "Basic.h"
 #include "Config.h"
 #include "Instruction.h"
@@ -100,12 +102,16 @@ public:
   size_t launchCount() const { return launches.size(); }
   std::string stageTimes(uint32_t iters);  // one line per launch: "<kind> <stage names> <ns>", each launch timed alone
   std::string planText() const;  // one line per launch: kind, stage names, limb count, exchange lists (tests)
+  std::string planDump() const;  // one line per launch: every field the execution consumes (the plan fingerprints of the tests)
   unsigned long long algorithmicBytes() const { return algBytes; }
   Statistic *stats() { return stat; }
   uint32_t N() const { return n; }
 
 private:
   struct Launch;
+  struct Planner;        // the fusion passes and their shared state (host/src/Planner.cpp)
+  struct LaunchBuilder;  // stage parts -> launches (host/src/Arch.cpp)
+  static uint32_t cap(uint32_t logN, const char *name);  // the back-end's capability table (hm_capability)
   Config *config;
   Backend backendKind;
   bool fuse;
@@ -136,7 +142,7 @@ private:
   std::vector<InputFill> fills;
   struct Binding { std::vector<AddrType> dst; Arch *src; std::vector<AddrType> srcAddrs; std::vector<uint32_t> dstLimbs, srcLimbs, mods; };
   std::vector<Binding> bindings;
-  std::vector<Launch *> launches;
+  std::vector<std::unique_ptr<Launch>> launches;
   size_t nextLaunch = 0;
   bool prepared = false;
   unsigned long long completedIns = 0, elapsedNs = 0, algBytes = 0;

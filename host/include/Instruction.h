@@ -32,7 +32,8 @@ public:
   std::vector<uint32_t> inMods;  // BCONV: modulus ids of the inputs
   unsigned long long refInstructions = 0;  // upstream instructions this record stands for
   unsigned long long refExtra = 0;         // ... of records folded into a BCONV record (not scaled by its MAC-port count)
-  // set by the backend's fusion passes (Arch::fusePasses), never by the generators:
+  // set by the backend's fusion passes (Arch::fusePasses, host/src/Planner.cpp), never by the generators; the fields that hold addresses
+  // are listed ONCE more, with their roles, in recordReads / recordWrites (Records.h): add a new one there too
   bool fusedSubScale = false;          // forward NTT whose epilogue is out = (minuend - NTT(in)) * constant [+ addend]
   AddrType fMinuend = 0, fAddend = 0;  // fAddend == 0: no addend
   // merged ModDown + rescale: the transform's input is in + fMixConst * fMix, the addend is scaled by fAddendConst
@@ -57,7 +58,7 @@ public:
   // fused inner product (ops == IP): out_k = sum_j ipX[j] * ipY[k][j]; out_0 = OutputOperand, out_1 = extraOutputs[0]
   std::vector<AddrType> ipX;
   std::vector<std::vector<AddrType>> ipY;
-  // fused NTT-epilogue x key MAC (Arch::fusePasses (7)): digit j with ipCoeff[j] set is still in coefficient
+  // fused NTT-epilogue x key MAC (Planner.cpp pass (7)): digit j with ipCoeff[j] set is still in coefficient
   // form at ipSrc[j] and goes through the forward transform inside the inner-product kernel; ipX[j] (the buffer the separate
   // transform would have written: NTTOut_beta(j)) then only serves as the scratch of its first pass
   std::vector<AddrType> ipSrc;

@@ -44,6 +44,9 @@ int hh_op_read_buffer_copy(hh_op *op, const char *name, uint32_t copy, uint64_t 
 int hh_op_write_buffer(hh_op *op, const char *name, uint32_t copy, const uint64_t *host);
 uint32_t hh_op_batch(hh_op *op);
 int hh_op_plan(hh_op *op, char *out, uint32_t cap);          /* launch plan, one line per launch */
+/* the full plan: every launch field the execution consumes, one line per launch.  *need (if not null) receives the bytes the text takes;
+ * out == NULL only asks for that size */
+int hh_op_plan_full(hh_op *op, char *out, uint32_t cap, uint32_t *need);
 /* hm_get_counter of the op's backend context (hip backend; e.g. "ntt_cross_xcd", "ntt_fused_small", "arith"): synchronises */
 int hh_op_backend_counter(hh_op *op, const char *name, uint64_t *value);
 int hh_op_stage_times(hh_op *op, uint32_t iters, char *out, uint32_t cap); /* "<kind> <stages> <ns>" per launch, each timed alone */

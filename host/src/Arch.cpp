@@ -8,12 +8,14 @@
 #include <cstring>
 #include <set>
 
+#include "Records.h"
+
 #include "../../homulator_amd/csrc/hm_params.h"
 #include "../../include/homulator_hip.h"
 
 // the back-end's capability table for this ring size (hm_capability: host-side data, no GPU): which fused forms have kernels.  The fusion
-// passes below ask it instead of naming ring sizes or digit widths (round 6).
-static uint32_t cap(uint32_t logN, const char *name) {
+// passes (Planner.cpp) and the launch builder ask it instead of naming ring sizes or digit widths (round 6).
+uint32_t Arch::cap(uint32_t logN, const char *name) {
   uint64_t v = 0;
   return hm_capability(logN, name, &v) == HM_OK ? (uint32_t)v : 0u;
 }
@@ -150,7 +152,6 @@ Arch::Arch(Config *cfg) : config(cfg) {
 }
 
 Arch::~Arch() {
-  for (Launch *l : launches) delete l;
   if (graph) hm_graph_destroy(static_cast<hm_graph *>(graph));
   if (ctx)
     for (void *p : sliceBuffers) hm_free(ctx, p);
@@ -256,1165 +257,573 @@ void Arch::issueIns(uint32_t index, uint32_t h, uint32_t w, std::vector<Instruct
 }
 
 // ---------------------------------------------------------------------------------------------------
-// fusion passes on the stage list (fuse = 1).  All of them preserve every value that a later stage or the
-// caller can observe except the intermediates they eliminate (listed in DESIGN.md §5).
+// stage -> launch.  Arch::buildLaunches (at the end of this section) splits the stages into parts one C-ABI call can express, gives every
+// part its dependency depth, and hands every (depth, key) group to LaunchBuilder, which has one emit function per launch kind.
 // ---------------------------------------------------------------------------------------------------
-void Arch::fusePasses(std::vector<Stage> &st) {
-  // consumers of every address
-  std::map<AddrType, int> uses;
-  auto operands = [](Instruction *i) {
-    std::vector<AddrType> v;
-    if (i->ops == BCONV_STEP2) v.assign(i->operandList.begin(), i->operandList.end() - 1);
-    else if (i->ops == MULT) {
-      const int m[9] = {3, 15, 7, 5, 5, 1, 5, 1, 13};
-      for (int b = 0; b < 4; ++b)
-        if (m[i->opcode] & (1 << b)) v.push_back(i->operandList[b]);
-    } else v.push_back(i->operandList[0]);
-    return v;
-  };
-  std::map<AddrType, Instruction *> producer;
-  for (auto &s : st)
-    for (Instruction *i : s.ins) {
-      for (AddrType a : operands(i)) uses[a]++;
-      producer[i->OutputOperand] = i;
-    }
-  std::set<Instruction *> dead;
-  // (1) pass-through NTT records: consumers read the source directly
-  std::map<AddrType, AddrType> alias;
-  for (auto &s : st)
-    for (Instruction *i : s.ins)
-      if ((i->ops == NTT) && i->passthrough) {
-        alias[i->OutputOperand] = i->operandList[0];
-        dead.insert(i);
-      }
-  for (auto &s : st)
-    for (Instruction *i : s.ins) {
-      if (dead.count(i)) continue;
-      for (AddrType &a : i->operandList) {
-        auto al = alias.find(a);
-        if (al != alias.end()) a = al->second;
-      }
-    }
-  // (2) INTT followed by a single MUL_CONST consumer: the constant goes into the INTT epilogue
-  for (auto &s : st)
-    for (Instruction *i : s.ins) {
-      if (i->ops != MULT || i->opcode != EWE_MUL_CONST || dead.count(i)) continue;
-      auto p = producer.find(i->operandList[0]);
-      if (p == producer.end() || p->second->ops != INTT || uses[i->operandList[0]] != 1 || p->second->hasConstant) continue;
-      p->second->hasConstant = true;
-      p->second->constant = i->constant;
-      p->second->OutputOperand = i->OutputOperand;
-      p->second->refInstructions += i->refInstructions;
-      producer[i->OutputOperand] = p->second;
-      dead.insert(i);
-    }
-  // (3) EWE chains: SUB then MUL_CONST -> SUB_SCALE ; SUB_SCALE then ADD -> SUB_SCALE_ADD
-  for (auto &s : st)
-    for (Instruction *i : s.ins) {
-      if (i->ops != MULT || dead.count(i)) continue;
-      if (i->opcode == EWE_MUL_CONST) {
-        auto p = producer.find(i->operandList[0]);
-        if (p == producer.end() || p->second->ops != MULT || p->second->opcode != EWE_SUB || dead.count(p->second) ||
-            uses[i->operandList[0]] != 1)
-          continue;
-        Instruction *sub = p->second;
-        i->opcode = EWE_SUB_SCALE;
-        i->operandList[0] = sub->operandList[0];
-        i->operandList[2] = sub->operandList[2];
-        i->refInstructions += sub->refInstructions;
-        dead.insert(sub);
-      } else if (i->opcode == EWE_ADD) {
-        for (int side = 0; side < 2; ++side) {
-          const int me = side ? 2 : 0, other = side ? 0 : 2;
-          auto p = producer.find(i->operandList[me]);
-          if (p == producer.end() || p->second->ops != MULT || p->second->opcode != EWE_SUB_SCALE || dead.count(p->second) ||
-              uses[i->operandList[me]] != 1)
-            continue;
-          Instruction *ss = p->second;
-          const AddrType addend = i->operandList[other];
-          i->opcode = EWE_SUB_SCALE_ADD;
-          i->operandList[0] = ss->operandList[0];
-          i->operandList[2] = ss->operandList[2];
-          i->operandList[3] = addend;
-          i->hasConstant = true;
-          i->constant = ss->constant;
-          i->refInstructions += ss->refInstructions;
-          dead.insert(ss);
-          break;
-        }
-      }
-    }
-  // (4) forward NTT whose only consumer is (minuend - x) * k [+ addend]: the epilogue moves into the transform's
-  //     last pass (ModDowNTT + ModDownSub + final add; Rescale_NTT + Rescale_SUB + Rescale_Mul)
-  for (auto &s : st)
-    for (Instruction *i : s.ins) {
-      if (i->ops != MULT || dead.count(i) || (i->opcode != EWE_SUB_SCALE && i->opcode != EWE_SUB_SCALE_ADD)) continue;
-      auto p = producer.find(i->operandList[2]);
-      if (p == producer.end() || p->second->ops != NTT || p->second->passthrough || dead.count(p->second) ||
-          p->second->fusedSubScale || uses[i->operandList[2]] != 1)
-        continue;
-      Instruction *t = p->second;
-      const AddrType minuend = i->operandList[0], addend = i->opcode == EWE_SUB_SCALE_ADD ? i->operandList[3] : 0;
-      const AddrType out = i->OutputOperand;
-      if (out == t->operandList[0] || out == minuend || out == addend) continue;  // out doubles as first-pass scratch
-      t->fusedSubScale = true;
-      t->fMinuend = minuend;
-      t->fAddend = addend;
-      t->hasConstant = true;
-      t->constant = i->constant;
-      t->OutputOperand = out;
-      t->refInstructions += i->refInstructions;
-      producer[out] = t;
-      dead.insert(i);
-    }
-  // (4b) ModDown finish followed by the rescale of the same limb.  T: h = (ip - NTT(conv)) * kT + d and
-  //      R: out = (h - NTT(r)) * kR with r = INTT(last limb of h) are both linear in the coefficient domain:
-  //      out = (ip - NTT(conv + kT^-1 * r)) * (kT kR) + d * kR — ONE transform per limb instead of two, and h never
-  //      exists (the last limb keeps T: r comes from it).  Bit-identical: everything is exact modular arithmetic.
-  for (auto &s : st)
-    for (Instruction *R : s.ins) {
-      if (R->ops != NTT || !R->fusedSubScale || R->fAddend || R->fMix || dead.count(R)) continue;
-      auto p = producer.find(R->fMinuend);
-      if (p == producer.end() || p->second == R || !p->second->fusedSubScale || p->second->fMix || dead.count(p->second) ||
-          p->second->mod_id != R->mod_id || uses[R->fMinuend] != 1)
-        continue;
-      Instruction *T = p->second;
-      const uint64_t q = modulus(R->mod_id);
-      // R survives (its stage comes after the INTT that produces r, so the stage list stays a topological order)
-      R->fMix = R->operandList[0];
-      R->fMixConst = hm::invmod(T->constant, q);
-      R->operandList[0] = T->operandList[0];
-      R->fMinuend = T->fMinuend;
-      R->fAddend = T->fAddend;
-      R->fAddendConst = T->fAddend ? R->constant : 0;
-      R->constant = hm::mulmod(T->constant, R->constant, q);
-      R->refInstructions += T->refInstructions;
-      dead.insert(T);
-    }
-  // (4c) the residue r = INTT(h_last) that the merged records mix in.  h_last = (ip - NTT(conv)) * kT + d is only ever
-  //      needed in coefficient form, where it is (INTT(ip) - conv) * kT + INTT(d): conv never has to be transformed and
-  //      brought back.  INTT(ip) and INTT(d) depend on nothing after the inner product, so they join the ModDown INTT
-  //      launch (equal dependency depth), and one element-wise SUB_SCALE_ADD on the last limb replaces the two
-  //      latency-bound single-limb transforms T_last and INTT(h_last).
-  {
-    struct Rewrite { Instruction *T, *X; size_t stage; };
-    std::vector<Rewrite> todo;
-    for (size_t si = 0; si < st.size(); ++si)
-      for (Instruction *X : st[si].ins) {
-        if (X->ops != INTT || X->hasConstant || dead.count(X)) continue;
-        auto p = producer.find(X->operandList[0]);
-        if (p == producer.end() || dead.count(p->second) || !p->second->fusedSubScale || p->second->fMix || p->second->ops != NTT ||
-            uses[X->operandList[0]] != 1)
-          continue;
-        bool mixedIn = false;
-        for (auto &s2 : st)
-          for (Instruction *i : s2.ins) mixedIn |= !dead.count(i) && i->fMix == X->OutputOperand;
-        if (mixedIn) todo.push_back(Rewrite{p->second, X, si});
-      }
-    AddrType fresh = limbIndex.empty() ? 1 : limbIndex.rbegin()->first + 1;
-    for (const Rewrite &w : todo) {
-      Instruction *T = w.T, *X = w.X;
-      const AddrType h = X->operandList[0], r = X->OutputOperand;
-      Instruction *ia = new Instruction("INTT", INTT, T->level_id);   // wa = INTT(ip_last), kept in h's limb
-      ia->mod_id = T->mod_id; ia->operandList = {T->fMinuend}; ia->OutputOperand = h; ia->refInstructions = T->refInstructions;
-      st[w.stage].ins.push_back(ia);
-      AddrType wb = 0;
-      if (T->fAddend) {                                               // wb = INTT(d_last), in a limb of its own
-        wb = fresh++;
-        registerLimbs({wb});
-        Instruction *ib = new Instruction("INTT", INTT, T->level_id);
-        ib->mod_id = T->mod_id; ib->operandList = {T->fAddend}; ib->OutputOperand = wb;
-        st[w.stage].ins.push_back(ib);
-      }
-      Instruction *e = new Instruction("MULT", MULT, T->level_id);    // r = (wa - conv_last) * kT [+ wb]
-      e->mod_id = T->mod_id;
-      e->opcode = wb ? EWE_SUB_SCALE_ADD : EWE_SUB_SCALE;
-      e->operandList = {h, 0, T->operandList[0], wb};
-      e->hasConstant = true; e->constant = T->constant;
-      e->OutputOperand = r; e->refInstructions = X->refInstructions;
-      st[w.stage].ins.push_back(e);
-      producer[h] = ia; producer[r] = e;
-      dead.insert(T); dead.insert(X);
-    }
-  }
-  // (5) tensor product: d1 = p*s + r*t (MAC2) with d0 = p*t and d2 = r*s (MUL) of the same limb -> one pass
-  {
-    std::map<std::pair<AddrType, AddrType>, Instruction *> muls;
-    for (auto &s : st)
-      for (Instruction *i : s.ins)
-        if (i->ops == MULT && i->opcode == EWE_MUL && !dead.count(i)) muls[{i->operandList[0], i->operandList[1]}] = i;
-    for (auto &s : st)
-      for (Instruction *i : s.ins) {
-        if (i->ops != MULT || i->opcode != EWE_MAC2 || dead.count(i)) continue;
-        const AddrType P = i->operandList[0], S = i->operandList[1], R = i->operandList[2], T = i->operandList[3];
-        auto u = muls.find({P, T}), v = muls.find({R, S});
-        if (u == muls.end() || v == muls.end() || u->second->mod_id != i->mod_id || v->second->mod_id != i->mod_id) continue;
-        i->fusedTensor = true;
-        i->extraOutputs = {u->second->OutputOperand, v->second->OutputOperand};
-        i->refInstructions += u->second->refInstructions + v->second->refInstructions;
-        dead.insert(u->second);
-        dead.insert(v->second);
-      }
-  }
-  // (6) inner product with the evaluation key: the chain MAC2 / MAC_ADD ... of one key collapses into a single sum
-  //     of products, and the two keys (same ext operands) into one two-output record (the HPIP unit's job)
-  {
-    struct Dot { std::vector<AddrType> x, y; std::vector<Instruction *> members; };
-    std::map<Instruction *, Dot> dots;
-    auto single = [&](AddrType a) { return uses[a] == 1; };
-    std::vector<Instruction *> order;
-    for (auto &s : st)
-      for (Instruction *i : s.ins) order.push_back(i);
-    for (Instruction *i : order) {
-      if (i->ops != MULT || dead.count(i) || i->fusedTensor) continue;
-      Dot d;
-      if (i->opcode == EWE_MUL) { d.x = {i->operandList[0]}; d.y = {i->operandList[1]}; }
-      else if (i->opcode == EWE_MAC2) { d.x = {i->operandList[0], i->operandList[2]}; d.y = {i->operandList[1], i->operandList[3]}; }
-      else if (i->opcode == EWE_MAC_ADD) {
-        auto p = producer.find(i->operandList[2]);
-        if (p == producer.end() || !dots.count(p->second) || !single(i->operandList[2]) || p->second->mod_id != i->mod_id) continue;
-        d = dots[p->second];
-        d.x.push_back(i->operandList[0]);
-        d.y.push_back(i->operandList[1]);
-      } else continue;
-      d.members.push_back(i);
-      dots[i] = d;
-    }
-    // keep the dots that end a chain (nobody extends them) and have a partner with the same x list or >= 3 terms
-    std::set<Instruction *> extended;
-    for (auto &kv : dots)
-      for (size_t m = 0; m + 1 < kv.second.members.size(); ++m) extended.insert(kv.second.members[m]);
-    std::map<std::pair<uint32_t, std::vector<AddrType>>, Instruction *> byX;
-    for (Instruction *i : order) {
-      auto it = dots.find(i);
-      if (it == dots.end() || extended.count(i) || it->second.x.size() > 4) continue;
-      Dot &d = it->second;
-      auto key = std::make_pair(i->mod_id, d.x);
-      auto partner = byX.find(key);
-      if (partner == byX.end()) { byX[key] = i; continue; }
-      Instruction *a = partner->second;  // first key
-      Dot &da = dots[a];
-      if (a->ops == IP) continue;        // already paired
-      // `i` (the later one) carries the fused record so that it is scheduled after every member of both chains
-      const AddrType outFirst = a->OutputOperand, outSecond = i->OutputOperand;
-      i->ops = IP;
-      i->ipX = d.x;
-      i->ipY = {da.y, d.y};
-      i->OutputOperand = outFirst;
-      i->extraOutputs = {outSecond};
-      producer[outFirst] = i;
-      for (Instruction *m : da.members) { i->refInstructions += m->refInstructions; dead.insert(m); }
-      for (Instruction *m : d.members)
-        if (m != i) { i->refInstructions += m->refInstructions; dead.insert(m); }
-      byX.erase(partner);
-    }
-  }
-  // (6h) hoisted rotations (hrotate_hoisted): two-key inner-product records whose digits are all automorphisms (one element per record) of the SAME
-  //      materialised digits, read by nothing else, merge into ONE record per (modulus, digit list): hm_inner_product_hoisted reads the digits once
-  //      for every rotation and gathers the key / scatters the output at the automorphism's destination; the automorphisms are never written.
-  //      The first record in stage order carries the merged one: every reader of any rotation's output comes after it.
-  if (fuseHoist) {
-    std::map<AddrType, std::vector<Instruction *>> readers;
-    for (auto &s : st)
-      for (Instruction *i : s.ins) {
-        if (dead.count(i)) continue;
-        if (i->ops == IP && !i->ipX.empty()) {
-          for (AddrType x : i->ipX) readers[x].push_back(i);
-          for (auto &y : i->ipY) for (AddrType yy : y) readers[yy].push_back(i);
-        } else {
-          for (AddrType a : operands(i)) readers[a].push_back(i);
-          if (i->fusedSubScale) { readers[i->fMinuend].push_back(i); if (i->fAddend) readers[i->fAddend].push_back(i); if (i->fMix) readers[i->fMix].push_back(i); }
-        }
-      }
-    typedef std::pair<uint32_t, std::vector<AddrType>> DigitsKey;   // (modulus, unrotated digits)
-    std::map<DigitsKey, std::vector<std::pair<Instruction *, std::vector<Instruction *>>>> groups;   // -> (record, its automorphisms) in stage order
-    std::vector<DigitsKey> groupOrder;
-    for (auto &s : st)
-      for (Instruction *ip : s.ins) {
-        if (ip->ops != IP || ip->ipX.empty() || dead.count(ip) || ip->ipY.size() != 2 || ip->ipXGalois || !ip->ipHoistG.empty() ||
-            std::find(ip->ipCoeff.begin(), ip->ipCoeff.end(), 1) != ip->ipCoeff.end())
-          continue;
-        std::vector<AddrType> src;
-        std::vector<Instruction *> autos;
-        for (AddrType x : ip->ipX) {
-          auto p = producer.find(x);
-          if (p == producer.end()) break;
-          Instruction *A = p->second;
-          const auto &rd = readers[x];
-          if (A->ops != AUTO || dead.count(A) || A->galois <= 1 || A->mod_id != ip->mod_id || (!autos.empty() && A->galois != autos[0]->galois) ||
-              rd.size() != 1 || rd[0] != ip)
-            break;
-          src.push_back(A->operandList[0]);
-          autos.push_back(A);
-        }
-        if (autos.size() != ip->ipX.size()) continue;
-        const DigitsKey key(ip->mod_id, src);
-        if (!groups.count(key)) groupOrder.push_back(key);
-        groups[key].push_back({ip, autos});
-      }
-    for (const DigitsKey &key : groupOrder) {
-      const auto &mem = groups[key];
-      for (size_t b = 0; b < mem.size(); b += HM_IP_HOISTED_MAX_ROT) {
-        const size_t e = std::min(mem.size(), b + (size_t)HM_IP_HOISTED_MAX_ROT);
-        std::set<uint32_t> distinct;
-        for (size_t m = b; m < e; ++m) distinct.insert(mem[m].second[0]->galois);
-        if (distinct.size() != e - b) continue;   // two records by one element are not rotations of one ciphertext
-        Instruction *c = mem[b].first;
-        std::vector<AddrType> outs;
-        std::vector<std::vector<AddrType>> ys;
-        std::vector<uint32_t> gs;
-        for (size_t m = b; m < e; ++m) {
-          Instruction *i = mem[m].first;
-          outs.push_back(i->OutputOperand);
-          outs.insert(outs.end(), i->extraOutputs.begin(), i->extraOutputs.end());
-          ys.insert(ys.end(), i->ipY.begin(), i->ipY.end());
-          gs.push_back(mem[m].second[0]->galois);
-          if (i != c) { c->refInstructions += i->refInstructions; dead.insert(i); }
-          for (Instruction *A : mem[m].second) { c->refInstructions += A->refInstructions; dead.insert(A); }
-        }
-        c->ipX = key.second;
-        c->ipY = ys;
-        c->ipHoistG = gs;
-        c->OutputOperand = outs[0];
-        c->extraOutputs.assign(outs.begin() + 1, outs.end());
-        for (AddrType o : outs) producer[o] = c;
-      }
-    }
-  }
-  // (7) HPIP as SURVEY.md 8f-2 specifies it: a forward transform whose only reader is an inner-product record moves INTO that
-  //     record (ModUp_NTT_(j) + InnerProOut: src/Operation.cpp:190-414).  The kernel runs the digit's ROW pass and multiplies
-  //     its registers into both keys' accumulators; the extended digit (NTTOut_beta(j)) is never written or read back — its
-  //     buffer only serves the first pass as scratch.
-  if (fuseHpip) {
-    std::map<AddrType, std::vector<Instruction *>> readers;
-    for (auto &s : st)
-      for (Instruction *i : s.ins) {
-        if (dead.count(i)) continue;
-        if (i->ops == IP && !i->ipX.empty()) {
-          for (AddrType x : i->ipX) readers[x].push_back(i);
-          for (auto &y : i->ipY) for (AddrType yy : y) readers[yy].push_back(i);
-        } else {
-          for (AddrType a : operands(i)) readers[a].push_back(i);
-          if (i->fusedSubScale) { readers[i->fMinuend].push_back(i); if (i->fAddend) readers[i->fAddend].push_back(i); if (i->fMix) readers[i->fMix].push_back(i); }
-        }
-      }
-    for (auto &s : st)
-      for (Instruction *ip : s.ins) {
-        if (ip->ops != IP || ip->ipX.empty() || dead.count(ip) || !ip->ipHoistG.empty()) continue;   // (6h): its digits stay materialised
-        ip->ipSrc = ip->ipX;
-        ip->ipCoeff.assign(ip->ipX.size(), 0);
-        std::vector<Instruction *> conv(ip->ipX.size(), nullptr);
-        // widest digit the fused conversion + first pass takes (0: none at this ring size); config key fuse_bconv_max_in caps it below what the
-        // back-end offers (A/B runs: 15 = the plan of rounds 3-5, where wider digits kept a conversion launch of their own)
-        // (default: the widest digit for which the fused form measured faster at this ring size, cap_bconv_col_pref_in)
-        const uint32_t maxConvIn = std::min<uint32_t>(cap(logN, "cap_bconv_col_max_in"), config->getValueOr("fuse_bconv_max_in", cap(logN, "cap_bconv_col_pref_in")));
-        bool allConv = fuseBconv && (world_ == 1 || shardFused || shardGather) && maxConvIn != 0;
-        for (size_t j = 0; j < ip->ipX.size(); ++j) {
-          auto p = producer.find(ip->ipX[j]);
-          if (p == producer.end()) continue;
-          Instruction *t = p->second;
-          if (t->ops != NTT || t->passthrough || t->fusedSubScale || dead.count(t) || t->mod_id != ip->mod_id) continue;
-          auto &rd = readers[ip->ipX[j]];
-          if (rd.size() != 1 || rd[0] != ip) continue;
-          ip->ipSrc[j] = t->operandList[0];
-          ip->ipCoeff[j] = 1;
-          ip->refInstructions += t->refInstructions;
-          dead.insert(t);
-          // (8) is the transform's input a conversion output that nobody else reads?
-          auto pb = producer.find(t->operandList[0]);
-          auto &rb = readers[t->operandList[0]];
-          if (pb != producer.end() && pb->second->ops == BCONV_STEP2 && !dead.count(pb->second) && rb.size() == 1 && rb[0] == t &&
-              pb->second->operandList.size() - 1 <= maxConvIn && pb->second->mod_id == ip->mod_id)
-            conv[j] = pb->second;
-          else allConv = false;
-        }
-        if (allConv && std::find(ip->ipCoeff.begin(), ip->ipCoeff.end(), 1) != ip->ipCoeff.end()) {
-          ip->ipConvIn.assign(ip->ipX.size(), {});
-          ip->ipConvMods.assign(ip->ipX.size(), {});
-          for (size_t j = 0; j < ip->ipX.size(); ++j) {
-            if (!conv[j]) continue;
-            ip->ipConvIn[j].assign(conv[j]->operandList.begin(), conv[j]->operandList.end() - 1);
-            ip->ipConvMods[j] = conv[j]->inMods;
-            ip->refInstructions += conv[j]->refInstructions * (unsigned long long)config->getValueOr("bconv_num_high", 1) * config->getValueOr("bconv_num_width", 1);
-            dead.insert(conv[j]);
-          }
-        }
-      }
-  }
-  // (7b, round 5) an inner-product record (HPIP form) whose outputs are read by inverse transforms and nothing else — the special limbs of
-  //      the key-switch sum (ModDownINTTOut_Key(k)) and, with (4c), the last Q limb (the rescale residue's INTT) — hands them over as the
-  //      FIRST pass of that inverse transform: a ROW pass over the 16 rows of the limb-poly the workgroup has just accumulated (the forward
-  //      ROW pass's last round and the inverse ROW pass's first are the same round, so the pass runs from the registers).  The kernel stores
-  //      the pass's hand-off into the INTT's output limb, the INTT record keeps its COL pass (hm_ntt_second_pass, with its scale), and the
-  //      evaluation-form sums of those limbs (InnerProduceOut_Key{k}[0 .. alpha)) are never written or read back.
-  if (fuseHpip && fuseIpInv && (world_ == 1 || shardGather) && cap(logN, "cap_ip_inverse_out")) {
-    std::map<AddrType, std::vector<Instruction *>> readers;
-    for (auto &s : st)
-      for (Instruction *i : s.ins) {
-        if (dead.count(i)) continue;
-        if (i->ops == IP && !i->ipX.empty()) {
-          for (AddrType x : (i->ipSrc.empty() ? i->ipX : i->ipSrc)) readers[x].push_back(i);
-          for (auto &cin : i->ipConvIn) for (AddrType x : cin) readers[x].push_back(i);
-          for (auto &y : i->ipY) for (AddrType yy : y) readers[yy].push_back(i);
-        } else {
-          for (AddrType a : operands(i)) readers[a].push_back(i);
-          if (i->fusedSubScale) { readers[i->fMinuend].push_back(i); if (i->fAddend) readers[i->fAddend].push_back(i); if (i->fMix) readers[i->fMix].push_back(i); }
-        }
-      }
-    for (auto &s : st)
-      for (Instruction *ip : s.ins) {
-        if (ip->ops != IP || ip->ipX.empty() || dead.count(ip) || ip->ipInvOut) continue;
-        if (std::find(ip->ipCoeff.begin(), ip->ipCoeff.end(), 1) == ip->ipCoeff.end()) continue;   // the fused transform x key kernel only
-        std::vector<AddrType *> outs = {&ip->OutputOperand};
-        for (AddrType &o : ip->extraOutputs) outs.push_back(&o);
-        std::vector<Instruction *> inv;
-        for (AddrType *o : outs) {
-          auto &rd = readers[*o];
-          if (rd.size() != 1 || rd[0]->ops != INTT || dead.count(rd[0]) || rd[0]->mod_id != ip->mod_id || rd[0]->secondOnly || rd[0]->operandList[0] != *o) break;
-          inv.push_back(rd[0]);
-        }
-        if (inv.size() != outs.size()) continue;
-        for (size_t k = 0; k < outs.size(); ++k) {
-          *outs[k] = inv[k]->OutputOperand;                      // the hand-off lands where the inverse transform finishes in place
-          inv[k]->operandList[0] = inv[k]->OutputOperand;
-          inv[k]->secondOnly = true;
-        }
-        ip->ipInvOut = true;
-      }
-  }
-  // (9, round 4) the ModDown side of (8): a fused forward transform (ModDowNTT + ModDownSub [+ rescale]) whose input is a P -> Q conversion
-  //     output that nobody else reads takes the conversion into its first pass (src/Operation.cpp:489-590): ModdownBConvOut_Key(k) is
-  //     never written or read back.  The last limb of a key keeps its conversion: the rescale residue is formed from it element-wise (4c).
-  if (fuseBconv && fuseModDown && (world_ == 1 || shardGather) && cap(logN, "cap_bconv_col_max_in_mix")) {
-    const uint32_t maxMixIn = cap(logN, "cap_bconv_col_max_in_mix");
-    std::map<AddrType, std::vector<Instruction *>> readers;
-    for (auto &s : st)
-      for (Instruction *i : s.ins) {
-        if (dead.count(i)) continue;
-        if (i->ops == IP && !i->ipX.empty()) {
-          for (AddrType x : (i->ipSrc.empty() ? i->ipX : i->ipSrc)) readers[x].push_back(i);
-          for (auto &cin : i->ipConvIn) for (AddrType x : cin) readers[x].push_back(i);
-          for (auto &y : i->ipY) for (AddrType yy : y) readers[yy].push_back(i);
-        } else {
-          for (AddrType a : operands(i)) readers[a].push_back(i);
-          if (i->fusedSubScale) { readers[i->fMinuend].push_back(i); if (i->fAddend) readers[i->fAddend].push_back(i); if (i->fMix) readers[i->fMix].push_back(i); }
-        }
-      }
-    for (auto &s : st)
-      for (Instruction *t : s.ins) {
-        if (t->ops != NTT || !t->fusedSubScale || t->passthrough || dead.count(t)) continue;
-        auto pb = producer.find(t->operandList[0]);
-        if (pb == producer.end() || pb->second->ops != BCONV_STEP2 || dead.count(pb->second) || pb->second->mod_id != t->mod_id) continue;
-        auto &rb = readers[t->operandList[0]];
-        if (rb.size() != 1 || rb[0] != t || pb->second->operandList.size() - 1 > (t->fMix ? maxMixIn : cap(logN, "cap_bconv_col_max_in"))) continue;
-        t->fConvIn.assign(pb->second->operandList.begin(), pb->second->operandList.end() - 1);
-        t->fConvMods = pb->second->inMods;
-        t->refInstructions += pb->second->refInstructions * (unsigned long long)config->getValueOr("bconv_num_high", 1) * config->getValueOr("bconv_num_width", 1);
-        dead.insert(pb->second);
-      }
-  }
-  // (10, round 4) r = (wa - conv_last) * kT [+ wb] (4c) directly behind the conversion that produces conv_last: the one-limb element-wise
-  //      launch becomes the conversion kernel's epilogue (hm_bconv_desc::sub_from)
-  if (fuseBconv && (world_ == 1 || shardGather)) {
-    std::map<AddrType, int> nread;
-    for (auto &s : st)
-      for (Instruction *i : s.ins) {
-        if (dead.count(i)) continue;
-        if (i->ops == IP && !i->ipX.empty()) {
-          for (AddrType x : (i->ipSrc.empty() ? i->ipX : i->ipSrc)) nread[x]++;
-          for (auto &cin : i->ipConvIn) for (AddrType x : cin) nread[x]++;
-          for (auto &y : i->ipY) for (AddrType yy : y) nread[yy]++;
-        } else {
-          for (AddrType a : operands(i)) nread[a]++;
-          if (i->fusedSubScale) { nread[i->fMinuend]++; if (i->fAddend) nread[i->fAddend]++; if (i->fMix) nread[i->fMix]++; }
-          for (AddrType x : i->fConvIn) nread[x]++;
-        }
-      }
-    for (auto &s : st)
-      for (size_t ei = 0; ei < s.ins.size(); ++ei) {
-        Instruction *e = s.ins[ei];
-        if (e->ops != MULT || dead.count(e) || (e->opcode != EWE_SUB_SCALE && e->opcode != EWE_SUB_SCALE_ADD)) continue;
-        auto pb = producer.find(e->operandList[2]);
-        if (pb == producer.end() || pb->second->ops != BCONV_STEP2 || dead.count(pb->second) || pb->second->fusedEpi || pb->second->mod_id != e->mod_id ||
-            nread[e->operandList[2]] != 1)
-          continue;
-        Instruction *cv = pb->second;
-        cv->fusedEpi = true;
-        cv->fSubFrom = e->operandList[0];
-        cv->fAdd = e->opcode == EWE_SUB_SCALE_ADD ? e->operandList[3] : 0;
-        cv->hasConstant = true;
-        cv->constant = e->constant;
-        cv->OutputOperand = e->OutputOperand;
-        cv->refExtra += e->refInstructions;   // (a conversion's own count is scaled by the MAC ports at launch time, the epilogue's is not)
-        producer[cv->OutputOperand] = cv;
-        // the conversion now reads what e read (the inverse transforms of 4c, queued in e's stage): it takes e's place in the stage list,
-        // which stays a topological order
-        for (auto &s2 : st) s2.ins.erase(std::remove(s2.ins.begin(), s2.ins.end(), cv), s2.ins.end());
-        std::replace(s.ins.begin(), s.ins.end(), e, cv);
-        dead.insert(e);
-      }
-  }
-  // (11, round 5) split-30 packed conversion inputs.  A limb-poly that an inverse transform writes and that nothing but base conversions read
-  //      (as a conversion INPUT: a separate conversion, a conversion inside a transform x key record or inside a fused transform) is
-  //      stored packed; a conversion takes packed inputs only if all of them are.
-  if (packBconvIn && (world_ == 1 || shardGather)) {
-    struct Conv { std::vector<AddrType> in; Instruction *ins; int digit; };   // digit: index into ipConvIn, -1 = the record's own conversion
-    std::vector<Conv> convs;
-    std::map<AddrType, int> otherReads;   // reads of an address that are not a conversion input
-    for (auto &s : st)
-      for (Instruction *i : s.ins) {
-        if (dead.count(i)) continue;
-        if (i->ops == IP && !i->ipX.empty()) {
-          const auto &src = i->ipSrc.empty() ? i->ipX : i->ipSrc;
-          for (size_t j = 0; j < src.size(); ++j) {
-            const bool conv = j < i->ipConvIn.size() && !i->ipConvIn[j].empty();
-            if (conv) convs.push_back(Conv{i->ipConvIn[j], i, (int)j});
-            else otherReads[src[j]]++;
-          }
-          for (auto &y : i->ipY) for (AddrType yy : y) otherReads[yy]++;
-          continue;
-        }
-        if (i->ops == INTT && i->secondOnly) continue;   // (7b) its one operand is its own output: the in-place second pass is no other reader of it
-        if (i->ops == BCONV_STEP2) convs.push_back(Conv{std::vector<AddrType>(i->operandList.begin(), i->operandList.end() - 1), i, -1});
-        else if (!i->fConvIn.empty()) {
-          if (i->fMix) { for (AddrType a : i->fConvIn) otherReads[a]++; }   // (the fused conversion with the mix prologue takes plain inputs)
-          else convs.push_back(Conv{i->fConvIn, i, -1});
-        } else for (AddrType a : operands(i)) otherReads[a]++;
-        if (i->fusedSubScale) { otherReads[i->fMinuend]++; if (i->fAddend) otherReads[i->fAddend]++; if (i->fMix) otherReads[i->fMix]++; }
-        if (i->fusedEpi) { otherReads[i->fSubFrom]++; if (i->fAdd) otherReads[i->fAdd]++; }
-      }
-    std::set<AddrType> cand;
-    for (auto &s : st)
-      for (Instruction *x : s.ins)
-        if (x->ops == INTT && !dead.count(x) && !otherReads.count(x->OutputOperand)) cand.insert(x->OutputOperand);
-    for (bool changed = true; changed;) {   // a conversion with one plain input keeps all of its inputs plain
-      changed = false;
-      for (const Conv &cv : convs) {
-        bool all = true;
-        for (AddrType a : cv.in) all &= cand.count(a) != 0;
-        if (all) continue;
-        for (AddrType a : cv.in) changed |= cand.erase(a) != 0;
-      }
-    }
-    std::set<AddrType> read;
-    for (const Conv &cv : convs) {
-      if (cv.in.empty() || !cand.count(cv.in[0])) continue;
-      if (cv.digit >= 0) { cv.ins->ipConvPacked.resize(cv.ins->ipConvIn.size(), 0); cv.ins->ipConvPacked[(size_t)cv.digit] = 1; }
-      else cv.ins->inPacked = true;
-      read.insert(cv.in.begin(), cv.in.end());
-    }
-    for (auto &s : st)
-      for (Instruction *x : s.ins)
-        if (x->ops == INTT && !dead.count(x) && read.count(x->OutputOperand)) x->packedOut = true;
-  }
-  // (12) round 6: an automorphism whose output is read ONLY as the input of inverse transforms, as the addend of fused forward transforms and / or as
-  //      the evaluation-form digits of transform x key records folds into those readers (hm_ntt_desc.in_galois, hm_ntt_fused_desc.addend_galois,
-  //      hm_ntt_ip_desc.x_galois): the index map takes aligned blocks to aligned blocks, so a kernel gathers through it with its own 16-byte loads,
-  //      and AUTOOutput is never written or read back.  hrotate: AUTO_Key(1) -> ModUp_INTT + the key product's own digits, AUTO_Key(0) -> the final
-  //      add inside ModDowNTT's epilogue: 6 -> 5 launches, 140 limb-polys less traffic.  Config key fuse_auto (default 1).
-  //      The key product takes ONE Galois element per launch: its records fold only if every evaluation-form digit of every such record of the op
-  //      is the output of a foldable automorphism by the same element.  Sharded plans fold the same way: a limb-poly's transforms and key product run on
-  //      the rank that owns the limb, where the automorphism's source limb lives too.
-  if (fuseAuto) {
-    struct Reader { Instruction *ins; int role; size_t digit; };   // role 0: INTT input, 1: fused forward transform's addend, 2: evaluation-form digit of a
-    std::map<AddrType, std::vector<Reader>> readers;               // transform x key record, -1: anything else
-    std::vector<Reader> ownDigits;
-    for (auto &s : st)
-      for (Instruction *i : s.ins) {
-        if (dead.count(i)) continue;
-        if (i->ops == IP && !i->ipX.empty()) {
-          // a transform x key record reads its own digits in evaluation form, a plain inner-product record (no digit transformed inside) all of them
-          const bool anyT = std::find(i->ipCoeff.begin(), i->ipCoeff.end(), 1) != i->ipCoeff.end(), can = !i->ipXGalois && i->ipHoistG.empty();   // (any plan: a limb-poly's key product runs on the rank that owns the limb, and so does the automorphism's source limb)
-          const auto &src = i->ipSrc.empty() ? i->ipX : i->ipSrc;
-          for (size_t j = 0; j < src.size(); ++j) {
-            const bool own = can && (!anyT || (!i->ipCoeff[j] && !(j < i->ipConvIn.size() && !i->ipConvIn[j].empty())));
-            readers[src[j]].push_back({i, own ? 2 : -1, j});
-            if (own) ownDigits.push_back({i, 2, j});
-          }
-          for (auto &v : i->ipConvIn) for (AddrType a : v) readers[a].push_back({i, -1, 0});
-          for (auto &y : i->ipY) for (AddrType a : y) readers[a].push_back({i, -1, 0});
-          continue;
-        }
-        const bool plainIntt = i->ops == INTT && !i->secondOnly && i->fConvIn.empty() && !i->inGalois;
-        for (AddrType a : operands(i)) readers[a].push_back({i, plainIntt && a == i->operandList[0] ? 0 : -1, 0});
-        for (AddrType a : i->fConvIn) readers[a].push_back({i, -1, 0});
-        if (i->fusedSubScale) {
-          readers[i->fMinuend].push_back({i, -1, 0});
-          if (i->fAddend) readers[i->fAddend].push_back({i, i->ops == NTT && !i->fMix && i->fConvIn.empty() && !i->fAddendGalois ? 1 : -1, 0});
-          if (i->fMix) readers[i->fMix].push_back({i, -1, 0});
-        }
-        if (i->fusedEpi) { readers[i->fSubFrom].push_back({i, -1, 0}); if (i->fAdd) readers[i->fAdd].push_back({i, -1, 0}); }
-      }
-    // (the readers will read the automorphism's SOURCE, and later than the automorphism did: nothing may write that source from the automorphism's
-    // stage on — the reference's operations never write their inputs; a program that does keeps its launch)
-    std::map<AddrType, size_t> lastWrite;
-    for (size_t si = 0; si < st.size(); ++si)
-      for (Instruction *i : st[si].ins) {
-        if (dead.count(i)) continue;
-        lastWrite[i->OutputOperand] = si;
-        for (AddrType o : i->extraOutputs) lastWrite[o] = si;
-      }
-    std::map<AddrType, Instruction *> cand;   // output address -> the automorphism that every reader can read through
-    bool anyOwn = false;
-    for (size_t si = 0; si < st.size(); ++si)
-      for (Instruction *A : st[si].ins) {
-        if (A->ops != AUTO || dead.count(A) || A->galois <= 1) continue;
-        { auto w = lastWrite.find(A->operandList[0]); if (w != lastWrite.end() && w->second >= si) continue; }
-        auto r = readers.find(A->OutputOperand);
-        if (r == readers.end() || r->second.empty()) continue;   // nobody reads it inside the op: a result
-        bool ok = true;
-        for (const Reader &x : r->second) ok &= x.role >= 0 && x.ins->mod_id == A->mod_id && x.ins->OutputOperand != A->operandList[0];
-        if (!ok) continue;
-        cand[A->OutputOperand] = A;
-        for (const Reader &x : r->second) anyOwn |= x.role == 2;
-      }
-    if (anyOwn) {   // one Galois element per key-product launch
-      uint32_t g0 = 0;
-      bool uniform = true;
-      for (const Reader &x : ownDigits) {
-        auto c = cand.find((x.ins->ipSrc.empty() ? x.ins->ipX : x.ins->ipSrc)[x.digit]);
-        if (c == cand.end() || (g0 && c->second->galois != g0)) { uniform = false; break; }
-        g0 = c->second->galois;
-      }
-      if (!uniform)
-        for (auto it = cand.begin(); it != cand.end();) {
-          bool own = false;
-          for (const Reader &x : readers[it->first]) own |= x.role == 2;
-          it = own ? cand.erase(it) : std::next(it);
-        }
-    }
-    for (auto &kv : cand) {
-      Instruction *A = kv.second;
-      auto &rd = readers[kv.first];
-      for (const Reader &x : rd) {
-        if (x.role == 0) { x.ins->operandList[0] = A->operandList[0]; x.ins->inGalois = A->galois; }
-        else if (x.role == 1) { x.ins->fAddend = A->operandList[0]; x.ins->fAddendGalois = A->galois; }
-        else {
-          x.ins->ipX[x.digit] = A->operandList[0];
-          if (!x.ins->ipSrc.empty()) x.ins->ipSrc[x.digit] = A->operandList[0];
-          x.ins->ipXGalois = A->galois;
-        }
-      }
-      rd.front().ins->refInstructions += A->refInstructions;
-      dead.insert(A);
-    }
-  }
-  // drop dead instructions and empty stages; upstream instructions of eliminated pass-through records are
-  // accounted on the first surviving instruction so that the retired total still matches getTotalIns()
-  unsigned long long orphan = 0;
-  std::vector<Stage> keep;
-  for (auto &s : st) {
-    Stage t = s;
-    t.ins.clear();
-    for (Instruction *i : s.ins) {
-      if (!dead.count(i)) t.ins.push_back(i);
-      else if (i->passthrough) orphan += i->refInstructions;
-    }
-    if (!t.ins.empty()) keep.push_back(t);
-  }
-  if (!keep.empty()) keep[0].ins[0]->refInstructions += orphan;
-  st.swap(keep);
+namespace {
+struct Part { std::string name; int key; std::vector<Instruction *> ins; int depth = 0; };
+typedef std::vector<const Part *> Group;
+
+// records of one stage with equal keys go into one C-ABI call (same kind / opcode / direction / operand shape)
+int partKey(const Instruction &i) {
+  if (!i.ipHoistG.empty()) return 6000 + (int)i.ipX.size() * 100 + (int)i.ipHoistG.size();                 // 6000+: hoisted key product, by digits and rotations
+  if (i.ops == IP && transformsInside(i)) return 400 + (int)i.ipX.size() * 10 + (int)i.ipY.size();         // 400+: transform x key, by digits and keys
+  if (isKeyProduct(i)) return 300 + (int)i.ipX.size() * 10 + (int)i.ipY.size();                            // 300+: key product, by digits and keys
+  if (i.fusedTensor) return 200;                                                                           // 200: tensor product
+  if (i.fusedSubScale) return (i.fMix ? 203 : 201) + (i.fConvIn.empty() ? 0 : 4);                          // 201 / 203: fused forward transform, plain / merged; 205 / 207: with its conversion
+  if (i.ops == MULT) return 100 + i.opcode;                                                                // 100+: element-wise, by opcode
+  if (i.ops == NTT && i.passthrough) return 100 + EWE_COPY;                                                //       (unfused: a pass-through transform is a copy)
+  if (i.ops == AUTO) return 1000 + (int)i.galois;                                                          // 1000+: automorphism, by element
+  return (int)i.ops + (i.secondOnly ? 5000 : 0);                                                           // below 100: by op; 5000+: second pass only (7b)
 }
 
-// ---------------------------------------------------------------------------------------------------
-// stage -> launch
-// ---------------------------------------------------------------------------------------------------
-void Arch::buildLaunches() {
-  std::vector<Stage> st = stages;
-  if (fuse) fusePasses(st);
-  const unsigned long long LP = (unsigned long long)n * 8;
-  // upstream issues every BCONV group to all MAC ports (include/Driver.h:307-320): same accounting here
-  const unsigned long long bconvPorts = (unsigned long long)config->getValueOr("bconv_num_high", 1) * config->getValueOr("bconv_num_width", 1);
-  const int useMask[9] = {3, 15, 7, 5, 5, 1, 5, 1, 13};
+// what the kernels of a record load: a fused conversion REPLACES the address it would have written (the passes count that one too)
+std::vector<AddrType> loads(const Instruction &i) {
+  std::vector<AddrType> v;
+  for (const Read &r : recordReads(i))
+    if (r.loaded()) v.push_back(r.addr);
+  return v;
+}
 
-  // ---- 1. split every stage into parts one C-ABI call can express (same kind / opcode / direction)
-  struct Part { std::string name; int key; std::vector<Instruction *> ins; int depth = 0; };
-  std::vector<Part> parts;
-  for (const Stage &s : st) {
-    size_t first = parts.size();
-    for (Instruction *i : s.ins) {
-      const bool nip = i->ops == IP && std::find(i->ipCoeff.begin(), i->ipCoeff.end(), 1) != i->ipCoeff.end();
-      int key = !i->ipHoistG.empty() ? 6000 + (int)i->ipX.size() * 100 + (int)i->ipHoistG.size() : nip ? 400 +(int)i->ipX.size() * 10 + (int)i->ipY.size() : i->ops == IP && !i->ipX.empty() ? 300 + (int)i->ipX.size() * 10 + (int)i->ipY.size() : i->fusedTensor ? 200 : i->fusedSubScale ? (i->fMix ? 203 : 201) + (i->fConvIn.empty() ? 0 : 4) : i->ops == MULT ? 100 + i->opcode : (i->ops == NTT && i->passthrough) ? 100 + EWE_COPY : i->ops == AUTO ? 1000 + (int)i->galois : (int)i->ops + (i->secondOnly ? 5000 : 0);
-      size_t p = first;
-      for (; p < parts.size(); ++p)
-        if (parts[p].key == key) break;
-      if (p == parts.size()) parts.push_back(Part{s.name, key, {}, 0});
-      parts[p].ins.push_back(i);
-    }
-  }
-  // ---- 2. dependency depth of every part (RAW, WAR and WAW through limb addresses).  With fuse = 1 parts
-  // of equal depth and kind are coalesced into one launch: the two keys of a ModDown, the beta digits of a
-  // ModUp, D0/D2 of the tensor product ...  The reference dispatches stage by stage (Operation.cpp:947-964);
-  // the stage ORDER it fixes is only a topological order of this graph.
-  auto reads = [&](Instruction *i) {
-    std::vector<AddrType> v;
-    if (i->ops == IP && !i->ipX.empty()) {
-      v = i->ipSrc.empty() ? i->ipX : i->ipSrc;
-      for (size_t j = 0; j < i->ipConvIn.size(); ++j)
-        if (!i->ipConvIn[j].empty()) { v[j] = i->ipConvIn[j][0]; v.insert(v.end(), i->ipConvIn[j].begin() + 1, i->ipConvIn[j].end()); }
-      for (auto &y : i->ipY) v.insert(v.end(), y.begin(), y.end());
-      return v;
-    }
-    if (i->ops == BCONV_STEP2) v.assign(i->operandList.begin(), i->operandList.end() - 1);
-    else if (i->ops == MULT) { for (int b = 0; b < 4; ++b) if (useMask[i->opcode] & (1 << b)) v.push_back(i->operandList[b]); }
-    else v.push_back(i->operandList[0]);
-    if (i->fusedSubScale) { v.push_back(i->fMinuend); if (i->fAddend) v.push_back(i->fAddend); if (i->fMix) v.push_back(i->fMix); }
-    if (!i->fConvIn.empty()) { v[0] = i->fConvIn[0]; v.insert(v.end(), i->fConvIn.begin() + 1, i->fConvIn.end()); }
-    if (i->fusedEpi) { v.push_back(i->fSubFrom); if (i->fAdd) v.push_back(i->fAdd); }
-    return v;
-  };
-  auto writes = [&](Instruction *i) {
-    std::vector<AddrType> v = {i->OutputOperand};
-    v.insert(v.end(), i->extraOutputs.begin(), i->extraOutputs.end());
-    for (size_t j = 0; j < i->ipCoeff.size(); ++j)
-      if (i->ipCoeff[j]) v.push_back(i->ipX[j]);   // first-pass scratch of a digit transformed inside the inner product
-    return v;
-  };
+// dependency depth of every part (RAW, WAR and WAW through limb addresses).  With fuse = 1 parts of equal depth and kind are coalesced
+// into one launch: the two keys of a ModDown, the beta digits of a ModUp, D0/D2 of the tensor product ...  The reference dispatches stage
+// by stage (Operation.cpp:947-964); the stage ORDER it fixes is only a topological order of this graph.
+void assignDepths(std::vector<Part> &parts, bool fuse) {
   std::map<AddrType, int> writerDepth, readerDepth;
   int serial = 0;
   for (Part &p : parts) {
     int d = 0;
     for (Instruction *i : p.ins) {
-      for (AddrType a : reads(i)) { auto w = writerDepth.find(a); if (w != writerDepth.end()) d = std::max(d, w->second + 1); }
-      for (AddrType o : writes(i)) {
-        auto w = writerDepth.find(o); if (w != writerDepth.end()) d = std::max(d, w->second + 1);
-        auto r = readerDepth.find(o); if (r != readerDepth.end()) d = std::max(d, r->second + 1);
+      for (AddrType a : loads(*i)) { auto w = writerDepth.find(a); if (w != writerDepth.end()) d = std::max(d, w->second + 1); }
+      for (const Write &o : recordWrites(*i)) {
+        auto w = writerDepth.find(o.addr); if (w != writerDepth.end()) d = std::max(d, w->second + 1);
+        auto r = readerDepth.find(o.addr); if (r != readerDepth.end()) d = std::max(d, r->second + 1);
       }
     }
     if (!fuse) d = serial++;  // unfused: one launch per stage part, upstream's order
     p.depth = d;
     for (Instruction *i : p.ins) {
-      for (AddrType a : reads(i)) { int &r = readerDepth[a]; r = std::max(r, d); }
-      for (AddrType o : writes(i)) writerDepth[o] = d;
+      for (AddrType a : loads(*i)) { int &r = readerDepth[a]; r = std::max(r, d); }
+      for (const Write &o : recordWrites(*i)) writerDepth[o.addr] = d;
     }
   }
-  // ---- multi-GPU: who holds each limb-poly.  Inputs: by the modulus they were filled for; everything else: by
-  // the modulus of the instruction that writes it.
-  std::map<AddrType, uint32_t> ownerOfAddr;
+}
+
+std::vector<Instruction *> flatten(const Group &group) {
+  std::vector<Instruction *> recs;
+  for (const Part *g : group) recs.insert(recs.end(), g->ins.begin(), g->ins.end());
+  return recs;
+}
+void addUnique(std::vector<int> &v, int x) { if (std::find(v.begin(), v.end(), x) == v.end()) v.push_back(x); }
+}  // namespace
+
+struct Arch::LaunchBuilder {
+  typedef std::unique_ptr<Launch> LaunchPtr;
+  typedef std::vector<LaunchPtr> Launches;
+  typedef const std::vector<Instruction *> &Recs;
+  Arch &A;
+  const unsigned long long LP;            // bytes of a limb-poly
+  const unsigned long long bconvPorts;    // upstream issues every BCONV group to all MAC ports (include/Driver.h:307-320): same accounting here
+  std::map<AddrType, uint32_t> ownerOfAddr;   // multi-GPU: who holds each limb-poly
+  std::map<AddrType, int> slotOfAddr;         // pipelined sharded plan: the exchange mark behind which an address is valid on this rank
+  int nextSlot = 0;
+
+  explicit LaunchBuilder(Arch &a)
+      : A(a), LP((unsigned long long)a.n * 8), bconvPorts((unsigned long long)a.config->getValueOr("bconv_num_high", 1) * a.config->getValueOr("bconv_num_width", 1)) {}
+
+  uint32_t limb(AddrType a) const { return A.limbOf(a); }
+  std::vector<uint32_t> limbs(const std::vector<AddrType> &v) const {
+    std::vector<uint32_t> o;
+    for (AddrType a : v) o.push_back(limb(a));
+    return o;
+  }
+  bool mine(const Instruction *i) const { return A.owner(i->mod_id) == A.rank_; }
+  void append(Launches &v) { for (LaunchPtr &l : v) A.launches.push_back(std::move(l)); }
+  // the conversion of a launch with these inputs and flags, created behind the others if there is none yet (the order of `probs` is the order
+  // of the kernel's work)
+  static Launch::Prob &findOrAddProb(Launch &L, const std::vector<uint32_t> &in, const std::vector<uint32_t> &inMods, bool inPacked, bool epi = false,
+                                     bool epAdd = false, bool *added = nullptr) {
+    if (added) *added = false;
+    for (auto &q : L.probs)
+      if (q.in == in && q.inMods == inMods && q.epi == epi && q.epAdd == epAdd && q.inPacked == inPacked) return q;
+    L.probs.push_back(Launch::Prob{in, inMods, {}, {}});
+    L.probs.back().epi = epi; L.probs.back().epAdd = epAdd; L.probs.back().inPacked = inPacked;
+    if (added) *added = true;
+    return L.probs.back();
+  }
+  // keys, outputs and modulus of a key-product record; (12) a launch reads its evaluation-form digits through ONE automorphism: the records
+  // that have such a digit must agree on it (0 = as stored counts), a record without one must not ask for any
+  void keyProductRecord(Launch &L, const Instruction *i) {
+    for (auto &y : i->ipY) for (AddrType yy : y) L.b.push_back(limb(yy));
+    L.out.push_back(limb(i->OutputOperand));
+    for (AddrType o : i->extraOutputs) L.out.push_back(limb(o));
+    L.mods.push_back(i->mod_id);
+    const bool evalDigit = i->ipCoeff.empty() || std::find(i->ipCoeff.begin(), i->ipCoeff.end(), 0) != i->ipCoeff.end();
+    if (evalDigit ? (xGaloisSet && L.xGalois != i->ipXGalois) : i->ipXGalois != 0)
+      throw std::runtime_error("key product: the records of one launch read their digits through different automorphisms");
+    if (evalDigit) { L.xGalois = i->ipXGalois; xGaloisSet = true; }
+  }
+  bool xGaloisSet = false;   // ... of the launch being built
+
+  void emitGroup(Group group);
+  void shardedTransformTimesKey(const Group &group);
+  void replicateForeignOperands(const Group &group);
+  std::set<int> slotsOf(const Part *g) const;
+  std::vector<Group> splitByExchangeMark(const Group &group) const;
+  void emitCompute(const Group &group, Launches &front, Launches &back);
+  void wrapShardedConversion(LaunchPtr L, Recs recs, Launches &front, Launches &back);
+  void ipHoisted(Launch &L, Recs recs);
+  void nttIp(Launch &L, Recs recs);
+  void ip(Launch &L, Recs recs);
+  void tensor(Launch &L, Recs recs);
+  void nttSubScale(Launch &L, Recs recs);
+  void copy(Launch &L, Recs recs);
+  void transform(Launch &L, Recs recs);
+  void automorphism(Launch &L, Recs recs);
+  void ewe(Launch &L, Recs recs);
+  void bconv(Launch &L, Recs recs);
+};
+
+// (6h) one hoisted key product: digits a [n][T], keys b [r][n][2][T], outputs out [r][n][2] (hm_ip_hoisted_desc)
+void Arch::LaunchBuilder::ipHoisted(Launch &L, Recs recs) {
+  Instruction *f = recs[0];
+  L.kind = Launch::L_IP_HOISTED; L.statKey = "EWE";
+  L.ipTerms = (uint32_t)f->ipX.size(); L.ipOuts = 2; L.hoistG = f->ipHoistG;
+  const size_t R = f->ipHoistG.size();
+  for (Instruction *i : recs) {
+    if (i->ipHoistG != f->ipHoistG) throw std::runtime_error("hoisted key product: the records of one launch rotate by different elements");
+    for (AddrType x : i->ipX) L.a.push_back(limb(x));
+    L.mods.push_back(i->mod_id);
+  }
+  for (size_t r = 0; r < R; ++r)
+    for (Instruction *i : recs)
+      for (size_t k = 0; k < 2; ++k) {
+        for (AddrType y : i->ipY[r * 2 + k]) L.b.push_back(limb(y));
+        L.out.push_back(limb(r == 0 && k == 0 ? i->OutputOperand : i->extraOutputs[r * 2 + k - 1]));
+      }
+  // digits read once, keys read and outputs written once per rotation
+  L.bytes = (unsigned long long)recs.size() * (L.ipTerms + 2 * R * L.ipTerms + 2 * R) * LP;
+}
+
+// transform x key on one GPU (7, 8, 7b): a = source, c = first-pass scratch of every (limb, digit); the digits' conversions as `probs`
+void Arch::LaunchBuilder::nttIp(Launch &L, Recs recs) {
+  L.kind = Launch::L_NTT_IP; L.statKey = "NTT";
+  L.ipTerms = (uint32_t)recs[0]->ipX.size(); L.ipOuts = (uint32_t)recs[0]->ipY.size();
+  unsigned long long lp = 0;
+  for (Instruction *i : recs) {
+    for (size_t j = 0; j < i->ipX.size(); ++j) {
+      L.a.push_back(limb(i->ipSrc[j])); L.c.push_back(limb(i->ipX[j])); L.ipCoeff.push_back(i->ipCoeff[j]);
+      lp += i->ipCoeff[j] ? 3 : 1;       // transformed digit: source read, hand-off written and read; own limb: read
+    }
+    for (size_t j = 0; j < i->ipConvIn.size(); ++j) {   // (8): the digit's conversion runs inside its first pass
+      if (i->ipConvIn[j].empty()) continue;
+      Launch::Prob &pr = findOrAddProb(L, limbs(i->ipConvIn[j]), i->ipConvMods[j], j < i->ipConvPacked.size() && i->ipConvPacked[j]);
+      pr.out.push_back(limb(i->ipX[j]));      // the hand-off limb of (limb, digit)
+      pr.outMods.push_back(i->mod_id);
+      lp -= 1;                                      // the converted limb is neither written nor read: source = the conversion's inputs
+    }
+    keyProductRecord(L, i);
+    L.ipInv.push_back(i->ipInvOut ? 1 : 0);
+    lp += (unsigned long long)L.ipTerms * L.ipOuts + L.ipOuts;
+  }
+  for (auto &q : L.probs) lp += q.in.size();
+  L.bytes = lp * LP;
+}
+
+void Arch::LaunchBuilder::ip(Launch &L, Recs recs) {
+  L.kind = Launch::L_IP; L.statKey = "EWE";
+  L.ipTerms = (uint32_t)recs[0]->ipX.size(); L.ipOuts = (uint32_t)recs[0]->ipY.size();
+  for (Instruction *i : recs) {
+    for (AddrType x : i->ipX) L.a.push_back(limb(x));
+    keyProductRecord(L, i);
+  }
+  L.bytes = (unsigned long long)(L.ipTerms * (1 + L.ipOuts) + L.ipOuts) * LP * recs.size();
+}
+
+void Arch::LaunchBuilder::tensor(Launch &L, Recs recs) {
+  L.kind = Launch::L_TENSOR; L.statKey = "EWE";
+  for (Instruction *i : recs) {  // a = c00 (P), b = c10 (T), c = c01 (R), d = c11 (S)
+    L.a.push_back(limb(i->operandList[0])); L.b.push_back(limb(i->operandList[3]));
+    L.c.push_back(limb(i->operandList[2])); L.d.push_back(limb(i->operandList[1]));
+    L.out.push_back(limb(i->extraOutputs[0])); L.out1.push_back(limb(i->OutputOperand)); L.out2.push_back(limb(i->extraOutputs[1]));
+    L.mods.push_back(i->mod_id);
+  }
+  L.bytes = 7 * LP * recs.size();
+}
+
+// fused forward transform (4, 4b, 9, 12)
+void Arch::LaunchBuilder::nttSubScale(Launch &L, Recs recs) {
+  L.kind = Launch::L_NTT_SUBSCALE; L.statKey = "NTT";
+  bool anyAddend = false;   // the addend is per limb-poly (hrotate: key 0 adds the rotated c0, key 1 nothing)
+  bool anyAddGalois = false;   // (12) ... and key 0's addend through the automorphism
+  for (Instruction *i : recs) { anyAddend |= i->fAddend != 0; anyAddGalois |= i->fAddendGalois != 0; }
+  for (Instruction *i : recs) {
+    L.a.push_back(limb(i->operandList[0])); L.b.push_back(limb(i->fMinuend));
+    if (anyAddend) L.c.push_back(i->fAddend ? limb(i->fAddend) : HM_NO_LIMB);
+    if (anyAddGalois) L.addGalois.push_back(i->fAddendGalois);
+    L.out.push_back(limb(i->OutputOperand)); L.mods.push_back(i->mod_id); L.k.push_back(i->constant);
+    if (recs[0]->fMix) {  // the part key keeps merged and plain records apart
+      L.d.push_back(limb(i->fMix)); L.mixK.push_back(i->fMixConst);
+      if (anyAddend) L.addK.push_back(i->fAddendConst ? i->fAddendConst : 1);
+    }
+  }
+  L.hasK = true;
+  L.bytes = (anyAddend ? 4 : 3) * LP * recs.size();
+  for (Instruction *i : recs) {   // (9): the conversion of this limb-poly runs inside its first pass
+    if (i->fConvIn.empty()) continue;
+    bool added;
+    Launch::Prob &pr = findOrAddProb(L, limbs(i->fConvIn), i->fConvMods, i->inPacked, false, false, &added);
+    if (added) L.bytes += LP * pr.in.size();
+    pr.out.push_back(limb(i->OutputOperand));   // the hand-off lands in the output limb
+    pr.outMods.push_back(i->mod_id);
+    L.bytes -= LP;                                  // the converted limb-poly is neither written nor read
+  }
+}
+
+// unfused mode: a pass-through transform materialises its copy
+void Arch::LaunchBuilder::copy(Launch &L, Recs recs) {
+  L.kind = Launch::L_EWE; L.opcode = EWE_COPY; L.statKey = "EWE";
+  for (Instruction *i : recs) { L.a.push_back(limb(i->operandList[0])); L.out.push_back(limb(i->OutputOperand)); L.mods.push_back(i->mod_id); }
+  L.bytes = 2 * LP * recs.size();
+}
+
+void Arch::LaunchBuilder::transform(Launch &L, Recs recs) {
+  Instruction *f = recs[0];
+  L.kind = f->ops == NTT ? Launch::L_NTT : Launch::L_INTT; L.statKey = "NTT";
+  L.secondOnly = f->secondOnly;
+  bool anyInGalois = false;
+  for (Instruction *i : recs) anyInGalois |= i->inGalois != 0;
+  for (Instruction *i : recs) {
+    if (anyInGalois) L.inGalois.push_back(i->inGalois);
+    L.a.push_back(limb(i->operandList[0])); L.out.push_back(limb(i->OutputOperand)); L.mods.push_back(i->mod_id);
+    L.k.push_back(i->hasConstant ? i->constant : 1);
+    L.hasK |= i->hasConstant;
+    if (f->ops == INTT) L.outPacked.push_back(i->packedOut ? 1 : 0);
+  }
+  L.bytes = 2 * LP * recs.size();
+}
+
+void Arch::LaunchBuilder::automorphism(Launch &L, Recs recs) {
+  L.kind = Launch::L_AUTO; L.statKey = "AUTO"; L.galois = recs[0]->galois;
+  for (Instruction *i : recs) { L.a.push_back(limb(i->operandList[0])); L.out.push_back(limb(i->OutputOperand)); }
+  L.bytes = 2 * LP * recs.size();
+}
+
+void Arch::LaunchBuilder::ewe(Launch &L, Recs group) {
+  L.kind = Launch::L_EWE; L.opcode = group[0]->opcode; L.statKey = "EWE";
+  const int m = eweOperandMask(group[0]->opcode);
+  int nops = 1;
+  for (int b = 0; b < 4; ++b) nops += (m >> b) & 1;
+  // entries of one modulus side by side: records that share an operand (pmult: c0 x pt and c1 x pt of a limb) then sit 128 workgroups apart
+  // in dispatch order, on the same XCD, and the second reader finds the shared limb-poly in L2 instead of fetching it again
+  std::vector<Instruction *> recs = group;
+  std::stable_sort(recs.begin(), recs.end(), [](const Instruction *x, const Instruction *y) { return x->mod_id < y->mod_id; });
+  for (Instruction *i : recs) {
+    auto get = [&](int b) { return (m & (1 << b)) ? limb(i->operandList[b]) : 0u; };
+    L.a.push_back(get(0)); L.b.push_back(get(1)); L.c.push_back(get(2)); L.d.push_back(get(3));
+    L.out.push_back(limb(i->OutputOperand)); L.mods.push_back(i->mod_id);
+    L.k.push_back(i->hasConstant ? i->constant : 0);
+    L.hasK |= i->hasConstant;
+  }
+  L.bytes = (unsigned long long)nops * LP * recs.size();
+}
+
+// one conversion per distinct (input limbs, epilogue form, input form)
+void Arch::LaunchBuilder::bconv(Launch &L, Recs recs) {
+  L.kind = Launch::L_BCONV; L.statKey = "BCONV";
+  for (Instruction *i : recs) {
+    std::vector<AddrType> convIn;
+    for (size_t x = 0; x + 1 < i->operandList.size(); ++x) convIn.push_back(i->operandList[x]);
+    Launch::Prob &pr = findOrAddProb(L, limbs(convIn), i->inMods, i->inPacked, i->fusedEpi, i->fAdd != 0);
+    pr.out.push_back(limb(i->OutputOperand));
+    pr.outMods.push_back(i->mod_id);
+    if (i->fusedEpi) {   // (10): out = (fSubFrom - conv) * k [+ fAdd]
+      pr.epA.push_back(limb(i->fSubFrom)); pr.epK.push_back(i->constant);
+      if (i->fAdd) pr.epB.push_back(limb(i->fAdd));
+      L.bytes += LP * (i->fAdd ? 2 : 1);
+    }
+  }
+  if (A.world_ > 1 && A.batch_ > 1 && !A.shardGather) {  // sharded batch: the ops of the batch share the exchanges around the conversion
+    const uint32_t per = (uint32_t)A.limbIndex.size();
+    const size_t p0 = L.probs.size();
+    for (uint32_t c = 1; c < A.batch_; ++c)
+      for (size_t i = 0; i < p0; ++i) {
+        Launch::Prob q = L.probs[i];
+        for (uint32_t &x : q.in) x += c * per;
+        for (uint32_t &x : q.out) x += c * per;
+        L.probs.push_back(q);
+      }
+    L.refInstructions *= A.batch_;
+  }
+  for (auto &q : L.probs) L.bytes += LP * (q.in.size() + q.out.size());
+}
+
+// all-to-all plan: limb-sharded -> coefficient slices -> convert every output on this rank's slice -> limb-sharded
+void Arch::LaunchBuilder::wrapShardedConversion(LaunchPtr L, Recs recs, Launches &front, Launches &back) {
+  LaunchPtr XI = std::make_unique<Launch>(), XO = std::make_unique<Launch>();
+  XI->kind = Launch::L_EXCH_IN; XO->kind = Launch::L_EXCH_OUT; XI->statKey = XO->statKey = "XCHG";
+  XI->name = L->name + ":limbs->slices"; XO->name = L->name + ":slices->limbs";
+  for (auto &q : L->probs) {
+    for (size_t x = 0; x < q.in.size(); ++x)
+      if (std::find(XI->exLimbs.begin(), XI->exLimbs.end(), q.in[x]) == XI->exLimbs.end()) { XI->exLimbs.push_back(q.in[x]); XI->exOwners.push_back(A.owner(q.inMods[x])); }
+    for (size_t x = 0; x < q.out.size(); ++x) { XO->exLimbs.push_back(q.out[x]); XO->exOwners.push_back(A.owner(q.outMods[x])); }
+  }
+  std::vector<uint32_t> inRows(XI->exLimbs.size()), outRows(XO->exLimbs.size());
+  hm_slice_rows(XI->exOwners.data(), (uint32_t)inRows.size(), A.world_, inRows.data());
+  hm_slice_rows(XO->exOwners.data(), (uint32_t)outRows.size(), A.world_, outRows.data());
+  size_t o = 0;
+  for (auto &q : L->probs) {
+    for (uint32_t &x : q.in) x = inRows[std::find(XI->exLimbs.begin(), XI->exLimbs.end(), x) - XI->exLimbs.begin()];
+    for (uint32_t &x : q.out) x = outRows[o++];
+  }
+  L->logLen = XI->logLen = XO->logLen = A.logN - (uint32_t)__builtin_ctz(A.world_);
+  XI->bytes = LP * XI->exLimbs.size() / A.world_;
+  XO->bytes = LP * XO->exLimbs.size() / A.world_;
+  L->bytes /= A.world_;
+  if (A.pipelineDigits) {
+    XI->waitSlots = L->waitSlots;   // (its inputs come from the compute stream; marks matter only if an exchange produced them)
+    XI->recordSlot = nextSlot++;
+    L->waitSlots = {XI->recordSlot};
+    XO->recordSlot = nextSlot++;
+    for (Instruction *i : recs) slotOfAddr[i->OutputOperand] = XO->recordSlot;
+  }
+  L->xin = XI.get(); L->xout = XO.get();
+  A.algBytes += L->bytes;
+  (A.pipelineDigits ? front : back).push_back(std::move(XI));
+  back.push_back(std::move(L));
+  back.push_back(std::move(XO));
+}
+
+// one launch for the records of a group (all of one part key)
+void Arch::LaunchBuilder::emitCompute(const Group &group, Launches &front, Launches &back) {
+  const std::vector<Instruction *> recs = flatten(group);
+  Instruction *f = recs[0];
+  LaunchPtr L = std::make_unique<Launch>();
+  xGaloisSet = false;
+  if (A.pipelineDigits)
+    for (const Part *g : group) for (int sl : slotsOf(g)) addUnique(L->waitSlots, sl);
+  for (const Part *g : group) L->name += (L->name.empty() ? "" : "+") + g->name;
+  for (Instruction *i : recs) L->refInstructions += i->refInstructions * (i->ops == BCONV_STEP2 ? bconvPorts : 1ull) + i->refExtra;
+  if (f->ops == IP && !f->ipHoistG.empty()) ipHoisted(*L, recs);
+  else if (f->ops == IP && transformsInside(*f)) nttIp(*L, recs);
+  else if (isKeyProduct(*f)) ip(*L, recs);
+  else if (f->fusedTensor) tensor(*L, recs);
+  else if (f->fusedSubScale) nttSubScale(*L, recs);
+  else if (f->ops == NTT && f->passthrough) copy(*L, recs);
+  else if (f->ops == NTT || f->ops == INTT) transform(*L, recs);
+  else if (f->ops == AUTO) automorphism(*L, recs);
+  else if (f->ops == MULT) ewe(*L, recs);
+  else if (f->ops == BCONV_STEP2) {
+    bconv(*L, recs);
+    if (A.world_ > 1 && !A.shardGather) return wrapShardedConversion(std::move(L), recs, front, back);
+  } else throw std::runtime_error("no unit executes op " + f->GetOpName());
+  A.algBytes += L->bytes;
+  back.push_back(std::move(L));
+}
+
+// sharded ModUp with the fused kernels (round 4).  Per digit j: limbs -> COLUMN slices of the digit's limbs (all-to-all), conversion +
+// first pass on this rank's columns for EVERY output limb (hm_bconv_col), column slices -> limbs of the first-pass hand-off
+// (all-to-all back); then ONE transform x key launch over this rank's extended limbs (second pass + MAC with both keys).
+// Every rank issues every exchange (the lists come from the global graph), also a rank that owns no extended limb.
+void Arch::LaunchBuilder::shardedTransformTimesKey(const Group &group) {
+  const std::vector<Instruction *> recs = flatten(group);
+  Launch digs;   // per digit (probs): in = the conversion's inputs, out = the hand-off limbs of every extended limb
+  for (Instruction *i : recs)
+    for (size_t j = 0; j < i->ipConvIn.size(); ++j) {
+      if (i->ipConvIn[j].empty()) continue;
+      Launch::Prob &dg = findOrAddProb(digs, limbs(i->ipConvIn[j]), i->ipConvMods[j], false);
+      dg.out.push_back(limb(i->ipX[j]));
+      dg.outMods.push_back(i->mod_id);
+    }
+  const uint32_t per = (uint32_t)A.limbIndex.size();
+  Launches front, back;
+  std::vector<int> outSlots;
+  const uint32_t nTiles = cap(A.logN, "cap_col_slices") / A.world_;   // column tiles of a limb-poly per rank
+  for (size_t dj = 0; dj < digs.probs.size(); ++dj) {
+    const Launch::Prob &dg = digs.probs[dj];
+    LaunchPtr XI = std::make_unique<Launch>(), BC = std::make_unique<Launch>(), XO = std::make_unique<Launch>();
+    XI->kind = Launch::L_EXCH_IN_COL; BC->kind = Launch::L_BCONV_COL; XO->kind = Launch::L_EXCH_OUT_COL;
+    XI->statKey = XO->statKey = "XCHG"; BC->statKey = "BCONV";
+    BC->name = "ModUp_BCONV_COL_(" + std::to_string(dj) + ")";
+    XI->name = BC->name + ":limbs->columns"; XO->name = BC->name + ":columns->limbs";
+    for (uint32_t c = 0; c < A.batch_; ++c) {   // the ops of a batch share the exchanges
+      for (size_t x = 0; x < dg.in.size(); ++x) { XI->exLimbs.push_back(dg.in[x] + c * per); XI->exOwners.push_back(A.owner(dg.inMods[x])); }
+      for (size_t x = 0; x < dg.out.size(); ++x) { XO->exLimbs.push_back(dg.out[x] + c * per); XO->exOwners.push_back(A.owner(dg.outMods[x])); }
+    }
+    std::vector<uint32_t> inRows(XI->exLimbs.size()), outRows(XO->exLimbs.size());
+    hm_slice_rows(XI->exOwners.data(), (uint32_t)inRows.size(), A.world_, inRows.data());
+    hm_slice_rows(XO->exOwners.data(), (uint32_t)outRows.size(), A.world_, outRows.data());
+    for (uint32_t c = 0; c < A.batch_; ++c) {
+      Launch::Prob q{{}, dg.inMods, {}, dg.outMods};
+      for (size_t x = 0; x < dg.in.size(); ++x) q.in.push_back(inRows[c * dg.in.size() + x]);
+      for (size_t x = 0; x < dg.out.size(); ++x) q.out.push_back(outRows[c * dg.out.size() + x]);
+      BC->probs.push_back(q);
+    }
+    BC->galois = A.rank_ * nTiles;    // first column tile of this rank's slice
+    BC->logLen = nTiles;            // ... and how many
+    BC->refInstructions = 0;        // (accounted on the transform x key launch, as in the one-GPU plan)
+    XI->bytes = LP * XI->exLimbs.size() / A.world_;
+    XO->bytes = LP * XO->exLimbs.size() / A.world_;
+    BC->bytes = (XI->bytes + XO->bytes);
+    if (A.pipelineDigits) {
+      XI->recordSlot = nextSlot++;
+      BC->waitSlots = {XI->recordSlot};
+      XO->recordSlot = nextSlot++;
+    }
+    outSlots.push_back(XO->recordSlot);
+    BC->xin = XI.get(); BC->xout = XO.get();
+    A.algBytes += BC->bytes;
+    (A.pipelineDigits ? front : back).push_back(std::move(XI));
+    back.push_back(std::move(BC));
+    back.push_back(std::move(XO));
+  }
+  // this rank's extended limbs: the one-GPU launch's operands, but a converted digit arrives as its first-pass hand-off (ipCoeff 2) and no
+  // conversion runs inside
+  LaunchPtr L = std::make_unique<Launch>();
+  xGaloisSet = false;
+  L->kind = Launch::L_NTT_IP; L->statKey = "NTT";
+  L->ipTerms = (uint32_t)recs[0]->ipX.size(); L->ipOuts = (uint32_t)recs[0]->ipY.size();
+  unsigned long long lp = 0;
+  for (const Part *g : group) {
+    bool any = false;
+    for (Instruction *i : g->ins) {
+      if (!mine(i)) continue;
+      L->refInstructions += i->refInstructions;
+      any = true;
+      for (size_t j = 0; j < i->ipX.size(); ++j) {
+        const bool conv = j < i->ipConvIn.size() && !i->ipConvIn[j].empty();
+        L->a.push_back(limb(i->ipSrc[j])); L->c.push_back(limb(i->ipX[j]));
+        L->ipCoeff.push_back(conv ? 2 : i->ipCoeff[j]);
+        lp += 1;
+      }
+      keyProductRecord(*L, i);
+      lp += (unsigned long long)L->ipTerms * L->ipOuts + L->ipOuts;
+    }
+    if (any) L->name += (L->name.empty() ? "" : "+") + g->name;
+  }
+  L->bytes = lp * LP;
+  if (A.pipelineDigits) for (int sl : outSlots) L->waitSlots.push_back(sl);
+  append(front);
+  append(back);
+  // (a rank without extended limbs still waits for nothing: its exchanges are complete on their own stream)
+  if (!L->mods.empty()) { A.algBytes += L->bytes; A.launches.push_back(std::move(L)); }
+}
+
+// operands written on another rank (the rescale's r = INTT(x_last); with the gather plan also the conversions' inputs): replicate them
+// first — every rank derives the same list from the global graph, so the collective is entered by all
+void Arch::LaunchBuilder::replicateForeignOperands(const Group &group) {
+  std::vector<AddrType> need;
+  for (Instruction *i : flatten(group))
+    for (AddrType a : loads(*i)) {
+      auto oo = ownerOfAddr.find(a);
+      if (oo != ownerOfAddr.end() && oo->second != A.owner(i->mod_id) && std::find(need.begin(), need.end(), a) == need.end()) need.push_back(a);
+    }
+  if (need.empty()) return;
+  LaunchPtr R = std::make_unique<Launch>();
+  R->kind = Launch::L_REPLICATE; R->statKey = "XCHG"; R->name = "replicate";
+  for (AddrType a : need) { R->exLimbs.push_back(limb(a)); R->exOwners.push_back(ownerOfAddr[a]); }
+  R->bytes = LP * need.size();
+  if (A.pipelineDigits) {
+    for (AddrType a : need) { auto it = slotOfAddr.find(a); if (it != slotOfAddr.end()) addUnique(R->waitSlots, it->second); }
+    R->recordSlot = nextSlot++;
+    for (AddrType a : need) slotOfAddr[a] = R->recordSlot;
+  }
+  A.launches.push_back(std::move(R));
+}
+
+std::set<int> Arch::LaunchBuilder::slotsOf(const Part *g) const {
+  std::set<int> ss;
+  for (Instruction *i : g->ins)
+    for (AddrType a : loads(*i)) { auto it = slotOfAddr.find(a); if (it != slotOfAddr.end()) ss.insert(it->second); }
+  return ss;
+}
+
+// pipelined sharded plan: parts that depend on different exchanges (digit j's transforms read what exchange XO_j delivered)
+// become launches of their own, each waiting for its own mark; the conversions are split by input basis (= by digit; the two
+// keys of a ModDown share theirs and stay together).  Exchange-in launches of all digits are issued first.
+std::vector<Group> Arch::LaunchBuilder::splitByExchangeMark(const Group &group) const {
+  std::vector<Group> subgroups;
+  std::vector<std::set<int>> sigs;
+  std::vector<std::vector<uint32_t>> bases;
+  const bool isConv = group[0]->ins[0]->ops == BCONV_STEP2;
+  for (const Part *g : group) {
+    const std::set<int> sg = slotsOf(g);
+    const std::vector<uint32_t> bs = isConv ? g->ins[0]->inMods : std::vector<uint32_t>();
+    size_t k = 0;
+    for (; k < subgroups.size(); ++k) if (sigs[k] == sg && bases[k] == bs) break;
+    if (k == subgroups.size()) { subgroups.emplace_back(); sigs.push_back(sg); bases.push_back(bs); }
+    subgroups[k].push_back(g);
+  }
+  return subgroups;
+}
+
+// the parts of one depth and key -> launches
+void Arch::LaunchBuilder::emitGroup(Group group) {
+  Instruction *f = group[0]->ins[0];
+  if (A.world_ > 1 && f->ops == IP && !A.shardGather) {
+    bool fusedConversion = false;
+    for (Instruction *i : flatten(group))
+      for (auto &cin : i->ipConvIn) fusedConversion |= !cin.empty();
+    if (fusedConversion) return shardedTransformTimesKey(group);
+  }
+  std::vector<Part> mineParts;
+  if (A.world_ > 1 && (f->ops != BCONV_STEP2 || A.shardGather)) {
+    replicateForeignOperands(group);
+    for (const Part *g : group) {   // keep the instructions whose modulus this rank owns
+      Part m{g->name, g->key, {}, g->depth};
+      for (Instruction *i : g->ins)
+        if (mine(i)) m.ins.push_back(i);
+      if (!m.ins.empty()) mineParts.push_back(m);
+    }
+    group.clear();
+    for (const Part &m : mineParts) group.push_back(&m);
+    if (group.empty()) return;
+  }
+  Launches front, back;
+  for (const Group &sub : A.pipelineDigits ? splitByExchangeMark(group) : std::vector<Group>{group}) emitCompute(sub, front, back);
+  append(front);
+  append(back);
+}
+
+void Arch::buildLaunches() {
+  std::vector<Stage> st = stages;
+  if (fuse) fusePasses(st);
+  // 1. split every stage into parts one C-ABI call can express
+  std::vector<Part> parts;
+  for (const Stage &s : st) {
+    const size_t first = parts.size();
+    for (Instruction *i : s.ins) {
+      const int key = partKey(*i);
+      size_t p = first;
+      while (p < parts.size() && parts[p].key != key) ++p;
+      if (p == parts.size()) parts.push_back(Part{s.name, key, {}, 0});
+      parts[p].ins.push_back(i);
+    }
+  }
+  // 2. dependency depth
+  assignDepths(parts, fuse);
+  LaunchBuilder b(*this);
+  // multi-GPU: who holds each limb-poly.  Inputs: by the modulus they were filled for; everything else: by the modulus of the
+  // instruction that writes it.
   if (world_ > 1) {
     for (const InputFill &f : fills)
-      for (size_t i = 0; i < f.addrs.size(); ++i) ownerOfAddr[f.addrs[i]] = owner(f.mods[i]);
+      for (size_t i = 0; i < f.addrs.size(); ++i) b.ownerOfAddr[f.addrs[i]] = owner(f.mods[i]);
     for (const Part &p : parts)
       for (Instruction *i : p.ins)
-        for (AddrType o : writes(i)) ownerOfAddr[o] = owner(i->mod_id);
+        for (const Write &o : recordWrites(*i)) b.ownerOfAddr[o.addr] = owner(i->mod_id);
   }
-  const uint32_t logLen = logN - (uint32_t)__builtin_ctz(world_);
-  // ---- 3. coalesce and emit, level by level
-  std::map<AddrType, int> slotOfAddr;   // pipelined sharded plan: the exchange mark behind which an address is valid on this rank
-  int nextSlot = 0;
+  // 3. coalesce and emit, level by level: the parts of equal depth and key, in the order of the first of them
   int maxDepth = 0;
   for (const Part &p : parts) maxDepth = std::max(maxDepth, p.depth);
   for (int d = 0; d <= maxDepth; ++d) {
     std::vector<int> keysDone;
     for (size_t pi = 0; pi < parts.size(); ++pi) {
-      if (parts[pi].depth != d) continue;
-      const int key = parts[pi].key;
-      if (std::find(keysDone.begin(), keysDone.end(), key) != keysDone.end()) continue;
-      keysDone.push_back(key);
-      std::vector<const Part *> group;
+      if (parts[pi].depth != d || std::find(keysDone.begin(), keysDone.end(), parts[pi].key) != keysDone.end()) continue;
+      keysDone.push_back(parts[pi].key);
+      Group group;
       for (size_t pj = pi; pj < parts.size(); ++pj)
-        if (parts[pj].depth == d && parts[pj].key == key) group.push_back(&parts[pj]);
-      Instruction *f = group[0]->ins[0];
-      std::vector<Part> mineParts;
-      bool nipSharded = false;
-      if (world_ > 1 && f->ops == IP && !shardGather)
-        for (const Part *g : group)
-          for (Instruction *i : g->ins)
-            for (auto &cin : i->ipConvIn) nipSharded |= !cin.empty();
-      if (nipSharded) {
-        // ---- sharded ModUp with the fused kernels (round 4).  Per digit j: limbs -> COLUMN slices of the digit's limbs (all-to-all), conversion +
-        // first pass on this rank's columns for EVERY output limb (hm_bconv_col), column slices -> limbs of the first-pass hand-off
-        // (all-to-all back); then ONE transform x key launch over this rank's extended limbs (second pass + MAC with both keys).
-        // Every rank issues every exchange (the lists come from the global graph), also a rank that owns no extended limb.
-        struct Dig { std::vector<uint32_t> in, inMods, hand, handMods; };
-        std::vector<Dig> digs;
-        for (const Part *g : group)
-          for (Instruction *i : g->ins)
-            for (size_t j = 0; j < i->ipConvIn.size(); ++j) {
-              if (i->ipConvIn[j].empty()) continue;
-              std::vector<uint32_t> in;
-              for (AddrType x : i->ipConvIn[j]) in.push_back(limbOf(x));
-              Dig *dg = nullptr;
-              for (auto &q : digs) if (q.in == in && q.inMods == i->ipConvMods[j]) dg = &q;
-              if (!dg) { digs.push_back(Dig{in, i->ipConvMods[j], {}, {}}); dg = &digs.back(); }
-              dg->hand.push_back(limbOf(i->ipX[j]));
-              dg->handMods.push_back(i->mod_id);
-            }
-        const uint32_t per = (uint32_t)limbIndex.size();
-        std::vector<Launch *> front, back;
-        std::vector<int> outSlots;
-        const uint32_t nTiles = cap(logN, "cap_col_slices") / world_;   // column tiles of a limb-poly per rank
-        for (size_t dj = 0; dj < digs.size(); ++dj) {
-          Dig &dg = digs[dj];
-          Launch *XI = new Launch, *BC = new Launch, *XO = new Launch;
-          XI->kind = Launch::L_EXCH_IN_COL; BC->kind = Launch::L_BCONV_COL; XO->kind = Launch::L_EXCH_OUT_COL;
-          XI->statKey = XO->statKey = "XCHG"; BC->statKey = "BCONV";
-          BC->name = "ModUp_BCONV_COL_(" + std::to_string(dj) + ")";
-          XI->name = BC->name + ":limbs->columns"; XO->name = BC->name + ":columns->limbs";
-          for (uint32_t c = 0; c < batch_; ++c) {   // the ops of a batch share the exchanges
-            for (size_t x = 0; x < dg.in.size(); ++x) { XI->exLimbs.push_back(dg.in[x] + c * per); XI->exOwners.push_back(owner(dg.inMods[x])); }
-            for (size_t x = 0; x < dg.hand.size(); ++x) { XO->exLimbs.push_back(dg.hand[x] + c * per); XO->exOwners.push_back(owner(dg.handMods[x])); }
-          }
-          std::vector<uint32_t> inRows(XI->exLimbs.size()), outRows(XO->exLimbs.size());
-          hm_slice_rows(XI->exOwners.data(), (uint32_t)inRows.size(), world_, inRows.data());
-          hm_slice_rows(XO->exOwners.data(), (uint32_t)outRows.size(), world_, outRows.data());
-          for (uint32_t c = 0; c < batch_; ++c) {
-            Launch::Prob q{{}, dg.inMods, {}, dg.handMods};
-            for (size_t x = 0; x < dg.in.size(); ++x) q.in.push_back(inRows[c * dg.in.size() + x]);
-            for (size_t x = 0; x < dg.hand.size(); ++x) q.out.push_back(outRows[c * dg.hand.size() + x]);
-            BC->probs.push_back(q);
-          }
-          BC->galois = rank_ * nTiles;    // first column tile of this rank's slice
-          BC->logLen = nTiles;            // ... and how many
-          BC->refInstructions = 0;        // (accounted on the transform x key launch, as in the one-GPU plan)
-          XI->bytes = LP * XI->exLimbs.size() / world_;
-          XO->bytes = LP * XO->exLimbs.size() / world_;
-          BC->bytes = (XI->bytes + XO->bytes);
-          if (pipelineDigits) {
-            XI->recordSlot = nextSlot++;
-            BC->waitSlots = {XI->recordSlot};
-            XO->recordSlot = nextSlot++;
-          }
-          outSlots.push_back(XO->recordSlot);
-          BC->xin = XI; BC->xout = XO;
-          (pipelineDigits ? front : back).push_back(XI);
-          back.push_back(BC);
-          back.push_back(XO);
-          algBytes += BC->bytes;
-        }
-        // this rank's extended limbs
-        Launch *L = new Launch;
-        L->kind = Launch::L_NTT_IP; L->statKey = "NTT";
-        L->ipTerms = (uint32_t)f->ipX.size(); L->ipOuts = (uint32_t)f->ipY.size();
-        unsigned long long lp = 0;
-        for (const Part *g : group) {
-          bool any = false;
-          for (Instruction *i : g->ins) {
-            L->refInstructions += owner(i->mod_id) == rank_ ? i->refInstructions : 0;
-            if (owner(i->mod_id) != rank_) continue;
-            any = true;
-            for (size_t j = 0; j < i->ipX.size(); ++j) {
-              const bool conv = j < i->ipConvIn.size() && !i->ipConvIn[j].empty();
-              L->a.push_back(limbOf(i->ipSrc[j])); L->c.push_back(limbOf(i->ipX[j]));
-              L->ipCoeff.push_back(conv ? 2 : i->ipCoeff[j]);
-              lp += i->ipCoeff[j] ? 1 : 1;
-            }
-            for (auto &y : i->ipY) for (AddrType yy : y) L->b.push_back(limbOf(yy));
-            L->out.push_back(limbOf(i->OutputOperand));
-            for (AddrType o : i->extraOutputs) L->out.push_back(limbOf(o));
-            L->mods.push_back(i->mod_id);
-            if (i->ipXGalois) L->xGalois = i->ipXGalois;   // (12)
-            lp += (unsigned long long)L->ipTerms * L->ipOuts + L->ipOuts;
-          }
-          if (any) L->name += (L->name.empty() ? "" : "+") + g->name;
-        }
-        L->bytes = lp * LP;
-        if (pipelineDigits) for (int sl : outSlots) L->waitSlots.push_back(sl);
-        launches.insert(launches.end(), front.begin(), front.end());
-        launches.insert(launches.end(), back.begin(), back.end());
-        if (!L->mods.empty()) { algBytes += L->bytes; launches.push_back(L); }
-        else {   // a rank without extended limbs still waits for nothing: its exchanges are complete on their own stream
-          delete L;
-        }
-        continue;
-      }
-      if (world_ > 1 && (f->ops != BCONV_STEP2 || shardGather)) {
-        // (a) operands written on another rank (the rescale's r = INTT(x_last); with the gather plan also the conversions' inputs): replicate them first — every
-        //     rank derives the same list from the global graph, so the collective is entered by all
-        std::vector<AddrType> need;
-        for (const Part *g : group)
-          for (Instruction *i : g->ins)
-            for (AddrType a : reads(i)) {
-              auto oo = ownerOfAddr.find(a);
-              if (oo != ownerOfAddr.end() && oo->second != owner(i->mod_id) && std::find(need.begin(), need.end(), a) == need.end()) need.push_back(a);
-            }
-        if (!need.empty()) {
-          Launch *R = new Launch;
-          R->kind = Launch::L_REPLICATE; R->statKey = "XCHG"; R->name = "replicate";
-          for (AddrType a : need) { R->exLimbs.push_back(limbOf(a)); R->exOwners.push_back(ownerOfAddr[a]); }
-          R->bytes = LP * need.size();
-          if (pipelineDigits) {
-            for (AddrType a : need) { auto it = slotOfAddr.find(a); if (it != slotOfAddr.end() && std::find(R->waitSlots.begin(), R->waitSlots.end(), it->second) == R->waitSlots.end()) R->waitSlots.push_back(it->second); }
-            R->recordSlot = nextSlot++;
-            for (AddrType a : need) slotOfAddr[a] = R->recordSlot;
-          }
-          launches.push_back(R);
-        }
-        // (b) keep the instructions whose modulus this rank owns
-        for (const Part *g : group) {
-          Part m{g->name, g->key, {}, g->depth};
-          for (Instruction *i : g->ins)
-            if (owner(i->mod_id) == rank_) m.ins.push_back(i);
-          if (!m.ins.empty()) mineParts.push_back(m);
-        }
-        group.clear();
-        for (const Part &m : mineParts) group.push_back(&m);
-        if (group.empty()) continue;
-        f = group[0]->ins[0];
-      }
-      // pipelined sharded plan: parts that depend on different exchanges (digit j's transforms read what exchange XO_j delivered)
-      // become launches of their own, each waiting for its own mark; the conversions are split by input basis (= by digit; the two
-      // keys of a ModDown share theirs and stay together).  Exchange-in launches of all digits are issued first.
-      std::vector<std::vector<const Part *>> subgroups;
-      auto slotsOf = [&](const Part *g) {
-        std::set<int> ss;
-        for (Instruction *i : g->ins)
-          for (AddrType a : reads(i)) { auto it = slotOfAddr.find(a); if (it != slotOfAddr.end()) ss.insert(it->second); }
-        return ss;
-      };
-      if (pipelineDigits) {
-        std::vector<std::set<int>> sigs;
-        std::vector<std::vector<uint32_t>> bases;
-        for (const Part *g : group) {
-          const std::set<int> sg = slotsOf(g);
-          const std::vector<uint32_t> bs = f->ops == BCONV_STEP2 ? g->ins[0]->inMods : std::vector<uint32_t>();
-          size_t k = 0;
-          for (; k < subgroups.size(); ++k) if (sigs[k] == sg && bases[k] == bs) break;
-          if (k == subgroups.size()) { subgroups.emplace_back(); sigs.push_back(sg); bases.push_back(bs); }
-          subgroups[k].push_back(g);
-        }
-      } else subgroups.push_back(group);
-      std::vector<Launch *> front, back;
-      for (const std::vector<const Part *> &subgroup : subgroups) {
-      const std::vector<const Part *> &group = subgroup;
-      f = group[0]->ins[0];
-      Launch *L = new Launch;
-      if (pipelineDigits)
-        for (const Part *g : group) for (int sl : slotsOf(g)) if (std::find(L->waitSlots.begin(), L->waitSlots.end(), sl) == L->waitSlots.end()) L->waitSlots.push_back(sl);
-      for (const Part *g : group) L->name += (L->name.empty() ? "" : "+") + g->name;
-      size_t count = 0;
-      for (const Part *g : group)
-        for (Instruction *i : g->ins) { L->refInstructions += i->refInstructions * (i->ops == BCONV_STEP2 ? bconvPorts : 1ull) + i->refExtra; ++count; }
-      if (f->ops == IP && !f->ipHoistG.empty()) {
-        // (6h) one hoisted key product: digits a [n][T], keys b [r][n][2][T], outputs out [r][n][2] (hm_ip_hoisted_desc)
-        L->kind = Launch::L_IP_HOISTED; L->statKey = "EWE";
-        L->ipTerms = (uint32_t)f->ipX.size(); L->ipOuts = 2; L->hoistG = f->ipHoistG;
-        const size_t R = f->ipHoistG.size();
-        std::vector<Instruction *> recs;
-        for (const Part *g : group) recs.insert(recs.end(), g->ins.begin(), g->ins.end());
-        for (Instruction *i : recs) {
-          if (i->ipHoistG != f->ipHoistG) { delete L; throw std::runtime_error("hoisted key product: the records of one launch rotate by different elements"); }
-          for (AddrType x : i->ipX) L->a.push_back(limbOf(x));
-          L->mods.push_back(i->mod_id);
-        }
-        for (size_t r = 0; r < R; ++r)
-          for (Instruction *i : recs)
-            for (size_t k = 0; k < 2; ++k) {
-              for (AddrType y : i->ipY[r * 2 + k]) L->b.push_back(limbOf(y));
-              L->out.push_back(limbOf(r == 0 && k == 0 ? i->OutputOperand : i->extraOutputs[r * 2 + k - 1]));
-            }
-        // digits read once, keys read and outputs written once per rotation
-        L->bytes = (unsigned long long)recs.size() * (L->ipTerms + 2 * R * L->ipTerms + 2 * R) * LP;
-      } else if (f->ops == IP && std::find(f->ipCoeff.begin(), f->ipCoeff.end(), 1) != f->ipCoeff.end()) {
-        L->kind = Launch::L_NTT_IP; L->statKey = "NTT";
-        L->ipTerms = (uint32_t)f->ipX.size(); L->ipOuts = (uint32_t)f->ipY.size();
-        unsigned long long lp = 0;
-        for (const Part *g : group)
-          for (Instruction *i : g->ins) {
-            for (size_t j = 0; j < i->ipX.size(); ++j) {
-              L->a.push_back(limbOf(i->ipSrc[j])); L->c.push_back(limbOf(i->ipX[j])); L->ipCoeff.push_back(i->ipCoeff[j]);
-              lp += i->ipCoeff[j] ? 3 : 1;       // transformed digit: source read, hand-off written and read; own limb: read
-            }
-            for (size_t j = 0; j < i->ipConvIn.size(); ++j) {   // (8): the digit's conversion runs inside its first pass
-              if (i->ipConvIn[j].empty()) continue;
-              std::vector<uint32_t> in;
-              for (AddrType x : i->ipConvIn[j]) in.push_back(limbOf(x));
-              Launch::Prob *pr = nullptr;
-              const bool pk = j < i->ipConvPacked.size() && i->ipConvPacked[j];
-              for (auto &q : L->probs) if (q.in == in && q.inMods == i->ipConvMods[j] && q.inPacked == pk) pr = &q;
-              if (!pr) { L->probs.push_back(Launch::Prob{in, i->ipConvMods[j], {}, {}}); pr = &L->probs.back(); pr->inPacked = pk; }
-              pr->out.push_back(limbOf(i->ipX[j]));      // the hand-off limb of (limb, digit)
-              pr->outMods.push_back(i->mod_id);
-              lp -= 1;                                      // the converted limb is neither written nor read: source = the conversion's inputs
-            }
-            for (auto &y : i->ipY) for (AddrType yy : y) L->b.push_back(limbOf(yy));
-            L->out.push_back(limbOf(i->OutputOperand));
-            for (AddrType o : i->extraOutputs) L->out.push_back(limbOf(o));
-            L->mods.push_back(i->mod_id);
-            L->ipInv.push_back(i->ipInvOut ? 1 : 0);
-            if (i->ipXGalois) L->xGalois = i->ipXGalois;   // (12): uniform over the op's records by construction
-            lp += (unsigned long long)L->ipTerms * L->ipOuts + L->ipOuts;
-          }
-        for (auto &q : L->probs) lp += q.in.size();
-        L->bytes = lp * LP;
-      } else if (f->ops == IP && !f->ipX.empty()) {
-        L->kind = Launch::L_IP; L->statKey = "EWE";
-        L->ipTerms = (uint32_t)f->ipX.size(); L->ipOuts = (uint32_t)f->ipY.size();
-        for (const Part *g : group)
-          for (Instruction *i : g->ins) {
-            for (AddrType x : i->ipX) L->a.push_back(limbOf(x));
-            for (auto &y : i->ipY) for (AddrType yy : y) L->b.push_back(limbOf(yy));
-            L->out.push_back(limbOf(i->OutputOperand));
-            for (AddrType o : i->extraOutputs) L->out.push_back(limbOf(o));
-            L->mods.push_back(i->mod_id);
-            if (i->ipXGalois) L->xGalois = i->ipXGalois;   // (12): uniform over the op's records by construction
-          }
-        L->bytes = (unsigned long long)(L->ipTerms * (1 + L->ipOuts) + L->ipOuts) * LP * count;
-      } else if (f->fusedTensor) {
-        L->kind = Launch::L_TENSOR; L->statKey = "EWE";
-        for (const Part *g : group)
-          for (Instruction *i : g->ins) {  // a = c00 (P), b = c10 (T), c = c01 (R), d = c11 (S)
-            L->a.push_back(limbOf(i->operandList[0])); L->b.push_back(limbOf(i->operandList[3]));
-            L->c.push_back(limbOf(i->operandList[2])); L->d.push_back(limbOf(i->operandList[1]));
-            L->out.push_back(limbOf(i->extraOutputs[0])); L->out1.push_back(limbOf(i->OutputOperand)); L->out2.push_back(limbOf(i->extraOutputs[1]));
-            L->mods.push_back(i->mod_id);
-          }
-        L->bytes = 7 * LP * count;
-      } else if (f->fusedSubScale) {
-        L->kind = Launch::L_NTT_SUBSCALE; L->statKey = "NTT";
-        bool anyAddend = false;   // the addend is per limb-poly (hrotate: key 0 adds the rotated c0, key 1 nothing)
-        bool anyAddGalois = false;   // (12) ... and key 0's addend through the automorphism
-        for (const Part *g : group)
-          for (Instruction *i : g->ins) { anyAddend |= i->fAddend != 0; anyAddGalois |= i->fAddendGalois != 0; }
-        for (const Part *g : group)
-          for (Instruction *i : g->ins) {
-            L->a.push_back(limbOf(i->operandList[0])); L->b.push_back(limbOf(i->fMinuend));
-            if (anyAddend) L->c.push_back(i->fAddend ? limbOf(i->fAddend) : HM_NO_LIMB);
-            if (anyAddGalois) L->addGalois.push_back(i->fAddendGalois);
-            L->out.push_back(limbOf(i->OutputOperand)); L->mods.push_back(i->mod_id); L->k.push_back(i->constant);
-            if (f->fMix) {  // the part key keeps merged and plain records apart
-              L->d.push_back(limbOf(i->fMix)); L->mixK.push_back(i->fMixConst);
-              if (anyAddend) L->addK.push_back(i->fAddendConst ? i->fAddendConst : 1);
-            }
-          }
-        L->hasK = true;
-        L->bytes = (anyAddend ? 4 : 3) * LP * count;
-        for (const Part *g : group)
-          for (Instruction *i : g->ins) {   // (9): the conversion of this limb-poly runs inside its first pass
-            if (i->fConvIn.empty()) continue;
-            std::vector<uint32_t> in;
-            for (AddrType x : i->fConvIn) in.push_back(limbOf(x));
-            Launch::Prob *pr = nullptr;
-            for (auto &q : L->probs) if (q.in == in && q.inMods == i->fConvMods && q.inPacked == i->inPacked) pr = &q;
-            if (!pr) { L->probs.push_back(Launch::Prob{in, i->fConvMods, {}, {}}); pr = &L->probs.back(); pr->inPacked = i->inPacked; L->bytes += LP * in.size(); }
-            pr->out.push_back(limbOf(i->OutputOperand));   // the hand-off lands in the output limb
-            pr->outMods.push_back(i->mod_id);
-            L->bytes -= LP;                                  // the converted limb-poly is neither written nor read
-          }
-      } else if (f->ops == NTT && f->passthrough) {  // unfused mode: materialise the copy
-        L->kind = Launch::L_EWE; L->opcode = EWE_COPY; L->statKey = "EWE";
-        for (const Part *g : group)
-          for (Instruction *i : g->ins) { L->a.push_back(limbOf(i->operandList[0])); L->out.push_back(limbOf(i->OutputOperand)); L->mods.push_back(i->mod_id); }
-        L->bytes = 2 * LP * count;
-      } else if (f->ops == NTT || f->ops == INTT) {
-        L->kind = f->ops == NTT ? Launch::L_NTT : Launch::L_INTT; L->statKey = "NTT";
-        L->secondOnly = f->secondOnly;
-        bool anyInGalois = false;
-        for (const Part *g : group)
-          for (Instruction *i : g->ins) anyInGalois |= i->inGalois != 0;
-        for (const Part *g : group)
-          for (Instruction *i : g->ins) {
-            if (anyInGalois) L->inGalois.push_back(i->inGalois);
-            L->a.push_back(limbOf(i->operandList[0])); L->out.push_back(limbOf(i->OutputOperand)); L->mods.push_back(i->mod_id);
-            L->k.push_back(i->hasConstant ? i->constant : 1);
-            L->hasK |= i->hasConstant;
-            if (f->ops == INTT) L->outPacked.push_back(i->packedOut ? 1 : 0);
-          }
-        L->bytes = 2 * LP * count;
-      } else if (f->ops == AUTO) {
-        L->kind = Launch::L_AUTO; L->statKey = "AUTO"; L->galois = f->galois;
-        for (const Part *g : group)
-          for (Instruction *i : g->ins) { L->a.push_back(limbOf(i->operandList[0])); L->out.push_back(limbOf(i->OutputOperand)); }
-        L->bytes = 2 * LP * count;
-      } else if (f->ops == MULT) {
-        L->kind = Launch::L_EWE; L->opcode = f->opcode; L->statKey = "EWE";
-        const int m = useMask[f->opcode];
-        int nops = 1;
-        for (int b = 0; b < 4; ++b) nops += (m >> b) & 1;
-        // entries of one modulus side by side: records that share an operand (pmult: c0 x pt and c1 x pt of a limb) then sit 128 workgroups apart
-        // in dispatch order, on the same XCD, and the second reader finds the shared limb-poly in L2 instead of fetching it again
-        std::vector<Instruction *> recs;
-        for (const Part *g : group) recs.insert(recs.end(), g->ins.begin(), g->ins.end());
-        std::stable_sort(recs.begin(), recs.end(), [](const Instruction *x, const Instruction *y) { return x->mod_id < y->mod_id; });
-        for (Instruction *i : recs) {
-          auto get = [&](int b) { return (m & (1 << b)) ? limbOf(i->operandList[b]) : 0u; };
-          L->a.push_back(get(0)); L->b.push_back(get(1)); L->c.push_back(get(2)); L->d.push_back(get(3));
-          L->out.push_back(limbOf(i->OutputOperand)); L->mods.push_back(i->mod_id);
-          L->k.push_back(i->hasConstant ? i->constant : 0);
-          L->hasK |= i->hasConstant;
-        }
-        L->bytes = (unsigned long long)nops * LP * count;
-      } else if (f->ops == BCONV_STEP2) {
-        L->kind = Launch::L_BCONV; L->statKey = "BCONV";
-        for (const Part *g : group) {
-          // one conversion per distinct (input limbs) inside the part
-          for (Instruction *i : g->ins) {
-            std::vector<uint32_t> in;
-            for (size_t x = 0; x + 1 < i->operandList.size(); ++x) in.push_back(limbOf(i->operandList[x]));
-            Launch::Prob *pr = nullptr;
-            for (auto &q : L->probs) if (q.in == in && q.inMods == i->inMods && q.epi == i->fusedEpi && q.epAdd == (i->fAdd != 0) && q.inPacked == i->inPacked) pr = &q;
-            if (!pr) { L->probs.push_back(Launch::Prob{in, i->inMods, {}, {}}); pr = &L->probs.back(); pr->epi = i->fusedEpi; pr->epAdd = i->fAdd != 0; pr->inPacked = i->inPacked; }
-            pr->out.push_back(limbOf(i->OutputOperand));
-            pr->outMods.push_back(i->mod_id);
-            if (i->fusedEpi) {   // (10): out = (fSubFrom - conv) * k [+ fAdd]
-              pr->epA.push_back(limbOf(i->fSubFrom)); pr->epK.push_back(i->constant);
-              if (i->fAdd) pr->epB.push_back(limbOf(i->fAdd));
-              L->bytes += LP * (i->fAdd ? 2 : 1);
-            }
-          }
-        }
-        if (world_ > 1 && batch_ > 1 && !shardGather) {  // sharded batch: the ops of the batch share the exchanges around the conversion
-          const uint32_t per = (uint32_t)limbIndex.size();
-          const size_t p0 = L->probs.size();
-          for (uint32_t c = 1; c < batch_; ++c)
-            for (size_t i = 0; i < p0; ++i) {
-              Launch::Prob q = L->probs[i];
-              for (uint32_t &x : q.in) x += c * per;
-              for (uint32_t &x : q.out) x += c * per;
-              L->probs.push_back(q);
-            }
-          L->refInstructions *= batch_;
-        }
-        for (auto &q : L->probs) L->bytes += LP * (q.in.size() + q.out.size());
-        if (world_ > 1 && !shardGather) {
-          // limb-sharded -> coefficient slices -> convert every output on this rank's slice -> limb-sharded
-          Launch *XI = new Launch, *XO = new Launch;
-          XI->kind = Launch::L_EXCH_IN; XO->kind = Launch::L_EXCH_OUT; XI->statKey = XO->statKey = "XCHG";
-          XI->name = L->name + ":limbs->slices"; XO->name = L->name + ":slices->limbs";
-          std::vector<uint32_t> inOwn, outOwn;
-          for (auto &q : L->probs) {
-            for (size_t x = 0; x < q.in.size(); ++x) {
-              size_t pos = std::find(XI->exLimbs.begin(), XI->exLimbs.end(), q.in[x]) - XI->exLimbs.begin();
-              if (pos == XI->exLimbs.size()) { XI->exLimbs.push_back(q.in[x]); XI->exOwners.push_back(owner(q.inMods[x])); }
-            }
-            for (size_t x = 0; x < q.out.size(); ++x) { XO->exLimbs.push_back(q.out[x]); XO->exOwners.push_back(owner(q.outMods[x])); }
-          }
-          std::vector<uint32_t> inRows(XI->exLimbs.size()), outRows(XO->exLimbs.size());
-          hm_slice_rows(XI->exOwners.data(), (uint32_t)inRows.size(), world_, inRows.data());
-          hm_slice_rows(XO->exOwners.data(), (uint32_t)outRows.size(), world_, outRows.data());
-          size_t o = 0;
-          for (auto &q : L->probs) {
-            for (uint32_t &x : q.in) x = inRows[std::find(XI->exLimbs.begin(), XI->exLimbs.end(), x) - XI->exLimbs.begin()];
-            for (uint32_t &x : q.out) x = outRows[o++];
-          }
-          L->logLen = XI->logLen = XO->logLen = logLen;
-          XI->bytes = LP * XI->exLimbs.size() / world_;
-          XO->bytes = LP * XO->exLimbs.size() / world_;
-          L->bytes /= world_;
-          if (pipelineDigits) {
-            XI->waitSlots = L->waitSlots;   // (its inputs come from the compute stream; marks matter only if an exchange produced them)
-            XI->recordSlot = nextSlot++;
-            L->waitSlots = {XI->recordSlot};
-            XO->recordSlot = nextSlot++;
-            for (const Part *g : group)
-              for (Instruction *i : g->ins) slotOfAddr[i->OutputOperand] = XO->recordSlot;
-          }
-          L->xin = XI; L->xout = XO;
-          (pipelineDigits ? front : back).push_back(XI);
-          algBytes += L->bytes;
-          back.push_back(L);
-          back.push_back(XO);
-          continue;
-        }
-      } else {
-        delete L;
-        throw std::runtime_error("no unit executes op " + f->GetOpName());
-      }
-      algBytes += L->bytes;
-      back.push_back(L);
-      }  // subgroups
-      launches.insert(launches.end(), front.begin(), front.end());
-      launches.insert(launches.end(), back.begin(), back.end());
+        if (parts[pj].depth == d && parts[pj].key == parts[pi].key) group.push_back(&parts[pj]);
+      b.emitGroup(group);
     }
   }
 }
@@ -1435,7 +844,7 @@ void Arch::replicateForBatch() {
     for (uint32_t c = 1; c < batch_; ++c)
       for (size_t i = 0; i < n0; ++i) v.push_back(isLimb && v[i] != HM_NO_LIMB && !sharedLimbs.count(v[i]) ? v[i] + c * per : v[i]);
   };
-  for (Launch *l : launches) {
+  for (auto &l : launches) {
     if (world_ > 1 && !shardGather && (l->kind == Launch::L_BCONV || l->kind == Launch::L_EXCH_IN || l->kind == Launch::L_EXCH_OUT)) continue;  // built batched
     if (l->kind == Launch::L_BCONV_COL || l->kind == Launch::L_EXCH_IN_COL || l->kind == Launch::L_EXCH_OUT_COL) continue;           // built batched
     if (l->kind == Launch::L_REPLICATE) {
@@ -1549,7 +958,7 @@ void Arch::prepare() {
   if (world_ > 1) {
     if (!commReady) throw std::runtime_error("world > 1 but no transport was set (commInitRccl / commInitExternal)");
     if (pipelineDigits && hm_exchange_stream(ctx, 1) != HM_OK) throw std::runtime_error(std::string("hm_exchange_stream: ") + hm_last_error(ctx));
-    for (Launch *bc : launches) {
+    for (auto &bc : launches) {
       if (bc->kind != Launch::L_BCONV_COL || !bc->xin) continue;
       Launch *xi = bc->xin, *xo = bc->xout;
       void *si = nullptr, *so = nullptr;   // limb-poly layout: a row per limb-poly, this rank's columns valid
@@ -1559,7 +968,7 @@ void Arch::prepare() {
       xi->slicesIn = bc->slicesIn = static_cast<uint64_t *>(si);
       bc->slicesOut = xo->slicesOut = static_cast<uint64_t *>(so);
     }
-    for (Launch *bc : launches) {
+    for (auto &bc : launches) {
       if (bc->kind != Launch::L_BCONV || !bc->xin) continue;
       Launch *xi = bc->xin, *xo = bc->xout;
       void *si = nullptr, *so = nullptr;
@@ -1619,7 +1028,7 @@ std::string Arch::stageTimes(uint32_t iters) {
 std::string Arch::planText() const {
   const char *const *names = kLaunchKindNames;
   std::string out;
-  for (const Launch *l : launches) {
+  for (const auto &l : launches) {
     size_t cnt = l->out.size();
     if (l->kind == Launch::L_BCONV || l->kind == Launch::L_BCONV_COL) { cnt = 0; for (auto &q : l->probs) cnt += q.out.size(); }
     if (l->kind == Launch::L_IP || l->kind == Launch::L_NTT_IP || l->kind == Launch::L_IP_HOISTED) cnt = l->mods.size();
@@ -1645,6 +1054,40 @@ std::string Arch::planText() const {
     if (!l->exLimbs.empty()) {
       out += " limbs=";
       for (size_t i = 0; i < l->exLimbs.size(); ++i) out += std::to_string(l->exLimbs[i]) + ":" + std::to_string(l->exOwners[i]) + ",";
+    }
+    out += "\n";
+  }
+  return out;
+}
+
+// Every field of every launch that enqueue() or replicateForBatch() consumes, one line per launch in launch order (the plan fingerprints of
+// tests/test_host_plan_fingerprint.py hash this text).  Deterministic: no pointer is printed, xin / xout appear as launch indices.
+std::string Arch::planDump() const {
+  std::string out;
+  auto vec = [&out](const char *name, const auto &v) {
+    if (v.empty()) return;
+    out += std::string(" ") + name + "=";
+    for (size_t i = 0; i < v.size(); ++i) out += (i ? "," : "") + std::to_string(v[i]);
+  };
+  auto indexOf = [this](const Launch *x) {
+    for (size_t i = 0; i < launches.size(); ++i)
+      if (launches[i].get() == x) return std::to_string(i);
+    return std::string(x ? "?" : "-");
+  };
+  for (const auto &l : launches) {
+    out += std::string(kLaunchKindNames[l->kind]) + " " + l->name + " stat=" + l->statKey + " opcode=" + std::to_string(l->opcode) + " galois=" + std::to_string(l->galois) +
+           " logLen=" + std::to_string(l->logLen) + " secondOnly=" + std::to_string(l->secondOnly) + " hasK=" + std::to_string(l->hasK) + " xGalois=" + std::to_string(l->xGalois) +
+           " ipTerms=" + std::to_string(l->ipTerms) + " ipOuts=" + std::to_string(l->ipOuts) + " ref=" + std::to_string(l->refInstructions) + " bytes=" + std::to_string(l->bytes) +
+           " mark=" + std::to_string(l->recordSlot) + " xin=" + indexOf(l->xin) + " xout=" + indexOf(l->xout);
+    vec("wait", l->waitSlots); vec("hoistG", l->hoistG); vec("ipCoeff", l->ipCoeff); vec("ipInv", l->ipInv); vec("outPacked", l->outPacked);
+    vec("inGalois", l->inGalois); vec("addGalois", l->addGalois);
+    vec("a", l->a); vec("b", l->b); vec("c", l->c); vec("d", l->d); vec("out", l->out); vec("out1", l->out1); vec("out2", l->out2);
+    vec("mods", l->mods); vec("inMods", l->inMods); vec("k", l->k); vec("mixK", l->mixK); vec("addK", l->addK);
+    vec("exLimbs", l->exLimbs); vec("exOwners", l->exOwners);
+    for (const Launch::Prob &q : l->probs) {
+      out += " prob{epi=" + std::to_string(q.epi) + " epAdd=" + std::to_string(q.epAdd) + " inPacked=" + std::to_string(q.inPacked);
+      vec("in", q.in); vec("inMods", q.inMods); vec("out", q.out); vec("outMods", q.outMods); vec("epA", q.epA); vec("epB", q.epB); vec("epK", q.epK);
+      out += "}";
     }
     out += "\n";
   }
@@ -1806,7 +1249,7 @@ void Arch::shownStat() {
     };
     double fetch = 0, write = 0, b = 0;
     if (num("whole_op_fetch_kib", fetch) && num("whole_op_write_kib", write) && num("whole_op_batch", b) && (uint32_t)b == batch_ && n == 65536 && maxLevel_ == 45 && curLevel_ == 35 &&
-        std::any_of(launches.begin(), launches.end(), [](const Launch *l) { return l->kind == Launch::L_TENSOR; })) {
+        std::any_of(launches.begin(), launches.end(), [](const std::unique_ptr<Launch> &l) { return l->kind == Launch::L_TENSOR; })) {
       stat->setStat("HBM_fetch_KiB_per_op", (unsigned long long)(2 * fetch));   // FETCH_SIZE counts 64 B per 128-B request on gfx950
       stat->setStat("HBM_write_KiB_per_op", (unsigned long long)write);
       stat->setStat("HBM_bytes_per_op", (unsigned long long)((2 * fetch + write) * 1024));
@@ -1837,14 +1280,14 @@ void Arch::run() {
     if (runCount++ >= 1) {
       hm_graph *g = nullptr;
       if (hm_capture_begin(ctx) != HM_OK) throw std::runtime_error(std::string("hm_capture_begin: ") + hm_last_error(ctx));
-      for (Launch *l : launches) enqueue(*l);
+      for (auto &l : launches) enqueue(*l);
       if (hm_capture_end(ctx, &g) != HM_OK) throw std::runtime_error(std::string("hm_capture_end: ") + hm_last_error(ctx));
       graph = g;
       if (hm_graph_launch(ctx, g) != HM_OK) throw std::runtime_error(std::string("hm_graph_launch: ") + hm_last_error(ctx));
       return;
     }
   }
-  for (Launch *l : launches) enqueue(*l);
+  for (auto &l : launches) enqueue(*l);
 }
 void Arch::sync() {
   if (ctx) hm_sync(ctx);

@@ -713,7 +713,7 @@ HROTATE::HROTATE(std::string labelName, uint32_t maxLevel, uint32_t currentLevel
 // ModUp of the UNROTATED c1 (KeySwitch MODUP): D_j = ModUp(c1).  Per rotation (KeySwitch ROTATED_KEY_PRODUCT, stage keys and buffers suffixed
 // _Rot<r>): AUTO of every extended digit, the key product with the rotation's own key, the ModDown, then out<r> = (sigma_r(c0) + ks0_r, ks1_r).
 // Not bit-identical to R hrotates: ModUp(sigma(c1)) and sigma(ModUp(c1)) differ by multiples of Q in the converted limbs; both key switches are
-// valid.  Unfused, the stages run one launch each; fused, pass (6h) of Arch::fusePasses turns the R key products into one hoisted launch.
+// valid.  Unfused, the stages run one launch each; fused, pass (6h) of Arch::fusePasses (Planner.cpp) turns the R key products into one hoisted launch.
 HROTATE_HOISTED::HROTATE_HOISTED(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch)
     : OperationBase("HROTATE_HOISTED", cfg, _arch, maxLevel, currentLevel, alpha) {
   label = labelName;

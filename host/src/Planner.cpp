@@ -1,0 +1,680 @@
+// Planner.cpp — the fusion passes on the stage list (fuse = 1): Arch::fusePasses is the list of passes, each pass a function of its own.
+// All of them preserve every value that a later stage or the caller can observe except the intermediates they eliminate (listed in
+// DESIGN.md §5).  What a record reads and writes is asked of Records.h; a pass that needs "who reads this address" filters recordReads().
+#include <algorithm>
+#include <iterator>
+#include <set>
+
+#include "Arch.h"
+#include "Records.h"
+#include "../../homulator_amd/csrc/hm_params.h"
+#include "../../include/homulator_hip.h"
+
+struct Arch::Planner {
+  Arch &A;
+  std::vector<Stage> &st;
+  // consumers of every address, counted ONCE, before pass 1 rewrites operands through its aliases, and never updated: passes 2-6 rely on
+  // that snapshot (an address with one consumer then has at most one now).  Passes 6h-12 rebuild their view (readers()) at their own start.
+  std::map<AddrType, int> uses;
+  // the record that writes an address.  Updated by the passes that move an output (2, 4, 4c, 6, 6h, 10), deliberately not by the others.
+  std::map<AddrType, Instruction *> producer;
+  std::set<Instruction *> dead;   // (looked up only: nothing may iterate it, a plan must not depend on pointer order)
+
+  Planner(Arch &a, std::vector<Stage> &s) : A(a), st(s) {
+    for (auto &s : st)
+      for (Instruction *i : s.ins) {
+        for (const Read &r : recordReads(*i)) uses[r.addr]++;
+        producer[i->OutputOperand] = i;
+      }
+  }
+  bool live(Instruction *i) const { return !dead.count(i); }
+  Instruction *producerOf(AddrType a) const { auto p = producer.find(a); return p == producer.end() ? nullptr : p->second; }
+  uint32_t cap(const char *name) const { return Arch::cap(A.logN, name); }
+  unsigned long long bconvPorts() const { return (unsigned long long)A.config->getValueOr("bconv_num_high", 1) * A.config->getValueOr("bconv_num_width", 1); }
+  // every read of every live record, as the record list stands now.  The replaced inputs of fused conversions count (Read::loaded)
+  typedef std::map<AddrType, std::vector<Instruction *>> Readers;
+  Readers readers() const {
+    Readers rd;
+    for (auto &s : st)
+      for (Instruction *i : s.ins)
+        if (live(i))
+          for (const Read &r : recordReads(*i)) rd[r.addr].push_back(i);
+    return rd;
+  }
+  static bool onlyReader(Readers &rd, AddrType a, Instruction *i) { auto &v = rd[a]; return v.size() == 1 && v[0] == i; }
+
+  void passThrough();      // 1
+  void inttScale();        // 2
+  void eweChains();        // 3
+  void nttSubScale();      // 4
+  void mergeRescale();     // 4b
+  void residue();          // 4c
+  void tensor();           // 5
+  void keyProduct();       // 6
+  void hoist();            // 6h
+  void transformTimesKey();   // 7 + 8
+  void keyProductInverseOut();   // 7b
+  void modDownConversion();   // 9
+  void conversionEpilogue();  // 10
+  void packConversionInputs();   // 11
+  void foldAutomorphisms();   // 12
+  void sweep();
+};
+
+void Arch::fusePasses(std::vector<Stage> &st) {
+  Planner p(*this, st);
+  const bool oneGpuKernels = world_ == 1 || shardGather;   // the plans whose conversions run in the one-GPU kernels
+  p.passThrough();
+  p.inttScale();
+  p.eweChains();
+  p.nttSubScale();
+  p.mergeRescale();
+  p.residue();
+  p.tensor();
+  p.keyProduct();
+  if (fuseHoist) p.hoist();
+  if (fuseHpip) p.transformTimesKey();
+  if (fuseHpip && fuseIpInv && oneGpuKernels && p.cap("cap_ip_inverse_out")) p.keyProductInverseOut();
+  if (fuseBconv && fuseModDown && oneGpuKernels && p.cap("cap_bconv_col_max_in_mix")) p.modDownConversion();
+  if (fuseBconv && oneGpuKernels) p.conversionEpilogue();
+  if (packBconvIn && oneGpuKernels) p.packConversionInputs();
+  if (fuseAuto) p.foldAutomorphisms();
+  p.sweep();
+}
+
+// (1) pass-through NTT records: consumers read the source directly.
+//     Reads: passthrough (generators).  Sets: operandList of every consumer.
+void Arch::Planner::passThrough() {
+  std::map<AddrType, AddrType> alias;
+  for (auto &s : st)
+    for (Instruction *i : s.ins)
+      if ((i->ops == NTT) && i->passthrough) {
+        alias[i->OutputOperand] = i->operandList[0];
+        dead.insert(i);
+      }
+  for (auto &s : st)
+    for (Instruction *i : s.ins) {
+      if (dead.count(i)) continue;
+      for (AddrType &a : i->operandList) {
+        auto al = alias.find(a);
+        if (al != alias.end()) a = al->second;
+      }
+    }
+}
+
+// (2) INTT followed by a single MUL_CONST consumer: the constant goes into the INTT epilogue.
+//     Sets on the INTT: hasConstant, constant, OutputOperand.
+void Arch::Planner::inttScale() {
+  for (auto &s : st)
+    for (Instruction *i : s.ins) {
+      if (i->ops != MULT || i->opcode != EWE_MUL_CONST || dead.count(i)) continue;
+      auto p = producer.find(i->operandList[0]);
+      if (p == producer.end() || p->second->ops != INTT || uses[i->operandList[0]] != 1 || p->second->hasConstant) continue;
+      p->second->hasConstant = true;
+      p->second->constant = i->constant;
+      p->second->OutputOperand = i->OutputOperand;
+      p->second->refInstructions += i->refInstructions;
+      producer[i->OutputOperand] = p->second;
+      dead.insert(i);
+    }
+}
+
+// (3) EWE chains: SUB then MUL_CONST -> SUB_SCALE ; SUB_SCALE then ADD -> SUB_SCALE_ADD.
+//     Sets on the surviving MULT record: opcode, operandList, hasConstant, constant.
+void Arch::Planner::eweChains() {
+  for (auto &s : st)
+    for (Instruction *i : s.ins) {
+      if (i->ops != MULT || dead.count(i)) continue;
+      if (i->opcode == EWE_MUL_CONST) {
+        auto p = producer.find(i->operandList[0]);
+        if (p == producer.end() || p->second->ops != MULT || p->second->opcode != EWE_SUB || dead.count(p->second) ||
+            uses[i->operandList[0]] != 1)
+          continue;
+        Instruction *sub = p->second;
+        i->opcode = EWE_SUB_SCALE;
+        i->operandList[0] = sub->operandList[0];
+        i->operandList[2] = sub->operandList[2];
+        i->refInstructions += sub->refInstructions;
+        dead.insert(sub);
+      } else if (i->opcode == EWE_ADD) {
+        for (int side = 0; side < 2; ++side) {
+          const int me = side ? 2 : 0, other = side ? 0 : 2;
+          auto p = producer.find(i->operandList[me]);
+          if (p == producer.end() || p->second->ops != MULT || p->second->opcode != EWE_SUB_SCALE || dead.count(p->second) ||
+              uses[i->operandList[me]] != 1)
+            continue;
+          Instruction *ss = p->second;
+          const AddrType addend = i->operandList[other];
+          i->opcode = EWE_SUB_SCALE_ADD;
+          i->operandList[0] = ss->operandList[0];
+          i->operandList[2] = ss->operandList[2];
+          i->operandList[3] = addend;
+          i->hasConstant = true;
+          i->constant = ss->constant;
+          i->refInstructions += ss->refInstructions;
+          dead.insert(ss);
+          break;
+        }
+      }
+    }
+}
+
+// (4) forward NTT whose only consumer is (minuend - x) * k [+ addend]: the epilogue moves into the transform's
+//     last pass (ModDowNTT + ModDownSub + final add; Rescale_NTT + Rescale_SUB + Rescale_Mul).
+//     Reads: the SUB_SCALE[_ADD] records of (3).  Sets on the NTT: fusedSubScale, fMinuend, fAddend, hasConstant, constant, OutputOperand.
+void Arch::Planner::nttSubScale() {
+  for (auto &s : st)
+    for (Instruction *i : s.ins) {
+      if (i->ops != MULT || dead.count(i) || (i->opcode != EWE_SUB_SCALE && i->opcode != EWE_SUB_SCALE_ADD)) continue;
+      auto p = producer.find(i->operandList[2]);
+      if (p == producer.end() || p->second->ops != NTT || p->second->passthrough || dead.count(p->second) ||
+          p->second->fusedSubScale || uses[i->operandList[2]] != 1)
+        continue;
+      Instruction *t = p->second;
+      const AddrType minuend = i->operandList[0], addend = i->opcode == EWE_SUB_SCALE_ADD ? i->operandList[3] : 0;
+      const AddrType out = i->OutputOperand;
+      if (out == t->operandList[0] || out == minuend || out == addend) continue;  // out doubles as first-pass scratch
+      t->fusedSubScale = true;
+      t->fMinuend = minuend;
+      t->fAddend = addend;
+      t->hasConstant = true;
+      t->constant = i->constant;
+      t->OutputOperand = out;
+      t->refInstructions += i->refInstructions;
+      producer[out] = t;
+      dead.insert(i);
+    }
+}
+
+// (4b) ModDown finish followed by the rescale of the same limb.  T: h = (ip - NTT(conv)) * kT + d and
+//      R: out = (h - NTT(r)) * kR with r = INTT(last limb of h) are both linear in the coefficient domain:
+//      out = (ip - NTT(conv + kT^-1 * r)) * (kT kR) + d * kR — ONE transform per limb instead of two, and h never
+//      exists (the last limb keeps T: r comes from it).  Bit-identical: everything is exact modular arithmetic.
+//      Reads: the fused transforms of (4).  Sets on R: fMix, fMixConst, fAddendConst, operandList[0], fMinuend, fAddend, constant.
+void Arch::Planner::mergeRescale() {
+  for (auto &s : st)
+    for (Instruction *R : s.ins) {
+      if (R->ops != NTT || !R->fusedSubScale || R->fAddend || R->fMix || dead.count(R)) continue;
+      auto p = producer.find(R->fMinuend);
+      if (p == producer.end() || p->second == R || !p->second->fusedSubScale || p->second->fMix || dead.count(p->second) ||
+          p->second->mod_id != R->mod_id || uses[R->fMinuend] != 1)
+        continue;
+      Instruction *T = p->second;
+      const uint64_t q = A.modulus(R->mod_id);
+      // R survives (its stage comes after the INTT that produces r, so the stage list stays a topological order)
+      R->fMix = R->operandList[0];
+      R->fMixConst = hm::invmod(T->constant, q);
+      R->operandList[0] = T->operandList[0];
+      R->fMinuend = T->fMinuend;
+      R->fAddend = T->fAddend;
+      R->fAddendConst = T->fAddend ? R->constant : 0;
+      R->constant = hm::mulmod(T->constant, R->constant, q);
+      R->refInstructions += T->refInstructions;
+      dead.insert(T);
+    }
+}
+
+// (4c) the residue r = INTT(h_last) that the merged records mix in.  h_last = (ip - NTT(conv)) * kT + d is only ever
+//      needed in coefficient form, where it is (INTT(ip) - conv) * kT + INTT(d): conv never has to be transformed and
+//      brought back.  INTT(ip) and INTT(d) depend on nothing after the inner product, so they join the ModDown INTT
+//      launch (equal dependency depth), and one element-wise SUB_SCALE_ADD on the last limb replaces the two
+//      latency-bound single-limb transforms T_last and INTT(h_last).
+//      Reads: fMix of (4b), the fused transform of (4).  Adds records (two INTT, one MULT) to the stage of the INTT it replaces and
+//      a limb of its own for INTT(d_last).
+void Arch::Planner::residue() {
+  struct Rewrite { Instruction *T, *X; size_t stage; };
+  std::vector<Rewrite> todo;
+  for (size_t si = 0; si < st.size(); ++si)
+    for (Instruction *X : st[si].ins) {
+      if (X->ops != INTT || X->hasConstant || dead.count(X)) continue;
+      auto p = producer.find(X->operandList[0]);
+      if (p == producer.end() || dead.count(p->second) || !p->second->fusedSubScale || p->second->fMix || p->second->ops != NTT ||
+          uses[X->operandList[0]] != 1)
+        continue;
+      bool mixedIn = false;
+      for (auto &s2 : st)
+        for (Instruction *i : s2.ins) mixedIn |= !dead.count(i) && i->fMix == X->OutputOperand;
+      if (mixedIn) todo.push_back(Rewrite{p->second, X, si});
+    }
+  AddrType fresh = A.limbIndex.empty() ? 1 : A.limbIndex.rbegin()->first + 1;
+  for (const Rewrite &w : todo) {
+    Instruction *T = w.T, *X = w.X;
+    const AddrType h = X->operandList[0], r = X->OutputOperand;
+    Instruction *ia = new Instruction("INTT", INTT, T->level_id);   // wa = INTT(ip_last), kept in h's limb
+    ia->mod_id = T->mod_id; ia->operandList = {T->fMinuend}; ia->OutputOperand = h; ia->refInstructions = T->refInstructions;
+    st[w.stage].ins.push_back(ia);
+    AddrType wb = 0;
+    if (T->fAddend) {                                               // wb = INTT(d_last), in a limb of its own
+      wb = fresh++;
+      A.registerLimbs({wb});
+      Instruction *ib = new Instruction("INTT", INTT, T->level_id);
+      ib->mod_id = T->mod_id; ib->operandList = {T->fAddend}; ib->OutputOperand = wb;
+      st[w.stage].ins.push_back(ib);
+    }
+    Instruction *e = new Instruction("MULT", MULT, T->level_id);    // r = (wa - conv_last) * kT [+ wb]
+    e->mod_id = T->mod_id;
+    e->opcode = wb ? EWE_SUB_SCALE_ADD : EWE_SUB_SCALE;
+    e->operandList = {h, 0, T->operandList[0], wb};
+    e->hasConstant = true; e->constant = T->constant;
+    e->OutputOperand = r; e->refInstructions = X->refInstructions;
+    st[w.stage].ins.push_back(e);
+    producer[h] = ia; producer[r] = e;
+    dead.insert(T); dead.insert(X);
+  }
+}
+
+// (5) tensor product: d1 = p*s + r*t (MAC2) with d0 = p*t and d2 = r*s (MUL) of the same limb -> one pass.
+//     Sets on the MAC2 record: fusedTensor, extraOutputs.
+void Arch::Planner::tensor() {
+  std::map<std::pair<AddrType, AddrType>, Instruction *> muls;
+  for (auto &s : st)
+    for (Instruction *i : s.ins)
+      if (i->ops == MULT && i->opcode == EWE_MUL && !dead.count(i)) muls[{i->operandList[0], i->operandList[1]}] = i;
+  for (auto &s : st)
+    for (Instruction *i : s.ins) {
+      if (i->ops != MULT || i->opcode != EWE_MAC2 || dead.count(i)) continue;
+      const AddrType P = i->operandList[0], S = i->operandList[1], R = i->operandList[2], T = i->operandList[3];
+      auto u = muls.find({P, T}), v = muls.find({R, S});
+      if (u == muls.end() || v == muls.end() || u->second->mod_id != i->mod_id || v->second->mod_id != i->mod_id) continue;
+      i->fusedTensor = true;
+      i->extraOutputs = {u->second->OutputOperand, v->second->OutputOperand};
+      i->refInstructions += u->second->refInstructions + v->second->refInstructions;
+      dead.insert(u->second);
+      dead.insert(v->second);
+    }
+}
+
+// (6) inner product with the evaluation key: the chain MAC2 / MAC_ADD ... of one key collapses into a single sum
+//     of products, and the two keys (same ext operands) into one two-output record (the HPIP unit's job).
+//     Reads: fusedTensor (5).  Sets on the later chain's last record: ops = IP, ipX, ipY, OutputOperand, extraOutputs.
+void Arch::Planner::keyProduct() {
+  struct Dot { std::vector<AddrType> x, y; std::vector<Instruction *> members; };
+  std::map<Instruction *, Dot> dots;
+  auto single = [&](AddrType a) { return uses[a] == 1; };
+  std::vector<Instruction *> order;
+  for (auto &s : st)
+    for (Instruction *i : s.ins) order.push_back(i);
+  for (Instruction *i : order) {
+    if (i->ops != MULT || dead.count(i) || i->fusedTensor) continue;
+    Dot d;
+    if (i->opcode == EWE_MUL) { d.x = {i->operandList[0]}; d.y = {i->operandList[1]}; }
+    else if (i->opcode == EWE_MAC2) { d.x = {i->operandList[0], i->operandList[2]}; d.y = {i->operandList[1], i->operandList[3]}; }
+    else if (i->opcode == EWE_MAC_ADD) {
+      auto p = producer.find(i->operandList[2]);
+      if (p == producer.end() || !dots.count(p->second) || !single(i->operandList[2]) || p->second->mod_id != i->mod_id) continue;
+      d = dots[p->second];
+      d.x.push_back(i->operandList[0]);
+      d.y.push_back(i->operandList[1]);
+    } else continue;
+    d.members.push_back(i);
+    dots[i] = d;
+  }
+  // keep the dots that end a chain (nobody extends them) and have a partner with the same x list or >= 3 terms
+  std::set<Instruction *> extended;
+  for (auto &kv : dots)   // (fills a set: the iteration order leaks nowhere)
+    for (size_t m = 0; m + 1 < kv.second.members.size(); ++m) extended.insert(kv.second.members[m]);
+  std::map<std::pair<uint32_t, std::vector<AddrType>>, Instruction *> byX;
+  for (Instruction *i : order) {
+    auto it = dots.find(i);
+    if (it == dots.end() || extended.count(i) || it->second.x.size() > 4) continue;
+    Dot &d = it->second;
+    auto key = std::make_pair(i->mod_id, d.x);
+    auto partner = byX.find(key);
+    if (partner == byX.end()) { byX[key] = i; continue; }
+    Instruction *a = partner->second;  // first key
+    Dot &da = dots[a];
+    if (a->ops == IP) continue;        // already paired
+    // `i` (the later one) carries the fused record so that it is scheduled after every member of both chains
+    const AddrType outFirst = a->OutputOperand, outSecond = i->OutputOperand;
+    i->ops = IP;
+    i->ipX = d.x;
+    i->ipY = {da.y, d.y};
+    i->OutputOperand = outFirst;
+    i->extraOutputs = {outSecond};
+    producer[outFirst] = i;
+    for (Instruction *m : da.members) { i->refInstructions += m->refInstructions; dead.insert(m); }
+    for (Instruction *m : d.members)
+      if (m != i) { i->refInstructions += m->refInstructions; dead.insert(m); }
+    byX.erase(partner);
+  }
+}
+
+// (6h) hoisted rotations (hrotate_hoisted): two-key inner-product records whose digits are all automorphisms (one element per record) of the SAME
+//      materialised digits, read by nothing else, merge into ONE record per (modulus, digit list): hm_inner_product_hoisted reads the digits once
+//      for every rotation and gathers the key / scatters the output at the automorphism's destination; the automorphisms are never written.
+//      The first record in stage order carries the merged one: every reader of any rotation's output comes after it.
+//      Reads: the key-product records of (6).  Sets on the carrying record: ipX (the unrotated digits), ipY, ipHoistG, OutputOperand, extraOutputs.
+void Arch::Planner::hoist() {
+  Readers rd = readers();
+  typedef std::pair<uint32_t, std::vector<AddrType>> DigitsKey;   // (modulus, unrotated digits)
+  std::map<DigitsKey, std::vector<std::pair<Instruction *, std::vector<Instruction *>>>> groups;   // -> (record, its automorphisms) in stage order
+  std::vector<DigitsKey> groupOrder;
+  for (auto &s : st)
+    for (Instruction *ip : s.ins) {
+      if (!isKeyProduct(*ip) || dead.count(ip) || ip->ipY.size() != 2 || ip->ipXGalois || !ip->ipHoistG.empty() || transformsInside(*ip)) continue;
+      std::vector<AddrType> src;
+      std::vector<Instruction *> autos;
+      for (AddrType x : ip->ipX) {
+        Instruction *a = producerOf(x);
+        if (!a || a->ops != AUTO || dead.count(a) || a->galois <= 1 || a->mod_id != ip->mod_id || (!autos.empty() && a->galois != autos[0]->galois) ||
+            !onlyReader(rd, x, ip))
+          break;
+        src.push_back(a->operandList[0]);
+        autos.push_back(a);
+      }
+      if (autos.size() != ip->ipX.size()) continue;
+      const DigitsKey key(ip->mod_id, src);
+      if (!groups.count(key)) groupOrder.push_back(key);
+      groups[key].push_back({ip, autos});
+    }
+  for (const DigitsKey &key : groupOrder) {
+    const auto &mem = groups[key];
+    for (size_t b = 0; b < mem.size(); b += HM_IP_HOISTED_MAX_ROT) {
+      const size_t e = std::min(mem.size(), b + (size_t)HM_IP_HOISTED_MAX_ROT);
+      std::set<uint32_t> distinct;
+      for (size_t m = b; m < e; ++m) distinct.insert(mem[m].second[0]->galois);
+      if (distinct.size() != e - b) continue;   // two records by one element are not rotations of one ciphertext
+      Instruction *c = mem[b].first;
+      std::vector<AddrType> outs;
+      std::vector<std::vector<AddrType>> ys;
+      std::vector<uint32_t> gs;
+      for (size_t m = b; m < e; ++m) {
+        Instruction *i = mem[m].first;
+        outs.push_back(i->OutputOperand);
+        outs.insert(outs.end(), i->extraOutputs.begin(), i->extraOutputs.end());
+        ys.insert(ys.end(), i->ipY.begin(), i->ipY.end());
+        gs.push_back(mem[m].second[0]->galois);
+        if (i != c) { c->refInstructions += i->refInstructions; dead.insert(i); }
+        for (Instruction *a : mem[m].second) { c->refInstructions += a->refInstructions; dead.insert(a); }
+      }
+      c->ipX = key.second;
+      c->ipY = ys;
+      c->ipHoistG = gs;
+      c->OutputOperand = outs[0];
+      c->extraOutputs.assign(outs.begin() + 1, outs.end());
+      for (AddrType o : outs) producer[o] = c;
+    }
+  }
+}
+
+// (7) HPIP as SURVEY.md 8f-2 specifies it: a forward transform whose only reader is an inner-product record moves INTO that
+//     record (ModUp_NTT_(j) + InnerProOut: src/Operation.cpp:190-414).  The kernel runs the digit's ROW pass and multiplies
+//     its registers into both keys' accumulators; the extended digit (NTTOut_beta(j)) is never written or read back — its
+//     buffer only serves the first pass as scratch.
+// (8) the base conversion that produces such a digit, if nobody else reads its output, moves into the transform's first pass as well
+//     (decided per digit; taken only if every transformed digit of the record allows it).
+//     Reads: the key-product records of (6), not the hoisted ones of (6h); fusedSubScale (4).  Sets on every such record: ipSrc, ipCoeff; (8):
+//     ipConvIn, ipConvMods.
+void Arch::Planner::transformTimesKey() {
+  Readers rd = readers();
+  for (auto &s : st)
+    for (Instruction *ip : s.ins) {
+      if (!isKeyProduct(*ip) || dead.count(ip) || !ip->ipHoistG.empty()) continue;   // (6h): its digits stay materialised
+      ip->ipSrc = ip->ipX;
+      ip->ipCoeff.assign(ip->ipX.size(), 0);
+      std::vector<Instruction *> conv(ip->ipX.size(), nullptr);
+      // widest digit the fused conversion + first pass takes (0: none at this ring size); config key fuse_bconv_max_in caps it below what the
+      // back-end offers (A/B runs: 15 = the plan of rounds 3-5, where wider digits kept a conversion launch of their own)
+      // (default: the widest digit for which the fused form measured faster at this ring size, cap_bconv_col_pref_in)
+      const uint32_t maxConvIn = std::min<uint32_t>(cap("cap_bconv_col_max_in"), A.config->getValueOr("fuse_bconv_max_in", cap("cap_bconv_col_pref_in")));
+      bool allConv = A.fuseBconv && (A.world_ == 1 || A.shardFused || A.shardGather) && maxConvIn != 0;
+      for (size_t j = 0; j < ip->ipX.size(); ++j) {
+        Instruction *t = producerOf(ip->ipX[j]);
+        if (!t) continue;
+        if (t->ops != NTT || t->passthrough || t->fusedSubScale || dead.count(t) || t->mod_id != ip->mod_id) continue;
+        if (!onlyReader(rd, ip->ipX[j], ip)) continue;
+        ip->ipSrc[j] = t->operandList[0];
+        ip->ipCoeff[j] = 1;
+        ip->refInstructions += t->refInstructions;
+        dead.insert(t);
+        // (8) is the transform's input a conversion output that nobody else reads?
+        Instruction *cv = producerOf(t->operandList[0]);
+        if (cv && cv->ops == BCONV_STEP2 && !dead.count(cv) && onlyReader(rd, t->operandList[0], t) && cv->operandList.size() - 1 <= maxConvIn &&
+            cv->mod_id == ip->mod_id)
+          conv[j] = cv;
+        else allConv = false;
+      }
+      if (allConv && transformsInside(*ip)) {
+        ip->ipConvIn.assign(ip->ipX.size(), {});
+        ip->ipConvMods.assign(ip->ipX.size(), {});
+        for (size_t j = 0; j < ip->ipX.size(); ++j) {
+          if (!conv[j]) continue;
+          ip->ipConvIn[j].assign(conv[j]->operandList.begin(), conv[j]->operandList.end() - 1);
+          ip->ipConvMods[j] = conv[j]->inMods;
+          ip->refInstructions += conv[j]->refInstructions * bconvPorts();
+          dead.insert(conv[j]);
+        }
+      }
+    }
+}
+
+// (7b, round 5) an inner-product record (HPIP form) whose outputs are read by inverse transforms and nothing else — the special limbs of
+//      the key-switch sum (ModDownINTTOut_Key(k)) and, with (4c), the last Q limb (the rescale residue's INTT) — hands them over as the
+//      FIRST pass of that inverse transform: a ROW pass over the 16 rows of the limb-poly the workgroup has just accumulated (the forward
+//      ROW pass's last round and the inverse ROW pass's first are the same round, so the pass runs from the registers).  The kernel stores
+//      the pass's hand-off into the INTT's output limb, the INTT record keeps its COL pass (hm_ntt_second_pass, with its scale), and the
+//      evaluation-form sums of those limbs (InnerProduceOut_Key{k}[0 .. alpha)) are never written or read back.
+//      Reads: ipCoeff (7).  Sets: ipInvOut, OutputOperand / extraOutputs on the key product; secondOnly, operandList[0] on the inverse transforms.
+void Arch::Planner::keyProductInverseOut() {
+  Readers rd = readers();
+  for (auto &s : st)
+    for (Instruction *ip : s.ins) {
+      if (!isKeyProduct(*ip) || dead.count(ip) || ip->ipInvOut) continue;
+      if (!transformsInside(*ip)) continue;   // the fused transform x key kernel only
+      std::vector<AddrType *> outs = {&ip->OutputOperand};
+      for (AddrType &o : ip->extraOutputs) outs.push_back(&o);
+      std::vector<Instruction *> inv;
+      for (AddrType *o : outs) {
+        auto &r = rd[*o];
+        if (r.size() != 1 || r[0]->ops != INTT || dead.count(r[0]) || r[0]->mod_id != ip->mod_id || r[0]->secondOnly || r[0]->operandList[0] != *o) break;
+        inv.push_back(r[0]);
+      }
+      if (inv.size() != outs.size()) continue;
+      for (size_t k = 0; k < outs.size(); ++k) {
+        *outs[k] = inv[k]->OutputOperand;                      // the hand-off lands where the inverse transform finishes in place
+        inv[k]->operandList[0] = inv[k]->OutputOperand;
+        inv[k]->secondOnly = true;
+      }
+      ip->ipInvOut = true;
+    }
+}
+
+// (9, round 4) the ModDown side of (8): a fused forward transform (ModDowNTT + ModDownSub [+ rescale]) whose input is a P -> Q conversion
+//     output that nobody else reads takes the conversion into its first pass (src/Operation.cpp:489-590): ModdownBConvOut_Key(k) is
+//     never written or read back.  The last limb of a key keeps its conversion: the rescale residue is formed from it element-wise (4c).
+//     Reads: fusedSubScale (4), fMix (4b).  Sets on the transform: fConvIn, fConvMods.
+void Arch::Planner::modDownConversion() {
+  const uint32_t maxMixIn = cap("cap_bconv_col_max_in_mix");
+  Readers rd = readers();
+  for (auto &s : st)
+    for (Instruction *t : s.ins) {
+      if (t->ops != NTT || !t->fusedSubScale || t->passthrough || dead.count(t)) continue;
+      Instruction *cv = producerOf(t->operandList[0]);
+      if (!cv || cv->ops != BCONV_STEP2 || dead.count(cv) || cv->mod_id != t->mod_id) continue;
+      if (!onlyReader(rd, t->operandList[0], t) || cv->operandList.size() - 1 > (t->fMix ? maxMixIn : cap("cap_bconv_col_max_in"))) continue;
+      t->fConvIn.assign(cv->operandList.begin(), cv->operandList.end() - 1);
+      t->fConvMods = cv->inMods;
+      t->refInstructions += cv->refInstructions * bconvPorts();
+      dead.insert(cv);
+    }
+}
+
+// (10, round 4) r = (wa - conv_last) * kT [+ wb] (4c) directly behind the conversion that produces conv_last: the one-limb element-wise
+//      launch becomes the conversion kernel's epilogue (hm_bconv_desc::sub_from).
+//      Reads: the SUB_SCALE[_ADD] record of (4c).  Sets on the conversion: fusedEpi, fSubFrom, fAdd, hasConstant, constant, OutputOperand, refExtra;
+//      moves it to the element-wise record's place in the stage list.
+void Arch::Planner::conversionEpilogue() {
+  Readers rd = readers();
+  for (auto &s : st)
+    for (size_t ei = 0; ei < s.ins.size(); ++ei) {
+      Instruction *e = s.ins[ei];
+      if (e->ops != MULT || dead.count(e) || (e->opcode != EWE_SUB_SCALE && e->opcode != EWE_SUB_SCALE_ADD)) continue;
+      Instruction *cv = producerOf(e->operandList[2]);
+      if (!cv || cv->ops != BCONV_STEP2 || dead.count(cv) || cv->fusedEpi || cv->mod_id != e->mod_id || rd[e->operandList[2]].size() != 1) continue;
+      cv->fusedEpi = true;
+      cv->fSubFrom = e->operandList[0];
+      cv->fAdd = e->opcode == EWE_SUB_SCALE_ADD ? e->operandList[3] : 0;
+      cv->hasConstant = true;
+      cv->constant = e->constant;
+      cv->OutputOperand = e->OutputOperand;
+      cv->refExtra += e->refInstructions;   // (a conversion's own count is scaled by the MAC ports at launch time, the epilogue's is not)
+      producer[cv->OutputOperand] = cv;
+      // the conversion now reads what e read (the inverse transforms of 4c, queued in e's stage): it takes e's place in the stage list,
+      // which stays a topological order
+      for (auto &s2 : st) s2.ins.erase(std::remove(s2.ins.begin(), s2.ins.end(), cv), s2.ins.end());
+      std::replace(s.ins.begin(), s.ins.end(), e, cv);
+      dead.insert(e);
+    }
+}
+
+// (11, round 5) split-30 packed conversion inputs.  A limb-poly that an inverse transform writes and that nothing but base conversions read
+//      (as a conversion INPUT: a separate conversion, a conversion inside a transform x key record or inside a fused transform) is
+//      stored packed; a conversion takes packed inputs only if all of them are.
+//      Reads: ipConvIn (8), fConvIn (9), fMix (4b), secondOnly (7b), fusedEpi (10).  Sets: packedOut on inverse transforms, inPacked / ipConvPacked
+//      on the records that convert.
+void Arch::Planner::packConversionInputs() {
+  struct Conv { std::vector<AddrType> in; Instruction *ins; size_t digit; };   // digit: index into ipConvIn, kNoDigit = the record's own conversion
+  std::vector<Conv> convs;
+  std::map<AddrType, int> otherReads;   // reads of an address that are not a conversion input
+  for (auto &s : st)
+    for (Instruction *i : s.ins) {
+      if (dead.count(i)) continue;
+      size_t first = convs.size();
+      for (const Read &r : recordReads(*i)) {
+        if (!r.loaded()) continue;                     // a replaced input is read by nobody
+        if (r.role == Role::SecondPassIn) continue;    // (7b) its one operand is its own output: the in-place second pass is no other reader of it
+        const bool plainConv = r.role == Role::ConvIn && !(i->ops != BCONV_STEP2 && r.digit == kNoDigit && i->fMix);   // (the fused conversion with the mix prologue takes plain inputs)
+        if (!plainConv) { otherReads[r.addr]++; continue; }
+        size_t c = first;
+        while (c < convs.size() && convs[c].digit != r.digit) ++c;
+        if (c == convs.size()) convs.push_back(Conv{{}, i, r.digit});
+        convs[c].in.push_back(r.addr);
+      }
+    }
+  std::set<AddrType> cand;
+  for (auto &s : st)
+    for (Instruction *x : s.ins)
+      if (x->ops == INTT && !dead.count(x) && !otherReads.count(x->OutputOperand)) cand.insert(x->OutputOperand);
+  for (bool changed = true; changed;) {   // a conversion with one plain input keeps all of its inputs plain
+    changed = false;
+    for (const Conv &cv : convs) {
+      bool all = true;
+      for (AddrType a : cv.in) all &= cand.count(a) != 0;
+      if (all) continue;
+      for (AddrType a : cv.in) changed |= cand.erase(a) != 0;
+    }
+  }
+  std::set<AddrType> read;
+  for (const Conv &cv : convs) {
+    if (cv.in.empty() || !cand.count(cv.in[0])) continue;
+    if (cv.digit != kNoDigit) { cv.ins->ipConvPacked.resize(cv.ins->ipConvIn.size(), 0); cv.ins->ipConvPacked[cv.digit] = 1; }
+    else cv.ins->inPacked = true;
+    read.insert(cv.in.begin(), cv.in.end());
+  }
+  for (auto &s : st)
+    for (Instruction *x : s.ins)
+      if (x->ops == INTT && !dead.count(x) && read.count(x->OutputOperand)) x->packedOut = true;
+}
+
+// (12) round 6: an automorphism whose output is read ONLY as the input of inverse transforms, as the addend of fused forward transforms and / or as
+//      the evaluation-form digits of transform x key records folds into those readers (hm_ntt_desc.in_galois, hm_ntt_fused_desc.addend_galois,
+//      hm_ntt_ip_desc.x_galois): the index map takes aligned blocks to aligned blocks, so a kernel gathers through it with its own 16-byte loads,
+//      and AUTOOutput is never written or read back.  hrotate: AUTO_Key(1) -> ModUp_INTT + the key product's own digits, AUTO_Key(0) -> the final
+//      add inside ModDowNTT's epilogue: 6 -> 5 launches, 140 limb-polys less traffic.  Config key fuse_auto (default 1).
+//      The key product takes ONE Galois element per launch: its records fold only if every evaluation-form digit of every such record of the op
+//      is the output of a foldable automorphism by the same element.  Sharded plans fold the same way: a limb-poly's transforms and key product run on
+//      the rank that owns the limb, where the automorphism's source limb lives too.
+//      Reads: fusedSubScale / fAddend (4), fMix (4b), ipHoistG (6h), ipSrc / ipCoeff (7), ipConvIn (8), secondOnly (7b), fConvIn (9).  Sets: inGalois +
+//      operandList[0] on inverse transforms, fAddendGalois + fAddend on fused forward transforms, ipXGalois + ipX / ipSrc on key products.
+void Arch::Planner::foldAutomorphisms() {
+  enum Fold { NONE, INTT_IN, ADDEND, OWN_DIGIT };   // how a reader can read through the automorphism (NONE: it cannot)
+  struct Reader { Instruction *ins; Fold fold; size_t digit; };
+  std::map<AddrType, std::vector<Reader>> readers;
+  std::vector<Reader> ownDigits;
+  for (auto &s : st)
+    for (Instruction *i : s.ins) {
+      if (dead.count(i)) continue;
+      for (const Read &r : recordReads(*i)) {
+        Fold f = NONE;
+        // a transform x key record reads its own digits in evaluation form, a plain inner-product record (no digit transformed inside) all of them
+        // (any plan: a limb-poly's key product runs on the rank that owns the limb, and so does the automorphism's source limb)
+        if (r.role == Role::IpDigit && !i->ipXGalois && i->ipHoistG.empty()) f = OWN_DIGIT;
+        else if (r.role == Role::InttIn && !i->inGalois) f = INTT_IN;
+        else if (r.role == Role::Addend && i->ops == NTT && !i->fMix && i->fConvIn.empty() && !i->fAddendGalois) f = ADDEND;
+        readers[r.addr].push_back({i, f, r.digit});
+        if (f == OWN_DIGIT) ownDigits.push_back({i, f, r.digit});
+      }
+    }
+  // (the readers will read the automorphism's SOURCE, and later than the automorphism did: nothing may write that source from the automorphism's
+  // stage on — the reference's operations never write their inputs; a program that does keeps its launch).  Outputs only: the first-pass scratch
+  // of a transformed digit is the buffer of a forward transform's output, which is no automorphism's source.
+  std::map<AddrType, size_t> lastWrite;
+  for (size_t si = 0; si < st.size(); ++si)
+    for (Instruction *i : st[si].ins) {
+      if (dead.count(i)) continue;
+      for (const Write &w : recordWrites(*i))
+        if (w.role == WriteRole::Output) lastWrite[w.addr] = si;
+    }
+  std::map<AddrType, Instruction *> cand;   // output address -> the automorphism that every reader can read through
+  bool anyOwn = false;
+  for (size_t si = 0; si < st.size(); ++si)
+    for (Instruction *a : st[si].ins) {
+      if (a->ops != AUTO || dead.count(a) || a->galois <= 1) continue;
+      { auto w = lastWrite.find(a->operandList[0]); if (w != lastWrite.end() && w->second >= si) continue; }
+      auto r = readers.find(a->OutputOperand);
+      if (r == readers.end() || r->second.empty()) continue;   // nobody reads it inside the op: a result
+      bool ok = true;
+      for (const Reader &x : r->second) ok &= x.fold != NONE && x.ins->mod_id == a->mod_id && x.ins->OutputOperand != a->operandList[0];
+      if (!ok) continue;
+      cand[a->OutputOperand] = a;
+      for (const Reader &x : r->second) anyOwn |= x.fold == OWN_DIGIT;
+    }
+  if (anyOwn) {   // one Galois element per key-product launch
+    uint32_t g0 = 0;
+    bool uniform = true;
+    for (const Reader &x : ownDigits) {
+      auto c = cand.find((x.ins->ipSrc.empty() ? x.ins->ipX : x.ins->ipSrc)[x.digit]);
+      if (c == cand.end() || (g0 && c->second->galois != g0)) { uniform = false; break; }
+      g0 = c->second->galois;
+    }
+    if (!uniform)
+      for (auto it = cand.begin(); it != cand.end();) {
+        bool own = false;
+        for (const Reader &x : readers[it->first]) own |= x.fold == OWN_DIGIT;
+        it = own ? cand.erase(it) : std::next(it);
+      }
+  }
+  for (auto &kv : cand) {
+    Instruction *a = kv.second;
+    auto &rd = readers[kv.first];
+    for (const Reader &x : rd) {
+      if (x.fold == INTT_IN) { x.ins->operandList[0] = a->operandList[0]; x.ins->inGalois = a->galois; }
+      else if (x.fold == ADDEND) { x.ins->fAddend = a->operandList[0]; x.ins->fAddendGalois = a->galois; }
+      else {
+        x.ins->ipX[x.digit] = a->operandList[0];
+        if (!x.ins->ipSrc.empty()) x.ins->ipSrc[x.digit] = a->operandList[0];
+        x.ins->ipXGalois = a->galois;
+      }
+    }
+    rd.front().ins->refInstructions += a->refInstructions;
+    dead.insert(a);
+  }
+}
+
+// drop dead instructions and empty stages; upstream instructions of eliminated pass-through records are
+// accounted on the first surviving instruction so that the retired total still matches getTotalIns()
+void Arch::Planner::sweep() {
+  unsigned long long orphan = 0;
+  std::vector<Stage> keep;
+  for (auto &s : st) {
+    Stage t = s;
+    t.ins.clear();
+    for (Instruction *i : s.ins) {
+      if (!dead.count(i)) t.ins.push_back(i);
+      else if (i->passthrough) orphan += i->refInstructions;
+    }
+    if (!t.ins.empty()) keep.push_back(t);
+  }
+  if (!keep.empty()) keep[0].ins[0]->refInstructions += orphan;
+  st.swap(keep);
+}

@@ -107,6 +107,10 @@ int hh_op_plan(hh_op *h, char *out, uint32_t cap) {
   HH_TRY(h->op->prepare(); std::string s = h->arch->planText(); if (s.size() + 1 > cap) throw std::runtime_error("buffer too small");
          memcpy(out, s.c_str(), s.size() + 1))
 }
+int hh_op_plan_full(hh_op *h, char *out, uint32_t cap, uint32_t *need) {
+  HH_TRY(h->op->prepare(); std::string s = h->arch->planDump(); if (need) *need = (uint32_t)s.size() + 1; if (!out) return 0;
+         if (s.size() + 1 > cap) throw std::runtime_error("buffer too small"); memcpy(out, s.c_str(), s.size() + 1))
+}
 int hh_op_stage_times(hh_op *h, uint32_t iters, char *out, uint32_t cap) {
   HH_TRY(h->op->prepare(); std::string s = h->arch->stageTimes(iters); if (s.size() + 1 > cap) throw std::runtime_error("buffer too small");
          memcpy(out, s.c_str(), s.size() + 1))

@@ -94,9 +94,11 @@ def test_mixed_launch_keeps_the_wide_digits_conversion():
 
 def test_no_ring_size_is_named_in_the_planner():
     """round 6: the fusion passes ask the back-end's capability table (hm_capability, homulator_amd/csrc/hm_caps.h) — no ring size or digit
-    width is spelled out in host/src/Arch.cpp"""
+    width is spelled out in the planner: the fusion passes (host/src/Planner.cpp), the launch builder (host/src/Arch.cpp) and the description
+    of a record's reads they share (host/include/Records.h)"""
     import os
-    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "host", "src", "Arch.cpp")).read()
+    host_dir = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "host")
+    src = "".join(open(os.path.join(host_dir, *f)).read() for f in (("src", "Arch.cpp"), ("src", "Planner.cpp"), ("include", "Records.h")))
     assert not re.search(r"logN\s*[=!<>]=\s*1[3-7]", src) and "<= 15" not in src and "> 15" not in src and "n >> 12" not in src
 
 
