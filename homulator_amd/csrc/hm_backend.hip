@@ -10,6 +10,7 @@
 #include <map>
 #include <tuple>
 #include <type_traits>
+#include <utility>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -21,6 +22,7 @@
 #include "hm_ntt_core.h"
 #include "hm_params.h"
 #include "hm_caps.h"
+#include "hm_launch.h"
 
 // ------------------------------------------------------------------------------------------------
 // kernels
@@ -654,7 +656,7 @@ struct hm_ctx {
   HmW *d_twist_fwd = nullptr, *d_twist_inv = nullptr;  // [L+K][N/256][3], hm::Params::make_twist
   HmMod *d_mods = nullptr;
   std::map<std::vector<uint32_t>, uint64_t *> bconv_tables;  // key: n_in, in_ids..., out_ids...
-  std::map<std::string, void *> ntt_tables;                  // launch tables (device_table), key: their bytes
+  std::map<std::string, void *> launch_tables;                  // launch tables (device_table), key: their bytes
   int live_graphs = 0;                                        // captured graphs that reference the tables: no eviction while > 0
   // ... the graphs themselves: hm_destroy detaches them (a late hm_graph_destroy must not touch a freed context)
   std::vector<struct hm_graph *> graphs;
@@ -874,7 +876,7 @@ extern "C" void hm_destroy(hm_ctx *c) {
   if (c->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(c->comm);
   (void)hipFree(c->stage_send);
   (void)hipFree(c->stage_recv);
-  for (auto &kv : c->ntt_tables) (void)hipFree(kv.second);
+  for (auto &kv : c->launch_tables) (void)hipFree(kv.second);
   (void)hipFree(c->d_tw_fwd);
   (void)hipFree(c->d_tw_inv);
   (void)hipFree(c->d_twist_fwd);
@@ -1143,8 +1145,6 @@ extern "C" hm_status hm_timer_stop(hm_ctx *c, uint64_t *ns) {
 // ------------------------------------------------------------------------------------------------
 // launches
 // ------------------------------------------------------------------------------------------------
-static inline uint32_t limb_at(const uint32_t *l, uint32_t i) { return l ? l[i] : i; }
-
 static hm_status check_limbs(hm_ctx *c, const char *what, const uint32_t *l, uint32_t n) {
   for (uint32_t i = 0; l && i < n; ++i)
     if (l[i] > 0xFFFFu) return fail(c, HM_ERR_ARG, "%s: limb index %u exceeds 65535", what, l[i]);
@@ -1236,11 +1236,9 @@ static void launch_ntt(hm_ctx *c, const HmNttArgs &a, int form, bool firstPassOn
   // finishes.  Up to eight such kernels in flight on one GPU (contexts, instances; HIP drives four hardware queues by default) cannot
   // starve one another; the spins are bounded all the same.
   if (K.one[0] && a.n_limbs <= fused_small_entries(c) && a.logG == 0) {
+    HmNttFusedArgs f = {c->ntt_ws, c->err_dev, c->fused_test_spread, c->fused_test_timeout ? 1u << 10 : HM_SPIN_LIMIT, c->fused_test_timeout};
 #if defined(HM_FUSED_TRACE)
-    const HmNttFusedArgs f = {c->ntt_ws, c->err_dev, c->fused_test_spread, c->fused_test_timeout ? 1u << 10 : HM_SPIN_LIMIT, c->fused_test_timeout,
-        c->fused_trace};
-#else
-    const HmNttFusedArgs f = {c->ntt_ws, c->err_dev, c->fused_test_spread, c->fused_test_timeout ? 1u << 10 : HM_SPIN_LIMIT, c->fused_test_timeout};
+    f.trace = c->fused_trace;
 #endif
     if (c->capturing) c->capture_has_fused = true;
     bool inPlace = a.in == a.out;   // every limb-poly transformed onto itself: the input loads keep their lines for the hand-off
@@ -1257,21 +1255,21 @@ static void launch_ntt(hm_ctx *c, const HmNttArgs &a, int form, bool firstPassOn
 // (hm_capture_begin pins the cache); a miss while the stream is capturing is an error, not a hidden synchronisation.
 static hm_status device_table(hm_ctx *c, const void *data, size_t bytes, const void **out) {
   const std::string key(static_cast<const char *>(data), bytes);
-  auto it = c->ntt_tables.find(key);
-  if (it == c->ntt_tables.end()) {
+  auto it = c->launch_tables.find(key);
+  if (it == c->launch_tables.end()) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(c->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
       return fail(c, HM_ERR_UNSUPPORTED, "a launch table is missing while the stream is capturing: run the plan once before hm_capture_begin");
     // callers that never repeat a launch (tests): start over rather than grow without bound
-    if (c->ntt_tables.size() >= 1024 && c->live_graphs == 0 && !c->capturing) {
+    if (c->launch_tables.size() >= 1024 && c->live_graphs == 0 && !c->capturing) {
       HM_HIP(c, hipStreamSynchronize(c->stream));
-      for (auto &kv : c->ntt_tables) (void)hipFree(kv.second);
-      c->ntt_tables.clear();
+      for (auto &kv : c->launch_tables) (void)hipFree(kv.second);
+      c->launch_tables.clear();
     }
     void *dev = nullptr;
     HM_HIP(c, hipMalloc(&dev, bytes));
     HM_HIP(c, hipMemcpy(dev, data, bytes, hipMemcpyHostToDevice));
-    it = c->ntt_tables.emplace(key, dev).first;
+    it = c->launch_tables.emplace(key, dev).first;
   }
   *out = it->second;
   return HM_OK;
@@ -1328,70 +1326,34 @@ static hm_status ntt_common(hm_ctx *c, const char *what, const uint64_t *in, con
       return fail(c, HM_ERR_ARG, "%s: Galois element [%u] is not an odd number below 2N", what, g);
     anyInGalois |= gi > 1; anyAddGalois |= ga > 1;
   }
-  if (anyInGalois && in == out) {   // a gathered input is read from OTHER tiles than the one a workgroup writes: no limb-poly the call writes may be one it gathers from
-    std::vector<char> written;
-    for (uint32_t g = 0; g < n; ++g) { const uint32_t l = limb_at(out_limbs, g); if (l >= written.size()) written.resize((size_t)l + 1, 0); written[l] = 1; }
-    for (uint32_t g = 0; g < n; ++g) {
-      const uint32_t l = limb_at(in_limbs, g);
-      if (f.inGalois[g] > 1 && l < written.size() && written[l]) return fail(c, HM_ERR_ARG,
-          "%s: limb-poly [%u] is read through an automorphism from a limb the call also writes (not in place, and not onto another entry's source)", what, g);
-    }
+  if (anyInGalois) {   // a gathered input is read from OTHER tiles than the one a workgroup writes: no limb-poly the call writes may be one it gathers from
+    const int64_t g = hm_first_overlap(out, out_limbs, n, in, in_limbs, n, c->P.N, [&](uint32_t i) { return f.inGalois[i] > 1; });
+    if (g >= 0) return fail(c, HM_ERR_ARG,
+        "%s: limb-poly [%u] is read through an automorphism from a limb the call also writes (not in place, and not onto another entry's source)", what, (uint32_t)g);
   }
   if (anyInGalois && (!inverse || f.secondPassOnly)) return fail(c, HM_ERR_ARG, "%s: only the inverse transform reads its input through an automorphism", what);
   if (anyAddGalois && (!fused || f.mix || !f.addend)) return fail(c, HM_ERR_UNSUPPORTED,
       "%s: the addend is read through an automorphism by the fused forward transform without the mix prologue only", what);
-  if (anyAddGalois && f.addend == out) {   // ... from other positions than the ones a workgroup writes: no output limb-poly may be a gathered addend
-    std::vector<char> written;
-    for (uint32_t g = 0; g < n; ++g) { const uint32_t l = limb_at(out_limbs, g); if (l >= written.size()) written.resize((size_t)l + 1, 0); written[l] = 1; }
-    for (uint32_t g = 0; g < n; ++g) {
-      if (f.addGalois[g] <= 1 || (f.addend_limbs && f.addend_limbs[g] == HM_NO_LIMB)) continue;
-      const uint32_t l = limb_at(f.addend_limbs, g);
-      if (l < written.size() && written[l]) return fail(c, HM_ERR_ARG, "%s: the addend of limb-poly [%u] is read through an automorphism from a limb the call writes", what, g);
-    }
+  if (anyAddGalois) {   // ... from other positions than the ones a workgroup writes: no output limb-poly may be a gathered addend
+    const int64_t g = hm_first_overlap(out, out_limbs, n, f.addend, f.addend_limbs, n, c->P.N,
+        [&](uint32_t i) { return f.addGalois[i] > 1 && !(f.addend_limbs && f.addend_limbs[i] == HM_NO_LIMB); });
+    if (g >= 0) return fail(c, HM_ERR_ARG, "%s: the addend of limb-poly [%u] is read through an automorphism from a limb the call writes", what, (uint32_t)g);
   }
   HM_HIP(c, hipSetDevice(c->device));
-  // group limb-polys that share a modulus (see hm_block_map): G = the largest of 8, 4, 2 for which at least 7 of 8 limb-polys
-  // of the call fall into full same-modulus groups (a batch of 10 ops x 2 keys has 20 limb-polys per modulus, a 50-limb sweep
-  // of the extended basis one: G = 2 then costs nothing); leftovers of a modulus share groups with other leftovers
-  std::map<uint32_t, std::vector<int>> byMod;
-  for (uint32_t i = 0; i < n; ++i) byMod[mod_ids[i]].push_back((int)i);
-  uint32_t logG = 1;
-  // a call that will run as ONE launch (k_ntt_fused8) takes single limb-polys as groups: a kernel then has at most 15 workgroups per XCD
+  // group limb-polys that share a modulus (hm_launch.h: hm_ntt_group_policy); leftovers of a modulus share groups with other leftovers.
+  // A call that will run as ONE launch (k_ntt_fused8) takes single limb-polys as groups: a kernel then has at most 15 workgroups per XCD
   // waiting for siblings that have no slot yet (launch_ntt), and the 50-limb sweep 56 entries instead of 64
-  if (fused_small_entries(c) && !f.firstPassOnly && !f.secondPassOnly && (n + 7) / 8 * 8 <= fused_small_entries(c)) logG = 0;
-#ifndef HM_NTT_MAX_LOGG
-#define HM_NTT_MAX_LOGG 3
-#endif
-  for (uint32_t lg = HM_NTT_MAX_LOGG; lg >= 2; --lg) {
-    size_t full = 0;
-    for (auto &kv : byMod) full += kv.second.size() >> lg << lg;
-    if (full * 8 >= (size_t)n * 7 && n >= (64u << lg)) { logG = lg; break; }
-  }
-  const uint32_t G = 1u << logG;
-  std::vector<std::vector<int>> groups;  // indices into the caller's lists, -1 = empty
-  {
-    std::vector<int> rest;
-    for (auto &kv : byMod) {
-      auto &v = kv.second;
-      size_t i = 0;
-      for (; i + G <= v.size(); i += G) groups.emplace_back(v.begin() + i, v.begin() + i + G);
-      rest.insert(rest.end(), v.begin() + i, v.end());   // leftovers of one modulus stay adjacent: they still share among themselves
-    }
-    for (size_t i = 0; i < rest.size(); i += G) {
-      std::vector<int> g(rest.begin() + i, rest.begin() + std::min(rest.size(), i + G));
-      g.resize(G, -1);
-      groups.push_back(g);
-    }
-  }
+  const bool oneLaunch = fused_small_entries(c) && !f.firstPassOnly && !f.secondPassOnly && (n + 7) / 8 * 8 <= fused_small_entries(c);
+  std::vector<uint32_t> all(n);
+  for (uint32_t i = 0; i < n; ++i) all[i] = i;
+  const HmGrouping grouping = hm_group_by_modulus(mod_ids, all, hm_ntt_group_policy(oneLaunch));
+  const auto &groups = grouping.groups;
+  const uint32_t logG = grouping.logG, G = 1u << logG;
   // As few launches as the kernel-argument segment allows (HM_NTT_MAX_ENTRIES records), of equal size; the constants
   // of a launch live in a device table cached by content (plans repeat their launches)
-  // whole blocks of 8 groups (one per XCD)
-  const uint32_t maxGroups = std::max(8u, std::min<uint32_t>(HM_NTT_MAX_ENTRIES, c->ntt_launch_entries) / G / 8 * 8);
-  const uint32_t nLaunch = ((uint32_t)groups.size() + maxGroups - 1) / maxGroups;
-  const uint32_t perLaunch = nLaunch ? (((uint32_t)groups.size() + nLaunch - 1) / nLaunch + 7) / 8 * 8 : 0;
-  for (uint32_t base = 0; base < groups.size(); base += perLaunch) {
-    const uint32_t ng = std::min<uint32_t>(perLaunch, (uint32_t)groups.size() - base);
-    const uint32_t cnt = ((ng + 7) / 8) * 8 * G;  // entries: blocks of 8 groups = 8G entries
+  const HmLaunchSplit parts = hm_launch_split((uint32_t)groups.size(), std::min<uint32_t>(HM_NTT_MAX_ENTRIES, c->ntt_launch_entries), G);
+  for (uint32_t base = 0; base < groups.size(); base += parts.perLaunch) {
+    const uint32_t ng = hm_launch_groups(parts, (uint32_t)groups.size(), base), cnt = hm_launch_entries(ng, G);
     std::vector<HmNttEntry> tab(cnt);
     memset(tab.data(), 0, sizeof(HmNttEntry) * cnt);
     HmNttArgs a;
@@ -1400,7 +1362,7 @@ static hm_status ntt_common(hm_ctx *c, const char *what, const uint64_t *in, con
       for (uint32_t which = 0; which < G; ++which) {
         const int gi = groups[base + kk][which];
         if (gi < 0) continue;
-        const uint32_t g = (uint32_t)gi, e = (kk / 8) * 8 * G + which * 8 + (kk % 8), m = mod_ids[g];
+        const uint32_t g = (uint32_t)gi, e = hm_entry_slot(kk, which, G), m = mod_ids[g];
         const uint64_t q = c->P.mod[m];
         HmNttEntry &t = tab[e];
         a.limb[e] = HmLimb{(uint16_t)limb_at(in_limbs, g), (uint16_t)limb_at(out_limbs, g), (uint16_t)m, 0};
@@ -1435,14 +1397,10 @@ static hm_status ntt_common(hm_ctx *c, const char *what, const uint64_t *in, con
     a.minuend = f.minuend; a.addend = f.addend; a.mix = f.mix;
     a.logN = c->P.logN; a.n_limbs = cnt; a.logG = logG;
     const int form = inverse ? (anyInGalois ? 4 : 3) : fused ? (f.mix ? 2 : anyAddGalois ? 5 : 1) : 0;
-    switch (c->P.logN - HM_ROW_LOG) {
-    case 5: launch_ntt<5>(c, a, form, f.firstPassOnly, f.secondPassOnly); break;
-    case 6: launch_ntt<6>(c, a, form, f.firstPassOnly, f.secondPassOnly); break;
-    case 7: launch_ntt<7>(c, a, form, f.firstPassOnly, f.secondPassOnly); break;
-    case 8: launch_ntt<8>(c, a, form, f.firstPassOnly, f.secondPassOnly); break;
-    case 9: launch_ntt<9>(c, a, form, f.firstPassOnly, f.secondPassOnly); break;
-    default: return fail(c, HM_ERR_UNSUPPORTED, "%s: logN %u", what, c->P.logN);
-    }
+    static void (*const launch[])(hm_ctx *, const HmNttArgs &, int, bool, bool) = {launch_ntt<5>, launch_ntt<6>, launch_ntt<7>, launch_ntt<8>, launch_ntt<9>};
+    const uint32_t log1 = c->P.logN - HM_ROW_LOG;   // the COL pass's sub-transform length
+    if (log1 < 5 || log1 > 9) return fail(c, HM_ERR_UNSUPPORTED, "%s: logN %u", what, c->P.logN);
+    launch[log1 - 5](c, a, form, f.firstPassOnly, f.secondPassOnly);
     HM_HIP(c, hipGetLastError());
   }
   return HM_OK;
@@ -1492,12 +1450,12 @@ extern "C" hm_status hm_ntt_sub_scale(hm_ctx *c, const uint64_t *in, const uint3
   return ntt_common(c, "hm_ntt_sub_scale", in, in_limbs, out, out_limbs, mod_ids, n, 0, k, f);
 }
 
-static hm_status bconv_col_launch(hm_ctx *c, const hm_bconv_desc *descs, uint32_t n_desc, const struct BcolMix *mix, uint32_t tile0 = 0, uint32_t n_tiles = 0);
 struct BcolMix {   // the MODE 4 prologue of a fused conversion (x = conv + k * mix): per conversion, per output, the operand's limb and the constant
   const uint64_t *mix;
   const uint32_t *const *mix_limbs;
   const uint64_t *const *mix_k;
 };
+static hm_status bconv_col_launch(hm_ctx *c, const hm_bconv_desc *descs, uint32_t n_desc, const BcolMix *mix, uint32_t tile0 = 0, uint32_t n_tiles = 0);
 extern "C" hm_status hm_ntt_mix_sub_scale(hm_ctx *c, const hm_ntt_fused_desc *d) {
   if (!c) return HM_ERR_ARG;
   if (!d || (!d->in && !d->n_conv) || !d->out || !d->minuend || !d->k) return fail(c, HM_ERR_ARG, "hm_ntt_mix_sub_scale: null argument");
@@ -1620,6 +1578,11 @@ template <int OP>
 static void launch_ewe(hm_ctx *c, const HmEweArgs &a) {
   hipLaunchKernelGGL((k_ewe<OP>), dim3(a.n_limbs * (c->P.N / (512 * HM_EWE_UNITS))), dim3(256), 0, c->stream, a);
 }
+template <int... OP>
+static void launch_ewe_op(std::integer_sequence<int, OP...>, int op, hm_ctx *c, const HmEweArgs &a) {
+  static void (*const launch[])(hm_ctx *, const HmEweArgs &) = {launch_ewe<OP>...};   // one instantiation per opcode, in HmEweOp's order
+  launch[op](c, a);
+}
 
 extern "C" hm_status hm_ewe(hm_ctx *c, int op, const uint64_t *pa, const uint32_t *la, const uint64_t *pb,
                             const uint32_t *lb, const uint64_t *pc, const uint32_t *lc, const uint64_t *pd,
@@ -1653,17 +1616,7 @@ extern "C" hm_status hm_ewe(hm_ctx *c, int op, const uint64_t *pa, const uint32_
         a.k[i] = HmTw{k[g], hm::shoup(k[g], c->P.mod[m])};
       }
     }
-    switch (op) {
-    case HM_EWE_MUL: launch_ewe<HM_EWE_MUL>(c, a); break;
-    case HM_EWE_MAC2: launch_ewe<HM_EWE_MAC2>(c, a); break;
-    case HM_EWE_MAC_ADD: launch_ewe<HM_EWE_MAC_ADD>(c, a); break;
-    case HM_EWE_ADD: launch_ewe<HM_EWE_ADD>(c, a); break;
-    case HM_EWE_SUB: launch_ewe<HM_EWE_SUB>(c, a); break;
-    case HM_EWE_MUL_CONST: launch_ewe<HM_EWE_MUL_CONST>(c, a); break;
-    case HM_EWE_SUB_SCALE: launch_ewe<HM_EWE_SUB_SCALE>(c, a); break;
-    case HM_EWE_COPY: launch_ewe<HM_EWE_COPY>(c, a); break;
-    case HM_EWE_SUB_SCALE_ADD: launch_ewe<HM_EWE_SUB_SCALE_ADD>(c, a); break;
-    }
+    launch_ewe_op(std::make_integer_sequence<int, HM_EWE_NOPS>{}, op, c, a);
     HM_HIP(c, hipGetLastError());
   }
   return HM_OK;
@@ -1688,11 +1641,9 @@ extern "C" hm_status hm_inner_product_ex(hm_ctx *c, const hm_ip_desc *d) {
   const uint32_t n = d->n, n_terms = d->n_terms, n_out = d->n_out;
   if (d->x_galois && (!(d->x_galois & 1) || d->x_galois >= 2 * c->P.N)) return fail(c, HM_ERR_ARG, "hm_inner_product: x_galois is not an odd number below 2N");
   if (!x || !y || !out || !x_limbs || !y_limbs || !out_limbs) return fail(c, HM_ERR_ARG, "hm_inner_product: null argument");
-  if (d->x_galois > 1 && x == out) {   // gathered operands come from other positions than the ones a workgroup writes
-    for (uint32_t i = 0; i < n * n_terms; ++i)
-      for (uint32_t k = 0; k < n * n_out; ++k)
-        if (x_limbs[i] == out_limbs[k]) return fail(c, HM_ERR_ARG, "hm_inner_product: an operand read through the automorphism is a limb the call writes");
-  }
+  // gathered operands come from other positions than the ones a workgroup writes
+  if (d->x_galois > 1 && hm_limbs_overlap(out, out_limbs, n * n_out, x, x_limbs, n * n_terms, c->P.N))
+    return fail(c, HM_ERR_ARG, "hm_inner_product: an operand read through the automorphism is a limb the call writes");
   if (n_terms == 0 || n_terms > HM_IP_MAX_TERMS || n_out == 0 || n_out > HM_IP_MAX_OUT)
     return fail(c, HM_ERR_ARG, "hm_inner_product: n_terms in [1,%d], n_out in [1,%d]", HM_IP_MAX_TERMS, HM_IP_MAX_OUT);
   hm_status st;
@@ -1783,23 +1734,6 @@ __global__ void __launch_bounds__(256) k_inner_product_hoisted(HmIpHoistArgs a) 
   }
 }
 
-// does a limb-poly of (ib, il[0..ni)) share an address with a limb-poly of (ob, ol[0..no))?  Compared as address RANGES (base + limb x N words),
-// so that different base pointers into one allocation are caught as well
-static bool limb_ranges_overlap(const uint64_t *ob, const uint32_t *ol, uint32_t no, const uint64_t *ib, const uint32_t *il, uint32_t ni, uint32_t N) {
-  uint32_t top = 0;
-  for (uint32_t i = 0; i < no; ++i) top = std::max(top, ol[i]);
-  std::vector<uint8_t> written((size_t)top + 1, 0);
-  for (uint32_t i = 0; i < no; ++i) written[ol[i]] = 1;
-  const int64_t lb = (int64_t)N * 8, base = (int64_t)(reinterpret_cast<intptr_t>(ib) - reinterpret_cast<intptr_t>(ob));
-  for (uint32_t i = 0; i < ni; ++i) {
-    const int64_t s = base + (int64_t)il[i] * lb;                   // bytes [s, s + lb) from the output base
-    const int64_t o0 = s >= 0 ? s / lb : -((-s + lb - 1) / lb);     // output limb-polys touched: o0, and o0 + 1 unless s is aligned to one
-    for (int64_t o = o0; o <= o0 + (s != o0 * lb ? 1 : 0); ++o)
-      if (o >= 0 && o <= (int64_t)top && written[(size_t)o]) return true;
-  }
-  return false;
-}
-
 extern "C" hm_status hm_inner_product_hoisted(hm_ctx *c, const hm_ip_hoisted_desc *d) {
   if (!c) return HM_ERR_ARG;
   if (!d || !d->x || !d->x_limbs || !d->y || !d->y_limbs || !d->out || !d->out_limbs || !d->mod_ids || !d->galois)
@@ -1814,9 +1748,9 @@ extern "C" hm_status hm_inner_product_hoisted(hm_ctx *c, const hm_ip_hoisted_des
       (st = check_limbs(c, "hm_inner_product_hoisted", d->out_limbs, R * n * 2)) || (st = check_mods(c, "hm_inner_product_hoisted", d->mod_ids, n)))
     return st;
   // every output is stored at other positions than the ones its workgroup reads (the scatter of sigma_r): it may overlap no digit and no key
-  if (limb_ranges_overlap(d->out, d->out_limbs, R * n * 2, d->x, d->x_limbs, n * T, N))
+  if (hm_limbs_overlap(d->out, d->out_limbs, R * n * 2, d->x, d->x_limbs, n * T, N))
     return fail(c, HM_ERR_ARG, "hm_inner_product_hoisted: an output limb-poly overlaps a digit (x)");
-  if (limb_ranges_overlap(d->out, d->out_limbs, R * n * 2, d->y, d->y_limbs, R * n * 2 * T, N))
+  if (hm_limbs_overlap(d->out, d->out_limbs, R * n * 2, d->y, d->y_limbs, R * n * 2 * T, N))
     return fail(c, HM_ERR_ARG, "hm_inner_product_hoisted: an output limb-poly overlaps a key limb-poly (y)");
   if (n == 0) return HM_OK;
   std::vector<HmIpHoistRec> recs((size_t)R * n);
@@ -1855,6 +1789,28 @@ extern "C" hm_status hm_inner_product_hoisted(hm_ctx *c, const hm_ip_hoisted_des
   return HM_OK;
 }
 
+// The kernel of hm_ntt_inner_product's second launch: OUTS keys; INVOUT 0 = outputs in evaluation form, 1 = every limb's outputs leave as the
+// first pass of their inverse transform (the generic chain: a launch of their own), 2 = per limb (mont32: one launch); XG = evaluation-form
+// operands read through an automorphism (round 6, hm_ntt_ip_desc.x_galois); SMALL = the small-launch geometry.  nullptr: the form the other
+// back-end has
+typedef void (*nip_kernel)(HmNipArgs);
+template <int OUTS, int INVOUT, bool XG, bool SMALL>
+static constexpr nip_kernel nip_kernel_of() {
+  if constexpr (INVOUT == (HM_GENERIC ? 2 : 1)) return nullptr;
+  else if constexpr (SMALL) return k_ntt_row_ip8<OUTS, INVOUT, XG>;
+  else return k_ntt_row_ip<OUTS, INVOUT, XG>;
+}
+template <bool XG, bool SMALL>
+static nip_kernel nip_kernel_pick(uint32_t outs, int invForm) {
+  static const nip_kernel kern[HM_NIP_MAX_OUT][3] = {
+      {nip_kernel_of<1, 0, XG, SMALL>(), nip_kernel_of<1, 1, XG, SMALL>(), nip_kernel_of<1, 2, XG, SMALL>()},
+      {nip_kernel_of<2, 0, XG, SMALL>(), nip_kernel_of<2, 1, XG, SMALL>(), nip_kernel_of<2, 2, XG, SMALL>()}};
+  return kern[outs - 1][invForm];
+}
+static nip_kernel nip_kernel_for(uint32_t outs, int invForm, bool xg, bool small) {
+  return (xg ? (small ? nip_kernel_pick<true, true> : nip_kernel_pick<true, false>) : (small ? nip_kernel_pick<false, true> : nip_kernel_pick<false, false>))(outs, invForm);
+}
+
 // K1 x K5: out[i][k] = sum_j X_j[i] * y[i][k][j] with X_j[i] = NTT(x[i][j]) for the digits that go through
 // the transform (x_is_coeff) and x[i][j] itself for a digit's own limbs.  Two launches: the COL pass of every transformed
 // (limb, digit) into `hand`, then k_ntt_row_ip: ROW pass, product with both keys, accumulation over the digits in registers.
@@ -1871,13 +1827,9 @@ extern "C" hm_status hm_ntt_inner_product(hm_ctx *c, const hm_ntt_ip_desc *d) {
       if (d->out_inverse[i]) return fail(c, HM_ERR_UNSUPPORTED, "hm_ntt_inner_product: out_inverse needs N = 2^15 or 2^16");
   }
   if (d->x_galois && (!(d->x_galois & 1) || d->x_galois >= 2 * c->P.N)) return fail(c, HM_ERR_ARG, "hm_ntt_inner_product: x_galois is not an odd number below 2N");
-  if (d->x_galois > 1 && d->x == d->out) {   // gathered operands come from other positions than the ones a workgroup writes
-    std::vector<char> written;
-    for (uint32_t i = 0; i < n * K; ++i) { const uint32_t l = d->out_limbs[i]; if (l >= written.size()) written.resize((size_t)l + 1, 0); written[l] = 1; }
-    for (uint32_t i = 0; i < n * T; ++i)
-      if (!d->x_is_coeff[i] && d->x_limbs[i] < written.size() && written[d->x_limbs[i]]) return fail(c, HM_ERR_ARG,
-          "hm_ntt_inner_product: an operand read through the automorphism is a limb the call writes");
-  }
+  // gathered operands (the evaluation-form digits) come from other positions than the ones a workgroup writes
+  if (d->x_galois > 1 && hm_first_overlap(d->out, d->out_limbs, n * K, d->x, d->x_limbs, n * T, c->P.N, [&](uint32_t i) { return !d->x_is_coeff[i]; }) >= 0)
+    return fail(c, HM_ERR_ARG, "hm_ntt_inner_product: an operand read through the automorphism is a limb the call writes");
   hm_status st;
   if ((st = check_limbs(c, "hm_ntt_inner_product", d->x_limbs, n * T)) || (st = check_limbs(c, "hm_ntt_inner_product", d->y_limbs, n * T * K)) ||
       (st = check_limbs(c, "hm_ntt_inner_product", d->out_limbs, n * K)) || (st = check_mods(c, "hm_ntt_inner_product", d->mod_ids, n)))
@@ -1927,55 +1879,25 @@ extern "C" hm_status hm_ntt_inner_product(hm_ctx *c, const hm_ntt_ip_desc *d) {
   for (int set = 0; set < (split ? 2 : 1); ++set) {
   auto inSet = [&](uint32_t i) { return !split || (d->out_inverse[i] ? 1 : 0) == set; };
   const int invForm = !anyInv ? 0 : split ? set : 2;
-  std::map<uint32_t, std::vector<uint32_t>> byMod;
-  uint32_t nSet = 0;
+  std::vector<uint32_t> members;
   for (uint32_t i = 0; i < n; ++i)
-    if (inSet(i)) { byMod[d->mod_ids[i]].push_back(i); ++nSet; }
-  if (!nSet) continue;
-  uint32_t logG = 0;
-  for (uint32_t lg = 3; lg >= 1; --lg) {
-    size_t full = 0;
-    for (auto &kv : byMod) full += kv.second.size() >> lg << lg;
-    if (full * 8 >= (size_t)nSet * 7 && nSet >= (8u << lg)) { logG = lg; break; }
-  }
-  const uint32_t G = 1u << logG;
-  std::vector<std::vector<int>> groups;
-  {
-    std::vector<int> rest;
-    for (auto &kv : byMod) {
-      auto &v = kv.second;
-      size_t i = 0;
-      for (; i + G <= v.size(); i += G) groups.emplace_back(v.begin() + i, v.begin() + i + G);
-      rest.insert(rest.end(), v.begin() + i, v.end());
-    }
-    for (size_t i = 0; i < rest.size(); i += G) {
-      std::vector<int> g(rest.begin() + i, rest.begin() + std::min(rest.size(), i + G));
-      g.resize(G, -1);
-      groups.push_back(g);
-    }
-  }
+    if (inSet(i)) members.push_back(i);
+  if (members.empty()) continue;
+  HmGrouping grouping = hm_group_by_modulus(d->mod_ids, members, hm_nip_group_policy());
+  auto &groups = grouping.groups;
+  const uint32_t logG = grouping.logG, G = 1u << logG;
   // longest first: a limb whose digits all go through the transform (the special limbs of a ModUp: beta transforms) costs more than one
   // with a digit of its own; workgroups are dispatched in entry order, so the heavy ones start first and the partly filled last round of a
   // small launch holds light ones
-  {
-    auto weight = [&](const std::vector<int> &g) {
-      uint32_t w = 0;
-      for (int gi : g)
-        if (gi >= 0)
-          {
-            for (uint32_t j = 0; j < T; ++j) w += d->x_is_coeff[(uint32_t)gi * T + j] ? 3 : 1;
-            if (d->out_inverse && d->out_inverse[gi]) w += 2 * K;   // ... and an inverse first pass per output on top
-          }
-      return w;
-    };
-    std::stable_sort(groups.begin(), groups.end(), [&](const std::vector<int> &a, const std::vector<int> &b) { return weight(a) > weight(b); });
-  }
-  const uint32_t maxGroups = HM_NIP_MAX_LIMBS / G / 8 * 8;
-  const uint32_t nLaunch = ((uint32_t)groups.size() + maxGroups - 1) / maxGroups;
-  const uint32_t perLaunch = nLaunch ? (((uint32_t)groups.size() + nLaunch - 1) / nLaunch + 7) / 8 * 8 : 0;
-  for (uint32_t base = 0; base < groups.size(); base += perLaunch) {
-    const uint32_t ng = std::min<uint32_t>(perLaunch, (uint32_t)groups.size() - base);
-    const uint32_t cnt = ((ng + 7) / 8) * 8 * G;
+  hm_sort_groups_heaviest_first(groups, [&](uint32_t i) {
+    uint32_t w = 0;
+    for (uint32_t j = 0; j < T; ++j) w += d->x_is_coeff[i * T + j] ? 3 : 1;
+    if (d->out_inverse && d->out_inverse[i]) w += 2 * K;   // ... and an inverse first pass per output on top
+    return w;
+  });
+  const HmLaunchSplit parts = hm_launch_split((uint32_t)groups.size(), HM_NIP_MAX_LIMBS, G);
+  for (uint32_t base = 0; base < groups.size(); base += parts.perLaunch) {
+    const uint32_t ng = hm_launch_groups(parts, (uint32_t)groups.size(), base), cnt = hm_launch_entries(ng, G);
     HmNipArgs a;
     std::vector<HmNipLimb> recs(cnt);
     memset(recs.data(), 0, sizeof(HmNipLimb) * cnt);
@@ -1984,7 +1906,7 @@ extern "C" hm_status hm_ntt_inner_product(hm_ctx *c, const hm_ntt_ip_desc *d) {
       for (uint32_t which = 0; which < G; ++which) {
         const int gi = groups[base + kk][which];
         if (gi < 0) continue;
-        const uint32_t i = (uint32_t)gi, e = (kk / 8) * 8 * G + which * 8 + (kk % 8);
+        const uint32_t i = (uint32_t)gi, e = hm_entry_slot(kk, which, G);
         HmNipLimb &l = recs[e];
         l.mod = (uint16_t)d->mod_ids[i];
         for (uint32_t j = 0; j < T; ++j) {
@@ -2003,27 +1925,10 @@ extern "C" hm_status hm_ntt_inner_product(hm_ctx *c, const hm_ntt_ip_desc *d) {
     a.tw = c->d_tw_fwd; a.twist = c->d_twist_fwd; a.tw_inv = c->d_tw_inv; a.twist_inv = c->d_twist_inv; a.mods = c->d_mods;
     a.logN = c->P.logN; a.n_limbs = cnt; a.logG = logG; a.n_terms = T;
     const dim3 grid(cnt * (c->P.N >> HM_TL_ROW)), block((1 << HM_TL_ROW) / HM_EPT);
-    typedef void (*nip_kernel)(HmNipArgs);
-#if HM_GENERIC
-    static const nip_kernel kern[2][3] = {{k_ntt_row_ip<1, 0>, k_ntt_row_ip<1, 1>, nullptr}, {k_ntt_row_ip<2, 0>, k_ntt_row_ip<2, 1>, nullptr}};
-    static const nip_kernel kern8[2][3] = {{k_ntt_row_ip8<1, 0>, k_ntt_row_ip8<1, 1>, nullptr}, {k_ntt_row_ip8<2, 0>, k_ntt_row_ip8<2, 1>, nullptr}};
-#else
-    static const nip_kernel kern[2][3] = {{k_ntt_row_ip<1, 0>, nullptr, k_ntt_row_ip<1, 2>}, {k_ntt_row_ip<2, 0>, nullptr, k_ntt_row_ip<2, 2>}};
-    static const nip_kernel kern8[2][3] = {{k_ntt_row_ip8<1, 0>, nullptr, k_ntt_row_ip8<1, 2>}, {k_ntt_row_ip8<2, 0>, nullptr, k_ntt_row_ip8<2, 2>}};
-#endif
-    // (round 6) the same with the evaluation-form operands read through an automorphism (hm_ntt_ip_desc.x_galois)
-#if HM_GENERIC
-    static const nip_kernel kernG[2][3] = {{k_ntt_row_ip<1, 0, true>, k_ntt_row_ip<1, 1, true>, nullptr}, {k_ntt_row_ip<2, 0, true>, k_ntt_row_ip<2, 1, true>, nullptr}};
-    static const nip_kernel kern8G[2][3] = {{k_ntt_row_ip8<1, 0, true>, k_ntt_row_ip8<1, 1, true>, nullptr}, {k_ntt_row_ip8<2, 0, true>, k_ntt_row_ip8<2, 1, true>, nullptr}};
-#else
-    static const nip_kernel kernG[2][3] = {{k_ntt_row_ip<1, 0, true>, nullptr, k_ntt_row_ip<1, 2, true>}, {k_ntt_row_ip<2, 0, true>, nullptr, k_ntt_row_ip<2, 2, true>}};
-    static const nip_kernel kern8G[2][3] = {{k_ntt_row_ip8<1, 0, true>, nullptr, k_ntt_row_ip8<1, 2, true>}, {k_ntt_row_ip8<2, 0, true>, nullptr, k_ntt_row_ip8<2, 2, true>}};
-#endif
-    const bool xg = d->x_galois > 1;
     a.x_galois = d->x_galois;
     // small launches (one op at a time: 50 limb records = 800 workgroups on 768 slots of the wide form) take the small-launch geometry
-    if (cnt <= small_entries(c, c->nip_small)) hipLaunchKernelGGL((xg ? kern8G : kern8)[K - 1][invForm], grid, dim3((1 << HM_TL_ROW) / 8), 0, c->stream, a);
-    else hipLaunchKernelGGL((xg ? kernG : kern)[K - 1][invForm], grid, block, 0, c->stream, a);
+    const bool small = cnt <= small_entries(c, c->nip_small);
+    hipLaunchKernelGGL(nip_kernel_for(K, invForm, d->x_galois > 1, small), grid, small ? dim3((1 << HM_TL_ROW) / 8) : block, 0, c->stream, a);
     HM_HIP(c, hipGetLastError());
   }
   }   // sets
@@ -2054,6 +1959,49 @@ extern "C" hm_status hm_bconv_consts(hm_ctx *c, const uint32_t *in_ids, uint32_t
   return HM_OK;
 }
 
+// What hm_bconv_batch ("hm_bconv") and the fused conversion check of every descriptor.  `max_in`: the widest input basis the caller's kernels take
+// (`wide` / `note`: how the caller reports a wider one)
+static hm_status check_bconv_desc(hm_ctx *c, const char *what, const hm_bconv_desc &d, uint32_t max_in, hm_status wide = HM_ERR_ARG, const char *note = "") {
+  if (d.n_in == 0 || d.n_in > max_in) return fail(c, wide, "%s: n_in %u not in [1,%u]%s", what, d.n_in, max_in, note);
+  if (d.n_out == 0 || d.n_out > HM_BCONV_MAX_OUT) return fail(c, HM_ERR_ARG, "%s: n_out %u not in [1,%d]", what, d.n_out, HM_BCONV_MAX_OUT);
+  hm_status st;
+  if ((st = check_limbs(c, what, d.in_limbs, d.n_in)) || (st = check_limbs(c, what, d.out_limbs, d.n_out)) ||
+      (st = check_mods(c, what, d.in_ids, d.n_in)) || (st = check_mods(c, what, d.out_ids, d.n_out)))
+    return st;
+  for (uint32_t i = 0; i < d.n_in; ++i)
+    for (uint32_t t = 0; t < d.n_out; ++t)
+      if (d.in_ids[i] == d.out_ids[t]) return fail(c, HM_ERR_ARG, "%s: modulus %u is in both bases", what, d.in_ids[i]);
+  return HM_OK;
+}
+
+// The device table of a conversion, cached per (input basis, output basis, kernel width); built and uploaded on first use.  Format: [n_out][row],
+// row = HM_BCONV_ROW(kn): one output's factors contiguous and padded (wide scalar loads), Montgomery form, split-30 packed; kn = the input-basis
+// size of the kernel that reads it (> n_in: a narrow digit in the widest digit's kernel, zero columns for the inputs it does not have: a table
+// of its own).  Behind the rows: {q, -q^-1} per output (HmQn), *qn
+static hm_status bconv_table(hm_ctx *c, const hm_bconv_desc &d, uint32_t kn, const uint64_t **table, const uint64_t **qn) {
+  std::vector<uint32_t> key;
+  key.push_back(d.n_in | (kn != d.n_in ? kn << 16 : 0u));
+  key.insert(key.end(), d.in_ids, d.in_ids + d.n_in);
+  key.insert(key.end(), d.out_ids, d.out_ids + d.n_out);
+  const uint32_t row = HM_BCONV_ROW(kn);
+  auto it = c->bconv_tables.find(key);
+  if (it == c->bconv_tables.end()) {
+    std::vector<uint64_t> qh(d.n_in), tb((size_t)d.n_in * d.n_out);
+    c->P.bconv_consts(d.in_ids, d.n_in, d.out_ids, d.n_out, qh.data(), tb.data());
+    std::vector<uint64_t> tt((size_t)row * d.n_out, 0);
+    for (uint32_t i = 0; i < d.n_in; ++i)
+      for (uint32_t t = 0; t < d.n_out; ++t) tt[(size_t)t * row + i] = hm_bconv_entry(tb[(size_t)i * d.n_out + t], c->P.modc[d.out_ids[t]]);
+    for (uint32_t t = 0; t < d.n_out; ++t) { tt.push_back(c->P.modc[d.out_ids[t]].q); tt.push_back(c->P.modc[d.out_ids[t]].nqinv); }
+    uint64_t *dev = nullptr;
+    HM_HIP(c, hipMalloc(&dev, 8ull * tt.size()));
+    HM_HIP(c, hipMemcpy(dev, tt.data(), 8ull * tt.size(), hipMemcpyHostToDevice));
+    it = c->bconv_tables.emplace(key, dev).first;
+  }
+  *table = it->second;
+  *qn = it->second + (size_t)row * d.n_out;
+  return HM_OK;
+}
+
 extern "C" hm_status hm_bconv_batch(hm_ctx *c, const hm_bconv_desc *descs, uint32_t n_desc) {
   if (!c) return HM_ERR_ARG;
   if (!descs || n_desc == 0) return fail(c, HM_ERR_ARG, "hm_bconv_batch: no problems");
@@ -2065,45 +2013,13 @@ extern "C" hm_status hm_bconv_batch(hm_ctx *c, const hm_bconv_desc *descs, uint3
     const hm_bconv_desc &d = descs[pi];
     if (!d.in || !d.out) return fail(c, HM_ERR_ARG, "hm_bconv: null buffer");
     if ((d.log_len ? d.log_len : c->P.logN) != logN) return fail(c, HM_ERR_ARG, "hm_bconv_batch: mixed log_len");
-    if (d.n_in == 0 || d.n_in > HM_BCONV_MAX_IN) return fail(c, HM_ERR_ARG, "hm_bconv: n_in %u not in [1,%d]", d.n_in, HM_BCONV_MAX_IN);
-    if (d.n_out == 0 || d.n_out > HM_BCONV_MAX_OUT) return fail(c, HM_ERR_ARG, "hm_bconv: n_out %u not in [1,%d]", d.n_out, HM_BCONV_MAX_OUT);
     hm_status st;
-    if ((st = check_limbs(c, "hm_bconv", d.in_limbs, d.n_in)) || (st = check_limbs(c, "hm_bconv", d.out_limbs, d.n_out)) ||
-        (st = check_mods(c, "hm_bconv", d.in_ids, d.n_in)) || (st = check_mods(c, "hm_bconv", d.out_ids, d.n_out)))
-      return st;
-    for (uint32_t i = 0; i < d.n_in; ++i)
-      for (uint32_t t = 0; t < d.n_out; ++t)
-        if (d.in_ids[i] == d.out_ids[t]) return fail(c, HM_ERR_ARG, "hm_bconv: modulus %u is in both bases", d.in_ids[i]);
-    // conversion tables are cached per (input basis, output basis); built and uploaded on first use
-    std::vector<uint32_t> key;
-    key.push_back(d.n_in);
-    key.insert(key.end(), d.in_ids, d.in_ids + d.n_in);
-    key.insert(key.end(), d.out_ids, d.out_ids + d.n_out);
-    auto it = c->bconv_tables.find(key);
-    if (it == c->bconv_tables.end()) {
-      std::vector<uint64_t> qh(d.n_in), tb((size_t)d.n_in * d.n_out);
-      c->P.bconv_consts(d.in_ids, d.n_in, d.out_ids, d.n_out, qh.data(), tb.data());
-      const uint32_t row = HM_BCONV_ROW(d.n_in);
-      {  // device format: [n_out][row] (one output's factors contiguous and padded: wide scalar loads), Montgomery form, split-30 packed
-        std::vector<uint64_t> tt((size_t)row * d.n_out, 0);
-        for (uint32_t i = 0; i < d.n_in; ++i)
-          for (uint32_t t = 0; t < d.n_out; ++t) tt[(size_t)t * row + i] = hm_bconv_entry(tb[(size_t)i * d.n_out + t], c->P.modc[d.out_ids[t]]);
-        tb.swap(tt);
-      }
-      for (uint32_t t = 0; t < d.n_out; ++t) {  // behind the rows: {q, -q^-1} per output (HmQn)
-        tb.push_back(c->P.modc[d.out_ids[t]].q);
-        tb.push_back(c->P.modc[d.out_ids[t]].nqinv);
-      }
-      uint64_t *dev = nullptr;
-      HM_HIP(c, hipMalloc(&dev, 8ull * tb.size()));
-      HM_HIP(c, hipMemcpy(dev, tb.data(), 8ull * tb.size(), hipMemcpyHostToDevice));
-      it = c->bconv_tables.emplace(key, dev).first;
-    }
+    if ((st = check_bconv_desc(c, "hm_bconv", d, HM_BCONV_MAX_IN))) return st;
     HmBconvProb &p = probs[pi];
     memset(&p, 0, sizeof p);
-    p.in = d.in; p.out = d.out; p.table = it->second; p.n_in = d.n_in; p.n_out = d.n_out;
+    if ((st = bconv_table(c, d, d.n_in, &p.table, &p.qn))) return st;
+    p.in = d.in; p.out = d.out; p.n_in = d.n_in; p.n_out = d.n_out;
     p.in_packed = d.in_packed ? 1u : 0u;
-    p.qn = it->second + (size_t)HM_BCONV_ROW(d.n_in) * d.n_out;
     for (uint32_t i = 0; i < d.n_in; ++i) p.in_limb[i] = limb_at(d.in_limbs, i);
     for (uint32_t t = 0; t < d.n_out; ++t) {
       p.out_limb[t] = limb_at(d.out_limbs, t);
@@ -2219,39 +2135,14 @@ static hm_status bconv_col_launch(hm_ctx *c, const hm_bconv_desc *descs, uint32_
     const uint32_t kn = kernelNin[pi];   // the input-basis size of the kernel this conversion runs (>= d.n_in)
     if (!d.in || !d.out || !d.in_ids || !d.out_ids) return fail(c, HM_ERR_ARG, "fused conversion: null argument");
     const uint32_t maxIn = mix ? hm_caps(c->P.logN).bcol_max_in_mix : hm_caps(c->P.logN).bcol_max_in;
-    if (d.n_in == 0 || d.n_in > maxIn) return fail(c, HM_ERR_UNSUPPORTED, "fused conversion: n_in %u not in [1,%u]%s", d.n_in, maxIn, mix ?
-        " (with the mix prologue)" : "");
-    if (d.n_out == 0 || d.n_out > HM_BCONV_MAX_OUT) return fail(c, HM_ERR_ARG, "fused conversion: n_out %u not in [1,%d]", d.n_out, HM_BCONV_MAX_OUT);
+    hm_status cst;
+    if ((cst = check_bconv_desc(c, "fused conversion", d, maxIn, HM_ERR_UNSUPPORTED, mix ? " (with the mix prologue)" : ""))) return cst;
     if (d.log_len && d.log_len != c->P.logN) return fail(c, HM_ERR_UNSUPPORTED, "fused conversion: whole limb-polys only");
     if (d.out != descs[0].out) return fail(c, HM_ERR_ARG, "fused conversion: one hand-off buffer per call");
-    hm_status cst;
-    if ((cst = check_limbs(c, "fused conversion", d.in_limbs, d.n_in)) || (cst = check_limbs(c, "fused conversion", d.out_limbs, d.n_out)) ||
-        (cst = check_mods(c, "fused conversion", d.in_ids, d.n_in)) || (cst = check_mods(c, "fused conversion", d.out_ids, d.n_out)))
-      return cst;
-    for (uint32_t i = 0; i < d.n_in; ++i)
-      for (uint32_t t = 0; t < d.n_out; ++t)
-        if (d.in_ids[i] == d.out_ids[t]) return fail(c, HM_ERR_ARG, "fused conversion: modulus %u is in both bases", d.in_ids[i]);
-    std::vector<uint32_t> key;
-    key.push_back(d.n_in | (kn != d.n_in ? kn << 16 : 0u));   // (a table padded to a wider kernel's rows is a table of its own)
-    key.insert(key.end(), d.in_ids, d.in_ids + d.n_in);
-    key.insert(key.end(), d.out_ids, d.out_ids + d.n_out);
-    auto it = c->bconv_tables.find(key);
-    if (it == c->bconv_tables.end()) {
-      std::vector<uint64_t> qh(d.n_in), tb((size_t)d.n_in * d.n_out);
-      c->P.bconv_consts(d.in_ids, d.n_in, d.out_ids, d.n_out, qh.data(), tb.data());
-      const uint32_t row = HM_BCONV_ROW(kn);
-      std::vector<uint64_t> tt((size_t)row * d.n_out, 0);
-      for (uint32_t i = 0; i < d.n_in; ++i)
-        for (uint32_t t = 0; t < d.n_out; ++t) tt[(size_t)t * row + i] = hm_bconv_entry(tb[(size_t)i * d.n_out + t], c->P.modc[d.out_ids[t]]);
-      for (uint32_t t = 0; t < d.n_out; ++t) { tt.push_back(c->P.modc[d.out_ids[t]].q); tt.push_back(c->P.modc[d.out_ids[t]].nqinv); }
-      uint64_t *dev = nullptr;
-      HM_HIP(c, hipMalloc(&dev, 8ull * tt.size()));
-      HM_HIP(c, hipMemcpy(dev, tt.data(), 8ull * tt.size(), hipMemcpyHostToDevice));
-      it = c->bconv_tables.emplace(key, dev).first;
-    }
     HmBcolProb p;
     memset(&p, 0, sizeof p);
-    p.in = d.in; p.table = it->second; p.qn = it->second + (size_t)HM_BCONV_ROW(kn) * d.n_out; p.n_in = d.n_in; p.n_out = d.n_out;
+    if ((cst = bconv_table(c, d, kn, &p.table, &p.qn))) return cst;
+    p.in = d.in; p.n_in = d.n_in; p.n_out = d.n_out;
     p.in_packed = d.in_packed ? 1u : 0u;
     for (uint32_t i = 0; i < d.n_in; ++i) p.in_limb[i] = limb_at(d.in_limbs, i);
     {   // ONE buffer descriptor per conversion: the lowest input limb-poly is the base, the others are byte offsets from it (HmBcolProb::in_off)

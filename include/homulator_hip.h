@@ -111,7 +111,8 @@ typedef struct hm_ntt_fused_desc {
   /* optional (NULL: none; round 6): addend_galois[i] = g > 1 reads the addend of limb-poly i through the automorphism X -> X^g (evaluation form, as
    * hm_automorph): out = (minuend - NTT(in)) * k + automorph_g(addend) [* addend_k] — hrotate's final add takes AUTOOutput(0) this way and
    * AUTO_Key(0) (src/Operation.cpp hrotate, InsGen::GenAUTO src/InsGen.cpp:46-71) is never written; 0 / 1 = the addend as stored.  g odd, below 2N.
-   * Needs an addend; not with mix or conv (HM_ERR_UNSUPPORTED).  Bit-identical to hm_automorph + the call without it. */
+   * Needs an addend; not with mix or conv (HM_ERR_UNSUPPORTED).  Bit-identical to hm_automorph + the call without it.  An addend read this way must
+   * not be a limb-poly the call writes (HM_ERR_ARG; compared by address, not by base pointer). */
   const uint32_t *addend_galois;
 } hm_ntt_fused_desc;
 hm_status hm_ntt_mix_sub_scale(hm_ctx *ctx, const hm_ntt_fused_desc *desc);
@@ -157,7 +158,8 @@ hm_status hm_inner_product(hm_ctx *ctx, const uint64_t *x, const uint32_t *x_lim
                            const uint32_t *mod_ids, uint32_t n, uint32_t n_terms, uint32_t n_out);
 /* The same with its arguments in one record (round 6) and x_galois = g > 1: the x operands are read through the automorphism X -> X^g (as
  * hm_automorph would have stored them; 0 / 1: as stored) — a one-digit key switch of hrotate, whose Q limbs multiply the rotated c1 itself with the
- * key, then needs no AUTO_Key(1) launch (InsGen::GenAUTO src/InsGen.cpp:46-71).  Same reference interface as hm_inner_product. */
+ * key, then needs no AUTO_Key(1) launch (InsGen::GenAUTO src/InsGen.cpp:46-71).  Same reference interface as hm_inner_product.  An operand read
+ * this way must not be a limb-poly the call writes (HM_ERR_ARG; compared by address, not by base pointer). */
 typedef struct hm_ip_desc {
   const uint64_t *x;  const uint32_t *x_limbs;
   const uint64_t *y;  const uint32_t *y_limbs;
@@ -227,7 +229,8 @@ typedef struct hm_ntt_ip_desc {
   const uint8_t *out_inverse;
   /* optional (0: none; round 6): x_galois = g > 1 reads the digits that arrive in EVALUATION form (x_is_coeff == 0: a limb's own digit) through the
    * automorphism X -> X^g, as hm_automorph would have stored them: with hm_ntt_desc.in_galois on the ModUp INTT, hrotate's rotated c1 (AUTO_Key(1),
-   * InsGen::GenAUTO src/InsGen.cpp:46-71) is never written.  g odd, below 2N.  Bit-identical to hm_automorph + the call without it. */
+   * InsGen::GenAUTO src/InsGen.cpp:46-71) is never written.  g odd, below 2N.  Bit-identical to hm_automorph + the call without it.  A digit read
+   * this way must not be a limb-poly the call writes (HM_ERR_ARG; compared by address, not by base pointer). */
   uint32_t x_galois;
 } hm_ntt_ip_desc;
 hm_status hm_ntt_inner_product(hm_ctx *ctx, const hm_ntt_ip_desc *desc);
@@ -252,7 +255,7 @@ typedef struct hm_ntt_desc {
   /* optional (NULL: none; round 6; inverse only, not with second_pass_only): in_galois[i] = g > 1 reads limb-poly i of `in` through the automorphism
    * X -> X^g: out_i = INTT(automorph_g(in_i)) — AUTO_Key(1) + ModUp_INTT of hrotate in one pass over HBM (the index map takes aligned blocks to
    * aligned blocks, so the transform's own 16-byte loads serve).  0 / 1 = as stored.  A limb-poly read this way must not be a limb-poly the same call writes
-   * (neither in place nor another entry's output: HM_ERR_ARG). */
+   * (neither in place nor another entry's output: HM_ERR_ARG; compared by address, not by base pointer). */
   const uint32_t *in_galois;
 } hm_ntt_desc;
 hm_status hm_ntt_ex(hm_ctx *ctx, const hm_ntt_desc *desc);

@@ -13,6 +13,7 @@
 #include "../../homulator_amd/csrc/hm_modarith.h"
 #include "../../homulator_amd/csrc/hm_ntt_core.h"
 #include "../../homulator_amd/csrc/hm_params.h"
+#include "../../homulator_amd/csrc/hm_launch.h"
 
 struct Emu {
   hm::Params P;
@@ -393,6 +394,35 @@ void emu_bfly(void *h, uint32_t mod, int kind, uint64_t *X, uint64_t *Y, uint64_
   else if (kind == 1) hm_bfly_fwd_k<1>(*X, *Y, wt, m);
   else if (kind == 2) hm_bfly_fwd_k<2>(*X, *Y, wt, m);
   else hm_bfly_inv(*X, *Y, wt, m);
+}
+// ---- the back-end's launch layouts (hm_launch.h) as its entry points compute them.  policy 0: a transform (ntt_common; one_launch = the call runs
+// as ONE launch), 1: the last pass x key product (hm_ntt_inner_product; weight = per limb-poly cost for its heaviest-first order, or NULL).
+// Writes logG, per limb-poly its launch and slot, per launch its entry count (up to max_launch); returns the number of launches
+uint32_t emu_launch_layout(int policy, int one_launch, uint32_t entry_cap, const uint32_t *mod_ids, uint32_t n, const uint32_t *weight, uint32_t *logG,
+                           uint32_t *launch_of, uint32_t *slot_of, uint32_t *entries_of, uint32_t max_launch) {
+  std::vector<uint32_t> all(n);
+  for (uint32_t i = 0; i < n; ++i) all[i] = i;
+  HmGrouping g = hm_group_by_modulus(mod_ids, all, policy == 0 ? hm_ntt_group_policy(one_launch != 0) : hm_nip_group_policy());
+  if (weight) hm_sort_groups_heaviest_first(g.groups, [&](uint32_t i) { return weight[i]; });
+  const uint32_t G = 1u << g.logG, nGroups = (uint32_t)g.groups.size();
+  const HmLaunchSplit parts = hm_launch_split(nGroups, entry_cap, G);
+  uint32_t launch = 0;
+  for (uint32_t base = 0; base < nGroups; base += parts.perLaunch, ++launch) {
+    const uint32_t ng = hm_launch_groups(parts, nGroups, base);
+    if (launch < max_launch) entries_of[launch] = hm_launch_entries(ng, G);
+    for (uint32_t kk = 0; kk < ng; ++kk)
+      for (uint32_t which = 0; which < G; ++which)
+        if (g.groups[base + kk][which] >= 0) {
+          launch_of[g.groups[base + kk][which]] = launch;
+          slot_of[g.groups[base + kk][which]] = hm_entry_slot(kk, which, G);
+        }
+  }
+  *logG = g.logG;
+  return launch;
+}
+// the alias test of the entry points: the first entry of (ib, il) among those with pick[i] != 0 (NULL: all) that shares an address with (ob, ol); -1: none
+int64_t emu_first_overlap(uint64_t ob, const uint32_t *ol, uint32_t no, uint64_t ib, const uint32_t *il, uint32_t ni, uint32_t N, const uint8_t *pick) {
+  return hm_first_overlap(reinterpret_cast<const void *>(ob), ol, no, reinterpret_cast<const void *>(ib), il, ni, N, [&](uint32_t i) { return !pick || pick[i]; });
 }
 int emu_row_lds_word(int ept, int R, int tid, int a, int inverse) {
   if (ept == 16) return R == 0 ? row_unit16<0>(tid, a, inverse) : R == 1 ? row_unit16<1>(tid, a, inverse) : row_unit16<2>(tid, a, inverse);

@@ -442,6 +442,93 @@ def test_inner_product_reads_x_through_an_automorphism(env, terms, outs):
         b_.free()
 
 
+class _At:
+    """a device address inside a buffer: another base pointer into the same allocation"""
+
+    def __init__(self, buf, limb):
+        self.ptr = buf.limb_ptr(limb)
+
+
+def test_gathered_operands_are_compared_by_address_transforms(env):
+    """hm_ntt_ex (in_galois) and hm_ntt_mix_sub_scale (addend_galois): the gathered operand and the output given as two DIFFERENT base pointers into one
+    allocation whose limb lists name the same memory are refused like the same lists on one pointer; shifted to disjoint limb-polys the call
+    runs and is bit-exact"""
+    ctx, o, hip = env
+    n, N2 = 5, 2 * o.N
+    ids = [i % (o.L + o.K) for i in range(n)]
+    gs = [5, N2 - 1, 25, 1, 3]
+    x, mn, ad = (o.fill_uniform(ids, s) for s in (21, 22, 23))
+    auto = lambda v: np.stack([o.automorph_eval(v[r][None], g)[0] for r, g in enumerate(gs)])
+    pool = ctx.alloc(3 * n)
+    same, apart = list(range(n + 1, 2 * n)) + [n], list(range(2 * n, 3 * n))   # pool limbs [n, 2n): the operand's own, one entry on; [2n, 3n): free
+    # ---- the inverse transform's gathered input: pool limbs [n, 2n), passed as (pool + n limbs, identity list)
+    pool.upload(x, limb0=n)
+    with pytest.raises(hip.HmError, match="read through an automorphism from a limb the call also writes"):
+        ctx.ntt(_At(pool, n), pool, ids, inverse=True, in_galois=gs, out_limbs=same)
+    with pytest.raises(hip.HmError, match="read through an automorphism from a limb the call also writes"):
+        ctx.ntt(pool, _At(pool, n), ids, inverse=True, in_galois=gs, in_limbs=list(range(n, 2 * n)))   # ... and with a negative offset
+    ctx.ntt(_At(pool, n), pool, ids, inverse=True, in_galois=gs, out_limbs=apart)
+    assert np.array_equal(pool.download(limb0=2 * n, n=n), o.ntt(ids, auto(x), inverse=True))
+    assert np.array_equal(pool.download(limb0=n, n=n), x)
+    # ---- the fused forward transform's gathered addend
+    dx, dmn = ctx.from_host(x), ctx.from_host(mn)
+    k = [o.moduli[m] - 3 - r for r, m in enumerate(ids)]
+    pool.upload(ad, limb0=n)
+    with pytest.raises(hip.HmError, match="the addend of limb-poly .* is read through an automorphism from a limb the call writes"):
+        ctx.ntt_mix_sub_scale(dx, dmn, pool, ids, k, addend=_At(pool, n), addend_galois=gs, out_limbs=same)
+    ctx.ntt_mix_sub_scale(dx, dmn, pool, ids, k, addend=_At(pool, n), addend_galois=gs, out_limbs=apart)
+    exp = o.ewe(3, ids, o.ewe(6, ids, mn, None, o.ntt(ids, x), k=k), None, auto(ad))
+    assert np.array_equal(pool.download(limb0=2 * n, n=n), exp)
+    for b_ in (pool, dx, dmn):
+        b_.free()
+
+
+def test_gathered_operands_are_compared_by_address_inner_products(env):
+    """hm_inner_product_ex and hm_ntt_inner_product (x_galois): x and out as two different base pointers into one allocation.  Lists that name the
+    same memory are refused; shifted to disjoint limb-polys the calls run and are bit-exact"""
+    ctx, o, hip = env
+    M, terms, outs, n, g = o.L + o.K, 3, 2, 9, 5
+    ids = [(i * 5 + 1) % M for i in range(n)]
+    X = [o.fill_uniform(ids, 10 + j) for j in range(terms)]
+    Y = [[o.fill_uniform(ids, 100 + 10 * k + j) for j in range(terms)] for k in range(outs)]
+    S = outs * n + 3                                    # x lives at pool limbs [S, S + terms n), passed as (pool + S limbs, lists from 0)
+    pool = ctx.alloc(S + terms * n)
+    pool.upload(np.concatenate(X), limb0=S)
+    xb = _At(pool, S)
+    yb = ctx.from_host(np.concatenate([Y[k][j] for k in range(outs) for j in range(terms)]))
+    xl = [j * n + i for i in range(n) for j in range(terms)]
+    yl = [(k * terms + j) * n + i for i in range(n) for k in range(outs) for j in range(terms)]
+    ol = [k * n + i for i in range(n) for k in range(outs)]           # pool limbs [0, outs n): apart from x
+    same = [S + l for l in ol]                                        # pool limbs [S, S + outs n): x's first limb-polys
+    with pytest.raises(hip.HmError, match="an operand read through the automorphism is a limb the call writes"):
+        ctx.inner_product(xb, xl, yb, yl, pool, same, ids, terms, outs, x_galois=g)
+    ctx.inner_product(xb, xl, yb, yl, pool, ol, ids, terms, outs, x_galois=g)
+    got = pool.download(limb0=0, n=outs * n)
+    XR = [o.automorph_eval(X[j], g) for j in range(terms)]
+    for k in range(outs):
+        exp = o.ewe(0, ids, XR[0], Y[k][0])
+        for j in range(1, terms):
+            exp = o.ewe(2, ids, XR[j], Y[k][j], exp)
+        assert np.array_equal(got[k * n:(k + 1) * n], exp), k
+    # ---- hm_ntt_inner_product: the digits in evaluation form are the gathered ones (limb-poly 0's first digit is one: it sits at `same`)
+    coeff = [[(i + j) % 3 != 0 for j in range(terms)] for i in range(n)]
+    flags = [c for row in coeff for c in row]
+    hand, ref, rot = ctx.alloc(n * terms), ctx.alloc(n * outs), ctx.alloc(n * terms)
+    with pytest.raises(hip.HmError, match="an operand read through the automorphism is a limb the call writes"):
+        ctx.ntt_inner_product(xb, xl, flags, hand, xl, yb, yl, pool, same, ids, terms, outs, x_galois=g)
+    Xr = [X[j].copy() for j in range(terms)]            # the reference: the oracle rotates the evaluation-form operands, then the plain call
+    for j in range(terms):
+        for i in range(n):
+            if not coeff[i][j]:
+                Xr[j][i] = o.automorph_eval(X[j][i][None], g)[0]
+    rot.upload(np.concatenate(Xr))
+    ctx.ntt_inner_product(rot, xl, flags, hand, xl, yb, yl, ref, ol, ids, terms, outs)
+    ctx.ntt_inner_product(xb, xl, flags, hand, xl, yb, yl, pool, ol, ids, terms, outs, x_galois=g)
+    assert np.array_equal(pool.download(limb0=0, n=outs * n), ref.download())
+    for b_ in (pool, yb, hand, ref, rot):
+        b_.free()
+
+
 @pytest.mark.parametrize("n,inv", [(70, False), (70, True), (9, True), (9, False)], ids=["wide", "wide-inverse-out", "small-inverse-out", "small"])
 @pytest.mark.parametrize("outs", [2, 1])
 def test_ntt_inner_product_reads_own_digits_through_an_automorphism(env, n, inv, outs):
