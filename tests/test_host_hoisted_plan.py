@@ -45,6 +45,34 @@ def test_one_hoisted_key_product_whatever_the_rotation_count(cfg, L, ell, alpha)
     assert counts == {7}
 
 
+@pytest.mark.parametrize("alpha", [1, 2, 3, 5, 13])
+def test_route_by_digit_count_at_every_level(alpha):
+    """every level of a 13-limb chain (N = 2^13 override; the grid tests/test_gpu_hoisted_shapes.py executes): pass 6 builds key-product records
+    of at most 4 terms, so beta = ceil(l / alpha) <= 4 takes the hoisted route (7 launches, no automorphism launch) and beta >= 5 the fallback
+    route (an automorphism launch per rotation, element-wise key products, no hoisted launch); both keep the unfused plan's instruction total"""
+    L = 13
+    for ell in range(1, L + 1):
+        beta = -(-ell // alpha)
+        for R in (1, 4):
+            p, total, n, _ = build("config_4_N15.cfg", L, ell, alpha, N=1 << 13, rotations=R)
+            kinds = [ln.split()[0] for ln in p]
+            assert n == len(kinds)
+            if beta <= 4:
+                assert kinds == ["INTT", "BCONV", "NTT", "IP_HOISTED", "INTT", "BCONV", "NTT_SUBSCALE"] and n == 7, (ell, R, kinds)
+                assert f" rot={R} " in p[3] + " "
+            else:
+                assert "IP_HOISTED" not in kinds and kinds.count("AUTO") >= 1 and "EWE" in kinds, (ell, R, kinds)
+            assert build("config_4_N15.cfg", L, ell, alpha, fuse=False, N=1 << 13, rotations=R)[1] == total, (ell, R)
+
+
+def test_batched_hoisted_launch_carries_every_op():
+    """batch = B: ONE hoisted launch of B (l + alpha) entries, the launch count of the single op, B times its stage bytes"""
+    one = build("config_4.cfg", 45, 35, 15, rotations=4)
+    p, _, n, nbytes = build("config_4.cfg", 45, 35, 15, rotations=4, batch=10)
+    assert n == one[2] == 7 and nbytes == 10 * one[3]
+    assert n_of(p[3]) == 10 * (35 + 15) and p[3].split()[0] == "IP_HOISTED"
+
+
 def test_fuse_hoist_off_keeps_a_key_product_per_rotation():
     p, total, _, _ = build("config_4.cfg", 45, 35, 15, rotations=4, fuse_hoist=0)
     kinds = [ln.split()[0] for ln in p]
