@@ -13,110 +13,108 @@
 #include "Driver.h"
 #include "InsGen.h"
 
-typedef std::map<std::string, std::vector<INSGROUP>> StageMap;  // stage key -> [level] -> instruction group
+#include <array>
+#include <deque>
 
+// the stages of one builder: (stage key, [level] -> instruction group) in the order they were emitted, with upstream's lookup by key
+class StageList {
+  std::deque<std::pair<std::string, std::vector<INSGROUP>>> stages_;  // a deque: what add() returns stays where it is
+
+public:
+  std::vector<INSGROUP> &add(const std::string &key, std::vector<INSGROUP> groups) {
+    stages_.emplace_back(key, std::move(groups));
+    return stages_.back().second;
+  }
+  const std::vector<INSGROUP> &at(const std::string &key) const {
+    for (const auto &s : stages_)
+      if (s.first == key) return s.second;
+    throw std::out_of_range("no stage " + key);
+  }
+  auto begin() const { return stages_.begin(); }
+  auto end() const { return stages_.end(); }
+};
+
+// a buffer as one part of a key switch hands it to the next: its limb addresses and, per limb, the group of the stage that writes it.  The
+// consumer depends on these groups and looks up no name.
+struct Limbs {
+  std::vector<AddrType> addr;
+  std::vector<INSGROUP> from;
+};
+
+// The key switch in parts, with explicit values between them: modUp -> [rotateDigits ->] keyProduct -> modDown.  Upstream's constructor is the
+// whole key switch of its input; the hoisted rotations (HROTATE_HOISTED) run modUp once and the other three parts per rotation, every buffer and
+// stage key of a rotation carrying the suffix "_Rot<r>".
 class KeySwitch {
 public:
-  // FULL: the whole key switch of the input (upstream's constructor).  The hoisted rotations (HROTATE_HOISTED) build its parts separately:
-  // MODUP = the ModUp of the input alone (digits NTTOut_beta(j)); ROTATED_KEY_PRODUCT = for one rotation, the automorphism of every extended
-  // digit of an earlier MODUP, the key product with this rotation's key and the ModDown, every buffer and stage key carrying the suffix `rot`.
-  enum Part { FULL, MODUP, ROTATED_KEY_PRODUCT };
+  typedef std::vector<Limbs> Digits;                   // per digit j: the E = level + alpha limbs of the extended digit, in evaluation form
+  typedef std::array<Limbs, 2> Accumulators;           // per key component k: the E limbs of sum_j digit_j * evk_{j,k}
+  typedef std::array<std::vector<AddrType>, 2> Output; // per key component k: the `level` limbs of the switched polynomial
 
 private:
-  std::vector<AddrType> *DataPool;
   std::map<AddrType, std::vector<Instruction *>> *DataInsMap;
   InsGen *insGenPointer;
-  std::vector<AddrType> preAddr;
-  uint32_t Level, Alpha, Beta, dnum, MaxLevel;
+  uint32_t Level, Alpha, Beta, MaxLevel;
   AddrManage *memMange;
   Arch *arch;
   std::string baseName;
-  Part part_ = FULL;
-  std::string rot;   // "" except for ROTATED_KEY_PRODUCT: "_Rot<r>"
-  StageMap KeySwicthInsMap;
-  std::vector<std::string> KeySwitchInsMapName;
-
-  uint32_t digitSize(uint32_t beta) const { return std::min(Alpha, Level - beta * Alpha); }
-  uint32_t extMod(uint32_t t) const { return t < Level ? t : MaxLevel + (t - Level); }
-  // the evaluation-form digits the key product reads, and the stage that produces them
-  std::string digitBuffer(uint32_t j) const { return rot.empty() ? "NTTOut_beta(" + std::to_string(j) + ")" : "AUTOOut" + rot + "_beta(" + std::to_string(j) + ")"; }
-  std::string digitStage(uint32_t j) const { return rot.empty() ? "ModUp_NTT_(" + std::to_string(j) + ")" : "AUTO" + rot + "_beta(" + std::to_string(j) + ")"; }
+  std::vector<uint32_t> qMods, pMods, extMods;  // modulus ids of the `level` Q limbs, of the alpha special primes, and of both (the extended basis)
+  StageList stages;
+  Output out_;
 
 public:
   KeySwitch(std::string labelName, uint32_t maxlevel, uint32_t level, uint32_t alpha,
             const std::vector<AddrType> &inputPolynomialAddress, std::vector<AddrType> *pool,
             std::map<AddrType, std::vector<Instruction *>> *map, InsGen *insgen, AddrManage *memoryMange);
-  // any part; ROTATED_KEY_PRODUCT: galois = the rotation's element, keySeed = the synthetic stream of its key
-  KeySwitch(std::string labelName, uint32_t maxlevel, uint32_t level, uint32_t alpha,
-            const std::vector<AddrType> &inputPolynomialAddress, std::vector<AddrType> *pool,
-            std::map<AddrType, std::vector<Instruction *>> *map, InsGen *insgen, AddrManage *memoryMange,
-            Part part, const std::string &rotSuffix = "", uint32_t galois = 0, uint64_t keySeed = 0);
-  std::pair<StageMap, std::vector<std::string>> getInsMap() { return {KeySwicthInsMap, KeySwitchInsMapName}; }
+  // emits nothing: the caller composes the parts
+  KeySwitch(std::string labelName, uint32_t maxlevel, uint32_t level, uint32_t alpha, std::vector<AddrType> *pool,
+            std::map<AddrType, std::vector<Instruction *>> *map, InsGen *insgen, AddrManage *memoryMange);
+  const StageList &getInsMap() const { return stages; }
+  StageList takeStages() { return std::exchange(stages, StageList()); }  // the stages emitted since the last call
+  const Output &output() const { return out_; }                         // of upstream's constructor
 
-  void ModUp();
-  void RotateDigits(uint32_t galois);
-  void ModUpINTT();
-  void ModUpDecompFusionBConvStep1(uint32_t beta);
-  void ModUpBConvStep2(uint32_t beta);
-  void ModUpNTT(uint32_t beta);
-  void InnerProduceOperation(uint64_t evkSeed);
-  void ModDownINTT();
-  void ModDownBConvStep1();
-  void ModDownBConvStep2();
-  void ModDowNTT();
-  void ModDownSub();
+  // inputMayBeOpInput: the input may be an op's own input ciphertext, which no instruction produces (otherwise a limb without producer throws)
+  Digits modUp(const std::vector<AddrType> &input, bool inputMayBeOpInput);
+  Digits rotateDigits(const Digits &digits, uint32_t galois, const std::string &suffix);
+  Accumulators keyProduct(const Digits &digits, uint64_t keySeed, const std::string &suffix);  // keySeed: the synthetic stream of the key
+  Output modDown(const Accumulators &acc, const std::string &suffix);
 };
 
 class TensorCompute {
 private:
-  InsGen *insGenPointer;
-  uint32_t currentLevel;
-  AddrManage *memMange;
-  std::string baseName;
-  StageMap TensorComputeInsMap;
-  std::vector<std::string> TensorComputeInsMapName;
-  std::vector<AddrType> ciph1_c0, ciph1_c1, ciph2_c0, ciph2_c1;
+  StageList stages;
+  std::array<std::vector<AddrType>, 3> d_;
 
 public:
   TensorCompute(std::string labelName, uint32_t level, Ciphertext *cipher1, Ciphertext *cipher2,
                 std::vector<AddrType> *pool, std::map<AddrType, std::vector<Instruction *>> *map, InsGen *insgen,
                 AddrManage *memoryMange);
-  void computeD0();
-  void computeD1();
-  void computeD2();
-  std::pair<StageMap, std::vector<std::string>> getInsMap() { return {TensorComputeInsMap, TensorComputeInsMapName}; }
+  const StageList &getInsMap() const { return stages; }
+  const std::vector<AddrType> &d(uint32_t i) const { return d_[i]; }  // TensorD<i>Out
 };
 
 class Rescale {
 private:
-  std::map<AddrType, std::vector<Instruction *>> *DataInsMap;
-  std::vector<AddrType> preAddr;
-  InsGen *insGenPointer;
-  uint32_t currentLevel;
-  AddrManage *memMange;
-  Arch *arch;
-  std::string baseName;
-  StageMap RescaleInsMap;
-  std::vector<std::string> RescaleInsMapName;
+  StageList stages;
+  std::vector<AddrType> out_;
 
 public:
   Rescale(std::string labelName, uint32_t level, const std::vector<AddrType> &inputPolynomialAddress,
           std::vector<AddrType> *pool, std::map<AddrType, std::vector<Instruction *>> *map, InsGen *insgen,
           AddrManage *memoryMange);
-  void NTTOps();
-  void SubOps();
-  void MulOps();
-  std::pair<StageMap, std::vector<std::string>> getInsMap() { return {RescaleInsMap, RescaleInsMapName}; }
+  const StageList &getInsMap() const { return stages; }
+  const std::vector<AddrType> &output() const { return out_; }  // <base>_Rescale_MulOut
 };
 
-// common part of the five op classes: generators, driver, address plan, synthetic inputs, simulate()
+// common part of the op classes: generators, driver, address plan, synthetic inputs, simulate()
 class OperationBase {
 protected:
   std::vector<AddrType> Datapool;
-  std::map<AddrType, std::vector<Instruction *>> DataInsMap;
-  InsGen *insgener;
-  Driver *driver;
-  AddrManage *addrManager = nullptr;
+  std::map<AddrType, std::vector<Instruction *>> DataInsMap;  // owns the instructions (freed by the destructor)
+  InsGen insgener;
+  Driver driver;
+  std::unique_ptr<AddrManage> addrManager;  // made by makeInputs(): the temporaries start after the inputs
+  std::vector<Ciphertext> cts;              // the input ciphertexts ct1, ct2
+  std::unique_ptr<Plaintext> ptx;           // the input plaintext pt
   Arch *arch;
   Config *config;
   std::string opName;       // HMULT, HROTATE, ...
@@ -127,10 +125,18 @@ protected:
   std::map<std::string, std::vector<AddrType>> namedInputs;   // ct1.c0, ct1.c1, ... for readBuffer
   std::map<std::string, std::vector<AddrType>> namedOutputs;  // out.c0, out.c1
 
-  OperationBase(const std::string &op, Config *cfg, Arch *_arch, uint32_t maxLevel, uint32_t curLevel, uint32_t alpha);
-  void dispatch(std::pair<StageMap, std::vector<std::string>> m);
-  void inputCiphertext(const std::string &name, Ciphertext *ct, uint64_t seed);
-  void inputPlaintext(const std::string &name, Plaintext *pt, uint64_t seed);
+  OperationBase(const std::string &op, const std::string &labelName, Config *cfg, Arch *_arch, uint32_t maxLevel, uint32_t curLevel, uint32_t alpha);
+  // every op's preamble: `ciphertexts` input ciphertexts ct1, ct2 (synthetic streams seed, seed + 2000) and, if asked, the plaintext pt
+  // (seed + 4000) at the current level, then the address plan of the temporaries behind them
+  void makeInputs(uint32_t ciphertexts, bool plaintext = false);
+  std::vector<AddrType> alloc(const std::string &name, uint32_t limbs);  // MallocMem + getAddr
+  std::vector<AddrType> component(uint32_t ct, uint32_t k) const { return k == 0 ? cts[ct].getC0Addr() : cts[ct].getC1Addr(); }  // c_k of input ct
+  void setOutput(const std::string &out, uint32_t k, const std::vector<AddrType> &limbs) { namedOutputs[out + ".c" + std::to_string(k)] = limbs; }
+  void dispatch(const StageList &m);
+  // the two halves of a rotation around its key switch, shared by HROTATE (suffix "") and HROTATE_HOISTED ("_Rot<r>"): sigma_g of component k
+  // of ct1 into AUTOOutput<suffix>(k); and <out>.c0 = sigma_g(c0) + ks0, <out>.c1 = ks1
+  std::vector<AddrType> rotateComponent(uint32_t k, uint32_t galois, const std::string &suffix);
+  void finishRotation(const std::string &out, const std::vector<AddrType> &rotatedC0, const KeySwitch::Output &ks, const std::string &suffix);
   void finishConstruction();  // registers every temporary with the backend
 
 public:
@@ -154,34 +160,28 @@ public:
 };
 
 class HMULT : public OperationBase {
-  Ciphertext *c1, *c2;
 public:
   HMULT(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
 };
 class HROTATE : public OperationBase {
-  Ciphertext *ciph;
 public:
   HROTATE(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
 };
 // hrotate_hoisted (build extension; the reference has no such op): R rotations of ONE ciphertext with ONE ModUp (config keys `rotations` = R,
 // default 4, 1..16, and `galois` = g, default 5; rotation r = 1..R by g^r mod 2N).  Outputs out<r>.c0 / out<r>.c1, keys IP_Rot<r>_Key<k>_<j>.
 class HROTATE_HOISTED : public OperationBase {
-  Ciphertext *ciph;
 public:
   HROTATE_HOISTED(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
 };
 class HADD : public OperationBase {
-  Ciphertext *c1, *c2;
 public:
   HADD(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
 };
 class PMULT : public OperationBase {
-  Ciphertext *ctx; Plaintext *ptx;
 public:
   PMULT(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
 };
 class PADD : public OperationBase {
-  Ciphertext *ctx; Plaintext *ptx;
 public:
   PADD(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
 };
