@@ -1789,6 +1789,156 @@ extern "C" hm_status hm_inner_product_hoisted(hm_ctx *c, const hm_ip_hoisted_des
   return HM_OK;
 }
 
+// ---- K5 weighted sum of rotations (hm_inner_product_lintrans): sum_r pt_r * (the hoisted key product of rotation r), formed before anything is
+// stored.  The sum over the rotations needs a fixed destination, so this is the GATHER form of the kernel above: a thread owns the aligned pair p
+// of the outputs; rotation by rotation it loads every digit's pair at the automorphism's source of p (hm_auto_src(p, g_r): an aligned pair, in
+// order or swapped — k_inner_product's x_galois map), both keys and the plaintext at p, forms t_k = reduce(sum_j x_j y_kj) exactly as
+// k_inner_product_hoisted does and adds pt * t_k to a 128-bit accumulator per key and word.  Entries with an addend source (the Q limbs: c0)
+// gather it at the same source and accumulate pt * c0 as a third output.  One record per (rotation, entry) in a device table; the digits, the
+// addend, the outputs and the modulus are read from rotation 0's record.
+struct HmIpLinRec {
+  uint16_t x[HM_IP_MAX_TERMS];
+  uint16_t y[2][HM_IP_MAX_TERMS];
+  uint16_t out[2];
+  uint16_t pt, add_src, add_out;
+  uint16_t mod, has_add, pad;
+};
+struct HmIpLinArgs {
+  const uint64_t *x, *y, *pt, *addend;
+  uint64_t *out, *addend_out;
+  const HmMod *mods;
+  const HmIpLinRec *rec;   // [n_rot][n_limbs]
+  uint32_t logN, n_limbs, n_rot;
+  uint32_t galois[HM_IP_LINTRANS_MAX_ROT];
+};
+
+template <int TERMS>
+__global__ void __launch_bounds__(256) k_inner_product_lintrans(HmIpLinArgs a) {
+  const uint32_t N = 1u << a.logN;
+  const uint32_t per_limb = N / 512;
+  const uint32_t entry = blockIdx.x / per_limb, chunk = blockIdx.x % per_limb;
+  if (entry >= a.n_limbs) return;
+  const HmIpLinRec &l0 = a.rec[entry];
+  const HmMod m = a.mods[l0.mod];
+  const bool add = l0.has_add != 0;   // workgroup-uniform
+  const uint32_t p = chunk * 512 + 2 * threadIdx.x;
+  hm_u128 S[2][2] = {{0, 0}, {0, 0}}, U[2] = {0, 0};
+#pragma unroll 1
+  for (uint32_t r = 0; r < a.n_rot; ++r) {
+    const HmIpLinRec &lb = a.rec[(size_t)r * a.n_limbs + entry];
+    const uint32_t s = hm_auto_src(p, a.galois[r], a.logN);
+    const size_t sp = s & ~1u;
+    const bool swap = s & 1u;
+    ulonglong2 vx[TERMS], vy[2][TERMS];
+#pragma unroll
+    for (int j = 0; j < TERMS; ++j) vx[j] = *reinterpret_cast<const ulonglong2 *>(a.x + (size_t)l0.x[j] * N + sp);
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+#pragma unroll
+      for (int j = 0; j < TERMS; ++j) vy[k][j] = *reinterpret_cast<const ulonglong2 *>(a.y + (size_t)lb.y[k][j] * N + p);
+    const ulonglong2 vp = *reinterpret_cast<const ulonglong2 *>(a.pt + (size_t)lb.pt * N + p);
+    if (add) {
+      const ulonglong2 vc = *reinterpret_cast<const ulonglong2 *>(a.addend + (size_t)l0.add_src * N + sp);
+      U[0] += (hm_u128)vp.x * (swap ? vc.y : vc.x);
+      U[1] += (hm_u128)vp.y * (swap ? vc.x : vc.y);
+    }
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      hm_u128 s0 = 0, s1 = 0;
+#pragma unroll
+      for (int j = 0; j < TERMS; ++j) {
+        const uint64_t x0 = swap ? vx[j].y : vx[j].x, x1 = swap ? vx[j].x : vx[j].y;
+        s0 += (hm_u128)x0 * vy[k][j].x;
+        s1 += (hm_u128)x1 * vy[k][j].y;
+      }
+      // the same sums and reduction as k_inner_product_hoisted's: t_k is that kernel's output, bit for bit
+      S[k][0] += (hm_u128)vp.x * hm_barrett(s0, m);
+      S[k][1] += (hm_u128)vp.y * hm_barrett(s1, m);
+    }
+  }
+  // n_rot <= 16 products of two residues below q < 2^60: every accumulator stays below 2^124, inside 128 bits but beyond hm_barrett's
+  // z < 2^(k+63) (sums of up to 8 products), so the top word is folded first (hm_barrett_wide: f < 2^64 + 2q < 2^(k+63) for k > 20)
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const ulonglong2 o = {hm_barrett_wide(S[k][0], m), hm_barrett_wide(S[k][1], m)};
+    *reinterpret_cast<ulonglong2 *>(a.out + (size_t)l0.out[k] * N + p) = o;
+  }
+  if (add) {
+    const ulonglong2 o = {hm_barrett_wide(U[0], m), hm_barrett_wide(U[1], m)};
+    *reinterpret_cast<ulonglong2 *>(a.addend_out + (size_t)l0.add_out * N + p) = o;
+  }
+}
+
+extern "C" hm_status hm_inner_product_lintrans(hm_ctx *c, const hm_ip_lintrans_desc *d) {
+  static const char *const what = "hm_inner_product_lintrans";
+  if (!c) return HM_ERR_ARG;
+  if (!d || !d->x || !d->x_limbs || !d->y || !d->y_limbs || !d->pt || !d->pt_limbs || !d->out || !d->out_limbs || !d->mod_ids || !d->galois)
+    return fail(c, HM_ERR_ARG, "%s: null argument", what);
+  const bool anyAdd = d->addend_limbs != nullptr;
+  if (anyAdd && (!d->addend || !d->addend_out || !d->addend_out_limbs))
+    return fail(c, HM_ERR_ARG, "%s: null argument (addend, addend_limbs, addend_out and addend_out_limbs go together)", what);
+  const uint32_t n = d->n, T = d->n_terms, R = d->n_rot, N = c->P.N;
+  if (T == 0 || T > HM_IP_MAX_TERMS || R == 0 || R > HM_IP_LINTRANS_MAX_ROT)
+    return fail(c, HM_ERR_ARG, "%s: n_terms in [1,%d], n_rot in [1,%d]", what, HM_IP_MAX_TERMS, HM_IP_LINTRANS_MAX_ROT);
+  for (uint32_t r = 0; r < R; ++r)
+    if (!(d->galois[r] & 1) || d->galois[r] >= 2 * N) return fail(c, HM_ERR_ARG, "%s: galois[%u] is not an odd number below 2N", what, r);
+  std::vector<uint32_t> addSrc, addOut;   // the entries that carry an addend
+  for (uint32_t i = 0; anyAdd && i < n; ++i)
+    if (d->addend_limbs[i] != HM_NO_LIMB) { addSrc.push_back(d->addend_limbs[i]); addOut.push_back(d->addend_out_limbs[i]); }
+  const uint32_t nAdd = (uint32_t)addSrc.size();
+  hm_status st;
+  if ((st = check_limbs(c, what, d->x_limbs, n * T)) || (st = check_limbs(c, what, d->y_limbs, R * n * 2 * T)) || (st = check_limbs(c, what, d->pt_limbs, R * n)) ||
+      (st = check_limbs(c, what, d->out_limbs, n * 2)) || (st = check_limbs(c, what, addSrc.data(), nAdd)) || (st = check_limbs(c, what, addOut.data(), nAdd)) ||
+      (st = check_mods(c, what, d->mod_ids, n)))
+    return st;
+  // a workgroup reads the digits and the addend at other positions than the ones it writes, and every rotation's keys and plaintext after the
+  // first could be another workgroup's output: no output may overlap any input
+  struct In { const char *name; const void *base; const uint32_t *limbs; uint32_t count; };
+  const In ins[4] = {{"a digit (x)", d->x, d->x_limbs, n * T}, {"a key limb-poly (y)", d->y, d->y_limbs, R * n * 2 * T},
+                     {"a plaintext limb-poly (pt)", d->pt, d->pt_limbs, R * n}, {"an addend source", d->addend, addSrc.data(), nAdd}};
+  for (const In &in : ins) {
+    if (in.count && hm_limbs_overlap(d->out, d->out_limbs, n * 2, in.base, in.limbs, in.count, N))
+      return fail(c, HM_ERR_ARG, "%s: an output limb-poly overlaps %s", what, in.name);
+    if (in.count && nAdd && hm_limbs_overlap(d->addend_out, addOut.data(), nAdd, in.base, in.limbs, in.count, N))
+      return fail(c, HM_ERR_ARG, "%s: an addend output limb-poly overlaps %s", what, in.name);
+  }
+  if (n == 0) return HM_OK;
+  std::vector<HmIpLinRec> recs((size_t)R * n);
+  memset(recs.data(), 0, sizeof(HmIpLinRec) * recs.size());
+  for (uint32_t r = 0; r < R; ++r)
+    for (uint32_t i = 0; i < n; ++i) {
+      const size_t e = (size_t)r * n + i;
+      HmIpLinRec &l = recs[e];
+      l.mod = (uint16_t)d->mod_ids[i];
+      l.pt = (uint16_t)d->pt_limbs[e];
+      for (uint32_t j = 0; j < T; ++j) l.x[j] = (uint16_t)d->x_limbs[(size_t)i * T + j];
+      for (uint32_t k = 0; k < 2; ++k) {
+        l.out[k] = (uint16_t)d->out_limbs[(size_t)i * 2 + k];
+        for (uint32_t j = 0; j < T; ++j) l.y[k][j] = (uint16_t)d->y_limbs[(e * 2 + k) * T + j];
+      }
+      if (anyAdd && d->addend_limbs[i] != HM_NO_LIMB) {
+        l.has_add = 1; l.add_src = (uint16_t)d->addend_limbs[i]; l.add_out = (uint16_t)d->addend_out_limbs[i];
+      }
+    }
+  HM_HIP(c, hipSetDevice(c->device));
+  const void *dtab = nullptr;
+  if ((st = device_table(c, recs.data(), sizeof(HmIpLinRec) * recs.size(), &dtab))) return st;
+  HmIpLinArgs a;
+  a.x = d->x; a.y = d->y; a.pt = d->pt; a.addend = d->addend; a.out = d->out; a.addend_out = d->addend_out;
+  a.mods = c->d_mods; a.rec = static_cast<const HmIpLinRec *>(dtab);
+  a.logN = c->P.logN; a.n_limbs = n; a.n_rot = R;
+  for (uint32_t r = 0; r < HM_IP_LINTRANS_MAX_ROT; ++r) a.galois[r] = r < R ? d->galois[r] : 1u;
+  const dim3 grid(n * (N / 512));
+  switch (T) {
+  case 1: hipLaunchKernelGGL(k_inner_product_lintrans<1>, grid, dim3(256), 0, c->stream, a); break;
+  case 2: hipLaunchKernelGGL(k_inner_product_lintrans<2>, grid, dim3(256), 0, c->stream, a); break;
+  case 3: hipLaunchKernelGGL(k_inner_product_lintrans<3>, grid, dim3(256), 0, c->stream, a); break;
+  case 4: hipLaunchKernelGGL(k_inner_product_lintrans<4>, grid, dim3(256), 0, c->stream, a); break;
+  }
+  HM_HIP(c, hipGetLastError());
+  return HM_OK;
+}
+
 // The kernel of hm_ntt_inner_product's second launch: OUTS keys; INVOUT 0 = outputs in evaluation form, 1 = every limb's outputs leave as the
 // first pass of their inverse transform (the generic chain: a launch of their own), 2 = per limb (mont32: one launch); XG = evaluation-form
 // operands read through an automorphism (round 6, hm_ntt_ip_desc.x_galois); SMALL = the small-launch geometry.  nullptr: the form the other

@@ -76,10 +76,11 @@ int main(int argc, char *argv[]) {
     HROTATE *hrotate = new HROTATE("test_hrotate", maxlevel, currentlevel, alpha, config, arch);
     if (arch->world() > 1) rcclRendezvous(arch, idFile);
     hrotate->simulate();
-  } else if (ops == "hrotate_hoisted") {   // build extension: R rotations of one ciphertext, one ModUp (config keys rotations, galois)
-    HROTATE_HOISTED *hoisted = nullptr;
+  } else if (ops == "hrotate_hoisted" || ops == "hlintrans") {   // build extensions: R rotations of one ciphertext with one ModUp (config keys
+    OperationBase *hoisted = nullptr;                            // rotations, galois); hlintrans: their plaintext-weighted sum, one ModDown
     try {
-      hoisted = new HROTATE_HOISTED("test_hrotate_hoisted", maxlevel, currentlevel, alpha, config, arch);
+      if (ops == "hlintrans") hoisted = new HLINTRANS("test_hlintrans", maxlevel, currentlevel, alpha, config, arch);
+      else hoisted = new HROTATE_HOISTED("test_hrotate_hoisted", maxlevel, currentlevel, alpha, config, arch);
     } catch (const std::exception &e) {
       std::cerr << e.what() << std::endl;
       return 1;

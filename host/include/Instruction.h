@@ -70,6 +70,11 @@ public:
   // (6h) hoisted key product (hm_inner_product_hoisted): ipX = the UNROTATED digits, rotation r reads them through X -> X^ipHoistG[r] with keys
   // ipY[2r + k]; its outputs are out_{r,k} = (OutputOperand, extraOutputs...)[2r + k].  Empty: not hoisted
   std::vector<uint32_t> ipHoistG;
+  // (6l) weighted sum of the hoisted key products (hm_inner_product_lintrans): a hoisted record (ipX, ipY, ipHoistG as above) whose rotation r is
+  // multiplied by the plaintext limb ipLinPt[r] and summed over r before it is stored: OutputOperand = S_0, extraOutputs[0] = S_1.  ipLinAddend != 0
+  // (the Q limbs): extraOutputs[1] = sum_r ipLinPt[r] * sigma_r(ipLinAddend).  ipLinPt empty: no weighted sum
+  std::vector<AddrType> ipLinPt;
+  AddrType ipLinAddend = 0;
   std::vector<Instruction *> depsInsList;
 
   Instruction(std::string name, ins_ops op, uint32_t level) : ops(op), Name(std::move(name)), level_id(level) {}

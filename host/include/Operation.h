@@ -115,6 +115,7 @@ protected:
   std::unique_ptr<AddrManage> addrManager;  // made by makeInputs(): the temporaries start after the inputs
   std::vector<Ciphertext> cts;              // the input ciphertexts ct1, ct2
   std::unique_ptr<Plaintext> ptx;           // the input plaintext pt
+  std::vector<Plaintext> extPtx;            // the input plaintexts pt1, pt2, ... on the extended basis (HLINTRANS)
   Arch *arch;
   Config *config;
   std::string opName;       // HMULT, HROTATE, ...
@@ -127,15 +128,19 @@ protected:
 
   OperationBase(const std::string &op, const std::string &labelName, Config *cfg, Arch *_arch, uint32_t maxLevel, uint32_t curLevel, uint32_t alpha);
   // every op's preamble: `ciphertexts` input ciphertexts ct1, ct2 (synthetic streams seed, seed + 2000) and, if asked, the plaintext pt
-  // (seed + 4000) at the current level, then the address plan of the temporaries behind them
-  void makeInputs(uint32_t ciphertexts, bool plaintext = false);
+  // (seed + 4000) at the current level, then `extPlaintexts` plaintexts pt<r>, r = 1.., on the extended basis (the current level's Q limbs, then
+  // the alpha special primes; seed + 4000 + 100000 r), then the address plan of the temporaries behind them
+  void makeInputs(uint32_t ciphertexts, bool plaintext = false, uint32_t extPlaintexts = 0);
+  // what the ops that hoist the ModUp over rotations (HROTATE_HOISTED, HLINTRANS; `op` names the op in the messages) check first: no backend = sim,
+  // no world > 1; config keys `rotations` = R (default 4, 1..16) and `galois` = g (default 5, odd, below 2N).  Returns g^r mod 2N, r = 1..R, distinct
+  std::vector<uint32_t> hoistedRotations(const std::string &op) const;
   std::vector<AddrType> alloc(const std::string &name, uint32_t limbs);  // MallocMem + getAddr
   std::vector<AddrType> component(uint32_t ct, uint32_t k) const { return k == 0 ? cts[ct].getC0Addr() : cts[ct].getC1Addr(); }  // c_k of input ct
   void setOutput(const std::string &out, uint32_t k, const std::vector<AddrType> &limbs) { namedOutputs[out + ".c" + std::to_string(k)] = limbs; }
   void dispatch(const StageList &m);
   // the two halves of a rotation around its key switch, shared by HROTATE (suffix "") and HROTATE_HOISTED ("_Rot<r>"): sigma_g of component k
   // of ct1 into AUTOOutput<suffix>(k); and <out>.c0 = sigma_g(c0) + ks0, <out>.c1 = ks1
-  std::vector<AddrType> rotateComponent(uint32_t k, uint32_t galois, const std::string &suffix);
+  Limbs rotateComponent(uint32_t k, uint32_t galois, const std::string &suffix);
   void finishRotation(const std::string &out, const std::vector<AddrType> &rotatedC0, const KeySwitch::Output &ks, const std::string &suffix);
   void finishConstruction();  // registers every temporary with the backend
 
@@ -173,6 +178,13 @@ class HROTATE_HOISTED : public OperationBase {
 public:
   HROTATE_HOISTED(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
 };
+// hlintrans (build extension): sum_r pt_r (.) rot_r(ct1) over the R rotations of hrotate_hoisted (same config keys, same keys IP_Rot<r>_Key<k>_<j>),
+// with ONE ModUp and ONE ModDown: the plaintexts pt<r> are given on the extended basis and the weighted sum is formed on it, before the ModDown.
+// One output ciphertext out at the input's level; no rescale (as PMULT).
+class HLINTRANS : public OperationBase {
+public:
+  HLINTRANS(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
+};
 class HADD : public OperationBase {
 public:
   HADD(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
@@ -196,7 +208,7 @@ class OpChain {
   std::vector<Arch *> archs;
   std::vector<OperationBase *> ops;
 public:
-  // ops: comma-separated list of hmult | hrotate | hadd | pmult | padd, e.g. "hmult,hrotate,hadd,hmult"; hrotate_hoisted (R output
+  // ops: comma-separated list of hmult | hrotate | hadd | pmult | padd | hlintrans, e.g. "hmult,hrotate,hadd,hmult"; hrotate_hoisted (R output
   // ciphertexts) only as the last op
   OpChain(const std::string &cfgPath, const std::string &opList, uint32_t maxLevel, uint32_t curLevel, uint32_t alpha,
           const std::map<std::string, uint32_t> &overrides = {});

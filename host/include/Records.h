@@ -26,6 +26,8 @@ enum class Role {
   IpReplacedSrc,  // ... the conversion output ipSrc[j] that the fused conversion ipConvIn[j] replaces: never written, never loaded
   ConvIn,         // input of a base conversion: a BCONV record's own, ipConvIn[j] (digit = j), fConvIn
   Key,            // key product: evaluation-key limb
+  LinPlain,       // weighted sum of hoisted key products (6l): a rotation's plaintext limb
+  LinAddend,      // ... the addend source, read through every rotation's automorphism (the unrotated c0)
   Minuend, Addend, Mix,   // fused forward transform (4, 4b)
   EpiSub, EpiAdd,         // conversion with the element-wise epilogue (10): fSubFrom, fAdd
   ReplacedIn      // the transform input operandList[0] that the fused conversion fConvIn replaces (9): never written, never loaded
@@ -57,6 +59,8 @@ inline std::vector<Read> recordReads(const Instruction &i) {
         for (size_t x = 1; x < i.ipConvIn[j].size(); ++x) v.push_back({i.ipConvIn[j][x], Role::ConvIn, j});
     for (auto &y : i.ipY)
       for (AddrType a : y) v.push_back({a, Role::Key, kNoDigit});
+    for (AddrType a : i.ipLinPt) v.push_back({a, Role::LinPlain, kNoDigit});
+    if (i.ipLinAddend) v.push_back({i.ipLinAddend, Role::LinAddend, kNoDigit});
     return v;
   }
   if (i.ops == BCONV_STEP2) {

@@ -24,8 +24,11 @@ uint32_t Arch::cap(uint32_t logN, const char *name) {
 struct Arch::Launch {
   enum Kind { L_NTT, L_INTT, L_EWE, L_BCONV, L_AUTO, L_NTT_SUBSCALE, L_TENSOR, L_EXCH_IN, L_EXCH_OUT, L_REPLICATE, L_IP, L_NTT_IP,
               L_BCONV_COL, L_EXCH_IN_COL, L_EXCH_OUT_COL,   // round 4: conversion + first pass on a rank's column slice, between the transposed-domain exchanges
-              L_IP_HOISTED } kind;                           // (6h) the key products of several rotations from one set of digits
+              L_IP_HOISTED,                                  // (6h) the key products of several rotations from one set of digits
+              L_IP_LINTRANS } kind;                          // (6l) ... and their plaintext-weighted sum
   std::vector<uint32_t> hoistG;   // L_IP_HOISTED: the Galois element of every rotation (a: digits [n][T], b: keys [r][n][2][T], out: [r][n][2])
+                                  // L_IP_LINTRANS: the same, with c: plaintexts [r][n], d: addend source [n] / out1: addend output [n] (HM_NO_LIMB: none; both
+                                  // empty: no entry has one), out: [n][2]
   Launch *xin = nullptr, *xout = nullptr;   // sharded BCONV: the exchange launches around it (they share its slice buffers)
   int recordSlot = -1;            // exchange launches of a pipelined sharded plan: the mark set behind them (hm_exchange_mark)
   std::vector<int> waitSlots;     // marks the compute stream waits for before this launch (hm_exchange_wait)
@@ -124,6 +127,9 @@ Arch::Arch(Config *cfg) : config(cfg) {
   // (6h) hrotate_hoisted: the R key products over automorphisms of the same digits become one hm_inner_product_hoisted launch.  Config key
   // fuse_hoist (default 1).
   fuseHoist = cfg->getValueOr("fuse_hoist", 1) != 0;
+  // (6l) hlintrans: those key products, the plaintext products and the sums over the rotations become one hm_inner_product_lintrans launch.
+  // Config key fuse_lintrans (default 1).
+  fuseLintrans = cfg->getValueOr("fuse_lintrans", 1) != 0;
   // sharded runs: the exchanges of digit j+1 run on the context's exchange stream while digit j converts and transforms (SURVEY.md 7:
   // 2 beta + 2 all-to-alls per key switch instead of 4, same order on every rank).  The per-digit transforms must then stay separate
   // launches, so the fused NTT x key kernel (which needs all digits) is not used.
@@ -266,6 +272,7 @@ typedef std::vector<const Part *> Group;
 
 // records of one stage with equal keys go into one C-ABI call (same kind / opcode / direction / operand shape)
 int partKey(const Instruction &i) {
+  if (!i.ipLinPt.empty()) return 7000 + (int)i.ipX.size() * 100 + (int)i.ipHoistG.size();                  // 7000+: weighted sum of hoisted key products, by digits and rotations
   if (!i.ipHoistG.empty()) return 6000 + (int)i.ipX.size() * 100 + (int)i.ipHoistG.size();                 // 6000+: hoisted key product, by digits and rotations
   if (i.ops == IP && transformsInside(i)) return 400 + (int)i.ipX.size() * 10 + (int)i.ipY.size();         // 400+: transform x key, by digits and keys
   if (isKeyProduct(i)) return 300 + (int)i.ipX.size() * 10 + (int)i.ipY.size();                            // 300+: key product, by digits and keys
@@ -373,6 +380,7 @@ struct Arch::LaunchBuilder {
   void emitCompute(const Group &group, Launches &front, Launches &back);
   void wrapShardedConversion(LaunchPtr L, Recs recs, Launches &front, Launches &back);
   void ipHoisted(Launch &L, Recs recs);
+  void ipLintrans(Launch &L, Recs recs);
   void nttIp(Launch &L, Recs recs);
   void ip(Launch &L, Recs recs);
   void tensor(Launch &L, Recs recs);
@@ -403,6 +411,36 @@ void Arch::LaunchBuilder::ipHoisted(Launch &L, Recs recs) {
       }
   // digits read once, keys read and outputs written once per rotation
   L.bytes = (unsigned long long)recs.size() * (L.ipTerms + 2 * R * L.ipTerms + 2 * R) * LP;
+}
+
+// (6l) one weighted sum of hoisted key products: the hoisted launch's digits and keys, plaintexts c [r][n], outputs out [n][2]; entries with an
+// addend: source d [n], output out1 [n] (hm_ip_lintrans_desc)
+void Arch::LaunchBuilder::ipLintrans(Launch &L, Recs recs) {
+  Instruction *f = recs[0];
+  L.kind = Launch::L_IP_LINTRANS; L.statKey = "EWE";
+  L.ipTerms = (uint32_t)f->ipX.size(); L.ipOuts = 2; L.hoistG = f->ipHoistG;
+  const size_t R = f->ipHoistG.size();
+  size_t addends = 0;
+  for (Instruction *i : recs) addends += i->ipLinAddend != 0;
+  for (Instruction *i : recs) {
+    if (i->ipHoistG != f->ipHoistG) throw std::runtime_error("weighted rotations: the records of one launch rotate by different elements");
+    for (AddrType x : i->ipX) L.a.push_back(limb(x));
+    L.mods.push_back(i->mod_id);
+    L.out.push_back(limb(i->OutputOperand)); L.out.push_back(limb(i->extraOutputs[0]));
+    if (addends) {
+      L.d.push_back(i->ipLinAddend ? limb(i->ipLinAddend) : HM_NO_LIMB);
+      L.out1.push_back(i->ipLinAddend ? limb(i->extraOutputs[1]) : HM_NO_LIMB);
+    }
+  }
+  for (size_t r = 0; r < R; ++r)
+    for (Instruction *i : recs) {
+      for (size_t k = 0; k < 2; ++k)
+        for (AddrType y : i->ipY[r * 2 + k]) L.b.push_back(limb(y));
+      L.c.push_back(limb(i->ipLinPt[r]));
+    }
+  // limb-polys touched: the digits and the addend source once (every rotation gathers from the same ones), keys and plaintext once per rotation,
+  // two outputs per entry and one per addend
+  L.bytes = ((unsigned long long)recs.size() * (L.ipTerms + 2 * R * L.ipTerms + R + 2) + (unsigned long long)addends * 2) * LP;
 }
 
 // transform x key on one GPU (7, 8, 7b): a = source, c = first-pass scratch of every (limb, digit); the digits' conversions as `probs`
@@ -604,7 +642,8 @@ void Arch::LaunchBuilder::emitCompute(const Group &group, Launches &front, Launc
     for (const Part *g : group) for (int sl : slotsOf(g)) addUnique(L->waitSlots, sl);
   for (const Part *g : group) L->name += (L->name.empty() ? "" : "+") + g->name;
   for (Instruction *i : recs) L->refInstructions += i->refInstructions * (i->ops == BCONV_STEP2 ? bconvPorts : 1ull) + i->refExtra;
-  if (f->ops == IP && !f->ipHoistG.empty()) ipHoisted(*L, recs);
+  if (f->ops == IP && !f->ipLinPt.empty()) ipLintrans(*L, recs);
+  else if (f->ops == IP && !f->ipHoistG.empty()) ipHoisted(*L, recs);
   else if (f->ops == IP && transformsInside(*f)) nttIp(*L, recs);
   else if (isKeyProduct(*f)) ip(*L, recs);
   else if (f->fusedTensor) tensor(*L, recs);
@@ -854,7 +893,7 @@ void Arch::replicateForBatch() {
       l->bytes *= batch_;
       continue;
     }
-    if (l->kind == Launch::L_IP_HOISTED) {
+    if (l->kind == Launch::L_IP_HOISTED || l->kind == Launch::L_IP_LINTRANS) {
       // entry-major as the inner product below (the ops of a batch share the keys), inside every rotation's block of keys and outputs
       const size_t n0 = l->mods.size();
       auto inter = [&](std::vector<uint32_t> &v, size_t blocks, size_t width, bool isLimb) {
@@ -864,12 +903,17 @@ void Arch::replicateForBatch() {
             for (uint32_t c = 0; c < batch_; ++c)
               for (size_t w = 0; w < width; ++w) {
                 const uint32_t x = v[(r * n0 + e) * width + w];
-                o.push_back(isLimb && c && !sharedLimbs.count(x) ? x + c * per : x);
+                o.push_back(isLimb && c && x != HM_NO_LIMB && !sharedLimbs.count(x) ? x + c * per : x);
               }
         v.swap(o);
       };
       const size_t R = l->hoistG.size();
-      inter(l->a, 1, l->ipTerms, true); inter(l->b, R, 2 * (size_t)l->ipTerms, true); inter(l->out, R, 2, true); inter(l->mods, 1, 1, false);
+      inter(l->a, 1, l->ipTerms, true); inter(l->b, R, 2 * (size_t)l->ipTerms, true); inter(l->mods, 1, 1, false);
+      if (l->kind == Launch::L_IP_HOISTED) inter(l->out, R, 2, true);
+      else {
+        inter(l->out, 1, 2, true); inter(l->c, R, 1, true);
+        if (!l->d.empty()) { inter(l->d, 1, 1, true); inter(l->out1, 1, 1, true); }
+      }
       l->refInstructions *= batch_;
       l->bytes *= batch_;
       continue;
@@ -1002,7 +1046,7 @@ void Arch::prepare() {
 }
 
 static const char *const kLaunchKindNames[] = {"NTT", "INTT", "EWE", "BCONV", "AUTO", "NTT_SUBSCALE", "TENSOR", "EXCH_IN", "EXCH_OUT", "REPLICATE", "IP", "NTT_IP",
-                                               "BCONV_COL", "EXCH_IN_COL", "EXCH_OUT_COL", "IP_HOISTED"};
+                                               "BCONV_COL", "EXCH_IN_COL", "EXCH_OUT_COL", "IP_HOISTED", "IP_LINTRANS"};
 
 // Per-launch device time (SURVEY.md §8d "per-stage hipEvent times", exchange time at N > 1): every launch of the plan
 // bracketed by its own event pair, in plan order so that the data dependencies (and, sharded, the collectives) line up.
@@ -1031,7 +1075,7 @@ std::string Arch::planText() const {
   for (const auto &l : launches) {
     size_t cnt = l->out.size();
     if (l->kind == Launch::L_BCONV || l->kind == Launch::L_BCONV_COL) { cnt = 0; for (auto &q : l->probs) cnt += q.out.size(); }
-    if (l->kind == Launch::L_IP || l->kind == Launch::L_NTT_IP || l->kind == Launch::L_IP_HOISTED) cnt = l->mods.size();
+    if (l->kind == Launch::L_IP || l->kind == Launch::L_NTT_IP || l->kind == Launch::L_IP_HOISTED || l->kind == Launch::L_IP_LINTRANS) cnt = l->mods.size();
     out += std::string(names[l->kind]) + " " + l->name + " n=" + std::to_string(cnt) + " ref=" + std::to_string(l->refInstructions);
     // pass 11: limb-polys an inverse transform stores split-30 packed / conversions (separate or inside a transform's first pass) that read packed inputs
     const size_t po = (size_t)std::count(l->outPacked.begin(), l->outPacked.end(), 1), pi = (size_t)std::count_if(l->probs.begin(), l->probs.end(), [](const Launch::Prob &q) { return q.inPacked; });
@@ -1049,6 +1093,8 @@ std::string Arch::planText() const {
       out += " rot=" + std::to_string(l->hoistG.size()) + " g=";
       for (size_t r = 0; r < l->hoistG.size(); ++r) out += (r ? "," : "") + std::to_string(l->hoistG[r]);
     }
+    if (l->kind == Launch::L_IP_LINTRANS)   // (6l): entries that also form the addend output
+      out += " addend=" + std::to_string(l->d.size() - (size_t)std::count(l->d.begin(), l->d.end(), HM_NO_LIMB));
     if (l->recordSlot >= 0) out += " mark=" + std::to_string(l->recordSlot);
     if (!l->waitSlots.empty()) { out += " wait="; for (int w : l->waitSlots) out += std::to_string(w) + ","; }
     if (!l->exLimbs.empty()) {
@@ -1136,6 +1182,14 @@ void Arch::enqueue(Launch &l) {
     const hm_ip_hoisted_desc d = {pool, l.a.data(), pool, l.b.data(), pool, l.out.data(), l.mods.data(), (uint32_t)l.mods.size(), l.ipTerms,
                                   (uint32_t)l.hoistG.size(), l.hoistG.data()};
     st = hm_inner_product_hoisted(ctx, &d);
+    break;
+  }
+  case Launch::L_IP_LINTRANS: {
+    const bool add = !l.d.empty();
+    const hm_ip_lintrans_desc d = {pool, l.a.data(), pool, l.b.data(), pool, l.c.data(), add ? pool : nullptr, add ? l.d.data() : nullptr, pool, l.out.data(),
+                                   add ? pool : nullptr, add ? l.out1.data() : nullptr, l.mods.data(), (uint32_t)l.mods.size(), l.ipTerms,
+                                   (uint32_t)l.hoistG.size(), l.hoistG.data()};
+    st = hm_inner_product_lintrans(ctx, &d);
     break;
   }
   case Launch::L_NTT_IP: {

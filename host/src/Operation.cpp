@@ -369,7 +369,7 @@ OperationBase::~OperationBase() {
   for (auto &kv : DataInsMap)
     for (Instruction *i : kv.second) delete i;
 }
-void OperationBase::makeInputs(uint32_t ciphertexts, bool plaintext) {
+void OperationBase::makeInputs(uint32_t ciphertexts, bool plaintext, uint32_t extPlaintexts) {
   for (uint32_t i = 0; i < ciphertexts; i++) {
     cts.emplace_back(level_, N, Datapool, batchSize);
     const std::vector<AddrType> c0 = cts[i].getC0Addr(), c1 = cts[i].getC1Addr();
@@ -387,6 +387,15 @@ void OperationBase::makeInputs(uint32_t ciphertexts, bool plaintext) {
     arch->addInputFill(InputFill{ptx->getC0Addr(), range(0, level_), seed + 4000});
     namedInputs["pt"] = ptx->getC0Addr();
   }
+  std::vector<uint32_t> extMods = range(0, level_);
+  for (uint32_t p : range(maxLevel_, alpha_)) extMods.push_back(p);
+  for (uint32_t r = 1; r <= extPlaintexts; r++) {
+    extPtx.emplace_back(level_ + alpha_, N, Datapool, batchSize);
+    const std::vector<AddrType> pt = extPtx.back().getC0Addr();
+    arch->registerLimbs(pt);
+    arch->addInputFill(InputFill{pt, extMods, seed + 4000 + 100000ull * r});
+    namedInputs["pt" + S(r)] = pt;
+  }
   addrManager.reset(new AddrManage(Datapool.back() + 1, batchSize));
   addrManager->setGlobalDatapPoll(&Datapool);
 }
@@ -394,11 +403,28 @@ std::vector<AddrType> OperationBase::alloc(const std::string &name, uint32_t lim
 void OperationBase::dispatch(const StageList &m) {
   for (const auto &stage : m) driver.dispatchInstructions(stage.first, stage.second);
 }
-std::vector<AddrType> OperationBase::rotateComponent(uint32_t k, uint32_t galois, const std::string &suffix) {
+Limbs OperationBase::rotateComponent(uint32_t k, uint32_t galois, const std::string &suffix) {
   PerLimb s{label + "_AUTO" + suffix + "_Level(", ")_k(" + S(k) + ")", range(0, level_), alloc("AUTOOutput" + suffix + "(" + S(k) + ")", level_)};
   s.a = component(0, k);
-  driver.dispatchInstructions("AUTO" + suffix + "_Key(" + S(k) + ")", autoLimbs(&insgener, galois, s));
-  return s.out;
+  const Limbs rotated{s.out, autoLimbs(&insgener, galois, s)};
+  driver.dispatchInstructions("AUTO" + suffix + "_Key(" + S(k) + ")", rotated.from);
+  return rotated;
+}
+std::vector<uint32_t> OperationBase::hoistedRotations(const std::string &op) const {
+  if (arch->backend() == Arch::BACKEND_SIM) throw std::runtime_error(op + ": backend = sim has no such op (the reference has no hoisted rotation)");
+  if (arch->world() > 1) throw std::runtime_error(op + ": world > 1 is not supported (sharded hoisting is not built)");
+  const uint32_t R = config->getValueOr("rotations", 4), galois = config->getValueOr("galois", 5), twoN = 2 * N;
+  if (R < 1 || R > 16) throw std::runtime_error(op + ": rotations = " + S(R) + ", must be in [1, 16]");
+  if (!(galois & 1) || galois >= twoN) throw std::runtime_error(op + ": galois = " + S(galois) + " must be odd and below 2N = " + S(twoN));
+  std::vector<uint32_t> gs;
+  uint64_t gr = 1;
+  for (uint32_t r = 1; r <= R; ++r) {
+    gr = gr * galois % twoN;
+    if (gr == 1 || std::find(gs.begin(), gs.end(), (uint32_t)gr) != gs.end())
+      throw std::runtime_error(op + ": galois^" + S(r) + " mod 2N repeats an element or is 1: the " + S(R) + " rotations are not distinct");
+    gs.push_back((uint32_t)gr);
+  }
+  return gs;
 }
 void OperationBase::finishRotation(const std::string &out, const std::vector<AddrType> &rotatedC0, const KeySwitch::Output &ks, const std::string &suffix) {
   PerLimb s{label + "_HROTATEadd" + suffix + "_Level(", ")", range(0, level_), alloc("HROTATEOutput" + suffix + "(1)", level_)};
@@ -566,7 +592,7 @@ HROTATE::HROTATE(std::string labelName, uint32_t maxLevel, uint32_t currentLevel
     : OperationBase("HROTATE", labelName, cfg, _arch, maxLevel, currentLevel, alpha) {
   makeInputs(1);
   const uint32_t galois = cfg->getValueOr("galois", 5);
-  const std::vector<AddrType> rc0 = rotateComponent(0, galois, ""), rc1 = rotateComponent(1, galois, "");
+  const std::vector<AddrType> rc0 = rotateComponent(0, galois, "").addr, rc1 = rotateComponent(1, galois, "").addr;
   KeySwitch ksw(labelName, maxLevel, currentLevel, alpha, rc1, &Datapool, &DataInsMap, &insgener, addrManager.get());
   dispatch(ksw.getInsMap());
   finishRotation("out", rc0, ksw.output(), "");
@@ -580,19 +606,8 @@ HROTATE::HROTATE(std::string labelName, uint32_t maxLevel, uint32_t currentLevel
 // valid.  Unfused, the stages run one launch each; fused, pass (6h) of Arch::fusePasses (Planner.cpp) turns the R key products into one hoisted launch.
 HROTATE_HOISTED::HROTATE_HOISTED(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch)
     : OperationBase("HROTATE_HOISTED", labelName, cfg, _arch, maxLevel, currentLevel, alpha) {
-  if (arch->backend() == Arch::BACKEND_SIM) throw std::runtime_error("hrotate_hoisted: backend = sim has no such op (the reference has no hoisted rotation)");
-  if (arch->world() > 1) throw std::runtime_error("hrotate_hoisted: world > 1 is not supported (sharded hoisting is not built)");
-  const uint32_t R = cfg->getValueOr("rotations", 4), galois = cfg->getValueOr("galois", 5), twoN = 2 * N;
-  if (R < 1 || R > 16) throw std::runtime_error("hrotate_hoisted: rotations = " + S(R) + ", must be in [1, 16]");
-  if (!(galois & 1) || galois >= twoN) throw std::runtime_error("hrotate_hoisted: galois = " + S(galois) + " must be odd and below 2N = " + S(twoN));
-  std::vector<uint32_t> gs;
-  uint64_t gr = 1;
-  for (uint32_t r = 1; r <= R; ++r) {
-    gr = gr * galois % twoN;
-    if (gr == 1 || std::find(gs.begin(), gs.end(), (uint32_t)gr) != gs.end())
-      throw std::runtime_error("hrotate_hoisted: galois^" + S(r) + " mod 2N repeats an element or is 1: the " + S(R) + " rotations are not distinct");
-    gs.push_back((uint32_t)gr);
-  }
+  const std::vector<uint32_t> gs = hoistedRotations("hrotate_hoisted");
+  const uint32_t R = (uint32_t)gs.size();
   makeInputs(1);
 
   KeySwitch ks(labelName, maxLevel, currentLevel, alpha, &Datapool, &DataInsMap, &insgener, addrManager.get());
@@ -603,8 +618,70 @@ HROTATE_HOISTED::HROTATE_HOISTED(std::string labelName, uint32_t maxLevel, uint3
     // rotation r's key: the synthetic stream seed + 10000 + 100000 r (+ (2 j + k) 1000 per digit and component, as IP_Key<k>_<j>)
     const KeySwitch::Output out = ks.modDown(ks.keyProduct(ks.rotateDigits(digits, gs[r - 1], rs), seed + 10000 + 100000ull * r, rs), rs);
     dispatch(ks.takeStages());
-    finishRotation("out" + S(r), rotateComponent(0, gs[r - 1], rs), out, rs);
+    finishRotation("out" + S(r), rotateComponent(0, gs[r - 1], rs).addr, out, rs);
   }
+  finishConstruction();
+}
+
+// hlintrans (build extension).  out = sum_r pt_r (.) rot_r(ct1) over hrotate_hoisted's R rotations, with its shared ModUp D_j = ModUp(c1) and ONE
+// ModDown: the plaintexts pt<r> live on the extended basis, multiplying by them and the ModDown are both linear, so the weighted sum is formed
+// on the E = l + alpha limbs first:
+//   acc_{r,k} = sum_j sigma_r(D_j) evk_r[j][k]       rotateDigits + keyProduct per rotation, as hrotate_hoisted
+//   S_k = sum_r acc_{r,k} pt_r   (E limbs),   U = sum_r sigma_r(c0) pt_r[Q limbs]   (l limbs)        MUL, then MAC_ADD per further rotation
+//   out.c0 = U + ModDown(S_0),   out.c1 = ModDown(S_1)
+// A valid key switch, not bit-identical to hrotate_hoisted + R pmult + R - 1 hadd (that rounds in R ModDowns, this in one).  Unfused, the stages
+// run one launch each; fused, pass (6l) of Arch::fusePasses (Planner.cpp) turns everything between the ModUp and the ModDown into one launch.
+HLINTRANS::HLINTRANS(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch)
+    : OperationBase("HLINTRANS", labelName, cfg, _arch, maxLevel, currentLevel, alpha) {
+  const std::vector<uint32_t> gs = hoistedRotations("hlintrans");
+  const uint32_t R = (uint32_t)gs.size();
+  makeInputs(1, /*plaintext=*/false, /*extPlaintexts=*/R);
+
+  KeySwitch ks(labelName, maxLevel, currentLevel, alpha, &Datapool, &DataInsMap, &insgener, addrManager.get());
+  const KeySwitch::Digits digits = ks.modUp(cts[0].getC1Addr(), /*inputMayBeOpInput=*/true);
+  dispatch(ks.takeStages());
+  std::array<std::vector<Limbs>, 3> terms;          // per rotation: acc_{r,0}, acc_{r,1}, sigma_r(c0)
+  std::array<std::vector<std::vector<AddrType>>, 3> weights;   // ... and the plaintext limbs they meet
+  for (uint32_t r = 1; r <= R; ++r) {
+    const std::string rs = "_Rot" + S(r);
+    const KeySwitch::Accumulators acc = ks.keyProduct(ks.rotateDigits(digits, gs[r - 1], rs), seed + 10000 + 100000ull * r, rs);
+    dispatch(ks.takeStages());
+    const std::vector<AddrType> pt = namedInputs.at("pt" + S(r));
+    terms[0].push_back(acc[0]); terms[1].push_back(acc[1]); terms[2].push_back(rotateComponent(0, gs[r - 1], rs));
+    weights[0].push_back(pt); weights[1].push_back(pt); weights[2].push_back(slice(pt, 0, currentLevel));
+  }
+  // sum_r terms[r] * weights[r] over the limbs of `mods`: MUL, then one MAC_ADD per further rotation, the last into LinTransOut_<tag>.  The term
+  // is operand a: pass (6) pairs chains that share their a operands into key products, and the plaintexts are shared by all three sums
+  std::vector<uint32_t> extMods = range(0, currentLevel);
+  for (uint32_t p : range(maxLevel, alpha)) extMods.push_back(p);
+  const std::array<std::string, 3> tags = {"Key0", "Key1", "C0"};
+  std::array<Limbs, 3> sums;
+  for (uint32_t t = 0; t < 3; ++t) {
+    Limbs &sum = sums[t];
+    for (uint32_t r = 0; r < R; ++r) {
+      const std::string at = "(" + S(r + 1) + ")_" + tags[t];
+      PerLimb s{labelName + "_LinTrans_" + tags[t] + "_Rot(" + S(r + 1) + ")_Level(", ")", t < 2 ? extMods : range(0, currentLevel),
+                alloc(r + 1 < R ? "LinTransOut_temp" + at : "LinTransOut_" + tags[t], t < 2 ? currentLevel + alpha : currentLevel)};
+      s.a = terms[t][r].addr;
+      s.b = weights[t][r];
+      s.after = {&terms[t][r].from};
+      const Limbs before = sum;
+      if (r) {
+        s.c = before.addr;
+        s.after.push_back(&before.from);
+      }
+      sum = {s.out, eweLimbs(&insgener, r ? EWE_MAC_ADD : EWE_MUL, s)};
+      driver.dispatchInstructions("LinTrans_" + at, sum.from);
+    }
+  }
+  const KeySwitch::Output down = ks.modDown({sums[0], sums[1]}, "");
+  dispatch(ks.takeStages());
+  PerLimb s{labelName + "_HLINTRANSadd_Level(", ")", range(0, currentLevel), alloc("HLINTRANSOutput(0)", currentLevel)};
+  s.a = down[0];
+  s.c = sums[2].addr;
+  driver.dispatchInstructions("HLINTRANS_Hadd", eweLimbs(&insgener, EWE_ADD, s));
+  setOutput("out", 0, s.out);
+  setOutput("out", 1, down[1]);
   finishConstruction();
 }
 
@@ -660,6 +737,7 @@ static OperationBase *makeOp(const std::string &o, uint32_t maxLevel, uint32_t l
   if (o == "pmult") return new PMULT("test_pmult", maxLevel, level, alpha, cfg, arch);
   if (o == "padd") return new PADD("test_ADD", maxLevel, level, alpha, cfg, arch);
   if (o == "hrotate_hoisted") return new HROTATE_HOISTED("test_hrotate_hoisted", maxLevel, level, alpha, cfg, arch);
+  if (o == "hlintrans") return new HLINTRANS("test_hlintrans", maxLevel, level, alpha, cfg, arch);
   throw std::runtime_error("Error operation requirement, please double confirm!");
 }
 

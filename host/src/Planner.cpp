@@ -51,7 +51,16 @@ struct Arch::Planner {
   void residue();          // 4c
   void tensor();           // 5
   void keyProduct();       // 6
-  void hoist();            // 6h
+  // what (6l) and (6h) both recognise: the live two-key key-product records whose digits are all automorphisms, by one element per record, of
+  // the same materialised digits and are read by nothing else; per (modulus, unrotated digits) the records and their automorphisms, in stage order
+  typedef std::pair<uint32_t, std::vector<AddrType>> DigitsKey;
+  struct RotationGroups {
+    std::map<DigitsKey, std::vector<std::pair<Instruction *, std::vector<Instruction *>>>> members;
+    std::vector<DigitsKey> order;   // first appearance
+  };
+  RotationGroups rotationGroups(Readers &rd);
+  void weightedRotations();   // 6l
+  void hoist();               // 6h
   void transformTimesKey();   // 7 + 8
   void keyProductInverseOut();   // 7b
   void modDownConversion();   // 9
@@ -72,6 +81,7 @@ void Arch::fusePasses(std::vector<Stage> &st) {
   p.residue();
   p.tensor();
   p.keyProduct();
+  if (fuseLintrans) p.weightedRotations();   // before (6h): the records it merges are the ones (6h) would claim
   if (fuseHoist) p.hoist();
   if (fuseHpip) p.transformTimesKey();
   if (fuseHpip && fuseIpInv && oneGpuKernels && p.cap("cap_ip_inverse_out")) p.keyProductInverseOut();
@@ -339,16 +349,9 @@ void Arch::Planner::keyProduct() {
   }
 }
 
-// (6h) hoisted rotations (hrotate_hoisted): two-key inner-product records whose digits are all automorphisms (one element per record) of the SAME
-//      materialised digits, read by nothing else, merge into ONE record per (modulus, digit list): hm_inner_product_hoisted reads the digits once
-//      for every rotation and gathers the key / scatters the output at the automorphism's destination; the automorphisms are never written.
-//      The first record in stage order carries the merged one: every reader of any rotation's output comes after it.
-//      Reads: the key-product records of (6).  Sets on the carrying record: ipX (the unrotated digits), ipY, ipHoistG, OutputOperand, extraOutputs.
-void Arch::Planner::hoist() {
-  Readers rd = readers();
-  typedef std::pair<uint32_t, std::vector<AddrType>> DigitsKey;   // (modulus, unrotated digits)
-  std::map<DigitsKey, std::vector<std::pair<Instruction *, std::vector<Instruction *>>>> groups;   // -> (record, its automorphisms) in stage order
-  std::vector<DigitsKey> groupOrder;
+// the rotations of one ciphertext that share their ModUp, as (6l) and (6h) find them (declared with the passes above)
+Arch::Planner::RotationGroups Arch::Planner::rotationGroups(Readers &rd) {
+  RotationGroups g;
   for (auto &s : st)
     for (Instruction *ip : s.ins) {
       if (!isKeyProduct(*ip) || dead.count(ip) || ip->ipY.size() != 2 || ip->ipXGalois || !ip->ipHoistG.empty() || transformsInside(*ip)) continue;
@@ -364,11 +367,119 @@ void Arch::Planner::hoist() {
       }
       if (autos.size() != ip->ipX.size()) continue;
       const DigitsKey key(ip->mod_id, src);
-      if (!groups.count(key)) groupOrder.push_back(key);
-      groups[key].push_back({ip, autos});
+      if (!g.members.count(key)) g.order.push_back(key);
+      g.members[key].push_back({ip, autos});
     }
-  for (const DigitsKey &key : groupOrder) {
-    const auto &mem = groups[key];
+  return g;
+}
+
+// (6l) weighted sum of rotations (hlintrans): the records (6h) would merge, when every rotation's two outputs are read only by ONE chain
+//      MUL, MAC_ADD ... against operands nobody produces (plaintexts), S_k = sum_r acc_{r,k} * pt_r, merge WITH those chains into one record per
+//      (modulus, digit list): hm_inner_product_lintrans forms the weighted sum in registers and stores S_0, S_1 only.  If a third chain multiplies
+//      the same plaintext limbs with automorphisms, by the rotations' elements, of ONE source (the Q limbs: U = sum_r sigma_r(c0) * pt_r), it joins
+//      as the record's addend output.  Never written: the rotated digits, the per-rotation sums, the rotated c0.  The first key-product record in
+//      stage order carries the merged one: everything it reads is older, every reader of S_k and U comes after the chains' ends.
+//      Reads: the key-product records of (6).  Sets on the carrying record: ipX (the unrotated digits), ipY, ipHoistG, ipLinPt, ipLinAddend,
+//      OutputOperand, extraOutputs.
+void Arch::Planner::weightedRotations() {
+  Readers rd = readers();
+  RotationGroups found = rotationGroups(rd);
+  // the `length` records of the chain that starts with `first` (a MUL) and goes on through MAC_ADD records, each the only reader of the one before
+  // (empty: there is no such chain)
+  typedef std::vector<Instruction *> Chain;
+  auto chainFrom = [&](Instruction *first, size_t length) {
+    Chain c;
+    for (Instruction *i = first; c.size() < length;) {
+      c.push_back(i);
+      if (c.size() == length) break;
+      auto &next = rd[i->OutputOperand];
+      if (next.size() != 1 || !live(next[0]) || next[0]->ops != MULT || next[0]->opcode != EWE_MAC_ADD || next[0]->operandList[2] != i->OutputOperand ||
+          next[0]->mod_id != first->mod_id)
+        return Chain();
+      i = next[0];
+    }
+    return c;
+  };
+  auto isMul = [&](Instruction *i, uint32_t mod) { return live(i) && i->ops == MULT && i->opcode == EWE_MUL && i->mod_id == mod; };
+  for (const DigitsKey &key : found.order) {
+    const auto &mem = found.members[key];
+    const size_t R = mem.size();
+    if (R > HM_IP_LINTRANS_MAX_ROT) continue;
+    std::set<uint32_t> distinct;
+    for (auto &m : mem) distinct.insert(m.second[0]->galois);
+    if (distinct.size() != R) continue;   // two records by one element are not rotations of one ciphertext
+    // S_k: link r multiplies rotation r's output k (operand a) with that rotation's plaintext limb (operand b, the same for both k)
+    Chain S[2];
+    std::vector<AddrType> pt;
+    bool ok = true;
+    for (size_t k = 0; k < 2 && ok; ++k) {
+      const AddrType out0 = k == 0 ? mem[0].first->OutputOperand : mem[0].first->extraOutputs[0];
+      auto &r0 = rd[out0];
+      ok = r0.size() == 1 && isMul(r0[0], key.first) && r0[0]->operandList[0] == out0;
+      if (!ok) break;
+      S[k] = chainFrom(r0[0], R);
+      ok = S[k].size() == R;
+      for (size_t r = 0; r < R && ok; ++r) {
+        Instruction *l = S[k][r];
+        const AddrType out = k == 0 ? mem[r].first->OutputOperand : mem[r].first->extraOutputs[0];
+        ok = l->operandList[0] == out && onlyReader(rd, out, l) && !producerOf(l->operandList[1]) && (k == 0 || l->operandList[1] == pt[r]);
+        if (ok && k == 0) pt.push_back(l->operandList[1]);
+      }
+    }
+    if (!ok) continue;
+    // U: a third MUL reader of the first plaintext limb whose chain multiplies pt_r with sigma_r of one source
+    Chain U;
+    AddrType addend = 0;
+    std::vector<Instruction *> addendAutos;
+    for (Instruction *u : rd[pt[0]]) {
+      if (u == S[0][0] || u == S[1][0] || !isMul(u, key.first) || u->operandList[1] != pt[0]) continue;
+      Chain c = chainFrom(u, R);
+      std::vector<Instruction *> autos;
+      for (size_t r = 0; r < c.size(); ++r) {
+        Instruction *l = c[r], *a = producerOf(l->operandList[0]);
+        if (l->operandList[1] != pt[r] || !a || a->ops != AUTO || !live(a) || a->mod_id != key.first || a->galois != mem[r].second[0]->galois ||
+            !onlyReader(rd, l->operandList[0], l) || (r && a->operandList[0] != autos[0]->operandList[0]))
+          break;
+        autos.push_back(a);
+      }
+      if (autos.size() != R) continue;
+      U = c; addend = autos[0]->operandList[0]; addendAutos = autos;
+      break;
+    }
+    Instruction *c = mem[0].first;
+    std::vector<std::vector<AddrType>> ys;
+    std::vector<uint32_t> gs;
+    auto absorb = [&](Instruction *i) { if (i != c) { c->refInstructions += i->refInstructions; dead.insert(i); } };
+    for (size_t r = 0; r < R; ++r) {
+      ys.insert(ys.end(), mem[r].first->ipY.begin(), mem[r].first->ipY.end());
+      gs.push_back(mem[r].second[0]->galois);
+      absorb(mem[r].first);
+      for (Instruction *a : mem[r].second) absorb(a);
+      for (size_t k = 0; k < 2; ++k) absorb(S[k][r]);
+      if (addend) { absorb(U[r]); absorb(addendAutos[r]); }
+    }
+    c->ipX = key.second;
+    c->ipY = ys;
+    c->ipHoistG = gs;
+    c->ipLinPt = pt;
+    c->ipLinAddend = addend;
+    c->OutputOperand = S[0].back()->OutputOperand;
+    c->extraOutputs = {S[1].back()->OutputOperand};
+    if (addend) c->extraOutputs.push_back(U.back()->OutputOperand);
+    for (const Write &w : recordWrites(*c)) producer[w.addr] = c;
+  }
+}
+
+// (6h) hoisted rotations (hrotate_hoisted): two-key inner-product records whose digits are all automorphisms (one element per record) of the SAME
+//      materialised digits, read by nothing else, merge into ONE record per (modulus, digit list): hm_inner_product_hoisted reads the digits once
+//      for every rotation and gathers the key / scatters the output at the automorphism's destination; the automorphisms are never written.
+//      The first record in stage order carries the merged one: every reader of any rotation's output comes after it.
+//      Reads: the key-product records of (6).  Sets on the carrying record: ipX (the unrotated digits), ipY, ipHoistG, OutputOperand, extraOutputs.
+void Arch::Planner::hoist() {
+  Readers rd = readers();
+  RotationGroups found = rotationGroups(rd);
+  for (const DigitsKey &key : found.order) {
+    const auto &mem = found.members[key];
     for (size_t b = 0; b < mem.size(); b += HM_IP_HOISTED_MAX_ROT) {
       const size_t e = std::min(mem.size(), b + (size_t)HM_IP_HOISTED_MAX_ROT);
       std::set<uint32_t> distinct;

@@ -188,6 +188,32 @@ typedef struct hm_ip_hoisted_desc {
   const uint32_t *galois;                         /* [n_rot] */
 } hm_ip_hoisted_desc;
 hm_status hm_inner_product_hoisted(hm_ctx *ctx, const hm_ip_hoisted_desc *desc);
+/* Plaintext-weighted sum of the hoisted key products (hlintrans): what hm_inner_product_hoisted forms per rotation is
+ * multiplied by that rotation's plaintext and summed over the rotations BEFORE it is stored,
+ *   t[r][i][k]    = sum_j automorph_{galois[r]}(x[i][j]) (.) y[r][i][k][j]      (reduced: hm_inner_product_hoisted's out[r][i][k])
+ *   out[i][k]     = sum_r pt[r][i] (.) t[r][i][k],                               k < 2, j < n_terms <= 4, r < n_rot <= 16
+ *   addend_out[i] = sum_r pt[r][i] (.) automorph_{galois[r]}(addend[i])          for the entries i that carry an addend source,
+ * every residue fully reduced: bit-identical to hm_inner_product_hoisted followed by the HM_OP_MUL / HM_OP_MAC_ADD chains (and hm_automorph of the
+ * addend), none of whose n_rot * 2 n + n_rot * n_add intermediates is written.  A workgroup owns the DESTINATION (gather form): per rotation it
+ * loads the digits' (and the addend's) aligned pair at the automorphism's source, in order or swapped (hm_automorph's index map), and both keys
+ * and the plaintext at the destination.  Row-major lists: x_limbs[i * n_terms + j], y_limbs[((r * n + i) * 2 + k) * n_terms + j],
+ * pt_limbs[r * n + i], out_limbs[i * 2 + k].  addend / addend_limbs / addend_out / addend_out_limbs are optional together (NULL: no entry has an
+ * addend); addend_limbs[i] == HM_NO_LIMB: entry i has none and addend_out_limbs[i] is ignored.  Every galois[r] is odd and below 2N.  No output
+ * limb-poly (out, addend_out) may overlap, by address range, a digit, a key, a plaintext or an addend source: HM_ERR_ARG.  Safe under graph
+ * capture once it has run with the same limb lists. */
+#define HM_IP_LINTRANS_MAX_ROT 16
+typedef struct hm_ip_lintrans_desc {
+  const uint64_t *x;       const uint32_t *x_limbs;           /* digits [n][n_terms] */
+  const uint64_t *y;       const uint32_t *y_limbs;           /* keys [n_rot][n][2][n_terms] */
+  const uint64_t *pt;      const uint32_t *pt_limbs;          /* plaintexts [n_rot][n] */
+  const uint64_t *addend;  const uint32_t *addend_limbs;      /* optional addend source [n]; HM_NO_LIMB: none for this entry */
+  uint64_t *out;           const uint32_t *out_limbs;         /* [n][2] */
+  uint64_t *addend_out;    const uint32_t *addend_out_limbs;  /* [n], read where addend_limbs[i] != HM_NO_LIMB */
+  const uint32_t *mod_ids;                                    /* [n] */
+  uint32_t n, n_terms, n_rot;
+  const uint32_t *galois;                                     /* [n_rot] */
+} hm_ip_lintrans_desc;
+hm_status hm_inner_product_lintrans(hm_ctx *ctx, const hm_ip_lintrans_desc *desc);
 
 /* K1 x K5 — the HPIP unit as a fused NTT-epilogue x evaluation-key MAC: for extended limb i,
  *     out[i][k] = sum_{j < n_terms} X_j[i] * y[i][k][j],   X_j[i] = NTT(x[i][j]) if x_is_coeff[i][j] else x[i][j]
