@@ -18,6 +18,7 @@
 
 #include "../../include/homulator_hip.h"
 #include "hm_elem_core.h"
+#include "hm_ip_core.h"
 #include "hm_modarith.h"
 #include "hm_ntt_core.h"
 #include "hm_params.h"
@@ -507,41 +508,21 @@ __global__ void __launch_bounds__(256) k_ewe(HmEweArgs a) {
   }
 }
 
+// K5 (hm_ip_core.h): one workgroup per 512 coefficients of an entry, in the plain, the hoisted and the weighted-sum form
 template <int TERMS, int OUTS>
 __global__ void __launch_bounds__(256) k_inner_product(HmIpArgs a) {
-  const uint32_t N = 1u << a.logN;
-  const uint32_t per_limb = N / 512;
-  const uint32_t entry = blockIdx.x / per_limb, chunk = blockIdx.x % per_limb;
-  if (entry >= a.n_limbs) return;
-  const HmIpLimb &lb = a.limb[entry];
-  const HmMod m = a.mods[lb.mod];
-  const size_t off = (size_t)chunk * 512 + 2 * threadIdx.x;
-  ulonglong2 vx[TERMS], vy[OUTS][TERMS];
-  // x through an automorphism (wave-uniform choice): the aligned pair that holds this unit's two sources, swapped when it arrives in the other order
-  size_t offx = off;
-  bool swap = false;
-  if (a.x_galois > 1) {
-    const uint32_t s = hm_auto_src((uint32_t)off, a.x_galois, a.logN);
-    offx = s & ~1u; swap = s & 1u;
-  }
-#pragma unroll
-  for (int j = 0; j < TERMS; ++j) {
-    vx[j] = *reinterpret_cast<const ulonglong2 *>(a.x + (size_t)lb.x[j] * N + offx);
-    if (swap) { const unsigned long long t = vx[j].x; vx[j].x = vx[j].y; vx[j].y = t; }
-#pragma unroll
-    for (int k = 0; k < OUTS; ++k) vy[k][j] = *reinterpret_cast<const ulonglong2 *>(a.y + (size_t)lb.y[k][j] * N + off);
-  }
-#pragma unroll
-  for (int k = 0; k < OUTS; ++k) {
-    hm_u128 s0 = 0, s1 = 0;
-#pragma unroll
-    for (int j = 0; j < TERMS; ++j) {
-      s0 += (hm_u128)vx[j].x * vy[k][j].x;
-      s1 += (hm_u128)vx[j].y * vy[k][j].y;
-    }
-    const ulonglong2 r = {hm_barrett(s0, m), hm_barrett(s1, m)};  // TERMS <= 4 products below 2^120: within 2^(k+63)
-    *reinterpret_cast<ulonglong2 *>(a.out + (size_t)lb.out[k] * N + off) = r;
-  }
+  const uint32_t per_limb = (1u << a.logN) / HM_IP_CHUNK, entry = blockIdx.x / per_limb;
+  if (entry < a.n_limbs) hm_ip_thread<TERMS, OUTS>(a, entry, blockIdx.x % per_limb, threadIdx.x);
+}
+template <int TERMS>
+__global__ void __launch_bounds__(256) k_inner_product_hoisted(HmIpHoistArgs a) {
+  const uint32_t per_limb = (1u << a.logN) / HM_IP_CHUNK, entry = blockIdx.x / per_limb;
+  if (entry < a.n_limbs) hm_ip_hoisted_thread<TERMS>(a, entry, blockIdx.x % per_limb, threadIdx.x);
+}
+template <int TERMS>
+__global__ void __launch_bounds__(256) k_inner_product_lintrans(HmIpLinArgs a) {
+  const uint32_t per_limb = (1u << a.logN) / HM_IP_CHUNK, entry = blockIdx.x / per_limb;
+  if (entry < a.n_limbs) hm_ip_lintrans_thread<TERMS>(a, entry, blockIdx.x % per_limb, threadIdx.x);
 }
 
 // One kernel per input-basis size: a single kernel switching over n_in is allocated for its largest case (140 VGPRs
@@ -1622,10 +1603,39 @@ extern "C" hm_status hm_ewe(hm_ctx *c, int op, const uint64_t *pa, const uint32_
   return HM_OK;
 }
 
-template <int T, int O>
-static void launch_ip(hm_ctx *c, const HmIpArgs &a) {
-  hipLaunchKernelGGL((k_inner_product<T, O>), dim3(a.n_limbs * (c->P.N / 512)), dim3(256), 0, c->stream, a);
+// ---- K5, the key product (hm_ip_core.h).  A form's kernels by [n_terms - 1][n_out - 1] (the forms over rotations: always two keys) and their launch
+#define HM_K(k) {{k<1>}, {k<2>}, {k<3>}, {k<4>}}
+static void (*const k_ip[HM_IP_MAX_TERMS][HM_IP_MAX_OUT])(HmIpArgs) = {{k_inner_product<1, 1>, k_inner_product<1, 2>}, {k_inner_product<2, 1>, k_inner_product<2, 2>},
+                                                                       {k_inner_product<3, 1>, k_inner_product<3, 2>}, {k_inner_product<4, 1>, k_inner_product<4, 2>}};
+static void (*const k_ip_hoisted[HM_IP_MAX_TERMS][1])(HmIpHoistArgs) = HM_K(k_inner_product_hoisted);
+static void (*const k_ip_lintrans[HM_IP_MAX_TERMS][1])(HmIpLinArgs) = HM_K(k_inner_product_lintrans);
+#undef HM_K
+template <class Args, size_t OUTS>
+static void launch_ip(hm_ctx *c, void (*const (&kernel)[HM_IP_MAX_TERMS][OUTS])(Args), const Args &a, uint32_t T, uint32_t O = 1) {
+  hipLaunchKernelGGL(kernel[T - 1][O - 1], dim3(a.n_limbs * ((1u << a.logN) / HM_IP_CHUNK)), dim3(256), 0, c->stream, a);
 }
+
+// What the three entry points check first, in this order: no null argument (null_msg: the refusal, or nullptr), n_terms and the second count
+// (n_out / n_rot) in range, every Galois element (nullptr: the form has no list) odd and below 2N, every limb and modulus index in range
+struct IpList { const uint32_t *limbs; uint32_t count; };
+static hm_status ip_check(hm_ctx *c, const char *what, const char *null_msg, uint32_t T, const char *second, uint32_t v, uint32_t vmax, const uint32_t *galois,
+                          std::initializer_list<IpList> lists, const uint32_t *mod_ids, uint32_t n) {
+  if (null_msg) return fail(c, HM_ERR_ARG, "%s: %s", what, null_msg);
+  if (T == 0 || T > HM_IP_MAX_TERMS || v == 0 || v > vmax) return fail(c, HM_ERR_ARG, "%s: n_terms in [1,%d], %s in [1,%d]", what, HM_IP_MAX_TERMS, second, vmax);
+  for (uint32_t r = 0; galois && r < v; ++r)
+    if (!(galois[r] & 1) || galois[r] >= 2 * c->P.N) return fail(c, HM_ERR_ARG, "%s: galois[%u] is not an odd number below 2N", what, r);
+  for (const IpList &l : lists)
+    if (hm_status st = check_limbs(c, what, l.limbs, l.count)) return st;
+  return check_mods(c, what, mod_ids, n);
+}
+template <class Rec>
+static hm_status ip_device_recs(hm_ctx *c, const std::vector<Rec> &recs, const Rec **out) {
+  const void *tab = nullptr;
+  const hm_status st = device_table(c, recs.data(), sizeof(Rec) * recs.size(), &tab);
+  *out = static_cast<const Rec *>(tab);
+  return st;
+}
+
 extern "C" hm_status hm_inner_product(hm_ctx *c, const uint64_t *x, const uint32_t *x_limbs, const uint64_t *y,
                                       const uint32_t *y_limbs, uint64_t *out, const uint32_t *out_limbs,
                                       const uint32_t *mod_ids, uint32_t n, uint32_t n_terms, uint32_t n_out) {
@@ -1633,263 +1643,84 @@ extern "C" hm_status hm_inner_product(hm_ctx *c, const uint64_t *x, const uint32
   return hm_inner_product_ex(c, &d);
 }
 extern "C" hm_status hm_inner_product_ex(hm_ctx *c, const hm_ip_desc *d) {
+  static const char *const what = "hm_inner_product";
+  static const hm_ip_desc none = {};
   if (!c) return HM_ERR_ARG;
-  if (!d) return fail(c, HM_ERR_ARG, "hm_inner_product: null argument");
-  const uint64_t *x = d->x, *y = d->y;
-  uint64_t *out = d->out;
-  const uint32_t *x_limbs = d->x_limbs, *y_limbs = d->y_limbs, *out_limbs = d->out_limbs, *mod_ids = d->mod_ids;
-  const uint32_t n = d->n, n_terms = d->n_terms, n_out = d->n_out;
-  if (d->x_galois && (!(d->x_galois & 1) || d->x_galois >= 2 * c->P.N)) return fail(c, HM_ERR_ARG, "hm_inner_product: x_galois is not an odd number below 2N");
-  if (!x || !y || !out || !x_limbs || !y_limbs || !out_limbs) return fail(c, HM_ERR_ARG, "hm_inner_product: null argument");
-  // gathered operands come from other positions than the ones a workgroup writes
-  if (d->x_galois > 1 && hm_limbs_overlap(out, out_limbs, n * n_out, x, x_limbs, n * n_terms, c->P.N))
-    return fail(c, HM_ERR_ARG, "hm_inner_product: an operand read through the automorphism is a limb the call writes");
-  if (n_terms == 0 || n_terms > HM_IP_MAX_TERMS || n_out == 0 || n_out > HM_IP_MAX_OUT)
-    return fail(c, HM_ERR_ARG, "hm_inner_product: n_terms in [1,%d], n_out in [1,%d]", HM_IP_MAX_TERMS, HM_IP_MAX_OUT);
+  if (!d) d = &none;   // every pointer null: refused as such
+  const uint32_t n = d->n, T = d->n_terms, K = d->n_out;
+  if (d->x_galois && (!(d->x_galois & 1) || d->x_galois >= 2 * c->P.N)) return fail(c, HM_ERR_ARG, "%s: x_galois is not an odd number below 2N", what);
+  const bool null = !d->x || !d->y || !d->out || !d->x_limbs || !d->y_limbs || !d->out_limbs;
   hm_status st;
-  if ((st = check_limbs(c, "hm_inner_product", x_limbs, n * n_terms)) || (st = check_limbs(c, "hm_inner_product", y_limbs, n * n_terms * n_out)) ||
-      (st = check_limbs(c, "hm_inner_product", out_limbs, n * n_out)) || (st = check_mods(c, "hm_inner_product", mod_ids, n)))
+  if ((st = ip_check(c, what, null ? "null argument" : nullptr, T, "n_out", K, HM_IP_MAX_OUT, nullptr,
+                     {{d->x_limbs, n * T}, {d->y_limbs, n * T * K}, {d->out_limbs, n * K}}, d->mod_ids, n)))
     return st;
+  // gathered operands come from other positions than the ones a workgroup writes
+  if (d->x_galois > 1 && hm_limbs_overlap(d->out, d->out_limbs, n * K, d->x, d->x_limbs, n * T, c->P.N))
+    return fail(c, HM_ERR_ARG, "%s: an operand read through the automorphism is a limb the call writes", what);
   HM_HIP(c, hipSetDevice(c->device));
   for (uint32_t base = 0; base < n; base += HM_IP_MAX_LIMBS) {
     const uint32_t cnt = std::min<uint32_t>(HM_IP_MAX_LIMBS, n - base);
     HmIpArgs a;
-    a.x = x; a.y = y; a.out = out; a.mods = c->d_mods; a.logN = c->P.logN; a.n_limbs = cnt; a.n_terms = n_terms; a.n_out = n_out;
+    a.x = d->x; a.y = d->y; a.out = d->out; a.mods = c->d_mods; a.logN = c->P.logN; a.n_limbs = cnt; a.n_terms = T; a.n_out = K;
     a.x_galois = d->x_galois;
-    for (uint32_t i = 0; i < cnt; ++i) {
-      const uint32_t g = base + i;
-      HmIpLimb &l = a.limb[i];
-      l.mod = (uint16_t)mod_ids[g]; l.pad = 0;
-      for (uint32_t j = 0; j < n_terms; ++j) l.x[j] = (uint16_t)x_limbs[g * n_terms + j];
-      for (uint32_t k = 0; k < n_out; ++k) {
-        l.out[k] = (uint16_t)out_limbs[g * n_out + k];
-        for (uint32_t j = 0; j < n_terms; ++j) l.y[k][j] = (uint16_t)y_limbs[(g * n_out + k) * n_terms + j];
-      }
-    }
-    switch (n_terms * 10 + n_out) {
-    case 11: launch_ip<1, 1>(c, a); break; case 12: launch_ip<1, 2>(c, a); break;
-    case 21: launch_ip<2, 1>(c, a); break; case 22: launch_ip<2, 2>(c, a); break;
-    case 31: launch_ip<3, 1>(c, a); break; case 32: launch_ip<3, 2>(c, a); break;
-    case 41: launch_ip<4, 1>(c, a); break; case 42: launch_ip<4, 2>(c, a); break;
-    }
+    hm_ip_fill_recs(a.limb, d->x_limbs + (size_t)base * T, d->y_limbs + (size_t)base * K * T, d->out_limbs + (size_t)base * K, (size_t)cnt * K,
+                    d->mod_ids + base, cnt, T, K, 1);
+    launch_ip(c, k_ip, a, T, K);
     HM_HIP(c, hipGetLastError());
   }
   return HM_OK;
 }
 
-// ---- K5 hoisted (hm_inner_product_hoisted): the key products of n_rot rotations of ONE ciphertext from its unrotated digits.  sigma_g takes the
-// aligned pair (off, off + 1) of a digit to the aligned pair at hm_auto_src(off, g^-1 mod 2N), in order or swapped (hm_ntt_core.h): a thread
-// loads its pair of every digit ONCE and, rotation by rotation, gathers the two keys and stores the two sums at that destination.  One record per
-// (rotation, entry) in a device table (16 rotations of 64 entries do not fit the kernel arguments).
-struct HmIpHoistRec {
-  uint16_t x[HM_IP_MAX_TERMS];
-  uint16_t y[2][HM_IP_MAX_TERMS];
-  uint16_t out[2];
-  uint16_t mod, pad;
-};
-struct HmIpHoistArgs {
-  const uint64_t *x, *y;
-  uint64_t *out;
-  const HmMod *mods;
-  const HmIpHoistRec *rec;   // [n_rot][n_limbs]
-  uint32_t logN, n_limbs, n_rot;
-  uint32_t dst_galois[HM_IP_HOISTED_MAX_ROT];   // g_r^-1 mod 2N: coefficient i of a digit lands at hm_auto_src(i, g_r^-1) of rotation r
-};
-
-template <int TERMS>
-__global__ void __launch_bounds__(256) k_inner_product_hoisted(HmIpHoistArgs a) {
-  const uint32_t N = 1u << a.logN;
-  const uint32_t per_limb = N / 512;
-  const uint32_t entry = blockIdx.x / per_limb, chunk = blockIdx.x % per_limb;
-  if (entry >= a.n_limbs) return;
-  const HmIpHoistRec &l0 = a.rec[entry];
-  const HmMod m = a.mods[l0.mod];
-  const uint32_t off = chunk * 512 + 2 * threadIdx.x;
-  ulonglong2 vx[TERMS];
-#pragma unroll
-  for (int j = 0; j < TERMS; ++j) vx[j] = *reinterpret_cast<const ulonglong2 *>(a.x + (size_t)l0.x[j] * N + off);
-#pragma unroll 1
-  for (uint32_t r = 0; r < a.n_rot; ++r) {
-    const HmIpHoistRec &lb = a.rec[(size_t)r * a.n_limbs + entry];
-    const uint32_t d = hm_auto_src(off, a.dst_galois[r], a.logN);
-    const size_t p = d & ~1u;
-    const bool swap = d & 1u;
-    ulonglong2 vy[2][TERMS];
-#pragma unroll
-    for (int k = 0; k < 2; ++k)
-#pragma unroll
-      for (int j = 0; j < TERMS; ++j) vy[k][j] = *reinterpret_cast<const ulonglong2 *>(a.y + (size_t)lb.y[k][j] * N + p);
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      hm_u128 s0 = 0, s1 = 0;
-#pragma unroll
-      for (int j = 0; j < TERMS; ++j) {
-        const uint64_t x0 = swap ? vx[j].y : vx[j].x, x1 = swap ? vx[j].x : vx[j].y;
-        s0 += (hm_u128)x0 * vy[k][j].x;
-        s1 += (hm_u128)x1 * vy[k][j].y;
-      }
-      const ulonglong2 o = {hm_barrett(s0, m), hm_barrett(s1, m)};   // the same sums as k_inner_product's: bit-identical outputs
-      *reinterpret_cast<ulonglong2 *>(a.out + (size_t)lb.out[k] * N + p) = o;
-    }
-  }
-}
-
+// hoisted: one record per (rotation, entry) in a device table
 extern "C" hm_status hm_inner_product_hoisted(hm_ctx *c, const hm_ip_hoisted_desc *d) {
+  static const char *const what = "hm_inner_product_hoisted";
+  static const hm_ip_hoisted_desc none = {};
   if (!c) return HM_ERR_ARG;
-  if (!d || !d->x || !d->x_limbs || !d->y || !d->y_limbs || !d->out || !d->out_limbs || !d->mod_ids || !d->galois)
-    return fail(c, HM_ERR_ARG, "hm_inner_product_hoisted: null argument");
+  if (!d) d = &none;
   const uint32_t n = d->n, T = d->n_terms, R = d->n_rot, N = c->P.N;
-  if (T == 0 || T > HM_IP_MAX_TERMS || R == 0 || R > HM_IP_HOISTED_MAX_ROT)
-    return fail(c, HM_ERR_ARG, "hm_inner_product_hoisted: n_terms in [1,%d], n_rot in [1,%d]", HM_IP_MAX_TERMS, HM_IP_HOISTED_MAX_ROT);
-  for (uint32_t r = 0; r < R; ++r)
-    if (!(d->galois[r] & 1) || d->galois[r] >= 2 * N) return fail(c, HM_ERR_ARG, "hm_inner_product_hoisted: galois[%u] is not an odd number below 2N", r);
+  const bool null = !d->x || !d->x_limbs || !d->y || !d->y_limbs || !d->out || !d->out_limbs || !d->mod_ids || !d->galois;
   hm_status st;
-  if ((st = check_limbs(c, "hm_inner_product_hoisted", d->x_limbs, n * T)) || (st = check_limbs(c, "hm_inner_product_hoisted", d->y_limbs, R * n * 2 * T)) ||
-      (st = check_limbs(c, "hm_inner_product_hoisted", d->out_limbs, R * n * 2)) || (st = check_mods(c, "hm_inner_product_hoisted", d->mod_ids, n)))
+  if ((st = ip_check(c, what, null ? "null argument" : nullptr, T, "n_rot", R, HM_IP_HOISTED_MAX_ROT, d->galois,
+                     {{d->x_limbs, n * T}, {d->y_limbs, R * n * 2 * T}, {d->out_limbs, R * n * 2}}, d->mod_ids, n)))
     return st;
   // every output is stored at other positions than the ones its workgroup reads (the scatter of sigma_r): it may overlap no digit and no key
   if (hm_limbs_overlap(d->out, d->out_limbs, R * n * 2, d->x, d->x_limbs, n * T, N))
-    return fail(c, HM_ERR_ARG, "hm_inner_product_hoisted: an output limb-poly overlaps a digit (x)");
+    return fail(c, HM_ERR_ARG, "%s: an output limb-poly overlaps a digit (x)", what);
   if (hm_limbs_overlap(d->out, d->out_limbs, R * n * 2, d->y, d->y_limbs, R * n * 2 * T, N))
-    return fail(c, HM_ERR_ARG, "hm_inner_product_hoisted: an output limb-poly overlaps a key limb-poly (y)");
+    return fail(c, HM_ERR_ARG, "%s: an output limb-poly overlaps a key limb-poly (y)", what);
   if (n == 0) return HM_OK;
   std::vector<HmIpHoistRec> recs((size_t)R * n);
-  memset(recs.data(), 0, sizeof(HmIpHoistRec) * recs.size());
-  for (uint32_t r = 0; r < R; ++r)
-    for (uint32_t i = 0; i < n; ++i) {
-      HmIpHoistRec &l = recs[(size_t)r * n + i];
-      const size_t e = (size_t)r * n + i;
-      l.mod = (uint16_t)d->mod_ids[i];
-      for (uint32_t j = 0; j < T; ++j) l.x[j] = (uint16_t)d->x_limbs[(size_t)i * T + j];
-      for (uint32_t k = 0; k < 2; ++k) {
-        l.out[k] = (uint16_t)d->out_limbs[e * 2 + k];
-        for (uint32_t j = 0; j < T; ++j) l.y[k][j] = (uint16_t)d->y_limbs[(e * 2 + k) * T + j];
-      }
-    }
+  hm_ip_fill_recs(recs.data(), d->x_limbs, d->y_limbs, d->out_limbs, (size_t)R * n * 2, d->mod_ids, n, T, 2, R);
   HM_HIP(c, hipSetDevice(c->device));
-  const void *dtab = nullptr;
-  if ((st = device_table(c, recs.data(), sizeof(HmIpHoistRec) * recs.size(), &dtab))) return st;
   HmIpHoistArgs a;
-  a.x = d->x; a.y = d->y; a.out = d->out; a.mods = c->d_mods; a.rec = static_cast<const HmIpHoistRec *>(dtab);
+  if ((st = ip_device_recs(c, recs, &a.rec))) return st;
+  a.x = d->x; a.y = d->y; a.out = d->out; a.mods = c->d_mods;
   a.logN = c->P.logN; a.n_limbs = n; a.n_rot = R;
-  for (uint32_t r = 0; r < HM_IP_HOISTED_MAX_ROT; ++r) {
-    const uint32_t g = r < R ? d->galois[r] : 1u;
-    uint32_t v = g;                                   // g^-1 mod 2^32 (g odd: Newton's iteration doubles the correct low bits), then mod 2N
-    for (int it = 0; it < 5; ++it) v *= 2u - g * v;
-    a.dst_galois[r] = v & (2 * N - 1);
-  }
-  const dim3 grid(n * (N / 512));
-  switch (T) {
-  case 1: hipLaunchKernelGGL(k_inner_product_hoisted<1>, grid, dim3(256), 0, c->stream, a); break;
-  case 2: hipLaunchKernelGGL(k_inner_product_hoisted<2>, grid, dim3(256), 0, c->stream, a); break;
-  case 3: hipLaunchKernelGGL(k_inner_product_hoisted<3>, grid, dim3(256), 0, c->stream, a); break;
-  case 4: hipLaunchKernelGGL(k_inner_product_hoisted<4>, grid, dim3(256), 0, c->stream, a); break;
-  }
+  for (uint32_t r = 0; r < HM_IP_HOISTED_MAX_ROT; ++r) a.dst_galois[r] = hm_auto_inv(r < R ? d->galois[r] : 1u, a.logN);
+  launch_ip(c, k_ip_hoisted, a, T);
   HM_HIP(c, hipGetLastError());
   return HM_OK;
 }
 
-// ---- K5 weighted sum of rotations (hm_inner_product_lintrans): sum_r pt_r * (the hoisted key product of rotation r), formed before anything is
-// stored.  The sum over the rotations needs a fixed destination, so this is the GATHER form of the kernel above: a thread owns the aligned pair p
-// of the outputs; rotation by rotation it loads every digit's pair at the automorphism's source of p (hm_auto_src(p, g_r): an aligned pair, in
-// order or swapped — k_inner_product's x_galois map), both keys and the plaintext at p, forms t_k = reduce(sum_j x_j y_kj) exactly as
-// k_inner_product_hoisted does and adds pt * t_k to a 128-bit accumulator per key and word.  Entries with an addend source (the Q limbs: c0)
-// gather it at the same source and accumulate pt * c0 as a third output.  One record per (rotation, entry) in a device table; the digits, the
-// addend, the outputs and the modulus are read from rotation 0's record.
-struct HmIpLinRec {
-  uint16_t x[HM_IP_MAX_TERMS];
-  uint16_t y[2][HM_IP_MAX_TERMS];
-  uint16_t out[2];
-  uint16_t pt, add_src, add_out;
-  uint16_t mod, has_add, pad;
-};
-struct HmIpLinArgs {
-  const uint64_t *x, *y, *pt, *addend;
-  uint64_t *out, *addend_out;
-  const HmMod *mods;
-  const HmIpLinRec *rec;   // [n_rot][n_limbs]
-  uint32_t logN, n_limbs, n_rot;
-  uint32_t galois[HM_IP_LINTRANS_MAX_ROT];
-};
-
-template <int TERMS>
-__global__ void __launch_bounds__(256) k_inner_product_lintrans(HmIpLinArgs a) {
-  const uint32_t N = 1u << a.logN;
-  const uint32_t per_limb = N / 512;
-  const uint32_t entry = blockIdx.x / per_limb, chunk = blockIdx.x % per_limb;
-  if (entry >= a.n_limbs) return;
-  const HmIpLinRec &l0 = a.rec[entry];
-  const HmMod m = a.mods[l0.mod];
-  const bool add = l0.has_add != 0;   // workgroup-uniform
-  const uint32_t p = chunk * 512 + 2 * threadIdx.x;
-  hm_u128 S[2][2] = {{0, 0}, {0, 0}}, U[2] = {0, 0};
-#pragma unroll 1
-  for (uint32_t r = 0; r < a.n_rot; ++r) {
-    const HmIpLinRec &lb = a.rec[(size_t)r * a.n_limbs + entry];
-    const uint32_t s = hm_auto_src(p, a.galois[r], a.logN);
-    const size_t sp = s & ~1u;
-    const bool swap = s & 1u;
-    ulonglong2 vx[TERMS], vy[2][TERMS];
-#pragma unroll
-    for (int j = 0; j < TERMS; ++j) vx[j] = *reinterpret_cast<const ulonglong2 *>(a.x + (size_t)l0.x[j] * N + sp);
-#pragma unroll
-    for (int k = 0; k < 2; ++k)
-#pragma unroll
-      for (int j = 0; j < TERMS; ++j) vy[k][j] = *reinterpret_cast<const ulonglong2 *>(a.y + (size_t)lb.y[k][j] * N + p);
-    const ulonglong2 vp = *reinterpret_cast<const ulonglong2 *>(a.pt + (size_t)lb.pt * N + p);
-    if (add) {
-      const ulonglong2 vc = *reinterpret_cast<const ulonglong2 *>(a.addend + (size_t)l0.add_src * N + sp);
-      U[0] += (hm_u128)vp.x * (swap ? vc.y : vc.x);
-      U[1] += (hm_u128)vp.y * (swap ? vc.x : vc.y);
-    }
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      hm_u128 s0 = 0, s1 = 0;
-#pragma unroll
-      for (int j = 0; j < TERMS; ++j) {
-        const uint64_t x0 = swap ? vx[j].y : vx[j].x, x1 = swap ? vx[j].x : vx[j].y;
-        s0 += (hm_u128)x0 * vy[k][j].x;
-        s1 += (hm_u128)x1 * vy[k][j].y;
-      }
-      // the same sums and reduction as k_inner_product_hoisted's: t_k is that kernel's output, bit for bit
-      S[k][0] += (hm_u128)vp.x * hm_barrett(s0, m);
-      S[k][1] += (hm_u128)vp.y * hm_barrett(s1, m);
-    }
-  }
-  // n_rot <= 16 products of two residues below q < 2^60: every accumulator stays below 2^124, inside 128 bits but beyond hm_barrett's
-  // z < 2^(k+63) (sums of up to 8 products), so the top word is folded first (hm_barrett_wide: f < 2^64 + 2q < 2^(k+63) for k > 20)
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const ulonglong2 o = {hm_barrett_wide(S[k][0], m), hm_barrett_wide(S[k][1], m)};
-    *reinterpret_cast<ulonglong2 *>(a.out + (size_t)l0.out[k] * N + p) = o;
-  }
-  if (add) {
-    const ulonglong2 o = {hm_barrett_wide(U[0], m), hm_barrett_wide(U[1], m)};
-    *reinterpret_cast<ulonglong2 *>(a.addend_out + (size_t)l0.add_out * N + p) = o;
-  }
-}
-
+// weighted sum of rotations: the hoisted form's records (every rotation's outputs are rotation 0's) with the plaintext and the addend on top
 extern "C" hm_status hm_inner_product_lintrans(hm_ctx *c, const hm_ip_lintrans_desc *d) {
   static const char *const what = "hm_inner_product_lintrans";
+  static const hm_ip_lintrans_desc none = {};
   if (!c) return HM_ERR_ARG;
-  if (!d || !d->x || !d->x_limbs || !d->y || !d->y_limbs || !d->pt || !d->pt_limbs || !d->out || !d->out_limbs || !d->mod_ids || !d->galois)
-    return fail(c, HM_ERR_ARG, "%s: null argument", what);
+  if (!d) d = &none;
   const bool anyAdd = d->addend_limbs != nullptr;
-  if (anyAdd && (!d->addend || !d->addend_out || !d->addend_out_limbs))
-    return fail(c, HM_ERR_ARG, "%s: null argument (addend, addend_limbs, addend_out and addend_out_limbs go together)", what);
+  const char *null = nullptr;
+  if (!d->x || !d->x_limbs || !d->y || !d->y_limbs || !d->pt || !d->pt_limbs || !d->out || !d->out_limbs || !d->mod_ids || !d->galois) null = "null argument";
+  else if (anyAdd && (!d->addend || !d->addend_out || !d->addend_out_limbs)) null = "null argument (addend, addend_limbs, addend_out and addend_out_limbs go together)";
   const uint32_t n = d->n, T = d->n_terms, R = d->n_rot, N = c->P.N;
-  if (T == 0 || T > HM_IP_MAX_TERMS || R == 0 || R > HM_IP_LINTRANS_MAX_ROT)
-    return fail(c, HM_ERR_ARG, "%s: n_terms in [1,%d], n_rot in [1,%d]", what, HM_IP_MAX_TERMS, HM_IP_LINTRANS_MAX_ROT);
-  for (uint32_t r = 0; r < R; ++r)
-    if (!(d->galois[r] & 1) || d->galois[r] >= 2 * N) return fail(c, HM_ERR_ARG, "%s: galois[%u] is not an odd number below 2N", what, r);
   std::vector<uint32_t> addSrc, addOut;   // the entries that carry an addend
-  for (uint32_t i = 0; anyAdd && i < n; ++i)
+  for (uint32_t i = 0; !null && anyAdd && i < n; ++i)
     if (d->addend_limbs[i] != HM_NO_LIMB) { addSrc.push_back(d->addend_limbs[i]); addOut.push_back(d->addend_out_limbs[i]); }
   const uint32_t nAdd = (uint32_t)addSrc.size();
   hm_status st;
-  if ((st = check_limbs(c, what, d->x_limbs, n * T)) || (st = check_limbs(c, what, d->y_limbs, R * n * 2 * T)) || (st = check_limbs(c, what, d->pt_limbs, R * n)) ||
-      (st = check_limbs(c, what, d->out_limbs, n * 2)) || (st = check_limbs(c, what, addSrc.data(), nAdd)) || (st = check_limbs(c, what, addOut.data(), nAdd)) ||
-      (st = check_mods(c, what, d->mod_ids, n)))
+  if ((st = ip_check(c, what, null, T, "n_rot", R, HM_IP_LINTRANS_MAX_ROT, d->galois,
+                     {{d->x_limbs, n * T}, {d->y_limbs, R * n * 2 * T}, {d->pt_limbs, R * n}, {d->out_limbs, n * 2}, {addSrc.data(), nAdd}, {addOut.data(), nAdd}},
+                     d->mod_ids, n)))
     return st;
   // a workgroup reads the digits and the addend at other positions than the ones it writes, and every rotation's keys and plaintext after the
   // first could be another workgroup's output: no output may overlap any input
@@ -1904,37 +1735,15 @@ extern "C" hm_status hm_inner_product_lintrans(hm_ctx *c, const hm_ip_lintrans_d
   }
   if (n == 0) return HM_OK;
   std::vector<HmIpLinRec> recs((size_t)R * n);
-  memset(recs.data(), 0, sizeof(HmIpLinRec) * recs.size());
-  for (uint32_t r = 0; r < R; ++r)
-    for (uint32_t i = 0; i < n; ++i) {
-      const size_t e = (size_t)r * n + i;
-      HmIpLinRec &l = recs[e];
-      l.mod = (uint16_t)d->mod_ids[i];
-      l.pt = (uint16_t)d->pt_limbs[e];
-      for (uint32_t j = 0; j < T; ++j) l.x[j] = (uint16_t)d->x_limbs[(size_t)i * T + j];
-      for (uint32_t k = 0; k < 2; ++k) {
-        l.out[k] = (uint16_t)d->out_limbs[(size_t)i * 2 + k];
-        for (uint32_t j = 0; j < T; ++j) l.y[k][j] = (uint16_t)d->y_limbs[(e * 2 + k) * T + j];
-      }
-      if (anyAdd && d->addend_limbs[i] != HM_NO_LIMB) {
-        l.has_add = 1; l.add_src = (uint16_t)d->addend_limbs[i]; l.add_out = (uint16_t)d->addend_out_limbs[i];
-      }
-    }
+  hm_ip_fill_recs(recs.data(), d->x_limbs, d->y_limbs, d->out_limbs, (size_t)n * 2, d->mod_ids, n, T, 2, R);
+  hm_ip_fill_lin(recs.data(), d->pt_limbs, d->addend_limbs, d->addend_out_limbs, n, R);
   HM_HIP(c, hipSetDevice(c->device));
-  const void *dtab = nullptr;
-  if ((st = device_table(c, recs.data(), sizeof(HmIpLinRec) * recs.size(), &dtab))) return st;
   HmIpLinArgs a;
+  if ((st = ip_device_recs(c, recs, &a.rec))) return st;
   a.x = d->x; a.y = d->y; a.pt = d->pt; a.addend = d->addend; a.out = d->out; a.addend_out = d->addend_out;
-  a.mods = c->d_mods; a.rec = static_cast<const HmIpLinRec *>(dtab);
-  a.logN = c->P.logN; a.n_limbs = n; a.n_rot = R;
+  a.mods = c->d_mods; a.logN = c->P.logN; a.n_limbs = n; a.n_rot = R;
   for (uint32_t r = 0; r < HM_IP_LINTRANS_MAX_ROT; ++r) a.galois[r] = r < R ? d->galois[r] : 1u;
-  const dim3 grid(n * (N / 512));
-  switch (T) {
-  case 1: hipLaunchKernelGGL(k_inner_product_lintrans<1>, grid, dim3(256), 0, c->stream, a); break;
-  case 2: hipLaunchKernelGGL(k_inner_product_lintrans<2>, grid, dim3(256), 0, c->stream, a); break;
-  case 3: hipLaunchKernelGGL(k_inner_product_lintrans<3>, grid, dim3(256), 0, c->stream, a); break;
-  case 4: hipLaunchKernelGGL(k_inner_product_lintrans<4>, grid, dim3(256), 0, c->stream, a); break;
-  }
+  launch_ip(c, k_ip_lintrans, a, T);
   HM_HIP(c, hipGetLastError());
   return HM_OK;
 }

@@ -1,0 +1,205 @@
+// hm_ip_core.h — K5, the inner product with the evaluation key, in its three forms: plain (hm_inner_product_ex), hoisted
+// (hm_inner_product_hoisted) and the weighted sum of rotations (hm_inner_product_lintrans).
+// Per-thread bodies (no cross-thread state) and the records they read, shared by the HIP kernels, the entry points and the host emulator.
+// A workgroup of 256 threads covers 512 coefficients of one entry: thread tid of chunk c owns the aligned pair at c * 512 + 2 * tid.
+//
+// Reference shape: the HPIP unit (InsGen::GenHPIP src/InsGen.cpp:356-406, HPIP src/Components.cpp:571-595; in the shipped configs it runs on
+// the EWE as beta-1 MAC groups per key, KeySwitch::InnerProduceOperation src/Operation.cpp:294-414).  One pass: acc_k = sum_j x_j * y_{j,k}.
+#pragma once
+#include "../../include/homulator_hip.h"   // HM_IP_HOISTED_MAX_ROT, HM_IP_LINTRANS_MAX_ROT
+#include "hm_modarith.h"
+#include "hm_ntt_core.h"
+
+#define HM_IP_MAX_TERMS 4
+#define HM_IP_MAX_OUT 2
+#define HM_IP_MAX_LIMBS 64
+#define HM_IP_CHUNK 512   // coefficients per workgroup
+
+// ---- records: the limbs of one entry's digits, keys and outputs, then what the form adds.  HmIpKeys is the prefix of all three.
+struct HmIpKeys {
+  uint16_t x[HM_IP_MAX_TERMS];
+  uint16_t y[HM_IP_MAX_OUT][HM_IP_MAX_TERMS];
+  uint16_t out[HM_IP_MAX_OUT];
+};
+struct HmIpLimb : HmIpKeys {
+  uint16_t mod, pad;
+};
+typedef HmIpLimb HmIpHoistRec;   // one per (rotation, entry), in a device table (16 rotations of 64 entries do not fit the kernel arguments)
+struct HmIpLinRec : HmIpKeys {   // one per (rotation, entry); the digits, the addend, the outputs and the modulus are read from rotation 0's
+  uint16_t pt, add_src, add_out;
+  uint16_t mod, has_add, pad;
+};
+static_assert(sizeof(HmIpKeys) == 28 && sizeof(HmIpHoistRec) == 32 && sizeof(HmIpLinRec) == 40, "the device tables' record sizes");
+
+struct HmIpArgs {
+  const uint64_t *x, *y;
+  uint64_t *out;
+  const HmMod *mods;
+  uint32_t logN, n_limbs, n_terms, n_out;
+  uint32_t x_galois;   // > 1: the x operands are read through the automorphism X -> X^x_galois (round 6, hm_inner_product_ex)
+  HmIpLimb limb[HM_IP_MAX_LIMBS];
+};
+struct HmIpHoistArgs {
+  const uint64_t *x, *y;
+  uint64_t *out;
+  const HmMod *mods;
+  const HmIpHoistRec *rec;   // [n_rot][n_limbs]
+  uint32_t logN, n_limbs, n_rot;
+  uint32_t dst_galois[HM_IP_HOISTED_MAX_ROT];   // g_r^-1 mod 2N: coefficient i of a digit lands at hm_auto_src(i, g_r^-1) of rotation r
+};
+struct HmIpLinArgs {
+  const uint64_t *x, *y, *pt, *addend;
+  uint64_t *out, *addend_out;
+  const HmMod *mods;
+  const HmIpLinRec *rec;   // [n_rot][n_limbs]
+  uint32_t logN, n_limbs, n_rot;
+  uint32_t galois[HM_IP_LINTRANS_MAX_ROT];
+};
+
+// The records of n entries x n_rot rotations, rec[r * n + i], from the entry points' limb lists: digits x [n][T], keys y [n_rot][n][K][T],
+// outputs out [n_outs / K][K] — every rotation its own (n_outs = n_rot * n * K) or all of them rotation 0's (n_outs = n * K).  Host side.
+template <class Rec>
+inline void hm_ip_fill_recs(Rec *rec, const uint32_t *x, const uint32_t *y, const uint32_t *out, size_t n_outs, const uint32_t *mod_ids, uint32_t n,
+                            uint32_t T, uint32_t K, uint32_t n_rot) {
+  for (size_t e = 0; e < (size_t)n_rot * n; ++e) {
+    const size_t i = e % n;
+    Rec l{};
+    l.mod = (uint16_t)mod_ids[i];
+    for (uint32_t j = 0; j < T; ++j) l.x[j] = (uint16_t)x[i * T + j];
+    for (uint32_t k = 0; k < K; ++k) {
+      l.out[k] = (uint16_t)out[(e * K + k) % n_outs];
+      for (uint32_t j = 0; j < T; ++j) l.y[k][j] = (uint16_t)y[(e * K + k) * T + j];
+    }
+    rec[e] = l;
+  }
+}
+// ... and what the weighted sum adds: plaintexts pt [n_rot][n]; addend sources / outputs [n], or nullptr (none), HM_NO_LIMB: not this entry
+inline void hm_ip_fill_lin(HmIpLinRec *rec, const uint32_t *pt, const uint32_t *addend, const uint32_t *addend_out, uint32_t n, uint32_t n_rot) {
+  for (size_t e = 0; e < (size_t)n_rot * n; ++e) {
+    const size_t i = e % n;
+    rec[e].pt = (uint16_t)pt[e];
+    if (addend && addend[i] != HM_NO_LIMB) { rec[e].has_add = 1; rec[e].add_src = (uint16_t)addend[i]; rec[e].add_out = (uint16_t)addend_out[i]; }
+  }
+}
+
+// ---- per-thread pieces
+struct HmIpPair { uint64_t x, y; };   // an aligned pair of coefficients: one 16-byte access
+HM_HD HmIpPair hm_ip_ld(const uint64_t *base, uint32_t limb, uint32_t N, uint32_t off) {
+  HmIpPair v;
+  hm_ld2(base + (size_t)limb * N + off, v.x, v.y);
+  return v;
+}
+HM_HD void hm_ip_st(uint64_t *base, uint32_t limb, uint32_t N, uint32_t off, const HmIpPair &v) { hm_st2(base + (size_t)limb * N + off, v.x, v.y); }
+
+// sum_j x_j * y_j mod q for both words of a pair, the digit words taken in the other order when `swap` (hm_auto_pair): the ONE place the three
+// forms multiply and reduce.  TERMS <= 4 products below 2^120: within hm_barrett's 2^(k+63)
+template <int TERMS>
+HM_HD HmIpPair hm_ip_dot(const HmIpPair *vx, const HmIpPair *vy, bool swap, const HmMod &m) {
+  hm_u128 s0 = 0, s1 = 0;
+#pragma unroll
+  for (int j = 0; j < TERMS; ++j) {
+    const uint64_t x0 = swap ? vx[j].y : vx[j].x, x1 = swap ? vx[j].x : vx[j].y;
+    s0 += (hm_u128)x0 * vy[j].x;
+    s1 += (hm_u128)x1 * vy[j].y;
+  }
+  return HmIpPair{hm_barrett(s0, m), hm_barrett(s1, m)};
+}
+
+// plain: out_k = sum_j x_j y_kj at the thread's pair; x through an automorphism when x_galois > 1 (wave-uniform choice)
+template <int TERMS, int OUTS>
+HM_HD void hm_ip_thread(const HmIpArgs &a, uint32_t entry, uint32_t chunk, uint32_t tid) {
+  const uint32_t N = 1u << a.logN;
+  const HmIpLimb &lb = a.limb[entry];
+  const HmMod m = a.mods[lb.mod];
+  const uint32_t off = chunk * HM_IP_CHUNK + 2 * tid;
+  uint32_t offx = off;
+  bool swap = false;
+  if (a.x_galois > 1) offx = hm_auto_pair(off, a.x_galois, a.logN, swap);
+  HmIpPair vx[TERMS], vy[OUTS][TERMS];
+#pragma unroll
+  for (int j = 0; j < TERMS; ++j) {
+    vx[j] = hm_ip_ld(a.x, lb.x[j], N, offx);
+#pragma unroll
+    for (int k = 0; k < OUTS; ++k) vy[k][j] = hm_ip_ld(a.y, lb.y[k][j], N, off);
+  }
+#pragma unroll
+  for (int k = 0; k < OUTS; ++k) {
+    const HmIpPair o = hm_ip_dot<TERMS>(vx, vy[k], swap, m);
+    hm_ip_st(a.out, lb.out[k], N, off, o);
+  }
+}
+
+// hoisted, the SCATTER form: the key products of n_rot rotations of ONE ciphertext from its unrotated digits.  sigma_g takes the aligned pair
+// (off, off + 1) of a digit to the aligned pair at hm_auto_src(off, g^-1 mod 2N), in order or swapped: a thread loads its pair of every digit
+// ONCE and, rotation by rotation, gathers the two keys and stores the two sums at that destination.
+template <int TERMS>
+HM_HD void hm_ip_hoisted_thread(const HmIpHoistArgs &a, uint32_t entry, uint32_t chunk, uint32_t tid) {
+  const uint32_t N = 1u << a.logN;
+  const HmIpHoistRec &l0 = a.rec[entry];
+  const HmMod m = a.mods[l0.mod];
+  const uint32_t off = chunk * HM_IP_CHUNK + 2 * tid;
+  HmIpPair vx[TERMS];
+#pragma unroll
+  for (int j = 0; j < TERMS; ++j) vx[j] = hm_ip_ld(a.x, l0.x[j], N, off);
+#pragma unroll 1
+  for (uint32_t r = 0; r < a.n_rot; ++r) {
+    const HmIpHoistRec &lb = a.rec[(size_t)r * a.n_limbs + entry];
+    bool swap;
+    const uint32_t p = hm_auto_pair(off, a.dst_galois[r], a.logN, swap);
+    HmIpPair vy[2][TERMS];
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+#pragma unroll
+      for (int j = 0; j < TERMS; ++j) vy[k][j] = hm_ip_ld(a.y, lb.y[k][j], N, p);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const HmIpPair o = hm_ip_dot<TERMS>(vx, vy[k], swap, m);   // before lb.out[k] is read: two VGPRs fewer at TERMS = 3
+      hm_ip_st(a.out, lb.out[k], N, p, o);
+    }
+  }
+}
+
+// weighted sum of rotations, sum_r pt_r * (the hoisted key product of rotation r), formed before anything is stored.  The sum over the
+// rotations needs a fixed destination, so this is the GATHER form: a thread owns the aligned pair p of the outputs; rotation by rotation it
+// loads every digit's pair at the automorphism's source of p, both keys and the plaintext at p, and adds pt * (the hoisted form's output) to a
+// 128-bit accumulator per key and word.  Entries with an addend source (the Q limbs: c0) gather it at the same source and accumulate pt * c0
+// as a third output.
+template <int TERMS>
+HM_HD void hm_ip_lintrans_thread(const HmIpLinArgs &a, uint32_t entry, uint32_t chunk, uint32_t tid) {
+  const uint32_t N = 1u << a.logN;
+  const HmIpLinRec &l0 = a.rec[entry];
+  const HmMod m = a.mods[l0.mod];
+  const bool add = l0.has_add != 0;   // workgroup-uniform
+  const uint32_t p = chunk * HM_IP_CHUNK + 2 * tid;
+  hm_u128 S[2][2] = {{0, 0}, {0, 0}}, U[2] = {0, 0};
+#pragma unroll 1
+  for (uint32_t r = 0; r < a.n_rot; ++r) {
+    const HmIpLinRec &lb = a.rec[(size_t)r * a.n_limbs + entry];
+    bool swap;
+    const uint32_t sp = hm_auto_pair(p, a.galois[r], a.logN, swap);
+    HmIpPair vx[TERMS], vy[2][TERMS];
+#pragma unroll
+    for (int j = 0; j < TERMS; ++j) vx[j] = hm_ip_ld(a.x, l0.x[j], N, sp);
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+#pragma unroll
+      for (int j = 0; j < TERMS; ++j) vy[k][j] = hm_ip_ld(a.y, lb.y[k][j], N, p);
+    const HmIpPair vp = hm_ip_ld(a.pt, lb.pt, N, p);
+    if (add) {
+      const HmIpPair vc = hm_ip_ld(a.addend, l0.add_src, N, sp);
+      U[0] += (hm_u128)vp.x * (swap ? vc.y : vc.x);
+      U[1] += (hm_u128)vp.y * (swap ? vc.x : vc.y);
+    }
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const HmIpPair t = hm_ip_dot<TERMS>(vx, vy[k], swap, m);
+      S[k][0] += (hm_u128)vp.x * t.x;
+      S[k][1] += (hm_u128)vp.y * t.y;
+    }
+  }
+  // n_rot <= 16 products of two residues below q < 2^60: every accumulator stays below 2^124, inside 128 bits but beyond hm_barrett's
+  // z < 2^(k+63) (sums of up to 8 products), so the top word is folded first (hm_barrett_wide: f < 2^64 + 2q < 2^(k+63) for k > 20)
+#pragma unroll
+  for (int k = 0; k < 2; ++k) hm_ip_st(a.out, l0.out[k], N, p, HmIpPair{hm_barrett_wide(S[k][0], m), hm_barrett_wide(S[k][1], m)});
+  if (add) hm_ip_st(a.addend_out, l0.add_out, N, p, HmIpPair{hm_barrett_wide(U[0], m), hm_barrett_wide(U[1], m)});
+}

@@ -141,11 +141,24 @@ HM_HD uint32_t hm_auto_src(uint32_t i, uint32_t g, uint32_t logN) {
   uint32_t e = (g * (2 * hm_brev(i, logN) + 1)) & mask;
   return hm_brev((e - 1) >> 1, logN);
 }
+// g^-1 mod 2N (g odd: g g = 1 mod 8, and each Newton step doubles the correct low bits): out[hm_auto_src(i, g^-1)] = in[i] is the same map, scattered
+HM_HD uint32_t hm_auto_inv(uint32_t g, uint32_t logN) {
+  uint32_t v = g;
+  for (int it = 0; it < 5; ++it) v *= 2u - g * v;
+  return v & ((2u << logN) - 1);
+}
 // The map is affine in the natural index and both sides are stored bit-reversed, so every aligned block of 2^k outputs comes from ONE aligned
 // block of 2^k inputs, for every k: a 4096-coefficient tile from one tile, a 16-byte access unit (outputs 2m, 2m + 1) from one aligned pair
 // of inputs — in order, or swapped (hm_auto_src(2m + 1) = hm_auto_src(2m) ^ 1).  A transform can therefore read its input (MODE 6), or its
 // epilogue's addend (MODE 7), THROUGH the automorphism with the same 16-byte loads it uses anyway: hrotate's automorphism launch
 // (InsGen::GenAUTO, src/InsGen.cpp:46-71) folds into the ModUp INTT and the final add (round 6).
+
+// the aligned pair that holds the sources of the pair (i, i + 1), i even; swap: it arrives in the other order
+HM_HD uint32_t hm_auto_pair(uint32_t i, uint32_t g, uint32_t logN, bool &swap) {
+  const uint32_t s = hm_auto_src(i, g, logN);
+  swap = s & 1u;
+  return s & ~1u;
+}
 
 // 16-byte accesses (two adjacent words; p is 16-byte aligned)
 HM_HD void hm_ld2(const uint64_t *p, uint64_t &a, uint64_t &b) {
@@ -225,16 +238,16 @@ HM_HD void hm_gst2(uint64_t *g, uint32_t tile, int tid, int a, uint64_t v0, uint
 // the aligned pair that holds both sources, the words swapped when the pair arrives in the other order (hm_auto_src above)
 template <int AUX = 0>
 HM_HD void hm_gld2_auto(const uint64_t *g, uint32_t i, uint32_t galois, uint32_t logN, uint64_t &v0, uint64_t &v1) {
-  const uint32_t s = hm_auto_src(i, galois, logN);
+  bool swap;
+  const uint32_t s = hm_auto_pair(i, galois, logN, swap);
   uint64_t a, b;
 #if defined(__HIP_DEVICE_COMPILE__)
-  const hm_u32x4 t = __builtin_amdgcn_raw_buffer_load_b128(hm_rsrc(g), (int)((s & ~1u) << 3), 0, AUX);
+  const hm_u32x4 t = __builtin_amdgcn_raw_buffer_load_b128(hm_rsrc(g), (int)(s << 3), 0, AUX);
   a = (uint64_t)t.x | ((uint64_t)t.y << 32);
   b = (uint64_t)t.z | ((uint64_t)t.w << 32);
 #else
-  hm_ld2(g + (s & ~1u), a, b);
+  hm_ld2(g + s, a, b);
 #endif
-  const bool swap = s & 1u;
   v0 = swap ? b : a;
   v1 = swap ? a : b;
 }

@@ -371,6 +371,22 @@ struct Arch::LaunchBuilder {
     if (evalDigit) { L.xGalois = i->ipXGalois; xGaloisSet = true; }
   }
   bool xGaloisSet = false;   // ... of the launch being built
+  // what the two key products over the rotations of one launch share (the records must agree on the rotations): digits a [n][T], moduli, keys
+  // b [r][n][2][T].  Returns the number of rotations
+  size_t hoistedOperands(Launch &L, Recs recs, const char *what) {
+    L.statKey = "EWE";
+    L.ipTerms = (uint32_t)recs[0]->ipX.size(); L.ipOuts = 2; L.hoistG = recs[0]->ipHoistG;
+    for (Instruction *i : recs) {
+      if (i->ipHoistG != L.hoistG) throw std::runtime_error(std::string(what) + ": the records of one launch rotate by different elements");
+      for (AddrType x : i->ipX) L.a.push_back(limb(x));
+      L.mods.push_back(i->mod_id);
+    }
+    for (size_t r = 0; r < L.hoistG.size(); ++r)
+      for (Instruction *i : recs)
+        for (size_t k = 0; k < 2; ++k)
+          for (AddrType y : i->ipY[r * 2 + k]) L.b.push_back(limb(y));
+    return L.hoistG.size();
+  }
 
   void emitGroup(Group group);
   void shardedTransformTimesKey(const Group &group);
@@ -394,21 +410,11 @@ struct Arch::LaunchBuilder {
 
 // (6h) one hoisted key product: digits a [n][T], keys b [r][n][2][T], outputs out [r][n][2] (hm_ip_hoisted_desc)
 void Arch::LaunchBuilder::ipHoisted(Launch &L, Recs recs) {
-  Instruction *f = recs[0];
-  L.kind = Launch::L_IP_HOISTED; L.statKey = "EWE";
-  L.ipTerms = (uint32_t)f->ipX.size(); L.ipOuts = 2; L.hoistG = f->ipHoistG;
-  const size_t R = f->ipHoistG.size();
-  for (Instruction *i : recs) {
-    if (i->ipHoistG != f->ipHoistG) throw std::runtime_error("hoisted key product: the records of one launch rotate by different elements");
-    for (AddrType x : i->ipX) L.a.push_back(limb(x));
-    L.mods.push_back(i->mod_id);
-  }
+  L.kind = Launch::L_IP_HOISTED;
+  const size_t R = hoistedOperands(L, recs, "hoisted key product");
   for (size_t r = 0; r < R; ++r)
     for (Instruction *i : recs)
-      for (size_t k = 0; k < 2; ++k) {
-        for (AddrType y : i->ipY[r * 2 + k]) L.b.push_back(limb(y));
-        L.out.push_back(limb(r == 0 && k == 0 ? i->OutputOperand : i->extraOutputs[r * 2 + k - 1]));
-      }
+      for (size_t k = 0; k < 2; ++k) L.out.push_back(limb(r == 0 && k == 0 ? i->OutputOperand : i->extraOutputs[r * 2 + k - 1]));
   // digits read once, keys read and outputs written once per rotation
   L.bytes = (unsigned long long)recs.size() * (L.ipTerms + 2 * R * L.ipTerms + 2 * R) * LP;
 }
@@ -416,16 +422,11 @@ void Arch::LaunchBuilder::ipHoisted(Launch &L, Recs recs) {
 // (6l) one weighted sum of hoisted key products: the hoisted launch's digits and keys, plaintexts c [r][n], outputs out [n][2]; entries with an
 // addend: source d [n], output out1 [n] (hm_ip_lintrans_desc)
 void Arch::LaunchBuilder::ipLintrans(Launch &L, Recs recs) {
-  Instruction *f = recs[0];
-  L.kind = Launch::L_IP_LINTRANS; L.statKey = "EWE";
-  L.ipTerms = (uint32_t)f->ipX.size(); L.ipOuts = 2; L.hoistG = f->ipHoistG;
-  const size_t R = f->ipHoistG.size();
+  L.kind = Launch::L_IP_LINTRANS;
+  const size_t R = hoistedOperands(L, recs, "weighted rotations");
   size_t addends = 0;
   for (Instruction *i : recs) addends += i->ipLinAddend != 0;
   for (Instruction *i : recs) {
-    if (i->ipHoistG != f->ipHoistG) throw std::runtime_error("weighted rotations: the records of one launch rotate by different elements");
-    for (AddrType x : i->ipX) L.a.push_back(limb(x));
-    L.mods.push_back(i->mod_id);
     L.out.push_back(limb(i->OutputOperand)); L.out.push_back(limb(i->extraOutputs[0]));
     if (addends) {
       L.d.push_back(i->ipLinAddend ? limb(i->ipLinAddend) : HM_NO_LIMB);
@@ -433,11 +434,7 @@ void Arch::LaunchBuilder::ipLintrans(Launch &L, Recs recs) {
     }
   }
   for (size_t r = 0; r < R; ++r)
-    for (Instruction *i : recs) {
-      for (size_t k = 0; k < 2; ++k)
-        for (AddrType y : i->ipY[r * 2 + k]) L.b.push_back(limb(y));
-      L.c.push_back(limb(i->ipLinPt[r]));
-    }
+    for (Instruction *i : recs) L.c.push_back(limb(i->ipLinPt[r]));
   // limb-polys touched: the digits and the addend source once (every rotation gathers from the same ones), keys and plaintext once per rotation,
   // two outputs per entry and one per addend
   L.bytes = ((unsigned long long)recs.size() * (L.ipTerms + 2 * R * L.ipTerms + R + 2) + (unsigned long long)addends * 2) * LP;
@@ -1171,13 +1168,11 @@ void Arch::enqueue(Launch &l) {
                             l.out.data(), l.mods.data(), cnt, l.k.data());
     }
     break;
-  case Launch::L_IP:
-    if (l.xGalois) {
-      const hm_ip_desc d = {pool, l.a.data(), pool, l.b.data(), pool, l.out.data(), l.mods.data(), (uint32_t)l.mods.size(), l.ipTerms, l.ipOuts, l.xGalois};
-      st = hm_inner_product_ex(ctx, &d);
-    } else
-    st = hm_inner_product(ctx, pool, l.a.data(), pool, l.b.data(), pool, l.out.data(), l.mods.data(), (uint32_t)l.mods.size(), l.ipTerms, l.ipOuts);
+  case Launch::L_IP: {
+    const hm_ip_desc d = {pool, l.a.data(), pool, l.b.data(), pool, l.out.data(), l.mods.data(), (uint32_t)l.mods.size(), l.ipTerms, l.ipOuts, l.xGalois};
+    st = hm_inner_product_ex(ctx, &d);
     break;
+  }
   case Launch::L_IP_HOISTED: {
     const hm_ip_hoisted_desc d = {pool, l.a.data(), pool, l.b.data(), pool, l.out.data(), l.mods.data(), (uint32_t)l.mods.size(), l.ipTerms,
                                   (uint32_t)l.hoistG.size(), l.hoistG.data()};

@@ -10,6 +10,7 @@
 #include <stdexcept>
 #include <vector>
 #include "../../homulator_amd/csrc/hm_elem_core.h"
+#include "../../homulator_amd/csrc/hm_ip_core.h"
 #include "../../homulator_amd/csrc/hm_modarith.h"
 #include "../../homulator_amd/csrc/hm_ntt_core.h"
 #include "../../homulator_amd/csrc/hm_params.h"
@@ -144,6 +145,16 @@ static void run_intt_auto(const Emu &e, uint32_t mod, const uint64_t *in, uint64
   run_pass<G, HM_ROW_LOG, false, true, 6>(e, mod, in, out, sc, ep);
   run_pass<G, LOG1, true, true, 2>(e, mod, out, out, sc);
 }
+// K5 (hm_ip_core.h): a form's per-thread function over every (entry, chunk, thread) of its launch, in that order.  No thread reads what another
+// writes (the entry points refuse such calls), so the order is free
+template <class Args, class Thread>
+static void run_ip(const Args &a, Thread thread) {
+  for (uint32_t entry = 0; entry < a.n_limbs; ++entry)
+    for (uint32_t chunk = 0; chunk < (1u << a.logN) / HM_IP_CHUNK; ++chunk)
+      for (uint32_t tid = 0; tid < HM_IP_CHUNK / 2; ++tid) thread(a, entry, chunk, tid);
+}
+static bool ip_counts_ok(uint32_t T, uint32_t v, uint32_t vmax) { return T >= 1 && T <= HM_IP_MAX_TERMS && v >= 1 && v <= vmax; }
+
 extern "C" {
 // q == nullptr: the default chain; otherwise a caller-chosen one (q: L moduli, p: K special moduli; primes = 1 mod 2N below 2^60).
 // Returns nullptr if the chain does not fit this build's arithmetic.
@@ -395,6 +406,59 @@ void emu_bfly(void *h, uint32_t mod, int kind, uint64_t *X, uint64_t *Y, uint64_
   else if (kind == 2) hm_bfly_fwd_k<2>(*X, *Y, wt, m);
   else hm_bfly_inv(*X, *Y, wt, m);
 }
+// ---- K5 in its three forms on host arrays of limb-polys, arguments as the entry points' (include/homulator_hip.h); the records come from the
+// back-end's own builder (hm_ip_fill_recs).  Returns 1 for counts outside the kernels' range
+int emu_ip(void *h, const uint64_t *x, const uint32_t *xl, const uint64_t *y, const uint32_t *yl, uint64_t *out, const uint32_t *ol, const uint32_t *mod_ids,
+           uint32_t n, uint32_t T, uint32_t K, uint32_t x_galois) {
+  Emu &e = *(Emu *)h;
+  if (!ip_counts_ok(T, K, HM_IP_MAX_OUT) || n > HM_IP_MAX_LIMBS) return 1;
+  HmIpArgs a;
+  a.x = x; a.y = y; a.out = out; a.mods = e.P.modc.data(); a.logN = e.P.logN; a.n_limbs = n; a.n_terms = T; a.n_out = K; a.x_galois = x_galois;
+  hm_ip_fill_recs(a.limb, xl, yl, ol, (size_t)n * K, mod_ids, n, T, K, 1);
+  switch (T * 10 + K) {
+#define HM_CASE(t) case t * 10 + 1: run_ip(a, hm_ip_thread<t, 1>); break; case t * 10 + 2: run_ip(a, hm_ip_thread<t, 2>); break;
+    HM_CASE(1) HM_CASE(2) HM_CASE(3) HM_CASE(4)
+#undef HM_CASE
+  }
+  return 0;
+}
+int emu_ip_hoisted(void *h, const uint64_t *x, const uint32_t *xl, const uint64_t *y, const uint32_t *yl, uint64_t *out, const uint32_t *ol,
+                   const uint32_t *mod_ids, uint32_t n, uint32_t T, uint32_t R, const uint32_t *galois) {
+  Emu &e = *(Emu *)h;
+  if (!ip_counts_ok(T, R, HM_IP_HOISTED_MAX_ROT)) return 1;
+  std::vector<HmIpHoistRec> recs((size_t)R * n);
+  hm_ip_fill_recs(recs.data(), xl, yl, ol, (size_t)R * n * 2, mod_ids, n, T, 2, R);
+  HmIpHoistArgs a;
+  a.x = x; a.y = y; a.out = out; a.mods = e.P.modc.data(); a.rec = recs.data(); a.logN = e.P.logN; a.n_limbs = n; a.n_rot = R;
+  for (uint32_t r = 0; r < HM_IP_HOISTED_MAX_ROT; ++r) a.dst_galois[r] = hm_auto_inv(r < R ? galois[r] : 1u, a.logN);
+  switch (T) {
+#define HM_CASE(t) case t: run_ip(a, hm_ip_hoisted_thread<t>); break;
+    HM_CASE(1) HM_CASE(2) HM_CASE(3) HM_CASE(4)
+#undef HM_CASE
+  }
+  return 0;
+}
+// al == NULL: no entry has an addend
+int emu_ip_lintrans(void *h, const uint64_t *x, const uint32_t *xl, const uint64_t *y, const uint32_t *yl, const uint64_t *pt, const uint32_t *pl,
+                    const uint64_t *addend, const uint32_t *al, uint64_t *out, const uint32_t *ol, uint64_t *addend_out, const uint32_t *aol,
+                    const uint32_t *mod_ids, uint32_t n, uint32_t T, uint32_t R, const uint32_t *galois) {
+  Emu &e = *(Emu *)h;
+  if (!ip_counts_ok(T, R, HM_IP_LINTRANS_MAX_ROT)) return 1;
+  std::vector<HmIpLinRec> recs((size_t)R * n);
+  hm_ip_fill_recs(recs.data(), xl, yl, ol, (size_t)n * 2, mod_ids, n, T, 2, R);
+  hm_ip_fill_lin(recs.data(), pl, al, aol, n, R);
+  HmIpLinArgs a;
+  a.x = x; a.y = y; a.pt = pt; a.addend = addend; a.out = out; a.addend_out = addend_out;
+  a.mods = e.P.modc.data(); a.rec = recs.data(); a.logN = e.P.logN; a.n_limbs = n; a.n_rot = R;
+  for (uint32_t r = 0; r < HM_IP_LINTRANS_MAX_ROT; ++r) a.galois[r] = r < R ? galois[r] : 1u;
+  switch (T) {
+#define HM_CASE(t) case t: run_ip(a, hm_ip_lintrans_thread<t>); break;
+    HM_CASE(1) HM_CASE(2) HM_CASE(3) HM_CASE(4)
+#undef HM_CASE
+  }
+  return 0;
+}
+uint32_t emu_auto_inv(uint32_t g, uint32_t logN) { return hm_auto_inv(g, logN); }
 // ---- the back-end's launch layouts (hm_launch.h) as its entry points compute them.  policy 0: a transform (ntt_common; one_launch = the call runs
 // as ONE launch), 1: the last pass x key product (hm_ntt_inner_product; weight = per limb-poly cost for its heaviest-first order, or NULL).
 // Writes logG, per limb-poly its launch and slot, per launch its entry count (up to max_launch); returns the number of launches

@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from lintrans_ref import weighted_sum
 from oracle.homoracle import Oracle
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -43,6 +44,11 @@ def _load(name):
     L.emu_redc_wide.restype = C.c_uint64
     L.emu_redc_wide.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int]
     L.emu_bfly.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64]
+    L.emu_ip.argtypes = [C.c_void_p] * 8 + [C.c_uint32] * 4
+    L.emu_ip_hoisted.argtypes = [C.c_void_p] * 8 + [C.c_uint32] * 3 + [C.c_void_p]
+    L.emu_ip_lintrans.argtypes = [C.c_void_p] * 14 + [C.c_uint32] * 3 + [C.c_void_p]
+    L.emu_auto_inv.restype = C.c_uint32
+    L.emu_auto_inv.argtypes = [C.c_uint32, C.c_uint32]
     return L
 
 
@@ -567,3 +573,152 @@ def test_emu_transforms_that_read_through_an_automorphism(emu, logN, ept):
                 assert np.array_equal(out, o.ewe(3, [m], base, None, o.ewe(5, [m], o.automorph_eval(ad[None], g), k=[ak]))[0]), (m, g)
     finally:
         emu.emu_destroy(h)
+
+
+# ---- K5, the key product in its three forms (hm_ip_core.h): the kernels' per-thread functions over every (entry, chunk, thread) on records from the
+# back-end's own builder, against the oracle's automorphism and EWE_MUL / EWE_MAC_ADD chains (lintrans_ref.weighted_sum) as the GPU tests check the
+# kernels.  N = 2^13 (16 chunks per entry), 6 + 3 moduli, 5 entries of which two share a modulus, every limb list a random permutation of its
+# buffer, one guard limb-poly per output buffer.
+IP_MODS = [0, 8, 3, 8, 5]
+IP_GUARD = 0x5A5A5A5A5A5A5A5A
+NO_LIMB = 0xFFFFFFFF
+
+
+@pytest.fixture(scope="module")
+def ip_env(emu):
+    o = emu.oracle(13, 6, 3)
+    mods = np.array(o.moduli, dtype=np.uint64)
+    h = emu.emu_create_mods(o.logN, o.L, o.K, p(mods[:o.L]), p(mods[o.L:]))
+    assert h, "the emulator refused the chain"
+    yield emu, o, h
+    emu.emu_destroy(h)
+
+
+def ip_elements(R, twoN=2 << 13):
+    """test_gpu_lintrans.elements"""
+    return {1: [3], 3: [5, twoN - 1, twoN - 3]}.get(R) or [pow(5, r, twoN) for r in range(1, R + 1)]
+
+
+def u32(v):
+    return np.array(v, dtype=np.uint32)
+
+
+def ip_polys(o, count, limb_mod, seed, worst=False):
+    """[count][N]: limb-poly k reduced modulo limb_mod[k] (a limb no entry names: modulus 0), the edge values first; worst: q - 1 everywhere"""
+    ids = [limb_mod.get(k, 0) for k in range(count)]
+    if worst:
+        return np.stack([np.full(o.N, o.moduli[m] - 1, dtype=np.uint64) for m in ids])
+    v = o.fill_uniform(ids, seed)
+    for k, m in enumerate(ids):
+        v[k, :3] = [o.moduli[m] - 1, 0, o.moduli[m] - 1]
+    return v
+
+
+def ip_operands(o, rng, T, K, R, seed, share=False, worst=False):
+    """digits X [n T] with list xl [n][T] and keys Y [R n K T] with list yl [R][n][K][T]; share: entries 1 and 3 (one modulus) read the same digits"""
+    n = len(IP_MODS)
+    xl, yl = ([int(v) for v in rng.permutation(k)] for k in (n * T, R * n * K * T))
+    if share:
+        xl[3 * T:4 * T] = xl[T:2 * T]
+    xm = {xl[i * T + j]: IP_MODS[i] for i in range(n) for j in range(T)}
+    ym = {yl[e]: IP_MODS[e // (K * T) % n] for e in range(len(yl))}
+    return ip_polys(o, n * T, xm, seed, worst), xl, ip_polys(o, len(yl), ym, seed + 1, worst), yl
+
+
+def ip_key_products(o, X, xl, Y, yl, T, K, rot, g):
+    """[K][n][N]: sum_j sigma_g(x_j) y_kj with rotation `rot`'s keys — the automorphism of every digit (g > 1), then a MUL and MAC_ADDs"""
+    n = len(IP_MODS)
+    rx = [np.stack([X[xl[i * T + j]] for i in range(n)]) for j in range(T)]
+    if g > 1:
+        rx = [o.automorph_eval(v, g) for v in rx]
+    key = lambda k, j: np.stack([Y[yl[((rot * n + i) * K + k) * T + j]] for i in range(n)])
+    return [weighted_sum(o, IP_MODS, rx, [key(k, j) for j in range(T)]) for k in range(K)]
+
+
+@pytest.mark.parametrize("outs", [1, 2])
+@pytest.mark.parametrize("T", [1, 2, 3, 4])
+def test_emu_key_product_plain(ip_env, T, outs):
+    """hm_ip_thread<T, outs>: as stored (x_galois = 0) and through X -> X^5 and the conjugation X -> X^(2N - 1)"""
+    emu, o, h = ip_env
+    n = len(IP_MODS)
+    rng = np.random.default_rng(10 * T + outs)
+    X, xl, Y, yl = ip_operands(o, rng, T, outs, 1, 100 * T + outs)
+    operm = [int(v) for v in rng.permutation(n * outs + 1)]
+    ol = operm[:n * outs]
+    axl, ayl, aol, amods = u32(xl), u32(yl), u32(ol), u32(IP_MODS)
+    for g in (0, 5, 2 * o.N - 1):
+        out = np.full((n * outs + 1, o.N), IP_GUARD, dtype=np.uint64)
+        assert emu.emu_ip(h, p(X), p(axl), p(Y), p(ayl), p(out), p(aol), p(amods), n, T, outs, g) == 0
+        exp = ip_key_products(o, X, xl, Y, yl, T, outs, 0, g)
+        for k in range(outs):
+            assert np.array_equal(out[[ol[i * outs + k] for i in range(n)]], exp[k]), (T, outs, g, k)
+        assert np.all(out[operm[-1]] == IP_GUARD), "the guard limb-poly was written"
+
+
+@pytest.mark.parametrize("T,R,share", [(1, 1, False), (1, 3, False), (1, 16, False), (4, 1, False), (4, 3, False), (4, 16, False), (4, 3, True)])
+def test_emu_key_product_hoisted(ip_env, T, R, share):
+    """hm_ip_hoisted_thread<T>, the scatter through g^-1: rotation r's outputs are the key products of the digits rotated by g_r"""
+    emu, o, h = ip_env
+    n = len(IP_MODS)
+    galois = ip_elements(R)
+    assert all(g * emu.emu_auto_inv(g, 13) % (2 << 13) == 1 for g in galois)
+    rng = np.random.default_rng(100 * T + R + share)
+    X, xl, Y, yl = ip_operands(o, rng, T, 2, R, 1000 * T + R, share=share)
+    operm = [int(v) for v in rng.permutation(R * n * 2 + 1)]
+    ol = operm[:R * n * 2]
+    out = np.full((R * n * 2 + 1, o.N), IP_GUARD, dtype=np.uint64)
+    axl, ayl, aol, amods, ag = u32(xl), u32(yl), u32(ol), u32(IP_MODS), u32(galois)
+    assert emu.emu_ip_hoisted(h, p(X), p(axl), p(Y), p(ayl), p(out), p(aol), p(amods), n, T, R, p(ag)) == 0
+    for r, g in enumerate(galois):
+        exp = ip_key_products(o, X, xl, Y, yl, T, 2, r, g)
+        for k in range(2):
+            assert np.array_equal(out[[ol[(r * n + i) * 2 + k] for i in range(n)]], exp[k]), (T, R, r, k)
+    assert np.all(out[operm[-1]] == IP_GUARD), "the guard limb-poly was written"
+
+
+def run_emu_lintrans(emu, o, h, T, R, add_mask, seed, worst=False):
+    """one weighted sum of rotations as test_gpu_lintrans.run_kernel_case runs hm_inner_product_lintrans: add_mask[i]: entry i carries an addend"""
+    n, N = len(IP_MODS), o.N
+    galois = ip_elements(R)
+    rng = np.random.default_rng(seed)
+    X, xl, Y, yl = ip_operands(o, rng, T, 2, R, seed * 11, worst=worst)
+    adds = [i for i in range(n) if add_mask[i]]
+    npt, nc, no, na = R * n, max(1, len(adds)), 2 * n + 1, len(adds) + 1
+    pl, cperm, operm, aperm = ([int(v) for v in rng.permutation(k)] for k in (npt, nc, no, na))
+    ol = operm[:2 * n]
+    cl, al = [NO_LIMB] * n, [NO_LIMB] * n
+    for t, i in enumerate(adds):
+        cl[i], al[i] = cperm[t], aperm[t]
+    P = ip_polys(o, npt, {pl[r * n + i]: IP_MODS[i] for r in range(R) for i in range(n)}, seed * 11 + 2, worst)
+    Cs = ip_polys(o, nc, {cl[i]: IP_MODS[i] for i in adds}, seed * 11 + 3, worst)
+    got = np.full((no, N), IP_GUARD, dtype=np.uint64)
+    gotA = np.full((na, N), IP_GUARD, dtype=np.uint64)
+    axl, ayl, apl, acl, aol, aal, amods, ag = (u32(v) for v in (xl, yl, pl, cl, ol, al, IP_MODS, galois))
+    assert emu.emu_ip_lintrans(h, p(X), p(axl), p(Y), p(ayl), p(P), p(apl), p(Cs) if adds else None, p(acl) if adds else None, p(got), p(aol),
+                               p(gotA) if adds else None, p(aal) if adds else None, p(amods), n, T, R, p(ag)) == 0
+    terms = [ip_key_products(o, X, xl, Y, yl, T, 2, r, g) for r, g in enumerate(galois)]
+    pts = [np.stack([P[pl[r * n + i]] for i in range(n)]) for r in range(R)]
+    for k in range(2):
+        exp = weighted_sum(o, IP_MODS, [t[k] for t in terms], pts)
+        assert np.array_equal(got[[ol[i * 2 + k] for i in range(n)]], exp), (T, R, worst, "key", k)
+    if adds:
+        c0 = np.stack([Cs[cl[i]] for i in adds])
+        exp = weighted_sum(o, [IP_MODS[i] for i in adds], [o.automorph_eval(c0, g) for g in galois], [pt[adds] for pt in pts])
+        assert np.array_equal(gotA[[al[i] for i in adds]], exp), (T, R, worst, "addend")
+    assert np.all(got[operm[2 * n]] == IP_GUARD) and np.all(gotA[aperm[len(adds)]] == IP_GUARD), "a guard limb-poly was written"
+
+
+@pytest.mark.parametrize("addend", ["every second entry", "none"])
+@pytest.mark.parametrize("R", [1, 3, 16])
+@pytest.mark.parametrize("T", [1, 4])
+def test_emu_key_product_lintrans(ip_env, T, R, addend):
+    """hm_ip_lintrans_thread<T>, the gather through g: the plaintext-weighted sum over the rotations, and the addend's as a third output"""
+    emu, o, h = ip_env
+    run_emu_lintrans(emu, o, h, T, R, [addend != "none" and i % 2 == 0 for i in range(len(IP_MODS))], 100 * T + R)
+
+
+def test_emu_key_product_lintrans_worst_case_operands(ip_env):
+    """16 rotations of 4 digits with every operand q - 1: the largest value the 128-bit accumulators and hm_barrett_wide ever see (the "survey"
+    build: on the generic arithmetic with a chain of 60-bit moduli)"""
+    emu, o, h = ip_env
+    run_emu_lintrans(emu, o, h, 4, 16, [i % 2 == 0 for i in range(len(IP_MODS))], 7, worst=True)
