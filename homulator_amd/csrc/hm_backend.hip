@@ -24,6 +24,7 @@
 #include "hm_params.h"
 #include "hm_caps.h"
 #include "hm_launch.h"
+#include "hm_bconv_plan.h"
 
 // ------------------------------------------------------------------------------------------------
 // kernels
@@ -1894,305 +1895,7 @@ extern "C" hm_status hm_ntt_inner_product(hm_ctx *c, const hm_ntt_ip_desc *d) {
   return HM_OK;
 }
 
-// conversion + first transform pass as a call of its own, on a range of column tiles: what a rank runs on its column slice between the two
-// transposed-domain exchanges (hm_limbs_to_colslices -> hm_bconv_col -> hm_colslices_to_limbs -> hm_ntt_inner_product with x_is_coeff = 2)
-extern "C" hm_status hm_bconv_col(hm_ctx *c, const hm_bconv_desc *descs, uint32_t n_desc, uint32_t tile0, uint32_t n_tiles) {
-  if (!c) return HM_ERR_ARG;
-  if (!descs || n_desc == 0) return fail(c, HM_ERR_ARG, "hm_bconv_col: no problems");
-  for (uint32_t k = 0; k < n_desc; ++k)
-    if (descs[k].sub_from) return fail(c, HM_ERR_UNSUPPORTED, "hm_bconv_col: no epilogue on a fused conversion");
-  return bconv_col_launch(c, descs, n_desc, nullptr, tile0, n_tiles);
-}
-
-extern "C" hm_status hm_bconv_consts(hm_ctx *c, const uint32_t *in_ids, uint32_t n_in, const uint32_t *out_ids,
-                                     uint32_t n_out, uint64_t *qhat_inv, uint64_t *table) {
-  if (!c) return HM_ERR_ARG;
-  if (!in_ids || n_in == 0 || (n_out && !out_ids)) return fail(c, HM_ERR_ARG, "hm_bconv_consts: bad basis");
-  hm_status st;
-  if ((st = check_mods(c, "hm_bconv_consts", in_ids, n_in)) || (n_out && (st = check_mods(c, "hm_bconv_consts", out_ids, n_out))))
-    return st;
-  std::vector<uint64_t> qh(n_in), tb((size_t)n_in * std::max<uint32_t>(n_out, 1));
-  c->P.bconv_consts(in_ids, n_in, out_ids, n_out, qh.data(), tb.data());
-  if (qhat_inv) memcpy(qhat_inv, qh.data(), 8ull * n_in);
-  if (table && n_out) memcpy(table, tb.data(), 8ull * n_in * n_out);
-  return HM_OK;
-}
-
-// What hm_bconv_batch ("hm_bconv") and the fused conversion check of every descriptor.  `max_in`: the widest input basis the caller's kernels take
-// (`wide` / `note`: how the caller reports a wider one)
-static hm_status check_bconv_desc(hm_ctx *c, const char *what, const hm_bconv_desc &d, uint32_t max_in, hm_status wide = HM_ERR_ARG, const char *note = "") {
-  if (d.n_in == 0 || d.n_in > max_in) return fail(c, wide, "%s: n_in %u not in [1,%u]%s", what, d.n_in, max_in, note);
-  if (d.n_out == 0 || d.n_out > HM_BCONV_MAX_OUT) return fail(c, HM_ERR_ARG, "%s: n_out %u not in [1,%d]", what, d.n_out, HM_BCONV_MAX_OUT);
-  hm_status st;
-  if ((st = check_limbs(c, what, d.in_limbs, d.n_in)) || (st = check_limbs(c, what, d.out_limbs, d.n_out)) ||
-      (st = check_mods(c, what, d.in_ids, d.n_in)) || (st = check_mods(c, what, d.out_ids, d.n_out)))
-    return st;
-  for (uint32_t i = 0; i < d.n_in; ++i)
-    for (uint32_t t = 0; t < d.n_out; ++t)
-      if (d.in_ids[i] == d.out_ids[t]) return fail(c, HM_ERR_ARG, "%s: modulus %u is in both bases", what, d.in_ids[i]);
-  return HM_OK;
-}
-
-// The device table of a conversion, cached per (input basis, output basis, kernel width); built and uploaded on first use.  Format: [n_out][row],
-// row = HM_BCONV_ROW(kn): one output's factors contiguous and padded (wide scalar loads), Montgomery form, split-30 packed; kn = the input-basis
-// size of the kernel that reads it (> n_in: a narrow digit in the widest digit's kernel, zero columns for the inputs it does not have: a table
-// of its own).  Behind the rows: {q, -q^-1} per output (HmQn), *qn
-static hm_status bconv_table(hm_ctx *c, const hm_bconv_desc &d, uint32_t kn, const uint64_t **table, const uint64_t **qn) {
-  std::vector<uint32_t> key;
-  key.push_back(d.n_in | (kn != d.n_in ? kn << 16 : 0u));
-  key.insert(key.end(), d.in_ids, d.in_ids + d.n_in);
-  key.insert(key.end(), d.out_ids, d.out_ids + d.n_out);
-  const uint32_t row = HM_BCONV_ROW(kn);
-  auto it = c->bconv_tables.find(key);
-  if (it == c->bconv_tables.end()) {
-    std::vector<uint64_t> qh(d.n_in), tb((size_t)d.n_in * d.n_out);
-    c->P.bconv_consts(d.in_ids, d.n_in, d.out_ids, d.n_out, qh.data(), tb.data());
-    std::vector<uint64_t> tt((size_t)row * d.n_out, 0);
-    for (uint32_t i = 0; i < d.n_in; ++i)
-      for (uint32_t t = 0; t < d.n_out; ++t) tt[(size_t)t * row + i] = hm_bconv_entry(tb[(size_t)i * d.n_out + t], c->P.modc[d.out_ids[t]]);
-    for (uint32_t t = 0; t < d.n_out; ++t) { tt.push_back(c->P.modc[d.out_ids[t]].q); tt.push_back(c->P.modc[d.out_ids[t]].nqinv); }
-    uint64_t *dev = nullptr;
-    HM_HIP(c, hipMalloc(&dev, 8ull * tt.size()));
-    HM_HIP(c, hipMemcpy(dev, tt.data(), 8ull * tt.size(), hipMemcpyHostToDevice));
-    it = c->bconv_tables.emplace(key, dev).first;
-  }
-  *table = it->second;
-  *qn = it->second + (size_t)row * d.n_out;
-  return HM_OK;
-}
-
-extern "C" hm_status hm_bconv_batch(hm_ctx *c, const hm_bconv_desc *descs, uint32_t n_desc) {
-  if (!c) return HM_ERR_ARG;
-  if (!descs || n_desc == 0) return fail(c, HM_ERR_ARG, "hm_bconv_batch: no problems");
-  HM_HIP(c, hipSetDevice(c->device));
-  const uint32_t logN = descs[0].log_len ? descs[0].log_len : c->P.logN;
-  if (logN < 8 || logN > c->P.logN) return fail(c, HM_ERR_ARG, "hm_bconv: log_len %u", logN);
-  std::vector<HmBconvProb> probs(n_desc);
-  for (uint32_t pi = 0; pi < n_desc; ++pi) {
-    const hm_bconv_desc &d = descs[pi];
-    if (!d.in || !d.out) return fail(c, HM_ERR_ARG, "hm_bconv: null buffer");
-    if ((d.log_len ? d.log_len : c->P.logN) != logN) return fail(c, HM_ERR_ARG, "hm_bconv_batch: mixed log_len");
-    hm_status st;
-    if ((st = check_bconv_desc(c, "hm_bconv", d, HM_BCONV_MAX_IN))) return st;
-    HmBconvProb &p = probs[pi];
-    memset(&p, 0, sizeof p);
-    if ((st = bconv_table(c, d, d.n_in, &p.table, &p.qn))) return st;
-    p.in = d.in; p.out = d.out; p.n_in = d.n_in; p.n_out = d.n_out;
-    p.in_packed = d.in_packed ? 1u : 0u;
-    for (uint32_t i = 0; i < d.n_in; ++i) p.in_limb[i] = limb_at(d.in_limbs, i);
-    for (uint32_t t = 0; t < d.n_out; ++t) {
-      p.out_limb[t] = limb_at(d.out_limbs, t);
-    }
-    if (d.sub_from) {   // epilogue out = (sub_from - conv) * k [+ add]
-      if (!d.sub_k) return fail(c, HM_ERR_ARG, "hm_bconv: the epilogue needs its constants (sub_k)");
-      if (d.log_len && d.log_len != c->P.logN) return fail(c, HM_ERR_UNSUPPORTED, "hm_bconv: the epilogue works on whole limb-polys");
-      hm_status est;
-      if ((est = check_limbs(c, "hm_bconv", d.sub_from_limbs, d.n_out)) || (est = check_limbs(c, "hm_bconv", d.add_limbs, d.n_out))) return est;
-      std::vector<HmTw> ek(d.n_out);
-      for (uint32_t t = 0; t < d.n_out; ++t) {
-        const uint64_t q = c->P.mod[d.out_ids[t]];
-        if (d.sub_k[t] >= q) return fail(c, HM_ERR_ARG, "hm_bconv: sub_k[%u] is not reduced", t);
-        ek[t] = HmTw{d.sub_k[t], hm::shoup(d.sub_k[t], q)};
-        p.ep_a_limb[t] = limb_at(d.sub_from_limbs, t);
-        p.ep_b_limb[t] = d.add ? limb_at(d.add_limbs, t) : 0;
-      }
-      const void *dk = nullptr;
-      if ((est = device_table(c, ek.data(), sizeof(HmTw) * ek.size(), &dk))) return est;
-      p.ep_a = d.sub_from; p.ep_b = d.add; p.ep_k = static_cast<const HmTw *>(dk);
-    }
-  }
-  // one launch per distinct input-basis size (the digits of a ModUp differ only in the last, shorter digit), up to
-  // HM_BCONV_MAX_PROB problems each; the problem records go into a device table cached by content (plans repeat)
-  std::vector<char> done(n_desc, 0);
-  for (uint32_t first = 0; first < n_desc; ++first) {
-    if (done[first]) continue;
-    const uint32_t n_in = probs[first].n_in;
-    std::vector<HmBconvProb> grp;
-    uint32_t max_out = 0;
-    auto launch = [&]() -> hm_status {
-      const void *dtab = nullptr;
-      hm_status st = device_table(c, grp.data(), sizeof(HmBconvProb) * grp.size(), &dtab);
-      if (st) return st;
-      HmBconvArgs a;
-      a.prob = static_cast<const HmBconvProb *>(dtab); a.logN = logN; a.n_prob = (uint32_t)grp.size();
-      // output limbs per block: a block re-reads its N_IN input limbs for every chunk, so the chunk should be as large
-      // as the launch allows while leaving >= ~4 rounds of blocks for the chip (3 blocks of 256 threads per CU)
-      const uint32_t xb = std::max(1u, (1u << logN) / (HM_BCONV_THREADS * HM_BCONV_CPT));
-      const uint32_t want = c->bconv_blocks;
-      uint32_t nchunk = std::max<uint32_t>(1, (want + xb * a.n_prob - 1) / (xb * a.n_prob));
-      nchunk = std::min(nchunk, (max_out + HM_BCONV_CHUNK / 2 - 1) / std::max(1, HM_BCONV_CHUNK / 2));  // chunks of >= 4 outputs
-      nchunk = std::max<uint32_t>(1, nchunk);
-      a.chunk = (max_out + nchunk - 1) / nchunk;
-      dim3 grid(xb, (max_out + a.chunk - 1) / a.chunk, a.n_prob);
-      hipLaunchKernelGGL(k_bconv_by_n_in[n_in], grid, dim3(HM_BCONV_THREADS), 0, c->stream, a);
-      grp.clear(); max_out = 0;
-      return HM_OK;
-    };
-    for (uint32_t pi = first; pi < n_desc; ++pi) {
-      if (done[pi] || probs[pi].n_in != n_in) continue;
-      done[pi] = 1;
-      grp.push_back(probs[pi]);
-      max_out = std::max(max_out, probs[pi].n_out);
-      if (grp.size() == HM_BCONV_MAX_PROB) { hm_status st = launch(); if (st) return st; }
-    }
-    if (!grp.empty()) { hm_status st = launch(); if (st) return st; }
-    HM_HIP(c, hipGetLastError());
-  }
-  return HM_OK;
-}
-
-
-// conversion + first transform pass in one kernel (see k_bconv_col).  Same descriptors as hm_bconv_batch; `out` receives the COL pass's
-// hand-off of NTT(conversion), the form k_ntt_row_ip reads.  N = 2^16, n_in <= HM_BCOL_MAX_IN.
-// tile0 / n_tiles: the column tiles (16 columns each) to work on — all of them (n_tiles = 0) or a rank's column slice (hm_bconv_col)
-static hm_status bconv_col_launch(hm_ctx *c, const hm_bconv_desc *descs, uint32_t n_desc, const BcolMix *mix, uint32_t tile0, uint32_t n_tiles) {
-  if (!c || !descs || n_desc == 0) return HM_ERR_ARG;
-  const uint32_t allTiles = c->P.N >> HM_TL_COL;
-  if (!n_tiles) { tile0 = 0; n_tiles = allTiles; }
-  if ((n_tiles & (n_tiles - 1)) || tile0 % n_tiles || tile0 + n_tiles > allTiles) return fail(c, HM_ERR_ARG, "fused conversion: tile range [%u, %u) of %u",
-      tile0, tile0 + n_tiles, allTiles);
-  if (!hm_caps(c->P.logN).bcol_max_in) return fail(c, HM_ERR_UNSUPPORTED, "fused conversion: N = 2^15 or 2^16 only");
-  HM_HIP(c, hipSetDevice(c->device));
-  // output limbs per workgroup: two share the loaded and split inputs (+2 % hmult/s at batch 10), but halve the workgroups of a launch that
-  // fills the chip only once or twice (one op at a time: -2 %): by launch size unless the option says otherwise
-  // Small calls whose digits differ in width run as ONE launch of the widest digit's kernel (below) — and then with two outputs per workgroup: 920
-  // workgroups on the chip's 1 024 slots (one round) where one output per workgroup made 1 840 (1.8 rounds): one op at a time +1.3 % on top of
-  // the merge (gpurun_out: tools/r06_nout_ab.sh).  A small call of ONE width keeps one output per workgroup (level since the four-wave kernels).
-  uint32_t NOUT = c->bcol_outs;
-  size_t wgsAll = 0;
-  bool widths[2][HM_BCONV_MAX_IN + 1] = {};
-  uint32_t nWidths = 0;
-  for (uint32_t pi = 0; pi < n_desc; ++pi) {
-    wgsAll += (size_t)descs[pi].n_out * n_tiles;
-    bool &w = widths[descs[pi].in_packed ? 1 : 0][std::min<uint32_t>(descs[pi].n_in, HM_BCONV_MAX_IN)];
-    nWidths += !w;
-    w = true;
-  }
-  const bool mayMerge = c->bcol_merge && !mix && wgsAll <= 4096 && nWidths > 1;
-  if (!NOUT) NOUT = wgsAll > 4096 || mayMerge ? 2 : 1;
-  std::map<uint32_t, std::vector<HmBcolProb>> byIn;   // key: n_in, + 256 for conversions whose inputs are stored packed (kernels of their own)
-  bool farApart = false;
-  // Round 6, small launches (one op at a time, a rank's share of a sharded op): digits of different width are launches of different kernels, one
-  // behind the other, and each leaves the chip part empty — hmult 45/35/15: 1 120 workgroups of <15> on 1 024 slots (a second, nearly empty
-  // round: 40.7 us) and then 720 of <5> (19.5 us).  When the whole call is small, the narrower digits run the WIDEST digit's kernel with zero
-  // table columns for the inputs they do not have (the padded inputs re-read the digit's first limb: exact zeros are added): ONE launch of
-  // 1 840 workgroups (920 with two outputs each).  More multiply-adds for the narrow digit, fewer rounds for the launch; option "bconv_col_merge"
-  // (default 1; 0 = off).
-  std::vector<uint32_t> kernelNin(n_desc);
-  {
-    uint32_t widest[2] = {0, 0};
-    for (uint32_t pi = 0; pi < n_desc; ++pi) widest[descs[pi].in_packed ? 1 : 0] = std::max(widest[descs[pi].in_packed ? 1 : 0], descs[pi].n_in);
-    const bool merge = mayMerge;
-    for (uint32_t pi = 0; pi < n_desc; ++pi) {
-      const uint32_t w = widest[descs[pi].in_packed ? 1 : 0];
-      // (a digit runs the widest digit's kernel only inside one family: up to 15 limbs, or two input groups; and not for more than four times its own work)
-      kernelNin[pi] = merge && (w <= HM_BCOL_ONE_GROUP || descs[pi].n_in > HM_BCOL_ONE_GROUP) && w <= 4 * descs[pi].n_in ? w : descs[pi].n_in;
-    }
-  }
-  for (uint32_t pi = 0; pi < n_desc; ++pi) {
-    const hm_bconv_desc &d = descs[pi];
-    const uint32_t kn = kernelNin[pi];   // the input-basis size of the kernel this conversion runs (>= d.n_in)
-    if (!d.in || !d.out || !d.in_ids || !d.out_ids) return fail(c, HM_ERR_ARG, "fused conversion: null argument");
-    const uint32_t maxIn = mix ? hm_caps(c->P.logN).bcol_max_in_mix : hm_caps(c->P.logN).bcol_max_in;
-    hm_status cst;
-    if ((cst = check_bconv_desc(c, "fused conversion", d, maxIn, HM_ERR_UNSUPPORTED, mix ? " (with the mix prologue)" : ""))) return cst;
-    if (d.log_len && d.log_len != c->P.logN) return fail(c, HM_ERR_UNSUPPORTED, "fused conversion: whole limb-polys only");
-    if (d.out != descs[0].out) return fail(c, HM_ERR_ARG, "fused conversion: one hand-off buffer per call");
-    HmBcolProb p;
-    memset(&p, 0, sizeof p);
-    if ((cst = bconv_table(c, d, kn, &p.table, &p.qn))) return cst;
-    p.in = d.in; p.n_in = d.n_in; p.n_out = d.n_out;
-    p.in_packed = d.in_packed ? 1u : 0u;
-    for (uint32_t i = 0; i < d.n_in; ++i) p.in_limb[i] = limb_at(d.in_limbs, i);
-    {   // ONE buffer descriptor per conversion: the lowest input limb-poly is the base, the others are byte offsets from it (HmBcolProb::in_off)
-      uint32_t lo = p.in_limb[0], hi = p.in_limb[0];
-      for (uint32_t i = 1; i < d.n_in; ++i) { lo = std::min(lo, p.in_limb[i]); hi = std::max(hi, p.in_limb[i]); }
-      if (((uint64_t)(hi - lo) + 1) << (c->P.logN + 3) > (1ull << 32)) { farApart = true; break; }   // inputs more than 4 GiB apart: the fallback below
-      p.in_base = d.in + (size_t)lo * c->P.N;
-      for (uint32_t i = 0; i < d.n_in; ++i) p.in_off[i] = (p.in_limb[i] - lo) << (c->P.logN + 3);
-      // padded inputs: a valid limb-poly, zero table columns
-      for (uint32_t i = d.n_in; i < kn; ++i) { p.in_limb[i] = p.in_limb[0]; p.in_off[i] = p.in_off[0]; }
-    }
-    for (uint32_t t = 0; t < d.n_out; ++t) { p.out_limb[t] = limb_at(d.out_limbs, t); p.out_mod[t] = d.out_ids[t]; }
-    if (mix) {   // x = conv + k * mix before the first butterfly: constants in Shoup form, a device table cached by content
-      std::vector<HmTw> mk(d.n_out);
-      for (uint32_t t = 0; t < d.n_out; ++t) {
-        const uint64_t q = c->P.mod[d.out_ids[t]], k = mix->mix_k[pi][t];
-        if (k >= q) return fail(c, HM_ERR_ARG, "fused conversion: mix constant [%u][%u] is not reduced", pi, t);
-        if (mix->mix_limbs[pi][t] > 0xFFFFu) return fail(c, HM_ERR_ARG, "fused conversion: limb index exceeds 65535");
-        mk[t] = hm_kconst(k, q);
-        p.mix_limb[t] = mix->mix_limbs[pi][t];
-      }
-      const void *dk = nullptr;
-      hm_status st = device_table(c, mk.data(), sizeof(HmTw) * mk.size(), &dk);
-      if (st) return st;
-      p.mixk = static_cast<const HmTw *>(dk);
-    }
-    // (measured with the combination built: the fused ModDown conversion stays 2.5 % behind the separate one with packed inputs too —
-    // profiles/r05_late_ab.txt — so the 120 instantiations it needs are not shipped)
-    if (mix && d.in_packed) return fail(c, HM_ERR_UNSUPPORTED,
-        "fused conversion: packed inputs and the mix prologue do not combine (convert from plain inputs)");
-    byIn[kn + (d.in_packed ? 256u : 0u)].push_back(p);
-  }
-  if (farApart) {
-    // A conversion whose input limb-polys are spread over more than 4 GiB of the buffer cannot be addressed from one descriptor with 32-bit
-    // offsets.  The plans of the host layer never produce one (a digit's limbs are neighbours in the pool); a caller's list that does is
-    // served by the two steps the fused kernel stands for: the conversion into the hand-off limbs, then the first pass in place on them.
-    if (n_tiles != allTiles) return fail(c, HM_ERR_UNSUPPORTED,
-        "fused conversion on a column slice: the inputs of a conversion must lie within 4 GiB of each other");
-    hm_status st = hm_bconv_batch(c, descs, n_desc);
-    if (st) return st;
-    std::vector<uint32_t> limbs, mods, ml;
-    std::vector<uint64_t> mk;
-    for (uint32_t pi = 0; pi < n_desc; ++pi)
-      for (uint32_t t = 0; t < descs[pi].n_out; ++t) {
-        limbs.push_back(limb_at(descs[pi].out_limbs, t)); mods.push_back(descs[pi].out_ids[t]);
-        if (mix) { ml.push_back(mix->mix_limbs[pi][t]); mk.push_back(mix->mix_k[pi][t]); }
-      }
-    NttFused f;
-    f.firstPassOnly = true;
-    if (mix) { f.mix = mix->mix; f.mix_limbs = ml.data(); f.mix_k = mk.data(); f.minuend = descs[0].out;
-        /* (marks the fused form: the first pass only reads the mix operand) */ }
-    std::vector<uint64_t> ones(limbs.size(), 1);
-    return ntt_common(c, "fused conversion", descs[0].out, limbs.data(), descs[0].out, limbs.data(), mods.data(), (uint32_t)limbs.size(), 0, mix ?
-        ones.data() : nullptr, f);
-  }
-  struct Lnch { uint32_t n_in; dim3 grid; HmBcolArgs a; };
-  std::vector<Lnch> ls;
-  for (auto &kv : byIn) {
-    auto &grp = kv.second;
-    uint32_t max_out = 0;
-    uint64_t *out = descs[0].out;   // one hand-off buffer for the call (checked above)
-    for (auto &p : grp) max_out = std::max(max_out, p.n_out);
-    const uint32_t groups = (max_out + NOUT - 1) / NOUT;   // output groups per (conversion, tile)
-    const void *dtab = nullptr;
-    hm_status st = device_table(c, grp.data(), sizeof(HmBcolProb) * grp.size(), &dtab);
-    if (st) return st;
-    uint32_t logTiles = 0;
-    while ((1u << logTiles) < n_tiles) ++logTiles;
-    HmBcolArgs a = {static_cast<const HmBcolProb *>(dtab), out, c->d_tw_fwd, c->P.logN, (uint32_t)grp.size(), groups, mix ? mix->mix : nullptr, tile0,
-        logTiles};
-    const uint32_t pairs = ((uint32_t)grp.size() * n_tiles + 7) / 8 * 8;
-    ls.push_back(Lnch{kv.first, dim3(pairs * groups), a});
-  }
-  // Digits of different size are launches of different kernels (N_IN is a template parameter).  (Running them side by side on a second
-  // stream between a fork and a join event was measured slower: +21 us per op, profiles/README.md "side launches"; removed in round 5.)
-  const dim3 block((1 << HM_TL_COL) / HM_EPT);
-  for (size_t i = 0; i < ls.size(); ++i) {
-    const hm_bcol_kernel kern = hm_bcol_kernel_for(ls[i].n_in & 255u, c->P.logN, NOUT, mix != nullptr, ls[i].n_in >= 256u);
-    if (!kern) return fail(c, HM_ERR_UNSUPPORTED, "fused conversion: no kernel for n_in %u at N = 2^%u", ls[i].n_in, c->P.logN);
-    hipLaunchKernelGGL(kern, ls[i].grid, block, 0, c->stream, ls[i].a);
-    HM_HIP(c, hipGetLastError());
-  }
-  return HM_OK;
-}
-
-extern "C" hm_status hm_bconv(hm_ctx *c, const uint64_t *in, const uint32_t *in_limbs, const uint32_t *in_ids,
-                              uint32_t n_in, uint64_t *out, const uint32_t *out_limbs, const uint32_t *out_ids,
-                              uint32_t n_out) {
-  hm_bconv_desc d = {in, in_limbs, in_ids, n_in, out, out_limbs, out_ids, n_out, 0};
-  return hm_bconv_batch(c, &d, 1);
-}
+#include "hm_bconv.inl"     // base conversion: hm_bconv, hm_bconv_batch, hm_bconv_col, hm_bconv_consts and the fused conversion + first pass (bconv_col_launch)
 
 #include "hm_exchange.inl"   // multi-GPU exchange: communicators, limb <-> slice exchanges, replicate
 

@@ -1,6 +1,7 @@
-// hm_bcol.h — base conversion fused into the first pass of the transform that consumes it: kernel body, launch records and the
-// kernel table.  The instantiations (input-basis size x ring size x mix prologue) are compiled in several translation units
-// (hm_bcol_part.hip with -DHM_BCOL_PART=k, in parallel); hm_backend.hip looks kernels up through hm_bcol_kernel_for().
+// hm_bcol.h — base conversion fused into the first pass of the transform that consumes it: kernel body and the kernel table (the launch
+// records HmBcolProb / HmBcolArgs and the block map hm_bcol_block: hm_elem_core.h, where the CPU emulator can include them).
+// The instantiations (input-basis size x ring size x mix prologue) are compiled in several translation units (hm_bcol_part.hip with
+// -DHM_BCOL_PART=k, in parallel); hm_backend.hip looks kernels up through hm_bcol_kernel_for().
 #pragma once
 #include "hm_elem_core.h"
 #include "hm_ntt_core.h"
@@ -14,26 +15,6 @@
 // tiles (the workgroups of the same (p, t) for the other outputs sit in neighbouring dispatch slots of one XCD and find the inputs in
 // L2), then runs the COL pass on them: the converted limb-poly never exists in HBM, only the first pass's hand-off does.
 template <int V> struct HmIc { static constexpr int value = V; };
-#define HM_BCOL_ONE_GROUP 15    // up to here every input of an access unit is held at once (16: hipcc leaves the arrays in scratch, 1 KB per lane)
-struct HmBcolProb {
-  const uint64_t *in;
-  const uint64_t *table, *qn;
-  uint32_t n_in, n_out;
-  uint32_t in_limb[HM_BCONV_MAX_IN];
-  uint32_t out_limb[HM_BCONV_MAX_OUT];   // where the hand-off of output o goes (limb of `out`)
-  uint32_t out_mod[HM_BCONV_MAX_OUT];    // its modulus id (shared twiddles)
-  uint32_t mix_limb[HM_BCONV_MAX_OUT];   // MIX: the operand added to output o before the transform (limb of HmBcolArgs::mix), constant in mixk
-  const HmTw *mixk;                      // MIX: device, [n_out]
-  uint32_t in_packed;                    // the inputs are stored in the split-30 packed form (hm_pack30): no shift / mask per input and workgroup
-  // round 6 (scalar-register diet): ONE buffer descriptor for all inputs of a conversion — base = the lowest input limb-poly, input i at
-  // byte offset in_off[i] from it (a scalar operand of the load).  A descriptor per input (four scalar registers each: 60 for a 15-limb
-  // digit, 112 for 28) was hoisted out of the unit loop together with the table rows and spilled into vector-register lanes: 390
-  // v_readlane / v_writelane in 5 531 vector instructions of k_bconv_col2<15>, 1 444 in 9 045 of k_bconv_col2<28>.  The host checks that
-  // the inputs of a conversion lie within 4 GiB of each other (the digits of a plan are neighbours in the pool); a conversion whose inputs
-  // are further apart runs as conversion + first pass (bconv_col_launch).
-  const uint64_t *in_base;
-  uint32_t in_off[HM_BCONV_MAX_IN];
-};
 // the table pointer made opaque once per access unit: the rows of an output are then requested again for every unit (scalar loads that hit
 // the scalar cache, issued while the unit's vector loads are in flight) instead of being held — 64 scalar registers for two outputs of a
 // 15-limb digit — across the whole unit loop
@@ -64,14 +45,6 @@ __device__ __forceinline__ void hm_bcol_load_in(const PROB &p, int i, uint32_t t
 #endif
   hm_gld2<G0>(p.in + (size_t)p.in_limb[i] * N, tile, tid, u, v0, v1);
 }
-struct HmBcolArgs {
-  const HmBcolProb *prob;   // device
-  uint64_t *out;
-  const HmW *tw;
-  uint32_t logN, n_prob, max_out;   // max_out: output GROUPS (of NOUT limbs) per (conversion, tile)
-  const uint64_t *mix;
-  uint32_t tile0, logTiles;         // the column tiles this launch works on: [tile0, tile0 + 2^logTiles) (all of them, or a rank's column slice)
-};
 // One workgroup = (conversion, NOUT consecutive output limbs, column tile).  NOUT = 2 (round 4): the N_IN input access units of a thread
 // are loaded and split ONCE and multiplied into both outputs (half the L2 requests, the shift / mask work of the split amortised), then
 // the COL rounds run for one output after the other on the one LDS tile (the second output waits in registers).  MIX (round 4: the
@@ -232,13 +205,8 @@ __device__ __forceinline__ void hm_bconv_col_body(const HmBcolArgs &a) {
   using PS = HmPass<LOG1, true, false>;
   using G0 = HmRound<TL, LOG1, true, PS::exec(0)>;
   __shared__ __attribute__((aligned(16))) uint64_t lds[HmLds<TL, LOG1, true>::WORDS];
-  // blocks b, b + 8 share an XCD; inside an XCD: (conversion, tile) pairs, each with its max_out output groups in consecutive slots
-  const uint32_t b = blockIdx.x, xcd = b & 7u, slot = b >> 3;
-  // (the division runs on the vector unit: its results are made scalar again by hand, or every buffer access below becomes a waterfall loop)
-  const uint32_t sdiv = __builtin_amdgcn_readfirstlane(slot / a.max_out);
-  const uint32_t pair = sdiv * 8u + xcd, og = slot - sdiv * a.max_out;
-  const uint32_t logT = a.logTiles;
-  const uint32_t pi = pair >> logT, tile = a.tile0 + (pair & ((1u << logT) - 1u));
+  const HmBcolBlock blk = hm_bcol_block(blockIdx.x, a.max_out, a.tile0, a.logTiles);
+  const uint32_t pi = blk.pi, tile = blk.tile, og = blk.og;
   if (pi >= a.n_prob) return;
   const auto &p = HM_CONST_PROB_T(HmBcolProb, a.prob)[pi];
   const uint32_t o0 = og * NOUT;

@@ -9,6 +9,7 @@
 //            BCONVU 2x6 MAC array src/Components.cpp:268-295.
 //   K2 AUTO  InsGen::GenAUTO src/InsGen.cpp:46-71, AUTOU src/Components.cpp:173-194.
 #pragma once
+#include <cstddef>
 #include "hm_modarith.h"
 #include "hm_ntt_core.h"
 
@@ -128,6 +129,58 @@ struct HmBconvArgs {
   uint32_t logN, n_prob;
   uint32_t chunk;           // output limbs per block (the host trades input re-reads against blocks in flight)
 };
+// ---- the records of the base conversion fused into the first pass of the transform that consumes it (kernels: hm_bcol.h)
+#define HM_BCOL_ONE_GROUP 15    // up to here every input of an access unit is held at once (16: hipcc leaves the arrays in scratch, 1 KB per lane)
+struct HmBcolProb {
+  const uint64_t *in;
+  const uint64_t *table, *qn;
+  uint32_t n_in, n_out;
+  uint32_t in_limb[HM_BCONV_MAX_IN];
+  uint32_t out_limb[HM_BCONV_MAX_OUT];   // where the hand-off of output o goes (limb of `out`)
+  uint32_t out_mod[HM_BCONV_MAX_OUT];    // its modulus id (shared twiddles)
+  uint32_t mix_limb[HM_BCONV_MAX_OUT];   // MIX: the operand added to output o before the transform (limb of HmBcolArgs::mix), constant in mixk
+  const HmTw *mixk;                      // MIX: device, [n_out]
+  uint32_t in_packed;                    // the inputs are stored in the split-30 packed form (hm_pack30): no shift / mask per input and workgroup
+  // round 6 (scalar-register diet): ONE buffer descriptor for all inputs of a conversion — base = the lowest input limb-poly, input i at
+  // byte offset in_off[i] from it (a scalar operand of the load).  A descriptor per input (four scalar registers each: 60 for a 15-limb
+  // digit, 112 for 28) was hoisted out of the unit loop together with the table rows and spilled into vector-register lanes: 390
+  // v_readlane / v_writelane in 5 531 vector instructions of k_bconv_col2<15>, 1 444 in 9 045 of k_bconv_col2<28>.  The host checks that
+  // the inputs of a conversion lie within 4 GiB of each other (the digits of a plan are neighbours in the pool); a conversion whose inputs
+  // are further apart runs as conversion + first pass (bconv_col_launch).
+  const uint64_t *in_base;
+  uint32_t in_off[HM_BCONV_MAX_IN];
+};
+struct HmBcolArgs {
+  const HmBcolProb *prob;   // device
+  uint64_t *out;
+  const HmW *tw;
+  uint32_t logN, n_prob, max_out;   // max_out: output GROUPS (of NOUT limbs) per (conversion, tile)
+  const uint64_t *mix;
+  uint32_t tile0, logTiles;         // the column tiles this launch works on: [tile0, tile0 + 2^logTiles) (all of them, or a rank's column slice)
+};
+// The block-to-work map of the fused launch, one half of a contract with the host's grid (hm_bcol_plan, hm_bconv_plan.h: grid = max_out *
+// 8 * ceil(n_prob * tiles / 8)): blocks b, b + 8 share an XCD; inside an XCD: (conversion, tile) pairs, each with its max_out output groups
+// in consecutive slots.  pi >= n_prob (the padding of the pairs to a multiple of 8) and og * NOUT >= n_out (a conversion with fewer
+// outputs than the launch's widest) are the kernel's two early returns.
+struct HmBcolBlock {
+  uint32_t pi, tile, og;   // conversion, column tile, output group
+};
+HM_HD HmBcolBlock hm_bcol_block(uint32_t b, uint32_t max_out, uint32_t tile0, uint32_t logTiles) {
+  const uint32_t xcd = b & 7u, slot = b >> 3;
+  // (the division runs on the vector unit: its results are made scalar again by hand, or every buffer access of the kernel becomes a waterfall loop)
+#if defined(__HIP_DEVICE_COMPILE__)
+  const uint32_t sdiv = __builtin_amdgcn_readfirstlane(slot / max_out);
+#else
+  const uint32_t sdiv = slot / max_out;
+#endif
+  const uint32_t pair = sdiv * 8u + xcd;
+  return HmBcolBlock{pair >> logTiles, tile0 + (pair & ((1u << logTiles) - 1u)), slot - sdiv * max_out};
+}
+// (the records are read by compiled kernels through scalar loads at fixed offsets: the layouts are pinned)
+static_assert(sizeof(HmBconvProb) == 968 && offsetof(HmBconvProb, table) == 16 && offsetof(HmBconvProb, in_limb) == 40 && offsetof(HmBconvProb, out_limb) == 168,
+              "HmBconvProb: layout");
+static_assert(sizeof(HmBcolProb) == 1080 && offsetof(HmBcolProb, table) == 8 && offsetof(HmBcolProb, in_limb) == 32 && offsetof(HmBcolProb, out_limb) == 160 &&
+              offsetof(HmBcolProb, in_base) == 944 && offsetof(HmBcolProb, in_off) == 952, "HmBcolProb: layout");
 #if defined(__HIP_DEVICE_COMPILE__)
 typedef const HmBconvProb __attribute__((address_space(4))) *HmConstProb;
 #define HM_CONST_PROB(p) ((HmConstProb)(uintptr_t)(p))

@@ -15,6 +15,7 @@
 #include "../../homulator_amd/csrc/hm_ntt_core.h"
 #include "../../homulator_amd/csrc/hm_params.h"
 #include "../../homulator_amd/csrc/hm_launch.h"
+#include "../../homulator_amd/csrc/hm_bconv_plan.h"
 
 struct Emu {
   hm::Params P;
@@ -74,37 +75,27 @@ static void run_ntt(const Emu &e, uint32_t mod, const uint64_t *in, uint64_t *ou
   }
 }
 
-template <int N_IN>
-static void emu_bconv_n(Emu &e, HmBconvProb &p, const std::vector<uint64_t> &tb, const uint32_t *out_ids) {
-  const uint32_t row = HM_BCONV_ROW(p.n_in);
-  std::vector<uint64_t> tt((size_t)row * p.n_out, 0);  // device format: [n_out][row], Montgomery form, packed, zero-padded rows
-  std::vector<uint64_t> qn;                            // {q, -q^-1} per output
-  for (uint32_t i = 0; i < p.n_in; ++i)
-    for (uint32_t t = 0; t < p.n_out; ++t) tt[(size_t)t * row + i] = hm_bconv_entry(tb[(size_t)i * p.n_out + t], e.P.modc[out_ids[t]]);
-  for (uint32_t t = 0; t < p.n_out; ++t) { qn.push_back(e.P.modc[out_ids[t]].q); qn.push_back(e.P.modc[out_ids[t]].nqinv); }
-  p.table = tt.data();
-  p.qn = qn.data();
+// the conversion through the kernel of width KN >= p.n_in (p.table: the conversion's device table for that width, hm_bconv_table_words; the inputs
+// a narrow digit does not have: p.in_limb[n_in .. KN), hm_bcol_window)
+template <int KN>
+static void emu_bconv_n(const HmBconvProb &p, uint32_t logN) {
   for (uint32_t t0 = 0; t0 < p.n_out; t0 += HM_BCONV_CHUNK) {
     uint32_t t1 = t0 + HM_BCONV_CHUNK < p.n_out ? t0 + HM_BCONV_CHUNK : p.n_out;
-    for (uint32_t x = 0; x < e.P.N; x += HM_BCONV_CPT) {
-      if (p.in_packed) hm_bconv_thread<N_IN, HM_BCONV_CPT, true>(p, e.P.logN, x, t0, t1);
-      else hm_bconv_thread<N_IN, HM_BCONV_CPT, false>(p, e.P.logN, x, t0, t1);
+    for (uint32_t x = 0; x < (1u << logN); x += HM_BCONV_CPT) {
+      if (p.in_packed) hm_bconv_thread<KN, HM_BCONV_CPT, true>(p, logN, x, t0, t1);
+      else hm_bconv_thread<KN, HM_BCONV_CPT, false>(p, logN, x, t0, t1);
     }
   }
 }
 
 // round 6: the arithmetic of the two-group conversion of k_bconv_col (digits of 16 .. 32 limbs, hm_bcol_units_wide): per output and coefficient the
 // 128-bit sums of the group [0, 16) and of the group [16, n_in) (hm_bconv_cols: carry-free split-30 columns, recombined per group), added, ONE
-// Montgomery reduction for all n_in terms (hm_redc_wide<N_IN>).  Same table format as the kernel (rows of 8-entry groups, Montgomery form,
-// split-30 packed); packed != 0: the inputs arrive in the split-30 packed form.
+// Montgomery reduction for all n_in terms (hm_redc_wide<N_IN>).  Same table as the kernel (hm_bconv_table_words); packed != 0: the inputs arrive in the split-30 packed form.
 template <int N_IN>
-static void emu_bconv_wide_n(Emu &e, const uint32_t *out_ids, uint32_t n_out, const std::vector<uint64_t> &tb, const uint64_t *in, uint64_t *out, int packed) {
+static void emu_bconv_wide_n(Emu &e, const uint32_t *out_ids, uint32_t n_out, const std::vector<uint64_t> &table, const uint64_t *in, uint64_t *out, int packed) {
   constexpr int ROWS = (N_IN + 7) / 8, C1 = N_IN - 16;
   const uint32_t N = e.P.N;
-  std::vector<HmRow8> rows((size_t)n_out * ROWS);
-  for (auto &r : rows) for (auto &w : r.w) w = 0;
-  for (uint32_t t = 0; t < n_out; ++t)
-    for (int i = 0; i < N_IN; ++i) rows[(size_t)t * ROWS + i / 8].w[i % 8] = hm_bconv_entry(tb[(size_t)i * n_out + t], e.P.modc[out_ids[t]]);
+  HmConstRow8 rows = HM_CONST_ROWS(table.data());
   for (uint32_t t = 0; t < n_out; ++t) {
     const HmMod &m = e.P.modc[out_ids[t]];
     HmRow8 r0[2], r1[(C1 > 0 ? C1 + 7 : 8) / 8];
@@ -314,42 +305,45 @@ void emu_ewe(void *h, int op, uint32_t mod, const uint64_t *a, const uint64_t *b
   }
 }
 
-// packed != 0: the inputs are first brought into the split-30 packed form (hm_pack30) and the conversion is told so (in_packed)
-void emu_bconv_form(void *h, const uint32_t *in_ids, uint32_t n_in, const uint32_t *out_ids, uint32_t n_out,
-                    const uint64_t *in, uint64_t *out, int packed);
-void emu_bconv(void *h, const uint32_t *in_ids, uint32_t n_in, const uint32_t *out_ids, uint32_t n_out,
-               const uint64_t *in, uint64_t *out) { emu_bconv_form(h, in_ids, n_in, out_ids, n_out, in, out, 0); }
-void emu_bconv_form(void *h, const uint32_t *in_ids, uint32_t n_in, const uint32_t *out_ids, uint32_t n_out,
-                    const uint64_t *in, uint64_t *out, int packed) {
+// packed != 0: the inputs are first brought into the split-30 packed form (hm_pack30) and the conversion is told so (in_packed).
+// kn >= n_in: the width of the kernel the conversion runs (kn > n_in: a narrow digit in a wider digit's kernel, as bconv_col_launch merges them);
+// log_len: limb-polys of 2^log_len coefficients (hm_bconv_desc::log_len; 0 = the ring's)
+int emu_bconv_kn(void *h, const uint32_t *in_ids, uint32_t n_in, const uint32_t *out_ids, uint32_t n_out, uint32_t kn,
+                 const uint64_t *in, uint64_t *out, int packed, uint32_t log_len) {
   Emu &e = *(Emu *)h;
-  std::vector<uint64_t> qh(n_in), tb((size_t)n_in * n_out);
-  e.P.bconv_consts(in_ids, n_in, out_ids, n_out, qh.data(), tb.data());
+  const uint32_t logN = log_len ? log_len : e.P.logN;
+  if (kn < n_in || kn > HM_BCONV_MAX_IN || logN < 8 || logN > e.P.logN) return 1;
+  const std::vector<uint64_t> table = hm_bconv_table_words(e.P, in_ids, n_in, out_ids, n_out, kn);
   std::vector<uint64_t> pk;
   if (packed) {
-    pk.assign(in, in + (size_t)n_in * e.P.N);
+    pk.assign(in, in + ((size_t)n_in << logN));
     for (uint64_t &v : pk) v = hm_pack30(v);
     in = pk.data();
   }
-  HmBconvProb p{};
-  p.in_packed = packed ? 1u : 0u;
-  p.in = in; p.out = out; p.table = tb.data(); p.n_in = n_in; p.n_out = n_out;
-  for (uint32_t i = 0; i < n_in; ++i) p.in_limb[i] = i;
-  for (uint32_t t = 0; t < n_out; ++t) p.out_limb[t] = t;
-  switch (n_in) {
-#define HM_CASE(n) case n: emu_bconv_n<n>(e, p, tb, out_ids); break;
+  HmBconvProb p;
+  hm_bconv_fill(p, in, table.data(), kn, nullptr, n_in, nullptr, n_out, packed != 0);
+  p.out = out;
+  const HmBcolWindow w = hm_bcol_window(nullptr, n_in, kn, logN);
+  memcpy(p.in_limb, w.limb, sizeof p.in_limb);
+  switch (kn) {
+#define HM_CASE(n) case n: emu_bconv_n<n>(p, logN); break;
     HM_CASE(1) HM_CASE(2) HM_CASE(3) HM_CASE(4) HM_CASE(5) HM_CASE(6) HM_CASE(7) HM_CASE(8)
     HM_CASE(9) HM_CASE(10) HM_CASE(11) HM_CASE(12) HM_CASE(13) HM_CASE(14) HM_CASE(15) HM_CASE(16)
     HM_CASE(17) HM_CASE(18) HM_CASE(19) HM_CASE(20) HM_CASE(21) HM_CASE(22) HM_CASE(23) HM_CASE(24)
     HM_CASE(25) HM_CASE(26) HM_CASE(27) HM_CASE(28) HM_CASE(29) HM_CASE(30) HM_CASE(31) HM_CASE(32)
 #undef HM_CASE
   }
+  return 0;
 }
+void emu_bconv_form(void *h, const uint32_t *in_ids, uint32_t n_in, const uint32_t *out_ids, uint32_t n_out,
+                    const uint64_t *in, uint64_t *out, int packed) { emu_bconv_kn(h, in_ids, n_in, out_ids, n_out, n_in, in, out, packed, 0); }
+void emu_bconv(void *h, const uint32_t *in_ids, uint32_t n_in, const uint32_t *out_ids, uint32_t n_out,
+               const uint64_t *in, uint64_t *out) { emu_bconv_kn(h, in_ids, n_in, out_ids, n_out, n_in, in, out, 0, 0); }
 int emu_bconv_two_groups(void *h, const uint32_t *in_ids, uint32_t n_in, const uint32_t *out_ids, uint32_t n_out, const uint64_t *in, uint64_t *out, int packed) {
   Emu &e = *(Emu *)h;
-  std::vector<uint64_t> qh(n_in), tb((size_t)n_in * n_out);
-  e.P.bconv_consts(in_ids, n_in, out_ids, n_out, qh.data(), tb.data());
+  const std::vector<uint64_t> table = hm_bconv_table_words(e.P, in_ids, n_in, out_ids, n_out, n_in);
   switch (n_in) {
-#define HM_CASE(n) case n: emu_bconv_wide_n<n>(e, out_ids, n_out, tb, in, out, packed); break;
+#define HM_CASE(n) case n: emu_bconv_wide_n<n>(e, out_ids, n_out, table, in, out, packed); break;
     HM_CASE(16) HM_CASE(17) HM_CASE(18) HM_CASE(19) HM_CASE(20) HM_CASE(21) HM_CASE(22) HM_CASE(23) HM_CASE(24)
     HM_CASE(25) HM_CASE(26) HM_CASE(27) HM_CASE(28) HM_CASE(29) HM_CASE(30) HM_CASE(31) HM_CASE(32)
 #undef HM_CASE
@@ -484,6 +478,54 @@ uint32_t emu_launch_layout(int policy, int one_launch, uint32_t entry_cap, const
   *logG = g.logG;
   return launch;
 }
+// ---- the conversion's launch plans (hm_bconv_plan.h) as its entry points compute them.  Per descriptor: its launch and its place among the launch's
+// members; per launch (up to max_launch): a row of `info`; returns the number of launches.
+// stand-alone (hm_bconv_batch): info row = {n_in, chunk, grid x, grid y, grid z}
+uint32_t emu_bconv_plan(const uint32_t *n_in, const uint32_t *n_out, uint32_t n_desc, uint32_t log_len, uint32_t bconv_blocks, uint32_t *launch_of,
+                        uint32_t *place_of, uint32_t *info, uint32_t max_launch) {
+  std::vector<HmBconvShape> d(n_desc);
+  for (uint32_t i = 0; i < n_desc; ++i) d[i] = HmBconvShape{n_in[i], n_out[i], false};
+  const std::vector<HmBconvLaunch> ls = hm_bconv_plan(d.data(), n_desc, log_len, bconv_blocks);
+  for (uint32_t k = 0; k < ls.size(); ++k) {
+    for (uint32_t j = 0; j < ls[k].members.size(); ++j) { launch_of[ls[k].members[j]] = k; place_of[ls[k].members[j]] = j; }
+    const uint32_t row[5] = {ls[k].n_in, ls[k].chunk, ls[k].grid[0], ls[k].grid[1], ls[k].grid[2]};
+    if (k < max_launch) memcpy(info + 5 * k, row, sizeof row);
+  }
+  return (uint32_t)ls.size();
+}
+// fused conversion + first pass (bconv_col_launch): outs / merge = the options bconv_col_outs / bconv_col_merge; writes NOUT and per descriptor its
+// kernel width; info row = {kernel key (width, + 256 packed), output groups, grid, logTiles}
+uint32_t emu_bcol_plan(const uint32_t *n_in, const uint32_t *n_out, const uint8_t *packed, uint32_t n_desc, uint32_t n_tiles, uint32_t outs, int merge, int mix,
+                       uint32_t *nout, uint32_t *kn, uint32_t *launch_of, uint32_t *place_of, uint32_t *info, uint32_t max_launch) {
+  std::vector<HmBconvShape> d(n_desc);
+  for (uint32_t i = 0; i < n_desc; ++i) d[i] = HmBconvShape{n_in[i], n_out[i], packed[i] != 0};
+  const HmBcolPlan plan = hm_bcol_plan(d.data(), n_desc, n_tiles, outs, merge != 0, mix != 0);
+  *nout = plan.NOUT;
+  for (uint32_t i = 0; i < n_desc; ++i) kn[i] = plan.kn[i];
+  for (uint32_t k = 0; k < plan.launches.size(); ++k) {
+    const HmBcolLaunch &l = plan.launches[k];
+    for (uint32_t j = 0; j < l.members.size(); ++j) { launch_of[l.members[j]] = k; place_of[l.members[j]] = j; }
+    const uint32_t row[4] = {l.key, l.groups, l.grid, l.logTiles};
+    if (k < max_launch) memcpy(info + 4 * k, row, sizeof row);
+  }
+  return (uint32_t)plan.launches.size();
+}
+// the kernel's block map (hm_bcol_block) over a whole grid: out[3 b ..] = {conversion, tile, output group} of block b
+void emu_bcol_blocks(uint32_t grid, uint32_t groups, uint32_t tile0, uint32_t log_tiles, uint32_t *out) {
+  for (uint32_t b = 0; b < grid; ++b) {
+    const HmBcolBlock k = hm_bcol_block(b, groups, tile0, log_tiles);
+    out[3 * b] = k.pi; out[3 * b + 1] = k.tile; out[3 * b + 2] = k.og;
+  }
+}
+// the input window of a fused conversion (hm_bcol_window): returns fits; base limb, and per kernel input its limb and byte offset
+int emu_bcol_window(const uint32_t *in_limbs, uint32_t n_in, uint32_t kn, uint32_t logN, uint32_t *base, uint32_t *limb, uint32_t *off) {
+  const HmBcolWindow w = hm_bcol_window(in_limbs, n_in, kn, logN);
+  *base = w.base;
+  memcpy(limb, w.limb, 4 * kn);
+  memcpy(off, w.off, 4 * kn);
+  return w.fits;
+}
+int emu_tile_range_ok(uint32_t tile0, uint32_t n_tiles, uint32_t all_tiles) { return hm_tile_range_ok(tile0, n_tiles, all_tiles); }
 // the alias test of the entry points: the first entry of (ib, il) among those with pick[i] != 0 (NULL: all) that shares an address with (ob, ol); -1: none
 int64_t emu_first_overlap(uint64_t ob, const uint32_t *ol, uint32_t no, uint64_t ib, const uint32_t *il, uint32_t ni, uint32_t N, const uint8_t *pick) {
   return hm_first_overlap(reinterpret_cast<const void *>(ob), ol, no, reinterpret_cast<const void *>(ib), il, ni, N, [&](uint32_t i) { return !pick || pick[i]; });
