@@ -125,6 +125,13 @@ def load():
     L.hm_get_counter.argtypes = [vp, C.c_char_p, C.POINTER(u64)]
     L.hm_capability.argtypes = [u32, C.c_char_p, C.POINTER(u64)]
     L.hm_comm_init_external.argtypes = [vp, i32, i32, vp, vp]
+    L.hm_slice_rows.argtypes = [vp, u32, u32, vp]
+    L.hm_limbs_to_slices.argtypes = [vp, vp, vp, vp, u32, vp]
+    L.hm_slices_to_limbs.argtypes = [vp, vp, vp, vp, vp, u32]
+    L.hm_limbs_to_colslices.argtypes = [vp, vp, vp, vp, u32, vp]
+    L.hm_colslices_to_limbs.argtypes = [vp, vp, vp, vp, vp, u32]
+    L.hm_replicate_limbs.argtypes = [vp, vp, vp, vp, u32]
+    L.hm_bconv_col.argtypes = [vp, C.POINTER(hm_bconv_desc), u32, u32, u32]
     L.hm_timer_start.argtypes = [vp]
     L.hm_timer_stop.argtypes = [vp, C.POINTER(u64)]
     _lib = L
@@ -369,8 +376,8 @@ class Context:
         k4, poi = _u32(out_ids)
         self._ck(self.L.hm_bconv(self.h, src.ptr, pil, pii, len(in_ids), dst.ptr, pol, poi, len(out_ids)))
 
-    def bconv_batch(self, probs, log_len=0):
-        """several conversions in one launch: probs = [(src, in_limbs, in_ids, dst, out_limbs, out_ids[, in_packed]), ...]"""
+    @staticmethod
+    def _bconv_descs(probs, log_len=0):
         keep, descs = [], (hm_bconv_desc * len(probs))()
         for d, (src, in_limbs, in_ids, dst, out_limbs, out_ids, *pk) in zip(descs, probs):
             arrs = [_u32(in_limbs), _u32(in_ids), _u32(out_limbs), _u32(out_ids)]
@@ -378,7 +385,18 @@ class Context:
             d.in_packed = 1 if pk and pk[0] else 0
             d.in_, d.in_limbs, d.in_ids, d.n_in = src.ptr, arrs[0][1], arrs[1][1], len(in_ids)
             d.out, d.out_limbs, d.out_ids, d.n_out, d.log_len = dst.ptr, arrs[2][1], arrs[3][1], len(out_ids), log_len
+        return keep, descs
+
+    def bconv_batch(self, probs, log_len=0):
+        """several conversions in one launch: probs = [(src, in_limbs, in_ids, dst, out_limbs, out_ids[, in_packed]), ...]"""
+        keep, descs = self._bconv_descs(probs, log_len)
         self._ck(self.L.hm_bconv_batch(self.h, descs, len(probs)))
+
+    def bconv_col(self, probs, tile0=0, n_tiles=0):
+        """conversion + first pass of the forward transform of every output, on the column tiles [tile0, tile0 + n_tiles) (n_tiles = 0: all):
+        the same `probs` tuples as bconv_batch; every dst must be the one hand-off buffer of the call (hm_bconv_col)"""
+        keep, descs = self._bconv_descs(probs)
+        self._ck(self.L.hm_bconv_col(self.h, descs, len(probs), int(tile0), int(n_tiles)))
 
     def bconv_consts(self, in_ids, out_ids):
         k1, pii = _u32(in_ids)
@@ -388,6 +406,38 @@ class Context:
         self._ck(self.L.hm_bconv_consts(self.h, pii, len(in_ids), poi, len(out_ids), qh.ctypes.data_as(C.c_void_p),
                                         tb.ctypes.data_as(C.c_void_p)))
         return qh, tb[:, :len(out_ids)]
+
+    # ---- several ranks: the exchanges around the base conversions (buffers: anything with a device address `.ptr`)
+    def comm_init_external(self, rank, world, fn):
+        """collective: every rank of the communicator calls it at the same time.  fn: an hm_exchange_fn (homulator_amd.dist.EXCHANGE_FN), kept
+        alive by this context"""
+        self._exchange_fn = fn
+        self._ck(self.L.hm_comm_init_external(self.h, int(rank), int(world), C.cast(fn, C.c_void_p), None))
+
+    def limbs_to_slices(self, buf, limbs, owners, slices):
+        k1, pl = _u32(limbs)
+        k2, po = _u32(owners)
+        self._ck(self.L.hm_limbs_to_slices(self.h, buf.ptr, pl, po, len(owners), slices.ptr))
+
+    def slices_to_limbs(self, slices, buf, limbs, owners):
+        k1, pl = _u32(limbs)
+        k2, po = _u32(owners)
+        self._ck(self.L.hm_slices_to_limbs(self.h, slices.ptr, buf.ptr, pl, po, len(owners)))
+
+    def limbs_to_colslices(self, buf, limbs, owners, slices):
+        k1, pl = _u32(limbs)
+        k2, po = _u32(owners)
+        self._ck(self.L.hm_limbs_to_colslices(self.h, buf.ptr, pl, po, len(owners), slices.ptr))
+
+    def colslices_to_limbs(self, slices, buf, limbs, owners):
+        k1, pl = _u32(limbs)
+        k2, po = _u32(owners)
+        self._ck(self.L.hm_colslices_to_limbs(self.h, slices.ptr, buf.ptr, pl, po, len(owners)))
+
+    def replicate_limbs(self, buf, limbs, owners):
+        k1, pl = _u32(limbs)
+        k2, po = _u32(owners)
+        self._ck(self.L.hm_replicate_limbs(self.h, buf.ptr, pl, po, len(owners)))
 
     def fill_uniform(self, dst, mod_ids, seed, out_limbs=None):
         k1, pol = _u32(out_limbs)
