@@ -474,6 +474,13 @@ __global__ void __launch_bounds__(256) k_tensor(HmTensorArgs a) {
   *reinterpret_cast<ulonglong2 *>(a.o2 + (size_t)lb.o2 * N + x) = r2;
 }
 
+// sum of T tensor products (hm_elem_core.h: hm_tensor_dot_thread): k_tensor's geometry — a workgroup owns 512 coefficients of one record, a thread an
+// aligned pair — with the records in a device table and T a run-time loop
+__global__ void __launch_bounds__(256) k_tensor_dot(HmTensorDotArgs a) {
+  const uint32_t logPer = a.logN - 9, entry = blockIdx.x >> logPer;
+  if (entry < a.n_limbs) hm_tensor_dot_thread(a, entry, blockIdx.x & ((1u << logPer) - 1u), threadIdx.x);
+}
+
 // 16-byte units per thread of the element-wise kernel, 512 coefficients apart, all loads in flight before the first use.  1: 89 600 workgroups for a batch of
 // ten hadd; 2 / 4 measured padd +3 / +5 %, pmult +1 %, hadd within the noise (tools/r06_ewe_ab.sh): not worth a second shape of the kernel's launch
 #ifndef HM_EWE_UNITS
@@ -1533,6 +1540,55 @@ extern "C" hm_status hm_tensor(hm_ctx *c, const uint64_t *pa, const uint32_t *la
     hipLaunchKernelGGL(k_tensor, dim3(cnt * (c->P.N / 512)), dim3(256), 0, c->stream, a);
     HM_HIP(c, hipGetLastError());
   }
+  return HM_OK;
+}
+
+// sum of n_terms tensor products: operand lists [n][n_terms], output lists [n]; one record per entry in a device table, ONE launch for any n
+extern "C" hm_status hm_tensor_dot(hm_ctx *c, const uint64_t *pa, const uint32_t *la, const uint64_t *pb, const uint32_t *lb,
+                                   const uint64_t *pc, const uint32_t *lc, const uint64_t *pd, const uint32_t *ld, uint64_t *o0,
+                                   const uint32_t *l0, uint64_t *o1, const uint32_t *l1, uint64_t *o2, const uint32_t *l2,
+                                   const uint32_t *mod_ids, uint32_t n, uint32_t n_terms) {
+  static const char *const what = "hm_tensor_dot";
+  if (!c) return HM_ERR_ARG;
+  if (!pa || !pb || !pc || !pd || !o0 || !o1 || !o2) return fail(c, HM_ERR_ARG, "%s: null buffer", what);
+  const uint32_t T = n_terms, N = c->P.N;
+  if (T == 0 || T > HM_DOT_MAX_TERMS) return fail(c, HM_ERR_ARG, "%s: n_terms = %u, must be in [1, %d]", what, T, HM_DOT_MAX_TERMS);
+  if ((uint64_t)n * T > 0xFFFFFFFFull / HM_DOT_REC_WORDS(T)) return fail(c, HM_ERR_ARG, "%s: n = %u entries of %u terms are too many for one call", what, n, T);
+  struct List { const char *name; const void *base; const uint32_t *limbs; uint32_t count; };
+  const List ins[4] = {{"a", pa, la, n * T}, {"b", pb, lb, n * T}, {"c", pc, lc, n * T}, {"d", pd, ld, n * T}};
+  const List outs[3] = {{"o0", o0, l0, n}, {"o1", o1, l1, n}, {"o2", o2, l2, n}};
+  hm_status st;
+  for (const List &l : ins)
+    if ((st = check_limbs(c, what, l.limbs, l.count))) return st;
+  for (const List &l : outs)
+    if ((st = check_limbs(c, what, l.limbs, l.count))) return st;
+  if ((st = check_mods(c, what, mod_ids, n))) return st;
+  // a workgroup stores its three outputs after ALL its loads, and the same operand limb-poly may serve several records (a ciphertext that takes
+  // part in two pairs): no output may share an address with any input or with another output
+  for (const List &o : outs)
+    for (const List &i : ins)
+      if (hm_limbs_overlap(o.base, o.limbs, o.count, i.base, i.limbs, i.count, N))
+        return fail(c, HM_ERR_ARG, "%s: an output limb-poly (%s) overlaps an input limb-poly (%s)", what, o.name, i.name);
+  {
+    std::vector<uintptr_t> starts;
+    for (const List &o : outs)
+      for (uint32_t i = 0; i < o.count; ++i) starts.push_back(reinterpret_cast<uintptr_t>(o.base) + (uintptr_t)limb_at(o.limbs, i) * N * 8);
+    std::sort(starts.begin(), starts.end());
+    for (size_t i = 1; i < starts.size(); ++i)
+      if (starts[i] - starts[i - 1] < (uintptr_t)N * 8) return fail(c, HM_ERR_ARG, "%s: two output limb-polys overlap", what);
+  }
+  if (n == 0) return HM_OK;
+  std::vector<uint32_t> recs((size_t)n * HM_DOT_REC_WORDS(T));
+  hm_tensor_dot_fill_recs(recs.data(), la, lb, lc, ld, l0, l1, l2, mod_ids, n, T);
+  HM_HIP(c, hipSetDevice(c->device));
+  HmTensorDotArgs a;
+  const void *tab = nullptr;
+  if ((st = device_table(c, recs.data(), recs.size() * sizeof(uint32_t), &tab))) return st;
+  a.rec = static_cast<const uint32_t *>(tab);
+  a.a = pa; a.b = pb; a.c = pc; a.d = pd; a.o0 = o0; a.o1 = o1; a.o2 = o2;
+  a.mods = c->d_mods; a.logN = c->P.logN; a.n_limbs = n; a.n_terms = T;
+  hipLaunchKernelGGL(k_tensor_dot, dim3(n * (N / 512)), dim3(256), 0, c->stream, a);
+  HM_HIP(c, hipGetLastError());
   return HM_OK;
 }
 

@@ -10,6 +10,7 @@
 //   K2 AUTO  InsGen::GenAUTO src/InsGen.cpp:46-71, AUTOU src/Components.cpp:173-194.
 #pragma once
 #include <cstddef>
+#include "../../include/homulator_hip.h"   // HM_TENSOR_DOT_MAX_TERMS
 #include "hm_modarith.h"
 #include "hm_ntt_core.h"
 
@@ -207,6 +208,110 @@ typedef const HmMod __attribute__((address_space(4))) *HmConstMod;
 typedef const HmMod *HmConstMod;
 #define HM_CONST_MODS(p) (p)
 #endif
+
+// Sum of T tensor products in one pass over the 4T inputs (hm_tensor_dot; HDOT):
+//   d0 = sum_t a_t b_t,  d1 = sum_t (a_t d_t + c_t b_t),  d2 = sum_t c_t d_t      with a_t = c00, b_t = c10, c_t = c01, d_t = c11 of pair t.
+// The raw 64 x 64 products are summed in three 128-bit accumulators per coefficient and each accumulator is reduced ONCE: T <= HM_DOT_MAX_TERMS = 16
+// pairs put 2T <= 32 products below 2^120 into d1's, a sum below 2^125, and hm_barrett_wide takes any 128-bit value.  One form on both arithmetic
+// back-ends: the launch streams 4T + 3 limb-polys per record and does about ten multiplies per loaded word.
+#define HM_DOT_MAX_TERMS HM_TENSOR_DOT_MAX_TERMS
+static_assert(HM_DOT_MAX_TERMS <= 16, "d1's accumulator: 2T products below 2^120 must stay below 2^128");
+// a record = HM_DOT_REC_WORDS(T) 32-bit words: modulus id, the limbs of d0, d1, d2, then (a, b, c, d) of every pair; a multiple of 16 bytes
+#define HM_DOT_REC_WORDS(T) (4u + 4u * (T))
+struct HmTensorDotArgs {
+  const uint64_t *a, *b, *c, *d;
+  uint64_t *o0, *o1, *o2;
+  const HmMod *mods;
+  const uint32_t *rec;   // device, [n_limbs][HM_DOT_REC_WORDS(n_terms)]: read through the scalar cache (wave-uniform index)
+  uint32_t logN, n_limbs, n_terms;
+};
+// The records of n entries from the entry point's limb lists (a .. d: [n][T], o0 .. o2: [n]; a null list is the identity).  Host side.
+inline void hm_tensor_dot_fill_recs(uint32_t *rec, const uint32_t *la, const uint32_t *lb, const uint32_t *lc, const uint32_t *ld, const uint32_t *l0,
+                                    const uint32_t *l1, const uint32_t *l2, const uint32_t *mod_ids, uint32_t n, uint32_t T) {
+  auto at = [](const uint32_t *l, uint32_t i) { return l ? l[i] : i; };
+  for (uint32_t i = 0; i < n; ++i) {
+    uint32_t *r = rec + (size_t)i * HM_DOT_REC_WORDS(T);
+    r[0] = mod_ids[i]; r[1] = at(l0, i); r[2] = at(l1, i); r[3] = at(l2, i);
+    for (uint32_t t = 0; t < T; ++t) {
+      const uint32_t e = i * T + t;
+      r[4 + 4 * t] = at(la, e); r[5 + 4 * t] = at(lb, e); r[6 + 4 * t] = at(lc, e); r[7 + 4 * t] = at(ld, e);
+    }
+  }
+}
+struct HmDotAcc {   // one coefficient's three sums
+  hm_u128 d0, d1, d2;
+};
+HM_HD void hm_tensor_dot_acc(HmDotAcc &s, uint64_t a, uint64_t b, uint64_t c, uint64_t d) {
+  s.d0 += (hm_u128)a * b;
+  s.d1 += (hm_u128)a * d;
+  s.d1 += (hm_u128)c * b;
+  s.d2 += (hm_u128)c * d;
+}
+// hipcc sinks loads to their first use; this keeps what was issued above it above the arithmetic below it (no instruction is emitted)
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(HM_ABL_DOT_NOPIN)   // (timing-only ablation: the loads where hipcc puts them)
+#define HM_DOT_ISSUED() __builtin_amdgcn_sched_barrier(0)
+#else
+#define HM_DOT_ISSUED() ((void)0)
+#endif
+struct HmDotPair {   // the aligned pair of coefficients a thread owns, of the four operands of one pair of ciphertexts
+  uint64_t a[2], b[2], c[2], d[2];
+};
+struct HmDotLimbs {   // the (a, b, c, d) limbs of one pair: four words of the record
+  uint32_t a, b, c, d;
+};
+template <class REC>
+HM_HD HmDotLimbs hm_tensor_dot_limbs(REC rec, uint32_t t) {
+  return HmDotLimbs{rec[4 + 4 * t], rec[5 + 4 * t], rec[6 + 4 * t], rec[7 + 4 * t]};
+}
+// four 16-byte loads from wave-uniform bases at one lane offset
+HM_HD HmDotPair hm_tensor_dot_ld(const HmTensorDotArgs &g, const HmDotLimbs &l, size_t N, uint32_t lane_bytes) {
+  HmDotPair v;
+  hm_bld2(g.a + l.a * N, lane_bytes, v.a[0], v.a[1]);
+  hm_bld2(g.b + l.b * N, lane_bytes, v.b[0], v.b[1]);
+  hm_bld2(g.c + l.c * N, lane_bytes, v.c[0], v.c[1]);
+  hm_bld2(g.d + l.d * N, lane_bytes, v.d[0], v.d[1]);
+  return v;
+}
+HM_HD void hm_tensor_dot_acc2(HmDotAcc (&s)[2], const HmDotPair &v) {
+  hm_tensor_dot_acc(s[0], v.a[0], v.b[0], v.c[0], v.d[0]);
+  hm_tensor_dot_acc(s[1], v.a[1], v.b[1], v.c[1], v.d[1]);
+}
+// thread tid of the workgroup that owns chunk `chunk` (512 coefficients) of record `entry`: the pair at chunk * 512 + 2 tid.  T is a run-time
+// loop, two pairs per round in two named register sets (no copy between them): the four loads of pair t + 1 are issued before the products of
+// pair t are formed, and the record words of a pair are requested a step before its loads (index clamped to the last pair: always inside the record).
+HM_HD void hm_tensor_dot_thread(const HmTensorDotArgs &g, uint32_t entry, uint32_t chunk, uint32_t tid) {
+  const size_t N = (size_t)1 << g.logN;
+  const uint32_t T = g.n_terms, lane_bytes = (chunk * 512u + 2u * tid) << 3;
+  const auto rec = HM_CONST_PROB_T(uint32_t, g.rec) + (size_t)entry * HM_DOT_REC_WORDS(T);
+  const HmMod m = HM_CONST_MODS(g.mods)[rec[0]];
+  HmDotAcc s[2] = {{0, 0, 0}, {0, 0, 0}};
+  HmDotPair p0 = hm_tensor_dot_ld(g, hm_tensor_dot_limbs(rec, 0), N, lane_bytes), p1;
+  HmDotLimbs l = hm_tensor_dot_limbs(rec, T > 1 ? 1u : 0u);
+  uint32_t t = 1;
+#pragma unroll 1
+  for (; t + 1 < T; t += 2) {
+    p1 = hm_tensor_dot_ld(g, l, N, lane_bytes);                  // pair t
+    l = hm_tensor_dot_limbs(rec, t + 1);
+    HM_DOT_ISSUED();
+    hm_tensor_dot_acc2(s, p0);
+    p0 = hm_tensor_dot_ld(g, l, N, lane_bytes);                  // pair t + 1
+    l = hm_tensor_dot_limbs(rec, t + 2 < T ? t + 2 : T - 1);
+    HM_DOT_ISSUED();
+    hm_tensor_dot_acc2(s, p1);
+  }
+  if (t < T) {   // (wave-uniform) an even number of pairs: one more behind the rounds
+    p1 = hm_tensor_dot_ld(g, l, N, lane_bytes);
+    HM_DOT_ISSUED();
+    hm_tensor_dot_acc2(s, p0);
+    hm_tensor_dot_acc2(s, p1);
+  } else {
+    hm_tensor_dot_acc2(s, p0);
+  }
+  hm_bst2(g.o0 + rec[1] * N, lane_bytes, hm_barrett_wide(s[0].d0, m), hm_barrett_wide(s[1].d0, m));
+  hm_bst2(g.o1 + rec[2] * N, lane_bytes, hm_barrett_wide(s[0].d1, m), hm_barrett_wide(s[1].d1, m));
+  hm_bst2(g.o2 + rec[3] * N, lane_bytes, hm_barrett_wide(s[0].d2, m), hm_barrett_wide(s[1].d2, m));
+}
+
 // The conversion table is read through the SCALAR cache: every lane of a wave needs the same entries, so they are
 // s_load'ed into SGPRs (asynchronously, no VGPRs, no LDS, no barrier) and feed v_mad_u64_u32 as scalar operands.
 // hipcc only emits scalar loads for memory it knows to be constant, hence the constant-address-space view of the

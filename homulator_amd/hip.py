@@ -22,7 +22,7 @@ SYMBOLS = [
     "hm_capture_begin", "hm_capture_end", "hm_graph_launch", "hm_graph_destroy", "hm_comm_info", "hm_slice_rows", "hm_limbs_to_slices", "hm_slices_to_limbs", "hm_replicate_limbs",
     "hm_set_option", "hm_get_counter", "hm_ntt_inner_product", "hm_exchange_stream", "hm_exchange_mark", "hm_exchange_wait",
     "hm_bconv_col", "hm_limbs_to_colslices", "hm_colslices_to_limbs", "hm_ntt_second_pass", "hm_ntt_ex", "hm_capability", "hm_inner_product_ex",
-    "hm_inner_product_hoisted", "hm_inner_product_lintrans",
+    "hm_inner_product_hoisted", "hm_inner_product_lintrans", "hm_tensor_dot",
 ]
 
 
@@ -113,6 +113,7 @@ def load():
     L.hm_ntt_sub_scale.argtypes = [vp] + [vp] * 9 + [u32, vp]
     L.hm_ntt_mix_sub_scale.argtypes = [vp, C.POINTER(hm_ntt_fused_desc)]
     L.hm_tensor.argtypes = [vp] + [vp] * 15 + [u32]
+    L.hm_tensor_dot.argtypes = [vp] + [vp] * 15 + [u32, u32]
     L.hm_inner_product.argtypes = [vp] + [vp] * 7 + [u32, u32, u32]
     L.hm_automorph.argtypes = [vp, vp, vp, vp, vp, u32, u32]
     L.hm_ewe.argtypes = [vp, i32] + [vp] * 11 + [u32, vp]
@@ -298,6 +299,14 @@ class Context:
         keep = [_u32(x) for x in ls] + [_u32(mod_ids)]
         self._ck(self.L.hm_tensor(self.h, a.ptr, keep[0][1], b.ptr, keep[1][1], c.ptr, keep[2][1], d.ptr, keep[3][1], o0.ptr, keep[4][1],
                                   o1.ptr, keep[5][1], o2.ptr, keep[6][1], keep[7][1], len(mod_ids)))
+
+    def tensor_dot(self, a, b, c, d, o0, o1, o2, mod_ids, n_terms, limbs=None):
+        """o0 = sum_t a_t * b_t, o1 = sum_t (a_t * d_t + c_t * b_t), o2 = sum_t c_t * d_t over n_terms pairs per entry (hm_tensor_dot).  limbs: the
+        seven limb lists in argument order (None: the identity), a .. d [n][n_terms], o0 .. o2 [n]; buffers: anything with a device address `.ptr`"""
+        ls = limbs or [None] * 7
+        keep = [_u32(x) for x in ls] + [_u32(mod_ids)]
+        self._ck(self.L.hm_tensor_dot(self.h, a.ptr, keep[0][1], b.ptr, keep[1][1], c.ptr, keep[2][1], d.ptr, keep[3][1], o0.ptr, keep[4][1],
+                                      o1.ptr, keep[5][1], o2.ptr, keep[6][1], keep[7][1], len(mod_ids), int(n_terms)))
 
     def inner_product(self, x, x_limbs, y, y_limbs, out, out_limbs, mod_ids, n_terms, n_out, x_galois=0):
         keep = [_u32(v) for v in (x_limbs, y_limbs, out_limbs, mod_ids)]

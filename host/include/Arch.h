@@ -126,6 +126,7 @@ private:
   bool fuseModDown = true;   // pass (9): the ModDown conversion inside the merged transform's first pass (default: by batch size)
   bool fuseHoist = true;     // pass (6h): the key products of rotations of one ciphertext read its digits once (hrotate_hoisted)
   bool fuseLintrans = true;  // pass (6l): ... and their plaintext-weighted sum is formed before anything is stored (hlintrans)
+  bool fuseDot = true;       // pass (5d): the tensor products of several pairs of ciphertexts are summed before anything is stored (hdot)
   uint32_t n = 0, logN = 0, clusterCount = 1;
   uint32_t maxLevel_ = 0, curLevel_ = 0, world_ = 1, rank_ = 0;
   uint32_t batch_ = 1;  // config key `batch`: independent ops (own inputs, shared evaluation key) carried by every launch

@@ -29,6 +29,7 @@ public:
   uint64_t constant = 0;   // per-limb constant of MUL_CONST / SUB_SCALE, or the INTT epilogue scale
   uint32_t galois = 0;
   bool passthrough = false;  // an NTT-kind instruction whose input is already in evaluation form (copy)
+  bool sumHead = false;      // a tensor product's MAC2 (d1) that is pair 1 of a SUM of tensor products (HDOT): pass (5d) starts its record here
   std::vector<uint32_t> inMods;  // BCONV: modulus ids of the inputs
   unsigned long long refInstructions = 0;  // upstream instructions this record stands for
   unsigned long long refExtra = 0;         // ... of records folded into a BCONV record (not scaled by its MAC-port count)
@@ -55,6 +56,9 @@ public:
   AddrType fSubFrom = 0, fAdd = 0;
   bool fusedTensor = false;            // MAC2 record that also produces d0 -> extraOutputs[0] and d2 -> extraOutputs[1]
   std::vector<AddrType> extraOutputs;
+  // (5d) sum of tensor products (hm_tensor_dot): a fusedTensor record that absorbed the chains behind its three outputs.  dotOperands = (c00, c10,
+  // c01, c11) of every pair, pair 1 first; OutputOperand = the final d1, extraOutputs = the final d0, d2.  Empty: a plain tensor product
+  std::vector<AddrType> dotOperands;
   // fused inner product (ops == IP): out_k = sum_j ipX[j] * ipY[k][j]; out_0 = OutputOperand, out_1 = extraOutputs[0]
   std::vector<AddrType> ipX;
   std::vector<std::vector<AddrType>> ipY;

@@ -85,9 +85,10 @@ private:
   std::array<std::vector<AddrType>, 3> d_;
 
 public:
+  // bufferPrefix / bufferSuffix: the outputs are <prefix>D<i>Out<suffix> (upstream: TensorD<i>Out; HDOT names its own)
   TensorCompute(std::string labelName, uint32_t level, Ciphertext *cipher1, Ciphertext *cipher2,
                 std::vector<AddrType> *pool, std::map<AddrType, std::vector<Instruction *>> *map, InsGen *insgen,
-                AddrManage *memoryMange);
+                AddrManage *memoryMange, const std::string &bufferPrefix = "Tensor", const std::string &bufferSuffix = "");
   const StageList &getInsMap() const { return stages; }
   const std::vector<AddrType> &d(uint32_t i) const { return d_[i]; }  // TensorD<i>Out
 };
@@ -113,7 +114,7 @@ protected:
   InsGen insgener;
   Driver driver;
   std::unique_ptr<AddrManage> addrManager;  // made by makeInputs(): the temporaries start after the inputs
-  std::vector<Ciphertext> cts;              // the input ciphertexts ct1, ct2
+  std::vector<Ciphertext> cts;              // the input ciphertexts ct1, ct2, ... (HDOT: ct1 .. ct<2T>)
   std::unique_ptr<Plaintext> ptx;           // the input plaintext pt
   std::vector<Plaintext> extPtx;            // the input plaintexts pt1, pt2, ... on the extended basis (HLINTRANS)
   Arch *arch;
@@ -185,6 +186,13 @@ class HLINTRANS : public OperationBase {
 public:
   HLINTRANS(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
 };
+// hdot (build extension): sum_t ct<2t-1> * ct<2t> over T pairs of ciphertexts (config key `terms` = T, default 4, 1..16) with ONE relinearisation
+// and ONE rescale: the tensor products are summed first (d_i = sum_t d_i,t), then HMULT's tail runs once.  Inputs ct1 .. ct<2T>, key IP_Key<k>_<j>
+// (hmult's), one output ciphertext out at level - 1.  Bit-identical to tensor + hadd of the d's + hmult's tail; terms = 1 is hmult.
+class HDOT : public OperationBase {
+public:
+  HDOT(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
+};
 class HADD : public OperationBase {
 public:
   HADD(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
@@ -208,7 +216,7 @@ class OpChain {
   std::vector<Arch *> archs;
   std::vector<OperationBase *> ops;
 public:
-  // ops: comma-separated list of hmult | hrotate | hadd | pmult | padd | hlintrans, e.g. "hmult,hrotate,hadd,hmult"; hrotate_hoisted (R output
+  // ops: comma-separated list of hmult | hrotate | hadd | pmult | padd | hlintrans | hdot, e.g. "hmult,hrotate,hadd,hmult"; hrotate_hoisted (R output
   // ciphertexts) only as the last op
   OpChain(const std::string &cfgPath, const std::string &opList, uint32_t maxLevel, uint32_t curLevel, uint32_t alpha,
           const std::map<std::string, uint32_t> &overrides = {});

@@ -65,6 +65,8 @@ inline std::vector<Read> recordReads(const Instruction &i) {
   }
   if (i.ops == BCONV_STEP2) {
     for (size_t x = 0; x + 1 < i.operandList.size(); ++x) v.push_back({i.operandList[x], Role::ConvIn, kNoDigit});
+  } else if (!i.dotOperands.empty()) {   // (5d): the operands of every pair, pair 1's (operandList) among them
+    for (AddrType a : i.dotOperands) v.push_back({a, Role::Operand, kNoDigit});
   } else if (i.ops == MULT) {
     for (int b = 0; b < 4; ++b)
       if (eweOperandMask(i.opcode) & (1 << b)) v.push_back({i.operandList[b], Role::Operand, kNoDigit});

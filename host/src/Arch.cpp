@@ -25,7 +25,8 @@ struct Arch::Launch {
   enum Kind { L_NTT, L_INTT, L_EWE, L_BCONV, L_AUTO, L_NTT_SUBSCALE, L_TENSOR, L_EXCH_IN, L_EXCH_OUT, L_REPLICATE, L_IP, L_NTT_IP,
               L_BCONV_COL, L_EXCH_IN_COL, L_EXCH_OUT_COL,   // round 4: conversion + first pass on a rank's column slice, between the transposed-domain exchanges
               L_IP_HOISTED,                                  // (6h) the key products of several rotations from one set of digits
-              L_IP_LINTRANS } kind;                          // (6l) ... and their plaintext-weighted sum
+              L_IP_LINTRANS,                                 // (6l) ... and their plaintext-weighted sum
+              L_TENSOR_DOT } kind;                           // (5d) the tensor products of several pairs of ciphertexts, summed
   std::vector<uint32_t> hoistG;   // L_IP_HOISTED: the Galois element of every rotation (a: digits [n][T], b: keys [r][n][2][T], out: [r][n][2])
                                   // L_IP_LINTRANS: the same, with c: plaintexts [r][n], d: addend source [n] / out1: addend output [n] (HM_NO_LIMB: none; both
                                   // empty: no entry has one), out: [n][2]
@@ -39,6 +40,7 @@ struct Arch::Launch {
   std::vector<uint32_t> inGalois, addGalois;   // (12) L_INTT: per limb-poly, the input / L_NTT_SUBSCALE: the addend is read through X -> X^g (0: as stored); empty: none
   uint32_t xGalois = 0;                        // (12) L_NTT_IP: the evaluation-form digits, L_IP: the x operands are read through X -> X^g
   uint32_t ipTerms = 0, ipOuts = 0;
+  uint32_t dotTerms = 0;          // L_TENSOR_DOT: pairs per record (a, b, c, d: [n][dotTerms], roles as L_TENSOR; out, out1, out2: [n])
   std::string name;
   std::string statKey;
   int opcode = 0;
@@ -130,6 +132,9 @@ Arch::Arch(Config *cfg) : config(cfg) {
   // (6l) hlintrans: those key products, the plaintext products and the sums over the rotations become one hm_inner_product_lintrans launch.
   // Config key fuse_lintrans (default 1).
   fuseLintrans = cfg->getValueOr("fuse_lintrans", 1) != 0;
+  // (5d) hdot: the tensor product of pair 1 and the multiply-accumulate chains of the further pairs become one hm_tensor_dot launch.  Config key
+  // fuse_dot (default 1).
+  fuseDot = cfg->getValueOr("fuse_dot", 1) != 0;
   // sharded runs: the exchanges of digit j+1 run on the context's exchange stream while digit j converts and transforms (SURVEY.md 7:
   // 2 beta + 2 all-to-alls per key switch instead of 4, same order on every rank).  The per-digit transforms must then stay separate
   // launches, so the fused NTT x key kernel (which needs all digits) is not used.
@@ -276,6 +281,7 @@ int partKey(const Instruction &i) {
   if (!i.ipHoistG.empty()) return 6000 + (int)i.ipX.size() * 100 + (int)i.ipHoistG.size();                 // 6000+: hoisted key product, by digits and rotations
   if (i.ops == IP && transformsInside(i)) return 400 + (int)i.ipX.size() * 10 + (int)i.ipY.size();         // 400+: transform x key, by digits and keys
   if (isKeyProduct(i)) return 300 + (int)i.ipX.size() * 10 + (int)i.ipY.size();                            // 300+: key product, by digits and keys
+  if (!i.dotOperands.empty()) return 8000 + (int)i.dotOperands.size() / 4;                                 // 8000+: sum of tensor products, by pairs
   if (i.fusedTensor) return 200;                                                                           // 200: tensor product
   if (i.fusedSubScale) return (i.fMix ? 203 : 201) + (i.fConvIn.empty() ? 0 : 4);                          // 201 / 203: fused forward transform, plain / merged; 205 / 207: with its conversion
   if (i.ops == MULT) return 100 + i.opcode;                                                                // 100+: element-wise, by opcode
@@ -400,6 +406,7 @@ struct Arch::LaunchBuilder {
   void nttIp(Launch &L, Recs recs);
   void ip(Launch &L, Recs recs);
   void tensor(Launch &L, Recs recs);
+  void tensorDot(Launch &L, Recs recs);
   void nttSubScale(Launch &L, Recs recs);
   void copy(Launch &L, Recs recs);
   void transform(Launch &L, Recs recs);
@@ -484,6 +491,21 @@ void Arch::LaunchBuilder::tensor(Launch &L, Recs recs) {
     L.mods.push_back(i->mod_id);
   }
   L.bytes = 7 * LP * recs.size();
+}
+
+// (5d) a, b, c, d = c00, c10, c01, c11 of every pair [n][T]; out, out1, out2 = d0, d1, d2 [n] (hm_tensor_dot)
+void Arch::LaunchBuilder::tensorDot(Launch &L, Recs recs) {
+  L.kind = Launch::L_TENSOR_DOT; L.statKey = "EWE";
+  L.dotTerms = (uint32_t)recs[0]->dotOperands.size() / 4;
+  for (Instruction *i : recs) {
+    for (size_t t = 0; t < L.dotTerms; ++t) {
+      L.a.push_back(limb(i->dotOperands[4 * t])); L.b.push_back(limb(i->dotOperands[4 * t + 1]));
+      L.c.push_back(limb(i->dotOperands[4 * t + 2])); L.d.push_back(limb(i->dotOperands[4 * t + 3]));
+    }
+    L.out.push_back(limb(i->extraOutputs[0])); L.out1.push_back(limb(i->OutputOperand)); L.out2.push_back(limb(i->extraOutputs[1]));
+    L.mods.push_back(i->mod_id);
+  }
+  L.bytes = (4ull * L.dotTerms + 3) * LP * recs.size();   // every operand read once, the three sums written once
 }
 
 // fused forward transform (4, 4b, 9, 12)
@@ -643,6 +665,7 @@ void Arch::LaunchBuilder::emitCompute(const Group &group, Launches &front, Launc
   else if (f->ops == IP && !f->ipHoistG.empty()) ipHoisted(*L, recs);
   else if (f->ops == IP && transformsInside(*f)) nttIp(*L, recs);
   else if (isKeyProduct(*f)) ip(*L, recs);
+  else if (!f->dotOperands.empty()) tensorDot(*L, recs);
   else if (f->fusedTensor) tensor(*L, recs);
   else if (f->fusedSubScale) nttSubScale(*L, recs);
   else if (f->ops == NTT && f->passthrough) copy(*L, recs);
@@ -1043,7 +1066,7 @@ void Arch::prepare() {
 }
 
 static const char *const kLaunchKindNames[] = {"NTT", "INTT", "EWE", "BCONV", "AUTO", "NTT_SUBSCALE", "TENSOR", "EXCH_IN", "EXCH_OUT", "REPLICATE", "IP", "NTT_IP",
-                                               "BCONV_COL", "EXCH_IN_COL", "EXCH_OUT_COL", "IP_HOISTED", "IP_LINTRANS"};
+                                               "BCONV_COL", "EXCH_IN_COL", "EXCH_OUT_COL", "IP_HOISTED", "IP_LINTRANS", "TENSOR_DOT"};
 
 // Per-launch device time (SURVEY.md §8d "per-stage hipEvent times", exchange time at N > 1): every launch of the plan
 // bracketed by its own event pair, in plan order so that the data dependencies (and, sharded, the collectives) line up.
@@ -1090,6 +1113,7 @@ std::string Arch::planText() const {
       out += " rot=" + std::to_string(l->hoistG.size()) + " g=";
       for (size_t r = 0; r < l->hoistG.size(); ++r) out += (r ? "," : "") + std::to_string(l->hoistG[r]);
     }
+    if (l->kind == Launch::L_TENSOR_DOT) out += " terms=" + std::to_string(l->dotTerms);   // (5d): pairs summed per record
     if (l->kind == Launch::L_IP_LINTRANS)   // (6l): entries that also form the addend output
       out += " addend=" + std::to_string(l->d.size() - (size_t)std::count(l->d.begin(), l->d.end(), HM_NO_LIMB));
     if (l->recordSlot >= 0) out += " mark=" + std::to_string(l->recordSlot);
@@ -1122,6 +1146,7 @@ std::string Arch::planDump() const {
            " logLen=" + std::to_string(l->logLen) + " secondOnly=" + std::to_string(l->secondOnly) + " hasK=" + std::to_string(l->hasK) + " xGalois=" + std::to_string(l->xGalois) +
            " ipTerms=" + std::to_string(l->ipTerms) + " ipOuts=" + std::to_string(l->ipOuts) + " ref=" + std::to_string(l->refInstructions) + " bytes=" + std::to_string(l->bytes) +
            " mark=" + std::to_string(l->recordSlot) + " xin=" + indexOf(l->xin) + " xout=" + indexOf(l->xout);
+    if (l->dotTerms) out += " terms=" + std::to_string(l->dotTerms);
     vec("wait", l->waitSlots); vec("hoistG", l->hoistG); vec("ipCoeff", l->ipCoeff); vec("ipInv", l->ipInv); vec("outPacked", l->outPacked);
     vec("inGalois", l->inGalois); vec("addGalois", l->addGalois);
     vec("a", l->a); vec("b", l->b); vec("c", l->c); vec("d", l->d); vec("out", l->out); vec("out1", l->out1); vec("out2", l->out2);
@@ -1200,6 +1225,10 @@ void Arch::enqueue(Launch &l) {
   case Launch::L_TENSOR:
     st = hm_tensor(ctx, pool, l.a.data(), pool, l.b.data(), pool, l.c.data(), pool, l.d.data(), pool, l.out.data(), pool, l.out1.data(), pool,
                    l.out2.data(), l.mods.data(), cnt);
+    break;
+  case Launch::L_TENSOR_DOT:
+    st = hm_tensor_dot(ctx, pool, l.a.data(), pool, l.b.data(), pool, l.c.data(), pool, l.d.data(), pool, l.out.data(), pool, l.out1.data(), pool,
+                       l.out2.data(), l.mods.data(), cnt, l.dotTerms);
     break;
   case Launch::L_EXCH_IN:
     st = hm_limbs_to_slices(ctx, pool, l.exLimbs.data(), l.exOwners.data(), (uint32_t)l.exLimbs.size(), l.slicesIn);

@@ -278,19 +278,20 @@ KeySwitch::Output KeySwitch::modDown(const Accumulators &acc, const std::string 
 // =====================================================================================================
 TensorCompute::TensorCompute(std::string labelName, uint32_t level, Ciphertext *cipher1, Ciphertext *cipher2,
                              std::vector<AddrType> *, std::map<AddrType, std::vector<Instruction *>> *, InsGen *insgen,
-                             AddrManage *memoryMange) {
+                             AddrManage *memoryMange, const std::string &bufferPrefix, const std::string &bufferSuffix) {
   const std::vector<AddrType> c00 = cipher1->getC0Addr(), c01 = cipher1->getC1Addr(), c10 = cipher2->getC0Addr(), c11 = cipher2->getC1Addr();
-  PerLimb d0{labelName + "_TensorCompute_D0_Level(", ")", range(0, level), alloc(memoryMange, "TensorD0Out", level)};  // computeD0 :624-660
+  auto buffer = [&](const char *d) { return bufferPrefix + d + "Out" + bufferSuffix; };
+  PerLimb d0{labelName + "_TensorCompute_D0_Level(", ")", range(0, level), alloc(memoryMange, buffer("D0"), level)};  // computeD0 :624-660
   d0.a = c00;
   d0.b = c10;
   stages.add("TensorCompute_INS_D0", eweLimbs(insgen, EWE_MUL, d0));
-  PerLimb d1{labelName + "_TensorCompute_D1_Level(", ")", d0.mods, alloc(memoryMange, "TensorD1Out", level)};  // computeD1 :662-699
+  PerLimb d1{labelName + "_TensorCompute_D1_Level(", ")", d0.mods, alloc(memoryMange, buffer("D1"), level)};  // computeD1 :662-699
   d1.a = c00;
   d1.b = c11;
   d1.c = c01;
   d1.d = c10;
   stages.add("TensorCompute_INS_D1", eweLimbs(insgen, EWE_MAC2, d1));
-  PerLimb d2{labelName + "_TensorCompute_D2_Level(", ")", d0.mods, alloc(memoryMange, "TensorD2Out", level)};  // computeD2 :701-739
+  PerLimb d2{labelName + "_TensorCompute_D2_Level(", ")", d0.mods, alloc(memoryMange, buffer("D2"), level)};  // computeD2 :701-739
   d2.a = c01;
   d2.b = c11;
   stages.add("TensorCompute_INS_D2", eweLimbs(insgen, EWE_MUL, d2));
@@ -685,6 +686,68 @@ HLINTRANS::HLINTRANS(std::string labelName, uint32_t maxLevel, uint32_t currentL
   finishConstruction();
 }
 
+// hdot (build extension).  out = Rescale(d0 + ks0(d2)), Rescale(d1 + ks1(d2)) with d_i = sum_t d_i,t over the T pairs (ct<2t-1>, ct<2t>): the
+// tensor product, the key switch and the rescale are linear in (d0, d1, d2), so ONE relinearisation and ONE rescale serve the whole sum.  Pair 1
+// runs TensorCompute's three stages; pair t >= 2 adds its products onto the running sums, d0 += c00 c10 and d2 += c01 c11 (MAC_ADD), d1 += c00 c11 +
+// c01 c10 (MAC2 into a per-pair temporary, then ADD); the last pair writes DotD<i>Out.  Then HMULT's tail, stage for stage.  Every sum is the
+// canonical residue of the exact integer sum: bit-identical to tensor + EWE_ADD of the d's + hmult's tail, and to hmult at T = 1.  Unfused, the
+// stages run one launch each; fused, pass (5d) of Arch::fusePasses (Planner.cpp) turns everything in front of the key switch into one launch.
+HDOT::HDOT(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch)
+    : OperationBase("HDOT", labelName, cfg, _arch, maxLevel, currentLevel, alpha) {
+  if (arch->backend() == Arch::BACKEND_SIM) throw std::runtime_error("hdot: backend = sim has no such op (the reference has no sum of products)");
+  if (arch->world() > 1) throw std::runtime_error("hdot: world > 1 is not supported (the sharded plan is not built)");
+  const uint32_t T = cfg->getValueOr("terms", 4);
+  if (T < 1 || T > 16) throw std::runtime_error("hdot: terms = " + S(T) + ", must be in [1, 16]");
+  makeInputs(2 * T);
+  auto name = [&](uint32_t i, uint32_t pair) { return "DotD" + S(i) + "Out" + (pair < T ? "_temp(" + S(pair) + ")" : ""); };   // pair: 1-based
+
+  TensorCompute tcm(labelName, currentLevel, &cts[0], &cts[1], &Datapool, &DataInsMap, &insgener, addrManager.get(), "Dot", T > 1 ? "_temp(1)" : "");
+  for (const INSGROUP &g : tcm.getInsMap().at("TensorCompute_INS_D1")) g[0]->sumHead = true;
+  dispatch(tcm.getInsMap());
+  std::array<Limbs, 3> d;
+  for (uint32_t i = 0; i < 3; ++i) d[i] = {tcm.d(i), tcm.getInsMap().at("TensorCompute_INS_D" + S(i))};
+  for (uint32_t p = 2; p <= T; ++p) {
+    const std::vector<AddrType> c00 = component(2 * p - 2, 0), c01 = component(2 * p - 2, 1), c10 = component(2 * p - 1, 0), c11 = component(2 * p - 1, 1);
+    const std::string at = "_Pair(" + S(p) + ")_Level(";
+    auto emit = [&](const std::string &key, ewe_opcode op, const PerLimb &s) {
+      Limbs out{s.out, eweLimbs(&insgener, op, s)};
+      driver.dispatchInstructions(key + "_(" + S(p) + ")", out.from);
+      return out;
+    };
+    const std::array<Limbs, 3> before = d;
+    PerLimb s0{labelName + "_Dot_D0" + at, ")", range(0, currentLevel), alloc(name(0, p), currentLevel)};   // d0 += c00 c10
+    s0.a = c00; s0.b = c10; s0.c = before[0].addr; s0.after = {&before[0].from};
+    d[0] = emit("Dot_D0", EWE_MAC_ADD, s0);
+    PerLimb m1{labelName + "_Dot_D1Mac" + at, ")", s0.mods, alloc("DotD1Mac(" + S(p) + ")", currentLevel)};   // c00 c11 + c01 c10
+    m1.a = c00; m1.b = c11; m1.c = c01; m1.d = c10;
+    const Limbs mac = emit("Dot_D1Mac", EWE_MAC2, m1);
+    PerLimb s1{labelName + "_Dot_D1" + at, ")", s0.mods, alloc(name(1, p), currentLevel)};                    // d1 += that
+    s1.a = before[1].addr; s1.c = mac.addr; s1.after = {&before[1].from, &mac.from};
+    d[1] = emit("Dot_D1", EWE_ADD, s1);
+    PerLimb s2{labelName + "_Dot_D2" + at, ")", s0.mods, alloc(name(2, p), currentLevel)};                    // d2 += c01 c11
+    s2.a = c01; s2.b = c11; s2.c = before[2].addr; s2.after = {&before[2].from};
+    d[2] = emit("Dot_D2", EWE_MAC_ADD, s2);
+  }
+
+  // HMULT's tail (HMULT::HMULT above), on the sums
+  KeySwitch ksw(labelName, maxLevel, currentLevel, alpha, d[2].addr, &Datapool, &DataInsMap, &insgener, addrManager.get());
+  dispatch(ksw.getInsMap());
+  std::array<std::vector<AddrType>, 2> sum;
+  for (uint32_t k = 0; k < 2; k++) {
+    PerLimb s{labelName + "_HMULTHadd_Level(", ")_k(" + S(k) + ")", range(0, currentLevel), alloc("HMULTHaddOutput(" + S(k) + ")", currentLevel)};
+    s.a = ksw.output()[k];
+    s.c = d[k].addr;
+    driver.dispatchInstructions("HMULT_Hadd_Key(" + S(k) + ")", eweLimbs(&insgener, EWE_ADD, s));
+    sum[k] = s.out;
+  }
+  for (uint32_t k = 0; k < 2; k++) {
+    Rescale res(labelName + "_" + S(k), currentLevel, sum[k], &Datapool, &DataInsMap, &insgener, addrManager.get());
+    dispatch(res.getInsMap());
+    setOutput("out", k, res.output());
+  }
+  finishConstruction();
+}
+
 // reference: HADD::HADD :1114-1176
 HADD::HADD(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch)
     : OperationBase("HADD", labelName, cfg, _arch, maxLevel, currentLevel, alpha) {
@@ -738,6 +801,7 @@ static OperationBase *makeOp(const std::string &o, uint32_t maxLevel, uint32_t l
   if (o == "padd") return new PADD("test_ADD", maxLevel, level, alpha, cfg, arch);
   if (o == "hrotate_hoisted") return new HROTATE_HOISTED("test_hrotate_hoisted", maxLevel, level, alpha, cfg, arch);
   if (o == "hlintrans") return new HLINTRANS("test_hlintrans", maxLevel, level, alpha, cfg, arch);
+  if (o == "hdot") return new HDOT("test_hdot", maxLevel, level, alpha, cfg, arch);
   throw std::runtime_error("Error operation requirement, please double confirm!");
 }
 

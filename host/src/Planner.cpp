@@ -50,6 +50,7 @@ struct Arch::Planner {
   void mergeRescale();     // 4b
   void residue();          // 4c
   void tensor();           // 5
+  void tensorDot();        // 5d
   void keyProduct();       // 6
   // what (6l) and (6h) both recognise: the live two-key key-product records whose digits are all automorphisms, by one element per record, of
   // the same materialised digits and are read by nothing else; per (modulus, unrotated digits) the records and their automorphisms, in stage order
@@ -80,6 +81,7 @@ void Arch::fusePasses(std::vector<Stage> &st) {
   p.mergeRescale();
   p.residue();
   p.tensor();
+  if (fuseDot) p.tensorDot();   // before (6): the multiply-accumulate chains it absorbs are not key products
   p.keyProduct();
   if (fuseLintrans) p.weightedRotations();   // before (6h): the records it merges are the ones (6h) would claim
   if (fuseHoist) p.hoist();
@@ -292,6 +294,62 @@ void Arch::Planner::tensor() {
       dead.insert(u->second);
       dead.insert(v->second);
     }
+}
+
+// (5d) sum of tensor products (hdot): behind a tensor record of (5) whose MAC2 is marked as pair 1 of a sum (sumHead), pair after pair, d0 and d2
+//      go on through ONE MAC_ADD each (d0 += c00 c10, d2 += c01 c11) and d1 through ONE ADD of a MAC2 of the same four operands
+//      (c00 c11 + c01 c10); every intermediate is read only by the next link.  The links that agree on their four operands, pair by pair, merge
+//      WITH the tensor record into one record per limb: hm_tensor_dot sums the raw products of all pairs and stores the three final sums only.
+//      Never written: the three outputs of every pair but the last, and the per-pair MAC2.  The record takes the place of the last record it
+//      absorbs in the stage list: every operand of every pair is older, every reader of the sums comes after the chains' ends.
+//      Reads: fusedTensor / extraOutputs (5).  Sets on the tensor record: dotOperands, OutputOperand, extraOutputs.
+void Arch::Planner::tensorDot() {
+  Readers rd = readers();
+  std::map<Instruction *, std::pair<size_t, size_t>> place;   // record -> (stage, position)
+  for (size_t si = 0; si < st.size(); ++si)
+    for (size_t k = 0; k < st[si].ins.size(); ++k) place[st[si].ins[k]] = {si, k};
+  std::vector<Instruction *> heads;
+  for (auto &s : st)
+    for (Instruction *i : s.ins)
+      if (live(i) && i->fusedTensor && i->sumHead && i->dotOperands.empty()) heads.push_back(i);
+  // the one live reader of `a`, if it is an element-wise record of this modulus with this opcode
+  auto next = [&](AddrType a, ewe_opcode op, uint32_t mod) -> Instruction * {
+    auto &r = rd[a];
+    return r.size() == 1 && live(r[0]) && r[0]->ops == MULT && r[0]->opcode == op && r[0]->mod_id == mod && !r[0]->fusedTensor ? r[0] : nullptr;
+  };
+  for (Instruction *c : heads) {
+    // pair 1: MAC2 operands (P, S, R, T) = (c00, c11, c01, c10)
+    c->dotOperands = {c->operandList[0], c->operandList[3], c->operandList[2], c->operandList[1]};
+    AddrType d0 = c->extraOutputs[0], d1 = c->OutputOperand, d2 = c->extraOutputs[1];
+    Instruction *last = c;
+    auto absorb = [&](Instruction *i) {
+      c->refInstructions += i->refInstructions;
+      dead.insert(i);
+      if (place[i] > place[last]) last = i;
+    };
+    while (c->dotOperands.size() / 4 < HM_TENSOR_DOT_MAX_TERMS) {
+      Instruction *m0 = next(d0, EWE_MAC_ADD, c->mod_id), *m2 = next(d2, EWE_MAC_ADD, c->mod_id), *add = next(d1, EWE_ADD, c->mod_id);
+      if (!m0 || !m2 || !add || m0->operandList[2] != d0 || m2->operandList[2] != d2) break;
+      const AddrType other = add->operandList[0] == d1 ? add->operandList[2] : add->operandList[0];
+      if ((add->operandList[0] != d1 && add->operandList[2] != d1) || other == d1) break;
+      Instruction *mac = producerOf(other);
+      if (!mac || !live(mac) || mac->ops != MULT || mac->opcode != EWE_MAC2 || mac->fusedTensor || mac->mod_id != c->mod_id || !onlyReader(rd, other, add)) break;
+      const AddrType c00 = m0->operandList[0], c10 = m0->operandList[1], c01 = m2->operandList[0], c11 = m2->operandList[1];
+      if (mac->operandList[0] != c00 || mac->operandList[1] != c11 || mac->operandList[2] != c01 || mac->operandList[3] != c10) break;
+      c->dotOperands.insert(c->dotOperands.end(), {c00, c10, c01, c11});
+      absorb(m0); absorb(m2); absorb(mac); absorb(add);
+      d0 = m0->OutputOperand; d1 = add->OutputOperand; d2 = m2->OutputOperand;
+    }
+    c->OutputOperand = d1;
+    c->extraOutputs = {d0, d2};
+    for (const Write &w : recordWrites(*c)) producer[w.addr] = c;
+    if (last != c) {   // the record moves to where its last link stood
+      auto &from = st[place[c].first].ins;
+      from.erase(std::remove(from.begin(), from.end(), c), from.end());
+      auto &to = st[place[last].first].ins;
+      std::replace(to.begin(), to.end(), last, c);
+    }
+  }
 }
 
 // (6) inner product with the evaluation key: the chain MAC2 / MAC_ADD ... of one key collapses into a single sum

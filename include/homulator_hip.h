@@ -147,6 +147,22 @@ hm_status hm_tensor(hm_ctx *ctx, const uint64_t *a, const uint32_t *a_limbs, con
                     uint64_t *o0, const uint32_t *o0_limbs, uint64_t *o1, const uint32_t *o1_limbs, uint64_t *o2,
                     const uint32_t *o2_limbs, const uint32_t *mod_ids, uint32_t n);
 
+/* K3, sum of n_terms tensor products in one pass over the 4 n_terms input polynomials (HDOT): for entry i,
+ *   o0[i] = sum_t a[i][t] * b[i][t],   o1[i] = sum_t (a[i][t] * d[i][t] + c[i][t] * b[i][t]),   o2[i] = sum_t c[i][t] * d[i][t],   t < n_terms <= 16,
+ * with the roles of hm_tensor per pair t (a = c00, b = c10, c = c01, d = c11): the tensor products of n_terms pairs of ciphertexts, summed before
+ * anything is stored.  Every residue is the canonical residue of the exact integer sum, so the result is bit-identical to hm_tensor on pair 0
+ * followed by HM_OP_MAC_ADD (o0, o2) and HM_OP_MAC2 + HM_OP_ADD (o1) per further pair, none of whose 4 (n_terms - 1) n intermediates is written;
+ * n_terms = 1 is hm_tensor.  Operand lists are row-major, a_limbs[i * n_terms + t] (the same for b, c, d); output lists have n entries.
+ * Replaces the TensorCompute stages of src/Operation.cpp:624-739 run once per pair and the additions between them.  The records live in a device
+ * table: one launch serves any n, and the call is safe under graph capture once it has run with the same lists.  HM_ERR_ARG: a null buffer,
+ * n_terms outside 1..16, a limb or modulus id out of range, an output limb-poly that overlaps (by address range, not by base pointer) an input
+ * limb-poly or another output limb-poly. */
+#define HM_TENSOR_DOT_MAX_TERMS 16
+hm_status hm_tensor_dot(hm_ctx *ctx, const uint64_t *a, const uint32_t *a_limbs, const uint64_t *b, const uint32_t *b_limbs,
+                        const uint64_t *c, const uint32_t *c_limbs, const uint64_t *d, const uint32_t *d_limbs,
+                        uint64_t *o0, const uint32_t *o0_limbs, uint64_t *o1, const uint32_t *o1_limbs, uint64_t *o2,
+                        const uint32_t *o2_limbs, const uint32_t *mod_ids, uint32_t n, uint32_t n_terms);
+
 /* K5 — inner product with the evaluation key in one pass: for limb i, out[i][k] = sum_{j < n_terms}
  * x[i][j] * y[i][k][j], k < n_out (n_terms <= 4 digits, n_out <= 2 keys).  Limb lists are row-major:
  * x_limbs[i * n_terms + j], y_limbs[(i * n_out + k) * n_terms + j], out_limbs[i * n_out + k].  Replaces
