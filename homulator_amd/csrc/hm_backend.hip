@@ -516,7 +516,7 @@ __global__ void __launch_bounds__(256) k_ewe(HmEweArgs a) {
   }
 }
 
-// K5 (hm_ip_core.h): one workgroup per 512 coefficients of an entry, in the plain, the hoisted and the weighted-sum form
+// K5 (hm_ip_core.h): one workgroup per 512 coefficients of an entry, in the plain, the hoisted, the weighted-sum and the sum-of-ciphertexts form
 template <int TERMS, int OUTS>
 __global__ void __launch_bounds__(256) k_inner_product(HmIpArgs a) {
   const uint32_t per_limb = (1u << a.logN) / HM_IP_CHUNK, entry = blockIdx.x / per_limb;
@@ -531,6 +531,11 @@ template <int TERMS>
 __global__ void __launch_bounds__(256) k_inner_product_lintrans(HmIpLinArgs a) {
   const uint32_t per_limb = (1u << a.logN) / HM_IP_CHUNK, entry = blockIdx.x / per_limb;
   if (entry < a.n_limbs) hm_ip_lintrans_thread<TERMS>(a, entry, blockIdx.x % per_limb, threadIdx.x);
+}
+template <int TERMS>
+__global__ void __launch_bounds__(256) k_inner_product_rotsum(HmIpSumArgs a) {
+  const uint32_t per_limb = (1u << a.logN) / HM_IP_CHUNK, entry = blockIdx.x / per_limb;
+  if (entry < a.n_limbs) hm_ip_rotsum_thread<TERMS>(a, entry, blockIdx.x % per_limb, threadIdx.x);
 }
 
 // One kernel per input-basis size: a single kernel switching over n_in is allocated for its largest case (140 VGPRs
@@ -1666,6 +1671,7 @@ static void (*const k_ip[HM_IP_MAX_TERMS][HM_IP_MAX_OUT])(HmIpArgs) = {{k_inner_
                                                                        {k_inner_product<3, 1>, k_inner_product<3, 2>}, {k_inner_product<4, 1>, k_inner_product<4, 2>}};
 static void (*const k_ip_hoisted[HM_IP_MAX_TERMS][1])(HmIpHoistArgs) = HM_K(k_inner_product_hoisted);
 static void (*const k_ip_lintrans[HM_IP_MAX_TERMS][1])(HmIpLinArgs) = HM_K(k_inner_product_lintrans);
+static void (*const k_ip_rotsum[HM_IP_MAX_TERMS][1])(HmIpSumArgs) = HM_K(k_inner_product_rotsum);
 #undef HM_K
 template <class Args, size_t OUTS>
 static void launch_ip(hm_ctx *c, void (*const (&kernel)[HM_IP_MAX_TERMS][OUTS])(Args), const Args &a, uint32_t T, uint32_t O = 1) {
@@ -1801,6 +1807,67 @@ extern "C" hm_status hm_inner_product_lintrans(hm_ctx *c, const hm_ip_lintrans_d
   a.mods = c->d_mods; a.logN = c->P.logN; a.n_limbs = n; a.n_rot = R;
   for (uint32_t r = 0; r < HM_IP_LINTRANS_MAX_ROT; ++r) a.galois[r] = r < R ? d->galois[r] : 1u;
   launch_ip(c, k_ip_lintrans, a, T);
+  HM_HIP(c, hipGetLastError());
+  return HM_OK;
+}
+
+// sum of rotations of different ciphertexts: one record per (ciphertext, entry), every ciphertext's outputs are ciphertext 0's
+extern "C" hm_status hm_inner_product_rotsum(hm_ctx *c, const hm_ip_rotsum_desc *d) {
+  static const char *const what = "hm_inner_product_rotsum";
+  static const hm_ip_rotsum_desc none = {};
+  if (!c) return HM_ERR_ARG;
+  if (!d) d = &none;
+  const bool anyAdd = d->addend_limbs != nullptr;
+  const char *null = nullptr;
+  if (!d->x || !d->x_limbs || !d->y || !d->y_limbs || !d->out || !d->out_limbs || !d->mod_ids || !d->galois) null = "null argument";
+  else if (anyAdd && (!d->addend || !d->addend_out || !d->addend_out_limbs)) null = "null argument (addend, addend_limbs, addend_out and addend_out_limbs go together)";
+  const uint32_t n = d->n, T = d->n_terms, G = d->n_ct, N = c->P.N;
+  const bool counts = T >= 1 && T <= HM_IP_MAX_TERMS && G >= 1 && G <= HM_IP_ROTSUM_MAX_CT;
+  std::vector<uint32_t> addSrc, addOut;   // the addend sources [n_ct][entries that carry one] and those entries' outputs
+  for (uint32_t e = 0; !null && counts && anyAdd && e < G * n; ++e) {
+    const bool has = d->addend_limbs[e] != HM_NO_LIMB;
+    if (has != (d->addend_limbs[e % n] != HM_NO_LIMB))
+      return fail(c, HM_ERR_ARG, "%s: entry %u has an addend source in some ciphertexts only", what, e % n);
+    if (has) addSrc.push_back(d->addend_limbs[e]);
+    if (has && e < n) addOut.push_back(d->addend_out_limbs[e]);
+  }
+  const uint32_t nAdd = (uint32_t)addOut.size();
+  hm_status st;
+  if ((st = ip_check(c, what, null, T, "n_ct", G, HM_IP_ROTSUM_MAX_CT, d->galois,
+                     {{d->x_limbs, G * n * T}, {d->y_limbs, G * n * 2 * T}, {d->out_limbs, n * 2}, {addSrc.data(), G * nAdd}, {addOut.data(), nAdd}},
+                     d->mod_ids, n)))
+    return st;
+  // a workgroup reads the digits and the addends at other positions than the ones it writes, and every ciphertext's keys after the first
+  // could be another workgroup's output: no output may overlap any input, and no two outputs each other
+  struct In { const char *name; const void *base; const uint32_t *limbs; uint32_t count; };
+  const In ins[3] = {{"a digit (x)", d->x, d->x_limbs, G * n * T}, {"a key limb-poly (y)", d->y, d->y_limbs, G * n * 2 * T},
+                     {"an addend source", d->addend, addSrc.data(), G * nAdd}};
+  for (const In &in : ins) {
+    if (in.count && hm_limbs_overlap(d->out, d->out_limbs, n * 2, in.base, in.limbs, in.count, N))
+      return fail(c, HM_ERR_ARG, "%s: an output limb-poly overlaps %s", what, in.name);
+    if (in.count && nAdd && hm_limbs_overlap(d->addend_out, addOut.data(), nAdd, in.base, in.limbs, in.count, N))
+      return fail(c, HM_ERR_ARG, "%s: an addend output limb-poly overlaps %s", what, in.name);
+  }
+  // the outputs among themselves: limb-polys of one base overlap when they are the same one
+  auto repeats = [](const uint32_t *l, uint32_t count) {
+    std::vector<uint32_t> v(l, l + count);
+    std::sort(v.begin(), v.end());
+    return std::adjacent_find(v.begin(), v.end()) != v.end();
+  };
+  if (repeats(d->out_limbs, n * 2) || repeats(addOut.data(), nAdd)) return fail(c, HM_ERR_ARG, "%s: two output limb-polys are the same", what);
+  if (nAdd && hm_limbs_overlap(d->out, d->out_limbs, n * 2, d->addend_out, addOut.data(), nAdd, N))
+    return fail(c, HM_ERR_ARG, "%s: an output limb-poly overlaps an addend output", what);
+  if (n == 0) return HM_OK;
+  std::vector<HmIpSumRec> recs((size_t)G * n);
+  hm_ip_fill_recs(recs.data(), d->x_limbs, d->y_limbs, d->out_limbs, (size_t)n * 2, d->mod_ids, n, T, 2, G);
+  hm_ip_fill_sum(recs.data(), d->x_limbs, d->addend_limbs, d->addend_out_limbs, n, T, G);
+  HM_HIP(c, hipSetDevice(c->device));
+  HmIpSumArgs a;
+  if ((st = ip_device_recs(c, recs, &a.rec))) return st;
+  a.x = d->x; a.y = d->y; a.addend = d->addend; a.out = d->out; a.addend_out = d->addend_out;
+  a.mods = c->d_mods; a.logN = c->P.logN; a.n_limbs = n; a.n_ct = G;
+  for (uint32_t g = 0; g < HM_IP_ROTSUM_MAX_CT; ++g) a.galois[g] = g < G ? d->galois[g] : 1u;
+  launch_ip(c, k_ip_rotsum, a, T);
   HM_HIP(c, hipGetLastError());
   return HM_OK;
 }

@@ -1,12 +1,13 @@
-// hm_ip_core.h — K5, the inner product with the evaluation key, in its three forms: plain (hm_inner_product_ex), hoisted
-// (hm_inner_product_hoisted) and the weighted sum of rotations (hm_inner_product_lintrans).
+// hm_ip_core.h — K5, the inner product with the evaluation key, in its four forms: plain (hm_inner_product_ex), hoisted
+// (hm_inner_product_hoisted), the weighted sum of rotations (hm_inner_product_lintrans) and the sum of rotations of different ciphertexts
+// (hm_inner_product_rotsum).
 // Per-thread bodies (no cross-thread state) and the records they read, shared by the HIP kernels, the entry points and the host emulator.
 // A workgroup of 256 threads covers 512 coefficients of one entry: thread tid of chunk c owns the aligned pair at c * 512 + 2 * tid.
 //
 // Reference shape: the HPIP unit (InsGen::GenHPIP src/InsGen.cpp:356-406, HPIP src/Components.cpp:571-595; in the shipped configs it runs on
 // the EWE as beta-1 MAC groups per key, KeySwitch::InnerProduceOperation src/Operation.cpp:294-414).  One pass: acc_k = sum_j x_j * y_{j,k}.
 #pragma once
-#include "../../include/homulator_hip.h"   // HM_IP_HOISTED_MAX_ROT, HM_IP_LINTRANS_MAX_ROT
+#include "../../include/homulator_hip.h"   // HM_IP_HOISTED_MAX_ROT, HM_IP_LINTRANS_MAX_ROT, HM_IP_ROTSUM_MAX_CT
 #include "hm_modarith.h"
 #include "hm_ntt_core.h"
 
@@ -29,7 +30,10 @@ struct HmIpLinRec : HmIpKeys {   // one per (rotation, entry); the digits, the a
   uint16_t pt, add_src, add_out;
   uint16_t mod, has_add, pad;
 };
-static_assert(sizeof(HmIpKeys) == 28 && sizeof(HmIpHoistRec) == 32 && sizeof(HmIpLinRec) == 40, "the device tables' record sizes");
+struct HmIpSumRec : HmIpKeys {   // one per (ciphertext, entry): its own digits, keys and addend source; the outputs and the modulus are ciphertext 0's
+  uint16_t mod, add_src, add_out, has_add;
+};
+static_assert(sizeof(HmIpKeys) == 28 && sizeof(HmIpHoistRec) == 32 && sizeof(HmIpLinRec) == 40 && sizeof(HmIpSumRec) == 36, "the device tables' record sizes");
 
 struct HmIpArgs {
   const uint64_t *x, *y;
@@ -55,6 +59,14 @@ struct HmIpLinArgs {
   uint32_t logN, n_limbs, n_rot;
   uint32_t galois[HM_IP_LINTRANS_MAX_ROT];
 };
+struct HmIpSumArgs {
+  const uint64_t *x, *y, *addend;
+  uint64_t *out, *addend_out;
+  const HmMod *mods;
+  const HmIpSumRec *rec;   // [n_ct][n_limbs]
+  uint32_t logN, n_limbs, n_ct;
+  uint32_t galois[HM_IP_ROTSUM_MAX_CT];
+};
 
 // The records of n entries x n_rot rotations, rec[r * n + i], from the entry points' limb lists: digits x [n][T], keys y [n_rot][n][K][T],
 // outputs out [n_outs / K][K] — every rotation its own (n_outs = n_rot * n * K) or all of them rotation 0's (n_outs = n * K).  Host side.
@@ -79,6 +91,14 @@ inline void hm_ip_fill_lin(HmIpLinRec *rec, const uint32_t *pt, const uint32_t *
     const size_t i = e % n;
     rec[e].pt = (uint16_t)pt[e];
     if (addend && addend[i] != HM_NO_LIMB) { rec[e].has_add = 1; rec[e].add_src = (uint16_t)addend[i]; rec[e].add_out = (uint16_t)addend_out[i]; }
+  }
+}
+// ... and what the sum over ciphertexts changes: every ciphertext has its own digits x [n_ct][n][T] and addend source [n_ct][n] (or nullptr)
+inline void hm_ip_fill_sum(HmIpSumRec *rec, const uint32_t *x, const uint32_t *addend, const uint32_t *addend_out, uint32_t n, uint32_t T, uint32_t n_ct) {
+  for (size_t e = 0; e < (size_t)n_ct * n; ++e) {
+    const size_t i = e % n;
+    for (uint32_t j = 0; j < T; ++j) rec[e].x[j] = (uint16_t)x[e * T + j];
+    if (addend && addend[e] != HM_NO_LIMB) { rec[e].has_add = 1; rec[e].add_src = (uint16_t)addend[e]; rec[e].add_out = (uint16_t)addend_out[i]; }
   }
 }
 
@@ -202,4 +222,95 @@ HM_HD void hm_ip_lintrans_thread(const HmIpLinArgs &a, uint32_t entry, uint32_t 
 #pragma unroll
   for (int k = 0; k < 2; ++k) hm_ip_st(a.out, l0.out[k], N, p, HmIpPair{hm_barrett_wide(S[k][0], m), hm_barrett_wide(S[k][1], m)});
   if (add) hm_ip_st(a.addend_out, l0.add_out, N, p, HmIpPair{hm_barrett_wide(U[0], m), hm_barrett_wide(U[1], m)});
+}
+
+// sum of rotations of n_ct DIFFERENT ciphertexts, sum_c (the key product of ciphertext c through sigma_c), formed before anything is stored: the
+// gather form again.  A thread owns the aligned pair p of the outputs; ciphertext by ciphertext it loads every digit's pair at the
+// automorphism's source of p, both keys at p, and adds the RAW 64 x 64 products to one 128-bit accumulator per key and word: n_ct * TERMS <=
+// 64 products below 2^120 stay below 2^126, and each accumulator is reduced ONCE (hm_barrett_wide takes any 128-bit value).  Entries with
+// addend sources (the Q limbs: every ciphertext's c0) gather them at the same source; at most 16 residues below 2^60 sum to below 2^64.
+template <int TERMS>
+struct HmIpSumOps {   // what one ciphertext brings to the thread's pair
+  HmIpPair x[TERMS], y[2][TERMS], c;
+  bool swap;
+};
+template <int TERMS>
+HM_HD void hm_ip_rotsum_ld(HmIpSumOps<TERMS> &v, const HmIpSumArgs &a, uint32_t c, uint32_t entry, uint32_t p, bool add) {
+  const uint32_t N = 1u << a.logN;
+  const HmIpSumRec &lb = a.rec[(size_t)c * a.n_limbs + entry];
+  const uint32_t sp = hm_auto_pair(p, a.galois[c], a.logN, v.swap);
+#pragma unroll
+  for (int j = 0; j < TERMS; ++j) v.x[j] = hm_ip_ld(a.x, lb.x[j], N, sp);
+#pragma unroll
+  for (int k = 0; k < 2; ++k)
+#pragma unroll
+    for (int j = 0; j < TERMS; ++j) v.y[k][j] = hm_ip_ld(a.y, lb.y[k][j], N, p);
+  v.c = add ? hm_ip_ld(a.addend, lb.add_src, N, sp) : HmIpPair{0, 0};
+}
+template <int TERMS>
+HM_HD void hm_ip_rotsum_acc(hm_u128 (&S)[2][2], uint64_t (&U)[2], const HmIpSumOps<TERMS> &v) {
+#pragma unroll
+  for (int j = 0; j < TERMS; ++j) {
+    const uint64_t x0 = v.swap ? v.x[j].y : v.x[j].x, x1 = v.swap ? v.x[j].x : v.x[j].y;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      S[k][0] += (hm_u128)x0 * v.y[k][j].x;
+      S[k][1] += (hm_u128)x1 * v.y[k][j].y;
+    }
+  }
+  U[0] += v.swap ? v.c.y : v.c.x;
+  U[1] += v.swap ? v.c.x : v.c.y;
+}
+// HM_IP_ROTSUM_AHEAD = 1: the loads of ciphertext c + 1 are issued before the products of ciphertext c are formed, in two named register sets
+// (no copy between them), kept above the arithmetic as hm_tensor_dot_thread keeps its own; 0: one ciphertext at a time, the loads where hipcc
+// puts them.  The faster form on the MI355X is the default (DESIGN.md section 14 records both).
+#ifndef HM_IP_ROTSUM_AHEAD
+#define HM_IP_ROTSUM_AHEAD 0
+#endif
+#if defined(__HIP_DEVICE_COMPILE__) && HM_IP_ROTSUM_AHEAD
+#define HM_IP_ROTSUM_ISSUED() __builtin_amdgcn_sched_barrier(0)
+#else
+#define HM_IP_ROTSUM_ISSUED() ((void)0)
+#endif
+template <int TERMS>
+HM_HD void hm_ip_rotsum_thread(const HmIpSumArgs &a, uint32_t entry, uint32_t chunk, uint32_t tid) {
+  const uint32_t N = 1u << a.logN;
+  const HmIpSumRec &l0 = a.rec[entry];
+  const HmMod m = a.mods[l0.mod];
+  const bool add = l0.has_add != 0;   // workgroup-uniform, the same for every ciphertext of the entry
+  const uint32_t p = chunk * HM_IP_CHUNK + 2 * tid, G = a.n_ct;
+  hm_u128 S[2][2] = {{0, 0}, {0, 0}};
+  uint64_t U[2] = {0, 0};
+  HmIpSumOps<TERMS> v0;
+#if HM_IP_ROTSUM_AHEAD
+  HmIpSumOps<TERMS> v1;
+  hm_ip_rotsum_ld(v0, a, 0, entry, p, add);
+  uint32_t c = 1;
+#pragma unroll 1
+  for (; c + 1 < G; c += 2) {
+    hm_ip_rotsum_ld(v1, a, c, entry, p, add);
+    HM_IP_ROTSUM_ISSUED();
+    hm_ip_rotsum_acc(S, U, v0);
+    hm_ip_rotsum_ld(v0, a, c + 1, entry, p, add);
+    HM_IP_ROTSUM_ISSUED();
+    hm_ip_rotsum_acc(S, U, v1);
+  }
+  if (c < G) {   // (wave-uniform) an even number of ciphertexts: one more behind the rounds
+    hm_ip_rotsum_ld(v1, a, c, entry, p, add);
+    HM_IP_ROTSUM_ISSUED();
+    hm_ip_rotsum_acc(S, U, v0);
+    hm_ip_rotsum_acc(S, U, v1);
+  } else {
+    hm_ip_rotsum_acc(S, U, v0);
+  }
+#else
+#pragma unroll 1
+  for (uint32_t c = 0; c < G; ++c) {
+    hm_ip_rotsum_ld(v0, a, c, entry, p, add);
+    hm_ip_rotsum_acc(S, U, v0);
+  }
+#endif
+#pragma unroll
+  for (int k = 0; k < 2; ++k) hm_ip_st(a.out, l0.out[k], N, p, HmIpPair{hm_barrett_wide(S[k][0], m), hm_barrett_wide(S[k][1], m)});
+  if (add) hm_ip_st(a.addend_out, l0.add_out, N, p, HmIpPair{hm_barrett(U[0], m), hm_barrett(U[1], m)});
 }

@@ -22,7 +22,7 @@ SYMBOLS = [
     "hm_capture_begin", "hm_capture_end", "hm_graph_launch", "hm_graph_destroy", "hm_comm_info", "hm_slice_rows", "hm_limbs_to_slices", "hm_slices_to_limbs", "hm_replicate_limbs",
     "hm_set_option", "hm_get_counter", "hm_ntt_inner_product", "hm_exchange_stream", "hm_exchange_mark", "hm_exchange_wait",
     "hm_bconv_col", "hm_limbs_to_colslices", "hm_colslices_to_limbs", "hm_ntt_second_pass", "hm_ntt_ex", "hm_capability", "hm_inner_product_ex",
-    "hm_inner_product_hoisted", "hm_inner_product_lintrans", "hm_tensor_dot",
+    "hm_inner_product_hoisted", "hm_inner_product_lintrans", "hm_inner_product_rotsum", "hm_tensor_dot",
 ]
 
 
@@ -48,6 +48,13 @@ class hm_ip_lintrans_desc(C.Structure):
                 ("addend", C.c_void_p), ("addend_limbs", C.c_void_p), ("out", C.c_void_p), ("out_limbs", C.c_void_p),
                 ("addend_out", C.c_void_p), ("addend_out_limbs", C.c_void_p), ("mod_ids", C.c_void_p),
                 ("n", C.c_uint32), ("n_terms", C.c_uint32), ("n_rot", C.c_uint32), ("galois", C.c_void_p)]
+
+
+class hm_ip_rotsum_desc(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("x_limbs", C.c_void_p), ("y", C.c_void_p), ("y_limbs", C.c_void_p),
+                ("addend", C.c_void_p), ("addend_limbs", C.c_void_p), ("out", C.c_void_p), ("out_limbs", C.c_void_p),
+                ("addend_out", C.c_void_p), ("addend_out_limbs", C.c_void_p), ("mod_ids", C.c_void_p),
+                ("n", C.c_uint32), ("n_terms", C.c_uint32), ("n_ct", C.c_uint32), ("galois", C.c_void_p)]
 
 
 class hm_ntt_ip_desc(C.Structure):
@@ -110,6 +117,7 @@ def load():
     L.hm_inner_product_ex.argtypes = [vp, C.POINTER(hm_ip_desc)]
     L.hm_inner_product_hoisted.argtypes = [vp, C.POINTER(hm_ip_hoisted_desc)]
     L.hm_inner_product_lintrans.argtypes = [vp, C.POINTER(hm_ip_lintrans_desc)]
+    L.hm_inner_product_rotsum.argtypes = [vp, C.POINTER(hm_ip_rotsum_desc)]
     L.hm_ntt_sub_scale.argtypes = [vp] + [vp] * 9 + [u32, vp]
     L.hm_ntt_mix_sub_scale.argtypes = [vp, C.POINTER(hm_ntt_fused_desc)]
     L.hm_tensor.argtypes = [vp] + [vp] * 15 + [u32]
@@ -335,6 +343,17 @@ class Context:
         d = hm_ip_lintrans_desc(x.ptr, keep[0][1], y.ptr, keep[1][1], pt.ptr, keep[2][1], ptr(addend), keep[3][1], out.ptr, keep[4][1],
                                 ptr(addend_out), keep[5][1], keep[6][1], len(mod_ids), n_terms, len(galois), keep[7][1])
         self._ck(self.L.hm_inner_product_lintrans(self.h, C.byref(d)))
+
+    def inner_product_rotsum(self, x, x_limbs, y, y_limbs, out, out_limbs, mod_ids, n_terms, galois,
+                             addend=None, addend_limbs=None, addend_out=None, addend_out_limbs=None):
+        """out[i][k] = sum_c sum_j automorph_{galois[c]}(x[c][i][j]) * y[c][i][k][j], k < 2, and for the entries with addend sources
+        (addend_limbs[c][i] != NO_LIMB) addend_out[i] = sum_c automorph_{galois[c]}(addend[c][i]) (hm_inner_product_rotsum).  Limb lists:
+        x_limbs [c][n][n_terms], y_limbs [c][n][2][n_terms], out_limbs [n][2], addend_limbs [c][n], addend_out_limbs [n]"""
+        keep = [_u32(v) for v in (x_limbs, y_limbs, addend_limbs, out_limbs, addend_out_limbs, mod_ids, galois)]
+        ptr = lambda v: None if v is None else v.ptr
+        d = hm_ip_rotsum_desc(x.ptr, keep[0][1], y.ptr, keep[1][1], ptr(addend), keep[2][1], out.ptr, keep[3][1],
+                              ptr(addend_out), keep[4][1], keep[5][1], len(mod_ids), n_terms, len(galois), keep[6][1])
+        self._ck(self.L.hm_inner_product_rotsum(self.h, C.byref(d)))
 
     def ntt_second_pass(self, buf, mod_ids, inverse=False, limbs=None, scale=None):
         """the last pass of transforms whose first pass another call has already run into `buf` (in place)"""

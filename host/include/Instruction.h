@@ -79,6 +79,12 @@ public:
   // (the Q limbs): extraOutputs[1] = sum_r ipLinPt[r] * sigma_r(ipLinAddend).  ipLinPt empty: no weighted sum
   std::vector<AddrType> ipLinPt;
   AddrType ipLinAddend = 0;
+  // (6s) sum of the key products of rotations of DIFFERENT ciphertexts (hm_inner_product_rotsum): ciphertext c reads its own unrotated digits
+  // ipSumX[c] (ipSumX[0] == ipX) through X -> X^ipHoistG[c] with keys ipY[2c + k], and the sum over c is formed before it is stored:
+  // OutputOperand = S_0, extraOutputs[0] = S_1.  ipSumAddend non-empty (the Q limbs): extraOutputs[1] = sum_c sigma_c(ipSumAddend[c]).
+  // ipSumX empty: no such sum
+  std::vector<std::vector<AddrType>> ipSumX;
+  std::vector<AddrType> ipSumAddend;
   std::vector<Instruction *> depsInsList;
 
   Instruction(std::string name, ins_ops op, uint32_t level) : ops(op), Name(std::move(name)), level_id(level) {}

@@ -73,7 +73,8 @@ public:
   const Output &output() const { return out_; }                         // of upstream's constructor
 
   // inputMayBeOpInput: the input may be an op's own input ciphertext, which no instruction produces (otherwise a limb without producer throws)
-  Digits modUp(const std::vector<AddrType> &input, bool inputMayBeOpInput);
+  // suffix: on every buffer and stage key, for the ops that run more than one ModUp (HROTSUM: "_Ct<i>" from the second ciphertext on)
+  Digits modUp(const std::vector<AddrType> &input, bool inputMayBeOpInput, const std::string &suffix = "");
   Digits rotateDigits(const Digits &digits, uint32_t galois, const std::string &suffix);
   Accumulators keyProduct(const Digits &digits, uint64_t keySeed, const std::string &suffix);  // keySeed: the synthetic stream of the key
   Output modDown(const Accumulators &acc, const std::string &suffix);
@@ -114,7 +115,7 @@ protected:
   InsGen insgener;
   Driver driver;
   std::unique_ptr<AddrManage> addrManager;  // made by makeInputs(): the temporaries start after the inputs
-  std::vector<Ciphertext> cts;              // the input ciphertexts ct1, ct2, ... (HDOT: ct1 .. ct<2T>)
+  std::vector<Ciphertext> cts;              // the input ciphertexts ct1, ct2, ... (HDOT: ct1 .. ct<2T>, HROTSUM: ct1 .. ct<G>)
   std::unique_ptr<Plaintext> ptx;           // the input plaintext pt
   std::vector<Plaintext> extPtx;            // the input plaintexts pt1, pt2, ... on the extended basis (HLINTRANS)
   Arch *arch;
@@ -132,7 +133,8 @@ protected:
   // (seed + 4000) at the current level, then `extPlaintexts` plaintexts pt<r>, r = 1.., on the extended basis (the current level's Q limbs, then
   // the alpha special primes; seed + 4000 + 100000 r), then the address plan of the temporaries behind them
   void makeInputs(uint32_t ciphertexts, bool plaintext = false, uint32_t extPlaintexts = 0);
-  // what the ops that hoist the ModUp over rotations (HROTATE_HOISTED, HLINTRANS; `op` names the op in the messages) check first: no backend = sim,
+  // what the ops that hoist the ModUp over rotations (HROTATE_HOISTED, HLINTRANS) or sum rotations in front of one ModDown (HROTSUM) check
+  // first (`op` names the op in the messages): no backend = sim,
   // no world > 1; config keys `rotations` = R (default 4, 1..16) and `galois` = g (default 5, odd, below 2N).  Returns g^r mod 2N, r = 1..R, distinct
   std::vector<uint32_t> hoistedRotations(const std::string &op) const;
   std::vector<AddrType> alloc(const std::string &name, uint32_t limbs);  // MallocMem + getAddr
@@ -141,7 +143,7 @@ protected:
   void dispatch(const StageList &m);
   // the two halves of a rotation around its key switch, shared by HROTATE (suffix "") and HROTATE_HOISTED ("_Rot<r>"): sigma_g of component k
   // of ct1 into AUTOOutput<suffix>(k); and <out>.c0 = sigma_g(c0) + ks0, <out>.c1 = ks1
-  Limbs rotateComponent(uint32_t k, uint32_t galois, const std::string &suffix);
+  Limbs rotateComponent(uint32_t k, uint32_t galois, const std::string &suffix, uint32_t ct = 0);   // ct: of input ciphertext ct<ct + 1>
   void finishRotation(const std::string &out, const std::vector<AddrType> &rotatedC0, const KeySwitch::Output &ks, const std::string &suffix);
   void finishConstruction();  // registers every temporary with the backend
 
@@ -193,6 +195,13 @@ class HDOT : public OperationBase {
 public:
   HDOT(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
 };
+// hrotsum (build extension): sum_i rot_{g^i}(ct<i>) over G DIFFERENT ciphertexts (config keys rotations = G and galois = g as hrotate_hoisted, same
+// keys IP_Rot<i>_Key<k>_<j>), with G ModUps and ONE ModDown: the key products are summed on the extended basis.  One output ciphertext out at the
+// inputs' level; no rescale.
+class HROTSUM : public OperationBase {
+public:
+  HROTSUM(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
+};
 class HADD : public OperationBase {
 public:
   HADD(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
@@ -216,7 +225,7 @@ class OpChain {
   std::vector<Arch *> archs;
   std::vector<OperationBase *> ops;
 public:
-  // ops: comma-separated list of hmult | hrotate | hadd | pmult | padd | hlintrans | hdot, e.g. "hmult,hrotate,hadd,hmult"; hrotate_hoisted (R output
+  // ops: comma-separated list of hmult | hrotate | hadd | pmult | padd | hlintrans | hdot | hrotsum, e.g. "hmult,hrotate,hadd,hmult"; hrotate_hoisted (R output
   // ciphertexts) only as the last op
   OpChain(const std::string &cfgPath, const std::string &opList, uint32_t maxLevel, uint32_t curLevel, uint32_t alpha,
           const std::map<std::string, uint32_t> &overrides = {});

@@ -28,6 +28,7 @@ enum class Role {
   Key,            // key product: evaluation-key limb
   LinPlain,       // weighted sum of hoisted key products (6l): a rotation's plaintext limb
   LinAddend,      // ... the addend source, read through every rotation's automorphism (the unrotated c0)
+  SumAddend,      // sum of rotations of different ciphertexts (6s): a ciphertext's addend source, read through its automorphism (its unrotated c0)
   Minuend, Addend, Mix,   // fused forward transform (4, 4b)
   EpiSub, EpiAdd,         // conversion with the element-wise epilogue (10): fSubFrom, fAdd
   ReplacedIn      // the transform input operandList[0] that the fused conversion fConvIn replaces (9): never written, never loaded
@@ -57,10 +58,13 @@ inline std::vector<Read> recordReads(const Instruction &i) {
     for (size_t j = 0; j < src.size(); ++j)
       if (converted(j))
         for (size_t x = 1; x < i.ipConvIn[j].size(); ++x) v.push_back({i.ipConvIn[j][x], Role::ConvIn, j});
+    for (size_t c = 1; c < i.ipSumX.size(); ++c)   // (6s): the digits of the further ciphertexts, behind the first one's (ipX, above)
+      for (size_t j = 0; j < i.ipSumX[c].size(); ++j) v.push_back({i.ipSumX[c][j], Role::IpDigit, j});
     for (auto &y : i.ipY)
       for (AddrType a : y) v.push_back({a, Role::Key, kNoDigit});
     for (AddrType a : i.ipLinPt) v.push_back({a, Role::LinPlain, kNoDigit});
     if (i.ipLinAddend) v.push_back({i.ipLinAddend, Role::LinAddend, kNoDigit});
+    for (AddrType a : i.ipSumAddend) v.push_back({a, Role::SumAddend, kNoDigit});
     return v;
   }
   if (i.ops == BCONV_STEP2) {

@@ -26,7 +26,8 @@ struct Arch::Launch {
               L_BCONV_COL, L_EXCH_IN_COL, L_EXCH_OUT_COL,   // round 4: conversion + first pass on a rank's column slice, between the transposed-domain exchanges
               L_IP_HOISTED,                                  // (6h) the key products of several rotations from one set of digits
               L_IP_LINTRANS,                                 // (6l) ... and their plaintext-weighted sum
-              L_TENSOR_DOT } kind;                           // (5d) the tensor products of several pairs of ciphertexts, summed
+              L_TENSOR_DOT,                                  // (5d) the tensor products of several pairs of ciphertexts, summed
+              L_IP_ROTSUM } kind;                            // (6s) the key products of rotations of different ciphertexts, summed
   std::vector<uint32_t> hoistG;   // L_IP_HOISTED: the Galois element of every rotation (a: digits [n][T], b: keys [r][n][2][T], out: [r][n][2])
                                   // L_IP_LINTRANS: the same, with c: plaintexts [r][n], d: addend source [n] / out1: addend output [n] (HM_NO_LIMB: none; both
                                   // empty: no entry has one), out: [n][2]
@@ -40,6 +41,8 @@ struct Arch::Launch {
   std::vector<uint32_t> inGalois, addGalois;   // (12) L_INTT: per limb-poly, the input / L_NTT_SUBSCALE: the addend is read through X -> X^g (0: as stored); empty: none
   uint32_t xGalois = 0;                        // (12) L_NTT_IP: the evaluation-form digits, L_IP: the x operands are read through X -> X^g
   uint32_t ipTerms = 0, ipOuts = 0;
+                                  // L_IP_ROTSUM: hoistG = the element of every ciphertext; a: digits [c][n][T], b: keys [c][n][2][T], d: addend sources
+                                  // [c][n] / out1: addend output [n] (HM_NO_LIMB: none; both empty: no entry has one), out: [n][2]
   uint32_t dotTerms = 0;          // L_TENSOR_DOT: pairs per record (a, b, c, d: [n][dotTerms], roles as L_TENSOR; out, out1, out2: [n])
   std::string name;
   std::string statKey;
@@ -135,6 +138,9 @@ Arch::Arch(Config *cfg) : config(cfg) {
   // (5d) hdot: the tensor product of pair 1 and the multiply-accumulate chains of the further pairs become one hm_tensor_dot launch.  Config key
   // fuse_dot (default 1).
   fuseDot = cfg->getValueOr("fuse_dot", 1) != 0;
+  // (6s) hrotsum: the key products of rotations of different ciphertexts, the sums over the ciphertexts and the rotated c0's become one
+  // hm_inner_product_rotsum launch.  Config key fuse_rotsum (default 1).
+  fuseRotsum = cfg->getValueOr("fuse_rotsum", 1) != 0;
   // sharded runs: the exchanges of digit j+1 run on the context's exchange stream while digit j converts and transforms (SURVEY.md 7:
   // 2 beta + 2 all-to-alls per key switch instead of 4, same order on every rank).  The per-digit transforms must then stay separate
   // launches, so the fused NTT x key kernel (which needs all digits) is not used.
@@ -277,7 +283,9 @@ typedef std::vector<const Part *> Group;
 
 // records of one stage with equal keys go into one C-ABI call (same kind / opcode / direction / operand shape)
 int partKey(const Instruction &i) {
+  if (!i.ipSumX.empty()) return 9000 + (int)i.ipX.size() * 100 + (int)i.ipSumX.size();                     // 9000+: sum of rotations of different ciphertexts, by digits and ciphertexts
   if (!i.ipLinPt.empty()) return 7000 + (int)i.ipX.size() * 100 + (int)i.ipHoistG.size();                  // 7000+: weighted sum of hoisted key products, by digits and rotations
+  if (i.ipHoistG.size() == 1) return 20000 + (int)i.ipX.size() + 8 * (int)i.ipHoistG[0];                   // 20000+: hoisted key product of ONE rotation, by digits and element (hrotsum with fuse_rotsum = 0: one per ciphertext)
   if (!i.ipHoistG.empty()) return 6000 + (int)i.ipX.size() * 100 + (int)i.ipHoistG.size();                 // 6000+: hoisted key product, by digits and rotations
   if (i.ops == IP && transformsInside(i)) return 400 + (int)i.ipX.size() * 10 + (int)i.ipY.size();         // 400+: transform x key, by digits and keys
   if (isKeyProduct(i)) return 300 + (int)i.ipX.size() * 10 + (int)i.ipY.size();                            // 300+: key product, by digits and keys
@@ -403,6 +411,7 @@ struct Arch::LaunchBuilder {
   void wrapShardedConversion(LaunchPtr L, Recs recs, Launches &front, Launches &back);
   void ipHoisted(Launch &L, Recs recs);
   void ipLintrans(Launch &L, Recs recs);
+  void ipRotsum(Launch &L, Recs recs);
   void nttIp(Launch &L, Recs recs);
   void ip(Launch &L, Recs recs);
   void tensor(Launch &L, Recs recs);
@@ -445,6 +454,32 @@ void Arch::LaunchBuilder::ipLintrans(Launch &L, Recs recs) {
   // limb-polys touched: the digits and the addend source once (every rotation gathers from the same ones), keys and plaintext once per rotation,
   // two outputs per entry and one per addend
   L.bytes = ((unsigned long long)recs.size() * (L.ipTerms + 2 * R * L.ipTerms + R + 2) + (unsigned long long)addends * 2) * LP;
+}
+
+// (6s) one sum of rotations of different ciphertexts: digits a [c][n][T], keys b [c][n][2][T], outputs out [n][2]; entries with addends: sources
+// d [c][n], output out1 [n] (hm_ip_rotsum_desc)
+void Arch::LaunchBuilder::ipRotsum(Launch &L, Recs recs) {
+  Instruction *f = recs[0];
+  L.kind = Launch::L_IP_ROTSUM; L.statKey = "EWE";
+  L.ipTerms = (uint32_t)f->ipX.size(); L.ipOuts = 2; L.hoistG = f->ipHoistG;
+  const size_t G = f->ipSumX.size();
+  size_t addends = 0;
+  for (Instruction *i : recs) addends += !i->ipSumAddend.empty();
+  for (Instruction *i : recs) {
+    if (i->ipHoistG != L.hoistG) throw std::runtime_error("sum of rotations: the records of one launch rotate by different elements");
+    L.mods.push_back(i->mod_id);
+    L.out.push_back(limb(i->OutputOperand)); L.out.push_back(limb(i->extraOutputs[0]));
+    if (addends) L.out1.push_back(i->ipSumAddend.empty() ? HM_NO_LIMB : limb(i->extraOutputs[1]));
+  }
+  for (size_t c = 0; c < G; ++c)
+    for (Instruction *i : recs) {
+      for (AddrType x : i->ipSumX[c]) L.a.push_back(limb(x));
+      for (size_t k = 0; k < 2; ++k)
+        for (AddrType y : i->ipY[c * 2 + k]) L.b.push_back(limb(y));
+      if (addends) L.d.push_back(i->ipSumAddend.empty() ? HM_NO_LIMB : limb(i->ipSumAddend[c]));
+    }
+  // limb-polys touched: every ciphertext's digits, keys and addend source once, two outputs per entry and one per entry with addends
+  L.bytes = ((unsigned long long)recs.size() * (G * 3 * L.ipTerms + 2) + (unsigned long long)addends * (G + 1)) * LP;
 }
 
 // transform x key on one GPU (7, 8, 7b): a = source, c = first-pass scratch of every (limb, digit); the digits' conversions as `probs`
@@ -661,7 +696,8 @@ void Arch::LaunchBuilder::emitCompute(const Group &group, Launches &front, Launc
     for (const Part *g : group) for (int sl : slotsOf(g)) addUnique(L->waitSlots, sl);
   for (const Part *g : group) L->name += (L->name.empty() ? "" : "+") + g->name;
   for (Instruction *i : recs) L->refInstructions += i->refInstructions * (i->ops == BCONV_STEP2 ? bconvPorts : 1ull) + i->refExtra;
-  if (f->ops == IP && !f->ipLinPt.empty()) ipLintrans(*L, recs);
+  if (f->ops == IP && !f->ipSumX.empty()) ipRotsum(*L, recs);
+  else if (f->ops == IP && !f->ipLinPt.empty()) ipLintrans(*L, recs);
   else if (f->ops == IP && !f->ipHoistG.empty()) ipHoisted(*L, recs);
   else if (f->ops == IP && transformsInside(*f)) nttIp(*L, recs);
   else if (isKeyProduct(*f)) ip(*L, recs);
@@ -913,7 +949,7 @@ void Arch::replicateForBatch() {
       l->bytes *= batch_;
       continue;
     }
-    if (l->kind == Launch::L_IP_HOISTED || l->kind == Launch::L_IP_LINTRANS) {
+    if (l->kind == Launch::L_IP_HOISTED || l->kind == Launch::L_IP_LINTRANS || l->kind == Launch::L_IP_ROTSUM) {
       // entry-major as the inner product below (the ops of a batch share the keys), inside every rotation's block of keys and outputs
       const size_t n0 = l->mods.size();
       auto inter = [&](std::vector<uint32_t> &v, size_t blocks, size_t width, bool isLimb) {
@@ -928,9 +964,12 @@ void Arch::replicateForBatch() {
         v.swap(o);
       };
       const size_t R = l->hoistG.size();
-      inter(l->a, 1, l->ipTerms, true); inter(l->b, R, 2 * (size_t)l->ipTerms, true); inter(l->mods, 1, 1, false);
+      inter(l->a, l->kind == Launch::L_IP_ROTSUM ? R : 1, l->ipTerms, true); inter(l->b, R, 2 * (size_t)l->ipTerms, true); inter(l->mods, 1, 1, false);
       if (l->kind == Launch::L_IP_HOISTED) inter(l->out, R, 2, true);
-      else {
+      else if (l->kind == Launch::L_IP_ROTSUM) {   // every ciphertext its own digits and addend source
+        inter(l->out, 1, 2, true);
+        if (!l->d.empty()) { inter(l->d, R, 1, true); inter(l->out1, 1, 1, true); }
+      } else {
         inter(l->out, 1, 2, true); inter(l->c, R, 1, true);
         if (!l->d.empty()) { inter(l->d, 1, 1, true); inter(l->out1, 1, 1, true); }
       }
@@ -1066,7 +1105,7 @@ void Arch::prepare() {
 }
 
 static const char *const kLaunchKindNames[] = {"NTT", "INTT", "EWE", "BCONV", "AUTO", "NTT_SUBSCALE", "TENSOR", "EXCH_IN", "EXCH_OUT", "REPLICATE", "IP", "NTT_IP",
-                                               "BCONV_COL", "EXCH_IN_COL", "EXCH_OUT_COL", "IP_HOISTED", "IP_LINTRANS", "TENSOR_DOT"};
+                                               "BCONV_COL", "EXCH_IN_COL", "EXCH_OUT_COL", "IP_HOISTED", "IP_LINTRANS", "TENSOR_DOT", "IP_ROTSUM"};
 
 // Per-launch device time (SURVEY.md §8d "per-stage hipEvent times", exchange time at N > 1): every launch of the plan
 // bracketed by its own event pair, in plan order so that the data dependencies (and, sharded, the collectives) line up.
@@ -1095,7 +1134,9 @@ std::string Arch::planText() const {
   for (const auto &l : launches) {
     size_t cnt = l->out.size();
     if (l->kind == Launch::L_BCONV || l->kind == Launch::L_BCONV_COL) { cnt = 0; for (auto &q : l->probs) cnt += q.out.size(); }
-    if (l->kind == Launch::L_IP || l->kind == Launch::L_NTT_IP || l->kind == Launch::L_IP_HOISTED || l->kind == Launch::L_IP_LINTRANS) cnt = l->mods.size();
+    if (l->kind == Launch::L_IP || l->kind == Launch::L_NTT_IP || l->kind == Launch::L_IP_HOISTED || l->kind == Launch::L_IP_LINTRANS ||
+        l->kind == Launch::L_IP_ROTSUM)
+      cnt = l->mods.size();
     out += std::string(names[l->kind]) + " " + l->name + " n=" + std::to_string(cnt) + " ref=" + std::to_string(l->refInstructions);
     // pass 11: limb-polys an inverse transform stores split-30 packed / conversions (separate or inside a transform's first pass) that read packed inputs
     const size_t po = (size_t)std::count(l->outPacked.begin(), l->outPacked.end(), 1), pi = (size_t)std::count_if(l->probs.begin(), l->probs.end(), [](const Launch::Prob &q) { return q.inPacked; });
@@ -1116,6 +1157,8 @@ std::string Arch::planText() const {
     if (l->kind == Launch::L_TENSOR_DOT) out += " terms=" + std::to_string(l->dotTerms);   // (5d): pairs summed per record
     if (l->kind == Launch::L_IP_LINTRANS)   // (6l): entries that also form the addend output
       out += " addend=" + std::to_string(l->d.size() - (size_t)std::count(l->d.begin(), l->d.end(), HM_NO_LIMB));
+    if (l->kind == Launch::L_IP_ROTSUM)   // (6s): entries that also form the addend output
+      out += " addend=" + std::to_string(l->out1.size() - (size_t)std::count(l->out1.begin(), l->out1.end(), HM_NO_LIMB));
     if (l->recordSlot >= 0) out += " mark=" + std::to_string(l->recordSlot);
     if (!l->waitSlots.empty()) { out += " wait="; for (int w : l->waitSlots) out += std::to_string(w) + ","; }
     if (!l->exLimbs.empty()) {
@@ -1210,6 +1253,14 @@ void Arch::enqueue(Launch &l) {
                                    add ? pool : nullptr, add ? l.out1.data() : nullptr, l.mods.data(), (uint32_t)l.mods.size(), l.ipTerms,
                                    (uint32_t)l.hoistG.size(), l.hoistG.data()};
     st = hm_inner_product_lintrans(ctx, &d);
+    break;
+  }
+  case Launch::L_IP_ROTSUM: {
+    const bool add = !l.d.empty();
+    const hm_ip_rotsum_desc d = {pool, l.a.data(), pool, l.b.data(), add ? pool : nullptr, add ? l.d.data() : nullptr, pool, l.out.data(),
+                                 add ? pool : nullptr, add ? l.out1.data() : nullptr, l.mods.data(), (uint32_t)l.mods.size(), l.ipTerms,
+                                 (uint32_t)l.hoistG.size(), l.hoistG.data()};
+    st = hm_inner_product_rotsum(ctx, &d);
     break;
   }
   case Launch::L_NTT_IP: {

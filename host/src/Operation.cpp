@@ -100,11 +100,12 @@ KeySwitch::KeySwitch(std::string labelName, uint32_t maxlevel, uint32_t level, u
 }
 
 // reference: KeySwitch::KeySwitch :33-40 — the ModUp: INTT of the input, then per digit scale, conversion and forward transforms
-KeySwitch::Digits KeySwitch::modUp(const std::vector<AddrType> &input, bool inputMayBeOpInput) {
+KeySwitch::Digits KeySwitch::modUp(const std::vector<AddrType> &input, bool inputMayBeOpInput, const std::string &suffix) {
+  const std::string baseName = this->baseName + suffix;
   const uint32_t E = Level + Alpha;
   // reference: KeySwitch::ModUpINTT :63-102 — one INTT per input limb; throws when the input has no producer, unless it may be the op's own input
   // ciphertext (the hoisted rotations)
-  PerLimb in{baseName + "_ModUp_INTT(", ")_", qMods, alloc(memMange, "ModUpINTTOut", Level)};
+  PerLimb in{baseName + "_ModUp_INTT(", ")_", qMods, alloc(memMange, "ModUpINTTOut" + suffix, Level)};
   std::vector<INSGROUP> producers;
   for (uint32_t l = 0; l < Level; l++) {
     auto prod = DataInsMap->find(input[l]);
@@ -113,13 +114,13 @@ KeySwitch::Digits KeySwitch::modUp(const std::vector<AddrType> &input, bool inpu
   }
   in.a = input;
   in.after = {&producers};
-  const Limbs intt{in.out, stages.add("ModUp_INTT", nttLimbs(insGenPointer, false, in))};
-  const std::vector<AddrType> offset = alloc(memMange, "ModUpDecompOffset", 1), decompOut = alloc(memMange, "ModUpDecompOut", Level);
+  const Limbs intt{in.out, stages.add("ModUp_INTT" + suffix, nttLimbs(insGenPointer, false, in))};
+  const std::vector<AddrType> offset = alloc(memMange, "ModUpDecompOffset" + suffix, 1), decompOut = alloc(memMange, "ModUpDecompOut" + suffix, Level);
 
   Digits digits;
   for (uint32_t be = 0; be < Beta; be++) {
     const uint32_t lo = be * Alpha, dj = std::min(Alpha, Level - lo);
-    const std::string B = S(be);
+    const std::string B = S(be), B_ = suffix + "_(" + B + ")";
     // reference: ModUpDecompFusionBConvStep1 :104-135 — y_i = x_i * [(Q_Dj/q_i)^-1]_{q_i} for the limbs of digit j
     const Limbs x = slice(intt, lo, dj);
     PerLimb sc{baseName + "_decompFusionBConvStep1_beta(" + B + ")_Level(", ")_", range(lo, dj), slice(decompOut, lo, dj)};
@@ -128,14 +129,14 @@ KeySwitch::Digits KeySwitch::modUp(const std::vector<AddrType> &input, bool inpu
     sc.b = offset;
     sc.after = {&x.from};
     sc.constants = arch->bconvScale(sc.mods);
-    std::vector<INSGROUP> &scaled = stages.add("ModUp_DecompOut" + B + ")", eweLimbs(insGenPointer, EWE_MUL_CONST, sc));  // sic: upstream's key has the stray parenthesis (:133)
+    std::vector<INSGROUP> &scaled = stages.add("ModUp_DecompOut" + suffix + B + ")", eweLimbs(insGenPointer, EWE_MUL_CONST, sc));  // sic: upstream's key has the stray parenthesis (:133)
 
     // reference: ModUpBConvStep2 :137-188 — every limb of the extended basis outside the digit, d_j-deep MAC each
     // reference: ModUpNTT :190-292 — E NTT instructions per digit.  Upstream also spends an NTT on each of the
     // digit's own limbs; mathematically those are the original evaluation-form input limbs, so here they are
     // pass-through records (a copy, or nothing once the consumers are redirected) that still count as NTTs.
-    const AddrType table = allocTable(memMange, "BConvMap_(" + B + ")");
-    const std::vector<AddrType> convOut = alloc(memMange, "BConvOut_(" + B + ")", E - dj), digit = alloc(memMange, "NTTOut_beta(" + B + ")", E);
+    const AddrType table = allocTable(memMange, "BConvMap" + B_);
+    const std::vector<AddrType> convOut = alloc(memMange, "BConvOut" + B_, E - dj), digit = alloc(memMange, "NTTOut" + suffix + "_beta(" + B + ")", E);
     std::vector<INSGROUP> conv, ntt;
     for (uint32_t t = 0; t < E; t++) {
       const std::string name = baseName + "_ModUp_NTT_beta(" + B + ")_Level(" + S(t) + ")_";
@@ -148,8 +149,8 @@ KeySwitch::Digits KeySwitch::modUp(const std::vector<AddrType> &input, bool inpu
         ntt.push_back(insGenPointer->GenNTT(t, name, &conv[o], true, convOut[o], digit[t], extMods[t]));
       }
     }
-    stages.add("ModUp_BCONV_(" + B + ")", conv);
-    digits.push_back({digit, stages.add("ModUp_NTT_(" + B + ")", ntt)});
+    stages.add("ModUp_BCONV" + B_, conv);
+    digits.push_back({digit, stages.add("ModUp_NTT" + B_, ntt)});
   }
   return digits;
 }
@@ -404,9 +405,9 @@ std::vector<AddrType> OperationBase::alloc(const std::string &name, uint32_t lim
 void OperationBase::dispatch(const StageList &m) {
   for (const auto &stage : m) driver.dispatchInstructions(stage.first, stage.second);
 }
-Limbs OperationBase::rotateComponent(uint32_t k, uint32_t galois, const std::string &suffix) {
+Limbs OperationBase::rotateComponent(uint32_t k, uint32_t galois, const std::string &suffix, uint32_t ct) {
   PerLimb s{label + "_AUTO" + suffix + "_Level(", ")_k(" + S(k) + ")", range(0, level_), alloc("AUTOOutput" + suffix + "(" + S(k) + ")", level_)};
-  s.a = component(0, k);
+  s.a = component(ct, k);
   const Limbs rotated{s.out, autoLimbs(&insgener, galois, s)};
   driver.dispatchInstructions("AUTO" + suffix + "_Key(" + S(k) + ")", rotated.from);
   return rotated;
@@ -748,6 +749,59 @@ HDOT::HDOT(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint
   finishConstruction();
 }
 
+// hrotsum (build extension).  out = sum_i rot_{g_i}(ct<i>), g_i = g^i mod 2N, over G DIFFERENT ciphertexts with ONE ModDown: the ModDown is linear,
+// so the G key products are summed on the E = l + alpha limbs and brought down once (the ModUps cannot be shared: the ciphertexts differ).
+//   D_{i,j} = ModUp(ct<i>.c1)                          per ciphertext, on the unrotated c1 (buffers and stages of ciphertext i >= 2 suffixed _Ct<i>)
+//   acc_{i,k} = sum_j sigma_i(D_{i,j}) evk_i[j][k]     rotateDigits + keyProduct with hrotate_hoisted's key of rotation i (suffix _Rot<i>)
+//   S_k = sum_i acc_{i,k}   (E limbs),   U = sum_i sigma_i(ct<i>.c0)   (l limbs)        one ADD per further ciphertext onto the running sums
+//   out.c0 = U + ModDown(S_0),   out.c1 = ModDown(S_1)
+// Every sum is the canonical residue of the exact integer sum.  A valid key switch, not bit-identical to G hrotate + G - 1 hadd (that rounds in
+// G ModDowns, this in one); at G = 1 it is hrotate_hoisted with rotations = 1.  Unfused, the stages run one launch each; fused, pass (6s) of
+// Arch::fusePasses (Planner.cpp) turns everything between the ModUps and the ModDown into one launch.
+HROTSUM::HROTSUM(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch)
+    : OperationBase("HROTSUM", labelName, cfg, _arch, maxLevel, currentLevel, alpha) {
+  const std::vector<uint32_t> gs = hoistedRotations("hrotsum");
+  const uint32_t G = (uint32_t)gs.size();
+  makeInputs(G);
+
+  KeySwitch ks(labelName, maxLevel, currentLevel, alpha, &Datapool, &DataInsMap, &insgener, addrManager.get());
+  std::vector<uint32_t> extMods = range(0, currentLevel);
+  for (uint32_t p : range(maxLevel, alpha)) extMods.push_back(p);
+  const std::array<std::string, 3> tags = {"Key0", "Key1", "C0"};
+  std::array<Limbs, 3> sums;   // S_0, S_1, U so far
+  for (uint32_t i = 1; i <= G; ++i) {
+    const std::string rs = "_Rot" + S(i);
+    const KeySwitch::Digits digits = ks.modUp(cts[i - 1].getC1Addr(), /*inputMayBeOpInput=*/true, i == 1 ? "" : "_Ct" + S(i));
+    const KeySwitch::Accumulators acc = ks.keyProduct(ks.rotateDigits(digits, gs[i - 1], rs), seed + 10000 + 100000ull * i, rs);
+    dispatch(ks.takeStages());
+    const std::array<Limbs, 3> terms = {acc[0], acc[1], rotateComponent(0, gs[i - 1], rs, i - 1)};
+    if (i == 1) {
+      sums = terms;
+      continue;
+    }
+    for (uint32_t t = 0; t < 3; ++t) {
+      const std::string at = "(" + S(i) + ")_" + tags[t];
+      PerLimb s{labelName + "_RotSum_" + tags[t] + "_Ct(" + S(i) + ")_Level(", ")", t < 2 ? extMods : range(0, currentLevel),
+                alloc(i < G ? "RotSum_" + at : "RotSumOut_" + tags[t], t < 2 ? currentLevel + alpha : currentLevel)};
+      const Limbs before = sums[t];
+      s.a = before.addr;
+      s.c = terms[t].addr;
+      s.after = {&before.from, &terms[t].from};
+      sums[t] = {s.out, eweLimbs(&insgener, EWE_ADD, s)};
+      driver.dispatchInstructions("RotSum_" + at, sums[t].from);
+    }
+  }
+  const KeySwitch::Output down = ks.modDown({sums[0], sums[1]}, "");
+  dispatch(ks.takeStages());
+  PerLimb s{labelName + "_HROTSUMadd_Level(", ")", range(0, currentLevel), alloc("HROTSUMOutput(0)", currentLevel)};
+  s.a = down[0];
+  s.c = sums[2].addr;
+  driver.dispatchInstructions("HROTSUM_Hadd", eweLimbs(&insgener, EWE_ADD, s));
+  setOutput("out", 0, s.out);
+  setOutput("out", 1, down[1]);
+  finishConstruction();
+}
+
 // reference: HADD::HADD :1114-1176
 HADD::HADD(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch)
     : OperationBase("HADD", labelName, cfg, _arch, maxLevel, currentLevel, alpha) {
@@ -802,6 +856,7 @@ static OperationBase *makeOp(const std::string &o, uint32_t maxLevel, uint32_t l
   if (o == "hrotate_hoisted") return new HROTATE_HOISTED("test_hrotate_hoisted", maxLevel, level, alpha, cfg, arch);
   if (o == "hlintrans") return new HLINTRANS("test_hlintrans", maxLevel, level, alpha, cfg, arch);
   if (o == "hdot") return new HDOT("test_hdot", maxLevel, level, alpha, cfg, arch);
+  if (o == "hrotsum") return new HROTSUM("test_hrotsum", maxLevel, level, alpha, cfg, arch);
   throw std::runtime_error("Error operation requirement, please double confirm!");
 }
 

@@ -60,6 +60,7 @@ struct Arch::Planner {
     std::vector<DigitsKey> order;   // first appearance
   };
   RotationGroups rotationGroups(Readers &rd);
+  void sumOfRotations();      // 6s
   void weightedRotations();   // 6l
   void hoist();               // 6h
   void transformTimesKey();   // 7 + 8
@@ -83,6 +84,7 @@ void Arch::fusePasses(std::vector<Stage> &st) {
   p.tensor();
   if (fuseDot) p.tensorDot();   // before (6): the multiply-accumulate chains it absorbs are not key products
   p.keyProduct();
+  if (fuseRotsum) p.sumOfRotations();        // before (6l) and (6h): each record it merges is a group of one rotation to them
   if (fuseLintrans) p.weightedRotations();   // before (6h): the records it merges are the ones (6h) would claim
   if (fuseHoist) p.hoist();
   if (fuseHpip) p.transformTimesKey();
@@ -429,6 +431,129 @@ Arch::Planner::RotationGroups Arch::Planner::rotationGroups(Readers &rd) {
       g.members[key].push_back({ip, autos});
     }
   return g;
+}
+
+// (6s) sum of rotations of DIFFERENT ciphertexts (hrotsum): key-product records of (6) with one modulus whose digits are all automorphisms, one
+//      element per record, of materialised digits nothing else reads — the digit lists DIFFER between the records, which is what rotationGroups
+//      does not group — and whose outputs k = 0, 1 are read only by ONE chain of EWE_ADD records each that adds one record's output k per link,
+//      S_k = sum_c acc_{c,k}, merge WITH the two chains into one record: hm_inner_product_rotsum sums the raw products of every ciphertext in
+//      registers and stores S_0, S_1 only.  If a third ADD chain (the Q limbs: U = sum_c sigma_c(c0 of ciphertext c)) adds automorphisms by the
+//      same elements, in the same order, each of its own source, it joins as the record's addend output.  Never written: the rotated digits, the
+//      2G per-ciphertext sums, the partial sums, the rotated c0's.  The first key-product record in stage order carries the merged one; it moves
+//      to where the last link of S_0, S_1 stood: every ciphertext's digits are older, every reader of S_k and U comes after the chains' ends.
+//      Reads: the key-product records of (6).  Sets on the carrying record: ipX, ipSumX (every ciphertext's unrotated digits), ipY, ipHoistG,
+//      ipSumAddend, OutputOperand, extraOutputs.
+void Arch::Planner::sumOfRotations() {
+  Readers rd = readers();
+  RotationGroups found = rotationGroups(rd);
+  struct Member { Instruction *ip; std::vector<Instruction *> autos; std::vector<AddrType> digits; };
+  std::map<Instruction *, Member> candidates;   // (looked up only)
+  for (const DigitsKey &key : found.order)
+    for (auto &m : found.members[key]) candidates[m.first] = Member{m.first, m.second, key.second};
+  std::map<Instruction *, std::pair<size_t, size_t>> place;   // record -> (stage, position)
+  for (size_t si = 0; si < st.size(); ++si)
+    for (size_t k = 0; k < st[si].ins.size(); ++k) place[st[si].ins[k]] = {si, k};
+  // the one live reader of `a`, if it is an ADD of this modulus that reads `a` once; `other`: what it adds to `a`
+  auto addOf = [&](AddrType a, uint32_t mod, AddrType &other) -> Instruction * {
+    auto &r = rd[a];
+    if (r.size() != 1 || !live(r[0]) || r[0]->ops != MULT || r[0]->opcode != EWE_ADD || r[0]->mod_id != mod) return nullptr;
+    const AddrType x = r[0]->operandList[0], y = r[0]->operandList[2];
+    if ((x == a) == (y == a)) return nullptr;
+    other = x == a ? y : x;
+    return r[0];
+  };
+  std::vector<Instruction *> order;
+  for (auto &s : st)
+    for (Instruction *i : s.ins)
+      if (candidates.count(i)) order.push_back(i);
+  std::set<Instruction *> taken;
+  for (Instruction *c : order) {
+    if (taken.count(c)) continue;
+    const uint32_t mod = c->mod_id;
+    // S_0: link by link, the running sum plus the output 0 of a further candidate record
+    std::vector<Instruction *> mem = {c}, S[2];
+    for (AddrType sum = c->OutputOperand; mem.size() < HM_IP_ROTSUM_MAX_CT;) {
+      AddrType other = 0;
+      Instruction *l = addOf(sum, mod, other), *ip = l ? producerOf(other) : nullptr;
+      if (!ip || !candidates.count(ip) || taken.count(ip) || ip->mod_id != mod || ip->OutputOperand != other || !onlyReader(rd, other, l) ||
+          ip->ipX.size() != c->ipX.size() || std::find(mem.begin(), mem.end(), ip) != mem.end())
+        break;
+      mem.push_back(ip);
+      S[0].push_back(l);
+      sum = l->OutputOperand;
+    }
+    const size_t G = mem.size();
+    if (G < 2) continue;
+    // S_1: the same records in the same order
+    bool ok = true;
+    for (AddrType sum = c->extraOutputs[0]; ok && S[1].size() + 1 < G;) {
+      AddrType other = 0;
+      Instruction *l = addOf(sum, mod, other), *ip = mem[S[1].size() + 1];
+      ok = l && other == ip->extraOutputs[0] && onlyReader(rd, other, l);
+      if (ok) { S[1].push_back(l); sum = l->OutputOperand; }
+    }
+    if (!ok) continue;
+    // where the merged record goes: the place of the last key product or link of S_0, S_1.  Every limb's record then stands in the stage of
+    // S_1's last link, so that the records with and without an addend share a launch
+    Instruction *last = c;
+    for (Instruction *i : mem) if (place[i] > place[last]) last = i;
+    for (auto &chain : S) for (Instruction *i : chain) if (place[i] > place[last]) last = i;
+    // U: an ADD chain over automorphisms by the records' elements, in their order, each of its own source (written, if at all, before that
+    // place) and read by its link only
+    std::vector<Instruction *> U, addendAutos;
+    for (auto &s : st) {
+      for (Instruction *a0 : s.ins) {
+        if (!live(a0) || a0->ops != AUTO || a0->mod_id != mod || a0->galois != candidates[c].autos[0]->galois || rd[a0->OutputOperand].size() != 1) continue;
+        if (std::find(candidates[c].autos.begin(), candidates[c].autos.end(), a0) != candidates[c].autos.end()) continue;
+        std::vector<Instruction *> links, autos = {a0};
+        for (AddrType sum = a0->OutputOperand; autos.size() < G;) {
+          AddrType other = 0;
+          Instruction *l = addOf(sum, mod, other), *a = l ? producerOf(other) : nullptr;
+          if (!a || !live(a) || a->ops != AUTO || a->mod_id != mod || a->galois != candidates[mem[autos.size()]].autos[0]->galois || !onlyReader(rd, other, l))
+            break;
+          if (Instruction *w = producerOf(a->operandList[0])) if (place[w] > place[last]) break;
+          autos.push_back(a);
+          links.push_back(l);
+          sum = l->OutputOperand;
+        }
+        if (Instruction *w = producerOf(a0->operandList[0])) if (place[w] > place[last]) continue;
+        if (autos.size() != G) continue;
+        U = links; addendAutos = autos;
+        break;
+      }
+      if (!U.empty()) break;
+    }
+    std::vector<std::vector<AddrType>> xs, ys;
+    std::vector<uint32_t> gs;
+    std::vector<AddrType> addends;
+    auto absorb = [&](Instruction *i) { if (i != c) { c->refInstructions += i->refInstructions; dead.insert(i); } };
+    for (size_t g = 0; g < G; ++g) {
+      const Member &m = candidates[mem[g]];
+      xs.push_back(m.digits);
+      ys.insert(ys.end(), m.ip->ipY.begin(), m.ip->ipY.end());
+      gs.push_back(m.autos[0]->galois);
+      taken.insert(m.ip);
+      absorb(m.ip);
+      for (Instruction *a : m.autos) absorb(a);
+      if (g) { absorb(S[0][g - 1]); absorb(S[1][g - 1]); }
+      if (!U.empty()) { addends.push_back(addendAutos[g]->operandList[0]); absorb(addendAutos[g]); if (g) absorb(U[g - 1]); }
+    }
+    c->ipX = xs[0];
+    c->ipSumX = xs;
+    c->ipY = ys;
+    c->ipHoistG = gs;
+    c->ipSumAddend = addends;
+    c->OutputOperand = S[0].back()->OutputOperand;
+    c->extraOutputs = {S[1].back()->OutputOperand};
+    if (!U.empty()) c->extraOutputs.push_back(U.back()->OutputOperand);
+    for (const Write &w : recordWrites(*c)) producer[w.addr] = c;
+    if (last != c) {   // the record moves there
+      auto &from = st[place[c].first].ins;
+      from.erase(std::remove(from.begin(), from.end(), c), from.end());
+      auto &to = st[place[last].first].ins;
+      std::replace(to.begin(), to.end(), last, c);
+    }
+  }
 }
 
 // (6l) weighted sum of rotations (hlintrans): the records (6h) would merge, when every rotation's two outputs are read only by ONE chain

@@ -230,6 +230,31 @@ typedef struct hm_ip_lintrans_desc {
   const uint32_t *galois;                                     /* [n_rot] */
 } hm_ip_lintrans_desc;
 hm_status hm_inner_product_lintrans(hm_ctx *ctx, const hm_ip_lintrans_desc *desc);
+/* Sum of the key products of rotations of n_ct DIFFERENT ciphertexts (hrotsum): every ciphertext has its own digits,
+ * keys and Galois element, and the sum over the ciphertexts is formed BEFORE anything is stored,
+ *   out[i][k]     = sum_c sum_j automorph_{galois[c]}(x[c][i][j]) (.) y[c][i][k][j]      k < 2, j < n_terms <= 4, c < n_ct <= 16
+ *   addend_out[i] = sum_c automorph_{galois[c]}(addend[c][i])                            for the entries i that carry addend sources,
+ * every residue the canonical one of the exact integer sum: bit-identical to n_ct calls of hm_inner_product_ex (x_galois = galois[c]),
+ * hm_automorph of the addends and HM_OP_ADD chains, none of whose intermediates is written.  The gather form of hm_inner_product_lintrans:
+ * a workgroup owns the destination; per ciphertext it loads the digits' (and the addend's) aligned pair at the automorphism's source, in
+ * order or swapped, and both keys at the destination.  Row-major lists: x_limbs[(c * n + i) * n_terms + j],
+ * y_limbs[((c * n + i) * 2 + k) * n_terms + j], addend_limbs[c * n + i], out_limbs[i * 2 + k].  addend / addend_limbs / addend_out /
+ * addend_out_limbs are optional together (NULL: no entry has an addend); an entry has a source in every ciphertext or
+ * addend_limbs[c * n + i] == HM_NO_LIMB for every c (then addend_out_limbs[i] is ignored).  Every galois[c] is odd and below 2N; two
+ * ciphertexts may share an element.  No output limb-poly (out, addend_out) may overlap, by address range, a digit, a key, an addend source
+ * or another output: HM_ERR_ARG.  Safe under graph capture once it has run with the same limb lists. */
+#define HM_IP_ROTSUM_MAX_CT 16
+typedef struct hm_ip_rotsum_desc {
+  const uint64_t *x;       const uint32_t *x_limbs;           /* digits [n_ct][n][n_terms] */
+  const uint64_t *y;       const uint32_t *y_limbs;           /* keys [n_ct][n][2][n_terms] */
+  const uint64_t *addend;  const uint32_t *addend_limbs;      /* optional addend sources [n_ct][n]; HM_NO_LIMB: none for this entry */
+  uint64_t *out;           const uint32_t *out_limbs;         /* [n][2] */
+  uint64_t *addend_out;    const uint32_t *addend_out_limbs;  /* [n], read where the entry has addend sources */
+  const uint32_t *mod_ids;                                    /* [n] */
+  uint32_t n, n_terms, n_ct;
+  const uint32_t *galois;                                     /* [n_ct] */
+} hm_ip_rotsum_desc;
+hm_status hm_inner_product_rotsum(hm_ctx *ctx, const hm_ip_rotsum_desc *desc);
 
 /* K1 x K5 — the HPIP unit as a fused NTT-epilogue x evaluation-key MAC: for extended limb i,
  *     out[i][k] = sum_{j < n_terms} X_j[i] * y[i][k][j],   X_j[i] = NTT(x[i][j]) if x_is_coeff[i][j] else x[i][j]
