@@ -516,7 +516,8 @@ __global__ void __launch_bounds__(256) k_ewe(HmEweArgs a) {
   }
 }
 
-// K5 (hm_ip_core.h): one workgroup per 512 coefficients of an entry, in the plain, the hoisted, the weighted-sum and the sum-of-ciphertexts form
+// K5 (hm_ip_core.h): one workgroup per 512 coefficients of an entry, in the plain, the hoisted, the weighted-sum, the several-weighted-sums and the
+// sum-of-ciphertexts form
 template <int TERMS, int OUTS>
 __global__ void __launch_bounds__(256) k_inner_product(HmIpArgs a) {
   const uint32_t per_limb = (1u << a.logN) / HM_IP_CHUNK, entry = blockIdx.x / per_limb;
@@ -531,6 +532,11 @@ template <int TERMS>
 __global__ void __launch_bounds__(256) k_inner_product_lintrans(HmIpLinArgs a) {
   const uint32_t per_limb = (1u << a.logN) / HM_IP_CHUNK, entry = blockIdx.x / per_limb;
   if (entry < a.n_limbs) hm_ip_lintrans_thread<TERMS>(a, entry, blockIdx.x % per_limb, threadIdx.x);
+}
+template <int TERMS, int TILE>   // blockIdx.y: the tile of outputs
+__global__ void __launch_bounds__(256) k_inner_product_lintrans_multi(HmIpLinMultiArgs a) {
+  const uint32_t per_limb = (1u << a.logN) / HM_IP_CHUNK, entry = blockIdx.x / per_limb;
+  if (entry < a.n_limbs && blockIdx.y * TILE < a.n_out) hm_ip_lintrans_multi_thread<TERMS, TILE>(a, entry, blockIdx.x % per_limb, threadIdx.x, blockIdx.y);
 }
 template <int TERMS>
 __global__ void __launch_bounds__(256) k_inner_product_rotsum(HmIpSumArgs a) {
@@ -684,6 +690,7 @@ struct hm_ctx {
   // ntt_launch_entries x N x 8 bytes; what is written and read between a hand-off line's store and its load decides whether the load is
   // served by the Infinity Cache (256 MiB) or by HBM
   uint32_t ntt_launch_entries = HM_NTT_MAX_ENTRIES;
+  uint32_t ip_multi_tile = 0;   // hm_set_option "ip_multi_tile": outputs per workgroup of hm_inner_product_lintrans_multi (0 = HM_IP_LINTRANS_MULTI_TILE)
   uint32_t nip_small = 64;  // transform x key launches of at most this many limb records (N = 2^16) run in the small-launch geometry (k_ntt_row_ip8); 0 = off
   int n_cu = 256;
   // multi-GPU
@@ -1029,6 +1036,11 @@ extern "C" hm_status hm_set_option(hm_ctx *c, const char *name, uint64_t value) 
     return HM_OK;
   }
   if (!strcmp(name, "ntt_launch_entries")) { c->ntt_launch_entries = (uint32_t)std::max<uint64_t>(8, value); return HM_OK; }
+  if (!strcmp(name, "ip_multi_tile")) {   // outputs per workgroup of hm_inner_product_lintrans_multi: 0 = HM_IP_LINTRANS_MULTI_TILE, or one of the two built sizes
+    if (value != 0 && value != 2 && value != 4) return fail(c, HM_ERR_ARG, "hm_set_option: ip_multi_tile is 0 (the default tile), 2 or 4");
+    c->ip_multi_tile = (uint32_t)value;
+    return HM_OK;
+  }
   if (!strcmp(name, "nip_small_limbs")) { c->nip_small = (uint32_t)value; return HM_OK; }
   if (!strcmp(name, "ntt_small_mode")) { c->small_mode = (uint32_t)value & 3u; return HM_OK; }
   if (!strcmp(name, "ntt_small_limbs")) { c->small_ept8 = value != 0; c->small_limbs = (uint32_t)value; return HM_OK; }
@@ -1673,6 +1685,11 @@ static void (*const k_ip_hoisted[HM_IP_MAX_TERMS][1])(HmIpHoistArgs) = HM_K(k_in
 static void (*const k_ip_lintrans[HM_IP_MAX_TERMS][1])(HmIpLinArgs) = HM_K(k_inner_product_lintrans);
 static void (*const k_ip_rotsum[HM_IP_MAX_TERMS][1])(HmIpSumArgs) = HM_K(k_inner_product_rotsum);
 #undef HM_K
+// several weighted sums: by [n_terms - 1][tile size: 0 = HM_IP_LINTRANS_MULTI_TILE, 1 = the other size of the A/B (hm_set_option "ip_multi_tile")]
+#define HM_IP_MULTI_TILE_ALT (HM_IP_LINTRANS_MULTI_TILE == 4 ? 2 : 4)
+#define HM_K(t) {k_inner_product_lintrans_multi<t, HM_IP_LINTRANS_MULTI_TILE>, k_inner_product_lintrans_multi<t, HM_IP_MULTI_TILE_ALT>}
+static void (*const k_ip_lintrans_multi[HM_IP_MAX_TERMS][2])(HmIpLinMultiArgs) = {HM_K(1), HM_K(2), HM_K(3), HM_K(4)};
+#undef HM_K
 template <class Args, size_t OUTS>
 static void launch_ip(hm_ctx *c, void (*const (&kernel)[HM_IP_MAX_TERMS][OUTS])(Args), const Args &a, uint32_t T, uint32_t O = 1) {
   hipLaunchKernelGGL(kernel[T - 1][O - 1], dim3(a.n_limbs * ((1u << a.logN) / HM_IP_CHUNK)), dim3(256), 0, c->stream, a);
@@ -1807,6 +1824,72 @@ extern "C" hm_status hm_inner_product_lintrans(hm_ctx *c, const hm_ip_lintrans_d
   a.mods = c->d_mods; a.logN = c->P.logN; a.n_limbs = n; a.n_rot = R;
   for (uint32_t r = 0; r < HM_IP_LINTRANS_MAX_ROT; ++r) a.galois[r] = r < R ? d->galois[r] : 1u;
   launch_ip(c, k_ip_lintrans, a, T);
+  HM_HIP(c, hipGetLastError());
+  return HM_OK;
+}
+
+// several weighted sums of the same rotations: the weighted sum's records, shared by the outputs, then every output's limbs and plaintexts, in one table
+extern "C" hm_status hm_inner_product_lintrans_multi(hm_ctx *c, const hm_ip_lintrans_multi_desc *d) {
+  static const char *const what = "hm_inner_product_lintrans_multi";
+  static const hm_ip_lintrans_multi_desc none = {};
+  if (!c) return HM_ERR_ARG;
+  if (!d) d = &none;
+  const bool anyAdd = d->addend_limbs != nullptr;
+  const char *null = nullptr;
+  if (!d->x || !d->x_limbs || !d->y || !d->y_limbs || !d->pt || !d->pt_limbs || !d->out || !d->out_limbs || !d->mod_ids || !d->galois) null = "null argument";
+  else if (anyAdd && (!d->addend || !d->addend_out || !d->addend_out_limbs)) null = "null argument (addend, addend_limbs, addend_out and addend_out_limbs go together)";
+  else if (!anyAdd && (d->addend || d->addend_out || d->addend_out_limbs)) null = "null argument (an addend or addend outputs without addend_limbs)";
+  const uint32_t n = d->n, T = d->n_terms, R = d->n_rot, G = d->n_out, N = c->P.N;
+  if (!null && (G == 0 || G > HM_IP_LINTRANS_MULTI_MAX_OUT)) return fail(c, HM_ERR_ARG, "%s: n_out = %u, must be in [1,%d]", what, G, HM_IP_LINTRANS_MULTI_MAX_OUT);
+  std::vector<uint32_t> addSrc, addOut;   // the entries that carry an addend: their source, and every output's addend output [n_out][those entries]
+  for (uint32_t i = 0; !null && anyAdd && i < n; ++i)
+    if (d->addend_limbs[i] != HM_NO_LIMB) addSrc.push_back(d->addend_limbs[i]);
+  for (uint32_t e = 0; !null && anyAdd && e < G * n; ++e)
+    if (d->addend_limbs[e % n] != HM_NO_LIMB) addOut.push_back(d->addend_out_limbs[e]);
+  const uint32_t nAdd = (uint32_t)addSrc.size();
+  hm_status st;
+  if ((st = ip_check(c, what, null, T, "n_rot", R, HM_IP_LINTRANS_MAX_ROT, d->galois,
+                     {{d->x_limbs, n * T}, {d->y_limbs, R * n * 2 * T}, {d->pt_limbs, G * R * n}, {d->out_limbs, G * n * 2}, {addSrc.data(), nAdd},
+                      {addOut.data(), G * nAdd}},
+                     d->mod_ids, n)))
+    return st;
+  // a workgroup reads the digits and the addend at other positions than the ones it writes, and every key, plaintext and other tile's operand
+  // could be another workgroup's output: no output may overlap any input, and no two outputs each other
+  struct In { const char *name; const void *base; const uint32_t *limbs; uint32_t count; };
+  const In ins[4] = {{"a digit (x)", d->x, d->x_limbs, n * T}, {"a key limb-poly (y)", d->y, d->y_limbs, R * n * 2 * T},
+                     {"a plaintext limb-poly (pt)", d->pt, d->pt_limbs, G * R * n}, {"the addend source", d->addend, addSrc.data(), nAdd}};
+  for (const In &in : ins) {
+    if (in.count && hm_limbs_overlap(d->out, d->out_limbs, G * n * 2, in.base, in.limbs, in.count, N))
+      return fail(c, HM_ERR_ARG, "%s: an output limb-poly overlaps %s", what, in.name);
+    if (in.count && nAdd && hm_limbs_overlap(d->addend_out, addOut.data(), G * nAdd, in.base, in.limbs, in.count, N))
+      return fail(c, HM_ERR_ARG, "%s: an addend output limb-poly overlaps %s", what, in.name);
+  }
+  {
+    std::vector<uintptr_t> starts;
+    for (uint32_t i = 0; i < G * n * 2; ++i) starts.push_back(reinterpret_cast<uintptr_t>(d->out) + (uintptr_t)d->out_limbs[i] * N * 8);
+    for (uint32_t i = 0; i < G * nAdd; ++i) starts.push_back(reinterpret_cast<uintptr_t>(d->addend_out) + (uintptr_t)addOut[i] * N * 8);
+    std::sort(starts.begin(), starts.end());
+    for (size_t i = 1; i < starts.size(); ++i)
+      if (starts[i] - starts[i - 1] < (uintptr_t)N * 8) return fail(c, HM_ERR_ARG, "%s: two output limb-polys overlap", what);
+  }
+  if (n == 0) return HM_OK;
+  std::vector<unsigned char> table(hm_ip_multi_table_bytes(n, R, G));
+  HmIpLinRec *recs = reinterpret_cast<HmIpLinRec *>(table.data());
+  hm_ip_fill_recs(recs, d->x_limbs, d->y_limbs, d->out_limbs, (size_t)n * 2, d->mod_ids, n, T, 2, R);
+  hm_ip_fill_lin(recs, d->pt_limbs, d->addend_limbs, d->addend_out_limbs, n, R);
+  hm_ip_fill_multi(table.data(), d->pt_limbs, d->out_limbs, d->addend_limbs, d->addend_out_limbs, n, R, G);
+  HM_HIP(c, hipSetDevice(c->device));
+  HmIpLinMultiArgs a;
+  const void *tab = nullptr;
+  if ((st = device_table(c, table.data(), table.size(), &tab))) return st;
+  a.rec = static_cast<const HmIpLinRec *>(tab);
+  a.outs = reinterpret_cast<const HmIpMultiOut *>(a.rec + (size_t)R * n);
+  a.pts = reinterpret_cast<const uint16_t *>(a.outs + (size_t)G * n);
+  a.x = d->x; a.y = d->y; a.pt = d->pt; a.addend = d->addend; a.out = d->out; a.addend_out = d->addend_out;
+  a.mods = c->d_mods; a.logN = c->P.logN; a.n_limbs = n; a.n_rot = R; a.n_out = G;
+  for (uint32_t r = 0; r < HM_IP_LINTRANS_MAX_ROT; ++r) a.galois[r] = r < R ? d->galois[r] : 1u;
+  const uint32_t alt = c->ip_multi_tile && c->ip_multi_tile != HM_IP_LINTRANS_MULTI_TILE, tile = alt ? HM_IP_MULTI_TILE_ALT : HM_IP_LINTRANS_MULTI_TILE;
+  hipLaunchKernelGGL(k_ip_lintrans_multi[T - 1][alt], dim3(n * (N / HM_IP_CHUNK), (G + tile - 1) / tile), dim3(256), 0, c->stream, a);
   HM_HIP(c, hipGetLastError());
   return HM_OK;
 }

@@ -1,6 +1,6 @@
-// hm_ip_core.h — K5, the inner product with the evaluation key, in its four forms: plain (hm_inner_product_ex), hoisted
-// (hm_inner_product_hoisted), the weighted sum of rotations (hm_inner_product_lintrans) and the sum of rotations of different ciphertexts
-// (hm_inner_product_rotsum).
+// hm_ip_core.h — K5, the inner product with the evaluation key, in its five forms: plain (hm_inner_product_ex), hoisted
+// (hm_inner_product_hoisted), the weighted sum of rotations (hm_inner_product_lintrans), the sum of rotations of different ciphertexts
+// (hm_inner_product_rotsum) and several weighted sums of the same rotations (hm_inner_product_lintrans_multi).
 // Per-thread bodies (no cross-thread state) and the records they read, shared by the HIP kernels, the entry points and the host emulator.
 // A workgroup of 256 threads covers 512 coefficients of one entry: thread tid of chunk c owns the aligned pair at c * 512 + 2 * tid.
 //
@@ -33,7 +33,11 @@ struct HmIpLinRec : HmIpKeys {   // one per (rotation, entry); the digits, the a
 struct HmIpSumRec : HmIpKeys {   // one per (ciphertext, entry): its own digits, keys and addend source; the outputs and the modulus are ciphertext 0's
   uint16_t mod, add_src, add_out, has_add;
 };
-static_assert(sizeof(HmIpKeys) == 28 && sizeof(HmIpHoistRec) == 32 && sizeof(HmIpLinRec) == 40 && sizeof(HmIpSumRec) == 36, "the device tables' record sizes");
+struct HmIpMultiOut {   // several weighted sums: one per (output, entry), behind the HmIpLinRec records [n_rot][n] the outputs share (whose pt, out and add_out are output 0's)
+  uint16_t out[2], add_out, pad;
+};
+static_assert(sizeof(HmIpKeys) == 28 && sizeof(HmIpHoistRec) == 32 && sizeof(HmIpLinRec) == 40 && sizeof(HmIpSumRec) == 36 && sizeof(HmIpMultiOut) == 8,
+              "the device tables' record sizes");
 
 struct HmIpArgs {
   const uint64_t *x, *y;
@@ -57,6 +61,16 @@ struct HmIpLinArgs {
   const HmMod *mods;
   const HmIpLinRec *rec;   // [n_rot][n_limbs]
   uint32_t logN, n_limbs, n_rot;
+  uint32_t galois[HM_IP_LINTRANS_MAX_ROT];
+};
+struct HmIpLinMultiArgs {
+  const uint64_t *x, *y, *pt, *addend;
+  uint64_t *out, *addend_out;
+  const HmMod *mods;
+  const HmIpLinRec *rec;      // [n_rot][n_limbs]: digits, keys, modulus, addend source
+  const HmIpMultiOut *outs;   // [n_out][n_limbs]
+  const uint16_t *pts;        // [n_out][n_rot][n_limbs]
+  uint32_t logN, n_limbs, n_rot, n_out;
   uint32_t galois[HM_IP_LINTRANS_MAX_ROT];
 };
 struct HmIpSumArgs {
@@ -92,6 +106,22 @@ inline void hm_ip_fill_lin(HmIpLinRec *rec, const uint32_t *pt, const uint32_t *
     rec[e].pt = (uint16_t)pt[e];
     if (addend && addend[i] != HM_NO_LIMB) { rec[e].has_add = 1; rec[e].add_src = (uint16_t)addend[i]; rec[e].add_out = (uint16_t)addend_out[i]; }
   }
+}
+// ... and what several weighted sums add behind those records, in ONE table (one content-cached allocation): the outputs' limbs out [n_out][n][2]
+// and addend_out [n_out][n] as HmIpMultiOut [n_out][n], then the plaintext limbs pt [n_out][n_rot][n] as 16-bit words.  `recs`: the table's first
+// n_rot * n * sizeof(HmIpLinRec) bytes, filled by hm_ip_fill_recs + hm_ip_fill_lin with output 0's lists
+inline size_t hm_ip_multi_table_bytes(uint32_t n, uint32_t n_rot, uint32_t n_out) {
+  return (size_t)n_rot * n * sizeof(HmIpLinRec) + (size_t)n_out * n * sizeof(HmIpMultiOut) + (size_t)n_out * n_rot * n * sizeof(uint16_t);
+}
+inline void hm_ip_fill_multi(unsigned char *table, const uint32_t *pt, const uint32_t *out, const uint32_t *addend, const uint32_t *addend_out, uint32_t n,
+                             uint32_t n_rot, uint32_t n_out) {
+  HmIpMultiOut *o = reinterpret_cast<HmIpMultiOut *>(table + (size_t)n_rot * n * sizeof(HmIpLinRec));
+  uint16_t *p = reinterpret_cast<uint16_t *>(o + (size_t)n_out * n);
+  for (size_t e = 0; e < (size_t)n_out * n; ++e) {
+    const bool add = addend && addend[e % n] != HM_NO_LIMB;
+    o[e] = HmIpMultiOut{{(uint16_t)out[e * 2], (uint16_t)out[e * 2 + 1]}, (uint16_t)(add ? addend_out[e] : 0), 0};
+  }
+  for (size_t e = 0; e < (size_t)n_out * n_rot * n; ++e) p[e] = (uint16_t)pt[e];
 }
 // ... and what the sum over ciphertexts changes: every ciphertext has its own digits x [n_ct][n][T] and addend source [n_ct][n] (or nullptr)
 inline void hm_ip_fill_sum(HmIpSumRec *rec, const uint32_t *x, const uint32_t *addend, const uint32_t *addend_out, uint32_t n, uint32_t T, uint32_t n_ct) {
@@ -222,6 +252,67 @@ HM_HD void hm_ip_lintrans_thread(const HmIpLinArgs &a, uint32_t entry, uint32_t 
 #pragma unroll
   for (int k = 0; k < 2; ++k) hm_ip_st(a.out, l0.out[k], N, p, HmIpPair{hm_barrett_wide(S[k][0], m), hm_barrett_wide(S[k][1], m)});
   if (add) hm_ip_st(a.addend_out, l0.add_out, N, p, HmIpPair{hm_barrett_wide(U[0], m), hm_barrett_wide(U[1], m)});
+}
+
+// n_out weighted sums of the SAME rotations, out_m = sum_r pt_{m,r} * (the hoisted key product of rotation r): the gather form of
+// hm_ip_lintrans_thread, whose per-rotation work — the digits' pairs at the automorphism's source of p, both keys at p, t_k = hm_ip_dot — is done
+// ONCE for the TILE outputs [tile * TILE, min(n_out, (tile + 1) * TILE)) the thread serves; per output only the plaintext pair is loaded and
+// pt * t_k added to that output's own 128-bit accumulators (and pt * c0 to its addend accumulator).  Every output sees exactly the operations of
+// hm_ip_lintrans_thread in its order: bit-identical to n_out runs of it.  The accumulators are indexed by unrolled loops only (registers).
+template <int TERMS, int TILE>
+HM_HD void hm_ip_lintrans_multi_thread(const HmIpLinMultiArgs &a, uint32_t entry, uint32_t chunk, uint32_t tid, uint32_t tile) {
+  const uint32_t N = 1u << a.logN;
+  const HmIpLinRec &l0 = a.rec[entry];
+  const HmMod m = a.mods[l0.mod];
+  const bool add = l0.has_add != 0;   // workgroup-uniform
+  const uint32_t p = chunk * HM_IP_CHUNK + 2 * tid, m0 = tile * TILE;
+  const uint32_t cnt = a.n_out - m0 < (uint32_t)TILE ? a.n_out - m0 : (uint32_t)TILE;   // (workgroup-uniform) outputs of this tile
+  hm_u128 S[TILE][2][2], U[TILE][2];
+#pragma unroll
+  for (int o = 0; o < TILE; ++o) { S[o][0][0] = S[o][0][1] = S[o][1][0] = S[o][1][1] = 0; U[o][0] = U[o][1] = 0; }
+#pragma unroll 1
+  for (uint32_t r = 0; r < a.n_rot; ++r) {
+    const HmIpLinRec &lb = a.rec[(size_t)r * a.n_limbs + entry];
+    bool swap;
+    const uint32_t sp = hm_auto_pair(p, a.galois[r], a.logN, swap);
+    HmIpPair vx[TERMS], vy[2][TERMS];
+#pragma unroll
+    for (int j = 0; j < TERMS; ++j) vx[j] = hm_ip_ld(a.x, l0.x[j], N, sp);
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+#pragma unroll
+      for (int j = 0; j < TERMS; ++j) vy[k][j] = hm_ip_ld(a.y, lb.y[k][j], N, p);
+    HmIpPair vc{0, 0};
+    if (add) {
+      const HmIpPair c = hm_ip_ld(a.addend, l0.add_src, N, sp);
+      vc = swap ? HmIpPair{c.y, c.x} : c;
+    }
+    const HmIpPair t0 = hm_ip_dot<TERMS>(vx, vy[0], swap, m), t1 = hm_ip_dot<TERMS>(vx, vy[1], swap, m);
+#pragma unroll
+    for (int o = 0; o < TILE; ++o) {
+      if ((uint32_t)o < cnt) {
+        const HmIpPair vp = hm_ip_ld(a.pt, a.pts[((size_t)(m0 + o) * a.n_rot + r) * a.n_limbs + entry], N, p);
+        if (add) {
+          U[o][0] += (hm_u128)vp.x * vc.x;
+          U[o][1] += (hm_u128)vp.y * vc.y;
+        }
+        S[o][0][0] += (hm_u128)vp.x * t0.x;
+        S[o][0][1] += (hm_u128)vp.y * t0.y;
+        S[o][1][0] += (hm_u128)vp.x * t1.x;
+        S[o][1][1] += (hm_u128)vp.y * t1.y;
+      }
+    }
+  }
+  // n_rot <= 16 products below 2^120 per accumulator: below 2^124, reduced once by hm_barrett_wide as in hm_ip_lintrans_thread
+#pragma unroll
+  for (int o = 0; o < TILE; ++o) {
+    if ((uint32_t)o < cnt) {
+      const HmIpMultiOut &lo = a.outs[(size_t)(m0 + o) * a.n_limbs + entry];
+#pragma unroll
+      for (int k = 0; k < 2; ++k) hm_ip_st(a.out, lo.out[k], N, p, HmIpPair{hm_barrett_wide(S[o][k][0], m), hm_barrett_wide(S[o][k][1], m)});
+      if (add) hm_ip_st(a.addend_out, lo.add_out, N, p, HmIpPair{hm_barrett_wide(U[o][0], m), hm_barrett_wide(U[o][1], m)});
+    }
+  }
 }
 
 // sum of rotations of n_ct DIFFERENT ciphertexts, sum_c (the key product of ciphertext c through sigma_c), formed before anything is stored: the

@@ -13,6 +13,7 @@ BACKEND_LIBS = ("libhm_m32.so", "libhm_gen.so")
 
 OP_MUL, OP_MAC2, OP_MAC_ADD, OP_ADD, OP_SUB, OP_MUL_CONST, OP_SUB_SCALE, OP_COPY, OP_SUB_SCALE_ADD = range(9)
 NO_LIMB = 0xFFFFFFFF   # HM_NO_LIMB: "this entry has no such operand" in an optional limb list
+LINTRANS_MULTI_TILE = 2   # HM_IP_LINTRANS_MULTI_TILE: outputs a workgroup of hm_inner_product_lintrans_multi serves
 
 # every symbol include/homulator_hip.h declares
 SYMBOLS = [
@@ -22,7 +23,8 @@ SYMBOLS = [
     "hm_capture_begin", "hm_capture_end", "hm_graph_launch", "hm_graph_destroy", "hm_comm_info", "hm_slice_rows", "hm_limbs_to_slices", "hm_slices_to_limbs", "hm_replicate_limbs",
     "hm_set_option", "hm_get_counter", "hm_ntt_inner_product", "hm_exchange_stream", "hm_exchange_mark", "hm_exchange_wait",
     "hm_bconv_col", "hm_limbs_to_colslices", "hm_colslices_to_limbs", "hm_ntt_second_pass", "hm_ntt_ex", "hm_capability", "hm_inner_product_ex",
-    "hm_inner_product_hoisted", "hm_inner_product_lintrans", "hm_inner_product_rotsum", "hm_tensor_dot",
+    "hm_inner_product_hoisted", "hm_inner_product_lintrans", "hm_inner_product_rotsum", "hm_inner_product_lintrans_multi",
+    "hm_tensor_dot",
 ]
 
 
@@ -48,6 +50,13 @@ class hm_ip_lintrans_desc(C.Structure):
                 ("addend", C.c_void_p), ("addend_limbs", C.c_void_p), ("out", C.c_void_p), ("out_limbs", C.c_void_p),
                 ("addend_out", C.c_void_p), ("addend_out_limbs", C.c_void_p), ("mod_ids", C.c_void_p),
                 ("n", C.c_uint32), ("n_terms", C.c_uint32), ("n_rot", C.c_uint32), ("galois", C.c_void_p)]
+
+
+class hm_ip_lintrans_multi_desc(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("x_limbs", C.c_void_p), ("y", C.c_void_p), ("y_limbs", C.c_void_p), ("pt", C.c_void_p), ("pt_limbs", C.c_void_p),
+                ("addend", C.c_void_p), ("addend_limbs", C.c_void_p), ("out", C.c_void_p), ("out_limbs", C.c_void_p),
+                ("addend_out", C.c_void_p), ("addend_out_limbs", C.c_void_p), ("mod_ids", C.c_void_p),
+                ("n", C.c_uint32), ("n_terms", C.c_uint32), ("n_rot", C.c_uint32), ("n_out", C.c_uint32), ("galois", C.c_void_p)]
 
 
 class hm_ip_rotsum_desc(C.Structure):
@@ -118,6 +127,7 @@ def load():
     L.hm_inner_product_hoisted.argtypes = [vp, C.POINTER(hm_ip_hoisted_desc)]
     L.hm_inner_product_lintrans.argtypes = [vp, C.POINTER(hm_ip_lintrans_desc)]
     L.hm_inner_product_rotsum.argtypes = [vp, C.POINTER(hm_ip_rotsum_desc)]
+    L.hm_inner_product_lintrans_multi.argtypes = [vp, C.POINTER(hm_ip_lintrans_multi_desc)]
     L.hm_ntt_sub_scale.argtypes = [vp] + [vp] * 9 + [u32, vp]
     L.hm_ntt_mix_sub_scale.argtypes = [vp, C.POINTER(hm_ntt_fused_desc)]
     L.hm_tensor.argtypes = [vp] + [vp] * 15 + [u32]
@@ -343,6 +353,18 @@ class Context:
         d = hm_ip_lintrans_desc(x.ptr, keep[0][1], y.ptr, keep[1][1], pt.ptr, keep[2][1], ptr(addend), keep[3][1], out.ptr, keep[4][1],
                                 ptr(addend_out), keep[5][1], keep[6][1], len(mod_ids), n_terms, len(galois), keep[7][1])
         self._ck(self.L.hm_inner_product_lintrans(self.h, C.byref(d)))
+
+    def inner_product_lintrans_multi(self, x, x_limbs, y, y_limbs, pt, pt_limbs, out, out_limbs, mod_ids, n_terms, galois, n_out,
+                                     addend=None, addend_limbs=None, addend_out=None, addend_out_limbs=None):
+        """n_out weighted sums of the same hoisted key products: out[m][i][k] = sum_r pt[m][r][i] * t[r][i][k] with t as inner_product_lintrans
+        forms it, once per rotation, and addend_out[m][i] = sum_r pt[m][r][i] * automorph_{galois[r]}(addend[i]) (hm_inner_product_lintrans_multi).
+        Limb lists: x_limbs [n][n_terms], y_limbs [r][n][2][n_terms], pt_limbs [m][r][n], out_limbs [m][n][2], addend_limbs [n],
+        addend_out_limbs [m][n]"""
+        keep = [_u32(v) for v in (x_limbs, y_limbs, pt_limbs, addend_limbs, out_limbs, addend_out_limbs, mod_ids, galois)]
+        ptr = lambda v: None if v is None else v.ptr
+        d = hm_ip_lintrans_multi_desc(x.ptr, keep[0][1], y.ptr, keep[1][1], pt.ptr, keep[2][1], ptr(addend), keep[3][1], out.ptr, keep[4][1],
+                                      ptr(addend_out), keep[5][1], keep[6][1], len(mod_ids), n_terms, len(galois), n_out, keep[7][1])
+        self._ck(self.L.hm_inner_product_lintrans_multi(self.h, C.byref(d)))
 
     def inner_product_rotsum(self, x, x_limbs, y, y_limbs, out, out_limbs, mod_ids, n_terms, galois,
                              addend=None, addend_limbs=None, addend_out=None, addend_out_limbs=None):

@@ -76,11 +76,12 @@ int main(int argc, char *argv[]) {
     HROTATE *hrotate = new HROTATE("test_hrotate", maxlevel, currentlevel, alpha, config, arch);
     if (arch->world() > 1) rcclRendezvous(arch, idFile);
     hrotate->simulate();
-  } else if (ops == "hrotate_hoisted" || ops == "hlintrans" || ops == "hdot" || ops == "hrotsum") {   // build extensions: R rotations of one ciphertext with one ModUp
+  } else if (ops == "hrotate_hoisted" || ops == "hlintrans" || ops == "hdot" || ops == "hrotsum" || ops == "hbsgs") {   // build extensions: R rotations of one ciphertext with one ModUp
     OperationBase *hoisted = nullptr;                            // (config keys rotations, galois); hlintrans: their plaintext-weighted sum, one
     try {                                                        // ModDown; hdot: sum of `terms` ciphertext products, one key switch, one rescale
       if (ops == "hdot") hoisted = new HDOT("test_hdot", maxlevel, currentlevel, alpha, config, arch);
       else if (ops == "hrotsum") hoisted = new HROTSUM("test_hrotsum", maxlevel, currentlevel, alpha, config, arch);   // sum of rotations of `rotations` ciphertexts
+      else if (ops == "hbsgs") hoisted = new HBSGS("test_hbsgs", maxlevel, currentlevel, alpha, config, arch);   // baby-step/giant-step transform: `rotations` x `giants`
       else if (ops == "hlintrans") hoisted = new HLINTRANS("test_hlintrans", maxlevel, currentlevel, alpha, config, arch);
       else hoisted = new HROTATE_HOISTED("test_hrotate_hoisted", maxlevel, currentlevel, alpha, config, arch);
     } catch (const std::exception &e) {

@@ -126,6 +126,7 @@ private:
   bool fuseModDown = true;   // pass (9): the ModDown conversion inside the merged transform's first pass (default: by batch size)
   bool fuseHoist = true;     // pass (6h): the key products of rotations of one ciphertext read its digits once (hrotate_hoisted)
   bool fuseLintrans = true;  // pass (6l): ... and their plaintext-weighted sum is formed before anything is stored (hlintrans)
+  bool fuseBsgs = true;      // pass (6m): ... and M >= 2 such sums over the same rotations share the key products (hbsgs)
   bool fuseRotsum = true;    // pass (6s): the key products of rotations of different ciphertexts are summed before anything is stored (hrotsum)
   bool fuseDot = true;       // pass (5d): the tensor products of several pairs of ciphertexts are summed before anything is stored (hdot)
   uint32_t n = 0, logN = 0, clusterCount = 1;

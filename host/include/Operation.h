@@ -73,7 +73,8 @@ public:
   const Output &output() const { return out_; }                         // of upstream's constructor
 
   // inputMayBeOpInput: the input may be an op's own input ciphertext, which no instruction produces (otherwise a limb without producer throws)
-  // suffix: on every buffer and stage key, for the ops that run more than one ModUp (HROTSUM: "_Ct<i>" from the second ciphertext on)
+  // suffix: on every buffer and stage key, for the ops that run more than one ModUp (HROTSUM: "_Ct<i>" from the second ciphertext on; HBSGS:
+  // "_Giant<i>" for the intermediate ciphertexts of the giant step)
   Digits modUp(const std::vector<AddrType> &input, bool inputMayBeOpInput, const std::string &suffix = "");
   Digits rotateDigits(const Digits &digits, uint32_t galois, const std::string &suffix);
   Accumulators keyProduct(const Digits &digits, uint64_t keySeed, const std::string &suffix);  // keySeed: the synthetic stream of the key
@@ -117,7 +118,7 @@ protected:
   std::unique_ptr<AddrManage> addrManager;  // made by makeInputs(): the temporaries start after the inputs
   std::vector<Ciphertext> cts;              // the input ciphertexts ct1, ct2, ... (HDOT: ct1 .. ct<2T>, HROTSUM: ct1 .. ct<G>)
   std::unique_ptr<Plaintext> ptx;           // the input plaintext pt
-  std::vector<Plaintext> extPtx;            // the input plaintexts pt1, pt2, ... on the extended basis (HLINTRANS)
+  std::vector<Plaintext> extPtx;            // the input plaintexts pt1, pt2, ... on the extended basis (HLINTRANS; HBSGS: pt<(i-1)R+r>)
   Arch *arch;
   Config *config;
   std::string opName;       // HMULT, HROTATE, ...
@@ -133,7 +134,7 @@ protected:
   // (seed + 4000) at the current level, then `extPlaintexts` plaintexts pt<r>, r = 1.., on the extended basis (the current level's Q limbs, then
   // the alpha special primes; seed + 4000 + 100000 r), then the address plan of the temporaries behind them
   void makeInputs(uint32_t ciphertexts, bool plaintext = false, uint32_t extPlaintexts = 0);
-  // what the ops that hoist the ModUp over rotations (HROTATE_HOISTED, HLINTRANS) or sum rotations in front of one ModDown (HROTSUM) check
+  // what the ops that hoist the ModUp over rotations (HROTATE_HOISTED, HLINTRANS, HBSGS) or sum rotations in front of one ModDown (HROTSUM) check
   // first (`op` names the op in the messages): no backend = sim,
   // no world > 1; config keys `rotations` = R (default 4, 1..16) and `galois` = g (default 5, odd, below 2N).  Returns g^r mod 2N, r = 1..R, distinct
   std::vector<uint32_t> hoistedRotations(const std::string &op) const;
@@ -144,6 +145,8 @@ protected:
   // the two halves of a rotation around its key switch, shared by HROTATE (suffix "") and HROTATE_HOISTED ("_Rot<r>"): sigma_g of component k
   // of ct1 into AUTOOutput<suffix>(k); and <out>.c0 = sigma_g(c0) + ks0, <out>.c1 = ks1
   Limbs rotateComponent(uint32_t k, uint32_t galois, const std::string &suffix, uint32_t ct = 0);   // ct: of input ciphertext ct<ct + 1>
+  // ... of any `level` limbs (HBSGS: the c0 of an intermediate ciphertext), waiting for their producers `in.from` (empty: op inputs)
+  Limbs rotateLimbs(const Limbs &in, uint32_t k, uint32_t galois, const std::string &suffix);
   void finishRotation(const std::string &out, const std::vector<AddrType> &rotatedC0, const KeySwitch::Output &ks, const std::string &suffix);
   void finishConstruction();  // registers every temporary with the backend
 
@@ -202,6 +205,14 @@ class HROTSUM : public OperationBase {
 public:
   HROTSUM(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
 };
+// hbsgs (build extension): the baby-step/giant-step linear transform out = sum_i rot_{h^i}( sum_r pt<(i-1)R+r> (.) rot_{g^r}(ct1) ), i = 1..G (config
+// key giants, default 4, 1..16; galois_giant = h, default g^R mod 2N), r = 1..R (rotations, galois as hlintrans, same keys IP_Rot<r>_Key<k>_<j>), with
+// ONE ModUp of ct1 and one key product per baby rotation shared by the G inner sums; then hrotsum's body on the G intermediate ciphertexts with the
+// keys IP_Giant<i>_Key<k>_<j>.  Bit-identical to G hlintrans ops + one hrotsum.  One output ciphertext out at the input's level; no rescale.
+class HBSGS : public OperationBase {
+public:
+  HBSGS(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
+};
 class HADD : public OperationBase {
 public:
   HADD(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
@@ -225,7 +236,7 @@ class OpChain {
   std::vector<Arch *> archs;
   std::vector<OperationBase *> ops;
 public:
-  // ops: comma-separated list of hmult | hrotate | hadd | pmult | padd | hlintrans | hdot | hrotsum, e.g. "hmult,hrotate,hadd,hmult"; hrotate_hoisted (R output
+  // ops: comma-separated list of hmult | hrotate | hadd | pmult | padd | hlintrans | hdot | hrotsum | hbsgs, e.g. "hmult,hrotate,hadd,hmult"; hrotate_hoisted (R output
   // ciphertexts) only as the last op
   OpChain(const std::string &cfgPath, const std::string &opList, uint32_t maxLevel, uint32_t curLevel, uint32_t alpha,
           const std::map<std::string, uint32_t> &overrides = {});

@@ -27,7 +27,8 @@ struct Arch::Launch {
               L_IP_HOISTED,                                  // (6h) the key products of several rotations from one set of digits
               L_IP_LINTRANS,                                 // (6l) ... and their plaintext-weighted sum
               L_TENSOR_DOT,                                  // (5d) the tensor products of several pairs of ciphertexts, summed
-              L_IP_ROTSUM } kind;                            // (6s) the key products of rotations of different ciphertexts, summed
+              L_IP_ROTSUM,                                   // (6s) the key products of rotations of different ciphertexts, summed
+              L_IP_LINTRANS_MULTI } kind;                    // (6m) several plaintext-weighted sums of the same hoisted key products
   std::vector<uint32_t> hoistG;   // L_IP_HOISTED: the Galois element of every rotation (a: digits [n][T], b: keys [r][n][2][T], out: [r][n][2])
                                   // L_IP_LINTRANS: the same, with c: plaintexts [r][n], d: addend source [n] / out1: addend output [n] (HM_NO_LIMB: none; both
                                   // empty: no entry has one), out: [n][2]
@@ -43,6 +44,8 @@ struct Arch::Launch {
   uint32_t ipTerms = 0, ipOuts = 0;
                                   // L_IP_ROTSUM: hoistG = the element of every ciphertext; a: digits [c][n][T], b: keys [c][n][2][T], d: addend sources
                                   // [c][n] / out1: addend output [n] (HM_NO_LIMB: none; both empty: no entry has one), out: [n][2]
+                                  // L_IP_LINTRANS_MULTI: as L_IP_LINTRANS with multiOuts groups: c: plaintexts [m][r][n], out: [m][n][2], out1: [m][n]
+  uint32_t multiOuts = 0;
   uint32_t dotTerms = 0;          // L_TENSOR_DOT: pairs per record (a, b, c, d: [n][dotTerms], roles as L_TENSOR; out, out1, out2: [n])
   std::string name;
   std::string statKey;
@@ -141,6 +144,9 @@ Arch::Arch(Config *cfg) : config(cfg) {
   // (6s) hrotsum: the key products of rotations of different ciphertexts, the sums over the ciphertexts and the rotated c0's become one
   // hm_inner_product_rotsum launch.  Config key fuse_rotsum (default 1).
   fuseRotsum = cfg->getValueOr("fuse_rotsum", 1) != 0;
+  // (6m) hbsgs: the key products of the baby rotations and the M >= 2 weighted sums over them become one hm_inner_product_lintrans_multi launch.
+  // Config key fuse_bsgs (default 1).
+  fuseBsgs = cfg->getValueOr("fuse_bsgs", 1) != 0;
   // sharded runs: the exchanges of digit j+1 run on the context's exchange stream while digit j converts and transforms (SURVEY.md 7:
   // 2 beta + 2 all-to-alls per key switch instead of 4, same order on every rank).  The per-digit transforms must then stay separate
   // launches, so the fused NTT x key kernel (which needs all digits) is not used.
@@ -284,6 +290,7 @@ typedef std::vector<const Part *> Group;
 // records of one stage with equal keys go into one C-ABI call (same kind / opcode / direction / operand shape)
 int partKey(const Instruction &i) {
   if (!i.ipSumX.empty()) return 9000 + (int)i.ipX.size() * 100 + (int)i.ipSumX.size();                     // 9000+: sum of rotations of different ciphertexts, by digits and ciphertexts
+  if (!i.ipMultiPt.empty()) return 10000 + (int)i.ipX.size() * 400 + ((int)i.ipHoistG.size() - 1) * 17 + (int)i.ipMultiPt.size();   // 10000+: several weighted sums, by digits, rotations and groups
   if (!i.ipLinPt.empty()) return 7000 + (int)i.ipX.size() * 100 + (int)i.ipHoistG.size();                  // 7000+: weighted sum of hoisted key products, by digits and rotations
   if (i.ipHoistG.size() == 1) return 20000 + (int)i.ipX.size() + 8 * (int)i.ipHoistG[0];                   // 20000+: hoisted key product of ONE rotation, by digits and element (hrotsum with fuse_rotsum = 0: one per ciphertext)
   if (!i.ipHoistG.empty()) return 6000 + (int)i.ipX.size() * 100 + (int)i.ipHoistG.size();                 // 6000+: hoisted key product, by digits and rotations
@@ -412,6 +419,7 @@ struct Arch::LaunchBuilder {
   void ipHoisted(Launch &L, Recs recs);
   void ipLintrans(Launch &L, Recs recs);
   void ipRotsum(Launch &L, Recs recs);
+  void ipLintransMulti(Launch &L, Recs recs);
   void nttIp(Launch &L, Recs recs);
   void ip(Launch &L, Recs recs);
   void tensor(Launch &L, Recs recs);
@@ -454,6 +462,35 @@ void Arch::LaunchBuilder::ipLintrans(Launch &L, Recs recs) {
   // limb-polys touched: the digits and the addend source once (every rotation gathers from the same ones), keys and plaintext once per rotation,
   // two outputs per entry and one per addend
   L.bytes = ((unsigned long long)recs.size() * (L.ipTerms + 2 * R * L.ipTerms + R + 2) + (unsigned long long)addends * 2) * LP;
+}
+
+// (6m) M weighted sums of the same hoisted key products: the hoisted launch's digits and keys, plaintexts c [m][r][n], outputs out [m][n][2]; entries
+// with an addend: source d [n], outputs out1 [m][n] (hm_ip_lintrans_multi_desc)
+void Arch::LaunchBuilder::ipLintransMulti(Launch &L, Recs recs) {
+  L.kind = Launch::L_IP_LINTRANS_MULTI;
+  const size_t R = hoistedOperands(L, recs, "weighted rotations (several sums)"), M = recs[0]->ipMultiPt.size();
+  L.multiOuts = (uint32_t)M;
+  size_t addends = 0;
+  for (Instruction *i : recs) {
+    if (i->ipMultiPt.size() != M) throw std::runtime_error("weighted rotations (several sums): the records of one launch form different numbers of sums");
+    addends += i->ipLinAddend != 0;
+  }
+  auto outOf = [](const Instruction *i, size_t x) { return x == 0 ? i->OutputOperand : i->extraOutputs[x - 1]; };
+  if (addends)
+    for (Instruction *i : recs) L.d.push_back(i->ipLinAddend ? limb(i->ipLinAddend) : HM_NO_LIMB);
+  for (size_t m = 0; m < M; ++m) {
+    for (Instruction *i : recs) {
+      const size_t w = i->ipLinAddend ? 3 : 2;
+      L.out.push_back(limb(outOf(i, m * w))); L.out.push_back(limb(outOf(i, m * w + 1)));
+      if (addends) L.out1.push_back(i->ipLinAddend ? limb(outOf(i, m * w + 2)) : HM_NO_LIMB);
+    }
+    for (size_t r = 0; r < R; ++r)
+      for (Instruction *i : recs) L.c.push_back(limb(i->ipMultiPt[m][r]));
+  }
+  // limb-polys touched: a workgroup serves a tile of outputs, so the digits, the keys and the addend source are read once per tile; every group's
+  // plaintexts once; two outputs per entry and group and one per addend and group
+  const unsigned long long tiles = (M + HM_IP_LINTRANS_MULTI_TILE - 1) / HM_IP_LINTRANS_MULTI_TILE;
+  L.bytes = ((unsigned long long)recs.size() * (tiles * (L.ipTerms + 2 * R * L.ipTerms) + M * R + 2 * M) + (unsigned long long)addends * (tiles + M)) * LP;
 }
 
 // (6s) one sum of rotations of different ciphertexts: digits a [c][n][T], keys b [c][n][2][T], outputs out [n][2]; entries with addends: sources
@@ -697,6 +734,7 @@ void Arch::LaunchBuilder::emitCompute(const Group &group, Launches &front, Launc
   for (const Part *g : group) L->name += (L->name.empty() ? "" : "+") + g->name;
   for (Instruction *i : recs) L->refInstructions += i->refInstructions * (i->ops == BCONV_STEP2 ? bconvPorts : 1ull) + i->refExtra;
   if (f->ops == IP && !f->ipSumX.empty()) ipRotsum(*L, recs);
+  else if (f->ops == IP && !f->ipMultiPt.empty()) ipLintransMulti(*L, recs);
   else if (f->ops == IP && !f->ipLinPt.empty()) ipLintrans(*L, recs);
   else if (f->ops == IP && !f->ipHoistG.empty()) ipHoisted(*L, recs);
   else if (f->ops == IP && transformsInside(*f)) nttIp(*L, recs);
@@ -949,7 +987,7 @@ void Arch::replicateForBatch() {
       l->bytes *= batch_;
       continue;
     }
-    if (l->kind == Launch::L_IP_HOISTED || l->kind == Launch::L_IP_LINTRANS || l->kind == Launch::L_IP_ROTSUM) {
+    if (l->kind == Launch::L_IP_HOISTED || l->kind == Launch::L_IP_LINTRANS || l->kind == Launch::L_IP_ROTSUM || l->kind == Launch::L_IP_LINTRANS_MULTI) {
       // entry-major as the inner product below (the ops of a batch share the keys), inside every rotation's block of keys and outputs
       const size_t n0 = l->mods.size();
       auto inter = [&](std::vector<uint32_t> &v, size_t blocks, size_t width, bool isLimb) {
@@ -969,6 +1007,10 @@ void Arch::replicateForBatch() {
       else if (l->kind == Launch::L_IP_ROTSUM) {   // every ciphertext its own digits and addend source
         inter(l->out, 1, 2, true);
         if (!l->d.empty()) { inter(l->d, R, 1, true); inter(l->out1, 1, 1, true); }
+      } else if (l->kind == Launch::L_IP_LINTRANS_MULTI) {   // every group its own plaintexts and outputs
+        const size_t M = l->multiOuts;
+        inter(l->out, M, 2, true); inter(l->c, M * R, 1, true);
+        if (!l->d.empty()) { inter(l->d, 1, 1, true); inter(l->out1, M, 1, true); }
       } else {
         inter(l->out, 1, 2, true); inter(l->c, R, 1, true);
         if (!l->d.empty()) { inter(l->d, 1, 1, true); inter(l->out1, 1, 1, true); }
@@ -1105,7 +1147,8 @@ void Arch::prepare() {
 }
 
 static const char *const kLaunchKindNames[] = {"NTT", "INTT", "EWE", "BCONV", "AUTO", "NTT_SUBSCALE", "TENSOR", "EXCH_IN", "EXCH_OUT", "REPLICATE", "IP", "NTT_IP",
-                                               "BCONV_COL", "EXCH_IN_COL", "EXCH_OUT_COL", "IP_HOISTED", "IP_LINTRANS", "TENSOR_DOT", "IP_ROTSUM"};
+                                               "BCONV_COL", "EXCH_IN_COL", "EXCH_OUT_COL", "IP_HOISTED", "IP_LINTRANS", "TENSOR_DOT", "IP_ROTSUM",
+                                               "IP_LINTRANS_MULTI"};
 
 // Per-launch device time (SURVEY.md §8d "per-stage hipEvent times", exchange time at N > 1): every launch of the plan
 // bracketed by its own event pair, in plan order so that the data dependencies (and, sharded, the collectives) line up.
@@ -1135,7 +1178,7 @@ std::string Arch::planText() const {
     size_t cnt = l->out.size();
     if (l->kind == Launch::L_BCONV || l->kind == Launch::L_BCONV_COL) { cnt = 0; for (auto &q : l->probs) cnt += q.out.size(); }
     if (l->kind == Launch::L_IP || l->kind == Launch::L_NTT_IP || l->kind == Launch::L_IP_HOISTED || l->kind == Launch::L_IP_LINTRANS ||
-        l->kind == Launch::L_IP_ROTSUM)
+        l->kind == Launch::L_IP_ROTSUM || l->kind == Launch::L_IP_LINTRANS_MULTI)
       cnt = l->mods.size();
     out += std::string(names[l->kind]) + " " + l->name + " n=" + std::to_string(cnt) + " ref=" + std::to_string(l->refInstructions);
     // pass 11: limb-polys an inverse transform stores split-30 packed / conversions (separate or inside a transform's first pass) that read packed inputs
@@ -1157,6 +1200,8 @@ std::string Arch::planText() const {
     if (l->kind == Launch::L_TENSOR_DOT) out += " terms=" + std::to_string(l->dotTerms);   // (5d): pairs summed per record
     if (l->kind == Launch::L_IP_LINTRANS)   // (6l): entries that also form the addend output
       out += " addend=" + std::to_string(l->d.size() - (size_t)std::count(l->d.begin(), l->d.end(), HM_NO_LIMB));
+    if (l->kind == Launch::L_IP_LINTRANS_MULTI)   // (6m): groups, entries that also form the groups' addend outputs
+      out += " out=" + std::to_string(l->multiOuts) + " addend=" + std::to_string(l->d.size() - (size_t)std::count(l->d.begin(), l->d.end(), HM_NO_LIMB));
     if (l->kind == Launch::L_IP_ROTSUM)   // (6s): entries that also form the addend output
       out += " addend=" + std::to_string(l->out1.size() - (size_t)std::count(l->out1.begin(), l->out1.end(), HM_NO_LIMB));
     if (l->recordSlot >= 0) out += " mark=" + std::to_string(l->recordSlot);
@@ -1190,6 +1235,7 @@ std::string Arch::planDump() const {
            " ipTerms=" + std::to_string(l->ipTerms) + " ipOuts=" + std::to_string(l->ipOuts) + " ref=" + std::to_string(l->refInstructions) + " bytes=" + std::to_string(l->bytes) +
            " mark=" + std::to_string(l->recordSlot) + " xin=" + indexOf(l->xin) + " xout=" + indexOf(l->xout);
     if (l->dotTerms) out += " terms=" + std::to_string(l->dotTerms);
+    if (l->multiOuts) out += " multiOuts=" + std::to_string(l->multiOuts);
     vec("wait", l->waitSlots); vec("hoistG", l->hoistG); vec("ipCoeff", l->ipCoeff); vec("ipInv", l->ipInv); vec("outPacked", l->outPacked);
     vec("inGalois", l->inGalois); vec("addGalois", l->addGalois);
     vec("a", l->a); vec("b", l->b); vec("c", l->c); vec("d", l->d); vec("out", l->out); vec("out1", l->out1); vec("out2", l->out2);
@@ -1253,6 +1299,14 @@ void Arch::enqueue(Launch &l) {
                                    add ? pool : nullptr, add ? l.out1.data() : nullptr, l.mods.data(), (uint32_t)l.mods.size(), l.ipTerms,
                                    (uint32_t)l.hoistG.size(), l.hoistG.data()};
     st = hm_inner_product_lintrans(ctx, &d);
+    break;
+  }
+  case Launch::L_IP_LINTRANS_MULTI: {
+    const bool add = !l.d.empty();
+    const hm_ip_lintrans_multi_desc d = {pool, l.a.data(), pool, l.b.data(), pool, l.c.data(), add ? pool : nullptr, add ? l.d.data() : nullptr, pool,
+                                         l.out.data(), add ? pool : nullptr, add ? l.out1.data() : nullptr, l.mods.data(), (uint32_t)l.mods.size(),
+                                         l.ipTerms, (uint32_t)l.hoistG.size(), l.multiOuts, l.hoistG.data()};
+    st = hm_inner_product_lintrans_multi(ctx, &d);
     break;
   }
   case Launch::L_IP_ROTSUM: {

@@ -406,8 +406,12 @@ void OperationBase::dispatch(const StageList &m) {
   for (const auto &stage : m) driver.dispatchInstructions(stage.first, stage.second);
 }
 Limbs OperationBase::rotateComponent(uint32_t k, uint32_t galois, const std::string &suffix, uint32_t ct) {
+  return rotateLimbs(Limbs{component(ct, k), {}}, k, galois, suffix);
+}
+Limbs OperationBase::rotateLimbs(const Limbs &in, uint32_t k, uint32_t galois, const std::string &suffix) {
   PerLimb s{label + "_AUTO" + suffix + "_Level(", ")_k(" + S(k) + ")", range(0, level_), alloc("AUTOOutput" + suffix + "(" + S(k) + ")", level_)};
-  s.a = component(ct, k);
+  s.a = in.addr;
+  if (!in.from.empty()) s.after = {&in.from};
   const Limbs rotated{s.out, autoLimbs(&insgener, galois, s)};
   driver.dispatchInstructions("AUTO" + suffix + "_Key(" + S(k) + ")", rotated.from);
   return rotated;
@@ -802,6 +806,119 @@ HROTSUM::HROTSUM(std::string labelName, uint32_t maxLevel, uint32_t currentLevel
   finishConstruction();
 }
 
+// hbsgs (build extension).  The baby-step/giant-step linear transform out = sum_i rot_{h_i}( sum_r pt_{i,r} (.) rot_{g_r}(ct1) ), g_r = g^r, h_i = h^i mod 2N
+// (the double-hoisted baby step of Bossuat et al. in front of hrotsum's giant step):
+//   D_j = ModUp(c1)                                     ONCE, on the unrotated c1
+//   acc_{r,k} = sum_j sigma_{g_r}(D_j) evk_r[j][k]      once per baby rotation (suffix _Rot<r>), hlintrans's keys
+//   S_{i,k} = sum_r pt_{i,r} acc_{r,k}   (E limbs),   U_i = sum_r pt_{i,r}[Q limbs] sigma_{g_r}(c0)   (l limbs)      per giant step, HLINTRANS's MUL /
+//                                                       MAC_ADD stages with every buffer and stage key carrying _Grp<i>; pt_{i,r} = pt<(i-1)R+r>
+//   v_i = (U_i + ModDown(S_{i,0}), ModDown(S_{i,1}))    modDown(.., "_Grp<i>") and an ADD: G intermediate ciphertexts at level l
+//   out = hrotsum(v_1 .. v_G)                           HROTSUM's body with elements h_i, ModUps and stages suffixed _Giant<i>, keys IP_Giant<i>_Key<k>_<j>
+//                                                       (stream seed + 10000 + 100000 (16 + i))
+// Every sum is formed by the element-wise chains of HLINTRANS and HROTSUM: bit-identical to G hlintrans ops on ct1 (op i with the plaintexts pt_{i,.})
+// followed by one hrotsum of their outputs with galois = h.  Unfused, the stages run one launch each; fused, pass (6m) of Arch::fusePasses
+// (Planner.cpp) turns the baby key products and the G weighted sums into one launch and pass (6s) the giant step into another.
+// Not built: identity steps on either axis, carrying S_{i,0} to the end on the extended basis, a rescale, the sharded plan.
+HBSGS::HBSGS(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch)
+    : OperationBase("HBSGS", labelName, cfg, _arch, maxLevel, currentLevel, alpha) {
+  const std::vector<uint32_t> gs = hoistedRotations("hbsgs");
+  const uint32_t R = (uint32_t)gs.size(), G = cfg->getValueOr("giants", 4), twoN = 2 * N;
+  if (G < 1 || G > 16) throw std::runtime_error("hbsgs: giants = " + S(G) + ", must be in [1, 16]");
+  const uint32_t h = cfg->getValueOr("galois_giant", gs.back());   // default g^R mod 2N
+  if (!(h & 1) || h >= twoN) throw std::runtime_error("hbsgs: galois_giant = " + S(h) + " must be odd and below 2N = " + S(twoN));
+  std::vector<uint32_t> hs;
+  uint64_t hi = 1;
+  for (uint32_t i = 1; i <= G; ++i) {
+    hi = hi * h % twoN;
+    if (std::find(hs.begin(), hs.end(), (uint32_t)hi) != hs.end())
+      throw std::runtime_error("hbsgs: galois_giant^" + S(i) + " mod 2N repeats an element: the " + S(G) + " giant steps are not distinct");
+    hs.push_back((uint32_t)hi);
+  }
+  makeInputs(1, /*plaintext=*/false, /*extPlaintexts=*/G * R);
+
+  KeySwitch ks(labelName, maxLevel, currentLevel, alpha, &Datapool, &DataInsMap, &insgener, addrManager.get());
+  std::vector<uint32_t> extMods = range(0, currentLevel);
+  for (uint32_t p : range(maxLevel, alpha)) extMods.push_back(p);
+  const std::array<std::string, 3> tags = {"Key0", "Key1", "C0"};
+  // the baby step: one ModUp, one key product and one rotated c0 per baby rotation
+  const KeySwitch::Digits digits = ks.modUp(cts[0].getC1Addr(), /*inputMayBeOpInput=*/true);
+  dispatch(ks.takeStages());
+  std::array<std::vector<Limbs>, 3> terms;   // per baby rotation: acc_{r,0}, acc_{r,1}, sigma_r(c0)
+  for (uint32_t r = 1; r <= R; ++r) {
+    const std::string rs = "_Rot" + S(r);
+    const KeySwitch::Accumulators acc = ks.keyProduct(ks.rotateDigits(digits, gs[r - 1], rs), seed + 10000 + 100000ull * r, rs);
+    dispatch(ks.takeStages());
+    terms[0].push_back(acc[0]); terms[1].push_back(acc[1]); terms[2].push_back(rotateComponent(0, gs[r - 1], rs));
+  }
+  // per giant step i: the three weighted sums as HLINTRANS emits them, the ModDown and the ADD of U_i
+  std::vector<Limbs> vc0;                        // v_i.c0
+  std::vector<std::vector<AddrType>> vc1;        // v_i.c1
+  for (uint32_t i = 1; i <= G; ++i) {
+    const std::string gp = "_Grp" + S(i);
+    std::array<Limbs, 3> sums;
+    for (uint32_t t = 0; t < 3; ++t) {
+      Limbs &sum = sums[t];
+      for (uint32_t r = 0; r < R; ++r) {
+        const std::vector<AddrType> pt = namedInputs.at("pt" + S((i - 1) * R + r + 1));
+        const std::string at = "(" + S(r + 1) + ")_" + tags[t] + gp;
+        PerLimb s{labelName + "_LinTrans" + gp + "_" + tags[t] + "_Rot(" + S(r + 1) + ")_Level(", ")", t < 2 ? extMods : range(0, currentLevel),
+                  alloc(r + 1 < R ? "LinTransOut_temp" + at : "LinTransOut_" + tags[t] + gp, t < 2 ? currentLevel + alpha : currentLevel)};
+        s.a = terms[t][r].addr;
+        s.b = t < 2 ? pt : slice(pt, 0, currentLevel);
+        s.after = {&terms[t][r].from};
+        const Limbs before = sum;
+        if (r) {
+          s.c = before.addr;
+          s.after.push_back(&before.from);
+        }
+        sum = {s.out, eweLimbs(&insgener, r ? EWE_MAC_ADD : EWE_MUL, s)};
+        driver.dispatchInstructions("LinTrans_" + at, sum.from);
+      }
+    }
+    const KeySwitch::Output down = ks.modDown({sums[0], sums[1]}, gp);
+    dispatch(ks.takeStages());
+    PerLimb s{labelName + "_HBSGSadd" + gp + "_Level(", ")", range(0, currentLevel), alloc("HBSGSInner" + gp + "(0)", currentLevel)};
+    s.a = down[0];
+    s.c = sums[2].addr;
+    vc0.push_back({s.out, eweLimbs(&insgener, EWE_ADD, s)});
+    driver.dispatchInstructions("HBSGS_Hadd" + gp, vc0.back().from);
+    vc1.push_back(down[1]);
+  }
+  // the giant step: HROTSUM's body on the v_i
+  std::array<Limbs, 3> sums;   // T_0, T_1, V so far
+  for (uint32_t i = 1; i <= G; ++i) {
+    const std::string gt = "_Giant" + S(i);
+    const KeySwitch::Digits dg = ks.modUp(vc1[i - 1], /*inputMayBeOpInput=*/false, gt);
+    const KeySwitch::Accumulators acc = ks.keyProduct(ks.rotateDigits(dg, hs[i - 1], gt), seed + 10000 + 100000ull * (16 + i), gt);
+    dispatch(ks.takeStages());
+    const std::array<Limbs, 3> term = {acc[0], acc[1], rotateLimbs(vc0[i - 1], 0, hs[i - 1], gt)};
+    if (i == 1) {
+      sums = term;
+      continue;
+    }
+    for (uint32_t t = 0; t < 3; ++t) {
+      const std::string at = "(" + S(i) + ")_" + tags[t];
+      PerLimb s{labelName + "_GiantSum_" + tags[t] + "_Ct(" + S(i) + ")_Level(", ")", t < 2 ? extMods : range(0, currentLevel),
+                alloc(i < G ? "GiantSum_" + at : "GiantSumOut_" + tags[t], t < 2 ? currentLevel + alpha : currentLevel)};
+      const Limbs before = sums[t];
+      s.a = before.addr;
+      s.c = term[t].addr;
+      s.after = {&before.from, &term[t].from};
+      sums[t] = {s.out, eweLimbs(&insgener, EWE_ADD, s)};
+      driver.dispatchInstructions("GiantSum_" + at, sums[t].from);
+    }
+  }
+  const KeySwitch::Output down = ks.modDown({sums[0], sums[1]}, "");
+  dispatch(ks.takeStages());
+  PerLimb s{labelName + "_HBSGSadd_Level(", ")", range(0, currentLevel), alloc("HBSGSOutput(0)", currentLevel)};
+  s.a = down[0];
+  s.c = sums[2].addr;
+  driver.dispatchInstructions("HBSGS_Hadd", eweLimbs(&insgener, EWE_ADD, s));
+  setOutput("out", 0, s.out);
+  setOutput("out", 1, down[1]);
+  finishConstruction();
+}
+
 // reference: HADD::HADD :1114-1176
 HADD::HADD(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch)
     : OperationBase("HADD", labelName, cfg, _arch, maxLevel, currentLevel, alpha) {
@@ -857,6 +974,7 @@ static OperationBase *makeOp(const std::string &o, uint32_t maxLevel, uint32_t l
   if (o == "hlintrans") return new HLINTRANS("test_hlintrans", maxLevel, level, alpha, cfg, arch);
   if (o == "hdot") return new HDOT("test_hdot", maxLevel, level, alpha, cfg, arch);
   if (o == "hrotsum") return new HROTSUM("test_hrotsum", maxLevel, level, alpha, cfg, arch);
+  if (o == "hbsgs") return new HBSGS("test_hbsgs", maxLevel, level, alpha, cfg, arch);
   throw std::runtime_error("Error operation requirement, please double confirm!");
 }
 

@@ -2,6 +2,7 @@
 // All of them preserve every value that a later stage or the caller can observe except the intermediates they eliminate (listed in
 // DESIGN.md §5).  What a record reads and writes is asked of Records.h; a pass that needs "who reads this address" filters recordReads().
 #include <algorithm>
+#include <array>
 #include <iterator>
 #include <set>
 
@@ -60,6 +61,7 @@ struct Arch::Planner {
     std::vector<DigitsKey> order;   // first appearance
   };
   RotationGroups rotationGroups(Readers &rd);
+  void sharedWeightedRotations();   // 6m
   void sumOfRotations();      // 6s
   void weightedRotations();   // 6l
   void hoist();               // 6h
@@ -84,6 +86,7 @@ void Arch::fusePasses(std::vector<Stage> &st) {
   p.tensor();
   if (fuseDot) p.tensorDot();   // before (6): the multiply-accumulate chains it absorbs are not key products
   p.keyProduct();
+  if (fuseBsgs) p.sharedWeightedRotations();   // before (6s), (6l) and (6h): the records it merges are the ones they would claim
   if (fuseRotsum) p.sumOfRotations();        // before (6l) and (6h): each record it merges is a group of one rotation to them
   if (fuseLintrans) p.weightedRotations();   // before (6h): the records it merges are the ones (6h) would claim
   if (fuseHoist) p.hoist();
@@ -356,6 +359,8 @@ void Arch::Planner::tensorDot() {
 
 // (6) inner product with the evaluation key: the chain MAC2 / MAC_ADD ... of one key collapses into a single sum
 //     of products, and the two keys (same ext operands) into one two-output record (the HPIP unit's job).
+//     Two chains whose second operands are all weights shared between sums (unproduced, with further MUL / MAC_ADD readers) are left alone: the
+//     weighted sums of hbsgs share their terms between groups and their plaintexts between sums; a key limb has one reader.
 //     Reads: fusedTensor (5).  Sets on the later chain's last record: ops = IP, ipX, ipY, OutputOperand, extraOutputs.
 void Arch::Planner::keyProduct() {
   struct Dot { std::vector<AddrType> x, y; std::vector<Instruction *> members; };
@@ -380,6 +385,7 @@ void Arch::Planner::keyProduct() {
     dots[i] = d;
   }
   // keep the dots that end a chain (nobody extends them) and have a partner with the same x list or >= 3 terms
+  Readers rd = readers();   // as the records stand in front of this pass
   std::set<Instruction *> extended;
   for (auto &kv : dots)   // (fills a set: the iteration order leaks nowhere)
     for (size_t m = 0; m + 1 < kv.second.members.size(); ++m) extended.insert(kv.second.members[m]);
@@ -394,6 +400,17 @@ void Arch::Planner::keyProduct() {
     Instruction *a = partner->second;  // first key
     Dot &da = dots[a];
     if (a->ops == IP) continue;        // already paired
+    // Two chains that share their terms are NOT the two keys of a key product when every second operand of the later one is a weight shared
+    // between sums: nobody produces it and it has further readers, all of them MUL / MAC_ADD records that multiply by it too (hbsgs: the
+    // plaintext limbs of group m, read by its S_0, S_1 and U chains).  Those chains are (6m)'s.  The rule holds for every op and whatever
+    // fuse_bsgs says (the chains then stay element-wise); a key limb has one reader, so no key product of an existing op meets it, and an op
+    // that one day shares key limbs between two key products in exactly this way would have to be told apart here
+    auto sharedWeight = [&](AddrType y) {
+      auto &r = rd[y];
+      return r.size() > 1 && !producerOf(y) && std::all_of(r.begin(), r.end(), [&](Instruction *u) {
+        return u->ops == MULT && (u->opcode == EWE_MUL || u->opcode == EWE_MAC_ADD) && u->operandList[1] == y; });
+    };
+    if (std::all_of(d.y.begin(), d.y.end(), sharedWeight)) continue;
     // `i` (the later one) carries the fused record so that it is scheduled after every member of both chains
     const AddrType outFirst = a->OutputOperand, outSecond = i->OutputOperand;
     i->ops = IP;
@@ -431,6 +448,145 @@ Arch::Planner::RotationGroups Arch::Planner::rotationGroups(Readers &rd) {
       g.members[key].push_back({ip, autos});
     }
   return g;
+}
+
+// (6m) M >= 2 weighted sums of the SAME rotations (hbsgs, the baby step): the records (6l) would merge, when every rotation's two outputs are read
+//      by exactly M chains MUL, MAC_ADD ... against operands nobody produces (plaintexts), S_{m,k} = sum_r acc_{r,k} * pt_{m,r}, chain m using
+//      the same plaintext limb for k = 0 and k = 1 at every rotation, merge WITH all 2M chains into one record per (modulus, digit list):
+//      hm_inner_product_lintrans_multi forms every rotation's key product once and the M weighted sums in registers, and stores the S_{m,k} only.
+//      If every group m also has a chain that multiplies its plaintext limbs with automorphisms, by the rotations' elements, of ONE source (the Q
+//      limbs: U_m = sum_r sigma_r(c0) * pt_{m,r}; the M chains share the R automorphisms), the M chains join as addend outputs.  M = 1 is (6l)'s and
+//      stays untouched.  Never written: the rotated digits, the per-rotation sums, the rotated c0.  The first key-product record in stage order
+//      carries the merged one, as in (6l).
+//      Reads: the key-product records of (6).  Sets on the carrying record: ipX (the unrotated digits), ipY, ipHoistG, ipLinPt (group 0),
+//      ipMultiPt, ipLinAddend, OutputOperand, extraOutputs (group-major).  A non-empty ipHoistG keeps (7), (7b) and (12) off it.
+void Arch::Planner::sharedWeightedRotations() {
+  Readers rd = readers();
+  RotationGroups found = rotationGroups(rd);
+  typedef std::vector<Instruction *> Chain;
+  auto chainFrom = [&](Instruction *first, size_t length) {   // as in (6l)
+    Chain c;
+    for (Instruction *i = first; c.size() < length;) {
+      c.push_back(i);
+      if (c.size() == length) break;
+      auto &next = rd[i->OutputOperand];
+      if (next.size() != 1 || !live(next[0]) || next[0]->ops != MULT || next[0]->opcode != EWE_MAC_ADD || next[0]->operandList[2] != i->OutputOperand ||
+          next[0]->mod_id != first->mod_id)
+        return Chain();
+      i = next[0];
+    }
+    return c;
+  };
+  auto isMul = [&](Instruction *i, uint32_t mod) { return live(i) && i->ops == MULT && i->opcode == EWE_MUL && i->mod_id == mod; };
+  for (const DigitsKey &key : found.order) {
+    const auto &mem = found.members[key];
+    const size_t R = mem.size();
+    if (R > HM_IP_LINTRANS_MAX_ROT) continue;
+    std::set<uint32_t> distinct;
+    for (auto &m : mem) distinct.insert(m.second[0]->galois);
+    if (distinct.size() != R) continue;   // two records by one element are not rotations of one ciphertext
+    auto outOf = [&](size_t r, size_t k) { return k == 0 ? mem[r].first->OutputOperand : mem[r].first->extraOutputs[0]; };
+    const size_t M = rd[outOf(0, 0)].size();
+    if (M < 2 || M > HM_IP_LINTRANS_MULTI_MAX_OUT) continue;   // M = 1: (6l)
+    // S_{m,k}: the chains in the stage order of their first links at k = 0; the k = 1 chain of group m is the one with group m's plaintexts
+    std::vector<std::array<Chain, 2>> S(M);
+    std::vector<std::vector<AddrType>> pt(M);
+    bool ok = true;
+    for (size_t m = 0; m < M && ok; ++m) {
+      Instruction *first = rd[outOf(0, 0)][m];
+      ok = isMul(first, key.first) && first->operandList[0] == outOf(0, 0);
+      if (!ok) break;
+      S[m][0] = chainFrom(first, R);
+      ok = S[m][0].size() == R;
+      for (size_t r = 0; r < R && ok; ++r) {
+        Instruction *l = S[m][0][r];
+        ok = l->operandList[0] == outOf(r, 0) && !producerOf(l->operandList[1]);
+        if (ok) pt[m].push_back(l->operandList[1]);
+      }
+    }
+    auto &first1 = rd[outOf(0, 1)];
+    ok = ok && first1.size() == M;
+    for (size_t x = 0; x < M && ok; ++x) {
+      ok = isMul(first1[x], key.first) && first1[x]->operandList[0] == outOf(0, 1);
+      if (!ok) break;
+      size_t m = 0;
+      while (m < M && !(S[m][1].empty() && pt[m][0] == first1[x]->operandList[1])) ++m;
+      ok = m < M;
+      if (!ok) break;
+      S[m][1] = chainFrom(first1[x], R);
+      ok = S[m][1].size() == R;
+      for (size_t r = 0; r < R && ok; ++r) ok = S[m][1][r]->operandList[0] == outOf(r, 1) && S[m][1][r]->operandList[1] == pt[m][r];
+    }
+    // every rotation's outputs are read by these 2M chains and nothing else
+    for (size_t r = 0; r < R && ok; ++r)
+      for (size_t k = 0; k < 2 && ok; ++k) {
+        auto &readers = rd[outOf(r, k)];
+        ok = readers.size() == M;
+        for (size_t m = 0; m < M && ok; ++m) ok = std::find(readers.begin(), readers.end(), S[m][k][r]) != readers.end();
+      }
+    if (!ok) continue;
+    // U_m: a third MUL reader of group m's first plaintext limb whose chain multiplies pt_{m,r} with sigma_r of the one source; all or none
+    std::vector<Chain> U(M);
+    std::vector<Instruction *> addendAutos;
+    AddrType addend = 0;
+    bool allU = true;
+    for (size_t m = 0; m < M && allU; ++m) {
+      for (Instruction *u : rd[pt[m][0]]) {
+        if (u == S[m][0][0] || u == S[m][1][0] || !isMul(u, key.first) || u->operandList[1] != pt[m][0]) continue;
+        Chain c = chainFrom(u, R);
+        std::vector<Instruction *> autos;
+        for (size_t r = 0; r < c.size(); ++r) {
+          Instruction *l = c[r], *a = producerOf(l->operandList[0]);
+          if (l->operandList[1] != pt[m][r] || !a || a->ops != AUTO || !live(a) || a->mod_id != key.first || a->galois != mem[r].second[0]->galois ||
+              rd[l->operandList[0]].size() != M || (r && a->operandList[0] != autos[0]->operandList[0]) || (m && a != addendAutos[r]))
+            break;
+          autos.push_back(a);
+        }
+        if (autos.size() != R) continue;
+        U[m] = c;
+        if (m == 0) { addendAutos = autos; addend = autos[0]->operandList[0]; }
+        break;
+      }
+      allU = !U[m].empty();
+    }
+    for (size_t r = 0; r < R && allU; ++r)   // the rotated source is read by the M chains and nothing else
+      for (Instruction *reader : rd[addendAutos[r]->OutputOperand]) {
+        bool mine = false;
+        for (size_t m = 0; m < M; ++m) mine = mine || reader == U[m][r];
+        allU = allU && mine;
+      }
+    if (!allU) addend = 0;
+    Instruction *c = mem[0].first;
+    std::vector<std::vector<AddrType>> ys;
+    std::vector<uint32_t> gs;
+    auto absorb = [&](Instruction *i) { if (i != c && live(i)) { c->refInstructions += i->refInstructions; dead.insert(i); } };
+    for (size_t r = 0; r < R; ++r) {
+      ys.insert(ys.end(), mem[r].first->ipY.begin(), mem[r].first->ipY.end());
+      gs.push_back(mem[r].second[0]->galois);
+      absorb(mem[r].first);
+      for (Instruction *a : mem[r].second) absorb(a);
+      for (size_t m = 0; m < M; ++m) {
+        for (size_t k = 0; k < 2; ++k) absorb(S[m][k][r]);
+        if (addend) absorb(U[m][r]);
+      }
+      if (addend) absorb(addendAutos[r]);
+    }
+    std::vector<AddrType> outs;
+    for (size_t m = 0; m < M; ++m) {
+      outs.push_back(S[m][0].back()->OutputOperand);
+      outs.push_back(S[m][1].back()->OutputOperand);
+      if (addend) outs.push_back(U[m].back()->OutputOperand);
+    }
+    c->ipX = key.second;
+    c->ipY = ys;
+    c->ipHoistG = gs;
+    c->ipLinPt = pt[0];
+    c->ipMultiPt = pt;
+    c->ipLinAddend = addend;
+    c->OutputOperand = outs[0];
+    c->extraOutputs.assign(outs.begin() + 1, outs.end());
+    for (const Write &w : recordWrites(*c)) producer[w.addr] = c;
+  }
 }
 
 // (6s) sum of rotations of DIFFERENT ciphertexts (hrotsum): key-product records of (6) with one modulus whose digits are all automorphisms, one

@@ -230,6 +230,31 @@ typedef struct hm_ip_lintrans_desc {
   const uint32_t *galois;                                     /* [n_rot] */
 } hm_ip_lintrans_desc;
 hm_status hm_inner_product_lintrans(hm_ctx *ctx, const hm_ip_lintrans_desc *desc);
+/* n_out plaintext-weighted sums of the SAME hoisted key products (hbsgs): the baby step of a baby-step/giant-step linear
+ * transform.  hm_ip_lintrans_desc plus n_out <= 16; x, y, galois, addend and mod_ids are shared by all outputs,
+ *   t[r][i][k]       = sum_j automorph_{galois[r]}(x[i][j]) (.) y[r][i][k][j]          reduced, formed ONCE per rotation
+ *   out[m][i][k]     = sum_r pt[m][r][i] (.) t[r][i][k]                                 m < n_out
+ *   addend_out[m][i] = sum_r pt[m][r][i] (.) automorph_{galois[r]}(addend[i])           for the entries i that carry an addend source,
+ * bit-identical to n_out calls of hm_inner_product_lintrans that differ only in pt, out and addend_out.  Same gather geometry; a workgroup serves
+ * a tile of HM_IP_LINTRANS_MULTI_TILE outputs of its entry and chunk, so the digits and keys are read once per tile, ceil(n_out / tile) times in
+ * all, and every plaintext once.  Row-major lists: pt_limbs[(m * n_rot + r) * n + i], out_limbs[(m * n + i) * 2 + k], addend_out_limbs[m * n + i];
+ * x_limbs, y_limbs, addend_limbs as hm_ip_lintrans_desc.  addend_limbs non-NULL needs addend, addend_out and addend_out_limbs.  No output limb-poly
+ * (out, addend_out) may overlap, by address range, a digit, a key, a plaintext, the addend source or another output: HM_ERR_ARG.  Safe under graph
+ * capture once it has run with the same limb lists. */
+#define HM_IP_LINTRANS_MULTI_MAX_OUT 16
+#define HM_IP_LINTRANS_MULTI_TILE 2
+typedef struct hm_ip_lintrans_multi_desc {
+  const uint64_t *x;       const uint32_t *x_limbs;           /* digits [n][n_terms] */
+  const uint64_t *y;       const uint32_t *y_limbs;           /* keys [n_rot][n][2][n_terms] */
+  const uint64_t *pt;      const uint32_t *pt_limbs;          /* plaintexts [n_out][n_rot][n] */
+  const uint64_t *addend;  const uint32_t *addend_limbs;      /* optional addend source [n]; HM_NO_LIMB: none for this entry */
+  uint64_t *out;           const uint32_t *out_limbs;         /* [n_out][n][2] */
+  uint64_t *addend_out;    const uint32_t *addend_out_limbs;  /* [n_out][n], read where addend_limbs[i] != HM_NO_LIMB */
+  const uint32_t *mod_ids;                                    /* [n] */
+  uint32_t n, n_terms, n_rot, n_out;
+  const uint32_t *galois;                                     /* [n_rot] */
+} hm_ip_lintrans_multi_desc;
+hm_status hm_inner_product_lintrans_multi(hm_ctx *ctx, const hm_ip_lintrans_multi_desc *desc);
 /* Sum of the key products of rotations of n_ct DIFFERENT ciphertexts (hrotsum): every ciphertext has its own digits,
  * keys and Galois element, and the sum over the ciphertexts is formed BEFORE anything is stored,
  *   out[i][k]     = sum_c sum_j automorph_{galois[c]}(x[c][i][j]) (.) y[c][i][k][j]      k < 2, j < n_terms <= 4, c < n_ct <= 16
