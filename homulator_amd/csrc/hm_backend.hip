@@ -1699,7 +1699,7 @@ static void launch_ip(hm_ctx *c, void (*const (&kernel)[HM_IP_MAX_TERMS][OUTS])(
 // (n_out / n_rot) in range, every Galois element (nullptr: the form has no list) odd and below 2N, every limb and modulus index in range
 struct IpList { const uint32_t *limbs; uint32_t count; };
 static hm_status ip_check(hm_ctx *c, const char *what, const char *null_msg, uint32_t T, const char *second, uint32_t v, uint32_t vmax, const uint32_t *galois,
-                          std::initializer_list<IpList> lists, const uint32_t *mod_ids, uint32_t n) {
+                          const std::vector<IpList> &lists, const uint32_t *mod_ids, uint32_t n) {
   if (null_msg) return fail(c, HM_ERR_ARG, "%s: %s", what, null_msg);
   if (T == 0 || T > HM_IP_MAX_TERMS || v == 0 || v > vmax) return fail(c, HM_ERR_ARG, "%s: n_terms in [1,%d], %s in [1,%d]", what, HM_IP_MAX_TERMS, second, vmax);
   for (uint32_t r = 0; galois && r < v; ++r)
@@ -1707,6 +1707,28 @@ static hm_status ip_check(hm_ctx *c, const char *what, const char *null_msg, uin
   for (const IpList &l : lists)
     if (hm_status st = check_limbs(c, what, l.limbs, l.count)) return st;
   return check_mods(c, what, mod_ids, n);
+}
+// The three forms that sum over rotations (lintrans, lintrans_multi, rotsum) go on in the same way.  An addend is four arguments that go together.
+// ip_check runs over the limbs of the inputs `ins`, the outputs, the addend sources and the addend outputs, in this order.  Then: a workgroup reads
+// operands at other positions than the ones it writes, and operands that could be another workgroup's output, so no output and no addend output
+// may overlap any input, the addend sources last.  An operand: its name in the refusals, its base, its limbs
+static const char *const kAddendQuartet = "null argument (addend, addend_limbs, addend_out and addend_out_limbs go together)";
+struct IpOperand { const char *name; const void *base; const uint32_t *limbs; uint32_t count; };
+static hm_status ip_sum_check(hm_ctx *c, const char *what, const char *null_msg, uint32_t T, const char *second, uint32_t v, uint32_t vmax, const uint32_t *galois,
+                              std::vector<IpOperand> ins, const IpOperand &addSrc, const IpOperand &out, const IpOperand &addOut, const uint32_t *mod_ids,
+                              uint32_t n) {
+  std::vector<IpList> lists;
+  for (const IpOperand &in : ins) lists.push_back({in.limbs, in.count});
+  for (const IpOperand *o : {&out, &addSrc, &addOut}) lists.push_back({o->limbs, o->count});
+  if (hm_status st = ip_check(c, what, null_msg, T, second, v, vmax, galois, lists, mod_ids, n)) return st;
+  ins.push_back(addSrc);
+  for (const IpOperand &in : ins) {
+    if (in.count && hm_limbs_overlap(out.base, out.limbs, out.count, in.base, in.limbs, in.count, c->P.N))
+      return fail(c, HM_ERR_ARG, "%s: an output limb-poly overlaps %s", what, in.name);
+    if (in.count && addOut.count && hm_limbs_overlap(addOut.base, addOut.limbs, addOut.count, in.base, in.limbs, in.count, c->P.N))
+      return fail(c, HM_ERR_ARG, "%s: an addend output limb-poly overlaps %s", what, in.name);
+  }
+  return HM_OK;
 }
 template <class Rec>
 static hm_status ip_device_recs(hm_ctx *c, const std::vector<Rec> &recs, const Rec **out) {
@@ -1791,28 +1813,19 @@ extern "C" hm_status hm_inner_product_lintrans(hm_ctx *c, const hm_ip_lintrans_d
   const bool anyAdd = d->addend_limbs != nullptr;
   const char *null = nullptr;
   if (!d->x || !d->x_limbs || !d->y || !d->y_limbs || !d->pt || !d->pt_limbs || !d->out || !d->out_limbs || !d->mod_ids || !d->galois) null = "null argument";
-  else if (anyAdd && (!d->addend || !d->addend_out || !d->addend_out_limbs)) null = "null argument (addend, addend_limbs, addend_out and addend_out_limbs go together)";
-  const uint32_t n = d->n, T = d->n_terms, R = d->n_rot, N = c->P.N;
+  else if (anyAdd && (!d->addend || !d->addend_out || !d->addend_out_limbs)) null = kAddendQuartet;
+  const uint32_t n = d->n, T = d->n_terms, R = d->n_rot;
   std::vector<uint32_t> addSrc, addOut;   // the entries that carry an addend
   for (uint32_t i = 0; !null && anyAdd && i < n; ++i)
     if (d->addend_limbs[i] != HM_NO_LIMB) { addSrc.push_back(d->addend_limbs[i]); addOut.push_back(d->addend_out_limbs[i]); }
   const uint32_t nAdd = (uint32_t)addSrc.size();
   hm_status st;
-  if ((st = ip_check(c, what, null, T, "n_rot", R, HM_IP_LINTRANS_MAX_ROT, d->galois,
-                     {{d->x_limbs, n * T}, {d->y_limbs, R * n * 2 * T}, {d->pt_limbs, R * n}, {d->out_limbs, n * 2}, {addSrc.data(), nAdd}, {addOut.data(), nAdd}},
-                     d->mod_ids, n)))
+  if ((st = ip_sum_check(c, what, null, T, "n_rot", R, HM_IP_LINTRANS_MAX_ROT, d->galois,
+                         {{"a digit (x)", d->x, d->x_limbs, n * T}, {"a key limb-poly (y)", d->y, d->y_limbs, R * n * 2 * T},
+                          {"a plaintext limb-poly (pt)", d->pt, d->pt_limbs, R * n}},
+                         {"an addend source", d->addend, addSrc.data(), nAdd}, {"", d->out, d->out_limbs, n * 2}, {"", d->addend_out, addOut.data(), nAdd},
+                         d->mod_ids, n)))
     return st;
-  // a workgroup reads the digits and the addend at other positions than the ones it writes, and every rotation's keys and plaintext after the
-  // first could be another workgroup's output: no output may overlap any input
-  struct In { const char *name; const void *base; const uint32_t *limbs; uint32_t count; };
-  const In ins[4] = {{"a digit (x)", d->x, d->x_limbs, n * T}, {"a key limb-poly (y)", d->y, d->y_limbs, R * n * 2 * T},
-                     {"a plaintext limb-poly (pt)", d->pt, d->pt_limbs, R * n}, {"an addend source", d->addend, addSrc.data(), nAdd}};
-  for (const In &in : ins) {
-    if (in.count && hm_limbs_overlap(d->out, d->out_limbs, n * 2, in.base, in.limbs, in.count, N))
-      return fail(c, HM_ERR_ARG, "%s: an output limb-poly overlaps %s", what, in.name);
-    if (in.count && nAdd && hm_limbs_overlap(d->addend_out, addOut.data(), nAdd, in.base, in.limbs, in.count, N))
-      return fail(c, HM_ERR_ARG, "%s: an addend output limb-poly overlaps %s", what, in.name);
-  }
   if (n == 0) return HM_OK;
   std::vector<HmIpLinRec> recs((size_t)R * n);
   hm_ip_fill_recs(recs.data(), d->x_limbs, d->y_limbs, d->out_limbs, (size_t)n * 2, d->mod_ids, n, T, 2, R);
@@ -1837,7 +1850,7 @@ extern "C" hm_status hm_inner_product_lintrans_multi(hm_ctx *c, const hm_ip_lint
   const bool anyAdd = d->addend_limbs != nullptr;
   const char *null = nullptr;
   if (!d->x || !d->x_limbs || !d->y || !d->y_limbs || !d->pt || !d->pt_limbs || !d->out || !d->out_limbs || !d->mod_ids || !d->galois) null = "null argument";
-  else if (anyAdd && (!d->addend || !d->addend_out || !d->addend_out_limbs)) null = "null argument (addend, addend_limbs, addend_out and addend_out_limbs go together)";
+  else if (anyAdd && (!d->addend || !d->addend_out || !d->addend_out_limbs)) null = kAddendQuartet;
   else if (!anyAdd && (d->addend || d->addend_out || d->addend_out_limbs)) null = "null argument (an addend or addend outputs without addend_limbs)";
   const uint32_t n = d->n, T = d->n_terms, R = d->n_rot, G = d->n_out, N = c->P.N;
   if (!null && (G == 0 || G > HM_IP_LINTRANS_MULTI_MAX_OUT)) return fail(c, HM_ERR_ARG, "%s: n_out = %u, must be in [1,%d]", what, G, HM_IP_LINTRANS_MULTI_MAX_OUT);
@@ -1848,22 +1861,13 @@ extern "C" hm_status hm_inner_product_lintrans_multi(hm_ctx *c, const hm_ip_lint
     if (d->addend_limbs[e % n] != HM_NO_LIMB) addOut.push_back(d->addend_out_limbs[e]);
   const uint32_t nAdd = (uint32_t)addSrc.size();
   hm_status st;
-  if ((st = ip_check(c, what, null, T, "n_rot", R, HM_IP_LINTRANS_MAX_ROT, d->galois,
-                     {{d->x_limbs, n * T}, {d->y_limbs, R * n * 2 * T}, {d->pt_limbs, G * R * n}, {d->out_limbs, G * n * 2}, {addSrc.data(), nAdd},
-                      {addOut.data(), G * nAdd}},
-                     d->mod_ids, n)))
+  if ((st = ip_sum_check(c, what, null, T, "n_rot", R, HM_IP_LINTRANS_MAX_ROT, d->galois,
+                         {{"a digit (x)", d->x, d->x_limbs, n * T}, {"a key limb-poly (y)", d->y, d->y_limbs, R * n * 2 * T},
+                          {"a plaintext limb-poly (pt)", d->pt, d->pt_limbs, G * R * n}},
+                         {"the addend source", d->addend, addSrc.data(), nAdd}, {"", d->out, d->out_limbs, G * n * 2},
+                         {"", d->addend_out, addOut.data(), G * nAdd}, d->mod_ids, n)))
     return st;
-  // a workgroup reads the digits and the addend at other positions than the ones it writes, and every key, plaintext and other tile's operand
-  // could be another workgroup's output: no output may overlap any input, and no two outputs each other
-  struct In { const char *name; const void *base; const uint32_t *limbs; uint32_t count; };
-  const In ins[4] = {{"a digit (x)", d->x, d->x_limbs, n * T}, {"a key limb-poly (y)", d->y, d->y_limbs, R * n * 2 * T},
-                     {"a plaintext limb-poly (pt)", d->pt, d->pt_limbs, G * R * n}, {"the addend source", d->addend, addSrc.data(), nAdd}};
-  for (const In &in : ins) {
-    if (in.count && hm_limbs_overlap(d->out, d->out_limbs, G * n * 2, in.base, in.limbs, in.count, N))
-      return fail(c, HM_ERR_ARG, "%s: an output limb-poly overlaps %s", what, in.name);
-    if (in.count && nAdd && hm_limbs_overlap(d->addend_out, addOut.data(), G * nAdd, in.base, in.limbs, in.count, N))
-      return fail(c, HM_ERR_ARG, "%s: an addend output limb-poly overlaps %s", what, in.name);
-  }
+  // ... and no two outputs each other
   {
     std::vector<uintptr_t> starts;
     for (uint32_t i = 0; i < G * n * 2; ++i) starts.push_back(reinterpret_cast<uintptr_t>(d->out) + (uintptr_t)d->out_limbs[i] * N * 8);
@@ -1903,7 +1907,7 @@ extern "C" hm_status hm_inner_product_rotsum(hm_ctx *c, const hm_ip_rotsum_desc 
   const bool anyAdd = d->addend_limbs != nullptr;
   const char *null = nullptr;
   if (!d->x || !d->x_limbs || !d->y || !d->y_limbs || !d->out || !d->out_limbs || !d->mod_ids || !d->galois) null = "null argument";
-  else if (anyAdd && (!d->addend || !d->addend_out || !d->addend_out_limbs)) null = "null argument (addend, addend_limbs, addend_out and addend_out_limbs go together)";
+  else if (anyAdd && (!d->addend || !d->addend_out || !d->addend_out_limbs)) null = kAddendQuartet;
   const uint32_t n = d->n, T = d->n_terms, G = d->n_ct, N = c->P.N;
   const bool counts = T >= 1 && T <= HM_IP_MAX_TERMS && G >= 1 && G <= HM_IP_ROTSUM_MAX_CT;
   std::vector<uint32_t> addSrc, addOut;   // the addend sources [n_ct][entries that carry one] and those entries' outputs
@@ -1916,21 +1920,11 @@ extern "C" hm_status hm_inner_product_rotsum(hm_ctx *c, const hm_ip_rotsum_desc 
   }
   const uint32_t nAdd = (uint32_t)addOut.size();
   hm_status st;
-  if ((st = ip_check(c, what, null, T, "n_ct", G, HM_IP_ROTSUM_MAX_CT, d->galois,
-                     {{d->x_limbs, G * n * T}, {d->y_limbs, G * n * 2 * T}, {d->out_limbs, n * 2}, {addSrc.data(), G * nAdd}, {addOut.data(), nAdd}},
-                     d->mod_ids, n)))
+  if ((st = ip_sum_check(c, what, null, T, "n_ct", G, HM_IP_ROTSUM_MAX_CT, d->galois,
+                         {{"a digit (x)", d->x, d->x_limbs, G * n * T}, {"a key limb-poly (y)", d->y, d->y_limbs, G * n * 2 * T}},
+                         {"an addend source", d->addend, addSrc.data(), G * nAdd}, {"", d->out, d->out_limbs, n * 2}, {"", d->addend_out, addOut.data(), nAdd},
+                         d->mod_ids, n)))
     return st;
-  // a workgroup reads the digits and the addends at other positions than the ones it writes, and every ciphertext's keys after the first
-  // could be another workgroup's output: no output may overlap any input, and no two outputs each other
-  struct In { const char *name; const void *base; const uint32_t *limbs; uint32_t count; };
-  const In ins[3] = {{"a digit (x)", d->x, d->x_limbs, G * n * T}, {"a key limb-poly (y)", d->y, d->y_limbs, G * n * 2 * T},
-                     {"an addend source", d->addend, addSrc.data(), G * nAdd}};
-  for (const In &in : ins) {
-    if (in.count && hm_limbs_overlap(d->out, d->out_limbs, n * 2, in.base, in.limbs, in.count, N))
-      return fail(c, HM_ERR_ARG, "%s: an output limb-poly overlaps %s", what, in.name);
-    if (in.count && nAdd && hm_limbs_overlap(d->addend_out, addOut.data(), nAdd, in.base, in.limbs, in.count, N))
-      return fail(c, HM_ERR_ARG, "%s: an addend output limb-poly overlaps %s", what, in.name);
-  }
   // the outputs among themselves: limb-polys of one base overlap when they are the same one
   auto repeats = [](const uint32_t *l, uint32_t count) {
     std::vector<uint32_t> v(l, l + count);

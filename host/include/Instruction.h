@@ -74,15 +74,12 @@ public:
   // (6h) hoisted key product (hm_inner_product_hoisted): ipX = the UNROTATED digits, rotation r reads them through X -> X^ipHoistG[r] with keys
   // ipY[2r + k]; its outputs are out_{r,k} = (OutputOperand, extraOutputs...)[2r + k].  Empty: not hoisted
   std::vector<uint32_t> ipHoistG;
-  // (6l) weighted sum of the hoisted key products (hm_inner_product_lintrans): a hoisted record (ipX, ipY, ipHoistG as above) whose rotation r is
-  // multiplied by the plaintext limb ipLinPt[r] and summed over r before it is stored: OutputOperand = S_0, extraOutputs[0] = S_1.  ipLinAddend != 0
-  // (the Q limbs): extraOutputs[1] = sum_r ipLinPt[r] * sigma_r(ipLinAddend).  ipLinPt empty: no weighted sum
-  std::vector<AddrType> ipLinPt;
+  // (6m, 6l) M weighted sums of the hoisted key products (M = 1: hm_inner_product_lintrans, M >= 2: hm_inner_product_lintrans_multi): a hoisted
+  // record (ipX, ipY, ipHoistG as above) whose rotation r is multiplied by the plaintext limb ipLinPt[m][r] and summed over r before it is stored.
+  // ipLinAddend != 0 (the Q limbs): U_m = sum_r ipLinPt[m][r] * sigma_r(ipLinAddend) as well.  With w = 2 + (ipLinAddend != 0) outputs per sum,
+  // (OutputOperand, extraOutputs...)[m * w + k] = S_{m,k}, k < 2, and [m * w + 2] = U_m.  ipLinPt empty: no weighted sum
+  std::vector<std::vector<AddrType>> ipLinPt;
   AddrType ipLinAddend = 0;
-  // (6m) M >= 2 weighted sums of the SAME hoisted key products (hm_inner_product_lintrans_multi): a weighted-sum record (ipLinPt = group 0's
-  // plaintext limbs, ipLinAddend shared) with group m's plaintext limbs ipMultiPt[m][r] (ipMultiPt[0] == ipLinPt) and, with w = 2 + (ipLinAddend != 0)
-  // outputs per group, (OutputOperand, extraOutputs...)[m * w + k] = S_{m,k}, k < 2, and [m * w + 2] = U_m.  Empty: one weighted sum
-  std::vector<std::vector<AddrType>> ipMultiPt;
   // (6s) sum of the key products of rotations of DIFFERENT ciphertexts (hm_inner_product_rotsum): ciphertext c reads its own unrotated digits
   // ipSumX[c] (ipSumX[0] == ipX) through X -> X^ipHoistG[c] with keys ipY[2c + k], and the sum over c is formed before it is stored:
   // OutputOperand = S_0, extraOutputs[0] = S_1.  ipSumAddend non-empty (the Q limbs): extraOutputs[1] = sum_c sigma_c(ipSumAddend[c]).

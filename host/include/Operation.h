@@ -149,6 +149,17 @@ protected:
   Limbs rotateLimbs(const Limbs &in, uint32_t k, uint32_t galois, const std::string &suffix);
   void finishRotation(const std::string &out, const std::vector<AddrType> &rotatedC0, const KeySwitch::Output &ks, const std::string &suffix);
   void finishConstruction();  // registers every temporary with the backend
+  // the chains of element-wise stages that the ops summing on the extended basis are built of (HLINTRANS, HROTSUM, HBSGS).  A sum is three buffers,
+  // t = 0, 1: S_0, S_1 (tags Key0, Key1; the E = level + alpha limbs) and t = 2: U (tag C0; the `level` Q limbs); sumMods(t): their modulus ids.
+  struct SwitchedSum { Limbs c0; std::vector<AddrType> c1; };   // (U + ModDown(S_0), ModDown(S_1))
+  std::vector<uint32_t> sumMods(uint32_t t) const;
+  // the weighted sum sum_r terms[r] * pts[r]: stages LinTrans_(<r>)_<tag><suffix>, buffers LinTransOut_temp(<r>)_<tag><suffix>, the last LinTransOut_<tag><suffix>
+  Limbs weightedSum(uint32_t t, const std::vector<Limbs> &terms, const std::vector<std::vector<AddrType>> &pts, const std::string &suffix);
+  // the running sum: sum + term, the i-th term (i >= 2): stage and buffer <stem>_(<i>)_<tag>, the last buffer <stem>Out_<tag>
+  Limbs addTerm(uint32_t t, const Limbs &sum, const Limbs &term, const std::string &stem, uint32_t i, bool last);
+  // the tail: ModDown<suffix> of sums[0], sums[1], then c0 = its output 0 + sums[2] in stage <op>_Hadd<suffix>, buffer `buffer`
+  SwitchedSum sumDown(KeySwitch &ks, const std::array<Limbs, 3> &sums, const std::string &op, const std::string &buffer, const std::string &suffix);
+  void setOutput(const std::string &out, const SwitchedSum &ct);
 
 public:
   virtual ~OperationBase();

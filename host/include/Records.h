@@ -26,7 +26,7 @@ enum class Role {
   IpReplacedSrc,  // ... the conversion output ipSrc[j] that the fused conversion ipConvIn[j] replaces: never written, never loaded
   ConvIn,         // input of a base conversion: a BCONV record's own, ipConvIn[j] (digit = j), fConvIn
   Key,            // key product: evaluation-key limb
-  LinPlain,       // weighted sum of hoisted key products (6l, 6m): a rotation's plaintext limb (6m: of one group)
+  LinPlain,       // weighted sums of hoisted key products (6l, 6m): a rotation's plaintext limb, of one sum
   LinAddend,      // ... the addend source, read through every rotation's automorphism (the unrotated c0)
   SumAddend,      // sum of rotations of different ciphertexts (6s): a ciphertext's addend source, read through its automorphism (its unrotated c0)
   Minuend, Addend, Mix,   // fused forward transform (4, 4b)
@@ -62,9 +62,8 @@ inline std::vector<Read> recordReads(const Instruction &i) {
       for (size_t j = 0; j < i.ipSumX[c].size(); ++j) v.push_back({i.ipSumX[c][j], Role::IpDigit, j});
     for (auto &y : i.ipY)
       for (AddrType a : y) v.push_back({a, Role::Key, kNoDigit});
-    for (AddrType a : i.ipLinPt) v.push_back({a, Role::LinPlain, kNoDigit});
-    for (size_t m = 1; m < i.ipMultiPt.size(); ++m)   // (6m): the plaintext limbs of the further groups, behind group 0's (ipLinPt, above)
-      for (AddrType a : i.ipMultiPt[m]) v.push_back({a, Role::LinPlain, kNoDigit});
+    for (auto &row : i.ipLinPt)
+      for (AddrType a : row) v.push_back({a, Role::LinPlain, kNoDigit});
     if (i.ipLinAddend) v.push_back({i.ipLinAddend, Role::LinAddend, kNoDigit});
     for (AddrType a : i.ipSumAddend) v.push_back({a, Role::SumAddend, kNoDigit});
     return v;

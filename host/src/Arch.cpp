@@ -44,7 +44,7 @@ struct Arch::Launch {
   uint32_t ipTerms = 0, ipOuts = 0;
                                   // L_IP_ROTSUM: hoistG = the element of every ciphertext; a: digits [c][n][T], b: keys [c][n][2][T], d: addend sources
                                   // [c][n] / out1: addend output [n] (HM_NO_LIMB: none; both empty: no entry has one), out: [n][2]
-                                  // L_IP_LINTRANS_MULTI: as L_IP_LINTRANS with multiOuts groups: c: plaintexts [m][r][n], out: [m][n][2], out1: [m][n]
+                                  // L_IP_LINTRANS_MULTI: as L_IP_LINTRANS with multiOuts sums (L_IP_LINTRANS: 1): c: plaintexts [m][r][n], out: [m][n][2], out1: [m][n]
   uint32_t multiOuts = 0;
   uint32_t dotTerms = 0;          // L_TENSOR_DOT: pairs per record (a, b, c, d: [n][dotTerms], roles as L_TENSOR; out, out1, out2: [n])
   std::string name;
@@ -290,7 +290,7 @@ typedef std::vector<const Part *> Group;
 // records of one stage with equal keys go into one C-ABI call (same kind / opcode / direction / operand shape)
 int partKey(const Instruction &i) {
   if (!i.ipSumX.empty()) return 9000 + (int)i.ipX.size() * 100 + (int)i.ipSumX.size();                     // 9000+: sum of rotations of different ciphertexts, by digits and ciphertexts
-  if (!i.ipMultiPt.empty()) return 10000 + (int)i.ipX.size() * 400 + ((int)i.ipHoistG.size() - 1) * 17 + (int)i.ipMultiPt.size();   // 10000+: several weighted sums, by digits, rotations and groups
+  if (i.ipLinPt.size() > 1) return 10000 + (int)i.ipX.size() * 400 + ((int)i.ipHoistG.size() - 1) * 17 + (int)i.ipLinPt.size();   // 10000+: several weighted sums, by digits, rotations and groups
   if (!i.ipLinPt.empty()) return 7000 + (int)i.ipX.size() * 100 + (int)i.ipHoistG.size();                  // 7000+: weighted sum of hoisted key products, by digits and rotations
   if (i.ipHoistG.size() == 1) return 20000 + (int)i.ipX.size() + 8 * (int)i.ipHoistG[0];                   // 20000+: hoisted key product of ONE rotation, by digits and element (hrotsum with fuse_rotsum = 0: one per ciphertext)
   if (!i.ipHoistG.empty()) return 6000 + (int)i.ipX.size() * 100 + (int)i.ipHoistG.size();                 // 6000+: hoisted key product, by digits and rotations
@@ -392,20 +392,22 @@ struct Arch::LaunchBuilder {
     if (evalDigit) { L.xGalois = i->ipXGalois; xGaloisSet = true; }
   }
   bool xGaloisSet = false;   // ... of the launch being built
-  // what the two key products over the rotations of one launch share (the records must agree on the rotations): digits a [n][T], moduli, keys
-  // b [r][n][2][T].  Returns the number of rotations
-  size_t hoistedOperands(Launch &L, Recs recs, const char *what) {
+  // what the key products over the rotations of one launch share (the records must agree on the rotations): moduli, keys b [r][n][2][T] and the
+  // digits, a [n][T], or with digitsPerRotation (6s: every rotation is of a ciphertext of its own) a [r][n][T].  Returns the number of rotations
+  size_t hoistedOperands(Launch &L, Recs recs, const char *what, bool digitsPerRotation = false) {
     L.statKey = "EWE";
     L.ipTerms = (uint32_t)recs[0]->ipX.size(); L.ipOuts = 2; L.hoistG = recs[0]->ipHoistG;
     for (Instruction *i : recs) {
       if (i->ipHoistG != L.hoistG) throw std::runtime_error(std::string(what) + ": the records of one launch rotate by different elements");
-      for (AddrType x : i->ipX) L.a.push_back(limb(x));
+      if (!digitsPerRotation) for (AddrType x : i->ipX) L.a.push_back(limb(x));
       L.mods.push_back(i->mod_id);
     }
     for (size_t r = 0; r < L.hoistG.size(); ++r)
-      for (Instruction *i : recs)
+      for (Instruction *i : recs) {
+        if (digitsPerRotation) for (AddrType x : i->ipSumX[r]) L.a.push_back(limb(x));
         for (size_t k = 0; k < 2; ++k)
           for (AddrType y : i->ipY[r * 2 + k]) L.b.push_back(limb(y));
+      }
     return L.hoistG.size();
   }
 
@@ -419,7 +421,6 @@ struct Arch::LaunchBuilder {
   void ipHoisted(Launch &L, Recs recs);
   void ipLintrans(Launch &L, Recs recs);
   void ipRotsum(Launch &L, Recs recs);
-  void ipLintransMulti(Launch &L, Recs recs);
   void nttIp(Launch &L, Recs recs);
   void ip(Launch &L, Recs recs);
   void tensor(Launch &L, Recs recs);
@@ -443,36 +444,17 @@ void Arch::LaunchBuilder::ipHoisted(Launch &L, Recs recs) {
   L.bytes = (unsigned long long)recs.size() * (L.ipTerms + 2 * R * L.ipTerms + 2 * R) * LP;
 }
 
-// (6l) one weighted sum of hoisted key products: the hoisted launch's digits and keys, plaintexts c [r][n], outputs out [n][2]; entries with an
-// addend: source d [n], output out1 [n] (hm_ip_lintrans_desc)
+// (6l, 6m) M weighted sums of the same hoisted key products: the hoisted launch's digits and keys, plaintexts c [m][r][n], outputs out [m][n][2];
+// entries with an addend: source d [n], outputs out1 [m][n] (M = 1: hm_ip_lintrans_desc, else hm_ip_lintrans_multi_desc)
 void Arch::LaunchBuilder::ipLintrans(Launch &L, Recs recs) {
-  L.kind = Launch::L_IP_LINTRANS;
-  const size_t R = hoistedOperands(L, recs, "weighted rotations");
-  size_t addends = 0;
-  for (Instruction *i : recs) addends += i->ipLinAddend != 0;
-  for (Instruction *i : recs) {
-    L.out.push_back(limb(i->OutputOperand)); L.out.push_back(limb(i->extraOutputs[0]));
-    if (addends) {
-      L.d.push_back(i->ipLinAddend ? limb(i->ipLinAddend) : HM_NO_LIMB);
-      L.out1.push_back(i->ipLinAddend ? limb(i->extraOutputs[1]) : HM_NO_LIMB);
-    }
-  }
-  for (size_t r = 0; r < R; ++r)
-    for (Instruction *i : recs) L.c.push_back(limb(i->ipLinPt[r]));
-  // limb-polys touched: the digits and the addend source once (every rotation gathers from the same ones), keys and plaintext once per rotation,
-  // two outputs per entry and one per addend
-  L.bytes = ((unsigned long long)recs.size() * (L.ipTerms + 2 * R * L.ipTerms + R + 2) + (unsigned long long)addends * 2) * LP;
-}
-
-// (6m) M weighted sums of the same hoisted key products: the hoisted launch's digits and keys, plaintexts c [m][r][n], outputs out [m][n][2]; entries
-// with an addend: source d [n], outputs out1 [m][n] (hm_ip_lintrans_multi_desc)
-void Arch::LaunchBuilder::ipLintransMulti(Launch &L, Recs recs) {
-  L.kind = Launch::L_IP_LINTRANS_MULTI;
-  const size_t R = hoistedOperands(L, recs, "weighted rotations (several sums)"), M = recs[0]->ipMultiPt.size();
+  const size_t M = recs[0]->ipLinPt.size();
+  const std::string what = M == 1 ? "weighted rotations" : "weighted rotations (several sums)";
+  L.kind = M == 1 ? Launch::L_IP_LINTRANS : Launch::L_IP_LINTRANS_MULTI;
   L.multiOuts = (uint32_t)M;
+  const size_t R = hoistedOperands(L, recs, what.c_str());
   size_t addends = 0;
   for (Instruction *i : recs) {
-    if (i->ipMultiPt.size() != M) throw std::runtime_error("weighted rotations (several sums): the records of one launch form different numbers of sums");
+    if (i->ipLinPt.size() != M) throw std::runtime_error(what + ": the records of one launch form different numbers of sums");
     addends += i->ipLinAddend != 0;
   }
   auto outOf = [](const Instruction *i, size_t x) { return x == 0 ? i->OutputOperand : i->extraOutputs[x - 1]; };
@@ -485,10 +467,10 @@ void Arch::LaunchBuilder::ipLintransMulti(Launch &L, Recs recs) {
       if (addends) L.out1.push_back(i->ipLinAddend ? limb(outOf(i, m * w + 2)) : HM_NO_LIMB);
     }
     for (size_t r = 0; r < R; ++r)
-      for (Instruction *i : recs) L.c.push_back(limb(i->ipMultiPt[m][r]));
+      for (Instruction *i : recs) L.c.push_back(limb(i->ipLinPt[m][r]));
   }
-  // limb-polys touched: a workgroup serves a tile of outputs, so the digits, the keys and the addend source are read once per tile; every group's
-  // plaintexts once; two outputs per entry and group and one per addend and group
+  // limb-polys touched: a workgroup serves a tile of sums (one sum: one tile), so the digits, the keys and the addend source are read once per tile
+  // (every rotation gathers from the same ones); every sum's plaintexts once; two outputs per entry and sum and one per addend and sum
   const unsigned long long tiles = (M + HM_IP_LINTRANS_MULTI_TILE - 1) / HM_IP_LINTRANS_MULTI_TILE;
   L.bytes = ((unsigned long long)recs.size() * (tiles * (L.ipTerms + 2 * R * L.ipTerms) + M * R + 2 * M) + (unsigned long long)addends * (tiles + M)) * LP;
 }
@@ -496,25 +478,16 @@ void Arch::LaunchBuilder::ipLintransMulti(Launch &L, Recs recs) {
 // (6s) one sum of rotations of different ciphertexts: digits a [c][n][T], keys b [c][n][2][T], outputs out [n][2]; entries with addends: sources
 // d [c][n], output out1 [n] (hm_ip_rotsum_desc)
 void Arch::LaunchBuilder::ipRotsum(Launch &L, Recs recs) {
-  Instruction *f = recs[0];
-  L.kind = Launch::L_IP_ROTSUM; L.statKey = "EWE";
-  L.ipTerms = (uint32_t)f->ipX.size(); L.ipOuts = 2; L.hoistG = f->ipHoistG;
-  const size_t G = f->ipSumX.size();
+  L.kind = Launch::L_IP_ROTSUM;
+  const size_t G = hoistedOperands(L, recs, "sum of rotations", /*digitsPerRotation=*/true);
   size_t addends = 0;
   for (Instruction *i : recs) addends += !i->ipSumAddend.empty();
   for (Instruction *i : recs) {
-    if (i->ipHoistG != L.hoistG) throw std::runtime_error("sum of rotations: the records of one launch rotate by different elements");
-    L.mods.push_back(i->mod_id);
     L.out.push_back(limb(i->OutputOperand)); L.out.push_back(limb(i->extraOutputs[0]));
     if (addends) L.out1.push_back(i->ipSumAddend.empty() ? HM_NO_LIMB : limb(i->extraOutputs[1]));
   }
-  for (size_t c = 0; c < G; ++c)
-    for (Instruction *i : recs) {
-      for (AddrType x : i->ipSumX[c]) L.a.push_back(limb(x));
-      for (size_t k = 0; k < 2; ++k)
-        for (AddrType y : i->ipY[c * 2 + k]) L.b.push_back(limb(y));
-      if (addends) L.d.push_back(i->ipSumAddend.empty() ? HM_NO_LIMB : limb(i->ipSumAddend[c]));
-    }
+  for (size_t c = 0; c < G && addends; ++c)
+    for (Instruction *i : recs) L.d.push_back(i->ipSumAddend.empty() ? HM_NO_LIMB : limb(i->ipSumAddend[c]));
   // limb-polys touched: every ciphertext's digits, keys and addend source once, two outputs per entry and one per entry with addends
   L.bytes = ((unsigned long long)recs.size() * (G * 3 * L.ipTerms + 2) + (unsigned long long)addends * (G + 1)) * LP;
 }
@@ -734,7 +707,6 @@ void Arch::LaunchBuilder::emitCompute(const Group &group, Launches &front, Launc
   for (const Part *g : group) L->name += (L->name.empty() ? "" : "+") + g->name;
   for (Instruction *i : recs) L->refInstructions += i->refInstructions * (i->ops == BCONV_STEP2 ? bconvPorts : 1ull) + i->refExtra;
   if (f->ops == IP && !f->ipSumX.empty()) ipRotsum(*L, recs);
-  else if (f->ops == IP && !f->ipMultiPt.empty()) ipLintransMulti(*L, recs);
   else if (f->ops == IP && !f->ipLinPt.empty()) ipLintrans(*L, recs);
   else if (f->ops == IP && !f->ipHoistG.empty()) ipHoisted(*L, recs);
   else if (f->ops == IP && transformsInside(*f)) nttIp(*L, recs);
@@ -1007,13 +979,10 @@ void Arch::replicateForBatch() {
       else if (l->kind == Launch::L_IP_ROTSUM) {   // every ciphertext its own digits and addend source
         inter(l->out, 1, 2, true);
         if (!l->d.empty()) { inter(l->d, R, 1, true); inter(l->out1, 1, 1, true); }
-      } else if (l->kind == Launch::L_IP_LINTRANS_MULTI) {   // every group its own plaintexts and outputs
+      } else {   // the weighted sums (one: L_IP_LINTRANS): every sum its own plaintexts and outputs
         const size_t M = l->multiOuts;
         inter(l->out, M, 2, true); inter(l->c, M * R, 1, true);
         if (!l->d.empty()) { inter(l->d, 1, 1, true); inter(l->out1, M, 1, true); }
-      } else {
-        inter(l->out, 1, 2, true); inter(l->c, R, 1, true);
-        if (!l->d.empty()) { inter(l->d, 1, 1, true); inter(l->out1, 1, 1, true); }
       }
       l->refInstructions *= batch_;
       l->bytes *= batch_;
@@ -1235,7 +1204,7 @@ std::string Arch::planDump() const {
            " ipTerms=" + std::to_string(l->ipTerms) + " ipOuts=" + std::to_string(l->ipOuts) + " ref=" + std::to_string(l->refInstructions) + " bytes=" + std::to_string(l->bytes) +
            " mark=" + std::to_string(l->recordSlot) + " xin=" + indexOf(l->xin) + " xout=" + indexOf(l->xout);
     if (l->dotTerms) out += " terms=" + std::to_string(l->dotTerms);
-    if (l->multiOuts) out += " multiOuts=" + std::to_string(l->multiOuts);
+    if (l->kind == Launch::L_IP_LINTRANS_MULTI) out += " multiOuts=" + std::to_string(l->multiOuts);   // (one sum: the line of L_IP_LINTRANS has no such field)
     vec("wait", l->waitSlots); vec("hoistG", l->hoistG); vec("ipCoeff", l->ipCoeff); vec("ipInv", l->ipInv); vec("outPacked", l->outPacked);
     vec("inGalois", l->inGalois); vec("addGalois", l->addGalois);
     vec("a", l->a); vec("b", l->b); vec("c", l->c); vec("d", l->d); vec("out", l->out); vec("out1", l->out1); vec("out2", l->out2);

@@ -440,6 +440,67 @@ void OperationBase::finishRotation(const std::string &out, const std::vector<Add
   setOutput(out, 0, s.out);
   setOutput(out, 1, ks[1]);
 }
+// The sums on the extended basis (HLINTRANS, HROTSUM, HBSGS): t = 0, 1 (S_0, S_1: the key product's two components, E = level + alpha limbs) and
+// t = 2 (U: the rotated c0, the `level` Q limbs), by the tags their buffers and stage keys carry
+static const char *const kSumTags[3] = {"Key0", "Key1", "C0"};
+std::vector<uint32_t> OperationBase::sumMods(uint32_t t) const {
+  std::vector<uint32_t> mods = range(0, level_);
+  if (t < 2)
+    for (uint32_t p : range(maxLevel_, alpha_)) mods.push_back(p);
+  return mods;
+}
+// sum_r terms[r] * pts[r] (t = 2: the Q limbs of pts[r]): MUL, then one MAC_ADD per further rotation, the last into LinTransOut_<tag><suffix>.  The
+// term is operand a: pass (6) pairs chains that share their a operands into key products, and the plaintexts are shared by all three sums
+Limbs OperationBase::weightedSum(uint32_t t, const std::vector<Limbs> &terms, const std::vector<std::vector<AddrType>> &pts, const std::string &suffix) {
+  const std::string tag = kSumTags[t];
+  const std::vector<uint32_t> mods = sumMods(t);
+  const size_t R = terms.size();
+  Limbs sum;
+  for (size_t r = 0; r < R; ++r) {
+    const std::string at = "(" + S(r + 1) + ")_" + tag + suffix;
+    PerLimb s{label + "_LinTrans" + suffix + "_" + tag + "_Rot(" + S(r + 1) + ")_Level(", ")", mods,
+              alloc(r + 1 < R ? "LinTransOut_temp" + at : "LinTransOut_" + tag + suffix, (uint32_t)mods.size())};
+    s.a = terms[r].addr;
+    s.b = t < 2 ? pts[r] : slice(pts[r], 0, level_);
+    s.after = {&terms[r].from};
+    const Limbs before = sum;
+    if (r) {
+      s.c = before.addr;
+      s.after.push_back(&before.from);
+    }
+    sum = {s.out, eweLimbs(&insgener, r ? EWE_MAC_ADD : EWE_MUL, s)};
+    driver.dispatchInstructions("LinTrans_" + at, sum.from);
+  }
+  return sum;
+}
+// sum + term, the i-th: one ADD into <stem>_(<i>)_<tag>, the last into <stem>Out_<tag>
+Limbs OperationBase::addTerm(uint32_t t, const Limbs &sum, const Limbs &term, const std::string &stem, uint32_t i, bool last) {
+  const std::string tag = kSumTags[t], at = "(" + S(i) + ")_" + tag;
+  const std::vector<uint32_t> mods = sumMods(t);
+  PerLimb s{label + "_" + stem + "_" + tag + "_Ct(" + S(i) + ")_Level(", ")", mods, alloc(last ? stem + "Out_" + tag : stem + "_" + at, (uint32_t)mods.size())};
+  s.a = sum.addr;
+  s.c = term.addr;
+  s.after = {&sum.from, &term.from};
+  const Limbs out{s.out, eweLimbs(&insgener, EWE_ADD, s)};
+  driver.dispatchInstructions(stem + "_" + at, out.from);
+  return out;
+}
+// the ciphertext (U + ModDown(S_0), ModDown(S_1)) of the sums: stages <op>_Hadd<suffix> behind the ModDown's, c0 in `buffer`
+OperationBase::SwitchedSum OperationBase::sumDown(KeySwitch &ks, const std::array<Limbs, 3> &sums, const std::string &op, const std::string &buffer,
+                                                  const std::string &suffix) {
+  const KeySwitch::Output down = ks.modDown({sums[0], sums[1]}, suffix);
+  dispatch(ks.takeStages());
+  PerLimb s{label + "_" + op + "add" + suffix + "_Level(", ")", range(0, level_), alloc(buffer, level_)};
+  s.a = down[0];
+  s.c = sums[2].addr;
+  const Limbs c0{s.out, eweLimbs(&insgener, EWE_ADD, s)};
+  driver.dispatchInstructions(op + "_Hadd" + suffix, c0.from);
+  return {c0, down[1]};
+}
+void OperationBase::setOutput(const std::string &out, const SwitchedSum &ct) {
+  setOutput(out, 0, ct.c0.addr);
+  setOutput(out, 1, ct.c1);
+}
 void OperationBase::finishConstruction() {
   for (const std::string &n : addrManager->names()) arch->registerLimbs(addrManager->getAddr(n));
 }
@@ -647,47 +708,17 @@ HLINTRANS::HLINTRANS(std::string labelName, uint32_t maxLevel, uint32_t currentL
   const KeySwitch::Digits digits = ks.modUp(cts[0].getC1Addr(), /*inputMayBeOpInput=*/true);
   dispatch(ks.takeStages());
   std::array<std::vector<Limbs>, 3> terms;          // per rotation: acc_{r,0}, acc_{r,1}, sigma_r(c0)
-  std::array<std::vector<std::vector<AddrType>>, 3> weights;   // ... and the plaintext limbs they meet
+  std::vector<std::vector<AddrType>> pts;           // ... and the plaintext they meet
   for (uint32_t r = 1; r <= R; ++r) {
     const std::string rs = "_Rot" + S(r);
     const KeySwitch::Accumulators acc = ks.keyProduct(ks.rotateDigits(digits, gs[r - 1], rs), seed + 10000 + 100000ull * r, rs);
     dispatch(ks.takeStages());
-    const std::vector<AddrType> pt = namedInputs.at("pt" + S(r));
     terms[0].push_back(acc[0]); terms[1].push_back(acc[1]); terms[2].push_back(rotateComponent(0, gs[r - 1], rs));
-    weights[0].push_back(pt); weights[1].push_back(pt); weights[2].push_back(slice(pt, 0, currentLevel));
+    pts.push_back(namedInputs.at("pt" + S(r)));
   }
-  // sum_r terms[r] * weights[r] over the limbs of `mods`: MUL, then one MAC_ADD per further rotation, the last into LinTransOut_<tag>.  The term
-  // is operand a: pass (6) pairs chains that share their a operands into key products, and the plaintexts are shared by all three sums
-  std::vector<uint32_t> extMods = range(0, currentLevel);
-  for (uint32_t p : range(maxLevel, alpha)) extMods.push_back(p);
-  const std::array<std::string, 3> tags = {"Key0", "Key1", "C0"};
   std::array<Limbs, 3> sums;
-  for (uint32_t t = 0; t < 3; ++t) {
-    Limbs &sum = sums[t];
-    for (uint32_t r = 0; r < R; ++r) {
-      const std::string at = "(" + S(r + 1) + ")_" + tags[t];
-      PerLimb s{labelName + "_LinTrans_" + tags[t] + "_Rot(" + S(r + 1) + ")_Level(", ")", t < 2 ? extMods : range(0, currentLevel),
-                alloc(r + 1 < R ? "LinTransOut_temp" + at : "LinTransOut_" + tags[t], t < 2 ? currentLevel + alpha : currentLevel)};
-      s.a = terms[t][r].addr;
-      s.b = weights[t][r];
-      s.after = {&terms[t][r].from};
-      const Limbs before = sum;
-      if (r) {
-        s.c = before.addr;
-        s.after.push_back(&before.from);
-      }
-      sum = {s.out, eweLimbs(&insgener, r ? EWE_MAC_ADD : EWE_MUL, s)};
-      driver.dispatchInstructions("LinTrans_" + at, sum.from);
-    }
-  }
-  const KeySwitch::Output down = ks.modDown({sums[0], sums[1]}, "");
-  dispatch(ks.takeStages());
-  PerLimb s{labelName + "_HLINTRANSadd_Level(", ")", range(0, currentLevel), alloc("HLINTRANSOutput(0)", currentLevel)};
-  s.a = down[0];
-  s.c = sums[2].addr;
-  driver.dispatchInstructions("HLINTRANS_Hadd", eweLimbs(&insgener, EWE_ADD, s));
-  setOutput("out", 0, s.out);
-  setOutput("out", 1, down[1]);
+  for (uint32_t t = 0; t < 3; ++t) sums[t] = weightedSum(t, terms[t], pts, "");
+  setOutput("out", sumDown(ks, sums, "HLINTRANS", "HLINTRANSOutput(0)", ""));
   finishConstruction();
 }
 
@@ -769,40 +800,16 @@ HROTSUM::HROTSUM(std::string labelName, uint32_t maxLevel, uint32_t currentLevel
   makeInputs(G);
 
   KeySwitch ks(labelName, maxLevel, currentLevel, alpha, &Datapool, &DataInsMap, &insgener, addrManager.get());
-  std::vector<uint32_t> extMods = range(0, currentLevel);
-  for (uint32_t p : range(maxLevel, alpha)) extMods.push_back(p);
-  const std::array<std::string, 3> tags = {"Key0", "Key1", "C0"};
   std::array<Limbs, 3> sums;   // S_0, S_1, U so far
   for (uint32_t i = 1; i <= G; ++i) {
     const std::string rs = "_Rot" + S(i);
     const KeySwitch::Digits digits = ks.modUp(cts[i - 1].getC1Addr(), /*inputMayBeOpInput=*/true, i == 1 ? "" : "_Ct" + S(i));
     const KeySwitch::Accumulators acc = ks.keyProduct(ks.rotateDigits(digits, gs[i - 1], rs), seed + 10000 + 100000ull * i, rs);
     dispatch(ks.takeStages());
-    const std::array<Limbs, 3> terms = {acc[0], acc[1], rotateComponent(0, gs[i - 1], rs, i - 1)};
-    if (i == 1) {
-      sums = terms;
-      continue;
-    }
-    for (uint32_t t = 0; t < 3; ++t) {
-      const std::string at = "(" + S(i) + ")_" + tags[t];
-      PerLimb s{labelName + "_RotSum_" + tags[t] + "_Ct(" + S(i) + ")_Level(", ")", t < 2 ? extMods : range(0, currentLevel),
-                alloc(i < G ? "RotSum_" + at : "RotSumOut_" + tags[t], t < 2 ? currentLevel + alpha : currentLevel)};
-      const Limbs before = sums[t];
-      s.a = before.addr;
-      s.c = terms[t].addr;
-      s.after = {&before.from, &terms[t].from};
-      sums[t] = {s.out, eweLimbs(&insgener, EWE_ADD, s)};
-      driver.dispatchInstructions("RotSum_" + at, sums[t].from);
-    }
+    const std::array<Limbs, 3> term = {acc[0], acc[1], rotateComponent(0, gs[i - 1], rs, i - 1)};
+    for (uint32_t t = 0; t < 3; ++t) sums[t] = i == 1 ? term[t] : addTerm(t, sums[t], term[t], "RotSum", i, i == G);
   }
-  const KeySwitch::Output down = ks.modDown({sums[0], sums[1]}, "");
-  dispatch(ks.takeStages());
-  PerLimb s{labelName + "_HROTSUMadd_Level(", ")", range(0, currentLevel), alloc("HROTSUMOutput(0)", currentLevel)};
-  s.a = down[0];
-  s.c = sums[2].addr;
-  driver.dispatchInstructions("HROTSUM_Hadd", eweLimbs(&insgener, EWE_ADD, s));
-  setOutput("out", 0, s.out);
-  setOutput("out", 1, down[1]);
+  setOutput("out", sumDown(ks, sums, "HROTSUM", "HROTSUMOutput(0)", ""));
   finishConstruction();
 }
 
@@ -837,9 +844,6 @@ HBSGS::HBSGS(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, ui
   makeInputs(1, /*plaintext=*/false, /*extPlaintexts=*/G * R);
 
   KeySwitch ks(labelName, maxLevel, currentLevel, alpha, &Datapool, &DataInsMap, &insgener, addrManager.get());
-  std::vector<uint32_t> extMods = range(0, currentLevel);
-  for (uint32_t p : range(maxLevel, alpha)) extMods.push_back(p);
-  const std::array<std::string, 3> tags = {"Key0", "Key1", "C0"};
   // the baby step: one ModUp, one key product and one rotated c0 per baby rotation
   const KeySwitch::Digits digits = ks.modUp(cts[0].getC1Addr(), /*inputMayBeOpInput=*/true);
   dispatch(ks.takeStages());
@@ -850,72 +854,27 @@ HBSGS::HBSGS(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, ui
     dispatch(ks.takeStages());
     terms[0].push_back(acc[0]); terms[1].push_back(acc[1]); terms[2].push_back(rotateComponent(0, gs[r - 1], rs));
   }
-  // per giant step i: the three weighted sums as HLINTRANS emits them, the ModDown and the ADD of U_i
-  std::vector<Limbs> vc0;                        // v_i.c0
-  std::vector<std::vector<AddrType>> vc1;        // v_i.c1
+  // per giant step i: HLINTRANS's three weighted sums, the ModDown and the ADD of U_i give v_i
+  std::vector<SwitchedSum> v;
   for (uint32_t i = 1; i <= G; ++i) {
     const std::string gp = "_Grp" + S(i);
+    std::vector<std::vector<AddrType>> pts;
+    for (uint32_t r = 1; r <= R; ++r) pts.push_back(namedInputs.at("pt" + S((i - 1) * R + r)));
     std::array<Limbs, 3> sums;
-    for (uint32_t t = 0; t < 3; ++t) {
-      Limbs &sum = sums[t];
-      for (uint32_t r = 0; r < R; ++r) {
-        const std::vector<AddrType> pt = namedInputs.at("pt" + S((i - 1) * R + r + 1));
-        const std::string at = "(" + S(r + 1) + ")_" + tags[t] + gp;
-        PerLimb s{labelName + "_LinTrans" + gp + "_" + tags[t] + "_Rot(" + S(r + 1) + ")_Level(", ")", t < 2 ? extMods : range(0, currentLevel),
-                  alloc(r + 1 < R ? "LinTransOut_temp" + at : "LinTransOut_" + tags[t] + gp, t < 2 ? currentLevel + alpha : currentLevel)};
-        s.a = terms[t][r].addr;
-        s.b = t < 2 ? pt : slice(pt, 0, currentLevel);
-        s.after = {&terms[t][r].from};
-        const Limbs before = sum;
-        if (r) {
-          s.c = before.addr;
-          s.after.push_back(&before.from);
-        }
-        sum = {s.out, eweLimbs(&insgener, r ? EWE_MAC_ADD : EWE_MUL, s)};
-        driver.dispatchInstructions("LinTrans_" + at, sum.from);
-      }
-    }
-    const KeySwitch::Output down = ks.modDown({sums[0], sums[1]}, gp);
-    dispatch(ks.takeStages());
-    PerLimb s{labelName + "_HBSGSadd" + gp + "_Level(", ")", range(0, currentLevel), alloc("HBSGSInner" + gp + "(0)", currentLevel)};
-    s.a = down[0];
-    s.c = sums[2].addr;
-    vc0.push_back({s.out, eweLimbs(&insgener, EWE_ADD, s)});
-    driver.dispatchInstructions("HBSGS_Hadd" + gp, vc0.back().from);
-    vc1.push_back(down[1]);
+    for (uint32_t t = 0; t < 3; ++t) sums[t] = weightedSum(t, terms[t], pts, gp);
+    v.push_back(sumDown(ks, sums, "HBSGS", "HBSGSInner" + gp + "(0)", gp));
   }
-  // the giant step: HROTSUM's body on the v_i
+  // the giant step: HROTSUM's running sums over the v_i
   std::array<Limbs, 3> sums;   // T_0, T_1, V so far
   for (uint32_t i = 1; i <= G; ++i) {
     const std::string gt = "_Giant" + S(i);
-    const KeySwitch::Digits dg = ks.modUp(vc1[i - 1], /*inputMayBeOpInput=*/false, gt);
+    const KeySwitch::Digits dg = ks.modUp(v[i - 1].c1, /*inputMayBeOpInput=*/false, gt);
     const KeySwitch::Accumulators acc = ks.keyProduct(ks.rotateDigits(dg, hs[i - 1], gt), seed + 10000 + 100000ull * (16 + i), gt);
     dispatch(ks.takeStages());
-    const std::array<Limbs, 3> term = {acc[0], acc[1], rotateLimbs(vc0[i - 1], 0, hs[i - 1], gt)};
-    if (i == 1) {
-      sums = term;
-      continue;
-    }
-    for (uint32_t t = 0; t < 3; ++t) {
-      const std::string at = "(" + S(i) + ")_" + tags[t];
-      PerLimb s{labelName + "_GiantSum_" + tags[t] + "_Ct(" + S(i) + ")_Level(", ")", t < 2 ? extMods : range(0, currentLevel),
-                alloc(i < G ? "GiantSum_" + at : "GiantSumOut_" + tags[t], t < 2 ? currentLevel + alpha : currentLevel)};
-      const Limbs before = sums[t];
-      s.a = before.addr;
-      s.c = term[t].addr;
-      s.after = {&before.from, &term[t].from};
-      sums[t] = {s.out, eweLimbs(&insgener, EWE_ADD, s)};
-      driver.dispatchInstructions("GiantSum_" + at, sums[t].from);
-    }
+    const std::array<Limbs, 3> term = {acc[0], acc[1], rotateLimbs(v[i - 1].c0, 0, hs[i - 1], gt)};
+    for (uint32_t t = 0; t < 3; ++t) sums[t] = i == 1 ? term[t] : addTerm(t, sums[t], term[t], "GiantSum", i, i == G);
   }
-  const KeySwitch::Output down = ks.modDown({sums[0], sums[1]}, "");
-  dispatch(ks.takeStages());
-  PerLimb s{labelName + "_HBSGSadd_Level(", ")", range(0, currentLevel), alloc("HBSGSOutput(0)", currentLevel)};
-  s.a = down[0];
-  s.c = sums[2].addr;
-  driver.dispatchInstructions("HBSGS_Hadd", eweLimbs(&insgener, EWE_ADD, s));
-  setOutput("out", 0, s.out);
-  setOutput("out", 1, down[1]);
+  setOutput("out", sumDown(ks, sums, "HBSGS", "HBSGSOutput(0)", ""));
   finishConstruction();
 }
 

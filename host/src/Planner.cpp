@@ -43,6 +43,58 @@ struct Arch::Planner {
     return rd;
   }
   static bool onlyReader(Readers &rd, AddrType a, Instruction *i) { auto &v = rd[a]; return v.size() == 1 && v[0] == i; }
+  // the one live reader of `a`, if it is an element-wise record of this opcode and modulus (and no tensor record)
+  Instruction *soleReader(Readers &rd, AddrType a, ewe_opcode op, uint32_t mod) const {
+    auto &r = rd[a];
+    return r.size() == 1 && live(r[0]) && r[0]->ops == MULT && r[0]->opcode == op && r[0]->mod_id == mod && !r[0]->fusedTensor ? r[0] : nullptr;
+  }
+  bool isMul(Instruction *i, uint32_t mod) const { return live(i) && i->ops == MULT && i->opcode == EWE_MUL && i->mod_id == mod; }
+  // the `length` records of the chain that starts with `first` (a MUL) and goes on through MAC_ADD records of its modulus, each the only reader
+  // of the one before, which is its operand c (empty: there is no such chain)
+  typedef std::vector<Instruction *> Chain;
+  Chain chainFrom(Readers &rd, Instruction *first, size_t length) const {
+    Chain c = {first};
+    while (c.size() < length) {
+      Instruction *next = soleReader(rd, c.back()->OutputOperand, EWE_MAC_ADD, first->mod_id);
+      if (!next || next->operandList[2] != c.back()->OutputOperand) return Chain();
+      c.push_back(next);
+    }
+    return c;
+  }
+  // record `i` goes into `carrier`: it is never run, its upstream instructions are accounted for there
+  void absorb(Instruction *carrier, Instruction *i) {
+    if (i == carrier || !live(i)) return;
+    carrier->refInstructions += i->refInstructions;
+    dead.insert(i);
+  }
+  // the merged key product over rotations that `c` carries (6m/6l, 6s, 6h): digits, keys [2r + k], the rotations' elements, and its outputs
+  void carry(Instruction *c, const std::vector<AddrType> &x, const std::vector<std::vector<AddrType>> &ys, const std::vector<uint32_t> &gs,
+             const std::vector<AddrType> &outs) {
+    c->ipX = x;
+    c->ipY = ys;
+    c->ipHoistG = gs;
+    c->OutputOperand = outs[0];
+    c->extraOutputs.assign(outs.begin() + 1, outs.end());
+    for (const Write &w : recordWrites(*c)) producer[w.addr] = c;
+  }
+  // where every record stands, (stage, position), as the stages are when a pass starts: a record that absorbed later ones moves to the place of
+  // the last of them (5d, 6s)
+  struct Placement {
+    std::vector<Stage> &st;
+    std::map<Instruction *, std::pair<size_t, size_t>> at;
+    explicit Placement(std::vector<Stage> &stages) : st(stages) {
+      for (size_t si = 0; si < st.size(); ++si)
+        for (size_t k = 0; k < st[si].ins.size(); ++k) at[st[si].ins[k]] = {si, k};
+    }
+    bool after(Instruction *a, Instruction *b) { return at[a] > at[b]; }
+    void moveTo(Instruction *carrier, Instruction *last) {
+      if (last == carrier) return;
+      auto &from = st[at[carrier].first].ins;
+      from.erase(std::remove(from.begin(), from.end(), carrier), from.end());
+      auto &to = st[at[last].first].ins;
+      std::replace(to.begin(), to.end(), last, carrier);
+    }
+  };
 
   void passThrough();      // 1
   void inttScale();        // 2
@@ -53,17 +105,23 @@ struct Arch::Planner {
   void tensor();           // 5
   void tensorDot();        // 5d
   void keyProduct();       // 6
-  // what (6l) and (6h) both recognise: the live two-key key-product records whose digits are all automorphisms, by one element per record, of
+  // what (6m/6l), (6s) and (6h) all recognise: the live two-key key-product records whose digits are all automorphisms, by one element per record, of
   // the same materialised digits and are read by nothing else; per (modulus, unrotated digits) the records and their automorphisms, in stage order
   typedef std::pair<uint32_t, std::vector<AddrType>> DigitsKey;
+  typedef std::vector<std::pair<Instruction *, std::vector<Instruction *>>> Rotations;
   struct RotationGroups {
-    std::map<DigitsKey, std::vector<std::pair<Instruction *, std::vector<Instruction *>>>> members;
+    std::map<DigitsKey, Rotations> members;
     std::vector<DigitsKey> order;   // first appearance
   };
   RotationGroups rotationGroups(Readers &rd);
-  void sharedWeightedRotations();   // 6m
+  // two records by one element are not rotations of one ciphertext
+  static bool distinctElements(const Rotations &mem, size_t b, size_t e) {
+    std::set<uint32_t> distinct;
+    for (size_t m = b; m < e; ++m) distinct.insert(mem[m].second[0]->galois);
+    return distinct.size() == e - b;
+  }
+  void weightedRotations(size_t minSums, size_t maxSums);   // 6m (several sums) and 6l (one)
   void sumOfRotations();      // 6s
-  void weightedRotations();   // 6l
   void hoist();               // 6h
   void transformTimesKey();   // 7 + 8
   void keyProductInverseOut();   // 7b
@@ -86,9 +144,10 @@ void Arch::fusePasses(std::vector<Stage> &st) {
   p.tensor();
   if (fuseDot) p.tensorDot();   // before (6): the multiply-accumulate chains it absorbs are not key products
   p.keyProduct();
-  if (fuseBsgs) p.sharedWeightedRotations();   // before (6s), (6l) and (6h): the records it merges are the ones they would claim
-  if (fuseRotsum) p.sumOfRotations();        // before (6l) and (6h): each record it merges is a group of one rotation to them
-  if (fuseLintrans) p.weightedRotations();   // before (6h): the records it merges are the ones (6h) would claim
+  // (6m, 6l) before (6s) and (6h): the records it merges are the ones (6h) would claim, and none of them is (6s)'s (their outputs go into products,
+  // not into sums).  fuse_bsgs: the groups with several sums, fuse_lintrans: the ones with one
+  if (fuseBsgs || fuseLintrans) p.weightedRotations(fuseLintrans ? 1 : 2, fuseBsgs ? HM_IP_LINTRANS_MULTI_MAX_OUT : 1);
+  if (fuseRotsum) p.sumOfRotations();   // before (6h): each record it merges is a group of one rotation to it
   if (fuseHoist) p.hoist();
   if (fuseHpip) p.transformTimesKey();
   if (fuseHpip && fuseIpInv && oneGpuKernels && p.cap("cap_ip_inverse_out")) p.keyProductInverseOut();
@@ -310,30 +369,18 @@ void Arch::Planner::tensor() {
 //      Reads: fusedTensor / extraOutputs (5).  Sets on the tensor record: dotOperands, OutputOperand, extraOutputs.
 void Arch::Planner::tensorDot() {
   Readers rd = readers();
-  std::map<Instruction *, std::pair<size_t, size_t>> place;   // record -> (stage, position)
-  for (size_t si = 0; si < st.size(); ++si)
-    for (size_t k = 0; k < st[si].ins.size(); ++k) place[st[si].ins[k]] = {si, k};
+  Placement place(st);
   std::vector<Instruction *> heads;
   for (auto &s : st)
     for (Instruction *i : s.ins)
       if (live(i) && i->fusedTensor && i->sumHead && i->dotOperands.empty()) heads.push_back(i);
-  // the one live reader of `a`, if it is an element-wise record of this modulus with this opcode
-  auto next = [&](AddrType a, ewe_opcode op, uint32_t mod) -> Instruction * {
-    auto &r = rd[a];
-    return r.size() == 1 && live(r[0]) && r[0]->ops == MULT && r[0]->opcode == op && r[0]->mod_id == mod && !r[0]->fusedTensor ? r[0] : nullptr;
-  };
   for (Instruction *c : heads) {
     // pair 1: MAC2 operands (P, S, R, T) = (c00, c11, c01, c10)
     c->dotOperands = {c->operandList[0], c->operandList[3], c->operandList[2], c->operandList[1]};
     AddrType d0 = c->extraOutputs[0], d1 = c->OutputOperand, d2 = c->extraOutputs[1];
     Instruction *last = c;
-    auto absorb = [&](Instruction *i) {
-      c->refInstructions += i->refInstructions;
-      dead.insert(i);
-      if (place[i] > place[last]) last = i;
-    };
     while (c->dotOperands.size() / 4 < HM_TENSOR_DOT_MAX_TERMS) {
-      Instruction *m0 = next(d0, EWE_MAC_ADD, c->mod_id), *m2 = next(d2, EWE_MAC_ADD, c->mod_id), *add = next(d1, EWE_ADD, c->mod_id);
+      Instruction *m0 = soleReader(rd, d0, EWE_MAC_ADD, c->mod_id), *m2 = soleReader(rd, d2, EWE_MAC_ADD, c->mod_id), *add = soleReader(rd, d1, EWE_ADD, c->mod_id);
       if (!m0 || !m2 || !add || m0->operandList[2] != d0 || m2->operandList[2] != d2) break;
       const AddrType other = add->operandList[0] == d1 ? add->operandList[2] : add->operandList[0];
       if ((add->operandList[0] != d1 && add->operandList[2] != d1) || other == d1) break;
@@ -342,18 +389,16 @@ void Arch::Planner::tensorDot() {
       const AddrType c00 = m0->operandList[0], c10 = m0->operandList[1], c01 = m2->operandList[0], c11 = m2->operandList[1];
       if (mac->operandList[0] != c00 || mac->operandList[1] != c11 || mac->operandList[2] != c01 || mac->operandList[3] != c10) break;
       c->dotOperands.insert(c->dotOperands.end(), {c00, c10, c01, c11});
-      absorb(m0); absorb(m2); absorb(mac); absorb(add);
+      for (Instruction *i : {m0, m2, mac, add}) {
+        absorb(c, i);
+        if (place.after(i, last)) last = i;
+      }
       d0 = m0->OutputOperand; d1 = add->OutputOperand; d2 = m2->OutputOperand;
     }
     c->OutputOperand = d1;
     c->extraOutputs = {d0, d2};
     for (const Write &w : recordWrites(*c)) producer[w.addr] = c;
-    if (last != c) {   // the record moves to where its last link stood
-      auto &from = st[place[c].first].ins;
-      from.erase(std::remove(from.begin(), from.end(), c), from.end());
-      auto &to = st[place[last].first].ins;
-      std::replace(to.begin(), to.end(), last, c);
-    }
+    place.moveTo(c, last);   // to where its last link stood
   }
 }
 
@@ -450,44 +495,27 @@ Arch::Planner::RotationGroups Arch::Planner::rotationGroups(Readers &rd) {
   return g;
 }
 
-// (6m) M >= 2 weighted sums of the SAME rotations (hbsgs, the baby step): the records (6l) would merge, when every rotation's two outputs are read
-//      by exactly M chains MUL, MAC_ADD ... against operands nobody produces (plaintexts), S_{m,k} = sum_r acc_{r,k} * pt_{m,r}, chain m using
-//      the same plaintext limb for k = 0 and k = 1 at every rotation, merge WITH all 2M chains into one record per (modulus, digit list):
-//      hm_inner_product_lintrans_multi forms every rotation's key product once and the M weighted sums in registers, and stores the S_{m,k} only.
-//      If every group m also has a chain that multiplies its plaintext limbs with automorphisms, by the rotations' elements, of ONE source (the Q
-//      limbs: U_m = sum_r sigma_r(c0) * pt_{m,r}; the M chains share the R automorphisms), the M chains join as addend outputs.  M = 1 is (6l)'s and
-//      stays untouched.  Never written: the rotated digits, the per-rotation sums, the rotated c0.  The first key-product record in stage order
-//      carries the merged one, as in (6l).
-//      Reads: the key-product records of (6).  Sets on the carrying record: ipX (the unrotated digits), ipY, ipHoistG, ipLinPt (group 0),
-//      ipMultiPt, ipLinAddend, OutputOperand, extraOutputs (group-major).  A non-empty ipHoistG keeps (7), (7b) and (12) off it.
-void Arch::Planner::sharedWeightedRotations() {
+// (6m, 6l) M weighted sums of the SAME rotations, minSums <= M <= maxSums (6m: M >= 2, hbsgs's baby step; 6l: M = 1, hlintrans): the records (6h)
+//      would merge, when every rotation's two outputs are read by exactly M chains MUL, MAC_ADD ... against operands nobody produces (plaintexts),
+//      S_{m,k} = sum_r acc_{r,k} * pt_{m,r}, chain m using the same plaintext limb for k = 0 and k = 1 at every rotation, merge WITH all 2M chains
+//      into one record per (modulus, digit list): hm_inner_product_lintrans (M = 1) / hm_inner_product_lintrans_multi form every rotation's key
+//      product once and the M weighted sums in registers, and store the S_{m,k} only.  If every group m also has a chain that multiplies its
+//      plaintext limbs with automorphisms, by the rotations' elements, of ONE source (the Q limbs: U_m = sum_r sigma_r(c0) * pt_{m,r}; the M chains
+//      share the R automorphisms), the M chains join as addend outputs: all of them or none.  Never written: the rotated digits, the per-rotation
+//      sums, the rotated c0.  The first key-product record in stage order carries the merged one: everything it reads is older, every reader of
+//      S_{m,k} and U_m comes after the chains' ends.
+//      Reads: the key-product records of (6).  Sets on the carrying record: ipX (the unrotated digits), ipY, ipHoistG, ipLinPt ([m][r]), ipLinAddend,
+//      OutputOperand, extraOutputs (group-major).  A non-empty ipHoistG keeps (7), (7b) and (12) off it.
+void Arch::Planner::weightedRotations(size_t minSums, size_t maxSums) {
   Readers rd = readers();
   RotationGroups found = rotationGroups(rd);
-  typedef std::vector<Instruction *> Chain;
-  auto chainFrom = [&](Instruction *first, size_t length) {   // as in (6l)
-    Chain c;
-    for (Instruction *i = first; c.size() < length;) {
-      c.push_back(i);
-      if (c.size() == length) break;
-      auto &next = rd[i->OutputOperand];
-      if (next.size() != 1 || !live(next[0]) || next[0]->ops != MULT || next[0]->opcode != EWE_MAC_ADD || next[0]->operandList[2] != i->OutputOperand ||
-          next[0]->mod_id != first->mod_id)
-        return Chain();
-      i = next[0];
-    }
-    return c;
-  };
-  auto isMul = [&](Instruction *i, uint32_t mod) { return live(i) && i->ops == MULT && i->opcode == EWE_MUL && i->mod_id == mod; };
   for (const DigitsKey &key : found.order) {
     const auto &mem = found.members[key];
     const size_t R = mem.size();
-    if (R > HM_IP_LINTRANS_MAX_ROT) continue;
-    std::set<uint32_t> distinct;
-    for (auto &m : mem) distinct.insert(m.second[0]->galois);
-    if (distinct.size() != R) continue;   // two records by one element are not rotations of one ciphertext
+    if (R > HM_IP_LINTRANS_MAX_ROT || !distinctElements(mem, 0, R)) continue;
     auto outOf = [&](size_t r, size_t k) { return k == 0 ? mem[r].first->OutputOperand : mem[r].first->extraOutputs[0]; };
     const size_t M = rd[outOf(0, 0)].size();
-    if (M < 2 || M > HM_IP_LINTRANS_MULTI_MAX_OUT) continue;   // M = 1: (6l)
+    if (M < minSums || M > maxSums) continue;
     // S_{m,k}: the chains in the stage order of their first links at k = 0; the k = 1 chain of group m is the one with group m's plaintexts
     std::vector<std::array<Chain, 2>> S(M);
     std::vector<std::vector<AddrType>> pt(M);
@@ -496,7 +524,7 @@ void Arch::Planner::sharedWeightedRotations() {
       Instruction *first = rd[outOf(0, 0)][m];
       ok = isMul(first, key.first) && first->operandList[0] == outOf(0, 0);
       if (!ok) break;
-      S[m][0] = chainFrom(first, R);
+      S[m][0] = chainFrom(rd, first, R);
       ok = S[m][0].size() == R;
       for (size_t r = 0; r < R && ok; ++r) {
         Instruction *l = S[m][0][r];
@@ -513,7 +541,7 @@ void Arch::Planner::sharedWeightedRotations() {
       while (m < M && !(S[m][1].empty() && pt[m][0] == first1[x]->operandList[1])) ++m;
       ok = m < M;
       if (!ok) break;
-      S[m][1] = chainFrom(first1[x], R);
+      S[m][1] = chainFrom(rd, first1[x], R);
       ok = S[m][1].size() == R;
       for (size_t r = 0; r < R && ok; ++r) ok = S[m][1][r]->operandList[0] == outOf(r, 1) && S[m][1][r]->operandList[1] == pt[m][r];
     }
@@ -533,7 +561,7 @@ void Arch::Planner::sharedWeightedRotations() {
     for (size_t m = 0; m < M && allU; ++m) {
       for (Instruction *u : rd[pt[m][0]]) {
         if (u == S[m][0][0] || u == S[m][1][0] || !isMul(u, key.first) || u->operandList[1] != pt[m][0]) continue;
-        Chain c = chainFrom(u, R);
+        Chain c = chainFrom(rd, u, R);
         std::vector<Instruction *> autos;
         for (size_t r = 0; r < c.size(); ++r) {
           Instruction *l = c[r], *a = producerOf(l->operandList[0]);
@@ -559,17 +587,16 @@ void Arch::Planner::sharedWeightedRotations() {
     Instruction *c = mem[0].first;
     std::vector<std::vector<AddrType>> ys;
     std::vector<uint32_t> gs;
-    auto absorb = [&](Instruction *i) { if (i != c && live(i)) { c->refInstructions += i->refInstructions; dead.insert(i); } };
     for (size_t r = 0; r < R; ++r) {
       ys.insert(ys.end(), mem[r].first->ipY.begin(), mem[r].first->ipY.end());
       gs.push_back(mem[r].second[0]->galois);
-      absorb(mem[r].first);
-      for (Instruction *a : mem[r].second) absorb(a);
+      absorb(c, mem[r].first);
+      for (Instruction *a : mem[r].second) absorb(c, a);
       for (size_t m = 0; m < M; ++m) {
-        for (size_t k = 0; k < 2; ++k) absorb(S[m][k][r]);
-        if (addend) absorb(U[m][r]);
+        for (size_t k = 0; k < 2; ++k) absorb(c, S[m][k][r]);
+        if (addend) absorb(c, U[m][r]);
       }
-      if (addend) absorb(addendAutos[r]);
+      if (addend) absorb(c, addendAutos[r]);
     }
     std::vector<AddrType> outs;
     for (size_t m = 0; m < M; ++m) {
@@ -577,15 +604,9 @@ void Arch::Planner::sharedWeightedRotations() {
       outs.push_back(S[m][1].back()->OutputOperand);
       if (addend) outs.push_back(U[m].back()->OutputOperand);
     }
-    c->ipX = key.second;
-    c->ipY = ys;
-    c->ipHoistG = gs;
-    c->ipLinPt = pt[0];
-    c->ipMultiPt = pt;
+    c->ipLinPt = pt;
     c->ipLinAddend = addend;
-    c->OutputOperand = outs[0];
-    c->extraOutputs.assign(outs.begin() + 1, outs.end());
-    for (const Write &w : recordWrites(*c)) producer[w.addr] = c;
+    carry(c, key.second, ys, gs, outs);
   }
 }
 
@@ -606,17 +627,13 @@ void Arch::Planner::sumOfRotations() {
   std::map<Instruction *, Member> candidates;   // (looked up only)
   for (const DigitsKey &key : found.order)
     for (auto &m : found.members[key]) candidates[m.first] = Member{m.first, m.second, key.second};
-  std::map<Instruction *, std::pair<size_t, size_t>> place;   // record -> (stage, position)
-  for (size_t si = 0; si < st.size(); ++si)
-    for (size_t k = 0; k < st[si].ins.size(); ++k) place[st[si].ins[k]] = {si, k};
+  Placement place(st);
   // the one live reader of `a`, if it is an ADD of this modulus that reads `a` once; `other`: what it adds to `a`
   auto addOf = [&](AddrType a, uint32_t mod, AddrType &other) -> Instruction * {
-    auto &r = rd[a];
-    if (r.size() != 1 || !live(r[0]) || r[0]->ops != MULT || r[0]->opcode != EWE_ADD || r[0]->mod_id != mod) return nullptr;
-    const AddrType x = r[0]->operandList[0], y = r[0]->operandList[2];
-    if ((x == a) == (y == a)) return nullptr;
-    other = x == a ? y : x;
-    return r[0];
+    Instruction *l = soleReader(rd, a, EWE_ADD, mod);
+    if (!l || (l->operandList[0] == a) == (l->operandList[2] == a)) return nullptr;
+    other = l->operandList[0] == a ? l->operandList[2] : l->operandList[0];
+    return l;
   };
   std::vector<Instruction *> order;
   for (auto &s : st)
@@ -652,8 +669,8 @@ void Arch::Planner::sumOfRotations() {
     // where the merged record goes: the place of the last key product or link of S_0, S_1.  Every limb's record then stands in the stage of
     // S_1's last link, so that the records with and without an addend share a launch
     Instruction *last = c;
-    for (Instruction *i : mem) if (place[i] > place[last]) last = i;
-    for (auto &chain : S) for (Instruction *i : chain) if (place[i] > place[last]) last = i;
+    for (Instruction *i : mem) if (place.after(i, last)) last = i;
+    for (auto &chain : S) for (Instruction *i : chain) if (place.after(i, last)) last = i;
     // U: an ADD chain over automorphisms by the records' elements, in their order, each of its own source (written, if at all, before that
     // place) and read by its link only
     std::vector<Instruction *> U, addendAutos;
@@ -667,12 +684,12 @@ void Arch::Planner::sumOfRotations() {
           Instruction *l = addOf(sum, mod, other), *a = l ? producerOf(other) : nullptr;
           if (!a || !live(a) || a->ops != AUTO || a->mod_id != mod || a->galois != candidates[mem[autos.size()]].autos[0]->galois || !onlyReader(rd, other, l))
             break;
-          if (Instruction *w = producerOf(a->operandList[0])) if (place[w] > place[last]) break;
+          if (Instruction *w = producerOf(a->operandList[0])) if (place.after(w, last)) break;
           autos.push_back(a);
           links.push_back(l);
           sum = l->OutputOperand;
         }
-        if (Instruction *w = producerOf(a0->operandList[0])) if (place[w] > place[last]) continue;
+        if (Instruction *w = producerOf(a0->operandList[0])) if (place.after(w, last)) continue;
         if (autos.size() != G) continue;
         U = links; addendAutos = autos;
         break;
@@ -682,130 +699,23 @@ void Arch::Planner::sumOfRotations() {
     std::vector<std::vector<AddrType>> xs, ys;
     std::vector<uint32_t> gs;
     std::vector<AddrType> addends;
-    auto absorb = [&](Instruction *i) { if (i != c) { c->refInstructions += i->refInstructions; dead.insert(i); } };
     for (size_t g = 0; g < G; ++g) {
       const Member &m = candidates[mem[g]];
       xs.push_back(m.digits);
       ys.insert(ys.end(), m.ip->ipY.begin(), m.ip->ipY.end());
       gs.push_back(m.autos[0]->galois);
       taken.insert(m.ip);
-      absorb(m.ip);
-      for (Instruction *a : m.autos) absorb(a);
-      if (g) { absorb(S[0][g - 1]); absorb(S[1][g - 1]); }
-      if (!U.empty()) { addends.push_back(addendAutos[g]->operandList[0]); absorb(addendAutos[g]); if (g) absorb(U[g - 1]); }
+      absorb(c, m.ip);
+      for (Instruction *a : m.autos) absorb(c, a);
+      if (g) { absorb(c, S[0][g - 1]); absorb(c, S[1][g - 1]); }
+      if (!U.empty()) { addends.push_back(addendAutos[g]->operandList[0]); absorb(c, addendAutos[g]); if (g) absorb(c, U[g - 1]); }
     }
-    c->ipX = xs[0];
+    std::vector<AddrType> outs = {S[0].back()->OutputOperand, S[1].back()->OutputOperand};
+    if (!U.empty()) outs.push_back(U.back()->OutputOperand);
     c->ipSumX = xs;
-    c->ipY = ys;
-    c->ipHoistG = gs;
     c->ipSumAddend = addends;
-    c->OutputOperand = S[0].back()->OutputOperand;
-    c->extraOutputs = {S[1].back()->OutputOperand};
-    if (!U.empty()) c->extraOutputs.push_back(U.back()->OutputOperand);
-    for (const Write &w : recordWrites(*c)) producer[w.addr] = c;
-    if (last != c) {   // the record moves there
-      auto &from = st[place[c].first].ins;
-      from.erase(std::remove(from.begin(), from.end(), c), from.end());
-      auto &to = st[place[last].first].ins;
-      std::replace(to.begin(), to.end(), last, c);
-    }
-  }
-}
-
-// (6l) weighted sum of rotations (hlintrans): the records (6h) would merge, when every rotation's two outputs are read only by ONE chain
-//      MUL, MAC_ADD ... against operands nobody produces (plaintexts), S_k = sum_r acc_{r,k} * pt_r, merge WITH those chains into one record per
-//      (modulus, digit list): hm_inner_product_lintrans forms the weighted sum in registers and stores S_0, S_1 only.  If a third chain multiplies
-//      the same plaintext limbs with automorphisms, by the rotations' elements, of ONE source (the Q limbs: U = sum_r sigma_r(c0) * pt_r), it joins
-//      as the record's addend output.  Never written: the rotated digits, the per-rotation sums, the rotated c0.  The first key-product record in
-//      stage order carries the merged one: everything it reads is older, every reader of S_k and U comes after the chains' ends.
-//      Reads: the key-product records of (6).  Sets on the carrying record: ipX (the unrotated digits), ipY, ipHoistG, ipLinPt, ipLinAddend,
-//      OutputOperand, extraOutputs.
-void Arch::Planner::weightedRotations() {
-  Readers rd = readers();
-  RotationGroups found = rotationGroups(rd);
-  // the `length` records of the chain that starts with `first` (a MUL) and goes on through MAC_ADD records, each the only reader of the one before
-  // (empty: there is no such chain)
-  typedef std::vector<Instruction *> Chain;
-  auto chainFrom = [&](Instruction *first, size_t length) {
-    Chain c;
-    for (Instruction *i = first; c.size() < length;) {
-      c.push_back(i);
-      if (c.size() == length) break;
-      auto &next = rd[i->OutputOperand];
-      if (next.size() != 1 || !live(next[0]) || next[0]->ops != MULT || next[0]->opcode != EWE_MAC_ADD || next[0]->operandList[2] != i->OutputOperand ||
-          next[0]->mod_id != first->mod_id)
-        return Chain();
-      i = next[0];
-    }
-    return c;
-  };
-  auto isMul = [&](Instruction *i, uint32_t mod) { return live(i) && i->ops == MULT && i->opcode == EWE_MUL && i->mod_id == mod; };
-  for (const DigitsKey &key : found.order) {
-    const auto &mem = found.members[key];
-    const size_t R = mem.size();
-    if (R > HM_IP_LINTRANS_MAX_ROT) continue;
-    std::set<uint32_t> distinct;
-    for (auto &m : mem) distinct.insert(m.second[0]->galois);
-    if (distinct.size() != R) continue;   // two records by one element are not rotations of one ciphertext
-    // S_k: link r multiplies rotation r's output k (operand a) with that rotation's plaintext limb (operand b, the same for both k)
-    Chain S[2];
-    std::vector<AddrType> pt;
-    bool ok = true;
-    for (size_t k = 0; k < 2 && ok; ++k) {
-      const AddrType out0 = k == 0 ? mem[0].first->OutputOperand : mem[0].first->extraOutputs[0];
-      auto &r0 = rd[out0];
-      ok = r0.size() == 1 && isMul(r0[0], key.first) && r0[0]->operandList[0] == out0;
-      if (!ok) break;
-      S[k] = chainFrom(r0[0], R);
-      ok = S[k].size() == R;
-      for (size_t r = 0; r < R && ok; ++r) {
-        Instruction *l = S[k][r];
-        const AddrType out = k == 0 ? mem[r].first->OutputOperand : mem[r].first->extraOutputs[0];
-        ok = l->operandList[0] == out && onlyReader(rd, out, l) && !producerOf(l->operandList[1]) && (k == 0 || l->operandList[1] == pt[r]);
-        if (ok && k == 0) pt.push_back(l->operandList[1]);
-      }
-    }
-    if (!ok) continue;
-    // U: a third MUL reader of the first plaintext limb whose chain multiplies pt_r with sigma_r of one source
-    Chain U;
-    AddrType addend = 0;
-    std::vector<Instruction *> addendAutos;
-    for (Instruction *u : rd[pt[0]]) {
-      if (u == S[0][0] || u == S[1][0] || !isMul(u, key.first) || u->operandList[1] != pt[0]) continue;
-      Chain c = chainFrom(u, R);
-      std::vector<Instruction *> autos;
-      for (size_t r = 0; r < c.size(); ++r) {
-        Instruction *l = c[r], *a = producerOf(l->operandList[0]);
-        if (l->operandList[1] != pt[r] || !a || a->ops != AUTO || !live(a) || a->mod_id != key.first || a->galois != mem[r].second[0]->galois ||
-            !onlyReader(rd, l->operandList[0], l) || (r && a->operandList[0] != autos[0]->operandList[0]))
-          break;
-        autos.push_back(a);
-      }
-      if (autos.size() != R) continue;
-      U = c; addend = autos[0]->operandList[0]; addendAutos = autos;
-      break;
-    }
-    Instruction *c = mem[0].first;
-    std::vector<std::vector<AddrType>> ys;
-    std::vector<uint32_t> gs;
-    auto absorb = [&](Instruction *i) { if (i != c) { c->refInstructions += i->refInstructions; dead.insert(i); } };
-    for (size_t r = 0; r < R; ++r) {
-      ys.insert(ys.end(), mem[r].first->ipY.begin(), mem[r].first->ipY.end());
-      gs.push_back(mem[r].second[0]->galois);
-      absorb(mem[r].first);
-      for (Instruction *a : mem[r].second) absorb(a);
-      for (size_t k = 0; k < 2; ++k) absorb(S[k][r]);
-      if (addend) { absorb(U[r]); absorb(addendAutos[r]); }
-    }
-    c->ipX = key.second;
-    c->ipY = ys;
-    c->ipHoistG = gs;
-    c->ipLinPt = pt;
-    c->ipLinAddend = addend;
-    c->OutputOperand = S[0].back()->OutputOperand;
-    c->extraOutputs = {S[1].back()->OutputOperand};
-    if (addend) c->extraOutputs.push_back(U.back()->OutputOperand);
-    for (const Write &w : recordWrites(*c)) producer[w.addr] = c;
+    carry(c, xs[0], ys, gs, outs);
+    place.moveTo(c, last);
   }
 }
 
@@ -821,9 +731,7 @@ void Arch::Planner::hoist() {
     const auto &mem = found.members[key];
     for (size_t b = 0; b < mem.size(); b += HM_IP_HOISTED_MAX_ROT) {
       const size_t e = std::min(mem.size(), b + (size_t)HM_IP_HOISTED_MAX_ROT);
-      std::set<uint32_t> distinct;
-      for (size_t m = b; m < e; ++m) distinct.insert(mem[m].second[0]->galois);
-      if (distinct.size() != e - b) continue;   // two records by one element are not rotations of one ciphertext
+      if (!distinctElements(mem, b, e)) continue;
       Instruction *c = mem[b].first;
       std::vector<AddrType> outs;
       std::vector<std::vector<AddrType>> ys;
@@ -834,15 +742,10 @@ void Arch::Planner::hoist() {
         outs.insert(outs.end(), i->extraOutputs.begin(), i->extraOutputs.end());
         ys.insert(ys.end(), i->ipY.begin(), i->ipY.end());
         gs.push_back(mem[m].second[0]->galois);
-        if (i != c) { c->refInstructions += i->refInstructions; dead.insert(i); }
-        for (Instruction *a : mem[m].second) { c->refInstructions += a->refInstructions; dead.insert(a); }
+        absorb(c, i);
+        for (Instruction *a : mem[m].second) absorb(c, a);
       }
-      c->ipX = key.second;
-      c->ipY = ys;
-      c->ipHoistG = gs;
-      c->OutputOperand = outs[0];
-      c->extraOutputs.assign(outs.begin() + 1, outs.end());
-      for (AddrType o : outs) producer[o] = c;
+      carry(c, key.second, ys, gs, outs);
     }
   }
 }

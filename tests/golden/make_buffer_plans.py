@@ -8,9 +8,10 @@ on both sides of a change and compare:
     python tests/golden/make_buffer_plans.py --point "hrotate_hoisted 16/10/3 rotations=16"
 
 The points: config_4_N15.cfg, L = 16, l = 10 at alpha = 10, 5, 4, 3 and 1 (beta = 1, 2, 3, 4 and 10: the three branches of the key product, a short
-last digit at alpha = 4 and 3, and alpha = 1) for hmult, hrotate and hrotate_hoisted with 1, 2 and 16 rotations; hadd, pmult and padd at alpha = 4.
+last digit at alpha = 4 and 3, and alpha = 1) for hmult, hrotate and hrotate_hoisted with 1, 2 and 16 rotations; hadd, pmult and padd at alpha = 4;
+at the same five alphas hlintrans and hrotsum with 1, 2 and 16 rotations, hdot with 1 and 4 terms, hbsgs with 2 x 2 and 4 x 3 steps.
 structural.json pins the Malloc lines of the five original ops against the reference at other points; this file is this project's own record and
-also covers what the reference does not have (hrotate_hoisted).
+also covers what the reference does not have (hrotate_hoisted, hlintrans, hdot, hrotsum, hbsgs).
 
 tests/test_host_buffer_plan.py imports POINTS and record() from here and asserts equality.  Regenerate only on purpose:
     python tests/golden/make_buffer_plans.py
@@ -32,9 +33,15 @@ PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "buffer_plans.js
 CLI = os.path.join(ROOT, "host", "Homulator.run")
 CFG, L, ELL = "config_4_N15.cfg", 16, 10
 KEY_SWITCH_OPS = [("hmult", {}), ("hrotate", {})] + [("hrotate_hoisted", {"rotations": r}) for r in (1, 2, 16)]
+# the ops that sum on the extended basis (their buffers are what the GPU tests and OpChain address by name)
+SUM_OPS = [("hlintrans", {"rotations": r}) for r in (1, 2, 16)] + [("hdot", {"terms": t}) for t in (1, 4)] + \
+          [("hrotsum", {"rotations": g}) for g in (1, 2, 16)] + [("hbsgs", {"rotations": r, "giants": g}) for r, g in ((2, 2), (4, 3))]
+ALPHAS = (10, 5, 4, 3, 1)
 # (op, alpha, overrides)
-POINTS = [(op, alpha, ov) for alpha in (10, 5, 4, 3, 1) for op, ov in KEY_SWITCH_OPS] + [(op, 4, {}) for op in ("hadd", "pmult", "padd")]
-FULL = {("hmult", 4), ("hrotate", 4), ("hrotate_hoisted", 4, 2), ("hadd", 4), ("pmult", 4), ("padd", 4)}
+POINTS = [(op, alpha, ov) for alpha in ALPHAS for op, ov in KEY_SWITCH_OPS] + [(op, 4, {}) for op in ("hadd", "pmult", "padd")] + \
+         [(op, alpha, ov) for alpha in ALPHAS for op, ov in SUM_OPS]
+FULL = {("hmult", 4), ("hrotate", 4), ("hrotate_hoisted", 4, 2), ("hadd", 4), ("pmult", 4), ("padd", 4),
+        ("hlintrans", 4, 2), ("hdot", 4, 4), ("hrotsum", 4, 2), ("hbsgs", 4, 2, 2)}
 
 
 def key(pt):

@@ -38,6 +38,14 @@ SWITCHES = [{}, {"fuse": 0}] + [{k: 0} for k in FUSE_KEYS_OFF] + [{"fuse_moddown
 CHAINS = [{"chain_bits": b} for b in (0, 60, 36)]   # headline point only: pass 4b does modulus arithmetic
 BATCHES = [1, 4]
 SET_C = ("config_4.cfg", SETS["C"]["L"], SETS["C"]["L"] // 2, SETS["C"]["alpha"])
+# the ops that sum on the extended basis: (op, variants, the op's own planner switch).  Each runs fused, unfused and with its own switch off;
+# hbsgs, whose halves are hlintrans's and hrotsum's passes, also with those off
+SUM_OPS = [("hlintrans", [{"rotations": r} for r in (1, 4, 16)], "fuse_lintrans"),
+           ("hdot", [{"terms": t} for t in (1, 4, 16)], "fuse_dot"),
+           ("hrotsum", [{"rotations": g} for g in (1, 2, 16)], "fuse_rotsum"),
+           ("hbsgs", [{"rotations": r, "giants": g} for r, g in ((1, 2), (4, 4), (16, 2), (3, 16))], "fuse_bsgs")]
+BSGS_SWITCHES = [{"fuse_rotsum": 0}, {"fuse_lintrans": 0, "fuse_bsgs": 0}, {"fuse_hoist": 0, "fuse_lintrans": 0, "fuse_bsgs": 0}]
+BSGS_TOP_BATCH = 5   # headline point only: the largest batch of hbsgs's bench shape (limb-polys are addressed by 16-bit indices)
 
 
 def param_points(op):
@@ -46,6 +54,10 @@ def param_points(op):
         for ell in (s["L"], s["L"] // 2, min_level(op)):
             pts.append((s["cfg"], s["L"], ell, s["alpha"]))
     return pts + [HEADLINE, ("config_4.cfg", 45, 20, 16), ("config_4_N15.cfg", 16, 10, 4), ("config_4.cfg", 8, 8, 8)]
+
+
+def sum_points(op):
+    return param_points("hmult" if op == "hdot" else "hrotate")   # hdot rescales, as hmult does
 
 
 def key(pt):
@@ -65,6 +77,14 @@ def grid():
                 for b in BATCHES:
                     pts.append((cfg, L, ell, alpha, op, dict(variant, **sw, batch=b)))
         g[name] = pts
+    for op, variants, own in SUM_OPS:
+        for variant in variants:
+            pts = []
+            for cfg, L, ell, alpha in sum_points(op):
+                for sw in [{}, {"fuse": 0}, {own: 0}] + (BSGS_SWITCHES if op == "hbsgs" else []):
+                    for b in BATCHES + ([BSGS_TOP_BATCH] if op == "hbsgs" and (cfg, L, ell, alpha) == HEADLINE else []):
+                        pts.append((cfg, L, ell, alpha, op, dict(variant, **sw, batch=b)))
+            g[" ".join([op] + [f"{k}={v}" for k, v in variant.items()])] = pts
     for cfg, L, ell, alpha in (HEADLINE, SET_C):
         for op in ("hmult", "hrotate"):
             for world in (2, 4, 8, 16):

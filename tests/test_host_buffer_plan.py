@@ -1,7 +1,7 @@
 """The buffer plan of every op on the count backend (no GPU) against tests/golden/buffer_plans.json (tests/golden/make_buffer_plans.py, recorded
 from this project's own stage-graph builders): the CLI's `Malloc <name> from <first> to <last>` lines in order, and every named buffer of the op with
-its limb count.  tests/test_host_structural.py holds the five original ops to the reference's Malloc lines; this also covers hrotate_hoisted, the
-key product's three branches (beta = 1, 2, >= 3), a short last digit and alpha = 1."""
+its limb count.  tests/test_host_structural.py holds the five original ops to the reference's Malloc lines; this also covers hrotate_hoisted,
+hlintrans, hdot, hrotsum and hbsgs, the key product's three branches (beta = 1, 2, >= 3), a short last digit and alpha = 1."""
 import importlib.util
 import json
 import os
@@ -18,8 +18,8 @@ POINTS, key, record = gen.POINTS, gen.key, gen.record
 
 
 def test_fixture_covers_every_point():
-    assert sorted(GOLD) == sorted(key(p) for p in POINTS) and len(GOLD) == 28
-    assert sum("malloc" in g for g in GOLD.values()) == 6   # one readable point per op
+    assert sorted(GOLD) == sorted(key(p) for p in POINTS) and len(GOLD) == 28 + 5 * 10   # ... and ten variants of the summing ops at five alphas
+    assert sum("malloc" in g for g in GOLD.values()) == 10   # one readable point per op
 
 
 @pytest.mark.parametrize("pt", POINTS, ids=key)
