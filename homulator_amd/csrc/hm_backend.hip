@@ -539,6 +539,21 @@ __global__ void __launch_bounds__(256) k_inner_product_lintrans_multi(HmIpLinMul
   if (entry < a.n_limbs && blockIdx.y * TILE < a.n_out) hm_ip_lintrans_multi_thread<TERMS, TILE>(a, entry, blockIdx.x % per_limb, threadIdx.x, blockIdx.y);
 }
 template <int TERMS>
+__global__ void __launch_bounds__(256) k_inner_product_lintrans_id1(HmIpLinIdOneArgs a) {
+  const uint32_t per_limb = (1u << a.logN) / HM_IP_CHUNK, entry = blockIdx.x / per_limb;
+  if (entry < a.n_limbs) hm_ip_lintrans_thread<TERMS, true>(a, entry, blockIdx.x % per_limb, threadIdx.x);
+}
+template <int TERMS, int TILE>
+__global__ void __launch_bounds__(256) k_inner_product_lintrans_id(HmIpLinIdArgs a) {
+  const uint32_t per_limb = (1u << a.logN) / HM_IP_CHUNK, entry = blockIdx.x / per_limb;
+  if (entry < a.n_limbs && blockIdx.y * TILE < a.n_out) hm_ip_lintrans_multi_thread<TERMS, TILE, true>(a, entry, blockIdx.x % per_limb, threadIdx.x, blockIdx.y);
+}
+template <int TERMS>
+__global__ void __launch_bounds__(256) k_inner_product_rotsum_init(HmIpSumInitArgs a) {
+  const uint32_t per_limb = (1u << a.logN) / HM_IP_CHUNK, entry = blockIdx.x / per_limb;
+  if (entry < a.n_limbs) hm_ip_rotsum_thread<TERMS, true>(a, entry, blockIdx.x % per_limb, threadIdx.x);
+}
+template <int TERMS>
 __global__ void __launch_bounds__(256) k_inner_product_rotsum(HmIpSumArgs a) {
   const uint32_t per_limb = (1u << a.logN) / HM_IP_CHUNK, entry = blockIdx.x / per_limb;
   if (entry < a.n_limbs) hm_ip_rotsum_thread<TERMS>(a, entry, blockIdx.x % per_limb, threadIdx.x);
@@ -1684,11 +1699,16 @@ static void (*const k_ip[HM_IP_MAX_TERMS][HM_IP_MAX_OUT])(HmIpArgs) = {{k_inner_
 static void (*const k_ip_hoisted[HM_IP_MAX_TERMS][1])(HmIpHoistArgs) = HM_K(k_inner_product_hoisted);
 static void (*const k_ip_lintrans[HM_IP_MAX_TERMS][1])(HmIpLinArgs) = HM_K(k_inner_product_lintrans);
 static void (*const k_ip_rotsum[HM_IP_MAX_TERMS][1])(HmIpSumArgs) = HM_K(k_inner_product_rotsum);
+static void (*const k_ip_rotsum_init[HM_IP_MAX_TERMS][1])(HmIpSumInitArgs) = HM_K(k_inner_product_rotsum_init);   // ... with initial sums
+static void (*const k_ip_lintrans_id1[HM_IP_MAX_TERMS][1])(HmIpLinIdOneArgs) = HM_K(k_inner_product_lintrans_id1);   // one sum with the identity step
 #undef HM_K
 // several weighted sums: by [n_terms - 1][tile size: 0 = HM_IP_LINTRANS_MULTI_TILE, 1 = the other size of the A/B (hm_set_option "ip_multi_tile")]
 #define HM_IP_MULTI_TILE_ALT (HM_IP_LINTRANS_MULTI_TILE == 4 ? 2 : 4)
 #define HM_K(t) {k_inner_product_lintrans_multi<t, HM_IP_LINTRANS_MULTI_TILE>, k_inner_product_lintrans_multi<t, HM_IP_MULTI_TILE_ALT>}
 static void (*const k_ip_lintrans_multi[HM_IP_MAX_TERMS][2])(HmIpLinMultiArgs) = {HM_K(1), HM_K(2), HM_K(3), HM_K(4)};
+#undef HM_K
+#define HM_K(t) {k_inner_product_lintrans_id<t, HM_IP_LINTRANS_MULTI_TILE>, k_inner_product_lintrans_id<t, HM_IP_MULTI_TILE_ALT>}
+static void (*const k_ip_lintrans_id[HM_IP_MAX_TERMS][2])(HmIpLinIdArgs) = {HM_K(1), HM_K(2), HM_K(3), HM_K(4)};   // ... with the identity step
 #undef HM_K
 template <class Args, size_t OUTS>
 static void launch_ip(hm_ctx *c, void (*const (&kernel)[HM_IP_MAX_TERMS][OUTS])(Args), const Args &a, uint32_t T, uint32_t O = 1) {
@@ -1716,10 +1736,11 @@ static const char *const kAddendQuartet = "null argument (addend, addend_limbs, 
 struct IpOperand { const char *name; const void *base; const uint32_t *limbs; uint32_t count; };
 static hm_status ip_sum_check(hm_ctx *c, const char *what, const char *null_msg, uint32_t T, const char *second, uint32_t v, uint32_t vmax, const uint32_t *galois,
                               std::vector<IpOperand> ins, const IpOperand &addSrc, const IpOperand &out, const IpOperand &addOut, const uint32_t *mod_ids,
-                              uint32_t n) {
+                              uint32_t n, const IpOperand *addOut1 = nullptr) {
   std::vector<IpList> lists;
   for (const IpOperand &in : ins) lists.push_back({in.limbs, in.count});
   for (const IpOperand *o : {&out, &addSrc, &addOut}) lists.push_back({o->limbs, o->count});
+  if (addOut1) lists.push_back({addOut1->limbs, addOut1->count});   // (the identity step: the second addend's outputs; its source is among `ins`)
   if (hm_status st = ip_check(c, what, null_msg, T, second, v, vmax, galois, lists, mod_ids, n)) return st;
   ins.push_back(addSrc);
   for (const IpOperand &in : ins) {
@@ -1727,6 +1748,8 @@ static hm_status ip_sum_check(hm_ctx *c, const char *what, const char *null_msg,
       return fail(c, HM_ERR_ARG, "%s: an output limb-poly overlaps %s", what, in.name);
     if (in.count && addOut.count && hm_limbs_overlap(addOut.base, addOut.limbs, addOut.count, in.base, in.limbs, in.count, c->P.N))
       return fail(c, HM_ERR_ARG, "%s: an addend output limb-poly overlaps %s", what, in.name);
+    if (in.count && addOut1 && addOut1->count && hm_limbs_overlap(addOut1->base, addOut1->limbs, addOut1->count, in.base, in.limbs, in.count, c->P.N))
+      return fail(c, HM_ERR_ARG, "%s: a second addend output limb-poly overlaps %s", what, in.name);
   }
   return HM_OK;
 }
@@ -1842,16 +1865,16 @@ extern "C" hm_status hm_inner_product_lintrans(hm_ctx *c, const hm_ip_lintrans_d
 }
 
 // several weighted sums of the same rotations: the weighted sum's records, shared by the outputs, then every output's limbs and plaintexts, in one table
-extern "C" hm_status hm_inner_product_lintrans_multi(hm_ctx *c, const hm_ip_lintrans_multi_desc *d) {
-  static const char *const what = "hm_inner_product_lintrans_multi";
-  static const hm_ip_lintrans_multi_desc none = {};
-  if (!c) return HM_ERR_ARG;
-  if (!d) d = &none;
+// `id` != nullptr: hm_inner_product_lintrans_id, whose sums are `d` (the identity plaintexts are limbs of d->pt; the second addend's source is one
+// more input, its outputs one more set of outputs)
+static hm_status ip_lintrans_multi(hm_ctx *c, const char *what, const hm_ip_lintrans_multi_desc *d, const hm_ip_lintrans_id_desc *id) {
   const bool anyAdd = d->addend_limbs != nullptr;
   const char *null = nullptr;
   if (!d->x || !d->x_limbs || !d->y || !d->y_limbs || !d->pt || !d->pt_limbs || !d->out || !d->out_limbs || !d->mod_ids || !d->galois) null = "null argument";
   else if (anyAdd && (!d->addend || !d->addend_out || !d->addend_out_limbs)) null = kAddendQuartet;
   else if (!anyAdd && (d->addend || d->addend_out || d->addend_out_limbs)) null = "null argument (an addend or addend outputs without addend_limbs)";
+  else if (id && (!anyAdd || !id->id_pt_limbs || !id->addend1 || !id->addend1_limbs || !id->addend1_out || !id->addend1_out_limbs))
+    null = "null argument (the identity step needs the addend, id_pt_limbs, addend1, addend1_limbs, addend1_out and addend1_out_limbs)";
   const uint32_t n = d->n, T = d->n_terms, R = d->n_rot, G = d->n_out, N = c->P.N;
   if (!null && (G == 0 || G > HM_IP_LINTRANS_MULTI_MAX_OUT)) return fail(c, HM_ERR_ARG, "%s: n_out = %u, must be in [1,%d]", what, G, HM_IP_LINTRANS_MULTI_MAX_OUT);
   std::vector<uint32_t> addSrc, addOut;   // the entries that carry an addend: their source, and every output's addend output [n_out][those entries]
@@ -1860,30 +1883,69 @@ extern "C" hm_status hm_inner_product_lintrans_multi(hm_ctx *c, const hm_ip_lint
   for (uint32_t e = 0; !null && anyAdd && e < G * n; ++e)
     if (d->addend_limbs[e % n] != HM_NO_LIMB) addOut.push_back(d->addend_out_limbs[e]);
   const uint32_t nAdd = (uint32_t)addSrc.size();
+  std::vector<uint32_t> idPt, add1Src, add1Out;   // the identity step, on the entries that carry an addend: [n_out][those], [those], [n_out][those]
+  for (uint32_t i = 0; !null && id && i < n; ++i) {
+    if ((id->addend1_limbs[i] == HM_NO_LIMB) != (d->addend_limbs[i] == HM_NO_LIMB))
+      return fail(c, HM_ERR_ARG, "%s: entry %u has one of the two addend sources only", what, i);
+    if (id->addend1_limbs[i] != HM_NO_LIMB) add1Src.push_back(id->addend1_limbs[i]);
+  }
+  for (uint32_t e = 0; !null && id && e < G * n; ++e)
+    if (d->addend_limbs[e % n] != HM_NO_LIMB) { idPt.push_back(id->id_pt_limbs[e]); add1Out.push_back(id->addend1_out_limbs[e]); }
   hm_status st;
-  if ((st = ip_sum_check(c, what, null, T, "n_rot", R, HM_IP_LINTRANS_MAX_ROT, d->galois,
-                         {{"a digit (x)", d->x, d->x_limbs, n * T}, {"a key limb-poly (y)", d->y, d->y_limbs, R * n * 2 * T},
-                          {"a plaintext limb-poly (pt)", d->pt, d->pt_limbs, G * R * n}},
+  std::vector<IpOperand> ins = {{"a digit (x)", d->x, d->x_limbs, n * T}, {"a key limb-poly (y)", d->y, d->y_limbs, R * n * 2 * T},
+                                {"a plaintext limb-poly (pt)", d->pt, d->pt_limbs, G * R * n}};
+  IpOperand out1 = {"", nullptr, nullptr, 0};
+  if (id && !null) {
+    ins.push_back({"an identity plaintext limb-poly (pt)", d->pt, idPt.data(), (uint32_t)idPt.size()});
+    ins.push_back({"the second addend source", id->addend1, add1Src.data(), (uint32_t)add1Src.size()});
+    out1 = {"", id->addend1_out, add1Out.data(), (uint32_t)add1Out.size()};
+  }
+  if ((st = ip_sum_check(c, what, null, T, "n_rot", R, id ? HM_IP_LINTRANS_ID_MAX_ROT : HM_IP_LINTRANS_MAX_ROT, d->galois, ins,
                          {"the addend source", d->addend, addSrc.data(), nAdd}, {"", d->out, d->out_limbs, G * n * 2},
-                         {"", d->addend_out, addOut.data(), G * nAdd}, d->mod_ids, n)))
+                         {"", d->addend_out, addOut.data(), G * nAdd}, d->mod_ids, n, id ? &out1 : nullptr)))
     return st;
   // ... and no two outputs each other
   {
     std::vector<uintptr_t> starts;
     for (uint32_t i = 0; i < G * n * 2; ++i) starts.push_back(reinterpret_cast<uintptr_t>(d->out) + (uintptr_t)d->out_limbs[i] * N * 8);
     for (uint32_t i = 0; i < G * nAdd; ++i) starts.push_back(reinterpret_cast<uintptr_t>(d->addend_out) + (uintptr_t)addOut[i] * N * 8);
+    for (uint32_t x : add1Out) starts.push_back(reinterpret_cast<uintptr_t>(id->addend1_out) + (uintptr_t)x * N * 8);
     std::sort(starts.begin(), starts.end());
     for (size_t i = 1; i < starts.size(); ++i)
       if (starts[i] - starts[i - 1] < (uintptr_t)N * 8) return fail(c, HM_ERR_ARG, "%s: two output limb-polys overlap", what);
   }
   if (n == 0) return HM_OK;
-  std::vector<unsigned char> table(hm_ip_multi_table_bytes(n, R, G));
+  // one sum with the identity step: the single-sum kernel form, its records (hm_inner_product_lintrans's) with the identity records behind them
+  if (id && G == 1) {
+    const size_t recBytes = (size_t)R * n * sizeof(HmIpLinRec);
+    std::vector<unsigned char> one(recBytes + hm_ip_id_bytes(n, 1));
+    HmIpLinRec *r1 = reinterpret_cast<HmIpLinRec *>(one.data());
+    hm_ip_fill_recs(r1, d->x_limbs, d->y_limbs, d->out_limbs, (size_t)n * 2, d->mod_ids, n, T, 2, R);
+    hm_ip_fill_lin(r1, d->pt_limbs, d->addend_limbs, d->addend_out_limbs, n, R);
+    hm_ip_fill_id(one.data(), id->id_pt_limbs, d->addend_limbs, id->addend1_limbs, id->addend1_out_limbs, n, R, 1, recBytes);
+    HM_HIP(c, hipSetDevice(c->device));
+    const void *tab1 = nullptr;
+    if ((st = device_table(c, one.data(), one.size(), &tab1))) return st;
+    HmIpLinIdOneArgs a1;
+    a1.rec = static_cast<const HmIpLinRec *>(tab1);
+    a1.ids = reinterpret_cast<const HmIpIdRec *>(a1.rec + (size_t)R * n);
+    a1.add1_src = reinterpret_cast<const uint16_t *>(a1.ids + n);
+    a1.x = d->x; a1.y = d->y; a1.pt = d->pt; a1.addend = d->addend; a1.out = d->out; a1.addend_out = d->addend_out;
+    a1.addend1 = id->addend1; a1.addend1_out = id->addend1_out;
+    a1.mods = c->d_mods; a1.logN = c->P.logN; a1.n_limbs = n; a1.n_rot = R;
+    for (uint32_t r = 0; r < HM_IP_LINTRANS_MAX_ROT; ++r) a1.galois[r] = r < R ? d->galois[r] : 1u;
+    launch_ip(c, k_ip_lintrans_id1, a1, T);
+    HM_HIP(c, hipGetLastError());
+    return HM_OK;
+  }
+  std::vector<unsigned char> table(id ? hm_ip_id_table_bytes(n, R, G) : hm_ip_multi_table_bytes(n, R, G));
   HmIpLinRec *recs = reinterpret_cast<HmIpLinRec *>(table.data());
   hm_ip_fill_recs(recs, d->x_limbs, d->y_limbs, d->out_limbs, (size_t)n * 2, d->mod_ids, n, T, 2, R);
   hm_ip_fill_lin(recs, d->pt_limbs, d->addend_limbs, d->addend_out_limbs, n, R);
   hm_ip_fill_multi(table.data(), d->pt_limbs, d->out_limbs, d->addend_limbs, d->addend_out_limbs, n, R, G);
+  if (id) hm_ip_fill_id(table.data(), id->id_pt_limbs, d->addend_limbs, id->addend1_limbs, id->addend1_out_limbs, n, R, G);
   HM_HIP(c, hipSetDevice(c->device));
-  HmIpLinMultiArgs a;
+  HmIpLinIdArgs a;   // (without the identity step: its base, HmIpLinMultiArgs, is the kernel's argument)
   const void *tab = nullptr;
   if ((st = device_table(c, table.data(), table.size(), &tab))) return st;
   a.rec = static_cast<const HmIpLinRec *>(tab);
@@ -1893,23 +1955,42 @@ extern "C" hm_status hm_inner_product_lintrans_multi(hm_ctx *c, const hm_ip_lint
   a.mods = c->d_mods; a.logN = c->P.logN; a.n_limbs = n; a.n_rot = R; a.n_out = G;
   for (uint32_t r = 0; r < HM_IP_LINTRANS_MAX_ROT; ++r) a.galois[r] = r < R ? d->galois[r] : 1u;
   const uint32_t alt = c->ip_multi_tile && c->ip_multi_tile != HM_IP_LINTRANS_MULTI_TILE, tile = alt ? HM_IP_MULTI_TILE_ALT : HM_IP_LINTRANS_MULTI_TILE;
-  hipLaunchKernelGGL(k_ip_lintrans_multi[T - 1][alt], dim3(n * (N / HM_IP_CHUNK), (G + tile - 1) / tile), dim3(256), 0, c->stream, a);
+  const dim3 grid(n * (N / HM_IP_CHUNK), (G + tile - 1) / tile);
+  if (id) {
+    a.ids = reinterpret_cast<const HmIpIdRec *>(a.pts + (size_t)G * R * n);
+    a.add1_src = reinterpret_cast<const uint16_t *>(a.ids + (size_t)G * n);
+    a.addend1 = id->addend1; a.addend1_out = id->addend1_out;
+    hipLaunchKernelGGL(k_ip_lintrans_id[T - 1][alt], grid, dim3(256), 0, c->stream, a);
+  } else {
+    hipLaunchKernelGGL(k_ip_lintrans_multi[T - 1][alt], grid, dim3(256), 0, c->stream, static_cast<const HmIpLinMultiArgs &>(a));
+  }
   HM_HIP(c, hipGetLastError());
   return HM_OK;
 }
-
-// sum of rotations of different ciphertexts: one record per (ciphertext, entry), every ciphertext's outputs are ciphertext 0's
-extern "C" hm_status hm_inner_product_rotsum(hm_ctx *c, const hm_ip_rotsum_desc *d) {
-  static const char *const what = "hm_inner_product_rotsum";
-  static const hm_ip_rotsum_desc none = {};
+extern "C" hm_status hm_inner_product_lintrans_multi(hm_ctx *c, const hm_ip_lintrans_multi_desc *d) {
+  static const hm_ip_lintrans_multi_desc none = {};
+  if (!c) return HM_ERR_ARG;
+  return ip_lintrans_multi(c, "hm_inner_product_lintrans_multi", d ? d : &none, nullptr);
+}
+// ... with the identity step: the same table with the identity records behind it, the same geometry, the ID form of the kernel; one sum
+// (n_out = 1): the single-sum kernel form on hm_inner_product_lintrans's table, with the identity records behind it
+extern "C" hm_status hm_inner_product_lintrans_id(hm_ctx *c, const hm_ip_lintrans_id_desc *d) {
+  static const hm_ip_lintrans_id_desc none = {};
   if (!c) return HM_ERR_ARG;
   if (!d) d = &none;
+  return ip_lintrans_multi(c, "hm_inner_product_lintrans_id", &d->sums, d);
+}
+
+// sum of rotations of different ciphertexts: one record per (ciphertext, entry), every ciphertext's outputs are ciphertext 0's
+// `in` != nullptr: hm_inner_product_rotsum_init, whose sum is `d` (the initial sums are two more inputs, read where the outputs are written)
+static hm_status ip_rotsum(hm_ctx *c, const char *what, const hm_ip_rotsum_desc *d, const hm_ip_rotsum_init_desc *in) {
   const bool anyAdd = d->addend_limbs != nullptr;
   const char *null = nullptr;
   if (!d->x || !d->x_limbs || !d->y || !d->y_limbs || !d->out || !d->out_limbs || !d->mod_ids || !d->galois) null = "null argument";
   else if (anyAdd && (!d->addend || !d->addend_out || !d->addend_out_limbs)) null = kAddendQuartet;
-  const uint32_t n = d->n, T = d->n_terms, G = d->n_ct, N = c->P.N;
-  const bool counts = T >= 1 && T <= HM_IP_MAX_TERMS && G >= 1 && G <= HM_IP_ROTSUM_MAX_CT;
+  else if (in && (!in->init || !in->init_limbs || (anyAdd && !in->addend_init_limbs))) null = "null argument (init, init_limbs; addend_init_limbs with an addend)";
+  const uint32_t n = d->n, T = d->n_terms, G = d->n_ct, N = c->P.N, maxCt = in ? HM_IP_ROTSUM_INIT_MAX_CT : HM_IP_ROTSUM_MAX_CT;
+  const bool counts = T >= 1 && T <= HM_IP_MAX_TERMS && G >= 1 && G <= maxCt;
   std::vector<uint32_t> addSrc, addOut;   // the addend sources [n_ct][entries that carry one] and those entries' outputs
   for (uint32_t e = 0; !null && counts && anyAdd && e < G * n; ++e) {
     const bool has = d->addend_limbs[e] != HM_NO_LIMB;
@@ -1919,9 +2000,19 @@ extern "C" hm_status hm_inner_product_rotsum(hm_ctx *c, const hm_ip_rotsum_desc 
     if (has && e < n) addOut.push_back(d->addend_out_limbs[e]);
   }
   const uint32_t nAdd = (uint32_t)addOut.size();
+  std::vector<uint32_t> addInit;   // the initial addend sums, on the entries that carry addend sources
+  for (uint32_t i = 0; !null && counts && in && anyAdd && i < n; ++i) {
+    if ((in->addend_init_limbs[i] != HM_NO_LIMB) != (d->addend_limbs[i] != HM_NO_LIMB))
+      return fail(c, HM_ERR_ARG, "%s: entry %u has an initial addend sum without addend sources, or the reverse", what, i);
+    if (in->addend_init_limbs[i] != HM_NO_LIMB) addInit.push_back(in->addend_init_limbs[i]);
+  }
   hm_status st;
-  if ((st = ip_sum_check(c, what, null, T, "n_ct", G, HM_IP_ROTSUM_MAX_CT, d->galois,
-                         {{"a digit (x)", d->x, d->x_limbs, G * n * T}, {"a key limb-poly (y)", d->y, d->y_limbs, G * n * 2 * T}},
+  std::vector<IpOperand> ins = {{"a digit (x)", d->x, d->x_limbs, G * n * T}, {"a key limb-poly (y)", d->y, d->y_limbs, G * n * 2 * T}};
+  if (in && !null) {
+    ins.push_back({"an initial sum (init)", in->init, in->init_limbs, n * 2});
+    ins.push_back({"an initial addend sum", d->addend, addInit.data(), (uint32_t)addInit.size()});
+  }
+  if ((st = ip_sum_check(c, what, null, T, "n_ct", G, maxCt, d->galois, ins,
                          {"an addend source", d->addend, addSrc.data(), G * nAdd}, {"", d->out, d->out_limbs, n * 2}, {"", d->addend_out, addOut.data(), nAdd},
                          d->mod_ids, n)))
     return st;
@@ -1935,18 +2026,42 @@ extern "C" hm_status hm_inner_product_rotsum(hm_ctx *c, const hm_ip_rotsum_desc 
   if (nAdd && hm_limbs_overlap(d->out, d->out_limbs, n * 2, d->addend_out, addOut.data(), nAdd, N))
     return fail(c, HM_ERR_ARG, "%s: an output limb-poly overlaps an addend output", what);
   if (n == 0) return HM_OK;
-  std::vector<HmIpSumRec> recs((size_t)G * n);
-  hm_ip_fill_recs(recs.data(), d->x_limbs, d->y_limbs, d->out_limbs, (size_t)n * 2, d->mod_ids, n, T, 2, G);
-  hm_ip_fill_sum(recs.data(), d->x_limbs, d->addend_limbs, d->addend_out_limbs, n, T, G);
+  // one table: the records, then (with initial sums) one HmIpSumInit per entry
+  const size_t recBytes = (size_t)G * n * sizeof(HmIpSumRec);
+  std::vector<uint32_t> table((recBytes + (in ? (size_t)n * sizeof(HmIpSumInit) : 0) + 3) / 4);
+  HmIpSumRec *recs = reinterpret_cast<HmIpSumRec *>(table.data());
+  hm_ip_fill_recs(recs, d->x_limbs, d->y_limbs, d->out_limbs, (size_t)n * 2, d->mod_ids, n, T, 2, G);
+  hm_ip_fill_sum(recs, d->x_limbs, d->addend_limbs, d->addend_out_limbs, n, T, G);
+  if (in) hm_ip_fill_sum_init(reinterpret_cast<HmIpSumInit *>(recs + (size_t)G * n), in->init_limbs, anyAdd ? in->addend_init_limbs : nullptr, n);
   HM_HIP(c, hipSetDevice(c->device));
-  HmIpSumArgs a;
-  if ((st = ip_device_recs(c, recs, &a.rec))) return st;
+  HmIpSumInitArgs a;   // (without initial sums: its base, HmIpSumArgs, is the kernel's argument)
+  const void *tab = nullptr;
+  if ((st = device_table(c, table.data(), table.size() * 4, &tab))) return st;
+  a.rec = static_cast<const HmIpSumRec *>(tab);
   a.x = d->x; a.y = d->y; a.addend = d->addend; a.out = d->out; a.addend_out = d->addend_out;
   a.mods = c->d_mods; a.logN = c->P.logN; a.n_limbs = n; a.n_ct = G;
   for (uint32_t g = 0; g < HM_IP_ROTSUM_MAX_CT; ++g) a.galois[g] = g < G ? d->galois[g] : 1u;
-  launch_ip(c, k_ip_rotsum, a, T);
+  if (in) {
+    a.init = in->init;
+    a.inits = reinterpret_cast<const HmIpSumInit *>(a.rec + (size_t)G * n);
+    launch_ip(c, k_ip_rotsum_init, a, T);
+  } else {
+    launch_ip(c, k_ip_rotsum, static_cast<const HmIpSumArgs &>(a), T);
+  }
   HM_HIP(c, hipGetLastError());
   return HM_OK;
+}
+extern "C" hm_status hm_inner_product_rotsum(hm_ctx *c, const hm_ip_rotsum_desc *d) {
+  static const hm_ip_rotsum_desc none = {};
+  if (!c) return HM_ERR_ARG;
+  return ip_rotsum(c, "hm_inner_product_rotsum", d ? d : &none, nullptr);
+}
+// ... with initial sums: the accumulators start from init / the initial addend sum instead of zero
+extern "C" hm_status hm_inner_product_rotsum_init(hm_ctx *c, const hm_ip_rotsum_init_desc *d) {
+  static const hm_ip_rotsum_init_desc none = {};
+  if (!c) return HM_ERR_ARG;
+  if (!d) d = &none;
+  return ip_rotsum(c, "hm_inner_product_rotsum_init", &d->sum, d);
 }
 
 // The kernel of hm_ntt_inner_product's second launch: OUTS keys; INVOUT 0 = outputs in evaluation form, 1 = every limb's outputs leave as the

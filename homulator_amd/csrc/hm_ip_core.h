@@ -1,6 +1,8 @@
 // hm_ip_core.h — K5, the inner product with the evaluation key, in its five forms: plain (hm_inner_product_ex), hoisted
 // (hm_inner_product_hoisted), the weighted sum of rotations (hm_inner_product_lintrans), the sum of rotations of different ciphertexts
 // (hm_inner_product_rotsum) and several weighted sums of the same rotations (hm_inner_product_lintrans_multi).
+// The weighted sums also come with an identity step (hm_inner_product_lintrans_id), the sum over ciphertexts with initial sums
+// (hm_inner_product_rotsum_init): template flags of the same cores, off for the forms above.
 // Per-thread bodies (no cross-thread state) and the records they read, shared by the HIP kernels, the entry points and the host emulator.
 // A workgroup of 256 threads covers 512 coefficients of one entry: thread tid of chunk c owns the aligned pair at c * 512 + 2 * tid.
 //
@@ -36,7 +38,11 @@ struct HmIpSumRec : HmIpKeys {   // one per (ciphertext, entry): its own digits,
 struct HmIpMultiOut {   // several weighted sums: one per (output, entry), behind the HmIpLinRec records [n_rot][n] the outputs share (whose pt, out and add_out are output 0's)
   uint16_t out[2], add_out, pad;
 };
-static_assert(sizeof(HmIpKeys) == 28 && sizeof(HmIpHoistRec) == 32 && sizeof(HmIpLinRec) == 40 && sizeof(HmIpSumRec) == 36 && sizeof(HmIpMultiOut) == 8,
+struct HmIpIdRec {   // the identity step of several weighted sums: one per (output, entry), behind the table of HmIpMultiOut and plaintext limbs
+  uint16_t pt, add1_out;   // the identity plaintext's limb (in pt) and the limb of W = pt_0 * c1 (in addend1_out); read on entries with an addend only
+};
+static_assert(sizeof(HmIpKeys) == 28 && sizeof(HmIpHoistRec) == 32 && sizeof(HmIpLinRec) == 40 && sizeof(HmIpSumRec) == 36 && sizeof(HmIpMultiOut) == 8 &&
+                  sizeof(HmIpIdRec) == 4,
               "the device tables' record sizes");
 
 struct HmIpArgs {
@@ -73,6 +79,17 @@ struct HmIpLinMultiArgs {
   uint32_t logN, n_limbs, n_rot, n_out;
   uint32_t galois[HM_IP_LINTRANS_MAX_ROT];
 };
+struct HmIpIdStep {   // what the identity step (hm_inner_product_lintrans_id) adds to the arguments of a weighted sum: the unrotated term
+  const uint64_t *addend1;      // the second addend source (c1), read unrotated as `addend` (c0) is
+  uint64_t *addend1_out;
+  const HmIpIdRec *ids;         // [n_out][n_limbs] (one sum: [n_limbs]), behind the records in their table
+  const uint16_t *add1_src;     // [n_limbs]
+};
+struct HmIpLinIdOneArgs : HmIpLinArgs, HmIpIdStep {};     // ONE sum (n_out = 1): the single-sum kernel form
+struct HmIpLinIdArgs : HmIpLinMultiArgs, HmIpIdStep {};   // several sums
+struct HmIpSumInit {   // the sum over ciphertexts with initial sums (hm_inner_product_rotsum_init): one per entry, behind the HmIpSumRec records
+  uint16_t init[2], add_init, pad;   // limbs of the initial S_0, S_1 (in `init`) and of the initial addend sum (in `addend`; read with has_add)
+};
 struct HmIpSumArgs {
   const uint64_t *x, *y, *addend;
   uint64_t *out, *addend_out;
@@ -80,6 +97,10 @@ struct HmIpSumArgs {
   const HmIpSumRec *rec;   // [n_ct][n_limbs]
   uint32_t logN, n_limbs, n_ct;
   uint32_t galois[HM_IP_ROTSUM_MAX_CT];
+};
+struct HmIpSumInitArgs : HmIpSumArgs {
+  const uint64_t *init;
+  const HmIpSumInit *inits;     // [n_limbs]
 };
 
 // The records of n entries x n_rot rotations, rec[r * n + i], from the entry points' limb lists: digits x [n][T], keys y [n_rot][n][K][T],
@@ -123,6 +144,23 @@ inline void hm_ip_fill_multi(unsigned char *table, const uint32_t *pt, const uin
   }
   for (size_t e = 0; e < (size_t)n_out * n_rot * n; ++e) p[e] = (uint16_t)pt[e];
 }
+// ... and what the identity step adds behind that table (the same allocation): HmIpIdRec [n_out][n] from id_pt [n_out][n] and addend1_out [n_out][n],
+// then the second addend's source limbs addend1 [n] as 16-bit words.  Entries without an addend (addend[i] == HM_NO_LIMB) get zeros, never read
+inline size_t hm_ip_id_table_bytes(uint32_t n, uint32_t n_rot, uint32_t n_out) {
+  return hm_ip_multi_table_bytes(n, n_rot, n_out) + (size_t)n_out * n * sizeof(HmIpIdRec) + (size_t)n * sizeof(uint16_t);
+}
+// (one sum: the same records behind the HmIpLinRec [n_rot][n] of hm_inner_product_lintrans: `at` = the table's size without them)
+inline size_t hm_ip_id_bytes(uint32_t n, uint32_t n_out) { return (size_t)n_out * n * sizeof(HmIpIdRec) + (size_t)n * sizeof(uint16_t); }
+inline void hm_ip_fill_id(unsigned char *table, const uint32_t *id_pt, const uint32_t *addend, const uint32_t *addend1, const uint32_t *addend1_out, uint32_t n,
+                          uint32_t n_rot, uint32_t n_out, size_t at = 0) {
+  HmIpIdRec *d = reinterpret_cast<HmIpIdRec *>(table + (at ? at : hm_ip_multi_table_bytes(n, n_rot, n_out)));
+  uint16_t *s = reinterpret_cast<uint16_t *>(d + (size_t)n_out * n);
+  for (size_t e = 0; e < (size_t)n_out * n; ++e) {
+    const bool add = addend[e % n] != HM_NO_LIMB;
+    d[e] = HmIpIdRec{(uint16_t)(add ? id_pt[e] : 0), (uint16_t)(add ? addend1_out[e] : 0)};
+  }
+  for (uint32_t i = 0; i < n; ++i) s[i] = (uint16_t)(addend[i] != HM_NO_LIMB ? addend1[i] : 0);
+}
 // ... and what the sum over ciphertexts changes: every ciphertext has its own digits x [n_ct][n][T] and addend source [n_ct][n] (or nullptr)
 inline void hm_ip_fill_sum(HmIpSumRec *rec, const uint32_t *x, const uint32_t *addend, const uint32_t *addend_out, uint32_t n, uint32_t T, uint32_t n_ct) {
   for (size_t e = 0; e < (size_t)n_ct * n; ++e) {
@@ -130,6 +168,13 @@ inline void hm_ip_fill_sum(HmIpSumRec *rec, const uint32_t *x, const uint32_t *a
     for (uint32_t j = 0; j < T; ++j) rec[e].x[j] = (uint16_t)x[e * T + j];
     if (addend && addend[e] != HM_NO_LIMB) { rec[e].has_add = 1; rec[e].add_src = (uint16_t)addend[e]; rec[e].add_out = (uint16_t)addend_out[i]; }
   }
+}
+
+static_assert(sizeof(HmIpSumInit) == 8, "the device tables' record sizes");
+// ... and the initial sums behind the sum over ciphertexts' records: init [n][2], addend_init [n] (HM_NO_LIMB: none)
+inline void hm_ip_fill_sum_init(HmIpSumInit *t, const uint32_t *init, const uint32_t *addend_init, uint32_t n) {
+  for (uint32_t i = 0; i < n; ++i)
+    t[i] = HmIpSumInit{{(uint16_t)init[i * 2], (uint16_t)init[i * 2 + 1]}, (uint16_t)(addend_init && addend_init[i] != HM_NO_LIMB ? addend_init[i] : 0), 0};
 }
 
 // ---- per-thread pieces
@@ -214,14 +259,24 @@ HM_HD void hm_ip_hoisted_thread(const HmIpHoistArgs &a, uint32_t entry, uint32_t
 // loads every digit's pair at the automorphism's source of p, both keys and the plaintext at p, and adds pt * (the hoisted form's output) to a
 // 128-bit accumulator per key and word.  Entries with an addend source (the Q limbs: c0) gather it at the same source and accumulate pt * c0
 // as a third output.
-template <int TERMS>
-HM_HD void hm_ip_lintrans_thread(const HmIpLinArgs &a, uint32_t entry, uint32_t chunk, uint32_t tid) {
+// ID (Args = HmIpLinIdOneArgs): the identity step, as in hm_ip_lintrans_multi_thread below.  ID = false is the code as it was.
+template <int TERMS, bool ID = false, class Args = HmIpLinArgs>
+HM_HD void hm_ip_lintrans_thread(const Args &a, uint32_t entry, uint32_t chunk, uint32_t tid) {
   const uint32_t N = 1u << a.logN;
   const HmIpLinRec &l0 = a.rec[entry];
   const HmMod m = a.mods[l0.mod];
   const bool add = l0.has_add != 0;   // workgroup-uniform
   const uint32_t p = chunk * HM_IP_CHUNK + 2 * tid;
   hm_u128 S[2][2] = {{0, 0}, {0, 0}}, U[2] = {0, 0};
+  if constexpr (ID) {
+    if (add) {   // the unrotated pairs of c0, c1 and the identity plaintext at p: U starts from pt_0 * c0, W = pt_0 * c1 is stored at once
+      const HmIpIdRec &li = a.ids[entry];
+      const HmIpPair c0 = hm_ip_ld(a.addend, l0.add_src, N, p), c1 = hm_ip_ld(a.addend1, a.add1_src[entry], N, p), vp = hm_ip_ld(a.pt, li.pt, N, p);
+      U[0] = (hm_u128)vp.x * c0.x;
+      U[1] = (hm_u128)vp.y * c0.y;
+      hm_ip_st(a.addend1_out, li.add1_out, N, p, HmIpPair{hm_barrett((hm_u128)vp.x * c1.x, m), hm_barrett((hm_u128)vp.y * c1.y, m)});
+    }
+  }
 #pragma unroll 1
   for (uint32_t r = 0; r < a.n_rot; ++r) {
     const HmIpLinRec &lb = a.rec[(size_t)r * a.n_limbs + entry];
@@ -259,8 +314,13 @@ HM_HD void hm_ip_lintrans_thread(const HmIpLinArgs &a, uint32_t entry, uint32_t 
 // ONCE for the TILE outputs [tile * TILE, min(n_out, (tile + 1) * TILE)) the thread serves; per output only the plaintext pair is loaded and
 // pt * t_k added to that output's own 128-bit accumulators (and pt * c0 to its addend accumulator).  Every output sees exactly the operations of
 // hm_ip_lintrans_thread in its order: bit-identical to n_out runs of it.  The accumulators are indexed by unrolled loops only (registers).
-template <int TERMS, int TILE>
-HM_HD void hm_ip_lintrans_multi_thread(const HmIpLinMultiArgs &a, uint32_t entry, uint32_t chunk, uint32_t tid, uint32_t tile) {
+//
+// ID (hm_inner_product_lintrans_id, Args = HmIpLinIdArgs): the identity step.  On entries with an addend the thread also loads the UNROTATED pairs
+// of both addend sources (c0, c1) at p, once per tile: no automorphism, no swap.  Per output it loads that output's identity plaintext pair,
+// starts the addend accumulator from pt_0 * c0 instead of zero and stores W = hm_barrett(pt_0 * c1), a single product, as the second addend
+// output; the pairs are dead before the rotations start.  n_rot <= 15 keeps the accumulator at 16 products.  ID = false is the code above, untouched.
+template <int TERMS, int TILE, bool ID = false, class Args = HmIpLinMultiArgs>
+HM_HD void hm_ip_lintrans_multi_thread(const Args &a, uint32_t entry, uint32_t chunk, uint32_t tid, uint32_t tile) {
   const uint32_t N = 1u << a.logN;
   const HmIpLinRec &l0 = a.rec[entry];
   const HmMod m = a.mods[l0.mod];
@@ -270,6 +330,21 @@ HM_HD void hm_ip_lintrans_multi_thread(const HmIpLinMultiArgs &a, uint32_t entry
   hm_u128 S[TILE][2][2], U[TILE][2];
 #pragma unroll
   for (int o = 0; o < TILE; ++o) { S[o][0][0] = S[o][0][1] = S[o][1][0] = S[o][1][1] = 0; U[o][0] = U[o][1] = 0; }
+  if constexpr (ID) {
+    if (add) {
+      const HmIpPair c0 = hm_ip_ld(a.addend, l0.add_src, N, p), c1 = hm_ip_ld(a.addend1, a.add1_src[entry], N, p);
+#pragma unroll
+      for (int o = 0; o < TILE; ++o) {
+        if ((uint32_t)o < cnt) {
+          const HmIpIdRec &li = a.ids[(size_t)(m0 + o) * a.n_limbs + entry];
+          const HmIpPair vp = hm_ip_ld(a.pt, li.pt, N, p);
+          U[o][0] = (hm_u128)vp.x * c0.x;
+          U[o][1] = (hm_u128)vp.y * c0.y;
+          hm_ip_st(a.addend1_out, li.add1_out, N, p, HmIpPair{hm_barrett((hm_u128)vp.x * c1.x, m), hm_barrett((hm_u128)vp.y * c1.y, m)});
+        }
+      }
+    }
+  }
 #pragma unroll 1
   for (uint32_t r = 0; r < a.n_rot; ++r) {
     const HmIpLinRec &lb = a.rec[(size_t)r * a.n_limbs + entry];
@@ -363,8 +438,10 @@ HM_HD void hm_ip_rotsum_acc(hm_u128 (&S)[2][2], uint64_t (&U)[2], const HmIpSumO
 #else
 #define HM_IP_ROTSUM_ISSUED() ((void)0)
 #endif
-template <int TERMS>
-HM_HD void hm_ip_rotsum_thread(const HmIpSumArgs &a, uint32_t entry, uint32_t chunk, uint32_t tid) {
+// INIT (hm_inner_product_rotsum_init, Args = HmIpSumInitArgs): the accumulators start from the loaded pairs init[k] (and the addend accumulator
+// from the entry's initial addend sum) at p instead of zero; n_ct <= 15 keeps the addend accumulator at 16 residues.  INIT = false is the code as it was.
+template <int TERMS, bool INIT = false, class Args = HmIpSumArgs>
+HM_HD void hm_ip_rotsum_thread(const Args &a, uint32_t entry, uint32_t chunk, uint32_t tid) {
   const uint32_t N = 1u << a.logN;
   const HmIpSumRec &l0 = a.rec[entry];
   const HmMod m = a.mods[l0.mod];
@@ -372,6 +449,20 @@ HM_HD void hm_ip_rotsum_thread(const HmIpSumArgs &a, uint32_t entry, uint32_t ch
   const uint32_t p = chunk * HM_IP_CHUNK + 2 * tid, G = a.n_ct;
   hm_u128 S[2][2] = {{0, 0}, {0, 0}};
   uint64_t U[2] = {0, 0};
+  if constexpr (INIT) {
+    const HmIpSumInit &li = a.inits[entry];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const HmIpPair s = hm_ip_ld(a.init, li.init[k], N, p);
+      S[k][0] = s.x;
+      S[k][1] = s.y;
+    }
+    if (add) {
+      const HmIpPair u = hm_ip_ld(a.addend, li.add_init, N, p);
+      U[0] = u.x;
+      U[1] = u.y;
+    }
+  }
   HmIpSumOps<TERMS> v0;
 #if HM_IP_ROTSUM_AHEAD
   HmIpSumOps<TERMS> v1;

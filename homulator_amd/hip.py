@@ -24,7 +24,7 @@ SYMBOLS = [
     "hm_set_option", "hm_get_counter", "hm_ntt_inner_product", "hm_exchange_stream", "hm_exchange_mark", "hm_exchange_wait",
     "hm_bconv_col", "hm_limbs_to_colslices", "hm_colslices_to_limbs", "hm_ntt_second_pass", "hm_ntt_ex", "hm_capability", "hm_inner_product_ex",
     "hm_inner_product_hoisted", "hm_inner_product_lintrans", "hm_inner_product_rotsum", "hm_inner_product_lintrans_multi",
-    "hm_tensor_dot",
+    "hm_tensor_dot", "hm_inner_product_lintrans_id", "hm_inner_product_rotsum_init",
 ]
 
 
@@ -59,11 +59,20 @@ class hm_ip_lintrans_multi_desc(C.Structure):
                 ("n", C.c_uint32), ("n_terms", C.c_uint32), ("n_rot", C.c_uint32), ("n_out", C.c_uint32), ("galois", C.c_void_p)]
 
 
+class hm_ip_lintrans_id_desc(C.Structure):
+    _fields_ = [("sums", hm_ip_lintrans_multi_desc), ("id_pt_limbs", C.c_void_p), ("addend1", C.c_void_p), ("addend1_limbs", C.c_void_p),
+                ("addend1_out", C.c_void_p), ("addend1_out_limbs", C.c_void_p)]
+
+
 class hm_ip_rotsum_desc(C.Structure):
     _fields_ = [("x", C.c_void_p), ("x_limbs", C.c_void_p), ("y", C.c_void_p), ("y_limbs", C.c_void_p),
                 ("addend", C.c_void_p), ("addend_limbs", C.c_void_p), ("out", C.c_void_p), ("out_limbs", C.c_void_p),
                 ("addend_out", C.c_void_p), ("addend_out_limbs", C.c_void_p), ("mod_ids", C.c_void_p),
                 ("n", C.c_uint32), ("n_terms", C.c_uint32), ("n_ct", C.c_uint32), ("galois", C.c_void_p)]
+
+
+class hm_ip_rotsum_init_desc(C.Structure):
+    _fields_ = [("sum", hm_ip_rotsum_desc), ("init", C.c_void_p), ("init_limbs", C.c_void_p), ("addend_init_limbs", C.c_void_p)]
 
 
 class hm_ntt_ip_desc(C.Structure):
@@ -128,6 +137,8 @@ def load():
     L.hm_inner_product_lintrans.argtypes = [vp, C.POINTER(hm_ip_lintrans_desc)]
     L.hm_inner_product_rotsum.argtypes = [vp, C.POINTER(hm_ip_rotsum_desc)]
     L.hm_inner_product_lintrans_multi.argtypes = [vp, C.POINTER(hm_ip_lintrans_multi_desc)]
+    L.hm_inner_product_rotsum_init.argtypes = [vp, C.POINTER(hm_ip_rotsum_init_desc)]
+    L.hm_inner_product_lintrans_id.argtypes = [vp, C.POINTER(hm_ip_lintrans_id_desc)]
     L.hm_ntt_sub_scale.argtypes = [vp] + [vp] * 9 + [u32, vp]
     L.hm_ntt_mix_sub_scale.argtypes = [vp, C.POINTER(hm_ntt_fused_desc)]
     L.hm_tensor.argtypes = [vp] + [vp] * 15 + [u32]
@@ -366,6 +377,20 @@ class Context:
                                       ptr(addend_out), keep[5][1], keep[6][1], len(mod_ids), n_terms, len(galois), n_out, keep[7][1])
         self._ck(self.L.hm_inner_product_lintrans_multi(self.h, C.byref(d)))
 
+    def inner_product_lintrans_id(self, x, x_limbs, y, y_limbs, pt, pt_limbs, out, out_limbs, mod_ids, n_terms, galois, n_out,
+                                  addend, addend_limbs, addend_out, addend_out_limbs, id_pt_limbs, addend1, addend1_limbs, addend1_out, addend1_out_limbs):
+        """inner_product_lintrans_multi with the identity step (hm_inner_product_lintrans_id): on the entries with an addend source,
+        addend_out[m][i] += pt[id_pt_limbs[m][i]] * addend[i] and addend1_out[m][i] = pt[id_pt_limbs[m][i]] * addend1[i], both sources read
+        unrotated.  Further limb lists: id_pt_limbs [m][n] (limbs of pt), addend1_limbs [n] (NO_LIMB exactly where addend_limbs is),
+        addend1_out_limbs [m][n].  Any of the identity arguments may be None: the call is then refused by the library"""
+        keep = [_u32(v) for v in (x_limbs, y_limbs, pt_limbs, addend_limbs, out_limbs, addend_out_limbs, mod_ids, galois, id_pt_limbs, addend1_limbs,
+                                  addend1_out_limbs)]
+        ptr = lambda v: None if v is None else v.ptr
+        sums = hm_ip_lintrans_multi_desc(x.ptr, keep[0][1], y.ptr, keep[1][1], pt.ptr, keep[2][1], ptr(addend), keep[3][1], out.ptr, keep[4][1],
+                                         ptr(addend_out), keep[5][1], keep[6][1], len(mod_ids), n_terms, len(galois), n_out, keep[7][1])
+        d = hm_ip_lintrans_id_desc(sums, keep[8][1], ptr(addend1), keep[9][1], ptr(addend1_out), keep[10][1])
+        self._ck(self.L.hm_inner_product_lintrans_id(self.h, C.byref(d)))
+
     def inner_product_rotsum(self, x, x_limbs, y, y_limbs, out, out_limbs, mod_ids, n_terms, galois,
                              addend=None, addend_limbs=None, addend_out=None, addend_out_limbs=None):
         """out[i][k] = sum_c sum_j automorph_{galois[c]}(x[c][i][j]) * y[c][i][k][j], k < 2, and for the entries with addend sources
@@ -376,6 +401,17 @@ class Context:
         d = hm_ip_rotsum_desc(x.ptr, keep[0][1], y.ptr, keep[1][1], ptr(addend), keep[2][1], out.ptr, keep[3][1],
                               ptr(addend_out), keep[4][1], keep[5][1], len(mod_ids), n_terms, len(galois), keep[6][1])
         self._ck(self.L.hm_inner_product_rotsum(self.h, C.byref(d)))
+
+    def inner_product_rotsum_init(self, x, x_limbs, y, y_limbs, out, out_limbs, mod_ids, n_terms, galois, init, init_limbs,
+                                  addend=None, addend_limbs=None, addend_out=None, addend_out_limbs=None, addend_init_limbs=None):
+        """inner_product_rotsum whose sums start from init[i][k] (limb list [n][2]) and, on the entries with addend sources, from
+        addend[addend_init_limbs[i]] instead of zero (hm_inner_product_rotsum_init)"""
+        keep = [_u32(v) for v in (x_limbs, y_limbs, addend_limbs, out_limbs, addend_out_limbs, mod_ids, galois, init_limbs, addend_init_limbs)]
+        ptr = lambda v: None if v is None else v.ptr
+        s = hm_ip_rotsum_desc(x.ptr, keep[0][1], y.ptr, keep[1][1], ptr(addend), keep[2][1], out.ptr, keep[3][1],
+                              ptr(addend_out), keep[4][1], keep[5][1], len(mod_ids), n_terms, len(galois), keep[6][1])
+        d = hm_ip_rotsum_init_desc(s, ptr(init), keep[7][1], keep[8][1])
+        self._ck(self.L.hm_inner_product_rotsum_init(self.h, C.byref(d)))
 
     def ntt_second_pass(self, buf, mod_ids, inverse=False, limbs=None, scale=None):
         """the last pass of transforms whose first pass another call has already run into `buf` (in place)"""

@@ -80,12 +80,20 @@ public:
   // (OutputOperand, extraOutputs...)[m * w + k] = S_{m,k}, k < 2, and [m * w + 2] = U_m.  ipLinPt empty: no weighted sum
   std::vector<std::vector<AddrType>> ipLinPt;
   AddrType ipLinAddend = 0;
+  // ... with the identity step (hm_inner_product_lintrans_id; the Q limbs, with ipLinAddend): U_m also takes ipLinIdPt[m] * ipLinAddend, unrotated,
+  // and W_m = ipLinIdPt[m] * ipLinAddend1 (the unrotated c1) is one more output: w = 4 and [m * w + 3] = W_m.  ipLinIdPt empty: no identity step
+  std::vector<AddrType> ipLinIdPt;
+  AddrType ipLinAddend1 = 0;
   // (6s) sum of the key products of rotations of DIFFERENT ciphertexts (hm_inner_product_rotsum): ciphertext c reads its own unrotated digits
   // ipSumX[c] (ipSumX[0] == ipX) through X -> X^ipHoistG[c] with keys ipY[2c + k], and the sum over c is formed before it is stored:
   // OutputOperand = S_0, extraOutputs[0] = S_1.  ipSumAddend non-empty (the Q limbs): extraOutputs[1] = sum_c sigma_c(ipSumAddend[c]).
   // ipSumX empty: no such sum
   std::vector<std::vector<AddrType>> ipSumX;
   std::vector<AddrType> ipSumAddend;
+  // ... with initial sums (hm_inner_product_rotsum_init): S_k starts from ipSumInit[k] and, with ipSumAddend, the addend sum from
+  // ipSumAddendInit, each read where the outputs are written.  ipSumInit empty: the sums start from zero
+  std::vector<AddrType> ipSumInit;
+  AddrType ipSumAddendInit = 0;
   std::vector<Instruction *> depsInsList;
 
   Instruction(std::string name, ins_ops op, uint32_t level) : ops(op), Name(std::move(name)), level_id(level) {}

@@ -132,8 +132,12 @@ protected:
   OperationBase(const std::string &op, const std::string &labelName, Config *cfg, Arch *_arch, uint32_t maxLevel, uint32_t curLevel, uint32_t alpha);
   // every op's preamble: `ciphertexts` input ciphertexts ct1, ct2 (synthetic streams seed, seed + 2000) and, if asked, the plaintext pt
   // (seed + 4000) at the current level, then `extPlaintexts` plaintexts pt<r>, r = 1.., on the extended basis (the current level's Q limbs, then
-  // the alpha special primes; seed + 4000 + 100000 r), then the address plan of the temporaries behind them
-  void makeInputs(uint32_t ciphertexts, bool plaintext = false, uint32_t extPlaintexts = 0);
+  // the alpha special primes; seed + 4000 + 100000 r), then the named extra plaintexts `namedExt` on the extended basis too ((name, stream): seed +
+  // stream; the identity step's pt0), then the address plan of the temporaries behind them
+  typedef std::vector<std::pair<std::string, uint64_t>> NamedStreams;
+  void makeInputs(uint32_t ciphertexts, bool plaintext = false, uint32_t extPlaintexts = 0, const NamedStreams &namedExt = {});
+  // config key `identity` (0 or 1, default 0; read by the ops that have an identity step): the unrotated diagonal, DESIGN.md section 16
+  bool identityStep(const std::string &op) const;
   // what the ops that hoist the ModUp over rotations (HROTATE_HOISTED, HLINTRANS, HBSGS) or sum rotations in front of one ModDown (HROTSUM) check
   // first (`op` names the op in the messages): no backend = sim,
   // no world > 1; config keys `rotations` = R (default 4, 1..16) and `galois` = g (default 5, odd, below 2N).  Returns g^r mod 2N, r = 1..R, distinct
@@ -151,14 +155,19 @@ protected:
   void finishConstruction();  // registers every temporary with the backend
   // the chains of element-wise stages that the ops summing on the extended basis are built of (HLINTRANS, HROTSUM, HBSGS).  A sum is three buffers,
   // t = 0, 1: S_0, S_1 (tags Key0, Key1; the E = level + alpha limbs) and t = 2: U (tag C0; the `level` Q limbs); sumMods(t): their modulus ids.
-  struct SwitchedSum { Limbs c0; std::vector<AddrType> c1; };   // (U + ModDown(S_0), ModDown(S_1))
+  // With the identity step a fourth, t = 3: W (tag C1; the Q limbs), the unrotated c1 times the identity plaintext.
+  struct SwitchedSum { Limbs c0; std::vector<AddrType> c1; };   // (U + ModDown(S_0), ModDown(S_1)); with the identity step W + ModDown(S_1)
   std::vector<uint32_t> sumMods(uint32_t t) const;
   // the weighted sum sum_r terms[r] * pts[r]: stages LinTrans_(<r>)_<tag><suffix>, buffers LinTransOut_temp(<r>)_<tag><suffix>, the last LinTransOut_<tag><suffix>
-  Limbs weightedSum(uint32_t t, const std::vector<Limbs> &terms, const std::vector<std::vector<AddrType>> &pts, const std::string &suffix);
+  // `head` / `headPt`: an unrotated head term in front of them (the identity step), rotation 0 in the names: the chain's MUL is then its
+  Limbs weightedSum(uint32_t t, const std::vector<Limbs> &terms, const std::vector<std::vector<AddrType>> &pts, const std::string &suffix,
+                    const Limbs *head = nullptr, const std::vector<AddrType> *headPt = nullptr);
   // the running sum: sum + term, the i-th term (i >= 2): stage and buffer <stem>_(<i>)_<tag>, the last buffer <stem>Out_<tag>
   Limbs addTerm(uint32_t t, const Limbs &sum, const Limbs &term, const std::string &stem, uint32_t i, bool last);
   // the tail: ModDown<suffix> of sums[0], sums[1], then c0 = its output 0 + sums[2] in stage <op>_Hadd<suffix>, buffer `buffer`
-  SwitchedSum sumDown(KeySwitch &ks, const std::array<Limbs, 3> &sums, const std::string &op, const std::string &buffer, const std::string &suffix);
+  // `c1Addend` (the identity step's W): c1 = the ModDown's output 1 + it in stage <op>_Hadd1<suffix>, buffer <op>Output<suffix>(1)
+  SwitchedSum sumDown(KeySwitch &ks, const std::array<Limbs, 3> &sums, const std::string &op, const std::string &buffer, const std::string &suffix,
+                      const Limbs *c1Addend = nullptr);
   void setOutput(const std::string &out, const SwitchedSum &ct);
 
 public:

@@ -28,7 +28,11 @@ enum class Role {
   Key,            // key product: evaluation-key limb
   LinPlain,       // weighted sums of hoisted key products (6l, 6m): a rotation's plaintext limb, of one sum
   LinAddend,      // ... the addend source, read through every rotation's automorphism (the unrotated c0)
+  LinIdPlain,     // ... the identity step: the plaintext limb of the unrotated term, of one sum
+  LinAddend1,     // ... and the second addend source it multiplies, read where it is stored (the unrotated c1; c0 is LinAddend)
   SumAddend,      // sum of rotations of different ciphertexts (6s): a ciphertext's addend source, read through its automorphism (its unrotated c0)
+  SumInit,        // ... with initial sums: the polynomial S_k starts from
+  SumAddendInit,  // ... and the one the addend sum starts from
   Minuend, Addend, Mix,   // fused forward transform (4, 4b)
   EpiSub, EpiAdd,         // conversion with the element-wise epilogue (10): fSubFrom, fAdd
   ReplacedIn      // the transform input operandList[0] that the fused conversion fConvIn replaces (9): never written, never loaded
@@ -65,7 +69,11 @@ inline std::vector<Read> recordReads(const Instruction &i) {
     for (auto &row : i.ipLinPt)
       for (AddrType a : row) v.push_back({a, Role::LinPlain, kNoDigit});
     if (i.ipLinAddend) v.push_back({i.ipLinAddend, Role::LinAddend, kNoDigit});
+    for (AddrType a : i.ipLinIdPt) v.push_back({a, Role::LinIdPlain, kNoDigit});
+    if (i.ipLinAddend1) v.push_back({i.ipLinAddend1, Role::LinAddend1, kNoDigit});
     for (AddrType a : i.ipSumAddend) v.push_back({a, Role::SumAddend, kNoDigit});
+    for (AddrType a : i.ipSumInit) v.push_back({a, Role::SumInit, kNoDigit});
+    if (i.ipSumAddendInit) v.push_back({i.ipSumAddendInit, Role::SumAddendInit, kNoDigit});
     return v;
   }
   if (i.ops == BCONV_STEP2) {

@@ -45,7 +45,11 @@ struct Arch::Launch {
                                   // L_IP_ROTSUM: hoistG = the element of every ciphertext; a: digits [c][n][T], b: keys [c][n][2][T], d: addend sources
                                   // [c][n] / out1: addend output [n] (HM_NO_LIMB: none; both empty: no entry has one), out: [n][2]
                                   // L_IP_LINTRANS_MULTI: as L_IP_LINTRANS with multiOuts sums (L_IP_LINTRANS: 1): c: plaintexts [m][r][n], out: [m][n][2], out1: [m][n]
+                                  // L_IP_ROTSUM with initial sums (hm_ip_rotsum_init_desc): c: init [n][2], d1: the initial addend sums [n]
+                                  // ... with the identity step (hm_ip_lintrans_id_desc, either kind): idPt: identity plaintexts [m][n], d1: the second addend
+                                  // source [n], out2: its outputs [m][n] (HM_NO_LIMB where d is); all empty: no identity step
   uint32_t multiOuts = 0;
+  std::vector<uint32_t> idPt, d1;
   uint32_t dotTerms = 0;          // L_TENSOR_DOT: pairs per record (a, b, c, d: [n][dotTerms], roles as L_TENSOR; out, out1, out2: [n])
   std::string name;
   std::string statKey;
@@ -452,19 +456,27 @@ void Arch::LaunchBuilder::ipLintrans(Launch &L, Recs recs) {
   L.kind = M == 1 ? Launch::L_IP_LINTRANS : Launch::L_IP_LINTRANS_MULTI;
   L.multiOuts = (uint32_t)M;
   const size_t R = hoistedOperands(L, recs, what.c_str());
-  size_t addends = 0;
+  size_t addends = 0, identities = 0;
   for (Instruction *i : recs) {
     if (i->ipLinPt.size() != M) throw std::runtime_error(what + ": the records of one launch form different numbers of sums");
     addends += i->ipLinAddend != 0;
+    identities += !i->ipLinIdPt.empty();
   }
+  if (identities && identities != addends) throw std::runtime_error(what + ": the identity step on some of the records with an addend only");
   auto outOf = [](const Instruction *i, size_t x) { return x == 0 ? i->OutputOperand : i->extraOutputs[x - 1]; };
   if (addends)
     for (Instruction *i : recs) L.d.push_back(i->ipLinAddend ? limb(i->ipLinAddend) : HM_NO_LIMB);
+  if (identities)
+    for (Instruction *i : recs) L.d1.push_back(i->ipLinAddend1 ? limb(i->ipLinAddend1) : HM_NO_LIMB);
   for (size_t m = 0; m < M; ++m) {
     for (Instruction *i : recs) {
-      const size_t w = i->ipLinAddend ? 3 : 2;
+      const size_t w = !i->ipLinIdPt.empty() ? 4 : i->ipLinAddend ? 3 : 2;
       L.out.push_back(limb(outOf(i, m * w))); L.out.push_back(limb(outOf(i, m * w + 1)));
       if (addends) L.out1.push_back(i->ipLinAddend ? limb(outOf(i, m * w + 2)) : HM_NO_LIMB);
+      if (identities) {
+        L.idPt.push_back(w == 4 ? limb(i->ipLinIdPt[m]) : HM_NO_LIMB);
+        L.out2.push_back(w == 4 ? limb(outOf(i, m * w + 3)) : HM_NO_LIMB);
+      }
     }
     for (size_t r = 0; r < R; ++r)
       for (Instruction *i : recs) L.c.push_back(limb(i->ipLinPt[m][r]));
@@ -472,7 +484,9 @@ void Arch::LaunchBuilder::ipLintrans(Launch &L, Recs recs) {
   // limb-polys touched: a workgroup serves a tile of sums (one sum: one tile), so the digits, the keys and the addend source are read once per tile
   // (every rotation gathers from the same ones); every sum's plaintexts once; two outputs per entry and sum and one per addend and sum
   const unsigned long long tiles = (M + HM_IP_LINTRANS_MULTI_TILE - 1) / HM_IP_LINTRANS_MULTI_TILE;
-  L.bytes = ((unsigned long long)recs.size() * (tiles * (L.ipTerms + 2 * R * L.ipTerms) + M * R + 2 * M) + (unsigned long long)addends * (tiles + M)) * LP;
+  // the identity step: on the entries that have it, the second source once per tile, every sum's identity plaintext and its second addend output
+  L.bytes = ((unsigned long long)recs.size() * (tiles * (L.ipTerms + 2 * R * L.ipTerms) + M * R + 2 * M) + (unsigned long long)addends * (tiles + M) +
+             (unsigned long long)identities * (tiles + 2 * M)) * LP;
 }
 
 // (6s) one sum of rotations of different ciphertexts: digits a [c][n][T], keys b [c][n][2][T], outputs out [n][2]; entries with addends: sources
@@ -488,8 +502,18 @@ void Arch::LaunchBuilder::ipRotsum(Launch &L, Recs recs) {
   }
   for (size_t c = 0; c < G && addends; ++c)
     for (Instruction *i : recs) L.d.push_back(i->ipSumAddend.empty() ? HM_NO_LIMB : limb(i->ipSumAddend[c]));
-  // limb-polys touched: every ciphertext's digits, keys and addend source once, two outputs per entry and one per entry with addends
-  L.bytes = ((unsigned long long)recs.size() * (G * 3 * L.ipTerms + 2) + (unsigned long long)addends * (G + 1)) * LP;
+  // with initial sums (all records or none): c = init [n][2], d1 = the initial addend sums [n] (hm_ip_rotsum_init_desc)
+  size_t inits = 0, addInits = 0;
+  for (Instruction *i : recs) { inits += !i->ipSumInit.empty(); addInits += i->ipSumAddendInit != 0; }
+  if (inits && (inits != recs.size() || addInits != addends)) throw std::runtime_error("sum of rotations: initial sums on some of the records of one launch only");
+  for (Instruction *i : recs) {
+    if (!inits) break;
+    L.c.push_back(limb(i->ipSumInit[0])); L.c.push_back(limb(i->ipSumInit[1]));
+    if (addends) L.d1.push_back(i->ipSumAddendInit ? limb(i->ipSumAddendInit) : HM_NO_LIMB);
+  }
+  // limb-polys touched: every ciphertext's digits, keys and addend source once, two outputs per entry and one per entry with addends; the
+  // initial sums once
+  L.bytes = ((unsigned long long)recs.size() * (G * 3 * L.ipTerms + 2) + (unsigned long long)addends * (G + 1) + 2 * inits + addInits) * LP;
 }
 
 // transform x key on one GPU (7, 8, 7b): a = source, c = first-pass scratch of every (limb, digit); the digits' conversions as `probs`
@@ -979,10 +1003,13 @@ void Arch::replicateForBatch() {
       else if (l->kind == Launch::L_IP_ROTSUM) {   // every ciphertext its own digits and addend source
         inter(l->out, 1, 2, true);
         if (!l->d.empty()) { inter(l->d, R, 1, true); inter(l->out1, 1, 1, true); }
+        if (!l->c.empty()) inter(l->c, 1, 2, true);   // every op its own initial sums
+        if (!l->d1.empty()) inter(l->d1, 1, 1, true);
       } else {   // the weighted sums (one: L_IP_LINTRANS): every sum its own plaintexts and outputs
         const size_t M = l->multiOuts;
         inter(l->out, M, 2, true); inter(l->c, M * R, 1, true);
         if (!l->d.empty()) { inter(l->d, 1, 1, true); inter(l->out1, M, 1, true); }
+        if (!l->d1.empty()) { inter(l->d1, 1, 1, true); inter(l->idPt, M, 1, true); inter(l->out2, M, 1, true); }   // every op its own identity plaintexts and outputs
       }
       l->refInstructions *= batch_;
       l->bytes *= batch_;
@@ -1171,8 +1198,9 @@ std::string Arch::planText() const {
       out += " addend=" + std::to_string(l->d.size() - (size_t)std::count(l->d.begin(), l->d.end(), HM_NO_LIMB));
     if (l->kind == Launch::L_IP_LINTRANS_MULTI)   // (6m): groups, entries that also form the groups' addend outputs
       out += " out=" + std::to_string(l->multiOuts) + " addend=" + std::to_string(l->d.size() - (size_t)std::count(l->d.begin(), l->d.end(), HM_NO_LIMB));
+    if ((l->kind == Launch::L_IP_LINTRANS || l->kind == Launch::L_IP_LINTRANS_MULTI) && !l->d1.empty()) out += " id=1";   // ... with the identity step
     if (l->kind == Launch::L_IP_ROTSUM)   // (6s): entries that also form the addend output
-      out += " addend=" + std::to_string(l->out1.size() - (size_t)std::count(l->out1.begin(), l->out1.end(), HM_NO_LIMB));
+      out += " addend=" + std::to_string(l->out1.size() - (size_t)std::count(l->out1.begin(), l->out1.end(), HM_NO_LIMB)) + (l->c.empty() ? "" : " init=1");
     if (l->recordSlot >= 0) out += " mark=" + std::to_string(l->recordSlot);
     if (!l->waitSlots.empty()) { out += " wait="; for (int w : l->waitSlots) out += std::to_string(w) + ","; }
     if (!l->exLimbs.empty()) {
@@ -1207,6 +1235,7 @@ std::string Arch::planDump() const {
     if (l->kind == Launch::L_IP_LINTRANS_MULTI) out += " multiOuts=" + std::to_string(l->multiOuts);   // (one sum: the line of L_IP_LINTRANS has no such field)
     vec("wait", l->waitSlots); vec("hoistG", l->hoistG); vec("ipCoeff", l->ipCoeff); vec("ipInv", l->ipInv); vec("outPacked", l->outPacked);
     vec("inGalois", l->inGalois); vec("addGalois", l->addGalois);
+    vec("idPt", l->idPt); vec("d1", l->d1);
     vec("a", l->a); vec("b", l->b); vec("c", l->c); vec("d", l->d); vec("out", l->out); vec("out1", l->out1); vec("out2", l->out2);
     vec("mods", l->mods); vec("inMods", l->inMods); vec("k", l->k); vec("mixK", l->mixK); vec("addK", l->addK);
     vec("exLimbs", l->exLimbs); vec("exOwners", l->exOwners);
@@ -1264,6 +1293,13 @@ void Arch::enqueue(Launch &l) {
   }
   case Launch::L_IP_LINTRANS: {
     const bool add = !l.d.empty();
+    if (!l.d1.empty()) {   // the identity step: the several-sums form with one sum (the same limb lists)
+      const hm_ip_lintrans_id_desc d = {{pool, l.a.data(), pool, l.b.data(), pool, l.c.data(), pool, l.d.data(), pool, l.out.data(), pool, l.out1.data(),
+                                         l.mods.data(), (uint32_t)l.mods.size(), l.ipTerms, (uint32_t)l.hoistG.size(), 1, l.hoistG.data()},
+                                        l.idPt.data(), pool, l.d1.data(), pool, l.out2.data()};
+      st = hm_inner_product_lintrans_id(ctx, &d);
+      break;
+    }
     const hm_ip_lintrans_desc d = {pool, l.a.data(), pool, l.b.data(), pool, l.c.data(), add ? pool : nullptr, add ? l.d.data() : nullptr, pool, l.out.data(),
                                    add ? pool : nullptr, add ? l.out1.data() : nullptr, l.mods.data(), (uint32_t)l.mods.size(), l.ipTerms,
                                    (uint32_t)l.hoistG.size(), l.hoistG.data()};
@@ -1272,6 +1308,13 @@ void Arch::enqueue(Launch &l) {
   }
   case Launch::L_IP_LINTRANS_MULTI: {
     const bool add = !l.d.empty();
+    if (!l.d1.empty()) {
+      const hm_ip_lintrans_id_desc d = {{pool, l.a.data(), pool, l.b.data(), pool, l.c.data(), pool, l.d.data(), pool, l.out.data(), pool, l.out1.data(),
+                                         l.mods.data(), (uint32_t)l.mods.size(), l.ipTerms, (uint32_t)l.hoistG.size(), l.multiOuts, l.hoistG.data()},
+                                        l.idPt.data(), pool, l.d1.data(), pool, l.out2.data()};
+      st = hm_inner_product_lintrans_id(ctx, &d);
+      break;
+    }
     const hm_ip_lintrans_multi_desc d = {pool, l.a.data(), pool, l.b.data(), pool, l.c.data(), add ? pool : nullptr, add ? l.d.data() : nullptr, pool,
                                          l.out.data(), add ? pool : nullptr, add ? l.out1.data() : nullptr, l.mods.data(), (uint32_t)l.mods.size(),
                                          l.ipTerms, (uint32_t)l.hoistG.size(), l.multiOuts, l.hoistG.data()};
@@ -1280,6 +1323,14 @@ void Arch::enqueue(Launch &l) {
   }
   case Launch::L_IP_ROTSUM: {
     const bool add = !l.d.empty();
+    if (!l.c.empty()) {   // with initial sums
+      const hm_ip_rotsum_init_desc d = {{pool, l.a.data(), pool, l.b.data(), add ? pool : nullptr, add ? l.d.data() : nullptr, pool, l.out.data(),
+                                         add ? pool : nullptr, add ? l.out1.data() : nullptr, l.mods.data(), (uint32_t)l.mods.size(), l.ipTerms,
+                                         (uint32_t)l.hoistG.size(), l.hoistG.data()},
+                                        pool, l.c.data(), add ? l.d1.data() : nullptr};
+      st = hm_inner_product_rotsum_init(ctx, &d);
+      break;
+    }
     const hm_ip_rotsum_desc d = {pool, l.a.data(), pool, l.b.data(), add ? pool : nullptr, add ? l.d.data() : nullptr, pool, l.out.data(),
                                  add ? pool : nullptr, add ? l.out1.data() : nullptr, l.mods.data(), (uint32_t)l.mods.size(), l.ipTerms,
                                  (uint32_t)l.hoistG.size(), l.hoistG.data()};

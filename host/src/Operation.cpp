@@ -371,7 +371,7 @@ OperationBase::~OperationBase() {
   for (auto &kv : DataInsMap)
     for (Instruction *i : kv.second) delete i;
 }
-void OperationBase::makeInputs(uint32_t ciphertexts, bool plaintext, uint32_t extPlaintexts) {
+void OperationBase::makeInputs(uint32_t ciphertexts, bool plaintext, uint32_t extPlaintexts, const NamedStreams &namedExt) {
   for (uint32_t i = 0; i < ciphertexts; i++) {
     cts.emplace_back(level_, N, Datapool, batchSize);
     const std::vector<AddrType> c0 = cts[i].getC0Addr(), c1 = cts[i].getC1Addr();
@@ -397,6 +397,13 @@ void OperationBase::makeInputs(uint32_t ciphertexts, bool plaintext, uint32_t ex
     arch->registerLimbs(pt);
     arch->addInputFill(InputFill{pt, extMods, seed + 4000 + 100000ull * r});
     namedInputs["pt" + S(r)] = pt;
+  }
+  for (const auto &ns : namedExt) {   // behind the numbered ones: an op without them keeps its address plan
+    extPtx.emplace_back(level_ + alpha_, N, Datapool, batchSize);
+    const std::vector<AddrType> pt = extPtx.back().getC0Addr();
+    arch->registerLimbs(pt);
+    arch->addInputFill(InputFill{pt, extMods, seed + ns.second});
+    namedInputs[ns.first] = pt;
   }
   addrManager.reset(new AddrManage(Datapool.back() + 1, batchSize));
   addrManager->setGlobalDatapPoll(&Datapool);
@@ -432,6 +439,11 @@ std::vector<uint32_t> OperationBase::hoistedRotations(const std::string &op) con
   }
   return gs;
 }
+bool OperationBase::identityStep(const std::string &op) const {
+  const uint32_t id = config->getValueOr("identity", 0);
+  if (id > 1) throw std::runtime_error(op + ": identity = " + S(id) + ", must be 0 or 1");
+  return id == 1;
+}
 void OperationBase::finishRotation(const std::string &out, const std::vector<AddrType> &rotatedC0, const KeySwitch::Output &ks, const std::string &suffix) {
   PerLimb s{label + "_HROTATEadd" + suffix + "_Level(", ")", range(0, level_), alloc("HROTATEOutput" + suffix + "(1)", level_)};
   s.a = ks[0];
@@ -442,7 +454,7 @@ void OperationBase::finishRotation(const std::string &out, const std::vector<Add
 }
 // The sums on the extended basis (HLINTRANS, HROTSUM, HBSGS): t = 0, 1 (S_0, S_1: the key product's two components, E = level + alpha limbs) and
 // t = 2 (U: the rotated c0, the `level` Q limbs), by the tags their buffers and stage keys carry
-static const char *const kSumTags[3] = {"Key0", "Key1", "C0"};
+static const char *const kSumTags[4] = {"Key0", "Key1", "C0", "C1"};   // C1: W, the identity step's unrotated c1 term (the Q limbs, as C0)
 std::vector<uint32_t> OperationBase::sumMods(uint32_t t) const {
   std::vector<uint32_t> mods = range(0, level_);
   if (t < 2)
@@ -451,24 +463,27 @@ std::vector<uint32_t> OperationBase::sumMods(uint32_t t) const {
 }
 // sum_r terms[r] * pts[r] (t = 2: the Q limbs of pts[r]): MUL, then one MAC_ADD per further rotation, the last into LinTransOut_<tag><suffix>.  The
 // term is operand a: pass (6) pairs chains that share their a operands into key products, and the plaintexts are shared by all three sums
-Limbs OperationBase::weightedSum(uint32_t t, const std::vector<Limbs> &terms, const std::vector<std::vector<AddrType>> &pts, const std::string &suffix) {
+Limbs OperationBase::weightedSum(uint32_t t, const std::vector<Limbs> &terms, const std::vector<std::vector<AddrType>> &pts, const std::string &suffix,
+                                 const Limbs *head, const std::vector<AddrType> *headPt) {
   const std::string tag = kSumTags[t];
   const std::vector<uint32_t> mods = sumMods(t);
-  const size_t R = terms.size();
+  const size_t first = head ? 0 : 1, R = terms.size() + 1;   // rotation `first` .. R - 1; 0: the unrotated head term
   Limbs sum;
-  for (size_t r = 0; r < R; ++r) {
-    const std::string at = "(" + S(r + 1) + ")_" + tag + suffix;
-    PerLimb s{label + "_LinTrans" + suffix + "_" + tag + "_Rot(" + S(r + 1) + ")_Level(", ")", mods,
+  for (size_t r = first; r < R; ++r) {
+    const Limbs &term = r ? terms[r - 1] : *head;
+    const std::vector<AddrType> &pt = r ? pts[r - 1] : *headPt;
+    const std::string at = "(" + S(r) + ")_" + tag + suffix;
+    PerLimb s{label + "_LinTrans" + suffix + "_" + tag + "_Rot(" + S(r) + ")_Level(", ")", mods,
               alloc(r + 1 < R ? "LinTransOut_temp" + at : "LinTransOut_" + tag + suffix, (uint32_t)mods.size())};
-    s.a = terms[r].addr;
-    s.b = t < 2 ? pts[r] : slice(pts[r], 0, level_);
-    s.after = {&terms[r].from};
+    s.a = term.addr;
+    s.b = t < 2 ? pt : slice(pt, 0, level_);
+    if (!term.from.empty()) s.after = {&term.from};   // (the head term may be an op input: nothing to wait for)
     const Limbs before = sum;
-    if (r) {
+    if (r > first) {
       s.c = before.addr;
       s.after.push_back(&before.from);
     }
-    sum = {s.out, eweLimbs(&insgener, r ? EWE_MAC_ADD : EWE_MUL, s)};
+    sum = {s.out, eweLimbs(&insgener, r > first ? EWE_MAC_ADD : EWE_MUL, s)};
     driver.dispatchInstructions("LinTrans_" + at, sum.from);
   }
   return sum;
@@ -487,7 +502,7 @@ Limbs OperationBase::addTerm(uint32_t t, const Limbs &sum, const Limbs &term, co
 }
 // the ciphertext (U + ModDown(S_0), ModDown(S_1)) of the sums: stages <op>_Hadd<suffix> behind the ModDown's, c0 in `buffer`
 OperationBase::SwitchedSum OperationBase::sumDown(KeySwitch &ks, const std::array<Limbs, 3> &sums, const std::string &op, const std::string &buffer,
-                                                  const std::string &suffix) {
+                                                  const std::string &suffix, const Limbs *c1Addend) {
   const KeySwitch::Output down = ks.modDown({sums[0], sums[1]}, suffix);
   dispatch(ks.takeStages());
   PerLimb s{label + "_" + op + "add" + suffix + "_Level(", ")", range(0, level_), alloc(buffer, level_)};
@@ -495,6 +510,14 @@ OperationBase::SwitchedSum OperationBase::sumDown(KeySwitch &ks, const std::arra
   s.c = sums[2].addr;
   const Limbs c0{s.out, eweLimbs(&insgener, EWE_ADD, s)};
   driver.dispatchInstructions(op + "_Hadd" + suffix, c0.from);
+  if (c1Addend) {   // the same stage shape as c0's
+    PerLimb s1{label + "_" + op + "add1" + suffix + "_Level(", ")", range(0, level_), alloc(op + "Output" + suffix + "(1)", level_)};
+    s1.a = down[1];
+    s1.c = c1Addend->addr;
+    const Limbs c1{s1.out, eweLimbs(&insgener, EWE_ADD, s1)};
+    driver.dispatchInstructions(op + "_Hadd1" + suffix, c1.from);
+    return {c0, c1.addr};
+  }
   return {c0, down[1]};
 }
 void OperationBase::setOutput(const std::string &out, const SwitchedSum &ct) {
@@ -702,7 +725,12 @@ HLINTRANS::HLINTRANS(std::string labelName, uint32_t maxLevel, uint32_t currentL
     : OperationBase("HLINTRANS", labelName, cfg, _arch, maxLevel, currentLevel, alpha) {
   const std::vector<uint32_t> gs = hoistedRotations("hlintrans");
   const uint32_t R = (uint32_t)gs.size();
-  makeInputs(1, /*plaintext=*/false, /*extPlaintexts=*/R);
+  // identity = 1: one more plaintext pt0 (stream seed + 4300) weights the UNROTATED ciphertext, which meets no key:
+  //   U = pt0[Q] c0 + sum_r pt_r[Q] sigma_r(c0),   W = pt0[Q] c1,   out.c1 = W + ModDown(S_1)
+  // 16 terms per accumulator at most, so rotations <= 15
+  const bool identity = identityStep("hlintrans");
+  if (identity && R > 15) throw std::runtime_error("hlintrans: rotations = " + S(R) + " with identity = 1, must be in [1, 15]");
+  makeInputs(1, /*plaintext=*/false, /*extPlaintexts=*/R, identity ? NamedStreams{{"pt0", 4300}} : NamedStreams{});
 
   KeySwitch ks(labelName, maxLevel, currentLevel, alpha, &Datapool, &DataInsMap, &insgener, addrManager.get());
   const KeySwitch::Digits digits = ks.modUp(cts[0].getC1Addr(), /*inputMayBeOpInput=*/true);
@@ -717,8 +745,17 @@ HLINTRANS::HLINTRANS(std::string labelName, uint32_t maxLevel, uint32_t currentL
     pts.push_back(namedInputs.at("pt" + S(r)));
   }
   std::array<Limbs, 3> sums;
-  for (uint32_t t = 0; t < 3; ++t) sums[t] = weightedSum(t, terms[t], pts, "");
-  setOutput("out", sumDown(ks, sums, "HLINTRANS", "HLINTRANSOutput(0)", ""));
+  if (!identity) {
+    for (uint32_t t = 0; t < 3; ++t) sums[t] = weightedSum(t, terms[t], pts, "");
+    setOutput("out", sumDown(ks, sums, "HLINTRANS", "HLINTRANSOutput(0)", ""));
+  } else {
+    const Limbs c0{cts[0].getC0Addr(), {}}, c1{cts[0].getC1Addr(), {}};
+    const std::vector<AddrType> &pt0 = namedInputs.at("pt0");
+    for (uint32_t t = 0; t < 2; ++t) sums[t] = weightedSum(t, terms[t], pts, "");
+    sums[2] = weightedSum(2, terms[2], pts, "", &c0, &pt0);
+    const Limbs W = weightedSum(3, {}, {}, "", &c1, &pt0);
+    setOutput("out", sumDown(ks, sums, "HLINTRANS", "HLINTRANSOutput(0)", "", &W));
+  }
   finishConstruction();
 }
 
@@ -825,13 +862,20 @@ HROTSUM::HROTSUM(std::string labelName, uint32_t maxLevel, uint32_t currentLevel
 // Every sum is formed by the element-wise chains of HLINTRANS and HROTSUM: bit-identical to G hlintrans ops on ct1 (op i with the plaintexts pt_{i,.})
 // followed by one hrotsum of their outputs with galois = h.  Unfused, the stages run one launch each; fused, pass (6m) of Arch::fusePasses
 // (Planner.cpp) turns the baby key products and the G weighted sums into one launch and pass (6s) the giant step into another.
-// Not built: identity steps on either axis, carrying S_{i,0} to the end on the extended basis, a rescale, the sharded plan.
+// identity = 1 adds the identity steps on both axes (below).  Not built: carrying S_{i,0} to the end on the extended basis, a rescale, the sharded plan.
 HBSGS::HBSGS(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch)
     : OperationBase("HBSGS", labelName, cfg, _arch, maxLevel, currentLevel, alpha) {
   const std::vector<uint32_t> gs = hoistedRotations("hbsgs");
   const uint32_t R = (uint32_t)gs.size(), G = cfg->getValueOr("giants", 4), twoN = 2 * N;
   if (G < 1 || G > 16) throw std::runtime_error("hbsgs: giants = " + S(G) + ", must be in [1, 16]");
-  const uint32_t h = cfg->getValueOr("galois_giant", gs.back());   // default g^R mod 2N
+  // identity = 1: giant groups i = 0..G and baby steps r = 0..R with g_0 = h_0 = 1.  Group i's identity baby step is the
+  // plaintext pt0_<i> (stream seed + 4300 + 100000 i), group 0's rotations are ptg<r> (seed + 4600 + 100000 r).  Group 0 is never brought
+  // down on its own: its sums join the giant step's in front of the one final ModDown.  16 terms per accumulator at most
+  const bool identity = identityStep("hbsgs");
+  if (identity && R > 15) throw std::runtime_error("hbsgs: rotations = " + S(R) + " with identity = 1, must be in [1, 15]");
+  if (identity && G > 15) throw std::runtime_error("hbsgs: giants = " + S(G) + " with identity = 1, must be in [1, 15]");
+  const uint32_t gNext = (uint32_t)((uint64_t)gs.back() * cfg->getValueOr("galois", 5) % twoN);
+  const uint32_t h = cfg->getValueOr("galois_giant", identity ? gNext : gs.back());   // default g^R mod 2N; with the identity step g^(R+1)
   if (!(h & 1) || h >= twoN) throw std::runtime_error("hbsgs: galois_giant = " + S(h) + " must be odd and below 2N = " + S(twoN));
   std::vector<uint32_t> hs;
   uint64_t hi = 1;
@@ -841,7 +885,10 @@ HBSGS::HBSGS(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, ui
       throw std::runtime_error("hbsgs: galois_giant^" + S(i) + " mod 2N repeats an element: the " + S(G) + " giant steps are not distinct");
     hs.push_back((uint32_t)hi);
   }
-  makeInputs(1, /*plaintext=*/false, /*extPlaintexts=*/G * R);
+  NamedStreams named;
+  for (uint32_t i = 0; identity && i <= G; ++i) named.push_back({"pt0_" + S(i), 4300 + 100000ull * i});
+  for (uint32_t r = 1; identity && r <= R; ++r) named.push_back({"ptg" + S(r), 4600 + 100000ull * r});
+  makeInputs(1, /*plaintext=*/false, /*extPlaintexts=*/G * R, named);
 
   KeySwitch ks(labelName, maxLevel, currentLevel, alpha, &Datapool, &DataInsMap, &insgener, addrManager.get());
   // the baby step: one ModUp, one key product and one rotated c0 per baby rotation
@@ -856,13 +903,25 @@ HBSGS::HBSGS(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, ui
   }
   // per giant step i: HLINTRANS's three weighted sums, the ModDown and the ADD of U_i give v_i
   std::vector<SwitchedSum> v;
-  for (uint32_t i = 1; i <= G; ++i) {
+  std::array<Limbs, 3> group0;   // the identity step: S_{0,0}, S_{0,1}, U_0 stay on their bases
+  Limbs W0;
+  const Limbs c0{cts[0].getC0Addr(), {}}, c1{cts[0].getC1Addr(), {}};
+  for (uint32_t i = identity ? 0 : 1; i <= G; ++i) {
     const std::string gp = "_Grp" + S(i);
     std::vector<std::vector<AddrType>> pts;
-    for (uint32_t r = 1; r <= R; ++r) pts.push_back(namedInputs.at("pt" + S((i - 1) * R + r)));
+    for (uint32_t r = 1; r <= R; ++r) pts.push_back(namedInputs.at(i ? "pt" + S((i - 1) * R + r) : "ptg" + S(r)));
     std::array<Limbs, 3> sums;
-    for (uint32_t t = 0; t < 3; ++t) sums[t] = weightedSum(t, terms[t], pts, gp);
-    v.push_back(sumDown(ks, sums, "HBSGS", "HBSGSInner" + gp + "(0)", gp));
+    if (!identity) {
+      for (uint32_t t = 0; t < 3; ++t) sums[t] = weightedSum(t, terms[t], pts, gp);
+      v.push_back(sumDown(ks, sums, "HBSGS", "HBSGSInner" + gp + "(0)", gp));
+      continue;
+    }
+    const std::vector<AddrType> &pt0 = namedInputs.at("pt0_" + S(i));
+    for (uint32_t t = 0; t < 2; ++t) sums[t] = weightedSum(t, terms[t], pts, gp);
+    sums[2] = weightedSum(2, terms[2], pts, gp, &c0, &pt0);
+    const Limbs W = weightedSum(3, {}, {}, gp, &c1, &pt0);
+    if (i == 0) { group0 = sums; W0 = W; }
+    else v.push_back(sumDown(ks, sums, "HBSGS", "HBSGSInner" + gp + "(0)", gp, &W));
   }
   // the giant step: HROTSUM's running sums over the v_i
   std::array<Limbs, 3> sums;   // T_0, T_1, V so far
@@ -872,9 +931,11 @@ HBSGS::HBSGS(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, ui
     const KeySwitch::Accumulators acc = ks.keyProduct(ks.rotateDigits(dg, hs[i - 1], gt), seed + 10000 + 100000ull * (16 + i), gt);
     dispatch(ks.takeStages());
     const std::array<Limbs, 3> term = {acc[0], acc[1], rotateLimbs(v[i - 1].c0, 0, hs[i - 1], gt)};
-    for (uint32_t t = 0; t < 3; ++t) sums[t] = i == 1 ? term[t] : addTerm(t, sums[t], term[t], "GiantSum", i, i == G);
+    for (uint32_t t = 0; t < 3; ++t) sums[t] = i == 1 ? term[t] : addTerm(t, sums[t], term[t], "GiantSum", i, i == G && !identity);
   }
-  setOutput("out", sumDown(ks, sums, "HBSGS", "HBSGSOutput(0)", ""));
+  // the group-0 term last, one ADD per tag; W_0 is the c1 addend behind the ModDown
+  for (uint32_t t = 0; identity && t < 3; ++t) sums[t] = addTerm(t, sums[t], group0[t], "GiantSum", 0, true);
+  setOutput("out", sumDown(ks, sums, "HBSGS", "HBSGSOutput(0)", "", identity ? &W0 : nullptr));
   finishConstruction();
 }
 

@@ -504,8 +504,10 @@ Arch::Planner::RotationGroups Arch::Planner::rotationGroups(Readers &rd) {
 //      share the R automorphisms), the M chains join as addend outputs: all of them or none.  Never written: the rotated digits, the per-rotation
 //      sums, the rotated c0.  The first key-product record in stage order carries the merged one: everything it reads is older, every reader of
 //      S_{m,k} and U_m comes after the chains' ends.
+//      The identity step (identity = 1): a U chain may start one link earlier, with a MUL of the rotations' source itself against a plaintext limb
+//      of its own; it then brings the lone MUL W_m of that limb with a second source (the unrotated c1) along, as a fourth output per group.
 //      Reads: the key-product records of (6).  Sets on the carrying record: ipX (the unrotated digits), ipY, ipHoistG, ipLinPt ([m][r]), ipLinAddend,
-//      OutputOperand, extraOutputs (group-major).  A non-empty ipHoistG keeps (7), (7b) and (12) off it.
+//      ipLinIdPt ([m]), ipLinAddend1, OutputOperand, extraOutputs (group-major).  A non-empty ipHoistG keeps (7), (7b) and (12) off it.
 void Arch::Planner::weightedRotations(size_t minSums, size_t maxSums) {
   Readers rd = readers();
   RotationGroups found = rotationGroups(rd);
@@ -555,7 +557,7 @@ void Arch::Planner::weightedRotations(size_t minSums, size_t maxSums) {
     if (!ok) continue;
     // U_m: a third MUL reader of group m's first plaintext limb whose chain multiplies pt_{m,r} with sigma_r of the one source; all or none
     std::vector<Chain> U(M);
-    std::vector<Instruction *> addendAutos;
+    std::vector<Instruction *> addendAutos, idHead(M, nullptr), idW(M, nullptr);   // idHead / idW: the identity step's first link of U_m and its W_m
     AddrType addend = 0;
     bool allU = true;
     for (size_t m = 0; m < M && allU; ++m) {
@@ -575,7 +577,34 @@ void Arch::Planner::weightedRotations(size_t minSums, size_t maxSums) {
         if (m == 0) { addendAutos = autos; addend = autos[0]->operandList[0]; }
         break;
       }
-      allU = !U[m].empty();
+      // the identity step: the chain starts one link earlier, with a MUL of the rotations' SOURCE itself against a plaintext limb of its own (nobody
+      // produces it), and that limb's one other reader is the lone MUL W_m of a second source (the unrotated c1): U_m and W_m join together
+      for (Instruction *u : rd[pt[m][0]]) {
+        if (!U[m].empty()) break;
+        if (u == S[m][0][0] || u == S[m][1][0] || u->ops != MULT || soleReader(rd, u->operandList[2], EWE_MAC_ADD, key.first) != u || u->operandList[1] != pt[m][0]) continue;
+        Instruction *head = producerOf(u->operandList[2]);
+        if (!head || !isMul(head, key.first) || head->fusedTensor || producerOf(head->operandList[1])) continue;
+        Chain c = chainFrom(rd, head, R + 1);
+        std::vector<Instruction *> autos;
+        for (size_t r = 1; r < c.size(); ++r) {
+          Instruction *l = c[r], *a = producerOf(l->operandList[0]);
+          if (l->operandList[1] != pt[m][r - 1] || !a || a->ops != AUTO || !live(a) || a->mod_id != key.first || a->galois != mem[r - 1].second[0]->galois ||
+              rd[l->operandList[0]].size() != M || a->operandList[0] != head->operandList[0] || (m && a != addendAutos[r - 1]))
+            break;
+          autos.push_back(a);
+        }
+        auto &idReaders = rd[head->operandList[1]];
+        Instruction *w = idReaders.size() == 2 ? idReaders[idReaders[0] == head ? 1 : 0] : nullptr;
+        // ... whose source nobody in this plan produces (an op input, as the rotations' source: the carrying record stands in front of
+        // everything but the ModUp and must not read what is written behind it)
+        if (autos.size() != R || !w || w == head || !isMul(w, key.first) || w->fusedTensor || w->operandList[1] != head->operandList[1] ||
+            producerOf(w->operandList[0]) || producerOf(head->operandList[0]) || (m && w->operandList[0] != idW[0]->operandList[0]))
+          continue;
+        U[m] = Chain(c.begin() + 1, c.end());
+        idHead[m] = head; idW[m] = w;
+        if (m == 0) { addendAutos = autos; addend = head->operandList[0]; }
+      }
+      allU = !U[m].empty() && (m == 0 || (idHead[m] != nullptr) == (idHead[0] != nullptr));   // the identity step: all groups or none, as U
     }
     for (size_t r = 0; r < R && allU; ++r)   // the rotated source is read by the M chains and nothing else
       for (Instruction *reader : rd[addendAutos[r]->OutputOperand]) {
@@ -584,6 +613,7 @@ void Arch::Planner::weightedRotations(size_t minSums, size_t maxSums) {
         allU = allU && mine;
       }
     if (!allU) addend = 0;
+    const bool identity = addend && idHead[0];
     Instruction *c = mem[0].first;
     std::vector<std::vector<AddrType>> ys;
     std::vector<uint32_t> gs;
@@ -603,6 +633,13 @@ void Arch::Planner::weightedRotations(size_t minSums, size_t maxSums) {
       outs.push_back(S[m][0].back()->OutputOperand);
       outs.push_back(S[m][1].back()->OutputOperand);
       if (addend) outs.push_back(U[m].back()->OutputOperand);
+      if (identity) {
+        outs.push_back(idW[m]->OutputOperand);
+        c->ipLinIdPt.push_back(idHead[m]->operandList[1]);
+        c->ipLinAddend1 = idW[m]->operandList[0];
+        absorb(c, idHead[m]);
+        absorb(c, idW[m]);
+      }
     }
     c->ipLinPt = pt;
     c->ipLinAddend = addend;
@@ -618,8 +655,10 @@ void Arch::Planner::weightedRotations(size_t minSums, size_t maxSums) {
 //      same elements, in the same order, each of its own source, it joins as the record's addend output.  Never written: the rotated digits, the
 //      2G per-ciphertext sums, the partial sums, the rotated c0's.  The first key-product record in stage order carries the merged one; it moves
 //      to where the last link of S_0, S_1 stood: every ciphertext's digits are older, every reader of S_k and U comes after the chains' ends.
+//      Initial sums (hbsgs with the identity step): ONE trailing ADD per chain whose other operand is no candidate record's output, written
+//      before the carrying record, joins as the value the sum starts from (all chains or none; then one record alone may merge too).
 //      Reads: the key-product records of (6).  Sets on the carrying record: ipX, ipSumX (every ciphertext's unrotated digits), ipY, ipHoistG,
-//      ipSumAddend, OutputOperand, extraOutputs.
+//      ipSumAddend, ipSumInit, ipSumAddendInit, OutputOperand, extraOutputs.
 void Arch::Planner::sumOfRotations() {
   Readers rd = readers();
   RotationGroups found = rotationGroups(rd);
@@ -645,7 +684,8 @@ void Arch::Planner::sumOfRotations() {
     const uint32_t mod = c->mod_id;
     // S_0: link by link, the running sum plus the output 0 of a further candidate record
     std::vector<Instruction *> mem = {c}, S[2];
-    for (AddrType sum = c->OutputOperand; mem.size() < HM_IP_ROTSUM_MAX_CT;) {
+    AddrType end[3] = {c->OutputOperand, c->extraOutputs[0], 0};   // where the chains S_0, S_1, U end
+    for (AddrType &sum = end[0]; mem.size() < HM_IP_ROTSUM_MAX_CT;) {
       AddrType other = 0;
       Instruction *l = addOf(sum, mod, other), *ip = l ? producerOf(other) : nullptr;
       if (!ip || !candidates.count(ip) || taken.count(ip) || ip->mod_id != mod || ip->OutputOperand != other || !onlyReader(rd, other, l) ||
@@ -656,24 +696,43 @@ void Arch::Planner::sumOfRotations() {
       sum = l->OutputOperand;
     }
     const size_t G = mem.size();
-    if (G < 2) continue;
+    // the initial sums: ONE trailing ADD per chain whose other operand is no candidate record's output (hbsgs with the identity step: group 0's
+    // sums S_{0,k}, which were never brought down).  `init` = that operand
+    auto trailing = [&](AddrType sum, AddrType &init) -> Instruction * {
+      Instruction *l = addOf(sum, mod, init), *w = l ? producerOf(init) : nullptr;
+      return l && !(w && candidates.count(w)) ? l : nullptr;
+    };
+    AddrType init[3] = {0, 0, 0};
+    Instruction *tail[3] = {G < HM_IP_ROTSUM_MAX_CT ? trailing(end[0], init[0]) : nullptr, nullptr, nullptr};
+    if (G < 2 && !tail[0]) continue;
     // S_1: the same records in the same order
     bool ok = true;
-    for (AddrType sum = c->extraOutputs[0]; ok && S[1].size() + 1 < G;) {
+    for (AddrType &sum = end[1]; ok && S[1].size() + 1 < G;) {
       AddrType other = 0;
       Instruction *l = addOf(sum, mod, other), *ip = mem[S[1].size() + 1];
       ok = l && other == ip->extraOutputs[0] && onlyReader(rd, other, l);
       if (ok) { S[1].push_back(l); sum = l->OutputOperand; }
     }
     if (!ok) continue;
+    if (tail[0]) tail[1] = trailing(end[1], init[1]);
+    if (tail[0] && !tail[1]) {   // initial sums for both or for none
+      if (G < 2) continue;
+      tail[0] = nullptr;
+    }
     // where the merged record goes: the place of the last key product or link of S_0, S_1.  Every limb's record then stands in the stage of
     // S_1's last link, so that the records with and without an addend share a launch
     Instruction *last = c;
     for (Instruction *i : mem) if (place.after(i, last)) last = i;
     for (auto &chain : S) for (Instruction *i : chain) if (place.after(i, last)) last = i;
+    for (int k = 0; k < 2 && tail[0]; ++k) {
+      if (place.after(tail[k], last)) last = tail[k];
+      if (Instruction *w = producerOf(init[k])) ok = ok && !place.after(w, c);   // written before anything of the merged record
+    }
+    if (!ok) continue;
     // U: an ADD chain over automorphisms by the records' elements, in their order, each of its own source (written, if at all, before that
     // place) and read by its link only
     std::vector<Instruction *> U, addendAutos;
+    bool foundU = false;
     for (auto &s : st) {
       for (Instruction *a0 : s.ins) {
         if (!live(a0) || a0->ops != AUTO || a0->mod_id != mod || a0->galois != candidates[c].autos[0]->galois || rd[a0->OutputOperand].size() != 1) continue;
@@ -691,10 +750,16 @@ void Arch::Planner::sumOfRotations() {
         }
         if (Instruction *w = producerOf(a0->operandList[0])) if (place.after(w, last)) continue;
         if (autos.size() != G) continue;
-        U = links; addendAutos = autos;
+        end[2] = links.empty() ? a0->OutputOperand : links.back()->OutputOperand;
+        if (tail[0]) {   // with initial sums the addend sum has one too, or does not join
+          tail[2] = trailing(end[2], init[2]);
+          Instruction *w = tail[2] ? producerOf(init[2]) : nullptr;
+          if (!tail[2] || (w && place.after(w, c))) continue;
+        } else if (G < 2) continue;
+        U = links; addendAutos = autos; foundU = true;
         break;
       }
-      if (!U.empty()) break;
+      if (foundU) break;
     }
     std::vector<std::vector<AddrType>> xs, ys;
     std::vector<uint32_t> gs;
@@ -708,10 +773,13 @@ void Arch::Planner::sumOfRotations() {
       absorb(c, m.ip);
       for (Instruction *a : m.autos) absorb(c, a);
       if (g) { absorb(c, S[0][g - 1]); absorb(c, S[1][g - 1]); }
-      if (!U.empty()) { addends.push_back(addendAutos[g]->operandList[0]); absorb(c, addendAutos[g]); if (g) absorb(c, U[g - 1]); }
+      if (foundU) { addends.push_back(addendAutos[g]->operandList[0]); absorb(c, addendAutos[g]); if (g) absorb(c, U[g - 1]); }
     }
-    std::vector<AddrType> outs = {S[0].back()->OutputOperand, S[1].back()->OutputOperand};
-    if (!U.empty()) outs.push_back(U.back()->OutputOperand);
+    for (int k = 0; k < 3 && tail[0]; ++k)
+      if (tail[k]) { end[k] = tail[k]->OutputOperand; absorb(c, tail[k]); }
+    if (tail[0]) { c->ipSumInit = {init[0], init[1]}; c->ipSumAddendInit = tail[2] ? init[2] : 0; }
+    std::vector<AddrType> outs = {end[0], end[1]};
+    if (foundU) outs.push_back(end[2]);
     c->ipSumX = xs;
     c->ipSumAddend = addends;
     carry(c, xs[0], ys, gs, outs);

@@ -255,6 +255,24 @@ typedef struct hm_ip_lintrans_multi_desc {
   const uint32_t *galois;                                     /* [n_rot] */
 } hm_ip_lintrans_multi_desc;
 hm_status hm_inner_product_lintrans_multi(hm_ctx *ctx, const hm_ip_lintrans_multi_desc *desc);
+/* ... with the identity step (hlintrans with identity = 1): the unrotated term of every sum, which meets no key.  On the
+ * entries i that carry an addend source (sums.addend: c0; required, at least the pointers) and for every output m,
+ *   addend_out[m][i]  = pt[id_pt[m][i]] (.) addend[i] + sum_r pt[m][r][i] (.) automorph_{galois[r]}(addend[i])
+ *   addend1_out[m][i] = pt[id_pt[m][i]] (.) addend1[i]                                (c1: a single product)
+ * with addend[i] and addend1[i] read where they are stored (no automorphism); out[m][i][k] is hm_inner_product_lintrans_multi's.  Every residue
+ * fully reduced: bit-identical to hm_inner_product_lintrans_multi(&sums) followed by HM_OP_MAC_ADD (addend_out) and HM_OP_MUL (addend1_out).
+ * sums.n_rot <= HM_IP_LINTRANS_ID_MAX_ROT keeps every accumulator at 16 products.  sums.n_out = 1 runs the single-sum kernel form.  Row-major lists: id_pt_limbs[m * n + i] (limbs of sums.pt), addend1_limbs[i], addend1_out_limbs[m * n + i]; all three are read where
+ * sums.addend_limbs[i] != HM_NO_LIMB, and addend1_limbs[i] must be HM_NO_LIMB exactly where sums.addend_limbs[i] is.  No output limb-poly (out,
+ * addend_out, addend1_out) may overlap, by address range, any input or another output: HM_ERR_ARG.  Safe under graph capture once it has run
+ * with the same limb lists. */
+#define HM_IP_LINTRANS_ID_MAX_ROT 15
+typedef struct hm_ip_lintrans_id_desc {
+  hm_ip_lintrans_multi_desc sums;                                    /* n_out >= 1; addend (c0) required */
+  const uint32_t *id_pt_limbs;                                       /* [n_out][n], limbs of sums.pt */
+  const uint64_t *addend1;      const uint32_t *addend1_limbs;       /* c1 sources [n]; HM_NO_LIMB exactly where addend_limbs is */
+  uint64_t *addend1_out;        const uint32_t *addend1_out_limbs;   /* [n_out][n] */
+} hm_ip_lintrans_id_desc;
+hm_status hm_inner_product_lintrans_id(hm_ctx *ctx, const hm_ip_lintrans_id_desc *desc);
 /* Sum of the key products of rotations of n_ct DIFFERENT ciphertexts (hrotsum): every ciphertext has its own digits,
  * keys and Galois element, and the sum over the ciphertexts is formed BEFORE anything is stored,
  *   out[i][k]     = sum_c sum_j automorph_{galois[c]}(x[c][i][j]) (.) y[c][i][k][j]      k < 2, j < n_terms <= 4, c < n_ct <= 16
@@ -280,6 +298,19 @@ typedef struct hm_ip_rotsum_desc {
   const uint32_t *galois;                                     /* [n_ct] */
 } hm_ip_rotsum_desc;
 hm_status hm_inner_product_rotsum(hm_ctx *ctx, const hm_ip_rotsum_desc *desc);
+/* ... with initial sums (hbsgs with identity = 1): the sums start from stored polynomials instead of zero,
+ *   out[i][k]     = init[i][k] + sum_c ...,      addend_out[i] = addend[addend_init_limbs[i]] + sum_c ...
+ * init and the initial addend sums are read where the outputs are written (no automorphism).  Bit-identical to hm_inner_product_rotsum(&sum)
+ * followed by HM_OP_ADD.  sum.n_ct <= HM_IP_ROTSUM_INIT_MAX_CT keeps the addend accumulator at 16 residues.  addend_init_limbs (limbs of
+ * sum.addend) is needed with sum.addend_limbs and is HM_NO_LIMB exactly on the entries without addend sources.  The initial sums are inputs: no
+ * output may overlap them by address range (HM_ERR_ARG).  Safe under graph capture once it has run with the same limb lists. */
+#define HM_IP_ROTSUM_INIT_MAX_CT 15
+typedef struct hm_ip_rotsum_init_desc {
+  hm_ip_rotsum_desc sum;
+  const uint64_t *init;         const uint32_t *init_limbs;          /* [n][2] */
+  const uint32_t *addend_init_limbs;                                 /* [n] in sum.addend; HM_NO_LIMB where no addend */
+} hm_ip_rotsum_init_desc;
+hm_status hm_inner_product_rotsum_init(hm_ctx *ctx, const hm_ip_rotsum_init_desc *desc);
 
 /* K1 x K5 — the HPIP unit as a fused NTT-epilogue x evaluation-key MAC: for extended limb i,
  *     out[i][k] = sum_{j < n_terms} X_j[i] * y[i][k][j],   X_j[i] = NTT(x[i][j]) if x_is_coeff[i][j] else x[i][j]
