@@ -98,7 +98,7 @@ __device__ __forceinline__ void hm_ntt_pass_run(const HmNttArgs &a, uint64_t *ld
   typedef const HmNttEntry __attribute__((address_space(4))) *ConstEntry;
   const ConstEntry entries = (ConstEntry)(uintptr_t)a.entry;
   if constexpr (MODE == 2) { sc.w = entries[entry].sc.w; sc.ws = entries[entry].sc.ws; ep.pack = entries[entry].pack; }
-  if constexpr (MODE == 3 || MODE == 7) {
+  if constexpr (MODE == 3 || MODE == 7 || MODE == 8) {
     const auto &en = entries[entry];
     sc.w = en.sc.w; sc.ws = en.sc.ws;
     ep.a = a.minuend + (size_t)lb.aux * N;
@@ -107,6 +107,11 @@ __device__ __forceinline__ void hm_ntt_pass_run(const HmNttArgs &a, uint64_t *ld
     if constexpr (MODE == 7) { ep.g = en.galois; ep.logN = a.logN; }
   }
   if constexpr (MODE == 6) { ep.g = entries[entry].galois; ep.logN = a.logN; }
+  if constexpr (MODE == 8 || MODE == 9) {   // the second factor's limb-poly: the table's extension behind the n_limbs entry records
+    typedef const HmNttMulEntry __attribute__((address_space(4))) *ConstMul;
+    ep.b = ((ConstMul)(uintptr_t)(a.entry + a.n_limbs))[entry].b;
+    ep.bk.w = HM_CONST_MODS(a.mods)[mod].mu; ep.bk.ws = HM_CONST_MODS(a.mods)[mod].sh;
+  }
   if constexpr (MODE == 4) {
     const auto &en = entries[entry];
     ep.b = a.mix + (size_t)en.mixlimb * N;
@@ -128,7 +133,10 @@ __device__ __forceinline__ void hm_ntt_pass_body(const HmNttArgs &a) {
 #if defined(HM_ABL_EMPTY)   // timing-only ablation: launch, dispatch and the block map only
   return;
 #endif
-  hm_ntt_pass_run<LOGR, STRIDED, INV, MODE, 0, 0, HM_EPI_CHUNK, GEO>(a, lds, entry, tile, threadIdx.x);
+  // MODE 8 in the 16-coefficient geometry of the generic back-end: the second factor's chunk of two units does not fit 128 registers beside the
+  // Shoup twiddles (4 VGPRs spilled); requested one unit at a time it does
+  constexpr int EPICH = (MODE == 8 && HM_GENERIC && GEO::EPT == 16) ? 1 : HM_EPI_CHUNK;
+  hm_ntt_pass_run<LOGR, STRIDED, INV, MODE, 0, 0, EPICH, GEO>(a, lds, entry, tile, threadIdx.x);
 }
 
 // Minimum waves per SIMD the register allocator must leave room for (HIP's second launch-bound argument; it is ignored
@@ -142,7 +150,8 @@ __device__ __forceinline__ void hm_ntt_pass_body(const HmNttArgs &a) {
 #endif
 // MODE 0: first pass / plain hand-off; 1: forward final; 2: inverse final (x scale); 3: forward final with the fused
 // epilogue; 4: forward first pass with the mix prologue; 6: inverse first pass whose input is read through an automorphism; 7: MODE 3 with the
-// addend read through an automorphism (round 6: hrotate's automorphism launch folded into the ModUp INTT and the final add)
+// addend read through an automorphism (round 6: hrotate's automorphism launch folded into the ModUp INTT and the final add); 8: MODE 3 whose minuend
+// is the product of two stored limb-polys; 9: inverse first pass whose input is such a product (pmult's products folded into the rescale's transforms)
 template <int LOGR, bool INV, int MODE>
 __global__ void __launch_bounds__((1 << HM_TL_COL) / HM_EPT) __attribute__((amdgpu_waves_per_eu(HM_NTT_MIN_WAVES_COL))) k_ntt_col(HmNttArgs a) {
   hm_ntt_pass_body<LOGR, true, INV, MODE>(a);
@@ -693,7 +702,7 @@ struct hm_ctx {
   bool capture_has_fused = false;   // the capture in progress recorded a one-launch transform
   // launches of up to this many entries (N = 2^16) run as ONE launch in the small-launch geometry (k_ntt_fused8): 2-5 us faster than two kernels up to ~100
   // limb-polys, slower from 128 (tools/ntt_fused_small_ab.py); 0 = off
-  uint32_t fused_small = 96;
+  uint32_t fused_small = HM_NTT_FUSED_SMALL;
   uint32_t bcol_outs = 0;   // output limbs per workgroup of the fused conversion + first pass (1 | 2; 0 = by launch size)
   // k_bconv: blocks a launch should have at least before its outputs are cut into fewer, larger chunks (a block re-reads its inputs per chunk)
   uint32_t bconv_blocks = 3072;
@@ -1180,7 +1189,8 @@ static hm_status check_mods(hm_ctx *c, const char *what, const uint32_t *m, uint
 
 // The kernels of a transform, by form: 0 = forward, 1 = forward with the fused epilogue (MODE 3), 2 = forward with the mix prologue and
 // the epilogue (MODE 4 + 3), 3 = inverse, 4 = inverse with the input read through an automorphism (MODE 6), 5 = form 1 with the addend read
-// through an automorphism (MODE 7).  `first` / `second` = the two pass kernels in the order they run (forward: COL then ROW,
+// through an automorphism (MODE 7), 6 = form 1 with a product minuend (MODE 8), 7 = form 2 with a product minuend (MODE 4 + 8), 8 = inverse with a
+// product input (MODE 9).  `first` / `second` = the two pass kernels in the order they run (forward: COL then ROW,
 // inverse: ROW then COL) in the 16-coefficient geometry; `first8` / `second8` = the same in the small-launch geometry and `one` = both
 // passes in one launch ([0] out of place: non-temporal input loads, [1] in place); the small-launch forms exist where hm_caps says so
 // (N = 2^15 and 2^16).
@@ -1190,7 +1200,8 @@ struct HmNttKernels {
   hm_ntt_kernel first, second, first8, second8;
   hm_ntt_one_kernel one[2];
 };
-#define HM_NTT_FORMS 6
+static_assert(HM_NTT_MAX_LAUNCH_ENTRIES == HM_NTT_MAX_ENTRIES, "hm_caps.h states the launch's record count for the host layer");
+#define HM_NTT_FORMS 9
 template <int LOG1>
 static const HmNttKernels &ntt_kernels(int form) {
   static const HmNttKernels wide[HM_NTT_FORMS] = {
@@ -1199,7 +1210,10 @@ static const HmNttKernels &ntt_kernels(int form) {
       {k_ntt_col<LOG1, false, 4>, k_ntt_row<false, 3>, nullptr, nullptr, {nullptr, nullptr}},
       {k_ntt_row<true, 0>, k_ntt_col<LOG1, true, 2>, nullptr, nullptr, {nullptr, nullptr}},
       {k_ntt_row<true, 6>, k_ntt_col<LOG1, true, 2>, nullptr, nullptr, {nullptr, nullptr}},
-      {k_ntt_col<LOG1, false, 0>, k_ntt_row<false, 7>, nullptr, nullptr, {nullptr, nullptr}}};
+      {k_ntt_col<LOG1, false, 0>, k_ntt_row<false, 7>, nullptr, nullptr, {nullptr, nullptr}},
+      {k_ntt_col<LOG1, false, 0>, k_ntt_row<false, 8>, nullptr, nullptr, {nullptr, nullptr}},
+      {k_ntt_col<LOG1, false, 4>, k_ntt_row<false, 8>, nullptr, nullptr, {nullptr, nullptr}},
+      {k_ntt_row<true, 9>, k_ntt_col<LOG1, true, 2>, nullptr, nullptr, {nullptr, nullptr}}};
   return wide[form];
 }
 // the ring sizes of the reference's configurations (config/config_4.cfg: N = 2^16, config_4_N15.cfg: N = 2^15) have all three forms
@@ -1218,7 +1232,18 @@ static const HmNttKernels &ntt_kernels_all(int form) {
       {k_ntt_row<true, 6>, k_ntt_col<LOG1, true, 2>, k_ntt_row8<true, 6>, k_ntt_col8<LOG1, true, 2>, {k_ntt_fused8<LOG1, true, 6, 2, true>,
           k_ntt_fused8<LOG1, true, 6, 2, true>}},
       {k_ntt_col<LOG1, false, 0>, k_ntt_row<false, 7>, k_ntt_col8<LOG1, false, 0>, k_ntt_row8<false, 7>, {k_ntt_fused8<LOG1, false, 0, 7, true>,
-          k_ntt_fused8<LOG1, false, 0, 7, false>}}};
+          k_ntt_fused8<LOG1, false, 0, 7, false>}},
+      // (the product epilogue costs the 8-coefficient ROW kernel a wave per SIMD on both back-ends, and the generic one-launch form one too: those
+      // geometries are left out of forms 6 and 7, whose launches fall back to the next form: one-launch -> 16-coefficient two-kernel)
+#if HM_GENERIC
+      {k_ntt_col<LOG1, false, 0>, k_ntt_row<false, 8>, nullptr, nullptr, {nullptr, nullptr}},
+      {k_ntt_col<LOG1, false, 4>, k_ntt_row<false, 8>, nullptr, nullptr, {nullptr, nullptr}},
+#else
+      {k_ntt_col<LOG1, false, 0>, k_ntt_row<false, 8>, nullptr, nullptr, {k_ntt_fused8<LOG1, false, 0, 8, true>, k_ntt_fused8<LOG1, false, 0, 8, false>}},
+      {k_ntt_col<LOG1, false, 4>, k_ntt_row<false, 8>, nullptr, nullptr, {k_ntt_fused8<LOG1, false, 4, 8, true>, k_ntt_fused8<LOG1, false, 4, 8, false>}},
+#endif
+      {k_ntt_row<true, 9>, k_ntt_col<LOG1, true, 2>, k_ntt_row8<true, 9>, k_ntt_col8<LOG1, true, 2>, {k_ntt_fused8<LOG1, true, 9, 2, true>,
+          k_ntt_fused8<LOG1, true, 9, 2, false>}}};
   return both[form];
 }
 template <> const HmNttKernels &ntt_kernels<8>(int form) { return ntt_kernels_all<8>(form); }
@@ -1236,7 +1261,7 @@ template <int LOG1>
 static void launch_ntt(hm_ctx *c, const HmNttArgs &a, int form, bool firstPassOnly, bool secondPassOnly = false) {
   // n_limbs = entries, a multiple of 8 (one group per XCD); one workgroup per 4096-coefficient tile of each pass (HM_TL_COL == HM_TL_ROW)
   const HmNttKernels &K = ntt_kernels<LOG1>(form);
-  const bool inverse = form == 3 || form == 4;
+  const bool inverse = form == 3 || form == 4 || form == 8;
   const dim3 grid(a.n_limbs * (c->P.N >> HM_TL_ROW)), block16((1 << HM_TL_ROW) / HM_EPT), block8((1 << HM_TL_ROW) / 8);
   // small launches (one round of workgroups on the chip): the 8-coefficient geometry halves the serial work per wave (small_mode:
   // bit 0 = the COL pass, bit 1 = the ROW pass; the hand-off between the passes is the same in both geometries)
@@ -1295,9 +1320,17 @@ static hm_status device_table(hm_ctx *c, const void *data, size_t bytes, const v
   *out = it->second;
   return HM_OK;
 }
-static hm_status ntt_table(hm_ctx *c, const std::vector<HmNttEntry> &tab, const HmNttEntry **out) {
+// `mul` (empty: none): the table's extension for the product operands, one HmNttMulEntry per entry behind the entry records, in the same allocation
+static hm_status ntt_table(hm_ctx *c, const std::vector<HmNttEntry> &tab, const std::vector<HmNttMulEntry> &mul, const HmNttEntry **out) {
   const void *p = nullptr;
-  hm_status st = device_table(c, tab.data(), sizeof(HmNttEntry) * tab.size(), &p);
+  hm_status st;
+  if (mul.empty()) st = device_table(c, tab.data(), sizeof(HmNttEntry) * tab.size(), &p);
+  else {
+    std::vector<char> both(sizeof(HmNttEntry) * tab.size() + sizeof(HmNttMulEntry) * mul.size());
+    memcpy(both.data(), tab.data(), sizeof(HmNttEntry) * tab.size());
+    memcpy(both.data() + sizeof(HmNttEntry) * tab.size(), mul.data(), sizeof(HmNttMulEntry) * mul.size());
+    st = device_table(c, both.data(), both.size(), &p);
+  }
   *out = static_cast<const HmNttEntry *>(p);
   return st;
 }
@@ -1315,6 +1348,8 @@ struct NttFused {
   const uint8_t *outPacked = nullptr;   // inverse: per limb-poly, store the split-30 packed form (hm_pack30)
   const uint32_t *inGalois = nullptr;   // inverse (round 6): per limb-poly, the input is read through X -> X^g (0 / 1: as stored)
   const uint32_t *addGalois = nullptr;  // fused forward (round 6): per limb-poly, the addend is read through X -> X^g (0 / 1: as stored)
+  const uint64_t *mulB = nullptr;       // fused forward: the minuend, inverse: the input is the product with this operand (hm_ntt_mix_sub_scale_mul, hm_ntt_mul)
+  const uint32_t *mulB_limbs = nullptr; // ... fused forward: HM_NO_LIMB = a plain minuend for that limb-poly
   bool firstPassOnly = false;   // forward transform: run the COL pass only (the hand-off stays in `out`)
   bool secondPassOnly = false;  // forward transform: the hand-off is already in `out` (a fused conversion wrote it): run the ROW pass only
 };
@@ -1333,6 +1368,17 @@ static hm_status ntt_common(hm_ctx *c, const char *what, const uint64_t *in, con
   for (uint32_t g = 0; f.addend_limbs && g < n; ++g)
     if (f.addend_limbs[g] != HM_NO_LIMB && f.addend_limbs[g] >= 0xFFFFu) return fail(c, HM_ERR_ARG, "%s: addend limb index %u exceeds 65534", what,
         f.addend_limbs[g]);
+  for (uint32_t g = 0; f.mulB && f.mulB_limbs && g < n; ++g)
+    if (f.mulB_limbs[g] > 0xFFFFu && !(fused && f.mulB_limbs[g] == HM_NO_LIMB)) return fail(c, HM_ERR_ARG, "%s: product operand limb index %u exceeds 65535", what,
+        f.mulB_limbs[g]);
+  if (f.mulB && inverse) {   // a workgroup of the first pass writes its tile of `out` while others still read theirs of in_b: no limb-poly may be both
+    const int64_t g = hm_first_overlap(out, out_limbs, n, f.mulB, f.mulB_limbs, n, c->P.N, [](uint32_t) { return true; });
+    if (g >= 0) return fail(c, HM_ERR_ARG, "%s: the output overlaps in_b of limb-poly [%u]", what, (uint32_t)g);
+  }
+  if (f.mulB && fused) {   // `out` is the first pass's scratch: it must not hold a factor the epilogue reads afterwards
+    const int64_t g = hm_first_overlap(out, out_limbs, n, f.mulB, f.mulB_limbs, n, c->P.N, [&](uint32_t i) { return !(f.mulB_limbs && f.mulB_limbs[i] == HM_NO_LIMB); });
+    if (g >= 0) return fail(c, HM_ERR_ARG, "%s: the output overlaps minuend_b of limb-poly [%u] (out is the first pass's scratch)", what, (uint32_t)g);
+  }
   for (uint32_t g = 0; g < n; ++g) {
     const uint64_t q = c->P.mod[mod_ids[g]];
     if ((k && k[g] >= q) || (f.addend_k && f.addend_k[g] >= q) || (f.mix_k && f.mix_k[g] >= q))
@@ -1377,6 +1423,7 @@ static hm_status ntt_common(hm_ctx *c, const char *what, const uint64_t *in, con
     const uint32_t ng = hm_launch_groups(parts, (uint32_t)groups.size(), base), cnt = hm_launch_entries(ng, G);
     std::vector<HmNttEntry> tab(cnt);
     memset(tab.data(), 0, sizeof(HmNttEntry) * cnt);
+    std::vector<HmNttMulEntry> mul(f.mulB ? cnt : 0, HmNttMulEntry{nullptr});
     HmNttArgs a;
     for (uint32_t e = 0; e < cnt; ++e) a.limb[e] = HmLimb{0, 0, (uint16_t)HM_NTT_NONE, 0};
     for (uint32_t kk = 0; kk < ng; ++kk) {
@@ -1387,6 +1434,7 @@ static hm_status ntt_common(hm_ctx *c, const char *what, const uint64_t *in, con
         const uint64_t q = c->P.mod[m];
         HmNttEntry &t = tab[e];
         a.limb[e] = HmLimb{(uint16_t)limb_at(in_limbs, g), (uint16_t)limb_at(out_limbs, g), (uint16_t)m, 0};
+        if (f.mulB && !(f.mulB_limbs && f.mulB_limbs[g] == HM_NO_LIMB)) mul[e].b = f.mulB + (size_t)limb_at(f.mulB_limbs, g) * c->P.N;
         if (inverse) {
           uint64_t v = c->P.modc[m].ninv;
           if (k) v = hm::mulmod(v, k[g], q);
@@ -1408,7 +1456,7 @@ static hm_status ntt_common(hm_ctx *c, const char *what, const uint64_t *in, con
     }
     const HmNttEntry *dtab = nullptr;
     if (inverse || fused) {   // the plain forward transform needs no per-limb constants
-      if ((st = ntt_table(c, tab, &dtab))) return st;
+      if ((st = ntt_table(c, tab, mul, &dtab))) return st;
     }
     a.in = in; a.out = out;
     a.tw = inverse ? c->d_tw_inv : c->d_tw_fwd;
@@ -1417,7 +1465,7 @@ static hm_status ntt_common(hm_ctx *c, const char *what, const uint64_t *in, con
     a.entry = dtab;
     a.minuend = f.minuend; a.addend = f.addend; a.mix = f.mix;
     a.logN = c->P.logN; a.n_limbs = cnt; a.logG = logG;
-    const int form = inverse ? (anyInGalois ? 4 : 3) : fused ? (f.mix ? 2 : anyAddGalois ? 5 : 1) : 0;
+    const int form = inverse ? (f.mulB ? 8 : anyInGalois ? 4 : 3) : fused ? (f.mulB ? (f.mix ? 7 : 6) : f.mix ? 2 : anyAddGalois ? 5 : 1) : 0;
     static void (*const launch[])(hm_ctx *, const HmNttArgs &, int, bool, bool) = {launch_ntt<5>, launch_ntt<6>, launch_ntt<7>, launch_ntt<8>, launch_ntt<9>};
     const uint32_t log1 = c->P.logN - HM_ROW_LOG;   // the COL pass's sub-transform length
     if (log1 < 5 || log1 > 9) return fail(c, HM_ERR_UNSUPPORTED, "%s: logN %u", what, c->P.logN);
@@ -1460,6 +1508,18 @@ extern "C" hm_status hm_ntt_ex(hm_ctx *c, const hm_ntt_desc *d) {
   return ntt_common(c, "hm_ntt_ex", d->in, d->in_limbs, d->out, d->out_limbs, d->mod_ids, d->n, d->inverse, d->scale, f);
 }
 
+extern "C" hm_status hm_ntt_mul(hm_ctx *c, const hm_ntt_mul_desc *m) {
+  if (!c) return HM_ERR_ARG;
+  if (!m || !m->t.in || !m->t.out || !m->in_b) return fail(c, HM_ERR_ARG, "hm_ntt_mul: null buffer");
+  const hm_ntt_desc *d = &m->t;
+  if (!d->inverse) return fail(c, HM_ERR_UNSUPPORTED, "hm_ntt_mul: only the inverse transform takes a product input");
+  if (d->second_pass_only || d->in_galois) return fail(c, HM_ERR_UNSUPPORTED, "hm_ntt_mul: not with second_pass_only or in_galois");
+  NttFused f;
+  f.outPacked = d->out_packed;
+  f.mulB = m->in_b; f.mulB_limbs = m->in_b_limbs;
+  return ntt_common(c, "hm_ntt_mul", d->in, d->in_limbs, d->out, d->out_limbs, d->mod_ids, d->n, 1, d->scale, f);
+}
+
 extern "C" hm_status hm_ntt_sub_scale(hm_ctx *c, const uint64_t *in, const uint32_t *in_limbs, const uint64_t *minuend,
                                       const uint32_t *minuend_limbs, const uint64_t *addend, const uint32_t *addend_limbs,
                                       uint64_t *out, const uint32_t *out_limbs, const uint32_t *mod_ids, uint32_t n,
@@ -1477,6 +1537,21 @@ struct BcolMix {   // the MODE 4 prologue of a fused conversion (x = conv + k * 
   const uint64_t *const *mix_k;
 };
 static hm_status bconv_col_launch(hm_ctx *c, const hm_bconv_desc *descs, uint32_t n_desc, const BcolMix *mix, uint32_t tile0 = 0, uint32_t n_tiles = 0);
+extern "C" hm_status hm_ntt_mix_sub_scale_mul(hm_ctx *c, const hm_ntt_fused_mul_desc *m) {
+  static const char *const what = "hm_ntt_mix_sub_scale_mul";
+  if (!c) return HM_ERR_ARG;
+  if (!m || !m->t.in || !m->t.out || !m->t.minuend || !m->t.k || !m->minuend_b) return fail(c, HM_ERR_ARG, "%s: null argument", what);
+  const hm_ntt_fused_desc *d = &m->t;
+  if (d->n_conv || d->conv || d->addend_galois) return fail(c, HM_ERR_UNSUPPORTED, "%s: a product minuend combines with neither conv nor addend_galois", what);
+  if ((d->mix != nullptr) != (d->mix_k != nullptr)) return fail(c, HM_ERR_ARG, "%s: mix and mix_k go together", what);
+  if (d->addend_k && !d->addend) return fail(c, HM_ERR_ARG, "%s: addend_k without addend", what);
+  NttFused f;
+  f.minuend = d->minuend; f.minuend_limbs = d->minuend_limbs; f.addend = d->addend; f.addend_limbs = d->addend_limbs;
+  f.addend_k = d->addend_k; f.mix = d->mix; f.mix_limbs = d->mix_limbs; f.mix_k = d->mix_k;
+  f.mulB = m->minuend_b; f.mulB_limbs = m->minuend_b_limbs;
+  return ntt_common(c, what, d->in, d->in_limbs, d->out, d->out_limbs, d->mod_ids, d->n, 0, d->k, f);
+}
+
 extern "C" hm_status hm_ntt_mix_sub_scale(hm_ctx *c, const hm_ntt_fused_desc *d) {
   if (!c) return HM_ERR_ARG;
   if (!d || (!d->in && !d->n_conv) || !d->out || !d->minuend || !d->k) return fail(c, HM_ERR_ARG, "hm_ntt_mix_sub_scale: null argument");

@@ -10,6 +10,8 @@
 
 #define HM_BCOL_MAX_IN 32       // fused conversion + first pass: digits of up to 15 limbs hold every input of an access unit at once; 16 .. 32 (round 6) take two groups
 #define HM_BCOL_MAX_IN_MIX 15   // ... with the mix prologue (the opt-in fused ModDown conversion): one group only
+#define HM_NTT_FUSED_SMALL 96   // transform launches of up to this many limb-polys of N = 2^16 run in the one-launch form by default (option ntt_fused_small)
+#define HM_NTT_MAX_LAUNCH_ENTRIES 448   // records of one transform launch (HM_NTT_MAX_ENTRIES, hm_ntt_core.h)
 
 struct HmCaps {
   uint32_t small_geometry;    // the 8-coefficient passes (k_ntt_col8 / k_ntt_row8), the one-launch transform (k_ntt_fused8), the small-launch transform x key kernel (k_ntt_row_ip8)
@@ -39,5 +41,11 @@ static inline int hm_cap_by_name(uint32_t logN, const char *name, uint64_t *valu
   if (!strcmp(name, "cap_bconv_col_pref_in")) { *value = c.bcol_pref_in; return 0; }
   if (!strcmp(name, "cap_ip_inverse_out")) { *value = c.ip_inverse_out; return 0; }
   if (!strcmp(name, "cap_col_slices")) { *value = c.col_slices; return 0; }
+  // the default limit of the one-launch transform in limb-polys of THIS ring (what decides is the number of workgroups: a smaller ring admits more)
+  if (!strcmp(name, "cap_ntt_fused_small")) {
+    const uint64_t v = logN <= 16 ? (uint64_t)HM_NTT_FUSED_SMALL << (16 - logN) : 0;
+    *value = c.small_geometry ? (v < HM_NTT_MAX_LAUNCH_ENTRIES ? v : HM_NTT_MAX_LAUNCH_ENTRIES) : 0;
+    return 0;
+  }
   return 1;
 }

@@ -119,6 +119,20 @@ struct HmEpi {  // the prologue / epilogue operands of one limb-poly, resolved b
   uint32_t g, logN;          // MODE 6 / 7: the Galois element the input / the addend is gathered through, and the ring size its index map needs
 };
 HM_HD HmEpi hm_epi_none() { return HmEpi{nullptr, nullptr, HmTw{0, 0}, nullptr, HmTw{0, 0}, 0, 0, 0}; }
+// MODE 8 / 9 (the product operands): b is the second factor (MODE 8: the minuend is a (.) b, null = a plain minuend, wave-uniform; MODE 9: the input
+// is src (.) b) and bk carries the modulus's Barrett constants, bk.w = HmMod::mu, bk.ws = HmMod::sh (neither mode has a mix prologue in its own pass).
+// x y mod q, fully reduced, for x, y < q: hm_barrett on those constants.  [0, q): what a stored minuend / a stored input is, so everything behind
+// it is MODE 3's / the plain inverse pass's
+HM_HD uint64_t hm_epi_mul(uint64_t x, uint64_t y, uint64_t q, const HmEpi &ep) {
+  HmMod m = {};
+  m.q = q; m.mu = ep.bk.w; m.sh = (uint32_t)ep.bk.ws;
+  return hm_barrett((hm_u128)x * y, m);
+}
+// The extension of a launch's entry table for MODE 8 / 9 (behind its n_limbs HmNttEntry records, same device allocation): per entry the address of
+// the second factor's limb-poly (null: MODE 8 only, a plain minuend)
+struct HmNttMulEntry {
+  const uint64_t *b;
+};
 // Split-30 packed form (round 5): x < 2^60 stored as (x mod 2^30) | ((x >> 30) << 32) — the two 30-bit halves a base conversion multiplies
 // with, one per dword.  The inverse transforms that feed ONLY base conversions (ModUp_DecompOut, ModDownBConvStep1: src/Operation.cpp:
 // 104-135, 447-487) store this form (two instructions per value, once), and every conversion workgroup that reads the value (one per pair

@@ -267,18 +267,36 @@ HM_HD void hm_ph_load_global_mix(HmNttState &st, int tid, const uint64_t *g, uin
   }
 }
 
+// MODE 9: the input is the product of two stored limb-polys, src (.) ep.b, both reduced: hm_epi_mul leaves [0, q), the range a stored input has
+// (the first inverse butterfly accepts [0, 4q)).  The second factor is requested with the first, unit by unit
+template <int TL, int LOGR, bool STRIDED, int R, int AUX = 0>
+HM_HD void hm_ph_load_global_mul(HmNttState &st, int tid, const uint64_t *g, uint32_t tile, uint64_t q, const HmEpi &ep) {
+  using G = HmRound<TL, LOGR, STRIDED, R>;
+#pragma unroll
+  for (int a = 0; a < HM_UNITS; ++a) {
+    int i0, i1, x, c;
+    G::unit(tid, a, i0, i1, x, c);
+    uint64_t p0, p1, b0, b1;
+    hm_gld2<G, AUX>(g, tile, tid, a, p0, p1);
+    hm_gld2<G, AUX>(ep.b, tile, tid, a, b0, b1);
+    st.v[i0] = hm_epi_mul(p0, b0, q, ep);
+    st.v[i1] = hm_epi_mul(p1, b1, q, ep);
+  }
+}
+
 // MODE 5 (ROW pass of the fused transform x key inner product): the last pass keeps its results in registers (lazy, below
 // 2 HM_LAZY_Q q) and stores nothing; hm_ph_mac consumes them.
 // the epilogue of one coefficient.  MODE 0 / 4 / 6: store as is (lazy values, hand-off between the two passes; 4 = first
 // pass with the mix prologue, 6 = inverse first pass whose input is read through an automorphism); 1: forward final, reduce [0, 2 HM_LAZY_Q q) -> [0,q); 2: inverse final, multiply by the per-limb
 // constant and reduce to [0,q); 3: forward final fused with out = (minuend - x) * k [+ addend [* ak]]; 7: the same with the addend read through an
-// automorphism (hm_ph_store_global gathers it)
+// automorphism (hm_ph_store_global gathers it); 8: MODE 3 with a product minuend (hm_ph_store_global forms va = a (.) b with hm_epi_mul: va in [0, q), a
+// stored minuend's range, so the bound below holds unchanged); 9: inverse first pass with a product input (hm_ph_load_global_mul), stores as MODE 0
 // (sc, ep.dk, ep.bk: constant records made by hm_kconst on the host; hm_kmul multiplies by them)
 template <int MODE>
 HM_HD uint64_t hm_epilogue(uint64_t a, uint64_t va, uint64_t vd, uint64_t q, HmTw sc, const HmEpi &ep) {
   if (MODE == 1) return hm_reduce_fwd(a, q);
   if (MODE == 2) { a = hm_kmul(a, sc, q); return ep.pack ? hm_pack30(a) : a; }
-  if (MODE == 3 || MODE == 7) {  // a in [0, 2 HM_LAZY_Q q): minuend - a + 2 HM_LAZY_Q q stays positive and below 9q < 2^64 (mont32: 5q < 2^63); the product reduces it
+  if (MODE == 3 || MODE == 7 || MODE == 8) {  // a in [0, 2 HM_LAZY_Q q): minuend - a + 2 HM_LAZY_Q q stays positive and below 9q < 2^64 (mont32: 5q < 2^63); the product reduces it
     a = hm_kmul(va + 2 * HM_LAZY_Q * q - a, sc, q);
     if (ep.d) a = hm_addmod(a, ep.dk.w ? hm_kmul(vd, ep.dk, q) : vd, q);
   }
@@ -295,6 +313,19 @@ HM_HD void hm_ph_store_global(const HmNttState &st, int tid, uint64_t *g, uint32
     uint64_t ea[2 * CH], ed[2 * CH];
 #pragma unroll
     for (int k = 0; k < 2 * CH; ++k) ea[k] = ed[k] = 0;
+    if constexpr (MODE == 8) {   // the product minuend: both factors requested together, as late as the plain minuend is; va = a (.) b < q
+      uint64_t eb[2 * CH];
+#pragma unroll
+      for (int k = 0; k < CH && a2 + k < HM_UNITS; ++k) {
+        hm_gld2<G>(ep.a, tile, tid, a2 + k, ea[2 * k], ea[2 * k + 1]);
+        if (ep.b) hm_gld2<G>(ep.b, tile, tid, a2 + k, eb[2 * k], eb[2 * k + 1]);
+        if (ep.d) hm_gld2<G>(ep.d, tile, tid, a2 + k, ed[2 * k], ed[2 * k + 1]);
+      }
+      if (ep.b) {
+#pragma unroll
+        for (int k = 0; k < 2 * CH && a2 + k / 2 < HM_UNITS; ++k) ea[k] = hm_epi_mul(ea[k], eb[k], q, ep);
+      }
+    }
     if (MODE == 3 || MODE == 7) {
 #pragma unroll
       for (int k = 0; k < CH && a2 + k < HM_UNITS; ++k) {
@@ -321,7 +352,7 @@ HM_HD void hm_ph_store_global(const HmNttState &st, int tid, uint64_t *g, uint32
                  hm_epilogue<MODE>(st.v[i1], ea[2 * k + 1], ed[2 * k + 1], q, sc, ep));
     }
 #if defined(__HIP_DEVICE_COMPILE__)
-    if (MODE == 3 || MODE == 7) __builtin_amdgcn_sched_barrier(0);
+    if (MODE == 3 || MODE == 7 || MODE == 8) __builtin_amdgcn_sched_barrier(0);
 #endif
   }
 }
@@ -448,6 +479,7 @@ HM_HD void hm_ntt_phase(HmNttState &st, int tid, uint64_t *lds, const uint64_t *
     if (FROMREG) { static_assert(!FROMREG || MODE != 4, "the mix prologue reads its operands from memory"); }
     else if (MODE == 4) hm_ph_load_global_mix<TL, LOGR, STRIDED, r0, LDAUX>(st, tid, src, tile, q, ep);
     else if constexpr (MODE == 6) hm_ph_load_global_auto<TL, LOGR, STRIDED, r0, LDAUX>(st, tid, src, tile, ep);
+    else if constexpr (MODE == 9) hm_ph_load_global_mul<TL, LOGR, STRIDED, r0, LDAUX>(st, tid, src, tile, q, ep);
     else hm_ph_load_global<TL, LOGR, STRIDED, r0, LDAUX>(st, tid, src, tile);
     // the twist constants are requested one phase ahead of the twisted round (phase iTW + 1)
     if (iTW >= 0 && iTW <= 1) hm_ph_load_twist<TL, LOGR, STRIDED, (TWR >= 0 ? TWR : 0)>(st, tid, twist_tile);
@@ -475,7 +507,7 @@ HM_HD void hm_ntt_phase(HmNttState &st, int tid, uint64_t *lds, const uint64_t *
     constexpr int rl = PS::exec(n - 1);
     // fused epilogue (MODE 3) / register hand-over (MODE 5): the twist constants are dead before the last round's twiddles are
     // read from LDS (the other order keeps 12 more registers alive and spilled inside the one-launch transform)
-    constexpr bool TWIST_FIRST = (MODE == 3 || MODE == 5 || MODE == 7) && !INV && rl == TWR && PS::fromLds(rl);
+    constexpr bool TWIST_FIRST = (MODE == 3 || MODE == 5 || MODE == 7 || MODE == 8) && !INV && rl == TWR && PS::fromLds(rl);
     if (PS::fromLds(rl) && !TWIST_FIRST) hm_ph_load_tw<TL, LOGR, STRIDED, rl, PS::shared(rl)>(st, tid, ltw, s0, prefix0);
     hm_ph_load_lds<TL, LOGR, STRIDED, rl, INV>(st, tid, lds);
     if (!INV && rl == TWR) hm_ph_twist(st, q);

@@ -24,7 +24,7 @@ SYMBOLS = [
     "hm_set_option", "hm_get_counter", "hm_ntt_inner_product", "hm_exchange_stream", "hm_exchange_mark", "hm_exchange_wait",
     "hm_bconv_col", "hm_limbs_to_colslices", "hm_colslices_to_limbs", "hm_ntt_second_pass", "hm_ntt_ex", "hm_capability", "hm_inner_product_ex",
     "hm_inner_product_hoisted", "hm_inner_product_lintrans", "hm_inner_product_rotsum", "hm_inner_product_lintrans_multi",
-    "hm_tensor_dot", "hm_inner_product_lintrans_id", "hm_inner_product_rotsum_init",
+    "hm_tensor_dot", "hm_inner_product_lintrans_id", "hm_inner_product_rotsum_init", "hm_ntt_mix_sub_scale_mul", "hm_ntt_mul",
 ]
 
 
@@ -95,6 +95,14 @@ class hm_ntt_desc(C.Structure):
                 ("in_galois", C.c_void_p)]
 
 
+class hm_ntt_fused_mul_desc(C.Structure):
+    _fields_ = [("t", hm_ntt_fused_desc), ("minuend_b", C.c_void_p), ("minuend_b_limbs", C.c_void_p)]
+
+
+class hm_ntt_mul_desc(C.Structure):
+    _fields_ = [("t", hm_ntt_desc), ("in_b", C.c_void_p), ("in_b_limbs", C.c_void_p)]
+
+
 class hm_params(C.Structure):
     _fields_ = [("logN", C.c_uint32), ("L", C.c_uint32), ("K", C.c_uint32), ("device", C.c_int32),
                 ("q", C.c_void_p), ("p", C.c_void_p), ("psi", C.c_void_p)]
@@ -141,6 +149,8 @@ def load():
     L.hm_inner_product_lintrans_id.argtypes = [vp, C.POINTER(hm_ip_lintrans_id_desc)]
     L.hm_ntt_sub_scale.argtypes = [vp] + [vp] * 9 + [u32, vp]
     L.hm_ntt_mix_sub_scale.argtypes = [vp, C.POINTER(hm_ntt_fused_desc)]
+    L.hm_ntt_mix_sub_scale_mul.argtypes = [vp, C.POINTER(hm_ntt_fused_mul_desc)]
+    L.hm_ntt_mul.argtypes = [vp, C.POINTER(hm_ntt_mul_desc)]
     L.hm_tensor.argtypes = [vp] + [vp] * 15 + [u32]
     L.hm_tensor_dot.argtypes = [vp] + [vp] * 15 + [u32, u32]
     L.hm_inner_product.argtypes = [vp] + [vp] * 7 + [u32, u32, u32]
@@ -293,6 +303,15 @@ class Context:
         d = hm_ntt_desc(src.ptr, pi, dst.ptr, po, pm, n, 1 if inverse else 0, ps, 0, None if pk is None else pk.ctypes.data_as(C.c_void_p), pg)
         self._ck(self.L.hm_ntt_ex(self.h, C.byref(d)))
 
+    def ntt_mul(self, src, in_b, dst, mod_ids, in_limbs=None, in_b_limbs=None, out_limbs=None, scale=None, out_packed=None):
+        """dst = INTT(src (.) in_b) * N^-1 [* scale]: the product is formed while the first pass loads (hm_ntt_mul: the inverse transform)"""
+        keep = [_u32(x) for x in (in_limbs, out_limbs, mod_ids, in_b_limbs)]
+        k4, ps = _u64(scale)
+        pk = None if out_packed is None else np.ascontiguousarray(np.asarray(out_packed, dtype=np.uint8))
+        d = hm_ntt_mul_desc(hm_ntt_desc(src.ptr, keep[0][1], dst.ptr, keep[1][1], keep[2][1], len(mod_ids), 1, ps, 0,
+                                        None if pk is None else pk.ctypes.data_as(C.c_void_p), None), in_b.ptr, keep[3][1])
+        self._ck(self.L.hm_ntt_mul(self.h, C.byref(d)))
+
     def ntt_sub_scale(self, src, minuend, out, mod_ids, k, addend=None, in_limbs=None, minuend_limbs=None, addend_limbs=None,
                       out_limbs=None):
         keep = [_u32(x) for x in (in_limbs, minuend_limbs, addend_limbs, out_limbs, mod_ids)]
@@ -300,11 +319,9 @@ class Context:
         self._ck(self.L.hm_ntt_sub_scale(self.h, src.ptr, keep[0][1], minuend.ptr, keep[1][1], None if addend is None else addend.ptr,
                                          keep[2][1], out.ptr, keep[3][1], keep[4][1], len(mod_ids), pk))
 
-    def ntt_mix_sub_scale(self, src, minuend, out, mod_ids, k, mix=None, mix_k=None, addend=None, addend_k=None, in_limbs=None,
-                          mix_limbs=None, minuend_limbs=None, addend_limbs=None, out_limbs=None, conv=None, addend_galois=None):
-        """out = (minuend - NTT(src + mix_k * mix)) * k + addend * addend_k (merged ModDown + rescale of one limb).
-        conv = [(src, in_limbs, in_ids, out_limbs_of_the_fed_limb_polys, out_ids), ...]: `src` of those limb-polys is this base conversion,
-        computed inside the transform's first pass (src may then be None)"""
+    def _fused_desc(self, src, minuend, out, mod_ids, k, mix=None, mix_k=None, addend=None, addend_k=None, in_limbs=None, mix_limbs=None,
+                    minuend_limbs=None, addend_limbs=None, out_limbs=None, conv=None, addend_galois=None):
+        """(hm_ntt_fused_desc, what it points to: keep alive until the call has returned)"""
         keep = [_u32(x) for x in (in_limbs, mix_limbs, minuend_limbs, addend_limbs, out_limbs, mod_ids)]
         ks = [_u64(x) for x in (mix_k, addend_k, k)]
         kg = _u32(addend_galois)   # per limb: read the addend through the automorphism X -> X^g
@@ -321,7 +338,25 @@ class Context:
         d = hm_ntt_fused_desc(ptr(src) if src is not None else out.ptr, keep[0][1], ptr(mix), keep[1][1], ks[0][1], minuend.ptr, keep[2][1], ptr(addend), keep[3][1], ks[1][1],
                               out.ptr, keep[4][1], keep[5][1], len(mod_ids), ks[2][1], C.cast(descs, C.c_void_p) if conv else None, len(conv) if conv else 0,
                               kg[1])
+        return d, (keep, ks, kg, descs, keep2)
+
+    def ntt_mix_sub_scale(self, src, minuend, out, mod_ids, k, mix=None, mix_k=None, addend=None, addend_k=None, in_limbs=None,
+                          mix_limbs=None, minuend_limbs=None, addend_limbs=None, out_limbs=None, conv=None, addend_galois=None):
+        """out = (minuend - NTT(src + mix_k * mix)) * k + addend * addend_k (merged ModDown + rescale of one limb).
+        conv = [(src, in_limbs, in_ids, out_limbs_of_the_fed_limb_polys, out_ids), ...]: `src` of those limb-polys is this base conversion,
+        computed inside the transform's first pass (src may then be None)"""
+        d, keep = self._fused_desc(src, minuend, out, mod_ids, k, mix, mix_k, addend, addend_k, in_limbs, mix_limbs, minuend_limbs, addend_limbs,
+                                   out_limbs, conv, addend_galois)
         self._ck(self.L.hm_ntt_mix_sub_scale(self.h, C.byref(d)))
+
+    def ntt_mix_sub_scale_mul(self, src, minuend, minuend_b, out, mod_ids, k, minuend_b_limbs=None, mix=None, mix_k=None, addend=None, addend_k=None,
+                              in_limbs=None, mix_limbs=None, minuend_limbs=None, addend_limbs=None, out_limbs=None):
+        """out = (minuend (.) minuend_b - NTT(src + mix_k * mix)) * k + addend * addend_k: ntt_mix_sub_scale with a product minuend formed while the
+        epilogue loads (hm_ntt_mix_sub_scale_mul); NO_LIMB in minuend_b_limbs = a plain minuend for that limb-poly"""
+        d, keep = self._fused_desc(src, minuend, out, mod_ids, k, mix, mix_k, addend, addend_k, in_limbs, mix_limbs, minuend_limbs, addend_limbs, out_limbs)
+        kb = _u32(minuend_b_limbs)
+        m = hm_ntt_fused_mul_desc(d, minuend_b.ptr, kb[1])
+        self._ck(self.L.hm_ntt_mix_sub_scale_mul(self.h, C.byref(m)))
 
     def tensor(self, a, b, c, d, o0, o1, o2, mod_ids, limbs=None):
         ls = limbs or [None] * 7

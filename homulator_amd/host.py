@@ -236,6 +236,12 @@ class Op:
         self._ck(self.L.hh_op_read_buffer_copy(self.h, name.encode(), copy, out.ctypes.data_as(C.c_void_p)))
         return out
 
+    def output_level(self):
+        """limbs of the output ciphertext (out.c0): the input's level, one less behind a rescale (hmult, hdot, hrescale, rescale = 1)"""
+        n = C.c_uint32()
+        self._ck(self.L.hh_op_buffer_limbs(self.h, b"out.c0", C.byref(n)))
+        return n.value
+
     @property
     def batch(self):
         return self.L.hh_op_batch(self.h)

@@ -129,6 +129,9 @@ private:
   bool fuseBsgs = true;      // pass (6m): ... and M >= 2 such sums over the same rotations share the key products (hbsgs)
   bool fuseRotsum = true;    // pass (6s): the key products of rotations of different ciphertexts are summed before anything is stored (hrotsum)
   bool fuseDot = true;       // pass (5d): the tensor products of several pairs of ciphertexts are summed before anything is stored (hdot)
+  bool fusePmulRescale = true;   // pass (4p): a product of two op inputs read by one transform is formed by that transform (pmult with rescale = 1)
+  bool fusePmulAuto = true;      // ... the key is not given: the pass declines where it was measured no faster (the generic back-end's small launches)
+  bool genericArith = false;     // config key chain_bits: the chain hm_create serves with the generic arithmetic back-end
   uint32_t n = 0, logN = 0, clusterCount = 1;
   uint32_t maxLevel_ = 0, curLevel_ = 0, world_ = 1, rank_ = 0;
   uint32_t batch_ = 1;  // config key `batch`: independent ops (own inputs, shared evaluation key) carried by every launch

@@ -52,6 +52,9 @@ public:
   // (12, round 6) an AUTO record folded into its readers: an INTT record reads its input, a fused forward transform its addend, through X -> X^g
   uint32_t inGalois = 0, fAddendGalois = 0;   // 0: as stored
   uint32_t ipXGalois = 0;                     // ... and a transform x key record its evaluation-form digits (hm_ntt_ip_desc.x_galois)
+  // (4p) product operands of transforms: an EWE_MUL of two op inputs folded into its one reader.  A fused forward transform's minuend is
+  // fMinuend * fMinuendB, an INTT record's input operandList[0] * inMulB.  0: a plain operand
+  AddrType fMinuendB = 0, inMulB = 0;
   bool fusedEpi = false;
   AddrType fSubFrom = 0, fAdd = 0;
   bool fusedTensor = false;            // MAC2 record that also produces d0 -> extraOutputs[0] and d2 -> extraOutputs[1]

@@ -103,7 +103,7 @@ private:
 public:
   Rescale(std::string labelName, uint32_t level, const std::vector<AddrType> &inputPolynomialAddress,
           std::vector<AddrType> *pool, std::map<AddrType, std::vector<Instruction *>> *map, InsGen *insgen,
-          AddrManage *memoryMange);
+          AddrManage *memoryMange, bool inputMayBeOpInput = false);   // inputMayBeOpInput: as KeySwitch::modUp's (HRESCALE)
   const StageList &getInsMap() const { return stages; }
   const std::vector<AddrType> &output() const { return out_; }  // <base>_Rescale_MulOut
 };
@@ -142,6 +142,10 @@ protected:
   // first (`op` names the op in the messages): no backend = sim,
   // no world > 1; config keys `rotations` = R (default 4, 1..16) and `galois` = g (default 5, odd, below 2N).  Returns g^r mod 2N, r = 1..R, distinct
   std::vector<uint32_t> hoistedRotations(const std::string &op) const;
+  // config key `rescale` (0 or 1, default 0; read by PMULT, HLINTRANS, HROTSUM, HBSGS): the op's result goes through Rescale, DESIGN.md section 17
+  bool rescaleKey(const std::string &op) const;
+  // <out>.c<k> = Rescale(ct[k]), builder labels <label>_<k>, as HMULT's tail: the tail of the ops with rescale = 1, and all of HRESCALE
+  void setRescaledOutput(const std::string &out, const std::array<std::vector<AddrType>, 2> &ct, bool inputMayBeOpInput = false);
   std::vector<AddrType> alloc(const std::string &name, uint32_t limbs);  // MallocMem + getAddr
   std::vector<AddrType> component(uint32_t ct, uint32_t k) const { return k == 0 ? cts[ct].getC0Addr() : cts[ct].getC1Addr(); }  // c_k of input ct
   void setOutput(const std::string &out, uint32_t k, const std::vector<AddrType> &limbs) { namedOutputs[out + ".c" + std::to_string(k)] = limbs; }
@@ -168,7 +172,7 @@ protected:
   // `c1Addend` (the identity step's W): c1 = the ModDown's output 1 + it in stage <op>_Hadd1<suffix>, buffer <op>Output<suffix>(1)
   SwitchedSum sumDown(KeySwitch &ks, const std::array<Limbs, 3> &sums, const std::string &op, const std::string &buffer, const std::string &suffix,
                       const Limbs *c1Addend = nullptr);
-  void setOutput(const std::string &out, const SwitchedSum &ct);
+  void setOutput(const std::string &out, const SwitchedSum &ct, bool rescale = false);   // rescale: through setRescaledOutput
 
 public:
   virtual ~OperationBase();
@@ -241,6 +245,12 @@ class PMULT : public OperationBase {
 public:
   PMULT(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
 };
+// hrescale (build extension): out = Rescale of both components of ct1, at level - 1; the rescale of HMULT's tail as an op of its own, for what
+// PMULT and the summing ops leave at scale Delta^2 (they take it themselves with rescale = 1)
+class HRESCALE : public OperationBase {
+public:
+  HRESCALE(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
+};
 class PADD : public OperationBase {
 public:
   PADD(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
@@ -256,7 +266,7 @@ class OpChain {
   std::vector<Arch *> archs;
   std::vector<OperationBase *> ops;
 public:
-  // ops: comma-separated list of hmult | hrotate | hadd | pmult | padd | hlintrans | hdot | hrotsum | hbsgs, e.g. "hmult,hrotate,hadd,hmult"; hrotate_hoisted (R output
+  // ops: comma-separated list of hmult | hrotate | hadd | pmult | padd | hlintrans | hdot | hrotsum | hbsgs | hrescale, e.g. "hmult,hrotate,hadd,hmult"; hrotate_hoisted (R output
   // ciphertexts) only as the last op
   OpChain(const std::string &cfgPath, const std::string &opList, uint32_t maxLevel, uint32_t curLevel, uint32_t alpha,
           const std::map<std::string, uint32_t> &overrides = {});

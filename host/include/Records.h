@@ -34,6 +34,8 @@ enum class Role {
   SumInit,        // ... with initial sums: the polynomial S_k starts from
   SumAddendInit,  // ... and the one the addend sum starts from
   Minuend, Addend, Mix,   // fused forward transform (4, 4b)
+  MinuendMul,             // ... (4p) the second factor of a minuend that is a product
+  InttMul,                // (4p) the second factor of an inverse transform's input that is a product
   EpiSub, EpiAdd,         // conversion with the element-wise epilogue (10): fSubFrom, fAdd
   ReplacedIn      // the transform input operandList[0] that the fused conversion fConvIn replaces (9): never written, never loaded
 };
@@ -87,9 +89,11 @@ inline std::vector<Read> recordReads(const Instruction &i) {
     const Role r = !i.fConvIn.empty() ? Role::ReplacedIn : i.ops != INTT ? Role::Operand : i.secondOnly ? Role::SecondPassIn : Role::InttIn;
     v.push_back({i.operandList[0], r, kNoDigit});
     if (!i.fConvIn.empty()) v.push_back({i.fConvIn[0], Role::ConvIn, kNoDigit});
+    if (i.inMulB) v.push_back({i.inMulB, Role::InttMul, kNoDigit});
   }
   if (i.fusedSubScale) {
     v.push_back({i.fMinuend, Role::Minuend, kNoDigit});
+    if (i.fMinuendB) v.push_back({i.fMinuendB, Role::MinuendMul, kNoDigit});
     if (i.fAddend) v.push_back({i.fAddend, Role::Addend, kNoDigit});
     if (i.fMix) v.push_back({i.fMix, Role::Mix, kNoDigit});
   }

@@ -40,6 +40,7 @@ struct Arch::Launch {
   bool secondOnly = false;        // L_INTT (7b): hm_ntt_second_pass — the first pass was run by the inner-product kernel
   std::vector<uint8_t> outPacked; // L_INTT (11): per limb-poly, 1 = stored in the split-30 packed form of the conversions' inputs
   std::vector<uint32_t> inGalois, addGalois;   // (12) L_INTT: per limb-poly, the input / L_NTT_SUBSCALE: the addend is read through X -> X^g (0: as stored); empty: none
+  std::vector<uint32_t> mulB;                  // (4p) L_INTT: the input, L_NTT_SUBSCALE: the minuend is the product with this limb-poly (hm_ntt_mul / hm_ntt_mix_sub_scale_mul); empty: none
   uint32_t xGalois = 0;                        // (12) L_NTT_IP: the evaluation-form digits, L_IP: the x operands are read through X -> X^g
   uint32_t ipTerms = 0, ipOuts = 0;
                                   // L_IP_ROTSUM: hoistG = the element of every ciphertext; a: digits [c][n][T], b: keys [c][n][2][T], d: addend sources
@@ -145,6 +146,12 @@ Arch::Arch(Config *cfg) : config(cfg) {
   // (5d) hdot: the tensor product of pair 1 and the multiply-accumulate chains of the further pairs become one hm_tensor_dot launch.  Config key
   // fuse_dot (default 1).
   fuseDot = cfg->getValueOr("fuse_dot", 1) != 0;
+  // (4p) pmult with rescale = 1: the products are formed by the rescale's transforms while they load.  Config key fuse_pmul_rescale: 1 / 0 = always /
+  // never; not given = where it was measured faster than the three-launch plan: everywhere but the generic back-end's launches
+  // inside the one-launch form's limit, which has no product form there (Planner::productOperands)
+  fusePmulRescale = cfg->getValueOr("fuse_pmul_rescale", 1) != 0;
+  fusePmulAuto = !cfg->hasKey("fuse_pmul_rescale");
+  genericArith = cfg->getValueOr("chain_bits", 0) != 0;
   // (6s) hrotsum: the key products of rotations of different ciphertexts, the sums over the ciphertexts and the rotated c0's become one
   // hm_inner_product_rotsum launch.  Config key fuse_rotsum (default 1).
   fuseRotsum = cfg->getValueOr("fuse_rotsum", 1) != 0;
@@ -302,11 +309,12 @@ int partKey(const Instruction &i) {
   if (isKeyProduct(i)) return 300 + (int)i.ipX.size() * 10 + (int)i.ipY.size();                            // 300+: key product, by digits and keys
   if (!i.dotOperands.empty()) return 8000 + (int)i.dotOperands.size() / 4;                                 // 8000+: sum of tensor products, by pairs
   if (i.fusedTensor) return 200;                                                                           // 200: tensor product
+  if (i.fusedSubScale && i.fMinuendB) return i.fMix ? 211 : 209;                                           // 209 / 211: ... with a product minuend (4p)
   if (i.fusedSubScale) return (i.fMix ? 203 : 201) + (i.fConvIn.empty() ? 0 : 4);                          // 201 / 203: fused forward transform, plain / merged; 205 / 207: with its conversion
   if (i.ops == MULT) return 100 + i.opcode;                                                                // 100+: element-wise, by opcode
   if (i.ops == NTT && i.passthrough) return 100 + EWE_COPY;                                                //       (unfused: a pass-through transform is a copy)
   if (i.ops == AUTO) return 1000 + (int)i.galois;                                                          // 1000+: automorphism, by element
-  return (int)i.ops + (i.secondOnly ? 5000 : 0);                                                           // below 100: by op; 5000+: second pass only (7b)
+  return (int)i.ops + (i.secondOnly ? 5000 : 0) + (i.inMulB ? 5500 : 0);                                   // below 100: by op; 5000+: second pass only (7b); 5500+: product input (4p)
 }
 
 // what the kernels of a record load: a fused conversion REPLACES the address it would have written (the passes count that one too)
@@ -585,6 +593,7 @@ void Arch::LaunchBuilder::nttSubScale(Launch &L, Recs recs) {
   for (Instruction *i : recs) { anyAddend |= i->fAddend != 0; anyAddGalois |= i->fAddendGalois != 0; }
   for (Instruction *i : recs) {
     L.a.push_back(limb(i->operandList[0])); L.b.push_back(limb(i->fMinuend));
+    if (recs[0]->fMinuendB) L.mulB.push_back(limb(i->fMinuendB));   // the part key keeps product and plain minuends apart
     if (anyAddend) L.c.push_back(i->fAddend ? limb(i->fAddend) : HM_NO_LIMB);
     if (anyAddGalois) L.addGalois.push_back(i->fAddendGalois);
     L.out.push_back(limb(i->OutputOperand)); L.mods.push_back(i->mod_id); L.k.push_back(i->constant);
@@ -594,7 +603,7 @@ void Arch::LaunchBuilder::nttSubScale(Launch &L, Recs recs) {
     }
   }
   L.hasK = true;
-  L.bytes = (anyAddend ? 4 : 3) * LP * recs.size();
+  L.bytes = ((anyAddend ? 4 : 3) + (L.mulB.empty() ? 0 : 1)) * LP * recs.size();
   for (Instruction *i : recs) {   // (9): the conversion of this limb-poly runs inside its first pass
     if (i->fConvIn.empty()) continue;
     bool added;
@@ -625,8 +634,9 @@ void Arch::LaunchBuilder::transform(Launch &L, Recs recs) {
     L.k.push_back(i->hasConstant ? i->constant : 1);
     L.hasK |= i->hasConstant;
     if (f->ops == INTT) L.outPacked.push_back(i->packedOut ? 1 : 0);
+    if (f->inMulB) L.mulB.push_back(limb(i->inMulB));   // (the part key keeps product and plain inputs apart)
   }
-  L.bytes = 2 * LP * recs.size();
+  L.bytes = (L.mulB.empty() ? 2 : 3) * LP * recs.size();
 }
 
 void Arch::LaunchBuilder::automorphism(Launch &L, Recs recs) {
@@ -1057,7 +1067,7 @@ void Arch::replicateForBatch() {
       }
       rep(l->a, true); rep(l->b, true); rep(l->c, true); rep(l->d, true);
       rep(l->out, true); rep(l->out1, true); rep(l->out2, true); rep(l->mods, false);
-      rep(l->inGalois, false); rep(l->addGalois, false);
+      rep(l->inGalois, false); rep(l->addGalois, false); rep(l->mulB, true);
       for (std::vector<uint64_t> *kv : {&l->k, &l->mixK, &l->addK}) {
         const size_t k0 = kv->size();
         for (uint32_t c = 1; c < batch_; ++c)
@@ -1189,6 +1199,7 @@ std::string Arch::planText() const {
       if (cnt) out += std::string(gv == &l->inGalois ? " auto_in=" : " auto_addend=") + std::to_string(cnt) + "/g" + std::to_string(g);
     }
     if (l->xGalois) out += " auto_x=g" + std::to_string(l->xGalois);
+    if (!l->mulB.empty()) out += " mul=1";   // pass 4p: the input (INTT) / the minuend (fused forward transform) is a product formed while loading
     if (!l->hoistG.empty()) {   // (6h): rotations of the hoisted key product and their elements
       out += " rot=" + std::to_string(l->hoistG.size()) + " g=";
       for (size_t r = 0; r < l->hoistG.size(); ++r) out += (r ? "," : "") + std::to_string(l->hoistG[r]);
@@ -1234,7 +1245,7 @@ std::string Arch::planDump() const {
     if (l->dotTerms) out += " terms=" + std::to_string(l->dotTerms);
     if (l->kind == Launch::L_IP_LINTRANS_MULTI) out += " multiOuts=" + std::to_string(l->multiOuts);   // (one sum: the line of L_IP_LINTRANS has no such field)
     vec("wait", l->waitSlots); vec("hoistG", l->hoistG); vec("ipCoeff", l->ipCoeff); vec("ipInv", l->ipInv); vec("outPacked", l->outPacked);
-    vec("inGalois", l->inGalois); vec("addGalois", l->addGalois);
+    vec("inGalois", l->inGalois); vec("addGalois", l->addGalois); vec("mulB", l->mulB);
     vec("idPt", l->idPt); vec("d1", l->d1);
     vec("a", l->a); vec("b", l->b); vec("c", l->c); vec("d", l->d); vec("out", l->out); vec("out1", l->out1); vec("out2", l->out2);
     vec("mods", l->mods); vec("inMods", l->inMods); vec("k", l->k); vec("mixK", l->mixK); vec("addK", l->addK);
@@ -1263,18 +1274,28 @@ void Arch::enqueue(Launch &l) {
     const bool anyPacked = std::find(l.outPacked.begin(), l.outPacked.end(), 1) != l.outPacked.end();
     hm_ntt_desc d = {pool, l.a.data(), pool, l.out.data(), l.mods.data(), cnt, 1, l.hasK ? l.k.data() : nullptr, l.secondOnly ? 1 : 0,
                      anyPacked ? l.outPacked.data() : nullptr, l.inGalois.empty() ? nullptr : l.inGalois.data()};
-    st = hm_ntt_ex(ctx, &d);
+    if (!l.mulB.empty()) {   // (4p): the inputs are products
+      const hm_ntt_mul_desc m = {d, pool, l.mulB.data()};
+      st = hm_ntt_mul(ctx, &m);
+    } else {
+      st = hm_ntt_ex(ctx, &d);
+    }
     break;
   }
   case Launch::L_NTT_SUBSCALE:
-    if (!l.mixK.empty() || !l.probs.empty() || !l.addGalois.empty()) {
+    if (!l.mixK.empty() || !l.probs.empty() || !l.addGalois.empty() || !l.mulB.empty()) {
       for (auto &q : l.probs)
         descs.push_back(hm_bconv_desc{pool, q.in.data(), q.inMods.data(), (uint32_t)q.in.size(), pool, q.out.data(), q.outMods.data(), (uint32_t)q.out.size(), 0,
                                     nullptr, nullptr, nullptr, nullptr, nullptr, q.inPacked ? 1u : 0u});
       hm_ntt_fused_desc d = {pool, l.a.data(), l.mixK.empty() ? nullptr : pool, l.mixK.empty() ? nullptr : l.d.data(), l.mixK.empty() ? nullptr : l.mixK.data(), pool, l.b.data(),
                              l.c.empty() ? nullptr : pool, l.c.empty() ? nullptr : l.c.data(), l.addK.empty() ? nullptr : l.addK.data(), pool, l.out.data(), l.mods.data(), cnt,
                              l.k.data(), descs.empty() ? nullptr : descs.data(), (uint32_t)descs.size(), l.addGalois.empty() ? nullptr : l.addGalois.data()};
-      st = hm_ntt_mix_sub_scale(ctx, &d);
+      if (!l.mulB.empty()) {   // (4p): the minuends are products
+        const hm_ntt_fused_mul_desc m = {d, pool, l.mulB.data()};
+        st = hm_ntt_mix_sub_scale_mul(ctx, &m);
+      } else {
+        st = hm_ntt_mix_sub_scale(ctx, &d);
+      }
     } else {
       st = hm_ntt_sub_scale(ctx, pool, l.a.data(), pool, l.b.data(), l.c.empty() ? nullptr : pool, l.c.empty() ? nullptr : l.c.data(), pool,
                             l.out.data(), l.mods.data(), cnt, l.k.data());

@@ -307,7 +307,7 @@ TensorCompute::TensorCompute(std::string labelName, uint32_t level, Ciphertext *
 // upstream; same buffer list, every stage writes its own buffer).
 // =====================================================================================================
 Rescale::Rescale(std::string labelName, uint32_t level, const std::vector<AddrType> &input, std::vector<AddrType> *,
-                 std::map<AddrType, std::vector<Instruction *>> *map, InsGen *insgen, AddrManage *mem) {
+                 std::map<AddrType, std::vector<Instruction *>> *map, InsGen *insgen, AddrManage *mem, bool inputMayBeOpInput) {
   Arch *arch = insgen->backend();  // upstream's signature (include/Operation.h:156-162)
   const std::string base = labelName + "_Rescale";
   if (level < 2) throw std::runtime_error("Rescale needs at least two limbs");
@@ -318,10 +318,12 @@ Rescale::Rescale(std::string labelName, uint32_t level, const std::vector<AddrTy
   const std::vector<AddrType> subOut = alloc(mem, base + "_Rescale_SubOut", last);
   out_ = alloc(mem, base + "_Rescale_MulOut", last);
   const std::vector<AddrType> nttOut = alloc(mem, base + "_Rescale_Mul_Offset", last);
+  // throws when the last limb has no producer, unless the input may be the op's own input ciphertext (HRESCALE), as KeySwitch::modUp
   auto prod = map->find(input[last]);
-  if (prod == map->end()) throw std::runtime_error("Error! This dependece need exists!\n\n");
+  if (prod == map->end() && !inputMayBeOpInput) throw std::runtime_error("Error! This dependece need exists!\n\n");
+  INSGROUP producer = prod == map->end() ? INSGROUP() : prod->second;
   const std::vector<INSGROUP> &intt =
-      stages.add("Rescale_INTT", {insgen->GenNTT(0, base + "_Rescale_INTT(0)_", &prod->second, false, input[last], r[0], last)});
+      stages.add("Rescale_INTT", {insgen->GenNTT(0, base + "_Rescale_INTT(0)_", &producer, false, input[last], r[0], last)});
 
   const uint64_t qlast = arch->modulus(last);
   std::vector<uint64_t> qlastInv;
@@ -444,6 +446,18 @@ bool OperationBase::identityStep(const std::string &op) const {
   if (id > 1) throw std::runtime_error(op + ": identity = " + S(id) + ", must be 0 or 1");
   return id == 1;
 }
+bool OperationBase::rescaleKey(const std::string &op) const {
+  const uint32_t rs = config->getValueOr("rescale", 0);
+  if (rs > 1) throw std::runtime_error(op + ": rescale = " + S(rs) + ", must be 0 or 1");
+  return rs == 1;
+}
+void OperationBase::setRescaledOutput(const std::string &out, const std::array<std::vector<AddrType>, 2> &ct, bool inputMayBeOpInput) {
+  for (uint32_t k = 0; k < 2; k++) {
+    Rescale res(label + "_" + S(k), level_, ct[k], &Datapool, &DataInsMap, &insgener, addrManager.get(), inputMayBeOpInput);
+    dispatch(res.getInsMap());
+    setOutput(out, k, res.output());
+  }
+}
 void OperationBase::finishRotation(const std::string &out, const std::vector<AddrType> &rotatedC0, const KeySwitch::Output &ks, const std::string &suffix) {
   PerLimb s{label + "_HROTATEadd" + suffix + "_Level(", ")", range(0, level_), alloc("HROTATEOutput" + suffix + "(1)", level_)};
   s.a = ks[0];
@@ -520,7 +534,8 @@ OperationBase::SwitchedSum OperationBase::sumDown(KeySwitch &ks, const std::arra
   }
   return {c0, down[1]};
 }
-void OperationBase::setOutput(const std::string &out, const SwitchedSum &ct) {
+void OperationBase::setOutput(const std::string &out, const SwitchedSum &ct, bool rescale) {
+  if (rescale) return setRescaledOutput(out, {ct.c0.addr, ct.c1});
   setOutput(out, 0, ct.c0.addr);
   setOutput(out, 1, ct.c1);
 }
@@ -728,7 +743,7 @@ HLINTRANS::HLINTRANS(std::string labelName, uint32_t maxLevel, uint32_t currentL
   // identity = 1: one more plaintext pt0 (stream seed + 4300) weights the UNROTATED ciphertext, which meets no key:
   //   U = pt0[Q] c0 + sum_r pt_r[Q] sigma_r(c0),   W = pt0[Q] c1,   out.c1 = W + ModDown(S_1)
   // 16 terms per accumulator at most, so rotations <= 15
-  const bool identity = identityStep("hlintrans");
+  const bool identity = identityStep("hlintrans"), rescale = rescaleKey("hlintrans");
   if (identity && R > 15) throw std::runtime_error("hlintrans: rotations = " + S(R) + " with identity = 1, must be in [1, 15]");
   makeInputs(1, /*plaintext=*/false, /*extPlaintexts=*/R, identity ? NamedStreams{{"pt0", 4300}} : NamedStreams{});
 
@@ -747,14 +762,14 @@ HLINTRANS::HLINTRANS(std::string labelName, uint32_t maxLevel, uint32_t currentL
   std::array<Limbs, 3> sums;
   if (!identity) {
     for (uint32_t t = 0; t < 3; ++t) sums[t] = weightedSum(t, terms[t], pts, "");
-    setOutput("out", sumDown(ks, sums, "HLINTRANS", "HLINTRANSOutput(0)", ""));
+    setOutput("out", sumDown(ks, sums, "HLINTRANS", "HLINTRANSOutput(0)", ""), rescale);
   } else {
     const Limbs c0{cts[0].getC0Addr(), {}}, c1{cts[0].getC1Addr(), {}};
     const std::vector<AddrType> &pt0 = namedInputs.at("pt0");
     for (uint32_t t = 0; t < 2; ++t) sums[t] = weightedSum(t, terms[t], pts, "");
     sums[2] = weightedSum(2, terms[2], pts, "", &c0, &pt0);
     const Limbs W = weightedSum(3, {}, {}, "", &c1, &pt0);
-    setOutput("out", sumDown(ks, sums, "HLINTRANS", "HLINTRANSOutput(0)", "", &W));
+    setOutput("out", sumDown(ks, sums, "HLINTRANS", "HLINTRANSOutput(0)", "", &W), rescale);
   }
   finishConstruction();
 }
@@ -834,6 +849,7 @@ HROTSUM::HROTSUM(std::string labelName, uint32_t maxLevel, uint32_t currentLevel
     : OperationBase("HROTSUM", labelName, cfg, _arch, maxLevel, currentLevel, alpha) {
   const std::vector<uint32_t> gs = hoistedRotations("hrotsum");
   const uint32_t G = (uint32_t)gs.size();
+  const bool rescale = rescaleKey("hrotsum");
   makeInputs(G);
 
   KeySwitch ks(labelName, maxLevel, currentLevel, alpha, &Datapool, &DataInsMap, &insgener, addrManager.get());
@@ -846,7 +862,7 @@ HROTSUM::HROTSUM(std::string labelName, uint32_t maxLevel, uint32_t currentLevel
     const std::array<Limbs, 3> term = {acc[0], acc[1], rotateComponent(0, gs[i - 1], rs, i - 1)};
     for (uint32_t t = 0; t < 3; ++t) sums[t] = i == 1 ? term[t] : addTerm(t, sums[t], term[t], "RotSum", i, i == G);
   }
-  setOutput("out", sumDown(ks, sums, "HROTSUM", "HROTSUMOutput(0)", ""));
+  setOutput("out", sumDown(ks, sums, "HROTSUM", "HROTSUMOutput(0)", ""), rescale);
   finishConstruction();
 }
 
@@ -871,7 +887,7 @@ HBSGS::HBSGS(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, ui
   // identity = 1: giant groups i = 0..G and baby steps r = 0..R with g_0 = h_0 = 1.  Group i's identity baby step is the
   // plaintext pt0_<i> (stream seed + 4300 + 100000 i), group 0's rotations are ptg<r> (seed + 4600 + 100000 r).  Group 0 is never brought
   // down on its own: its sums join the giant step's in front of the one final ModDown.  16 terms per accumulator at most
-  const bool identity = identityStep("hbsgs");
+  const bool identity = identityStep("hbsgs"), rescale = rescaleKey("hbsgs");   // rescale: behind the final ModDown only, never the inner groups
   if (identity && R > 15) throw std::runtime_error("hbsgs: rotations = " + S(R) + " with identity = 1, must be in [1, 15]");
   if (identity && G > 15) throw std::runtime_error("hbsgs: giants = " + S(G) + " with identity = 1, must be in [1, 15]");
   const uint32_t gNext = (uint32_t)((uint64_t)gs.back() * cfg->getValueOr("galois", 5) % twoN);
@@ -935,7 +951,7 @@ HBSGS::HBSGS(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, ui
   }
   // the group-0 term last, one ADD per tag; W_0 is the c1 addend behind the ModDown
   for (uint32_t t = 0; identity && t < 3; ++t) sums[t] = addTerm(t, sums[t], group0[t], "GiantSum", 0, true);
-  setOutput("out", sumDown(ks, sums, "HBSGS", "HBSGSOutput(0)", "", identity ? &W0 : nullptr));
+  setOutput("out", sumDown(ks, sums, "HBSGS", "HBSGSOutput(0)", "", identity ? &W0 : nullptr), rescale);
   finishConstruction();
 }
 
@@ -956,14 +972,32 @@ HADD::HADD(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint
 // reference: PMULT::PMULT :1460-1523
 PMULT::PMULT(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch)
     : OperationBase("PMULT", labelName, cfg, _arch, maxLevel, currentLevel, alpha) {
+  // rescale = 1: both products go through Rescale, out at level - 1
+  const bool rescale = rescaleKey("pmult");
+  if (rescale && arch->backend() == Arch::BACKEND_SIM) throw std::runtime_error("pmult: rescale = 1 on backend = sim is not supported (the reference's pmult has no rescale)");
+  if (rescale && arch->world() > 1) throw std::runtime_error("pmult: rescale = 1 with world > 1 is not supported (the sharded plan is not built)");
   makeInputs(1, /*plaintext=*/true);
+  std::array<std::vector<AddrType>, 2> prod;
   for (uint32_t k = 0; k < 2; k++) {
     PerLimb s{labelName + "_PMULT_Level(", ")_k(" + S(k) + ")", range(0, currentLevel), alloc("HMult" + S(k) + "Out", currentLevel)};
     s.a = component(0, k);
     s.b = ptx->getC0Addr();
     driver.dispatchInstructions("PMULT_Key(" + S(k) + ")", eweLimbs(&insgener, EWE_MUL, s));
-    setOutput("out", k, s.out);
+    prod[k] = s.out;
   }
+  if (rescale) setRescaledOutput("out", prod);
+  else for (uint32_t k = 0; k < 2; k++) setOutput("out", k, prod[k]);
+  finishConstruction();
+}
+
+// hrescale (build extension): out = (Rescale(ct1.c0), Rescale(ct1.c1)) at level - 1, the two Rescale builders on the op's own
+// input ciphertext (no instruction produces it: inputMayBeOpInput, as the hoisted ModUps)
+HRESCALE::HRESCALE(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch)
+    : OperationBase("HRESCALE", labelName, cfg, _arch, maxLevel, currentLevel, alpha) {
+  if (arch->backend() == Arch::BACKEND_SIM) throw std::runtime_error("hrescale: backend = sim has no such op (the reference rescales only inside hmult)");
+  if (arch->world() > 1) throw std::runtime_error("hrescale: world > 1 is not supported (the sharded plan is not built)");
+  makeInputs(1);
+  setRescaledOutput("out", {component(0, 0), component(0, 1)}, /*inputMayBeOpInput=*/true);
   finishConstruction();
 }
 
@@ -995,6 +1029,7 @@ static OperationBase *makeOp(const std::string &o, uint32_t maxLevel, uint32_t l
   if (o == "hdot") return new HDOT("test_hdot", maxLevel, level, alpha, cfg, arch);
   if (o == "hrotsum") return new HROTSUM("test_hrotsum", maxLevel, level, alpha, cfg, arch);
   if (o == "hbsgs") return new HBSGS("test_hbsgs", maxLevel, level, alpha, cfg, arch);
+  if (o == "hrescale") return new HRESCALE("test_hrescale", maxLevel, level, alpha, cfg, arch);
   throw std::runtime_error("Error operation requirement, please double confirm!");
 }
 

@@ -100,6 +100,7 @@ struct Arch::Planner {
   void inttScale();        // 2
   void eweChains();        // 3
   void nttSubScale();      // 4
+  void productOperands();  // 4p
   void mergeRescale();     // 4b
   void residue();          // 4c
   void tensor();           // 5
@@ -139,6 +140,7 @@ void Arch::fusePasses(std::vector<Stage> &st) {
   p.inttScale();
   p.eweChains();
   p.nttSubScale();
+  if (fusePmulRescale && world_ == 1) p.productOperands();   // behind (4): it reads the fused transforms; in front of (4b): plain records stay (4b)'s
   p.mergeRescale();
   p.residue();
   p.tensor();
@@ -259,6 +261,49 @@ void Arch::Planner::nttSubScale() {
       t->refInstructions += i->refInstructions;
       producer[out] = t;
       dead.insert(i);
+    }
+}
+
+// (4p) product operands of transforms (pmult with rescale = 1): an EWE_MUL of two operands that nothing in the plan produces (op inputs), read
+//      by ONE record, is formed by that reader while it loads:
+//        a fused forward transform of (4) without conversion or gathered addend whose minuend it is: out = (a * b - NTT(x)) * k [+ addend];
+//        an inverse transform whose input it is: out = INTT(a * b) * N^-1 [* scale].
+//      The product limb-poly is never written nor read back.  The tensor MULs of hmult / hdot never match: (5) absorbs them later, and here
+//      their outputs are minuends of nothing ((4)'s minuend is the key-switch sum) or have a second reader.
+//      Reads: fusedSubScale / fMinuend (4).  Sets: fMinuendB + fMinuend on forward transforms, inMulB + operandList[0] on inverse transforms.
+void Arch::Planner::productOperands() {
+  Readers rd = readers();
+  if (A.fusePmulAuto && A.genericArith) {
+    // Not told either way, on the generic back-end: its one-launch transform has no product form (the extra operand costs that kernel a wave per
+    // SIMD), so a final launch inside the one-launch limit would trade the one-launch MODE 3 transform for two 16-coefficient kernels: measured
+    // equal to the three-launch plan.  The pass keeps out; larger launches are 16-coefficient kernels either way
+    size_t finals = 0;
+    for (auto &s : st)
+      for (Instruction *i : s.ins) finals += live(i) && i->ops == NTT && i->fusedSubScale && !i->passthrough;
+    if (finals * A.batch_ <= cap("cap_ntt_fused_small")) return;
+  }
+  auto productFor = [&](AddrType a, Instruction *reader) -> Instruction * {
+    Instruction *m = producerOf(a);
+    if (!m || !isMul(m, reader->mod_id) || m->fusedTensor || !onlyReader(rd, a, reader)) return nullptr;
+    if (producerOf(m->operandList[0]) || producerOf(m->operandList[1])) return nullptr;
+    return m;
+  };
+  for (auto &s : st)
+    for (Instruction *i : s.ins) {
+      if (!live(i) || i->passthrough) continue;
+      if (i->ops == NTT && i->fusedSubScale && !i->fMinuendB && i->fConvIn.empty() && !i->fAddendGalois) {
+        Instruction *m = productFor(i->fMinuend, i);
+        if (!m || m->operandList[0] == i->OutputOperand || m->operandList[1] == i->OutputOperand) continue;   // out doubles as first-pass scratch
+        i->fMinuend = m->operandList[0];
+        i->fMinuendB = m->operandList[1];
+        absorb(i, m);
+      } else if (i->ops == INTT && !i->secondOnly && !i->inGalois && !i->inMulB) {
+        Instruction *m = productFor(i->operandList[0], i);
+        if (!m) continue;
+        i->operandList[0] = m->operandList[0];
+        i->inMulB = m->operandList[1];
+        absorb(i, m);
+      }
     }
 }
 
@@ -909,7 +954,7 @@ void Arch::Planner::modDownConversion() {
   Readers rd = readers();
   for (auto &s : st)
     for (Instruction *t : s.ins) {
-      if (t->ops != NTT || !t->fusedSubScale || t->passthrough || dead.count(t)) continue;
+      if (t->ops != NTT || !t->fusedSubScale || t->passthrough || t->fMinuendB || dead.count(t)) continue;   // (a product minuend: not with a conversion)
       Instruction *cv = producerOf(t->operandList[0]);
       if (!cv || cv->ops != BCONV_STEP2 || dead.count(cv) || cv->mod_id != t->mod_id) continue;
       if (!onlyReader(rd, t->operandList[0], t) || cv->operandList.size() - 1 > (t->fMix ? maxMixIn : cap("cap_bconv_col_max_in"))) continue;
@@ -1020,8 +1065,8 @@ void Arch::Planner::foldAutomorphisms() {
         // a transform x key record reads its own digits in evaluation form, a plain inner-product record (no digit transformed inside) all of them
         // (any plan: a limb-poly's key product runs on the rank that owns the limb, and so does the automorphism's source limb)
         if (r.role == Role::IpDigit && !i->ipXGalois && i->ipHoistG.empty()) f = OWN_DIGIT;
-        else if (r.role == Role::InttIn && !i->inGalois) f = INTT_IN;
-        else if (r.role == Role::Addend && i->ops == NTT && !i->fMix && i->fConvIn.empty() && !i->fAddendGalois) f = ADDEND;
+        else if (r.role == Role::InttIn && !i->inGalois && !i->inMulB) f = INTT_IN;
+        else if (r.role == Role::Addend && i->ops == NTT && !i->fMix && i->fConvIn.empty() && !i->fAddendGalois && !i->fMinuendB) f = ADDEND;
         readers[r.addr].push_back({i, f, r.digit});
         if (f == OWN_DIGIT) ownDigits.push_back({i, f, r.digit});
       }

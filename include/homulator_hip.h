@@ -116,6 +116,17 @@ typedef struct hm_ntt_fused_desc {
   const uint32_t *addend_galois;
 } hm_ntt_fused_desc;
 hm_status hm_ntt_mix_sub_scale(hm_ctx *ctx, const hm_ntt_fused_desc *desc);
+/* The same with a minuend that is the PRODUCT of two stored limb-polys, formed while the epilogue loads (pmult followed by a rescale: PMULT_Key(k) +
+ * Rescale_NTT + Rescale_SUB + Rescale_Mul, src/Operation.cpp:1460-1523, 806-910, without the products in HBM):
+ *     out = (minuend (.) minuend_b - NTT(in [+ mix_k * mix])) * k  [+ addend [* addend_k]]
+ * minuend_b_limbs[i] == HM_NO_LIMB: a plain minuend for limb-poly i (minuend_b_limbs == NULL means 0, 1, .., n-1).  Not with conv or addend_galois
+ * (HM_ERR_UNSUPPORTED).  `out` must not alias `minuend_b` either (HM_ERR_ARG; compared by address range, not by base pointer).  Bit-identical to
+ * hm_ewe(HM_OP_MUL) into a temporary followed by hm_ntt_mix_sub_scale(&t) with that temporary as the minuend. */
+typedef struct hm_ntt_fused_mul_desc {
+  hm_ntt_fused_desc t;
+  const uint64_t *minuend_b; const uint32_t *minuend_b_limbs;
+} hm_ntt_fused_mul_desc;
+hm_status hm_ntt_mix_sub_scale_mul(hm_ctx *ctx, const hm_ntt_fused_mul_desc *desc);
 
 /* K2 — automorphism X -> X^galois in evaluation form.  Replaces issueIns(..., "AUTO", ...) for
  * InsGen::GenAUTO (src/InsGen.cpp:46-71).  in must not alias out. */
@@ -382,6 +393,16 @@ typedef struct hm_ntt_desc {
   const uint32_t *in_galois;
 } hm_ntt_desc;
 hm_status hm_ntt_ex(hm_ctx *ctx, const hm_ntt_desc *desc);
+/* The inverse transform of a PRODUCT of two stored limb-polys, formed while the first pass loads (the rescale residue of a plaintext product,
+ * PMULT_Key(k) + Rescale_INTT: src/Operation.cpp:1460-1523, 766-804): out_i = INTT(in_i (.) in_b_i) * N^-1 [* scale_i]; out_packed is honoured.
+ * Inverse only; not with second_pass_only or in_galois (HM_ERR_UNSUPPORTED).  in_b_limbs == NULL means 0, 1, .., n-1.  in == out is allowed as for
+ * hm_ntt; `out` must not overlap `in_b` (HM_ERR_ARG; compared by address range, not by base pointer).  Bit-identical to
+ * hm_ewe(HM_OP_MUL) into a temporary followed by hm_ntt_ex(&t) on that temporary. */
+typedef struct hm_ntt_mul_desc {
+  hm_ntt_desc t;
+  const uint64_t *in_b; const uint32_t *in_b_limbs;
+} hm_ntt_mul_desc;
+hm_status hm_ntt_mul(hm_ctx *ctx, const hm_ntt_mul_desc *desc);
 
 /* K4 — fast base conversion, matrix step: out_t = sum_i in_i * [Q_D / q_i]_t mod t for the input
  * basis in_ids (n_in <= 32) and output basis out_ids (n_out <= 64).  `in` must already hold
@@ -540,6 +561,7 @@ hm_status hm_set_option(hm_ctx *ctx, const char *name, uint64_t value);
  *   "cap_bconv_col_max_in_mix"  ... when the conversion carries the mix prologue (hm_ntt_fused_desc.conv with mix)
  *   "cap_ip_inverse_out"        1: hm_ntt_ip_desc.out_inverse is served
  *   "cap_col_slices"            ranks the column tiles of a limb-poly can be dealt to (hm_limbs_to_colslices / hm_bconv_col with a tile range)
+ *   "cap_ntt_fused_small"       transform launches of up to this many limb-polys run in the one-launch form by default (option ntt_fused_small); 0: none
  * Replaces: nothing upstream — the reference sizes its units from the .cfg (src/Arch.cpp:8-168) and has one shape of each. */
 hm_status hm_capability(uint32_t logN, const char *name, uint64_t *value);
 hm_status hm_get_counter(hm_ctx *ctx, const char *name, uint64_t *value); /* synchronises */
