@@ -25,6 +25,7 @@
 #include "hm_caps.h"
 #include "hm_launch.h"
 #include "hm_bconv_plan.h"
+#include "hm_table_cache.h"
 
 // ------------------------------------------------------------------------------------------------
 // kernels
@@ -671,6 +672,21 @@ __global__ void __launch_bounds__(256) k_fill(HmFillArgs a) {
 // ------------------------------------------------------------------------------------------------
 // context
 // ------------------------------------------------------------------------------------------------
+// the launch-table cache's (hm_table_cache.h) way to the device: hipError_t values as its backend status
+struct HipTables {
+  hipStream_t stream;
+  int upload(const void *data, size_t bytes, void **dev) {
+    hipError_t e = hipMalloc(dev, bytes);
+    if (e == hipSuccess && (e = hipMemcpy(*dev, data, bytes, hipMemcpyHostToDevice)) != hipSuccess) { (void)hipFree(*dev); *dev = nullptr; }
+    return (int)e;
+  }
+  void release(void *dev) { (void)hipFree(dev); }
+  int wait() { return (int)hipStreamSynchronize(stream); }
+  bool stream_capturing() {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    return hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+  }
+};
 struct hm_ctx {
   hm::Params P;
   int device = 0;
@@ -680,11 +696,10 @@ struct hm_ctx {
   HmW *d_twist_fwd = nullptr, *d_twist_inv = nullptr;  // [L+K][N/256][3], hm::Params::make_twist
   HmMod *d_mods = nullptr;
   std::map<std::vector<uint32_t>, uint64_t *> bconv_tables;  // key: n_in, in_ids..., out_ids...
-  std::map<std::string, void *> launch_tables;                  // launch tables (device_table), key: their bytes
-  int live_graphs = 0;                                        // captured graphs that reference the tables: no eviction while > 0
+  // launch tables (device_table): device copies keyed by their bytes, pinned while a graph captured from this context lives or is being recorded
+  HmTableCache<HipTables> tables;
   // ... the graphs themselves: hm_destroy detaches them (a late hm_graph_destroy must not touch a freed context)
   std::vector<struct hm_graph *> graphs;
-  bool capturing = false;
   std::string err;
   // one-launch transforms (k_ntt_fused): rendezvous words in HBM, a host-visible error word, and the switch
   HmNttSync *ntt_ws = nullptr;
@@ -901,7 +916,7 @@ extern "C" void hm_destroy(hm_ctx *c) {
   if (c->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(c->comm);
   (void)hipFree(c->stage_send);
   (void)hipFree(c->stage_recv);
-  for (auto &kv : c->launch_tables) (void)hipFree(kv.second);
+  { HipTables b{c->stream}; c->tables.clear(b); }
   (void)hipFree(c->d_tw_fwd);
   (void)hipFree(c->d_tw_inv);
   (void)hipFree(c->d_twist_fwd);
@@ -1036,6 +1051,11 @@ extern "C" hm_status hm_set_option(hm_ctx *c, const char *name, uint64_t value) 
   if (!strcmp(name, "ntt_fused_trace")) { c->fused_trace = reinterpret_cast<unsigned long long *>((uintptr_t)value); return HM_OK; }
 #endif
   if (!strcmp(name, "ntt_fused_test_timeout")) { c->fused_test_timeout = value != 0; return HM_OK; }
+  if (!strcmp(name, "launch_table_limit")) {   // test hook: tables the cache keeps before it starts over (HM_LAUNCH_TABLE_LIMIT)
+    if (value < 1) return fail(c, HM_ERR_ARG, "hm_set_option: launch_table_limit is at least 1");
+    c->tables.limit = (size_t)value;
+    return HM_OK;
+  }
   if (!strcmp(name, "ntt_fused_small")) {
     if (value > HM_NTT_MAX_ENTRIES) return fail(c, HM_ERR_ARG, "hm_set_option: ntt_fused_small above %d", HM_NTT_MAX_ENTRIES);
     if (value && c->fused_broken) return fail(c, HM_ERR_UNSUPPORTED,
@@ -1075,6 +1095,10 @@ extern "C" hm_status hm_get_counter(hm_ctx *c, const char *name, uint64_t *value
   // arithmetic back-end of this context: 0 = mont32 (word-wise Montgomery on q = h 2^32 + 1), 1 = generic
   if (!strcmp(name, "arith")) { *value = HM_GENERIC; return HM_OK; }
   if (!strcmp(name, "ntt_fused_slots_per_xcd")) { *value = c->fused_slots_per_xcd; return HM_OK; }
+  // the launch-table cache (hm_table_cache.h): tables it holds, times it started over since hm_create, its limit
+  if (!strcmp(name, "launch_tables")) { *value = c->tables.tables.size(); return HM_OK; }
+  if (!strcmp(name, "launch_table_evictions")) { *value = c->tables.evictions; return HM_OK; }
+  if (!strcmp(name, "launch_table_limit")) { *value = c->tables.limit; return HM_OK; }
   // the capability table of this context's ring size (hm_caps.h): what the host layer plans its fusions from
   if (!strncmp(name, "cap_", 4) && !hm_cap_by_name(c->P.logN, name, value)) return HM_OK;
   if (!strcmp(name, "ntt_fused_small")) { *value = c->fused_small; return HM_OK; }   // 0: the one-launch form is off (option, guard, or after a time-out)
@@ -1111,16 +1135,16 @@ extern "C" hm_status hm_capture_begin(hm_ctx *c) {
   if (!c) return HM_ERR_ARG;
   if (c->ext_fn) return fail(c, HM_ERR_UNSUPPORTED, "hm_capture_begin: an external exchange transport cannot be captured");
   HM_HIP(c, hipSetDevice(c->device));
-  c->capturing = true;  // kernel nodes of the graph keep the device addresses of the launch tables
+  c->tables.capturing = true;  // kernel nodes of the graph keep the device addresses of the launch tables
   c->capture_has_fused = false;
   hipError_t e = hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal);
-  if (e != hipSuccess) { c->capturing = false; return fail(c, HM_ERR_HIP, "hipStreamBeginCapture: %s", hipGetErrorString(e)); }
+  if (e != hipSuccess) { c->tables.capturing = false; return fail(c, HM_ERR_HIP, "hipStreamBeginCapture: %s", hipGetErrorString(e)); }
   return HM_OK;
 }
 extern "C" hm_status hm_capture_end(hm_ctx *c, hm_graph **out) {
   if (!c || !out) return HM_ERR_ARG;
   hm_graph *g = new hm_graph;
-  c->capturing = false;
+  c->tables.capturing = false;
   hipError_t e = hipStreamEndCapture(c->stream, &g->graph);
   if (e == hipSuccess) e = hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0);
   if (e != hipSuccess) {
@@ -1131,7 +1155,7 @@ extern "C" hm_status hm_capture_end(hm_ctx *c, hm_graph **out) {
   g->owner = c;
   g->has_fused = c->capture_has_fused;
   c->graphs.push_back(g);
-  c->live_graphs++;   // the launch-table cache is pinned while this graph lives (released in hm_graph_destroy)
+  c->tables.live_graphs++;   // the launch-table cache is pinned while this graph lives (released in hm_graph_destroy)
   *out = g;
   return HM_OK;
 }
@@ -1147,7 +1171,7 @@ extern "C" hm_status hm_graph_launch(hm_ctx *c, hm_graph *g) {
 extern "C" void hm_graph_destroy(hm_graph *g) {
   if (!g) return;
   if (g->owner) {
-    if (g->owner->live_graphs > 0) g->owner->live_graphs--;
+    if (g->owner->tables.live_graphs > 0) g->owner->tables.live_graphs--;
     auto &v = g->owner->graphs;
     v.erase(std::remove(v.begin(), v.end(), g), v.end());
   }
@@ -1286,7 +1310,7 @@ static void launch_ntt(hm_ctx *c, const HmNttArgs &a, int form, bool firstPassOn
 #if defined(HM_FUSED_TRACE)
     f.trace = c->fused_trace;
 #endif
-    if (c->capturing) c->capture_has_fused = true;
+    if (c->tables.capturing) c->capture_has_fused = true;
     bool inPlace = a.in == a.out;   // every limb-poly transformed onto itself: the input loads keep their lines for the hand-off
     for (uint32_t e = 0; inPlace && e < a.n_limbs; ++e) inPlace = a.limb[e].mod == HM_NTT_NONE || a.limb[e].in == a.limb[e].out;
     hipLaunchKernelGGL(K.one[inPlace ? 1 : 0], grid, block8, 0, c->stream, a, f);
@@ -1296,30 +1320,30 @@ static void launch_ntt(hm_ctx *c, const HmNttArgs &a, int form, bool firstPassOn
   hipLaunchKernelGGL(second8 ? K.second8 : K.second, grid, second8 ? block8 : block16, 0, c->stream, a);
 }
 
-// Device copy of a launch's table (NTT entry constants, base-conversion problem records), cached by content; uploaded
+// Device copy of a launch's table (NTT entry constants, base-conversion problem records), cached by content (hm_table_cache.h); uploaded
 // (synchronously) on first use.  Tables are never freed while a graph captured from this context may still replay them
-// (hm_capture_begin pins the cache); a miss while the stream is capturing is an error, not a hidden synchronisation.
-static hm_status device_table(hm_ctx *c, const void *data, size_t bytes, const void **out) {
-  const std::string key(static_cast<const char *>(data), bytes);
-  auto it = c->launch_tables.find(key);
-  if (it == c->launch_tables.end()) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(c->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-      return fail(c, HM_ERR_UNSUPPORTED, "a launch table is missing while the stream is capturing: run the plan once before hm_capture_begin");
-    // callers that never repeat a launch (tests): start over rather than grow without bound
-    if (c->launch_tables.size() >= 1024 && c->live_graphs == 0 && !c->capturing) {
-      HM_HIP(c, hipStreamSynchronize(c->stream));
-      for (auto &kv : c->launch_tables) (void)hipFree(kv.second);
-      c->launch_tables.clear();
-    }
-    void *dev = nullptr;
-    HM_HIP(c, hipMalloc(&dev, bytes));
-    HM_HIP(c, hipMemcpy(dev, data, bytes, hipMemcpyHostToDevice));
-    it = c->launch_tables.emplace(key, dev).first;
-  }
-  *out = it->second;
-  return HM_OK;
+// (hm_capture_begin pins the cache), and never inside a call: a call stores the addresses of its earlier tables in its later ones, so the cache
+// starts over only where an ABI call enters (HM_TABLE_CALL).  A miss while the stream is capturing is an error, not a hidden synchronisation.
+static hm_status table_backend_error(hm_ctx *c) {
+  return fail(c, HM_ERR_HIP, "launch tables: %s", hipGetErrorString((hipError_t)c->tables.backend_status));
 }
+static hm_status device_table(hm_ctx *c, const void *data, size_t bytes, const void **out) {
+  if (c->tables.depth == 0) return fail(c, HM_ERR_HIP, "a launch table was requested outside an HM_TABLE_CALL span");
+  HipTables b{c->stream};
+  switch (c->tables.get(b, data, bytes, out)) {
+    case HM_TABLE_OK: return HM_OK;
+    case HM_TABLE_CAPTURE_MISS:
+      return fail(c, HM_ERR_UNSUPPORTED, "a launch table is missing while the stream is capturing: run the plan once before hm_capture_begin");
+    default: return table_backend_error(c);
+  }
+}
+// The span of an ABI call that requests launch tables, from its entry to its return: no table handed out inside it is freed before it ends.  At the
+// entry of an outermost call the cache starts over if it holds its limit of tables and nothing pins it (after a stream synchronise: the kernels
+// already enqueued read theirs).
+#define HM_TABLE_CALL(c)                                         \
+  HipTables table_dev_{(c)->stream};                             \
+  HmTableCall<HipTables> table_call_((c)->tables, table_dev_);   \
+  if (table_call_.st) return table_backend_error(c)
 // `mul` (empty: none): the table's extension for the product operands, one HmNttMulEntry per entry behind the entry records, in the same allocation
 static hm_status ntt_table(hm_ctx *c, const std::vector<HmNttEntry> &tab, const std::vector<HmNttMulEntry> &mul, const HmNttEntry **out) {
   const void *p = nullptr;
@@ -1479,6 +1503,7 @@ extern "C" hm_status hm_ntt(hm_ctx *c, const uint64_t *in, const uint32_t *in_li
                             const uint32_t *out_limbs, const uint32_t *mod_ids, uint32_t n, int inverse,
                             const uint64_t *scale) {
   if (!c) return HM_ERR_ARG;
+  HM_TABLE_CALL(c);
   if (!in || !out) return fail(c, HM_ERR_ARG, "hm_ntt: null buffer");
   if (scale && !inverse) return fail(c, HM_ERR_ARG, "hm_ntt: scale is only defined for the inverse transform");
   return ntt_common(c, "hm_ntt", in, in_limbs, out, out_limbs, mod_ids, n, inverse, scale, NttFused{});
@@ -1487,6 +1512,7 @@ extern "C" hm_status hm_ntt(hm_ctx *c, const uint64_t *in, const uint32_t *in_li
 extern "C" hm_status hm_ntt_second_pass(hm_ctx *c, uint64_t *buf, const uint32_t *limbs, const uint32_t *mod_ids, uint32_t n, int inverse,
                                         const uint64_t *scale) {
   if (!c) return HM_ERR_ARG;
+  HM_TABLE_CALL(c);
   if (!buf) return fail(c, HM_ERR_ARG, "hm_ntt_second_pass: null buffer");
   if (scale && !inverse) return fail(c, HM_ERR_ARG, "hm_ntt_second_pass: scale is only defined for the inverse transform");
   NttFused f;
@@ -1496,6 +1522,7 @@ extern "C" hm_status hm_ntt_second_pass(hm_ctx *c, uint64_t *buf, const uint32_t
 
 extern "C" hm_status hm_ntt_ex(hm_ctx *c, const hm_ntt_desc *d) {
   if (!c) return HM_ERR_ARG;
+  HM_TABLE_CALL(c);
   if (!d || !d->out || (!d->in && !d->second_pass_only)) return fail(c, HM_ERR_ARG, "hm_ntt_ex: null buffer");
   if (d->scale && !d->inverse) return fail(c, HM_ERR_ARG, "hm_ntt_ex: scale is only defined for the inverse transform");
   if (d->out_packed && !d->inverse) return fail(c, HM_ERR_ARG, "hm_ntt_ex: out_packed is only defined for the inverse transform");
@@ -1510,6 +1537,7 @@ extern "C" hm_status hm_ntt_ex(hm_ctx *c, const hm_ntt_desc *d) {
 
 extern "C" hm_status hm_ntt_mul(hm_ctx *c, const hm_ntt_mul_desc *m) {
   if (!c) return HM_ERR_ARG;
+  HM_TABLE_CALL(c);
   if (!m || !m->t.in || !m->t.out || !m->in_b) return fail(c, HM_ERR_ARG, "hm_ntt_mul: null buffer");
   const hm_ntt_desc *d = &m->t;
   if (!d->inverse) return fail(c, HM_ERR_UNSUPPORTED, "hm_ntt_mul: only the inverse transform takes a product input");
@@ -1525,6 +1553,7 @@ extern "C" hm_status hm_ntt_sub_scale(hm_ctx *c, const uint64_t *in, const uint3
                                       uint64_t *out, const uint32_t *out_limbs, const uint32_t *mod_ids, uint32_t n,
                                       const uint64_t *k) {
   if (!c) return HM_ERR_ARG;
+  HM_TABLE_CALL(c);
   if (!in || !out || !minuend || !k) return fail(c, HM_ERR_ARG, "hm_ntt_sub_scale: null argument");
   NttFused f;
   f.minuend = minuend; f.minuend_limbs = minuend_limbs; f.addend = addend; f.addend_limbs = addend_limbs;
@@ -1540,6 +1569,7 @@ static hm_status bconv_col_launch(hm_ctx *c, const hm_bconv_desc *descs, uint32_
 extern "C" hm_status hm_ntt_mix_sub_scale_mul(hm_ctx *c, const hm_ntt_fused_mul_desc *m) {
   static const char *const what = "hm_ntt_mix_sub_scale_mul";
   if (!c) return HM_ERR_ARG;
+  HM_TABLE_CALL(c);
   if (!m || !m->t.in || !m->t.out || !m->t.minuend || !m->t.k || !m->minuend_b) return fail(c, HM_ERR_ARG, "%s: null argument", what);
   const hm_ntt_fused_desc *d = &m->t;
   if (d->n_conv || d->conv || d->addend_galois) return fail(c, HM_ERR_UNSUPPORTED, "%s: a product minuend combines with neither conv nor addend_galois", what);
@@ -1554,6 +1584,7 @@ extern "C" hm_status hm_ntt_mix_sub_scale_mul(hm_ctx *c, const hm_ntt_fused_mul_
 
 extern "C" hm_status hm_ntt_mix_sub_scale(hm_ctx *c, const hm_ntt_fused_desc *d) {
   if (!c) return HM_ERR_ARG;
+  HM_TABLE_CALL(c);
   if (!d || (!d->in && !d->n_conv) || !d->out || !d->minuend || !d->k) return fail(c, HM_ERR_ARG, "hm_ntt_mix_sub_scale: null argument");
   if ((d->mix != nullptr) != (d->mix_k != nullptr)) return fail(c, HM_ERR_ARG, "hm_ntt_mix_sub_scale: mix and mix_k go together");
   if (d->addend_k && !d->addend) return fail(c, HM_ERR_ARG, "hm_ntt_mix_sub_scale: addend_k without addend");
@@ -1657,6 +1688,7 @@ extern "C" hm_status hm_tensor_dot(hm_ctx *c, const uint64_t *pa, const uint32_t
                                    const uint32_t *mod_ids, uint32_t n, uint32_t n_terms) {
   static const char *const what = "hm_tensor_dot";
   if (!c) return HM_ERR_ARG;
+  HM_TABLE_CALL(c);
   if (!pa || !pb || !pc || !pd || !o0 || !o1 || !o2) return fail(c, HM_ERR_ARG, "%s: null buffer", what);
   const uint32_t T = n_terms, N = c->P.N;
   if (T == 0 || T > HM_DOT_MAX_TERMS) return fail(c, HM_ERR_ARG, "%s: n_terms = %u, must be in [1, %d]", what, T, HM_DOT_MAX_TERMS);
@@ -1876,6 +1908,7 @@ extern "C" hm_status hm_inner_product_hoisted(hm_ctx *c, const hm_ip_hoisted_des
   static const char *const what = "hm_inner_product_hoisted";
   static const hm_ip_hoisted_desc none = {};
   if (!c) return HM_ERR_ARG;
+  HM_TABLE_CALL(c);
   if (!d) d = &none;
   const uint32_t n = d->n, T = d->n_terms, R = d->n_rot, N = c->P.N;
   const bool null = !d->x || !d->x_limbs || !d->y || !d->y_limbs || !d->out || !d->out_limbs || !d->mod_ids || !d->galois;
@@ -1907,6 +1940,7 @@ extern "C" hm_status hm_inner_product_lintrans(hm_ctx *c, const hm_ip_lintrans_d
   static const char *const what = "hm_inner_product_lintrans";
   static const hm_ip_lintrans_desc none = {};
   if (!c) return HM_ERR_ARG;
+  HM_TABLE_CALL(c);
   if (!d) d = &none;
   const bool anyAdd = d->addend_limbs != nullptr;
   const char *null = nullptr;
@@ -2045,6 +2079,7 @@ static hm_status ip_lintrans_multi(hm_ctx *c, const char *what, const hm_ip_lint
 extern "C" hm_status hm_inner_product_lintrans_multi(hm_ctx *c, const hm_ip_lintrans_multi_desc *d) {
   static const hm_ip_lintrans_multi_desc none = {};
   if (!c) return HM_ERR_ARG;
+  HM_TABLE_CALL(c);
   return ip_lintrans_multi(c, "hm_inner_product_lintrans_multi", d ? d : &none, nullptr);
 }
 // ... with the identity step: the same table with the identity records behind it, the same geometry, the ID form of the kernel; one sum
@@ -2052,6 +2087,7 @@ extern "C" hm_status hm_inner_product_lintrans_multi(hm_ctx *c, const hm_ip_lint
 extern "C" hm_status hm_inner_product_lintrans_id(hm_ctx *c, const hm_ip_lintrans_id_desc *d) {
   static const hm_ip_lintrans_id_desc none = {};
   if (!c) return HM_ERR_ARG;
+  HM_TABLE_CALL(c);
   if (!d) d = &none;
   return ip_lintrans_multi(c, "hm_inner_product_lintrans_id", &d->sums, d);
 }
@@ -2129,12 +2165,14 @@ static hm_status ip_rotsum(hm_ctx *c, const char *what, const hm_ip_rotsum_desc 
 extern "C" hm_status hm_inner_product_rotsum(hm_ctx *c, const hm_ip_rotsum_desc *d) {
   static const hm_ip_rotsum_desc none = {};
   if (!c) return HM_ERR_ARG;
+  HM_TABLE_CALL(c);
   return ip_rotsum(c, "hm_inner_product_rotsum", d ? d : &none, nullptr);
 }
 // ... with initial sums: the accumulators start from init / the initial addend sum instead of zero
 extern "C" hm_status hm_inner_product_rotsum_init(hm_ctx *c, const hm_ip_rotsum_init_desc *d) {
   static const hm_ip_rotsum_init_desc none = {};
   if (!c) return HM_ERR_ARG;
+  HM_TABLE_CALL(c);
   if (!d) d = &none;
   return ip_rotsum(c, "hm_inner_product_rotsum_init", &d->sum, d);
 }
@@ -2166,6 +2204,7 @@ static nip_kernel nip_kernel_for(uint32_t outs, int invForm, bool xg, bool small
 // (limb, digit) into `hand`, then k_ntt_row_ip: ROW pass, product with both keys, accumulation over the digits in registers.
 extern "C" hm_status hm_ntt_inner_product(hm_ctx *c, const hm_ntt_ip_desc *d) {
   if (!c) return HM_ERR_ARG;
+  HM_TABLE_CALL(c);
   if (!d || !d->x || !d->x_limbs || !d->x_is_coeff || !d->y || !d->y_limbs || !d->out || !d->out_limbs || !d->mod_ids)
     return fail(c, HM_ERR_ARG, "hm_ntt_inner_product: null argument");
   const uint32_t n = d->n, T = d->n_terms, K = d->n_out;

@@ -6,6 +6,7 @@
 // transposed-domain exchanges (hm_limbs_to_colslices -> hm_bconv_col -> hm_colslices_to_limbs -> hm_ntt_inner_product with x_is_coeff = 2)
 extern "C" hm_status hm_bconv_col(hm_ctx *c, const hm_bconv_desc *descs, uint32_t n_desc, uint32_t tile0, uint32_t n_tiles) {
   if (!c) return HM_ERR_ARG;
+  HM_TABLE_CALL(c);
   if (!descs || n_desc == 0) return fail(c, HM_ERR_ARG, "hm_bconv_col: no problems");
   for (uint32_t k = 0; k < n_desc; ++k)
     if (descs[k].sub_from) return fail(c, HM_ERR_UNSUPPORTED, "hm_bconv_col: no epilogue on a fused conversion");
@@ -67,6 +68,7 @@ static hm_status bconv_table(hm_ctx *c, const hm_bconv_desc &d, uint32_t kn, con
 
 extern "C" hm_status hm_bconv_batch(hm_ctx *c, const hm_bconv_desc *descs, uint32_t n_desc) {
   if (!c) return HM_ERR_ARG;
+  HM_TABLE_CALL(c);
   if (!descs || n_desc == 0) return fail(c, HM_ERR_ARG, "hm_bconv_batch: no problems");
   HM_HIP(c, hipSetDevice(c->device));
   const uint32_t logN = descs[0].log_len ? descs[0].log_len : c->P.logN;
