@@ -113,6 +113,11 @@ __device__ __forceinline__ void hm_ntt_pass_run(const HmNttArgs &a, uint64_t *ld
     ep.b = ((ConstMul)(uintptr_t)(a.entry + a.n_limbs))[entry].b;
     ep.bk.w = HM_CONST_MODS(a.mods)[mod].mu; ep.bk.ws = HM_CONST_MODS(a.mods)[mod].sh;
   }
+  if constexpr (MODE == 10) {   // the lift's constants: the table's extension behind the n_limbs entry records (HmNttLiftEntry)
+    typedef const HmNttLiftEntry __attribute__((address_space(4))) *ConstLift;
+    const auto &le = ((ConstLift)(uintptr_t)(a.entry + a.n_limbs))[entry];
+    ep.dk.w = le.qs; ep.bk.ws = le.qs_mod_q; ep.bk.w = le.lm;
+  }
   if constexpr (MODE == 4) {
     const auto &en = entries[entry];
     ep.b = a.mix + (size_t)en.mixlimb * N;
@@ -152,7 +157,8 @@ __device__ __forceinline__ void hm_ntt_pass_body(const HmNttArgs &a) {
 // MODE 0: first pass / plain hand-off; 1: forward final; 2: inverse final (x scale); 3: forward final with the fused
 // epilogue; 4: forward first pass with the mix prologue; 6: inverse first pass whose input is read through an automorphism; 7: MODE 3 with the
 // addend read through an automorphism (round 6: hrotate's automorphism launch folded into the ModUp INTT and the final add); 8: MODE 3 whose minuend
-// is the product of two stored limb-polys; 9: inverse first pass whose input is such a product (pmult's products folded into the rescale's transforms)
+// is the product of two stored limb-polys; 9: inverse first pass whose input is such a product (pmult's products folded into the rescale's transforms); 10: forward first pass whose input is a stored limb-poly of another modulus,
+// centred and reduced into the entry's own while it loads (ModRaise: hm_ntt_lift)
 template <int LOGR, bool INV, int MODE>
 __global__ void __launch_bounds__((1 << HM_TL_COL) / HM_EPT) __attribute__((amdgpu_waves_per_eu(HM_NTT_MIN_WAVES_COL))) k_ntt_col(HmNttArgs a) {
   hm_ntt_pass_body<LOGR, true, INV, MODE>(a);
@@ -1214,7 +1220,7 @@ static hm_status check_mods(hm_ctx *c, const char *what, const uint32_t *m, uint
 // The kernels of a transform, by form: 0 = forward, 1 = forward with the fused epilogue (MODE 3), 2 = forward with the mix prologue and
 // the epilogue (MODE 4 + 3), 3 = inverse, 4 = inverse with the input read through an automorphism (MODE 6), 5 = form 1 with the addend read
 // through an automorphism (MODE 7), 6 = form 1 with a product minuend (MODE 8), 7 = form 2 with a product minuend (MODE 4 + 8), 8 = inverse with a
-// product input (MODE 9).  `first` / `second` = the two pass kernels in the order they run (forward: COL then ROW,
+// product input (MODE 9), 9 = forward with a lifted input (MODE 10 + 1).  `first` / `second` = the two pass kernels in the order they run (forward: COL then ROW,
 // inverse: ROW then COL) in the 16-coefficient geometry; `first8` / `second8` = the same in the small-launch geometry and `one` = both
 // passes in one launch ([0] out of place: non-temporal input loads, [1] in place); the small-launch forms exist where hm_caps says so
 // (N = 2^15 and 2^16).
@@ -1225,7 +1231,7 @@ struct HmNttKernels {
   hm_ntt_one_kernel one[2];
 };
 static_assert(HM_NTT_MAX_LAUNCH_ENTRIES == HM_NTT_MAX_ENTRIES, "hm_caps.h states the launch's record count for the host layer");
-#define HM_NTT_FORMS 9
+#define HM_NTT_FORMS 10
 template <int LOG1>
 static const HmNttKernels &ntt_kernels(int form) {
   static const HmNttKernels wide[HM_NTT_FORMS] = {
@@ -1237,7 +1243,8 @@ static const HmNttKernels &ntt_kernels(int form) {
       {k_ntt_col<LOG1, false, 0>, k_ntt_row<false, 7>, nullptr, nullptr, {nullptr, nullptr}},
       {k_ntt_col<LOG1, false, 0>, k_ntt_row<false, 8>, nullptr, nullptr, {nullptr, nullptr}},
       {k_ntt_col<LOG1, false, 4>, k_ntt_row<false, 8>, nullptr, nullptr, {nullptr, nullptr}},
-      {k_ntt_row<true, 9>, k_ntt_col<LOG1, true, 2>, nullptr, nullptr, {nullptr, nullptr}}};
+      {k_ntt_row<true, 9>, k_ntt_col<LOG1, true, 2>, nullptr, nullptr, {nullptr, nullptr}},
+      {k_ntt_col<LOG1, false, 10>, k_ntt_row<false, 1>, nullptr, nullptr, {nullptr, nullptr}}};
   return wide[form];
 }
 // the ring sizes of the reference's configurations (config/config_4.cfg: N = 2^16, config_4_N15.cfg: N = 2^15) have all three forms
@@ -1267,7 +1274,10 @@ static const HmNttKernels &ntt_kernels_all(int form) {
       {k_ntt_col<LOG1, false, 4>, k_ntt_row<false, 8>, nullptr, nullptr, {k_ntt_fused8<LOG1, false, 4, 8, true>, k_ntt_fused8<LOG1, false, 4, 8, false>}},
 #endif
       {k_ntt_row<true, 9>, k_ntt_col<LOG1, true, 2>, k_ntt_row8<true, 9>, k_ntt_col8<LOG1, true, 2>, {k_ntt_fused8<LOG1, true, 9, 2, true>,
-          k_ntt_fused8<LOG1, true, 9, 2, false>}}};
+          k_ntt_fused8<LOG1, true, 9, 2, false>}},
+      // (a lifted input is never read in place, and many entries read one source: plain input loads keep its lines for them)
+      {k_ntt_col<LOG1, false, 10>, k_ntt_row<false, 1>, k_ntt_col8<LOG1, false, 10>, k_ntt_row8<false, 1>, {k_ntt_fused8<LOG1, false, 10, 1, false>,
+          k_ntt_fused8<LOG1, false, 10, 1, false>}}};
   return both[form];
 }
 template <> const HmNttKernels &ntt_kernels<8>(int form) { return ntt_kernels_all<8>(form); }
@@ -1345,14 +1355,18 @@ static hm_status device_table(hm_ctx *c, const void *data, size_t bytes, const v
   HmTableCall<HipTables> table_call_((c)->tables, table_dev_);   \
   if (table_call_.st) return table_backend_error(c)
 // `mul` (empty: none): the table's extension for the product operands, one HmNttMulEntry per entry behind the entry records, in the same allocation
-static hm_status ntt_table(hm_ctx *c, const std::vector<HmNttEntry> &tab, const std::vector<HmNttMulEntry> &mul, const HmNttEntry **out) {
+// `lift` (empty: none; never with `mul`): the same for the lifted input's constants, one HmNttLiftEntry per entry
+static hm_status ntt_table(hm_ctx *c, const std::vector<HmNttEntry> &tab, const std::vector<HmNttMulEntry> &mul, const std::vector<HmNttLiftEntry> &lift,
+                           const HmNttEntry **out) {
   const void *p = nullptr;
   hm_status st;
-  if (mul.empty()) st = device_table(c, tab.data(), sizeof(HmNttEntry) * tab.size(), &p);
+  const void *ext = mul.empty() ? (const void *)lift.data() : (const void *)mul.data();
+  const size_t extBytes = mul.empty() ? sizeof(HmNttLiftEntry) * lift.size() : sizeof(HmNttMulEntry) * mul.size();
+  if (!extBytes) st = device_table(c, tab.data(), sizeof(HmNttEntry) * tab.size(), &p);
   else {
-    std::vector<char> both(sizeof(HmNttEntry) * tab.size() + sizeof(HmNttMulEntry) * mul.size());
+    std::vector<char> both(sizeof(HmNttEntry) * tab.size() + extBytes);
     memcpy(both.data(), tab.data(), sizeof(HmNttEntry) * tab.size());
-    memcpy(both.data() + sizeof(HmNttEntry) * tab.size(), mul.data(), sizeof(HmNttMulEntry) * mul.size());
+    memcpy(both.data() + sizeof(HmNttEntry) * tab.size(), ext, extBytes);
     st = device_table(c, both.data(), both.size(), &p);
   }
   *out = static_cast<const HmNttEntry *>(p);
@@ -1374,6 +1388,7 @@ struct NttFused {
   const uint32_t *addGalois = nullptr;  // fused forward (round 6): per limb-poly, the addend is read through X -> X^g (0 / 1: as stored)
   const uint64_t *mulB = nullptr;       // fused forward: the minuend, inverse: the input is the product with this operand (hm_ntt_mix_sub_scale_mul, hm_ntt_mul)
   const uint32_t *mulB_limbs = nullptr; // ... fused forward: HM_NO_LIMB = a plain minuend for that limb-poly
+  const uint32_t *liftSrcMods = nullptr; // plain forward: per limb-poly, the modulus the stored input is reduced by (hm_ntt_lift)
   bool firstPassOnly = false;   // forward transform: run the COL pass only (the hand-off stays in `out`)
   bool secondPassOnly = false;  // forward transform: the hand-off is already in `out` (a fused conversion wrote it): run the ROW pass only
 };
@@ -1448,6 +1463,7 @@ static hm_status ntt_common(hm_ctx *c, const char *what, const uint64_t *in, con
     std::vector<HmNttEntry> tab(cnt);
     memset(tab.data(), 0, sizeof(HmNttEntry) * cnt);
     std::vector<HmNttMulEntry> mul(f.mulB ? cnt : 0, HmNttMulEntry{nullptr});
+    std::vector<HmNttLiftEntry> lift(f.liftSrcMods ? cnt : 0, HmNttLiftEntry{0, 0, 0});
     HmNttArgs a;
     for (uint32_t e = 0; e < cnt; ++e) a.limb[e] = HmLimb{0, 0, (uint16_t)HM_NTT_NONE, 0};
     for (uint32_t kk = 0; kk < ng; ++kk) {
@@ -1459,6 +1475,10 @@ static hm_status ntt_common(hm_ctx *c, const char *what, const uint64_t *in, con
         HmNttEntry &t = tab[e];
         a.limb[e] = HmLimb{(uint16_t)limb_at(in_limbs, g), (uint16_t)limb_at(out_limbs, g), (uint16_t)m, 0};
         if (f.mulB && !(f.mulB_limbs && f.mulB_limbs[g] == HM_NO_LIMB)) mul[e].b = f.mulB + (size_t)limb_at(f.mulB_limbs, g) * c->P.N;
+        if (f.liftSrcMods) {
+          const uint64_t qs = c->P.mod[f.liftSrcMods[g]];
+          lift[e] = HmNttLiftEntry{qs, qs % q, (uint64_t)(((hm_u128)1 << 64) / q)};
+        }
         if (inverse) {
           uint64_t v = c->P.modc[m].ninv;
           if (k) v = hm::mulmod(v, k[g], q);
@@ -1479,8 +1499,8 @@ static hm_status ntt_common(hm_ctx *c, const char *what, const uint64_t *in, con
       }
     }
     const HmNttEntry *dtab = nullptr;
-    if (inverse || fused) {   // the plain forward transform needs no per-limb constants
-      if ((st = ntt_table(c, tab, mul, &dtab))) return st;
+    if (inverse || fused || f.liftSrcMods) {   // the plain forward transform needs no per-limb constants
+      if ((st = ntt_table(c, tab, mul, lift, &dtab))) return st;
     }
     a.in = in; a.out = out;
     a.tw = inverse ? c->d_tw_inv : c->d_tw_fwd;
@@ -1489,7 +1509,7 @@ static hm_status ntt_common(hm_ctx *c, const char *what, const uint64_t *in, con
     a.entry = dtab;
     a.minuend = f.minuend; a.addend = f.addend; a.mix = f.mix;
     a.logN = c->P.logN; a.n_limbs = cnt; a.logG = logG;
-    const int form = inverse ? (f.mulB ? 8 : anyInGalois ? 4 : 3) : fused ? (f.mulB ? (f.mix ? 7 : 6) : f.mix ? 2 : anyAddGalois ? 5 : 1) : 0;
+    const int form = inverse ? (f.mulB ? 8 : anyInGalois ? 4 : 3) : fused ? (f.mulB ? (f.mix ? 7 : 6) : f.mix ? 2 : anyAddGalois ? 5 : 1) : f.liftSrcMods ? 9 : 0;
     static void (*const launch[])(hm_ctx *, const HmNttArgs &, int, bool, bool) = {launch_ntt<5>, launch_ntt<6>, launch_ntt<7>, launch_ntt<8>, launch_ntt<9>};
     const uint32_t log1 = c->P.logN - HM_ROW_LOG;   // the COL pass's sub-transform length
     if (log1 < 5 || log1 > 9) return fail(c, HM_ERR_UNSUPPORTED, "%s: logN %u", what, c->P.logN);
@@ -1546,6 +1566,25 @@ extern "C" hm_status hm_ntt_mul(hm_ctx *c, const hm_ntt_mul_desc *m) {
   f.outPacked = d->out_packed;
   f.mulB = m->in_b; f.mulB_limbs = m->in_b_limbs;
   return ntt_common(c, "hm_ntt_mul", d->in, d->in_limbs, d->out, d->out_limbs, d->mod_ids, d->n, 1, d->scale, f);
+}
+
+extern "C" hm_status hm_ntt_lift(hm_ctx *c, const hm_ntt_lift_desc *l) {
+  if (!c) return HM_ERR_ARG;
+  HM_TABLE_CALL(c);
+  if (!l || !l->t.in || !l->t.out) return fail(c, HM_ERR_ARG, "hm_ntt_lift: null buffer");
+  const hm_ntt_desc *d = &l->t;
+  if (d->inverse) return fail(c, HM_ERR_UNSUPPORTED, "hm_ntt_lift: only the forward transform takes a lifted input");
+  if (d->second_pass_only || d->in_galois || d->scale || d->out_packed)
+    return fail(c, HM_ERR_UNSUPPORTED, "hm_ntt_lift: not with second_pass_only, in_galois, scale or out_packed");
+  hm_status st;
+  if ((st = check_mods(c, "hm_ntt_lift", l->src_mod_ids, d->n))) return st;
+  if ((st = check_limbs(c, "hm_ntt_lift", d->in_limbs, d->n)) || (st = check_limbs(c, "hm_ntt_lift", d->out_limbs, d->n))) return st;
+  // a workgroup of the first pass writes its tile of `out` while the entries that share a source still read theirs: no limb-poly may be both
+  const int64_t g = hm_first_overlap(d->out, d->out_limbs, d->n, d->in, d->in_limbs, d->n, c->P.N, [](uint32_t) { return true; });
+  if (g >= 0) return fail(c, HM_ERR_ARG, "hm_ntt_lift: the output overlaps the input of limb-poly [%u]", (uint32_t)g);
+  NttFused f;
+  f.liftSrcMods = l->src_mod_ids;
+  return ntt_common(c, "hm_ntt_lift", d->in, d->in_limbs, d->out, d->out_limbs, d->mod_ids, d->n, 0, nullptr, f);
 }
 
 extern "C" hm_status hm_ntt_sub_scale(hm_ctx *c, const uint64_t *in, const uint32_t *in_limbs, const uint64_t *minuend,

@@ -133,6 +133,26 @@ HM_HD uint64_t hm_epi_mul(uint64_t x, uint64_t y, uint64_t q, const HmEpi &ep) {
 struct HmNttMulEntry {
   const uint64_t *b;
 };
+// MODE 10 (ModRaise, the lifted forward first pass): the input is a stored limb-poly of ANOTHER modulus q_s, in coefficient form and reduced; the pass
+// transforms its centred representative reduced into the entry's own modulus q.  The constants ride in the extension of the launch's entry table
+// (behind its n_limbs HmNttEntry records, same device allocation) and reach the load routine in HmEpi: dk.w = q_s, bk.ws = q_s mod q,
+// bk.w = lm = floor(2^64 / q) (the mode has neither an addend nor a mix prologue).
+struct HmNttLiftEntry {
+  uint64_t qs, qs_mod_q, lm;
+};
+// centre_{q_s}(c) mod q in [0, q), for ANY word c < 2^60 and ANY q with 2 <= q < 2^60 (hm_barrett's shift by k - 1 needs a double-width argument
+// and does not serve a bare word against a small q).  Bounds:
+//   2^64 / q - 1 < lm <= 2^64 / q, so c / q - c / 2^64 < c lm / 2^64 <= c / q; c < 2^60 makes the gap less than 2^-4: t = floor(c lm / 2^64) is
+//   floor(c / q) or one less, and r = c - t q lies in [c mod q, c mod q + q], inside [0, 2q);
+//   the negative half (c > (q_s - 1) / 2, v = c - q_s) adds q - (q_s mod q) <= q: r < 3q < 2^62, two conditional subtractions reduce it.
+// The addend is chosen with a mask, not a branch: the halves are lane-varying.  q_s = q: t = 0 (c lm < 2^64), r = c, and the negative half adds q and
+// takes it off again: the lift is the identity, bit for bit.
+HM_HD uint64_t hm_lift(uint64_t c, uint64_t q, const HmEpi &ep) {
+  const uint64_t half = (ep.dk.w - 1) >> 1;
+  uint64_t r = c - hm_mulhi(c, ep.bk.w) * q;
+  r += (0 - (uint64_t)(c > half)) & (q - ep.bk.ws);
+  return hm_csub(hm_csub(r, 2 * q), q);
+}
 // Split-30 packed form (round 5): x < 2^60 stored as (x mod 2^30) | ((x >> 30) << 32) — the two 30-bit halves a base conversion multiplies
 // with, one per dword.  The inverse transforms that feed ONLY base conversions (ModUp_DecompOut, ModDownBConvStep1: src/Operation.cpp:
 // 104-135, 447-487) store this form (two instructions per value, once), and every conversion workgroup that reads the value (one per pair

@@ -284,13 +284,29 @@ HM_HD void hm_ph_load_global_mul(HmNttState &st, int tid, const uint64_t *g, uin
   }
 }
 
+// MODE 10 (ModRaise): the input is a stored, reduced limb-poly of another modulus q_s; hm_lift centres it against q_s and reduces it into [0, q) of the
+// pass's own modulus, the range a stored input has, so everything behind it is the plain forward first pass (the COL pass starts from reduced data)
+template <int TL, int LOGR, bool STRIDED, int R, int AUX = 0>
+HM_HD void hm_ph_load_global_lift(HmNttState &st, int tid, const uint64_t *g, uint32_t tile, uint64_t q, const HmEpi &ep) {
+  using G = HmRound<TL, LOGR, STRIDED, R>;
+#pragma unroll
+  for (int a = 0; a < HM_UNITS; ++a) {
+    int i0, i1, x, c;
+    G::unit(tid, a, i0, i1, x, c);
+    uint64_t p0, p1;
+    hm_gld2<G, AUX>(g, tile, tid, a, p0, p1);
+    st.v[i0] = hm_lift(p0, q, ep);
+    st.v[i1] = hm_lift(p1, q, ep);
+  }
+}
+
 // MODE 5 (ROW pass of the fused transform x key inner product): the last pass keeps its results in registers (lazy, below
 // 2 HM_LAZY_Q q) and stores nothing; hm_ph_mac consumes them.
 // the epilogue of one coefficient.  MODE 0 / 4 / 6: store as is (lazy values, hand-off between the two passes; 4 = first
 // pass with the mix prologue, 6 = inverse first pass whose input is read through an automorphism); 1: forward final, reduce [0, 2 HM_LAZY_Q q) -> [0,q); 2: inverse final, multiply by the per-limb
 // constant and reduce to [0,q); 3: forward final fused with out = (minuend - x) * k [+ addend [* ak]]; 7: the same with the addend read through an
 // automorphism (hm_ph_store_global gathers it); 8: MODE 3 with a product minuend (hm_ph_store_global forms va = a (.) b with hm_epi_mul: va in [0, q), a
-// stored minuend's range, so the bound below holds unchanged); 9: inverse first pass with a product input (hm_ph_load_global_mul), stores as MODE 0
+// stored minuend's range, so the bound below holds unchanged); 9: inverse first pass with a product input (hm_ph_load_global_mul), stores as MODE 0; 10: forward first pass with a lifted input (hm_ph_load_global_lift), stores as MODE 0
 // (sc, ep.dk, ep.bk: constant records made by hm_kconst on the host; hm_kmul multiplies by them)
 template <int MODE>
 HM_HD uint64_t hm_epilogue(uint64_t a, uint64_t va, uint64_t vd, uint64_t q, HmTw sc, const HmEpi &ep) {
@@ -480,6 +496,7 @@ HM_HD void hm_ntt_phase(HmNttState &st, int tid, uint64_t *lds, const uint64_t *
     else if (MODE == 4) hm_ph_load_global_mix<TL, LOGR, STRIDED, r0, LDAUX>(st, tid, src, tile, q, ep);
     else if constexpr (MODE == 6) hm_ph_load_global_auto<TL, LOGR, STRIDED, r0, LDAUX>(st, tid, src, tile, ep);
     else if constexpr (MODE == 9) hm_ph_load_global_mul<TL, LOGR, STRIDED, r0, LDAUX>(st, tid, src, tile, q, ep);
+    else if constexpr (MODE == 10) hm_ph_load_global_lift<TL, LOGR, STRIDED, r0, LDAUX>(st, tid, src, tile, q, ep);
     else hm_ph_load_global<TL, LOGR, STRIDED, r0, LDAUX>(st, tid, src, tile);
     // the twist constants are requested one phase ahead of the twisted round (phase iTW + 1)
     if (iTW >= 0 && iTW <= 1) hm_ph_load_twist<TL, LOGR, STRIDED, (TWR >= 0 ? TWR : 0)>(st, tid, twist_tile);

@@ -25,6 +25,7 @@ SYMBOLS = [
     "hm_bconv_col", "hm_limbs_to_colslices", "hm_colslices_to_limbs", "hm_ntt_second_pass", "hm_ntt_ex", "hm_capability", "hm_inner_product_ex",
     "hm_inner_product_hoisted", "hm_inner_product_lintrans", "hm_inner_product_rotsum", "hm_inner_product_lintrans_multi",
     "hm_tensor_dot", "hm_inner_product_lintrans_id", "hm_inner_product_rotsum_init", "hm_ntt_mix_sub_scale_mul", "hm_ntt_mul",
+    "hm_ntt_lift",
 ]
 
 
@@ -103,6 +104,10 @@ class hm_ntt_mul_desc(C.Structure):
     _fields_ = [("t", hm_ntt_desc), ("in_b", C.c_void_p), ("in_b_limbs", C.c_void_p)]
 
 
+class hm_ntt_lift_desc(C.Structure):
+    _fields_ = [("t", hm_ntt_desc), ("src_mod_ids", C.c_void_p)]
+
+
 class hm_params(C.Structure):
     _fields_ = [("logN", C.c_uint32), ("L", C.c_uint32), ("K", C.c_uint32), ("device", C.c_int32),
                 ("q", C.c_void_p), ("p", C.c_void_p), ("psi", C.c_void_p)]
@@ -151,6 +156,7 @@ def load():
     L.hm_ntt_mix_sub_scale.argtypes = [vp, C.POINTER(hm_ntt_fused_desc)]
     L.hm_ntt_mix_sub_scale_mul.argtypes = [vp, C.POINTER(hm_ntt_fused_mul_desc)]
     L.hm_ntt_mul.argtypes = [vp, C.POINTER(hm_ntt_mul_desc)]
+    L.hm_ntt_lift.argtypes = [vp, C.POINTER(hm_ntt_lift_desc)]
     L.hm_tensor.argtypes = [vp] + [vp] * 15 + [u32]
     L.hm_tensor_dot.argtypes = [vp] + [vp] * 15 + [u32, u32]
     L.hm_inner_product.argtypes = [vp] + [vp] * 7 + [u32, u32, u32]
@@ -311,6 +317,19 @@ class Context:
         d = hm_ntt_mul_desc(hm_ntt_desc(src.ptr, keep[0][1], dst.ptr, keep[1][1], keep[2][1], len(mod_ids), 1, ps, 0,
                                         None if pk is None else pk.ctypes.data_as(C.c_void_p), None), in_b.ptr, keep[3][1])
         self._ck(self.L.hm_ntt_mul(self.h, C.byref(d)))
+
+    def ntt_lift(self, src, dst, mod_ids, src_mod_ids, in_limbs=None, out_limbs=None, **refused):
+        """dst_i = NTT_{mod_ids[i]}(centre_{src_mod_ids[i]}(src_i) mod q_{mod_ids[i]}): the stored coefficients of another modulus are centred and
+        reduced while the first pass loads (hm_ntt_lift: ModRaise).  `refused`: hm_ntt_desc fields the call does not serve (inverse,
+        second_pass_only, in_galois, scale, out_packed), passed through so that the refusal is the library's"""
+        keep = [_u32(x) for x in (in_limbs, out_limbs, mod_ids, src_mod_ids, refused.get("in_galois"))]
+        k4, ps = _u64(refused.get("scale"))
+        pk = refused.get("out_packed")
+        pk = None if pk is None else np.ascontiguousarray(np.asarray(pk, dtype=np.uint8))
+        d = hm_ntt_lift_desc(hm_ntt_desc(src.ptr, keep[0][1], dst.ptr, keep[1][1], keep[2][1], len(mod_ids), 1 if refused.get("inverse") else 0, ps,
+                                         1 if refused.get("second_pass_only") else 0, None if pk is None else pk.ctypes.data_as(C.c_void_p),
+                                         keep[4][1]), keep[3][1])
+        self._ck(self.L.hm_ntt_lift(self.h, C.byref(d)))
 
     def ntt_sub_scale(self, src, minuend, out, mod_ids, k, addend=None, in_limbs=None, minuend_limbs=None, addend_limbs=None,
                       out_limbs=None):

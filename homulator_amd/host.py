@@ -237,7 +237,7 @@ class Op:
         return out
 
     def output_level(self):
-        """limbs of the output ciphertext (out.c0): the input's level, one less behind a rescale (hmult, hdot, hrescale, rescale = 1)"""
+        """limbs of the output ciphertext (out.c0): the input's level, one less behind a rescale (hmult, hdot, hrescale, rescale = 1), raise_to behind hmodraise"""
         n = C.c_uint32()
         self._ck(self.L.hh_op_buffer_limbs(self.h, b"out.c0", C.byref(n)))
         return n.value

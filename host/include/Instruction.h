@@ -16,6 +16,8 @@ enum ewe_opcode {
   EWE_MUL_CONST = 5, EWE_SUB_SCALE = 6, EWE_COPY = 7, EWE_SUB_SCALE_ADD = 8
 };
 
+static const uint32_t kNoLift = 0xFFFFFFFFu;   // Instruction::liftSrcMod of a plain forward transform
+
 class Instruction {
 public:
   ins_ops ops;
@@ -55,6 +57,9 @@ public:
   // (4p) product operands of transforms: an EWE_MUL of two op inputs folded into its one reader.  A fused forward transform's minuend is
   // fMinuend * fMinuendB, an INTT record's input operandList[0] * inMulB.  0: a plain operand
   AddrType fMinuendB = 0, inMulB = 0;
+  // (ModRaise, HMODRAISE) a forward transform whose stored input is reduced by ANOTHER modulus, liftSrcMod: the transform centres it against that
+  // modulus and reduces it into its own (mod_id) while it loads.  Set by the op builder, read by the launch builder.  kNoLift: a plain input
+  uint32_t liftSrcMod = kNoLift;
   bool fusedEpi = false;
   AddrType fSubFrom = 0, fAdd = 0;
   bool fusedTensor = false;            // MAC2 record that also produces d0 -> extraOutputs[0] and d2 -> extraOutputs[1]

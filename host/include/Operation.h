@@ -251,6 +251,12 @@ class HRESCALE : public OperationBase {
 public:
   HRESCALE(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
 };
+// hmodraise (build extension): out = ModRaise of ct1 (level 1) to level T = config key raise_to (default maxLevel): every limb j < T of both
+// components is NTT_{q_j} of the centred representative mod q_0 of the input's coefficients.  The one op whose output level is ABOVE its input's
+class HMODRAISE : public OperationBase {
+public:
+  HMODRAISE(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
+};
 class PADD : public OperationBase {
 public:
   PADD(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
@@ -266,7 +272,7 @@ class OpChain {
   std::vector<Arch *> archs;
   std::vector<OperationBase *> ops;
 public:
-  // ops: comma-separated list of hmult | hrotate | hadd | pmult | padd | hlintrans | hdot | hrotsum | hbsgs | hrescale, e.g. "hmult,hrotate,hadd,hmult"; hrotate_hoisted (R output
+  // ops: comma-separated list of hmult | hrotate | hadd | pmult | padd | hlintrans | hdot | hrotsum | hbsgs | hrescale | hmodraise, e.g. "hmult,hrotate,hadd,hmult"; hrotate_hoisted (R output
   // ciphertexts) only as the last op
   OpChain(const std::string &cfgPath, const std::string &opList, uint32_t maxLevel, uint32_t curLevel, uint32_t alpha,
           const std::map<std::string, uint32_t> &overrides = {});

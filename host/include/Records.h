@@ -36,6 +36,8 @@ enum class Role {
   Minuend, Addend, Mix,   // fused forward transform (4, 4b)
   MinuendMul,             // ... (4p) the second factor of a minuend that is a product
   InttMul,                // (4p) the second factor of an inverse transform's input that is a product
+  LiftIn,                 // the input of a forward transform that lifts it from another modulus (liftSrcMod, ModRaise): not an Operand, so the passes that
+                          // fold a producer into a transform's input or read it through an automorphism (9, 12) leave the record alone
   EpiSub, EpiAdd,         // conversion with the element-wise epilogue (10): fSubFrom, fAdd
   ReplacedIn      // the transform input operandList[0] that the fused conversion fConvIn replaces (9): never written, never loaded
 };
@@ -86,7 +88,7 @@ inline std::vector<Read> recordReads(const Instruction &i) {
     for (int b = 0; b < 4; ++b)
       if (eweOperandMask(i.opcode) & (1 << b)) v.push_back({i.operandList[b], Role::Operand, kNoDigit});
   } else {
-    const Role r = !i.fConvIn.empty() ? Role::ReplacedIn : i.ops != INTT ? Role::Operand : i.secondOnly ? Role::SecondPassIn : Role::InttIn;
+    const Role r = !i.fConvIn.empty() ? Role::ReplacedIn : i.ops == NTT && i.liftSrcMod != kNoLift ? Role::LiftIn : i.ops != INTT ? Role::Operand : i.secondOnly ? Role::SecondPassIn : Role::InttIn;
     v.push_back({i.operandList[0], r, kNoDigit});
     if (!i.fConvIn.empty()) v.push_back({i.fConvIn[0], Role::ConvIn, kNoDigit});
     if (i.inMulB) v.push_back({i.inMulB, Role::InttMul, kNoDigit});

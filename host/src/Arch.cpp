@@ -40,6 +40,7 @@ struct Arch::Launch {
   bool secondOnly = false;        // L_INTT (7b): hm_ntt_second_pass — the first pass was run by the inner-product kernel
   std::vector<uint8_t> outPacked; // L_INTT (11): per limb-poly, 1 = stored in the split-30 packed form of the conversions' inputs
   std::vector<uint32_t> inGalois, addGalois;   // (12) L_INTT: per limb-poly, the input / L_NTT_SUBSCALE: the addend is read through X -> X^g (0: as stored); empty: none
+  std::vector<uint32_t> liftMods;              // L_NTT: per limb-poly, the modulus its stored input is reduced by; the transform lifts it into its own (hm_ntt_lift, ModRaise); empty: none
   std::vector<uint32_t> mulB;                  // (4p) L_INTT: the input, L_NTT_SUBSCALE: the minuend is the product with this limb-poly (hm_ntt_mul / hm_ntt_mix_sub_scale_mul); empty: none
   uint32_t xGalois = 0;                        // (12) L_NTT_IP: the evaluation-form digits, L_IP: the x operands are read through X -> X^g
   uint32_t ipTerms = 0, ipOuts = 0;
@@ -314,6 +315,7 @@ int partKey(const Instruction &i) {
   if (i.ops == MULT) return 100 + i.opcode;                                                                // 100+: element-wise, by opcode
   if (i.ops == NTT && i.passthrough) return 100 + EWE_COPY;                                                //       (unfused: a pass-through transform is a copy)
   if (i.ops == AUTO) return 1000 + (int)i.galois;                                                          // 1000+: automorphism, by element
+  if (i.ops == NTT && i.liftSrcMod != kNoLift) return 5700;                                                // 5700: forward transform of a lifted input (ModRaise): never with plain ones
   return (int)i.ops + (i.secondOnly ? 5000 : 0) + (i.inMulB ? 5500 : 0);                                   // below 100: by op; 5000+: second pass only (7b); 5500+: product input (4p)
 }
 
@@ -635,8 +637,14 @@ void Arch::LaunchBuilder::transform(Launch &L, Recs recs) {
     L.hasK |= i->hasConstant;
     if (f->ops == INTT) L.outPacked.push_back(i->packedOut ? 1 : 0);
     if (f->inMulB) L.mulB.push_back(limb(i->inMulB));   // (the part key keeps product and plain inputs apart)
+    if (f->liftSrcMod != kNoLift) L.liftMods.push_back(i->liftSrcMod);   // (... and lifted and plain inputs)
   }
   L.bytes = (L.mulB.empty() ? 2 : 3) * LP * recs.size();
+  if (!L.liftMods.empty()) {   // many records read one source: every distinct source once, every output once
+    std::vector<uint32_t> src = L.a;
+    std::sort(src.begin(), src.end());
+    L.bytes = LP * ((size_t)(std::unique(src.begin(), src.end()) - src.begin()) + recs.size());
+  }
 }
 
 void Arch::LaunchBuilder::automorphism(Launch &L, Recs recs) {
@@ -1067,7 +1075,7 @@ void Arch::replicateForBatch() {
       }
       rep(l->a, true); rep(l->b, true); rep(l->c, true); rep(l->d, true);
       rep(l->out, true); rep(l->out1, true); rep(l->out2, true); rep(l->mods, false);
-      rep(l->inGalois, false); rep(l->addGalois, false); rep(l->mulB, true);
+      rep(l->inGalois, false); rep(l->addGalois, false); rep(l->mulB, true); rep(l->liftMods, false);
       for (std::vector<uint64_t> *kv : {&l->k, &l->mixK, &l->addK}) {
         const size_t k0 = kv->size();
         for (uint32_t c = 1; c < batch_; ++c)
@@ -1200,6 +1208,7 @@ std::string Arch::planText() const {
     }
     if (l->xGalois) out += " auto_x=g" + std::to_string(l->xGalois);
     if (!l->mulB.empty()) out += " mul=1";   // pass 4p: the input (INTT) / the minuend (fused forward transform) is a product formed while loading
+    if (!l->liftMods.empty()) out += " lift=1";   // ModRaise: the stored input is of another modulus, centred and reduced into the entry's own while loading
     if (!l->hoistG.empty()) {   // (6h): rotations of the hoisted key product and their elements
       out += " rot=" + std::to_string(l->hoistG.size()) + " g=";
       for (size_t r = 0; r < l->hoistG.size(); ++r) out += (r ? "," : "") + std::to_string(l->hoistG[r]);
@@ -1245,7 +1254,7 @@ std::string Arch::planDump() const {
     if (l->dotTerms) out += " terms=" + std::to_string(l->dotTerms);
     if (l->kind == Launch::L_IP_LINTRANS_MULTI) out += " multiOuts=" + std::to_string(l->multiOuts);   // (one sum: the line of L_IP_LINTRANS has no such field)
     vec("wait", l->waitSlots); vec("hoistG", l->hoistG); vec("ipCoeff", l->ipCoeff); vec("ipInv", l->ipInv); vec("outPacked", l->outPacked);
-    vec("inGalois", l->inGalois); vec("addGalois", l->addGalois); vec("mulB", l->mulB);
+    vec("inGalois", l->inGalois); vec("addGalois", l->addGalois); vec("mulB", l->mulB); vec("liftMods", l->liftMods);
     vec("idPt", l->idPt); vec("d1", l->d1);
     vec("a", l->a); vec("b", l->b); vec("c", l->c); vec("d", l->d); vec("out", l->out); vec("out1", l->out1); vec("out2", l->out2);
     vec("mods", l->mods); vec("inMods", l->inMods); vec("k", l->k); vec("mixK", l->mixK); vec("addK", l->addK);
@@ -1268,7 +1277,12 @@ void Arch::enqueue(Launch &l) {
   std::vector<hm_bconv_desc> descs;
   switch (l.kind) {
   case Launch::L_NTT:
-    st = hm_ntt(ctx, pool, l.a.data(), pool, l.out.data(), l.mods.data(), cnt, 0, nullptr);
+    if (!l.liftMods.empty()) {   // ModRaise: the inputs are stored limb-polys of other moduli
+      const hm_ntt_lift_desc m = {hm_ntt_desc{pool, l.a.data(), pool, l.out.data(), l.mods.data(), cnt, 0, nullptr, 0, nullptr, nullptr}, l.liftMods.data()};
+      st = hm_ntt_lift(ctx, &m);
+    } else {
+      st = hm_ntt(ctx, pool, l.a.data(), pool, l.out.data(), l.mods.data(), cnt, 0, nullptr);
+    }
     break;
   case Launch::L_INTT: {
     const bool anyPacked = std::find(l.outPacked.begin(), l.outPacked.end(), 1) != l.outPacked.end();

@@ -1001,6 +1001,41 @@ HRESCALE::HRESCALE(std::string labelName, uint32_t maxLevel, uint32_t currentLev
   finishConstruction();
 }
 
+// hmodraise (build extension): ModRaise of a level-1 ciphertext to level T (config key raise_to, default maxLevel).  Per
+// component k: c = INTT_{q_0}(ct1.c_k limb 0), then for every j < T out limb j = NTT_{q_j}(centre_{q_0}(c) mod q_j); the centring and the reduction
+// run inside the forward transform's first pass (liftSrcMod, hm_ntt_lift), so the 2 (T - 1) lifted limb-polys are never stored.  Limb 0 goes through
+// the same launch with source = target modulus: the identity, bit for bit.  Two stages, one launch each, at any batch
+HMODRAISE::HMODRAISE(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch)
+    : OperationBase("HMODRAISE", labelName, cfg, _arch, maxLevel, currentLevel, alpha) {
+  if (arch->backend() == Arch::BACKEND_SIM) throw std::runtime_error("hmodraise: backend = sim has no such op (the reference has no op that raises a level)");
+  if (arch->world() > 1) throw std::runtime_error("hmodraise: world > 1 is not supported (the sharded plan is not built)");
+  if (currentLevel != 1)
+    throw std::runtime_error("hmodraise: level " + S(currentLevel) + " is not supported, the input must be at level 1 (the overflow term of several input limbs is not built)");
+  const uint32_t T = cfg->getValueOr("raise_to", maxLevel);
+  if (T <= currentLevel || T > maxLevel)
+    throw std::runtime_error("hmodraise: raise_to = " + S(T) + ", must be above the input's level " + S(currentLevel) + " and at most maxLevel " + S(maxLevel));
+  makeInputs(1);
+  std::array<std::vector<AddrType>, 2> coeff, out;
+  std::vector<INSGROUP> intt, ntt;
+  for (uint32_t k = 0; k < 2; k++) {
+    coeff[k] = alloc("ModRaiseINTTOut(" + S(k) + ")", 1);
+    out[k] = alloc("HMODRAISEOutput(" + S(k) + ")", T);
+  }
+  INSGROUP none;   // the input is the op's own ciphertext: no instruction produces it
+  for (uint32_t k = 0; k < 2; k++)
+    intt.push_back(insgener.GenNTT(0, labelName + "_ModRaise_INTT_k(" + S(k) + ")", &none, false, component(0, k)[0], coeff[k][0], 0));
+  driver.dispatchInstructions("ModRaise_INTT", intt);
+  for (uint32_t k = 0; k < 2; k++)
+    for (uint32_t j = 0; j < T; j++) {
+      INSGROUP g = insgener.GenNTT(j, labelName + "_ModRaise_NTT_Level(" + S(j) + ")_k(" + S(k) + ")", &intt[k], true, coeff[k][0], out[k][j], j);
+      g[0]->liftSrcMod = 0;   // the stored coefficients are reduced by q_0
+      ntt.push_back(g);
+    }
+  driver.dispatchInstructions("ModRaise_NTT", ntt);
+  for (uint32_t k = 0; k < 2; k++) setOutput("out", k, out[k]);
+  finishConstruction();
+}
+
 // reference: PADD::PADD :1625-1680 (upstream adds the plaintext to both components; only c0 takes it)
 PADD::PADD(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch)
     : OperationBase("PADD", labelName, cfg, _arch, maxLevel, currentLevel, alpha) {
@@ -1030,6 +1065,7 @@ static OperationBase *makeOp(const std::string &o, uint32_t maxLevel, uint32_t l
   if (o == "hrotsum") return new HROTSUM("test_hrotsum", maxLevel, level, alpha, cfg, arch);
   if (o == "hbsgs") return new HBSGS("test_hbsgs", maxLevel, level, alpha, cfg, arch);
   if (o == "hrescale") return new HRESCALE("test_hrescale", maxLevel, level, alpha, cfg, arch);
+  if (o == "hmodraise") return new HMODRAISE("test_hmodraise", maxLevel, level, alpha, cfg, arch);
   throw std::runtime_error("Error operation requirement, please double confirm!");
 }
 

@@ -403,6 +403,18 @@ typedef struct hm_ntt_mul_desc {
   const uint64_t *in_b; const uint32_t *in_b_limbs;
 } hm_ntt_mul_desc;
 hm_status hm_ntt_mul(hm_ctx *ctx, const hm_ntt_mul_desc *desc);
+/* The forward transform of a LIFTED input (ModRaise): in_i is a stored limb-poly in coefficient form, reduced by the modulus src_mod_ids[i]; its
+ * centred representative (c if c <= (q_s - 1) / 2, else c - q_s) is reduced into [0, q) of mod_ids[i] while the first pass loads, and transformed:
+ *     out_i = NTT_{mod_ids[i]}( centre_{src_mod_ids[i]}(in_i) mod q_{mod_ids[i]} )
+ * Many entries may name the same `in` limb-poly (one source, every modulus of the raised chain); src_mod_ids[i] == mod_ids[i] is the plain forward
+ * transform, bit for bit.  Forward only; not with inverse, second_pass_only, in_galois, scale or out_packed (HM_ERR_UNSUPPORTED).  `out` must not
+ * overlap any limb-poly of `in` (HM_ERR_ARG; compared by address range, not by base pointer).  src_mod_ids are checked as mod_ids are.
+ * Replaces: nothing upstream: the reference has no op that raises a level. */
+typedef struct hm_ntt_lift_desc {
+  hm_ntt_desc t;
+  const uint32_t *src_mod_ids;
+} hm_ntt_lift_desc;
+hm_status hm_ntt_lift(hm_ctx *ctx, const hm_ntt_lift_desc *desc);
 
 /* K4 — fast base conversion, matrix step: out_t = sum_i in_i * [Q_D / q_i]_t mod t for the input
  * basis in_ids (n_in <= 32) and output basis out_ids (n_out <= 64).  `in` must already hold
