@@ -497,6 +497,12 @@ __global__ void __launch_bounds__(256) k_tensor_dot(HmTensorDotArgs a) {
   if (entry < a.n_limbs) hm_tensor_dot_thread(a, entry, blockIdx.x & ((1u << logPer) - 1u), threadIdx.x);
 }
 
+// scaled square of one ciphertext plus a constant (hm_elem_core.h: hm_tensor_square_thread): k_tensor's geometry, the records in a device table
+__global__ void __launch_bounds__(256) k_tensor_square(HmTensorSqArgs a) {
+  const uint32_t logPer = a.logN - 9, entry = blockIdx.x >> logPer;
+  if (entry < a.n_limbs) hm_tensor_square_thread(a, entry, blockIdx.x & ((1u << logPer) - 1u), threadIdx.x);
+}
+
 // 16-byte units per thread of the element-wise kernel, 512 coefficients apart, all loads in flight before the first use.  1: 89 600 workgroups for a batch of
 // ten hadd; 2 / 4 measured padd +3 / +5 %, pmult +1 %, hadd within the noise (tools/r06_ewe_ab.sh): not worth a second shape of the kernel's launch
 #ifndef HM_EWE_UNITS
@@ -1770,6 +1776,61 @@ extern "C" hm_status hm_tensor_dot(hm_ctx *c, const uint64_t *pa, const uint32_t
   return HM_OK;
 }
 
+// scaled square of one ciphertext plus a constant: one record per entry in a device table, ONE launch for any n
+extern "C" hm_status hm_tensor_square(hm_ctx *c, const uint64_t *pa, const uint32_t *la, const uint64_t *pc, const uint32_t *lc, uint64_t *o0,
+                                      const uint32_t *l0, uint64_t *o1, const uint32_t *l1, uint64_t *o2, const uint32_t *l2,
+                                      const uint32_t *mod_ids, uint32_t n, const uint64_t *scale, const uint64_t *addend) {
+  static const char *const what = "hm_tensor_square";
+  if (!c) return HM_ERR_ARG;
+  HM_TABLE_CALL(c);
+  if (!pa || !pc || !o0 || !o1 || !o2) return fail(c, HM_ERR_ARG, "%s: null buffer", what);
+  const uint32_t N = c->P.N;
+  if ((uint64_t)n > 0xFFFFFFFFull / sizeof(HmTensorSqRec)) return fail(c, HM_ERR_ARG, "%s: n = %u entries are too many for one call", what, n);
+  struct List { const char *name; const void *base; const uint32_t *limbs; uint32_t count; };
+  const List ins[2] = {{"a", pa, la, n}, {"c", pc, lc, n}};
+  const List outs[3] = {{"o0", o0, l0, n}, {"o1", o1, l1, n}, {"o2", o2, l2, n}};
+  hm_status st;
+  for (const List &l : ins)
+    if ((st = check_limbs(c, what, l.limbs, l.count))) return st;
+  for (const List &l : outs)
+    if ((st = check_limbs(c, what, l.limbs, l.count))) return st;
+  if ((st = check_mods(c, what, mod_ids, n))) return st;
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint64_t q = c->P.mod[mod_ids[i]];
+    if (scale && (scale[i] == 0 || scale[i] >= q)) return fail(c, HM_ERR_ARG, "%s: scale[%u] is %s", what, i, scale[i] ? "not reduced" : "zero");
+    if (addend && addend[i] >= q) return fail(c, HM_ERR_ARG, "%s: addend[%u] is not reduced", what, i);
+  }
+  // a workgroup stores its three outputs after both loads, and one input limb-poly may serve several records: no output may share an address
+  // with an input or with another output (hm_tensor_dot's rule and messages)
+  for (const List &o : outs)
+    for (const List &i : ins)
+      if (hm_limbs_overlap(o.base, o.limbs, o.count, i.base, i.limbs, i.count, N))
+        return fail(c, HM_ERR_ARG, "%s: an output limb-poly (%s) overlaps an input limb-poly (%s)", what, o.name, i.name);
+  {
+    std::vector<uintptr_t> starts;
+    for (const List &o : outs)
+      for (uint32_t i = 0; i < o.count; ++i) starts.push_back(reinterpret_cast<uintptr_t>(o.base) + (uintptr_t)limb_at(o.limbs, i) * N * 8);
+    std::sort(starts.begin(), starts.end());
+    for (size_t i = 1; i < starts.size(); ++i)
+      if (starts[i] - starts[i - 1] < (uintptr_t)N * 8) return fail(c, HM_ERR_ARG, "%s: two output limb-polys overlap", what);
+  }
+  if (n == 0) return HM_OK;
+  std::vector<HmTensorSqRec> recs(n);
+  std::vector<uint64_t> qs(n);
+  for (uint32_t i = 0; i < n; ++i) qs[i] = c->P.mod[mod_ids[i]];
+  hm_tensor_square_fill_recs(recs.data(), la, lc, l0, l1, l2, mod_ids, qs.data(), n, scale, addend);
+  HM_HIP(c, hipSetDevice(c->device));
+  HmTensorSqArgs a;
+  const void *tab = nullptr;
+  if ((st = device_table(c, recs.data(), recs.size() * sizeof(HmTensorSqRec), &tab))) return st;
+  a.rec = static_cast<const HmTensorSqRec *>(tab);
+  a.a = pa; a.c = pc; a.o0 = o0; a.o1 = o1; a.o2 = o2;
+  a.mods = c->d_mods; a.logN = c->P.logN; a.n_limbs = n;
+  hipLaunchKernelGGL(k_tensor_square, dim3(n * (N / 512)), dim3(256), 0, c->stream, a);
+  HM_HIP(c, hipGetLastError());
+  return HM_OK;
+}
+
 extern "C" hm_status hm_automorph(hm_ctx *c, const uint64_t *in, const uint32_t *in_limbs, uint64_t *out,
                                   const uint32_t *out_limbs, uint32_t n, uint32_t galois) {
   if (!c) return HM_ERR_ARG;
@@ -1809,7 +1870,7 @@ extern "C" hm_status hm_ewe(hm_ctx *c, int op, const uint64_t *pa, const uint32_
   const int uses = hm_ewe_uses(op);
   if (((uses & 1) && !pa) || ((uses & 2) && !pb) || ((uses & 4) && !pc) || ((uses & 8) && !pd) || !out)
     return fail(c, HM_ERR_ARG, "hm_ewe: opcode %d is missing an operand", op);
-  const bool needs_k = op == HM_EWE_MUL_CONST || op == HM_EWE_SUB_SCALE || op == HM_EWE_SUB_SCALE_ADD;
+  const bool needs_k = op == HM_EWE_MUL_CONST || op == HM_EWE_SUB_SCALE || op == HM_EWE_SUB_SCALE_ADD || op == HM_EWE_ADD_CONST;
   if (needs_k && !k) return fail(c, HM_ERR_ARG, "hm_ewe: opcode %d needs constants", op);
   hm_status st;
   if ((st = check_limbs(c, "hm_ewe", la, n)) || (st = check_limbs(c, "hm_ewe", lb, n)) ||

@@ -24,6 +24,7 @@ enum HmEweOp {
   HM_EWE_SUB_SCALE = 6,  // out = (a - c)*k
   HM_EWE_COPY = 7,       // out = a
   HM_EWE_SUB_SCALE_ADD = 8,  // out = (a - c)*k + d   (ModDown finish fused with the final add)
+  HM_EWE_ADD_CONST = 9,  // out = a + k         (a constant polynomial added to evaluation-form entries; k.w holds the residue on both back-ends)
   HM_EWE_NOPS
 };
 
@@ -50,6 +51,7 @@ HM_HD uint64_t hm_ewe_one(uint64_t a, uint64_t b, uint64_t c, uint64_t d, const 
   case HM_EWE_MUL_CONST: return hm_shoup(a, k.w, k.ws, m.q);
   case HM_EWE_SUB_SCALE: return hm_shoup(a - c + m.q, k.w, k.ws, m.q);
   case HM_EWE_SUB_SCALE_ADD: return hm_addmod(hm_shoup(a - c + m.q, k.w, k.ws, m.q), d, m.q);
+  case HM_EWE_ADD_CONST: return hm_addmod(a, k.w, m.q);
   default: return a;
   }
 }
@@ -58,7 +60,7 @@ HM_HD uint64_t hm_ewe_one(uint64_t a, uint64_t b, uint64_t c, uint64_t d, const 
 HM_HD constexpr int hm_ewe_uses(int op) {
   return op == HM_EWE_MUL ? 3 : op == HM_EWE_MAC2 ? 15 : op == HM_EWE_MAC_ADD ? 7 :
          op == HM_EWE_ADD ? 5 : op == HM_EWE_SUB ? 5 : op == HM_EWE_MUL_CONST ? 1 :
-         op == HM_EWE_SUB_SCALE ? 5 : op == HM_EWE_SUB_SCALE_ADD ? 13 : 1;
+         op == HM_EWE_SUB_SCALE ? 5 : op == HM_EWE_SUB_SCALE_ADD ? 13 : 1;   // (COPY, ADD_CONST: a)
 }
 
 // tensor product of two ciphertexts in one pass over the four inputs (TensorCompute::computeD0/D1/D2,
@@ -310,6 +312,90 @@ HM_HD void hm_tensor_dot_thread(const HmTensorDotArgs &g, uint32_t entry, uint32
   hm_bst2(g.o0 + rec[1] * N, lane_bytes, hm_barrett_wide(s[0].d0, m), hm_barrett_wide(s[1].d0, m));
   hm_bst2(g.o1 + rec[2] * N, lane_bytes, hm_barrett_wide(s[0].d1, m), hm_barrett_wide(s[1].d1, m));
   hm_bst2(g.o2 + rec[3] * N, lane_bytes, hm_barrett_wide(s[0].d2, m), hm_barrett_wide(s[1].d2, m));
+}
+
+// Scaled square of ONE ciphertext plus a constant, in one pass over its two polynomials (hm_tensor_square; HSQUARE):
+//   d0 = s a a + k,  d1 = 2 s a c,  d2 = s c c      with a = c0, c = c1, s in [1, q) and k in [0, q) per entry, every residue canonical.
+// The tensor product of a ciphertext with itself needs two loads and five products where hm_tensor_one, fed the same operands twice, takes
+// four and six; the scalar and the constant are linear and act in front of the key switch, so they are applied here, in registers.
+// A record = 64 bytes (a multiple of 16), read through the scalar cache (wave-uniform index).  The per-entry constants are stored in the form
+// the arithmetic takes (hm_tensor_square_fill_recs).  mont32: scale = s 2^128 mod q, which takes the place of m.r128 in the step to Montgomery
+// form, so that the scalar costs no product at all.  generic: scale = s with its Shoup companion scale_s = floor(s 2^64 / q): a and c are
+// multiplied by s once, by two Shoup products, in front of the three Barrett products.  addend = k on both.
+struct HmTensorSqRec {
+  uint32_t mod, a, c, o0, o1, o2;
+  uint32_t scaled, pad;   // generic: s != 1 (a limb-uniform branch skips the two products by s)
+  uint64_t scale, scale_s, addend, pad1;
+};
+static_assert(sizeof(HmTensorSqRec) == 64 && offsetof(HmTensorSqRec, scale) == 32, "HmTensorSqRec: layout");
+struct HmTensorSqArgs {
+  const uint64_t *a, *c;
+  uint64_t *o0, *o1, *o2;
+  const HmMod *mods;
+  const HmTensorSqRec *rec;   // device, [n_limbs]
+  uint32_t logN, n_limbs;
+};
+// host: the record form of the scalar s in [1, q)
+inline uint64_t hm_tensor_square_scale(uint64_t s, uint64_t q) { return HM_GENERIC ? s : hm_to_mont(hm_to_mont(s, q), q); }
+// The records of n entries from the entry point's limb lists (a null list is the identity) and constants (scale null: 1, addend null: 0; both
+// already checked: reduced, scale != 0); q[i] = the modulus of entry i.  Host side.
+inline void hm_tensor_square_fill_recs(HmTensorSqRec *rec, const uint32_t *la, const uint32_t *lc, const uint32_t *l0, const uint32_t *l1, const uint32_t *l2,
+                                       const uint32_t *mod_ids, const uint64_t *q, uint32_t n, const uint64_t *scale, const uint64_t *addend) {
+  auto at = [](const uint32_t *l, uint32_t i) { return l ? l[i] : i; };
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint64_t s = scale ? scale[i] : 1;
+    rec[i] = HmTensorSqRec{mod_ids[i], at(la, i), at(lc, i), at(l0, i), at(l1, i), at(l2, i), s != 1 ? 1u : 0u, 0u, hm_tensor_square_scale(s, q[i]),
+                           HM_GENERIC ? hm_shoup_companion(s, q[i]) : 0, addend ? addend[i] : 0, 0};
+  }
+}
+// mont32, with the bound of hm_mont_acc (v <= floor(x wt / 2^64) + q + h + 1, h = q >> 32 < 2^28, for x < 2^63 and no sum above 2^64) and the
+// largest modulus the back-end accepts, q < 2^60:
+//   at, ct   = a, c (x) st with a, c, st < q: floor(q q / 2^64) < q / 16, so at, ct < 1.0625 q + 2^28 + 1 < 2^61  (a s 2^64 mod q + {0, q})
+//   a (x) at, c (x) at, c (x) ct with the left operand below q: floor(q (1.0625 q + 2^28 + 1) / 2^64) < 0.07 q, so each is below 1.07 q + 2^28 + 1
+//            < 2 q: ONE conditional subtraction leaves the canonical residue (s a a, s a c, s c c: x wt 2^-64 with wt = y s 2^64)
+//   2 x with x < q is below 2 q, and d0 + k with d0, k < q is below 2 q: one conditional subtraction each
+//   inside hm_mont_acc, wt < 2^61: b0 w1 < 2^61, b1 w0 < 2^60, (~P0) h < 2^60, cc < 2^60 + 2^33, a sum below 2^63.
+// generic: as = s a and cs = s c by the exact Shoup product (canonical, for any 64-bit operand), then three Barrett products of canonical operands.
+HM_HD void hm_tensor_square_one(uint64_t a, uint64_t c, uint64_t scale, uint64_t scale_s, uint32_t scaled, uint64_t addend, const HmMod &m, uint64_t &d0,
+                                uint64_t &d1, uint64_t &d2) {
+#if HM_GENERIC
+  uint64_t as = a, cs = c;
+  if (scaled) {   // (limb-uniform)
+    as = hm_shoup(a, scale, scale_s, m.q);
+    cs = hm_shoup(c, scale, scale_s, m.q);
+  }
+  d0 = hm_mulmod(as, a, m);
+  const uint64_t x = hm_mulmod(as, c, m);
+  d2 = hm_mulmod(cs, c, m);
+  d1 = hm_csub(x + x, m.q);
+  d0 = hm_csub(d0 + addend, m.q);
+#else
+  (void)scaled; (void)scale_s;
+  const HmBflyMod bm = hm_bfly_mod(m.q);
+  const uint64_t at = hm_mont_acc(0, a, scale, bm), ct = hm_mont_acc(0, c, scale, bm);   // below 1.0625 q + 2^28 + 1
+  d0 = hm_csub_neg(hm_mont_acc(0, a, at, bm), bm.nq);                                    // lazy: below 1.07 q + 2^28 + 1
+  const uint64_t x = hm_csub_neg(hm_mont_acc(0, c, at, bm), bm.nq);
+  d2 = hm_csub_neg(hm_mont_acc(0, c, ct, bm), bm.nq);
+  d1 = hm_csub_neg(x + x, bm.nq);          // below 2 q
+  d0 = hm_csub_neg(d0 + addend, bm.nq);    // below 2 q
+#endif
+}
+// thread tid of the workgroup that owns chunk `chunk` (512 coefficients) of record `entry`: two 16-byte loads, three 16-byte stores
+HM_HD void hm_tensor_square_thread(const HmTensorSqArgs &g, uint32_t entry, uint32_t chunk, uint32_t tid) {
+  const size_t N = (size_t)1 << g.logN;
+  const uint32_t lane_bytes = (chunk * 512u + 2u * tid) << 3;
+  const auto r = HM_CONST_PROB_T(HmTensorSqRec, g.rec) + entry;
+  const HmMod m = HM_CONST_MODS(g.mods)[r->mod];
+  const uint64_t scale = r->scale, scale_s = r->scale_s, addend = r->addend;
+  const uint32_t scaled = r->scaled;
+  uint64_t a[2], c[2], d0[2], d1[2], d2[2];
+  hm_bld2(g.a + r->a * N, lane_bytes, a[0], a[1]);
+  hm_bld2(g.c + r->c * N, lane_bytes, c[0], c[1]);
+  hm_tensor_square_one(a[0], c[0], scale, scale_s, scaled, addend, m, d0[0], d1[0], d2[0]);
+  hm_tensor_square_one(a[1], c[1], scale, scale_s, scaled, addend, m, d0[1], d1[1], d2[1]);
+  hm_bst2(g.o0 + r->o0 * N, lane_bytes, d0[0], d0[1]);
+  hm_bst2(g.o1 + r->o1 * N, lane_bytes, d1[0], d1[1]);
+  hm_bst2(g.o2 + r->o2 * N, lane_bytes, d2[0], d2[1]);
 }
 
 // The conversion table is read through the SCALAR cache: every lane of a wave needs the same entries, so they are

@@ -11,7 +11,7 @@ LIB_PATH = os.environ.get("HOMULATOR_HIP_LIB") or os.path.join(_HERE, "lib", "li
 # primes h 2^32 + 1 (the default), Shoup / Barrett for any other NTT-friendly chain below 2^60
 BACKEND_LIBS = ("libhm_m32.so", "libhm_gen.so")
 
-OP_MUL, OP_MAC2, OP_MAC_ADD, OP_ADD, OP_SUB, OP_MUL_CONST, OP_SUB_SCALE, OP_COPY, OP_SUB_SCALE_ADD = range(9)
+OP_MUL, OP_MAC2, OP_MAC_ADD, OP_ADD, OP_SUB, OP_MUL_CONST, OP_SUB_SCALE, OP_COPY, OP_SUB_SCALE_ADD, OP_ADD_CONST = range(10)
 NO_LIMB = 0xFFFFFFFF   # HM_NO_LIMB: "this entry has no such operand" in an optional limb list
 LINTRANS_MULTI_TILE = 2   # HM_IP_LINTRANS_MULTI_TILE: outputs a workgroup of hm_inner_product_lintrans_multi serves
 
@@ -25,7 +25,7 @@ SYMBOLS = [
     "hm_bconv_col", "hm_limbs_to_colslices", "hm_colslices_to_limbs", "hm_ntt_second_pass", "hm_ntt_ex", "hm_capability", "hm_inner_product_ex",
     "hm_inner_product_hoisted", "hm_inner_product_lintrans", "hm_inner_product_rotsum", "hm_inner_product_lintrans_multi",
     "hm_tensor_dot", "hm_inner_product_lintrans_id", "hm_inner_product_rotsum_init", "hm_ntt_mix_sub_scale_mul", "hm_ntt_mul",
-    "hm_ntt_lift",
+    "hm_ntt_lift", "hm_tensor_square",
 ]
 
 
@@ -159,6 +159,7 @@ def load():
     L.hm_ntt_lift.argtypes = [vp, C.POINTER(hm_ntt_lift_desc)]
     L.hm_tensor.argtypes = [vp] + [vp] * 15 + [u32]
     L.hm_tensor_dot.argtypes = [vp] + [vp] * 15 + [u32, u32]
+    L.hm_tensor_square.argtypes = [vp] + [vp] * 11 + [u32, vp, vp]
     L.hm_inner_product.argtypes = [vp] + [vp] * 7 + [u32, u32, u32]
     L.hm_automorph.argtypes = [vp, vp, vp, vp, vp, u32, u32]
     L.hm_ewe.argtypes = [vp, i32] + [vp] * 11 + [u32, vp]
@@ -390,6 +391,16 @@ class Context:
         keep = [_u32(x) for x in ls] + [_u32(mod_ids)]
         self._ck(self.L.hm_tensor_dot(self.h, a.ptr, keep[0][1], b.ptr, keep[1][1], c.ptr, keep[2][1], d.ptr, keep[3][1], o0.ptr, keep[4][1],
                                       o1.ptr, keep[5][1], o2.ptr, keep[6][1], keep[7][1], len(mod_ids), int(n_terms)))
+
+    def tensor_square(self, a, c, o0, o1, o2, mod_ids, scale=None, addend=None, limbs=None):
+        """o0 = s * a * a + k, o1 = 2 * s * a * c, o2 = s * c * c per entry, s = scale[i] (None: 1) and k = addend[i] (None: 0) residues of the
+        entry's modulus (hm_tensor_square).  limbs: the five limb lists in argument order (None: the identity), [n] each; buffers: anything with
+        a device address `.ptr`"""
+        ls = limbs or [None] * 5
+        keep = [_u32(x) for x in ls] + [_u32(mod_ids)]
+        ks, ka = _u64(scale), _u64(addend)
+        self._ck(self.L.hm_tensor_square(self.h, a.ptr, keep[0][1], c.ptr, keep[1][1], o0.ptr, keep[2][1], o1.ptr, keep[3][1], o2.ptr, keep[4][1],
+                                         keep[5][1], len(mod_ids), ks[1], ka[1]))
 
     def inner_product(self, x, x_limbs, y, y_limbs, out, out_limbs, mod_ids, n_terms, n_out, x_galois=0):
         keep = [_u32(v) for v in (x_limbs, y_limbs, out_limbs, mod_ids)]

@@ -33,6 +33,7 @@ def load():
         L.hh_op_simulate.argtypes = [vp]
         L.hh_op_execute.argtypes = [vp, u32, C.POINTER(C.c_double)]
         L.hh_op_write_buffer.argtypes = [vp, C.c_char_p, u32, vp]
+        L.hh_op_set_constants.argtypes = [vp, C.c_char_p, vp, u32]
         L.hh_op_sim_run.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
         L.hh_op_sim_stats.argtypes = [vp, C.c_char_p, u32]
         L.hh_op_enqueue.argtypes = [vp, u32]
@@ -142,6 +143,12 @@ class Op:
         if a.shape != (n.value, self.N):
             raise HostError(f"{name}: expected shape {(n.value, self.N)}, got {a.shape}")
         self._ck(self.L.hh_op_write_buffer(self.h, name.encode(), copy, a.ctypes.data_as(C.c_void_p)))
+
+    def set_constants(self, name, values):
+        """replace the op's per-limb constants `name` (hsquare: "scale", "const") by one residue per limb of the current level, before the op
+        is prepared (hh_op_set_constants); shared by the ops of a batch"""
+        a = np.ascontiguousarray(np.asarray([int(v) for v in values], dtype=np.uint64))
+        self._ck(self.L.hh_op_set_constants(self.h, name.encode(), a.ctypes.data_as(C.c_void_p), len(a)))
 
     def sim_run(self):
         """backend = BACKEND_SIM: run the cycle model of the reference accelerator to completion.

@@ -89,6 +89,7 @@ public:
 
   // ---- whole-plan execution (bench / tests): prepare once, run many times
   void prepare();                       // allocate HBM, fill inputs, fuse and coalesce stages into launches
+  bool isPrepared() const { return prepared; }   // the plan is built: the records' constants are in the launches
   void run();                           // enqueue every launch once (asynchronous)
   void sync();
   double timedRun(uint32_t iters);      // ns per iteration, device time
@@ -129,6 +130,7 @@ private:
   bool fuseBsgs = true;      // pass (6m): ... and M >= 2 such sums over the same rotations share the key products (hbsgs)
   bool fuseRotsum = true;    // pass (6s): the key products of rotations of different ciphertexts are summed before anything is stored (hrotsum)
   bool fuseDot = true;       // pass (5d): the tensor products of several pairs of ciphertexts are summed before anything is stored (hdot)
+  bool fuseSquare = true;    // pass (5q): the tensor product of a ciphertext with itself reads it once and takes the scalar and the constant behind it (hsquare)
   bool fusePmulRescale = true;   // pass (4p): a product of two op inputs read by one transform is formed by that transform (pmult with rescale = 1)
   bool fusePmulAuto = true;      // ... the key is not given: the pass declines where it was measured no faster (the generic back-end's small launches)
   bool genericArith = false;     // config key chain_bits: the chain hm_create serves with the generic arithmetic back-end

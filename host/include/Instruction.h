@@ -13,7 +13,7 @@ extern std::vector<std::string> ins_ops_name;
 // the arithmetic of an EWE ("MULT"-tagged) instruction; numbering = include/homulator_hip.h hm_ewe_op
 enum ewe_opcode {
   EWE_MUL = 0, EWE_MAC2 = 1, EWE_MAC_ADD = 2, EWE_ADD = 3, EWE_SUB = 4,
-  EWE_MUL_CONST = 5, EWE_SUB_SCALE = 6, EWE_COPY = 7, EWE_SUB_SCALE_ADD = 8
+  EWE_MUL_CONST = 5, EWE_SUB_SCALE = 6, EWE_COPY = 7, EWE_SUB_SCALE_ADD = 8, EWE_ADD_CONST = 9
 };
 
 static const uint32_t kNoLift = 0xFFFFFFFFu;   // Instruction::liftSrcMod of a plain forward transform
@@ -32,6 +32,7 @@ public:
   uint32_t galois = 0;
   bool passthrough = false;  // an NTT-kind instruction whose input is already in evaluation form (copy)
   bool sumHead = false;      // a tensor product's MAC2 (d1) that is pair 1 of a SUM of tensor products (HDOT): pass (5d) starts its record here
+  bool squareHead = false;   // a tensor product's MAC2 (d1) of a ciphertext with ITSELF (HSQUARE): pass (5q) starts its record here
   std::vector<uint32_t> inMods;  // BCONV: modulus ids of the inputs
   unsigned long long refInstructions = 0;  // upstream instructions this record stands for
   unsigned long long refExtra = 0;         // ... of records folded into a BCONV record (not scaled by its MAC-port count)
@@ -67,6 +68,12 @@ public:
   // (5d) sum of tensor products (hm_tensor_dot): a fusedTensor record that absorbed the chains behind its three outputs.  dotOperands = (c00, c10,
   // c01, c11) of every pair, pair 1 first; OutputOperand = the final d1, extraOutputs = the final d0, d2.  Empty: a plain tensor product
   std::vector<AddrType> dotOperands;
+  // (5q) scaled square plus constant (hm_tensor_square): a fusedTensor record of a ciphertext with itself.  sqOperands = (c0, c1): its two reads;
+  // OutputOperand = the final d1, extraOutputs = the final d0, d2.  sqHasScale: the MUL_CONST records behind its three outputs went in, all
+  // with the constant sqScale; sqHasConst: the ADD_CONST record behind d0 went in, with the constant sqConst.  sqOperands empty: not a square
+  std::vector<AddrType> sqOperands;
+  bool sqHasScale = false, sqHasConst = false;
+  uint64_t sqScale = 1, sqConst = 0;
   // fused inner product (ops == IP): out_k = sum_j ipX[j] * ipY[k][j]; out_0 = OutputOperand, out_1 = extraOutputs[0]
   std::vector<AddrType> ipX;
   std::vector<std::vector<AddrType>> ipY;

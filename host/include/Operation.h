@@ -146,6 +146,13 @@ protected:
   bool rescaleKey(const std::string &op) const;
   // <out>.c<k> = Rescale(ct[k]), builder labels <label>_<k>, as HMULT's tail: the tail of the ops with rescale = 1, and all of HRESCALE
   void setRescaledOutput(const std::string &out, const std::array<std::vector<AddrType>, 2> &ct, bool inputMayBeOpInput = false);
+  // HMULT's tail on the three polynomials d of a tensor product (shared by HMULT, HDOT, HSQUARE): KS(d[2]); HMULT_Hadd_Key(k): d[k] + ks_k into
+  // HMULTHaddOutput(k); Rescale of both, out = the result at level - 1
+  void relinearizeAndRescale(const std::array<std::vector<AddrType>, 3> &d);
+  // Per-limb constants an op carries in its records (HSQUARE: "scale", "const"), by name: the records of limb j that hold value j, so that
+  // setConstants can patch Instruction::constant before the plan is built.  enabled = false: the op knows the name but its config key is 0
+  struct ConstantStage { bool enabled = false; std::string key; std::vector<std::vector<Instruction *>> records; bool nonZero = false; };
+  std::map<std::string, ConstantStage> constantStages;
   std::vector<AddrType> alloc(const std::string &name, uint32_t limbs);  // MallocMem + getAddr
   std::vector<AddrType> component(uint32_t ct, uint32_t k) const { return k == 0 ? cts[ct].getC0Addr() : cts[ct].getC1Addr(); }  // c_k of input ct
   void setOutput(const std::string &out, uint32_t k, const std::vector<AddrType> &limbs) { namedOutputs[out + ".c" + std::to_string(k)] = limbs; }
@@ -186,6 +193,9 @@ public:
   bool readBuffer(const std::string &name, uint64_t *host, uint32_t copy = 0);  // copy: op of the batch (config key `batch`)
   bool writeBuffer(const std::string &name, const uint64_t *host, uint32_t copy = 0);  // real data for an input / key buffer ([limbs][N], fully reduced)
   unsigned long long totalInstructions();
+  // replaces the per-limb constants `name` of the op (HSQUARE: "scale", "const") by n = level residues, values[j] reduced mod q_j; before prepare() only.
+  // Refused, by op and name: after prepare(), n != level, an unreduced value (or a zero where the constant multiplies), a name whose config key is 0
+  void setConstants(const std::string &name, const uint64_t *values, uint32_t n);
   Arch *getArch() { return arch; }
   std::vector<std::string> bufferNames() const;
   // continuous execution: this op's input ciphertext `input` ("ct1", "ct2") is the output ciphertext of `producer`
@@ -225,6 +235,15 @@ public:
 // hrotsum (build extension): sum_i rot_{g^i}(ct<i>) over G DIFFERENT ciphertexts (config keys rotations = G and galois = g as hrotate_hoisted, same
 // keys IP_Rot<i>_Key<k>_<j>), with G ModUps and ONE ModDown: the key products are summed on the extended basis.  One output ciphertext out at the
 // inputs' level; no rescale.
+// hsquare (build extension): out = Rescale(Relin(s * ct1^2) + k), one double-angle step y <- 2 y^2 - 1 of EvalMod with s = 2, k = -Delta^2.  The tensor
+// product of ct1 with ITSELF (d0 = a a, d1 = 2 a c, d2 = c c), then with config key sq_scale = 1 the per-limb scalars s_j on all three (synthetic:
+// word 0 of limb j of stream seed + 6000, a 0 replaced by 1) and with sq_const = 1 the per-limb constants k_j on every evaluation-form entry of d0
+// (stream seed + 6100), then HMULT's tail with hmult's key IP_Key<k>_<j>.  setConstants("scale" | "const") replaces the synthetic values.  One
+// input, one output ciphertext out at level - 1.  With both keys 0 bit-identical to hmult of ct1 with itself.
+class HSQUARE : public OperationBase {
+public:
+  HSQUARE(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
+};
 class HROTSUM : public OperationBase {
 public:
   HROTSUM(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
@@ -272,7 +291,7 @@ class OpChain {
   std::vector<Arch *> archs;
   std::vector<OperationBase *> ops;
 public:
-  // ops: comma-separated list of hmult | hrotate | hadd | pmult | padd | hlintrans | hdot | hrotsum | hbsgs | hrescale | hmodraise, e.g. "hmult,hrotate,hadd,hmult"; hrotate_hoisted (R output
+  // ops: comma-separated list of hmult | hrotate | hadd | pmult | padd | hlintrans | hdot | hrotsum | hbsgs | hrescale | hmodraise | hsquare, e.g. "hmult,hrotate,hadd,hmult"; hrotate_hoisted (R output
   // ciphertexts) only as the last op
   OpChain(const std::string &cfgPath, const std::string &opList, uint32_t maxLevel, uint32_t curLevel, uint32_t alpha,
           const std::map<std::string, uint32_t> &overrides = {});

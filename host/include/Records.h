@@ -9,7 +9,7 @@
 
 // operands of operandList[0..3] an EWE opcode reads, as a bit mask (index: ewe_opcode)
 inline int eweOperandMask(ewe_opcode op) {
-  static const int m[9] = {3, 15, 7, 5, 5, 1, 5, 1, 13};
+  static const int m[10] = {3, 15, 7, 5, 5, 1, 5, 1, 13, 1};
   return m[op];
 }
 
@@ -84,6 +84,8 @@ inline std::vector<Read> recordReads(const Instruction &i) {
     for (size_t x = 0; x + 1 < i.operandList.size(); ++x) v.push_back({i.operandList[x], Role::ConvIn, kNoDigit});
   } else if (!i.dotOperands.empty()) {   // (5d): the operands of every pair, pair 1's (operandList) among them
     for (AddrType a : i.dotOperands) v.push_back({a, Role::Operand, kNoDigit});
+  } else if (!i.sqOperands.empty()) {    // (5q): the two polynomials of the one ciphertext, each read once
+    for (AddrType a : i.sqOperands) v.push_back({a, Role::Operand, kNoDigit});
   } else if (i.ops == MULT) {
     for (int b = 0; b < 4; ++b)
       if (eweOperandMask(i.opcode) & (1 << b)) v.push_back({i.operandList[b], Role::Operand, kNoDigit});

@@ -28,7 +28,8 @@ struct Arch::Launch {
               L_IP_LINTRANS,                                 // (6l) ... and their plaintext-weighted sum
               L_TENSOR_DOT,                                  // (5d) the tensor products of several pairs of ciphertexts, summed
               L_IP_ROTSUM,                                   // (6s) the key products of rotations of different ciphertexts, summed
-              L_IP_LINTRANS_MULTI } kind;                    // (6m) several plaintext-weighted sums of the same hoisted key products
+              L_IP_LINTRANS_MULTI,                           // (6m) several plaintext-weighted sums of the same hoisted key products
+              L_TENSOR_SQUARE } kind;                        // (5q) the scaled square of one ciphertext plus a constant
   std::vector<uint32_t> hoistG;   // L_IP_HOISTED: the Galois element of every rotation (a: digits [n][T], b: keys [r][n][2][T], out: [r][n][2])
                                   // L_IP_LINTRANS: the same, with c: plaintexts [r][n], d: addend source [n] / out1: addend output [n] (HM_NO_LIMB: none; both
                                   // empty: no entry has one), out: [n][2]
@@ -53,6 +54,7 @@ struct Arch::Launch {
   uint32_t multiOuts = 0;
   std::vector<uint32_t> idPt, d1;
   uint32_t dotTerms = 0;          // L_TENSOR_DOT: pairs per record (a, b, c, d: [n][dotTerms], roles as L_TENSOR; out, out1, out2: [n])
+                                  // L_TENSOR_SQUARE: a = c0, c = c1, out, out1, out2 = d0, d1, d2 [n]; k: the scalars [n], addK: the constants [n] (empty: none)
   std::string name;
   std::string statKey;
   int opcode = 0;
@@ -147,6 +149,9 @@ Arch::Arch(Config *cfg) : config(cfg) {
   // (5d) hdot: the tensor product of pair 1 and the multiply-accumulate chains of the further pairs become one hm_tensor_dot launch.  Config key
   // fuse_dot (default 1).
   fuseDot = cfg->getValueOr("fuse_dot", 1) != 0;
+  // (5q) hsquare: the tensor product of the ciphertext with itself, the scalar on its three outputs and the constant on d0 become one
+  // hm_tensor_square launch.  Config key fuse_square (default 1).
+  fuseSquare = cfg->getValueOr("fuse_square", 1) != 0;
   // (4p) pmult with rescale = 1: the products are formed by the rescale's transforms while they load.  Config key fuse_pmul_rescale: 1 / 0 = always /
   // never; not given = where it was measured faster than the three-launch plan: everywhere but the generic back-end's launches
   // inside the one-launch form's limit, which has no product form there (Planner::productOperands)
@@ -309,6 +314,7 @@ int partKey(const Instruction &i) {
   if (i.ops == IP && transformsInside(i)) return 400 + (int)i.ipX.size() * 10 + (int)i.ipY.size();         // 400+: transform x key, by digits and keys
   if (isKeyProduct(i)) return 300 + (int)i.ipX.size() * 10 + (int)i.ipY.size();                            // 300+: key product, by digits and keys
   if (!i.dotOperands.empty()) return 8000 + (int)i.dotOperands.size() / 4;                                 // 8000+: sum of tensor products, by pairs
+  if (!i.sqOperands.empty()) return 8500 + (i.sqHasScale ? 1 : 0) + (i.sqHasConst ? 2 : 0);                // 8500+: scaled square plus constant, by what it absorbed
   if (i.fusedTensor) return 200;                                                                           // 200: tensor product
   if (i.fusedSubScale && i.fMinuendB) return i.fMix ? 211 : 209;                                           // 209 / 211: ... with a product minuend (4p)
   if (i.fusedSubScale) return (i.fMix ? 203 : 201) + (i.fConvIn.empty() ? 0 : 4);                          // 201 / 203: fused forward transform, plain / merged; 205 / 207: with its conversion
@@ -347,6 +353,44 @@ void assignDepths(std::vector<Part> &parts, bool fuse) {
     for (Instruction *i : p.ins) {
       for (AddrType a : loads(*i)) { int &r = readerDepth[a]; r = std::max(r, d); }
       for (const Write &o : recordWrites(*i)) writerDepth[o.addr] = d;
+    }
+  }
+}
+
+// One GPU runs its launches on ONE in-order stream, and the launches of a level go out in the order of the first part of every key.  A part one
+// level below a group of its own key may therefore join that group when every part of the group's level it conflicts with (RAW, WAR, WAW) is
+// launched in FRONT of the group: the stream orders them.  (hsquare with fuse_square = 0: the constant lands on d0 one launch behind the scalar
+// that ModUp's inverse transforms wait for; the inverse transform of d0's last limb joins them instead of running as a launch of one limb-poly.)
+void addUnique(std::vector<int> &v, int x);
+void joinEarlierGroups(std::vector<Part> &parts) {
+  struct Touched { std::set<AddrType> reads, writes; };
+  std::vector<Touched> t(parts.size());
+  int maxDepth = 0;
+  for (size_t p = 0; p < parts.size(); ++p) {
+    maxDepth = std::max(maxDepth, parts[p].depth);
+    for (Instruction *i : parts[p].ins) {
+      for (AddrType a : loads(*i)) t[p].reads.insert(a);
+      for (const Write &o : recordWrites(*i)) t[p].writes.insert(o.addr);
+    }
+  }
+  auto conflict = [&](size_t x, size_t y) {
+    for (AddrType a : t[x].writes)
+      if (t[y].reads.count(a) || t[y].writes.count(a)) return true;
+    for (AddrType a : t[x].reads)
+      if (t[y].writes.count(a)) return true;
+    return false;
+  };
+  for (int d = 0; d < maxDepth; ++d) {
+    std::vector<int> keys;   // the launch order of level d
+    for (const Part &p : parts)
+      if (p.depth == d) addUnique(keys, p.key);
+    auto pos = [&](int key) { return (int)(std::find(keys.begin(), keys.end(), key) - keys.begin()); };
+    for (size_t p = 0; p < parts.size(); ++p) {
+      if (parts[p].depth != d + 1 || pos(parts[p].key) == (int)keys.size()) continue;
+      bool ordered = true;
+      for (size_t r = 0; r < parts.size() && ordered; ++r)
+        if (r != p && parts[r].depth == d && pos(parts[r].key) >= pos(parts[p].key) && conflict(r, p)) ordered = false;
+      if (ordered) parts[p].depth = d;
     }
   }
 }
@@ -439,6 +483,7 @@ struct Arch::LaunchBuilder {
   void ip(Launch &L, Recs recs);
   void tensor(Launch &L, Recs recs);
   void tensorDot(Launch &L, Recs recs);
+  void tensorSquare(Launch &L, Recs recs);
   void nttSubScale(Launch &L, Recs recs);
   void copy(Launch &L, Recs recs);
   void transform(Launch &L, Recs recs);
@@ -585,6 +630,20 @@ void Arch::LaunchBuilder::tensorDot(Launch &L, Recs recs) {
     L.mods.push_back(i->mod_id);
   }
   L.bytes = (4ull * L.dotTerms + 3) * LP * recs.size();   // every operand read once, the three sums written once
+}
+
+// (5q) a, c = c0, c1 of the ciphertext [n]; out, out1, out2 = d0, d1, d2 [n]; k / addK = the scalars / the constants [n] (hm_tensor_square).  The
+// part key keeps records that absorbed different things apart
+void Arch::LaunchBuilder::tensorSquare(Launch &L, Recs recs) {
+  L.kind = Launch::L_TENSOR_SQUARE; L.statKey = "EWE";
+  for (Instruction *i : recs) {
+    L.a.push_back(limb(i->sqOperands[0])); L.c.push_back(limb(i->sqOperands[1]));
+    L.out.push_back(limb(i->extraOutputs[0])); L.out1.push_back(limb(i->OutputOperand)); L.out2.push_back(limb(i->extraOutputs[1]));
+    L.mods.push_back(i->mod_id);
+    if (recs[0]->sqHasScale) L.k.push_back(i->sqScale);
+    if (recs[0]->sqHasConst) L.addK.push_back(i->sqConst);
+  }
+  L.bytes = 5 * LP * recs.size();   // two polynomials read, three written
 }
 
 // fused forward transform (4, 4b, 9, 12)
@@ -754,6 +813,7 @@ void Arch::LaunchBuilder::emitCompute(const Group &group, Launches &front, Launc
   else if (f->ops == IP && transformsInside(*f)) nttIp(*L, recs);
   else if (isKeyProduct(*f)) ip(*L, recs);
   else if (!f->dotOperands.empty()) tensorDot(*L, recs);
+  else if (!f->sqOperands.empty()) tensorSquare(*L, recs);
   else if (f->fusedTensor) tensor(*L, recs);
   else if (f->fusedSubScale) nttSubScale(*L, recs);
   else if (f->ops == NTT && f->passthrough) copy(*L, recs);
@@ -949,6 +1009,10 @@ void Arch::buildLaunches() {
   }
   // 2. dependency depth
   assignDepths(parts, fuse);
+  // (only the plan that holds a square's tensor record which pass (5q) did not take: fuse_square = 0.  Every other plan keeps the plain
+  // level-by-level order it is pinned to, launch by launch: tests/golden/plan_fingerprints.json)
+  const bool plainSquare = std::any_of(parts.begin(), parts.end(), [](const Part &p) { return p.ins[0]->squareHead && p.ins[0]->fusedTensor && p.ins[0]->sqOperands.empty(); });
+  if (fuse && world_ == 1 && plainSquare) joinEarlierGroups(parts);
   LaunchBuilder b(*this);
   // multi-GPU: who holds each limb-poly.  Inputs: by the modulus they were filled for; everything else: by the modulus of the
   // instruction that writes it.
@@ -1162,7 +1226,7 @@ void Arch::prepare() {
 
 static const char *const kLaunchKindNames[] = {"NTT", "INTT", "EWE", "BCONV", "AUTO", "NTT_SUBSCALE", "TENSOR", "EXCH_IN", "EXCH_OUT", "REPLICATE", "IP", "NTT_IP",
                                                "BCONV_COL", "EXCH_IN_COL", "EXCH_OUT_COL", "IP_HOISTED", "IP_LINTRANS", "TENSOR_DOT", "IP_ROTSUM",
-                                               "IP_LINTRANS_MULTI"};
+                                               "IP_LINTRANS_MULTI", "TENSOR_SQUARE"};
 
 // Per-launch device time (SURVEY.md §8d "per-stage hipEvent times", exchange time at N > 1): every launch of the plan
 // bracketed by its own event pair, in plan order so that the data dependencies (and, sharded, the collectives) line up.
@@ -1214,6 +1278,8 @@ std::string Arch::planText() const {
       for (size_t r = 0; r < l->hoistG.size(); ++r) out += (r ? "," : "") + std::to_string(l->hoistG[r]);
     }
     if (l->kind == Launch::L_TENSOR_DOT) out += " terms=" + std::to_string(l->dotTerms);   // (5d): pairs summed per record
+    if (l->kind == Launch::L_TENSOR_SQUARE)   // (5q): what the records absorbed
+      out += std::string(" scale=") + (l->k.empty() ? "0" : "1") + " const=" + (l->addK.empty() ? "0" : "1");
     if (l->kind == Launch::L_IP_LINTRANS)   // (6l): entries that also form the addend output
       out += " addend=" + std::to_string(l->d.size() - (size_t)std::count(l->d.begin(), l->d.end(), HM_NO_LIMB));
     if (l->kind == Launch::L_IP_LINTRANS_MULTI)   // (6m): groups, entries that also form the groups' addend outputs
@@ -1389,6 +1455,10 @@ void Arch::enqueue(Launch &l) {
   case Launch::L_TENSOR_DOT:
     st = hm_tensor_dot(ctx, pool, l.a.data(), pool, l.b.data(), pool, l.c.data(), pool, l.d.data(), pool, l.out.data(), pool, l.out1.data(), pool,
                        l.out2.data(), l.mods.data(), cnt, l.dotTerms);
+    break;
+  case Launch::L_TENSOR_SQUARE:
+    st = hm_tensor_square(ctx, pool, l.a.data(), pool, l.c.data(), pool, l.out.data(), pool, l.out1.data(), pool, l.out2.data(), l.mods.data(), cnt,
+                          l.k.empty() ? nullptr : l.k.data(), l.addK.empty() ? nullptr : l.addK.data());
     break;
   case Launch::L_EXCH_IN:
     st = hm_limbs_to_slices(ctx, pool, l.exLimbs.data(), l.exOwners.data(), (uint32_t)l.exLimbs.size(), l.slicesIn);

@@ -5,6 +5,7 @@
 #include "SimProgram.h"
 
 #include <algorithm>
+#include <cctype>
 #include <chrono>
 #include <numeric>
 #include <sstream>
@@ -458,6 +459,41 @@ void OperationBase::setRescaledOutput(const std::string &out, const std::array<s
     setOutput(out, k, res.output());
   }
 }
+// reference: HMULT::HMULT :947-1023, behind the tensor product
+void OperationBase::relinearizeAndRescale(const std::array<std::vector<AddrType>, 3> &d) {
+  KeySwitch ksw(label, maxLevel_, level_, alpha_, d[2], &Datapool, &DataInsMap, &insgener, addrManager.get());
+  dispatch(ksw.getInsMap());
+  std::array<std::vector<AddrType>, 2> sum;
+  for (uint32_t k = 0; k < 2; k++) {
+    PerLimb s{label + "_HMULTHadd_Level(", ")_k(" + S(k) + ")", range(0, level_), alloc("HMULTHaddOutput(" + S(k) + ")", level_)};
+    s.a = ksw.output()[k];
+    s.c = d[k];
+    driver.dispatchInstructions("HMULT_Hadd_Key(" + S(k) + ")", eweLimbs(&insgener, EWE_ADD, s));
+    sum[k] = s.out;
+  }
+  for (uint32_t k = 0; k < 2; k++) {
+    Rescale res(label + "_" + S(k), level_, sum[k], &Datapool, &DataInsMap, &insgener, addrManager.get());
+    dispatch(res.getInsMap());
+    setOutput("out", k, res.output());
+  }
+}
+void OperationBase::setConstants(const std::string &name, const uint64_t *values, uint32_t n) {
+  std::string op = opName;
+  std::transform(op.begin(), op.end(), op.begin(), [](unsigned char ch) { return (char)std::tolower(ch); });
+  const std::string what = op + ": set_constants(\"" + name + "\")";
+  auto cs = constantStages.find(name);
+  if (cs == constantStages.end()) throw std::runtime_error(what + ": the op has no constants of that name");
+  if (!cs->second.enabled) throw std::runtime_error(what + ": " + cs->second.key + " = 0, the op carries no such constants");
+  if (arch->isPrepared()) throw std::runtime_error(what + " after prepare(): the plan is built");
+  if (!values) throw std::runtime_error(what + ": null values");
+  if (n != level_) throw std::runtime_error(what + ": n = " + S(n) + " values, the level is " + S(level_));
+  for (uint32_t j = 0; j < n; ++j) {
+    if (values[j] >= arch->modulus(j)) throw std::runtime_error(what + ": values[" + S(j) + "] is not reduced mod q_" + S(j));
+    if (cs->second.nonZero && values[j] == 0) throw std::runtime_error(what + ": values[" + S(j) + "] is zero");
+  }
+  for (uint32_t j = 0; j < n; ++j)
+    for (Instruction *i : cs->second.records[j]) i->constant = values[j];
+}
 void OperationBase::finishRotation(const std::string &out, const std::vector<AddrType> &rotatedC0, const KeySwitch::Output &ks, const std::string &suffix) {
   PerLimb s{label + "_HROTATEadd" + suffix + "_Level(", ")", range(0, level_), alloc("HROTATEOutput" + suffix + "(1)", level_)};
   s.a = ks[0];
@@ -672,22 +708,7 @@ HMULT::HMULT(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, ui
   TensorCompute tcm(labelName, currentLevel, &cts[0], &cts[1], &Datapool, &DataInsMap, &insgener, addrManager.get());
   dispatch(tcm.getInsMap());
 
-  KeySwitch ksw(labelName, maxLevel, currentLevel, alpha, tcm.d(2), &Datapool, &DataInsMap, &insgener, addrManager.get());
-  dispatch(ksw.getInsMap());
-
-  std::array<std::vector<AddrType>, 2> sum;
-  for (uint32_t k = 0; k < 2; k++) {
-    PerLimb s{labelName + "_HMULTHadd_Level(", ")_k(" + S(k) + ")", range(0, currentLevel), alloc("HMULTHaddOutput(" + S(k) + ")", currentLevel)};
-    s.a = ksw.output()[k];
-    s.c = tcm.d(k);
-    driver.dispatchInstructions("HMULT_Hadd_Key(" + S(k) + ")", eweLimbs(&insgener, EWE_ADD, s));
-    sum[k] = s.out;
-  }
-  for (uint32_t k = 0; k < 2; k++) {
-    Rescale res(labelName + "_" + S(k), currentLevel, sum[k], &Datapool, &DataInsMap, &insgener, addrManager.get());
-    dispatch(res.getInsMap());
-    setOutput("out", k, res.output());
-  }
+  relinearizeAndRescale({tcm.d(0), tcm.d(1), tcm.d(2)});
   finishConstruction();
 }
 
@@ -817,22 +838,63 @@ HDOT::HDOT(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint
     d[2] = emit("Dot_D2", EWE_MAC_ADD, s2);
   }
 
-  // HMULT's tail (HMULT::HMULT above), on the sums
-  KeySwitch ksw(labelName, maxLevel, currentLevel, alpha, d[2].addr, &Datapool, &DataInsMap, &insgener, addrManager.get());
-  dispatch(ksw.getInsMap());
-  std::array<std::vector<AddrType>, 2> sum;
-  for (uint32_t k = 0; k < 2; k++) {
-    PerLimb s{labelName + "_HMULTHadd_Level(", ")_k(" + S(k) + ")", range(0, currentLevel), alloc("HMULTHaddOutput(" + S(k) + ")", currentLevel)};
-    s.a = ksw.output()[k];
-    s.c = d[k].addr;
-    driver.dispatchInstructions("HMULT_Hadd_Key(" + S(k) + ")", eweLimbs(&insgener, EWE_ADD, s));
-    sum[k] = s.out;
-  }
-  for (uint32_t k = 0; k < 2; k++) {
-    Rescale res(labelName + "_" + S(k), currentLevel, sum[k], &Datapool, &DataInsMap, &insgener, addrManager.get());
-    dispatch(res.getInsMap());
-    setOutput("out", k, res.output());
-  }
+  relinearizeAndRescale({d[0].addr, d[1].addr, d[2].addr});   // HMULT's tail, on the sums
+  finishConstruction();
+}
+
+// hsquare (build extension).  out = Rescale(d0 + ks0(d2)), Rescale(d1 + ks1(d2)) with d0 = s a a + k, d1 = 2 s a c, d2 = s c c
+// (a = ct1.c0, c = ct1.c1).  TensorCompute on (ct1, ct1): its MAC2 a c + c a is 2 a c and its MULs are the squares; sq_scale = 1 adds three MUL_CONST
+// stages (s on d0, d1, d2: linear, so it acts in front of the key switch), sq_const = 1 one ADD_CONST stage on d0 (the constant polynomial k in
+// evaluation form, where an FHE library adds it, at scale Delta^2).  Then HMULT's tail, stage for stage.  Unfused, the stages run one launch each;
+// fused, pass (5q) of Arch::fusePasses (Planner.cpp) turns everything in front of the key switch into one launch that reads ct1 once.
+static uint64_t synthWord0(uint64_t stream, uint64_t q) {   // word 0 of a limb of the synthetic stream (hm_synth / ho_fill_uniform at x = 0)
+  uint64_t z = stream * 0xD1342543DE82EF95ull + 0x632BE59BD9B4E019ull;
+  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
+  z ^= z >> 27; z *= 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  return (uint64_t)(((unsigned __int128)z * q) >> 64);
+}
+HSQUARE::HSQUARE(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch)
+    : OperationBase("HSQUARE", labelName, cfg, _arch, maxLevel, currentLevel, alpha) {
+  if (arch->backend() == Arch::BACKEND_SIM) throw std::runtime_error("hsquare: backend = sim has no such op (the reference has no square)");
+  if (arch->world() > 1) throw std::runtime_error("hsquare: world > 1 is not supported (the sharded plan is not built)");
+  auto flag = [&](const char *key) {
+    const uint32_t v = cfg->getValueOr(key, 0);
+    if (v > 1) throw std::runtime_error(std::string("hsquare: ") + key + " = " + S(v) + ", must be 0 or 1");
+    return v == 1;
+  };
+  const bool scaled = flag("sq_scale"), shifted = flag("sq_const");
+  makeInputs(1);
+
+  TensorCompute tcm(labelName, currentLevel, &cts[0], &cts[0], &Datapool, &DataInsMap, &insgener, addrManager.get(), "Sq");
+  for (const INSGROUP &g : tcm.getInsMap().at("TensorCompute_INS_D1")) g[0]->squareHead = true;
+  dispatch(tcm.getInsMap());
+  std::array<Limbs, 3> d;
+  for (uint32_t i = 0; i < 3; ++i) d[i] = {tcm.d(i), tcm.getInsMap().at("TensorCompute_INS_D" + S(i))};
+  // a constant stage on polynomial i: one record per limb, kept by name for setConstants
+  auto constantStage = [&](const std::string &name, uint32_t i, ewe_opcode op, const std::string &tag, uint64_t stream, bool nonZero) {
+    ConstantStage &cs = constantStages[name];
+    cs.enabled = true;
+    cs.nonZero = nonZero;
+    cs.records.resize(currentLevel);
+    PerLimb s{labelName + "_Square_" + tag + "_D" + S(i) + "_Level(", ")", range(0, currentLevel), alloc("SqD" + S(i) + tag, currentLevel)};
+    s.a = d[i].addr;
+    const std::vector<INSGROUP> before = d[i].from;
+    s.after = {&before};
+    for (uint32_t j = 0; j < currentLevel; ++j) {
+      const uint64_t v = synthWord0(stream + j, arch->modulus(j));
+      s.constants.push_back(nonZero && v == 0 ? 1 : v);
+    }
+    d[i] = {s.out, eweLimbs(&insgener, op, s)};
+    driver.dispatchInstructions("Square_" + tag + "_D" + S(i), d[i].from);
+    for (uint32_t j = 0; j < currentLevel; ++j) cs.records[j].push_back(d[i].from[j][0]);
+  };
+  constantStages["scale"].key = "sq_scale";
+  constantStages["const"].key = "sq_const";
+  if (scaled)
+    for (uint32_t i = 0; i < 3; ++i) constantStage("scale", i, EWE_MUL_CONST, "Scale", seed + 6000, /*nonZero=*/true);
+  if (shifted) constantStage("const", 0, EWE_ADD_CONST, "Const", seed + 6100, /*nonZero=*/false);
+  relinearizeAndRescale({d[0].addr, d[1].addr, d[2].addr});
   finishConstruction();
 }
 
@@ -1066,6 +1128,7 @@ static OperationBase *makeOp(const std::string &o, uint32_t maxLevel, uint32_t l
   if (o == "hbsgs") return new HBSGS("test_hbsgs", maxLevel, level, alpha, cfg, arch);
   if (o == "hrescale") return new HRESCALE("test_hrescale", maxLevel, level, alpha, cfg, arch);
   if (o == "hmodraise") return new HMODRAISE("test_hmodraise", maxLevel, level, alpha, cfg, arch);
+  if (o == "hsquare") return new HSQUARE("test_hsquare", maxLevel, level, alpha, cfg, arch);
   throw std::runtime_error("Error operation requirement, please double confirm!");
 }
 

@@ -105,6 +105,7 @@ struct Arch::Planner {
   void residue();          // 4c
   void tensor();           // 5
   void tensorDot();        // 5d
+  void tensorSquare();     // 5q
   void keyProduct();       // 6
   // what (6m/6l), (6s) and (6h) all recognise: the live two-key key-product records whose digits are all automorphisms, by one element per record, of
   // the same materialised digits and are read by nothing else; per (modulus, unrotated digits) the records and their automorphisms, in stage order
@@ -145,6 +146,7 @@ void Arch::fusePasses(std::vector<Stage> &st) {
   p.residue();
   p.tensor();
   if (fuseDot) p.tensorDot();   // before (6): the multiply-accumulate chains it absorbs are not key products
+  if (fuseSquare) p.tensorSquare();
   p.keyProduct();
   // (6m, 6l) before (6s) and (6h): the records it merges are the ones (6h) would claim, and none of them is (6s)'s (their outputs go into products,
   // not into sums).  fuse_bsgs: the groups with several sums, fuse_lintrans: the ones with one
@@ -444,6 +446,52 @@ void Arch::Planner::tensorDot() {
     c->extraOutputs = {d0, d2};
     for (const Write &w : recordWrites(*c)) producer[w.addr] = c;
     place.moveTo(c, last);   // to where its last link stood
+  }
+}
+
+// (5q) scaled square plus constant (hsquare): a tensor record of (5) that the builder marked (squareHead) and whose operand pairs coincide
+//      (c00 == c10, c01 == c11: a ciphertext times itself) becomes a record of hm_tensor_square, which reads each polynomial once.  Behind it,
+//      the MUL_CONST records that are the only readers of its three outputs go in when all three carry the same constant (s d0, s d1, s d2), then the
+//      ADD_CONST record that is the only reader of d0 (d0 + k).  The record's outputs become the final buffers, so every later pass sees what it
+//      sees in hmult; it takes the place of the last record it absorbs.  Never written: the products in front of the scalar and of the constant.
+//      Reads: fusedTensor / extraOutputs (5).  Sets on the tensor record: sqOperands, sqHasScale, sqScale, sqHasConst, sqConst, OutputOperand,
+//      extraOutputs.
+void Arch::Planner::tensorSquare() {
+  Readers rd = readers();
+  Placement place(st);
+  std::vector<Instruction *> heads;
+  for (auto &s : st)
+    for (Instruction *i : s.ins)
+      if (live(i) && i->fusedTensor && i->squareHead && i->dotOperands.empty() && i->sqOperands.empty()) heads.push_back(i);
+  for (Instruction *c : heads) {
+    // MAC2 operands (P, S, R, T) = (c00, c11, c01, c10)
+    if (c->operandList[0] != c->operandList[3] || c->operandList[2] != c->operandList[1]) continue;
+    c->sqOperands = {c->operandList[0], c->operandList[2]};
+    AddrType d0 = c->extraOutputs[0], d1 = c->OutputOperand, d2 = c->extraOutputs[1];
+    Instruction *last = c;
+    auto take = [&](Instruction *i) {
+      absorb(c, i);
+      if (place.after(i, last)) last = i;
+    };
+    Instruction *m0 = soleReader(rd, d0, EWE_MUL_CONST, c->mod_id), *m1 = soleReader(rd, d1, EWE_MUL_CONST, c->mod_id), *m2 = soleReader(rd, d2, EWE_MUL_CONST, c->mod_id);
+    if (m0 && m1 && m2 && m0->hasConstant && m1->hasConstant && m2->hasConstant && m0->constant == m1->constant && m0->constant == m2->constant) {
+      c->sqHasScale = true;
+      c->sqScale = m0->constant;
+      for (Instruction *i : {m0, m1, m2}) take(i);
+      d0 = m0->OutputOperand; d1 = m1->OutputOperand; d2 = m2->OutputOperand;
+    }
+    if (Instruction *add = soleReader(rd, d0, EWE_ADD_CONST, c->mod_id)) {
+      if (add->hasConstant) {
+        c->sqHasConst = true;
+        c->sqConst = add->constant;
+        take(add);
+        d0 = add->OutputOperand;
+      }
+    }
+    c->OutputOperand = d1;
+    c->extraOutputs = {d0, d2};
+    for (const Write &w : recordWrites(*c)) producer[w.addr] = c;
+    place.moveTo(c, last);
   }
 }
 

@@ -58,6 +58,7 @@ int hh_op_create(hh_op **out, const char *cfg_path, const char *op_name, uint32_
     else if (o == "hbsgs") h->op = new HBSGS("test_hbsgs", maxLevel, curLevel, alpha, h->cfg, h->arch);
     else if (o == "hrescale") h->op = new HRESCALE("test_hrescale", maxLevel, curLevel, alpha, h->cfg, h->arch);
     else if (o == "hmodraise") h->op = new HMODRAISE("test_hmodraise", maxLevel, curLevel, alpha, h->cfg, h->arch);
+    else if (o == "hsquare") h->op = new HSQUARE("test_hsquare", maxLevel, curLevel, alpha, h->cfg, h->arch);
     else if (o == "hadd") h->op = new HADD("test_hadd", maxLevel, curLevel, alpha, h->cfg, h->arch);
     else if (o == "pmult") h->op = new PMULT("test_pmult", maxLevel, curLevel, alpha, h->cfg, h->arch);
     else if (o == "padd") h->op = new PADD("test_ADD", maxLevel, curLevel, alpha, h->cfg, h->arch);
@@ -106,6 +107,9 @@ int hh_op_read_buffer_copy(hh_op *h, const char *name, uint32_t copy, uint64_t *
 }
 int hh_op_write_buffer(hh_op *h, const char *name, uint32_t copy, const uint64_t *host) {
   HH_TRY(if (!h->op->writeBuffer(name, host, copy)) throw std::runtime_error("buffer not writable (not the hip backend, or copy >= batch)"))
+}
+int hh_op_set_constants(hh_op *h, const char *name, const uint64_t *values, uint32_t n) {
+  HH_TRY(if (!name) throw std::runtime_error("null argument"); h->op->setConstants(name, values, n))
 }
 uint32_t hh_op_batch(hh_op *h) { return h->arch->batch(); }
 uint32_t hh_op_N(hh_op *h) { return h->arch->N(); }

@@ -144,7 +144,8 @@ enum hm_ewe_op {
   HM_OP_MUL_CONST = 5,     /* out = a*k[i]         ModUp_DecompOut :104-135, ModDownBConvStep1 :447-487, Rescale_Mul :877-910 */
   HM_OP_SUB_SCALE = 6,     /* out = (a - c)*k[i]   KeySwitchFinalOutput :548-590 */
   HM_OP_COPY = 7,          /* out = a */
-  HM_OP_SUB_SCALE_ADD = 8  /* out = (a - c)*k[i] + d   fused ModDownSub + final add */
+  HM_OP_SUB_SCALE_ADD = 8, /* out = (a - c)*k[i] + d   fused ModDownSub + final add */
+  HM_OP_ADD_CONST = 9      /* out = a + k[i]       a constant added to every evaluation-form entry: the constant polynomial k (HSQUARE) */
 };
 hm_status hm_ewe(hm_ctx *ctx, int op, const uint64_t *a, const uint32_t *a_limbs, const uint64_t *b,
                  const uint32_t *b_limbs, const uint64_t *c, const uint32_t *c_limbs, const uint64_t *d,
@@ -173,6 +174,19 @@ hm_status hm_tensor_dot(hm_ctx *ctx, const uint64_t *a, const uint32_t *a_limbs,
                         const uint64_t *c, const uint32_t *c_limbs, const uint64_t *d, const uint32_t *d_limbs,
                         uint64_t *o0, const uint32_t *o0_limbs, uint64_t *o1, const uint32_t *o1_limbs, uint64_t *o2,
                         const uint32_t *o2_limbs, const uint32_t *mod_ids, uint32_t n, uint32_t n_terms);
+
+/* K3, scaled square of ONE ciphertext plus a constant in one pass over its two polynomials (HSQUARE): for entry i, with
+ * a = c0, c = c1, s = scale[i] in [1, q) and k = addend[i] in [0, q), per coefficient
+ *   o0[i] = s * a * a + k,   o1[i] = 2 * s * a * c,   o2[i] = s * c * c,
+ * every residue canonical: bit-identical to hm_tensor(a, a, c, c) followed by HM_OP_MUL_CONST on the three outputs and HM_OP_ADD_CONST on o0,
+ * none of whose intermediates is written (two limb-polys read and three written per entry where hm_tensor reads four).  scale == NULL: every
+ * s is 1; addend == NULL: every k is 0.  Both are host arrays of n residues.  The records live in a device table: one launch serves any n, and
+ * the call is safe under graph capture once it has run with the same lists and constants.  HM_ERR_ARG: a null buffer, a limb or modulus id out
+ * of range, an unreduced scale or addend, a zero scale, an output limb-poly that overlaps (by address range, not by base pointer) an input
+ * limb-poly or another output limb-poly.  n = 0 is HM_OK. */
+hm_status hm_tensor_square(hm_ctx *ctx, const uint64_t *a, const uint32_t *a_limbs, const uint64_t *c, const uint32_t *c_limbs,
+                           uint64_t *o0, const uint32_t *o0_limbs, uint64_t *o1, const uint32_t *o1_limbs, uint64_t *o2,
+                           const uint32_t *o2_limbs, const uint32_t *mod_ids, uint32_t n, const uint64_t *scale, const uint64_t *addend);
 
 /* K5 — inner product with the evaluation key in one pass: for limb i, out[i][k] = sum_{j < n_terms}
  * x[i][j] * y[i][k][j], k < n_out (n_terms <= 4 digits, n_out <= 2 keys).  Limb lists are row-major:
