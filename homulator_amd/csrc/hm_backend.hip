@@ -503,6 +503,12 @@ __global__ void __launch_bounds__(256) k_tensor_square(HmTensorSqArgs a) {
   if (entry < a.n_limbs) hm_tensor_square_thread(a, entry, blockIdx.x & ((1u << logPer) - 1u), threadIdx.x);
 }
 
+// sum of T scaled limb-polys plus a constant (hm_elem_core.h: hm_lincomb_thread): k_tensor_dot's geometry, the records in a device table
+__global__ void __launch_bounds__(256) k_lincomb(HmLincombArgs a) {
+  const uint32_t logPer = a.logN - 9, entry = blockIdx.x >> logPer;
+  if (entry < a.n_limbs) hm_lincomb_thread(a, entry, blockIdx.x & ((1u << logPer) - 1u), threadIdx.x);
+}
+
 // 16-byte units per thread of the element-wise kernel, 512 coefficients apart, all loads in flight before the first use.  1: 89 600 workgroups for a batch of
 // ten hadd; 2 / 4 measured padd +3 / +5 %, pmult +1 %, hadd within the noise (tools/r06_ewe_ab.sh): not worth a second shape of the kernel's launch
 #ifndef HM_EWE_UNITS
@@ -1827,6 +1833,51 @@ extern "C" hm_status hm_tensor_square(hm_ctx *c, const uint64_t *pa, const uint3
   a.a = pa; a.c = pc; a.o0 = o0; a.o1 = o1; a.o2 = o2;
   a.mods = c->d_mods; a.logN = c->P.logN; a.n_limbs = n;
   hipLaunchKernelGGL(k_tensor_square, dim3(n * (N / 512)), dim3(256), 0, c->stream, a);
+  HM_HIP(c, hipGetLastError());
+  return HM_OK;
+}
+
+// sum of n_terms scaled limb-polys plus a constant: input list and scalars [n][n_terms], output list and constants [n]; one record per entry in a
+// device table, ONE launch for any n
+extern "C" hm_status hm_lincomb(hm_ctx *c, const uint64_t *in, const uint32_t *li, uint64_t *out, const uint32_t *lo, const uint32_t *mod_ids,
+                                uint32_t n, uint32_t n_terms, const uint64_t *scale, const uint64_t *addend) {
+  static const char *const what = "hm_lincomb";
+  if (!c) return HM_ERR_ARG;
+  HM_TABLE_CALL(c);
+  if (!in || !out) return fail(c, HM_ERR_ARG, "%s: null buffer", what);
+  if (!scale) return fail(c, HM_ERR_ARG, "%s: scale is null", what);
+  const uint32_t T = n_terms, N = c->P.N;
+  if (T == 0 || T > HM_LINCOMB_MAX_TERMS) return fail(c, HM_ERR_ARG, "%s: n_terms = %u, must be in [1, %d]", what, T, HM_LINCOMB_MAX_TERMS);
+  if ((uint64_t)n * T > 0xFFFFFFFFull / HM_LINCOMB_REC_WORDS(T)) return fail(c, HM_ERR_ARG, "%s: n = %u entries of %u terms are too many for one call", what, n, T);
+  hm_status st;
+  if ((st = check_limbs(c, what, li, n * T)) || (st = check_limbs(c, what, lo, n)) || (st = check_mods(c, what, mod_ids, n))) return st;
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint64_t q = c->P.mod[mod_ids[i]];
+    for (uint32_t t = 0; t < T; ++t)
+      if (scale[(size_t)i * T + t] >= q) return fail(c, HM_ERR_ARG, "%s: scale[%u][%u] is not reduced", what, i, t);
+    if (addend && addend[i] >= q) return fail(c, HM_ERR_ARG, "%s: addend[%u] is not reduced", what, i);
+  }
+  // a workgroup stores its output after ALL its loads, and the same input limb-poly may serve several records and terms: no output may share an
+  // address with any input or with another output (hm_tensor_dot's rule and messages)
+  if (hm_limbs_overlap(out, lo, n, in, li, n * T, N)) return fail(c, HM_ERR_ARG, "%s: an output limb-poly (%s) overlaps an input limb-poly (%s)", what, "out", "in");
+  {
+    std::vector<uintptr_t> starts;
+    for (uint32_t i = 0; i < n; ++i) starts.push_back(reinterpret_cast<uintptr_t>(out) + (uintptr_t)limb_at(lo, i) * N * 8);
+    std::sort(starts.begin(), starts.end());
+    for (size_t i = 1; i < starts.size(); ++i)
+      if (starts[i] - starts[i - 1] < (uintptr_t)N * 8) return fail(c, HM_ERR_ARG, "%s: two output limb-polys overlap", what);
+  }
+  if (n == 0) return HM_OK;
+  std::vector<uint32_t> recs((size_t)n * HM_LINCOMB_REC_WORDS(T));
+  hm_lincomb_fill_recs(recs.data(), li, lo, mod_ids, n, T, scale, addend);
+  HM_HIP(c, hipSetDevice(c->device));
+  HmLincombArgs a;
+  const void *tab = nullptr;
+  if ((st = device_table(c, recs.data(), recs.size() * sizeof(uint32_t), &tab))) return st;
+  a.rec = static_cast<const uint32_t *>(tab);
+  a.in = in; a.out = out;
+  a.mods = c->d_mods; a.logN = c->P.logN; a.n_limbs = n; a.n_terms = T;
+  hipLaunchKernelGGL(k_lincomb, dim3(n * (N / 512)), dim3(256), 0, c->stream, a);
   HM_HIP(c, hipGetLastError());
   return HM_OK;
 }

@@ -398,6 +398,97 @@ HM_HD void hm_tensor_square_thread(const HmTensorSqArgs &g, uint32_t entry, uint
   hm_bst2(g.o2 + r->o2 * N, lane_bytes, d2[0], d2[1]);
 }
 
+// Sum of T scaled polynomials plus a constant in one pass over the T inputs (hm_lincomb; HLINCOMB):
+//   out = sum_t s_t x_t + k      with s_t, k in [0, q) per record and every x_t canonical.
+// The raw 64 x 64 products are summed in ONE 128-bit accumulator per coefficient, k is added, and the accumulator is reduced once, as
+// hm_tensor_dot_acc does: T <= HM_LINCOMB_MAX_TERMS = 16 products below 2^120 are below 2^124, plus k < 2^60 below 2^125, and hm_barrett_wide
+// takes any 128-bit value.  The result is the canonical residue of the exact integer sum, hence bit-identical to the chain of MUL_CONST, ADD
+// and ADD_CONST.  One form on both arithmetic back-ends: T + 1 limb-polys per record and one wide multiply per loaded word.
+static_assert(HM_LINCOMB_MAX_TERMS == 16, "the accumulator: 16 products below 2^120 plus k below 2^60 stay below 2^125");
+// a record = HM_LINCOMB_REC_WORDS(T) 32-bit words, a multiple of 16 bytes: (modulus id, output limb, T, 0), (k: 2 words, 0, 0), then per term
+// (input limb, 0, s_t: 2 words).  The 64-bit values sit at 8-byte offsets.
+#define HM_LINCOMB_REC_WORDS(T) (8u + 4u * (T))
+struct HmLincombArgs {
+  const uint64_t *in;
+  uint64_t *out;
+  const HmMod *mods;
+  const uint32_t *rec;   // device, [n_limbs][HM_LINCOMB_REC_WORDS(n_terms)]: read through the scalar cache (wave-uniform index)
+  uint32_t logN, n_limbs, n_terms;
+};
+// The records of n entries from the entry point's lists (in: [n][T], out: [n]; a null list is the identity) and constants (scale: [n][T];
+// addend: [n] or null = 0; both already checked: reduced).  Host side.
+inline void hm_lincomb_fill_recs(uint32_t *rec, const uint32_t *li, const uint32_t *lo, const uint32_t *mod_ids, uint32_t n, uint32_t T,
+                                 const uint64_t *scale, const uint64_t *addend) {
+  auto at = [](const uint32_t *l, uint32_t i) { return l ? l[i] : i; };
+  for (uint32_t i = 0; i < n; ++i) {
+    uint32_t *r = rec + (size_t)i * HM_LINCOMB_REC_WORDS(T);
+    const uint64_t k = addend ? addend[i] : 0;
+    r[0] = mod_ids[i]; r[1] = at(lo, i); r[2] = T; r[3] = 0;
+    r[4] = (uint32_t)k; r[5] = (uint32_t)(k >> 32); r[6] = 0; r[7] = 0;
+    for (uint32_t t = 0; t < T; ++t) {
+      const uint32_t e = i * T + t;
+      r[8 + 4 * t] = at(li, e); r[9 + 4 * t] = 0; r[10 + 4 * t] = (uint32_t)scale[e]; r[11 + 4 * t] = (uint32_t)(scale[e] >> 32);
+    }
+  }
+}
+struct HmLincombTerm {   // the (input limb, scalar) of one term: four words of the record
+  uint32_t limb;
+  uint64_t s;
+};
+template <class REC>
+HM_HD HmLincombTerm hm_lincomb_term(REC rec, uint32_t t) {
+  return HmLincombTerm{rec[8 + 4 * t], (uint64_t)rec[10 + 4 * t] | ((uint64_t)rec[11 + 4 * t] << 32)};
+}
+struct HmLincombPair {   // the aligned pair of coefficients a thread owns of one term, with the term's scalar
+  uint64_t x[2], s;
+};
+// one 16-byte load from a wave-uniform base at the lane's offset
+HM_HD HmLincombPair hm_lincomb_ld(const HmLincombArgs &g, const HmLincombTerm &l, size_t N, uint32_t lane_bytes) {
+  HmLincombPair v;
+  hm_bld2(g.in + l.limb * N, lane_bytes, v.x[0], v.x[1]);
+  v.s = l.s;
+  return v;
+}
+HM_HD void hm_lincomb_acc2(hm_u128 (&s)[2], const HmLincombPair &v) {
+  s[0] += (hm_u128)v.x[0] * v.s;
+  s[1] += (hm_u128)v.x[1] * v.s;
+}
+// thread tid of the workgroup that owns chunk `chunk` (512 coefficients) of record `entry`: the pair at chunk * 512 + 2 tid, T 16-byte loads and
+// one 16-byte store.  T is a run-time loop in hm_tensor_dot_thread's shape: two terms per round in two named register sets, the load of term
+// t + 1 issued before the products of term t, the record words of a term requested a step before its load (index clamped to the last term:
+// always inside the record).  An even T leaves one term behind the rounds, T = 1 runs no round at all.
+HM_HD void hm_lincomb_thread(const HmLincombArgs &g, uint32_t entry, uint32_t chunk, uint32_t tid) {
+  const size_t N = (size_t)1 << g.logN;
+  const uint32_t T = g.n_terms, lane_bytes = (chunk * 512u + 2u * tid) << 3;
+  const auto rec = HM_CONST_PROB_T(uint32_t, g.rec) + (size_t)entry * HM_LINCOMB_REC_WORDS(T);
+  const HmMod m = HM_CONST_MODS(g.mods)[rec[0]];
+  const uint64_t k = (uint64_t)rec[4] | ((uint64_t)rec[5] << 32);
+  hm_u128 s[2] = {0, 0};
+  HmLincombPair p0 = hm_lincomb_ld(g, hm_lincomb_term(rec, 0), N, lane_bytes), p1;
+  HmLincombTerm l = hm_lincomb_term(rec, T > 1 ? 1u : 0u);
+  uint32_t t = 1;
+#pragma unroll 1
+  for (; t + 1 < T; t += 2) {
+    p1 = hm_lincomb_ld(g, l, N, lane_bytes);                     // term t
+    l = hm_lincomb_term(rec, t + 1);
+    HM_DOT_ISSUED();
+    hm_lincomb_acc2(s, p0);
+    p0 = hm_lincomb_ld(g, l, N, lane_bytes);                     // term t + 1
+    l = hm_lincomb_term(rec, t + 2 < T ? t + 2 : T - 1);
+    HM_DOT_ISSUED();
+    hm_lincomb_acc2(s, p1);
+  }
+  if (t < T) {   // (wave-uniform) an even number of terms: one more behind the rounds
+    p1 = hm_lincomb_ld(g, l, N, lane_bytes);
+    HM_DOT_ISSUED();
+    hm_lincomb_acc2(s, p0);
+    hm_lincomb_acc2(s, p1);
+  } else {
+    hm_lincomb_acc2(s, p0);
+  }
+  hm_bst2(g.out + rec[1] * N, lane_bytes, hm_barrett_wide(s[0] + k, m), hm_barrett_wide(s[1] + k, m));
+}
+
 // The conversion table is read through the SCALAR cache: every lane of a wave needs the same entries, so they are
 // s_load'ed into SGPRs (asynchronously, no VGPRs, no LDS, no barrier) and feed v_mad_u64_u32 as scalar operands.
 // hipcc only emits scalar loads for memory it knows to be constant, hence the constant-address-space view of the

@@ -25,7 +25,7 @@ SYMBOLS = [
     "hm_bconv_col", "hm_limbs_to_colslices", "hm_colslices_to_limbs", "hm_ntt_second_pass", "hm_ntt_ex", "hm_capability", "hm_inner_product_ex",
     "hm_inner_product_hoisted", "hm_inner_product_lintrans", "hm_inner_product_rotsum", "hm_inner_product_lintrans_multi",
     "hm_tensor_dot", "hm_inner_product_lintrans_id", "hm_inner_product_rotsum_init", "hm_ntt_mix_sub_scale_mul", "hm_ntt_mul",
-    "hm_ntt_lift", "hm_tensor_square",
+    "hm_ntt_lift", "hm_tensor_square", "hm_lincomb",
 ]
 
 
@@ -160,6 +160,7 @@ def load():
     L.hm_tensor.argtypes = [vp] + [vp] * 15 + [u32]
     L.hm_tensor_dot.argtypes = [vp] + [vp] * 15 + [u32, u32]
     L.hm_tensor_square.argtypes = [vp] + [vp] * 11 + [u32, vp, vp]
+    L.hm_lincomb.argtypes = [vp] + [vp] * 5 + [u32, u32, vp, vp]
     L.hm_inner_product.argtypes = [vp] + [vp] * 7 + [u32, u32, u32]
     L.hm_automorph.argtypes = [vp, vp, vp, vp, vp, u32, u32]
     L.hm_ewe.argtypes = [vp, i32] + [vp] * 11 + [u32, vp]
@@ -401,6 +402,14 @@ class Context:
         ks, ka = _u64(scale), _u64(addend)
         self._ck(self.L.hm_tensor_square(self.h, a.ptr, keep[0][1], c.ptr, keep[1][1], o0.ptr, keep[2][1], o1.ptr, keep[3][1], o2.ptr, keep[4][1],
                                          keep[5][1], len(mod_ids), ks[1], ka[1]))
+
+    def lincomb(self, src, in_limbs, out, out_limbs, mod_ids, n_terms, scale, addend=None):
+        """out[i] = sum_t scale[i][t] * src[in_limbs[i][t]] + addend[i] per entry (hm_lincomb): in_limbs and scale are row-major [n][n_terms]
+        (flat), out_limbs and mod_ids [n] (a limb list None: the identity), scale and addend residues of the entry's modulus (addend None: 0);
+        buffers: anything with a device address `.ptr`"""
+        keep = [_u32(in_limbs), _u32(out_limbs), _u32(mod_ids)]
+        ks, ka = _u64(scale), _u64(addend)
+        self._ck(self.L.hm_lincomb(self.h, src.ptr, keep[0][1], out.ptr, keep[1][1], keep[2][1], len(mod_ids), int(n_terms), ks[1], ka[1]))
 
     def inner_product(self, x, x_limbs, y, y_limbs, out, out_limbs, mod_ids, n_terms, n_out, x_galois=0):
         keep = [_u32(v) for v in (x_limbs, y_limbs, out_limbs, mod_ids)]

@@ -33,6 +33,7 @@ public:
   bool passthrough = false;  // an NTT-kind instruction whose input is already in evaluation form (copy)
   bool sumHead = false;      // a tensor product's MAC2 (d1) that is pair 1 of a SUM of tensor products (HDOT): pass (5d) starts its record here
   bool squareHead = false;   // a tensor product's MAC2 (d1) of a ciphertext with ITSELF (HSQUARE): pass (5q) starts its record here
+  bool lincombHead = false;  // the MUL_CONST of term 1 of a sum of scaled ciphertexts (HLINCOMB): pass (5l) starts its record here
   std::vector<uint32_t> inMods;  // BCONV: modulus ids of the inputs
   unsigned long long refInstructions = 0;  // upstream instructions this record stands for
   unsigned long long refExtra = 0;         // ... of records folded into a BCONV record (not scaled by its MAC-port count)
@@ -74,6 +75,13 @@ public:
   std::vector<AddrType> sqOperands;
   bool sqHasScale = false, sqHasConst = false;
   uint64_t sqScale = 1, sqConst = 0;
+  // (5l) sum of scaled polynomials plus constant (hm_lincomb): the MUL_CONST record of term 1 that absorbed the MUL_CONST + ADD pairs of the further
+  // terms and the ADD_CONST behind them.  lcOperands = the T inputs in term order, lcScales = their scalars; OutputOperand = the final sum.
+  // lcHasConst: the ADD_CONST record went in, with the constant lcConst.  lcOperands empty: not such a sum
+  std::vector<AddrType> lcOperands;
+  std::vector<uint64_t> lcScales;
+  bool lcHasConst = false;
+  uint64_t lcConst = 0;
   // fused inner product (ops == IP): out_k = sum_j ipX[j] * ipY[k][j]; out_0 = OutputOperand, out_1 = extraOutputs[0]
   std::vector<AddrType> ipX;
   std::vector<std::vector<AddrType>> ipY;

@@ -149,7 +149,7 @@ protected:
   // HMULT's tail on the three polynomials d of a tensor product (shared by HMULT, HDOT, HSQUARE): KS(d[2]); HMULT_Hadd_Key(k): d[k] + ks_k into
   // HMULTHaddOutput(k); Rescale of both, out = the result at level - 1
   void relinearizeAndRescale(const std::array<std::vector<AddrType>, 3> &d);
-  // Per-limb constants an op carries in its records (HSQUARE: "scale", "const"), by name: the records of limb j that hold value j, so that
+  // Per-limb constants an op carries in its records (HSQUARE: "scale", "const"; HLINCOMB: "scale<t>", "const"), by name: the records of limb j that hold value j, so that
   // setConstants can patch Instruction::constant before the plan is built.  enabled = false: the op knows the name but its config key is 0
   struct ConstantStage { bool enabled = false; std::string key; std::vector<std::vector<Instruction *>> records; bool nonZero = false; };
   std::map<std::string, ConstantStage> constantStages;
@@ -193,7 +193,7 @@ public:
   bool readBuffer(const std::string &name, uint64_t *host, uint32_t copy = 0);  // copy: op of the batch (config key `batch`)
   bool writeBuffer(const std::string &name, const uint64_t *host, uint32_t copy = 0);  // real data for an input / key buffer ([limbs][N], fully reduced)
   unsigned long long totalInstructions();
-  // replaces the per-limb constants `name` of the op (HSQUARE: "scale", "const") by n = level residues, values[j] reduced mod q_j; before prepare() only.
+  // replaces the per-limb constants `name` of the op (HSQUARE: "scale", "const"; HLINCOMB: "scale1" .. "scale<T>", "const") by n = level residues, values[j] reduced mod q_j; before prepare() only.
   // Refused, by op and name: after prepare(), n != level, an unreduced value (or a zero where the constant multiplies), a name whose config key is 0
   void setConstants(const std::string &name, const uint64_t *values, uint32_t n);
   Arch *getArch() { return arch; }
@@ -244,6 +244,15 @@ class HSQUARE : public OperationBase {
 public:
   HSQUARE(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
 };
+// hlincomb (build extension): out = sum_t s_t * ct<t> + k, a linear combination of T ciphertexts at one level (config key terms = T as hdot: default 4,
+// 1..16) with per-limb scalars s_{t,j} in [0, q_j) (synthetic: word 0 of limb j of stream seed + 6200 + 100 t; zero = the term contributes nothing)
+// and, with config key lc_const = 1, per-limb constants k_j on every evaluation-form entry of c0 only (stream seed + 6290): the baby steps and the
+// giant-step recombination of EvalMod's polynomial evaluation.  setConstants("scale<t>" | "const") replaces the synthetic values.  No key, no
+// ModUp.  One output ciphertext out at the inputs' level, or through Rescale at level - 1 with config key rescale = 1.
+class HLINCOMB : public OperationBase {
+public:
+  HLINCOMB(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
+};
 class HROTSUM : public OperationBase {
 public:
   HROTSUM(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
@@ -291,7 +300,7 @@ class OpChain {
   std::vector<Arch *> archs;
   std::vector<OperationBase *> ops;
 public:
-  // ops: comma-separated list of hmult | hrotate | hadd | pmult | padd | hlintrans | hdot | hrotsum | hbsgs | hrescale | hmodraise | hsquare, e.g. "hmult,hrotate,hadd,hmult"; hrotate_hoisted (R output
+  // ops: comma-separated list of hmult | hrotate | hadd | pmult | padd | hlintrans | hdot | hrotsum | hbsgs | hrescale | hmodraise | hsquare | hlincomb, e.g. "hmult,hrotate,hadd,hmult"; hrotate_hoisted (R output
   // ciphertexts) only as the last op
   OpChain(const std::string &cfgPath, const std::string &opList, uint32_t maxLevel, uint32_t curLevel, uint32_t alpha,
           const std::map<std::string, uint32_t> &overrides = {});

@@ -86,6 +86,8 @@ inline std::vector<Read> recordReads(const Instruction &i) {
     for (AddrType a : i.dotOperands) v.push_back({a, Role::Operand, kNoDigit});
   } else if (!i.sqOperands.empty()) {    // (5q): the two polynomials of the one ciphertext, each read once
     for (AddrType a : i.sqOperands) v.push_back({a, Role::Operand, kNoDigit});
+  } else if (!i.lcOperands.empty()) {    // (5l): the input of every term
+    for (AddrType a : i.lcOperands) v.push_back({a, Role::Operand, kNoDigit});
   } else if (i.ops == MULT) {
     for (int b = 0; b < 4; ++b)
       if (eweOperandMask(i.opcode) & (1 << b)) v.push_back({i.operandList[b], Role::Operand, kNoDigit});

@@ -42,7 +42,8 @@ int hh_op_read_buffer_copy(hh_op *op, const char *name, uint32_t copy, uint64_t 
 /* real data in: overwrite a named input / key buffer ([n_limbs][N] words, fully reduced, evaluation form) of op `copy` of the batch; the
  * evaluation-key limbs ("IP_Key<k>_<j>", shared by the batch) live in copy 0.  Prepares the op if needed; synchronises. */
 int hh_op_write_buffer(hh_op *op, const char *name, uint32_t copy, const uint64_t *host);
-/* replaces the per-limb constants `name` of the op (hsquare: "scale", the s_j in [1, q_j); "const", the k_j in [0, q_j)) by n = level residues;
+/* replaces the per-limb constants `name` of the op (hsquare: "scale", the s_j in [1, q_j); "const", the k_j in [0, q_j); hlincomb: "scale1" .. "scale<T>",
+ * the s_{t,j} in [0, q_j), and "const") by n = level residues;
  * shared by the ops of a batch.  Before the op is prepared only; refused by op and name otherwise, and for n != level, an unreduced value, a
  * zero scale, or a name whose config key (sq_scale, sq_const) is 0. */
 int hh_op_set_constants(hh_op *op, const char *name, const uint64_t *values, uint32_t n);

@@ -29,7 +29,8 @@ struct Arch::Launch {
               L_TENSOR_DOT,                                  // (5d) the tensor products of several pairs of ciphertexts, summed
               L_IP_ROTSUM,                                   // (6s) the key products of rotations of different ciphertexts, summed
               L_IP_LINTRANS_MULTI,                           // (6m) several plaintext-weighted sums of the same hoisted key products
-              L_TENSOR_SQUARE } kind;                        // (5q) the scaled square of one ciphertext plus a constant
+              L_TENSOR_SQUARE,                               // (5q) the scaled square of one ciphertext plus a constant
+              L_LINCOMB } kind;                              // (5l) the sum of scaled polynomials plus a constant
   std::vector<uint32_t> hoistG;   // L_IP_HOISTED: the Galois element of every rotation (a: digits [n][T], b: keys [r][n][2][T], out: [r][n][2])
                                   // L_IP_LINTRANS: the same, with c: plaintexts [r][n], d: addend source [n] / out1: addend output [n] (HM_NO_LIMB: none; both
                                   // empty: no entry has one), out: [n][2]
@@ -54,6 +55,7 @@ struct Arch::Launch {
   uint32_t multiOuts = 0;
   std::vector<uint32_t> idPt, d1;
   uint32_t dotTerms = 0;          // L_TENSOR_DOT: pairs per record (a, b, c, d: [n][dotTerms], roles as L_TENSOR; out, out1, out2: [n])
+                                  // L_LINCOMB: terms per record (a: [n][dotTerms], out: [n]; k: the scalars [n][dotTerms], addK: the constants [n], empty: none)
                                   // L_TENSOR_SQUARE: a = c0, c = c1, out, out1, out2 = d0, d1, d2 [n]; k: the scalars [n], addK: the constants [n] (empty: none)
   std::string name;
   std::string statKey;
@@ -152,6 +154,9 @@ Arch::Arch(Config *cfg) : config(cfg) {
   // (5q) hsquare: the tensor product of the ciphertext with itself, the scalar on its three outputs and the constant on d0 become one
   // hm_tensor_square launch.  Config key fuse_square (default 1).
   fuseSquare = cfg->getValueOr("fuse_square", 1) != 0;
+  // (5l) hlincomb: the MUL_CONST of every term, the ADDs between them and the ADD_CONST behind them become one hm_lincomb launch.  Config key
+  // fuse_lincomb (default 1).
+  fuseLincomb = cfg->getValueOr("fuse_lincomb", 1) != 0;
   // (4p) pmult with rescale = 1: the products are formed by the rescale's transforms while they load.  Config key fuse_pmul_rescale: 1 / 0 = always /
   // never; not given = where it was measured faster than the three-launch plan: everywhere but the generic back-end's launches
   // inside the one-launch form's limit, which has no product form there (Planner::productOperands)
@@ -315,6 +320,7 @@ int partKey(const Instruction &i) {
   if (isKeyProduct(i)) return 300 + (int)i.ipX.size() * 10 + (int)i.ipY.size();                            // 300+: key product, by digits and keys
   if (!i.dotOperands.empty()) return 8000 + (int)i.dotOperands.size() / 4;                                 // 8000+: sum of tensor products, by pairs
   if (!i.sqOperands.empty()) return 8500 + (i.sqHasScale ? 1 : 0) + (i.sqHasConst ? 2 : 0);                // 8500+: scaled square plus constant, by what it absorbed
+  if (!i.lcOperands.empty()) return 8600 + (int)i.lcOperands.size();                                   // 8600+: sum of scaled polynomials, by terms
   if (i.fusedTensor) return 200;                                                                           // 200: tensor product
   if (i.fusedSubScale && i.fMinuendB) return i.fMix ? 211 : 209;                                           // 209 / 211: ... with a product minuend (4p)
   if (i.fusedSubScale) return (i.fMix ? 203 : 201) + (i.fConvIn.empty() ? 0 : 4);                          // 201 / 203: fused forward transform, plain / merged; 205 / 207: with its conversion
@@ -484,6 +490,7 @@ struct Arch::LaunchBuilder {
   void tensor(Launch &L, Recs recs);
   void tensorDot(Launch &L, Recs recs);
   void tensorSquare(Launch &L, Recs recs);
+  void lincomb(Launch &L, Recs recs);
   void nttSubScale(Launch &L, Recs recs);
   void copy(Launch &L, Recs recs);
   void transform(Launch &L, Recs recs);
@@ -644,6 +651,22 @@ void Arch::LaunchBuilder::tensorSquare(Launch &L, Recs recs) {
     if (recs[0]->sqHasConst) L.addK.push_back(i->sqConst);
   }
   L.bytes = 5 * LP * recs.size();   // two polynomials read, three written
+}
+
+// (5l) a = the input of every term [n][T]; out = the sum [n]; k = the scalars [n][T], addK = the constants [n] (hm_lincomb).  The part key keeps
+// records of different term counts apart; a record without a constant (c1 beside a c0 that has one) adds 0, which changes no residue
+void Arch::LaunchBuilder::lincomb(Launch &L, Recs recs) {
+  L.kind = Launch::L_LINCOMB; L.statKey = "EWE";
+  L.dotTerms = (uint32_t)recs[0]->lcOperands.size();
+  for (Instruction *i : recs) {
+    for (AddrType x : i->lcOperands) L.a.push_back(limb(x));
+    L.k.insert(L.k.end(), i->lcScales.begin(), i->lcScales.end());
+    L.out.push_back(limb(i->OutputOperand));
+    L.mods.push_back(i->mod_id);
+  }
+  if (std::any_of(recs.begin(), recs.end(), [](const Instruction *i) { return i->lcHasConst; }))
+    for (Instruction *i : recs) L.addK.push_back(i->lcHasConst ? i->lcConst : 0);
+  L.bytes = (L.dotTerms + 1ull) * LP * recs.size();   // every input read once, the sum written once
 }
 
 // fused forward transform (4, 4b, 9, 12)
@@ -814,6 +837,7 @@ void Arch::LaunchBuilder::emitCompute(const Group &group, Launches &front, Launc
   else if (isKeyProduct(*f)) ip(*L, recs);
   else if (!f->dotOperands.empty()) tensorDot(*L, recs);
   else if (!f->sqOperands.empty()) tensorSquare(*L, recs);
+  else if (!f->lcOperands.empty()) lincomb(*L, recs);
   else if (f->fusedTensor) tensor(*L, recs);
   else if (f->fusedSubScale) nttSubScale(*L, recs);
   else if (f->ops == NTT && f->passthrough) copy(*L, recs);
@@ -1226,7 +1250,7 @@ void Arch::prepare() {
 
 static const char *const kLaunchKindNames[] = {"NTT", "INTT", "EWE", "BCONV", "AUTO", "NTT_SUBSCALE", "TENSOR", "EXCH_IN", "EXCH_OUT", "REPLICATE", "IP", "NTT_IP",
                                                "BCONV_COL", "EXCH_IN_COL", "EXCH_OUT_COL", "IP_HOISTED", "IP_LINTRANS", "TENSOR_DOT", "IP_ROTSUM",
-                                               "IP_LINTRANS_MULTI", "TENSOR_SQUARE"};
+                                               "IP_LINTRANS_MULTI", "TENSOR_SQUARE", "LINCOMB"};
 
 // Per-launch device time (SURVEY.md §8d "per-stage hipEvent times", exchange time at N > 1): every launch of the plan
 // bracketed by its own event pair, in plan order so that the data dependencies (and, sharded, the collectives) line up.
@@ -1280,6 +1304,8 @@ std::string Arch::planText() const {
     if (l->kind == Launch::L_TENSOR_DOT) out += " terms=" + std::to_string(l->dotTerms);   // (5d): pairs summed per record
     if (l->kind == Launch::L_TENSOR_SQUARE)   // (5q): what the records absorbed
       out += std::string(" scale=") + (l->k.empty() ? "0" : "1") + " const=" + (l->addK.empty() ? "0" : "1");
+    if (l->kind == Launch::L_LINCOMB)   // (5l): terms summed per record, and whether a constant follows
+      out += " terms=" + std::to_string(l->dotTerms) + " const=" + (l->addK.empty() ? "0" : "1");
     if (l->kind == Launch::L_IP_LINTRANS)   // (6l): entries that also form the addend output
       out += " addend=" + std::to_string(l->d.size() - (size_t)std::count(l->d.begin(), l->d.end(), HM_NO_LIMB));
     if (l->kind == Launch::L_IP_LINTRANS_MULTI)   // (6m): groups, entries that also form the groups' addend outputs
@@ -1459,6 +1485,9 @@ void Arch::enqueue(Launch &l) {
   case Launch::L_TENSOR_SQUARE:
     st = hm_tensor_square(ctx, pool, l.a.data(), pool, l.c.data(), pool, l.out.data(), pool, l.out1.data(), pool, l.out2.data(), l.mods.data(), cnt,
                           l.k.empty() ? nullptr : l.k.data(), l.addK.empty() ? nullptr : l.addK.data());
+    break;
+  case Launch::L_LINCOMB:
+    st = hm_lincomb(ctx, pool, l.a.data(), pool, l.out.data(), l.mods.data(), cnt, l.dotTerms, l.k.data(), l.addK.empty() ? nullptr : l.addK.data());
     break;
   case Launch::L_EXCH_IN:
     st = hm_limbs_to_slices(ctx, pool, l.exLimbs.data(), l.exOwners.data(), (uint32_t)l.exLimbs.size(), l.slicesIn);

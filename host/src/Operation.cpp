@@ -898,6 +898,76 @@ HSQUARE::HSQUARE(std::string labelName, uint32_t maxLevel, uint32_t currentLevel
   finishConstruction();
 }
 
+// hlincomb (build extension).  Per component k, with x_t = ct<t>.c<k>: LinComb_Scale_(t)_C<k> = s_t x_t (MUL_CONST) for every t,
+// LinComb_Add_(t)_C<k> = the running sum plus term t (ADD) for t >= 2, and with lc_const = 1 LinComb_Const_C0 = the sum of c0 plus k (ADD_CONST: the
+// constant polynomial in evaluation form, on c0 only as PADD's plaintext).  The last buffer of a component is LinCombOutput(k).  Unfused, the stages
+// run as element-wise launches; fused, pass (5l) of Arch::fusePasses (Planner.cpp) turns each limb's chain into one record of ONE launch.
+HLINCOMB::HLINCOMB(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch)
+    : OperationBase("HLINCOMB", labelName, cfg, _arch, maxLevel, currentLevel, alpha) {
+  if (arch->backend() == Arch::BACKEND_SIM) throw std::runtime_error("hlincomb: backend = sim has no such op (the reference has no scalar product)");
+  if (arch->world() > 1) throw std::runtime_error("hlincomb: world > 1 is not supported (the sharded plan is not built)");
+  const uint32_t T = cfg->getValueOr("terms", 4);
+  if (T < 1 || T > 16) throw std::runtime_error("hlincomb: terms = " + S(T) + ", must be in [1, 16]");
+  const uint32_t lc = cfg->getValueOr("lc_const", 0);
+  if (lc > 1) throw std::runtime_error("hlincomb: lc_const = " + S(lc) + ", must be 0 or 1");
+  const bool shifted = lc == 1, rescale = rescaleKey("hlincomb");
+  makeInputs(T);
+  constantStages["const"].key = "lc_const";
+  // the records of limb j of a constant stage, kept by name for setConstants; both components share the scalars
+  auto keep = [&](const std::string &name, const std::vector<INSGROUP> &recs) {
+    ConstantStage &cs = constantStages[name];
+    cs.enabled = true;
+    cs.records.resize(currentLevel);
+    for (uint32_t j = 0; j < currentLevel; ++j) cs.records[j].push_back(recs[j][0]);
+  };
+  auto synth = [&](uint64_t stream) {
+    std::vector<uint64_t> v;
+    for (uint32_t j = 0; j < currentLevel; ++j) v.push_back(synthWord0(stream + j, arch->modulus(j)));
+    return v;
+  };
+  std::array<std::vector<AddrType>, 2> out;
+  for (uint32_t k = 0; k < 2; k++) {
+    const std::string C = "_C" + S(k);
+    const bool constHere = shifted && k == 0;
+    Limbs sum;
+    for (uint32_t t = 1; t <= T; ++t) {
+      const bool lastScale = T == 1 && !constHere;
+      PerLimb m{labelName + "_LinComb_Scale_(" + S(t) + ")" + C + "_Level(", ")", range(0, currentLevel),
+                alloc(lastScale ? "LinCombOutput(" + S(k) + ")" : "LinCombScaled(" + S(t) + ")" + C, currentLevel)};
+      m.a = component(t - 1, k);
+      m.constants = synth(seed + 6200 + 100ull * t);
+      const Limbs scaled{m.out, eweLimbs(&insgener, EWE_MUL_CONST, m)};
+      driver.dispatchInstructions("LinComb_Scale_(" + S(t) + ")" + C, scaled.from);
+      keep("scale" + S(t), scaled.from);
+      if (t == 1) {
+        for (const INSGROUP &g : scaled.from) g[0]->lincombHead = true;
+        sum = scaled;
+        continue;
+      }
+      const bool lastAdd = t == T && !constHere;
+      PerLimb a{labelName + "_LinComb_Add_(" + S(t) + ")" + C + "_Level(", ")", m.mods,
+                alloc(lastAdd ? "LinCombOutput(" + S(k) + ")" : "LinCombSum(" + S(t) + ")" + C, currentLevel)};
+      const Limbs before = sum;
+      a.a = before.addr; a.c = scaled.addr; a.after = {&before.from, &scaled.from};
+      sum = {a.out, eweLimbs(&insgener, EWE_ADD, a)};
+      driver.dispatchInstructions("LinComb_Add_(" + S(t) + ")" + C, sum.from);
+    }
+    if (constHere) {
+      PerLimb c{labelName + "_LinComb_Const" + C + "_Level(", ")", range(0, currentLevel), alloc("LinCombOutput(" + S(k) + ")", currentLevel)};
+      const Limbs before = sum;
+      c.a = before.addr; c.after = {&before.from};
+      c.constants = synth(seed + 6290);
+      sum = {c.out, eweLimbs(&insgener, EWE_ADD_CONST, c)};
+      driver.dispatchInstructions("LinComb_Const" + C, sum.from);
+      keep("const", sum.from);
+    }
+    out[k] = sum.addr;
+  }
+  if (rescale) setRescaledOutput("out", out);
+  else for (uint32_t k = 0; k < 2; k++) setOutput("out", k, out[k]);
+  finishConstruction();
+}
+
 // hrotsum (build extension).  out = sum_i rot_{g_i}(ct<i>), g_i = g^i mod 2N, over G DIFFERENT ciphertexts with ONE ModDown: the ModDown is linear,
 // so the G key products are summed on the E = l + alpha limbs and brought down once (the ModUps cannot be shared: the ciphertexts differ).
 //   D_{i,j} = ModUp(ct<i>.c1)                          per ciphertext, on the unrotated c1 (buffers and stages of ciphertext i >= 2 suffixed _Ct<i>)
@@ -1129,6 +1199,7 @@ static OperationBase *makeOp(const std::string &o, uint32_t maxLevel, uint32_t l
   if (o == "hrescale") return new HRESCALE("test_hrescale", maxLevel, level, alpha, cfg, arch);
   if (o == "hmodraise") return new HMODRAISE("test_hmodraise", maxLevel, level, alpha, cfg, arch);
   if (o == "hsquare") return new HSQUARE("test_hsquare", maxLevel, level, alpha, cfg, arch);
+  if (o == "hlincomb") return new HLINCOMB("test_hlincomb", maxLevel, level, alpha, cfg, arch);
   throw std::runtime_error("Error operation requirement, please double confirm!");
 }
 

@@ -106,6 +106,7 @@ struct Arch::Planner {
   void tensor();           // 5
   void tensorDot();        // 5d
   void tensorSquare();     // 5q
+  void linearCombination();   // 5l
   void keyProduct();       // 6
   // what (6m/6l), (6s) and (6h) all recognise: the live two-key key-product records whose digits are all automorphisms, by one element per record, of
   // the same materialised digits and are read by nothing else; per (modulus, unrotated digits) the records and their automorphisms, in stage order
@@ -147,6 +148,7 @@ void Arch::fusePasses(std::vector<Stage> &st) {
   p.tensor();
   if (fuseDot) p.tensorDot();   // before (6): the multiply-accumulate chains it absorbs are not key products
   if (fuseSquare) p.tensorSquare();
+  if (fuseLincomb) p.linearCombination();
   p.keyProduct();
   // (6m, 6l) before (6s) and (6h): the records it merges are the ones (6h) would claim, and none of them is (6s)'s (their outputs go into products,
   // not into sums).  fuse_bsgs: the groups with several sums, fuse_lintrans: the ones with one
@@ -492,6 +494,58 @@ void Arch::Planner::tensorSquare() {
     c->extraOutputs = {d0, d2};
     for (const Write &w : recordWrites(*c)) producer[w.addr] = c;
     place.moveTo(c, last);
+  }
+}
+
+// (5l) sum of scaled polynomials plus constant (hlincomb): from a MUL_CONST record that the builder marked as term 1 of a sum (lincombHead), term
+//      after term, the running sum goes on through ONE ADD whose other operand is a MUL_CONST record of the same modulus read by nothing else;
+//      behind the last term, ONE ADD_CONST.  Every intermediate is read only by the next link.  The links merge into the marked record:
+//      hm_lincomb sums the raw products s_t x_t of all terms, adds the constant and stores the final sum only.  Never written: the T scaled
+//      polynomials and the T - 1 partial sums (and the sum in front of the constant).  The record takes the place of the last record it absorbs.
+//      Only the builder of HLINCOMB sets the mark: the pass matches nothing in any other op.
+//      Sets on the marked record: lcOperands, lcScales, lcHasConst, lcConst, OutputOperand.
+void Arch::Planner::linearCombination() {
+  Readers rd = readers();
+  Placement place(st);
+  std::vector<Instruction *> heads;
+  for (auto &s : st)
+    for (Instruction *i : s.ins)
+      if (live(i) && i->lincombHead && i->ops == MULT && i->opcode == EWE_MUL_CONST && i->hasConstant && i->lcOperands.empty()) heads.push_back(i);
+  for (Instruction *c : heads) {
+    c->lcOperands = {c->operandList[0]};
+    c->lcScales = {c->constant};
+    AddrType sum = c->OutputOperand;
+    Instruction *last = c;
+    auto take = [&](Instruction *i) {
+      absorb(c, i);
+      if (place.after(i, last)) last = i;
+    };
+    while (c->lcOperands.size() < HM_LINCOMB_MAX_TERMS) {
+      Instruction *add = soleReader(rd, sum, EWE_ADD, c->mod_id);
+      if (!add) break;
+      const AddrType other = add->operandList[0] == sum ? add->operandList[2] : add->operandList[0];
+      if ((add->operandList[0] != sum && add->operandList[2] != sum) || other == sum) break;
+      Instruction *mul = producerOf(other);
+      if (!mul || !live(mul) || mul->ops != MULT || mul->opcode != EWE_MUL_CONST || !mul->hasConstant || mul->mod_id != c->mod_id || mul->lincombHead ||
+          !onlyReader(rd, other, add))
+        break;
+      c->lcOperands.push_back(mul->operandList[0]);
+      c->lcScales.push_back(mul->constant);
+      take(mul);
+      take(add);
+      sum = add->OutputOperand;
+    }
+    if (Instruction *add = soleReader(rd, sum, EWE_ADD_CONST, c->mod_id)) {
+      if (add->hasConstant) {
+        c->lcHasConst = true;
+        c->lcConst = add->constant;
+        take(add);
+        sum = add->OutputOperand;
+      }
+    }
+    c->OutputOperand = sum;
+    producer[sum] = c;
+    place.moveTo(c, last);   // to where its last link stood
   }
 }
 

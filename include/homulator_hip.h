@@ -188,6 +188,21 @@ hm_status hm_tensor_square(hm_ctx *ctx, const uint64_t *a, const uint32_t *a_lim
                            uint64_t *o0, const uint32_t *o0_limbs, uint64_t *o1, const uint32_t *o1_limbs, uint64_t *o2,
                            const uint32_t *o2_limbs, const uint32_t *mod_ids, uint32_t n, const uint64_t *scale, const uint64_t *addend);
 
+/* K3, sum of n_terms scaled limb-polys plus a constant in one pass over the n_terms inputs (HLINCOMB): for entry i, with
+ * s_t = scale[i * n_terms + t] in [0, q) and k = addend[i] in [0, q), per coefficient
+ *   out[i] = sum_t s_t * in[i][t] + k,   t < n_terms <= 16,
+ * the canonical residue of the exact integer sum: bit-identical to HM_OP_MUL_CONST per term, HM_OP_ADD between them and HM_OP_ADD_CONST
+ * behind, none of whose intermediates is written (n_terms + 1 limb-polys per entry where that chain moves 5 n_terms - 1).  A zero scalar is a
+ * term that contributes nothing.  in_limbs is row-major, in_limbs[i * n_terms + t] (the same limb-poly may appear in several entries and terms);
+ * out_limbs and mod_ids have n entries; a null limb list is the identity.  scale and addend are host arrays; addend == NULL: every k is 0.  The
+ * records live in a device table: one launch serves any n, and the call is safe under graph capture once it has run with the same lists and
+ * constants.  HM_ERR_ARG: a null buffer or a null mod_ids / scale, n_terms outside 1..16, a limb or modulus id out of range, an unreduced scale
+ * or addend, an output limb-poly that overlaps (by address range, not by base pointer) an input limb-poly or another output limb-poly.
+ * n = 0 is HM_OK. */
+#define HM_LINCOMB_MAX_TERMS 16
+hm_status hm_lincomb(hm_ctx *ctx, const uint64_t *in, const uint32_t *in_limbs, uint64_t *out, const uint32_t *out_limbs,
+                     const uint32_t *mod_ids, uint32_t n, uint32_t n_terms, const uint64_t *scale, const uint64_t *addend);
+
 /* K5 — inner product with the evaluation key in one pass: for limb i, out[i][k] = sum_{j < n_terms}
  * x[i][j] * y[i][k][j], k < n_out (n_terms <= 4 digits, n_out <= 2 keys).  Limb lists are row-major:
  * x_limbs[i * n_terms + j], y_limbs[(i * n_out + k) * n_terms + j], out_limbs[i * n_out + k].  Replaces
