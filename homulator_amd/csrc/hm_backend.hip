@@ -509,6 +509,13 @@ __global__ void __launch_bounds__(256) k_lincomb(HmLincombArgs a) {
   if (entry < a.n_limbs) hm_lincomb_thread(a, entry, blockIdx.x & ((1u << logPer) - 1u), threadIdx.x);
 }
 
+// scaled tensor product plus a linear combination of further ciphertexts plus a constant (hm_elem_core.h: hm_tensor_muladd_thread): k_tensor_dot's
+// geometry, the records in a device table
+__global__ void __launch_bounds__(256) k_tensor_muladd(HmTensorMulAddArgs a) {
+  const uint32_t logPer = a.logN - 9, entry = blockIdx.x >> logPer;
+  if (entry < a.n_limbs) hm_tensor_muladd_thread(a, entry, blockIdx.x & ((1u << logPer) - 1u), threadIdx.x);
+}
+
 // 16-byte units per thread of the element-wise kernel, 512 coefficients apart, all loads in flight before the first use.  1: 89 600 workgroups for a batch of
 // ten hadd; 2 / 4 measured padd +3 / +5 %, pmult +1 %, hadd within the noise (tools/r06_ewe_ab.sh): not worth a second shape of the kernel's launch
 #ifndef HM_EWE_UNITS
@@ -1878,6 +1885,71 @@ extern "C" hm_status hm_lincomb(hm_ctx *c, const uint64_t *in, const uint32_t *l
   a.in = in; a.out = out;
   a.mods = c->d_mods; a.logN = c->P.logN; a.n_limbs = n; a.n_terms = T;
   hipLaunchKernelGGL(k_lincomb, dim3(n * (N / 512)), dim3(256), 0, c->stream, a);
+  HM_HIP(c, hipGetLastError());
+  return HM_OK;
+}
+
+// scaled tensor product plus n_addends scaled ciphertexts plus a constant: operand and output lists [n], addend lists and scalars [n][n_addends];
+// one record per entry in a device table, ONE launch for any n
+extern "C" hm_status hm_tensor_muladd(hm_ctx *c, const uint64_t *pa, const uint32_t *la, const uint64_t *pb, const uint32_t *lb, const uint64_t *pc,
+                                      const uint32_t *lc, const uint64_t *pd, const uint32_t *ld, const uint64_t *px, const uint32_t *lx0,
+                                      const uint32_t *lx1, uint64_t *o0, const uint32_t *l0, uint64_t *o1, const uint32_t *l1, uint64_t *o2,
+                                      const uint32_t *l2, const uint32_t *mod_ids, uint32_t n, uint32_t n_addends, const uint64_t *scale,
+                                      const uint64_t *add_scale, const uint64_t *addend) {
+  static const char *const what = "hm_tensor_muladd";
+  if (!c) return HM_ERR_ARG;
+  HM_TABLE_CALL(c);
+  if (!pa || !pb || !pc || !pd || !o0 || !o1 || !o2) return fail(c, HM_ERR_ARG, "%s: null buffer", what);
+  const uint32_t A = n_addends, N = c->P.N;
+  if (A > HM_MULADD_MAX_ADDENDS) return fail(c, HM_ERR_ARG, "%s: n_addends = %u, must be in [0, %d]", what, A, HM_MULADD_MAX_ADDENDS);
+  if (A > 0 && !px) return fail(c, HM_ERR_ARG, "%s: null buffer", what);
+  if (A > 0 && (!lx0 || !lx1)) return fail(c, HM_ERR_ARG, "%s: x0_limbs or x1_limbs is null", what);
+  if (A > 0 && !add_scale) return fail(c, HM_ERR_ARG, "%s: add_scale is null", what);
+  if ((uint64_t)n > 0xFFFFFFFFull / (HM_MULADD_REC_WORDS(A) * sizeof(uint32_t)))
+    return fail(c, HM_ERR_ARG, "%s: n = %u entries of %u addends are too many for one call", what, n, A);
+  struct List { const char *name; const void *base; const uint32_t *limbs; uint32_t count; };
+  const List ins[6] = {{"a", pa, la, n}, {"b", pb, lb, n}, {"c", pc, lc, n}, {"d", pd, ld, n}, {"x", px, lx0, A ? n * A : 0}, {"x", px, lx1, A ? n * A : 0}};
+  const List outs[3] = {{"o0", o0, l0, n}, {"o1", o1, l1, n}, {"o2", o2, l2, n}};
+  hm_status st;
+  for (const List &l : ins)
+    if ((st = check_limbs(c, what, l.limbs, l.count))) return st;
+  for (const List &l : outs)
+    if ((st = check_limbs(c, what, l.limbs, l.count))) return st;
+  if ((st = check_mods(c, what, mod_ids, n))) return st;
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint64_t q = c->P.mod[mod_ids[i]];
+    if (scale && (scale[i] == 0 || scale[i] >= q)) return fail(c, HM_ERR_ARG, "%s: scale[%u] is %s", what, i, scale[i] ? "not reduced" : "zero");
+    for (uint32_t t = 0; t < A; ++t)
+      if (add_scale[(size_t)i * A + t] >= q) return fail(c, HM_ERR_ARG, "%s: add_scale[%u][%u] is not reduced", what, i, t);
+    if (addend && addend[i] >= q) return fail(c, HM_ERR_ARG, "%s: addend[%u] is not reduced", what, i);
+  }
+  // a workgroup stores its three outputs after ALL its loads, and the same input limb-poly may serve several records and addends: no output may
+  // share an address with any input or with another output (hm_tensor_dot's rule and messages)
+  for (const List &o : outs)
+    for (const List &i : ins)
+      if (i.count && hm_limbs_overlap(o.base, o.limbs, o.count, i.base, i.limbs, i.count, N))
+        return fail(c, HM_ERR_ARG, "%s: an output limb-poly (%s) overlaps an input limb-poly (%s)", what, o.name, i.name);
+  {
+    std::vector<uintptr_t> starts;
+    for (const List &o : outs)
+      for (uint32_t i = 0; i < o.count; ++i) starts.push_back(reinterpret_cast<uintptr_t>(o.base) + (uintptr_t)limb_at(o.limbs, i) * N * 8);
+    std::sort(starts.begin(), starts.end());
+    for (size_t i = 1; i < starts.size(); ++i)
+      if (starts[i] - starts[i - 1] < (uintptr_t)N * 8) return fail(c, HM_ERR_ARG, "%s: two output limb-polys overlap", what);
+  }
+  if (n == 0) return HM_OK;
+  std::vector<uint32_t> recs((size_t)n * HM_MULADD_REC_WORDS(A));
+  std::vector<uint64_t> qs(n);
+  for (uint32_t i = 0; i < n; ++i) qs[i] = c->P.mod[mod_ids[i]];
+  hm_tensor_muladd_fill_recs(recs.data(), la, lb, lc, ld, lx0, lx1, l0, l1, l2, mod_ids, qs.data(), n, A, scale, add_scale, addend);
+  HM_HIP(c, hipSetDevice(c->device));
+  HmTensorMulAddArgs a;
+  const void *tab = nullptr;
+  if ((st = device_table(c, recs.data(), recs.size() * sizeof(uint32_t), &tab))) return st;
+  a.rec = static_cast<const uint32_t *>(tab);
+  a.a = pa; a.b = pb; a.c = pc; a.d = pd; a.x = A ? px : pa; a.o0 = o0; a.o1 = o1; a.o2 = o2;
+  a.mods = c->d_mods; a.logN = c->P.logN; a.n_limbs = n; a.n_addends = A;
+  hipLaunchKernelGGL(k_tensor_muladd, dim3(n * (N / 512)), dim3(256), 0, c->stream, a);
   HM_HIP(c, hipGetLastError());
   return HM_OK;
 }

@@ -489,6 +489,148 @@ HM_HD void hm_lincomb_thread(const HmLincombArgs &g, uint32_t entry, uint32_t ch
   hm_bst2(g.out + rec[1] * N, lane_bytes, hm_barrett_wide(s[0] + k, m), hm_barrett_wide(s[1] + k, m));
 }
 
+// Scaled tensor product of TWO ciphertexts plus a linear combination of A further ciphertexts plus a constant, in one pass over the 4 + 2A
+// inputs (hm_tensor_muladd; HMULADD):
+//   d0 = s a b + sum_t u_t x_t + k,  d1 = s (a d + c b) + sum_t u_t y_t,  d2 = s c d
+// with hm_tensor_one's roles (a = c00, b = c10, c = c01, d = c11), x_t / y_t = c0 / c1 of addend t, s in [1, q), u_t and k in [0, q) per record and
+// every input canonical.  One form on both arithmetic back-ends: a and c are brought to as = s a mod q and cs = s c mod q, canonical, by the
+// exact Shoup product (hm_shoup: any 64-bit operand, w < q) behind a limb-uniform branch that s = 1 skips; then the raw 64 x 64 products as b,
+// as d + cs b, cs d and u_t x_t, u_t y_t are summed in three 128-bit accumulators per coefficient, k is added to d0's, and each accumulator is
+// reduced ONCE by hm_barrett_wide, which takes any 128-bit value.  Every factor is below q < 2^60, so a product is below 2^120: d1's accumulator
+// holds 2 + A <= 10 of them, below 10 * 2^120 < 2^124; d0's 1 + A <= 9 and k < 2^60, below 2^124 as well; d2's one.  The result is the canonical
+// residue of the exact integer sum, and s a b = (s a mod q) b mod q, hence bit-identical to hm_tensor followed by MUL_CONST, MUL_CONST + ADD per
+// addend and ADD_CONST.
+#define HM_MULADD_MAX_ADDENDS HM_TENSOR_MULADD_MAX_ADDENDS
+static_assert(HM_MULADD_MAX_ADDENDS == 8, "d1's accumulator: 2 + A <= 10 products below 2^120 stay below 2^124; d0's: 1 + A products plus k < 2^60 as well");
+// a record = HM_MULADD_REC_WORDS(A) 32-bit words, a multiple of 16 bytes, the 64-bit values at 8-byte offsets:
+//   0: modulus id   1..4: the limbs of a, b, c, d   5..7: the limbs of d0, d1, d2   8: A   9: s != 1
+//   10, 11: s   12, 13: its Shoup companion floor(s 2^64 / q)   14, 15: k
+// then per addend (limb of x_t, limb of y_t, u_t: 2 words)
+#define HM_MULADD_REC_HEAD 16u
+#define HM_MULADD_REC_WORDS(A) (HM_MULADD_REC_HEAD + 4u * (A))
+struct HmTensorMulAddArgs {
+  const uint64_t *a, *b, *c, *d, *x;
+  uint64_t *o0, *o1, *o2;
+  const HmMod *mods;
+  const uint32_t *rec;   // device, [n_limbs][HM_MULADD_REC_WORDS(n_addends)]: read through the scalar cache (wave-uniform index)
+  uint32_t logN, n_limbs, n_addends;
+};
+// The records of n entries from the entry point's limb lists (a .. d, o0 .. o2: [n], a null list is the identity; lx0, lx1: [n][A]) and
+// constants (scale: [n] or null = 1; add_scale: [n][A]; addend: [n] or null = 0; all already checked: reduced, scale != 0); q[i] = the modulus
+// of entry i.  Host side.
+inline void hm_tensor_muladd_fill_recs(uint32_t *rec, const uint32_t *la, const uint32_t *lb, const uint32_t *lc, const uint32_t *ld, const uint32_t *lx0,
+                                       const uint32_t *lx1, const uint32_t *l0, const uint32_t *l1, const uint32_t *l2, const uint32_t *mod_ids,
+                                       const uint64_t *q, uint32_t n, uint32_t A, const uint64_t *scale, const uint64_t *add_scale, const uint64_t *addend) {
+  auto at = [](const uint32_t *l, uint32_t i) { return l ? l[i] : i; };
+  auto put64 = [](uint32_t *r, uint64_t v) { r[0] = (uint32_t)v; r[1] = (uint32_t)(v >> 32); };
+  for (uint32_t i = 0; i < n; ++i) {
+    uint32_t *r = rec + (size_t)i * HM_MULADD_REC_WORDS(A);
+    const uint64_t s = scale ? scale[i] : 1;
+    r[0] = mod_ids[i]; r[1] = at(la, i); r[2] = at(lb, i); r[3] = at(lc, i); r[4] = at(ld, i);
+    r[5] = at(l0, i); r[6] = at(l1, i); r[7] = at(l2, i); r[8] = A; r[9] = s != 1 ? 1u : 0u;
+    put64(r + 10, s); put64(r + 12, hm_shoup_companion(s, q[i])); put64(r + 14, addend ? addend[i] : 0);
+    for (uint32_t t = 0; t < A; ++t) {
+      const uint32_t e = i * A + t;
+      uint32_t *w = r + HM_MULADD_REC_HEAD + 4 * t;
+      w[0] = lx0[e]; w[1] = lx1[e]; put64(w + 2, add_scale[e]);
+    }
+  }
+}
+template <class REC>
+HM_HD uint64_t hm_muladd_rec64(REC rec, uint32_t w) { return (uint64_t)rec[w] | ((uint64_t)rec[w + 1] << 32); }
+struct HmMulAddTerm {   // the (limb of x_t, limb of y_t, scalar) of one addend: four words of the record
+  uint32_t x, y;
+  uint64_t u;
+};
+// the words of addend t; the caller clamps t to the last addend, and a record without addends hands out words of its header instead (never used):
+// always inside the record
+template <class REC>
+HM_HD HmMulAddTerm hm_muladd_term(REC rec, uint32_t A, uint32_t t) {
+  const uint32_t w = A ? HM_MULADD_REC_HEAD + 4 * t : HM_MULADD_REC_HEAD - 4;
+  return HmMulAddTerm{rec[w], rec[w + 1], hm_muladd_rec64(rec, w + 2)};
+}
+struct HmMulAddPair {   // the aligned pair of coefficients a thread owns of both components of one addend, with the addend's scalar
+  uint64_t x[2], y[2], u;
+};
+// two 16-byte loads from wave-uniform bases at the lane's offset
+HM_HD HmMulAddPair hm_muladd_ld(const HmTensorMulAddArgs &g, const HmMulAddTerm &l, size_t N, uint32_t lane_bytes) {
+  HmMulAddPair v;
+  hm_bld2(g.x + l.x * N, lane_bytes, v.x[0], v.x[1]);
+  hm_bld2(g.x + l.y * N, lane_bytes, v.y[0], v.y[1]);
+  v.u = l.u;
+  return v;
+}
+HM_HD void hm_muladd_acc2(HmDotAcc (&s)[2], const HmMulAddPair &v) {
+  s[0].d0 += (hm_u128)v.x[0] * v.u;
+  s[0].d1 += (hm_u128)v.y[0] * v.u;
+  s[1].d0 += (hm_u128)v.x[1] * v.u;
+  s[1].d1 += (hm_u128)v.y[1] * v.u;
+}
+// the scaled product of one coefficient into fresh accumulators
+HM_HD void hm_muladd_product(HmDotAcc &s, uint64_t a, uint64_t b, uint64_t c, uint64_t d, uint64_t scale, uint64_t scale_s, uint32_t scaled, uint64_t k,
+                             const HmMod &m) {
+  uint64_t as = a, cs = c;
+  if (scaled) {   // (limb-uniform)
+    as = hm_shoup(a, scale, scale_s, m.q);
+    cs = hm_shoup(c, scale, scale_s, m.q);
+  }
+  s.d0 = (hm_u128)as * b + k;
+  s.d1 = (hm_u128)as * d + (hm_u128)cs * b;
+  s.d2 = (hm_u128)cs * d;
+}
+// thread tid of the workgroup that owns chunk `chunk` (512 coefficients) of record `entry`: the pair at chunk * 512 + 2 tid, four 16-byte loads
+// for the product, two per addend, three 16-byte stores.  A is a run-time loop in hm_lincomb_thread's shape with the product in the place of
+// its first term: the loads of addend 1 are issued before the products of the tensor product are formed, then two addends per round in two
+// named register sets, the loads of addend t + 1 issued before the products of addend t, the record words of an addend requested a step
+// before its loads (hm_muladd_term: always inside the record).  A = 0 and A = 1 run no round; one addend is left behind the rounds.
+HM_HD void hm_tensor_muladd_thread(const HmTensorMulAddArgs &g, uint32_t entry, uint32_t chunk, uint32_t tid) {
+  const size_t N = (size_t)1 << g.logN;
+  const uint32_t A = g.n_addends, lane_bytes = (chunk * 512u + 2u * tid) << 3;
+  const auto rec = HM_CONST_PROB_T(uint32_t, g.rec) + (size_t)entry * HM_MULADD_REC_WORDS(A);
+  const HmMod m = HM_CONST_MODS(g.mods)[rec[0]];
+  const uint32_t scaled = rec[9];
+  const uint64_t scale = hm_muladd_rec64(rec, 10), scale_s = hm_muladd_rec64(rec, 12), k = hm_muladd_rec64(rec, 14);
+  HmDotPair v;
+  hm_bld2(g.a + rec[1] * N, lane_bytes, v.a[0], v.a[1]);
+  hm_bld2(g.b + rec[2] * N, lane_bytes, v.b[0], v.b[1]);
+  hm_bld2(g.c + rec[3] * N, lane_bytes, v.c[0], v.c[1]);
+  hm_bld2(g.d + rec[4] * N, lane_bytes, v.d[0], v.d[1]);
+  HmMulAddTerm l = hm_muladd_term(rec, A, 0);
+  HmMulAddPair p0, p1;
+  uint32_t t = 0;
+  if (A > 0) {   // (wave-uniform) addend 1 under the product
+    p0 = hm_muladd_ld(g, l, N, lane_bytes);
+    l = hm_muladd_term(rec, A, A > 1 ? 1u : 0u);
+    t = 1;
+  }
+  HM_DOT_ISSUED();
+  HmDotAcc s[2];
+  hm_muladd_product(s[0], v.a[0], v.b[0], v.c[0], v.d[0], scale, scale_s, scaled, k, m);
+  hm_muladd_product(s[1], v.a[1], v.b[1], v.c[1], v.d[1], scale, scale_s, scaled, k, m);
+#pragma unroll 1
+  for (; t + 1 < A; t += 2) {
+    p1 = hm_muladd_ld(g, l, N, lane_bytes);                      // addend t + 1
+    l = hm_muladd_term(rec, A, t + 1);
+    HM_DOT_ISSUED();
+    hm_muladd_acc2(s, p0);
+    p0 = hm_muladd_ld(g, l, N, lane_bytes);                      // addend t + 2
+    l = hm_muladd_term(rec, A, t + 2 < A ? t + 2 : A - 1);
+    HM_DOT_ISSUED();
+    hm_muladd_acc2(s, p1);
+  }
+  if (t < A) {   // (wave-uniform) an even number of addends: one more behind the rounds
+    p1 = hm_muladd_ld(g, l, N, lane_bytes);
+    HM_DOT_ISSUED();
+    hm_muladd_acc2(s, p0);
+    hm_muladd_acc2(s, p1);
+  } else if (A > 0) {
+    hm_muladd_acc2(s, p0);
+  }
+  hm_bst2(g.o0 + rec[5] * N, lane_bytes, hm_barrett_wide(s[0].d0, m), hm_barrett_wide(s[1].d0, m));
+  hm_bst2(g.o1 + rec[6] * N, lane_bytes, hm_barrett_wide(s[0].d1, m), hm_barrett_wide(s[1].d1, m));
+  hm_bst2(g.o2 + rec[7] * N, lane_bytes, hm_barrett_wide(s[0].d2, m), hm_barrett_wide(s[1].d2, m));
+}
+
 // The conversion table is read through the SCALAR cache: every lane of a wave needs the same entries, so they are
 // s_load'ed into SGPRs (asynchronously, no VGPRs, no LDS, no barrier) and feed v_mad_u64_u32 as scalar operands.
 // hipcc only emits scalar loads for memory it knows to be constant, hence the constant-address-space view of the

@@ -25,7 +25,7 @@ SYMBOLS = [
     "hm_bconv_col", "hm_limbs_to_colslices", "hm_colslices_to_limbs", "hm_ntt_second_pass", "hm_ntt_ex", "hm_capability", "hm_inner_product_ex",
     "hm_inner_product_hoisted", "hm_inner_product_lintrans", "hm_inner_product_rotsum", "hm_inner_product_lintrans_multi",
     "hm_tensor_dot", "hm_inner_product_lintrans_id", "hm_inner_product_rotsum_init", "hm_ntt_mix_sub_scale_mul", "hm_ntt_mul",
-    "hm_ntt_lift", "hm_tensor_square", "hm_lincomb",
+    "hm_ntt_lift", "hm_tensor_square", "hm_lincomb", "hm_tensor_muladd",
 ]
 
 
@@ -161,6 +161,7 @@ def load():
     L.hm_tensor_dot.argtypes = [vp] + [vp] * 15 + [u32, u32]
     L.hm_tensor_square.argtypes = [vp] + [vp] * 11 + [u32, vp, vp]
     L.hm_lincomb.argtypes = [vp] + [vp] * 5 + [u32, u32, vp, vp]
+    L.hm_tensor_muladd.argtypes = [vp] + [vp] * 18 + [u32, u32, vp, vp, vp]
     L.hm_inner_product.argtypes = [vp] + [vp] * 7 + [u32, u32, u32]
     L.hm_automorph.argtypes = [vp, vp, vp, vp, vp, u32, u32]
     L.hm_ewe.argtypes = [vp, i32] + [vp] * 11 + [u32, vp]
@@ -410,6 +411,19 @@ class Context:
         keep = [_u32(in_limbs), _u32(out_limbs), _u32(mod_ids)]
         ks, ka = _u64(scale), _u64(addend)
         self._ck(self.L.hm_lincomb(self.h, src.ptr, keep[0][1], out.ptr, keep[1][1], keep[2][1], len(mod_ids), int(n_terms), ks[1], ka[1]))
+
+    def tensor_muladd(self, a, b, c, d, x, o0, o1, o2, mod_ids, n_addends=0, x0_limbs=None, x1_limbs=None, scale=None, add_scale=None, addend=None,
+                      limbs=None):
+        """o0 = s * a * b + sum_t u_t * x_t + k, o1 = s * (a * d + c * b) + sum_t u_t * y_t, o2 = s * c * d per entry (hm_tensor_muladd): s =
+        scale[i] (None: 1), u_t = add_scale[i][t], k = addend[i] (None: 0), residues of the entry's modulus; x_t / y_t = the limb-polys
+        x0_limbs[i][t] / x1_limbs[i][t] of the buffer x (row-major [n][n_addends], flat; x and the three lists may be None at n_addends = 0).
+        limbs: the seven limb lists of a, b, c, d, o0, o1, o2 (None: the identity), [n] each; buffers: anything with a device address `.ptr`"""
+        ls = limbs or [None] * 7
+        keep = [_u32(v) for v in ls] + [_u32(x0_limbs), _u32(x1_limbs), _u32(mod_ids)]
+        ks, ku, ka = _u64(scale), _u64(add_scale), _u64(addend)
+        self._ck(self.L.hm_tensor_muladd(self.h, a.ptr, keep[0][1], b.ptr, keep[1][1], c.ptr, keep[2][1], d.ptr, keep[3][1],
+                                         x.ptr if x is not None else None, keep[7][1], keep[8][1], o0.ptr, keep[4][1], o1.ptr, keep[5][1],
+                                         o2.ptr, keep[6][1], keep[9][1], len(mod_ids), int(n_addends), ks[1], ku[1], ka[1]))
 
     def inner_product(self, x, x_limbs, y, y_limbs, out, out_limbs, mod_ids, n_terms, n_out, x_galois=0):
         keep = [_u32(v) for v in (x_limbs, y_limbs, out_limbs, mod_ids)]

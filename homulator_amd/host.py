@@ -145,7 +145,8 @@ class Op:
         self._ck(self.L.hh_op_write_buffer(self.h, name.encode(), copy, a.ctypes.data_as(C.c_void_p)))
 
     def set_constants(self, name, values):
-        """replace the op's per-limb constants `name` (hsquare: "scale", "const"; hlincomb: "scale1" .. "scale<T>", "const") by one residue per
+        """replace the op's per-limb constants `name` (hsquare: "scale", "const"; hlincomb: "scale1" .. "scale<T>", "const"; hmuladd: "scale",
+        "addscale1" .. "addscale<A>", "const") by one residue per
         limb of the current level, before the op is prepared (hh_op_set_constants); shared by the ops of a batch"""
         a = np.ascontiguousarray(np.asarray([int(v) for v in values], dtype=np.uint64))
         self._ck(self.L.hh_op_set_constants(self.h, name.encode(), a.ctypes.data_as(C.c_void_p), len(a)))

@@ -132,6 +132,7 @@ private:
   bool fuseDot = true;       // pass (5d): the tensor products of several pairs of ciphertexts are summed before anything is stored (hdot)
   bool fuseSquare = true;    // pass (5q): the tensor product of a ciphertext with itself reads it once and takes the scalar and the constant behind it (hsquare)
   bool fuseLincomb = true;   // pass (5l): the scaled terms of a linear combination are summed before anything is stored, the constant behind them (hlincomb)
+  bool fuseMuladd = true;    // pass (5m): a tensor product takes the scalar, the scaled addends and the constant behind it (hmuladd)
   bool fusePmulRescale = true;   // pass (4p): a product of two op inputs read by one transform is formed by that transform (pmult with rescale = 1)
   bool fusePmulAuto = true;      // ... the key is not given: the pass declines where it was measured no faster (the generic back-end's small launches)
   bool genericArith = false;     // config key chain_bits: the chain hm_create serves with the generic arithmetic back-end

@@ -34,6 +34,7 @@ public:
   bool sumHead = false;      // a tensor product's MAC2 (d1) that is pair 1 of a SUM of tensor products (HDOT): pass (5d) starts its record here
   bool squareHead = false;   // a tensor product's MAC2 (d1) of a ciphertext with ITSELF (HSQUARE): pass (5q) starts its record here
   bool lincombHead = false;  // the MUL_CONST of term 1 of a sum of scaled ciphertexts (HLINCOMB): pass (5l) starts its record here
+  bool muladdHead = false;   // a tensor product's MAC2 (d1) that scalars, scaled addends and a constant follow (HMULADD): pass (5m) starts its record here
   std::vector<uint32_t> inMods;  // BCONV: modulus ids of the inputs
   unsigned long long refInstructions = 0;  // upstream instructions this record stands for
   unsigned long long refExtra = 0;         // ... of records folded into a BCONV record (not scaled by its MAC-port count)
@@ -82,6 +83,14 @@ public:
   std::vector<uint64_t> lcScales;
   bool lcHasConst = false;
   uint64_t lcConst = 0;
+  // (5m) scaled tensor product plus scaled addends plus constant (hm_tensor_muladd): a fusedTensor record that absorbed the chains behind its
+  // outputs.  maOperands = (c00, c10, c01, c11) of the product, then (x_t, y_t) of every addend; maAddScales = the scalars u_t; OutputOperand = the
+  // final d1, extraOutputs = the final d0, d2.  maHasScale: the MUL_CONST records behind the three outputs went in, all with the constant
+  // maScale; maHasConst: the ADD_CONST record behind d0 went in, with the constant maConst.  maOperands empty: not such a record
+  std::vector<AddrType> maOperands;
+  std::vector<uint64_t> maAddScales;
+  bool maHasScale = false, maHasConst = false;
+  uint64_t maScale = 1, maConst = 0;
   // fused inner product (ops == IP): out_k = sum_j ipX[j] * ipY[k][j]; out_0 = OutputOperand, out_1 = extraOutputs[0]
   std::vector<AddrType> ipX;
   std::vector<std::vector<AddrType>> ipY;

@@ -146,10 +146,10 @@ protected:
   bool rescaleKey(const std::string &op) const;
   // <out>.c<k> = Rescale(ct[k]), builder labels <label>_<k>, as HMULT's tail: the tail of the ops with rescale = 1, and all of HRESCALE
   void setRescaledOutput(const std::string &out, const std::array<std::vector<AddrType>, 2> &ct, bool inputMayBeOpInput = false);
-  // HMULT's tail on the three polynomials d of a tensor product (shared by HMULT, HDOT, HSQUARE): KS(d[2]); HMULT_Hadd_Key(k): d[k] + ks_k into
+  // HMULT's tail on the three polynomials d of a tensor product (shared by HMULT, HDOT, HSQUARE, HMULADD): KS(d[2]); HMULT_Hadd_Key(k): d[k] + ks_k into
   // HMULTHaddOutput(k); Rescale of both, out = the result at level - 1
   void relinearizeAndRescale(const std::array<std::vector<AddrType>, 3> &d);
-  // Per-limb constants an op carries in its records (HSQUARE: "scale", "const"; HLINCOMB: "scale<t>", "const"), by name: the records of limb j that hold value j, so that
+  // Per-limb constants an op carries in its records (HSQUARE: "scale", "const"; HLINCOMB: "scale<t>", "const"; HMULADD: "scale", "addscale<t>", "const"), by name: the records of limb j that hold value j, so that
   // setConstants can patch Instruction::constant before the plan is built.  enabled = false: the op knows the name but its config key is 0
   struct ConstantStage { bool enabled = false; std::string key; std::vector<std::vector<Instruction *>> records; bool nonZero = false; };
   std::map<std::string, ConstantStage> constantStages;
@@ -193,7 +193,7 @@ public:
   bool readBuffer(const std::string &name, uint64_t *host, uint32_t copy = 0);  // copy: op of the batch (config key `batch`)
   bool writeBuffer(const std::string &name, const uint64_t *host, uint32_t copy = 0);  // real data for an input / key buffer ([limbs][N], fully reduced)
   unsigned long long totalInstructions();
-  // replaces the per-limb constants `name` of the op (HSQUARE: "scale", "const"; HLINCOMB: "scale1" .. "scale<T>", "const") by n = level residues, values[j] reduced mod q_j; before prepare() only.
+  // replaces the per-limb constants `name` of the op (HSQUARE: "scale", "const"; HLINCOMB: "scale1" .. "scale<T>", "const"; HMULADD: "scale", "addscale1" .. "addscale<A>", "const") by n = level residues, values[j] reduced mod q_j; before prepare() only.
   // Refused, by op and name: after prepare(), n != level, an unreduced value (or a zero where the constant multiplies), a name whose config key is 0
   void setConstants(const std::string &name, const uint64_t *values, uint32_t n);
   Arch *getArch() { return arch; }
@@ -253,6 +253,17 @@ class HLINCOMB : public OperationBase {
 public:
   HLINCOMB(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
 };
+// hmuladd (build extension): out = Rescale(Relin(s * ct1 * ct2 + sum_t u_t * ct<2+t>) + k), one node of a polynomial evaluation (the Chebyshev step
+// T_{a+b} = 2 T_a T_b - T_{|a-b|}, the Paterson-Stockmeyer recombination p = q T_g + r).  2 + A input ciphertexts at one level (config key addends = A,
+// default 1, 0..8); with ma_scale = 1 the per-limb scalars s_j in [1, q_j) on the three polynomials of the tensor product (synthetic: word 0 of limb j
+// of stream seed + 6400, a 0 replaced by 1); the addend scalars u_{t,j} in [0, q_j) (stream seed + 6400 + 10 t; zero = the addend contributes nothing);
+// with ma_const = 1 the per-limb constants k_j on every evaluation-form entry of d0 only (stream seed + 6490).  All of it acts in front of the key
+// switch, at scale Delta^2 on the level of the inputs; then HMULT's tail with hmult's key IP_Key<k>_<j>.  setConstants("scale" | "addscale<t>" |
+// "const") replaces the synthetic values.  One output ciphertext out at level - 1.  A = 0 with both keys 0 is bit-identical to hmult.
+class HMULADD : public OperationBase {
+public:
+  HMULADD(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
+};
 class HROTSUM : public OperationBase {
 public:
   HROTSUM(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
@@ -300,7 +311,7 @@ class OpChain {
   std::vector<Arch *> archs;
   std::vector<OperationBase *> ops;
 public:
-  // ops: comma-separated list of hmult | hrotate | hadd | pmult | padd | hlintrans | hdot | hrotsum | hbsgs | hrescale | hmodraise | hsquare | hlincomb, e.g. "hmult,hrotate,hadd,hmult"; hrotate_hoisted (R output
+  // ops: comma-separated list of hmult | hrotate | hadd | pmult | padd | hlintrans | hdot | hrotsum | hbsgs | hrescale | hmodraise | hsquare | hlincomb | hmuladd, e.g. "hmult,hrotate,hadd,hmult"; hrotate_hoisted (R output
   // ciphertexts) only as the last op
   OpChain(const std::string &cfgPath, const std::string &opList, uint32_t maxLevel, uint32_t curLevel, uint32_t alpha,
           const std::map<std::string, uint32_t> &overrides = {});

@@ -88,6 +88,8 @@ inline std::vector<Read> recordReads(const Instruction &i) {
     for (AddrType a : i.sqOperands) v.push_back({a, Role::Operand, kNoDigit});
   } else if (!i.lcOperands.empty()) {    // (5l): the input of every term
     for (AddrType a : i.lcOperands) v.push_back({a, Role::Operand, kNoDigit});
+  } else if (!i.maOperands.empty()) {    // (5m): the four operands of the product, then both components of every addend
+    for (AddrType a : i.maOperands) v.push_back({a, Role::Operand, kNoDigit});
   } else if (i.ops == MULT) {
     for (int b = 0; b < 4; ++b)
       if (eweOperandMask(i.opcode) & (1 << b)) v.push_back({i.operandList[b], Role::Operand, kNoDigit});

@@ -30,7 +30,8 @@ struct Arch::Launch {
               L_IP_ROTSUM,                                   // (6s) the key products of rotations of different ciphertexts, summed
               L_IP_LINTRANS_MULTI,                           // (6m) several plaintext-weighted sums of the same hoisted key products
               L_TENSOR_SQUARE,                               // (5q) the scaled square of one ciphertext plus a constant
-              L_LINCOMB } kind;                              // (5l) the sum of scaled polynomials plus a constant
+              L_LINCOMB,                                     // (5l) the sum of scaled polynomials plus a constant
+              L_TENSOR_MULADD } kind;                        // (5m) the scaled tensor product plus scaled addends plus a constant
   std::vector<uint32_t> hoistG;   // L_IP_HOISTED: the Galois element of every rotation (a: digits [n][T], b: keys [r][n][2][T], out: [r][n][2])
                                   // L_IP_LINTRANS: the same, with c: plaintexts [r][n], d: addend source [n] / out1: addend output [n] (HM_NO_LIMB: none; both
                                   // empty: no entry has one), out: [n][2]
@@ -57,6 +58,9 @@ struct Arch::Launch {
   uint32_t dotTerms = 0;          // L_TENSOR_DOT: pairs per record (a, b, c, d: [n][dotTerms], roles as L_TENSOR; out, out1, out2: [n])
                                   // L_LINCOMB: terms per record (a: [n][dotTerms], out: [n]; k: the scalars [n][dotTerms], addK: the constants [n], empty: none)
                                   // L_TENSOR_SQUARE: a = c0, c = c1, out, out1, out2 = d0, d1, d2 [n]; k: the scalars [n], addK: the constants [n] (empty: none)
+  uint32_t maAddends = 0;         // L_TENSOR_MULADD: addends per record (a, b, c, d, out, out1, out2 as L_TENSOR; x0, x1: c0, c1 of the addends [n][maAddends];
+  std::vector<uint32_t> x0, x1;   // k: the scalars [n], maK: the addend scalars [n][maAddends], addK: the constants [n]; k / addK empty: none)
+  std::vector<uint64_t> maK;
   std::string name;
   std::string statKey;
   int opcode = 0;
@@ -157,6 +161,9 @@ Arch::Arch(Config *cfg) : config(cfg) {
   // (5l) hlincomb: the MUL_CONST of every term, the ADDs between them and the ADD_CONST behind them become one hm_lincomb launch.  Config key
   // fuse_lincomb (default 1).
   fuseLincomb = cfg->getValueOr("fuse_lincomb", 1) != 0;
+  // (5m) hmuladd: the tensor product, the scalar on its three outputs, the MUL_CONST + ADD pairs of the addends on d0 and d1 and the constant on d0
+  // become one hm_tensor_muladd launch.  Config key fuse_muladd (default 1).
+  fuseMuladd = cfg->getValueOr("fuse_muladd", 1) != 0;
   // (4p) pmult with rescale = 1: the products are formed by the rescale's transforms while they load.  Config key fuse_pmul_rescale: 1 / 0 = always /
   // never; not given = where it was measured faster than the three-launch plan: everywhere but the generic back-end's launches
   // inside the one-launch form's limit, which has no product form there (Planner::productOperands)
@@ -321,6 +328,7 @@ int partKey(const Instruction &i) {
   if (!i.dotOperands.empty()) return 8000 + (int)i.dotOperands.size() / 4;                                 // 8000+: sum of tensor products, by pairs
   if (!i.sqOperands.empty()) return 8500 + (i.sqHasScale ? 1 : 0) + (i.sqHasConst ? 2 : 0);                // 8500+: scaled square plus constant, by what it absorbed
   if (!i.lcOperands.empty()) return 8600 + (int)i.lcOperands.size();                                   // 8600+: sum of scaled polynomials, by terms
+  if (!i.maOperands.empty()) return 8700 + 4 * (int)i.maAddScales.size() + (i.maHasScale ? 1 : 0) + (i.maHasConst ? 2 : 0);   // 8700+: scaled product plus addends, by addends and what it absorbed
   if (i.fusedTensor) return 200;                                                                           // 200: tensor product
   if (i.fusedSubScale && i.fMinuendB) return i.fMix ? 211 : 209;                                           // 209 / 211: ... with a product minuend (4p)
   if (i.fusedSubScale) return (i.fMix ? 203 : 201) + (i.fConvIn.empty() ? 0 : 4);                          // 201 / 203: fused forward transform, plain / merged; 205 / 207: with its conversion
@@ -491,6 +499,7 @@ struct Arch::LaunchBuilder {
   void tensorDot(Launch &L, Recs recs);
   void tensorSquare(Launch &L, Recs recs);
   void lincomb(Launch &L, Recs recs);
+  void tensorMulAdd(Launch &L, Recs recs);
   void nttSubScale(Launch &L, Recs recs);
   void copy(Launch &L, Recs recs);
   void transform(Launch &L, Recs recs);
@@ -669,6 +678,27 @@ void Arch::LaunchBuilder::lincomb(Launch &L, Recs recs) {
   L.bytes = (L.dotTerms + 1ull) * LP * recs.size();   // every input read once, the sum written once
 }
 
+// (5m) a, b, c, d = c00, c10, c01, c11 [n]; x0, x1 = c0, c1 of every addend [n][A]; out, out1, out2 = d0, d1, d2 [n]; k = the scalars [n], maK = the
+// addend scalars [n][A], addK = the constants [n] (hm_tensor_muladd).  The part key keeps records of different addend counts, and records that
+// absorbed different things, apart
+void Arch::LaunchBuilder::tensorMulAdd(Launch &L, Recs recs) {
+  L.kind = Launch::L_TENSOR_MULADD; L.statKey = "EWE";
+  L.maAddends = (uint32_t)recs[0]->maAddScales.size();
+  for (Instruction *i : recs) {
+    L.a.push_back(limb(i->maOperands[0])); L.b.push_back(limb(i->maOperands[1]));
+    L.c.push_back(limb(i->maOperands[2])); L.d.push_back(limb(i->maOperands[3]));
+    for (uint32_t t = 0; t < L.maAddends; ++t) {
+      L.x0.push_back(limb(i->maOperands[4 + 2 * t])); L.x1.push_back(limb(i->maOperands[5 + 2 * t]));
+    }
+    L.maK.insert(L.maK.end(), i->maAddScales.begin(), i->maAddScales.end());
+    L.out.push_back(limb(i->extraOutputs[0])); L.out1.push_back(limb(i->OutputOperand)); L.out2.push_back(limb(i->extraOutputs[1]));
+    L.mods.push_back(i->mod_id);
+    if (recs[0]->maHasScale) L.k.push_back(i->maScale);
+    if (recs[0]->maHasConst) L.addK.push_back(i->maConst);
+  }
+  L.bytes = (7ull + 2 * L.maAddends) * LP * recs.size();   // four operands and both components of every addend read once, three polynomials written
+}
+
 // fused forward transform (4, 4b, 9, 12)
 void Arch::LaunchBuilder::nttSubScale(Launch &L, Recs recs) {
   L.kind = Launch::L_NTT_SUBSCALE; L.statKey = "NTT";
@@ -838,6 +868,7 @@ void Arch::LaunchBuilder::emitCompute(const Group &group, Launches &front, Launc
   else if (!f->dotOperands.empty()) tensorDot(*L, recs);
   else if (!f->sqOperands.empty()) tensorSquare(*L, recs);
   else if (!f->lcOperands.empty()) lincomb(*L, recs);
+  else if (!f->maOperands.empty()) tensorMulAdd(*L, recs);
   else if (f->fusedTensor) tensor(*L, recs);
   else if (f->fusedSubScale) nttSubScale(*L, recs);
   else if (f->ops == NTT && f->passthrough) copy(*L, recs);
@@ -1036,7 +1067,9 @@ void Arch::buildLaunches() {
   // (only the plan that holds a square's tensor record which pass (5q) did not take: fuse_square = 0.  Every other plan keeps the plain
   // level-by-level order it is pinned to, launch by launch: tests/golden/plan_fingerprints.json)
   const bool plainSquare = std::any_of(parts.begin(), parts.end(), [](const Part &p) { return p.ins[0]->squareHead && p.ins[0]->fusedTensor && p.ins[0]->sqOperands.empty(); });
-  if (fuse && world_ == 1 && plainSquare) joinEarlierGroups(parts);
+  // (... and the plan that holds a marked product's tensor record which pass (5m) did not take: fuse_muladd = 0)
+  const bool plainMuladd = std::any_of(parts.begin(), parts.end(), [](const Part &p) { return p.ins[0]->muladdHead && p.ins[0]->fusedTensor && p.ins[0]->maOperands.empty(); });
+  if (fuse && world_ == 1 && (plainSquare || plainMuladd)) joinEarlierGroups(parts);
   LaunchBuilder b(*this);
   // multi-GPU: who holds each limb-poly.  Inputs: by the modulus they were filled for; everything else: by the modulus of the
   // instruction that writes it.
@@ -1164,7 +1197,8 @@ void Arch::replicateForBatch() {
       rep(l->a, true); rep(l->b, true); rep(l->c, true); rep(l->d, true);
       rep(l->out, true); rep(l->out1, true); rep(l->out2, true); rep(l->mods, false);
       rep(l->inGalois, false); rep(l->addGalois, false); rep(l->mulB, true); rep(l->liftMods, false);
-      for (std::vector<uint64_t> *kv : {&l->k, &l->mixK, &l->addK}) {
+      rep(l->x0, true); rep(l->x1, true);
+      for (std::vector<uint64_t> *kv : {&l->k, &l->mixK, &l->addK, &l->maK}) {
         const size_t k0 = kv->size();
         for (uint32_t c = 1; c < batch_; ++c)
           for (size_t i = 0; i < k0; ++i) kv->push_back((*kv)[i]);
@@ -1250,7 +1284,7 @@ void Arch::prepare() {
 
 static const char *const kLaunchKindNames[] = {"NTT", "INTT", "EWE", "BCONV", "AUTO", "NTT_SUBSCALE", "TENSOR", "EXCH_IN", "EXCH_OUT", "REPLICATE", "IP", "NTT_IP",
                                                "BCONV_COL", "EXCH_IN_COL", "EXCH_OUT_COL", "IP_HOISTED", "IP_LINTRANS", "TENSOR_DOT", "IP_ROTSUM",
-                                               "IP_LINTRANS_MULTI", "TENSOR_SQUARE", "LINCOMB"};
+                                               "IP_LINTRANS_MULTI", "TENSOR_SQUARE", "LINCOMB", "TENSOR_MULADD"};
 
 // Per-launch device time (SURVEY.md §8d "per-stage hipEvent times", exchange time at N > 1): every launch of the plan
 // bracketed by its own event pair, in plan order so that the data dependencies (and, sharded, the collectives) line up.
@@ -1306,6 +1340,8 @@ std::string Arch::planText() const {
       out += std::string(" scale=") + (l->k.empty() ? "0" : "1") + " const=" + (l->addK.empty() ? "0" : "1");
     if (l->kind == Launch::L_LINCOMB)   // (5l): terms summed per record, and whether a constant follows
       out += " terms=" + std::to_string(l->dotTerms) + " const=" + (l->addK.empty() ? "0" : "1");
+    if (l->kind == Launch::L_TENSOR_MULADD)   // (5m): addends per record, and what the records absorbed
+      out += " addends=" + std::to_string(l->maAddends) + " scale=" + (l->k.empty() ? "0" : "1") + " const=" + (l->addK.empty() ? "0" : "1");
     if (l->kind == Launch::L_IP_LINTRANS)   // (6l): entries that also form the addend output
       out += " addend=" + std::to_string(l->d.size() - (size_t)std::count(l->d.begin(), l->d.end(), HM_NO_LIMB));
     if (l->kind == Launch::L_IP_LINTRANS_MULTI)   // (6m): groups, entries that also form the groups' addend outputs
@@ -1344,12 +1380,14 @@ std::string Arch::planDump() const {
            " ipTerms=" + std::to_string(l->ipTerms) + " ipOuts=" + std::to_string(l->ipOuts) + " ref=" + std::to_string(l->refInstructions) + " bytes=" + std::to_string(l->bytes) +
            " mark=" + std::to_string(l->recordSlot) + " xin=" + indexOf(l->xin) + " xout=" + indexOf(l->xout);
     if (l->dotTerms) out += " terms=" + std::to_string(l->dotTerms);
+    if (l->kind == Launch::L_TENSOR_MULADD) out += " addends=" + std::to_string(l->maAddends);
     if (l->kind == Launch::L_IP_LINTRANS_MULTI) out += " multiOuts=" + std::to_string(l->multiOuts);   // (one sum: the line of L_IP_LINTRANS has no such field)
     vec("wait", l->waitSlots); vec("hoistG", l->hoistG); vec("ipCoeff", l->ipCoeff); vec("ipInv", l->ipInv); vec("outPacked", l->outPacked);
     vec("inGalois", l->inGalois); vec("addGalois", l->addGalois); vec("mulB", l->mulB); vec("liftMods", l->liftMods);
     vec("idPt", l->idPt); vec("d1", l->d1);
     vec("a", l->a); vec("b", l->b); vec("c", l->c); vec("d", l->d); vec("out", l->out); vec("out1", l->out1); vec("out2", l->out2);
     vec("mods", l->mods); vec("inMods", l->inMods); vec("k", l->k); vec("mixK", l->mixK); vec("addK", l->addK);
+    vec("x0", l->x0); vec("x1", l->x1); vec("maK", l->maK);
     vec("exLimbs", l->exLimbs); vec("exOwners", l->exOwners);
     for (const Launch::Prob &q : l->probs) {
       out += " prob{epi=" + std::to_string(q.epi) + " epAdd=" + std::to_string(q.epAdd) + " inPacked=" + std::to_string(q.inPacked);
@@ -1488,6 +1526,12 @@ void Arch::enqueue(Launch &l) {
     break;
   case Launch::L_LINCOMB:
     st = hm_lincomb(ctx, pool, l.a.data(), pool, l.out.data(), l.mods.data(), cnt, l.dotTerms, l.k.data(), l.addK.empty() ? nullptr : l.addK.data());
+    break;
+  case Launch::L_TENSOR_MULADD:
+    st = hm_tensor_muladd(ctx, pool, l.a.data(), pool, l.b.data(), pool, l.c.data(), pool, l.d.data(), l.maAddends ? pool : nullptr,
+                          l.maAddends ? l.x0.data() : nullptr, l.maAddends ? l.x1.data() : nullptr, pool, l.out.data(), pool, l.out1.data(), pool,
+                          l.out2.data(), l.mods.data(), cnt, l.maAddends, l.k.empty() ? nullptr : l.k.data(), l.maAddends ? l.maK.data() : nullptr,
+                          l.addK.empty() ? nullptr : l.addK.data());
     break;
   case Launch::L_EXCH_IN:
     st = hm_limbs_to_slices(ctx, pool, l.exLimbs.data(), l.exOwners.data(), (uint32_t)l.exLimbs.size(), l.slicesIn);

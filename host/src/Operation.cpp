@@ -3,6 +3,7 @@
 // SURVEY.md Appendix A (upstream only needs shapes, and mislabels several operands: Appendix C).
 #include "Operation.h"
 #include "SimProgram.h"
+#include "../../include/homulator_hip.h"   // HM_TENSOR_MULADD_MAX_ADDENDS
 
 #include <algorithm>
 #include <cctype>
@@ -968,6 +969,87 @@ HLINCOMB::HLINCOMB(std::string labelName, uint32_t maxLevel, uint32_t currentLev
   finishConstruction();
 }
 
+// hmuladd (build extension).  out = Rescale(d0 + ks0(d2)), Rescale(d1 + ks1(d2)) with
+//   d0 = s a b + sum_t u_t x_t + k,  d1 = s (a d + c b) + sum_t u_t y_t,  d2 = s c d
+// (a, c = ct1.c0, ct1.c1; b, d = ct2.c0, ct2.c1; x_t, y_t = ct<2+t>.c0, .c1): one node of a polynomial evaluation, T_{a+b} = 2 T_a T_b - T_{|a-b|} or
+// p = q T_g + r.  TensorCompute on (ct1, ct2); ma_scale = 1 adds three MUL_CONST stages MulAdd_Scale_D<i> (s on d0, d1, d2); per addend t and
+// component k MulAdd_AddScale_(t)_C<k> = u_t ct<2+t>.c<k> (MUL_CONST) and MulAdd_Add_(t)_D<k> = d<k> plus that (ADD); ma_const = 1 one ADD_CONST
+// stage MulAdd_Const_D0.  Everything is linear and acts in front of the key switch, at scale Delta^2 on the level of the inputs.  Then HMULT's
+// tail, stage for stage.  Unfused, the stages run one launch each; fused, pass (5m) of Arch::fusePasses (Planner.cpp) turns everything in front
+// of the key switch into one launch.
+HMULADD::HMULADD(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch)
+    : OperationBase("HMULADD", labelName, cfg, _arch, maxLevel, currentLevel, alpha) {
+  if (arch->backend() == Arch::BACKEND_SIM) throw std::runtime_error("hmuladd: backend = sim has no such op (the reference has no scalar product)");
+  if (arch->world() > 1) throw std::runtime_error("hmuladd: world > 1 is not supported (the sharded plan is not built)");
+  if (currentLevel < 2) throw std::runtime_error("hmuladd: Rescale needs at least two limbs");
+  const uint32_t A = cfg->getValueOr("addends", 1);
+  if (A > HM_TENSOR_MULADD_MAX_ADDENDS) throw std::runtime_error("hmuladd: addends = " + S(A) + ", must be in [0, " + S(HM_TENSOR_MULADD_MAX_ADDENDS) + "]");
+  auto flag = [&](const char *key) {
+    const uint32_t v = cfg->getValueOr(key, 0);
+    if (v > 1) throw std::runtime_error(std::string("hmuladd: ") + key + " = " + S(v) + ", must be 0 or 1");
+    return v == 1;
+  };
+  const bool scaled = flag("ma_scale"), shifted = flag("ma_const");
+  makeInputs(2 + A);
+
+  TensorCompute tcm(labelName, currentLevel, &cts[0], &cts[1], &Datapool, &DataInsMap, &insgener, addrManager.get(), "Ma");
+  for (const INSGROUP &g : tcm.getInsMap().at("TensorCompute_INS_D1")) g[0]->muladdHead = true;
+  dispatch(tcm.getInsMap());
+  std::array<Limbs, 3> d;
+  for (uint32_t i = 0; i < 3; ++i) d[i] = {tcm.d(i), tcm.getInsMap().at("TensorCompute_INS_D" + S(i))};
+  // the records of limb j of a constant stage, kept by name for setConstants
+  auto keep = [&](const std::string &name, const std::vector<INSGROUP> &recs, bool nonZero) {
+    ConstantStage &cs = constantStages[name];
+    cs.enabled = true;
+    cs.nonZero = nonZero;
+    cs.records.resize(currentLevel);
+    for (uint32_t j = 0; j < currentLevel; ++j) cs.records[j].push_back(recs[j][0]);
+  };
+  auto synth = [&](uint64_t stream, bool nonZero) {
+    std::vector<uint64_t> v;
+    for (uint32_t j = 0; j < currentLevel; ++j) {
+      const uint64_t w = synthWord0(stream + j, arch->modulus(j));
+      v.push_back(nonZero && w == 0 ? 1 : w);
+    }
+    return v;
+  };
+  // one stage on polynomial i of the running d: out = op(d[i], other) with the constants, if any
+  auto stage = [&](uint32_t i, ewe_opcode op, const std::string &key, const std::string &buffer, const Limbs *other, const std::vector<uint64_t> &constants) {
+    PerLimb s{labelName + "_" + key + "_Level(", ")", range(0, currentLevel), alloc(buffer, currentLevel)};
+    const Limbs before = d[i];
+    s.a = before.addr;
+    s.after = {&before.from};
+    if (other) { s.c = other->addr; s.after.push_back(&other->from); }
+    s.constants = constants;
+    d[i] = {s.out, eweLimbs(&insgener, op, s)};
+    driver.dispatchInstructions(key, d[i].from);
+  };
+  constantStages["scale"].key = "ma_scale";
+  constantStages["const"].key = "ma_const";
+  if (scaled)
+    for (uint32_t i = 0; i < 3; ++i) {
+      stage(i, EWE_MUL_CONST, "MulAdd_Scale_D" + S(i), "MaD" + S(i) + "Scale", nullptr, synth(seed + 6400, /*nonZero=*/true));
+      keep("scale", d[i].from, /*nonZero=*/true);
+    }
+  for (uint32_t t = 1; t <= A; ++t)
+    for (uint32_t k = 0; k < 2; k++) {
+      const std::string C = "_C" + S(k);
+      PerLimb m{labelName + "_MulAdd_AddScale_(" + S(t) + ")" + C + "_Level(", ")", range(0, currentLevel), alloc("MaAddScaled(" + S(t) + ")" + C, currentLevel)};
+      m.a = component(1 + t, k);
+      m.constants = synth(seed + 6400 + 10ull * t, /*nonZero=*/false);
+      const Limbs term{m.out, eweLimbs(&insgener, EWE_MUL_CONST, m)};
+      driver.dispatchInstructions("MulAdd_AddScale_(" + S(t) + ")" + C, term.from);
+      keep("addscale" + S(t), term.from, /*nonZero=*/false);
+      stage(k, EWE_ADD, "MulAdd_Add_(" + S(t) + ")_D" + S(k), "MaD" + S(k) + "Sum(" + S(t) + ")", &term, {});
+    }
+  if (shifted) {
+    stage(0, EWE_ADD_CONST, "MulAdd_Const_D0", "MaD0Const", nullptr, synth(seed + 6490, /*nonZero=*/false));
+    keep("const", d[0].from, /*nonZero=*/false);
+  }
+  relinearizeAndRescale({d[0].addr, d[1].addr, d[2].addr});
+  finishConstruction();
+}
+
 // hrotsum (build extension).  out = sum_i rot_{g_i}(ct<i>), g_i = g^i mod 2N, over G DIFFERENT ciphertexts with ONE ModDown: the ModDown is linear,
 // so the G key products are summed on the E = l + alpha limbs and brought down once (the ModUps cannot be shared: the ciphertexts differ).
 //   D_{i,j} = ModUp(ct<i>.c1)                          per ciphertext, on the unrotated c1 (buffers and stages of ciphertext i >= 2 suffixed _Ct<i>)
@@ -1200,6 +1282,7 @@ static OperationBase *makeOp(const std::string &o, uint32_t maxLevel, uint32_t l
   if (o == "hmodraise") return new HMODRAISE("test_hmodraise", maxLevel, level, alpha, cfg, arch);
   if (o == "hsquare") return new HSQUARE("test_hsquare", maxLevel, level, alpha, cfg, arch);
   if (o == "hlincomb") return new HLINCOMB("test_hlincomb", maxLevel, level, alpha, cfg, arch);
+  if (o == "hmuladd") return new HMULADD("test_hmuladd", maxLevel, level, alpha, cfg, arch);
   throw std::runtime_error("Error operation requirement, please double confirm!");
 }
 

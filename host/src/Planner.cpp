@@ -107,6 +107,7 @@ struct Arch::Planner {
   void tensorDot();        // 5d
   void tensorSquare();     // 5q
   void linearCombination();   // 5l
+  void tensorMulAdd();     // 5m
   void keyProduct();       // 6
   // what (6m/6l), (6s) and (6h) all recognise: the live two-key key-product records whose digits are all automorphisms, by one element per record, of
   // the same materialised digits and are read by nothing else; per (modulus, unrotated digits) the records and their automorphisms, in stage order
@@ -149,6 +150,7 @@ void Arch::fusePasses(std::vector<Stage> &st) {
   if (fuseDot) p.tensorDot();   // before (6): the multiply-accumulate chains it absorbs are not key products
   if (fuseSquare) p.tensorSquare();
   if (fuseLincomb) p.linearCombination();
+  if (fuseMuladd) p.tensorMulAdd();
   p.keyProduct();
   // (6m, 6l) before (6s) and (6h): the records it merges are the ones (6h) would claim, and none of them is (6s)'s (their outputs go into products,
   // not into sums).  fuse_bsgs: the groups with several sums, fuse_lintrans: the ones with one
@@ -546,6 +548,72 @@ void Arch::Planner::linearCombination() {
     c->OutputOperand = sum;
     producer[sum] = c;
     place.moveTo(c, last);   // to where its last link stood
+  }
+}
+
+// (5m) scaled tensor product plus scaled addends plus constant (hmuladd): a tensor record of (5) that the builder marked (muladdHead) becomes a
+//      record of hm_tensor_muladd.  Behind it, the MUL_CONST records that are the only readers of its three outputs go in when all three carry the
+//      same constant (s d0, s d1, s d2).  Then, addend after addend, d0 and d1 each go on through ONE ADD whose other operand is a MUL_CONST record
+//      of the same modulus read by nothing else, both with the same constant u_t (u_t x_t onto d0, u_t y_t onto d1): an addend goes in with both
+//      its components or not at all, so d0 and d1 absorb the same number of ADDs.  Then the ADD_CONST record that is the only reader of d0.  The
+//      record's reads become the four product operands plus the 2A addend operands, its outputs the final buffers, so every later pass sees what
+//      it sees in hmult; it takes the place of the last record it absorbs.  Never written: the products in front of the scalar, the 2A scaled
+//      addends and the partial sums.  Only the builder of HMULADD sets the mark: the pass matches nothing in any other op.
+//      Reads: fusedTensor / extraOutputs (5).  Sets on the tensor record: maOperands, maAddScales, maHasScale, maScale, maHasConst, maConst,
+//      OutputOperand, extraOutputs.
+void Arch::Planner::tensorMulAdd() {
+  Readers rd = readers();
+  Placement place(st);
+  std::vector<Instruction *> heads;
+  for (auto &s : st)
+    for (Instruction *i : s.ins)
+      if (live(i) && i->fusedTensor && i->muladdHead && i->dotOperands.empty() && i->sqOperands.empty() && i->maOperands.empty()) heads.push_back(i);
+  for (Instruction *c : heads) {
+    // MAC2 operands (P, S, R, T) = (c00, c11, c01, c10); maOperands = (a, b, c, d) = (c00, c10, c01, c11)
+    c->maOperands = {c->operandList[0], c->operandList[3], c->operandList[2], c->operandList[1]};
+    AddrType d0 = c->extraOutputs[0], d1 = c->OutputOperand, d2 = c->extraOutputs[1];
+    Instruction *last = c;
+    auto take = [&](Instruction *i) {
+      absorb(c, i);
+      if (place.after(i, last)) last = i;
+    };
+    Instruction *m0 = soleReader(rd, d0, EWE_MUL_CONST, c->mod_id), *m1 = soleReader(rd, d1, EWE_MUL_CONST, c->mod_id), *m2 = soleReader(rd, d2, EWE_MUL_CONST, c->mod_id);
+    if (m0 && m1 && m2 && m0->hasConstant && m1->hasConstant && m2->hasConstant && m0->constant == m1->constant && m0->constant == m2->constant) {
+      c->maHasScale = true;
+      c->maScale = m0->constant;
+      for (Instruction *i : {m0, m1, m2}) take(i);
+      d0 = m0->OutputOperand; d1 = m1->OutputOperand; d2 = m2->OutputOperand;
+    }
+    // the ADD behind `sum` and the MUL_CONST that feeds it, if that is all that reads them
+    auto link = [&](AddrType sum, Instruction *&add, Instruction *&mul) {
+      add = soleReader(rd, sum, EWE_ADD, c->mod_id);
+      if (!add) return false;
+      const AddrType other = add->operandList[0] == sum ? add->operandList[2] : add->operandList[0];
+      if ((add->operandList[0] != sum && add->operandList[2] != sum) || other == sum) return false;
+      mul = producerOf(other);
+      return mul && live(mul) && mul->ops == MULT && mul->opcode == EWE_MUL_CONST && mul->hasConstant && mul->mod_id == c->mod_id && onlyReader(rd, other, add);
+    };
+    while (c->maAddScales.size() < HM_TENSOR_MULADD_MAX_ADDENDS) {
+      Instruction *a0 = nullptr, *u0 = nullptr, *a1 = nullptr, *u1 = nullptr;
+      if (!link(d0, a0, u0) || !link(d1, a1, u1) || u0->constant != u1->constant) break;
+      c->maOperands.push_back(u0->operandList[0]);
+      c->maOperands.push_back(u1->operandList[0]);
+      c->maAddScales.push_back(u0->constant);
+      for (Instruction *i : {u0, a0, u1, a1}) take(i);
+      d0 = a0->OutputOperand; d1 = a1->OutputOperand;
+    }
+    if (Instruction *add = soleReader(rd, d0, EWE_ADD_CONST, c->mod_id)) {
+      if (add->hasConstant) {
+        c->maHasConst = true;
+        c->maConst = add->constant;
+        take(add);
+        d0 = add->OutputOperand;
+      }
+    }
+    c->OutputOperand = d1;
+    c->extraOutputs = {d0, d2};
+    for (const Write &w : recordWrites(*c)) producer[w.addr] = c;
+    place.moveTo(c, last);
   }
 }
 

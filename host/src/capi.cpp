@@ -60,6 +60,7 @@ int hh_op_create(hh_op **out, const char *cfg_path, const char *op_name, uint32_
     else if (o == "hmodraise") h->op = new HMODRAISE("test_hmodraise", maxLevel, curLevel, alpha, h->cfg, h->arch);
     else if (o == "hsquare") h->op = new HSQUARE("test_hsquare", maxLevel, curLevel, alpha, h->cfg, h->arch);
     else if (o == "hlincomb") h->op = new HLINCOMB("test_hlincomb", maxLevel, curLevel, alpha, h->cfg, h->arch);
+    else if (o == "hmuladd") h->op = new HMULADD("test_hmuladd", maxLevel, curLevel, alpha, h->cfg, h->arch);
     else if (o == "hadd") h->op = new HADD("test_hadd", maxLevel, curLevel, alpha, h->cfg, h->arch);
     else if (o == "pmult") h->op = new PMULT("test_pmult", maxLevel, curLevel, alpha, h->cfg, h->arch);
     else if (o == "padd") h->op = new PADD("test_ADD", maxLevel, curLevel, alpha, h->cfg, h->arch);

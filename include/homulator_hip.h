@@ -203,6 +203,28 @@ hm_status hm_tensor_square(hm_ctx *ctx, const uint64_t *a, const uint32_t *a_lim
 hm_status hm_lincomb(hm_ctx *ctx, const uint64_t *in, const uint32_t *in_limbs, uint64_t *out, const uint32_t *out_limbs,
                      const uint32_t *mod_ids, uint32_t n, uint32_t n_terms, const uint64_t *scale, const uint64_t *addend);
 
+/* K3, scaled tensor product of two ciphertexts plus a linear combination of n_addends further ciphertexts plus a constant, in one pass over the
+ * 4 + 2 n_addends input polynomials (HMULADD): for entry i, with the roles of hm_tensor (a = c00, b = c10, c = c01,
+ * d = c11), x_t / y_t = c0 / c1 of addend t, s = scale[i] in [1, q), u_t = add_scale[i * n_addends + t] in [0, q) and k = addend[i] in [0, q),
+ * per coefficient
+ *   o0[i] = s * a * b + sum_t u_t * x_t + k,   o1[i] = s * (a * d + c * b) + sum_t u_t * y_t,   o2[i] = s * c * d,   t < n_addends <= 8,
+ * the canonical residue of the exact sum: bit-identical to hm_tensor followed by HM_OP_MUL_CONST on the three outputs, HM_OP_MUL_CONST +
+ * HM_OP_ADD per addend and component, and HM_OP_ADD_CONST on o0, none of whose intermediates is written.  Both components of the addends live
+ * in ONE buffer x: x0_limbs[i * n_addends + t] is the limb-poly of x_t, x1_limbs[i * n_addends + t] that of y_t.  A zero u_t is a term that
+ * contributes nothing; n_addends = 0 with scale == NULL and addend == NULL is hm_tensor.  scale == NULL: every s is 1; addend == NULL: every
+ * k is 0; scale, add_scale and addend are host arrays.  The records live in a device table: one launch serves any n, and the call is safe
+ * under graph capture once it has run with the same lists and constants.  HM_ERR_ARG: a null buffer, a null mod_ids, a null x, x0_limbs,
+ * x1_limbs or add_scale with n_addends > 0 (all four may be null at 0), n_addends above 8, a limb or modulus id out of range, an unreduced
+ * scale, add_scale or addend, a zero scale, an output limb-poly that overlaps (by address range, not by base pointer) an input limb-poly or
+ * another output limb-poly.  n = 0 is HM_OK. */
+#define HM_TENSOR_MULADD_MAX_ADDENDS 8
+hm_status hm_tensor_muladd(hm_ctx *ctx, const uint64_t *a, const uint32_t *a_limbs, const uint64_t *b, const uint32_t *b_limbs,
+                           const uint64_t *c, const uint32_t *c_limbs, const uint64_t *d, const uint32_t *d_limbs,
+                           const uint64_t *x, const uint32_t *x0_limbs, const uint32_t *x1_limbs,
+                           uint64_t *o0, const uint32_t *o0_limbs, uint64_t *o1, const uint32_t *o1_limbs, uint64_t *o2,
+                           const uint32_t *o2_limbs, const uint32_t *mod_ids, uint32_t n, uint32_t n_addends,
+                           const uint64_t *scale, const uint64_t *add_scale, const uint64_t *addend);
+
 /* K5 — inner product with the evaluation key in one pass: for limb i, out[i][k] = sum_{j < n_terms}
  * x[i][j] * y[i][k][j], k < n_out (n_terms <= 4 digits, n_out <= 2 keys).  Limb lists are row-major:
  * x_limbs[i * n_terms + j], y_limbs[(i * n_out + k) * n_terms + j], out_limbs[i * n_out + k].  Replaces
