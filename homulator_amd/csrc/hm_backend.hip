@@ -516,6 +516,13 @@ __global__ void __launch_bounds__(256) k_tensor_muladd(HmTensorMulAddArgs a) {
   if (entry < a.n_limbs) hm_tensor_muladd_thread(a, entry, blockIdx.x & ((1u << logPer) - 1u), threadIdx.x);
 }
 
+// real and imaginary parts of the slots from a polynomial and its conjugate (hm_elem_core.h: hm_reim_thread): k_lincomb's geometry, the records in a
+// device table
+__global__ void __launch_bounds__(256) k_reim_split(HmReimArgs a) {
+  const uint32_t logPer = a.logN - 9, entry = blockIdx.x >> logPer;
+  if (entry < a.n_limbs) hm_reim_thread(a, entry, blockIdx.x & ((1u << logPer) - 1u), threadIdx.x);
+}
+
 // 16-byte units per thread of the element-wise kernel, 512 coefficients apart, all loads in flight before the first use.  1: 89 600 workgroups for a batch of
 // ten hadd; 2 / 4 measured padd +3 / +5 %, pmult +1 %, hadd within the noise (tools/r06_ewe_ab.sh): not worth a second shape of the kernel's launch
 #ifndef HM_EWE_UNITS
@@ -1950,6 +1957,64 @@ extern "C" hm_status hm_tensor_muladd(hm_ctx *c, const uint64_t *pa, const uint3
   a.a = pa; a.b = pb; a.c = pc; a.d = pd; a.x = A ? px : pa; a.o0 = o0; a.o1 = o1; a.o2 = o2;
   a.mods = c->d_mods; a.logN = c->P.logN; a.n_limbs = n; a.n_addends = A;
   hipLaunchKernelGGL(k_tensor_muladd, dim3(n * (N / 512)), dim3(256), 0, c->stream, a);
+  HM_HIP(c, hipGetLastError());
+  return HM_OK;
+}
+
+// o_re = x + y, o_im = U (.) (x - y) with U the evaluation form of -X^(N/2), derived here from the context's own roots: one record per entry in a
+// device table, ONE launch for any n
+extern "C" hm_status hm_reim_split(hm_ctx *c, const uint64_t *px, const uint32_t *lx, const uint64_t *py, const uint32_t *ly, uint64_t *o_re,
+                                   const uint32_t *lre, uint64_t *o_im, const uint32_t *lim, const uint32_t *mod_ids, uint32_t n) {
+  static const char *const what = "hm_reim_split";
+  if (!c) return HM_ERR_ARG;
+  HM_TABLE_CALL(c);
+  if (!px || !py || !o_re || !o_im) return fail(c, HM_ERR_ARG, "%s: null buffer", what);
+  const uint32_t N = c->P.N;
+  if ((uint64_t)n > 0xFFFFFFFFull / (HM_REIM_REC_WORDS * sizeof(uint32_t))) return fail(c, HM_ERR_ARG, "%s: n = %u entries are too many for one call", what, n);
+  struct List { const char *name; const void *base; const uint32_t *limbs; uint32_t count; };
+  const List ins[2] = {{"x", px, lx, n}, {"y", py, ly, n}};
+  const List outs[2] = {{"o_re", o_re, lre, n}, {"o_im", o_im, lim, n}};
+  hm_status st;
+  for (const List &l : ins)
+    if ((st = check_limbs(c, what, l.limbs, l.count))) return st;
+  for (const List &l : outs)
+    if ((st = check_limbs(c, what, l.limbs, l.count))) return st;
+  if ((st = check_mods(c, what, mod_ids, n))) return st;
+  // a workgroup stores its two outputs after both loads, and one input limb-poly may serve several records: no output may share an address with
+  // an input or with another output (hm_tensor_dot's rule and messages)
+  for (const List &o : outs)
+    for (const List &i : ins)
+      if (hm_limbs_overlap(o.base, o.limbs, o.count, i.base, i.limbs, i.count, N))
+        return fail(c, HM_ERR_ARG, "%s: an output limb-poly (%s) overlaps an input limb-poly (%s)", what, o.name, i.name);
+  {
+    std::vector<uintptr_t> starts;
+    for (const List &o : outs)
+      for (uint32_t i = 0; i < o.count; ++i) starts.push_back(reinterpret_cast<uintptr_t>(o.base) + (uintptr_t)limb_at(o.limbs, i) * N * 8);
+    std::sort(starts.begin(), starts.end());
+    for (size_t i = 1; i < starts.size(); ++i)
+      if (starts[i] - starts[i - 1] < (uintptr_t)N * 8) return fail(c, HM_ERR_ARG, "%s: two output limb-polys overlap", what);
+  }
+  if (n == 0) return HM_OK;
+  // w = -psi^(N/2) mod q per entry, from the root table the transforms are built from (N >= 1024: a workgroup's 512 coefficients lie in one half)
+  std::vector<uint64_t> qs(n), ws(n);
+  std::map<uint32_t, uint64_t> wOf;
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t m = mod_ids[i];
+    qs[i] = c->P.mod[m];
+    auto f = wOf.find(m);
+    if (f == wOf.end()) f = wOf.emplace(m, qs[i] - hm::powmod(c->P.psi[m], N / 2, qs[i])).first;
+    ws[i] = f->second;
+  }
+  std::vector<uint32_t> recs((size_t)n * HM_REIM_REC_WORDS);
+  hm_reim_fill_recs(recs.data(), lx, ly, lre, lim, mod_ids, ws.data(), qs.data(), n);
+  HM_HIP(c, hipSetDevice(c->device));
+  HmReimArgs a;
+  const void *tab = nullptr;
+  if ((st = device_table(c, recs.data(), recs.size() * sizeof(uint32_t), &tab))) return st;
+  a.rec = static_cast<const uint32_t *>(tab);
+  a.x = px; a.y = py; a.o_re = o_re; a.o_im = o_im;
+  a.mods = c->d_mods; a.logN = c->P.logN; a.n_limbs = n;
+  hipLaunchKernelGGL(k_reim_split, dim3(n * (N / 512)), dim3(256), 0, c->stream, a);
   HM_HIP(c, hipGetLastError());
   return HM_OK;
 }

@@ -631,6 +631,57 @@ HM_HD void hm_tensor_muladd_thread(const HmTensorMulAddArgs &g, uint32_t entry, 
   hm_bst2(g.o2 + rec[7] * N, lane_bytes, hm_barrett_wide(s[0].d2, m), hm_barrett_wide(s[1].d2, m));
 }
 
+// Real and imaginary parts of the slots from a polynomial x and its conjugate y in one pass over both (hm_reim_split; HREIM):
+//   re = x + y,   im = U (.) (x - y)
+// with U the evaluation form of -X^(N/2).  Entry e of a limb-poly holds the value at psi^(2 brev(e) + 1); for e < N/2 the exponent is 1 mod 4, for
+// e >= N/2 it is 3 mod 4, and psi^(N/2) has order 4: U is the constant w = -psi^(N/2) mod q on entries [0, N/2) and q - w on [N/2, N), w^2 = -1.
+// A workgroup's 512 coefficients lie in one half (N >= 1024), so the choice is uniform per workgroup: chunk < N/1024 takes w.
+// One form on both arithmetic back-ends, every input canonical (< q < 2^60):
+//   re = hm_addmod(x, y): x + y < 2q < 2^61, one conditional subtraction, canonical;
+//   d  = hm_submod(x, y): in [0, q), canonical;
+//   im = hm_shoup(d, u, us, q): exact for any 64-bit d and u < q with us = floor(u 2^64 / q), canonical (hm_modarith.h).
+// The record carries w and ws = floor(w 2^64 / q) only.  For u = q - w: (q - w) 2^64 / q = 2^64 - w 2^64 / q, and w 2^64 / q is no integer (q is
+// an odd prime, 0 < w < q), so floor((q - w) 2^64 / q) = 2^64 - 1 - ws = ~ws, exactly.
+// Bit-identical to HM_OP_ADD, HM_OP_SUB and HM_OP_MUL by the stored U: each of those yields the canonical residue of the same exact value.
+// a record = HM_REIM_REC_WORDS 32-bit words (48 bytes, a multiple of 16), the 64-bit values at 8-byte offsets:
+//   0: modulus id   1, 2: the limbs of x, y   3, 4: the limbs of re, im   5..7: 0   8, 9: w   10, 11: ws
+#define HM_REIM_REC_WORDS 12u
+struct HmReimArgs {
+  const uint64_t *x, *y;
+  uint64_t *o_re, *o_im;
+  const HmMod *mods;
+  const uint32_t *rec;   // device, [n_limbs][HM_REIM_REC_WORDS]: read through the scalar cache (wave-uniform index)
+  uint32_t logN, n_limbs;
+};
+// The records of n entries from the entry point's limb lists (a null list is the identity); w[i] = -psi^(N/2) mod q[i], q[i] = the modulus of
+// entry i.  Host side.
+inline void hm_reim_fill_recs(uint32_t *rec, const uint32_t *lx, const uint32_t *ly, const uint32_t *lre, const uint32_t *lim, const uint32_t *mod_ids,
+                              const uint64_t *w, const uint64_t *q, uint32_t n) {
+  auto at = [](const uint32_t *l, uint32_t i) { return l ? l[i] : i; };
+  auto put64 = [](uint32_t *r, uint64_t v) { r[0] = (uint32_t)v; r[1] = (uint32_t)(v >> 32); };
+  for (uint32_t i = 0; i < n; ++i) {
+    uint32_t *r = rec + (size_t)i * HM_REIM_REC_WORDS;
+    r[0] = mod_ids[i]; r[1] = at(lx, i); r[2] = at(ly, i); r[3] = at(lre, i); r[4] = at(lim, i); r[5] = r[6] = r[7] = 0;
+    put64(r + 8, w[i]); put64(r + 10, hm_shoup_companion(w[i], q[i]));
+  }
+}
+// thread tid of the workgroup that owns chunk `chunk` (512 coefficients) of record `entry`: the pair at chunk * 512 + 2 tid, two 16-byte loads and
+// two 16-byte stores.  chunk < N / 512 (the launch has n N / 512 workgroups), so the last byte touched is N * 8 - 1 of each limb-poly.
+HM_HD void hm_reim_thread(const HmReimArgs &g, uint32_t entry, uint32_t chunk, uint32_t tid) {
+  const size_t N = (size_t)1 << g.logN;
+  const uint32_t lane_bytes = (chunk * 512u + 2u * tid) << 3;
+  const auto rec = HM_CONST_PROB_T(uint32_t, g.rec) + (size_t)entry * HM_REIM_REC_WORDS;
+  const uint64_t q = HM_CONST_MODS(g.mods)[rec[0]].q;
+  const uint64_t w = hm_muladd_rec64(rec, 8), ws = hm_muladd_rec64(rec, 10);
+  const bool first = chunk < (uint32_t)(N >> 10);   // (workgroup-uniform) entries [0, N/2)
+  const uint64_t u = first ? w : q - w, us = first ? ws : ~ws;
+  uint64_t x[2], y[2];
+  hm_bld2(g.x + rec[1] * N, lane_bytes, x[0], x[1]);
+  hm_bld2(g.y + rec[2] * N, lane_bytes, y[0], y[1]);
+  hm_bst2(g.o_re + rec[3] * N, lane_bytes, hm_addmod(x[0], y[0], q), hm_addmod(x[1], y[1], q));
+  hm_bst2(g.o_im + rec[4] * N, lane_bytes, hm_shoup(hm_submod(x[0], y[0], q), u, us, q), hm_shoup(hm_submod(x[1], y[1], q), u, us, q));
+}
+
 // The conversion table is read through the SCALAR cache: every lane of a wave needs the same entries, so they are
 // s_load'ed into SGPRs (asynchronously, no VGPRs, no LDS, no barrier) and feed v_mad_u64_u32 as scalar operands.
 // hipcc only emits scalar loads for memory it knows to be constant, hence the constant-address-space view of the

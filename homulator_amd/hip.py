@@ -25,7 +25,7 @@ SYMBOLS = [
     "hm_bconv_col", "hm_limbs_to_colslices", "hm_colslices_to_limbs", "hm_ntt_second_pass", "hm_ntt_ex", "hm_capability", "hm_inner_product_ex",
     "hm_inner_product_hoisted", "hm_inner_product_lintrans", "hm_inner_product_rotsum", "hm_inner_product_lintrans_multi",
     "hm_tensor_dot", "hm_inner_product_lintrans_id", "hm_inner_product_rotsum_init", "hm_ntt_mix_sub_scale_mul", "hm_ntt_mul",
-    "hm_ntt_lift", "hm_tensor_square", "hm_lincomb", "hm_tensor_muladd",
+    "hm_ntt_lift", "hm_tensor_square", "hm_lincomb", "hm_tensor_muladd", "hm_reim_split",
 ]
 
 
@@ -162,6 +162,7 @@ def load():
     L.hm_tensor_square.argtypes = [vp] + [vp] * 11 + [u32, vp, vp]
     L.hm_lincomb.argtypes = [vp] + [vp] * 5 + [u32, u32, vp, vp]
     L.hm_tensor_muladd.argtypes = [vp] + [vp] * 18 + [u32, u32, vp, vp, vp]
+    L.hm_reim_split.argtypes = [vp] + [vp] * 9 + [u32]
     L.hm_inner_product.argtypes = [vp] + [vp] * 7 + [u32, u32, u32]
     L.hm_automorph.argtypes = [vp, vp, vp, vp, vp, u32, u32]
     L.hm_ewe.argtypes = [vp, i32] + [vp] * 11 + [u32, vp]
@@ -424,6 +425,15 @@ class Context:
         self._ck(self.L.hm_tensor_muladd(self.h, a.ptr, keep[0][1], b.ptr, keep[1][1], c.ptr, keep[2][1], d.ptr, keep[3][1],
                                          x.ptr if x is not None else None, keep[7][1], keep[8][1], o0.ptr, keep[4][1], o1.ptr, keep[5][1],
                                          o2.ptr, keep[6][1], keep[9][1], len(mod_ids), int(n_addends), ks[1], ku[1], ka[1]))
+
+    def reim_split(self, x, y, o_re, o_im, mod_ids, limbs=None):
+        """o_re = x + y, o_im = U * (x - y) per entry, U the evaluation form of -X^(N/2) under the entry's modulus, derived by the back-end from
+        its own roots (hm_reim_split).  limbs: the four limb lists of x, y, o_re, o_im (None: the identity), [n] each; buffers: anything with
+        a device address `.ptr`"""
+        ls = limbs or [None] * 4
+        keep = [_u32(v) for v in ls] + [_u32(mod_ids)]
+        self._ck(self.L.hm_reim_split(self.h, x.ptr, keep[0][1], y.ptr, keep[1][1], o_re.ptr, keep[2][1], o_im.ptr, keep[3][1], keep[4][1],
+                                      len(mod_ids)))
 
     def inner_product(self, x, x_limbs, y, y_limbs, out, out_limbs, mod_ids, n_terms, n_out, x_galois=0):
         keep = [_u32(v) for v in (x_limbs, y_limbs, out_limbs, mod_ids)]

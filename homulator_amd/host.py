@@ -54,6 +54,7 @@ def load():
         L.hh_op_stage_times.argtypes = [vp, u32, C.c_char_p, u32]
         L.hh_op_backend_counter.argtypes = [vp, C.c_char_p, u64p]
         L.hh_op_bind_input.argtypes = [vp, C.c_char_p, vp]
+        L.hh_op_bind_input_from.argtypes = [vp, C.c_char_p, vp, C.c_char_p]
         L.hh_chain_create.argtypes = [C.POINTER(vp), C.c_char_p, C.c_char_p, u32, u32, u32, C.c_char_p, C.c_int]
         L.hh_chain_destroy.argtypes = [vp]
         L.hh_chain_size.restype = u32
@@ -122,9 +123,10 @@ class Op:
         self._ck(self.L.hh_op_snapshot_read(self.h, slot, out.ctypes.data_as(C.c_void_p)))
         return out
 
-    def bind_input(self, input_name, producer):
-        """continuous execution: this op's input ciphertext (\"ct1\" / \"ct2\") is `producer`'s output, kept in HBM"""
-        self._ck(self.L.hh_op_bind_input(self.h, input_name.encode(), producer.h))
+    def bind_input(self, input_name, producer, output="out"):
+        """continuous execution: this op's input ciphertext (\"ct1\" / \"ct2\") is `producer`'s output ciphertext `output` (\"out\"; hreim also
+        has \"out_im\"), kept in HBM"""
+        self._ck(self.L.hh_op_bind_input_from(self.h, input_name.encode(), producer.h, output.encode()))
 
     def __del__(self):
         try:

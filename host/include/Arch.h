@@ -57,6 +57,9 @@ public:
   void commInitExternal(void *fn, void *user);
   void registerLimbs(const std::vector<AddrType> &limbStarts);  // gives every limb-poly a place in HBM
   void addInputFill(const InputFill &f) { fills.push_back(f); }
+  // limb-polys that hold, under modulus mods[i], the evaluation form of -X^(N/2): w = -psi^(N/2) on entries [0, N/2), q - w on [N/2, N), from the
+  // host's roots; written into every copy of the batch when the op is prepared (HREIM's named buffer `unit`).  No input stream, no seed
+  void addUnitFill(const std::vector<AddrType> &addrs, const std::vector<uint32_t> &mods) { unitFills.push_back(InputFill{addrs, mods, 0}); }
   // continuous execution: before every run, limb-polys `dst` of this op are copied (device to device, stream-ordered after
   // the producer's work) from limb-polys `srcAddrs` of `src`; the synthetic fill of `dst` is dropped
   void bindInput(const std::vector<AddrType> &dst, Arch *src, const std::vector<AddrType> &srcAddrs);
@@ -133,6 +136,7 @@ private:
   bool fuseSquare = true;    // pass (5q): the tensor product of a ciphertext with itself reads it once and takes the scalar and the constant behind it (hsquare)
   bool fuseLincomb = true;   // pass (5l): the scaled terms of a linear combination are summed before anything is stored, the constant behind them (hlincomb)
   bool fuseMuladd = true;    // pass (5m): a tensor product takes the scalar, the scaled addends and the constant behind it (hmuladd)
+  bool fuseReim = true;      // pass (5r): the sum and the rotated difference of a polynomial and its conjugate are formed in one pass over both (hreim)
   bool fusePmulRescale = true;   // pass (4p): a product of two op inputs read by one transform is formed by that transform (pmult with rescale = 1)
   bool fusePmulAuto = true;      // ... the key is not given: the pass declines where it was measured no faster (the generic back-end's small launches)
   bool genericArith = false;     // config key chain_bits: the chain hm_create serves with the generic arithmetic back-end
@@ -151,6 +155,7 @@ private:
   std::map<AddrType, uint32_t> limbIndex;
   std::vector<Stage> stages;
   std::vector<InputFill> fills;
+  std::vector<InputFill> unitFills;   // addUnitFill
   struct Binding { std::vector<AddrType> dst; Arch *src; std::vector<AddrType> srcAddrs; std::vector<uint32_t> dstLimbs, srcLimbs, mods; };
   std::vector<Binding> bindings;
   std::vector<std::unique_ptr<Launch>> launches;

@@ -35,6 +35,7 @@ public:
   bool squareHead = false;   // a tensor product's MAC2 (d1) of a ciphertext with ITSELF (HSQUARE): pass (5q) starts its record here
   bool lincombHead = false;  // the MUL_CONST of term 1 of a sum of scaled ciphertexts (HLINCOMB): pass (5l) starts its record here
   bool muladdHead = false;   // a tensor product's MAC2 (d1) that scalars, scaled addends and a constant follow (HMULADD): pass (5m) starts its record here
+  bool reimHead = false;     // the ADD x + conj(x) of one limb and component (HREIM): pass (5r) starts its record here
   std::vector<uint32_t> inMods;  // BCONV: modulus ids of the inputs
   unsigned long long refInstructions = 0;  // upstream instructions this record stands for
   unsigned long long refExtra = 0;         // ... of records folded into a BCONV record (not scaled by its MAC-port count)
@@ -91,6 +92,10 @@ public:
   std::vector<uint64_t> maAddScales;
   bool maHasScale = false, maHasConst = false;
   uint64_t maScale = 1, maConst = 0;
+  // (5r) real and imaginary parts from a polynomial and its conjugate (hm_reim_split): the ADD record x + y that absorbed the SUB x - y of the same
+  // operands and the MUL of the difference by the evaluation form of -X^(N/2).  reimOperands = (x, y): its two reads; OutputOperand = the sum,
+  // extraOutputs = the product.  The stored factor is not read: the kernel derives it.  reimOperands empty: not such a record
+  std::vector<AddrType> reimOperands;
   // fused inner product (ops == IP): out_k = sum_j ipX[j] * ipY[k][j]; out_0 = OutputOperand, out_1 = extraOutputs[0]
   std::vector<AddrType> ipX;
   std::vector<std::vector<AddrType>> ipY;

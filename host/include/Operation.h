@@ -198,8 +198,9 @@ public:
   void setConstants(const std::string &name, const uint64_t *values, uint32_t n);
   Arch *getArch() { return arch; }
   std::vector<std::string> bufferNames() const;
-  // continuous execution: this op's input ciphertext `input` ("ct1", "ct2") is the output ciphertext of `producer`
-  void bindInput(const std::string &input, OperationBase *producer);
+  // continuous execution: this op's input ciphertext `input` ("ct1", "ct2") is the output ciphertext `output` of `producer` ("out"; HREIM has a
+  // second one, "out_im"); an output name the producer does not have is refused with the producer's op name
+  void bindInput(const std::string &input, OperationBase *producer, const std::string &output = "out");
   uint32_t outputLevel() const;  // limbs of out.c0
   const std::string &name() const { return opName; }
 };
@@ -264,6 +265,15 @@ class HMULADD : public OperationBase {
 public:
   HMULADD(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
 };
+// hreim (build extension): the real and the imaginary part of the slots of ct1 with ONE key switch: conj = hrotate_{2N-1}(ct1), exactly as HROTATE
+// computes it with hrotate's key IP_Key<k>_<j> (here the conjugation key; the config key galois is ignored), then per component
+// out.c<k> = ct1.c<k> + conj.c<k> (slots 2 Re z) and out_im.c<k> = U (.) (ct1.c<k> - conj.c<k>) (slots 2 Im z), U the evaluation form of -X^(N/2),
+// which the op keeps in its named buffer `unit` (level limbs, filled from the host's roots when the op is prepared: no input stream).  One input,
+// two output ciphertexts out and out_im at the input's level; the conjugate itself is the named output conj.
+class HREIM : public OperationBase {
+public:
+  HREIM(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
+};
 class HROTSUM : public OperationBase {
 public:
   HROTSUM(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
@@ -311,7 +321,7 @@ class OpChain {
   std::vector<Arch *> archs;
   std::vector<OperationBase *> ops;
 public:
-  // ops: comma-separated list of hmult | hrotate | hadd | pmult | padd | hlintrans | hdot | hrotsum | hbsgs | hrescale | hmodraise | hsquare | hlincomb | hmuladd, e.g. "hmult,hrotate,hadd,hmult"; hrotate_hoisted (R output
+  // ops: comma-separated list of hmult | hrotate | hadd | pmult | padd | hlintrans | hdot | hrotsum | hbsgs | hrescale | hmodraise | hsquare | hlincomb | hmuladd | hreim, e.g. "hmult,hrotate,hadd,hmult"; hrotate_hoisted (R output
   // ciphertexts) only as the last op
   OpChain(const std::string &cfgPath, const std::string &opList, uint32_t maxLevel, uint32_t curLevel, uint32_t alpha,
           const std::map<std::string, uint32_t> &overrides = {});

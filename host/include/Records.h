@@ -90,6 +90,8 @@ inline std::vector<Read> recordReads(const Instruction &i) {
     for (AddrType a : i.lcOperands) v.push_back({a, Role::Operand, kNoDigit});
   } else if (!i.maOperands.empty()) {    // (5m): the four operands of the product, then both components of every addend
     for (AddrType a : i.maOperands) v.push_back({a, Role::Operand, kNoDigit});
+  } else if (!i.reimOperands.empty()) {  // (5r): the polynomial and its conjugate, each read once
+    for (AddrType a : i.reimOperands) v.push_back({a, Role::Operand, kNoDigit});
   } else if (i.ops == MULT) {
     for (int b = 0; b < 4; ++b)
       if (eweOperandMask(i.opcode) & (1 << b)) v.push_back({i.operandList[b], Role::Operand, kNoDigit});

@@ -59,6 +59,9 @@ int hh_op_stage_times(hh_op *op, uint32_t iters, char *out, uint32_t cap); /* "<
  * copied device to device before every run of `dst`, stream-ordered after `src`; call before the first execute of `dst` and after `src` was
  * executed or prepared.  A chain builds the ops itself: op_list = "hmult,hrotate,hadd,...", levels follow the data. */
 int hh_op_bind_input(hh_op *dst, const char *input, hh_op *src);
+/* ... `src`'s output ciphertext `output` ("out"; hreim also has "out_im", the imaginary part): hh_op_bind_input is output = "out".  An output
+ * name `src` does not have is refused with its op name. */
+int hh_op_bind_input_from(hh_op *dst, const char *input, hh_op *src, const char *output);
 typedef struct hh_chain hh_chain;
 int hh_chain_create(hh_chain **out, const char *cfg_path, const char *op_list, uint32_t maxLevel, uint32_t curLevel, uint32_t alpha,
                     const char *overrides, int quiet);

@@ -31,7 +31,8 @@ struct Arch::Launch {
               L_IP_LINTRANS_MULTI,                           // (6m) several plaintext-weighted sums of the same hoisted key products
               L_TENSOR_SQUARE,                               // (5q) the scaled square of one ciphertext plus a constant
               L_LINCOMB,                                     // (5l) the sum of scaled polynomials plus a constant
-              L_TENSOR_MULADD } kind;                        // (5m) the scaled tensor product plus scaled addends plus a constant
+              L_TENSOR_MULADD,                               // (5m) the scaled tensor product plus scaled addends plus a constant
+              L_REIM } kind;                                 // (5r) the sum and the rotated difference of a polynomial and its conjugate
   std::vector<uint32_t> hoistG;   // L_IP_HOISTED: the Galois element of every rotation (a: digits [n][T], b: keys [r][n][2][T], out: [r][n][2])
                                   // L_IP_LINTRANS: the same, with c: plaintexts [r][n], d: addend source [n] / out1: addend output [n] (HM_NO_LIMB: none; both
                                   // empty: no entry has one), out: [n][2]
@@ -58,6 +59,7 @@ struct Arch::Launch {
   uint32_t dotTerms = 0;          // L_TENSOR_DOT: pairs per record (a, b, c, d: [n][dotTerms], roles as L_TENSOR; out, out1, out2: [n])
                                   // L_LINCOMB: terms per record (a: [n][dotTerms], out: [n]; k: the scalars [n][dotTerms], addK: the constants [n], empty: none)
                                   // L_TENSOR_SQUARE: a = c0, c = c1, out, out1, out2 = d0, d1, d2 [n]; k: the scalars [n], addK: the constants [n] (empty: none)
+                                  // L_REIM: a = the polynomial, c = its conjugate, out = the sum, out1 = the rotated difference [n]
   uint32_t maAddends = 0;         // L_TENSOR_MULADD: addends per record (a, b, c, d, out, out1, out2 as L_TENSOR; x0, x1: c0, c1 of the addends [n][maAddends];
   std::vector<uint32_t> x0, x1;   // k: the scalars [n], maK: the addend scalars [n][maAddends], addK: the constants [n]; k / addK empty: none)
   std::vector<uint64_t> maK;
@@ -164,6 +166,9 @@ Arch::Arch(Config *cfg) : config(cfg) {
   // (5m) hmuladd: the tensor product, the scalar on its three outputs, the MUL_CONST + ADD pairs of the addends on d0 and d1 and the constant on d0
   // become one hm_tensor_muladd launch.  Config key fuse_muladd (default 1).
   fuseMuladd = cfg->getValueOr("fuse_muladd", 1) != 0;
+  // (5r) hreim: the ADD, the SUB and the MUL by the evaluation form of -X^(N/2) behind the conjugation become one hm_reim_split launch.  Config key
+  // fuse_reim (default 1).
+  fuseReim = cfg->getValueOr("fuse_reim", 1) != 0;
   // (4p) pmult with rescale = 1: the products are formed by the rescale's transforms while they load.  Config key fuse_pmul_rescale: 1 / 0 = always /
   // never; not given = where it was measured faster than the three-launch plan: everywhere but the generic back-end's launches
   // inside the one-launch form's limit, which has no product form there (Planner::productOperands)
@@ -329,6 +334,7 @@ int partKey(const Instruction &i) {
   if (!i.sqOperands.empty()) return 8500 + (i.sqHasScale ? 1 : 0) + (i.sqHasConst ? 2 : 0);                // 8500+: scaled square plus constant, by what it absorbed
   if (!i.lcOperands.empty()) return 8600 + (int)i.lcOperands.size();                                   // 8600+: sum of scaled polynomials, by terms
   if (!i.maOperands.empty()) return 8700 + 4 * (int)i.maAddScales.size() + (i.maHasScale ? 1 : 0) + (i.maHasConst ? 2 : 0);   // 8700+: scaled product plus addends, by addends and what it absorbed
+  if (!i.reimOperands.empty()) return 8400;                                                                // 8400: sum and rotated difference of a polynomial and its conjugate
   if (i.fusedTensor) return 200;                                                                           // 200: tensor product
   if (i.fusedSubScale && i.fMinuendB) return i.fMix ? 211 : 209;                                           // 209 / 211: ... with a product minuend (4p)
   if (i.fusedSubScale) return (i.fMix ? 203 : 201) + (i.fConvIn.empty() ? 0 : 4);                          // 201 / 203: fused forward transform, plain / merged; 205 / 207: with its conversion
@@ -500,6 +506,7 @@ struct Arch::LaunchBuilder {
   void tensorSquare(Launch &L, Recs recs);
   void lincomb(Launch &L, Recs recs);
   void tensorMulAdd(Launch &L, Recs recs);
+  void reim(Launch &L, Recs recs);
   void nttSubScale(Launch &L, Recs recs);
   void copy(Launch &L, Recs recs);
   void transform(Launch &L, Recs recs);
@@ -699,6 +706,17 @@ void Arch::LaunchBuilder::tensorMulAdd(Launch &L, Recs recs) {
   L.bytes = (7ull + 2 * L.maAddends) * LP * recs.size();   // four operands and both components of every addend read once, three polynomials written
 }
 
+// (5r) a = the polynomial, c = its conjugate [n]; out = their sum, out1 = U (.) their difference [n] (hm_reim_split; the back-end derives U)
+void Arch::LaunchBuilder::reim(Launch &L, Recs recs) {
+  L.kind = Launch::L_REIM; L.statKey = "EWE";
+  for (Instruction *i : recs) {
+    L.a.push_back(limb(i->reimOperands[0])); L.c.push_back(limb(i->reimOperands[1]));
+    L.out.push_back(limb(i->OutputOperand)); L.out1.push_back(limb(i->extraOutputs[0]));
+    L.mods.push_back(i->mod_id);
+  }
+  L.bytes = 4 * LP * recs.size();   // two polynomials read, two written
+}
+
 // fused forward transform (4, 4b, 9, 12)
 void Arch::LaunchBuilder::nttSubScale(Launch &L, Recs recs) {
   L.kind = Launch::L_NTT_SUBSCALE; L.statKey = "NTT";
@@ -869,6 +887,7 @@ void Arch::LaunchBuilder::emitCompute(const Group &group, Launches &front, Launc
   else if (!f->sqOperands.empty()) tensorSquare(*L, recs);
   else if (!f->lcOperands.empty()) lincomb(*L, recs);
   else if (!f->maOperands.empty()) tensorMulAdd(*L, recs);
+  else if (!f->reimOperands.empty()) reim(*L, recs);
   else if (f->fusedTensor) tensor(*L, recs);
   else if (f->fusedSubScale) nttSubScale(*L, recs);
   else if (f->ops == NTT && f->passthrough) copy(*L, recs);
@@ -1280,11 +1299,21 @@ void Arch::prepare() {
         throw std::runtime_error(std::string("hm_fill_uniform: ") + hm_last_error(ctx));
     }
   hm_sync(ctx);
+  for (const InputFill &f : unitFills) {   // the evaluation form of -X^(N/2): two constant halves per limb, the same in every copy
+    std::vector<uint64_t> host((size_t)f.addrs.size() * n);
+    for (size_t i = 0; i < f.addrs.size(); ++i) {
+      const uint64_t q = modulus(f.mods[i]), w = q - hm::powmod(hostP(hostParams).psi.at(f.mods[i]), n / 2, q);
+      std::fill(host.begin() + i * n, host.begin() + i * n + n / 2, w);
+      std::fill(host.begin() + i * n + n / 2, host.begin() + (i + 1) * n, q - w);
+    }
+    for (uint32_t c = 0; c < batch_; ++c)
+      if (!writeLimbs(f.addrs, host.data(), c)) throw std::runtime_error(std::string("hm_memcpy_h2d (unit): ") + hm_last_error(ctx));
+  }
 }
 
 static const char *const kLaunchKindNames[] = {"NTT", "INTT", "EWE", "BCONV", "AUTO", "NTT_SUBSCALE", "TENSOR", "EXCH_IN", "EXCH_OUT", "REPLICATE", "IP", "NTT_IP",
                                                "BCONV_COL", "EXCH_IN_COL", "EXCH_OUT_COL", "IP_HOISTED", "IP_LINTRANS", "TENSOR_DOT", "IP_ROTSUM",
-                                               "IP_LINTRANS_MULTI", "TENSOR_SQUARE", "LINCOMB", "TENSOR_MULADD"};
+                                               "IP_LINTRANS_MULTI", "TENSOR_SQUARE", "LINCOMB", "TENSOR_MULADD", "REIM"};
 
 // Per-launch device time (SURVEY.md §8d "per-stage hipEvent times", exchange time at N > 1): every launch of the plan
 // bracketed by its own event pair, in plan order so that the data dependencies (and, sharded, the collectives) line up.
@@ -1532,6 +1561,9 @@ void Arch::enqueue(Launch &l) {
                           l.maAddends ? l.x0.data() : nullptr, l.maAddends ? l.x1.data() : nullptr, pool, l.out.data(), pool, l.out1.data(), pool,
                           l.out2.data(), l.mods.data(), cnt, l.maAddends, l.k.empty() ? nullptr : l.k.data(), l.maAddends ? l.maK.data() : nullptr,
                           l.addK.empty() ? nullptr : l.addK.data());
+    break;
+  case Launch::L_REIM:
+    st = hm_reim_split(ctx, pool, l.a.data(), pool, l.c.data(), pool, l.out.data(), pool, l.out1.data(), l.mods.data(), cnt);
     break;
   case Launch::L_EXCH_IN:
     st = hm_limbs_to_slices(ctx, pool, l.exLimbs.data(), l.exOwners.data(), (uint32_t)l.exLimbs.size(), l.slicesIn);

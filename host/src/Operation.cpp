@@ -596,12 +596,13 @@ std::vector<std::string> OperationBase::bufferNames() const {
 bool OperationBase::readBuffer(const std::string &name, uint64_t *host, uint32_t copy) { return arch->readLimbs(bufferAddrs(name), host, copy); }
 bool OperationBase::writeBuffer(const std::string &name, const uint64_t *host, uint32_t copy) { prepare(); return arch->writeLimbs(bufferAddrs(name), host, copy); }
 unsigned long long OperationBase::totalInstructions() { prepare(); return driver.getTotalIns(); }
-void OperationBase::bindInput(const std::string &input, OperationBase *producer) {
+void OperationBase::bindInput(const std::string &input, OperationBase *producer, const std::string &output) {
   for (const char *part : {".c0", ".c1"}) {
     auto in = namedInputs.find(input + part);
-    auto out = producer->namedOutputs.find(std::string("out") + part);
+    auto out = producer->namedOutputs.find(output + part);
     if (in == namedInputs.end()) throw std::runtime_error(opName + " has no input ciphertext " + input);
-    if (out == producer->namedOutputs.end()) throw std::runtime_error(producer->opName + " has no output ciphertext");
+    if (out == producer->namedOutputs.end())
+      throw std::runtime_error(producer->opName + (output == "out" ? " has no output ciphertext" : " has no output ciphertext " + output));
     arch->bindInput(in->second, producer->arch, out->second);
   }
 }
@@ -723,6 +724,45 @@ HROTATE::HROTATE(std::string labelName, uint32_t maxLevel, uint32_t currentLevel
   KeySwitch ksw(labelName, maxLevel, currentLevel, alpha, rc1, &Datapool, &DataInsMap, &insgener, addrManager.get());
   dispatch(ksw.getInsMap());
   finishRotation("out", rc0, ksw.output(), "");
+  finishConstruction();
+}
+
+// hreim (build extension).  HROTATE's body with galois = 2N - 1, unchanged, into the named output conj (buffers ReImConj(k):
+// HROTATE's own output buffers under that name), then per component k, existing opcodes only: ReIm_Add_C<k> = ct1.c<k> + conj.c<k> (ADD) into
+// ReImOutput(k), ReIm_Sub_C<k> = ct1.c<k> - conj.c<k> (SUB) into ReImDiff(k), ReIm_Mul_C<k> = that times the buffer `unit` (MUL) into ReImOutputIm(k).
+// Unfused, the three stages run as element-wise launches; fused, pass (5r) of Arch::fusePasses (Planner.cpp) turns the three records of a limb and
+// component into one record of ONE launch, which does not read `unit`.  Every buffer of HROTATE is allocated first, in HROTATE's order: the
+// launches in front of the tail are HROTATE's, field for field.
+HREIM::HREIM(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch)
+    : OperationBase("HREIM", labelName, cfg, _arch, maxLevel, currentLevel, alpha) {
+  if (arch->backend() == Arch::BACKEND_SIM) throw std::runtime_error("hreim: backend = sim has no such op (the reference has no monomial product)");
+  if (arch->world() > 1) throw std::runtime_error("hreim: world > 1 is not supported (the sharded plan is not built)");
+  makeInputs(1);
+  const uint32_t galois = 2 * N - 1;   // the conjugation; the config key galois is not read
+  const std::vector<AddrType> rc0 = rotateComponent(0, galois, "").addr, rc1 = rotateComponent(1, galois, "").addr;
+  KeySwitch ksw(labelName, maxLevel, currentLevel, alpha, rc1, &Datapool, &DataInsMap, &insgener, addrManager.get());
+  dispatch(ksw.getInsMap());
+  finishRotation("conj", rc0, ksw.output(), "");
+  const std::vector<AddrType> unit = alloc("unit", currentLevel);
+  arch->addUnitFill(unit, range(0, currentLevel));
+  for (uint32_t k = 0; k < 2; k++) {
+    const std::string C = "_C" + S(k);
+    const std::vector<AddrType> x = component(0, k), y = namedOutputs.at("conj.c" + S(k));
+    PerLimb a{labelName + "_ReIm_Add" + C + "_Level(", ")", range(0, currentLevel), alloc("ReImOutput(" + S(k) + ")", currentLevel)};
+    a.a = x; a.c = y;
+    const std::vector<INSGROUP> sum = eweLimbs(&insgener, EWE_ADD, a);
+    for (const INSGROUP &g : sum) g[0]->reimHead = true;
+    driver.dispatchInstructions("ReIm_Add" + C, sum);
+    PerLimb d{labelName + "_ReIm_Sub" + C + "_Level(", ")", a.mods, alloc("ReImDiff(" + S(k) + ")", currentLevel)};
+    d.a = x; d.c = y;
+    const Limbs diff{d.out, eweLimbs(&insgener, EWE_SUB, d)};
+    driver.dispatchInstructions("ReIm_Sub" + C, diff.from);
+    PerLimb m{labelName + "_ReIm_Mul" + C + "_Level(", ")", a.mods, alloc("ReImOutputIm(" + S(k) + ")", currentLevel)};
+    m.a = diff.addr; m.b = unit; m.after = {&diff.from};
+    driver.dispatchInstructions("ReIm_Mul" + C, eweLimbs(&insgener, EWE_MUL, m));
+    setOutput("out", k, a.out);
+    setOutput("out_im", k, m.out);
+  }
   finishConstruction();
 }
 
@@ -1283,6 +1323,7 @@ static OperationBase *makeOp(const std::string &o, uint32_t maxLevel, uint32_t l
   if (o == "hsquare") return new HSQUARE("test_hsquare", maxLevel, level, alpha, cfg, arch);
   if (o == "hlincomb") return new HLINCOMB("test_hlincomb", maxLevel, level, alpha, cfg, arch);
   if (o == "hmuladd") return new HMULADD("test_hmuladd", maxLevel, level, alpha, cfg, arch);
+  if (o == "hreim") return new HREIM("test_hreim", maxLevel, level, alpha, cfg, arch);
   throw std::runtime_error("Error operation requirement, please double confirm!");
 }
 

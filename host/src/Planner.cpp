@@ -108,6 +108,7 @@ struct Arch::Planner {
   void tensorSquare();     // 5q
   void linearCombination();   // 5l
   void tensorMulAdd();     // 5m
+  void realImaginary();    // 5r
   void keyProduct();       // 6
   // what (6m/6l), (6s) and (6h) all recognise: the live two-key key-product records whose digits are all automorphisms, by one element per record, of
   // the same materialised digits and are read by nothing else; per (modulus, unrotated digits) the records and their automorphisms, in stage order
@@ -151,6 +152,7 @@ void Arch::fusePasses(std::vector<Stage> &st) {
   if (fuseSquare) p.tensorSquare();
   if (fuseLincomb) p.linearCombination();
   if (fuseMuladd) p.tensorMulAdd();
+  if (fuseReim) p.realImaginary();
   p.keyProduct();
   // (6m, 6l) before (6s) and (6h): the records it merges are the ones (6h) would claim, and none of them is (6s)'s (their outputs go into products,
   // not into sums).  fuse_bsgs: the groups with several sums, fuse_lintrans: the ones with one
@@ -614,6 +616,41 @@ void Arch::Planner::tensorMulAdd() {
     c->extraOutputs = {d0, d2};
     for (const Write &w : recordWrites(*c)) producer[w.addr] = c;
     place.moveTo(c, last);
+  }
+}
+
+// (5r) real and imaginary parts (hreim): from an ADD record x + y that the builder marked (reimHead), with x an op input's limb and y the limb of
+//      its conjugate: the ONE live SUB record x - y of the same two operands, in this order, and modulus, whose output is read by ONE MUL record
+//      only, the difference its operand a and its operand b a limb that nothing produces (the stored evaluation form of -X^(N/2)).  The three
+//      merge into the marked record: hm_reim_split reads x and y once and stores the sum and the product; the factor is derived by the back-end
+//      from its roots, so the fused record does not read the stored one.  Never written: the difference.  The record takes the place of the last
+//      record it absorbs.  Only the builder of HREIM sets the mark: the pass matches nothing in any other op.
+//      Sets on the marked record: reimOperands, extraOutputs.
+void Arch::Planner::realImaginary() {
+  Readers rd = readers();
+  Placement place(st);
+  std::vector<Instruction *> heads;
+  for (auto &s : st)
+    for (Instruction *i : s.ins)
+      if (live(i) && i->reimHead && i->ops == MULT && i->opcode == EWE_ADD && i->reimOperands.empty() && i->extraOutputs.empty()) heads.push_back(i);
+  for (Instruction *c : heads) {
+    const AddrType x = c->operandList[0], y = c->operandList[2];
+    Instruction *sub = nullptr;
+    size_t subs = 0;
+    for (Instruction *r : rd[x])
+      if (r != c && live(r) && r->ops == MULT && r->opcode == EWE_SUB && r->mod_id == c->mod_id && r->operandList[0] == x && r->operandList[2] == y) { sub = r; ++subs; }
+    if (subs != 1) continue;
+    Instruction *mul = soleReader(rd, sub->OutputOperand, EWE_MUL, c->mod_id);
+    if (!mul || mul->operandList[0] != sub->OutputOperand || mul->operandList[1] == sub->OutputOperand || producerOf(mul->operandList[1])) continue;
+    c->reimOperands = {x, y};
+    c->extraOutputs = {mul->OutputOperand};
+    Instruction *last = c;
+    for (Instruction *i : {sub, mul}) {
+      absorb(c, i);
+      if (place.after(i, last)) last = i;
+    }
+    producer[mul->OutputOperand] = c;
+    place.moveTo(c, last);   // to where its last link stood
   }
 }
 

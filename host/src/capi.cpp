@@ -61,6 +61,7 @@ int hh_op_create(hh_op **out, const char *cfg_path, const char *op_name, uint32_
     else if (o == "hsquare") h->op = new HSQUARE("test_hsquare", maxLevel, curLevel, alpha, h->cfg, h->arch);
     else if (o == "hlincomb") h->op = new HLINCOMB("test_hlincomb", maxLevel, curLevel, alpha, h->cfg, h->arch);
     else if (o == "hmuladd") h->op = new HMULADD("test_hmuladd", maxLevel, curLevel, alpha, h->cfg, h->arch);
+    else if (o == "hreim") h->op = new HREIM("test_hreim", maxLevel, curLevel, alpha, h->cfg, h->arch);
     else if (o == "hadd") h->op = new HADD("test_hadd", maxLevel, curLevel, alpha, h->cfg, h->arch);
     else if (o == "pmult") h->op = new PMULT("test_pmult", maxLevel, curLevel, alpha, h->cfg, h->arch);
     else if (o == "padd") h->op = new PADD("test_ADD", maxLevel, curLevel, alpha, h->cfg, h->arch);
@@ -134,6 +135,7 @@ int hh_op_backend_counter(hh_op *h, const char *name, uint64_t *value) {
          if (hm_get_counter(h->arch->context(), name, value)) throw std::runtime_error(hm_last_error(h->arch->context())))
 }
 int hh_op_bind_input(hh_op *dst, const char *input, hh_op *src) { HH_TRY(dst->op->bindInput(input, src->op)) }
+int hh_op_bind_input_from(hh_op *dst, const char *input, hh_op *src, const char *output) { HH_TRY(dst->op->bindInput(input, src->op, output)) }
 
 struct hh_chain {
   OpChain *chain = nullptr;

@@ -225,6 +225,20 @@ hm_status hm_tensor_muladd(hm_ctx *ctx, const uint64_t *a, const uint32_t *a_lim
                            const uint32_t *o2_limbs, const uint32_t *mod_ids, uint32_t n, uint32_t n_addends,
                            const uint64_t *scale, const uint64_t *add_scale, const uint64_t *addend);
 
+/* K3, real and imaginary parts of the slots from a polynomial x and its conjugate y in one pass over both (HREIM): for
+ * entry i, per coefficient
+ *   o_re[i] = x[i] + y[i],   o_im[i] = U (.) (x[i] - y[i]),
+ * U the evaluation form of -X^(N/2) under the entry's modulus q: the constant w = -psi^(N/2) mod q on entries [0, N/2) and q - w on [N/2, N),
+ * w^2 = -1.  The back-end derives w from its own root table (hm_get_psi's psi); the caller passes no constants.  Every residue canonical:
+ * bit-identical to HM_OP_ADD, HM_OP_SUB and HM_OP_MUL by a stored U, whose difference is never written (4 limb-polys per entry where that
+ * chain moves 9).  The limb lists and mod_ids have n entries (the same input limb-poly may appear in several entries); a null limb list is the
+ * identity.  The records live in a device table: one launch serves any n, and the call is safe under graph capture once it has run with the
+ * same lists.  HM_ERR_ARG: a null buffer or a null mod_ids, a limb or modulus id out of range, an output limb-poly that overlaps (by address
+ * range, not by base pointer) an input limb-poly or another output limb-poly.  n = 0 is HM_OK. */
+hm_status hm_reim_split(hm_ctx *ctx, const uint64_t *x, const uint32_t *x_limbs, const uint64_t *y, const uint32_t *y_limbs,
+                        uint64_t *o_re, const uint32_t *o_re_limbs, uint64_t *o_im, const uint32_t *o_im_limbs,
+                        const uint32_t *mod_ids, uint32_t n);
+
 /* K5 — inner product with the evaluation key in one pass: for limb i, out[i][k] = sum_{j < n_terms}
  * x[i][j] * y[i][k][j], k < n_out (n_terms <= 4 digits, n_out <= 2 keys).  Limb lists are row-major:
  * x_limbs[i * n_terms + j], y_limbs[(i * n_out + k) * n_terms + j], out_limbs[i * n_out + k].  Replaces
