@@ -18,6 +18,7 @@
 
 #include "../../include/homulator_hip.h"
 #include "hm_elem_core.h"
+#include "hm_rec_core.h"
 #include "hm_ip_core.h"
 #include "hm_modarith.h"
 #include "hm_ntt_core.h"
@@ -490,38 +491,23 @@ __global__ void __launch_bounds__(256) k_tensor(HmTensorArgs a) {
   *reinterpret_cast<ulonglong2 *>(a.o2 + (size_t)lb.o2 * N + x) = r2;
 }
 
-// sum of T tensor products (hm_elem_core.h: hm_tensor_dot_thread): k_tensor's geometry — a workgroup owns 512 coefficients of one record, a thread an
-// aligned pair — with the records in a device table and T a run-time loop
-__global__ void __launch_bounds__(256) k_tensor_dot(HmTensorDotArgs a) {
+// The record-table kernels (hm_rec_core.h): k_tensor's geometry — a workgroup owns 512 coefficients of one record, a thread an aligned pair — with the
+// records in a device table.  THREAD: the per-thread core, called with (entry, chunk) of the workgroup.
+template <auto THREAD, class Args>
+__device__ __forceinline__ void hm_rec_block(const Args &a) {
   const uint32_t logPer = a.logN - 9, entry = blockIdx.x >> logPer;
-  if (entry < a.n_limbs) hm_tensor_dot_thread(a, entry, blockIdx.x & ((1u << logPer) - 1u), threadIdx.x);
+  if (entry < a.n_limbs) THREAD(a, entry, blockIdx.x & ((1u << logPer) - 1u), threadIdx.x);
 }
-
-// scaled square of one ciphertext plus a constant (hm_elem_core.h: hm_tensor_square_thread): k_tensor's geometry, the records in a device table
-__global__ void __launch_bounds__(256) k_tensor_square(HmTensorSqArgs a) {
-  const uint32_t logPer = a.logN - 9, entry = blockIdx.x >> logPer;
-  if (entry < a.n_limbs) hm_tensor_square_thread(a, entry, blockIdx.x & ((1u << logPer) - 1u), threadIdx.x);
-}
-
-// sum of T scaled limb-polys plus a constant (hm_elem_core.h: hm_lincomb_thread): k_tensor_dot's geometry, the records in a device table
-__global__ void __launch_bounds__(256) k_lincomb(HmLincombArgs a) {
-  const uint32_t logPer = a.logN - 9, entry = blockIdx.x >> logPer;
-  if (entry < a.n_limbs) hm_lincomb_thread(a, entry, blockIdx.x & ((1u << logPer) - 1u), threadIdx.x);
-}
-
-// scaled tensor product plus a linear combination of further ciphertexts plus a constant (hm_elem_core.h: hm_tensor_muladd_thread): k_tensor_dot's
-// geometry, the records in a device table
-__global__ void __launch_bounds__(256) k_tensor_muladd(HmTensorMulAddArgs a) {
-  const uint32_t logPer = a.logN - 9, entry = blockIdx.x >> logPer;
-  if (entry < a.n_limbs) hm_tensor_muladd_thread(a, entry, blockIdx.x & ((1u << logPer) - 1u), threadIdx.x);
-}
-
-// real and imaginary parts of the slots from a polynomial and its conjugate (hm_elem_core.h: hm_reim_thread): k_lincomb's geometry, the records in a
-// device table
-__global__ void __launch_bounds__(256) k_reim_split(HmReimArgs a) {
-  const uint32_t logPer = a.logN - 9, entry = blockIdx.x >> logPer;
-  if (entry < a.n_limbs) hm_reim_thread(a, entry, blockIdx.x & ((1u << logPer) - 1u), threadIdx.x);
-}
+// sum of T tensor products, T a run-time loop
+__global__ void __launch_bounds__(256) k_tensor_dot(HmTensorDotArgs a) { hm_rec_block<hm_tensor_dot_thread>(a); }
+// scaled square of one ciphertext plus a constant
+__global__ void __launch_bounds__(256) k_tensor_square(HmTensorSqArgs a) { hm_rec_block<hm_tensor_square_thread>(a); }
+// sum of T scaled limb-polys plus a constant
+__global__ void __launch_bounds__(256) k_lincomb(HmLincombArgs a) { hm_rec_block<hm_lincomb_thread>(a); }
+// scaled tensor product plus a linear combination of further ciphertexts plus a constant
+__global__ void __launch_bounds__(256) k_tensor_muladd(HmTensorMulAddArgs a) { hm_rec_block<hm_tensor_muladd_thread>(a); }
+// real and imaginary parts of the slots from a polynomial and its conjugate
+__global__ void __launch_bounds__(256) k_reim_split(HmReimArgs a) { hm_rec_block<hm_reim_thread>(a); }
 
 // 16-byte units per thread of the element-wise kernel, 512 coefficients apart, all loads in flight before the first use.  1: 89 600 workgroups for a batch of
 // ten hadd; 2 / 4 measured padd +3 / +5 %, pmult +1 %, hadd within the noise (tools/r06_ewe_ab.sh): not worth a second shape of the kernel's launch
@@ -1746,7 +1732,67 @@ extern "C" hm_status hm_tensor(hm_ctx *c, const uint64_t *pa, const uint32_t *la
   return HM_OK;
 }
 
-// sum of n_terms tensor products: operand lists [n][n_terms], output lists [n]; one record per entry in a device table, ONE launch for any n
+// ---- the record-table element-wise entry points (hm_rec_core.h): one record per entry in a device table, ONE launch for any n
+// An operand: its name in the refusals, its base, its limbs (null: the identity) and how many
+struct Operand { const char *name; const void *base; const uint32_t *limbs; uint32_t count; };
+// Per-entry constants: v = [n] ("name[i]" in the refusals) or, with rows, [n][per] ("name[i][t]"); null: the op's default, nothing to check
+struct RecConsts { const char *name; const uint64_t *v; bool nonzero; bool rows = false; uint32_t per = 1; };
+// What the five check behind their own arguments, in this order: every limb index (inputs, then outputs) and modulus id in range; every constant
+// below its entry's modulus (a scale: not zero either); then the aliasing rule.  A workgroup stores its outputs after ALL its loads, and the same
+// input limb-poly may serve several records and terms: no output may share an address with any input (an input list of count 0 is not read) or
+// with another output.
+static hm_status rec_check(hm_ctx *c, const char *what, std::initializer_list<Operand> ins, std::initializer_list<Operand> outs, const uint32_t *mod_ids,
+                           uint32_t n, std::initializer_list<RecConsts> consts) {
+  const uint32_t N = c->P.N;
+  hm_status st;
+  for (const Operand &l : ins)
+    if ((st = check_limbs(c, what, l.limbs, l.count))) return st;
+  for (const Operand &l : outs)
+    if ((st = check_limbs(c, what, l.limbs, l.count))) return st;
+  if ((st = check_mods(c, what, mod_ids, n))) return st;
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint64_t q = c->P.mod[mod_ids[i]];
+    for (const RecConsts &k : consts)
+      for (uint32_t t = 0; k.v && t < k.per; ++t) {
+        const uint64_t v = k.v[(size_t)i * k.per + t];
+        if (v < q && (v || !k.nonzero)) continue;
+        if (k.rows) return fail(c, HM_ERR_ARG, "%s: %s[%u][%u] is not reduced", what, k.name, i, t);
+        return fail(c, HM_ERR_ARG, "%s: %s[%u] is %s", what, k.name, i, v ? "not reduced" : "zero");
+      }
+  }
+  for (const Operand &o : outs)
+    for (const Operand &i : ins)
+      if (i.count && hm_limbs_overlap(o.base, o.limbs, o.count, i.base, i.limbs, i.count, N))
+        return fail(c, HM_ERR_ARG, "%s: an output limb-poly (%s) overlaps an input limb-poly (%s)", what, o.name, i.name);
+  std::vector<uintptr_t> starts;
+  for (const Operand &o : outs)
+    for (uint32_t i = 0; i < o.count; ++i) starts.push_back(reinterpret_cast<uintptr_t>(o.base) + (uintptr_t)limb_at(o.limbs, i) * N * 8);
+  std::sort(starts.begin(), starts.end());
+  for (size_t i = 1; i < starts.size(); ++i)
+    if (starts[i] - starts[i - 1] < (uintptr_t)N * 8) return fail(c, HM_ERR_ARG, "%s: two output limb-polys overlap", what);
+  return HM_OK;
+}
+// the moduli of the entries, for the *_fill_recs that store constants in the arithmetic's form
+static std::vector<uint64_t> rec_moduli(hm_ctx *c, const uint32_t *mod_ids, uint32_t n) {
+  std::vector<uint64_t> qs(n);
+  for (uint32_t i = 0; i < n; ++i) qs[i] = c->P.mod[mod_ids[i]];
+  return qs;
+}
+// The launch: the records into a device table, the fields every Args has, n * (N / 512) workgroups of 256 threads.  The caller has set the buffers
+// and the op's own counts.
+template <class Args, class Rec>
+static hm_status rec_launch(hm_ctx *c, void (*kernel)(Args), Args &a, const std::vector<Rec> &recs, uint32_t n) {
+  HM_HIP(c, hipSetDevice(c->device));
+  const void *tab = nullptr;
+  if (hm_status st = device_table(c, recs.data(), recs.size() * sizeof(Rec), &tab)) return st;
+  a.rec = static_cast<const Rec *>(tab);
+  a.mods = c->d_mods; a.logN = c->P.logN; a.n_limbs = n;
+  hipLaunchKernelGGL(kernel, dim3(n * (c->P.N / 512)), dim3(256), 0, c->stream, a);
+  HM_HIP(c, hipGetLastError());
+  return HM_OK;
+}
+
+// sum of n_terms tensor products: operand lists [n][n_terms], output lists [n]
 extern "C" hm_status hm_tensor_dot(hm_ctx *c, const uint64_t *pa, const uint32_t *la, const uint64_t *pb, const uint32_t *lb,
                                    const uint64_t *pc, const uint32_t *lc, const uint64_t *pd, const uint32_t *ld, uint64_t *o0,
                                    const uint32_t *l0, uint64_t *o1, const uint32_t *l1, uint64_t *o2, const uint32_t *l2,
@@ -1755,48 +1801,21 @@ extern "C" hm_status hm_tensor_dot(hm_ctx *c, const uint64_t *pa, const uint32_t
   if (!c) return HM_ERR_ARG;
   HM_TABLE_CALL(c);
   if (!pa || !pb || !pc || !pd || !o0 || !o1 || !o2) return fail(c, HM_ERR_ARG, "%s: null buffer", what);
-  const uint32_t T = n_terms, N = c->P.N;
+  const uint32_t T = n_terms;
   if (T == 0 || T > HM_DOT_MAX_TERMS) return fail(c, HM_ERR_ARG, "%s: n_terms = %u, must be in [1, %d]", what, T, HM_DOT_MAX_TERMS);
   if ((uint64_t)n * T > 0xFFFFFFFFull / HM_DOT_REC_WORDS(T)) return fail(c, HM_ERR_ARG, "%s: n = %u entries of %u terms are too many for one call", what, n, T);
-  struct List { const char *name; const void *base; const uint32_t *limbs; uint32_t count; };
-  const List ins[4] = {{"a", pa, la, n * T}, {"b", pb, lb, n * T}, {"c", pc, lc, n * T}, {"d", pd, ld, n * T}};
-  const List outs[3] = {{"o0", o0, l0, n}, {"o1", o1, l1, n}, {"o2", o2, l2, n}};
-  hm_status st;
-  for (const List &l : ins)
-    if ((st = check_limbs(c, what, l.limbs, l.count))) return st;
-  for (const List &l : outs)
-    if ((st = check_limbs(c, what, l.limbs, l.count))) return st;
-  if ((st = check_mods(c, what, mod_ids, n))) return st;
-  // a workgroup stores its three outputs after ALL its loads, and the same operand limb-poly may serve several records (a ciphertext that takes
-  // part in two pairs): no output may share an address with any input or with another output
-  for (const List &o : outs)
-    for (const List &i : ins)
-      if (hm_limbs_overlap(o.base, o.limbs, o.count, i.base, i.limbs, i.count, N))
-        return fail(c, HM_ERR_ARG, "%s: an output limb-poly (%s) overlaps an input limb-poly (%s)", what, o.name, i.name);
-  {
-    std::vector<uintptr_t> starts;
-    for (const List &o : outs)
-      for (uint32_t i = 0; i < o.count; ++i) starts.push_back(reinterpret_cast<uintptr_t>(o.base) + (uintptr_t)limb_at(o.limbs, i) * N * 8);
-    std::sort(starts.begin(), starts.end());
-    for (size_t i = 1; i < starts.size(); ++i)
-      if (starts[i] - starts[i - 1] < (uintptr_t)N * 8) return fail(c, HM_ERR_ARG, "%s: two output limb-polys overlap", what);
-  }
+  if (hm_status st = rec_check(c, what, {{"a", pa, la, n * T}, {"b", pb, lb, n * T}, {"c", pc, lc, n * T}, {"d", pd, ld, n * T}},
+                               {{"o0", o0, l0, n}, {"o1", o1, l1, n}, {"o2", o2, l2, n}}, mod_ids, n, {}))
+    return st;
   if (n == 0) return HM_OK;
   std::vector<uint32_t> recs((size_t)n * HM_DOT_REC_WORDS(T));
   hm_tensor_dot_fill_recs(recs.data(), la, lb, lc, ld, l0, l1, l2, mod_ids, n, T);
-  HM_HIP(c, hipSetDevice(c->device));
   HmTensorDotArgs a;
-  const void *tab = nullptr;
-  if ((st = device_table(c, recs.data(), recs.size() * sizeof(uint32_t), &tab))) return st;
-  a.rec = static_cast<const uint32_t *>(tab);
-  a.a = pa; a.b = pb; a.c = pc; a.d = pd; a.o0 = o0; a.o1 = o1; a.o2 = o2;
-  a.mods = c->d_mods; a.logN = c->P.logN; a.n_limbs = n; a.n_terms = T;
-  hipLaunchKernelGGL(k_tensor_dot, dim3(n * (N / 512)), dim3(256), 0, c->stream, a);
-  HM_HIP(c, hipGetLastError());
-  return HM_OK;
+  a.a = pa; a.b = pb; a.c = pc; a.d = pd; a.o0 = o0; a.o1 = o1; a.o2 = o2; a.n_terms = T;
+  return rec_launch(c, k_tensor_dot, a, recs, n);
 }
 
-// scaled square of one ciphertext plus a constant: one record per entry in a device table, ONE launch for any n
+// scaled square of one ciphertext plus a constant
 extern "C" hm_status hm_tensor_square(hm_ctx *c, const uint64_t *pa, const uint32_t *la, const uint64_t *pc, const uint32_t *lc, uint64_t *o0,
                                       const uint32_t *l0, uint64_t *o1, const uint32_t *l1, uint64_t *o2, const uint32_t *l2,
                                       const uint32_t *mod_ids, uint32_t n, const uint64_t *scale, const uint64_t *addend) {
@@ -1804,55 +1823,19 @@ extern "C" hm_status hm_tensor_square(hm_ctx *c, const uint64_t *pa, const uint3
   if (!c) return HM_ERR_ARG;
   HM_TABLE_CALL(c);
   if (!pa || !pc || !o0 || !o1 || !o2) return fail(c, HM_ERR_ARG, "%s: null buffer", what);
-  const uint32_t N = c->P.N;
   if ((uint64_t)n > 0xFFFFFFFFull / sizeof(HmTensorSqRec)) return fail(c, HM_ERR_ARG, "%s: n = %u entries are too many for one call", what, n);
-  struct List { const char *name; const void *base; const uint32_t *limbs; uint32_t count; };
-  const List ins[2] = {{"a", pa, la, n}, {"c", pc, lc, n}};
-  const List outs[3] = {{"o0", o0, l0, n}, {"o1", o1, l1, n}, {"o2", o2, l2, n}};
-  hm_status st;
-  for (const List &l : ins)
-    if ((st = check_limbs(c, what, l.limbs, l.count))) return st;
-  for (const List &l : outs)
-    if ((st = check_limbs(c, what, l.limbs, l.count))) return st;
-  if ((st = check_mods(c, what, mod_ids, n))) return st;
-  for (uint32_t i = 0; i < n; ++i) {
-    const uint64_t q = c->P.mod[mod_ids[i]];
-    if (scale && (scale[i] == 0 || scale[i] >= q)) return fail(c, HM_ERR_ARG, "%s: scale[%u] is %s", what, i, scale[i] ? "not reduced" : "zero");
-    if (addend && addend[i] >= q) return fail(c, HM_ERR_ARG, "%s: addend[%u] is not reduced", what, i);
-  }
-  // a workgroup stores its three outputs after both loads, and one input limb-poly may serve several records: no output may share an address
-  // with an input or with another output (hm_tensor_dot's rule and messages)
-  for (const List &o : outs)
-    for (const List &i : ins)
-      if (hm_limbs_overlap(o.base, o.limbs, o.count, i.base, i.limbs, i.count, N))
-        return fail(c, HM_ERR_ARG, "%s: an output limb-poly (%s) overlaps an input limb-poly (%s)", what, o.name, i.name);
-  {
-    std::vector<uintptr_t> starts;
-    for (const List &o : outs)
-      for (uint32_t i = 0; i < o.count; ++i) starts.push_back(reinterpret_cast<uintptr_t>(o.base) + (uintptr_t)limb_at(o.limbs, i) * N * 8);
-    std::sort(starts.begin(), starts.end());
-    for (size_t i = 1; i < starts.size(); ++i)
-      if (starts[i] - starts[i - 1] < (uintptr_t)N * 8) return fail(c, HM_ERR_ARG, "%s: two output limb-polys overlap", what);
-  }
+  if (hm_status st = rec_check(c, what, {{"a", pa, la, n}, {"c", pc, lc, n}}, {{"o0", o0, l0, n}, {"o1", o1, l1, n}, {"o2", o2, l2, n}}, mod_ids, n,
+                               {{"scale", scale, true}, {"addend", addend, false}}))
+    return st;
   if (n == 0) return HM_OK;
   std::vector<HmTensorSqRec> recs(n);
-  std::vector<uint64_t> qs(n);
-  for (uint32_t i = 0; i < n; ++i) qs[i] = c->P.mod[mod_ids[i]];
-  hm_tensor_square_fill_recs(recs.data(), la, lc, l0, l1, l2, mod_ids, qs.data(), n, scale, addend);
-  HM_HIP(c, hipSetDevice(c->device));
+  hm_tensor_square_fill_recs(recs.data(), la, lc, l0, l1, l2, mod_ids, rec_moduli(c, mod_ids, n).data(), n, scale, addend);
   HmTensorSqArgs a;
-  const void *tab = nullptr;
-  if ((st = device_table(c, recs.data(), recs.size() * sizeof(HmTensorSqRec), &tab))) return st;
-  a.rec = static_cast<const HmTensorSqRec *>(tab);
   a.a = pa; a.c = pc; a.o0 = o0; a.o1 = o1; a.o2 = o2;
-  a.mods = c->d_mods; a.logN = c->P.logN; a.n_limbs = n;
-  hipLaunchKernelGGL(k_tensor_square, dim3(n * (N / 512)), dim3(256), 0, c->stream, a);
-  HM_HIP(c, hipGetLastError());
-  return HM_OK;
+  return rec_launch(c, k_tensor_square, a, recs, n);
 }
 
-// sum of n_terms scaled limb-polys plus a constant: input list and scalars [n][n_terms], output list and constants [n]; one record per entry in a
-// device table, ONE launch for any n
+// sum of n_terms scaled limb-polys plus a constant: input list and scalars [n][n_terms], output list and constants [n]
 extern "C" hm_status hm_lincomb(hm_ctx *c, const uint64_t *in, const uint32_t *li, uint64_t *out, const uint32_t *lo, const uint32_t *mod_ids,
                                 uint32_t n, uint32_t n_terms, const uint64_t *scale, const uint64_t *addend) {
   static const char *const what = "hm_lincomb";
@@ -1860,44 +1843,20 @@ extern "C" hm_status hm_lincomb(hm_ctx *c, const uint64_t *in, const uint32_t *l
   HM_TABLE_CALL(c);
   if (!in || !out) return fail(c, HM_ERR_ARG, "%s: null buffer", what);
   if (!scale) return fail(c, HM_ERR_ARG, "%s: scale is null", what);
-  const uint32_t T = n_terms, N = c->P.N;
+  const uint32_t T = n_terms;
   if (T == 0 || T > HM_LINCOMB_MAX_TERMS) return fail(c, HM_ERR_ARG, "%s: n_terms = %u, must be in [1, %d]", what, T, HM_LINCOMB_MAX_TERMS);
   if ((uint64_t)n * T > 0xFFFFFFFFull / HM_LINCOMB_REC_WORDS(T)) return fail(c, HM_ERR_ARG, "%s: n = %u entries of %u terms are too many for one call", what, n, T);
-  hm_status st;
-  if ((st = check_limbs(c, what, li, n * T)) || (st = check_limbs(c, what, lo, n)) || (st = check_mods(c, what, mod_ids, n))) return st;
-  for (uint32_t i = 0; i < n; ++i) {
-    const uint64_t q = c->P.mod[mod_ids[i]];
-    for (uint32_t t = 0; t < T; ++t)
-      if (scale[(size_t)i * T + t] >= q) return fail(c, HM_ERR_ARG, "%s: scale[%u][%u] is not reduced", what, i, t);
-    if (addend && addend[i] >= q) return fail(c, HM_ERR_ARG, "%s: addend[%u] is not reduced", what, i);
-  }
-  // a workgroup stores its output after ALL its loads, and the same input limb-poly may serve several records and terms: no output may share an
-  // address with any input or with another output (hm_tensor_dot's rule and messages)
-  if (hm_limbs_overlap(out, lo, n, in, li, n * T, N)) return fail(c, HM_ERR_ARG, "%s: an output limb-poly (%s) overlaps an input limb-poly (%s)", what, "out", "in");
-  {
-    std::vector<uintptr_t> starts;
-    for (uint32_t i = 0; i < n; ++i) starts.push_back(reinterpret_cast<uintptr_t>(out) + (uintptr_t)limb_at(lo, i) * N * 8);
-    std::sort(starts.begin(), starts.end());
-    for (size_t i = 1; i < starts.size(); ++i)
-      if (starts[i] - starts[i - 1] < (uintptr_t)N * 8) return fail(c, HM_ERR_ARG, "%s: two output limb-polys overlap", what);
-  }
+  if (hm_status st = rec_check(c, what, {{"in", in, li, n * T}}, {{"out", out, lo, n}}, mod_ids, n, {{"scale", scale, false, true, T}, {"addend", addend, false}}))
+    return st;
   if (n == 0) return HM_OK;
   std::vector<uint32_t> recs((size_t)n * HM_LINCOMB_REC_WORDS(T));
   hm_lincomb_fill_recs(recs.data(), li, lo, mod_ids, n, T, scale, addend);
-  HM_HIP(c, hipSetDevice(c->device));
   HmLincombArgs a;
-  const void *tab = nullptr;
-  if ((st = device_table(c, recs.data(), recs.size() * sizeof(uint32_t), &tab))) return st;
-  a.rec = static_cast<const uint32_t *>(tab);
-  a.in = in; a.out = out;
-  a.mods = c->d_mods; a.logN = c->P.logN; a.n_limbs = n; a.n_terms = T;
-  hipLaunchKernelGGL(k_lincomb, dim3(n * (N / 512)), dim3(256), 0, c->stream, a);
-  HM_HIP(c, hipGetLastError());
-  return HM_OK;
+  a.in = in; a.out = out; a.n_terms = T;
+  return rec_launch(c, k_lincomb, a, recs, n);
 }
 
-// scaled tensor product plus n_addends scaled ciphertexts plus a constant: operand and output lists [n], addend lists and scalars [n][n_addends];
-// one record per entry in a device table, ONE launch for any n
+// scaled tensor product plus n_addends scaled ciphertexts plus a constant: operand and output lists [n], addend lists and scalars [n][n_addends]
 extern "C" hm_status hm_tensor_muladd(hm_ctx *c, const uint64_t *pa, const uint32_t *la, const uint64_t *pb, const uint32_t *lb, const uint64_t *pc,
                                       const uint32_t *lc, const uint64_t *pd, const uint32_t *ld, const uint64_t *px, const uint32_t *lx0,
                                       const uint32_t *lx1, uint64_t *o0, const uint32_t *l0, uint64_t *o1, const uint32_t *l1, uint64_t *o2,
@@ -1907,116 +1866,50 @@ extern "C" hm_status hm_tensor_muladd(hm_ctx *c, const uint64_t *pa, const uint3
   if (!c) return HM_ERR_ARG;
   HM_TABLE_CALL(c);
   if (!pa || !pb || !pc || !pd || !o0 || !o1 || !o2) return fail(c, HM_ERR_ARG, "%s: null buffer", what);
-  const uint32_t A = n_addends, N = c->P.N;
+  const uint32_t A = n_addends;
   if (A > HM_MULADD_MAX_ADDENDS) return fail(c, HM_ERR_ARG, "%s: n_addends = %u, must be in [0, %d]", what, A, HM_MULADD_MAX_ADDENDS);
   if (A > 0 && !px) return fail(c, HM_ERR_ARG, "%s: null buffer", what);
   if (A > 0 && (!lx0 || !lx1)) return fail(c, HM_ERR_ARG, "%s: x0_limbs or x1_limbs is null", what);
   if (A > 0 && !add_scale) return fail(c, HM_ERR_ARG, "%s: add_scale is null", what);
   if ((uint64_t)n > 0xFFFFFFFFull / (HM_MULADD_REC_WORDS(A) * sizeof(uint32_t)))
     return fail(c, HM_ERR_ARG, "%s: n = %u entries of %u addends are too many for one call", what, n, A);
-  struct List { const char *name; const void *base; const uint32_t *limbs; uint32_t count; };
-  const List ins[6] = {{"a", pa, la, n}, {"b", pb, lb, n}, {"c", pc, lc, n}, {"d", pd, ld, n}, {"x", px, lx0, A ? n * A : 0}, {"x", px, lx1, A ? n * A : 0}};
-  const List outs[3] = {{"o0", o0, l0, n}, {"o1", o1, l1, n}, {"o2", o2, l2, n}};
-  hm_status st;
-  for (const List &l : ins)
-    if ((st = check_limbs(c, what, l.limbs, l.count))) return st;
-  for (const List &l : outs)
-    if ((st = check_limbs(c, what, l.limbs, l.count))) return st;
-  if ((st = check_mods(c, what, mod_ids, n))) return st;
-  for (uint32_t i = 0; i < n; ++i) {
-    const uint64_t q = c->P.mod[mod_ids[i]];
-    if (scale && (scale[i] == 0 || scale[i] >= q)) return fail(c, HM_ERR_ARG, "%s: scale[%u] is %s", what, i, scale[i] ? "not reduced" : "zero");
-    for (uint32_t t = 0; t < A; ++t)
-      if (add_scale[(size_t)i * A + t] >= q) return fail(c, HM_ERR_ARG, "%s: add_scale[%u][%u] is not reduced", what, i, t);
-    if (addend && addend[i] >= q) return fail(c, HM_ERR_ARG, "%s: addend[%u] is not reduced", what, i);
-  }
-  // a workgroup stores its three outputs after ALL its loads, and the same input limb-poly may serve several records and addends: no output may
-  // share an address with any input or with another output (hm_tensor_dot's rule and messages)
-  for (const List &o : outs)
-    for (const List &i : ins)
-      if (i.count && hm_limbs_overlap(o.base, o.limbs, o.count, i.base, i.limbs, i.count, N))
-        return fail(c, HM_ERR_ARG, "%s: an output limb-poly (%s) overlaps an input limb-poly (%s)", what, o.name, i.name);
-  {
-    std::vector<uintptr_t> starts;
-    for (const List &o : outs)
-      for (uint32_t i = 0; i < o.count; ++i) starts.push_back(reinterpret_cast<uintptr_t>(o.base) + (uintptr_t)limb_at(o.limbs, i) * N * 8);
-    std::sort(starts.begin(), starts.end());
-    for (size_t i = 1; i < starts.size(); ++i)
-      if (starts[i] - starts[i - 1] < (uintptr_t)N * 8) return fail(c, HM_ERR_ARG, "%s: two output limb-polys overlap", what);
-  }
+  if (hm_status st = rec_check(c, what, {{"a", pa, la, n}, {"b", pb, lb, n}, {"c", pc, lc, n}, {"d", pd, ld, n}, {"x", px, lx0, n * A}, {"x", px, lx1, n * A}},
+                               {{"o0", o0, l0, n}, {"o1", o1, l1, n}, {"o2", o2, l2, n}}, mod_ids, n,
+                               {{"scale", scale, true}, {"add_scale", add_scale, false, true, A}, {"addend", addend, false}}))
+    return st;
   if (n == 0) return HM_OK;
   std::vector<uint32_t> recs((size_t)n * HM_MULADD_REC_WORDS(A));
-  std::vector<uint64_t> qs(n);
-  for (uint32_t i = 0; i < n; ++i) qs[i] = c->P.mod[mod_ids[i]];
-  hm_tensor_muladd_fill_recs(recs.data(), la, lb, lc, ld, lx0, lx1, l0, l1, l2, mod_ids, qs.data(), n, A, scale, add_scale, addend);
-  HM_HIP(c, hipSetDevice(c->device));
+  hm_tensor_muladd_fill_recs(recs.data(), la, lb, lc, ld, lx0, lx1, l0, l1, l2, mod_ids, rec_moduli(c, mod_ids, n).data(), n, A, scale, add_scale, addend);
   HmTensorMulAddArgs a;
-  const void *tab = nullptr;
-  if ((st = device_table(c, recs.data(), recs.size() * sizeof(uint32_t), &tab))) return st;
-  a.rec = static_cast<const uint32_t *>(tab);
-  a.a = pa; a.b = pb; a.c = pc; a.d = pd; a.x = A ? px : pa; a.o0 = o0; a.o1 = o1; a.o2 = o2;
-  a.mods = c->d_mods; a.logN = c->P.logN; a.n_limbs = n; a.n_addends = A;
-  hipLaunchKernelGGL(k_tensor_muladd, dim3(n * (N / 512)), dim3(256), 0, c->stream, a);
-  HM_HIP(c, hipGetLastError());
-  return HM_OK;
+  a.a = pa; a.b = pb; a.c = pc; a.d = pd; a.x = A ? px : pa; a.o0 = o0; a.o1 = o1; a.o2 = o2; a.n_addends = A;
+  return rec_launch(c, k_tensor_muladd, a, recs, n);
 }
 
-// o_re = x + y, o_im = U (.) (x - y) with U the evaluation form of -X^(N/2), derived here from the context's own roots: one record per entry in a
-// device table, ONE launch for any n
+// o_re = x + y, o_im = U (.) (x - y) with U the evaluation form of -X^(N/2), derived here from the context's own roots
 extern "C" hm_status hm_reim_split(hm_ctx *c, const uint64_t *px, const uint32_t *lx, const uint64_t *py, const uint32_t *ly, uint64_t *o_re,
                                    const uint32_t *lre, uint64_t *o_im, const uint32_t *lim, const uint32_t *mod_ids, uint32_t n) {
   static const char *const what = "hm_reim_split";
   if (!c) return HM_ERR_ARG;
   HM_TABLE_CALL(c);
   if (!px || !py || !o_re || !o_im) return fail(c, HM_ERR_ARG, "%s: null buffer", what);
-  const uint32_t N = c->P.N;
   if ((uint64_t)n > 0xFFFFFFFFull / (HM_REIM_REC_WORDS * sizeof(uint32_t))) return fail(c, HM_ERR_ARG, "%s: n = %u entries are too many for one call", what, n);
-  struct List { const char *name; const void *base; const uint32_t *limbs; uint32_t count; };
-  const List ins[2] = {{"x", px, lx, n}, {"y", py, ly, n}};
-  const List outs[2] = {{"o_re", o_re, lre, n}, {"o_im", o_im, lim, n}};
-  hm_status st;
-  for (const List &l : ins)
-    if ((st = check_limbs(c, what, l.limbs, l.count))) return st;
-  for (const List &l : outs)
-    if ((st = check_limbs(c, what, l.limbs, l.count))) return st;
-  if ((st = check_mods(c, what, mod_ids, n))) return st;
-  // a workgroup stores its two outputs after both loads, and one input limb-poly may serve several records: no output may share an address with
-  // an input or with another output (hm_tensor_dot's rule and messages)
-  for (const List &o : outs)
-    for (const List &i : ins)
-      if (hm_limbs_overlap(o.base, o.limbs, o.count, i.base, i.limbs, i.count, N))
-        return fail(c, HM_ERR_ARG, "%s: an output limb-poly (%s) overlaps an input limb-poly (%s)", what, o.name, i.name);
-  {
-    std::vector<uintptr_t> starts;
-    for (const List &o : outs)
-      for (uint32_t i = 0; i < o.count; ++i) starts.push_back(reinterpret_cast<uintptr_t>(o.base) + (uintptr_t)limb_at(o.limbs, i) * N * 8);
-    std::sort(starts.begin(), starts.end());
-    for (size_t i = 1; i < starts.size(); ++i)
-      if (starts[i] - starts[i - 1] < (uintptr_t)N * 8) return fail(c, HM_ERR_ARG, "%s: two output limb-polys overlap", what);
-  }
+  if (hm_status st = rec_check(c, what, {{"x", px, lx, n}, {"y", py, ly, n}}, {{"o_re", o_re, lre, n}, {"o_im", o_im, lim, n}}, mod_ids, n, {})) return st;
   if (n == 0) return HM_OK;
   // w = -psi^(N/2) mod q per entry, from the root table the transforms are built from (N >= 1024: a workgroup's 512 coefficients lie in one half)
-  std::vector<uint64_t> qs(n), ws(n);
+  const std::vector<uint64_t> qs = rec_moduli(c, mod_ids, n);
+  std::vector<uint64_t> ws(n);
   std::map<uint32_t, uint64_t> wOf;
   for (uint32_t i = 0; i < n; ++i) {
     const uint32_t m = mod_ids[i];
-    qs[i] = c->P.mod[m];
     auto f = wOf.find(m);
-    if (f == wOf.end()) f = wOf.emplace(m, qs[i] - hm::powmod(c->P.psi[m], N / 2, qs[i])).first;
+    if (f == wOf.end()) f = wOf.emplace(m, qs[i] - hm::powmod(c->P.psi[m], c->P.N / 2, qs[i])).first;
     ws[i] = f->second;
   }
   std::vector<uint32_t> recs((size_t)n * HM_REIM_REC_WORDS);
   hm_reim_fill_recs(recs.data(), lx, ly, lre, lim, mod_ids, ws.data(), qs.data(), n);
-  HM_HIP(c, hipSetDevice(c->device));
   HmReimArgs a;
-  const void *tab = nullptr;
-  if ((st = device_table(c, recs.data(), recs.size() * sizeof(uint32_t), &tab))) return st;
-  a.rec = static_cast<const uint32_t *>(tab);
   a.x = px; a.y = py; a.o_re = o_re; a.o_im = o_im;
-  a.mods = c->d_mods; a.logN = c->P.logN; a.n_limbs = n;
-  hipLaunchKernelGGL(k_reim_split, dim3(n * (N / 512)), dim3(256), 0, c->stream, a);
-  HM_HIP(c, hipGetLastError());
-  return HM_OK;
+  return rec_launch(c, k_reim_split, a, recs, n);
 }
 
 extern "C" hm_status hm_automorph(hm_ctx *c, const uint64_t *in, const uint32_t *in_limbs, uint64_t *out,
@@ -2126,19 +2019,18 @@ static hm_status ip_check(hm_ctx *c, const char *what, const char *null_msg, uin
 // The three forms that sum over rotations (lintrans, lintrans_multi, rotsum) go on in the same way.  An addend is four arguments that go together.
 // ip_check runs over the limbs of the inputs `ins`, the outputs, the addend sources and the addend outputs, in this order.  Then: a workgroup reads
 // operands at other positions than the ones it writes, and operands that could be another workgroup's output, so no output and no addend output
-// may overlap any input, the addend sources last.  An operand: its name in the refusals, its base, its limbs
+// may overlap any input, the addend sources last.
 static const char *const kAddendQuartet = "null argument (addend, addend_limbs, addend_out and addend_out_limbs go together)";
-struct IpOperand { const char *name; const void *base; const uint32_t *limbs; uint32_t count; };
 static hm_status ip_sum_check(hm_ctx *c, const char *what, const char *null_msg, uint32_t T, const char *second, uint32_t v, uint32_t vmax, const uint32_t *galois,
-                              std::vector<IpOperand> ins, const IpOperand &addSrc, const IpOperand &out, const IpOperand &addOut, const uint32_t *mod_ids,
-                              uint32_t n, const IpOperand *addOut1 = nullptr) {
+                              std::vector<Operand> ins, const Operand &addSrc, const Operand &out, const Operand &addOut, const uint32_t *mod_ids,
+                              uint32_t n, const Operand *addOut1 = nullptr) {
   std::vector<IpList> lists;
-  for (const IpOperand &in : ins) lists.push_back({in.limbs, in.count});
-  for (const IpOperand *o : {&out, &addSrc, &addOut}) lists.push_back({o->limbs, o->count});
+  for (const Operand &in : ins) lists.push_back({in.limbs, in.count});
+  for (const Operand *o : {&out, &addSrc, &addOut}) lists.push_back({o->limbs, o->count});
   if (addOut1) lists.push_back({addOut1->limbs, addOut1->count});   // (the identity step: the second addend's outputs; its source is among `ins`)
   if (hm_status st = ip_check(c, what, null_msg, T, second, v, vmax, galois, lists, mod_ids, n)) return st;
   ins.push_back(addSrc);
-  for (const IpOperand &in : ins) {
+  for (const Operand &in : ins) {
     if (in.count && hm_limbs_overlap(out.base, out.limbs, out.count, in.base, in.limbs, in.count, c->P.N))
       return fail(c, HM_ERR_ARG, "%s: an output limb-poly overlaps %s", what, in.name);
     if (in.count && addOut.count && hm_limbs_overlap(addOut.base, addOut.limbs, addOut.count, in.base, in.limbs, in.count, c->P.N))
@@ -2289,9 +2181,9 @@ static hm_status ip_lintrans_multi(hm_ctx *c, const char *what, const hm_ip_lint
   for (uint32_t e = 0; !null && id && e < G * n; ++e)
     if (d->addend_limbs[e % n] != HM_NO_LIMB) { idPt.push_back(id->id_pt_limbs[e]); add1Out.push_back(id->addend1_out_limbs[e]); }
   hm_status st;
-  std::vector<IpOperand> ins = {{"a digit (x)", d->x, d->x_limbs, n * T}, {"a key limb-poly (y)", d->y, d->y_limbs, R * n * 2 * T},
+  std::vector<Operand> ins = {{"a digit (x)", d->x, d->x_limbs, n * T}, {"a key limb-poly (y)", d->y, d->y_limbs, R * n * 2 * T},
                                 {"a plaintext limb-poly (pt)", d->pt, d->pt_limbs, G * R * n}};
-  IpOperand out1 = {"", nullptr, nullptr, 0};
+  Operand out1 = {"", nullptr, nullptr, 0};
   if (id && !null) {
     ins.push_back({"an identity plaintext limb-poly (pt)", d->pt, idPt.data(), (uint32_t)idPt.size()});
     ins.push_back({"the second addend source", id->addend1, add1Src.data(), (uint32_t)add1Src.size()});
@@ -2406,7 +2298,7 @@ static hm_status ip_rotsum(hm_ctx *c, const char *what, const hm_ip_rotsum_desc 
     if (in->addend_init_limbs[i] != HM_NO_LIMB) addInit.push_back(in->addend_init_limbs[i]);
   }
   hm_status st;
-  std::vector<IpOperand> ins = {{"a digit (x)", d->x, d->x_limbs, G * n * T}, {"a key limb-poly (y)", d->y, d->y_limbs, G * n * 2 * T}};
+  std::vector<Operand> ins = {{"a digit (x)", d->x, d->x_limbs, G * n * T}, {"a key limb-poly (y)", d->y, d->y_limbs, G * n * 2 * T}};
   if (in && !null) {
     ins.push_back({"an initial sum (init)", in->init, in->init_limbs, n * 2});
     ins.push_back({"an initial addend sum", d->addend, addInit.data(), (uint32_t)addInit.size()});

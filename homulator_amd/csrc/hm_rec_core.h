@@ -1,0 +1,456 @@
+// hm_rec_core.h — the record-table element-wise kernels: hm_tensor_dot, hm_tensor_square, hm_lincomb, hm_tensor_muladd, hm_reim_split.
+// Per-thread bodies (no cross-thread state) shared by the HIP kernels (hm_backend.hip: k_tensor_dot, k_tensor_square, k_lincomb, k_tensor_muladd,
+// k_reim_split) and the host emulator.
+//
+// A record-table kernel: one record per limb-poly of the call in a device table cached by content, read through the scalar cache (the index is
+// wave-uniform); k_tensor's geometry — a workgroup owns 512 coefficients of one record, a thread an aligned pair (16-byte accesses) — and ONE
+// launch for any number of records.  A record is a multiple of 16 bytes with its 64-bit values at 8-byte offsets; the host builds it with the
+// kernel's own *_fill_recs.
+#pragma once
+#include <cstddef>
+#include "../../include/homulator_hip.h"   // HM_TENSOR_DOT_MAX_TERMS, HM_LINCOMB_MAX_TERMS, HM_TENSOR_MULADD_MAX_ADDENDS
+#include "hm_elem_core.h"                  // HM_CONST_PROB_T, HM_CONST_MODS
+#include "hm_modarith.h"
+#include "hm_ntt_core.h"
+
+// ---- what every record is written and read with
+// host: entry i of a limb list; a null list is the identity
+inline uint32_t hm_rec_limb(const uint32_t *l, uint32_t i) { return l ? l[i] : i; }
+// host: a 64-bit value into two words of a record
+inline void hm_rec_put64(uint32_t *r, uint64_t v) { r[0] = (uint32_t)v; r[1] = (uint32_t)(v >> 32); }
+// the 64-bit value in words w, w + 1 of a record
+template <class REC>
+HM_HD uint64_t hm_rec64(REC rec, uint32_t w) { return (uint64_t)rec[w] | ((uint64_t)rec[w + 1] << 32); }
+// the byte offset, inside every limb-poly, of the pair that thread tid of the workgroup of chunk `chunk` owns: coefficients chunk * 512 + 2 tid, + 1
+HM_HD uint32_t hm_rec_lane_bytes(uint32_t chunk, uint32_t tid) { return (chunk * 512u + 2u * tid) << 3; }
+
+// hipcc sinks loads to their first use; this keeps what was issued above it above the arithmetic below it (no instruction is emitted)
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(HM_ABL_DOT_NOPIN)   // (timing-only ablation: the loads where hipcc puts them)
+#define HM_DOT_ISSUED() __builtin_amdgcn_sched_barrier(0)
+#else
+#define HM_DOT_ISSUED() ((void)0)
+#endif
+
+// ---- the term loop of the kernels that sum a run-time number of terms (pairs of hm_tensor_dot, terms of hm_lincomb, addends of hm_tensor_muladd)
+// term_at(t): the record words of term t; ld(l): the loads of the term with words l, issued; acc(p): its products into the sums.  Software-
+// pipelined by hand: two terms per round in two named register sets p0, p1 (no copy between them), the loads of term t + 1 issued before the
+// products of term t are formed, and the record words of a term requested a step before its loads.  The index of that request is clamped to the
+// last term, so no word beyond the record is ever read (term_at is never called with t >= T, nor at all for T = 0).
+// On entry terms [0, t) are issued: p0 holds the loads of term t - 1, its products still to be formed (have_p0; false only for t = T = 0, a sum
+// of no terms), and l = the words of term min(t, T - 1).  An odd number of terms left runs one more behind the rounds; none left (t = T) runs no
+// round at all.  Every branch is wave-uniform.
+template <class L, class P, class TermAt, class Ld, class Acc>
+HM_HD void hm_term_rounds(uint32_t t, uint32_t T, bool have_p0, L l, P p0, TermAt term_at, Ld ld, Acc acc) {
+  P p1;
+#pragma unroll 1
+  for (; t + 1 < T; t += 2) {
+    p1 = ld(l);                                   // term t
+    l = term_at(t + 1);
+    HM_DOT_ISSUED();
+    acc(p0);
+    p0 = ld(l);                                   // term t + 1
+    l = term_at(t + 2 < T ? t + 2 : T - 1);
+    HM_DOT_ISSUED();
+    acc(p1);
+  }
+  if (t < T) {
+    p1 = ld(l);
+    HM_DOT_ISSUED();
+    acc(p0);
+    acc(p1);
+  } else if (have_p0) {
+    acc(p0);
+  }
+}
+
+// ---- Sum of T tensor products in one pass over the 4T inputs (hm_tensor_dot; HDOT):
+//   d0 = sum_t a_t b_t,  d1 = sum_t (a_t d_t + c_t b_t),  d2 = sum_t c_t d_t      with a_t = c00, b_t = c10, c_t = c01, d_t = c11 of pair t.
+// The raw 64 x 64 products are summed in three 128-bit accumulators per coefficient and each accumulator is reduced ONCE: T <= HM_DOT_MAX_TERMS = 16
+// pairs put 2T <= 32 products below 2^120 into d1's, a sum below 2^125, and hm_barrett_wide takes any 128-bit value.  One form on both arithmetic
+// back-ends: the launch streams 4T + 3 limb-polys per record and does about ten multiplies per loaded word.
+#define HM_DOT_MAX_TERMS HM_TENSOR_DOT_MAX_TERMS
+static_assert(HM_DOT_MAX_TERMS <= 16, "d1's accumulator: 2T products below 2^120 must stay below 2^128");
+// a record = HM_DOT_REC_WORDS(T) 32-bit words: modulus id, the limbs of d0, d1, d2, then (a, b, c, d) of every pair; a multiple of 16 bytes
+#define HM_DOT_REC_WORDS(T) (4u + 4u * (T))
+struct HmTensorDotArgs {
+  const uint64_t *a, *b, *c, *d;
+  uint64_t *o0, *o1, *o2;
+  const HmMod *mods;
+  const uint32_t *rec;   // device, [n_limbs][HM_DOT_REC_WORDS(n_terms)]
+  uint32_t logN, n_limbs, n_terms;
+};
+// The records of n entries from the entry point's limb lists (a .. d: [n][T], o0 .. o2: [n]).  Host side.
+inline void hm_tensor_dot_fill_recs(uint32_t *rec, const uint32_t *la, const uint32_t *lb, const uint32_t *lc, const uint32_t *ld, const uint32_t *l0,
+                                    const uint32_t *l1, const uint32_t *l2, const uint32_t *mod_ids, uint32_t n, uint32_t T) {
+  for (uint32_t i = 0; i < n; ++i) {
+    uint32_t *r = rec + (size_t)i * HM_DOT_REC_WORDS(T);
+    r[0] = mod_ids[i]; r[1] = hm_rec_limb(l0, i); r[2] = hm_rec_limb(l1, i); r[3] = hm_rec_limb(l2, i);
+    for (uint32_t t = 0; t < T; ++t) {
+      const uint32_t e = i * T + t;
+      r[4 + 4 * t] = hm_rec_limb(la, e); r[5 + 4 * t] = hm_rec_limb(lb, e); r[6 + 4 * t] = hm_rec_limb(lc, e); r[7 + 4 * t] = hm_rec_limb(ld, e);
+    }
+  }
+}
+struct HmDotAcc {   // one coefficient's three sums
+  hm_u128 d0, d1, d2;
+};
+HM_HD void hm_tensor_dot_acc(HmDotAcc &s, uint64_t a, uint64_t b, uint64_t c, uint64_t d) {
+  s.d0 += (hm_u128)a * b;
+  s.d1 += (hm_u128)a * d;
+  s.d1 += (hm_u128)c * b;
+  s.d2 += (hm_u128)c * d;
+}
+struct HmDotPair {   // the aligned pair of coefficients a thread owns, of the four operands of one pair of ciphertexts
+  uint64_t a[2], b[2], c[2], d[2];
+};
+struct HmDotLimbs {   // the (a, b, c, d) limbs of one pair: four words of the record
+  uint32_t a, b, c, d;
+};
+template <class REC>
+HM_HD HmDotLimbs hm_tensor_dot_limbs(REC rec, uint32_t t) {
+  return HmDotLimbs{rec[4 + 4 * t], rec[5 + 4 * t], rec[6 + 4 * t], rec[7 + 4 * t]};
+}
+// four 16-byte loads from wave-uniform bases at one lane offset
+HM_HD HmDotPair hm_tensor_dot_ld(const HmTensorDotArgs &g, const HmDotLimbs &l, size_t N, uint32_t lane_bytes) {
+  HmDotPair v;
+  hm_bld2(g.a + l.a * N, lane_bytes, v.a[0], v.a[1]);
+  hm_bld2(g.b + l.b * N, lane_bytes, v.b[0], v.b[1]);
+  hm_bld2(g.c + l.c * N, lane_bytes, v.c[0], v.c[1]);
+  hm_bld2(g.d + l.d * N, lane_bytes, v.d[0], v.d[1]);
+  return v;
+}
+HM_HD void hm_tensor_dot_acc2(HmDotAcc (&s)[2], const HmDotPair &v) {
+  hm_tensor_dot_acc(s[0], v.a[0], v.b[0], v.c[0], v.d[0]);
+  hm_tensor_dot_acc(s[1], v.a[1], v.b[1], v.c[1], v.d[1]);
+}
+// thread tid of the workgroup that owns chunk `chunk` of record `entry`: 4T 16-byte loads (hm_term_rounds behind the loads of pair 0), three stores
+HM_HD void hm_tensor_dot_thread(const HmTensorDotArgs &g, uint32_t entry, uint32_t chunk, uint32_t tid) {
+  const size_t N = (size_t)1 << g.logN;
+  const uint32_t T = g.n_terms, lane_bytes = hm_rec_lane_bytes(chunk, tid);
+  const auto rec = HM_CONST_PROB_T(uint32_t, g.rec) + (size_t)entry * HM_DOT_REC_WORDS(T);
+  const HmMod m = HM_CONST_MODS(g.mods)[rec[0]];
+  HmDotAcc s[2] = {{0, 0, 0}, {0, 0, 0}};
+  const auto term_at = [&](uint32_t t) { return hm_tensor_dot_limbs(rec, t); };
+  const auto ld = [&](const HmDotLimbs &l) { return hm_tensor_dot_ld(g, l, N, lane_bytes); };
+  const HmDotPair p0 = ld(term_at(0));
+  hm_term_rounds(1, T, true, term_at(T > 1 ? 1u : 0u), p0, term_at, ld, [&](const HmDotPair &v) { hm_tensor_dot_acc2(s, v); });
+  hm_bst2(g.o0 + rec[1] * N, lane_bytes, hm_barrett_wide(s[0].d0, m), hm_barrett_wide(s[1].d0, m));
+  hm_bst2(g.o1 + rec[2] * N, lane_bytes, hm_barrett_wide(s[0].d1, m), hm_barrett_wide(s[1].d1, m));
+  hm_bst2(g.o2 + rec[3] * N, lane_bytes, hm_barrett_wide(s[0].d2, m), hm_barrett_wide(s[1].d2, m));
+}
+
+// ---- Scaled square of ONE ciphertext plus a constant, in one pass over its two polynomials (hm_tensor_square; HSQUARE):
+//   d0 = s a a + k,  d1 = 2 s a c,  d2 = s c c      with a = c0, c = c1, s in [1, q) and k in [0, q) per entry, every residue canonical.
+// The tensor product of a ciphertext with itself needs two loads and five products where hm_tensor_one, fed the same operands twice, takes
+// four and six; the scalar and the constant are linear and act in front of the key switch, so they are applied here, in registers.
+// A record = 64 bytes.  The per-entry constants are stored in the form the arithmetic takes (hm_tensor_square_fill_recs).  mont32: scale =
+// s 2^128 mod q, which takes the place of m.r128 in the step to Montgomery form, so that the scalar costs no product at all.  generic: scale = s
+// with its Shoup companion scale_s = floor(s 2^64 / q): a and c are multiplied by s once, by two Shoup products, in front of the three Barrett
+// products.  addend = k on both.
+struct HmTensorSqRec {
+  uint32_t mod, a, c, o0, o1, o2;
+  uint32_t scaled, pad;   // generic: s != 1 (a limb-uniform branch skips the two products by s)
+  uint64_t scale, scale_s, addend, pad1;
+};
+static_assert(sizeof(HmTensorSqRec) == 64 && offsetof(HmTensorSqRec, scale) == 32, "HmTensorSqRec: layout");
+struct HmTensorSqArgs {
+  const uint64_t *a, *c;
+  uint64_t *o0, *o1, *o2;
+  const HmMod *mods;
+  const HmTensorSqRec *rec;   // device, [n_limbs]
+  uint32_t logN, n_limbs;
+};
+// host: the record form of the scalar s in [1, q)
+inline uint64_t hm_tensor_square_scale(uint64_t s, uint64_t q) { return HM_GENERIC ? s : hm_to_mont(hm_to_mont(s, q), q); }
+// The records of n entries from the entry point's limb lists and constants (scale null: 1, addend null: 0; both already checked: reduced,
+// scale != 0); q[i] = the modulus of entry i.  Host side.
+inline void hm_tensor_square_fill_recs(HmTensorSqRec *rec, const uint32_t *la, const uint32_t *lc, const uint32_t *l0, const uint32_t *l1, const uint32_t *l2,
+                                       const uint32_t *mod_ids, const uint64_t *q, uint32_t n, const uint64_t *scale, const uint64_t *addend) {
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint64_t s = scale ? scale[i] : 1;
+    rec[i] = HmTensorSqRec{mod_ids[i], hm_rec_limb(la, i), hm_rec_limb(lc, i), hm_rec_limb(l0, i), hm_rec_limb(l1, i), hm_rec_limb(l2, i),
+                           s != 1 ? 1u : 0u, 0u, hm_tensor_square_scale(s, q[i]), HM_GENERIC ? hm_shoup_companion(s, q[i]) : 0, addend ? addend[i] : 0, 0};
+  }
+}
+// mont32, with the bound of hm_mont_acc (v <= floor(x wt / 2^64) + q + h + 1, h = q >> 32 < 2^28, for x < 2^63 and no sum above 2^64) and the
+// largest modulus the back-end accepts, q < 2^60:
+//   at, ct   = a, c (x) st with a, c, st < q: floor(q q / 2^64) < q / 16, so at, ct < 1.0625 q + 2^28 + 1 < 2^61  (a s 2^64 mod q + {0, q})
+//   a (x) at, c (x) at, c (x) ct with the left operand below q: floor(q (1.0625 q + 2^28 + 1) / 2^64) < 0.07 q, so each is below 1.07 q + 2^28 + 1
+//            < 2 q: ONE conditional subtraction leaves the canonical residue (s a a, s a c, s c c: x wt 2^-64 with wt = y s 2^64)
+//   2 x with x < q is below 2 q, and d0 + k with d0, k < q is below 2 q: one conditional subtraction each
+//   inside hm_mont_acc, wt < 2^61: b0 w1 < 2^61, b1 w0 < 2^60, (~P0) h < 2^60, cc < 2^60 + 2^33, a sum below 2^63.
+// generic: as = s a and cs = s c by the exact Shoup product (canonical, for any 64-bit operand), then three Barrett products of canonical operands.
+HM_HD void hm_tensor_square_one(uint64_t a, uint64_t c, uint64_t scale, uint64_t scale_s, uint32_t scaled, uint64_t addend, const HmMod &m, uint64_t &d0,
+                                uint64_t &d1, uint64_t &d2) {
+#if HM_GENERIC
+  uint64_t as = a, cs = c;
+  if (scaled) {   // (limb-uniform)
+    as = hm_shoup(a, scale, scale_s, m.q);
+    cs = hm_shoup(c, scale, scale_s, m.q);
+  }
+  d0 = hm_mulmod(as, a, m);
+  const uint64_t x = hm_mulmod(as, c, m);
+  d2 = hm_mulmod(cs, c, m);
+  d1 = hm_csub(x + x, m.q);
+  d0 = hm_csub(d0 + addend, m.q);
+#else
+  (void)scaled; (void)scale_s;
+  const HmBflyMod bm = hm_bfly_mod(m.q);
+  const uint64_t at = hm_mont_acc(0, a, scale, bm), ct = hm_mont_acc(0, c, scale, bm);   // below 1.0625 q + 2^28 + 1
+  d0 = hm_csub_neg(hm_mont_acc(0, a, at, bm), bm.nq);                                    // lazy: below 1.07 q + 2^28 + 1
+  const uint64_t x = hm_csub_neg(hm_mont_acc(0, c, at, bm), bm.nq);
+  d2 = hm_csub_neg(hm_mont_acc(0, c, ct, bm), bm.nq);
+  d1 = hm_csub_neg(x + x, bm.nq);          // below 2 q
+  d0 = hm_csub_neg(d0 + addend, bm.nq);    // below 2 q
+#endif
+}
+// thread tid of the workgroup that owns chunk `chunk` of record `entry`: two 16-byte loads, three 16-byte stores
+HM_HD void hm_tensor_square_thread(const HmTensorSqArgs &g, uint32_t entry, uint32_t chunk, uint32_t tid) {
+  const size_t N = (size_t)1 << g.logN;
+  const uint32_t lane_bytes = hm_rec_lane_bytes(chunk, tid);
+  const auto r = HM_CONST_PROB_T(HmTensorSqRec, g.rec) + entry;
+  const HmMod m = HM_CONST_MODS(g.mods)[r->mod];
+  const uint64_t scale = r->scale, scale_s = r->scale_s, addend = r->addend;
+  const uint32_t scaled = r->scaled;
+  uint64_t a[2], c[2], d0[2], d1[2], d2[2];
+  hm_bld2(g.a + r->a * N, lane_bytes, a[0], a[1]);
+  hm_bld2(g.c + r->c * N, lane_bytes, c[0], c[1]);
+  hm_tensor_square_one(a[0], c[0], scale, scale_s, scaled, addend, m, d0[0], d1[0], d2[0]);
+  hm_tensor_square_one(a[1], c[1], scale, scale_s, scaled, addend, m, d0[1], d1[1], d2[1]);
+  hm_bst2(g.o0 + r->o0 * N, lane_bytes, d0[0], d0[1]);
+  hm_bst2(g.o1 + r->o1 * N, lane_bytes, d1[0], d1[1]);
+  hm_bst2(g.o2 + r->o2 * N, lane_bytes, d2[0], d2[1]);
+}
+
+// ---- Sum of T scaled polynomials plus a constant in one pass over the T inputs (hm_lincomb; HLINCOMB):
+//   out = sum_t s_t x_t + k      with s_t, k in [0, q) per record and every x_t canonical.
+// The raw 64 x 64 products are summed in ONE 128-bit accumulator per coefficient, k is added, and the accumulator is reduced once, as
+// hm_tensor_dot_acc does: T <= HM_LINCOMB_MAX_TERMS = 16 products below 2^120 are below 2^124, plus k < 2^60 below 2^125, and hm_barrett_wide
+// takes any 128-bit value.  The result is the canonical residue of the exact integer sum, hence bit-identical to the chain of MUL_CONST, ADD
+// and ADD_CONST.  One form on both arithmetic back-ends: T + 1 limb-polys per record and one wide multiply per loaded word.
+static_assert(HM_LINCOMB_MAX_TERMS == 16, "the accumulator: 16 products below 2^120 plus k below 2^60 stay below 2^125");
+// a record = HM_LINCOMB_REC_WORDS(T) 32-bit words: (modulus id, output limb, T, 0), (k: 2 words, 0, 0), then per term (input limb, 0, s_t: 2 words)
+#define HM_LINCOMB_REC_WORDS(T) (8u + 4u * (T))
+struct HmLincombArgs {
+  const uint64_t *in;
+  uint64_t *out;
+  const HmMod *mods;
+  const uint32_t *rec;   // device, [n_limbs][HM_LINCOMB_REC_WORDS(n_terms)]
+  uint32_t logN, n_limbs, n_terms;
+};
+// The records of n entries from the entry point's lists (in: [n][T], out: [n]) and constants (scale: [n][T]; addend: [n] or null = 0; both
+// already checked: reduced).  Host side.
+inline void hm_lincomb_fill_recs(uint32_t *rec, const uint32_t *li, const uint32_t *lo, const uint32_t *mod_ids, uint32_t n, uint32_t T,
+                                 const uint64_t *scale, const uint64_t *addend) {
+  for (uint32_t i = 0; i < n; ++i) {
+    uint32_t *r = rec + (size_t)i * HM_LINCOMB_REC_WORDS(T);
+    r[0] = mod_ids[i]; r[1] = hm_rec_limb(lo, i); r[2] = T; r[3] = 0;
+    hm_rec_put64(r + 4, addend ? addend[i] : 0); r[6] = 0; r[7] = 0;
+    for (uint32_t t = 0; t < T; ++t) {
+      const uint32_t e = i * T + t;
+      r[8 + 4 * t] = hm_rec_limb(li, e); r[9 + 4 * t] = 0; hm_rec_put64(r + 10 + 4 * t, scale[e]);
+    }
+  }
+}
+struct HmLincombTerm {   // the (input limb, scalar) of one term: four words of the record
+  uint32_t limb;
+  uint64_t s;
+};
+template <class REC>
+HM_HD HmLincombTerm hm_lincomb_term(REC rec, uint32_t t) {
+  return HmLincombTerm{rec[8 + 4 * t], hm_rec64(rec, 10 + 4 * t)};
+}
+struct HmLincombPair {   // the aligned pair of coefficients a thread owns of one term, with the term's scalar
+  uint64_t x[2], s;
+};
+// one 16-byte load from a wave-uniform base at the lane's offset
+HM_HD HmLincombPair hm_lincomb_ld(const HmLincombArgs &g, const HmLincombTerm &l, size_t N, uint32_t lane_bytes) {
+  HmLincombPair v;
+  hm_bld2(g.in + l.limb * N, lane_bytes, v.x[0], v.x[1]);
+  v.s = l.s;
+  return v;
+}
+HM_HD void hm_lincomb_acc2(hm_u128 (&s)[2], const HmLincombPair &v) {
+  s[0] += (hm_u128)v.x[0] * v.s;
+  s[1] += (hm_u128)v.x[1] * v.s;
+}
+// thread tid of the workgroup that owns chunk `chunk` of record `entry`: T 16-byte loads (hm_term_rounds behind the load of term 0), one store
+HM_HD void hm_lincomb_thread(const HmLincombArgs &g, uint32_t entry, uint32_t chunk, uint32_t tid) {
+  const size_t N = (size_t)1 << g.logN;
+  const uint32_t T = g.n_terms, lane_bytes = hm_rec_lane_bytes(chunk, tid);
+  const auto rec = HM_CONST_PROB_T(uint32_t, g.rec) + (size_t)entry * HM_LINCOMB_REC_WORDS(T);
+  const HmMod m = HM_CONST_MODS(g.mods)[rec[0]];
+  const uint64_t k = hm_rec64(rec, 4);
+  hm_u128 s[2] = {0, 0};
+  const auto term_at = [&](uint32_t t) { return hm_lincomb_term(rec, t); };
+  const auto ld = [&](const HmLincombTerm &l) { return hm_lincomb_ld(g, l, N, lane_bytes); };
+  const HmLincombPair p0 = ld(term_at(0));
+  hm_term_rounds(1, T, true, term_at(T > 1 ? 1u : 0u), p0, term_at, ld, [&](const HmLincombPair &v) { hm_lincomb_acc2(s, v); });
+  hm_bst2(g.out + rec[1] * N, lane_bytes, hm_barrett_wide(s[0] + k, m), hm_barrett_wide(s[1] + k, m));
+}
+
+// ---- Scaled tensor product of TWO ciphertexts plus a linear combination of A further ciphertexts plus a constant, in one pass over the 4 + 2A
+// inputs (hm_tensor_muladd; HMULADD):
+//   d0 = s a b + sum_t u_t x_t + k,  d1 = s (a d + c b) + sum_t u_t y_t,  d2 = s c d
+// with hm_tensor_one's roles (a = c00, b = c10, c = c01, d = c11), x_t / y_t = c0 / c1 of addend t, s in [1, q), u_t and k in [0, q) per record and
+// every input canonical.  One form on both arithmetic back-ends: a and c are brought to as = s a mod q and cs = s c mod q, canonical, by the
+// exact Shoup product (hm_shoup: any 64-bit operand, w < q) behind a limb-uniform branch that s = 1 skips; then the raw 64 x 64 products as b,
+// as d + cs b, cs d and u_t x_t, u_t y_t are summed in three 128-bit accumulators per coefficient, k is added to d0's, and each accumulator is
+// reduced ONCE by hm_barrett_wide, which takes any 128-bit value.  Every factor is below q < 2^60, so a product is below 2^120: d1's accumulator
+// holds 2 + A <= 10 of them, below 10 * 2^120 < 2^124; d0's 1 + A <= 9 and k < 2^60, below 2^124 as well; d2's one.  The result is the canonical
+// residue of the exact integer sum, and s a b = (s a mod q) b mod q, hence bit-identical to hm_tensor followed by MUL_CONST, MUL_CONST + ADD per
+// addend and ADD_CONST.
+#define HM_MULADD_MAX_ADDENDS HM_TENSOR_MULADD_MAX_ADDENDS
+static_assert(HM_MULADD_MAX_ADDENDS == 8, "d1's accumulator: 2 + A <= 10 products below 2^120 stay below 2^124; d0's: 1 + A products plus k < 2^60 as well");
+// a record = HM_MULADD_REC_WORDS(A) 32-bit words:
+//   0: modulus id   1..4: the limbs of a, b, c, d   5..7: the limbs of d0, d1, d2   8: A   9: s != 1
+//   10, 11: s   12, 13: its Shoup companion floor(s 2^64 / q)   14, 15: k
+// then per addend (limb of x_t, limb of y_t, u_t: 2 words)
+#define HM_MULADD_REC_HEAD 16u
+#define HM_MULADD_REC_WORDS(A) (HM_MULADD_REC_HEAD + 4u * (A))
+struct HmTensorMulAddArgs {
+  const uint64_t *a, *b, *c, *d, *x;
+  uint64_t *o0, *o1, *o2;
+  const HmMod *mods;
+  const uint32_t *rec;   // device, [n_limbs][HM_MULADD_REC_WORDS(n_addends)]
+  uint32_t logN, n_limbs, n_addends;
+};
+// The records of n entries from the entry point's limb lists (a .. d, o0 .. o2: [n]; lx0, lx1: [n][A], never null) and constants (scale: [n] or
+// null = 1; add_scale: [n][A]; addend: [n] or null = 0; all already checked: reduced, scale != 0); q[i] = the modulus of entry i.  Host side.
+inline void hm_tensor_muladd_fill_recs(uint32_t *rec, const uint32_t *la, const uint32_t *lb, const uint32_t *lc, const uint32_t *ld, const uint32_t *lx0,
+                                       const uint32_t *lx1, const uint32_t *l0, const uint32_t *l1, const uint32_t *l2, const uint32_t *mod_ids,
+                                       const uint64_t *q, uint32_t n, uint32_t A, const uint64_t *scale, const uint64_t *add_scale, const uint64_t *addend) {
+  for (uint32_t i = 0; i < n; ++i) {
+    uint32_t *r = rec + (size_t)i * HM_MULADD_REC_WORDS(A);
+    const uint64_t s = scale ? scale[i] : 1;
+    r[0] = mod_ids[i]; r[1] = hm_rec_limb(la, i); r[2] = hm_rec_limb(lb, i); r[3] = hm_rec_limb(lc, i); r[4] = hm_rec_limb(ld, i);
+    r[5] = hm_rec_limb(l0, i); r[6] = hm_rec_limb(l1, i); r[7] = hm_rec_limb(l2, i); r[8] = A; r[9] = s != 1 ? 1u : 0u;
+    hm_rec_put64(r + 10, s); hm_rec_put64(r + 12, hm_shoup_companion(s, q[i])); hm_rec_put64(r + 14, addend ? addend[i] : 0);
+    for (uint32_t t = 0; t < A; ++t) {
+      const uint32_t e = i * A + t;
+      uint32_t *w = r + HM_MULADD_REC_HEAD + 4 * t;
+      w[0] = lx0[e]; w[1] = lx1[e]; hm_rec_put64(w + 2, add_scale[e]);
+    }
+  }
+}
+struct HmMulAddTerm {   // the (limb of x_t, limb of y_t, scalar) of one addend: four words of the record
+  uint32_t x, y;
+  uint64_t u;
+};
+// the words of addend t; the caller clamps t to the last addend, and a record without addends hands out words of its header instead (never used):
+// always inside the record
+template <class REC>
+HM_HD HmMulAddTerm hm_muladd_term(REC rec, uint32_t A, uint32_t t) {
+  const uint32_t w = A ? HM_MULADD_REC_HEAD + 4 * t : HM_MULADD_REC_HEAD - 4;
+  return HmMulAddTerm{rec[w], rec[w + 1], hm_rec64(rec, w + 2)};
+}
+struct HmMulAddPair {   // the aligned pair of coefficients a thread owns of both components of one addend, with the addend's scalar
+  uint64_t x[2], y[2], u;
+};
+// two 16-byte loads from wave-uniform bases at the lane's offset
+HM_HD HmMulAddPair hm_muladd_ld(const HmTensorMulAddArgs &g, const HmMulAddTerm &l, size_t N, uint32_t lane_bytes) {
+  HmMulAddPair v;
+  hm_bld2(g.x + l.x * N, lane_bytes, v.x[0], v.x[1]);
+  hm_bld2(g.x + l.y * N, lane_bytes, v.y[0], v.y[1]);
+  v.u = l.u;
+  return v;
+}
+HM_HD void hm_muladd_acc2(HmDotAcc (&s)[2], const HmMulAddPair &v) {
+  s[0].d0 += (hm_u128)v.x[0] * v.u;
+  s[0].d1 += (hm_u128)v.y[0] * v.u;
+  s[1].d0 += (hm_u128)v.x[1] * v.u;
+  s[1].d1 += (hm_u128)v.y[1] * v.u;
+}
+// the scaled product of one coefficient into fresh accumulators
+HM_HD void hm_muladd_product(HmDotAcc &s, uint64_t a, uint64_t b, uint64_t c, uint64_t d, uint64_t scale, uint64_t scale_s, uint32_t scaled, uint64_t k,
+                             const HmMod &m) {
+  uint64_t as = a, cs = c;
+  if (scaled) {   // (limb-uniform)
+    as = hm_shoup(a, scale, scale_s, m.q);
+    cs = hm_shoup(c, scale, scale_s, m.q);
+  }
+  s.d0 = (hm_u128)as * b + k;
+  s.d1 = (hm_u128)as * d + (hm_u128)cs * b;
+  s.d2 = (hm_u128)cs * d;
+}
+// thread tid of the workgroup that owns chunk `chunk` of record `entry`: four 16-byte loads for the product, two per addend, three 16-byte stores.
+// The product stands in the place of hm_term_rounds' first term: the loads of addend 0 are issued under it, before its products are formed
+// (hm_muladd_term: always inside the record), and the rounds go on from addend 1.  A = 0 and A = 1 run no round.
+HM_HD void hm_tensor_muladd_thread(const HmTensorMulAddArgs &g, uint32_t entry, uint32_t chunk, uint32_t tid) {
+  const size_t N = (size_t)1 << g.logN;
+  const uint32_t A = g.n_addends, lane_bytes = hm_rec_lane_bytes(chunk, tid);
+  const auto rec = HM_CONST_PROB_T(uint32_t, g.rec) + (size_t)entry * HM_MULADD_REC_WORDS(A);
+  const HmMod m = HM_CONST_MODS(g.mods)[rec[0]];
+  const uint32_t scaled = rec[9];
+  const uint64_t scale = hm_rec64(rec, 10), scale_s = hm_rec64(rec, 12), k = hm_rec64(rec, 14);
+  const auto term_at = [&](uint32_t t) { return hm_muladd_term(rec, A, t); };
+  const auto ld = [&](const HmMulAddTerm &l) { return hm_muladd_ld(g, l, N, lane_bytes); };
+  HmDotPair v;
+  hm_bld2(g.a + rec[1] * N, lane_bytes, v.a[0], v.a[1]);
+  hm_bld2(g.b + rec[2] * N, lane_bytes, v.b[0], v.b[1]);
+  hm_bld2(g.c + rec[3] * N, lane_bytes, v.c[0], v.c[1]);
+  hm_bld2(g.d + rec[4] * N, lane_bytes, v.d[0], v.d[1]);
+  HmMulAddTerm l = term_at(0);
+  HmMulAddPair p0;   // (A = 0 leaves it unwritten: hm_term_rounds, handed it by value, then reads none of it; zeroing it costs nine instructions)
+  if (A > 0) {   // (wave-uniform) addend 0 under the product
+    p0 = ld(l);
+    l = term_at(A > 1 ? 1u : 0u);
+  }
+  HM_DOT_ISSUED();
+  HmDotAcc s[2];
+  hm_muladd_product(s[0], v.a[0], v.b[0], v.c[0], v.d[0], scale, scale_s, scaled, k, m);
+  hm_muladd_product(s[1], v.a[1], v.b[1], v.c[1], v.d[1], scale, scale_s, scaled, k, m);
+  hm_term_rounds(A ? 1u : 0u, A, A > 0, l, p0, term_at, ld, [&](const HmMulAddPair &p) { hm_muladd_acc2(s, p); });
+  hm_bst2(g.o0 + rec[5] * N, lane_bytes, hm_barrett_wide(s[0].d0, m), hm_barrett_wide(s[1].d0, m));
+  hm_bst2(g.o1 + rec[6] * N, lane_bytes, hm_barrett_wide(s[0].d1, m), hm_barrett_wide(s[1].d1, m));
+  hm_bst2(g.o2 + rec[7] * N, lane_bytes, hm_barrett_wide(s[0].d2, m), hm_barrett_wide(s[1].d2, m));
+}
+
+// ---- Real and imaginary parts of the slots from a polynomial x and its conjugate y in one pass over both (hm_reim_split; HREIM):
+//   re = x + y,   im = U (.) (x - y)
+// with U the evaluation form of -X^(N/2).  Entry e of a limb-poly holds the value at psi^(2 brev(e) + 1); for e < N/2 the exponent is 1 mod 4, for
+// e >= N/2 it is 3 mod 4, and psi^(N/2) has order 4: U is the constant w = -psi^(N/2) mod q on entries [0, N/2) and q - w on [N/2, N), w^2 = -1.
+// A workgroup's 512 coefficients lie in one half (N >= 1024), so the choice is uniform per workgroup: chunk < N/1024 takes w.
+// One form on both arithmetic back-ends, every input canonical (< q < 2^60):
+//   re = hm_addmod(x, y): x + y < 2q < 2^61, one conditional subtraction, canonical;
+//   d  = hm_submod(x, y): in [0, q), canonical;
+//   im = hm_shoup(d, u, us, q): exact for any 64-bit d and u < q with us = floor(u 2^64 / q), canonical (hm_modarith.h).
+// The record carries w and ws = floor(w 2^64 / q) only.  For u = q - w: (q - w) 2^64 / q = 2^64 - w 2^64 / q, and w 2^64 / q is no integer (q is
+// an odd prime, 0 < w < q), so floor((q - w) 2^64 / q) = 2^64 - 1 - ws = ~ws, exactly.
+// Bit-identical to HM_OP_ADD, HM_OP_SUB and HM_OP_MUL by the stored U: each of those yields the canonical residue of the same exact value.
+// a record = HM_REIM_REC_WORDS 32-bit words (48 bytes):
+//   0: modulus id   1, 2: the limbs of x, y   3, 4: the limbs of re, im   5..7: 0   8, 9: w   10, 11: ws
+#define HM_REIM_REC_WORDS 12u
+struct HmReimArgs {
+  const uint64_t *x, *y;
+  uint64_t *o_re, *o_im;
+  const HmMod *mods;
+  const uint32_t *rec;   // device, [n_limbs][HM_REIM_REC_WORDS]
+  uint32_t logN, n_limbs;
+};
+// The records of n entries from the entry point's limb lists; w[i] = -psi^(N/2) mod q[i], q[i] = the modulus of entry i.  Host side.
+inline void hm_reim_fill_recs(uint32_t *rec, const uint32_t *lx, const uint32_t *ly, const uint32_t *lre, const uint32_t *lim, const uint32_t *mod_ids,
+                              const uint64_t *w, const uint64_t *q, uint32_t n) {
+  for (uint32_t i = 0; i < n; ++i) {
+    uint32_t *r = rec + (size_t)i * HM_REIM_REC_WORDS;
+    r[0] = mod_ids[i]; r[1] = hm_rec_limb(lx, i); r[2] = hm_rec_limb(ly, i); r[3] = hm_rec_limb(lre, i); r[4] = hm_rec_limb(lim, i);
+    r[5] = r[6] = r[7] = 0;
+    hm_rec_put64(r + 8, w[i]); hm_rec_put64(r + 10, hm_shoup_companion(w[i], q[i]));
+  }
+}
+// thread tid of the workgroup that owns chunk `chunk` of record `entry`: two 16-byte loads and two 16-byte stores.  chunk < N / 512 (the launch
+// has n N / 512 workgroups), so the last byte touched is N * 8 - 1 of each limb-poly.
+HM_HD void hm_reim_thread(const HmReimArgs &g, uint32_t entry, uint32_t chunk, uint32_t tid) {
+  const size_t N = (size_t)1 << g.logN;
+  const uint32_t lane_bytes = hm_rec_lane_bytes(chunk, tid);
+  const auto rec = HM_CONST_PROB_T(uint32_t, g.rec) + (size_t)entry * HM_REIM_REC_WORDS;
+  const uint64_t q = HM_CONST_MODS(g.mods)[rec[0]].q;
+  const uint64_t w = hm_rec64(rec, 8), ws = hm_rec64(rec, 10);
+  const bool first = chunk < (uint32_t)(N >> 10);   // (workgroup-uniform) entries [0, N/2)
+  const uint64_t u = first ? w : q - w, us = first ? ws : ~ws;
+  uint64_t x[2], y[2];
+  hm_bld2(g.x + rec[1] * N, lane_bytes, x[0], x[1]);
+  hm_bld2(g.y + rec[2] * N, lane_bytes, y[0], y[1]);
+  hm_bst2(g.o_re + rec[3] * N, lane_bytes, hm_addmod(x[0], y[0], q), hm_addmod(x[1], y[1], q));
+  hm_bst2(g.o_im + rec[4] * N, lane_bytes, hm_shoup(hm_submod(x[0], y[0], q), u, us, q), hm_shoup(hm_submod(x[1], y[1], q), u, us, q));
+}

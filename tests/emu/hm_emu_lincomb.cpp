@@ -1,11 +1,11 @@
-// hm_emu_lincomb.cpp — the per-thread core of hm_lincomb (hm_elem_core.h: hm_lincomb_thread and its helpers) on the CPU (TEST INFRASTRUCTURE,
+// hm_emu_lincomb.cpp — the per-thread core of hm_lincomb (hm_rec_core.h: hm_lincomb_thread and its helpers) on the CPU (TEST INFRASTRUCTURE,
 // compiled by tests/test_emu_lincomb.py with g++, once per arithmetic back-end: HM_GENERIC = 0 and -DHM_GENERIC=1).  The same records the entry
 // point builds (hm_lincomb_fill_recs), the same per-modulus constants (hm_params.cpp), every thread of the chosen workgroups one after the other.
 // It is not a CPU backend: the product library never links or calls this.
 #include <cstdint>
 #include <stdexcept>
 #include <vector>
-#include "../../homulator_amd/csrc/hm_elem_core.h"
+#include "../../homulator_amd/csrc/hm_rec_core.h"
 #include "../../homulator_amd/csrc/hm_params.h"
 
 extern "C" int emu_lincomb_generic() { return HM_GENERIC; }

@@ -1,11 +1,11 @@
-// hm_emu_muladd.cpp — the per-thread core of hm_tensor_muladd (hm_elem_core.h: hm_tensor_muladd_thread and its helpers) on the CPU (TEST
+// hm_emu_muladd.cpp — the per-thread core of hm_tensor_muladd (hm_rec_core.h: hm_tensor_muladd_thread and its helpers) on the CPU (TEST
 // INFRASTRUCTURE, compiled by tests/test_emu_muladd.py with g++, once per arithmetic back-end: HM_GENERIC = 0 and -DHM_GENERIC=1).  The same records
 // the entry point builds (hm_tensor_muladd_fill_recs), the same per-modulus constants (hm_params.cpp), every thread of the chosen workgroups one
 // after the other.  It is not a CPU backend: the product library never links or calls this.
 #include <cstdint>
 #include <stdexcept>
 #include <vector>
-#include "../../homulator_amd/csrc/hm_elem_core.h"
+#include "../../homulator_amd/csrc/hm_rec_core.h"
 #include "../../homulator_amd/csrc/hm_params.h"
 
 extern "C" int emu_muladd_generic() { return HM_GENERIC; }

@@ -1,4 +1,4 @@
-// hm_emu_reim.cpp — the per-thread core of hm_reim_split (hm_elem_core.h: hm_reim_thread) on the CPU (TEST INFRASTRUCTURE, compiled by
+// hm_emu_reim.cpp — the per-thread core of hm_reim_split (hm_rec_core.h: hm_reim_thread) on the CPU (TEST INFRASTRUCTURE, compiled by
 // tests/test_emu_reim.py with g++, once per arithmetic back-end: HM_GENERIC = 0 and -DHM_GENERIC=1).  The same records the entry point builds
 // (hm_reim_fill_recs) with the constant derived as the entry point derives it (w = q - psi^(N/2) from hm::Params::psi), the same per-modulus
 // constants (hm_params.cpp), every thread of the chosen workgroups one after the other.  It is not a CPU backend: the product library never links
@@ -6,7 +6,7 @@
 #include <cstdint>
 #include <stdexcept>
 #include <vector>
-#include "../../homulator_amd/csrc/hm_elem_core.h"
+#include "../../homulator_amd/csrc/hm_rec_core.h"
 #include "../../homulator_amd/csrc/hm_params.h"
 
 extern "C" int emu_reim_generic() { return HM_GENERIC; }

@@ -1,4 +1,4 @@
-"""The per-thread core of hm_tensor_dot (homulator_amd/csrc/hm_elem_core.h: hm_tensor_dot_thread) on the CPU against Python integers, no GPU:
+"""The per-thread core of hm_tensor_dot (homulator_amd/csrc/hm_rec_core.h: hm_tensor_dot_thread) on the CPU against Python integers, no GPU:
 tests/emu/hm_emu_dot.cpp compiles the device header with g++, once per arithmetic back-end (HM_GENERIC 0 and 1, as tests/emu/Makefile defines
 them), and runs every thread of the first and the last workgroup of every record.  T = 16 with every operand q - 1 puts 32 (q - 1)^2 into d1's
 128-bit accumulator: the largest value the wide reduction ever sees."""
@@ -50,9 +50,10 @@ def p(a):
 
 
 @pytest.mark.parametrize("fill", ["q-1", "zero", "random"])
-@pytest.mark.parametrize("T", [1, 2, 16])
+@pytest.mark.parametrize("T", [1, 2, 3, 4, 16])
 def test_core_against_python_integers(emu, moduli, T, fill):
-    """one record per modulus, every limb list a random permutation of its buffer"""
+    """one record per modulus, every limb list a random permutation of its buffer.  The four ways out of the term loop (hm_term_rounds): T = 1 no
+    round and no tail, 2 the tail alone, 3 one round and no tail, 4 one round and the tail; 16 the largest sum"""
     n = len(moduli)
     rng = np.random.default_rng(100 * T + len(fill))
     lists = [rng.permutation(n * T).astype(np.uint32) for _ in range(4)] + [rng.permutation(n).astype(np.uint32) for _ in range(3)]

@@ -1,4 +1,4 @@
-"""The per-thread core of hm_lincomb (homulator_amd/csrc/hm_elem_core.h: hm_lincomb_thread, the kernel of hlincomb) on the CPU, no GPU:
+"""The per-thread core of hm_lincomb (homulator_amd/csrc/hm_rec_core.h: hm_lincomb_thread, the kernel of hlincomb) on the CPU, no GPU:
 tests/emu/hm_emu_lincomb.cpp compiles the device header with g++, once per arithmetic back-end (HM_GENERIC 0 and 1), builds the records as the entry
 point does and runs every thread of the chosen workgroups.  Checked against Python integers: out = sum_t s_t x_t + k mod q.
 T: 1, 2, 3, 16 (no round of the two-term loop, the tail behind it, one round, the most).  Fills: uniform, all 0, all q - 1.  Scalars: 0, 1, q - 1,

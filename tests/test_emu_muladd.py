@@ -1,4 +1,4 @@
-"""The per-thread core of hm_tensor_muladd (homulator_amd/csrc/hm_elem_core.h: hm_tensor_muladd_thread, the kernel of hmuladd) on the CPU, no GPU:
+"""The per-thread core of hm_tensor_muladd (homulator_amd/csrc/hm_rec_core.h: hm_tensor_muladd_thread, the kernel of hmuladd) on the CPU, no GPU:
 tests/emu/hm_emu_muladd.cpp compiles the device header with g++, once per arithmetic back-end (HM_GENERIC 0 and 1), builds the records as the entry
 point does and runs every thread of the chosen workgroups.  Checked against Python integers:
     d0 = s a b + sum_t u_t x_t + k,  d1 = s (a d + c b) + sum_t u_t y_t,  d2 = s c d   mod q.

@@ -1,4 +1,4 @@
-"""The per-thread core of hm_reim_split (homulator_amd/csrc/hm_elem_core.h: hm_reim_thread, the kernel of hreim) on the CPU, no GPU:
+"""The per-thread core of hm_reim_split (homulator_amd/csrc/hm_rec_core.h: hm_reim_thread, the kernel of hreim) on the CPU, no GPU:
 tests/emu/hm_emu_reim.cpp compiles the device header with g++, once per arithmetic back-end (HM_GENERIC 0 and 1), builds the records as the entry
 point does, the constant w = -psi^(N/2) from the same root table, and runs every thread of the chosen workgroups.  Checked against Python integers:
 re = x + y mod q, im = U (x - y) mod q with U = w on entries [0, N/2) and q - w on [N/2, N).

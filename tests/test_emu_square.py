@@ -1,4 +1,4 @@
-"""The per-thread core of hm_tensor_square (homulator_amd/csrc/hm_elem_core.h: hm_tensor_square_one / hm_tensor_square_thread, the kernel of hsquare) and
+"""The per-thread core of hm_tensor_square (homulator_amd/csrc/hm_rec_core.h: hm_tensor_square_one / hm_tensor_square_thread, the kernel of hsquare) and
 the element-wise opcode ADD_CONST on the CPU, no GPU: tests/emu/hm_emu_square.cpp compiles the device header with g++, once per arithmetic back-end
 (HM_GENERIC 0 and 1), builds the records as the entry point does and runs every thread of the chosen workgroups.  Checked against Python integers:
 d0 = s a a + k, d1 = 2 s a c, d2 = s c c mod q.

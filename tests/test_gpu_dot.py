@@ -162,6 +162,8 @@ def test_refuses_bad_arguments():
         ctx.tensor_dot(*b, [NQ + NP], 1)
     with pytest.raises(hip.HmError, match="two output"):
         ctx.tensor_dot(*b[:4], b[4], b[4], b[6], [0], 1)
+    with pytest.raises(hip.HmError, match="two output limb-polys overlap"):   # through a limb list: entries 0 and 2 of o0, no input touched
+        ctx.tensor_dot(*b, [0, 0, 0], 1, limbs=[None] * 4 + [[0, 1, 0], None, None])
     with pytest.raises(hip.HmError, match="overlaps an input"):
         ctx.tensor_dot(*b[:4], b[0], b[5], b[6], [0], 1)
     ctx.tensor_dot(*b, [0], 1)                              # and the same call with nothing wrong is accepted

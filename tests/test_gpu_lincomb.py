@@ -206,6 +206,8 @@ def test_refuses_bad_arguments_and_accepts_n_0():
         ctx.lincomb(src, [0, 1], out, [0, 1], [0, 0], 1, [1, 1], [0, q0])
     with pytest.raises(hip.HmError, match="two output"):
         ctx.lincomb(src, [0, 1], out, [2, 2], [0, 0], 1, [1, 1])
+    with pytest.raises(hip.HmError, match="two output limb-polys overlap"):   # entries 0 and 2, apart in the list; no input touched
+        ctx.lincomb(src, [0, 1, 2], out, [2, 0, 2], [0, 0, 0], 1, [1, 1, 1])
     with pytest.raises(hip.HmError, match="overlaps an input"):
         ctx.lincomb(src, [0, 1], src, [3, 1], [0, 0], 1, [1, 1])
     keep = [hip._u32([0]), hip._u64([1, 1, 1])]

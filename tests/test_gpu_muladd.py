@@ -249,6 +249,8 @@ def test_refuses_bad_arguments_and_accepts_n_0():
         call(k=[q0])
     with pytest.raises(hip.HmError, match="two output"):
         call(limbs=[[0], [1], [2], [3], [0], [1], [1]])
+    with pytest.raises(hip.HmError, match="two output limb-polys overlap"):   # two entries: entry 0 of o1 and entry 1 of o2, no input touched
+        call(mods=(0, 0), lx0=(4, 6), lx1=(5, 7), u=(1, 1), limbs=[[0, 0], [1, 1], [2, 2], [3, 3], [0, 1], [2, 3], [4, 2]])
     with pytest.raises(hip.HmError, match="overlaps an input"):
         call(o1=src, limbs=[[0], [1], [2], [3], [0], [5], [2]])
     keep = [hip._u32([0])]

@@ -222,6 +222,8 @@ def test_refuses_bad_arguments():
         ctx.tensor_square(*b, [0, 0], addend=[0, q0])
     with pytest.raises(hip.HmError, match="two output"):
         ctx.tensor_square(b[0], b[1], b[2], b[2], b[4], [0])
+    with pytest.raises(hip.HmError, match="two output limb-polys overlap"):   # through a limb list: entries 0 and 2 of o1, no input touched
+        ctx.tensor_square(*b, [0, 0, 0], limbs=[None, None, None, [2, 0, 2], None])
     with pytest.raises(hip.HmError, match="overlaps an input"):
         ctx.tensor_square(b[0], b[1], b[0], b[3], b[4], [0])
     ctx.tensor_square(*b, [])                               # n = 0: nothing to do

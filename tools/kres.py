@@ -2,7 +2,8 @@
 usage: python tools/kres.py [substring ...]"""
 import re, subprocess, sys
 t = open('/tmp/hm_backend.resources').read()
-pat = re.compile(r"Function Name: (\S+).*?\n.*?TotalSGPRs: (\d+).*?\n.*?VGPRs: (\d+).*?\n.*?AGPRs: (\d+).*?\n.*?ScratchSize \[bytes/lane\]: (\d+).*?\n.*?Dynamic Stack.*?\n.*?Occupancy \[waves/SIMD\]: (\d+).*?\n.*?SGPRs Spill: (\d+).*?\n.*?VGPRs Spill: (\d+).*?\n.*?LDS Size \[bytes/block\]: (\d+)")
+# (a kernel that is no template instantiation has its source line echoed, two lines, under its name)
+pat = re.compile(r"Function Name: (\S+).*?\n(?:(?!.*remark:).*\n){0,2}.*?TotalSGPRs: (\d+).*?\n.*?VGPRs: (\d+).*?\n.*?AGPRs: (\d+).*?\n.*?ScratchSize \[bytes/lane\]: (\d+).*?\n.*?Dynamic Stack.*?\n.*?Occupancy \[waves/SIMD\]: (\d+).*?\n.*?SGPRs Spill: (\d+).*?\n.*?VGPRs Spill: (\d+).*?\n.*?LDS Size \[bytes/block\]: (\d+)")
 rows = pat.findall(t)
 names = subprocess.run(['c++filt'], input="\n".join(r[0] for r in rows), capture_output=True, text=True).stdout.split("\n")
 for r, d in zip(rows, names):
