@@ -508,6 +508,8 @@ __global__ void __launch_bounds__(256) k_lincomb(HmLincombArgs a) { hm_rec_block
 __global__ void __launch_bounds__(256) k_tensor_muladd(HmTensorMulAddArgs a) { hm_rec_block<hm_tensor_muladd_thread>(a); }
 // real and imaginary parts of the slots from a polynomial and its conjugate
 __global__ void __launch_bounds__(256) k_reim_split(HmReimArgs a) { hm_rec_block<hm_reim_thread>(a); }
+// sum of T limb-polys, each times a + b X^(N/2), plus a constant
+__global__ void __launch_bounds__(256) k_clincomb(HmClincombArgs a) { hm_rec_block<hm_clincomb_thread>(a); }
 
 // 16-byte units per thread of the element-wise kernel, 512 coefficients apart, all loads in flight before the first use.  1: 89 600 workgroups for a batch of
 // ten hadd; 2 / 4 measured padd +3 / +5 %, pmult +1 %, hadd within the noise (tools/r06_ewe_ab.sh): not worth a second shape of the kernel's launch
@@ -1910,6 +1912,40 @@ extern "C" hm_status hm_reim_split(hm_ctx *c, const uint64_t *px, const uint32_t
   HmReimArgs a;
   a.x = px; a.y = py; a.o_re = o_re; a.o_im = o_im;
   return rec_launch(c, k_reim_split, a, recs, n);
+}
+
+// sum of n_terms limb-polys, each times scale_re + scale_im X^(N/2), plus addend_re + addend_im X^(N/2): input list and scalars [n][n_terms], output
+// list and constants [n]; psi^(N/2) is derived here from the context's own roots, once per modulus of the call
+extern "C" hm_status hm_clincomb(hm_ctx *c, const uint64_t *in, const uint32_t *li, uint64_t *out, const uint32_t *lo, const uint32_t *mod_ids,
+                                 uint32_t n, uint32_t n_terms, const uint64_t *scale_re, const uint64_t *scale_im, const uint64_t *addend_re,
+                                 const uint64_t *addend_im) {
+  static const char *const what = "hm_clincomb";
+  if (!c) return HM_ERR_ARG;
+  HM_TABLE_CALL(c);
+  if (!in || !out) return fail(c, HM_ERR_ARG, "%s: null buffer", what);
+  if (!scale_re) return fail(c, HM_ERR_ARG, "%s: scale_re is null", what);
+  const uint32_t T = n_terms;
+  if (T == 0 || T > HM_CLINCOMB_MAX_TERMS) return fail(c, HM_ERR_ARG, "%s: n_terms = %u, must be in [1, %d]", what, T, HM_CLINCOMB_MAX_TERMS);
+  if ((uint64_t)n * T > 0xFFFFFFFFull / HM_CLINCOMB_REC_WORDS(T)) return fail(c, HM_ERR_ARG, "%s: n = %u entries of %u terms are too many for one call", what, n, T);
+  if (hm_status st = rec_check(c, what, {{"in", in, li, n * T}}, {{"out", out, lo, n}}, mod_ids, n,
+                               {{"scale_re", scale_re, false, true, T}, {"scale_im", scale_im, false, true, T}, {"addend_re", addend_re, false}, {"addend_im", addend_im, false}}))
+    return st;
+  if (n == 0) return HM_OK;
+  // v = psi^(N/2) mod q per entry, from the root table the transforms are built from (N >= 1024: a workgroup's 512 coefficients lie in one half)
+  const std::vector<uint64_t> qs = rec_moduli(c, mod_ids, n);
+  std::vector<uint64_t> vs(n);
+  std::map<uint32_t, uint64_t> vOf;
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t m = mod_ids[i];
+    auto f = vOf.find(m);
+    if (f == vOf.end()) f = vOf.emplace(m, hm::powmod(c->P.psi[m], c->P.N / 2, qs[i])).first;
+    vs[i] = f->second;
+  }
+  std::vector<uint32_t> recs((size_t)n * HM_CLINCOMB_REC_WORDS(T));
+  hm_clincomb_fill_recs(recs.data(), li, lo, mod_ids, vs.data(), qs.data(), n, T, scale_re, scale_im, addend_re, addend_im);
+  HmClincombArgs a;
+  a.in = in; a.out = out; a.n_terms = T;
+  return rec_launch(c, k_clincomb, a, recs, n);
 }
 
 extern "C" hm_status hm_automorph(hm_ctx *c, const uint64_t *in, const uint32_t *in_limbs, uint64_t *out,

@@ -1,6 +1,6 @@
-// hm_rec_core.h — the record-table element-wise kernels: hm_tensor_dot, hm_tensor_square, hm_lincomb, hm_tensor_muladd, hm_reim_split.
-// Per-thread bodies (no cross-thread state) shared by the HIP kernels (hm_backend.hip: k_tensor_dot, k_tensor_square, k_lincomb, k_tensor_muladd,
-// k_reim_split) and the host emulator.
+// hm_rec_core.h — the record-table element-wise kernels: hm_tensor_dot, hm_tensor_square, hm_lincomb, hm_tensor_muladd, hm_reim_split,
+// hm_clincomb.  Per-thread bodies (no cross-thread state) shared by the HIP kernels (hm_backend.hip: k_tensor_dot, k_tensor_square, k_lincomb, k_tensor_muladd,
+// k_reim_split, k_clincomb) and the host emulator.
 //
 // A record-table kernel: one record per limb-poly of the call in a device table cached by content, read through the scalar cache (the index is
 // wave-uniform); k_tensor's geometry — a workgroup owns 512 coefficients of one record, a thread an aligned pair (16-byte accesses) — and ONE
@@ -8,7 +8,7 @@
 // kernel's own *_fill_recs.
 #pragma once
 #include <cstddef>
-#include "../../include/homulator_hip.h"   // HM_TENSOR_DOT_MAX_TERMS, HM_LINCOMB_MAX_TERMS, HM_TENSOR_MULADD_MAX_ADDENDS
+#include "../../include/homulator_hip.h"   // HM_TENSOR_DOT_MAX_TERMS, HM_LINCOMB_MAX_TERMS, HM_TENSOR_MULADD_MAX_ADDENDS, HM_CLINCOMB_MAX_TERMS
 #include "hm_elem_core.h"                  // HM_CONST_PROB_T, HM_CONST_MODS
 #include "hm_modarith.h"
 #include "hm_ntt_core.h"
@@ -31,7 +31,7 @@ HM_HD uint32_t hm_rec_lane_bytes(uint32_t chunk, uint32_t tid) { return (chunk *
 #define HM_DOT_ISSUED() ((void)0)
 #endif
 
-// ---- the term loop of the kernels that sum a run-time number of terms (pairs of hm_tensor_dot, terms of hm_lincomb, addends of hm_tensor_muladd)
+// ---- the term loop of the kernels that sum a run-time number of terms (pairs of hm_tensor_dot, terms of hm_lincomb and hm_clincomb, addends of hm_tensor_muladd)
 // term_at(t): the record words of term t; ld(l): the loads of the term with words l, issued; acc(p): its products into the sums.  Software-
 // pipelined by hand: two terms per round in two named register sets p0, p1 (no copy between them), the loads of term t + 1 issued before the
 // products of term t are formed, and the record words of a term requested a step before its loads.  The index of that request is clamped to the
@@ -453,4 +453,79 @@ HM_HD void hm_reim_thread(const HmReimArgs &g, uint32_t entry, uint32_t chunk, u
   hm_bld2(g.y + rec[2] * N, lane_bytes, y[0], y[1]);
   hm_bst2(g.o_re + rec[3] * N, lane_bytes, hm_addmod(x[0], y[0], q), hm_addmod(x[1], y[1], q));
   hm_bst2(g.o_im + rec[4] * N, lane_bytes, hm_shoup(hm_submod(x[0], y[0], q), u, us, q), hm_shoup(hm_submod(x[1], y[1], q), u, us, q));
+}
+
+// ---- Sum of T polynomials, each times a + b X^(N/2), plus a constant, in one pass over the T inputs (hm_clincomb; HCLINCOMB):
+//   out = sum_t (a_t + b_t X^(N/2)) x_t + (k_re + k_im X^(N/2))      with a_t, b_t, k_re, k_im in [0, q) per record and every x_t canonical.
+// In evaluation form X^(N/2) is the constant v = psi^(N/2) on entries [0, N/2) of a limb-poly and q - v on [N/2, N) (hm_reim_split above: its w is
+// q - v), v^2 = -1.  So the factor of term t is ONE scalar per half,
+//   s_lo = a_t + b_t v mod q   on [0, N/2),      s_hi = a_t - b_t v mod q   on [N/2, N),
+// and the constant k_lo = k_re + k_im v, k_hi = k_re - k_im v likewise: the host forms the halves when it fills the records (hm_clincomb_halves)
+// and the kernel picks one set per workgroup, whose 512 coefficients lie in one half (N >= 1024): chunk < N/1024 takes the _lo words.  From there
+// it is hm_lincomb's arithmetic on both back-ends: raw 64 x 64 products in ONE 128-bit accumulator per coefficient, the constant added, one
+// hm_barrett_wide.  s_lo, s_hi, k_lo, k_hi < q < 2^60, so the bound is hm_lincomb's: T <= HM_CLINCOMB_MAX_TERMS = 16 products below 2^120 are below
+// 2^124, plus a constant below 2^60 below 2^125.  The result is the canonical residue of the exact sum, hence bit-identical to the chain of
+// MUL_CONST, MUL by the stored monomial, ADD and ADD_CONST.  T + 1 limb-polys per record and one wide multiply per loaded word.
+static_assert(HM_CLINCOMB_MAX_TERMS == 16, "the accumulator: 16 products below 2^120 plus a constant below 2^60 stay below 2^125");
+// a record = HM_CLINCOMB_REC_WORDS(T) 32-bit words (32 + 32 T bytes):
+//   (modulus id, output limb, T, 0), (k_lo: 2 words, k_hi: 2 words), then per term (input limb, 0, s_lo: 2 words, s_hi: 2 words, 0, 0)
+#define HM_CLINCOMB_REC_HEAD 8u
+#define HM_CLINCOMB_REC_WORDS(T) (HM_CLINCOMB_REC_HEAD + 8u * (T))
+struct HmClincombArgs {
+  const uint64_t *in;
+  uint64_t *out;
+  const HmMod *mods;
+  const uint32_t *rec;   // device, [n_limbs][HM_CLINCOMB_REC_WORDS(n_terms)]
+  uint32_t logN, n_limbs, n_terms;
+};
+// host: the two halves of a + b X^(N/2) in evaluation form, v = psi^(N/2) mod q; a, b, v < q
+inline void hm_clincomb_halves(uint64_t a, uint64_t b, uint64_t v, uint64_t q, uint64_t &lo, uint64_t &hi) {
+  const uint64_t bv = (uint64_t)(((unsigned __int128)b * v) % q);
+  lo = a + bv >= q ? a + bv - q : a + bv;
+  hi = a >= bv ? a - bv : a + q - bv;
+}
+// The records of n entries from the entry point's lists (in: [n][T], out: [n]) and constants (re: [n][T]; im: [n][T] or null = 0; add_re, add_im:
+// [n] or null = 0; all already checked: reduced); v[i] = psi^(N/2) mod q[i], q[i] = the modulus of entry i.  Host side.
+inline void hm_clincomb_fill_recs(uint32_t *rec, const uint32_t *li, const uint32_t *lo, const uint32_t *mod_ids, const uint64_t *v, const uint64_t *q,
+                                  uint32_t n, uint32_t T, const uint64_t *re, const uint64_t *im, const uint64_t *add_re, const uint64_t *add_im) {
+  for (uint32_t i = 0; i < n; ++i) {
+    uint32_t *r = rec + (size_t)i * HM_CLINCOMB_REC_WORDS(T);
+    uint64_t s_lo, s_hi;
+    r[0] = mod_ids[i]; r[1] = hm_rec_limb(lo, i); r[2] = T; r[3] = 0;
+    hm_clincomb_halves(add_re ? add_re[i] : 0, add_im ? add_im[i] : 0, v[i], q[i], s_lo, s_hi);
+    hm_rec_put64(r + 4, s_lo); hm_rec_put64(r + 6, s_hi);
+    for (uint32_t t = 0; t < T; ++t) {
+      const uint32_t e = i * T + t;
+      uint32_t *w = r + HM_CLINCOMB_REC_HEAD + 8 * t;
+      hm_clincomb_halves(re[e], im ? im[e] : 0, v[i], q[i], s_lo, s_hi);
+      w[0] = hm_rec_limb(li, e); w[1] = 0; hm_rec_put64(w + 2, s_lo); hm_rec_put64(w + 4, s_hi); w[6] = 0; w[7] = 0;
+    }
+  }
+}
+// the (input limb, scalar of the workgroup's half) of term t: hi = 0 takes s_lo, hi = 2 takes s_hi (the word offset of the half)
+template <class REC>
+HM_HD HmLincombTerm hm_clincomb_term(REC rec, uint32_t t, uint32_t hi) {
+  const uint32_t w = HM_CLINCOMB_REC_HEAD + 8 * t;
+  return HmLincombTerm{rec[w], hm_rec64(rec, w + 2 + hi)};
+}
+// thread tid of the workgroup that owns chunk `chunk` of record `entry`: T 16-byte loads (hm_term_rounds behind the load of term 0), one store.
+// chunk < N / 512 (the launch has n N / 512 workgroups), so the last byte touched is N * 8 - 1 of each limb-poly.
+HM_HD void hm_clincomb_thread(const HmClincombArgs &g, uint32_t entry, uint32_t chunk, uint32_t tid) {
+  const size_t N = (size_t)1 << g.logN;
+  const uint32_t T = g.n_terms, lane_bytes = hm_rec_lane_bytes(chunk, tid);
+  const auto rec = HM_CONST_PROB_T(uint32_t, g.rec) + (size_t)entry * HM_CLINCOMB_REC_WORDS(T);
+  const HmMod m = HM_CONST_MODS(g.mods)[rec[0]];
+  const uint32_t hi = chunk < (uint32_t)(N >> 10) ? 0u : 2u;   // (workgroup-uniform) entries [0, N/2) take the _lo words
+  const uint64_t k = hm_rec64(rec, 4 + hi);
+  hm_u128 s[2] = {0, 0};
+  const auto term_at = [&](uint32_t t) { return hm_clincomb_term(rec, t, hi); };
+  const auto ld = [&](const HmLincombTerm &l) {
+    HmLincombPair v;
+    hm_bld2(g.in + l.limb * N, lane_bytes, v.x[0], v.x[1]);
+    v.s = l.s;
+    return v;
+  };
+  const HmLincombPair p0 = ld(term_at(0));
+  hm_term_rounds(1, T, true, term_at(T > 1 ? 1u : 0u), p0, term_at, ld, [&](const HmLincombPair &v) { hm_lincomb_acc2(s, v); });
+  hm_bst2(g.out + rec[1] * N, lane_bytes, hm_barrett_wide(s[0] + k, m), hm_barrett_wide(s[1] + k, m));
 }

@@ -25,7 +25,7 @@ SYMBOLS = [
     "hm_bconv_col", "hm_limbs_to_colslices", "hm_colslices_to_limbs", "hm_ntt_second_pass", "hm_ntt_ex", "hm_capability", "hm_inner_product_ex",
     "hm_inner_product_hoisted", "hm_inner_product_lintrans", "hm_inner_product_rotsum", "hm_inner_product_lintrans_multi",
     "hm_tensor_dot", "hm_inner_product_lintrans_id", "hm_inner_product_rotsum_init", "hm_ntt_mix_sub_scale_mul", "hm_ntt_mul",
-    "hm_ntt_lift", "hm_tensor_square", "hm_lincomb", "hm_tensor_muladd", "hm_reim_split",
+    "hm_ntt_lift", "hm_tensor_square", "hm_lincomb", "hm_tensor_muladd", "hm_reim_split", "hm_clincomb",
 ]
 
 
@@ -163,6 +163,7 @@ def load():
     L.hm_lincomb.argtypes = [vp] + [vp] * 5 + [u32, u32, vp, vp]
     L.hm_tensor_muladd.argtypes = [vp] + [vp] * 18 + [u32, u32, vp, vp, vp]
     L.hm_reim_split.argtypes = [vp] + [vp] * 9 + [u32]
+    L.hm_clincomb.argtypes = [vp] + [vp] * 5 + [u32, u32, vp, vp, vp, vp]
     L.hm_inner_product.argtypes = [vp] + [vp] * 7 + [u32, u32, u32]
     L.hm_automorph.argtypes = [vp, vp, vp, vp, vp, u32, u32]
     L.hm_ewe.argtypes = [vp, i32] + [vp] * 11 + [u32, vp]
@@ -434,6 +435,16 @@ class Context:
         keep = [_u32(v) for v in ls] + [_u32(mod_ids)]
         self._ck(self.L.hm_reim_split(self.h, x.ptr, keep[0][1], y.ptr, keep[1][1], o_re.ptr, keep[2][1], o_im.ptr, keep[3][1], keep[4][1],
                                       len(mod_ids)))
+
+    def clincomb(self, src, in_limbs, out, out_limbs, mod_ids, n_terms, scale_re, scale_im=None, addend_re=None, addend_im=None):
+        """out[i] = sum_t (scale_re[i][t] + scale_im[i][t] * X^(N/2)) * src[in_limbs[i][t]] + addend_re[i] + addend_im[i] * X^(N/2) per entry
+        (hm_clincomb): in_limbs and the scalars are row-major [n][n_terms] (flat), out_limbs and mod_ids [n] (a limb list None: the identity), all
+        constants residues of the entry's modulus (scale_im / addend_re / addend_im None: 0); the back-end derives X^(N/2) from its own roots;
+        buffers: anything with a device address `.ptr`"""
+        keep = [_u32(in_limbs), _u32(out_limbs), _u32(mod_ids)]
+        ks = [_u64(v) for v in (scale_re, scale_im, addend_re, addend_im)]
+        self._ck(self.L.hm_clincomb(self.h, src.ptr, keep[0][1], out.ptr, keep[1][1], keep[2][1], len(mod_ids), int(n_terms), ks[0][1], ks[1][1],
+                                    ks[2][1], ks[3][1]))
 
     def inner_product(self, x, x_limbs, y, y_limbs, out, out_limbs, mod_ids, n_terms, n_out, x_galois=0):
         keep = [_u32(v) for v in (x_limbs, y_limbs, out_limbs, mod_ids)]

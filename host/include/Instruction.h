@@ -36,6 +36,7 @@ public:
   bool lincombHead = false;  // the MUL_CONST of term 1 of a sum of scaled ciphertexts (HLINCOMB): pass (5l) starts its record here
   bool muladdHead = false;   // a tensor product's MAC2 (d1) that scalars, scaled addends and a constant follow (HMULADD): pass (5m) starts its record here
   bool reimHead = false;     // the ADD x + conj(x) of one limb and component (HREIM): pass (5r) starts its record here
+  bool clincombHead = false; // the MUL_CONST a_1 x_1 of term 1 of a complex-weighted sum of ciphertexts (HCLINCOMB): pass (5c) starts its record here
   std::vector<uint32_t> inMods;  // BCONV: modulus ids of the inputs
   unsigned long long refInstructions = 0;  // upstream instructions this record stands for
   unsigned long long refExtra = 0;         // ... of records folded into a BCONV record (not scaled by its MAC-port count)
@@ -96,6 +97,15 @@ public:
   // operands and the MUL of the difference by the evaluation form of -X^(N/2).  reimOperands = (x, y): its two reads; OutputOperand = the sum,
   // extraOutputs = the product.  The stored factor is not read: the kernel derives it.  reimOperands empty: not such a record
   std::vector<AddrType> reimOperands;
+  // (5c) sum of polynomials times a + b X^(N/2) plus constant (hm_clincomb): the MUL_CONST record a_1 x_1 of term 1 that absorbed, per term, the
+  // MUL by the stored monomial, its MUL_CONST, the ADD of both parts and the ADD onto the running sum, and the ADD_CONST behind them.
+  // clOperands = the T inputs in term order, clScalesRe = a_t, clScalesIm = b_t (the stages carry q - b_t: the stored monomial is -X^(N/2));
+  // OutputOperand = the final sum.  clHasConst: the ADD_CONST record went in, with the constant clConst.  The stored monomial is not read: the
+  // kernel derives it.  clOperands empty: not such a sum
+  std::vector<AddrType> clOperands;
+  std::vector<uint64_t> clScalesRe, clScalesIm;
+  bool clHasConst = false;
+  uint64_t clConst = 0;
   // fused inner product (ops == IP): out_k = sum_j ipX[j] * ipY[k][j]; out_0 = OutputOperand, out_1 = extraOutputs[0]
   std::vector<AddrType> ipX;
   std::vector<std::vector<AddrType>> ipY;

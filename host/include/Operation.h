@@ -149,9 +149,10 @@ protected:
   // HMULT's tail on the three polynomials d of a tensor product (shared by HMULT, HDOT, HSQUARE, HMULADD): KS(d[2]); HMULT_Hadd_Key(k): d[k] + ks_k into
   // HMULTHaddOutput(k); Rescale of both, out = the result at level - 1
   void relinearizeAndRescale(const std::array<std::vector<AddrType>, 3> &d);
-  // Per-limb constants an op carries in its records (HSQUARE: "scale", "const"; HLINCOMB: "scale<t>", "const"; HMULADD: "scale", "addscale<t>", "const"), by name: the records of limb j that hold value j, so that
+  // Per-limb constants an op carries in its records (HSQUARE: "scale", "const"; HLINCOMB: "scale<t>", "const"; HCLINCOMB: "scale<t>", "scale_im<t>", "const"; HMULADD: "scale", "addscale<t>", "const"), by name: the records of limb j that hold value j, so that
   // setConstants can patch Instruction::constant before the plan is built.  enabled = false: the op knows the name but its config key is 0
-  struct ConstantStage { bool enabled = false; std::string key; std::vector<std::vector<Instruction *>> records; bool nonZero = false; };
+  // negated: the records carry q_j - value (HCLINCOMB's "scale_im<t>": the stage multiplies by the stored -X^(N/2))
+  struct ConstantStage { bool enabled = false; std::string key; std::vector<std::vector<Instruction *>> records; bool nonZero = false; bool negated = false; };
   std::map<std::string, ConstantStage> constantStages;
   std::vector<AddrType> alloc(const std::string &name, uint32_t limbs);  // MallocMem + getAddr
   std::vector<AddrType> component(uint32_t ct, uint32_t k) const { return k == 0 ? cts[ct].getC0Addr() : cts[ct].getC1Addr(); }  // c_k of input ct
@@ -274,6 +275,18 @@ class HREIM : public OperationBase {
 public:
   HREIM(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
 };
+// hclincomb (build extension): out = sum_t (a_t + b_t X^(N/2)) * ct<t> + k, a complex-weighted sum of T ciphertexts at one level: on the slots X^(N/2) is
+// the multiplication by i, so the weights are a_t + i b_t (config key terms = T as hlincomb: default 4, 1..16).  Per-limb scalars a_{t,j}, b_{t,j} in
+// [0, q_j), either may be 0 (synthetic: word 0 of limb j of stream seed + 6450 + 100 t for a, seed + 8150 + 100 t for b) and, with config key
+// cl_const = 1, per-limb real constants k_j on every evaluation-form entry of c0 only (stream seed + 9850): ct_re + i ct_im behind EvalMod, the
+// product of a ciphertext by a Gaussian-integer constant, the recombination of a complex polynomial.  The op keeps U = -X^(N/2) in evaluation form in
+// its named buffer `unit` as HREIM does.  setConstants("scale<t>" | "scale_im<t>" | "const") replaces the synthetic values ("scale_im<t>" takes b_t;
+// the stage that multiplies by U stores its negation).  No key, no ModUp.  One output ciphertext out at the inputs' level, or through Rescale at
+// level - 1 with config key rescale = 1.
+class HCLINCOMB : public OperationBase {
+public:
+  HCLINCOMB(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
+};
 class HROTSUM : public OperationBase {
 public:
   HROTSUM(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
@@ -321,7 +334,7 @@ class OpChain {
   std::vector<Arch *> archs;
   std::vector<OperationBase *> ops;
 public:
-  // ops: comma-separated list of hmult | hrotate | hadd | pmult | padd | hlintrans | hdot | hrotsum | hbsgs | hrescale | hmodraise | hsquare | hlincomb | hmuladd | hreim, e.g. "hmult,hrotate,hadd,hmult"; hrotate_hoisted (R output
+  // ops: comma-separated list of hmult | hrotate | hadd | pmult | padd | hlintrans | hdot | hrotsum | hbsgs | hrescale | hmodraise | hsquare | hlincomb | hmuladd | hreim | hclincomb, e.g. "hmult,hrotate,hadd,hmult"; hrotate_hoisted (R output
   // ciphertexts) only as the last op
   OpChain(const std::string &cfgPath, const std::string &opList, uint32_t maxLevel, uint32_t curLevel, uint32_t alpha,
           const std::map<std::string, uint32_t> &overrides = {});

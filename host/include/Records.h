@@ -92,6 +92,8 @@ inline std::vector<Read> recordReads(const Instruction &i) {
     for (AddrType a : i.maOperands) v.push_back({a, Role::Operand, kNoDigit});
   } else if (!i.reimOperands.empty()) {  // (5r): the polynomial and its conjugate, each read once
     for (AddrType a : i.reimOperands) v.push_back({a, Role::Operand, kNoDigit});
+  } else if (!i.clOperands.empty()) {    // (5c): the input of every term; the stored monomial is not read
+    for (AddrType a : i.clOperands) v.push_back({a, Role::Operand, kNoDigit});
   } else if (i.ops == MULT) {
     for (int b = 0; b < 4; ++b)
       if (eweOperandMask(i.opcode) & (1 << b)) v.push_back({i.operandList[b], Role::Operand, kNoDigit});

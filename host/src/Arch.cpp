@@ -32,7 +32,8 @@ struct Arch::Launch {
               L_TENSOR_SQUARE,                               // (5q) the scaled square of one ciphertext plus a constant
               L_LINCOMB,                                     // (5l) the sum of scaled polynomials plus a constant
               L_TENSOR_MULADD,                               // (5m) the scaled tensor product plus scaled addends plus a constant
-              L_REIM } kind;                                 // (5r) the sum and the rotated difference of a polynomial and its conjugate
+              L_REIM,                                        // (5r) the sum and the rotated difference of a polynomial and its conjugate
+              L_CLINCOMB } kind;                             // (5c) the sum of polynomials times a + b X^(N/2) plus a constant
   std::vector<uint32_t> hoistG;   // L_IP_HOISTED: the Galois element of every rotation (a: digits [n][T], b: keys [r][n][2][T], out: [r][n][2])
                                   // L_IP_LINTRANS: the same, with c: plaintexts [r][n], d: addend source [n] / out1: addend output [n] (HM_NO_LIMB: none; both
                                   // empty: no entry has one), out: [n][2]
@@ -60,6 +61,7 @@ struct Arch::Launch {
                                   // L_LINCOMB: terms per record (a: [n][dotTerms], out: [n]; k: the scalars [n][dotTerms], addK: the constants [n], empty: none)
                                   // L_TENSOR_SQUARE: a = c0, c = c1, out, out1, out2 = d0, d1, d2 [n]; k: the scalars [n], addK: the constants [n] (empty: none)
                                   // L_REIM: a = the polynomial, c = its conjugate, out = the sum, out1 = the rotated difference [n]
+                                  // L_CLINCOMB: as L_LINCOMB with k: the real parts a_t, maK: the monomial parts b_t [n][dotTerms]
   uint32_t maAddends = 0;         // L_TENSOR_MULADD: addends per record (a, b, c, d, out, out1, out2 as L_TENSOR; x0, x1: c0, c1 of the addends [n][maAddends];
   std::vector<uint32_t> x0, x1;   // k: the scalars [n], maK: the addend scalars [n][maAddends], addK: the constants [n]; k / addK empty: none)
   std::vector<uint64_t> maK;
@@ -169,6 +171,9 @@ Arch::Arch(Config *cfg) : config(cfg) {
   // (5r) hreim: the ADD, the SUB and the MUL by the evaluation form of -X^(N/2) behind the conjugation become one hm_reim_split launch.  Config key
   // fuse_reim (default 1).
   fuseReim = cfg->getValueOr("fuse_reim", 1) != 0;
+  // (5c) hclincomb: per term the MUL_CONST, the MUL by the evaluation form of -X^(N/2) with its MUL_CONST and the ADD of both, the ADDs between the
+  // terms and the ADD_CONST behind them become one hm_clincomb launch.  Config key fuse_clincomb (default 1).
+  fuseClincomb = cfg->getValueOr("fuse_clincomb", 1) != 0;
   // (4p) pmult with rescale = 1: the products are formed by the rescale's transforms while they load.  Config key fuse_pmul_rescale: 1 / 0 = always /
   // never; not given = where it was measured faster than the three-launch plan: everywhere but the generic back-end's launches
   // inside the one-launch form's limit, which has no product form there (Planner::productOperands)
@@ -335,6 +340,7 @@ int partKey(const Instruction &i) {
   if (!i.lcOperands.empty()) return 8600 + (int)i.lcOperands.size();                                   // 8600+: sum of scaled polynomials, by terms
   if (!i.maOperands.empty()) return 8700 + 4 * (int)i.maAddScales.size() + (i.maHasScale ? 1 : 0) + (i.maHasConst ? 2 : 0);   // 8700+: scaled product plus addends, by addends and what it absorbed
   if (!i.reimOperands.empty()) return 8400;                                                                // 8400: sum and rotated difference of a polynomial and its conjugate
+  if (!i.clOperands.empty()) return 8800 + (int)i.clOperands.size();                                       // 8800+: sum of polynomials times a + b X^(N/2), by terms
   if (i.fusedTensor) return 200;                                                                           // 200: tensor product
   if (i.fusedSubScale && i.fMinuendB) return i.fMix ? 211 : 209;                                           // 209 / 211: ... with a product minuend (4p)
   if (i.fusedSubScale) return (i.fMix ? 203 : 201) + (i.fConvIn.empty() ? 0 : 4);                          // 201 / 203: fused forward transform, plain / merged; 205 / 207: with its conversion
@@ -507,6 +513,7 @@ struct Arch::LaunchBuilder {
   void lincomb(Launch &L, Recs recs);
   void tensorMulAdd(Launch &L, Recs recs);
   void reim(Launch &L, Recs recs);
+  void clincomb(Launch &L, Recs recs);
   void nttSubScale(Launch &L, Recs recs);
   void copy(Launch &L, Recs recs);
   void transform(Launch &L, Recs recs);
@@ -717,6 +724,24 @@ void Arch::LaunchBuilder::reim(Launch &L, Recs recs) {
   L.bytes = 4 * LP * recs.size();   // two polynomials read, two written
 }
 
+// (5c) a = the input of every term [n][T]; out = the sum [n]; k / maK = the real / the monomial parts of the scalars [n][T], addK = the constants [n]
+// (hm_clincomb; the back-end derives X^(N/2)).  The part key keeps records of different term counts apart; a record without a constant (c1 beside a
+// c0 that has one) adds 0, which changes no residue
+void Arch::LaunchBuilder::clincomb(Launch &L, Recs recs) {
+  L.kind = Launch::L_CLINCOMB; L.statKey = "EWE";
+  L.dotTerms = (uint32_t)recs[0]->clOperands.size();
+  for (Instruction *i : recs) {
+    for (AddrType x : i->clOperands) L.a.push_back(limb(x));
+    L.k.insert(L.k.end(), i->clScalesRe.begin(), i->clScalesRe.end());
+    L.maK.insert(L.maK.end(), i->clScalesIm.begin(), i->clScalesIm.end());
+    L.out.push_back(limb(i->OutputOperand));
+    L.mods.push_back(i->mod_id);
+  }
+  if (std::any_of(recs.begin(), recs.end(), [](const Instruction *i) { return i->clHasConst; }))
+    for (Instruction *i : recs) L.addK.push_back(i->clHasConst ? i->clConst : 0);
+  L.bytes = (L.dotTerms + 1ull) * LP * recs.size();   // every input read once, the sum written once
+}
+
 // fused forward transform (4, 4b, 9, 12)
 void Arch::LaunchBuilder::nttSubScale(Launch &L, Recs recs) {
   L.kind = Launch::L_NTT_SUBSCALE; L.statKey = "NTT";
@@ -888,6 +913,7 @@ void Arch::LaunchBuilder::emitCompute(const Group &group, Launches &front, Launc
   else if (!f->lcOperands.empty()) lincomb(*L, recs);
   else if (!f->maOperands.empty()) tensorMulAdd(*L, recs);
   else if (!f->reimOperands.empty()) reim(*L, recs);
+  else if (!f->clOperands.empty()) clincomb(*L, recs);
   else if (f->fusedTensor) tensor(*L, recs);
   else if (f->fusedSubScale) nttSubScale(*L, recs);
   else if (f->ops == NTT && f->passthrough) copy(*L, recs);
@@ -1313,7 +1339,7 @@ void Arch::prepare() {
 
 static const char *const kLaunchKindNames[] = {"NTT", "INTT", "EWE", "BCONV", "AUTO", "NTT_SUBSCALE", "TENSOR", "EXCH_IN", "EXCH_OUT", "REPLICATE", "IP", "NTT_IP",
                                                "BCONV_COL", "EXCH_IN_COL", "EXCH_OUT_COL", "IP_HOISTED", "IP_LINTRANS", "TENSOR_DOT", "IP_ROTSUM",
-                                               "IP_LINTRANS_MULTI", "TENSOR_SQUARE", "LINCOMB", "TENSOR_MULADD", "REIM"};
+                                               "IP_LINTRANS_MULTI", "TENSOR_SQUARE", "LINCOMB", "TENSOR_MULADD", "REIM", "CLINCOMB"};
 
 // Per-launch device time (SURVEY.md §8d "per-stage hipEvent times", exchange time at N > 1): every launch of the plan
 // bracketed by its own event pair, in plan order so that the data dependencies (and, sharded, the collectives) line up.
@@ -1368,6 +1394,8 @@ std::string Arch::planText() const {
     if (l->kind == Launch::L_TENSOR_SQUARE)   // (5q): what the records absorbed
       out += std::string(" scale=") + (l->k.empty() ? "0" : "1") + " const=" + (l->addK.empty() ? "0" : "1");
     if (l->kind == Launch::L_LINCOMB)   // (5l): terms summed per record, and whether a constant follows
+      out += " terms=" + std::to_string(l->dotTerms) + " const=" + (l->addK.empty() ? "0" : "1");
+    if (l->kind == Launch::L_CLINCOMB)   // (5c): terms summed per record, and whether a constant follows
       out += " terms=" + std::to_string(l->dotTerms) + " const=" + (l->addK.empty() ? "0" : "1");
     if (l->kind == Launch::L_TENSOR_MULADD)   // (5m): addends per record, and what the records absorbed
       out += " addends=" + std::to_string(l->maAddends) + " scale=" + (l->k.empty() ? "0" : "1") + " const=" + (l->addK.empty() ? "0" : "1");
@@ -1564,6 +1592,10 @@ void Arch::enqueue(Launch &l) {
     break;
   case Launch::L_REIM:
     st = hm_reim_split(ctx, pool, l.a.data(), pool, l.c.data(), pool, l.out.data(), pool, l.out1.data(), l.mods.data(), cnt);
+    break;
+  case Launch::L_CLINCOMB:
+    st = hm_clincomb(ctx, pool, l.a.data(), pool, l.out.data(), l.mods.data(), cnt, l.dotTerms, l.k.data(), l.maK.data(),
+                     l.addK.empty() ? nullptr : l.addK.data(), nullptr);
     break;
   case Launch::L_EXCH_IN:
     st = hm_limbs_to_slices(ctx, pool, l.exLimbs.data(), l.exOwners.data(), (uint32_t)l.exLimbs.size(), l.slicesIn);

@@ -493,7 +493,7 @@ void OperationBase::setConstants(const std::string &name, const uint64_t *values
     if (cs->second.nonZero && values[j] == 0) throw std::runtime_error(what + ": values[" + S(j) + "] is zero");
   }
   for (uint32_t j = 0; j < n; ++j)
-    for (Instruction *i : cs->second.records[j]) i->constant = values[j];
+    for (Instruction *i : cs->second.records[j]) i->constant = cs->second.negated && values[j] ? arch->modulus(j) - values[j] : values[j];
 }
 void OperationBase::finishRotation(const std::string &out, const std::vector<AddrType> &rotatedC0, const KeySwitch::Output &ks, const std::string &suffix) {
   PerLimb s{label + "_HROTATEadd" + suffix + "_Level(", ")", range(0, level_), alloc("HROTATEOutput" + suffix + "(1)", level_)};
@@ -1009,6 +1009,104 @@ HLINCOMB::HLINCOMB(std::string labelName, uint32_t maxLevel, uint32_t currentLev
   finishConstruction();
 }
 
+// hclincomb (build extension).  Per component k and term t, with x_t = ct<t>.c<k>, existing opcodes only, `unit` being HREIM's
+// named buffer U = -X^(N/2) in evaluation form (Arch::addUnitFill), so that +X^(N/2) b is U (q - b mod q):
+//   CLinComb_Re_(t)_C<k> = a_t x_t (MUL_CONST),  CLinComb_Rot_(t)_C<k> = x_t (.) unit (MUL),  CLinComb_Im_(t)_C<k> = that times (q - b_t) mod q (MUL_CONST),
+//   CLinComb_Term_(t)_C<k> = Re + Im (ADD),  CLinComb_Add_(t)_C<k> = the running sum plus the term (ADD) for t >= 2,
+// and with cl_const = 1 CLinComb_Const_C0 = the sum of c0 plus k (ADD_CONST, on c0 only as PADD's plaintext).  The last buffer of a component is
+// CLinCombOutput(k).  Unfused, the stages run as element-wise launches; fused, pass (5c) of Arch::fusePasses (Planner.cpp) turns each limb's chain
+// into one record of ONE launch, which does not read `unit`.
+HCLINCOMB::HCLINCOMB(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch)
+    : OperationBase("HCLINCOMB", labelName, cfg, _arch, maxLevel, currentLevel, alpha) {
+  if (arch->backend() == Arch::BACKEND_SIM) throw std::runtime_error("hclincomb: backend = sim has no such op (the reference has no monomial product)");
+  if (arch->world() > 1) throw std::runtime_error("hclincomb: world > 1 is not supported (the sharded plan is not built)");
+  const uint32_t T = cfg->getValueOr("terms", 4);
+  if (T < 1 || T > 16) throw std::runtime_error("hclincomb: terms = " + S(T) + ", must be in [1, 16]");
+  const uint32_t cl = cfg->getValueOr("cl_const", 0);
+  if (cl > 1) throw std::runtime_error("hclincomb: cl_const = " + S(cl) + ", must be 0 or 1");
+  const bool shifted = cl == 1, rescale = rescaleKey("hclincomb");
+  makeInputs(T);
+  constantStages["const"].key = "cl_const";
+  const std::vector<AddrType> unit = alloc("unit", currentLevel);
+  arch->addUnitFill(unit, range(0, currentLevel));
+  // the records of limb j of a constant stage, kept by name for setConstants; both components share the scalars.  negated: the stage carries
+  // q - value (the monomial part: the stored factor is -X^(N/2))
+  auto keep = [&](const std::string &name, const std::vector<INSGROUP> &recs, bool negated) {
+    ConstantStage &cs = constantStages[name];
+    cs.enabled = true;
+    cs.negated = negated;
+    cs.records.resize(currentLevel);
+    for (uint32_t j = 0; j < currentLevel; ++j) cs.records[j].push_back(recs[j][0]);
+  };
+  auto synth = [&](uint64_t stream, bool negated) {
+    std::vector<uint64_t> v;
+    for (uint32_t j = 0; j < currentLevel; ++j) {
+      const uint64_t x = synthWord0(stream + j, arch->modulus(j));
+      v.push_back(negated && x ? arch->modulus(j) - x : x);
+    }
+    return v;
+  };
+  std::array<std::vector<AddrType>, 2> out;
+  for (uint32_t k = 0; k < 2; k++) {
+    const std::string C = "_C" + S(k);
+    const bool constHere = shifted && k == 0;
+    Limbs sum;
+    for (uint32_t t = 1; t <= T; ++t) {
+      const std::string at = "_(" + S(t) + ")" + C;
+      const std::vector<AddrType> x = component(t - 1, k);
+      auto emit = [&](const std::string &stage, ewe_opcode op, const PerLimb &s) {
+        Limbs o{s.out, eweLimbs(&insgener, op, s)};
+        driver.dispatchInstructions("CLinComb_" + stage + at, o.from);
+        return o;
+      };
+      auto stageOf = [&](const std::string &stage, const std::string &buffer) {
+        return PerLimb{labelName + "_CLinComb_" + stage + at + "_Level(", ")", range(0, currentLevel), alloc(buffer, currentLevel)};
+      };
+      PerLimb re = stageOf("Re", "CLinCombRe" + at);
+      re.a = x;
+      re.constants = synth(seed + 6450 + 100ull * t, false);
+      const Limbs real = emit("Re", EWE_MUL_CONST, re);
+      keep("scale" + S(t), real.from, false);
+      if (t == 1)
+        for (const INSGROUP &g : real.from) g[0]->clincombHead = true;
+      PerLimb ro = stageOf("Rot", "CLinCombRot" + at);
+      ro.a = x; ro.b = unit;
+      const Limbs rot = emit("Rot", EWE_MUL, ro);
+      PerLimb im = stageOf("Im", "CLinCombIm" + at);
+      im.a = rot.addr; im.after = {&rot.from};
+      im.constants = synth(seed + 8150 + 100ull * t, true);
+      const Limbs imag = emit("Im", EWE_MUL_CONST, im);
+      keep("scale_im" + S(t), imag.from, true);
+      const bool lastTerm = T == 1 && !constHere;
+      PerLimb te = stageOf("Term", lastTerm ? "CLinCombOutput(" + S(k) + ")" : "CLinCombTerm" + at);
+      te.a = real.addr; te.c = imag.addr; te.after = {&real.from, &imag.from};
+      const Limbs term = emit("Term", EWE_ADD, te);
+      if (t == 1) {
+        sum = term;
+        continue;
+      }
+      const bool lastAdd = t == T && !constHere;
+      PerLimb a = stageOf("Add", lastAdd ? "CLinCombOutput(" + S(k) + ")" : "CLinCombSum" + at);
+      const Limbs before = sum;
+      a.a = before.addr; a.c = term.addr; a.after = {&before.from, &term.from};
+      sum = emit("Add", EWE_ADD, a);
+    }
+    if (constHere) {
+      PerLimb c{labelName + "_CLinComb_Const" + C + "_Level(", ")", range(0, currentLevel), alloc("CLinCombOutput(" + S(k) + ")", currentLevel)};
+      const Limbs before = sum;
+      c.a = before.addr; c.after = {&before.from};
+      c.constants = synth(seed + 9850, false);
+      sum = {c.out, eweLimbs(&insgener, EWE_ADD_CONST, c)};
+      driver.dispatchInstructions("CLinComb_Const" + C, sum.from);
+      keep("const", sum.from, false);
+    }
+    out[k] = sum.addr;
+  }
+  if (rescale) setRescaledOutput("out", out);
+  else for (uint32_t k = 0; k < 2; k++) setOutput("out", k, out[k]);
+  finishConstruction();
+}
+
 // hmuladd (build extension).  out = Rescale(d0 + ks0(d2)), Rescale(d1 + ks1(d2)) with
 //   d0 = s a b + sum_t u_t x_t + k,  d1 = s (a d + c b) + sum_t u_t y_t,  d2 = s c d
 // (a, c = ct1.c0, ct1.c1; b, d = ct2.c0, ct2.c1; x_t, y_t = ct<2+t>.c0, .c1): one node of a polynomial evaluation, T_{a+b} = 2 T_a T_b - T_{|a-b|} or
@@ -1324,6 +1422,7 @@ static OperationBase *makeOp(const std::string &o, uint32_t maxLevel, uint32_t l
   if (o == "hlincomb") return new HLINCOMB("test_hlincomb", maxLevel, level, alpha, cfg, arch);
   if (o == "hmuladd") return new HMULADD("test_hmuladd", maxLevel, level, alpha, cfg, arch);
   if (o == "hreim") return new HREIM("test_hreim", maxLevel, level, alpha, cfg, arch);
+  if (o == "hclincomb") return new HCLINCOMB("test_hclincomb", maxLevel, level, alpha, cfg, arch);
   throw std::runtime_error("Error operation requirement, please double confirm!");
 }
 

@@ -109,6 +109,7 @@ struct Arch::Planner {
   void linearCombination();   // 5l
   void tensorMulAdd();     // 5m
   void realImaginary();    // 5r
+  void complexCombination();   // 5c
   void keyProduct();       // 6
   // what (6m/6l), (6s) and (6h) all recognise: the live two-key key-product records whose digits are all automorphisms, by one element per record, of
   // the same materialised digits and are read by nothing else; per (modulus, unrotated digits) the records and their automorphisms, in stage order
@@ -153,6 +154,7 @@ void Arch::fusePasses(std::vector<Stage> &st) {
   if (fuseLincomb) p.linearCombination();
   if (fuseMuladd) p.tensorMulAdd();
   if (fuseReim) p.realImaginary();
+  if (fuseClincomb) p.complexCombination();
   p.keyProduct();
   // (6m, 6l) before (6s) and (6h): the records it merges are the ones (6h) would claim, and none of them is (6s)'s (their outputs go into products,
   // not into sums).  fuse_bsgs: the groups with several sums, fuse_lintrans: the ones with one
@@ -650,6 +652,86 @@ void Arch::Planner::realImaginary() {
       if (place.after(i, last)) last = i;
     }
     producer[mul->OutputOperand] = c;
+    place.moveTo(c, last);   // to where its last link stood
+  }
+}
+
+// (5c) sum of polynomials times a + b X^(N/2) plus constant (hclincomb): from a MUL_CONST record a_1 x_1 that the builder marked as term 1 of such a
+//      sum (clincombHead).  A term is the ADD of two MUL_CONST records of the same modulus, each read by nothing else: the real part a_t x_t, and
+//      the monomial part whose operand is the output, read by nothing else, of a MUL record of the SAME x_t by a limb that nothing produces (the
+//      stored evaluation form of -X^(N/2)); its constant is q - b_t.  Term 1 is the ADD that reads the marked record; term after term, the running
+//      sum goes on through ONE ADD whose other operand is such a term, read by nothing else; behind the last term, ONE ADD_CONST.  The links merge
+//      into the marked record: hm_clincomb sums the raw products of all terms by the scalar of each half, adds the constant and stores the final
+//      sum only; the factor is derived by the back-end from its roots, so the fused record does not read the stored one.  Never written: the 4T
+//      parts and the T - 1 partial sums (and the sum in front of the constant).  The record takes the place of the last record it absorbs.
+//      Only the builder of HCLINCOMB sets the mark: the pass matches nothing in any other op.
+//      Sets on the marked record: clOperands, clScalesRe, clScalesIm, clHasConst, clConst, OutputOperand.
+void Arch::Planner::complexCombination() {
+  Readers rd = readers();
+  Placement place(st);
+  std::vector<Instruction *> heads;
+  for (auto &s : st)
+    for (Instruction *i : s.ins)
+      if (live(i) && i->clincombHead && i->ops == MULT && i->opcode == EWE_MUL_CONST && i->hasConstant && i->clOperands.empty()) heads.push_back(i);
+  for (Instruction *c : heads) {
+    const uint64_t q = A.modulus(c->mod_id);
+    // the records of one term behind its ADD `term`, with `re` one of its operands' producers (null: either): re, rot, im, or none
+    struct Term { Instruction *re = nullptr, *rot = nullptr, *im = nullptr; };
+    auto scaled = [&](AddrType a, Instruction *reader) -> Instruction * {
+      Instruction *m = producerOf(a);
+      return m && live(m) && m->ops == MULT && m->opcode == EWE_MUL_CONST && m->hasConstant && m->mod_id == c->mod_id && onlyReader(rd, a, reader) ? m : nullptr;
+    };
+    auto termOf = [&](Instruction *term, Term &t) {
+      if (term->operandList[0] == term->operandList[2]) return false;
+      t.re = scaled(term->operandList[0], term);
+      t.im = scaled(term->operandList[2], term);
+      if (!t.re || !t.im || t.im->clincombHead || (t.re->clincombHead && t.re != c)) return false;
+      t.rot = producerOf(t.im->operandList[0]);
+      return t.rot && isMul(t.rot, c->mod_id) && !t.rot->fusedTensor && onlyReader(rd, t.rot->OutputOperand, t.im) &&
+             t.rot->operandList[0] == t.re->operandList[0] && t.rot->operandList[1] != t.rot->operandList[0] && !producerOf(t.rot->operandList[1]);
+    };
+    Instruction *first = soleReader(rd, c->OutputOperand, EWE_ADD, c->mod_id);
+    Term t1;
+    if (!first || first->operandList[0] != c->OutputOperand || !termOf(first, t1) || t1.re != c) continue;
+    Instruction *last = c;
+    auto take = [&](Instruction *i) {
+      absorb(c, i);
+      if (place.after(i, last)) last = i;
+    };
+    auto add = [&](const Term &t) {
+      c->clOperands.push_back(t.re->operandList[0]);
+      c->clScalesRe.push_back(t.re->constant);
+      c->clScalesIm.push_back(t.im->constant ? q - t.im->constant : 0);
+      take(t.re); take(t.rot); take(t.im);
+    };
+    // (the marked record's own fields are read by add() before anything overwrites them: re == c, absorb(c, c) does nothing)
+    add(t1);
+    take(first);
+    AddrType sum = first->OutputOperand;
+    while (c->clOperands.size() < HM_CLINCOMB_MAX_TERMS) {
+      Instruction *link = soleReader(rd, sum, EWE_ADD, c->mod_id);
+      if (!link || link->operandList[0] != sum || link->operandList[2] == sum) break;
+      const AddrType other = link->operandList[2];
+      Instruction *term = producerOf(other);
+      Term t;
+      if (!term || !live(term) || term->ops != MULT || term->opcode != EWE_ADD || term->mod_id != c->mod_id || term->fusedTensor || !onlyReader(rd, other, link) ||
+          !termOf(term, t))
+        break;
+      add(t);
+      take(term);
+      take(link);
+      sum = link->OutputOperand;
+    }
+    if (Instruction *k = soleReader(rd, sum, EWE_ADD_CONST, c->mod_id)) {
+      if (k->hasConstant) {
+        c->clHasConst = true;
+        c->clConst = k->constant;
+        take(k);
+        sum = k->OutputOperand;
+      }
+    }
+    c->OutputOperand = sum;
+    producer[sum] = c;
     place.moveTo(c, last);   // to where its last link stood
   }
 }

@@ -239,6 +239,26 @@ hm_status hm_reim_split(hm_ctx *ctx, const uint64_t *x, const uint32_t *x_limbs,
                         uint64_t *o_re, const uint32_t *o_re_limbs, uint64_t *o_im, const uint32_t *o_im_limbs,
                         const uint32_t *mod_ids, uint32_t n);
 
+/* K3, sum of n_terms limb-polys, each times a Gaussian-integer-like scalar a + b X^(N/2), plus a constant, in one pass over the n_terms inputs
+ * (HCLINCOMB): for entry i, with a_t = scale_re[i * n_terms + t], b_t = scale_im[i * n_terms + t], k_re = addend_re[i] and
+ * k_im = addend_im[i], all in [0, q),
+ *   out[i] = sum_t (a_t + b_t X^(N/2)) * in[i][t] + (k_re + k_im X^(N/2)),   t < n_terms <= 16,
+ * the product by X^(N/2) taken in the ring: on the slots it is the multiplication by i.  In evaluation form X^(N/2) is the constant
+ * v = psi^(N/2) mod q on entries [0, N/2) of a limb-poly and q - v on [N/2, N); the back-end derives v from its own root table (hm_get_psi's
+ * psi) and the caller passes (a, b), never the halves.  The result is the canonical residue of the exact sum: bit-identical to HM_OP_MUL_CONST
+ * by a_t, HM_OP_MUL by a stored X^(N/2) and HM_OP_MUL_CONST by b_t, HM_OP_ADD of the two and between the terms, and HM_OP_ADD_CONST behind, none
+ * of whose intermediates is written (n_terms + 1 limb-polys per entry where that chain moves 13 n_terms - 3 without the constant).  in_limbs is
+ * row-major, in_limbs[i * n_terms + t] (the same limb-poly may appear in several entries and terms); out_limbs and mod_ids have n entries; a
+ * null limb list is the identity.  The constants are host arrays; scale_im == NULL: every b_t is 0; addend_re / addend_im == NULL: every k_re /
+ * k_im is 0.  With scale_im == NULL and addend_im == NULL the call is hm_lincomb, bit for bit.  The records live in a device table: one launch
+ * serves any n, and the call is safe under graph capture once it has run with the same lists and constants.  HM_ERR_ARG: a null buffer or a
+ * null mod_ids / scale_re, n_terms outside 1..16, a limb or modulus id out of range, an unreduced constant, an output limb-poly that overlaps
+ * (by address range, not by base pointer) an input limb-poly or another output limb-poly.  n = 0 is HM_OK. */
+#define HM_CLINCOMB_MAX_TERMS 16
+hm_status hm_clincomb(hm_ctx *ctx, const uint64_t *in, const uint32_t *in_limbs, uint64_t *out, const uint32_t *out_limbs,
+                      const uint32_t *mod_ids, uint32_t n, uint32_t n_terms, const uint64_t *scale_re, const uint64_t *scale_im,
+                      const uint64_t *addend_re, const uint64_t *addend_im);
+
 /* K5 — inner product with the evaluation key in one pass: for limb i, out[i][k] = sum_{j < n_terms}
  * x[i][j] * y[i][k][j], k < n_out (n_terms <= 4 digits, n_out <= 2 keys).  Limb lists are row-major:
  * x_limbs[i * n_terms + j], y_limbs[(i * n_out + k) * n_terms + j], out_limbs[i * n_out + k].  Replaces
