@@ -510,6 +510,8 @@ __global__ void __launch_bounds__(256) k_tensor_muladd(HmTensorMulAddArgs a) { h
 __global__ void __launch_bounds__(256) k_reim_split(HmReimArgs a) { hm_rec_block<hm_reim_thread>(a); }
 // sum of T limb-polys, each times a + b X^(N/2), plus a constant
 __global__ void __launch_bounds__(256) k_clincomb(HmClincombArgs a) { hm_rec_block<hm_clincomb_thread>(a); }
+// sum of T ciphertexts, each times a plaintext limb-poly loaded once for both components, plus a plaintext on c0
+__global__ void __launch_bounds__(256) k_plincomb(HmPlincombArgs a) { hm_rec_block<hm_plincomb_thread>(a); }
 
 // 16-byte units per thread of the element-wise kernel, 512 coefficients apart, all loads in flight before the first use.  1: 89 600 workgroups for a batch of
 // ten hadd; 2 / 4 measured padd +3 / +5 %, pmult +1 %, hadd within the noise (tools/r06_ewe_ab.sh): not worth a second shape of the kernel's launch
@@ -1946,6 +1948,29 @@ extern "C" hm_status hm_clincomb(hm_ctx *c, const uint64_t *in, const uint32_t *
   HmClincombArgs a;
   a.in = in; a.out = out; a.n_terms = T;
   return rec_launch(c, k_clincomb, a, recs, n);
+}
+
+// sum of n_terms ciphertexts, each times a plaintext limb-poly, plus a plaintext on c0: term lists [n][n_terms], output and addend lists [n]; a
+// record is one output limb with both components
+extern "C" hm_status hm_plincomb(hm_ctx *c, const uint64_t *p, const uint32_t *lp, const uint64_t *x, const uint32_t *lx0, const uint32_t *lx1,
+                                 const uint64_t *addend, const uint32_t *la, uint64_t *out, const uint32_t *l0, const uint32_t *l1,
+                                 const uint32_t *mod_ids, uint32_t n, uint32_t n_terms) {
+  static const char *const what = "hm_plincomb";
+  if (!c) return HM_ERR_ARG;
+  HM_TABLE_CALL(c);
+  if (!p || !x || !out) return fail(c, HM_ERR_ARG, "%s: null buffer", what);
+  const uint32_t T = n_terms;
+  if (T == 0 || T > HM_PLINCOMB_MAX_TERMS) return fail(c, HM_ERR_ARG, "%s: n_terms = %u, must be in [1, %d]", what, T, HM_PLINCOMB_MAX_TERMS);
+  if ((uint64_t)n * T > 0xFFFFFFFFull / HM_PLINCOMB_REC_WORDS(T)) return fail(c, HM_ERR_ARG, "%s: n = %u entries of %u terms are too many for one call", what, n, T);
+  if (hm_status st = rec_check(c, what, {{"p", p, lp, n * T}, {"x", x, lx0, n * T}, {"x", x, lx1, n * T}, {"addend", addend, la, addend ? n : 0}},
+                               {{"out", out, l0, n}, {"out", out, l1, n}}, mod_ids, n, {}))
+    return st;
+  if (n == 0) return HM_OK;
+  std::vector<uint32_t> recs((size_t)n * HM_PLINCOMB_REC_WORDS(T));
+  hm_plincomb_fill_recs(recs.data(), lp, lx0, lx1, addend != nullptr, la, l0, l1, mod_ids, n, T);
+  HmPlincombArgs a;
+  a.p = p; a.x = x; a.addend = addend ? addend : p; a.out = out; a.n_terms = T;
+  return rec_launch(c, k_plincomb, a, recs, n);
 }
 
 extern "C" hm_status hm_automorph(hm_ctx *c, const uint64_t *in, const uint32_t *in_limbs, uint64_t *out,

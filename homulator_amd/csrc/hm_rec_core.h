@@ -1,6 +1,6 @@
 // hm_rec_core.h — the record-table element-wise kernels: hm_tensor_dot, hm_tensor_square, hm_lincomb, hm_tensor_muladd, hm_reim_split,
-// hm_clincomb.  Per-thread bodies (no cross-thread state) shared by the HIP kernels (hm_backend.hip: k_tensor_dot, k_tensor_square, k_lincomb, k_tensor_muladd,
-// k_reim_split, k_clincomb) and the host emulator.
+// hm_clincomb, hm_plincomb.  Per-thread bodies (no cross-thread state) shared by the HIP kernels (hm_backend.hip: k_tensor_dot, k_tensor_square, k_lincomb,
+// k_tensor_muladd, k_reim_split, k_clincomb, k_plincomb) and the host emulator.
 //
 // A record-table kernel: one record per limb-poly of the call in a device table cached by content, read through the scalar cache (the index is
 // wave-uniform); k_tensor's geometry — a workgroup owns 512 coefficients of one record, a thread an aligned pair (16-byte accesses) — and ONE
@@ -8,7 +8,7 @@
 // kernel's own *_fill_recs.
 #pragma once
 #include <cstddef>
-#include "../../include/homulator_hip.h"   // HM_TENSOR_DOT_MAX_TERMS, HM_LINCOMB_MAX_TERMS, HM_TENSOR_MULADD_MAX_ADDENDS, HM_CLINCOMB_MAX_TERMS
+#include "../../include/homulator_hip.h"   // HM_TENSOR_DOT_MAX_TERMS, HM_LINCOMB_MAX_TERMS, HM_TENSOR_MULADD_MAX_ADDENDS, HM_CLINCOMB_MAX_TERMS, HM_PLINCOMB_MAX_TERMS
 #include "hm_elem_core.h"                  // HM_CONST_PROB_T, HM_CONST_MODS
 #include "hm_modarith.h"
 #include "hm_ntt_core.h"
@@ -31,7 +31,7 @@ HM_HD uint32_t hm_rec_lane_bytes(uint32_t chunk, uint32_t tid) { return (chunk *
 #define HM_DOT_ISSUED() ((void)0)
 #endif
 
-// ---- the term loop of the kernels that sum a run-time number of terms (pairs of hm_tensor_dot, terms of hm_lincomb and hm_clincomb, addends of hm_tensor_muladd)
+// ---- the term loop of the kernels that sum a run-time number of terms (pairs of hm_tensor_dot, terms of hm_lincomb, hm_clincomb and hm_plincomb, addends of hm_tensor_muladd)
 // term_at(t): the record words of term t; ld(l): the loads of the term with words l, issued; acc(p): its products into the sums.  Software-
 // pipelined by hand: two terms per round in two named register sets p0, p1 (no copy between them), the loads of term t + 1 issued before the
 // products of term t are formed, and the record words of a term requested a step before its loads.  The index of that request is clamped to the
@@ -528,4 +528,85 @@ HM_HD void hm_clincomb_thread(const HmClincombArgs &g, uint32_t entry, uint32_t 
   const HmLincombPair p0 = ld(term_at(0));
   hm_term_rounds(1, T, true, term_at(T > 1 ? 1u : 0u), p0, term_at, ld, [&](const HmLincombPair &v) { hm_lincomb_acc2(s, v); });
   hm_bst2(g.out + rec[1] * N, lane_bytes, hm_barrett_wide(s[0] + k, m), hm_barrett_wide(s[1] + k, m));
+}
+
+// ---- Sum of T ciphertexts, each times a plaintext, plus a plaintext on c0, in one pass over the 3T inputs (hm_plincomb; HPLINCOMB):
+//   o0 = sum_t p_t (.) x_t + p_0,   o1 = sum_t p_t (.) y_t      with p_t a limb-poly of plaintext t, x_t / y_t = c0 / c1 of ciphertext t, every
+// residue canonical.  A record is one output limb with BOTH components: the pair of p_t a thread loads serves the product with x_t and the one with
+// y_t, so a term costs three 16-byte loads where two separate sums would take four.  The raw 64 x 64 products are summed in TWO 128-bit
+// accumulators per coefficient (c0's and c1's), the addend goes into c0's, and each accumulator is reduced once: T <= HM_PLINCOMB_MAX_TERMS = 16
+// products below 2^120 are below 2^124, plus an addend below 2^60 below 2^125, and hm_barrett_wide takes any 128-bit value.  The result is the
+// canonical residue of the exact integer sum, hence bit-identical to the chain of MUL, MAC_ADD and ADD.  One form on both arithmetic back-ends:
+// 3T + 2 (+ 1) limb-polys per record and two wide multiplies per three loaded words.
+static_assert(HM_PLINCOMB_MAX_TERMS == 16, "either accumulator: 16 products below 2^120 plus an addend below 2^60 stay below 2^125");
+// a record = HM_PLINCOMB_REC_WORDS(T) 32-bit words (32 + 16 T bytes):
+//   (modulus id, limb of o0, limb of o1, T), (addend flag, addend limb, 0, 0), then per term (limb of p_t, limb of x_t, limb of y_t, 0)
+#define HM_PLINCOMB_REC_HEAD 8u
+#define HM_PLINCOMB_REC_WORDS(T) (HM_PLINCOMB_REC_HEAD + 4u * (T))
+struct HmPlincombArgs {
+  const uint64_t *p, *x, *addend;   // addend: any readable buffer when no record has one (never loaded from)
+  uint64_t *out;
+  const HmMod *mods;
+  const uint32_t *rec;   // device, [n_limbs][HM_PLINCOMB_REC_WORDS(n_terms)]
+  uint32_t logN, n_limbs, n_terms;
+};
+// The records of n entries from the entry point's limb lists (lp, lx0, lx1: [n][T]; l0, l1: [n]; la: [n], read with has_addend only).  Host side.
+inline void hm_plincomb_fill_recs(uint32_t *rec, const uint32_t *lp, const uint32_t *lx0, const uint32_t *lx1, bool has_addend, const uint32_t *la,
+                                  const uint32_t *l0, const uint32_t *l1, const uint32_t *mod_ids, uint32_t n, uint32_t T) {
+  for (uint32_t i = 0; i < n; ++i) {
+    uint32_t *r = rec + (size_t)i * HM_PLINCOMB_REC_WORDS(T);
+    r[0] = mod_ids[i]; r[1] = hm_rec_limb(l0, i); r[2] = hm_rec_limb(l1, i); r[3] = T;
+    r[4] = has_addend ? 1u : 0u; r[5] = has_addend ? hm_rec_limb(la, i) : 0u; r[6] = 0; r[7] = 0;
+    for (uint32_t t = 0; t < T; ++t) {
+      const uint32_t e = i * T + t;
+      uint32_t *w = r + HM_PLINCOMB_REC_HEAD + 4 * t;
+      w[0] = hm_rec_limb(lp, e); w[1] = hm_rec_limb(lx0, e); w[2] = hm_rec_limb(lx1, e); w[3] = 0;
+    }
+  }
+}
+struct HmPlincombLimbs {   // the limbs of (p_t, x_t, y_t) of one term: three words of the record
+  uint32_t p, x, y;
+};
+template <class REC>
+HM_HD HmPlincombLimbs hm_plincomb_limbs(REC rec, uint32_t t) {
+  const uint32_t w = HM_PLINCOMB_REC_HEAD + 4 * t;
+  return HmPlincombLimbs{rec[w], rec[w + 1], rec[w + 2]};
+}
+struct HmPlincombPair {   // the aligned pair of coefficients a thread owns of the plaintext and of both components of one term
+  uint64_t p[2], x[2], y[2];
+};
+struct HmPlincombAcc {   // one coefficient's two sums
+  hm_u128 c0, c1;
+};
+// three 16-byte loads from wave-uniform bases at the lane's offset
+HM_HD HmPlincombPair hm_plincomb_ld(const HmPlincombArgs &g, const HmPlincombLimbs &l, size_t N, uint32_t lane_bytes) {
+  HmPlincombPair v;
+  hm_bld2(g.p + l.p * N, lane_bytes, v.p[0], v.p[1]);
+  hm_bld2(g.x + l.x * N, lane_bytes, v.x[0], v.x[1]);
+  hm_bld2(g.x + l.y * N, lane_bytes, v.y[0], v.y[1]);
+  return v;
+}
+HM_HD void hm_plincomb_acc2(HmPlincombAcc (&s)[2], const HmPlincombPair &v) {
+  s[0].c0 += (hm_u128)v.p[0] * v.x[0];
+  s[0].c1 += (hm_u128)v.p[0] * v.y[0];
+  s[1].c0 += (hm_u128)v.p[1] * v.x[1];
+  s[1].c1 += (hm_u128)v.p[1] * v.y[1];
+}
+// thread tid of the workgroup that owns chunk `chunk` of record `entry`: 3T 16-byte loads (hm_term_rounds behind the loads of term 0), one more for
+// the addend behind a record-uniform flag, two 16-byte stores.  chunk < N / 512 (the launch has n N / 512 workgroups), so the last byte touched is
+// N * 8 - 1 of each limb-poly.
+HM_HD void hm_plincomb_thread(const HmPlincombArgs &g, uint32_t entry, uint32_t chunk, uint32_t tid) {
+  const size_t N = (size_t)1 << g.logN;
+  const uint32_t T = g.n_terms, lane_bytes = hm_rec_lane_bytes(chunk, tid);
+  const auto rec = HM_CONST_PROB_T(uint32_t, g.rec) + (size_t)entry * HM_PLINCOMB_REC_WORDS(T);
+  const HmMod m = HM_CONST_MODS(g.mods)[rec[0]];
+  uint64_t k[2] = {0, 0};
+  if (rec[4]) hm_bld2(g.addend + rec[5] * N, lane_bytes, k[0], k[1]);   // (record-uniform)
+  const auto term_at = [&](uint32_t t) { return hm_plincomb_limbs(rec, t); };
+  const auto ld = [&](const HmPlincombLimbs &l) { return hm_plincomb_ld(g, l, N, lane_bytes); };
+  const HmPlincombPair p0 = ld(term_at(0));
+  HmPlincombAcc s[2] = {{k[0], 0}, {k[1], 0}};
+  hm_term_rounds(1, T, true, term_at(T > 1 ? 1u : 0u), p0, term_at, ld, [&](const HmPlincombPair &v) { hm_plincomb_acc2(s, v); });
+  hm_bst2(g.out + rec[1] * N, lane_bytes, hm_barrett_wide(s[0].c0, m), hm_barrett_wide(s[1].c0, m));
+  hm_bst2(g.out + rec[2] * N, lane_bytes, hm_barrett_wide(s[0].c1, m), hm_barrett_wide(s[1].c1, m));
 }

@@ -25,7 +25,7 @@ SYMBOLS = [
     "hm_bconv_col", "hm_limbs_to_colslices", "hm_colslices_to_limbs", "hm_ntt_second_pass", "hm_ntt_ex", "hm_capability", "hm_inner_product_ex",
     "hm_inner_product_hoisted", "hm_inner_product_lintrans", "hm_inner_product_rotsum", "hm_inner_product_lintrans_multi",
     "hm_tensor_dot", "hm_inner_product_lintrans_id", "hm_inner_product_rotsum_init", "hm_ntt_mix_sub_scale_mul", "hm_ntt_mul",
-    "hm_ntt_lift", "hm_tensor_square", "hm_lincomb", "hm_tensor_muladd", "hm_reim_split", "hm_clincomb",
+    "hm_ntt_lift", "hm_tensor_square", "hm_lincomb", "hm_tensor_muladd", "hm_reim_split", "hm_clincomb", "hm_plincomb",
 ]
 
 
@@ -164,6 +164,7 @@ def load():
     L.hm_tensor_muladd.argtypes = [vp] + [vp] * 18 + [u32, u32, vp, vp, vp]
     L.hm_reim_split.argtypes = [vp] + [vp] * 9 + [u32]
     L.hm_clincomb.argtypes = [vp] + [vp] * 5 + [u32, u32, vp, vp, vp, vp]
+    L.hm_plincomb.argtypes = [vp] + [vp] * 11 + [u32, u32]
     L.hm_inner_product.argtypes = [vp] + [vp] * 7 + [u32, u32, u32]
     L.hm_automorph.argtypes = [vp, vp, vp, vp, vp, u32, u32]
     L.hm_ewe.argtypes = [vp, i32] + [vp] * 11 + [u32, vp]
@@ -445,6 +446,14 @@ class Context:
         ks = [_u64(v) for v in (scale_re, scale_im, addend_re, addend_im)]
         self._ck(self.L.hm_clincomb(self.h, src.ptr, keep[0][1], out.ptr, keep[1][1], keep[2][1], len(mod_ids), int(n_terms), ks[0][1], ks[1][1],
                                     ks[2][1], ks[3][1]))
+
+    def plincomb(self, p, p_limbs, x, x0_limbs, x1_limbs, out, o0_limbs, o1_limbs, mod_ids, n_terms, addend=None, addend_limbs=None):
+        """out[o0_limbs[i]] = sum_t p[p_limbs[i][t]] * x[x0_limbs[i][t]] + addend[addend_limbs[i]], out[o1_limbs[i]] = sum_t p[p_limbs[i][t]] *
+        x[x1_limbs[i][t]] per entry, coefficient by coefficient (hm_plincomb): the term lists are row-major [n][n_terms] (flat), the output and
+        addend lists and mod_ids [n] (a limb list None: the identity); addend None: no addend; buffers: anything with a device address `.ptr`"""
+        keep = [_u32(v) for v in (p_limbs, x0_limbs, x1_limbs, addend_limbs, o0_limbs, o1_limbs, mod_ids)]
+        self._ck(self.L.hm_plincomb(self.h, p.ptr, keep[0][1], x.ptr, keep[1][1], keep[2][1], None if addend is None else addend.ptr, keep[3][1],
+                                    out.ptr, keep[4][1], keep[5][1], keep[6][1], len(mod_ids), int(n_terms)))
 
     def inner_product(self, x, x_limbs, y, y_limbs, out, out_limbs, mod_ids, n_terms, n_out, x_galois=0):
         keep = [_u32(v) for v in (x_limbs, y_limbs, out_limbs, mod_ids)]

@@ -37,6 +37,8 @@ public:
   bool muladdHead = false;   // a tensor product's MAC2 (d1) that scalars, scaled addends and a constant follow (HMULADD): pass (5m) starts its record here
   bool reimHead = false;     // the ADD x + conj(x) of one limb and component (HREIM): pass (5r) starts its record here
   bool clincombHead = false; // the MUL_CONST a_1 x_1 of term 1 of a complex-weighted sum of ciphertexts (HCLINCOMB): pass (5c) starts its record here
+  bool plincombHead = false; // the MUL p_1 x_1 of term 1 of one component of a plaintext-weighted sum of ciphertexts (HPLINCOMB): pass (5p) starts its record here;
+                             // also the ADD of that sum's plaintext addend, which the pass takes behind the last term only if it is marked
   std::vector<uint32_t> inMods;  // BCONV: modulus ids of the inputs
   unsigned long long refInstructions = 0;  // upstream instructions this record stands for
   unsigned long long refExtra = 0;         // ... of records folded into a BCONV record (not scaled by its MAC-port count)
@@ -106,6 +108,13 @@ public:
   std::vector<uint64_t> clScalesRe, clScalesIm;
   bool clHasConst = false;
   uint64_t clConst = 0;
+  // (5p) sum of ciphertexts times plaintexts plus a plaintext on c0 (hm_plincomb): the MUL record p_1 x_1 of c0's chain that absorbed the MAC_ADD
+  // records behind it, the ADD of the addend, and the whole chain of c1 on the same plaintext limbs.  plOperands = (p_t, x_t, y_t) per term, in
+  // term order; plAddend = the plaintext limb added to c0 (plHasAddend); OutputOperand = c0's final sum, extraOutputs = c1's.  plOperands empty:
+  // not such a sum
+  std::vector<AddrType> plOperands;
+  bool plHasAddend = false;
+  AddrType plAddend = 0;
   // fused inner product (ops == IP): out_k = sum_j ipX[j] * ipY[k][j]; out_0 = OutputOperand, out_1 = extraOutputs[0]
   std::vector<AddrType> ipX;
   std::vector<std::vector<AddrType>> ipY;

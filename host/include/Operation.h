@@ -118,6 +118,7 @@ protected:
   std::unique_ptr<AddrManage> addrManager;  // made by makeInputs(): the temporaries start after the inputs
   std::vector<Ciphertext> cts;              // the input ciphertexts ct1, ct2, ... (HDOT: ct1 .. ct<2T>, HROTSUM: ct1 .. ct<G>)
   std::unique_ptr<Plaintext> ptx;           // the input plaintext pt
+  std::vector<Plaintext> levelPtx;          // the input plaintexts pt1, pt2, ... (pt0) of `level` limbs on the ciphertext basis (HPLINCOMB)
   std::vector<Plaintext> extPtx;            // the input plaintexts pt1, pt2, ... on the extended basis (HLINTRANS; HBSGS: pt<(i-1)R+r>)
   Arch *arch;
   Config *config;
@@ -135,7 +136,8 @@ protected:
   // the alpha special primes; seed + 4000 + 100000 r), then the named extra plaintexts `namedExt` on the extended basis too ((name, stream): seed +
   // stream; the identity step's pt0), then the address plan of the temporaries behind them
   typedef std::vector<std::pair<std::string, uint64_t>> NamedStreams;
-  void makeInputs(uint32_t ciphertexts, bool plaintext = false, uint32_t extPlaintexts = 0, const NamedStreams &namedExt = {});
+  // namedLevel: plaintexts of `level` limbs on the ciphertext basis, by name and stream (HPLINCOMB), behind everything else
+  void makeInputs(uint32_t ciphertexts, bool plaintext = false, uint32_t extPlaintexts = 0, const NamedStreams &namedExt = {}, const NamedStreams &namedLevel = {});
   // config key `identity` (0 or 1, default 0; read by the ops that have an identity step): the unrotated diagonal, DESIGN.md section 16
   bool identityStep(const std::string &op) const;
   // what the ops that hoist the ModUp over rotations (HROTATE_HOISTED, HLINTRANS, HBSGS) or sum rotations in front of one ModDown (HROTSUM) check
@@ -287,6 +289,16 @@ class HCLINCOMB : public OperationBase {
 public:
   HCLINCOMB(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
 };
+// hplincomb (build extension): out = (sum_t pt<t> (.) ct<t>.c0 + pt0, sum_t pt<t> (.) ct<t>.c1), a plaintext-weighted sum of T ciphertexts at one level
+// (config key terms = T as hlincomb: default 4, 1..16).  pt<t> are named input plaintexts of `level` limbs in evaluation form on the ciphertext basis
+// (synthetic: stream seed + 4000 + 100000 t, as hlintrans numbers its plaintexts; replaceable through writeBuffer("pt<t>", ...)); with config key
+// pl_addend = 1 one more, pt0 (stream seed + 4000 + 100000 * 17), is added to c0 only, as PADD's plaintext: the inner sum of a baby-step/giant-step
+// transform over rotations that already exist, masking and merging, a polynomial with slot-wise coefficients, a linear layer's bias.  No key, no
+// ModUp.  One output ciphertext out at the inputs' level, or through Rescale at level - 1 with config key rescale = 1.
+class HPLINCOMB : public OperationBase {
+public:
+  HPLINCOMB(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
+};
 class HROTSUM : public OperationBase {
 public:
   HROTSUM(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
@@ -334,7 +346,7 @@ class OpChain {
   std::vector<Arch *> archs;
   std::vector<OperationBase *> ops;
 public:
-  // ops: comma-separated list of hmult | hrotate | hadd | pmult | padd | hlintrans | hdot | hrotsum | hbsgs | hrescale | hmodraise | hsquare | hlincomb | hmuladd | hreim | hclincomb, e.g. "hmult,hrotate,hadd,hmult"; hrotate_hoisted (R output
+  // ops: comma-separated list of hmult | hrotate | hadd | pmult | padd | hlintrans | hdot | hrotsum | hbsgs | hrescale | hmodraise | hsquare | hlincomb | hmuladd | hreim | hclincomb | hplincomb, e.g. "hmult,hrotate,hadd,hmult"; hrotate_hoisted (R output
   // ciphertexts) only as the last op
   OpChain(const std::string &cfgPath, const std::string &opList, uint32_t maxLevel, uint32_t curLevel, uint32_t alpha,
           const std::map<std::string, uint32_t> &overrides = {});

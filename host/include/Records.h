@@ -94,6 +94,9 @@ inline std::vector<Read> recordReads(const Instruction &i) {
     for (AddrType a : i.reimOperands) v.push_back({a, Role::Operand, kNoDigit});
   } else if (!i.clOperands.empty()) {    // (5c): the input of every term; the stored monomial is not read
     for (AddrType a : i.clOperands) v.push_back({a, Role::Operand, kNoDigit});
+  } else if (!i.plOperands.empty()) {    // (5p): plaintext and both components of every term, then the addend
+    for (AddrType a : i.plOperands) v.push_back({a, Role::Operand, kNoDigit});
+    if (i.plHasAddend) v.push_back({i.plAddend, Role::Operand, kNoDigit});
   } else if (i.ops == MULT) {
     for (int b = 0; b < 4; ++b)
       if (eweOperandMask(i.opcode) & (1 << b)) v.push_back({i.operandList[b], Role::Operand, kNoDigit});

@@ -33,7 +33,8 @@ struct Arch::Launch {
               L_LINCOMB,                                     // (5l) the sum of scaled polynomials plus a constant
               L_TENSOR_MULADD,                               // (5m) the scaled tensor product plus scaled addends plus a constant
               L_REIM,                                        // (5r) the sum and the rotated difference of a polynomial and its conjugate
-              L_CLINCOMB } kind;                             // (5c) the sum of polynomials times a + b X^(N/2) plus a constant
+              L_CLINCOMB,                                    // (5c) the sum of polynomials times a + b X^(N/2) plus a constant
+              L_PLINCOMB } kind;                             // (5p) the sum of ciphertexts times plaintexts plus a plaintext on c0, both components
   std::vector<uint32_t> hoistG;   // L_IP_HOISTED: the Galois element of every rotation (a: digits [n][T], b: keys [r][n][2][T], out: [r][n][2])
                                   // L_IP_LINTRANS: the same, with c: plaintexts [r][n], d: addend source [n] / out1: addend output [n] (HM_NO_LIMB: none; both
                                   // empty: no entry has one), out: [n][2]
@@ -62,6 +63,8 @@ struct Arch::Launch {
                                   // L_TENSOR_SQUARE: a = c0, c = c1, out, out1, out2 = d0, d1, d2 [n]; k: the scalars [n], addK: the constants [n] (empty: none)
                                   // L_REIM: a = the polynomial, c = its conjugate, out = the sum, out1 = the rotated difference [n]
                                   // L_CLINCOMB: as L_LINCOMB with k: the real parts a_t, maK: the monomial parts b_t [n][dotTerms]
+                                  // L_PLINCOMB: terms per record (b: the plaintexts, x0, x1: c0, c1 of the ciphertexts [n][dotTerms]; d: the addend [n], empty:
+                                  // none; out, out1: the sums of c0, c1 [n])
   uint32_t maAddends = 0;         // L_TENSOR_MULADD: addends per record (a, b, c, d, out, out1, out2 as L_TENSOR; x0, x1: c0, c1 of the addends [n][maAddends];
   std::vector<uint32_t> x0, x1;   // k: the scalars [n], maK: the addend scalars [n][maAddends], addK: the constants [n]; k / addK empty: none)
   std::vector<uint64_t> maK;
@@ -174,6 +177,9 @@ Arch::Arch(Config *cfg) : config(cfg) {
   // (5c) hclincomb: per term the MUL_CONST, the MUL by the evaluation form of -X^(N/2) with its MUL_CONST and the ADD of both, the ADDs between the
   // terms and the ADD_CONST behind them become one hm_clincomb launch.  Config key fuse_clincomb (default 1).
   fuseClincomb = cfg->getValueOr("fuse_clincomb", 1) != 0;
+  // (5p) hplincomb: the MUL and the MAC_ADDs of both components and the ADD of the plaintext addend become one hm_plincomb launch.  Config key
+  // fuse_plincomb (default 1).
+  fusePlincomb = cfg->getValueOr("fuse_plincomb", 1) != 0;
   // (4p) pmult with rescale = 1: the products are formed by the rescale's transforms while they load.  Config key fuse_pmul_rescale: 1 / 0 = always /
   // never; not given = where it was measured faster than the three-launch plan: everywhere but the generic back-end's launches
   // inside the one-launch form's limit, which has no product form there (Planner::productOperands)
@@ -341,6 +347,7 @@ int partKey(const Instruction &i) {
   if (!i.maOperands.empty()) return 8700 + 4 * (int)i.maAddScales.size() + (i.maHasScale ? 1 : 0) + (i.maHasConst ? 2 : 0);   // 8700+: scaled product plus addends, by addends and what it absorbed
   if (!i.reimOperands.empty()) return 8400;                                                                // 8400: sum and rotated difference of a polynomial and its conjugate
   if (!i.clOperands.empty()) return 8800 + (int)i.clOperands.size();                                       // 8800+: sum of polynomials times a + b X^(N/2), by terms
+  if (!i.plOperands.empty()) return 8900 + 2 * ((int)i.plOperands.size() / 3) + (i.plHasAddend ? 1 : 0);   // 8900+: sum of ciphertexts times plaintexts, by terms and addend
   if (i.fusedTensor) return 200;                                                                           // 200: tensor product
   if (i.fusedSubScale && i.fMinuendB) return i.fMix ? 211 : 209;                                           // 209 / 211: ... with a product minuend (4p)
   if (i.fusedSubScale) return (i.fMix ? 203 : 201) + (i.fConvIn.empty() ? 0 : 4);                          // 201 / 203: fused forward transform, plain / merged; 205 / 207: with its conversion
@@ -514,6 +521,7 @@ struct Arch::LaunchBuilder {
   void tensorMulAdd(Launch &L, Recs recs);
   void reim(Launch &L, Recs recs);
   void clincomb(Launch &L, Recs recs);
+  void plincomb(Launch &L, Recs recs);
   void nttSubScale(Launch &L, Recs recs);
   void copy(Launch &L, Recs recs);
   void transform(Launch &L, Recs recs);
@@ -742,6 +750,23 @@ void Arch::LaunchBuilder::clincomb(Launch &L, Recs recs) {
   L.bytes = (L.dotTerms + 1ull) * LP * recs.size();   // every input read once, the sum written once
 }
 
+// (5p) b = the plaintext, x0 / x1 = c0 / c1 of the ciphertext of every term [n][T]; d = the addend [n] (empty: no record has one); out / out1 = the
+// sums of c0 / c1 [n] (hm_plincomb).  The part key keeps records of different term counts apart, and those with an addend from those without
+void Arch::LaunchBuilder::plincomb(Launch &L, Recs recs) {
+  L.kind = Launch::L_PLINCOMB; L.statKey = "EWE";
+  L.dotTerms = (uint32_t)recs[0]->plOperands.size() / 3;
+  const bool addend = recs[0]->plHasAddend;
+  for (Instruction *i : recs) {
+    for (uint32_t t = 0; t < L.dotTerms; ++t) {
+      L.b.push_back(limb(i->plOperands[3 * t])); L.x0.push_back(limb(i->plOperands[3 * t + 1])); L.x1.push_back(limb(i->plOperands[3 * t + 2]));
+    }
+    if (addend) L.d.push_back(limb(i->plAddend));
+    L.out.push_back(limb(i->OutputOperand)); L.out1.push_back(limb(i->extraOutputs[0]));
+    L.mods.push_back(i->mod_id);
+  }
+  L.bytes = (3ull * L.dotTerms + 2 + (addend ? 1 : 0)) * LP * recs.size();   // plaintext and both components of every term read once, two sums written
+}
+
 // fused forward transform (4, 4b, 9, 12)
 void Arch::LaunchBuilder::nttSubScale(Launch &L, Recs recs) {
   L.kind = Launch::L_NTT_SUBSCALE; L.statKey = "NTT";
@@ -914,6 +939,7 @@ void Arch::LaunchBuilder::emitCompute(const Group &group, Launches &front, Launc
   else if (!f->maOperands.empty()) tensorMulAdd(*L, recs);
   else if (!f->reimOperands.empty()) reim(*L, recs);
   else if (!f->clOperands.empty()) clincomb(*L, recs);
+  else if (!f->plOperands.empty()) plincomb(*L, recs);
   else if (f->fusedTensor) tensor(*L, recs);
   else if (f->fusedSubScale) nttSubScale(*L, recs);
   else if (f->ops == NTT && f->passthrough) copy(*L, recs);
@@ -1339,7 +1365,7 @@ void Arch::prepare() {
 
 static const char *const kLaunchKindNames[] = {"NTT", "INTT", "EWE", "BCONV", "AUTO", "NTT_SUBSCALE", "TENSOR", "EXCH_IN", "EXCH_OUT", "REPLICATE", "IP", "NTT_IP",
                                                "BCONV_COL", "EXCH_IN_COL", "EXCH_OUT_COL", "IP_HOISTED", "IP_LINTRANS", "TENSOR_DOT", "IP_ROTSUM",
-                                               "IP_LINTRANS_MULTI", "TENSOR_SQUARE", "LINCOMB", "TENSOR_MULADD", "REIM", "CLINCOMB"};
+                                               "IP_LINTRANS_MULTI", "TENSOR_SQUARE", "LINCOMB", "TENSOR_MULADD", "REIM", "CLINCOMB", "PLINCOMB"};
 
 // Per-launch device time (SURVEY.md §8d "per-stage hipEvent times", exchange time at N > 1): every launch of the plan
 // bracketed by its own event pair, in plan order so that the data dependencies (and, sharded, the collectives) line up.
@@ -1397,6 +1423,8 @@ std::string Arch::planText() const {
       out += " terms=" + std::to_string(l->dotTerms) + " const=" + (l->addK.empty() ? "0" : "1");
     if (l->kind == Launch::L_CLINCOMB)   // (5c): terms summed per record, and whether a constant follows
       out += " terms=" + std::to_string(l->dotTerms) + " const=" + (l->addK.empty() ? "0" : "1");
+    if (l->kind == Launch::L_PLINCOMB)   // (5p): terms summed per record, and whether a plaintext addend follows
+      out += " terms=" + std::to_string(l->dotTerms) + " addend=" + (l->d.empty() ? "0" : "1");
     if (l->kind == Launch::L_TENSOR_MULADD)   // (5m): addends per record, and what the records absorbed
       out += " addends=" + std::to_string(l->maAddends) + " scale=" + (l->k.empty() ? "0" : "1") + " const=" + (l->addK.empty() ? "0" : "1");
     if (l->kind == Launch::L_IP_LINTRANS)   // (6l): entries that also form the addend output
@@ -1596,6 +1624,10 @@ void Arch::enqueue(Launch &l) {
   case Launch::L_CLINCOMB:
     st = hm_clincomb(ctx, pool, l.a.data(), pool, l.out.data(), l.mods.data(), cnt, l.dotTerms, l.k.data(), l.maK.data(),
                      l.addK.empty() ? nullptr : l.addK.data(), nullptr);
+    break;
+  case Launch::L_PLINCOMB:
+    st = hm_plincomb(ctx, pool, l.b.data(), pool, l.x0.data(), l.x1.data(), l.d.empty() ? nullptr : pool, l.d.empty() ? nullptr : l.d.data(), pool,
+                     l.out.data(), l.out1.data(), l.mods.data(), cnt, l.dotTerms);
     break;
   case Launch::L_EXCH_IN:
     st = hm_limbs_to_slices(ctx, pool, l.exLimbs.data(), l.exOwners.data(), (uint32_t)l.exLimbs.size(), l.slicesIn);

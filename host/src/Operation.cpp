@@ -375,7 +375,7 @@ OperationBase::~OperationBase() {
   for (auto &kv : DataInsMap)
     for (Instruction *i : kv.second) delete i;
 }
-void OperationBase::makeInputs(uint32_t ciphertexts, bool plaintext, uint32_t extPlaintexts, const NamedStreams &namedExt) {
+void OperationBase::makeInputs(uint32_t ciphertexts, bool plaintext, uint32_t extPlaintexts, const NamedStreams &namedExt, const NamedStreams &namedLevel) {
   for (uint32_t i = 0; i < ciphertexts; i++) {
     cts.emplace_back(level_, N, Datapool, batchSize);
     const std::vector<AddrType> c0 = cts[i].getC0Addr(), c1 = cts[i].getC1Addr();
@@ -407,6 +407,13 @@ void OperationBase::makeInputs(uint32_t ciphertexts, bool plaintext, uint32_t ex
     const std::vector<AddrType> pt = extPtx.back().getC0Addr();
     arch->registerLimbs(pt);
     arch->addInputFill(InputFill{pt, extMods, seed + ns.second});
+    namedInputs[ns.first] = pt;
+  }
+  for (const auto &ns : namedLevel) {   // behind everything else: an op without them keeps its address plan
+    levelPtx.emplace_back(level_, N, Datapool, batchSize);
+    const std::vector<AddrType> pt = levelPtx.back().getC0Addr();
+    arch->registerLimbs(pt);
+    arch->addInputFill(InputFill{pt, range(0, level_), seed + ns.second});
     namedInputs[ns.first] = pt;
   }
   addrManager.reset(new AddrManage(Datapool.back() + 1, batchSize));
@@ -1107,6 +1114,62 @@ HCLINCOMB::HCLINCOMB(std::string labelName, uint32_t maxLevel, uint32_t currentL
   finishConstruction();
 }
 
+// hplincomb (build extension).  Per component k, with x_t = ct<t>.c<k> and p_t = pt<t>, existing opcodes only:
+//   PLinComb_Mul_(1)_C<k> = p_1 (.) x_1 (MUL),  PLinComb_Mac_(t)_C<k> = p_t (.) x_t + the running sum (MAC_ADD) for t >= 2,
+// and with pl_addend = 1 PLinComb_Addend_C0 = the sum of c0 plus pt0 (ADD, on c0 only as PADD's plaintext).  The last buffer of a component is
+// PLinCombOutput(k).  The ciphertext is operand a and the plaintext operand b, as PMULT's: the two chains then share no a operand, so pass (6)
+// never takes them for the two keys of a key product.  Unfused, the stages run as element-wise launches; fused, pass (5p) of Arch::fusePasses
+// (Planner.cpp) turns the two chains of a limb into one record of ONE launch.
+HPLINCOMB::HPLINCOMB(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch)
+    : OperationBase("HPLINCOMB", labelName, cfg, _arch, maxLevel, currentLevel, alpha) {
+  if (arch->backend() == Arch::BACKEND_SIM) throw std::runtime_error("hplincomb: backend = sim has no such op (the reference sums no plaintext products)");
+  if (arch->world() > 1) throw std::runtime_error("hplincomb: world > 1 is not supported (the sharded plan is not built)");
+  const uint32_t T = cfg->getValueOr("terms", 4);
+  if (T < 1 || T > 16) throw std::runtime_error("hplincomb: terms = " + S(T) + ", must be in [1, 16]");
+  const uint32_t pl = cfg->getValueOr("pl_addend", 0);
+  if (pl > 1) throw std::runtime_error("hplincomb: pl_addend = " + S(pl) + ", must be 0 or 1");
+  const bool addend = pl == 1, rescale = rescaleKey("hplincomb");
+  NamedStreams pts;
+  for (uint32_t t = 1; t <= T; ++t) pts.push_back({"pt" + S(t), 4000 + 100000ull * t});
+  if (addend) pts.push_back({"pt0", 4000 + 100000ull * 17});
+  makeInputs(T, /*plaintext=*/false, /*extPlaintexts=*/0, NamedStreams{}, pts);
+  std::array<std::vector<AddrType>, 2> out;
+  for (uint32_t k = 0; k < 2; k++) {
+    const std::string C = "_C" + S(k);
+    const bool addendHere = addend && k == 0;
+    Limbs sum;
+    for (uint32_t t = 1; t <= T; ++t) {
+      const std::string stage = std::string(t == 1 ? "PLinComb_Mul_(" : "PLinComb_Mac_(") + S(t) + ")" + C;
+      const bool last = t == T && !addendHere;
+      PerLimb s{labelName + "_" + stage + "_Level(", ")", range(0, currentLevel),
+                alloc(last ? "PLinCombOutput(" + S(k) + ")" : "PLinCombSum(" + S(t) + ")" + C, currentLevel)};
+      s.a = component(t - 1, k);
+      s.b = namedInputs.at("pt" + S(t));
+      const Limbs before = sum;
+      if (t > 1) {
+        s.c = before.addr;
+        s.after = {&before.from};
+      }
+      sum = {s.out, eweLimbs(&insgener, t == 1 ? EWE_MUL : EWE_MAC_ADD, s)};
+      driver.dispatchInstructions(stage, sum.from);
+      if (t == 1)
+        for (const INSGROUP &g : sum.from) g[0]->plincombHead = true;
+    }
+    if (addendHere) {
+      PerLimb a{labelName + "_PLinComb_Addend" + C + "_Level(", ")", range(0, currentLevel), alloc("PLinCombOutput(" + S(k) + ")", currentLevel)};
+      const Limbs before = sum;
+      a.a = before.addr; a.c = namedInputs.at("pt0"); a.after = {&before.from};
+      sum = {a.out, eweLimbs(&insgener, EWE_ADD, a)};
+      driver.dispatchInstructions("PLinComb_Addend" + C, sum.from);
+      for (const INSGROUP &g : sum.from) g[0]->plincombHead = true;   // the addend belongs to the marked sum
+    }
+    out[k] = sum.addr;
+  }
+  if (rescale) setRescaledOutput("out", out);
+  else for (uint32_t k = 0; k < 2; k++) setOutput("out", k, out[k]);
+  finishConstruction();
+}
+
 // hmuladd (build extension).  out = Rescale(d0 + ks0(d2)), Rescale(d1 + ks1(d2)) with
 //   d0 = s a b + sum_t u_t x_t + k,  d1 = s (a d + c b) + sum_t u_t y_t,  d2 = s c d
 // (a, c = ct1.c0, ct1.c1; b, d = ct2.c0, ct2.c1; x_t, y_t = ct<2+t>.c0, .c1): one node of a polynomial evaluation, T_{a+b} = 2 T_a T_b - T_{|a-b|} or
@@ -1423,6 +1486,7 @@ static OperationBase *makeOp(const std::string &o, uint32_t maxLevel, uint32_t l
   if (o == "hmuladd") return new HMULADD("test_hmuladd", maxLevel, level, alpha, cfg, arch);
   if (o == "hreim") return new HREIM("test_hreim", maxLevel, level, alpha, cfg, arch);
   if (o == "hclincomb") return new HCLINCOMB("test_hclincomb", maxLevel, level, alpha, cfg, arch);
+  if (o == "hplincomb") return new HPLINCOMB("test_hplincomb", maxLevel, level, alpha, cfg, arch);
   throw std::runtime_error("Error operation requirement, please double confirm!");
 }
 

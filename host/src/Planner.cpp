@@ -110,6 +110,7 @@ struct Arch::Planner {
   void tensorMulAdd();     // 5m
   void realImaginary();    // 5r
   void complexCombination();   // 5c
+  void plaintextCombination(); // 5p
   void keyProduct();       // 6
   // what (6m/6l), (6s) and (6h) all recognise: the live two-key key-product records whose digits are all automorphisms, by one element per record, of
   // the same materialised digits and are read by nothing else; per (modulus, unrotated digits) the records and their automorphisms, in stage order
@@ -155,6 +156,7 @@ void Arch::fusePasses(std::vector<Stage> &st) {
   if (fuseMuladd) p.tensorMulAdd();
   if (fuseReim) p.realImaginary();
   if (fuseClincomb) p.complexCombination();
+  if (fusePlincomb) p.plaintextCombination();
   p.keyProduct();
   // (6m, 6l) before (6s) and (6h): the records it merges are the ones (6h) would claim, and none of them is (6s)'s (their outputs go into products,
   // not into sums).  fuse_bsgs: the groups with several sums, fuse_lintrans: the ones with one
@@ -294,7 +296,7 @@ void Arch::Planner::productOperands() {
   }
   auto productFor = [&](AddrType a, Instruction *reader) -> Instruction * {
     Instruction *m = producerOf(a);
-    if (!m || !isMul(m, reader->mod_id) || m->fusedTensor || !onlyReader(rd, a, reader)) return nullptr;
+    if (!m || !isMul(m, reader->mod_id) || m->fusedTensor || m->plincombHead || !onlyReader(rd, a, reader)) return nullptr;   // (a one-term hplincomb keeps its own launch: (5p))
     if (producerOf(m->operandList[0]) || producerOf(m->operandList[1])) return nullptr;
     return m;
   };
@@ -732,6 +734,74 @@ void Arch::Planner::complexCombination() {
     }
     c->OutputOperand = sum;
     producer[sum] = c;
+    place.moveTo(c, last);   // to where its last link stood
+  }
+}
+
+// (5p) sum of ciphertexts times plaintexts plus a plaintext on c0 (hplincomb): from a MUL record p_1 (.) x_1 that the builder marked as term 1 of
+//      one component's sum (plincombHead).  A chain is that record followed, term after term, by ONE MAC_ADD record of the same modulus whose
+//      operand c is the running sum, read by nothing else; behind the last term, ONE marked ADD of the sum (operand a) and a limb that nothing
+//      produces (the plaintext addend).  Two chains of one modulus whose plaintext limbs (operand b) coincide term by term are the two components
+//      of one output limb: they merge into the marked record of the chain that carries the addend, or of the earlier one if neither does.
+//      hm_plincomb loads every plaintext pair once for both products, sums the raw products of each component in its own accumulator, adds the
+//      addend to c0's and stores the two final sums only.  A chain without a partner stays as it is.  Never written: the 2 (T - 1) partial sums
+//      and the sum in front of the addend.  The record takes the place of the last record it absorbs.
+//      Only the builder of HPLINCOMB sets the mark: the pass matches nothing in any other op.
+//      Sets on the marked record: plOperands, plHasAddend, plAddend, OutputOperand, extraOutputs.
+void Arch::Planner::plaintextCombination() {
+  Readers rd = readers();
+  Placement place(st);
+  struct Sum { std::vector<Instruction *> terms; Instruction *add = nullptr; };
+  typedef std::pair<uint32_t, std::vector<AddrType>> Key;   // modulus, the plaintext limb of every term
+  std::map<Key, std::vector<Sum>> byPlain;
+  std::vector<Key> order;   // first appearance
+  for (auto &s : st)
+    for (Instruction *i : s.ins) {
+      if (!live(i) || !i->plincombHead || !isMul(i, i->mod_id) || i->fusedTensor || !i->plOperands.empty()) continue;
+      Sum c;
+      c.terms = {i};
+      while (c.terms.size() < HM_PLINCOMB_MAX_TERMS) {
+        Instruction *next = soleReader(rd, c.terms.back()->OutputOperand, EWE_MAC_ADD, i->mod_id);
+        if (!next || next->operandList[2] != c.terms.back()->OutputOperand || next->operandList[0] == next->operandList[2] ||
+            next->operandList[1] == next->operandList[2])
+          break;
+        c.terms.push_back(next);
+      }
+      const AddrType sum = c.terms.back()->OutputOperand;
+      Instruction *add = soleReader(rd, sum, EWE_ADD, i->mod_id);
+      if (add && add->plincombHead && add->operandList[0] == sum && add->operandList[2] != sum && !producerOf(add->operandList[2])) c.add = add;
+      Key key{i->mod_id, {}};
+      for (Instruction *t : c.terms) key.second.push_back(t->operandList[1]);
+      if (!byPlain.count(key)) order.push_back(key);
+      byPlain[key].push_back(c);
+    }
+  for (const Key &key : order) {
+    std::vector<Sum> &sums = byPlain[key];
+    if (sums.size() != 2 || (sums[0].add && sums[1].add)) continue;
+    const Sum &s0 = sums[1].add ? sums[1] : sums[0], &s1 = sums[1].add ? sums[0] : sums[1];
+    Instruction *c = s0.terms[0];
+    for (size_t t = 0; t < s0.terms.size(); ++t) {
+      c->plOperands.push_back(s0.terms[t]->operandList[1]);
+      c->plOperands.push_back(s0.terms[t]->operandList[0]);
+      c->plOperands.push_back(s1.terms[t]->operandList[0]);
+    }
+    Instruction *last = c;
+    auto take = [&](Instruction *i) {
+      absorb(c, i);
+      if (place.after(i, last)) last = i;
+    };
+    for (Instruction *i : s0.terms) take(i);
+    for (Instruction *i : s1.terms) take(i);
+    AddrType out0 = s0.terms.back()->OutputOperand;
+    if (s0.add) {
+      c->plHasAddend = true;
+      c->plAddend = s0.add->operandList[2];
+      take(s0.add);
+      out0 = s0.add->OutputOperand;
+    }
+    c->OutputOperand = out0;
+    c->extraOutputs = {s1.terms.back()->OutputOperand};
+    for (const Write &w : recordWrites(*c)) producer[w.addr] = c;
     place.moveTo(c, last);   // to where its last link stood
   }
 }

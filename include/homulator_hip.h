@@ -259,6 +259,24 @@ hm_status hm_clincomb(hm_ctx *ctx, const uint64_t *in, const uint32_t *in_limbs,
                       const uint32_t *mod_ids, uint32_t n, uint32_t n_terms, const uint64_t *scale_re, const uint64_t *scale_im,
                       const uint64_t *addend_re, const uint64_t *addend_im);
 
+/* K3, sum of n_terms ciphertexts, each times a plaintext limb-poly, plus a plaintext on c0, in one pass over the 3 n_terms inputs (HPLINCOMB,
+ * DESIGN.md section 24): for entry i (one output limb, both components), with p_t = p[p_limbs[i * n_terms + t]], x_t = x[x0_limbs[i * n_terms + t]]
+ * and y_t = x[x1_limbs[i * n_terms + t]], coefficient by coefficient,
+ *   out[o0_limbs[i]] = sum_t p_t * x_t + addend[addend_limbs[i]],   out[o1_limbs[i]] = sum_t p_t * y_t,   t < n_terms <= 16,
+ * every residue canonical.  Each p_t is loaded once for both products.  The result is the canonical residue of the exact sum: bit-identical,
+ * per term and component, to HM_OP_MUL (term 0) / HM_OP_MAC_ADD (the others) and, for the addend, HM_OP_ADD, none of whose intermediates is
+ * written (3 n_terms + 2 limb-polys per entry, one more with the addend, where that chain moves 8 n_terms - 2).  The term lists are row-major,
+ * [n][n_terms] (the same limb-poly may appear in several entries and terms: a plaintext limb usually serves every copy of a batch); o0_limbs,
+ * o1_limbs, addend_limbs and mod_ids have n entries; a null limb list is the identity.  addend == NULL: no addend (addend_limbs is not read).
+ * p, x and addend may be different allocations or one.  The records live in a device table: one launch serves any n, and the call is safe under
+ * graph capture once it has run with the same lists.  HM_ERR_ARG: a null buffer or a null mod_ids, n_terms outside 1..16, a limb or modulus id
+ * out of range, an output limb-poly that overlaps (by address range, not by base pointer) an input limb-poly, the addend or another output
+ * limb-poly, the two outputs of one entry included.  n = 0 is HM_OK. */
+#define HM_PLINCOMB_MAX_TERMS 16
+hm_status hm_plincomb(hm_ctx *ctx, const uint64_t *p, const uint32_t *p_limbs, const uint64_t *x, const uint32_t *x0_limbs,
+                      const uint32_t *x1_limbs, const uint64_t *addend, const uint32_t *addend_limbs, uint64_t *out,
+                      const uint32_t *o0_limbs, const uint32_t *o1_limbs, const uint32_t *mod_ids, uint32_t n, uint32_t n_terms);
+
 /* K5 — inner product with the evaluation key in one pass: for limb i, out[i][k] = sum_{j < n_terms}
  * x[i][j] * y[i][k][j], k < n_out (n_terms <= 4 digits, n_out <= 2 keys).  Limb lists are row-major:
  * x_limbs[i * n_terms + j], y_limbs[(i * n_out + k) * n_terms + j], out_limbs[i * n_out + k].  Replaces
