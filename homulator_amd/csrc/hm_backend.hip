@@ -512,6 +512,8 @@ __global__ void __launch_bounds__(256) k_reim_split(HmReimArgs a) { hm_rec_block
 __global__ void __launch_bounds__(256) k_clincomb(HmClincombArgs a) { hm_rec_block<hm_clincomb_thread>(a); }
 // sum of T ciphertexts, each times a plaintext limb-poly loaded once for both components, plus a plaintext on c0
 __global__ void __launch_bounds__(256) k_plincomb(HmPlincombArgs a) { hm_rec_block<hm_plincomb_thread>(a); }
+// scaled sum of T tensor products plus a linear combination of further ciphertexts plus a constant, T and A run-time loops
+__global__ void __launch_bounds__(256) k_tensor_dotadd(HmTensorDotAddArgs a) { hm_rec_block<hm_tensor_dotadd_thread>(a); }
 
 // 16-byte units per thread of the element-wise kernel, 512 coefficients apart, all loads in flight before the first use.  1: 89 600 workgroups for a batch of
 // ten hadd; 2 / 4 measured padd +3 / +5 %, pmult +1 %, hadd within the noise (tools/r06_ewe_ab.sh): not worth a second shape of the kernel's launch
@@ -1760,7 +1762,7 @@ static hm_status rec_check(hm_ctx *c, const char *what, std::initializer_list<Op
       for (uint32_t t = 0; k.v && t < k.per; ++t) {
         const uint64_t v = k.v[(size_t)i * k.per + t];
         if (v < q && (v || !k.nonzero)) continue;
-        if (k.rows) return fail(c, HM_ERR_ARG, "%s: %s[%u][%u] is not reduced", what, k.name, i, t);
+        if (k.rows) return fail(c, HM_ERR_ARG, "%s: %s[%u][%u] is %s", what, k.name, i, t, v ? "not reduced" : "zero");
         return fail(c, HM_ERR_ARG, "%s: %s[%u] is %s", what, k.name, i, v ? "not reduced" : "zero");
       }
   }
@@ -1887,6 +1889,37 @@ extern "C" hm_status hm_tensor_muladd(hm_ctx *c, const uint64_t *pa, const uint3
   HmTensorMulAddArgs a;
   a.a = pa; a.b = pb; a.c = pc; a.d = pd; a.x = A ? px : pa; a.o0 = o0; a.o1 = o1; a.o2 = o2; a.n_addends = A;
   return rec_launch(c, k_tensor_muladd, a, recs, n);
+}
+
+// scaled sum of n_terms tensor products plus n_addends scaled ciphertexts plus a constant: operand lists and pair scalars [n][n_terms], addend
+// lists and scalars [n][n_addends], output lists and constants [n]
+extern "C" hm_status hm_tensor_dotadd(hm_ctx *c, const uint64_t *pa, const uint32_t *la, const uint64_t *pb, const uint32_t *lb, const uint64_t *pc,
+                                      const uint32_t *lc, const uint64_t *pd, const uint32_t *ld, const uint64_t *px, const uint32_t *lx0,
+                                      const uint32_t *lx1, uint64_t *o0, const uint32_t *l0, uint64_t *o1, const uint32_t *l1, uint64_t *o2,
+                                      const uint32_t *l2, const uint32_t *mod_ids, uint32_t n, uint32_t n_terms, uint32_t n_addends,
+                                      const uint64_t *scale, const uint64_t *add_scale, const uint64_t *addend) {
+  static const char *const what = "hm_tensor_dotadd";
+  if (!c) return HM_ERR_ARG;
+  HM_TABLE_CALL(c);
+  if (!pa || !pb || !pc || !pd || !o0 || !o1 || !o2) return fail(c, HM_ERR_ARG, "%s: null buffer", what);
+  const uint32_t T = n_terms, A = n_addends;
+  if (T == 0 || T > HM_DOTADD_MAX_TERMS) return fail(c, HM_ERR_ARG, "%s: n_terms = %u, must be in [1, %d]", what, T, HM_DOTADD_MAX_TERMS);
+  if (A > HM_DOTADD_MAX_ADDENDS) return fail(c, HM_ERR_ARG, "%s: n_addends = %u, must be in [0, %d]", what, A, HM_DOTADD_MAX_ADDENDS);
+  if (A > 0 && !px) return fail(c, HM_ERR_ARG, "%s: null buffer", what);
+  if (A > 0 && (!lx0 || !lx1)) return fail(c, HM_ERR_ARG, "%s: x0_limbs or x1_limbs is null", what);
+  if (A > 0 && !add_scale) return fail(c, HM_ERR_ARG, "%s: add_scale is null", what);
+  if ((uint64_t)n > 0xFFFFFFFFull / (HM_DOTADD_REC_WORDS(T, A) * sizeof(uint32_t)))
+    return fail(c, HM_ERR_ARG, "%s: n = %u entries of %u terms and %u addends are too many for one call", what, n, T, A);
+  if (hm_status st = rec_check(c, what, {{"a", pa, la, n * T}, {"b", pb, lb, n * T}, {"c", pc, lc, n * T}, {"d", pd, ld, n * T}, {"x", px, lx0, n * A}, {"x", px, lx1, n * A}},
+                               {{"o0", o0, l0, n}, {"o1", o1, l1, n}, {"o2", o2, l2, n}}, mod_ids, n,
+                               {{"scale", scale, true, true, T}, {"add_scale", add_scale, false, true, A}, {"addend", addend, false}}))
+    return st;
+  if (n == 0) return HM_OK;
+  std::vector<uint32_t> recs((size_t)n * HM_DOTADD_REC_WORDS(T, A));
+  hm_tensor_dotadd_fill_recs(recs.data(), la, lb, lc, ld, lx0, lx1, l0, l1, l2, mod_ids, rec_moduli(c, mod_ids, n).data(), n, T, A, scale, add_scale, addend);
+  HmTensorDotAddArgs a;
+  a.a = pa; a.b = pb; a.c = pc; a.d = pd; a.x = A ? px : pa; a.o0 = o0; a.o1 = o1; a.o2 = o2; a.n_terms = T; a.n_addends = A;
+  return rec_launch(c, k_tensor_dotadd, a, recs, n);
 }
 
 // o_re = x + y, o_im = U (.) (x - y) with U the evaluation form of -X^(N/2), derived here from the context's own roots

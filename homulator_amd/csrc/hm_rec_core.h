@@ -1,6 +1,6 @@
 // hm_rec_core.h — the record-table element-wise kernels: hm_tensor_dot, hm_tensor_square, hm_lincomb, hm_tensor_muladd, hm_reim_split,
-// hm_clincomb, hm_plincomb.  Per-thread bodies (no cross-thread state) shared by the HIP kernels (hm_backend.hip: k_tensor_dot, k_tensor_square, k_lincomb,
-// k_tensor_muladd, k_reim_split, k_clincomb, k_plincomb) and the host emulator.
+// hm_clincomb, hm_plincomb, hm_tensor_dotadd.  Per-thread bodies (no cross-thread state) shared by the HIP kernels (hm_backend.hip: k_tensor_dot, k_tensor_square, k_lincomb,
+// k_tensor_muladd, k_reim_split, k_clincomb, k_plincomb, k_tensor_dotadd) and the host emulator.
 //
 // A record-table kernel: one record per limb-poly of the call in a device table cached by content, read through the scalar cache (the index is
 // wave-uniform); k_tensor's geometry — a workgroup owns 512 coefficients of one record, a thread an aligned pair (16-byte accesses) — and ONE
@@ -8,7 +8,7 @@
 // kernel's own *_fill_recs.
 #pragma once
 #include <cstddef>
-#include "../../include/homulator_hip.h"   // HM_TENSOR_DOT_MAX_TERMS, HM_LINCOMB_MAX_TERMS, HM_TENSOR_MULADD_MAX_ADDENDS, HM_CLINCOMB_MAX_TERMS, HM_PLINCOMB_MAX_TERMS
+#include "../../include/homulator_hip.h"   // HM_TENSOR_DOT_MAX_TERMS, HM_LINCOMB_MAX_TERMS, HM_TENSOR_MULADD_MAX_ADDENDS, HM_CLINCOMB_MAX_TERMS, HM_PLINCOMB_MAX_TERMS, HM_TENSOR_DOTADD_MAX_TERMS, HM_TENSOR_DOTADD_MAX_ADDENDS
 #include "hm_elem_core.h"                  // HM_CONST_PROB_T, HM_CONST_MODS
 #include "hm_modarith.h"
 #include "hm_ntt_core.h"
@@ -609,4 +609,135 @@ HM_HD void hm_plincomb_thread(const HmPlincombArgs &g, uint32_t entry, uint32_t 
   hm_term_rounds(1, T, true, term_at(T > 1 ? 1u : 0u), p0, term_at, ld, [&](const HmPlincombPair &v) { hm_plincomb_acc2(s, v); });
   hm_bst2(g.out + rec[1] * N, lane_bytes, hm_barrett_wide(s[0].c0, m), hm_barrett_wide(s[1].c0, m));
   hm_bst2(g.out + rec[2] * N, lane_bytes, hm_barrett_wide(s[0].c1, m), hm_barrett_wide(s[1].c1, m));
+}
+
+// ---- Scaled sum of T tensor products plus a linear combination of A further ciphertexts plus a constant, in one pass over the 4T + 2A inputs
+// (hm_tensor_dotadd; HDOTADD):
+//   d0 = sum_t s_t a_t b_t + sum_r u_r x_r + k,  d1 = sum_t s_t (a_t d_t + c_t b_t) + sum_r u_r y_r,  d2 = sum_t s_t c_t d_t
+// with hm_tensor_dot's roles per pair (a_t = c00, b_t = c10, c_t = c01, d_t = c11), x_r / y_r = c0 / c1 of addend r, s_t in [1, q), u_r and k in
+// [0, q) per record and every input canonical.  One form on both arithmetic back-ends: a pair with s_t != 1 first brings a_t and c_t to
+// s_t a_t mod q and s_t c_t mod q, canonical, by the exact Shoup product (hm_shoup: any 64-bit operand, w < q) behind a wave-uniform branch that
+// s_t = 1 skips; then the raw 64 x 64 products of every pair and every addend are summed in three 128-bit accumulators per coefficient
+// (HmDotAcc), k is added to d0's, and each accumulator is reduced ONCE by hm_barrett_wide, which takes any 128-bit value.  Every factor is below
+// q < 2^60, so a product is below 2^120: d1's accumulator holds 2T + A <= 40 of them, below 40 * 2^120 < 2^126; d0's T + A <= 24 and k < 2^60;
+// d2's T <= 16.  The result is the canonical residue of the exact integer sum, and s a b = (s a mod q) b mod q, hence bit-identical to hm_tensor
+// per pair followed by MUL_CONST, ADD, MUL_CONST + ADD per addend and ADD_CONST.
+#define HM_DOTADD_MAX_TERMS HM_TENSOR_DOTADD_MAX_TERMS
+#define HM_DOTADD_MAX_ADDENDS HM_TENSOR_DOTADD_MAX_ADDENDS
+static_assert(HM_DOTADD_MAX_TERMS == 16 && HM_DOTADD_MAX_ADDENDS == 8,
+              "d1's accumulator: 2T + A <= 40 products below 2^120 stay below 2^126; d0's: T + A <= 24 products plus k < 2^60 as well");
+// a record = HM_DOTADD_REC_WORDS(T, A) 32-bit words (32 + 32 T + 16 A bytes):
+//   0: modulus id   1..3: the limbs of d0, d1, d2   4: T   5: A   6, 7: k
+// then per pair (limbs of a, b, c, d; s_t: 2 words; its Shoup companion floor(s_t 2^64 / q): 2 words)
+// then per addend (limb of x_r, limb of y_r, u_r: 2 words) — hm_tensor_muladd's addend words
+#define HM_DOTADD_REC_HEAD 8u
+#define HM_DOTADD_REC_ADDENDS(T) (HM_DOTADD_REC_HEAD + 8u * (T))
+#define HM_DOTADD_REC_WORDS(T, A) (HM_DOTADD_REC_ADDENDS(T) + 4u * (A))
+struct HmTensorDotAddArgs {
+  const uint64_t *a, *b, *c, *d, *x;
+  uint64_t *o0, *o1, *o2;
+  const HmMod *mods;
+  const uint32_t *rec;   // device, [n_limbs][HM_DOTADD_REC_WORDS(n_terms, n_addends)]
+  uint32_t logN, n_limbs, n_terms, n_addends;
+};
+// The records of n entries from the entry point's limb lists (a .. d: [n][T], o0 .. o2: [n], a null list is the identity; lx0, lx1: [n][A], never
+// null at A > 0) and constants (scale: [n][T] or null = 1; add_scale: [n][A]; addend: [n] or null = 0; all already checked: reduced, scale != 0);
+// q[i] = the modulus of entry i.  Host side.
+inline void hm_tensor_dotadd_fill_recs(uint32_t *rec, const uint32_t *la, const uint32_t *lb, const uint32_t *lc, const uint32_t *ld, const uint32_t *lx0,
+                                       const uint32_t *lx1, const uint32_t *l0, const uint32_t *l1, const uint32_t *l2, const uint32_t *mod_ids,
+                                       const uint64_t *q, uint32_t n, uint32_t T, uint32_t A, const uint64_t *scale, const uint64_t *add_scale,
+                                       const uint64_t *addend) {
+  for (uint32_t i = 0; i < n; ++i) {
+    uint32_t *r = rec + (size_t)i * HM_DOTADD_REC_WORDS(T, A);
+    r[0] = mod_ids[i]; r[1] = hm_rec_limb(l0, i); r[2] = hm_rec_limb(l1, i); r[3] = hm_rec_limb(l2, i); r[4] = T; r[5] = A;
+    hm_rec_put64(r + 6, addend ? addend[i] : 0);
+    for (uint32_t t = 0; t < T; ++t) {
+      const uint32_t e = i * T + t;
+      const uint64_t s = scale ? scale[e] : 1;
+      uint32_t *w = r + HM_DOTADD_REC_HEAD + 8 * t;
+      w[0] = hm_rec_limb(la, e); w[1] = hm_rec_limb(lb, e); w[2] = hm_rec_limb(lc, e); w[3] = hm_rec_limb(ld, e);
+      hm_rec_put64(w + 4, s); hm_rec_put64(w + 6, hm_shoup_companion(s, q[i]));
+    }
+    for (uint32_t t = 0; t < A; ++t) {
+      const uint32_t e = i * A + t;
+      uint32_t *w = r + HM_DOTADD_REC_ADDENDS(T) + 4 * t;
+      w[0] = lx0[e]; w[1] = lx1[e]; hm_rec_put64(w + 2, add_scale[e]);
+    }
+  }
+}
+struct HmDotAddTerm {   // the limbs of one pair with its scalar and the scalar's Shoup companion: eight words of the record
+  HmDotLimbs l;
+  uint64_t s, ss;
+};
+template <class REC>
+HM_HD HmDotAddTerm hm_dotadd_term(REC rec, uint32_t t) {
+  const uint32_t w = HM_DOTADD_REC_HEAD + 8 * t;
+  return HmDotAddTerm{HmDotLimbs{rec[w], rec[w + 1], rec[w + 2], rec[w + 3]}, hm_rec64(rec, w + 4), hm_rec64(rec, w + 6)};
+}
+// the words of addend r; the caller clamps r to the last addend, and a record without addends hands out words of its header instead (never used):
+// always inside the record
+template <class REC>
+HM_HD HmMulAddTerm hm_dotadd_addend(REC rec, uint32_t T, uint32_t A, uint32_t r) {
+  const uint32_t w = A ? HM_DOTADD_REC_ADDENDS(T) + 4 * r : HM_DOTADD_REC_HEAD - 4;
+  return HmMulAddTerm{rec[w], rec[w + 1], hm_rec64(rec, w + 2)};
+}
+struct HmDotAddPair {   // the aligned pair of coefficients a thread owns of the four operands of one pair, with the pair's scalar
+  HmDotPair v;
+  uint64_t s, ss;
+};
+// one coefficient of one pair into the sums: s = 1 leaves a and c as they are
+HM_HD void hm_tensor_dotadd_acc(HmDotAcc &acc, uint64_t a, uint64_t b, uint64_t c, uint64_t d, uint64_t s, uint64_t ss, uint64_t q) {
+  uint64_t as = a, cs = c;
+  if (s != 1) {   // (wave-uniform)
+    as = hm_shoup(a, s, ss, q);
+    cs = hm_shoup(c, s, ss, q);
+  }
+  hm_tensor_dot_acc(acc, as, b, cs, d);
+}
+HM_HD void hm_tensor_dotadd_acc2(HmDotAcc (&acc)[2], const HmDotAddPair &p, uint64_t q) {
+  hm_tensor_dotadd_acc(acc[0], p.v.a[0], p.v.b[0], p.v.c[0], p.v.d[0], p.s, p.ss, q);
+  hm_tensor_dotadd_acc(acc[1], p.v.a[1], p.v.b[1], p.v.c[1], p.v.d[1], p.s, p.ss, q);
+}
+// thread tid of the workgroup that owns chunk `chunk` of record `entry`: four 16-byte loads per pair, two per addend, three 16-byte stores.
+// hm_term_rounds twice: over the pairs behind the loads of pair 0, as hm_tensor_dot_thread, then over the addends, as hm_tensor_muladd_thread.  The
+// loads of addend 0 are issued together with pair 0's and held through the pair loop (8 VGPRs and the scalar), so the addend loop starts with its
+// first term in flight.  chunk < N / 512 (the launch has n N / 512 workgroups), so the last byte touched is N * 8 - 1 of each limb-poly.
+HM_HD void hm_tensor_dotadd_thread(const HmTensorDotAddArgs &g, uint32_t entry, uint32_t chunk, uint32_t tid) {
+  const size_t N = (size_t)1 << g.logN;
+  const uint32_t T = g.n_terms, A = g.n_addends, lane_bytes = hm_rec_lane_bytes(chunk, tid);
+  const auto rec = HM_CONST_PROB_T(uint32_t, g.rec) + (size_t)entry * HM_DOTADD_REC_WORDS(T, A);
+  const HmMod m = HM_CONST_MODS(g.mods)[rec[0]];
+  const uint64_t k = hm_rec64(rec, 6);
+  const auto term_at = [&](uint32_t t) { return hm_dotadd_term(rec, t); };
+  const auto ld = [&](const HmDotAddTerm &l) {
+    HmDotAddPair p;
+    hm_bld2(g.a + l.l.a * N, lane_bytes, p.v.a[0], p.v.a[1]);
+    hm_bld2(g.b + l.l.b * N, lane_bytes, p.v.b[0], p.v.b[1]);
+    hm_bld2(g.c + l.l.c * N, lane_bytes, p.v.c[0], p.v.c[1]);
+    hm_bld2(g.d + l.l.d * N, lane_bytes, p.v.d[0], p.v.d[1]);
+    p.s = l.s; p.ss = l.ss;
+    return p;
+  };
+  const auto addend_at = [&](uint32_t r) { return hm_dotadd_addend(rec, T, A, r); };
+  const auto ld_addend = [&](const HmMulAddTerm &l) {
+    HmMulAddPair p;
+    hm_bld2(g.x + l.x * N, lane_bytes, p.x[0], p.x[1]);
+    hm_bld2(g.x + l.y * N, lane_bytes, p.y[0], p.y[1]);
+    p.u = l.u;
+    return p;
+  };
+  const HmDotAddPair p0 = ld(term_at(0));
+  HmMulAddTerm la = addend_at(0);
+  HmMulAddPair x0;   // (A = 0 leaves it unwritten: hm_term_rounds, handed it by value, then reads none of it)
+  if (A > 0) {   // (wave-uniform) addend 0 under the pairs
+    x0 = ld_addend(la);
+    la = addend_at(A > 1 ? 1u : 0u);
+  }
+  HM_DOT_ISSUED();
+  HmDotAcc s[2] = {{k, 0, 0}, {k, 0, 0}};
+  hm_term_rounds(1, T, true, term_at(T > 1 ? 1u : 0u), p0, term_at, ld, [&](const HmDotAddPair &p) { hm_tensor_dotadd_acc2(s, p, m.q); });
+  hm_term_rounds(A ? 1u : 0u, A, A > 0, la, x0, addend_at, ld_addend, [&](const HmMulAddPair &p) { hm_muladd_acc2(s, p); });
+  hm_bst2(g.o0 + rec[1] * N, lane_bytes, hm_barrett_wide(s[0].d0, m), hm_barrett_wide(s[1].d0, m));
+  hm_bst2(g.o1 + rec[2] * N, lane_bytes, hm_barrett_wide(s[0].d1, m), hm_barrett_wide(s[1].d1, m));
+  hm_bst2(g.o2 + rec[3] * N, lane_bytes, hm_barrett_wide(s[0].d2, m), hm_barrett_wide(s[1].d2, m));
 }

@@ -26,6 +26,7 @@ SYMBOLS = [
     "hm_inner_product_hoisted", "hm_inner_product_lintrans", "hm_inner_product_rotsum", "hm_inner_product_lintrans_multi",
     "hm_tensor_dot", "hm_inner_product_lintrans_id", "hm_inner_product_rotsum_init", "hm_ntt_mix_sub_scale_mul", "hm_ntt_mul",
     "hm_ntt_lift", "hm_tensor_square", "hm_lincomb", "hm_tensor_muladd", "hm_reim_split", "hm_clincomb", "hm_plincomb",
+    "hm_tensor_dotadd",
 ]
 
 
@@ -165,6 +166,7 @@ def load():
     L.hm_reim_split.argtypes = [vp] + [vp] * 9 + [u32]
     L.hm_clincomb.argtypes = [vp] + [vp] * 5 + [u32, u32, vp, vp, vp, vp]
     L.hm_plincomb.argtypes = [vp] + [vp] * 11 + [u32, u32]
+    L.hm_tensor_dotadd.argtypes = [vp] + [vp] * 18 + [u32, u32, u32, vp, vp, vp]
     L.hm_inner_product.argtypes = [vp] + [vp] * 7 + [u32, u32, u32]
     L.hm_automorph.argtypes = [vp, vp, vp, vp, vp, u32, u32]
     L.hm_ewe.argtypes = [vp, i32] + [vp] * 11 + [u32, vp]
@@ -454,6 +456,20 @@ class Context:
         keep = [_u32(v) for v in (p_limbs, x0_limbs, x1_limbs, addend_limbs, o0_limbs, o1_limbs, mod_ids)]
         self._ck(self.L.hm_plincomb(self.h, p.ptr, keep[0][1], x.ptr, keep[1][1], keep[2][1], None if addend is None else addend.ptr, keep[3][1],
                                     out.ptr, keep[4][1], keep[5][1], keep[6][1], len(mod_ids), int(n_terms)))
+
+    def tensor_dotadd(self, a, b, c, d, x, o0, o1, o2, mod_ids, n_terms, n_addends=0, x0_limbs=None, x1_limbs=None, scale=None, add_scale=None,
+                      addend=None, limbs=None):
+        """o0 = sum_t s_t * a_t * b_t + sum_r u_r * x_r + k, o1 = sum_t s_t * (a_t * d_t + c_t * b_t) + sum_r u_r * y_r, o2 = sum_t s_t * c_t *
+        d_t per entry (hm_tensor_dotadd): s_t = scale[i][t] (None: 1), u_r = add_scale[i][r], k = addend[i] (None: 0), residues of the entry's
+        modulus; x_r / y_r = the limb-polys x0_limbs[i][r] / x1_limbs[i][r] of the buffer x (row-major [n][n_addends], flat; x and the three
+        lists may be None at n_addends = 0).  limbs: the seven limb lists of a, b, c, d ([n][n_terms], flat) and o0, o1, o2 ([n]) (None: the
+        identity); buffers: anything with a device address `.ptr`"""
+        ls = limbs or [None] * 7
+        keep = [_u32(v) for v in ls] + [_u32(x0_limbs), _u32(x1_limbs), _u32(mod_ids)]
+        ks, ku, ka = _u64(scale), _u64(add_scale), _u64(addend)
+        self._ck(self.L.hm_tensor_dotadd(self.h, a.ptr, keep[0][1], b.ptr, keep[1][1], c.ptr, keep[2][1], d.ptr, keep[3][1],
+                                         x.ptr if x is not None else None, keep[7][1], keep[8][1], o0.ptr, keep[4][1], o1.ptr, keep[5][1],
+                                         o2.ptr, keep[6][1], keep[9][1], len(mod_ids), int(n_terms), int(n_addends), ks[1], ku[1], ka[1]))
 
     def inner_product(self, x, x_limbs, y, y_limbs, out, out_limbs, mod_ids, n_terms, n_out, x_galois=0):
         keep = [_u32(v) for v in (x_limbs, y_limbs, out_limbs, mod_ids)]

@@ -39,6 +39,8 @@ public:
   bool clincombHead = false; // the MUL_CONST a_1 x_1 of term 1 of a complex-weighted sum of ciphertexts (HCLINCOMB): pass (5c) starts its record here
   bool plincombHead = false; // the MUL p_1 x_1 of term 1 of one component of a plaintext-weighted sum of ciphertexts (HPLINCOMB): pass (5p) starts its record here;
                              // also the ADD of that sum's plaintext addend, which the pass takes behind the last term only if it is marked
+  bool dotaddHead = false;   // a tensor product's MAC2 (d1) that is pair 1 of a scaled SUM of tensor products plus scaled addends plus a constant (HDOTADD):
+                             // pass (5a) starts its record here
   std::vector<uint32_t> inMods;  // BCONV: modulus ids of the inputs
   unsigned long long refInstructions = 0;  // upstream instructions this record stands for
   unsigned long long refExtra = 0;         // ... of records folded into a BCONV record (not scaled by its MAC-port count)
@@ -115,6 +117,15 @@ public:
   std::vector<AddrType> plOperands;
   bool plHasAddend = false;
   AddrType plAddend = 0;
+  // (5a) scaled sum of tensor products plus scaled addends plus constant (hm_tensor_dotadd): a fusedTensor record that absorbed the tensor records
+  // of the further pairs and the chains behind the outputs.  daOperands = (c00, c10, c01, c11) of every pair, pair 1 first, then (x_r, y_r) of
+  // every addend; daScales = the scalar s_t of every pair (1: the pair had no MUL_CONST records), daAddScales = the scalars u_r; OutputOperand =
+  // the final d1, extraOutputs = the final d0, d2.  daHasScale: the MUL_CONST records of at least one pair went in; daHasConst: the ADD_CONST
+  // record behind d0 went in, with the constant daConst.  daOperands empty: not such a record
+  std::vector<AddrType> daOperands;
+  std::vector<uint64_t> daScales, daAddScales;
+  bool daHasScale = false, daHasConst = false;
+  uint64_t daConst = 0;
   // fused inner product (ops == IP): out_k = sum_j ipX[j] * ipY[k][j]; out_0 = OutputOperand, out_1 = extraOutputs[0]
   std::vector<AddrType> ipX;
   std::vector<std::vector<AddrType>> ipY;

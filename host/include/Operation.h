@@ -148,10 +148,10 @@ protected:
   bool rescaleKey(const std::string &op) const;
   // <out>.c<k> = Rescale(ct[k]), builder labels <label>_<k>, as HMULT's tail: the tail of the ops with rescale = 1, and all of HRESCALE
   void setRescaledOutput(const std::string &out, const std::array<std::vector<AddrType>, 2> &ct, bool inputMayBeOpInput = false);
-  // HMULT's tail on the three polynomials d of a tensor product (shared by HMULT, HDOT, HSQUARE, HMULADD): KS(d[2]); HMULT_Hadd_Key(k): d[k] + ks_k into
+  // HMULT's tail on the three polynomials d of a tensor product (shared by HMULT, HDOT, HSQUARE, HMULADD, HDOTADD): KS(d[2]); HMULT_Hadd_Key(k): d[k] + ks_k into
   // HMULTHaddOutput(k); Rescale of both, out = the result at level - 1
   void relinearizeAndRescale(const std::array<std::vector<AddrType>, 3> &d);
-  // Per-limb constants an op carries in its records (HSQUARE: "scale", "const"; HLINCOMB: "scale<t>", "const"; HCLINCOMB: "scale<t>", "scale_im<t>", "const"; HMULADD: "scale", "addscale<t>", "const"), by name: the records of limb j that hold value j, so that
+  // Per-limb constants an op carries in its records (HSQUARE: "scale", "const"; HLINCOMB: "scale<t>", "const"; HCLINCOMB: "scale<t>", "scale_im<t>", "const"; HMULADD: "scale", "addscale<t>", "const"; HDOTADD: "scale<t>", "addscale<r>", "const"), by name: the records of limb j that hold value j, so that
   // setConstants can patch Instruction::constant before the plan is built.  enabled = false: the op knows the name but its config key is 0
   // negated: the records carry q_j - value (HCLINCOMB's "scale_im<t>": the stage multiplies by the stored -X^(N/2))
   struct ConstantStage { bool enabled = false; std::string key; std::vector<std::vector<Instruction *>> records; bool nonZero = false; bool negated = false; };
@@ -196,7 +196,7 @@ public:
   bool readBuffer(const std::string &name, uint64_t *host, uint32_t copy = 0);  // copy: op of the batch (config key `batch`)
   bool writeBuffer(const std::string &name, const uint64_t *host, uint32_t copy = 0);  // real data for an input / key buffer ([limbs][N], fully reduced)
   unsigned long long totalInstructions();
-  // replaces the per-limb constants `name` of the op (HSQUARE: "scale", "const"; HLINCOMB: "scale1" .. "scale<T>", "const"; HMULADD: "scale", "addscale1" .. "addscale<A>", "const") by n = level residues, values[j] reduced mod q_j; before prepare() only.
+  // replaces the per-limb constants `name` of the op (HSQUARE: "scale", "const"; HLINCOMB: "scale1" .. "scale<T>", "const"; HMULADD: "scale", "addscale1" .. "addscale<A>", "const"; HDOTADD: "scale1" .. "scale<T>", "addscale1" .. "addscale<A>", "const") by n = level residues, values[j] reduced mod q_j; before prepare() only.
   // Refused, by op and name: after prepare(), n != level, an unreduced value (or a zero where the constant multiplies), a name whose config key is 0
   void setConstants(const std::string &name, const uint64_t *values, uint32_t n);
   Arch *getArch() { return arch; }
@@ -299,6 +299,18 @@ class HPLINCOMB : public OperationBase {
 public:
   HPLINCOMB(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
 };
+// hdotadd (build extension): out = Rescale(Relin(sum_t s_t * ct<2t-1> * ct<2t> + sum_r u_r * ct<2T+r>) + k), one node of a polynomial evaluation with
+// several products (the Paterson-Stockmeyer recombination p = sum_i q_i G_i + r, one component of a complex product).  2T + A input ciphertexts at
+// one level >= 2 (config keys terms = T, default 4, 1..16, and addends = A, default 1, 0..8); with da_scale = 1 the per-pair per-limb scalars s_{t,j}
+// in [1, q_j) on the three polynomials of pair t (synthetic: word 0 of limb j of stream seed + 6050 + 50 t, a 0 replaced by 1); the addend scalars
+// u_{r,j} in [0, q_j) (stream seed + 7050 + 50 r; zero = the addend contributes nothing); with da_const = 1 the per-limb constants k_j on every
+// evaluation-form entry of d0 only (stream seed + 7900).  All of it acts in front of the key switch, at scale Delta^2 on the level of the inputs;
+// then HMULT's tail with hmult's key IP_Key<k>_<j>.  setConstants("scale<t>" | "addscale<r>" | "const") replaces the synthetic values.  One output
+// ciphertext out at level - 1.  A = 0 with both keys 0 is bit-identical to hdot, T = 1 to hmuladd with the same constants.
+class HDOTADD : public OperationBase {
+public:
+  HDOTADD(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
+};
 class HROTSUM : public OperationBase {
 public:
   HROTSUM(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
@@ -346,7 +358,7 @@ class OpChain {
   std::vector<Arch *> archs;
   std::vector<OperationBase *> ops;
 public:
-  // ops: comma-separated list of hmult | hrotate | hadd | pmult | padd | hlintrans | hdot | hrotsum | hbsgs | hrescale | hmodraise | hsquare | hlincomb | hmuladd | hreim | hclincomb | hplincomb, e.g. "hmult,hrotate,hadd,hmult"; hrotate_hoisted (R output
+  // ops: comma-separated list of hmult | hrotate | hadd | pmult | padd | hlintrans | hdot | hrotsum | hbsgs | hrescale | hmodraise | hsquare | hlincomb | hmuladd | hreim | hclincomb | hplincomb | hdotadd, e.g. "hmult,hrotate,hadd,hmult"; hrotate_hoisted (R output
   // ciphertexts) only as the last op
   OpChain(const std::string &cfgPath, const std::string &opList, uint32_t maxLevel, uint32_t curLevel, uint32_t alpha,
           const std::map<std::string, uint32_t> &overrides = {});

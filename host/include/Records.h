@@ -97,6 +97,8 @@ inline std::vector<Read> recordReads(const Instruction &i) {
   } else if (!i.plOperands.empty()) {    // (5p): plaintext and both components of every term, then the addend
     for (AddrType a : i.plOperands) v.push_back({a, Role::Operand, kNoDigit});
     if (i.plHasAddend) v.push_back({i.plAddend, Role::Operand, kNoDigit});
+  } else if (!i.daOperands.empty()) {    // (5a): the four operands of every pair, then both components of every addend
+    for (AddrType a : i.daOperands) v.push_back({a, Role::Operand, kNoDigit});
   } else if (i.ops == MULT) {
     for (int b = 0; b < 4; ++b)
       if (eweOperandMask(i.opcode) & (1 << b)) v.push_back({i.operandList[b], Role::Operand, kNoDigit});

@@ -34,7 +34,8 @@ struct Arch::Launch {
               L_TENSOR_MULADD,                               // (5m) the scaled tensor product plus scaled addends plus a constant
               L_REIM,                                        // (5r) the sum and the rotated difference of a polynomial and its conjugate
               L_CLINCOMB,                                    // (5c) the sum of polynomials times a + b X^(N/2) plus a constant
-              L_PLINCOMB } kind;                             // (5p) the sum of ciphertexts times plaintexts plus a plaintext on c0, both components
+              L_PLINCOMB,                                    // (5p) the sum of ciphertexts times plaintexts plus a plaintext on c0, both components
+              L_TENSOR_DOTADD } kind;                        // (5a) the scaled sum of tensor products plus scaled addends plus a constant
   std::vector<uint32_t> hoistG;   // L_IP_HOISTED: the Galois element of every rotation (a: digits [n][T], b: keys [r][n][2][T], out: [r][n][2])
                                   // L_IP_LINTRANS: the same, with c: plaintexts [r][n], d: addend source [n] / out1: addend output [n] (HM_NO_LIMB: none; both
                                   // empty: no entry has one), out: [n][2]
@@ -65,6 +66,8 @@ struct Arch::Launch {
                                   // L_CLINCOMB: as L_LINCOMB with k: the real parts a_t, maK: the monomial parts b_t [n][dotTerms]
                                   // L_PLINCOMB: terms per record (b: the plaintexts, x0, x1: c0, c1 of the ciphertexts [n][dotTerms]; d: the addend [n], empty:
                                   // none; out, out1: the sums of c0, c1 [n])
+                                  // L_TENSOR_DOTADD: pairs per record (a, b, c, d: [n][dotTerms]) and maAddends addends (x0, x1: [n][maAddends]); out, out1, out2 [n];
+                                  // k: the pair scalars [n][dotTerms] (empty: none), maK: the addend scalars [n][maAddends], addK: the constants [n] (empty: none)
   uint32_t maAddends = 0;         // L_TENSOR_MULADD: addends per record (a, b, c, d, out, out1, out2 as L_TENSOR; x0, x1: c0, c1 of the addends [n][maAddends];
   std::vector<uint32_t> x0, x1;   // k: the scalars [n], maK: the addend scalars [n][maAddends], addK: the constants [n]; k / addK empty: none)
   std::vector<uint64_t> maK;
@@ -180,6 +183,9 @@ Arch::Arch(Config *cfg) : config(cfg) {
   // (5p) hplincomb: the MUL and the MAC_ADDs of both components and the ADD of the plaintext addend become one hm_plincomb launch.  Config key
   // fuse_plincomb (default 1).
   fusePlincomb = cfg->getValueOr("fuse_plincomb", 1) != 0;
+  // (5a) hdotadd: the tensor products of all pairs, the scalars on their outputs, the ADDs between the pairs, the MUL_CONST + ADD pairs of the
+  // addends on d0 and d1 and the constant on d0 become one hm_tensor_dotadd launch.  Config key fuse_dotadd (default 1).
+  fuseDotadd = cfg->getValueOr("fuse_dotadd", 1) != 0;
   // (4p) pmult with rescale = 1: the products are formed by the rescale's transforms while they load.  Config key fuse_pmul_rescale: 1 / 0 = always /
   // never; not given = where it was measured faster than the three-launch plan: everywhere but the generic back-end's launches
   // inside the one-launch form's limit, which has no product form there (Planner::productOperands)
@@ -345,6 +351,7 @@ int partKey(const Instruction &i) {
   if (!i.sqOperands.empty()) return 8500 + (i.sqHasScale ? 1 : 0) + (i.sqHasConst ? 2 : 0);                // 8500+: scaled square plus constant, by what it absorbed
   if (!i.lcOperands.empty()) return 8600 + (int)i.lcOperands.size();                                   // 8600+: sum of scaled polynomials, by terms
   if (!i.maOperands.empty()) return 8700 + 4 * (int)i.maAddScales.size() + (i.maHasScale ? 1 : 0) + (i.maHasConst ? 2 : 0);   // 8700+: scaled product plus addends, by addends and what it absorbed
+  if (!i.daOperands.empty()) return 8100 + 9 * ((int)i.daScales.size() - 1) + (int)i.daAddScales.size();                          // 8100+: scaled sum of products plus addends, by pairs and addends (8100 .. 8243)
   if (!i.reimOperands.empty()) return 8400;                                                                // 8400: sum and rotated difference of a polynomial and its conjugate
   if (!i.clOperands.empty()) return 8800 + (int)i.clOperands.size();                                       // 8800+: sum of polynomials times a + b X^(N/2), by terms
   if (!i.plOperands.empty()) return 8900 + 2 * ((int)i.plOperands.size() / 3) + (i.plHasAddend ? 1 : 0);   // 8900+: sum of ciphertexts times plaintexts, by terms and addend
@@ -522,6 +529,7 @@ struct Arch::LaunchBuilder {
   void reim(Launch &L, Recs recs);
   void clincomb(Launch &L, Recs recs);
   void plincomb(Launch &L, Recs recs);
+  void tensorDotAdd(Launch &L, Recs recs);
   void nttSubScale(Launch &L, Recs recs);
   void copy(Launch &L, Recs recs);
   void transform(Launch &L, Recs recs);
@@ -767,6 +775,33 @@ void Arch::LaunchBuilder::plincomb(Launch &L, Recs recs) {
   L.bytes = (3ull * L.dotTerms + 2 + (addend ? 1 : 0)) * LP * recs.size();   // plaintext and both components of every term read once, two sums written
 }
 
+// (5a) a, b, c, d = c00, c10, c01, c11 of every pair [n][T]; x0, x1 = c0, c1 of every addend [n][A]; out, out1, out2 = d0, d1, d2 [n]; k = the pair
+// scalars [n][T], maK = the addend scalars [n][A], addK = the constants [n] (hm_tensor_dotadd).  The part key keeps records of different pair
+// and addend counts apart; a record without scalars beside one that has them multiplies by 1, one without a constant adds 0: neither changes a
+// residue
+void Arch::LaunchBuilder::tensorDotAdd(Launch &L, Recs recs) {
+  L.kind = Launch::L_TENSOR_DOTADD; L.statKey = "EWE";
+  L.dotTerms = (uint32_t)recs[0]->daScales.size();
+  L.maAddends = (uint32_t)recs[0]->daAddScales.size();
+  const bool scaled = std::any_of(recs.begin(), recs.end(), [](const Instruction *i) { return i->daHasScale; });
+  const bool shifted = std::any_of(recs.begin(), recs.end(), [](const Instruction *i) { return i->daHasConst; });
+  for (Instruction *i : recs) {
+    for (size_t t = 0; t < L.dotTerms; ++t) {
+      L.a.push_back(limb(i->daOperands[4 * t])); L.b.push_back(limb(i->daOperands[4 * t + 1]));
+      L.c.push_back(limb(i->daOperands[4 * t + 2])); L.d.push_back(limb(i->daOperands[4 * t + 3]));
+    }
+    for (size_t r = 0; r < L.maAddends; ++r) {
+      L.x0.push_back(limb(i->daOperands[4 * L.dotTerms + 2 * r])); L.x1.push_back(limb(i->daOperands[4 * L.dotTerms + 2 * r + 1]));
+    }
+    if (scaled) L.k.insert(L.k.end(), i->daScales.begin(), i->daScales.end());
+    L.maK.insert(L.maK.end(), i->daAddScales.begin(), i->daAddScales.end());
+    if (shifted) L.addK.push_back(i->daHasConst ? i->daConst : 0);
+    L.out.push_back(limb(i->extraOutputs[0])); L.out1.push_back(limb(i->OutputOperand)); L.out2.push_back(limb(i->extraOutputs[1]));
+    L.mods.push_back(i->mod_id);
+  }
+  L.bytes = (4ull * L.dotTerms + 2 * L.maAddends + 3) * LP * recs.size();   // every operand and both components of every addend read once, three sums written
+}
+
 // fused forward transform (4, 4b, 9, 12)
 void Arch::LaunchBuilder::nttSubScale(Launch &L, Recs recs) {
   L.kind = Launch::L_NTT_SUBSCALE; L.statKey = "NTT";
@@ -940,6 +975,7 @@ void Arch::LaunchBuilder::emitCompute(const Group &group, Launches &front, Launc
   else if (!f->reimOperands.empty()) reim(*L, recs);
   else if (!f->clOperands.empty()) clincomb(*L, recs);
   else if (!f->plOperands.empty()) plincomb(*L, recs);
+  else if (!f->daOperands.empty()) tensorDotAdd(*L, recs);
   else if (f->fusedTensor) tensor(*L, recs);
   else if (f->fusedSubScale) nttSubScale(*L, recs);
   else if (f->ops == NTT && f->passthrough) copy(*L, recs);
@@ -1365,7 +1401,7 @@ void Arch::prepare() {
 
 static const char *const kLaunchKindNames[] = {"NTT", "INTT", "EWE", "BCONV", "AUTO", "NTT_SUBSCALE", "TENSOR", "EXCH_IN", "EXCH_OUT", "REPLICATE", "IP", "NTT_IP",
                                                "BCONV_COL", "EXCH_IN_COL", "EXCH_OUT_COL", "IP_HOISTED", "IP_LINTRANS", "TENSOR_DOT", "IP_ROTSUM",
-                                               "IP_LINTRANS_MULTI", "TENSOR_SQUARE", "LINCOMB", "TENSOR_MULADD", "REIM", "CLINCOMB", "PLINCOMB"};
+                                               "IP_LINTRANS_MULTI", "TENSOR_SQUARE", "LINCOMB", "TENSOR_MULADD", "REIM", "CLINCOMB", "PLINCOMB", "TENSOR_DOTADD"};
 
 // Per-launch device time (SURVEY.md §8d "per-stage hipEvent times", exchange time at N > 1): every launch of the plan
 // bracketed by its own event pair, in plan order so that the data dependencies (and, sharded, the collectives) line up.
@@ -1427,6 +1463,8 @@ std::string Arch::planText() const {
       out += " terms=" + std::to_string(l->dotTerms) + " addend=" + (l->d.empty() ? "0" : "1");
     if (l->kind == Launch::L_TENSOR_MULADD)   // (5m): addends per record, and what the records absorbed
       out += " addends=" + std::to_string(l->maAddends) + " scale=" + (l->k.empty() ? "0" : "1") + " const=" + (l->addK.empty() ? "0" : "1");
+    if (l->kind == Launch::L_TENSOR_DOTADD)   // (5a): pairs and addends per record, and what the records absorbed
+      out += " terms=" + std::to_string(l->dotTerms) + " addends=" + std::to_string(l->maAddends) + " scale=" + (l->k.empty() ? "0" : "1") + " const=" + (l->addK.empty() ? "0" : "1");
     if (l->kind == Launch::L_IP_LINTRANS)   // (6l): entries that also form the addend output
       out += " addend=" + std::to_string(l->d.size() - (size_t)std::count(l->d.begin(), l->d.end(), HM_NO_LIMB));
     if (l->kind == Launch::L_IP_LINTRANS_MULTI)   // (6m): groups, entries that also form the groups' addend outputs
@@ -1465,7 +1503,7 @@ std::string Arch::planDump() const {
            " ipTerms=" + std::to_string(l->ipTerms) + " ipOuts=" + std::to_string(l->ipOuts) + " ref=" + std::to_string(l->refInstructions) + " bytes=" + std::to_string(l->bytes) +
            " mark=" + std::to_string(l->recordSlot) + " xin=" + indexOf(l->xin) + " xout=" + indexOf(l->xout);
     if (l->dotTerms) out += " terms=" + std::to_string(l->dotTerms);
-    if (l->kind == Launch::L_TENSOR_MULADD) out += " addends=" + std::to_string(l->maAddends);
+    if (l->kind == Launch::L_TENSOR_MULADD || l->kind == Launch::L_TENSOR_DOTADD) out += " addends=" + std::to_string(l->maAddends);
     if (l->kind == Launch::L_IP_LINTRANS_MULTI) out += " multiOuts=" + std::to_string(l->multiOuts);   // (one sum: the line of L_IP_LINTRANS has no such field)
     vec("wait", l->waitSlots); vec("hoistG", l->hoistG); vec("ipCoeff", l->ipCoeff); vec("ipInv", l->ipInv); vec("outPacked", l->outPacked);
     vec("inGalois", l->inGalois); vec("addGalois", l->addGalois); vec("mulB", l->mulB); vec("liftMods", l->liftMods);
@@ -1628,6 +1666,12 @@ void Arch::enqueue(Launch &l) {
   case Launch::L_PLINCOMB:
     st = hm_plincomb(ctx, pool, l.b.data(), pool, l.x0.data(), l.x1.data(), l.d.empty() ? nullptr : pool, l.d.empty() ? nullptr : l.d.data(), pool,
                      l.out.data(), l.out1.data(), l.mods.data(), cnt, l.dotTerms);
+    break;
+  case Launch::L_TENSOR_DOTADD:
+    st = hm_tensor_dotadd(ctx, pool, l.a.data(), pool, l.b.data(), pool, l.c.data(), pool, l.d.data(), l.maAddends ? pool : nullptr,
+                          l.maAddends ? l.x0.data() : nullptr, l.maAddends ? l.x1.data() : nullptr, pool, l.out.data(), pool, l.out1.data(), pool,
+                          l.out2.data(), l.mods.data(), cnt, l.dotTerms, l.maAddends, l.k.empty() ? nullptr : l.k.data(),
+                          l.maAddends ? l.maK.data() : nullptr, l.addK.empty() ? nullptr : l.addK.data());
     break;
   case Launch::L_EXCH_IN:
     st = hm_limbs_to_slices(ctx, pool, l.exLimbs.data(), l.exOwners.data(), (uint32_t)l.exLimbs.size(), l.slicesIn);

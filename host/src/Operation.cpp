@@ -1251,6 +1251,99 @@ HMULADD::HMULADD(std::string labelName, uint32_t maxLevel, uint32_t currentLevel
   finishConstruction();
 }
 
+// hdotadd (build extension).  out = Rescale(d0 + ks0(d2)), Rescale(d1 + ks1(d2)) with
+//   d0 = sum_t s_t a_t b_t + sum_r u_r x_r + k,  d1 = sum_t s_t (a_t d_t + c_t b_t) + sum_r u_r y_r,  d2 = sum_t s_t c_t d_t
+// (a_t, c_t = ct<2t-1>.c0, .c1; b_t, d_t = ct<2t>.c0, .c1; x_r, y_r = ct<2T+r>.c0, .c1): one node of a polynomial evaluation with several products,
+// p = sum_i q_i G_i + r, or one component of a complex product behind hreim.  Existing opcodes only, in one uniform form: per pair t TensorCompute
+// into buffers of its own (DaD<i>Out_(t)); da_scale = 1 adds three MUL_CONST stages DotAdd_Scale_(t)_D<i> (s_t on the pair's d0, d1, d2); for
+// t >= 2 three ADD stages DotAdd_Sum_(t)_D<i> onto the running sums; then the addends exactly as HMULADD emits them, DotAdd_AddScale_(r)_C<k> =
+// u_r ct<2T+r>.c<k> (MUL_CONST) and DotAdd_Add_(r)_D<k> (ADD); da_const = 1 one ADD_CONST stage DotAdd_Const_D0.  Everything is linear and acts
+// in front of the key switch, at scale Delta^2 on the level of the inputs.  Then HMULT's tail, stage for stage.  Unfused, the stages run one
+// launch each; fused, pass (5a) of Arch::fusePasses (Planner.cpp) turns everything in front of the key switch into one launch.
+HDOTADD::HDOTADD(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch)
+    : OperationBase("HDOTADD", labelName, cfg, _arch, maxLevel, currentLevel, alpha) {
+  if (arch->backend() == Arch::BACKEND_SIM) throw std::runtime_error("hdotadd: backend = sim has no such op (the reference has no sum of scaled products)");
+  if (arch->world() > 1) throw std::runtime_error("hdotadd: world > 1 is not supported (the sharded plan is not built)");
+  if (currentLevel < 2) throw std::runtime_error("hdotadd: Rescale needs at least two limbs");
+  const uint32_t T = cfg->getValueOr("terms", 4), A = cfg->getValueOr("addends", 1);
+  if (T < 1 || T > HM_TENSOR_DOTADD_MAX_TERMS) throw std::runtime_error("hdotadd: terms = " + S(T) + ", must be in [1, " + S(HM_TENSOR_DOTADD_MAX_TERMS) + "]");
+  if (A > HM_TENSOR_DOTADD_MAX_ADDENDS) throw std::runtime_error("hdotadd: addends = " + S(A) + ", must be in [0, " + S(HM_TENSOR_DOTADD_MAX_ADDENDS) + "]");
+  auto flag = [&](const char *key, uint32_t dflt) {
+    const uint32_t v = cfg->getValueOr(key, dflt);
+    if (v > 1) throw std::runtime_error(std::string("hdotadd: ") + key + " = " + S(v) + ", must be 0 or 1");
+    return v == 1;
+  };
+  const bool scaled = flag("da_scale", 0), shifted = flag("da_const", 0);
+  flag("fuse_dotadd", 1);
+  makeInputs(2 * T + A);
+
+  // the records of limb j of a constant stage, kept by name for setConstants
+  auto keep = [&](const std::string &name, const std::vector<INSGROUP> &recs, bool nonZero) {
+    ConstantStage &cs = constantStages[name];
+    cs.enabled = true;
+    cs.nonZero = nonZero;
+    cs.records.resize(currentLevel);
+    for (uint32_t j = 0; j < currentLevel; ++j) cs.records[j].push_back(recs[j][0]);
+  };
+  auto synth = [&](uint64_t stream, bool nonZero) {
+    std::vector<uint64_t> v;
+    for (uint32_t j = 0; j < currentLevel; ++j) {
+      const uint64_t w = synthWord0(stream + j, arch->modulus(j));
+      v.push_back(nonZero && w == 0 ? 1 : w);
+    }
+    return v;
+  };
+  // one stage on polynomial i of `d`: out = op(d[i], other) with the constants, if any
+  auto stage = [&](std::array<Limbs, 3> &d, uint32_t i, ewe_opcode op, const std::string &key, const std::string &buffer, const Limbs *other,
+                   const std::vector<uint64_t> &constants) {
+    PerLimb s{labelName + "_" + key + "_Level(", ")", range(0, currentLevel), alloc(buffer, currentLevel)};
+    const Limbs before = d[i];
+    s.a = before.addr;
+    s.after = {&before.from};
+    if (other) { s.c = other->addr; s.after.push_back(&other->from); }
+    s.constants = constants;
+    d[i] = {s.out, eweLimbs(&insgener, op, s)};
+    driver.dispatchInstructions(key, d[i].from);
+  };
+  for (uint32_t t = 1; t <= T; ++t) constantStages["scale" + S(t)].key = "da_scale";
+  constantStages["const"].key = "da_const";
+  std::array<Limbs, 3> d;   // the running sums
+  for (uint32_t t = 1; t <= T; ++t) {
+    const std::string P = "(" + S(t) + ")";
+    TensorCompute tcm(t == 1 ? labelName : labelName + "_Pair" + P, currentLevel, &cts[2 * t - 2], &cts[2 * t - 1], &Datapool, &DataInsMap, &insgener,
+                      addrManager.get(), "Da", "_" + P);
+    if (t == 1)
+      for (const INSGROUP &g : tcm.getInsMap().at("TensorCompute_INS_D1")) g[0]->dotaddHead = true;
+    for (const auto &st : tcm.getInsMap()) driver.dispatchInstructions(t == 1 ? st.first : st.first + "_" + P, st.second);
+    std::array<Limbs, 3> p;
+    for (uint32_t i = 0; i < 3; ++i) p[i] = {tcm.d(i), tcm.getInsMap().at("TensorCompute_INS_D" + S(i))};
+    if (scaled)
+      for (uint32_t i = 0; i < 3; ++i) {
+        stage(p, i, EWE_MUL_CONST, "DotAdd_Scale_" + P + "_D" + S(i), "DaD" + S(i) + "Scale" + P, nullptr, synth(seed + 6050 + 50ull * t, /*nonZero=*/true));
+        keep("scale" + S(t), p[i].from, /*nonZero=*/true);
+      }
+    if (t == 1) { d = p; continue; }
+    for (uint32_t i = 0; i < 3; ++i) stage(d, i, EWE_ADD, "DotAdd_Sum_" + P + "_D" + S(i), "DaD" + S(i) + "Sum" + P, &p[i], {});
+  }
+  for (uint32_t r = 1; r <= A; ++r)
+    for (uint32_t k = 0; k < 2; k++) {
+      const std::string C = "_C" + S(k);
+      PerLimb m{labelName + "_DotAdd_AddScale_(" + S(r) + ")" + C + "_Level(", ")", range(0, currentLevel), alloc("DaAddScaled(" + S(r) + ")" + C, currentLevel)};
+      m.a = component(2 * T + r - 1, k);
+      m.constants = synth(seed + 7050 + 50ull * r, /*nonZero=*/false);
+      const Limbs term{m.out, eweLimbs(&insgener, EWE_MUL_CONST, m)};
+      driver.dispatchInstructions("DotAdd_AddScale_(" + S(r) + ")" + C, term.from);
+      keep("addscale" + S(r), term.from, /*nonZero=*/false);
+      stage(d, k, EWE_ADD, "DotAdd_Add_(" + S(r) + ")_D" + S(k), "DaD" + S(k) + "Add(" + S(r) + ")", &term, {});
+    }
+  if (shifted) {
+    stage(d, 0, EWE_ADD_CONST, "DotAdd_Const_D0", "DaD0Const", nullptr, synth(seed + 7900, /*nonZero=*/false));
+    keep("const", d[0].from, /*nonZero=*/false);
+  }
+  relinearizeAndRescale({d[0].addr, d[1].addr, d[2].addr});
+  finishConstruction();
+}
+
 // hrotsum (build extension).  out = sum_i rot_{g_i}(ct<i>), g_i = g^i mod 2N, over G DIFFERENT ciphertexts with ONE ModDown: the ModDown is linear,
 // so the G key products are summed on the E = l + alpha limbs and brought down once (the ModUps cannot be shared: the ciphertexts differ).
 //   D_{i,j} = ModUp(ct<i>.c1)                          per ciphertext, on the unrotated c1 (buffers and stages of ciphertext i >= 2 suffixed _Ct<i>)
@@ -1487,6 +1580,7 @@ static OperationBase *makeOp(const std::string &o, uint32_t maxLevel, uint32_t l
   if (o == "hreim") return new HREIM("test_hreim", maxLevel, level, alpha, cfg, arch);
   if (o == "hclincomb") return new HCLINCOMB("test_hclincomb", maxLevel, level, alpha, cfg, arch);
   if (o == "hplincomb") return new HPLINCOMB("test_hplincomb", maxLevel, level, alpha, cfg, arch);
+  if (o == "hdotadd") return new HDOTADD("test_hdotadd", maxLevel, level, alpha, cfg, arch);
   throw std::runtime_error("Error operation requirement, please double confirm!");
 }
 

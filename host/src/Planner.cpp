@@ -111,6 +111,7 @@ struct Arch::Planner {
   void realImaginary();    // 5r
   void complexCombination();   // 5c
   void plaintextCombination(); // 5p
+  void tensorDotAdd();     // 5a
   void keyProduct();       // 6
   // what (6m/6l), (6s) and (6h) all recognise: the live two-key key-product records whose digits are all automorphisms, by one element per record, of
   // the same materialised digits and are read by nothing else; per (modulus, unrotated digits) the records and their automorphisms, in stage order
@@ -157,6 +158,7 @@ void Arch::fusePasses(std::vector<Stage> &st) {
   if (fuseReim) p.realImaginary();
   if (fuseClincomb) p.complexCombination();
   if (fusePlincomb) p.plaintextCombination();
+  if (fuseDotadd) p.tensorDotAdd();
   p.keyProduct();
   // (6m, 6l) before (6s) and (6h): the records it merges are the ones (6h) would claim, and none of them is (6s)'s (their outputs go into products,
   // not into sums).  fuse_bsgs: the groups with several sums, fuse_lintrans: the ones with one
@@ -399,21 +401,29 @@ void Arch::Planner::residue() {
 // (5) tensor product: d1 = p*s + r*t (MAC2) with d0 = p*t and d2 = r*s (MUL) of the same limb -> one pass.
 //     Sets on the MAC2 record: fusedTensor, extraOutputs.
 void Arch::Planner::tensor() {
-  std::map<std::pair<AddrType, AddrType>, Instruction *> muls;
+  // (several MULs of the same two operands: the pairs of an hdotadd whose inputs are bound to the same ciphertexts; each MAC2 takes one of its own)
+  std::map<std::pair<AddrType, AddrType>, std::vector<Instruction *>> muls;
   for (auto &s : st)
     for (Instruction *i : s.ins)
-      if (i->ops == MULT && i->opcode == EWE_MUL && !dead.count(i)) muls[{i->operandList[0], i->operandList[1]}] = i;
+      if (i->ops == MULT && i->opcode == EWE_MUL && !dead.count(i)) muls[{i->operandList[0], i->operandList[1]}].push_back(i);
+  auto mulOf = [&](AddrType x, AddrType y, uint32_t mod, Instruction *besides) -> Instruction * {
+    auto m = muls.find({x, y});
+    if (m == muls.end()) return nullptr;
+    for (Instruction *i : m->second)
+      if (i != besides && !dead.count(i) && i->mod_id == mod) return i;
+    return nullptr;
+  };
   for (auto &s : st)
     for (Instruction *i : s.ins) {
       if (i->ops != MULT || i->opcode != EWE_MAC2 || dead.count(i)) continue;
       const AddrType P = i->operandList[0], S = i->operandList[1], R = i->operandList[2], T = i->operandList[3];
-      auto u = muls.find({P, T}), v = muls.find({R, S});
-      if (u == muls.end() || v == muls.end() || u->second->mod_id != i->mod_id || v->second->mod_id != i->mod_id) continue;
+      Instruction *u = mulOf(P, T, i->mod_id, nullptr), *v = mulOf(R, S, i->mod_id, u);
+      if (!u || !v) continue;
       i->fusedTensor = true;
-      i->extraOutputs = {u->second->OutputOperand, v->second->OutputOperand};
-      i->refInstructions += u->second->refInstructions + v->second->refInstructions;
-      dead.insert(u->second);
-      dead.insert(v->second);
+      i->extraOutputs = {u->OutputOperand, v->OutputOperand};
+      i->refInstructions += u->refInstructions + v->refInstructions;
+      dead.insert(u);
+      dead.insert(v);
     }
 }
 
@@ -618,6 +628,134 @@ void Arch::Planner::tensorMulAdd() {
     }
     c->OutputOperand = d1;
     c->extraOutputs = {d0, d2};
+    for (const Write &w : recordWrites(*c)) producer[w.addr] = c;
+    place.moveTo(c, last);
+  }
+}
+
+// (5a) scaled sum of tensor products plus scaled addends plus constant (hdotadd): a tensor record of (5) that the builder marked (dotaddHead) becomes
+//      a record of hm_tensor_dotadd.  It absorbs, in this order:
+//        its three sole-reader MUL_CONST records when all three carry the same constant (s_1 d0, s_1 d1, s_1 d2);
+//        pair after pair, the three ADD records that are the only readers of the running d0, d1, d2 and whose other operands are the three
+//        outputs of ONE unmarked tensor record of (5) of the same modulus, read by nothing else, either directly or, all three, through a
+//        MUL_CONST record of one constant s_t read by nothing else: the tensor record, its MUL_CONSTs and the ADDs go in, all three or none;
+//        the addends and the constant, as pass (5m) takes them: per addend ONE ADD on d0 and ONE on d1 whose other operands are MUL_CONST records
+//        of the same constant u_r read by nothing else, then the ADD_CONST record that is the only reader of d0.
+//      The record's reads become the 4T operands plus the 2A addend operands (recordReads), its outputs the final buffers, so every later pass
+//      sees what it sees in hmult; it takes the place of the last record it absorbs and keeps fusedTensor, so pass (6) stays off it.  Never
+//      written: the 3T products, their scaled copies, the 2A scaled addends and the partial sums.  Only the builder of HDOTADD sets the mark: the
+//      pass matches nothing in any other op.
+//      Reads: fusedTensor / extraOutputs (5).  Sets on the marked record: daOperands, daScales, daAddScales, daHasScale, daHasConst, daConst,
+//      OutputOperand, extraOutputs.
+void Arch::Planner::tensorDotAdd() {
+  Readers rd = readers();
+  Placement place(st);
+  std::vector<Instruction *> heads;
+  for (auto &s : st)
+    for (Instruction *i : s.ins)
+      if (live(i) && i->fusedTensor && i->dotaddHead && i->dotOperands.empty() && i->sqOperands.empty() && i->maOperands.empty() && i->daOperands.empty())
+        heads.push_back(i);
+  for (Instruction *c : heads) {
+    // MAC2 operands (P, S, R, T) = (c00, c11, c01, c10); daOperands = (a, b, c, d) = (c00, c10, c01, c11) per pair
+    c->daOperands = {c->operandList[0], c->operandList[3], c->operandList[2], c->operandList[1]};
+    std::array<AddrType, 3> d = {c->extraOutputs[0], c->OutputOperand, c->extraOutputs[1]};
+    Instruction *last = c;
+    auto take = [&](Instruction *i) {
+      absorb(c, i);
+      if (place.after(i, last)) last = i;
+    };
+    // the MUL_CONST records that are the only readers of the three polynomials `of`, if all three carry one constant
+    typedef std::array<Instruction *, 3> Three;
+    auto scalars = [&](const std::array<AddrType, 3> &of, Three &m) {
+      for (int i = 0; i < 3; ++i) m[i] = soleReader(rd, of[i], EWE_MUL_CONST, c->mod_id);
+      return m[0] && m[1] && m[2] && m[0]->hasConstant && m[1]->hasConstant && m[2]->hasConstant && m[0]->constant == m[1]->constant &&
+             m[0]->constant == m[2]->constant;
+    };
+    Three m;
+    uint64_t s1 = 1;
+    if (scalars(d, m)) {
+      c->daHasScale = true;
+      s1 = m[0]->constant;
+      for (int i = 0; i < 3; ++i) { take(m[i]); d[i] = m[i]->OutputOperand; }
+    }
+    c->daScales.push_back(s1);
+    // the ADD behind `sum` if that is all that reads it, and its other operand
+    auto sumLink = [&](AddrType sum, AddrType &other) -> Instruction * {
+      Instruction *add = soleReader(rd, sum, EWE_ADD, c->mod_id);
+      if (!add) return nullptr;
+      other = add->operandList[0] == sum ? add->operandList[2] : add->operandList[0];
+      if ((add->operandList[0] != sum && add->operandList[2] != sum) || other == sum) return nullptr;
+      return add;
+    };
+    while (c->daScales.size() < HM_TENSOR_DOTADD_MAX_TERMS) {
+      Three add, mul = {nullptr, nullptr, nullptr};
+      std::array<AddrType, 3> src;
+      bool ok = true;
+      for (int i = 0; i < 3 && ok; ++i) ok = (add[i] = sumLink(d[i], src[i])) != nullptr;
+      if (!ok) break;
+      // through the pair's MUL_CONST records, all three or none
+      int scaledOps = 0;
+      for (int i = 0; i < 3; ++i) {
+        Instruction *p = producerOf(src[i]);
+        if (p && live(p) && p->ops == MULT && p->opcode == EWE_MUL_CONST && !p->fusedTensor && p->hasConstant && p->mod_id == c->mod_id && onlyReader(rd, src[i], add[i])) {
+          mul[i] = p;
+          ++scaledOps;
+        }
+      }
+      if (scaledOps != 0 && scaledOps != 3) break;
+      std::array<AddrType, 3> prod = src;
+      if (scaledOps == 3) {
+        if (mul[0]->constant != mul[1]->constant || mul[0]->constant != mul[2]->constant) break;
+        for (int i = 0; i < 3; ++i) prod[i] = mul[i]->operandList[0];
+      }
+      // the three products are the outputs of one unmarked tensor record, each read by its link only
+      Instruction *x = producerOf(prod[1]);
+      if (!x || x == c || !live(x) || !x->fusedTensor || x->dotaddHead || x->mod_id != c->mod_id || !x->dotOperands.empty() || !x->sqOperands.empty() ||
+          !x->maOperands.empty() || !x->daOperands.empty() || x->OutputOperand != prod[1] || x->extraOutputs.size() != 2 ||
+          x->extraOutputs[0] != prod[0] || x->extraOutputs[1] != prod[2])
+        break;
+      for (int i = 0; i < 3 && ok; ++i) ok = onlyReader(rd, prod[i], scaledOps ? mul[i] : add[i]);
+      if (!ok) break;
+      c->daOperands.insert(c->daOperands.end(), {x->operandList[0], x->operandList[3], x->operandList[2], x->operandList[1]});
+      c->daScales.push_back(scaledOps ? mul[0]->constant : 1);
+      if (scaledOps) c->daHasScale = true;
+      take(x);
+      for (int i = 0; i < 3; ++i) {
+        if (mul[i]) take(mul[i]);
+        take(add[i]);
+        d[i] = add[i]->OutputOperand;
+      }
+    }
+    // the addends: (5m)'s links
+    auto link = [&](AddrType sum, Instruction *&add, Instruction *&mul) {
+      AddrType other = 0;
+      add = sumLink(sum, other);
+      if (!add) return false;
+      mul = producerOf(other);
+      return mul && live(mul) && mul->ops == MULT && mul->opcode == EWE_MUL_CONST && !mul->fusedTensor && mul->hasConstant && mul->mod_id == c->mod_id &&
+             onlyReader(rd, other, add);
+    };
+    std::vector<AddrType> addends;
+    while (c->daAddScales.size() < HM_TENSOR_DOTADD_MAX_ADDENDS) {
+      Instruction *a0 = nullptr, *u0 = nullptr, *a1 = nullptr, *u1 = nullptr;
+      if (!link(d[0], a0, u0) || !link(d[1], a1, u1) || u0->constant != u1->constant) break;
+      addends.push_back(u0->operandList[0]);
+      addends.push_back(u1->operandList[0]);
+      c->daAddScales.push_back(u0->constant);
+      for (Instruction *i : {u0, a0, u1, a1}) take(i);
+      d[0] = a0->OutputOperand; d[1] = a1->OutputOperand;
+    }
+    c->daOperands.insert(c->daOperands.end(), addends.begin(), addends.end());
+    if (Instruction *add = soleReader(rd, d[0], EWE_ADD_CONST, c->mod_id)) {
+      if (add->hasConstant) {
+        c->daHasConst = true;
+        c->daConst = add->constant;
+        take(add);
+        d[0] = add->OutputOperand;
+      }
+    }
+    c->OutputOperand = d[1];
+    c->extraOutputs = {d[0], d[2]};
     for (const Write &w : recordWrites(*c)) producer[w.addr] = c;
     place.moveTo(c, last);
   }

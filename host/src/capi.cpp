@@ -64,6 +64,7 @@ int hh_op_create(hh_op **out, const char *cfg_path, const char *op_name, uint32_
     else if (o == "hreim") h->op = new HREIM("test_hreim", maxLevel, curLevel, alpha, h->cfg, h->arch);
     else if (o == "hclincomb") h->op = new HCLINCOMB("test_hclincomb", maxLevel, curLevel, alpha, h->cfg, h->arch);
     else if (o == "hplincomb") h->op = new HPLINCOMB("test_hplincomb", maxLevel, curLevel, alpha, h->cfg, h->arch);
+    else if (o == "hdotadd") h->op = new HDOTADD("test_hdotadd", maxLevel, curLevel, alpha, h->cfg, h->arch);
     else if (o == "hadd") h->op = new HADD("test_hadd", maxLevel, curLevel, alpha, h->cfg, h->arch);
     else if (o == "pmult") h->op = new PMULT("test_pmult", maxLevel, curLevel, alpha, h->cfg, h->arch);
     else if (o == "padd") h->op = new PADD("test_ADD", maxLevel, curLevel, alpha, h->cfg, h->arch);

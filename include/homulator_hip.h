@@ -277,6 +277,33 @@ hm_status hm_plincomb(hm_ctx *ctx, const uint64_t *p, const uint32_t *p_limbs, c
                       const uint32_t *x1_limbs, const uint64_t *addend, const uint32_t *addend_limbs, uint64_t *out,
                       const uint32_t *o0_limbs, const uint32_t *o1_limbs, const uint32_t *mod_ids, uint32_t n, uint32_t n_terms);
 
+/* K3, scaled sum of n_terms tensor products plus a linear combination of n_addends further ciphertexts plus a constant, in one pass over the
+ * 4 n_terms + 2 n_addends input polynomials (HDOTADD): for entry i, with the roles of hm_tensor_dot per pair (a_t = c00,
+ * b_t = c10, c_t = c01, d_t = c11 of pair t), x_r / y_r = c0 / c1 of addend r, s_t = scale[i * n_terms + t] in [1, q),
+ * u_r = add_scale[i * n_addends + r] in [0, q) and k = addend[i] in [0, q), per coefficient
+ *   o0[i] = sum_t s_t * a_t * b_t + sum_r u_r * x_r + k,   o1[i] = sum_t s_t * (a_t * d_t + c_t * b_t) + sum_r u_r * y_r,
+ *   o2[i] = sum_t s_t * c_t * d_t,   t < n_terms <= 16,   r < n_addends <= 8,
+ * the canonical residue of the exact sum: bit-identical to hm_tensor per pair followed by hm_ewe with HM_OP_MUL_CONST on the three outputs of
+ * every pair, HM_OP_ADD of the pairs onto running sums, HM_OP_MUL_CONST + HM_OP_ADD per addend and component, and HM_OP_ADD_CONST on o0, none
+ * of whose intermediates is written (4 n_terms + 2 n_addends + 3 limb-polys per entry where that chain moves 22 n_terms + 12 n_addends - 6
+ * with the constant).  The operand lists are row-major, a_limbs[i * n_terms + t] (the same limb-poly may appear in several entries and pairs);
+ * both components of the addends live in ONE buffer x: x0_limbs[i * n_addends + r] is the limb-poly of x_r, x1_limbs[i * n_addends + r] that
+ * of y_r; the output lists and mod_ids have n entries; a null limb list is the identity.  A zero u_r is a term that contributes nothing;
+ * n_addends = 0 with scale == NULL and addend == NULL is hm_tensor_dot, n_terms = 1 is hm_tensor_muladd, both bit for bit.  scale == NULL:
+ * every s is 1; addend == NULL: every k is 0; scale, add_scale and addend are host arrays.  The records live in a device table: one launch
+ * serves any n, and the call is safe under graph capture once it has run with the same lists and constants.  HM_ERR_ARG: a null buffer, a
+ * null mod_ids, a null x, x0_limbs, x1_limbs or add_scale with n_addends > 0 (all four may be null at 0), n_terms outside 1..16, n_addends
+ * above 8, a limb or modulus id out of range, an unreduced scale, add_scale or addend, a zero scale, an output limb-poly that overlaps (by
+ * address range, not by base pointer) an input limb-poly, an addend or another output limb-poly.  n = 0 is HM_OK. */
+#define HM_TENSOR_DOTADD_MAX_TERMS 16
+#define HM_TENSOR_DOTADD_MAX_ADDENDS 8
+hm_status hm_tensor_dotadd(hm_ctx *ctx, const uint64_t *a, const uint32_t *a_limbs, const uint64_t *b, const uint32_t *b_limbs,
+                           const uint64_t *c, const uint32_t *c_limbs, const uint64_t *d, const uint32_t *d_limbs,
+                           const uint64_t *x, const uint32_t *x0_limbs, const uint32_t *x1_limbs,
+                           uint64_t *o0, const uint32_t *o0_limbs, uint64_t *o1, const uint32_t *o1_limbs, uint64_t *o2,
+                           const uint32_t *o2_limbs, const uint32_t *mod_ids, uint32_t n, uint32_t n_terms, uint32_t n_addends,
+                           const uint64_t *scale, const uint64_t *add_scale, const uint64_t *addend);
+
 /* K5 — inner product with the evaluation key in one pass: for limb i, out[i][k] = sum_{j < n_terms}
  * x[i][j] * y[i][k][j], k < n_out (n_terms <= 4 digits, n_out <= 2 keys).  Limb lists are row-major:
  * x_limbs[i * n_terms + j], y_limbs[(i * n_out + k) * n_terms + j], out_limbs[i * n_out + k].  Replaces
