@@ -514,6 +514,9 @@ __global__ void __launch_bounds__(256) k_clincomb(HmClincombArgs a) { hm_rec_blo
 __global__ void __launch_bounds__(256) k_plincomb(HmPlincombArgs a) { hm_rec_block<hm_plincomb_thread>(a); }
 // scaled sum of T tensor products plus a linear combination of further ciphertexts plus a constant, T and A run-time loops
 __global__ void __launch_bounds__(256) k_tensor_dotadd(HmTensorDotAddArgs a) { hm_rec_block<hm_tensor_dotadd_thread>(a); }
+// several scaled sums of the same T limb-polys, the inputs read once per tile of TILE outputs; both tiles are built (hm_set_option "lincomb_multi_tile")
+template <uint32_t TILE>
+__global__ void __launch_bounds__(256) k_lincomb_multi(HmLincombMultiArgs a) { hm_rec_block<hm_lincomb_multi_thread<TILE>>(a); }
 
 // 16-byte units per thread of the element-wise kernel, 512 coefficients apart, all loads in flight before the first use.  1: 89 600 workgroups for a batch of
 // ten hadd; 2 / 4 measured padd +3 / +5 %, pmult +1 %, hadd within the noise (tools/r06_ewe_ab.sh): not worth a second shape of the kernel's launch
@@ -753,6 +756,7 @@ struct hm_ctx {
   // ntt_launch_entries x N x 8 bytes; what is written and read between a hand-off line's store and its load decides whether the load is
   // served by the Infinity Cache (256 MiB) or by HBM
   uint32_t ntt_launch_entries = HM_NTT_MAX_ENTRIES;
+  uint32_t lincomb_multi_tile = 0;   // hm_set_option "lincomb_multi_tile": outputs per record of hm_lincomb_multi (0 = HM_LINCOMB_MULTI_TILE)
   uint32_t ip_multi_tile = 0;   // hm_set_option "ip_multi_tile": outputs per workgroup of hm_inner_product_lintrans_multi (0 = HM_IP_LINTRANS_MULTI_TILE)
   uint32_t nip_small = 64;  // transform x key launches of at most this many limb records (N = 2^16) run in the small-launch geometry (k_ntt_row_ip8); 0 = off
   int n_cu = 256;
@@ -1104,6 +1108,11 @@ extern "C" hm_status hm_set_option(hm_ctx *c, const char *name, uint64_t value) 
     return HM_OK;
   }
   if (!strcmp(name, "ntt_launch_entries")) { c->ntt_launch_entries = (uint32_t)std::max<uint64_t>(8, value); return HM_OK; }
+  if (!strcmp(name, "lincomb_multi_tile")) {   // outputs per record of hm_lincomb_multi: 0 = HM_LINCOMB_MULTI_TILE, or one of the two built sizes
+    if (value != 0 && value != 4 && value != 8) return fail(c, HM_ERR_ARG, "hm_set_option: lincomb_multi_tile is 0 (the default tile), 4 or 8");
+    c->lincomb_multi_tile = (uint32_t)value;
+    return HM_OK;
+  }
   if (!strcmp(name, "ip_multi_tile")) {   // outputs per workgroup of hm_inner_product_lintrans_multi: 0 = HM_IP_LINTRANS_MULTI_TILE, or one of the two built sizes
     if (value != 0 && value != 2 && value != 4) return fail(c, HM_ERR_ARG, "hm_set_option: ip_multi_tile is 0 (the default tile), 2 or 4");
     c->ip_multi_tile = (uint32_t)value;
@@ -1860,6 +1869,34 @@ extern "C" hm_status hm_lincomb(hm_ctx *c, const uint64_t *in, const uint32_t *l
   HmLincombArgs a;
   a.in = in; a.out = out; a.n_terms = T;
   return rec_launch(c, k_lincomb, a, recs, n);
+}
+
+// n_out scaled sums of the same n_terms limb-polys, each plus a constant: input list [n][n_terms], output list and constants [n][n_out], scalars
+// [n][n_out][n_terms]; ceil(n_out / tile) records per entry
+extern "C" hm_status hm_lincomb_multi(hm_ctx *c, const uint64_t *in, const uint32_t *li, uint64_t *out, const uint32_t *lo, const uint32_t *mod_ids,
+                                      uint32_t n, uint32_t n_terms, uint32_t n_out, const uint64_t *scale, const uint64_t *addend) {
+  static const char *const what = "hm_lincomb_multi";
+  if (!c) return HM_ERR_ARG;
+  HM_TABLE_CALL(c);
+  if (!in || !out) return fail(c, HM_ERR_ARG, "%s: null buffer", what);
+  if (!scale) return fail(c, HM_ERR_ARG, "%s: scale is null", what);
+  const uint32_t T = n_terms, M = n_out;
+  if (T == 0 || T > HM_LINCOMB_MAX_TERMS) return fail(c, HM_ERR_ARG, "%s: n_terms = %u, must be in [1, %d]", what, T, HM_LINCOMB_MAX_TERMS);
+  if (M == 0 || M > HM_LINCOMB_MULTI_MAX_OUT) return fail(c, HM_ERR_ARG, "%s: n_out = %u, must be in [1, %d]", what, M, HM_LINCOMB_MULTI_MAX_OUT);
+  const bool alt = c->lincomb_multi_tile && c->lincomb_multi_tile != HM_LINCOMB_MULTI_TILE;
+  const uint32_t tile = alt ? HM_LINCOMB_MULTI_TILE_ALT : HM_LINCOMB_MULTI_TILE, tiles = hm_lincomb_multi_tiles(M, tile);
+  // the table's words, and with them the records and (N / 512 <= 2^8 workgroups per record) the grid, fit 32 bits
+  if ((uint64_t)n * tiles > 0xFFFFFFFFull / HM_MLINCOMB_REC_WORDS(T, tile) || (uint64_t)n * tiles * (c->P.N / 512) > 0x7FFFFFFFull)
+    return fail(c, HM_ERR_ARG, "%s: n = %u entries of %u terms and %u outputs are too many for one call", what, n, T, M);
+  if (hm_status st = rec_check(c, what, {{"in", in, li, n * T}}, {{"out", out, lo, n * M}}, mod_ids, n,
+                               {{"scale", scale, false, true, M * T}, {"addend", addend, false, true, M}}))
+    return st;
+  if (n == 0) return HM_OK;
+  std::vector<uint32_t> recs((size_t)n * tiles * HM_MLINCOMB_REC_WORDS(T, tile));
+  hm_lincomb_multi_fill_recs(recs.data(), li, lo, mod_ids, n, T, M, tile, scale, addend);
+  HmLincombMultiArgs a;
+  a.in = in; a.out = out; a.n_terms = T;
+  return rec_launch(c, tile == 8 ? k_lincomb_multi<8> : k_lincomb_multi<4>, a, recs, n * tiles);
 }
 
 // scaled tensor product plus n_addends scaled ciphertexts plus a constant: operand and output lists [n], addend lists and scalars [n][n_addends]

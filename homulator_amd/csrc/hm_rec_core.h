@@ -1,6 +1,6 @@
 // hm_rec_core.h — the record-table element-wise kernels: hm_tensor_dot, hm_tensor_square, hm_lincomb, hm_tensor_muladd, hm_reim_split,
-// hm_clincomb, hm_plincomb, hm_tensor_dotadd.  Per-thread bodies (no cross-thread state) shared by the HIP kernels (hm_backend.hip: k_tensor_dot, k_tensor_square, k_lincomb,
-// k_tensor_muladd, k_reim_split, k_clincomb, k_plincomb, k_tensor_dotadd) and the host emulator.
+// hm_clincomb, hm_plincomb, hm_tensor_dotadd, hm_lincomb_multi.  Per-thread bodies (no cross-thread state) shared by the HIP kernels (hm_backend.hip: k_tensor_dot, k_tensor_square, k_lincomb,
+// k_tensor_muladd, k_reim_split, k_clincomb, k_plincomb, k_tensor_dotadd, k_lincomb_multi) and the host emulator.
 //
 // A record-table kernel: one record per limb-poly of the call in a device table cached by content, read through the scalar cache (the index is
 // wave-uniform); k_tensor's geometry — a workgroup owns 512 coefficients of one record, a thread an aligned pair (16-byte accesses) — and ONE
@@ -8,7 +8,7 @@
 // kernel's own *_fill_recs.
 #pragma once
 #include <cstddef>
-#include "../../include/homulator_hip.h"   // HM_TENSOR_DOT_MAX_TERMS, HM_LINCOMB_MAX_TERMS, HM_TENSOR_MULADD_MAX_ADDENDS, HM_CLINCOMB_MAX_TERMS, HM_PLINCOMB_MAX_TERMS, HM_TENSOR_DOTADD_MAX_TERMS, HM_TENSOR_DOTADD_MAX_ADDENDS
+#include "../../include/homulator_hip.h"   // HM_TENSOR_DOT_MAX_TERMS, HM_LINCOMB_MAX_TERMS, HM_TENSOR_MULADD_MAX_ADDENDS, HM_CLINCOMB_MAX_TERMS, HM_PLINCOMB_MAX_TERMS, HM_TENSOR_DOTADD_MAX_TERMS, HM_TENSOR_DOTADD_MAX_ADDENDS, HM_LINCOMB_MULTI_TILE
 #include "hm_elem_core.h"                  // HM_CONST_PROB_T, HM_CONST_MODS
 #include "hm_modarith.h"
 #include "hm_ntt_core.h"
@@ -287,6 +287,113 @@ HM_HD void hm_lincomb_thread(const HmLincombArgs &g, uint32_t entry, uint32_t ch
   const HmLincombPair p0 = ld(term_at(0));
   hm_term_rounds(1, T, true, term_at(T > 1 ? 1u : 0u), p0, term_at, ld, [&](const HmLincombPair &v) { hm_lincomb_acc2(s, v); });
   hm_bst2(g.out + rec[1] * N, lane_bytes, hm_barrett_wide(s[0] + k, m), hm_barrett_wide(s[1] + k, m));
+}
+
+// ---- M scaled sums of the SAME T polynomials, each plus a constant, the inputs read once per tile of outputs (hm_lincomb_multi; HMLINCOMB,
+// DESIGN.md section 26):
+//   out_m = sum_t s_{m,t} x_t + k_m      with s_{m,t}, k_m in [0, q) per record and every x_t canonical.
+// hm_lincomb's arithmetic per output: the raw 64 x 64 products in ONE 128-bit accumulator per coefficient and output, k_m added, one
+// hm_barrett_wide; the bound is hm_lincomb's.  Every output is the canonical residue of the exact integer sum, hence bit-identical to hm_lincomb
+// per output.  A record is one limb-poly position with a TILE of up to TILE outputs: the pair of x_t a thread loads goes into 2 TILE
+// accumulators, so an entry of M outputs moves ceil(M / TILE) T + M limb-polys where M hm_lincomb records move M (T + 1).  One form on both
+// arithmetic back-ends.
+static_assert(HM_LINCOMB_MAX_TERMS == 16, "every accumulator: 16 products below 2^120 plus k below 2^60 stay below 2^125");
+static_assert(HM_LINCOMB_MULTI_TILE == 4 || HM_LINCOMB_MULTI_TILE == 8, "the two built tiles");
+#define HM_LINCOMB_MULTI_TILE_ALT (HM_LINCOMB_MULTI_TILE == 8 ? 4u : 8u)   // the other built tile (hm_set_option "lincomb_multi_tile")
+// a record = HM_MLINCOMB_REC_WORDS(T, TILE) 32-bit words, a multiple of 16 bytes:
+//   (modulus id, T, outputs in this tile: 1..TILE, 0), the T input limbs (padded with 0 to a multiple of four words), then per output slot of the
+//   tile (output limb, 0, k: 2 words, s_{m,0} .. s_{m,T-1}: 2 words each).  The slots behind a short last tile hold zeros and are never used
+//   but for their scalars, which the term loop requests with the others (inside the record) and multiplies with nothing.
+#define HM_MLINCOMB_REC_HEAD 4u
+#define HM_MLINCOMB_SLOT_WORDS(T) (4u + 2u * (T))
+#define HM_MLINCOMB_SLOT0(T) (HM_MLINCOMB_REC_HEAD + (((T) + 3u) & ~3u))
+#define HM_MLINCOMB_REC_WORDS(T, TILE) (HM_MLINCOMB_SLOT0(T) + (TILE) * HM_MLINCOMB_SLOT_WORDS(T))
+// records per entry: the tiles of its M outputs
+inline uint32_t hm_lincomb_multi_tiles(uint32_t M, uint32_t tile) { return (M + tile - 1) / tile; }
+struct HmLincombMultiArgs {
+  const uint64_t *in;
+  uint64_t *out;
+  const HmMod *mods;
+  const uint32_t *rec;   // device, [n_limbs][HM_MLINCOMB_REC_WORDS(n_terms, TILE)]; n_limbs = records = entries x tiles per entry
+  uint32_t logN, n_limbs, n_terms;
+};
+// The records of n entries from the entry point's lists (in: [n][T], out: [n][M]) and constants (scale: [n][M][T]; addend: [n][M] or null = 0;
+// both already checked: reduced): hm_lincomb_multi_tiles(M, tile) records per entry, tile after tile.  Host side.
+inline void hm_lincomb_multi_fill_recs(uint32_t *rec, const uint32_t *li, const uint32_t *lo, const uint32_t *mod_ids, uint32_t n, uint32_t T, uint32_t M,
+                                       uint32_t tile, const uint64_t *scale, const uint64_t *addend) {
+  const uint32_t tiles = hm_lincomb_multi_tiles(M, tile), words = HM_MLINCOMB_REC_WORDS(T, tile);
+  for (uint32_t i = 0; i < n; ++i)
+    for (uint32_t r = 0; r < tiles; ++r) {
+      uint32_t *w = rec + ((size_t)i * tiles + r) * words;
+      const uint32_t cnt = M - r * tile < tile ? M - r * tile : tile;
+      for (uint32_t x = 0; x < words; ++x) w[x] = 0;
+      w[0] = mod_ids[i]; w[1] = T; w[2] = cnt;
+      for (uint32_t t = 0; t < T; ++t) w[HM_MLINCOMB_REC_HEAD + t] = hm_rec_limb(li, i * T + t);
+      for (uint32_t o = 0; o < cnt; ++o) {
+        const size_t e = (size_t)i * M + r * tile + o;
+        uint32_t *s = w + HM_MLINCOMB_SLOT0(T) + o * HM_MLINCOMB_SLOT_WORDS(T);
+        s[0] = hm_rec_limb(lo, (uint32_t)e);
+        hm_rec_put64(s + 2, addend ? addend[e] : 0);
+        for (uint32_t t = 0; t < T; ++t) hm_rec_put64(s + 4 + 2 * t, scale[e * T + t]);
+      }
+    }
+}
+struct HmLincombMultiTerm {   // the input limb of one term, with the term's index: its scalars are requested with its load
+  uint32_t limb, t;
+};
+template <class REC>
+HM_HD HmLincombMultiTerm hm_lincomb_multi_term(REC rec, uint32_t t) {
+  return HmLincombMultiTerm{rec[HM_MLINCOMB_REC_HEAD + t], t};
+}
+template <uint32_t TILE>
+struct HmLincombMultiPair {   // the aligned pair of coefficients a thread owns of one term, with the term's scalars
+  uint64_t x[2], s[TILE];
+};
+// the products of one term into the accumulators of the cnt outputs of the tile: the slot index is a compile-time index of an unrolled loop
+// (a run-time one would put the accumulators into scratch), a short tile leaves it behind a wave-uniform branch
+template <uint32_t TILE>
+HM_HD void hm_lincomb_multi_acc(hm_u128 (&s)[TILE][2], const HmLincombMultiPair<TILE> &v, uint32_t cnt) {
+#pragma unroll
+  for (uint32_t o = 0; o < TILE; ++o) {
+    if (o < cnt) {   // (wave-uniform; a branch of its own per slot: an early exit would hand every accumulator on through every exit)
+      s[o][0] += (hm_u128)v.x[0] * v.s[o];
+      s[o][1] += (hm_u128)v.x[1] * v.s[o];
+    }
+  }
+}
+// thread tid of the workgroup that owns chunk `chunk` of record `entry`: T 16-byte loads (hm_term_rounds behind the load of term 0), then one
+// 16-byte store per output of the tile, after all loads.  chunk < N / 512 (the launch has n_limbs N / 512 workgroups), so the last byte touched
+// is N * 8 - 1 of each limb-poly.
+template <uint32_t TILE>
+HM_HD void hm_lincomb_multi_thread(const HmLincombMultiArgs &g, uint32_t entry, uint32_t chunk, uint32_t tid) {
+  const size_t N = (size_t)1 << g.logN;
+  const uint32_t T = g.n_terms, lane_bytes = hm_rec_lane_bytes(chunk, tid);
+  const auto rec = HM_CONST_PROB_T(uint32_t, g.rec) + (size_t)entry * HM_MLINCOMB_REC_WORDS(T, TILE);
+  const HmMod m = HM_CONST_MODS(g.mods)[rec[0]];
+  const uint32_t cnt = rec[2];
+  hm_u128 s[TILE][2];
+#pragma unroll
+  for (uint32_t o = 0; o < TILE; ++o) s[o][0] = s[o][1] = 0;
+  const auto term_at = [&](uint32_t t) { return hm_lincomb_multi_term(rec, t); };
+  // one 16-byte load from a wave-uniform base at the lane's offset; the term's scalar of every slot of the tile is requested beside it (the limb
+  // a step ahead, as every term loop's words; the TILE scalars with the load, so that two sets of them are live, not three)
+  const auto ld = [&](const HmLincombMultiTerm &l) {
+    HmLincombMultiPair<TILE> v;
+    hm_bld2(g.in + l.limb * N, lane_bytes, v.x[0], v.x[1]);
+#pragma unroll
+    for (uint32_t o = 0; o < TILE; ++o) v.s[o] = hm_rec64(rec, HM_MLINCOMB_SLOT0(T) + o * HM_MLINCOMB_SLOT_WORDS(T) + 4 + 2 * l.t);
+    return v;
+  };
+  const HmLincombMultiPair<TILE> p0 = ld(term_at(0));
+  hm_term_rounds(1, T, true, term_at(T > 1 ? 1u : 0u), p0, term_at, ld, [&](const HmLincombMultiPair<TILE> &v) { hm_lincomb_multi_acc<TILE>(s, v, cnt); });
+#pragma unroll
+  for (uint32_t o = 0; o < TILE; ++o) {
+    if (o < cnt) {   // (wave-uniform)
+      const uint32_t w = HM_MLINCOMB_SLOT0(T) + o * HM_MLINCOMB_SLOT_WORDS(T);
+      const uint64_t k = hm_rec64(rec, w + 2);
+      hm_bst2(g.out + rec[w] * N, lane_bytes, hm_barrett_wide(s[o][0] + k, m), hm_barrett_wide(s[o][1] + k, m));
+    }
+  }
 }
 
 // ---- Scaled tensor product of TWO ciphertexts plus a linear combination of A further ciphertexts plus a constant, in one pass over the 4 + 2A

@@ -13,6 +13,8 @@ BACKEND_LIBS = ("libhm_m32.so", "libhm_gen.so")
 
 OP_MUL, OP_MAC2, OP_MAC_ADD, OP_ADD, OP_SUB, OP_MUL_CONST, OP_SUB_SCALE, OP_COPY, OP_SUB_SCALE_ADD, OP_ADD_CONST = range(10)
 NO_LIMB = 0xFFFFFFFF   # HM_NO_LIMB: "this entry has no such operand" in an optional limb list
+LINCOMB_MULTI_MAX_OUT = 16   # HM_LINCOMB_MULTI_MAX_OUT: outputs per entry of hm_lincomb_multi
+LINCOMB_MULTI_TILE = 4       # HM_LINCOMB_MULTI_TILE: outputs a record of hm_lincomb_multi serves (the inputs are read once per tile)
 LINTRANS_MULTI_TILE = 2   # HM_IP_LINTRANS_MULTI_TILE: outputs a workgroup of hm_inner_product_lintrans_multi serves
 
 # every symbol include/homulator_hip.h declares
@@ -26,7 +28,7 @@ SYMBOLS = [
     "hm_inner_product_hoisted", "hm_inner_product_lintrans", "hm_inner_product_rotsum", "hm_inner_product_lintrans_multi",
     "hm_tensor_dot", "hm_inner_product_lintrans_id", "hm_inner_product_rotsum_init", "hm_ntt_mix_sub_scale_mul", "hm_ntt_mul",
     "hm_ntt_lift", "hm_tensor_square", "hm_lincomb", "hm_tensor_muladd", "hm_reim_split", "hm_clincomb", "hm_plincomb",
-    "hm_tensor_dotadd",
+    "hm_tensor_dotadd", "hm_lincomb_multi",
 ]
 
 
@@ -162,6 +164,7 @@ def load():
     L.hm_tensor_dot.argtypes = [vp] + [vp] * 15 + [u32, u32]
     L.hm_tensor_square.argtypes = [vp] + [vp] * 11 + [u32, vp, vp]
     L.hm_lincomb.argtypes = [vp] + [vp] * 5 + [u32, u32, vp, vp]
+    L.hm_lincomb_multi.argtypes = [vp] + [vp] * 5 + [u32, u32, u32, vp, vp]
     L.hm_tensor_muladd.argtypes = [vp] + [vp] * 18 + [u32, u32, vp, vp, vp]
     L.hm_reim_split.argtypes = [vp] + [vp] * 9 + [u32]
     L.hm_clincomb.argtypes = [vp] + [vp] * 5 + [u32, u32, vp, vp, vp, vp]
@@ -416,6 +419,15 @@ class Context:
         keep = [_u32(in_limbs), _u32(out_limbs), _u32(mod_ids)]
         ks, ka = _u64(scale), _u64(addend)
         self._ck(self.L.hm_lincomb(self.h, src.ptr, keep[0][1], out.ptr, keep[1][1], keep[2][1], len(mod_ids), int(n_terms), ks[1], ka[1]))
+
+    def lincomb_multi(self, src, in_limbs, out, out_limbs, mod_ids, n_terms, n_out, scale, addend=None):
+        """out[out_limbs[i][m]] = sum_t scale[i][m][t] * src[in_limbs[i][t]] + addend[i][m] per entry and output (hm_lincomb_multi): in_limbs is
+        row-major [n][n_terms], out_limbs and addend [n][n_out], scale [n][n_out][n_terms] (all flat), mod_ids [n] (a limb list None: the
+        identity), scale and addend residues of the entry's modulus (addend None: 0); buffers: anything with a device address `.ptr`"""
+        keep = [_u32(in_limbs), _u32(out_limbs), _u32(mod_ids)]
+        ks, ka = _u64(scale), _u64(addend)
+        self._ck(self.L.hm_lincomb_multi(self.h, src.ptr, keep[0][1], out.ptr, keep[1][1], keep[2][1], len(mod_ids), int(n_terms), int(n_out),
+                                         ks[1], ka[1]))
 
     def tensor_muladd(self, a, b, c, d, x, o0, o1, o2, mod_ids, n_addends=0, x0_limbs=None, x1_limbs=None, scale=None, add_scale=None, addend=None,
                       limbs=None):

@@ -149,7 +149,7 @@ class Op:
     def set_constants(self, name, values):
         """replace the op's per-limb constants `name` (hsquare: "scale", "const"; hlincomb: "scale1" .. "scale<T>", "const"; hmuladd: "scale",
         "addscale1" .. "addscale<A>", "const"; hclincomb: "scale1" .. "scale<T>", "scale_im1" .. "scale_im<T>", "const"; hdotadd: "scale1" ..
-        "scale<T>", "addscale1" .. "addscale<A>", "const") by one residue per
+        "scale<T>", "addscale1" .. "addscale<A>", "const"; hmlincomb: "scale<m>_<t>" for m = 1 .. M and t = 1 .. T, "const<m>") by one residue per
         limb of the current level, before the op is prepared (hh_op_set_constants); shared by the ops of a batch"""
         a = np.ascontiguousarray(np.asarray([int(v) for v in values], dtype=np.uint64))
         self._ck(self.L.hh_op_set_constants(self.h, name.encode(), a.ctypes.data_as(C.c_void_p), len(a)))

@@ -76,10 +76,11 @@ int main(int argc, char *argv[]) {
     HROTATE *hrotate = new HROTATE("test_hrotate", maxlevel, currentlevel, alpha, config, arch);
     if (arch->world() > 1) rcclRendezvous(arch, idFile);
     hrotate->simulate();
-  } else if (ops == "hrotate_hoisted" || ops == "hlintrans" || ops == "hdot" || ops == "hrotsum" || ops == "hbsgs" || ops == "hrescale" || ops == "hmodraise" || ops == "hsquare" || ops == "hlincomb" || ops == "hmuladd" || ops == "hreim" || ops == "hclincomb" || ops == "hplincomb" || ops == "hdotadd") {   // build extensions: R rotations of one ciphertext with one ModUp
+  } else if (ops == "hrotate_hoisted" || ops == "hlintrans" || ops == "hdot" || ops == "hrotsum" || ops == "hbsgs" || ops == "hrescale" || ops == "hmodraise" || ops == "hsquare" || ops == "hlincomb" || ops == "hmuladd" || ops == "hreim" || ops == "hclincomb" || ops == "hplincomb" || ops == "hdotadd" || ops == "hmlincomb") {   // build extensions: R rotations of one ciphertext with one ModUp
     OperationBase *hoisted = nullptr;                            // (config keys rotations, galois); hlintrans: their plaintext-weighted sum, one
     try {                                                        // ModDown; hdot: sum of `terms` ciphertext products, one key switch, one rescale
       if (ops == "hmodraise") hoisted = new HMODRAISE("test_hmodraise", maxlevel, currentlevel, alpha, config, arch);   // ModRaise of a level-1 ciphertext
+      else if (ops == "hmlincomb") hoisted = new HMLINCOMB("test_hmlincomb", maxlevel, currentlevel, alpha, config, arch);   // several scaled sums of the same ciphertexts plus constants (terms, outputs, ml_const)
       else if (ops == "hdotadd") hoisted = new HDOTADD("test_hdotadd", maxlevel, currentlevel, alpha, config, arch);   // scaled sum of products plus scaled ciphertexts plus constant (terms, addends, da_scale, da_const)
       else if (ops == "hplincomb") hoisted = new HPLINCOMB("test_hplincomb", maxlevel, currentlevel, alpha, config, arch);   // plaintext-weighted sum of ciphertexts plus a plaintext (terms, pl_addend)
       else if (ops == "hclincomb") hoisted = new HCLINCOMB("test_hclincomb", maxlevel, currentlevel, alpha, config, arch);   // complex-weighted sum of ciphertexts plus constant (terms, cl_const)

@@ -138,6 +138,7 @@ private:
   bool fuseMuladd = true;    // pass (5m): a tensor product takes the scalar, the scaled addends and the constant behind it (hmuladd)
   bool fuseReim = true;      // pass (5r): the sum and the rotated difference of a polynomial and its conjugate are formed in one pass over both (hreim)
   bool fuseClincomb = true;  // pass (5c): the real and the monomial part of every term of a complex-weighted sum are summed before anything is stored (hclincomb)
+  bool fuseMlincomb = true;  // pass (5L): the (5l) sums over one list of inputs read them once (hmlincomb)
   bool fuseDotadd = true;    // pass (5a): the tensor products of several pairs take their scalars, are summed, and take the scaled addends and the constant, in one pass (hdotadd)
   bool fusePlincomb = true;  // pass (5p): both components of a plaintext-weighted sum of ciphertexts are summed in one pass, each plaintext limb loaded once (hplincomb)
   bool fusePmulRescale = true;   // pass (4p): a product of two op inputs read by one transform is formed by that transform (pmult with rescale = 1)

@@ -89,6 +89,12 @@ public:
   std::vector<uint64_t> lcScales;
   bool lcHasConst = false;
   uint64_t lcConst = 0;
+  // (5L) several (5l) sums over ONE list of inputs (hm_lincomb_multi): the first of them, which absorbed the others.  lcOperands = the shared T
+  // inputs; mlScales[m] = the T scalars of output m, mlConsts[m] = its constant (0 where the absorbed record had none; mlHasConst: some had
+  // one); OutputOperand = output 1, extraOutputs = outputs 2 .. M, in the order the sums were emitted.  mlScales empty: not such a record
+  std::vector<std::vector<uint64_t>> mlScales;
+  std::vector<uint64_t> mlConsts;
+  bool mlHasConst = false;
   // (5m) scaled tensor product plus scaled addends plus constant (hm_tensor_muladd): a fusedTensor record that absorbed the chains behind its
   // outputs.  maOperands = (c00, c10, c01, c11) of the product, then (x_t, y_t) of every addend; maAddScales = the scalars u_t; OutputOperand = the
   // final d1, extraOutputs = the final d0, d2.  maHasScale: the MUL_CONST records behind the three outputs went in, all with the constant

@@ -151,7 +151,7 @@ protected:
   // HMULT's tail on the three polynomials d of a tensor product (shared by HMULT, HDOT, HSQUARE, HMULADD, HDOTADD): KS(d[2]); HMULT_Hadd_Key(k): d[k] + ks_k into
   // HMULTHaddOutput(k); Rescale of both, out = the result at level - 1
   void relinearizeAndRescale(const std::array<std::vector<AddrType>, 3> &d);
-  // Per-limb constants an op carries in its records (HSQUARE: "scale", "const"; HLINCOMB: "scale<t>", "const"; HCLINCOMB: "scale<t>", "scale_im<t>", "const"; HMULADD: "scale", "addscale<t>", "const"; HDOTADD: "scale<t>", "addscale<r>", "const"), by name: the records of limb j that hold value j, so that
+  // Per-limb constants an op carries in its records (HSQUARE: "scale", "const"; HLINCOMB: "scale<t>", "const"; HMLINCOMB: "scale<m>_<t>", "const<m>"; HCLINCOMB: "scale<t>", "scale_im<t>", "const"; HMULADD: "scale", "addscale<t>", "const"; HDOTADD: "scale<t>", "addscale<r>", "const"), by name: the records of limb j that hold value j, so that
   // setConstants can patch Instruction::constant before the plan is built.  enabled = false: the op knows the name but its config key is 0
   // negated: the records carry q_j - value (HCLINCOMB's "scale_im<t>": the stage multiplies by the stored -X^(N/2))
   struct ConstantStage { bool enabled = false; std::string key; std::vector<std::vector<Instruction *>> records; bool nonZero = false; bool negated = false; };
@@ -196,7 +196,7 @@ public:
   bool readBuffer(const std::string &name, uint64_t *host, uint32_t copy = 0);  // copy: op of the batch (config key `batch`)
   bool writeBuffer(const std::string &name, const uint64_t *host, uint32_t copy = 0);  // real data for an input / key buffer ([limbs][N], fully reduced)
   unsigned long long totalInstructions();
-  // replaces the per-limb constants `name` of the op (HSQUARE: "scale", "const"; HLINCOMB: "scale1" .. "scale<T>", "const"; HMULADD: "scale", "addscale1" .. "addscale<A>", "const"; HDOTADD: "scale1" .. "scale<T>", "addscale1" .. "addscale<A>", "const") by n = level residues, values[j] reduced mod q_j; before prepare() only.
+  // replaces the per-limb constants `name` of the op (HSQUARE: "scale", "const"; HLINCOMB: "scale1" .. "scale<T>", "const"; HMLINCOMB: "scale<m>_<t>", "const<m>"; HMULADD: "scale", "addscale1" .. "addscale<A>", "const"; HDOTADD: "scale1" .. "scale<T>", "addscale1" .. "addscale<A>", "const") by n = level residues, values[j] reduced mod q_j; before prepare() only.
   // Refused, by op and name: after prepare(), n != level, an unreduced value (or a zero where the constant multiplies), a name whose config key is 0
   void setConstants(const std::string &name, const uint64_t *values, uint32_t n);
   Arch *getArch() { return arch; }
@@ -256,6 +256,17 @@ public:
 class HLINCOMB : public OperationBase {
 public:
   HLINCOMB(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
+};
+// hmlincomb (build extension): out<m> = sum_t s_{m,t} * ct<t> + k_m for m = 1..M, M linear combinations of the SAME T ciphertexts at one level
+// (config keys terms = T as hlincomb: default 4, 1..16; outputs = M: default 4, 1..16) with per-limb scalars s_{m,t,j} in [0, q_j) (synthetic:
+// word 0 of limb j of stream seed + 8000 + 1000 m + 100 + 50 t; zero = the term contributes nothing) and, with config key ml_const = 1, per-limb
+// constants k_{m,j} on every evaluation-form entry of c0 only (stream seed + 8000 + 1000 m + 950): the baby blocks and the remainder of a
+// Paterson-Stockmeyer evaluation, which are M combinations of the same baby powers.  setConstants("scale<m>_<t>" | "const<m>") replaces the
+// synthetic values.  No key, no ModUp.  M output ciphertexts out1 .. out<M> at the inputs' level, or each through Rescale at level - 1 with
+// config key rescale = 1; "out" names out1.  Bit-identical to M hlincomb ops with the same constants
+class HMLINCOMB : public OperationBase {
+public:
+  HMLINCOMB(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch);
 };
 // hmuladd (build extension): out = Rescale(Relin(s * ct1 * ct2 + sum_t u_t * ct<2+t>) + k), one node of a polynomial evaluation (the Chebyshev step
 // T_{a+b} = 2 T_a T_b - T_{|a-b|}, the Paterson-Stockmeyer recombination p = q T_g + r).  2 + A input ciphertexts at one level (config key addends = A,
@@ -358,7 +369,7 @@ class OpChain {
   std::vector<Arch *> archs;
   std::vector<OperationBase *> ops;
 public:
-  // ops: comma-separated list of hmult | hrotate | hadd | pmult | padd | hlintrans | hdot | hrotsum | hbsgs | hrescale | hmodraise | hsquare | hlincomb | hmuladd | hreim | hclincomb | hplincomb | hdotadd, e.g. "hmult,hrotate,hadd,hmult"; hrotate_hoisted (R output
+  // ops: comma-separated list of hmult | hrotate | hadd | pmult | padd | hlintrans | hdot | hrotsum | hbsgs | hrescale | hmodraise | hsquare | hlincomb | hmuladd | hreim | hclincomb | hplincomb | hdotadd | hmlincomb ("out" = its out1), e.g. "hmult,hrotate,hadd,hmult"; hrotate_hoisted (R output
   // ciphertexts) only as the last op
   OpChain(const std::string &cfgPath, const std::string &opList, uint32_t maxLevel, uint32_t curLevel, uint32_t alpha,
           const std::map<std::string, uint32_t> &overrides = {});

@@ -86,7 +86,7 @@ inline std::vector<Read> recordReads(const Instruction &i) {
     for (AddrType a : i.dotOperands) v.push_back({a, Role::Operand, kNoDigit});
   } else if (!i.sqOperands.empty()) {    // (5q): the two polynomials of the one ciphertext, each read once
     for (AddrType a : i.sqOperands) v.push_back({a, Role::Operand, kNoDigit});
-  } else if (!i.lcOperands.empty()) {    // (5l): the input of every term
+  } else if (!i.lcOperands.empty()) {    // (5l): the input of every term; (5L, several sums over them: mlScales) once for all outputs, which are OutputOperand and extraOutputs
     for (AddrType a : i.lcOperands) v.push_back({a, Role::Operand, kNoDigit});
   } else if (!i.maOperands.empty()) {    // (5m): the four operands of the product, then both components of every addend
     for (AddrType a : i.maOperands) v.push_back({a, Role::Operand, kNoDigit});

@@ -45,9 +45,9 @@ int hh_op_write_buffer(hh_op *op, const char *name, uint32_t copy, const uint64_
 /* replaces the per-limb constants `name` of the op (hsquare: "scale", the s_j in [1, q_j); "const", the k_j in [0, q_j); hlincomb: "scale1" .. "scale<T>",
  * the s_{t,j} in [0, q_j), and "const"; hmuladd: "scale", "addscale1" .. "addscale<A>", the u_{t,j} in [0, q_j), and "const"; hclincomb:
  * "scale1" .. "scale<T>" and "scale_im1" .. "scale_im<T>", the a_{t,j} and b_{t,j} in [0, q_j), and "const"; hdotadd: "scale1" .. "scale<T>", the s_{t,j} in [1, q_j), "addscale1" .. "addscale<A>" and
- * "const") by n = level residues;
+ * "const"; hmlincomb: "scale<m>_<t>", the s_{m,t,j} in [0, q_j), and "const<m>", m = 1 .. M, t = 1 .. T) by n = level residues;
  * shared by the ops of a batch.  Before the op is prepared only; refused by op and name otherwise, and for n != level, an unreduced value, a
- * zero scale, or a name whose config key (sq_scale, sq_const, lc_const, ma_scale, ma_const, cl_const, da_scale, da_const) is 0. */
+ * zero scale, or a name whose config key (sq_scale, sq_const, lc_const, ma_scale, ma_const, cl_const, da_scale, da_const, ml_const) is 0. */
 int hh_op_set_constants(hh_op *op, const char *name, const uint64_t *values, uint32_t n);
 uint32_t hh_op_batch(hh_op *op);
 int hh_op_plan(hh_op *op, char *out, uint32_t cap);          /* launch plan, one line per launch */

@@ -35,7 +35,8 @@ struct Arch::Launch {
               L_REIM,                                        // (5r) the sum and the rotated difference of a polynomial and its conjugate
               L_CLINCOMB,                                    // (5c) the sum of polynomials times a + b X^(N/2) plus a constant
               L_PLINCOMB,                                    // (5p) the sum of ciphertexts times plaintexts plus a plaintext on c0, both components
-              L_TENSOR_DOTADD } kind;                        // (5a) the scaled sum of tensor products plus scaled addends plus a constant
+              L_TENSOR_DOTADD,                               // (5a) the scaled sum of tensor products plus scaled addends plus a constant
+              L_LINCOMB_MULTI } kind;                        // (5L) several sums of scaled polynomials over the same inputs, each plus a constant
   std::vector<uint32_t> hoistG;   // L_IP_HOISTED: the Galois element of every rotation (a: digits [n][T], b: keys [r][n][2][T], out: [r][n][2])
                                   // L_IP_LINTRANS: the same, with c: plaintexts [r][n], d: addend source [n] / out1: addend output [n] (HM_NO_LIMB: none; both
                                   // empty: no entry has one), out: [n][2]
@@ -61,6 +62,8 @@ struct Arch::Launch {
   std::vector<uint32_t> idPt, d1;
   uint32_t dotTerms = 0;          // L_TENSOR_DOT: pairs per record (a, b, c, d: [n][dotTerms], roles as L_TENSOR; out, out1, out2: [n])
                                   // L_LINCOMB: terms per record (a: [n][dotTerms], out: [n]; k: the scalars [n][dotTerms], addK: the constants [n], empty: none)
+                                  // L_LINCOMB_MULTI: terms per record and multiOuts sums (a: [n][dotTerms], out: [n][multiOuts]; k: the scalars
+                                  // [n][multiOuts][dotTerms], addK: the constants [n][multiOuts], empty: none)
                                   // L_TENSOR_SQUARE: a = c0, c = c1, out, out1, out2 = d0, d1, d2 [n]; k: the scalars [n], addK: the constants [n] (empty: none)
                                   // L_REIM: a = the polynomial, c = its conjugate, out = the sum, out1 = the rotated difference [n]
                                   // L_CLINCOMB: as L_LINCOMB with k: the real parts a_t, maK: the monomial parts b_t [n][dotTerms]
@@ -186,6 +189,9 @@ Arch::Arch(Config *cfg) : config(cfg) {
   // (5a) hdotadd: the tensor products of all pairs, the scalars on their outputs, the ADDs between the pairs, the MUL_CONST + ADD pairs of the
   // addends on d0 and d1 and the constant on d0 become one hm_tensor_dotadd launch.  Config key fuse_dotadd (default 1).
   fuseDotadd = cfg->getValueOr("fuse_dotadd", 1) != 0;
+  // (5L) hmlincomb: the (5l) records over one list of inputs become one record of ONE hm_lincomb_multi launch.  Config key fuse_mlincomb
+  // (default 1); 0 leaves them to (5l)'s launch
+  fuseMlincomb = cfg->getValueOr("fuse_mlincomb", 1) != 0;
   // (4p) pmult with rescale = 1: the products are formed by the rescale's transforms while they load.  Config key fuse_pmul_rescale: 1 / 0 = always /
   // never; not given = where it was measured faster than the three-launch plan: everywhere but the generic back-end's launches
   // inside the one-launch form's limit, which has no product form there (Planner::productOperands)
@@ -349,6 +355,7 @@ int partKey(const Instruction &i) {
   if (isKeyProduct(i)) return 300 + (int)i.ipX.size() * 10 + (int)i.ipY.size();                            // 300+: key product, by digits and keys
   if (!i.dotOperands.empty()) return 8000 + (int)i.dotOperands.size() / 4;                                 // 8000+: sum of tensor products, by pairs
   if (!i.sqOperands.empty()) return 8500 + (i.sqHasScale ? 1 : 0) + (i.sqHasConst ? 2 : 0);                // 8500+: scaled square plus constant, by what it absorbed
+  if (!i.mlScales.empty()) return 12000 + 16 * ((int)i.lcOperands.size() - 1) + (int)i.mlScales.size() - 1;   // 12000+: several sums of scaled polynomials, by terms and sums (12000 .. 12255)
   if (!i.lcOperands.empty()) return 8600 + (int)i.lcOperands.size();                                   // 8600+: sum of scaled polynomials, by terms
   if (!i.maOperands.empty()) return 8700 + 4 * (int)i.maAddScales.size() + (i.maHasScale ? 1 : 0) + (i.maHasConst ? 2 : 0);   // 8700+: scaled product plus addends, by addends and what it absorbed
   if (!i.daOperands.empty()) return 8100 + 9 * ((int)i.daScales.size() - 1) + (int)i.daAddScales.size();                          // 8100+: scaled sum of products plus addends, by pairs and addends (8100 .. 8243)
@@ -525,6 +532,7 @@ struct Arch::LaunchBuilder {
   void tensorDot(Launch &L, Recs recs);
   void tensorSquare(Launch &L, Recs recs);
   void lincomb(Launch &L, Recs recs);
+  void lincombMulti(Launch &L, Recs recs);
   void tensorMulAdd(Launch &L, Recs recs);
   void reim(Launch &L, Recs recs);
   void clincomb(Launch &L, Recs recs);
@@ -706,6 +714,26 @@ void Arch::LaunchBuilder::lincomb(Launch &L, Recs recs) {
   if (std::any_of(recs.begin(), recs.end(), [](const Instruction *i) { return i->lcHasConst; }))
     for (Instruction *i : recs) L.addK.push_back(i->lcHasConst ? i->lcConst : 0);
   L.bytes = (L.dotTerms + 1ull) * LP * recs.size();   // every input read once, the sum written once
+}
+
+// (5L) a = the input of every term [n][T]; out = the M sums [n][M]; k = the scalars [n][M][T], addK = the constants [n][M] (hm_lincomb_multi).  The
+// part key keeps records of different term and sum counts apart; a record without constants (c1 beside a c0 that has them) adds 0.  The back-end
+// reads the inputs once per tile of HM_LINCOMB_MULTI_TILE sums
+void Arch::LaunchBuilder::lincombMulti(Launch &L, Recs recs) {
+  L.kind = Launch::L_LINCOMB_MULTI; L.statKey = "EWE";
+  L.dotTerms = (uint32_t)recs[0]->lcOperands.size();
+  L.multiOuts = (uint32_t)recs[0]->mlScales.size();
+  for (Instruction *i : recs) {
+    for (AddrType x : i->lcOperands) L.a.push_back(limb(x));
+    for (const std::vector<uint64_t> &row : i->mlScales) L.k.insert(L.k.end(), row.begin(), row.end());
+    L.out.push_back(limb(i->OutputOperand));
+    for (AddrType o : i->extraOutputs) L.out.push_back(limb(o));
+    L.mods.push_back(i->mod_id);
+  }
+  if (std::any_of(recs.begin(), recs.end(), [](const Instruction *i) { return i->mlHasConst; }))
+    for (Instruction *i : recs) L.addK.insert(L.addK.end(), i->mlConsts.begin(), i->mlConsts.end());
+  const unsigned long long tiles = (L.multiOuts + HM_LINCOMB_MULTI_TILE - 1) / HM_LINCOMB_MULTI_TILE;
+  L.bytes = (tiles * L.dotTerms + L.multiOuts) * LP * recs.size();   // every input read once per tile of sums, every sum written once
 }
 
 // (5m) a, b, c, d = c00, c10, c01, c11 [n]; x0, x1 = c0, c1 of every addend [n][A]; out, out1, out2 = d0, d1, d2 [n]; k = the scalars [n], maK = the
@@ -970,6 +998,7 @@ void Arch::LaunchBuilder::emitCompute(const Group &group, Launches &front, Launc
   else if (isKeyProduct(*f)) ip(*L, recs);
   else if (!f->dotOperands.empty()) tensorDot(*L, recs);
   else if (!f->sqOperands.empty()) tensorSquare(*L, recs);
+  else if (!f->mlScales.empty()) lincombMulti(*L, recs);
   else if (!f->lcOperands.empty()) lincomb(*L, recs);
   else if (!f->maOperands.empty()) tensorMulAdd(*L, recs);
   else if (!f->reimOperands.empty()) reim(*L, recs);
@@ -1401,7 +1430,8 @@ void Arch::prepare() {
 
 static const char *const kLaunchKindNames[] = {"NTT", "INTT", "EWE", "BCONV", "AUTO", "NTT_SUBSCALE", "TENSOR", "EXCH_IN", "EXCH_OUT", "REPLICATE", "IP", "NTT_IP",
                                                "BCONV_COL", "EXCH_IN_COL", "EXCH_OUT_COL", "IP_HOISTED", "IP_LINTRANS", "TENSOR_DOT", "IP_ROTSUM",
-                                               "IP_LINTRANS_MULTI", "TENSOR_SQUARE", "LINCOMB", "TENSOR_MULADD", "REIM", "CLINCOMB", "PLINCOMB", "TENSOR_DOTADD"};
+                                               "IP_LINTRANS_MULTI", "TENSOR_SQUARE", "LINCOMB", "TENSOR_MULADD", "REIM", "CLINCOMB", "PLINCOMB", "TENSOR_DOTADD",
+                                               "LINCOMB_MULTI"};
 
 // Per-launch device time (SURVEY.md §8d "per-stage hipEvent times", exchange time at N > 1): every launch of the plan
 // bracketed by its own event pair, in plan order so that the data dependencies (and, sharded, the collectives) line up.
@@ -1457,6 +1487,8 @@ std::string Arch::planText() const {
       out += std::string(" scale=") + (l->k.empty() ? "0" : "1") + " const=" + (l->addK.empty() ? "0" : "1");
     if (l->kind == Launch::L_LINCOMB)   // (5l): terms summed per record, and whether a constant follows
       out += " terms=" + std::to_string(l->dotTerms) + " const=" + (l->addK.empty() ? "0" : "1");
+    if (l->kind == Launch::L_LINCOMB_MULTI)   // (5L): terms and sums per record, and whether constants follow
+      out += " terms=" + std::to_string(l->dotTerms) + " out=" + std::to_string(l->multiOuts) + " const=" + (l->addK.empty() ? "0" : "1");
     if (l->kind == Launch::L_CLINCOMB)   // (5c): terms summed per record, and whether a constant follows
       out += " terms=" + std::to_string(l->dotTerms) + " const=" + (l->addK.empty() ? "0" : "1");
     if (l->kind == Launch::L_PLINCOMB)   // (5p): terms summed per record, and whether a plaintext addend follows
@@ -1504,7 +1536,7 @@ std::string Arch::planDump() const {
            " mark=" + std::to_string(l->recordSlot) + " xin=" + indexOf(l->xin) + " xout=" + indexOf(l->xout);
     if (l->dotTerms) out += " terms=" + std::to_string(l->dotTerms);
     if (l->kind == Launch::L_TENSOR_MULADD || l->kind == Launch::L_TENSOR_DOTADD) out += " addends=" + std::to_string(l->maAddends);
-    if (l->kind == Launch::L_IP_LINTRANS_MULTI) out += " multiOuts=" + std::to_string(l->multiOuts);   // (one sum: the line of L_IP_LINTRANS has no such field)
+    if (l->kind == Launch::L_IP_LINTRANS_MULTI || l->kind == Launch::L_LINCOMB_MULTI) out += " multiOuts=" + std::to_string(l->multiOuts);   // (one sum: the line of L_IP_LINTRANS has no such field)
     vec("wait", l->waitSlots); vec("hoistG", l->hoistG); vec("ipCoeff", l->ipCoeff); vec("ipInv", l->ipInv); vec("outPacked", l->outPacked);
     vec("inGalois", l->inGalois); vec("addGalois", l->addGalois); vec("mulB", l->mulB); vec("liftMods", l->liftMods);
     vec("idPt", l->idPt); vec("d1", l->d1);
@@ -1649,6 +1681,10 @@ void Arch::enqueue(Launch &l) {
     break;
   case Launch::L_LINCOMB:
     st = hm_lincomb(ctx, pool, l.a.data(), pool, l.out.data(), l.mods.data(), cnt, l.dotTerms, l.k.data(), l.addK.empty() ? nullptr : l.addK.data());
+    break;
+  case Launch::L_LINCOMB_MULTI:
+    st = hm_lincomb_multi(ctx, pool, l.a.data(), pool, l.out.data(), l.mods.data(), (uint32_t)l.mods.size(), l.dotTerms, l.multiOuts, l.k.data(),
+                          l.addK.empty() ? nullptr : l.addK.data());
     break;
   case Launch::L_TENSOR_MULADD:
     st = hm_tensor_muladd(ctx, pool, l.a.data(), pool, l.b.data(), pool, l.c.data(), pool, l.d.data(), l.maAddends ? pool : nullptr,

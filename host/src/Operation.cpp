@@ -1016,6 +1016,95 @@ HLINCOMB::HLINCOMB(std::string labelName, uint32_t maxLevel, uint32_t currentLev
   finishConstruction();
 }
 
+// hmlincomb (build extension).  For every output m, HLINCOMB's stages from existing opcodes only.  Per component k, with
+// x_t = ct<t>.c<k>: MLinComb_Scale_(m,t)_C<k> = s_{m,t} x_t (MUL_CONST) for every t, MLinComb_Add_(m,t)_C<k> = the running sum plus term t (ADD)
+// for t >= 2, and with ml_const = 1 MLinComb_Const_(m)_C0 = the sum of c0 plus k_m (ADD_CONST).  The last buffer of a sum is MLinCombOutput(m,k).
+// Every sum is emitted before any rescale, so that nothing reads an output in front of the last sum.  Unfused, the stages run as element-wise
+// launches; fused, pass (5l) turns each (m, limb, component) chain into one record and pass (5L) merges the M records over one list of inputs
+// into one record of ONE hm_lincomb_multi launch (Planner.cpp); fuse_mlincomb = 0 leaves them to (5l)'s launch.
+HMLINCOMB::HMLINCOMB(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch)
+    : OperationBase("HMLINCOMB", labelName, cfg, _arch, maxLevel, currentLevel, alpha) {
+  if (arch->backend() == Arch::BACKEND_SIM) throw std::runtime_error("hmlincomb: backend = sim has no such op (the reference has no scalar product)");
+  if (arch->world() > 1) throw std::runtime_error("hmlincomb: world > 1 is not supported (the sharded plan is not built)");
+  const uint32_t T = cfg->getValueOr("terms", 4);
+  if (T < 1 || T > 16) throw std::runtime_error("hmlincomb: terms = " + S(T) + ", must be in [1, 16]");
+  const uint32_t M = cfg->getValueOr("outputs", 4);
+  if (M < 1 || M > 16) throw std::runtime_error("hmlincomb: outputs = " + S(M) + ", must be in [1, 16]");
+  const uint32_t mc = cfg->getValueOr("ml_const", 0);
+  if (mc > 1) throw std::runtime_error("hmlincomb: ml_const = " + S(mc) + ", must be 0 or 1");
+  const uint32_t fm = cfg->getValueOr("fuse_mlincomb", 1);
+  if (fm > 1) throw std::runtime_error("hmlincomb: fuse_mlincomb = " + S(fm) + ", must be 0 or 1");
+  const bool shifted = mc == 1, rescale = rescaleKey("hmlincomb");
+  if (rescale && currentLevel < 2) throw std::runtime_error("hmlincomb: Rescale needs at least two limbs");
+  makeInputs(T);
+  // the records of limb j of a constant stage, kept by name for setConstants; both components share the scalars
+  auto keep = [&](const std::string &name, const std::vector<INSGROUP> &recs) {
+    ConstantStage &cs = constantStages[name];
+    cs.enabled = true;
+    cs.records.resize(currentLevel);
+    for (uint32_t j = 0; j < currentLevel; ++j) cs.records[j].push_back(recs[j][0]);
+  };
+  auto synth = [&](uint64_t stream) {
+    std::vector<uint64_t> v;
+    for (uint32_t j = 0; j < currentLevel; ++j) v.push_back(synthWord0(stream + j, arch->modulus(j)));
+    return v;
+  };
+  std::vector<std::array<std::vector<AddrType>, 2>> outs(M);
+  for (uint32_t m = 1; m <= M; ++m) {
+    constantStages["const" + S(m)].key = "ml_const";
+    const uint64_t streams = seed + 8000 + 1000ull * m;
+    for (uint32_t k = 0; k < 2; k++) {
+      const std::string C = "_C" + S(k), result = "MLinCombOutput(" + S(m) + "," + S(k) + ")";
+      const bool constHere = shifted && k == 0;
+      Limbs sum;
+      for (uint32_t t = 1; t <= T; ++t) {
+        const std::string mt = "(" + S(m) + "," + S(t) + ")";
+        const bool lastScale = T == 1 && !constHere;
+        PerLimb s{labelName + "_MLinComb_Scale_" + mt + C + "_Level(", ")", range(0, currentLevel),
+                  alloc(lastScale ? result : "MLinCombScaled" + mt + C, currentLevel)};
+        s.a = component(t - 1, k);
+        s.constants = synth(streams + 100 + 50ull * t);
+        const Limbs scaled{s.out, eweLimbs(&insgener, EWE_MUL_CONST, s)};
+        driver.dispatchInstructions("MLinComb_Scale_" + mt + C, scaled.from);
+        keep("scale" + S(m) + "_" + S(t), scaled.from);
+        if (t == 1) {
+          for (const INSGROUP &g : scaled.from) g[0]->lincombHead = true;
+          sum = scaled;
+          continue;
+        }
+        const bool lastAdd = t == T && !constHere;
+        PerLimb a{labelName + "_MLinComb_Add_" + mt + C + "_Level(", ")", s.mods, alloc(lastAdd ? result : "MLinCombSum" + mt + C, currentLevel)};
+        const Limbs before = sum;
+        a.a = before.addr; a.c = scaled.addr; a.after = {&before.from, &scaled.from};
+        sum = {a.out, eweLimbs(&insgener, EWE_ADD, a)};
+        driver.dispatchInstructions("MLinComb_Add_" + mt + C, sum.from);
+      }
+      if (constHere) {
+        PerLimb c{labelName + "_MLinComb_Const_(" + S(m) + ")" + C + "_Level(", ")", range(0, currentLevel), alloc(result, currentLevel)};
+        const Limbs before = sum;
+        c.a = before.addr; c.after = {&before.from};
+        c.constants = synth(streams + 950);
+        sum = {c.out, eweLimbs(&insgener, EWE_ADD_CONST, c)};
+        driver.dispatchInstructions("MLinComb_Const_(" + S(m) + ")" + C, sum.from);
+        keep("const" + S(m), sum.from);
+      }
+      outs[m - 1][k] = sum.addr;
+    }
+  }
+  for (uint32_t m = 1; m <= M; ++m)
+    for (uint32_t k = 0; k < 2; k++) {
+      std::vector<AddrType> out = outs[m - 1][k];
+      if (rescale) {   // setRescaledOutput's builder, with a label of its own per output
+        Rescale res(label + "_Out" + S(m) + "_" + S(k), level_, out, &Datapool, &DataInsMap, &insgener, addrManager.get());
+        dispatch(res.getInsMap());
+        out = res.output();
+      }
+      setOutput("out" + S(m), k, out);
+      if (m == 1) setOutput("out", k, out);   // "out" names out1: the op is a legal link of a chain
+    }
+  finishConstruction();
+}
+
 // hclincomb (build extension).  Per component k and term t, with x_t = ct<t>.c<k>, existing opcodes only, `unit` being HREIM's
 // named buffer U = -X^(N/2) in evaluation form (Arch::addUnitFill), so that +X^(N/2) b is U (q - b mod q):
 //   CLinComb_Re_(t)_C<k> = a_t x_t (MUL_CONST),  CLinComb_Rot_(t)_C<k> = x_t (.) unit (MUL),  CLinComb_Im_(t)_C<k> = that times (q - b_t) mod q (MUL_CONST),
@@ -1576,6 +1665,7 @@ static OperationBase *makeOp(const std::string &o, uint32_t maxLevel, uint32_t l
   if (o == "hmodraise") return new HMODRAISE("test_hmodraise", maxLevel, level, alpha, cfg, arch);
   if (o == "hsquare") return new HSQUARE("test_hsquare", maxLevel, level, alpha, cfg, arch);
   if (o == "hlincomb") return new HLINCOMB("test_hlincomb", maxLevel, level, alpha, cfg, arch);
+  if (o == "hmlincomb") return new HMLINCOMB("test_hmlincomb", maxLevel, level, alpha, cfg, arch);
   if (o == "hmuladd") return new HMULADD("test_hmuladd", maxLevel, level, alpha, cfg, arch);
   if (o == "hreim") return new HREIM("test_hreim", maxLevel, level, alpha, cfg, arch);
   if (o == "hclincomb") return new HCLINCOMB("test_hclincomb", maxLevel, level, alpha, cfg, arch);

@@ -107,6 +107,7 @@ struct Arch::Planner {
   void tensorDot();        // 5d
   void tensorSquare();     // 5q
   void linearCombination();   // 5l
+  void multiCombination();    // 5L
   void tensorMulAdd();     // 5m
   void realImaginary();    // 5r
   void complexCombination();   // 5c
@@ -154,6 +155,7 @@ void Arch::fusePasses(std::vector<Stage> &st) {
   if (fuseDot) p.tensorDot();   // before (6): the multiply-accumulate chains it absorbs are not key products
   if (fuseSquare) p.tensorSquare();
   if (fuseLincomb) p.linearCombination();
+  if (fuseMlincomb) p.multiCombination();   // behind (5l): it merges the records (5l) formed
   if (fuseMuladd) p.tensorMulAdd();
   if (fuseReim) p.realImaginary();
   if (fuseClincomb) p.complexCombination();
@@ -564,6 +566,46 @@ void Arch::Planner::linearCombination() {
     c->OutputOperand = sum;
     producer[sum] = c;
     place.moveTo(c, last);   // to where its last link stood
+  }
+}
+
+// (5L) several sums of scaled polynomials over the same inputs (hmlincomb): the live (5l) records of one modulus whose lcOperands are the same list
+//      in the same order merge, up to HM_LINCOMB_MULTI_MAX_OUT at a time, into the first of them: hm_lincomb_multi loads every input once per
+//      tile of outputs and stores every sum once.  The merged record carries the outputs, the scalar rows and the constants in the order the sums
+//      stand in the stages, the refInstructions of everything it absorbs, and takes the place of the last record it absorbs: every input is
+//      produced in front of the first of them, and nothing reads an output in front of the last (the builder emits every sum before anything that
+//      reads one).  Only HMLINCOMB produces several (5l) records over one operand list: the pass matches nothing in any other op.
+//      Sets on the first record: mlScales, mlConsts, mlHasConst, OutputOperand (unchanged), extraOutputs.
+void Arch::Planner::multiCombination() {
+  Placement place(st);
+  typedef std::pair<uint32_t, std::vector<AddrType>> Key;
+  std::map<Key, std::vector<Instruction *>> members;
+  std::vector<Key> order;   // first appearance
+  for (auto &s : st)
+    for (Instruction *i : s.ins)
+      if (live(i) && !i->lcOperands.empty() && i->mlScales.empty() && i->extraOutputs.empty()) {
+        const Key k{i->mod_id, i->lcOperands};
+        if (!members.count(k)) order.push_back(k);
+        members[k].push_back(i);
+      }
+  for (const Key &k : order) {
+    const std::vector<Instruction *> &mem = members[k];
+    for (size_t b = 0; b < mem.size(); b += HM_LINCOMB_MULTI_MAX_OUT) {
+      const size_t e = std::min(mem.size(), b + (size_t)HM_LINCOMB_MULTI_MAX_OUT);
+      if (e - b < 2) continue;   // one sum: (5l)'s record and launch
+      Instruction *c = mem[b], *last = c;
+      for (size_t m = b; m < e; ++m) {
+        Instruction *i = mem[m];
+        c->mlScales.push_back(i->lcScales);
+        c->mlConsts.push_back(i->lcHasConst ? i->lcConst : 0);
+        c->mlHasConst = c->mlHasConst || i->lcHasConst;
+        if (i != c) c->extraOutputs.push_back(i->OutputOperand);
+        absorb(c, i);
+        if (place.after(i, last)) last = i;
+      }
+      for (const Write &w : recordWrites(*c)) producer[w.addr] = c;
+      place.moveTo(c, last);
+    }
   }
 }
 

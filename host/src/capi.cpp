@@ -60,6 +60,7 @@ int hh_op_create(hh_op **out, const char *cfg_path, const char *op_name, uint32_
     else if (o == "hmodraise") h->op = new HMODRAISE("test_hmodraise", maxLevel, curLevel, alpha, h->cfg, h->arch);
     else if (o == "hsquare") h->op = new HSQUARE("test_hsquare", maxLevel, curLevel, alpha, h->cfg, h->arch);
     else if (o == "hlincomb") h->op = new HLINCOMB("test_hlincomb", maxLevel, curLevel, alpha, h->cfg, h->arch);
+    else if (o == "hmlincomb") h->op = new HMLINCOMB("test_hmlincomb", maxLevel, curLevel, alpha, h->cfg, h->arch);
     else if (o == "hmuladd") h->op = new HMULADD("test_hmuladd", maxLevel, curLevel, alpha, h->cfg, h->arch);
     else if (o == "hreim") h->op = new HREIM("test_hreim", maxLevel, curLevel, alpha, h->cfg, h->arch);
     else if (o == "hclincomb") h->op = new HCLINCOMB("test_hclincomb", maxLevel, curLevel, alpha, h->cfg, h->arch);

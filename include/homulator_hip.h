@@ -203,6 +203,25 @@ hm_status hm_tensor_square(hm_ctx *ctx, const uint64_t *a, const uint32_t *a_lim
 hm_status hm_lincomb(hm_ctx *ctx, const uint64_t *in, const uint32_t *in_limbs, uint64_t *out, const uint32_t *out_limbs,
                      const uint32_t *mod_ids, uint32_t n, uint32_t n_terms, const uint64_t *scale, const uint64_t *addend);
 
+/* K3, n_out scaled sums of the SAME n_terms limb-polys, each plus a constant, the inputs read once per tile of outputs (HMLINCOMB, DESIGN.md
+ * section 26): for entry i and output m, with s_t = scale[(i * n_out + m) * n_terms + t] in [0, q) and k = addend[i * n_out + m] in [0, q), per
+ * coefficient
+ *   out[i][m] = sum_t s_t * in[i][t] + k,   t < n_terms <= 16,   m < n_out <= HM_LINCOMB_MULTI_MAX_OUT,
+ * the canonical residue of the exact integer sum: bit-identical to n_out calls of hm_lincomb that differ in out, scale and addend.  A
+ * workgroup forms a tile of HM_LINCOMB_MULTI_TILE outputs of its entry and chunk, so the inputs are read ceil(n_out / tile) times and every
+ * output is written once: (ceil(n_out / tile) n_terms + n_out) limb-polys per entry where the n_out calls move n_out (n_terms + 1).
+ * in_limbs is row-major, in_limbs[i * n_terms + t] (the same limb-poly may appear in several entries and terms); out_limbs is row-major,
+ * out_limbs[i * n_out + m]; mod_ids has n entries; a null limb list is the identity.  scale and addend are host arrays; addend == NULL: every
+ * k is 0.  The records live in a device table: one launch serves any n, and the call is safe under graph capture once it has run with the
+ * same lists and constants.  HM_ERR_ARG: a null buffer or a null mod_ids / scale, n_terms outside 1..16, n_out outside 1..16, a limb or
+ * modulus id out of range, an unreduced scale or addend, a record table beyond 2^32 words, an output limb-poly that overlaps (by address
+ * range, not by base pointer) an input limb-poly or another output limb-poly.  n = 0 is HM_OK.
+ * hm_set_option("lincomb_multi_tile", 4 | 8) selects the other built tile for measurements (0: the default); it changes no result. */
+#define HM_LINCOMB_MULTI_MAX_OUT 16
+#define HM_LINCOMB_MULTI_TILE    4
+hm_status hm_lincomb_multi(hm_ctx *ctx, const uint64_t *in, const uint32_t *in_limbs, uint64_t *out, const uint32_t *out_limbs,
+                           const uint32_t *mod_ids, uint32_t n, uint32_t n_terms, uint32_t n_out, const uint64_t *scale, const uint64_t *addend);
+
 /* K3, scaled tensor product of two ciphertexts plus a linear combination of n_addends further ciphertexts plus a constant, in one pass over the
  * 4 + 2 n_addends input polynomials (HMULADD): for entry i, with the roles of hm_tensor (a = c00, b = c10, c = c01,
  * d = c11), x_t / y_t = c0 / c1 of addend t, s = scale[i] in [1, q), u_t = add_scale[i * n_addends + t] in [0, q) and k = addend[i] in [0, q),
