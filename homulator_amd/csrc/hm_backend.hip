@@ -22,6 +22,7 @@
 #include "hm_ip_core.h"
 #include "hm_modarith.h"
 #include "hm_ntt_core.h"
+#include "hm_slot_core.h"
 #include "hm_params.h"
 #include "hm_caps.h"
 #include "hm_launch.h"
@@ -398,6 +399,28 @@ __global__ void __launch_bounds__((1 << HM_TL_ROW) / 8) k_ntt_fused8(HmNttArgs a
 // hand-off resident only at a look-ahead where second passes wait for first passes (-24 % fabric traffic, +27 % time) and loses 14 % at
 // the look-ahead where nobody waits, because the L2 then no longer holds the hand-off: profiles/r05_ntt_queue.txt.  Removed in round 5.)
 
+// ---- the slot transform (hm_slot_core.h; hm_encode / hm_decode): one launch per pass, a workgroup per tile of a vector ----
+template <bool INVERSE, bool HIGH>
+__device__ __forceinline__ void hm_slot_pass(const HmSlotArgs &a, HmC *lds, uint32_t v, uint32_t tile, uint32_t tid) {
+  if constexpr (!HIGH && !INVERSE) hm_slot_load_coef(a, v, tile, tid, lds);
+  else hm_slot_load<HIGH>(a, v, tile, tid, lds);
+  __syncthreads();
+  for (uint32_t s = 0; s < (HIGH ? a.log1 : a.log2); ++s) {
+    hm_slot_stage<INVERSE, HIGH>(a, tile, tid, lds, s);
+    __syncthreads();
+  }
+  if constexpr (!HIGH && INVERSE) hm_slot_store_coef(a, v, tile, tid, lds);
+  else hm_slot_store<HIGH>(a, v, tile, tid, lds);
+}
+// INVERSE = encode (HIGH pass, then LOW with the rounding epilogue); forward = decode (LOW with the centring prologue, then HIGH)
+template <bool INVERSE>
+__global__ void __launch_bounds__(HM_SLOT_THREADS) k_slot_fft(HmSlotArgs a, uint32_t high) {
+  __shared__ __attribute__((aligned(16))) HmC lds[HM_SLOT_LDS];
+  const uint32_t v = blockIdx.x / a.tiles, tile = blockIdx.x % a.tiles;
+  if (high) hm_slot_pass<INVERSE, true>(a, lds, v, tile, threadIdx.x);
+  else hm_slot_pass<INVERSE, false>(a, lds, v, tile, threadIdx.x);
+}
+
 // ---- K1 x K5: last transform pass x evaluation key, both keys, all digits of one extended limb in one workgroup ---------
 #define HM_NIP_MAX_TERMS 4
 static_assert(HM_GENERIC || HM_NIP_MAX_TERMS <= 5, "mont32 lazy key products: five terms of less than 1.5q + 2^28 stay below 8q (hm_mac_add)");
@@ -731,6 +754,12 @@ struct hm_ctx {
   // one-launch transforms (k_ntt_fused): rendezvous words in HBM, a host-visible error word, and the switch
   HmNttSync *ntt_ws = nullptr;
   unsigned *err_host = nullptr, *err_dev = nullptr;
+  // the slot transform (hm_encode / hm_decode): root and exponent tables, the overflow flag, and the hand-off between encode's passes; made by
+  // the first call that needs them (slot_prepare)
+  HmC *d_slot_roots = nullptr, *d_slot_tmp = nullptr;
+  uint32_t *d_slot_rot = nullptr, *d_slot_flag = nullptr;
+  size_t slot_tmp_vecs = 0;
+  std::vector<HmC *> slot_tmp_retired;   // hand-offs outgrown while a captured graph lived
   bool small_ept8 = true;      // launches of at most small_limbs entries use the 8-coefficient geometry (N = 2^16)
   uint32_t small_mode = 3;     // which passes of a small launch use it: bit 0 COL, bit 1 ROW
   uint32_t small_limbs = 64;   // measured (tools/ntt_small_ab.py): 2-3 us per launch faster up to ~64 entries, equal at 115, slower from 128
@@ -951,6 +980,11 @@ extern "C" void hm_destroy(hm_ctx *c) {
   (void)hipFree(c->d_twist_inv);
   (void)hipFree(c->d_mods);
   (void)hipFree(c->ntt_ws);
+  (void)hipFree(c->d_slot_roots);
+  (void)hipFree(c->d_slot_rot);
+  (void)hipFree(c->d_slot_flag);
+  (void)hipFree(c->d_slot_tmp);
+  for (HmC *p : c->slot_tmp_retired) (void)hipFree(p);
   (void)hipHostFree(c->err_host);
   if (c->xstream) { (void)hipStreamSynchronize(c->xstream); (void)hipStreamDestroy(c->xstream); }
   if (c->xdep) (void)hipEventDestroy(c->xdep);
@@ -1148,6 +1182,16 @@ extern "C" hm_status hm_get_counter(hm_ctx *c, const char *name, uint64_t *value
     HM_HIP(c, hipStreamSynchronize(c->stream));
     unsigned v = 0;
     HM_HIP(c, hipMemcpy(&v, &c->ntt_ws->stats[0], sizeof v, hipMemcpyDeviceToHost));
+    *value = v;
+    return check_device_error(c);
+  }
+  if (!strcmp(name, "encode_overflow")) {   // 1: a coefficient of an hm_encode since the last reading exceeded (q_src - 1) / 2; cleared by reading
+    *value = 0;
+    if (!c->d_slot_flag) return HM_OK;
+    HM_HIP(c, hipStreamSynchronize(c->stream));
+    uint32_t v = 0;
+    HM_HIP(c, hipMemcpy(&v, c->d_slot_flag, sizeof v, hipMemcpyDeviceToHost));
+    if (v) HM_HIP(c, hipMemset(c->d_slot_flag, 0, sizeof v));
     *value = v;
     return check_device_error(c);
   }
@@ -1612,6 +1656,135 @@ extern "C" hm_status hm_ntt_lift(hm_ctx *c, const hm_ntt_lift_desc *l) {
   NttFused f;
   f.liftSrcMods = l->src_mod_ids;
   return ntt_common(c, "hm_ntt_lift", d->in, d->in_limbs, d->out, d->out_limbs, d->mod_ids, d->n, 0, nullptr, f);
+}
+
+// ---- hm_encode / hm_decode: slot vectors <-> plaintexts (hm_slot_core.h) ----
+// the context's tables of the slot transform and `vecs` vectors of hand-off; allocates on the first call and when a call brings more vectors than
+// any before it, which a capturing stream cannot do.  A hand-off that is outgrown while a captured graph lives (its k_slot_fft nodes keep the
+// address) is retired, not freed: it goes when no graph lives any more, or with the context
+static hm_status slot_upload(hm_ctx *c, const void *src, size_t bytes, void **member) {
+  void *p = nullptr;
+  HM_HIP(c, hipMalloc(&p, bytes));
+  const hipError_t e = src ? hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) : hipMemset(p, 0, bytes);
+  if (e != hipSuccess) { (void)hipFree(p); return fail(c, HM_ERR_HIP, "slot tables: %s", hipGetErrorString(e)); }
+  *member = p;
+  return HM_OK;
+}
+static hm_status slot_prepare(hm_ctx *c, const char *what, size_t vecs) {
+  static_assert(HM_SLOT_MIN_LOGN == 12 && HM_SLOT_MAX_LOGN == 16, "hm_cap_slot_transform (hm_caps.h) names the rings the tile split serves");
+  if (!hm_cap_slot_transform(c->P.logN)) return fail(c, HM_ERR_UNSUPPORTED, "%s: no slot transform at N = 2^%u", what, c->P.logN);
+  const uint32_t logn = c->P.logN - 1;
+  const bool tables = c->d_slot_roots && c->d_slot_rot && c->d_slot_flag;
+  if (tables && vecs <= c->slot_tmp_vecs) return HM_OK;
+  if (c->tables.capturing) return fail(c, HM_ERR_UNSUPPORTED, "%s: the slot tables are missing while the stream is capturing: run the call once before hm_capture_begin", what);
+  HM_HIP(c, hipSetDevice(c->device));
+  hm_status st;
+  if (!tables) {   // each pointer is set only once its table is filled: a failure half way leaks nothing and the next call makes the rest
+    std::vector<HmC> roots;
+    std::vector<uint32_t> rot;
+    hm_slot_tables(c->P.logN, roots, rot);
+    if (!c->d_slot_rot && (st = slot_upload(c, rot.data(), sizeof(uint32_t) * rot.size(), reinterpret_cast<void **>(&c->d_slot_rot)))) return st;
+    if (!c->d_slot_flag && (st = slot_upload(c, nullptr, sizeof(uint32_t), reinterpret_cast<void **>(&c->d_slot_flag)))) return st;
+    if (!c->d_slot_roots && (st = slot_upload(c, roots.data(), sizeof(HmC) * roots.size(), reinterpret_cast<void **>(&c->d_slot_roots)))) return st;
+  }
+  if (vecs > c->slot_tmp_vecs) {
+    HM_HIP(c, hipStreamSynchronize(c->stream));   // launches in flight read the old hand-off
+    if (c->d_slot_tmp) c->slot_tmp_retired.push_back(c->d_slot_tmp);
+    c->d_slot_tmp = nullptr; c->slot_tmp_vecs = 0;
+    if (!c->tables.pinned()) {
+      for (HmC *p : c->slot_tmp_retired) (void)hipFree(p);
+      c->slot_tmp_retired.clear();
+    }
+    HM_HIP(c, hipMalloc(&c->d_slot_tmp, (sizeof(HmC) * vecs) << logn));
+    c->slot_tmp_vecs = vecs;
+  }
+  return HM_OK;
+}
+// what both calls check of their scale, their slot buffer and their scratch limb-polys
+static hm_status slot_check(hm_ctx *c, const char *what, const double *slots, double scale, const uint64_t *work, const uint32_t *work_limbs, uint32_t n_vec) {
+  if (!slots || !work) return fail(c, HM_ERR_ARG, "%s: null buffer", what);
+  if (!(scale > 0) || !std::isfinite(scale)) return fail(c, HM_ERR_ARG, "%s: scale must be finite and positive", what);
+  if ((reinterpret_cast<uintptr_t>(slots) & 15u) || (reinterpret_cast<uintptr_t>(work) & 15u)) return fail(c, HM_ERR_ARG, "%s: slots and work must be 16-byte aligned", what);
+  return check_limbs(c, what, work_limbs, n_vec);
+}
+static HmSlotArgs slot_args(hm_ctx *c, uint32_t mod_id, const uint32_t *dlimbs, uint64_t *coef, double mul) {
+  HmSlotArgs a{};
+  a.roots = c->d_slot_roots; a.rot = c->d_slot_rot; a.flag = c->d_slot_flag;
+  a.coef = coef; a.limbs = dlimbs; a.mul = mul;
+  a.q = c->P.mod[mod_id]; a.half = (a.q - 1) / 2;
+  a.logn = c->P.logN - 1; a.log1 = hm_slot_log1(a.logn); a.log2 = hm_slot_log2(a.logn); a.tiles = (1u << a.logn) >> HM_SLOT_TL;
+  return a;
+}
+static hm_status slot_limb_table(hm_ctx *c, const uint32_t *limbs, uint32_t n_vec, const uint32_t **out) {
+  std::vector<uint32_t> l(n_vec);
+  for (uint32_t v = 0; v < n_vec; ++v) l[v] = limb_at(limbs, v);
+  const void *p = nullptr;
+  const hm_status st = device_table(c, l.data(), sizeof(uint32_t) * n_vec, &p);
+  *out = static_cast<const uint32_t *>(p);
+  return st;
+}
+
+extern "C" hm_status hm_encode(hm_ctx *c, const double *slots, uint32_t n_vec, double scale, uint64_t *work, const uint32_t *work_limbs,
+                               uint32_t src_mod_id, uint64_t *out, const uint32_t *out_limbs, const uint32_t *mod_ids, uint32_t n_mod) {
+  if (!c) return HM_ERR_ARG;
+  if (n_vec == 0) return HM_OK;
+  HM_TABLE_CALL(c);
+  hm_status st;
+  if ((st = slot_check(c, "hm_encode", slots, scale, work, work_limbs, n_vec)) || (st = check_mods(c, "hm_encode", &src_mod_id, 1))) return st;
+  if (n_mod && !out) return fail(c, HM_ERR_ARG, "hm_encode: null buffer");
+  const uint64_t total = (uint64_t)n_vec * n_mod;
+  if (total > 0xFFFFFFFFull) return fail(c, HM_ERR_ARG, "hm_encode: n_vec * n_mod exceeds 2^32");
+  if (n_mod) {
+    if ((st = check_mods(c, "hm_encode", mod_ids, n_mod)) || (st = check_limbs(c, "hm_encode", out_limbs, (uint32_t)total))) return st;
+    const int64_t g = hm_first_overlap(out, out_limbs, (uint32_t)total, work, work_limbs, n_vec, c->P.N, [](uint32_t) { return true; });
+    if (g >= 0) return fail(c, HM_ERR_ARG, "hm_encode: the output overlaps work of vector [%u]", (uint32_t)g);
+  }
+  const double mul = scale * (2.0 / (double)c->P.N);
+  if (!std::isfinite(mul)) return fail(c, HM_ERR_ARG, "hm_encode: scale must be finite and positive");
+  if ((st = slot_prepare(c, "hm_encode", n_vec))) return st;
+  const uint32_t *dlimbs = nullptr;
+  if ((st = slot_limb_table(c, work_limbs, n_vec, &dlimbs))) return st;
+  HM_HIP(c, hipSetDevice(c->device));
+  HmSlotArgs a = slot_args(c, src_mod_id, dlimbs, work, mul);
+  a.zin = reinterpret_cast<const HmC *>(slots); a.zout = c->d_slot_tmp;
+  hipLaunchKernelGGL(k_slot_fft<true>, dim3(n_vec * a.tiles), dim3(HM_SLOT_THREADS), 0, c->stream, a, 1u);
+  a.zin = c->d_slot_tmp; a.zout = nullptr;
+  hipLaunchKernelGGL(k_slot_fft<true>, dim3(n_vec * a.tiles), dim3(HM_SLOT_THREADS), 0, c->stream, a, 0u);
+  HM_HIP(c, hipGetLastError());
+  if (!n_mod) return HM_OK;
+  // every (vector, modulus) pair in ONE lifted forward transform: the stored residues of q_src are centred into each modulus while the first pass loads
+  std::vector<uint32_t> in_l(total), mods(total), src(total, src_mod_id);
+  for (uint32_t v = 0; v < n_vec; ++v)
+    for (uint32_t m = 0; m < n_mod; ++m) { in_l[(size_t)v * n_mod + m] = limb_at(work_limbs, v); mods[(size_t)v * n_mod + m] = mod_ids[m]; }
+  NttFused f;
+  f.liftSrcMods = src.data();
+  return ntt_common(c, "hm_encode", work, in_l.data(), out, out_limbs, mods.data(), (uint32_t)total, 0, nullptr, f);
+}
+
+extern "C" hm_status hm_decode(hm_ctx *c, const uint64_t *in, const uint32_t *in_limbs, uint32_t mod_id, double scale, uint64_t *work,
+                               const uint32_t *work_limbs, double *slots, uint32_t n_vec) {
+  if (!c) return HM_ERR_ARG;
+  if (n_vec == 0) return HM_OK;
+  HM_TABLE_CALL(c);
+  hm_status st;
+  if (!in) return fail(c, HM_ERR_ARG, "hm_decode: null buffer");
+  if ((st = slot_check(c, "hm_decode", slots, scale, work, work_limbs, n_vec)) || (st = check_mods(c, "hm_decode", &mod_id, 1)) ||
+      (st = check_limbs(c, "hm_decode", in_limbs, n_vec)))
+    return st;
+  const int64_t g = hm_first_overlap(work, work_limbs, n_vec, in, in_limbs, n_vec, c->P.N, [](uint32_t) { return true; });
+  if (g >= 0) return fail(c, HM_ERR_ARG, "hm_decode: work overlaps the input of vector [%u]", (uint32_t)g);
+  if ((st = slot_prepare(c, "hm_decode", 0))) return st;
+  const uint32_t *dlimbs = nullptr;
+  if ((st = slot_limb_table(c, work_limbs, n_vec, &dlimbs))) return st;
+  const std::vector<uint32_t> mods(n_vec, mod_id);
+  if ((st = ntt_common(c, "hm_decode", in, in_limbs, work, work_limbs, mods.data(), n_vec, 1, nullptr, NttFused{}))) return st;
+  HmSlotArgs a = slot_args(c, mod_id, dlimbs, work, 1.0 / scale);
+  a.zout = reinterpret_cast<HmC *>(slots);
+  hipLaunchKernelGGL(k_slot_fft<false>, dim3(n_vec * a.tiles), dim3(HM_SLOT_THREADS), 0, c->stream, a, 0u);
+  a.zin = a.zout;
+  hipLaunchKernelGGL(k_slot_fft<false>, dim3(n_vec * a.tiles), dim3(HM_SLOT_THREADS), 0, c->stream, a, 1u);
+  HM_HIP(c, hipGetLastError());
+  return HM_OK;
 }
 
 extern "C" hm_status hm_ntt_sub_scale(hm_ctx *c, const uint64_t *in, const uint32_t *in_limbs, const uint64_t *minuend,

@@ -32,6 +32,8 @@ static inline HmCaps hm_caps(uint32_t logN) {
   default: return HmCaps{0, 0, 0, 0, 0, 0};
   }
 }
+// the slot transform (hm_encode / hm_decode, hm_slot_core.h): n = N / 2 = 2^12 .. 2^16 splits into two passes of at most 2^8 over tiles of 2^11
+static inline uint32_t hm_cap_slot_transform(uint32_t logN) { return logN >= 13 && logN <= 17; }
 // 0 = found
 static inline int hm_cap_by_name(uint32_t logN, const char *name, uint64_t *value) {
   const HmCaps c = hm_caps(logN);
@@ -41,6 +43,7 @@ static inline int hm_cap_by_name(uint32_t logN, const char *name, uint64_t *valu
   if (!strcmp(name, "cap_bconv_col_pref_in")) { *value = c.bcol_pref_in; return 0; }
   if (!strcmp(name, "cap_ip_inverse_out")) { *value = c.ip_inverse_out; return 0; }
   if (!strcmp(name, "cap_col_slices")) { *value = c.col_slices; return 0; }
+  if (!strcmp(name, "cap_slot_transform")) { *value = hm_cap_slot_transform(logN); return 0; }
   // the default limit of the one-launch transform in limb-polys of THIS ring (what decides is the number of workgroups: a smaller ring admits more)
   if (!strcmp(name, "cap_ntt_fused_small")) {
     const uint64_t v = logN <= 16 ? (uint64_t)HM_NTT_FUSED_SMALL << (16 - logN) : 0;

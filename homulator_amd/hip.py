@@ -28,7 +28,7 @@ SYMBOLS = [
     "hm_inner_product_hoisted", "hm_inner_product_lintrans", "hm_inner_product_rotsum", "hm_inner_product_lintrans_multi",
     "hm_tensor_dot", "hm_inner_product_lintrans_id", "hm_inner_product_rotsum_init", "hm_ntt_mix_sub_scale_mul", "hm_ntt_mul",
     "hm_ntt_lift", "hm_tensor_square", "hm_lincomb", "hm_tensor_muladd", "hm_reim_split", "hm_clincomb", "hm_plincomb",
-    "hm_tensor_dotadd", "hm_lincomb_multi",
+    "hm_tensor_dotadd", "hm_lincomb_multi", "hm_encode", "hm_decode",
 ]
 
 
@@ -160,6 +160,8 @@ def load():
     L.hm_ntt_mix_sub_scale_mul.argtypes = [vp, C.POINTER(hm_ntt_fused_mul_desc)]
     L.hm_ntt_mul.argtypes = [vp, C.POINTER(hm_ntt_mul_desc)]
     L.hm_ntt_lift.argtypes = [vp, C.POINTER(hm_ntt_lift_desc)]
+    L.hm_encode.argtypes = [vp, vp, u32, C.c_double, vp, vp, u32, vp, vp, vp, u32]
+    L.hm_decode.argtypes = [vp, vp, vp, u32, C.c_double, vp, vp, vp, u32]
     L.hm_tensor.argtypes = [vp] + [vp] * 15 + [u32]
     L.hm_tensor_dot.argtypes = [vp] + [vp] * 15 + [u32, u32]
     L.hm_tensor_square.argtypes = [vp] + [vp] * 11 + [u32, vp, vp]
@@ -212,6 +214,23 @@ def _u32(a):
         return None, None
     arr = np.ascontiguousarray(np.asarray(a, dtype=np.uint32))
     return arr, arr.ctypes.data_as(C.c_void_p)
+
+
+def _dev_ptr(x):
+    """the device address of a DeviceBuf (`.ptr`) or of anything that has `data_ptr()` (a torch tensor on the GPU)"""
+    return x.ptr if hasattr(x, "ptr") else x.data_ptr()
+
+
+def _on_device(x):
+    """a DeviceBuf, or an object with data_ptr(); one that says it is not on the GPU (a CPU torch tensor: is_cuda False) is refused, since its host
+    address would reach the kernels"""
+    if hasattr(x, "ptr"):
+        return True
+    if not hasattr(x, "data_ptr"):
+        return False
+    if not getattr(x, "is_cuda", True):
+        raise ValueError("a tensor with data_ptr() must be on the GPU (move it there, or pass a numpy array)")
+    return True
 
 
 def _u64(a):
@@ -588,6 +607,103 @@ class Context:
                            C.cast(descs, C.c_void_p) if conv else None, len(conv) if conv else 0,
                            None if inv is None else inv.ctypes.data_as(C.c_void_p), int(x_galois))
         self._ck(self.L.hm_ntt_inner_product(self.h, C.byref(d)))
+
+    # ---- slot vectors <-> plaintexts (hm_encode / hm_decode)
+    def largest_modulus(self):
+        return max(range(len(self.moduli)), key=lambda m: self.moduli[m])
+
+    def encode(self, z, scale, mod_ids, src_mod=None, n_vec=None, work=None, work_limbs=None, out=None, out_limbs=None):
+        """The plaintexts of slot vectors z at scale `scale` on the moduli mod_ids (hm_encode).
+        z on the host: complex128, [n] or [n_vec][n] with n = N / 2; returns uint64 [n_vec][len(mod_ids)][N] in evaluation form, or, with
+        mod_ids empty, the coefficient-form residues of the source modulus, [n_vec][N].
+        z on the device (a DeviceBuf, or anything with data_ptr(): a contiguous complex128 torch tensor; whoever filled it has synchronised):
+        n_vec vectors (default: what z.numel() holds, else 1); returns the DeviceBuf that holds the result, limb-polys in the same order
+        (`out`, or `work` when mod_ids is empty).  With `work` (and `out`) given the call only enqueues on the context's stream and can be
+        captured; a `work` left to default is a fresh buffer freed behind the call, which synchronises and cannot happen inside a capture.
+        src_mod: the modulus the coefficients are rounded into (default: the largest of the chain); work / out: buffers of the caller's, with their
+        limb lists, instead of fresh ones."""
+        n = self.N // 2
+        mod_ids = [int(m) for m in mod_ids]
+        src_mod = self.largest_modulus() if src_mod is None else int(src_mod)
+        host = not _on_device(z)
+        tmp = []
+        if host:
+            a = np.ascontiguousarray(np.asarray(z, dtype=np.complex128)).reshape(-1, n)
+            n_vec = a.shape[0]
+            zbuf = self.alloc(max(1, n_vec))
+            tmp.append(zbuf)
+            if n_vec:
+                self._ck(self.L.hm_memcpy_h2d(self.h, zbuf.ptr, a.ctypes.data_as(C.c_void_p), a.nbytes))
+            zptr = zbuf.ptr
+        else:
+            if n_vec is None:
+                n_vec = z.numel() // n if hasattr(z, "numel") else 1
+            zptr = _dev_ptr(z)
+        if work is None:
+            work = self.alloc(max(1, n_vec))
+            if host or mod_ids:
+                tmp.append(work)
+        if out is None and mod_ids:
+            out = self.alloc(max(1, n_vec * len(mod_ids)))
+            if host:
+                tmp.append(out)
+        k1, pw = _u32(work_limbs)
+        k2, po = _u32(out_limbs)
+        k3, pm = _u32(mod_ids)
+        try:
+            self._ck(self.L.hm_encode(self.h, zptr, n_vec, float(scale), _dev_ptr(work), pw, src_mod, None if out is None else _dev_ptr(out), po, pm,
+                                      len(mod_ids)))
+            if not host:
+                return out if mod_ids else work
+            res, rows = (out, n_vec * len(mod_ids)) if mod_ids else (work, n_vec)
+            limbs = (out_limbs if mod_ids else work_limbs)
+            got = np.empty((rows, self.N), dtype=np.uint64)
+            for r in range(rows):
+                self._ck(self.L.hm_memcpy_d2h(self.h, got[r].ctypes.data_as(C.c_void_p), _dev_ptr(res) + 8 * self.N * (r if limbs is None else int(limbs[r])),
+                                              8 * self.N))
+            return got.reshape(n_vec, len(mod_ids), self.N) if mod_ids else got
+        finally:
+            for b in tmp:
+                b.free()
+
+    def decode(self, buf, limbs, mod_id, scale, work=None, work_limbs=None, out=None):
+        """The slots of evaluation-form limb-polys modulo q_(mod_id) at scale `scale` (hm_decode), one vector per entry of `limbs` (None: the rows
+        of buf in order).
+        buf on the host: uint64 [rows][N]; returns complex128 [n_vec][N / 2].
+        buf on the device (a DeviceBuf or anything with data_ptr()): `limbs` must be given; returns `out` (anything on the device with room for
+        n_vec x N / 2 complex128, 16-byte aligned; default: a fresh DeviceBuf of n_vec limb-polys, vector v in limb-poly v as (re, im) doubles).
+        With `work` given the call only enqueues and can be captured; a default `work` is freed behind the call, which synchronises."""
+        n = self.N // 2
+        host = not _on_device(buf)
+        tmp = []
+        if host:
+            a = np.ascontiguousarray(buf, dtype=np.uint64).reshape(-1, self.N)
+            n_vec = a.shape[0] if limbs is None else len(limbs)
+            src = self.from_host(a) if a.shape[0] else self.alloc(1)
+            tmp.append(src)
+        else:
+            n_vec = len(limbs)
+            src = buf
+        if work is None:
+            work = self.alloc(max(1, n_vec))
+            tmp.append(work)
+        if out is None:
+            out = self.alloc(max(1, n_vec))
+            if host:
+                tmp.append(out)
+        k1, pi = _u32(limbs)
+        k2, pw = _u32(work_limbs)
+        try:
+            self._ck(self.L.hm_decode(self.h, _dev_ptr(src), pi, int(mod_id), float(scale), _dev_ptr(work), pw, _dev_ptr(out), n_vec))
+            if not host:
+                return out
+            got = np.empty((n_vec, n), dtype=np.complex128)
+            if n_vec:
+                self._ck(self.L.hm_memcpy_d2h(self.h, got.ctypes.data_as(C.c_void_p), _dev_ptr(out), got.nbytes))
+            return got
+        finally:
+            for b in tmp:
+                b.free()
 
     def automorph(self, src, dst, n, galois, in_limbs=None, out_limbs=None):
         k1, pi = _u32(in_limbs)

@@ -34,6 +34,7 @@ def load():
         L.hh_op_execute.argtypes = [vp, u32, C.POINTER(C.c_double)]
         L.hh_op_write_buffer.argtypes = [vp, C.c_char_p, u32, vp]
         L.hh_op_set_constants.argtypes = [vp, C.c_char_p, vp, u32]
+        L.hh_op_encode_plaintext.argtypes = [vp, C.c_char_p, vp, u32, C.c_double, u32]
         L.hh_op_sim_run.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
         L.hh_op_sim_stats.argtypes = [vp, C.c_char_p, u32]
         L.hh_op_enqueue.argtypes = [vp, u32]
@@ -145,6 +146,12 @@ class Op:
         if a.shape != (n.value, self.N):
             raise HostError(f"{name}: expected shape {(n.value, self.N)}, got {a.shape}")
         self._ck(self.L.hh_op_write_buffer(self.h, name.encode(), copy, a.ctypes.data_as(C.c_void_p)))
+
+    def encode_plaintext(self, name, z, scale, copy=0):
+        """fill the input plaintext `name` (pt; pt<r>, pt0; pt<t>) with the encoding of the N / 2 complex slots z at scale `scale`: every limb of the
+        buffer under its own modulus, encoded on the device (hh_op_encode_plaintext); errors begin with `encode_plaintext:`"""
+        a = np.ascontiguousarray(np.asarray(z, dtype=np.complex128).reshape(-1))
+        self._ck(self.L.hh_op_encode_plaintext(self.h, name.encode(), a.ctypes.data_as(C.c_void_p), len(a), float(scale), int(copy)))
 
     def set_constants(self, name, values):
         """replace the op's per-limb constants `name` (hsquare: "scale", "const"; hlincomb: "scale1" .. "scale<T>", "const"; hmuladd: "scale",

@@ -98,6 +98,12 @@ public:
   double timedRun(uint32_t iters);      // ns per iteration, device time
   bool readLimbs(const std::vector<AddrType> &addrs, uint64_t *host, uint32_t copy = 0);  // download limbs (N words each) of op `copy` of the batch
   bool writeLimbs(const std::vector<AddrType> &addrs, const uint64_t *host, uint32_t copy = 0);  // upload limbs (real ciphertexts / keys); shared key limbs live in copy 0
+  // a slot vector (N / 2 complex values as (re, im) doubles, on the host) into limb-polys `addrs` of op `copy`, evaluation form under moduli
+  // `mods`, at scale `scale`: hm_encode with the largest modulus of the chain as its source modulus.  Its scratch (two limb-polys: the slots and
+  // hm_encode's `work`) is an allocation of this Arch's own beside the pool, kept until the Arch goes, so the op's address plan is untouched.
+  // After prepare(); synchronises.  Refusals (backend, world, copy, overflow) are exceptions whose text begins "encode_plaintext:".  An overflow
+  // is found after the call: the limb-polys then hold the encoding with 0 in place of every coefficient beyond half the source modulus
+  void encodeLimbs(const std::vector<AddrType> &addrs, const std::vector<uint32_t> &mods, const double *slots, double scale, uint32_t copy);
   // asynchronous helpers on the op's stream (tests of the chain ordering, streaming callers):
   void refill(const std::vector<AddrType> &addrs, uint64_t seed);              // new synthetic input data (all ops of the batch)
   void snapshot(const std::vector<AddrType> &addrs, uint32_t slot);             // device-side copy of the limbs as they are NOW in stream order
@@ -153,6 +159,7 @@ private:
   void *graph = nullptr;  // hm_graph*: the whole plan captured once, replayed by run()
   std::vector<void *> sliceBuffers;
   std::map<uint32_t, std::pair<uint64_t *, size_t>> snapshots;  // slot -> (device buffer, limbs)
+  uint64_t *encodeScratch = nullptr;   // encodeLimbs: two limb-polys of its own (hm_malloc), the slot vector and hm_encode's `work`
   hm_ctx *ctx = nullptr;
   void *hostParams = nullptr;  // hm::Params: moduli / roots / conversion constants on the host (both backends)
   uint64_t *pool = nullptr;  // all limb-polys, [limb][N]

@@ -14,6 +14,7 @@
 #include "InsGen.h"
 
 #include <array>
+#include <complex>
 #include <deque>
 
 // the stages of one builder: (stage key, [level] -> instruction group) in the order they were emitted, with upstream's lookup by key
@@ -129,6 +130,7 @@ protected:
   uint64_t seed;
   std::map<std::string, std::vector<AddrType>> namedInputs;   // ct1.c0, ct1.c1, ... for readBuffer
   std::map<std::string, std::vector<AddrType>> namedOutputs;  // out.c0, out.c1
+  std::map<std::string, std::vector<uint32_t>> plaintextMods;  // the input plaintexts by name (pt, pt<r>, pt0, ...): the modulus of every limb, for encodePlaintext
 
   OperationBase(const std::string &op, const std::string &labelName, Config *cfg, Arch *_arch, uint32_t maxLevel, uint32_t curLevel, uint32_t alpha);
   // every op's preamble: `ciphertexts` input ciphertexts ct1, ct2 (synthetic streams seed, seed + 2000) and, if asked, the plaintext pt
@@ -195,6 +197,12 @@ public:
   std::vector<AddrType> bufferAddrs(const std::string &name) const;  // named buffer (Malloc name, input or output alias)
   bool readBuffer(const std::string &name, uint64_t *host, uint32_t copy = 0);  // copy: op of the batch (config key `batch`)
   bool writeBuffer(const std::string &name, const uint64_t *host, uint32_t copy = 0);  // real data for an input / key buffer ([limbs][N], fully reduced)
+  // fills the input plaintext `name` (pt of PMULT / PADD; pt<r>, pt0 of HLINTRANS / HBSGS; pt<t>, pt0 of HPLINCOMB) of op `copy` with the encoding
+  // of N / 2 slots at scale `scale`: every limb the buffer has (level, or level + alpha on the extended basis) under its own modulus, encoded on
+  // the device (hm_encode).  Prepares the op if needed; synchronises.  Refused with a message beginning "encode_plaintext:"
+  // for an unknown name, a name that is no plaintext, a wrong length, backend != hip, world > 1, or a coefficient beyond half the largest modulus
+  // (found after the encode: the buffer then holds the encoding with 0 in place of every such coefficient)
+  void encodePlaintext(const std::string &name, const std::vector<std::complex<double>> &slots, double scale, uint32_t copy = 0);
   unsigned long long totalInstructions();
   // replaces the per-limb constants `name` of the op (HSQUARE: "scale", "const"; HLINCOMB: "scale1" .. "scale<T>", "const"; HMLINCOMB: "scale<m>_<t>", "const<m>"; HMULADD: "scale", "addscale1" .. "addscale<A>", "const"; HDOTADD: "scale1" .. "scale<T>", "addscale1" .. "addscale<A>", "const") by n = level residues, values[j] reduced mod q_j; before prepare() only.
   // Refused, by op and name: after prepare(), n != level, an unreduced value (or a zero where the constant multiplies), a name whose config key is 0

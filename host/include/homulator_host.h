@@ -42,6 +42,11 @@ int hh_op_read_buffer_copy(hh_op *op, const char *name, uint32_t copy, uint64_t 
 /* real data in: overwrite a named input / key buffer ([n_limbs][N] words, fully reduced, evaluation form) of op `copy` of the batch; the
  * evaluation-key limbs ("IP_Key<k>_<j>", shared by the batch) live in copy 0.  Prepares the op if needed; synchronises. */
 int hh_op_write_buffer(hh_op *op, const char *name, uint32_t copy, const uint64_t *host);
+/* OperationBase::encodePlaintext: the input plaintext `name` of op `copy` becomes the encoding of n_slots = N / 2 slots ((re, im) doubles on the host)
+ * at scale `scale`, every limb under its own modulus, encoded on the device (hm_encode).  Prepares the op if needed; synchronises.  Errors begin
+ * "encode_plaintext:" (unknown name, no plaintext, wrong length, backend != hip, world > 1, a coefficient beyond half the largest modulus: that
+ * one is found after the encode, and the buffer then holds the encoding with 0 in place of every such coefficient). */
+int hh_op_encode_plaintext(hh_op *op, const char *name, const double *slots, uint32_t n_slots, double scale, uint32_t copy);
 /* replaces the per-limb constants `name` of the op (hsquare: "scale", the s_j in [1, q_j); "const", the k_j in [0, q_j); hlincomb: "scale1" .. "scale<T>",
  * the s_{t,j} in [0, q_j), and "const"; hmuladd: "scale", "addscale1" .. "addscale<A>", the u_{t,j} in [0, q_j), and "const"; hclincomb:
  * "scale1" .. "scale<T>" and "scale_im1" .. "scale_im<T>", the a_{t,j} and b_{t,j} in [0, q_j), and "const"; hdotadd: "scale1" .. "scale<T>", the s_{t,j} in [1, q_j), "addscale1" .. "addscale<A>" and

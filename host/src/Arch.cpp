@@ -237,6 +237,7 @@ Arch::~Arch() {
     for (void *p : sliceBuffers) hm_free(ctx, p);
   if (ctx)
     for (auto &kv : snapshots) hm_free(ctx, kv.second.first);
+  if (ctx && encodeScratch) hm_free(ctx, encodeScratch);
   if (ctx) {
     if (pool) hm_free(ctx, pool);
     hm_destroy(ctx);
@@ -1900,6 +1901,35 @@ bool Arch::writeLimbs(const std::vector<AddrType> &addrs, const uint64_t *host, 
   for (size_t i = 0; i < addrs.size(); ++i)
     if (hm_memcpy_h2d(ctx, pool + ((size_t)limbOf(addrs[i]) + (size_t)copy * limbIndex.size()) * n, host + i * n, (size_t)n * 8) != HM_OK) return false;
   return true;
+}
+void Arch::encodeLimbs(const std::vector<AddrType> &addrs, const std::vector<uint32_t> &mods, const double *slots, double scale, uint32_t copy) {
+  if (world_ > 1) throw std::runtime_error("encode_plaintext: not on a sharded plan (world > 1)");
+  if (backendKind != BACKEND_HIP) throw std::runtime_error("encode_plaintext: only the hip backend holds values");
+  if (!prepared) prepare();
+  if (!pool || copy >= batch_) throw std::runtime_error("encode_plaintext: copy " + std::to_string(copy) + " is not an op of the batch");
+  auto ck = [&](hm_status st, const char *what) { if (st != HM_OK) throw std::runtime_error(std::string("encode_plaintext: ") + what + ": " + hm_last_error(ctx)); };
+  if (!encodeScratch) {
+    void *p = nullptr;
+    ck(hm_malloc(ctx, 2 * (size_t)n * 8, &p), "hm_malloc");
+    encodeScratch = static_cast<uint64_t *>(p);
+  }
+  const hm::Params &hp = hostP(hostParams);
+  uint32_t src = 0;
+  for (uint32_t m = 1; m < hp.mod.size(); ++m)
+    if (hp.mod[m] > hp.mod[src]) src = m;
+  std::vector<uint32_t> limbs;
+  for (AddrType a : addrs) limbs.push_back(limbOf(a));
+  uint64_t *copyPool = pool + (size_t)copy * limbIndex.size() * n;   // the copy's own base, as writeLimbs: limb numbers stay those of one op
+  sync();
+  uint64_t stale = 0;
+  ck(hm_get_counter(ctx, "encode_overflow", &stale), "hm_get_counter");   // an earlier caller's flag is not this vector's
+  ck(hm_memcpy_h2d(ctx, encodeScratch, slots, (size_t)n * 8), "hm_memcpy_h2d");
+  const uint32_t workLimb = 1;
+  ck(hm_encode(ctx, reinterpret_cast<const double *>(encodeScratch), 1, scale, encodeScratch, &workLimb, src, copyPool, limbs.data(), mods.data(), (uint32_t)mods.size()),
+     "hm_encode");
+  uint64_t over = 0;
+  ck(hm_get_counter(ctx, "encode_overflow", &over), "hm_get_counter");
+  if (over) throw std::runtime_error("encode_plaintext: a coefficient exceeds half the largest modulus of the chain at this scale");
 }
 bool Arch::readLimbs(const std::vector<AddrType> &addrs, uint64_t *host, uint32_t copy) {
   if (backendKind != BACKEND_HIP || !pool || copy >= batch_) return false;

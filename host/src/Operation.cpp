@@ -392,6 +392,7 @@ void OperationBase::makeInputs(uint32_t ciphertexts, bool plaintext, uint32_t ex
     arch->registerLimbs(ptx->getC0Addr());
     arch->addInputFill(InputFill{ptx->getC0Addr(), range(0, level_), seed + 4000});
     namedInputs["pt"] = ptx->getC0Addr();
+    plaintextMods["pt"] = range(0, level_);
   }
   std::vector<uint32_t> extMods = range(0, level_);
   for (uint32_t p : range(maxLevel_, alpha_)) extMods.push_back(p);
@@ -401,6 +402,7 @@ void OperationBase::makeInputs(uint32_t ciphertexts, bool plaintext, uint32_t ex
     arch->registerLimbs(pt);
     arch->addInputFill(InputFill{pt, extMods, seed + 4000 + 100000ull * r});
     namedInputs["pt" + S(r)] = pt;
+    plaintextMods["pt" + S(r)] = extMods;
   }
   for (const auto &ns : namedExt) {   // behind the numbered ones: an op without them keeps its address plan
     extPtx.emplace_back(level_ + alpha_, N, Datapool, batchSize);
@@ -408,6 +410,7 @@ void OperationBase::makeInputs(uint32_t ciphertexts, bool plaintext, uint32_t ex
     arch->registerLimbs(pt);
     arch->addInputFill(InputFill{pt, extMods, seed + ns.second});
     namedInputs[ns.first] = pt;
+    plaintextMods[ns.first] = extMods;
   }
   for (const auto &ns : namedLevel) {   // behind everything else: an op without them keeps its address plan
     levelPtx.emplace_back(level_, N, Datapool, batchSize);
@@ -415,6 +418,7 @@ void OperationBase::makeInputs(uint32_t ciphertexts, bool plaintext, uint32_t ex
     arch->registerLimbs(pt);
     arch->addInputFill(InputFill{pt, range(0, level_), seed + ns.second});
     namedInputs[ns.first] = pt;
+    plaintextMods[ns.first] = range(0, level_);
   }
   addrManager.reset(new AddrManage(Datapool.back() + 1, batchSize));
   addrManager->setGlobalDatapPoll(&Datapool);
@@ -602,6 +606,16 @@ std::vector<std::string> OperationBase::bufferNames() const {
 }
 bool OperationBase::readBuffer(const std::string &name, uint64_t *host, uint32_t copy) { return arch->readLimbs(bufferAddrs(name), host, copy); }
 bool OperationBase::writeBuffer(const std::string &name, const uint64_t *host, uint32_t copy) { prepare(); return arch->writeLimbs(bufferAddrs(name), host, copy); }
+void OperationBase::encodePlaintext(const std::string &name, const std::vector<std::complex<double>> &slots, double scale, uint32_t copy) {
+  auto pt = plaintextMods.find(name);
+  if (pt == plaintextMods.end()) {
+    const bool known = namedInputs.count(name) || namedOutputs.count(name) || [&] { for (auto &n : addrManager->names()) if (n == name) return true; return false; }();
+    throw std::runtime_error("encode_plaintext: " + opName + (known ? " buffer " + name + " is no plaintext input" : " has no buffer " + name));
+  }
+  if (slots.size() != N / 2) throw std::runtime_error("encode_plaintext: " + std::to_string(slots.size()) + " slots given, the ring has " + std::to_string(N / 2));
+  static_assert(sizeof(std::complex<double>) == 2 * sizeof(double), "std::complex<double> is (re, im)");
+  arch->encodeLimbs(namedInputs.at(name), pt->second, reinterpret_cast<const double *>(slots.data()), scale, copy);
+}
 unsigned long long OperationBase::totalInstructions() { prepare(); return driver.getTotalIns(); }
 void OperationBase::bindInput(const std::string &input, OperationBase *producer, const std::string &output) {
   for (const char *part : {".c0", ".c1"}) {

@@ -115,6 +115,11 @@ int hh_op_read_buffer_copy(hh_op *h, const char *name, uint32_t copy, uint64_t *
 int hh_op_write_buffer(hh_op *h, const char *name, uint32_t copy, const uint64_t *host) {
   HH_TRY(if (!h->op->writeBuffer(name, host, copy)) throw std::runtime_error("buffer not writable (not the hip backend, or copy >= batch)"))
 }
+int hh_op_encode_plaintext(hh_op *h, const char *name, const double *slots, uint32_t n_slots, double scale, uint32_t copy) {
+  HH_TRY(if (!name || !slots) throw std::runtime_error("encode_plaintext: null argument");
+         std::vector<std::complex<double>> z(n_slots); for (uint32_t j = 0; j < n_slots; ++j) z[j] = std::complex<double>(slots[2 * j], slots[2 * j + 1]);
+         h->op->encodePlaintext(name, z, scale, copy))
+}
 int hh_op_set_constants(hh_op *h, const char *name, const uint64_t *values, uint32_t n) {
   HH_TRY(if (!name) throw std::runtime_error("null argument"); h->op->setConstants(name, values, n))
 }

@@ -565,6 +565,32 @@ typedef struct hm_ntt_lift_desc {
 } hm_ntt_lift_desc;
 hm_status hm_ntt_lift(hm_ctx *ctx, const hm_ntt_lift_desc *desc);
 
+/* Slot vectors <-> plaintexts: the canonical embedding of CKKS on the device.  N = ring degree, n = N / 2 slots,
+ * zeta = exp(i pi / N), e_j = 5^j mod 2N; slot j of a real polynomial m is m(zeta^e_j).
+ * hm_encode: for each of the n_vec vectors z (device, [n_vec][n][2] doubles re, im; 16-byte aligned)
+ *     m_k = (2 / N) Re sum_j z_j zeta^(-e_j k),   c_k = rint(scale * m_k) (ties to even),   k < N
+ * is stored as ONE coefficient-form limb-poly work[work_limbs[v]] modulo the SOURCE modulus src_mod_id; then ONE lifted forward transform
+ * (hm_ntt_lift's path) writes out[out_limbs[v * n_mod + m]] = NTT_{mod_ids[m]}(c mod q_{mod_ids[m]}) for every vector and modulus.  n_mod = 0
+ * stops after `work` (out, out_limbs, mod_ids are not read).  A coefficient with |c_k| > (q_src - 1) / 2 is stored as 0, never wrapped, and
+ * raises the counter "encode_overflow" (hm_get_counter; cleared by reading).  Two launches of a double-precision transform of length n (each
+ * workgroup a tile in LDS, roots from a table made on the host in long double; no sin / cos on the device) + the transform's.
+ * hm_decode: the reverse for ONE evaluation-form limb-poly per vector, modulo mod_id: work[work_limbs[v]] = INTT(in[in_limbs[v]]);
+ *     c = centre_q(work),   m_k = (double)c_k * (1 / scale),   slots[v][j] = sum_k m_k zeta^(e_j k).
+ * NULL limb lists mean 0, 1, .., as everywhere.  HM_ERR_ARG: a null buffer, limb or modulus ids out of range, a scale that is not finite and
+ * positive, slots or work not 16-byte aligned, work overlapping out (hm_encode) or in (hm_decode) by address range.  n_vec = 0 is HM_OK.
+ * The caller keeps the limb-polys of one call apart: work_limbs name n_vec DIFFERENT limb-polys, and `slots` overlaps neither `work` nor `in` /
+ * `out` (not checked: a pass of one vector would read what a pass of another writes).
+ * The first call of a context allocates the tables, and a call with more vectors than any before it a larger hand-off between hm_encode's two
+ * launches; a capturing stream is refused both (HM_ERR_UNSUPPORTED: run the call once, with the n_vec to be captured, before hm_capture_begin).
+ * After that the calls can be captured.  A captured graph keeps the address of the hand-off it was recorded with: while any graph of the
+ * context lives, a hand-off that a later, larger call outgrows is kept (until no graph lives, or hm_destroy) and never freed under the graph,
+ * so eager calls of any n_vec and replays mix freely.  hm_capability "cap_slot_transform": 1 for the rings served, N = 2^13 .. 2^17.
+ * Replaces: nothing upstream (the reference moves address tokens, never values). */
+hm_status hm_encode(hm_ctx *ctx, const double *slots, uint32_t n_vec, double scale, uint64_t *work, const uint32_t *work_limbs,
+                    uint32_t src_mod_id, uint64_t *out, const uint32_t *out_limbs, const uint32_t *mod_ids, uint32_t n_mod);
+hm_status hm_decode(hm_ctx *ctx, const uint64_t *in, const uint32_t *in_limbs, uint32_t mod_id, double scale, uint64_t *work,
+                    const uint32_t *work_limbs, double *slots, uint32_t n_vec);
+
 /* K4 — fast base conversion, matrix step: out_t = sum_i in_i * [Q_D / q_i]_t mod t for the input
  * basis in_ids (n_in <= 32) and output basis out_ids (n_out <= 64).  `in` must already hold
  * y_i = x_i * [(Q_D/q_i)^-1]_{q_i} (hm_ntt's scale or HM_OP_MUL_CONST with hm_bconv_consts).
@@ -710,6 +736,7 @@ void hm_graph_destroy(hm_graph *graph);
  *   "ntt_cross_xcd"  limb-polys of one-launch transforms whose workgroups were NOT all placed on one XCD and took the
  *                    agent-scope hand-off (slow, still correct); expected 0 under the dispatcher's observed round-robin placement.
  *   "ntt_fused_small", "ntt_fused_slots_per_xcd"  the threshold in force (0 = the one-launch form is off) and the guard's figure.
+ *   "encode_overflow"  1: since the last reading an hm_encode met a coefficient beyond half its source modulus (stored as 0); cleared by reading.
  * No reference counterpart: the reference's Arch has no tunables besides the .cfg keys (src/Arch.cpp:8-168). */
 hm_status hm_set_option(hm_ctx *ctx, const char *name, uint64_t value);
 /* What the back-end has kernels for at ring size N = 2^logN (round 6: one table, homulator_amd/csrc/hm_caps.h, instead of ring-size tests in
@@ -721,6 +748,7 @@ hm_status hm_set_option(hm_ctx *ctx, const char *name, uint64_t value);
  *                               transform's first pass; a planner's default, not a limit of the entry points)
  *   "cap_bconv_col_max_in_mix"  ... when the conversion carries the mix prologue (hm_ntt_fused_desc.conv with mix)
  *   "cap_ip_inverse_out"        1: hm_ntt_ip_desc.out_inverse is served
+ *   "cap_slot_transform"        1: hm_encode / hm_decode are served (N = 2^13 .. 2^17)
  *   "cap_col_slices"            ranks the column tiles of a limb-poly can be dealt to (hm_limbs_to_colslices / hm_bconv_col with a tile range)
  *   "cap_ntt_fused_small"       transform launches of up to this many limb-polys run in the one-launch form by default (option ntt_fused_small); 0: none
  * Replaces: nothing upstream — the reference sizes its units from the .cfg (src/Arch.cpp:8-168) and has one shape of each. */
