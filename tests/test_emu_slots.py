@@ -99,7 +99,8 @@ def decode_error(logN, name, scale):
     return float(np.abs(got - want).max())
 
 
-CASES = [(13, f, s) for f in FILLS for s in SCALES] + [(16, "uniform", SCALES[2]), (17, "uniform", SCALES[2])]
+CASES = [(13, f, s) for f in FILLS for s in SCALES] + [(14, "uniform", SCALES[1]), (14, "uniform", SCALES[2]), (16, "uniform", SCALES[2]),
+                                                      (17, "uniform", SCALES[2])]
 IDS = [f"N2^{l}-{f}-scale2^{int(np.log2(s))}" for l, f, s in CASES]
 
 
