@@ -55,6 +55,14 @@ def bsgs_id(o, ell, ct, g, h, baby_keys, giant_keys, pts, pt0s, ptgs):
     return o.ewe(EWE_ADD, Q, moddown(o, ell, T[0]), None, V), o.ewe(EWE_ADD, Q, moddown(o, ell, T[1]), None, W[0])
 
 
+def lintrans_id_inputs(o, ell, R, seed, copy=0, batch_seed_stride=100000):
+    """hlintrans's synthetic streams for op `copy` of a batch: (the ciphertext, rotation r's key (one for every op of the batch), pt<r>, pt0)"""
+    ids = o.ext_ids(ell)
+    c = copy * batch_seed_stride
+    return (o.synth_ct(ell, seed + c), [o.synth_evk(ell, seed + 10000 + 100000 * r) for r in range(1, R + 1)],
+            [o.fill_uniform(ids, seed + 4000 + 100000 * r + c) for r in range(1, R + 1)], o.fill_uniform(ids, seed + PT0_STREAM + c))
+
+
 def bsgs_id_inputs(o, ell, R, G, seed, copy=0, batch_seed_stride=100000):
     """the op's synthetic streams behind bsgs_ref.synthetic_inputs: (pt0s[i], i = 0..G; ptgs[r - 1], r = 1..R) of op `copy` of a batch"""
     ids = o.ext_ids(ell)

@@ -255,11 +255,8 @@ def test_refuses_bad_arguments():
 # ============================================================================================================================
 def inputs(o, ell, R, c=0, seed=SEED):
     """the op's synthetic streams for op c of a batch: the ciphertext, rotation r's key (one for every op of the batch), pt<r> and pt0"""
-    from identity_ref import PT0_STREAM
-    ids = o.ext_ids(ell)
-    return (o.synth_ct(ell, seed + c * BATCH_SEED_STRIDE), [o.synth_evk(ell, seed + 10000 + 100000 * r) for r in range(1, R + 1)],
-            [o.fill_uniform(ids, seed + 4000 + 100000 * r + c * BATCH_SEED_STRIDE) for r in range(1, R + 1)],
-            o.fill_uniform(ids, seed + PT0_STREAM + c * BATCH_SEED_STRIDE))
+    from identity_ref import lintrans_id_inputs
+    return lintrans_id_inputs(o, ell, R, seed, copy=c, batch_seed_stride=BATCH_SEED_STRIDE)
 
 
 def read_out(op, copy=0):

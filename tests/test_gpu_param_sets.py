@@ -109,8 +109,10 @@ def test_sweep_runner_layout(tmp_path):
 @pytest.mark.parametrize("alpha", [1, 2, 3, 5, 13])
 def test_every_level_small_ring(alpha):
     """hmult and hrotate at EVERY level of a 13-limb chain on a small ring (N = 2^13 through the `N` config override):
-    all digit shapes (beta = 1 .. 13, short last digits, a one-limb last digit) go through the fused plan, including
-    the merged ModDown + rescale transform, and must equal the oracle bit for bit"""
+    all digit shapes (beta = 1 .. 13, short last digits, a one-limb last digit), including the merged ModDown + rescale
+    transform, must equal the oracle bit for bit.  At N = 2^13 the capability table (homulator_amd/csrc/hm_caps.h) gives its
+    `default` row, the plain plan: the ModUp conversion is a launch of its own and the ModDown INTT runs whole.  The fused
+    plan's sweep over every level, at N = 2^15, is tests/test_gpu_level_sweep.py"""
     from homulator_amd import host
     L, logN = 13, 13
     o = Oracle(logN, L, alpha)
