@@ -18,6 +18,63 @@ enum ewe_opcode {
 
 static const uint32_t kNoLift = 0xFFFFFFFFu;   // Instruction::liftSrcMod of a plain forward transform
 
+// The fused element-wise records of passes (5d) .. (5a) (host/src/Planner.cpp): which kernel family a record has become (Fused::form), and, as
+// Instruction::mark, which pass the op builder wants to start at a record.  The marks, per form:
+//   TensorDot     a tensor product's MAC2 (d1) that is pair 1 of a SUM of tensor products (HDOT): pass (5d)
+//   Square        a tensor product's MAC2 (d1) of a ciphertext with ITSELF (HSQUARE): pass (5q)
+//   Lincomb       the MUL_CONST of term 1 of a sum of scaled ciphertexts (HLINCOMB, HMLINCOMB): pass (5l)
+//   LincombMulti  (never a mark: pass (5L) merges the records (5l) formed)
+//   MulAdd        a tensor product's MAC2 (d1) that scalars, scaled addends and a constant follow (HMULADD): pass (5m)
+//   ReIm          the ADD x + conj(x) of one limb and component (HREIM): pass (5r)
+//   CLincomb      the MUL_CONST a_1 x_1 of term 1 of a complex-weighted sum of ciphertexts (HCLINCOMB): pass (5c)
+//   PLincomb      the MUL p_1 x_1 of term 1 of one component of a plaintext-weighted sum of ciphertexts (HPLINCOMB): pass (5p); also the ADD of
+//                 that sum's plaintext addend, which the pass takes behind the last term only if it is marked
+//   DotAdd        a tensor product's MAC2 (d1) that is pair 1 of a scaled SUM of tensor products plus scaled addends plus a constant (HDOTADD):
+//                 pass (5a)
+enum class FusedForm : uint8_t { None, TensorDot, Square, Lincomb, LincombMulti, MulAdd, ReIm, CLincomb, PLincomb, DotAdd };
+
+// What a fused element-wise record reads and carries, whatever its form.  `reads` is every address it reads, in the order recordReads
+// (Records.h) reports them; the outputs are the record's OutputOperand and extraOutputs.  Per form (T = terms, A = addends):
+//   TensorDot (hm_tensor_dot)        a fusedTensor record that absorbed the chains behind its three outputs.  reads = (c00, c10, c01, c11) of
+//                                    every pair, pair 1 first; OutputOperand = the final d1, extraOutputs = the final d0, d2
+//   Square (hm_tensor_square)        a fusedTensor record of a ciphertext with itself.  reads = (c0, c1); outputs as TensorDot.  hasScale: the
+//                                    MUL_CONST records behind its three outputs went in, all with the constant scales[0]; hasConst: the ADD_CONST
+//                                    record behind d0 went in, with `constant`
+//   Lincomb (hm_lincomb)             the MUL_CONST record of term 1 that absorbed the MUL_CONST + ADD pairs of the further terms and the ADD_CONST
+//                                    behind them.  reads = the T inputs in term order, scales = their scalars; OutputOperand = the final sum;
+//                                    hasConst / constant: the ADD_CONST record
+//   LincombMulti (hm_lincomb_multi)  several Lincomb records over ONE list of inputs: the first of them, which absorbed the others.  reads = the
+//                                    shared T inputs; rowScales[m] = the T scalars of output m, rowConsts[m] = its constant (0 where the absorbed
+//                                    record had none; hasConst: some had one); OutputOperand = output 1, extraOutputs = outputs 2 .. M, in the
+//                                    order the sums were emitted (scales / constant stay output 1's, unread)
+//   MulAdd (hm_tensor_muladd)        a fusedTensor record that absorbed the chains behind its outputs.  reads = (c00, c10, c01, c11) of the
+//                                    product, then (x_t, y_t) of every addend; scales2 = the scalars u_t; outputs as TensorDot.  hasScale /
+//                                    scales[0], hasConst / constant: as Square
+//   ReIm (hm_reim_split)             the ADD record x + y that absorbed the SUB x - y of the same operands and the MUL of the difference by the
+//                                    evaluation form of -X^(N/2).  reads = (x, y); OutputOperand = the sum, extraOutputs = the product.  The
+//                                    stored factor is not read: the kernel derives it
+//   CLincomb (hm_clincomb)           the MUL_CONST record a_1 x_1 of term 1 that absorbed, per term, the MUL by the stored monomial, its
+//                                    MUL_CONST, the ADD of both parts and the ADD onto the running sum, and the ADD_CONST behind them.  reads = the
+//                                    T inputs in term order, scales = a_t, scales2 = b_t (the stages carry q - b_t: the stored monomial is
+//                                    -X^(N/2), which is not read); OutputOperand = the final sum; hasConst / constant: the ADD_CONST record
+//   PLincomb (hm_plincomb)           the MUL record p_1 x_1 of c0's chain that absorbed the MAC_ADD records behind it, the ADD of the addend, and
+//                                    the whole chain of c1 on the same plaintext limbs.  reads = (p_t, x_t, y_t) per term, in term order, then,
+//                                    with hasAddend, the plaintext limb added to c0; OutputOperand = c0's final sum, extraOutputs = c1's
+//   DotAdd (hm_tensor_dotadd)        a fusedTensor record that absorbed the tensor records of the further pairs and the chains behind the outputs.
+//                                    reads = (c00, c10, c01, c11) of every pair, pair 1 first, then (x_r, y_r) of every addend; scales = the
+//                                    scalar s_t of every pair (1: the pair had no MUL_CONST records), scales2 = the scalars u_r; outputs as
+//                                    TensorDot.  hasScale: the MUL_CONST records of at least one pair went in; hasConst / constant: as Square
+struct Fused {
+  FusedForm form = FusedForm::None;
+  std::vector<AddrType> reads;
+  uint32_t terms = 0, addends = 0;
+  std::vector<uint64_t> scales, scales2;
+  std::vector<std::vector<uint64_t>> rowScales;
+  std::vector<uint64_t> rowConsts;
+  bool hasScale = false, hasConst = false, hasAddend = false;
+  uint64_t constant = 0;
+};
+
 class Instruction {
 public:
   ins_ops ops;
@@ -31,21 +88,13 @@ public:
   uint64_t constant = 0;   // per-limb constant of MUL_CONST / SUB_SCALE, or the INTT epilogue scale
   uint32_t galois = 0;
   bool passthrough = false;  // an NTT-kind instruction whose input is already in evaluation form (copy)
-  bool sumHead = false;      // a tensor product's MAC2 (d1) that is pair 1 of a SUM of tensor products (HDOT): pass (5d) starts its record here
-  bool squareHead = false;   // a tensor product's MAC2 (d1) of a ciphertext with ITSELF (HSQUARE): pass (5q) starts its record here
-  bool lincombHead = false;  // the MUL_CONST of term 1 of a sum of scaled ciphertexts (HLINCOMB): pass (5l) starts its record here
-  bool muladdHead = false;   // a tensor product's MAC2 (d1) that scalars, scaled addends and a constant follow (HMULADD): pass (5m) starts its record here
-  bool reimHead = false;     // the ADD x + conj(x) of one limb and component (HREIM): pass (5r) starts its record here
-  bool clincombHead = false; // the MUL_CONST a_1 x_1 of term 1 of a complex-weighted sum of ciphertexts (HCLINCOMB): pass (5c) starts its record here
-  bool plincombHead = false; // the MUL p_1 x_1 of term 1 of one component of a plaintext-weighted sum of ciphertexts (HPLINCOMB): pass (5p) starts its record here;
-                             // also the ADD of that sum's plaintext addend, which the pass takes behind the last term only if it is marked
-  bool dotaddHead = false;   // a tensor product's MAC2 (d1) that is pair 1 of a scaled SUM of tensor products plus scaled addends plus a constant (HDOTADD):
-                             // pass (5a) starts its record here
+  FusedForm mark = FusedForm::None;   // set by the op builder: the pass of this form starts its record here (see FusedForm); at most one per record
   std::vector<uint32_t> inMods;  // BCONV: modulus ids of the inputs
   unsigned long long refInstructions = 0;  // upstream instructions this record stands for
   unsigned long long refExtra = 0;         // ... of records folded into a BCONV record (not scaled by its MAC-port count)
   // set by the backend's fusion passes (Arch::fusePasses, host/src/Planner.cpp), never by the generators; the fields that hold addresses
-  // are listed ONCE more, with their roles, in recordReads / recordWrites (Records.h): add a new one there too
+  // are listed ONCE more, with their roles, in recordReads / recordWrites (Records.h): add a new one there too.  (A new fused element-wise
+  // form needs no field: it is one more FusedForm, whose reads are Fused::reads)
   bool fusedSubScale = false;          // forward NTT whose epilogue is out = (minuend - NTT(in)) * constant [+ addend]
   AddrType fMinuend = 0, fAddend = 0;  // fAddend == 0: no addend
   // merged ModDown + rescale: the transform's input is in + fMixConst * fMix, the addend is scaled by fAddendConst
@@ -73,65 +122,7 @@ public:
   AddrType fSubFrom = 0, fAdd = 0;
   bool fusedTensor = false;            // MAC2 record that also produces d0 -> extraOutputs[0] and d2 -> extraOutputs[1]
   std::vector<AddrType> extraOutputs;
-  // (5d) sum of tensor products (hm_tensor_dot): a fusedTensor record that absorbed the chains behind its three outputs.  dotOperands = (c00, c10,
-  // c01, c11) of every pair, pair 1 first; OutputOperand = the final d1, extraOutputs = the final d0, d2.  Empty: a plain tensor product
-  std::vector<AddrType> dotOperands;
-  // (5q) scaled square plus constant (hm_tensor_square): a fusedTensor record of a ciphertext with itself.  sqOperands = (c0, c1): its two reads;
-  // OutputOperand = the final d1, extraOutputs = the final d0, d2.  sqHasScale: the MUL_CONST records behind its three outputs went in, all
-  // with the constant sqScale; sqHasConst: the ADD_CONST record behind d0 went in, with the constant sqConst.  sqOperands empty: not a square
-  std::vector<AddrType> sqOperands;
-  bool sqHasScale = false, sqHasConst = false;
-  uint64_t sqScale = 1, sqConst = 0;
-  // (5l) sum of scaled polynomials plus constant (hm_lincomb): the MUL_CONST record of term 1 that absorbed the MUL_CONST + ADD pairs of the further
-  // terms and the ADD_CONST behind them.  lcOperands = the T inputs in term order, lcScales = their scalars; OutputOperand = the final sum.
-  // lcHasConst: the ADD_CONST record went in, with the constant lcConst.  lcOperands empty: not such a sum
-  std::vector<AddrType> lcOperands;
-  std::vector<uint64_t> lcScales;
-  bool lcHasConst = false;
-  uint64_t lcConst = 0;
-  // (5L) several (5l) sums over ONE list of inputs (hm_lincomb_multi): the first of them, which absorbed the others.  lcOperands = the shared T
-  // inputs; mlScales[m] = the T scalars of output m, mlConsts[m] = its constant (0 where the absorbed record had none; mlHasConst: some had
-  // one); OutputOperand = output 1, extraOutputs = outputs 2 .. M, in the order the sums were emitted.  mlScales empty: not such a record
-  std::vector<std::vector<uint64_t>> mlScales;
-  std::vector<uint64_t> mlConsts;
-  bool mlHasConst = false;
-  // (5m) scaled tensor product plus scaled addends plus constant (hm_tensor_muladd): a fusedTensor record that absorbed the chains behind its
-  // outputs.  maOperands = (c00, c10, c01, c11) of the product, then (x_t, y_t) of every addend; maAddScales = the scalars u_t; OutputOperand = the
-  // final d1, extraOutputs = the final d0, d2.  maHasScale: the MUL_CONST records behind the three outputs went in, all with the constant
-  // maScale; maHasConst: the ADD_CONST record behind d0 went in, with the constant maConst.  maOperands empty: not such a record
-  std::vector<AddrType> maOperands;
-  std::vector<uint64_t> maAddScales;
-  bool maHasScale = false, maHasConst = false;
-  uint64_t maScale = 1, maConst = 0;
-  // (5r) real and imaginary parts from a polynomial and its conjugate (hm_reim_split): the ADD record x + y that absorbed the SUB x - y of the same
-  // operands and the MUL of the difference by the evaluation form of -X^(N/2).  reimOperands = (x, y): its two reads; OutputOperand = the sum,
-  // extraOutputs = the product.  The stored factor is not read: the kernel derives it.  reimOperands empty: not such a record
-  std::vector<AddrType> reimOperands;
-  // (5c) sum of polynomials times a + b X^(N/2) plus constant (hm_clincomb): the MUL_CONST record a_1 x_1 of term 1 that absorbed, per term, the
-  // MUL by the stored monomial, its MUL_CONST, the ADD of both parts and the ADD onto the running sum, and the ADD_CONST behind them.
-  // clOperands = the T inputs in term order, clScalesRe = a_t, clScalesIm = b_t (the stages carry q - b_t: the stored monomial is -X^(N/2));
-  // OutputOperand = the final sum.  clHasConst: the ADD_CONST record went in, with the constant clConst.  The stored monomial is not read: the
-  // kernel derives it.  clOperands empty: not such a sum
-  std::vector<AddrType> clOperands;
-  std::vector<uint64_t> clScalesRe, clScalesIm;
-  bool clHasConst = false;
-  uint64_t clConst = 0;
-  // (5p) sum of ciphertexts times plaintexts plus a plaintext on c0 (hm_plincomb): the MUL record p_1 x_1 of c0's chain that absorbed the MAC_ADD
-  // records behind it, the ADD of the addend, and the whole chain of c1 on the same plaintext limbs.  plOperands = (p_t, x_t, y_t) per term, in
-  // term order; plAddend = the plaintext limb added to c0 (plHasAddend); OutputOperand = c0's final sum, extraOutputs = c1's.  plOperands empty:
-  // not such a sum
-  std::vector<AddrType> plOperands;
-  bool plHasAddend = false;
-  AddrType plAddend = 0;
-  // (5a) scaled sum of tensor products plus scaled addends plus constant (hm_tensor_dotadd): a fusedTensor record that absorbed the tensor records
-  // of the further pairs and the chains behind the outputs.  daOperands = (c00, c10, c01, c11) of every pair, pair 1 first, then (x_r, y_r) of
-  // every addend; daScales = the scalar s_t of every pair (1: the pair had no MUL_CONST records), daAddScales = the scalars u_r; OutputOperand =
-  // the final d1, extraOutputs = the final d0, d2.  daHasScale: the MUL_CONST records of at least one pair went in; daHasConst: the ADD_CONST
-  // record behind d0 went in, with the constant daConst.  daOperands empty: not such a record
-  std::vector<AddrType> daOperands;
-  std::vector<uint64_t> daScales, daAddScales;
-  bool daHasScale = false, daHasConst = false;
-  uint64_t daConst = 0;
+  Fused fu;                            // (5d .. 5a) the fused element-wise record this one has become; fu.form == None: none of them
   // fused inner product (ops == IP): out_k = sum_j ipX[j] * ipY[k][j]; out_0 = OutputOperand, out_1 = extraOutputs[0]
   std::vector<AddrType> ipX;
   std::vector<std::vector<AddrType>> ipY;

@@ -158,6 +158,35 @@ protected:
   // negated: the records carry q_j - value (HCLINCOMB's "scale_im<t>": the stage multiplies by the stored -X^(N/2))
   struct ConstantStage { bool enabled = false; std::string key; std::vector<std::vector<Instruction *>> records; bool nonZero = false; bool negated = false; };
   std::map<std::string, ConstantStage> constantStages;
+  // ---- what the builders of the fused element-wise ops share (HREIM, HDOT .. HDOTADD).  `op` names the op in the messages
+  // a build extension has no backend = sim ("... has no such op (<why>)") and no world > 1
+  void refuseSimAndSharded(const std::string &op, const std::string &why) const;
+  bool flag(const std::string &op, const char *key, uint32_t dflt = 0) const;   // a config key that is 0 or 1
+  uint32_t countKey(const std::string &op, const char *key, uint32_t dflt, uint32_t lo, uint32_t hi) const;   // ... in [lo, hi] (terms, addends, outputs)
+  // per-limb constants from the synthetic stream `stream` (word 0 of limb j's stream); nonZero: 1 in place of 0 (a constant that multiplies);
+  // negated: q_j - value
+  std::vector<uint64_t> synth(uint64_t stream, bool nonZero = false, bool negated = false) const;
+  // the records of limb j of a constant stage (one group per limb), kept under `name` for setConstants
+  void keep(const std::string &name, const std::vector<INSGROUP> &recs, bool nonZero = false, bool negated = false);
+  // one element-wise stage over the `level` limbs, stage key `key`, labels <label>_<key>_Level(j), into the new buffer `buffer`: out = op(a, b, c)
+  // with the per-limb constants, if any.  a, c wait for their producers (`from` empty: an op input, nothing to wait for); b is a stored operand
+  Limbs eweStage(const std::string &key, ewe_opcode op, const std::string &buffer, const Limbs &a, const Limbs *c = nullptr,
+                 const std::vector<uint64_t> &constants = {}, const std::vector<AddrType> &b = {});
+  // the three polynomials d0, d1, d2 of a tensor product with their producers; its MAC2 records (d1) get the mark
+  static std::array<Limbs, 3> tensorProduct(const TensorCompute &tcm, FusedForm mark);
+  static std::array<std::vector<AddrType>, 3> addrs(const std::array<Limbs, 3> &d);
+  // the same scalar on d0, d1, d2 (HSQUARE, HMULADD, HDOTADD): three MUL_CONST stages <key>_D<i> into <buffer>D<i>Scale<suffix>, constants `constants`
+  void scaleTriple(std::array<Limbs, 3> &d, const std::string &key, const std::string &buffer, const std::string &suffix, const std::string &constants,
+                   uint64_t stream);
+  // the tail of HMULADD and HDOTADD on the running d: per addend t = 1..A (input ciphertext firstCt + t, stream + step t) and component k,
+  // <op>_AddScale_(t)_C<k> (MUL_CONST, constants "addscale<t>") and <op>_Add_(t)_D<k> (ADD) into <buffer>D<k><sumWord>(t); shifted: <op>_Const_D0
+  void addendTail(std::array<Limbs, 3> &d, const std::string &op, const std::string &buffer, const std::string &sumWord, uint32_t A, uint32_t firstCt,
+                  uint64_t stream, uint64_t step, bool shifted, uint64_t constStream);
+  // HLINCOMB's and HMLINCOMB's chain on component k: <op>_Scale_<index t)>_C<k> = s_t ct<t>.c<k> (MUL_CONST, stream + step t, constants <scale><t>;
+  // term 1 carries the mark Lincomb), <op>_Add_<index t)>_C<k> for t >= 2, and with constHere <constKey>_C<k> (ADD_CONST, constants <constName>);
+  // the last buffer is `result`
+  struct ScaledSumNames { std::string op, index, result, constKey, scale, constName; uint64_t stream, step, constStream; };
+  Limbs scaledSum(uint32_t k, uint32_t T, bool constHere, const ScaledSumNames &n);
   std::vector<AddrType> alloc(const std::string &name, uint32_t limbs);  // MallocMem + getAddr
   std::vector<AddrType> component(uint32_t ct, uint32_t k) const { return k == 0 ? cts[ct].getC0Addr() : cts[ct].getC1Addr(); }  // c_k of input ct
   void setOutput(const std::string &out, uint32_t k, const std::vector<AddrType> &limbs) { namedOutputs[out + ".c" + std::to_string(k)] = limbs; }

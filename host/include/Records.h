@@ -82,23 +82,8 @@ inline std::vector<Read> recordReads(const Instruction &i) {
   }
   if (i.ops == BCONV_STEP2) {
     for (size_t x = 0; x + 1 < i.operandList.size(); ++x) v.push_back({i.operandList[x], Role::ConvIn, kNoDigit});
-  } else if (!i.dotOperands.empty()) {   // (5d): the operands of every pair, pair 1's (operandList) among them
-    for (AddrType a : i.dotOperands) v.push_back({a, Role::Operand, kNoDigit});
-  } else if (!i.sqOperands.empty()) {    // (5q): the two polynomials of the one ciphertext, each read once
-    for (AddrType a : i.sqOperands) v.push_back({a, Role::Operand, kNoDigit});
-  } else if (!i.lcOperands.empty()) {    // (5l): the input of every term; (5L, several sums over them: mlScales) once for all outputs, which are OutputOperand and extraOutputs
-    for (AddrType a : i.lcOperands) v.push_back({a, Role::Operand, kNoDigit});
-  } else if (!i.maOperands.empty()) {    // (5m): the four operands of the product, then both components of every addend
-    for (AddrType a : i.maOperands) v.push_back({a, Role::Operand, kNoDigit});
-  } else if (!i.reimOperands.empty()) {  // (5r): the polynomial and its conjugate, each read once
-    for (AddrType a : i.reimOperands) v.push_back({a, Role::Operand, kNoDigit});
-  } else if (!i.clOperands.empty()) {    // (5c): the input of every term; the stored monomial is not read
-    for (AddrType a : i.clOperands) v.push_back({a, Role::Operand, kNoDigit});
-  } else if (!i.plOperands.empty()) {    // (5p): plaintext and both components of every term, then the addend
-    for (AddrType a : i.plOperands) v.push_back({a, Role::Operand, kNoDigit});
-    if (i.plHasAddend) v.push_back({i.plAddend, Role::Operand, kNoDigit});
-  } else if (!i.daOperands.empty()) {    // (5a): the four operands of every pair, then both components of every addend
-    for (AddrType a : i.daOperands) v.push_back({a, Role::Operand, kNoDigit});
+  } else if (i.fu.form != FusedForm::None) {   // (5d .. 5a): the form's reads in its own order (Instruction.h), pair 1's (operandList) among them
+    for (AddrType a : i.fu.reads) v.push_back({a, Role::Operand, kNoDigit});
   } else if (i.ops == MULT) {
     for (int b = 0; b < 4; ++b)
       if (eweOperandMask(i.opcode) & (1 << b)) v.push_back({i.operandList[b], Role::Operand, kNoDigit});

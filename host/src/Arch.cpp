@@ -354,15 +354,19 @@ int partKey(const Instruction &i) {
   if (!i.ipHoistG.empty()) return 6000 + (int)i.ipX.size() * 100 + (int)i.ipHoistG.size();                 // 6000+: hoisted key product, by digits and rotations
   if (i.ops == IP && transformsInside(i)) return 400 + (int)i.ipX.size() * 10 + (int)i.ipY.size();         // 400+: transform x key, by digits and keys
   if (isKeyProduct(i)) return 300 + (int)i.ipX.size() * 10 + (int)i.ipY.size();                            // 300+: key product, by digits and keys
-  if (!i.dotOperands.empty()) return 8000 + (int)i.dotOperands.size() / 4;                                 // 8000+: sum of tensor products, by pairs
-  if (!i.sqOperands.empty()) return 8500 + (i.sqHasScale ? 1 : 0) + (i.sqHasConst ? 2 : 0);                // 8500+: scaled square plus constant, by what it absorbed
-  if (!i.mlScales.empty()) return 12000 + 16 * ((int)i.lcOperands.size() - 1) + (int)i.mlScales.size() - 1;   // 12000+: several sums of scaled polynomials, by terms and sums (12000 .. 12255)
-  if (!i.lcOperands.empty()) return 8600 + (int)i.lcOperands.size();                                   // 8600+: sum of scaled polynomials, by terms
-  if (!i.maOperands.empty()) return 8700 + 4 * (int)i.maAddScales.size() + (i.maHasScale ? 1 : 0) + (i.maHasConst ? 2 : 0);   // 8700+: scaled product plus addends, by addends and what it absorbed
-  if (!i.daOperands.empty()) return 8100 + 9 * ((int)i.daScales.size() - 1) + (int)i.daAddScales.size();                          // 8100+: scaled sum of products plus addends, by pairs and addends (8100 .. 8243)
-  if (!i.reimOperands.empty()) return 8400;                                                                // 8400: sum and rotated difference of a polynomial and its conjugate
-  if (!i.clOperands.empty()) return 8800 + (int)i.clOperands.size();                                       // 8800+: sum of polynomials times a + b X^(N/2), by terms
-  if (!i.plOperands.empty()) return 8900 + 2 * ((int)i.plOperands.size() / 3) + (i.plHasAddend ? 1 : 0);   // 8900+: sum of ciphertexts times plaintexts, by terms and addend
+  const Fused &f = i.fu;
+  switch (f.form) {
+    case FusedForm::None: break;
+    case FusedForm::TensorDot: return 8000 + (int)f.terms;                                                  // 8000+: sum of tensor products, by pairs
+    case FusedForm::Square: return 8500 + (f.hasScale ? 1 : 0) + (f.hasConst ? 2 : 0);                      // 8500+: scaled square plus constant, by what it absorbed
+    case FusedForm::LincombMulti: return 12000 + 16 * ((int)f.terms - 1) + (int)f.rowScales.size() - 1;     // 12000+: several sums of scaled polynomials, by terms and sums (12000 .. 12255)
+    case FusedForm::Lincomb: return 8600 + (int)f.terms;                                                    // 8600+: sum of scaled polynomials, by terms
+    case FusedForm::MulAdd: return 8700 + 4 * (int)f.addends + (f.hasScale ? 1 : 0) + (f.hasConst ? 2 : 0); // 8700+: scaled product plus addends, by addends and what it absorbed
+    case FusedForm::DotAdd: return 8100 + 9 * ((int)f.terms - 1) + (int)f.addends;                          // 8100+: scaled sum of products plus addends, by pairs and addends (8100 .. 8243)
+    case FusedForm::ReIm: return 8400;                                                                      // 8400: sum and rotated difference of a polynomial and its conjugate
+    case FusedForm::CLincomb: return 8800 + (int)f.terms;                                                   // 8800+: sum of polynomials times a + b X^(N/2), by terms
+    case FusedForm::PLincomb: return 8900 + 2 * (int)f.terms + (f.hasAddend ? 1 : 0);                       // 8900+: sum of ciphertexts times plaintexts, by terms and addend
+  }
   if (i.fusedTensor) return 200;                                                                           // 200: tensor product
   if (i.fusedSubScale && i.fMinuendB) return i.fMix ? 211 : 209;                                           // 209 / 211: ... with a product minuend (4p)
   if (i.fusedSubScale) return (i.fMix ? 203 : 201) + (i.fConvIn.empty() ? 0 : 4);                          // 201 / 203: fused forward transform, plain / merged; 205 / 207: with its conversion
@@ -530,15 +534,14 @@ struct Arch::LaunchBuilder {
   void nttIp(Launch &L, Recs recs);
   void ip(Launch &L, Recs recs);
   void tensor(Launch &L, Recs recs);
-  void tensorDot(Launch &L, Recs recs);
+  void tensorOutputs(Launch &L, const Instruction *i);
   void tensorSquare(Launch &L, Recs recs);
-  void lincomb(Launch &L, Recs recs);
+  void lincomb(Launch &L, Recs recs);        // (5l) and (5c)
   void lincombMulti(Launch &L, Recs recs);
   void tensorMulAdd(Launch &L, Recs recs);
   void reim(Launch &L, Recs recs);
-  void clincomb(Launch &L, Recs recs);
   void plincomb(Launch &L, Recs recs);
-  void tensorDotAdd(Launch &L, Recs recs);
+  void tensorDotAdd(Launch &L, Recs recs);   // (5a) and (5d)
   void nttSubScale(Launch &L, Recs recs);
   void copy(Launch &L, Recs recs);
   void transform(Launch &L, Recs recs);
@@ -666,25 +669,15 @@ void Arch::LaunchBuilder::tensor(Launch &L, Recs recs) {
   for (Instruction *i : recs) {  // a = c00 (P), b = c10 (T), c = c01 (R), d = c11 (S)
     L.a.push_back(limb(i->operandList[0])); L.b.push_back(limb(i->operandList[3]));
     L.c.push_back(limb(i->operandList[2])); L.d.push_back(limb(i->operandList[1]));
-    L.out.push_back(limb(i->extraOutputs[0])); L.out1.push_back(limb(i->OutputOperand)); L.out2.push_back(limb(i->extraOutputs[1]));
-    L.mods.push_back(i->mod_id);
+    tensorOutputs(L, i);
   }
   L.bytes = 7 * LP * recs.size();
 }
 
-// (5d) a, b, c, d = c00, c10, c01, c11 of every pair [n][T]; out, out1, out2 = d0, d1, d2 [n] (hm_tensor_dot)
-void Arch::LaunchBuilder::tensorDot(Launch &L, Recs recs) {
-  L.kind = Launch::L_TENSOR_DOT; L.statKey = "EWE";
-  L.dotTerms = (uint32_t)recs[0]->dotOperands.size() / 4;
-  for (Instruction *i : recs) {
-    for (size_t t = 0; t < L.dotTerms; ++t) {
-      L.a.push_back(limb(i->dotOperands[4 * t])); L.b.push_back(limb(i->dotOperands[4 * t + 1]));
-      L.c.push_back(limb(i->dotOperands[4 * t + 2])); L.d.push_back(limb(i->dotOperands[4 * t + 3]));
-    }
-    L.out.push_back(limb(i->extraOutputs[0])); L.out1.push_back(limb(i->OutputOperand)); L.out2.push_back(limb(i->extraOutputs[1]));
-    L.mods.push_back(i->mod_id);
-  }
-  L.bytes = (4ull * L.dotTerms + 3) * LP * recs.size();   // every operand read once, the three sums written once
+// the three sums of a tensor form: out, out1, out2 = d0, d1, d2 [n]
+void Arch::LaunchBuilder::tensorOutputs(Launch &L, const Instruction *i) {
+  L.out.push_back(limb(i->extraOutputs[0])); L.out1.push_back(limb(i->OutputOperand)); L.out2.push_back(limb(i->extraOutputs[1]));
+  L.mods.push_back(i->mod_id);
 }
 
 // (5q) a, c = c0, c1 of the ciphertext [n]; out, out1, out2 = d0, d1, d2 [n]; k / addK = the scalars / the constants [n] (hm_tensor_square).  The
@@ -692,28 +685,30 @@ void Arch::LaunchBuilder::tensorDot(Launch &L, Recs recs) {
 void Arch::LaunchBuilder::tensorSquare(Launch &L, Recs recs) {
   L.kind = Launch::L_TENSOR_SQUARE; L.statKey = "EWE";
   for (Instruction *i : recs) {
-    L.a.push_back(limb(i->sqOperands[0])); L.c.push_back(limb(i->sqOperands[1]));
-    L.out.push_back(limb(i->extraOutputs[0])); L.out1.push_back(limb(i->OutputOperand)); L.out2.push_back(limb(i->extraOutputs[1]));
-    L.mods.push_back(i->mod_id);
-    if (recs[0]->sqHasScale) L.k.push_back(i->sqScale);
-    if (recs[0]->sqHasConst) L.addK.push_back(i->sqConst);
+    L.a.push_back(limb(i->fu.reads[0])); L.c.push_back(limb(i->fu.reads[1]));
+    tensorOutputs(L, i);
+    if (recs[0]->fu.hasScale) L.k.push_back(i->fu.scales[0]);
+    if (recs[0]->fu.hasConst) L.addK.push_back(i->fu.constant);
   }
   L.bytes = 5 * LP * recs.size();   // two polynomials read, three written
 }
 
-// (5l) a = the input of every term [n][T]; out = the sum [n]; k = the scalars [n][T], addK = the constants [n] (hm_lincomb).  The part key keeps
-// records of different term counts apart; a record without a constant (c1 beside a c0 that has one) adds 0, which changes no residue
+// (5l) a = the input of every term [n][T]; out = the sum [n]; k = the scalars [n][T], addK = the constants [n] (hm_lincomb).
+// (5c) the same with k / maK = the real / the monomial parts of the scalars [n][T] (hm_clincomb; the back-end derives X^(N/2)): a (5l) record has
+// no second scalar list.  The part key keeps records of different term counts apart; a record without a constant (c1 beside a c0 that has one)
+// adds 0, which changes no residue
 void Arch::LaunchBuilder::lincomb(Launch &L, Recs recs) {
-  L.kind = Launch::L_LINCOMB; L.statKey = "EWE";
-  L.dotTerms = (uint32_t)recs[0]->lcOperands.size();
+  L.kind = recs[0]->fu.form == FusedForm::CLincomb ? Launch::L_CLINCOMB : Launch::L_LINCOMB; L.statKey = "EWE";
+  L.dotTerms = recs[0]->fu.terms;
   for (Instruction *i : recs) {
-    for (AddrType x : i->lcOperands) L.a.push_back(limb(x));
-    L.k.insert(L.k.end(), i->lcScales.begin(), i->lcScales.end());
+    for (AddrType x : i->fu.reads) L.a.push_back(limb(x));
+    L.k.insert(L.k.end(), i->fu.scales.begin(), i->fu.scales.end());
+    L.maK.insert(L.maK.end(), i->fu.scales2.begin(), i->fu.scales2.end());
     L.out.push_back(limb(i->OutputOperand));
     L.mods.push_back(i->mod_id);
   }
-  if (std::any_of(recs.begin(), recs.end(), [](const Instruction *i) { return i->lcHasConst; }))
-    for (Instruction *i : recs) L.addK.push_back(i->lcHasConst ? i->lcConst : 0);
+  if (std::any_of(recs.begin(), recs.end(), [](const Instruction *i) { return i->fu.hasConst; }))
+    for (Instruction *i : recs) L.addK.push_back(i->fu.hasConst ? i->fu.constant : 0);
   L.bytes = (L.dotTerms + 1ull) * LP * recs.size();   // every input read once, the sum written once
 }
 
@@ -722,17 +717,17 @@ void Arch::LaunchBuilder::lincomb(Launch &L, Recs recs) {
 // reads the inputs once per tile of HM_LINCOMB_MULTI_TILE sums
 void Arch::LaunchBuilder::lincombMulti(Launch &L, Recs recs) {
   L.kind = Launch::L_LINCOMB_MULTI; L.statKey = "EWE";
-  L.dotTerms = (uint32_t)recs[0]->lcOperands.size();
-  L.multiOuts = (uint32_t)recs[0]->mlScales.size();
+  L.dotTerms = recs[0]->fu.terms;
+  L.multiOuts = (uint32_t)recs[0]->fu.rowScales.size();
   for (Instruction *i : recs) {
-    for (AddrType x : i->lcOperands) L.a.push_back(limb(x));
-    for (const std::vector<uint64_t> &row : i->mlScales) L.k.insert(L.k.end(), row.begin(), row.end());
+    for (AddrType x : i->fu.reads) L.a.push_back(limb(x));
+    for (const std::vector<uint64_t> &row : i->fu.rowScales) L.k.insert(L.k.end(), row.begin(), row.end());
     L.out.push_back(limb(i->OutputOperand));
     for (AddrType o : i->extraOutputs) L.out.push_back(limb(o));
     L.mods.push_back(i->mod_id);
   }
-  if (std::any_of(recs.begin(), recs.end(), [](const Instruction *i) { return i->mlHasConst; }))
-    for (Instruction *i : recs) L.addK.insert(L.addK.end(), i->mlConsts.begin(), i->mlConsts.end());
+  if (std::any_of(recs.begin(), recs.end(), [](const Instruction *i) { return i->fu.hasConst; }))
+    for (Instruction *i : recs) L.addK.insert(L.addK.end(), i->fu.rowConsts.begin(), i->fu.rowConsts.end());
   const unsigned long long tiles = (L.multiOuts + HM_LINCOMB_MULTI_TILE - 1) / HM_LINCOMB_MULTI_TILE;
   L.bytes = (tiles * L.dotTerms + L.multiOuts) * LP * recs.size();   // every input read once per tile of sums, every sum written once
 }
@@ -742,18 +737,17 @@ void Arch::LaunchBuilder::lincombMulti(Launch &L, Recs recs) {
 // absorbed different things, apart
 void Arch::LaunchBuilder::tensorMulAdd(Launch &L, Recs recs) {
   L.kind = Launch::L_TENSOR_MULADD; L.statKey = "EWE";
-  L.maAddends = (uint32_t)recs[0]->maAddScales.size();
+  L.maAddends = recs[0]->fu.addends;
   for (Instruction *i : recs) {
-    L.a.push_back(limb(i->maOperands[0])); L.b.push_back(limb(i->maOperands[1]));
-    L.c.push_back(limb(i->maOperands[2])); L.d.push_back(limb(i->maOperands[3]));
+    const std::vector<AddrType> &r = i->fu.reads;
+    L.a.push_back(limb(r[0])); L.b.push_back(limb(r[1])); L.c.push_back(limb(r[2])); L.d.push_back(limb(r[3]));
     for (uint32_t t = 0; t < L.maAddends; ++t) {
-      L.x0.push_back(limb(i->maOperands[4 + 2 * t])); L.x1.push_back(limb(i->maOperands[5 + 2 * t]));
+      L.x0.push_back(limb(r[4 + 2 * t])); L.x1.push_back(limb(r[5 + 2 * t]));
     }
-    L.maK.insert(L.maK.end(), i->maAddScales.begin(), i->maAddScales.end());
-    L.out.push_back(limb(i->extraOutputs[0])); L.out1.push_back(limb(i->OutputOperand)); L.out2.push_back(limb(i->extraOutputs[1]));
-    L.mods.push_back(i->mod_id);
-    if (recs[0]->maHasScale) L.k.push_back(i->maScale);
-    if (recs[0]->maHasConst) L.addK.push_back(i->maConst);
+    L.maK.insert(L.maK.end(), i->fu.scales2.begin(), i->fu.scales2.end());
+    tensorOutputs(L, i);
+    if (recs[0]->fu.hasScale) L.k.push_back(i->fu.scales[0]);
+    if (recs[0]->fu.hasConst) L.addK.push_back(i->fu.constant);
   }
   L.bytes = (7ull + 2 * L.maAddends) * LP * recs.size();   // four operands and both components of every addend read once, three polynomials written
 }
@@ -762,42 +756,25 @@ void Arch::LaunchBuilder::tensorMulAdd(Launch &L, Recs recs) {
 void Arch::LaunchBuilder::reim(Launch &L, Recs recs) {
   L.kind = Launch::L_REIM; L.statKey = "EWE";
   for (Instruction *i : recs) {
-    L.a.push_back(limb(i->reimOperands[0])); L.c.push_back(limb(i->reimOperands[1]));
+    L.a.push_back(limb(i->fu.reads[0])); L.c.push_back(limb(i->fu.reads[1]));
     L.out.push_back(limb(i->OutputOperand)); L.out1.push_back(limb(i->extraOutputs[0]));
     L.mods.push_back(i->mod_id);
   }
   L.bytes = 4 * LP * recs.size();   // two polynomials read, two written
 }
 
-// (5c) a = the input of every term [n][T]; out = the sum [n]; k / maK = the real / the monomial parts of the scalars [n][T], addK = the constants [n]
-// (hm_clincomb; the back-end derives X^(N/2)).  The part key keeps records of different term counts apart; a record without a constant (c1 beside a
-// c0 that has one) adds 0, which changes no residue
-void Arch::LaunchBuilder::clincomb(Launch &L, Recs recs) {
-  L.kind = Launch::L_CLINCOMB; L.statKey = "EWE";
-  L.dotTerms = (uint32_t)recs[0]->clOperands.size();
-  for (Instruction *i : recs) {
-    for (AddrType x : i->clOperands) L.a.push_back(limb(x));
-    L.k.insert(L.k.end(), i->clScalesRe.begin(), i->clScalesRe.end());
-    L.maK.insert(L.maK.end(), i->clScalesIm.begin(), i->clScalesIm.end());
-    L.out.push_back(limb(i->OutputOperand));
-    L.mods.push_back(i->mod_id);
-  }
-  if (std::any_of(recs.begin(), recs.end(), [](const Instruction *i) { return i->clHasConst; }))
-    for (Instruction *i : recs) L.addK.push_back(i->clHasConst ? i->clConst : 0);
-  L.bytes = (L.dotTerms + 1ull) * LP * recs.size();   // every input read once, the sum written once
-}
-
 // (5p) b = the plaintext, x0 / x1 = c0 / c1 of the ciphertext of every term [n][T]; d = the addend [n] (empty: no record has one); out / out1 = the
 // sums of c0 / c1 [n] (hm_plincomb).  The part key keeps records of different term counts apart, and those with an addend from those without
 void Arch::LaunchBuilder::plincomb(Launch &L, Recs recs) {
   L.kind = Launch::L_PLINCOMB; L.statKey = "EWE";
-  L.dotTerms = (uint32_t)recs[0]->plOperands.size() / 3;
-  const bool addend = recs[0]->plHasAddend;
+  L.dotTerms = recs[0]->fu.terms;
+  const bool addend = recs[0]->fu.hasAddend;
   for (Instruction *i : recs) {
+    const std::vector<AddrType> &r = i->fu.reads;
     for (uint32_t t = 0; t < L.dotTerms; ++t) {
-      L.b.push_back(limb(i->plOperands[3 * t])); L.x0.push_back(limb(i->plOperands[3 * t + 1])); L.x1.push_back(limb(i->plOperands[3 * t + 2]));
+      L.b.push_back(limb(r[3 * t])); L.x0.push_back(limb(r[3 * t + 1])); L.x1.push_back(limb(r[3 * t + 2]));
     }
-    if (addend) L.d.push_back(limb(i->plAddend));
+    if (addend) L.d.push_back(limb(r[3 * L.dotTerms]));
     L.out.push_back(limb(i->OutputOperand)); L.out1.push_back(limb(i->extraOutputs[0]));
     L.mods.push_back(i->mod_id);
   }
@@ -807,26 +784,26 @@ void Arch::LaunchBuilder::plincomb(Launch &L, Recs recs) {
 // (5a) a, b, c, d = c00, c10, c01, c11 of every pair [n][T]; x0, x1 = c0, c1 of every addend [n][A]; out, out1, out2 = d0, d1, d2 [n]; k = the pair
 // scalars [n][T], maK = the addend scalars [n][A], addK = the constants [n] (hm_tensor_dotadd).  The part key keeps records of different pair
 // and addend counts apart; a record without scalars beside one that has them multiplies by 1, one without a constant adds 0: neither changes a
-// residue
+// residue.
+// (5d) the same without addends, scalars and constant (hm_tensor_dot): a (5d) record carries none of them
 void Arch::LaunchBuilder::tensorDotAdd(Launch &L, Recs recs) {
-  L.kind = Launch::L_TENSOR_DOTADD; L.statKey = "EWE";
-  L.dotTerms = (uint32_t)recs[0]->daScales.size();
-  L.maAddends = (uint32_t)recs[0]->daAddScales.size();
-  const bool scaled = std::any_of(recs.begin(), recs.end(), [](const Instruction *i) { return i->daHasScale; });
-  const bool shifted = std::any_of(recs.begin(), recs.end(), [](const Instruction *i) { return i->daHasConst; });
+  L.kind = recs[0]->fu.form == FusedForm::TensorDot ? Launch::L_TENSOR_DOT : Launch::L_TENSOR_DOTADD; L.statKey = "EWE";
+  L.dotTerms = recs[0]->fu.terms;
+  L.maAddends = recs[0]->fu.addends;
+  const bool scaled = std::any_of(recs.begin(), recs.end(), [](const Instruction *i) { return i->fu.hasScale; });
+  const bool shifted = std::any_of(recs.begin(), recs.end(), [](const Instruction *i) { return i->fu.hasConst; });
   for (Instruction *i : recs) {
+    const std::vector<AddrType> &r = i->fu.reads;
     for (size_t t = 0; t < L.dotTerms; ++t) {
-      L.a.push_back(limb(i->daOperands[4 * t])); L.b.push_back(limb(i->daOperands[4 * t + 1]));
-      L.c.push_back(limb(i->daOperands[4 * t + 2])); L.d.push_back(limb(i->daOperands[4 * t + 3]));
+      L.a.push_back(limb(r[4 * t])); L.b.push_back(limb(r[4 * t + 1])); L.c.push_back(limb(r[4 * t + 2])); L.d.push_back(limb(r[4 * t + 3]));
     }
-    for (size_t r = 0; r < L.maAddends; ++r) {
-      L.x0.push_back(limb(i->daOperands[4 * L.dotTerms + 2 * r])); L.x1.push_back(limb(i->daOperands[4 * L.dotTerms + 2 * r + 1]));
+    for (size_t a = 0; a < L.maAddends; ++a) {
+      L.x0.push_back(limb(r[4 * L.dotTerms + 2 * a])); L.x1.push_back(limb(r[4 * L.dotTerms + 2 * a + 1]));
     }
-    if (scaled) L.k.insert(L.k.end(), i->daScales.begin(), i->daScales.end());
-    L.maK.insert(L.maK.end(), i->daAddScales.begin(), i->daAddScales.end());
-    if (shifted) L.addK.push_back(i->daHasConst ? i->daConst : 0);
-    L.out.push_back(limb(i->extraOutputs[0])); L.out1.push_back(limb(i->OutputOperand)); L.out2.push_back(limb(i->extraOutputs[1]));
-    L.mods.push_back(i->mod_id);
+    if (scaled) L.k.insert(L.k.end(), i->fu.scales.begin(), i->fu.scales.end());
+    L.maK.insert(L.maK.end(), i->fu.scales2.begin(), i->fu.scales2.end());
+    if (shifted) L.addK.push_back(i->fu.hasConst ? i->fu.constant : 0);
+    tensorOutputs(L, i);
   }
   L.bytes = (4ull * L.dotTerms + 2 * L.maAddends + 3) * LP * recs.size();   // every operand and both components of every addend read once, three sums written
 }
@@ -997,15 +974,17 @@ void Arch::LaunchBuilder::emitCompute(const Group &group, Launches &front, Launc
   else if (f->ops == IP && !f->ipHoistG.empty()) ipHoisted(*L, recs);
   else if (f->ops == IP && transformsInside(*f)) nttIp(*L, recs);
   else if (isKeyProduct(*f)) ip(*L, recs);
-  else if (!f->dotOperands.empty()) tensorDot(*L, recs);
-  else if (!f->sqOperands.empty()) tensorSquare(*L, recs);
-  else if (!f->mlScales.empty()) lincombMulti(*L, recs);
-  else if (!f->lcOperands.empty()) lincomb(*L, recs);
-  else if (!f->maOperands.empty()) tensorMulAdd(*L, recs);
-  else if (!f->reimOperands.empty()) reim(*L, recs);
-  else if (!f->clOperands.empty()) clincomb(*L, recs);
-  else if (!f->plOperands.empty()) plincomb(*L, recs);
-  else if (!f->daOperands.empty()) tensorDotAdd(*L, recs);
+  else if (f->fu.form != FusedForm::None)
+    switch (f->fu.form) {
+      case FusedForm::TensorDot: case FusedForm::DotAdd: tensorDotAdd(*L, recs); break;
+      case FusedForm::Square: tensorSquare(*L, recs); break;
+      case FusedForm::Lincomb: case FusedForm::CLincomb: lincomb(*L, recs); break;
+      case FusedForm::LincombMulti: lincombMulti(*L, recs); break;
+      case FusedForm::MulAdd: tensorMulAdd(*L, recs); break;
+      case FusedForm::ReIm: reim(*L, recs); break;
+      case FusedForm::PLincomb: plincomb(*L, recs); break;
+      case FusedForm::None: break;
+    }
   else if (f->fusedTensor) tensor(*L, recs);
   else if (f->fusedSubScale) nttSubScale(*L, recs);
   else if (f->ops == NTT && f->passthrough) copy(*L, recs);
@@ -1203,9 +1182,9 @@ void Arch::buildLaunches() {
   assignDepths(parts, fuse);
   // (only the plan that holds a square's tensor record which pass (5q) did not take: fuse_square = 0.  Every other plan keeps the plain
   // level-by-level order it is pinned to, launch by launch: tests/golden/plan_fingerprints.json)
-  const bool plainSquare = std::any_of(parts.begin(), parts.end(), [](const Part &p) { return p.ins[0]->squareHead && p.ins[0]->fusedTensor && p.ins[0]->sqOperands.empty(); });
+  const bool plainSquare = std::any_of(parts.begin(), parts.end(), [](const Part &p) { return p.ins[0]->mark == FusedForm::Square && p.ins[0]->fusedTensor && p.ins[0]->fu.form == FusedForm::None; });
   // (... and the plan that holds a marked product's tensor record which pass (5m) did not take: fuse_muladd = 0)
-  const bool plainMuladd = std::any_of(parts.begin(), parts.end(), [](const Part &p) { return p.ins[0]->muladdHead && p.ins[0]->fusedTensor && p.ins[0]->maOperands.empty(); });
+  const bool plainMuladd = std::any_of(parts.begin(), parts.end(), [](const Part &p) { return p.ins[0]->mark == FusedForm::MulAdd && p.ins[0]->fusedTensor && p.ins[0]->fu.form == FusedForm::None; });
   if (fuse && world_ == 1 && (plainSquare || plainMuladd)) joinEarlierGroups(parts);
   LaunchBuilder b(*this);
   // multi-GPU: who holds each limb-poly.  Inputs: by the modulus they were filled for; everything else: by the modulus of the

@@ -506,6 +506,110 @@ void OperationBase::setConstants(const std::string &name, const uint64_t *values
   for (uint32_t j = 0; j < n; ++j)
     for (Instruction *i : cs->second.records[j]) i->constant = cs->second.negated && values[j] ? arch->modulus(j) - values[j] : values[j];
 }
+static uint64_t synthWord0(uint64_t stream, uint64_t q) {   // word 0 of a limb of the synthetic stream (hm_synth / ho_fill_uniform at x = 0)
+  uint64_t z = stream * 0xD1342543DE82EF95ull + 0x632BE59BD9B4E019ull;
+  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
+  z ^= z >> 27; z *= 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  return (uint64_t)(((unsigned __int128)z * q) >> 64);
+}
+// ---- what the builders of the fused element-wise ops share (HREIM, HDOT .. HDOTADD)
+void OperationBase::refuseSimAndSharded(const std::string &op, const std::string &why) const {
+  if (arch->backend() == Arch::BACKEND_SIM) throw std::runtime_error(op + ": backend = sim has no such op (" + why + ")");
+  if (arch->world() > 1) throw std::runtime_error(op + ": world > 1 is not supported (the sharded plan is not built)");
+}
+bool OperationBase::flag(const std::string &op, const char *key, uint32_t dflt) const {
+  const uint32_t v = config->getValueOr(key, dflt);
+  if (v > 1) throw std::runtime_error(op + ": " + key + " = " + S(v) + ", must be 0 or 1");
+  return v == 1;
+}
+uint32_t OperationBase::countKey(const std::string &op, const char *key, uint32_t dflt, uint32_t lo, uint32_t hi) const {
+  const uint32_t v = config->getValueOr(key, dflt);
+  if (v < lo || v > hi) throw std::runtime_error(op + ": " + key + " = " + S(v) + ", must be in [" + S(lo) + ", " + S(hi) + "]");
+  return v;
+}
+std::vector<uint64_t> OperationBase::synth(uint64_t stream, bool nonZero, bool negated) const {
+  std::vector<uint64_t> v;
+  for (uint32_t j = 0; j < level_; ++j) {
+    const uint64_t w = synthWord0(stream + j, arch->modulus(j));
+    v.push_back(nonZero && w == 0 ? 1 : negated && w ? arch->modulus(j) - w : w);
+  }
+  return v;
+}
+void OperationBase::keep(const std::string &name, const std::vector<INSGROUP> &recs, bool nonZero, bool negated) {
+  ConstantStage &cs = constantStages[name];
+  cs.enabled = true;
+  cs.nonZero = nonZero;
+  cs.negated = negated;
+  cs.records.resize(level_);
+  for (uint32_t j = 0; j < level_; ++j) cs.records[j].push_back(recs[j][0]);
+}
+Limbs OperationBase::eweStage(const std::string &key, ewe_opcode op, const std::string &buffer, const Limbs &a, const Limbs *c,
+                              const std::vector<uint64_t> &constants, const std::vector<AddrType> &b) {
+  PerLimb s{label + "_" + key + "_Level(", ")", range(0, level_), alloc(buffer, level_)};
+  s.a = a.addr;
+  s.b = b;
+  if (!a.from.empty()) s.after.push_back(&a.from);
+  if (c) {
+    s.c = c->addr;
+    if (!c->from.empty()) s.after.push_back(&c->from);
+  }
+  s.constants = constants;
+  Limbs out{s.out, eweLimbs(&insgener, op, s)};
+  driver.dispatchInstructions(key, out.from);
+  return out;
+}
+std::array<Limbs, 3> OperationBase::tensorProduct(const TensorCompute &tcm, FusedForm mark) {
+  for (const INSGROUP &g : tcm.getInsMap().at("TensorCompute_INS_D1")) g[0]->mark = mark;
+  std::array<Limbs, 3> d;
+  for (uint32_t i = 0; i < 3; ++i) d[i] = {tcm.d(i), tcm.getInsMap().at("TensorCompute_INS_D" + S(i))};
+  return d;
+}
+std::array<std::vector<AddrType>, 3> OperationBase::addrs(const std::array<Limbs, 3> &d) { return {d[0].addr, d[1].addr, d[2].addr}; }
+void OperationBase::scaleTriple(std::array<Limbs, 3> &d, const std::string &key, const std::string &buffer, const std::string &suffix,
+                                const std::string &constants, uint64_t stream) {
+  for (uint32_t i = 0; i < 3; ++i) {
+    d[i] = eweStage(key + "_D" + S(i), EWE_MUL_CONST, buffer + "D" + S(i) + "Scale" + suffix, d[i], nullptr, synth(stream, /*nonZero=*/true));
+    keep(constants, d[i].from, /*nonZero=*/true);
+  }
+}
+void OperationBase::addendTail(std::array<Limbs, 3> &d, const std::string &op, const std::string &buffer, const std::string &sumWord, uint32_t A,
+                               uint32_t firstCt, uint64_t stream, uint64_t step, bool shifted, uint64_t constStream) {
+  for (uint32_t t = 1; t <= A; ++t)
+    for (uint32_t k = 0; k < 2; k++) {
+      const std::string C = "_C" + S(k);
+      const Limbs term = eweStage(op + "_AddScale_(" + S(t) + ")" + C, EWE_MUL_CONST, buffer + "AddScaled(" + S(t) + ")" + C, {component(firstCt + t - 1, k), {}},
+                                  nullptr, synth(stream + step * t));
+      keep("addscale" + S(t), term.from);
+      d[k] = eweStage(op + "_Add_(" + S(t) + ")_D" + S(k), EWE_ADD, buffer + "D" + S(k) + sumWord + "(" + S(t) + ")", d[k], &term);
+    }
+  if (shifted) {
+    d[0] = eweStage(op + "_Const_D0", EWE_ADD_CONST, buffer + "D0Const", d[0], nullptr, synth(constStream));
+    keep("const", d[0].from);
+  }
+}
+Limbs OperationBase::scaledSum(uint32_t k, uint32_t T, bool constHere, const ScaledSumNames &n) {
+  const std::string C = "_C" + S(k);
+  Limbs sum;
+  for (uint32_t t = 1; t <= T; ++t) {
+    const std::string at = n.index + S(t) + ")";
+    const bool lastScale = T == 1 && !constHere, lastAdd = t == T && !constHere;
+    const Limbs scaled = eweStage(n.op + "_Scale_" + at + C, EWE_MUL_CONST, lastScale ? n.result : n.op + "Scaled" + at + C, {component(t - 1, k), {}}, nullptr,
+                                  synth(n.stream + n.step * t));
+    keep(n.scale + S(t), scaled.from);
+    if (t == 1) {
+      for (const INSGROUP &g : scaled.from) g[0]->mark = FusedForm::Lincomb;
+      sum = scaled;
+      continue;
+    }
+    sum = eweStage(n.op + "_Add_" + at + C, EWE_ADD, lastAdd ? n.result : n.op + "Sum" + at + C, sum, &scaled);
+  }
+  if (constHere) {
+    sum = eweStage(n.constKey + C, EWE_ADD_CONST, n.result, sum, nullptr, synth(n.constStream));
+    keep(n.constName, sum.from);
+  }
+  return sum;
+}
 void OperationBase::finishRotation(const std::string &out, const std::vector<AddrType> &rotatedC0, const KeySwitch::Output &ks, const std::string &suffix) {
   PerLimb s{label + "_HROTATEadd" + suffix + "_Level(", ")", range(0, level_), alloc("HROTATEOutput" + suffix + "(1)", level_)};
   s.a = ks[0];
@@ -756,8 +860,7 @@ HROTATE::HROTATE(std::string labelName, uint32_t maxLevel, uint32_t currentLevel
 // launches in front of the tail are HROTATE's, field for field.
 HREIM::HREIM(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch)
     : OperationBase("HREIM", labelName, cfg, _arch, maxLevel, currentLevel, alpha) {
-  if (arch->backend() == Arch::BACKEND_SIM) throw std::runtime_error("hreim: backend = sim has no such op (the reference has no monomial product)");
-  if (arch->world() > 1) throw std::runtime_error("hreim: world > 1 is not supported (the sharded plan is not built)");
+  refuseSimAndSharded("hreim", "the reference has no monomial product");
   makeInputs(1);
   const uint32_t galois = 2 * N - 1;   // the conjugation; the config key galois is not read
   const std::vector<AddrType> rc0 = rotateComponent(0, galois, "").addr, rc1 = rotateComponent(1, galois, "").addr;
@@ -768,21 +871,13 @@ HREIM::HREIM(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, ui
   arch->addUnitFill(unit, range(0, currentLevel));
   for (uint32_t k = 0; k < 2; k++) {
     const std::string C = "_C" + S(k);
-    const std::vector<AddrType> x = component(0, k), y = namedOutputs.at("conj.c" + S(k));
-    PerLimb a{labelName + "_ReIm_Add" + C + "_Level(", ")", range(0, currentLevel), alloc("ReImOutput(" + S(k) + ")", currentLevel)};
-    a.a = x; a.c = y;
-    const std::vector<INSGROUP> sum = eweLimbs(&insgener, EWE_ADD, a);
-    for (const INSGROUP &g : sum) g[0]->reimHead = true;
-    driver.dispatchInstructions("ReIm_Add" + C, sum);
-    PerLimb d{labelName + "_ReIm_Sub" + C + "_Level(", ")", a.mods, alloc("ReImDiff(" + S(k) + ")", currentLevel)};
-    d.a = x; d.c = y;
-    const Limbs diff{d.out, eweLimbs(&insgener, EWE_SUB, d)};
-    driver.dispatchInstructions("ReIm_Sub" + C, diff.from);
-    PerLimb m{labelName + "_ReIm_Mul" + C + "_Level(", ")", a.mods, alloc("ReImOutputIm(" + S(k) + ")", currentLevel)};
-    m.a = diff.addr; m.b = unit; m.after = {&diff.from};
-    driver.dispatchInstructions("ReIm_Mul" + C, eweLimbs(&insgener, EWE_MUL, m));
-    setOutput("out", k, a.out);
-    setOutput("out_im", k, m.out);
+    const Limbs x{component(0, k), {}}, y{namedOutputs.at("conj.c" + S(k)), {}};
+    const Limbs sum = eweStage("ReIm_Add" + C, EWE_ADD, "ReImOutput(" + S(k) + ")", x, &y);
+    for (const INSGROUP &g : sum.from) g[0]->mark = FusedForm::ReIm;
+    const Limbs diff = eweStage("ReIm_Sub" + C, EWE_SUB, "ReImDiff(" + S(k) + ")", x, &y);
+    const Limbs im = eweStage("ReIm_Mul" + C, EWE_MUL, "ReImOutputIm(" + S(k) + ")", diff, nullptr, {}, unit);
+    setOutput("out", k, sum.addr);
+    setOutput("out_im", k, im.addr);
   }
   finishConstruction();
 }
@@ -865,18 +960,14 @@ HLINTRANS::HLINTRANS(std::string labelName, uint32_t maxLevel, uint32_t currentL
 // stages run one launch each; fused, pass (5d) of Arch::fusePasses (Planner.cpp) turns everything in front of the key switch into one launch.
 HDOT::HDOT(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch)
     : OperationBase("HDOT", labelName, cfg, _arch, maxLevel, currentLevel, alpha) {
-  if (arch->backend() == Arch::BACKEND_SIM) throw std::runtime_error("hdot: backend = sim has no such op (the reference has no sum of products)");
-  if (arch->world() > 1) throw std::runtime_error("hdot: world > 1 is not supported (the sharded plan is not built)");
-  const uint32_t T = cfg->getValueOr("terms", 4);
-  if (T < 1 || T > 16) throw std::runtime_error("hdot: terms = " + S(T) + ", must be in [1, 16]");
+  refuseSimAndSharded("hdot", "the reference has no sum of products");
+  const uint32_t T = countKey("hdot", "terms", 4, 1, 16);
   makeInputs(2 * T);
   auto name = [&](uint32_t i, uint32_t pair) { return "DotD" + S(i) + "Out" + (pair < T ? "_temp(" + S(pair) + ")" : ""); };   // pair: 1-based
 
   TensorCompute tcm(labelName, currentLevel, &cts[0], &cts[1], &Datapool, &DataInsMap, &insgener, addrManager.get(), "Dot", T > 1 ? "_temp(1)" : "");
-  for (const INSGROUP &g : tcm.getInsMap().at("TensorCompute_INS_D1")) g[0]->sumHead = true;
+  std::array<Limbs, 3> d = tensorProduct(tcm, FusedForm::TensorDot);
   dispatch(tcm.getInsMap());
-  std::array<Limbs, 3> d;
-  for (uint32_t i = 0; i < 3; ++i) d[i] = {tcm.d(i), tcm.getInsMap().at("TensorCompute_INS_D" + S(i))};
   for (uint32_t p = 2; p <= T; ++p) {
     const std::vector<AddrType> c00 = component(2 * p - 2, 0), c01 = component(2 * p - 2, 1), c10 = component(2 * p - 1, 0), c11 = component(2 * p - 1, 1);
     const std::string at = "_Pair(" + S(p) + ")_Level(";
@@ -900,7 +991,7 @@ HDOT::HDOT(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint
     d[2] = emit("Dot_D2", EWE_MAC_ADD, s2);
   }
 
-  relinearizeAndRescale({d[0].addr, d[1].addr, d[2].addr});   // HMULT's tail, on the sums
+  relinearizeAndRescale(addrs(d));   // HMULT's tail, on the sums
   finishConstruction();
 }
 
@@ -909,54 +1000,23 @@ HDOT::HDOT(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint
 // stages (s on d0, d1, d2: linear, so it acts in front of the key switch), sq_const = 1 one ADD_CONST stage on d0 (the constant polynomial k in
 // evaluation form, where an FHE library adds it, at scale Delta^2).  Then HMULT's tail, stage for stage.  Unfused, the stages run one launch each;
 // fused, pass (5q) of Arch::fusePasses (Planner.cpp) turns everything in front of the key switch into one launch that reads ct1 once.
-static uint64_t synthWord0(uint64_t stream, uint64_t q) {   // word 0 of a limb of the synthetic stream (hm_synth / ho_fill_uniform at x = 0)
-  uint64_t z = stream * 0xD1342543DE82EF95ull + 0x632BE59BD9B4E019ull;
-  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-  z ^= z >> 27; z *= 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return (uint64_t)(((unsigned __int128)z * q) >> 64);
-}
 HSQUARE::HSQUARE(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch)
     : OperationBase("HSQUARE", labelName, cfg, _arch, maxLevel, currentLevel, alpha) {
-  if (arch->backend() == Arch::BACKEND_SIM) throw std::runtime_error("hsquare: backend = sim has no such op (the reference has no square)");
-  if (arch->world() > 1) throw std::runtime_error("hsquare: world > 1 is not supported (the sharded plan is not built)");
-  auto flag = [&](const char *key) {
-    const uint32_t v = cfg->getValueOr(key, 0);
-    if (v > 1) throw std::runtime_error(std::string("hsquare: ") + key + " = " + S(v) + ", must be 0 or 1");
-    return v == 1;
-  };
-  const bool scaled = flag("sq_scale"), shifted = flag("sq_const");
+  refuseSimAndSharded("hsquare", "the reference has no square");
+  const bool scaled = flag("hsquare", "sq_scale"), shifted = flag("hsquare", "sq_const");
   makeInputs(1);
 
   TensorCompute tcm(labelName, currentLevel, &cts[0], &cts[0], &Datapool, &DataInsMap, &insgener, addrManager.get(), "Sq");
-  for (const INSGROUP &g : tcm.getInsMap().at("TensorCompute_INS_D1")) g[0]->squareHead = true;
+  std::array<Limbs, 3> d = tensorProduct(tcm, FusedForm::Square);
   dispatch(tcm.getInsMap());
-  std::array<Limbs, 3> d;
-  for (uint32_t i = 0; i < 3; ++i) d[i] = {tcm.d(i), tcm.getInsMap().at("TensorCompute_INS_D" + S(i))};
-  // a constant stage on polynomial i: one record per limb, kept by name for setConstants
-  auto constantStage = [&](const std::string &name, uint32_t i, ewe_opcode op, const std::string &tag, uint64_t stream, bool nonZero) {
-    ConstantStage &cs = constantStages[name];
-    cs.enabled = true;
-    cs.nonZero = nonZero;
-    cs.records.resize(currentLevel);
-    PerLimb s{labelName + "_Square_" + tag + "_D" + S(i) + "_Level(", ")", range(0, currentLevel), alloc("SqD" + S(i) + tag, currentLevel)};
-    s.a = d[i].addr;
-    const std::vector<INSGROUP> before = d[i].from;
-    s.after = {&before};
-    for (uint32_t j = 0; j < currentLevel; ++j) {
-      const uint64_t v = synthWord0(stream + j, arch->modulus(j));
-      s.constants.push_back(nonZero && v == 0 ? 1 : v);
-    }
-    d[i] = {s.out, eweLimbs(&insgener, op, s)};
-    driver.dispatchInstructions("Square_" + tag + "_D" + S(i), d[i].from);
-    for (uint32_t j = 0; j < currentLevel; ++j) cs.records[j].push_back(d[i].from[j][0]);
-  };
   constantStages["scale"].key = "sq_scale";
   constantStages["const"].key = "sq_const";
-  if (scaled)
-    for (uint32_t i = 0; i < 3; ++i) constantStage("scale", i, EWE_MUL_CONST, "Scale", seed + 6000, /*nonZero=*/true);
-  if (shifted) constantStage("const", 0, EWE_ADD_CONST, "Const", seed + 6100, /*nonZero=*/false);
-  relinearizeAndRescale({d[0].addr, d[1].addr, d[2].addr});
+  if (scaled) scaleTriple(d, "Square_Scale", "Sq", "", "scale", seed + 6000);
+  if (shifted) {
+    d[0] = eweStage("Square_Const_D0", EWE_ADD_CONST, "SqD0Const", d[0], nullptr, synth(seed + 6100));
+    keep("const", d[0].from);
+  }
+  relinearizeAndRescale(addrs(d));
   finishConstruction();
 }
 
@@ -966,65 +1026,14 @@ HSQUARE::HSQUARE(std::string labelName, uint32_t maxLevel, uint32_t currentLevel
 // run as element-wise launches; fused, pass (5l) of Arch::fusePasses (Planner.cpp) turns each limb's chain into one record of ONE launch.
 HLINCOMB::HLINCOMB(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch)
     : OperationBase("HLINCOMB", labelName, cfg, _arch, maxLevel, currentLevel, alpha) {
-  if (arch->backend() == Arch::BACKEND_SIM) throw std::runtime_error("hlincomb: backend = sim has no such op (the reference has no scalar product)");
-  if (arch->world() > 1) throw std::runtime_error("hlincomb: world > 1 is not supported (the sharded plan is not built)");
-  const uint32_t T = cfg->getValueOr("terms", 4);
-  if (T < 1 || T > 16) throw std::runtime_error("hlincomb: terms = " + S(T) + ", must be in [1, 16]");
-  const uint32_t lc = cfg->getValueOr("lc_const", 0);
-  if (lc > 1) throw std::runtime_error("hlincomb: lc_const = " + S(lc) + ", must be 0 or 1");
-  const bool shifted = lc == 1, rescale = rescaleKey("hlincomb");
+  refuseSimAndSharded("hlincomb", "the reference has no scalar product");
+  const uint32_t T = countKey("hlincomb", "terms", 4, 1, 16);
+  const bool shifted = flag("hlincomb", "lc_const"), rescale = rescaleKey("hlincomb");
   makeInputs(T);
   constantStages["const"].key = "lc_const";
-  // the records of limb j of a constant stage, kept by name for setConstants; both components share the scalars
-  auto keep = [&](const std::string &name, const std::vector<INSGROUP> &recs) {
-    ConstantStage &cs = constantStages[name];
-    cs.enabled = true;
-    cs.records.resize(currentLevel);
-    for (uint32_t j = 0; j < currentLevel; ++j) cs.records[j].push_back(recs[j][0]);
-  };
-  auto synth = [&](uint64_t stream) {
-    std::vector<uint64_t> v;
-    for (uint32_t j = 0; j < currentLevel; ++j) v.push_back(synthWord0(stream + j, arch->modulus(j)));
-    return v;
-  };
-  std::array<std::vector<AddrType>, 2> out;
-  for (uint32_t k = 0; k < 2; k++) {
-    const std::string C = "_C" + S(k);
-    const bool constHere = shifted && k == 0;
-    Limbs sum;
-    for (uint32_t t = 1; t <= T; ++t) {
-      const bool lastScale = T == 1 && !constHere;
-      PerLimb m{labelName + "_LinComb_Scale_(" + S(t) + ")" + C + "_Level(", ")", range(0, currentLevel),
-                alloc(lastScale ? "LinCombOutput(" + S(k) + ")" : "LinCombScaled(" + S(t) + ")" + C, currentLevel)};
-      m.a = component(t - 1, k);
-      m.constants = synth(seed + 6200 + 100ull * t);
-      const Limbs scaled{m.out, eweLimbs(&insgener, EWE_MUL_CONST, m)};
-      driver.dispatchInstructions("LinComb_Scale_(" + S(t) + ")" + C, scaled.from);
-      keep("scale" + S(t), scaled.from);
-      if (t == 1) {
-        for (const INSGROUP &g : scaled.from) g[0]->lincombHead = true;
-        sum = scaled;
-        continue;
-      }
-      const bool lastAdd = t == T && !constHere;
-      PerLimb a{labelName + "_LinComb_Add_(" + S(t) + ")" + C + "_Level(", ")", m.mods,
-                alloc(lastAdd ? "LinCombOutput(" + S(k) + ")" : "LinCombSum(" + S(t) + ")" + C, currentLevel)};
-      const Limbs before = sum;
-      a.a = before.addr; a.c = scaled.addr; a.after = {&before.from, &scaled.from};
-      sum = {a.out, eweLimbs(&insgener, EWE_ADD, a)};
-      driver.dispatchInstructions("LinComb_Add_(" + S(t) + ")" + C, sum.from);
-    }
-    if (constHere) {
-      PerLimb c{labelName + "_LinComb_Const" + C + "_Level(", ")", range(0, currentLevel), alloc("LinCombOutput(" + S(k) + ")", currentLevel)};
-      const Limbs before = sum;
-      c.a = before.addr; c.after = {&before.from};
-      c.constants = synth(seed + 6290);
-      sum = {c.out, eweLimbs(&insgener, EWE_ADD_CONST, c)};
-      driver.dispatchInstructions("LinComb_Const" + C, sum.from);
-      keep("const", sum.from);
-    }
-    out[k] = sum.addr;
-  }
+  std::array<std::vector<AddrType>, 2> out;   // both components share the scalars
+  for (uint32_t k = 0; k < 2; k++)
+    out[k] = scaledSum(k, T, shifted && k == 0, {"LinComb", "(", "LinCombOutput(" + S(k) + ")", "LinComb_Const", "scale", "const", seed + 6200, 100, seed + 6290}).addr;
   if (rescale) setRescaledOutput("out", out);
   else for (uint32_t k = 0; k < 2; k++) setOutput("out", k, out[k]);
   finishConstruction();
@@ -1038,72 +1047,20 @@ HLINCOMB::HLINCOMB(std::string labelName, uint32_t maxLevel, uint32_t currentLev
 // into one record of ONE hm_lincomb_multi launch (Planner.cpp); fuse_mlincomb = 0 leaves them to (5l)'s launch.
 HMLINCOMB::HMLINCOMB(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch)
     : OperationBase("HMLINCOMB", labelName, cfg, _arch, maxLevel, currentLevel, alpha) {
-  if (arch->backend() == Arch::BACKEND_SIM) throw std::runtime_error("hmlincomb: backend = sim has no such op (the reference has no scalar product)");
-  if (arch->world() > 1) throw std::runtime_error("hmlincomb: world > 1 is not supported (the sharded plan is not built)");
-  const uint32_t T = cfg->getValueOr("terms", 4);
-  if (T < 1 || T > 16) throw std::runtime_error("hmlincomb: terms = " + S(T) + ", must be in [1, 16]");
-  const uint32_t M = cfg->getValueOr("outputs", 4);
-  if (M < 1 || M > 16) throw std::runtime_error("hmlincomb: outputs = " + S(M) + ", must be in [1, 16]");
-  const uint32_t mc = cfg->getValueOr("ml_const", 0);
-  if (mc > 1) throw std::runtime_error("hmlincomb: ml_const = " + S(mc) + ", must be 0 or 1");
-  const uint32_t fm = cfg->getValueOr("fuse_mlincomb", 1);
-  if (fm > 1) throw std::runtime_error("hmlincomb: fuse_mlincomb = " + S(fm) + ", must be 0 or 1");
-  const bool shifted = mc == 1, rescale = rescaleKey("hmlincomb");
+  refuseSimAndSharded("hmlincomb", "the reference has no scalar product");
+  const uint32_t T = countKey("hmlincomb", "terms", 4, 1, 16), M = countKey("hmlincomb", "outputs", 4, 1, 16);
+  const bool shifted = flag("hmlincomb", "ml_const");
+  flag("hmlincomb", "fuse_mlincomb", 1);
+  const bool rescale = rescaleKey("hmlincomb");
   if (rescale && currentLevel < 2) throw std::runtime_error("hmlincomb: Rescale needs at least two limbs");
   makeInputs(T);
-  // the records of limb j of a constant stage, kept by name for setConstants; both components share the scalars
-  auto keep = [&](const std::string &name, const std::vector<INSGROUP> &recs) {
-    ConstantStage &cs = constantStages[name];
-    cs.enabled = true;
-    cs.records.resize(currentLevel);
-    for (uint32_t j = 0; j < currentLevel; ++j) cs.records[j].push_back(recs[j][0]);
-  };
-  auto synth = [&](uint64_t stream) {
-    std::vector<uint64_t> v;
-    for (uint32_t j = 0; j < currentLevel; ++j) v.push_back(synthWord0(stream + j, arch->modulus(j)));
-    return v;
-  };
   std::vector<std::array<std::vector<AddrType>, 2>> outs(M);
   for (uint32_t m = 1; m <= M; ++m) {
     constantStages["const" + S(m)].key = "ml_const";
     const uint64_t streams = seed + 8000 + 1000ull * m;
-    for (uint32_t k = 0; k < 2; k++) {
-      const std::string C = "_C" + S(k), result = "MLinCombOutput(" + S(m) + "," + S(k) + ")";
-      const bool constHere = shifted && k == 0;
-      Limbs sum;
-      for (uint32_t t = 1; t <= T; ++t) {
-        const std::string mt = "(" + S(m) + "," + S(t) + ")";
-        const bool lastScale = T == 1 && !constHere;
-        PerLimb s{labelName + "_MLinComb_Scale_" + mt + C + "_Level(", ")", range(0, currentLevel),
-                  alloc(lastScale ? result : "MLinCombScaled" + mt + C, currentLevel)};
-        s.a = component(t - 1, k);
-        s.constants = synth(streams + 100 + 50ull * t);
-        const Limbs scaled{s.out, eweLimbs(&insgener, EWE_MUL_CONST, s)};
-        driver.dispatchInstructions("MLinComb_Scale_" + mt + C, scaled.from);
-        keep("scale" + S(m) + "_" + S(t), scaled.from);
-        if (t == 1) {
-          for (const INSGROUP &g : scaled.from) g[0]->lincombHead = true;
-          sum = scaled;
-          continue;
-        }
-        const bool lastAdd = t == T && !constHere;
-        PerLimb a{labelName + "_MLinComb_Add_" + mt + C + "_Level(", ")", s.mods, alloc(lastAdd ? result : "MLinCombSum" + mt + C, currentLevel)};
-        const Limbs before = sum;
-        a.a = before.addr; a.c = scaled.addr; a.after = {&before.from, &scaled.from};
-        sum = {a.out, eweLimbs(&insgener, EWE_ADD, a)};
-        driver.dispatchInstructions("MLinComb_Add_" + mt + C, sum.from);
-      }
-      if (constHere) {
-        PerLimb c{labelName + "_MLinComb_Const_(" + S(m) + ")" + C + "_Level(", ")", range(0, currentLevel), alloc(result, currentLevel)};
-        const Limbs before = sum;
-        c.a = before.addr; c.after = {&before.from};
-        c.constants = synth(streams + 950);
-        sum = {c.out, eweLimbs(&insgener, EWE_ADD_CONST, c)};
-        driver.dispatchInstructions("MLinComb_Const_(" + S(m) + ")" + C, sum.from);
-        keep("const" + S(m), sum.from);
-      }
-      outs[m - 1][k] = sum.addr;
-    }
+    for (uint32_t k = 0; k < 2; k++)
+      outs[m - 1][k] = scaledSum(k, T, shifted && k == 0, {"MLinComb", "(" + S(m) + ",", "MLinCombOutput(" + S(m) + "," + S(k) + ")", "MLinComb_Const_(" + S(m) + ")",
+                                                           "scale" + S(m) + "_", "const" + S(m), streams + 100, 50, streams + 950}).addr;
   }
   for (uint32_t m = 1; m <= M; ++m)
     for (uint32_t k = 0; k < 2; k++) {
@@ -1128,87 +1085,35 @@ HMLINCOMB::HMLINCOMB(std::string labelName, uint32_t maxLevel, uint32_t currentL
 // into one record of ONE launch, which does not read `unit`.
 HCLINCOMB::HCLINCOMB(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch)
     : OperationBase("HCLINCOMB", labelName, cfg, _arch, maxLevel, currentLevel, alpha) {
-  if (arch->backend() == Arch::BACKEND_SIM) throw std::runtime_error("hclincomb: backend = sim has no such op (the reference has no monomial product)");
-  if (arch->world() > 1) throw std::runtime_error("hclincomb: world > 1 is not supported (the sharded plan is not built)");
-  const uint32_t T = cfg->getValueOr("terms", 4);
-  if (T < 1 || T > 16) throw std::runtime_error("hclincomb: terms = " + S(T) + ", must be in [1, 16]");
-  const uint32_t cl = cfg->getValueOr("cl_const", 0);
-  if (cl > 1) throw std::runtime_error("hclincomb: cl_const = " + S(cl) + ", must be 0 or 1");
-  const bool shifted = cl == 1, rescale = rescaleKey("hclincomb");
+  refuseSimAndSharded("hclincomb", "the reference has no monomial product");
+  const uint32_t T = countKey("hclincomb", "terms", 4, 1, 16);
+  const bool shifted = flag("hclincomb", "cl_const"), rescale = rescaleKey("hclincomb");
   makeInputs(T);
   constantStages["const"].key = "cl_const";
   const std::vector<AddrType> unit = alloc("unit", currentLevel);
   arch->addUnitFill(unit, range(0, currentLevel));
-  // the records of limb j of a constant stage, kept by name for setConstants; both components share the scalars.  negated: the stage carries
-  // q - value (the monomial part: the stored factor is -X^(N/2))
-  auto keep = [&](const std::string &name, const std::vector<INSGROUP> &recs, bool negated) {
-    ConstantStage &cs = constantStages[name];
-    cs.enabled = true;
-    cs.negated = negated;
-    cs.records.resize(currentLevel);
-    for (uint32_t j = 0; j < currentLevel; ++j) cs.records[j].push_back(recs[j][0]);
-  };
-  auto synth = [&](uint64_t stream, bool negated) {
-    std::vector<uint64_t> v;
-    for (uint32_t j = 0; j < currentLevel; ++j) {
-      const uint64_t x = synthWord0(stream + j, arch->modulus(j));
-      v.push_back(negated && x ? arch->modulus(j) - x : x);
-    }
-    return v;
-  };
-  std::array<std::vector<AddrType>, 2> out;
+  std::array<std::vector<AddrType>, 2> out;   // both components share the scalars
   for (uint32_t k = 0; k < 2; k++) {
-    const std::string C = "_C" + S(k);
+    const std::string C = "_C" + S(k), result = "CLinCombOutput(" + S(k) + ")";
     const bool constHere = shifted && k == 0;
     Limbs sum;
     for (uint32_t t = 1; t <= T; ++t) {
       const std::string at = "_(" + S(t) + ")" + C;
-      const std::vector<AddrType> x = component(t - 1, k);
-      auto emit = [&](const std::string &stage, ewe_opcode op, const PerLimb &s) {
-        Limbs o{s.out, eweLimbs(&insgener, op, s)};
-        driver.dispatchInstructions("CLinComb_" + stage + at, o.from);
-        return o;
-      };
-      auto stageOf = [&](const std::string &stage, const std::string &buffer) {
-        return PerLimb{labelName + "_CLinComb_" + stage + at + "_Level(", ")", range(0, currentLevel), alloc(buffer, currentLevel)};
-      };
-      PerLimb re = stageOf("Re", "CLinCombRe" + at);
-      re.a = x;
-      re.constants = synth(seed + 6450 + 100ull * t, false);
-      const Limbs real = emit("Re", EWE_MUL_CONST, re);
-      keep("scale" + S(t), real.from, false);
+      const Limbs x{component(t - 1, k), {}};
+      const Limbs real = eweStage("CLinComb_Re" + at, EWE_MUL_CONST, "CLinCombRe" + at, x, nullptr, synth(seed + 6450 + 100ull * t));
+      keep("scale" + S(t), real.from);
       if (t == 1)
-        for (const INSGROUP &g : real.from) g[0]->clincombHead = true;
-      PerLimb ro = stageOf("Rot", "CLinCombRot" + at);
-      ro.a = x; ro.b = unit;
-      const Limbs rot = emit("Rot", EWE_MUL, ro);
-      PerLimb im = stageOf("Im", "CLinCombIm" + at);
-      im.a = rot.addr; im.after = {&rot.from};
-      im.constants = synth(seed + 8150 + 100ull * t, true);
-      const Limbs imag = emit("Im", EWE_MUL_CONST, im);
-      keep("scale_im" + S(t), imag.from, true);
-      const bool lastTerm = T == 1 && !constHere;
-      PerLimb te = stageOf("Term", lastTerm ? "CLinCombOutput(" + S(k) + ")" : "CLinCombTerm" + at);
-      te.a = real.addr; te.c = imag.addr; te.after = {&real.from, &imag.from};
-      const Limbs term = emit("Term", EWE_ADD, te);
-      if (t == 1) {
-        sum = term;
-        continue;
-      }
-      const bool lastAdd = t == T && !constHere;
-      PerLimb a = stageOf("Add", lastAdd ? "CLinCombOutput(" + S(k) + ")" : "CLinCombSum" + at);
-      const Limbs before = sum;
-      a.a = before.addr; a.c = term.addr; a.after = {&before.from, &term.from};
-      sum = emit("Add", EWE_ADD, a);
+        for (const INSGROUP &g : real.from) g[0]->mark = FusedForm::CLincomb;
+      const Limbs rot = eweStage("CLinComb_Rot" + at, EWE_MUL, "CLinCombRot" + at, x, nullptr, {}, unit);
+      // the monomial part carries q - value: the stored factor is -X^(N/2)
+      const Limbs imag = eweStage("CLinComb_Im" + at, EWE_MUL_CONST, "CLinCombIm" + at, rot, nullptr, synth(seed + 8150 + 100ull * t, false, /*negated=*/true));
+      keep("scale_im" + S(t), imag.from, false, /*negated=*/true);
+      const Limbs term = eweStage("CLinComb_Term" + at, EWE_ADD, T == 1 && !constHere ? result : "CLinCombTerm" + at, real, &imag);
+      sum = t == 1 ? term : eweStage("CLinComb_Add" + at, EWE_ADD, t == T && !constHere ? result : "CLinCombSum" + at, sum, &term);
     }
     if (constHere) {
-      PerLimb c{labelName + "_CLinComb_Const" + C + "_Level(", ")", range(0, currentLevel), alloc("CLinCombOutput(" + S(k) + ")", currentLevel)};
-      const Limbs before = sum;
-      c.a = before.addr; c.after = {&before.from};
-      c.constants = synth(seed + 9850, false);
-      sum = {c.out, eweLimbs(&insgener, EWE_ADD_CONST, c)};
-      driver.dispatchInstructions("CLinComb_Const" + C, sum.from);
-      keep("const", sum.from, false);
+      sum = eweStage("CLinComb_Const" + C, EWE_ADD_CONST, result, sum, nullptr, synth(seed + 9850));
+      keep("const", sum.from);
     }
     out[k] = sum.addr;
   }
@@ -1225,46 +1130,29 @@ HCLINCOMB::HCLINCOMB(std::string labelName, uint32_t maxLevel, uint32_t currentL
 // (Planner.cpp) turns the two chains of a limb into one record of ONE launch.
 HPLINCOMB::HPLINCOMB(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch)
     : OperationBase("HPLINCOMB", labelName, cfg, _arch, maxLevel, currentLevel, alpha) {
-  if (arch->backend() == Arch::BACKEND_SIM) throw std::runtime_error("hplincomb: backend = sim has no such op (the reference sums no plaintext products)");
-  if (arch->world() > 1) throw std::runtime_error("hplincomb: world > 1 is not supported (the sharded plan is not built)");
-  const uint32_t T = cfg->getValueOr("terms", 4);
-  if (T < 1 || T > 16) throw std::runtime_error("hplincomb: terms = " + S(T) + ", must be in [1, 16]");
-  const uint32_t pl = cfg->getValueOr("pl_addend", 0);
-  if (pl > 1) throw std::runtime_error("hplincomb: pl_addend = " + S(pl) + ", must be 0 or 1");
-  const bool addend = pl == 1, rescale = rescaleKey("hplincomb");
+  refuseSimAndSharded("hplincomb", "the reference sums no plaintext products");
+  const uint32_t T = countKey("hplincomb", "terms", 4, 1, 16);
+  const bool addend = flag("hplincomb", "pl_addend"), rescale = rescaleKey("hplincomb");
   NamedStreams pts;
   for (uint32_t t = 1; t <= T; ++t) pts.push_back({"pt" + S(t), 4000 + 100000ull * t});
   if (addend) pts.push_back({"pt0", 4000 + 100000ull * 17});
   makeInputs(T, /*plaintext=*/false, /*extPlaintexts=*/0, NamedStreams{}, pts);
   std::array<std::vector<AddrType>, 2> out;
   for (uint32_t k = 0; k < 2; k++) {
-    const std::string C = "_C" + S(k);
+    const std::string C = "_C" + S(k), result = "PLinCombOutput(" + S(k) + ")";
     const bool addendHere = addend && k == 0;
     Limbs sum;
     for (uint32_t t = 1; t <= T; ++t) {
       const std::string stage = std::string(t == 1 ? "PLinComb_Mul_(" : "PLinComb_Mac_(") + S(t) + ")" + C;
-      const bool last = t == T && !addendHere;
-      PerLimb s{labelName + "_" + stage + "_Level(", ")", range(0, currentLevel),
-                alloc(last ? "PLinCombOutput(" + S(k) + ")" : "PLinCombSum(" + S(t) + ")" + C, currentLevel)};
-      s.a = component(t - 1, k);
-      s.b = namedInputs.at("pt" + S(t));
-      const Limbs before = sum;
-      if (t > 1) {
-        s.c = before.addr;
-        s.after = {&before.from};
-      }
-      sum = {s.out, eweLimbs(&insgener, t == 1 ? EWE_MUL : EWE_MAC_ADD, s)};
-      driver.dispatchInstructions(stage, sum.from);
+      sum = eweStage(stage, t == 1 ? EWE_MUL : EWE_MAC_ADD, t == T && !addendHere ? result : "PLinCombSum(" + S(t) + ")" + C, {component(t - 1, k), {}},
+                     t == 1 ? nullptr : &sum, {}, namedInputs.at("pt" + S(t)));
       if (t == 1)
-        for (const INSGROUP &g : sum.from) g[0]->plincombHead = true;
+        for (const INSGROUP &g : sum.from) g[0]->mark = FusedForm::PLincomb;
     }
     if (addendHere) {
-      PerLimb a{labelName + "_PLinComb_Addend" + C + "_Level(", ")", range(0, currentLevel), alloc("PLinCombOutput(" + S(k) + ")", currentLevel)};
-      const Limbs before = sum;
-      a.a = before.addr; a.c = namedInputs.at("pt0"); a.after = {&before.from};
-      sum = {a.out, eweLimbs(&insgener, EWE_ADD, a)};
-      driver.dispatchInstructions("PLinComb_Addend" + C, sum.from);
-      for (const INSGROUP &g : sum.from) g[0]->plincombHead = true;   // the addend belongs to the marked sum
+      const Limbs pt0{namedInputs.at("pt0"), {}};
+      sum = eweStage("PLinComb_Addend" + C, EWE_ADD, result, sum, &pt0);
+      for (const INSGROUP &g : sum.from) g[0]->mark = FusedForm::PLincomb;   // the addend belongs to the marked sum
     }
     out[k] = sum.addr;
   }
@@ -1283,74 +1171,20 @@ HPLINCOMB::HPLINCOMB(std::string labelName, uint32_t maxLevel, uint32_t currentL
 // of the key switch into one launch.
 HMULADD::HMULADD(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch)
     : OperationBase("HMULADD", labelName, cfg, _arch, maxLevel, currentLevel, alpha) {
-  if (arch->backend() == Arch::BACKEND_SIM) throw std::runtime_error("hmuladd: backend = sim has no such op (the reference has no scalar product)");
-  if (arch->world() > 1) throw std::runtime_error("hmuladd: world > 1 is not supported (the sharded plan is not built)");
+  refuseSimAndSharded("hmuladd", "the reference has no scalar product");
   if (currentLevel < 2) throw std::runtime_error("hmuladd: Rescale needs at least two limbs");
-  const uint32_t A = cfg->getValueOr("addends", 1);
-  if (A > HM_TENSOR_MULADD_MAX_ADDENDS) throw std::runtime_error("hmuladd: addends = " + S(A) + ", must be in [0, " + S(HM_TENSOR_MULADD_MAX_ADDENDS) + "]");
-  auto flag = [&](const char *key) {
-    const uint32_t v = cfg->getValueOr(key, 0);
-    if (v > 1) throw std::runtime_error(std::string("hmuladd: ") + key + " = " + S(v) + ", must be 0 or 1");
-    return v == 1;
-  };
-  const bool scaled = flag("ma_scale"), shifted = flag("ma_const");
+  const uint32_t A = countKey("hmuladd", "addends", 1, 0, HM_TENSOR_MULADD_MAX_ADDENDS);
+  const bool scaled = flag("hmuladd", "ma_scale"), shifted = flag("hmuladd", "ma_const");
   makeInputs(2 + A);
 
   TensorCompute tcm(labelName, currentLevel, &cts[0], &cts[1], &Datapool, &DataInsMap, &insgener, addrManager.get(), "Ma");
-  for (const INSGROUP &g : tcm.getInsMap().at("TensorCompute_INS_D1")) g[0]->muladdHead = true;
+  std::array<Limbs, 3> d = tensorProduct(tcm, FusedForm::MulAdd);
   dispatch(tcm.getInsMap());
-  std::array<Limbs, 3> d;
-  for (uint32_t i = 0; i < 3; ++i) d[i] = {tcm.d(i), tcm.getInsMap().at("TensorCompute_INS_D" + S(i))};
-  // the records of limb j of a constant stage, kept by name for setConstants
-  auto keep = [&](const std::string &name, const std::vector<INSGROUP> &recs, bool nonZero) {
-    ConstantStage &cs = constantStages[name];
-    cs.enabled = true;
-    cs.nonZero = nonZero;
-    cs.records.resize(currentLevel);
-    for (uint32_t j = 0; j < currentLevel; ++j) cs.records[j].push_back(recs[j][0]);
-  };
-  auto synth = [&](uint64_t stream, bool nonZero) {
-    std::vector<uint64_t> v;
-    for (uint32_t j = 0; j < currentLevel; ++j) {
-      const uint64_t w = synthWord0(stream + j, arch->modulus(j));
-      v.push_back(nonZero && w == 0 ? 1 : w);
-    }
-    return v;
-  };
-  // one stage on polynomial i of the running d: out = op(d[i], other) with the constants, if any
-  auto stage = [&](uint32_t i, ewe_opcode op, const std::string &key, const std::string &buffer, const Limbs *other, const std::vector<uint64_t> &constants) {
-    PerLimb s{labelName + "_" + key + "_Level(", ")", range(0, currentLevel), alloc(buffer, currentLevel)};
-    const Limbs before = d[i];
-    s.a = before.addr;
-    s.after = {&before.from};
-    if (other) { s.c = other->addr; s.after.push_back(&other->from); }
-    s.constants = constants;
-    d[i] = {s.out, eweLimbs(&insgener, op, s)};
-    driver.dispatchInstructions(key, d[i].from);
-  };
   constantStages["scale"].key = "ma_scale";
   constantStages["const"].key = "ma_const";
-  if (scaled)
-    for (uint32_t i = 0; i < 3; ++i) {
-      stage(i, EWE_MUL_CONST, "MulAdd_Scale_D" + S(i), "MaD" + S(i) + "Scale", nullptr, synth(seed + 6400, /*nonZero=*/true));
-      keep("scale", d[i].from, /*nonZero=*/true);
-    }
-  for (uint32_t t = 1; t <= A; ++t)
-    for (uint32_t k = 0; k < 2; k++) {
-      const std::string C = "_C" + S(k);
-      PerLimb m{labelName + "_MulAdd_AddScale_(" + S(t) + ")" + C + "_Level(", ")", range(0, currentLevel), alloc("MaAddScaled(" + S(t) + ")" + C, currentLevel)};
-      m.a = component(1 + t, k);
-      m.constants = synth(seed + 6400 + 10ull * t, /*nonZero=*/false);
-      const Limbs term{m.out, eweLimbs(&insgener, EWE_MUL_CONST, m)};
-      driver.dispatchInstructions("MulAdd_AddScale_(" + S(t) + ")" + C, term.from);
-      keep("addscale" + S(t), term.from, /*nonZero=*/false);
-      stage(k, EWE_ADD, "MulAdd_Add_(" + S(t) + ")_D" + S(k), "MaD" + S(k) + "Sum(" + S(t) + ")", &term, {});
-    }
-  if (shifted) {
-    stage(0, EWE_ADD_CONST, "MulAdd_Const_D0", "MaD0Const", nullptr, synth(seed + 6490, /*nonZero=*/false));
-    keep("const", d[0].from, /*nonZero=*/false);
-  }
-  relinearizeAndRescale({d[0].addr, d[1].addr, d[2].addr});
+  if (scaled) scaleTriple(d, "MulAdd_Scale", "Ma", "", "scale", seed + 6400);
+  addendTail(d, "MulAdd", "Ma", "Sum", A, /*firstCt=*/2, seed + 6400, 10, shifted, seed + 6490);
+  relinearizeAndRescale(addrs(d));
   finishConstruction();
 }
 
@@ -1365,49 +1199,13 @@ HMULADD::HMULADD(std::string labelName, uint32_t maxLevel, uint32_t currentLevel
 // launch each; fused, pass (5a) of Arch::fusePasses (Planner.cpp) turns everything in front of the key switch into one launch.
 HDOTADD::HDOTADD(std::string labelName, uint32_t maxLevel, uint32_t currentLevel, uint32_t alpha, Config *cfg, Arch *_arch)
     : OperationBase("HDOTADD", labelName, cfg, _arch, maxLevel, currentLevel, alpha) {
-  if (arch->backend() == Arch::BACKEND_SIM) throw std::runtime_error("hdotadd: backend = sim has no such op (the reference has no sum of scaled products)");
-  if (arch->world() > 1) throw std::runtime_error("hdotadd: world > 1 is not supported (the sharded plan is not built)");
+  refuseSimAndSharded("hdotadd", "the reference has no sum of scaled products");
   if (currentLevel < 2) throw std::runtime_error("hdotadd: Rescale needs at least two limbs");
-  const uint32_t T = cfg->getValueOr("terms", 4), A = cfg->getValueOr("addends", 1);
-  if (T < 1 || T > HM_TENSOR_DOTADD_MAX_TERMS) throw std::runtime_error("hdotadd: terms = " + S(T) + ", must be in [1, " + S(HM_TENSOR_DOTADD_MAX_TERMS) + "]");
-  if (A > HM_TENSOR_DOTADD_MAX_ADDENDS) throw std::runtime_error("hdotadd: addends = " + S(A) + ", must be in [0, " + S(HM_TENSOR_DOTADD_MAX_ADDENDS) + "]");
-  auto flag = [&](const char *key, uint32_t dflt) {
-    const uint32_t v = cfg->getValueOr(key, dflt);
-    if (v > 1) throw std::runtime_error(std::string("hdotadd: ") + key + " = " + S(v) + ", must be 0 or 1");
-    return v == 1;
-  };
-  const bool scaled = flag("da_scale", 0), shifted = flag("da_const", 0);
-  flag("fuse_dotadd", 1);
+  const uint32_t T = countKey("hdotadd", "terms", 4, 1, HM_TENSOR_DOTADD_MAX_TERMS), A = countKey("hdotadd", "addends", 1, 0, HM_TENSOR_DOTADD_MAX_ADDENDS);
+  const bool scaled = flag("hdotadd", "da_scale"), shifted = flag("hdotadd", "da_const");
+  flag("hdotadd", "fuse_dotadd", 1);
   makeInputs(2 * T + A);
 
-  // the records of limb j of a constant stage, kept by name for setConstants
-  auto keep = [&](const std::string &name, const std::vector<INSGROUP> &recs, bool nonZero) {
-    ConstantStage &cs = constantStages[name];
-    cs.enabled = true;
-    cs.nonZero = nonZero;
-    cs.records.resize(currentLevel);
-    for (uint32_t j = 0; j < currentLevel; ++j) cs.records[j].push_back(recs[j][0]);
-  };
-  auto synth = [&](uint64_t stream, bool nonZero) {
-    std::vector<uint64_t> v;
-    for (uint32_t j = 0; j < currentLevel; ++j) {
-      const uint64_t w = synthWord0(stream + j, arch->modulus(j));
-      v.push_back(nonZero && w == 0 ? 1 : w);
-    }
-    return v;
-  };
-  // one stage on polynomial i of `d`: out = op(d[i], other) with the constants, if any
-  auto stage = [&](std::array<Limbs, 3> &d, uint32_t i, ewe_opcode op, const std::string &key, const std::string &buffer, const Limbs *other,
-                   const std::vector<uint64_t> &constants) {
-    PerLimb s{labelName + "_" + key + "_Level(", ")", range(0, currentLevel), alloc(buffer, currentLevel)};
-    const Limbs before = d[i];
-    s.a = before.addr;
-    s.after = {&before.from};
-    if (other) { s.c = other->addr; s.after.push_back(&other->from); }
-    s.constants = constants;
-    d[i] = {s.out, eweLimbs(&insgener, op, s)};
-    driver.dispatchInstructions(key, d[i].from);
-  };
   for (uint32_t t = 1; t <= T; ++t) constantStages["scale" + S(t)].key = "da_scale";
   constantStages["const"].key = "da_const";
   std::array<Limbs, 3> d;   // the running sums
@@ -1415,35 +1213,14 @@ HDOTADD::HDOTADD(std::string labelName, uint32_t maxLevel, uint32_t currentLevel
     const std::string P = "(" + S(t) + ")";
     TensorCompute tcm(t == 1 ? labelName : labelName + "_Pair" + P, currentLevel, &cts[2 * t - 2], &cts[2 * t - 1], &Datapool, &DataInsMap, &insgener,
                       addrManager.get(), "Da", "_" + P);
-    if (t == 1)
-      for (const INSGROUP &g : tcm.getInsMap().at("TensorCompute_INS_D1")) g[0]->dotaddHead = true;
+    std::array<Limbs, 3> p = tensorProduct(tcm, t == 1 ? FusedForm::DotAdd : FusedForm::None);
     for (const auto &st : tcm.getInsMap()) driver.dispatchInstructions(t == 1 ? st.first : st.first + "_" + P, st.second);
-    std::array<Limbs, 3> p;
-    for (uint32_t i = 0; i < 3; ++i) p[i] = {tcm.d(i), tcm.getInsMap().at("TensorCompute_INS_D" + S(i))};
-    if (scaled)
-      for (uint32_t i = 0; i < 3; ++i) {
-        stage(p, i, EWE_MUL_CONST, "DotAdd_Scale_" + P + "_D" + S(i), "DaD" + S(i) + "Scale" + P, nullptr, synth(seed + 6050 + 50ull * t, /*nonZero=*/true));
-        keep("scale" + S(t), p[i].from, /*nonZero=*/true);
-      }
+    if (scaled) scaleTriple(p, "DotAdd_Scale_" + P, "Da", P, "scale" + S(t), seed + 6050 + 50ull * t);
     if (t == 1) { d = p; continue; }
-    for (uint32_t i = 0; i < 3; ++i) stage(d, i, EWE_ADD, "DotAdd_Sum_" + P + "_D" + S(i), "DaD" + S(i) + "Sum" + P, &p[i], {});
+    for (uint32_t i = 0; i < 3; ++i) d[i] = eweStage("DotAdd_Sum_" + P + "_D" + S(i), EWE_ADD, "DaD" + S(i) + "Sum" + P, d[i], &p[i]);
   }
-  for (uint32_t r = 1; r <= A; ++r)
-    for (uint32_t k = 0; k < 2; k++) {
-      const std::string C = "_C" + S(k);
-      PerLimb m{labelName + "_DotAdd_AddScale_(" + S(r) + ")" + C + "_Level(", ")", range(0, currentLevel), alloc("DaAddScaled(" + S(r) + ")" + C, currentLevel)};
-      m.a = component(2 * T + r - 1, k);
-      m.constants = synth(seed + 7050 + 50ull * r, /*nonZero=*/false);
-      const Limbs term{m.out, eweLimbs(&insgener, EWE_MUL_CONST, m)};
-      driver.dispatchInstructions("DotAdd_AddScale_(" + S(r) + ")" + C, term.from);
-      keep("addscale" + S(r), term.from, /*nonZero=*/false);
-      stage(d, k, EWE_ADD, "DotAdd_Add_(" + S(r) + ")_D" + S(k), "DaD" + S(k) + "Add(" + S(r) + ")", &term, {});
-    }
-  if (shifted) {
-    stage(d, 0, EWE_ADD_CONST, "DotAdd_Const_D0", "DaD0Const", nullptr, synth(seed + 7900, /*nonZero=*/false));
-    keep("const", d[0].from, /*nonZero=*/false);
-  }
-  relinearizeAndRescale({d[0].addr, d[1].addr, d[2].addr});
+  addendTail(d, "DotAdd", "Da", "Add", A, /*firstCt=*/2 * T, seed + 7050, 50, shifted, seed + 7900);   // the addends and the constant exactly as HMULADD's
+  relinearizeAndRescale(addrs(d));
   finishConstruction();
 }
 

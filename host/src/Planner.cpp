@@ -96,6 +96,104 @@ struct Arch::Planner {
     }
   };
 
+  // ---- what the passes (5d) .. (5a) share: the marked records, the links they follow, and the record that absorbs them
+  // the live records the op builder marked for the pass of `form` (Instruction::mark) and that no pass has taken, in stage order
+  std::vector<Instruction *> markedHeads(FusedForm form) const {
+    std::vector<Instruction *> heads;
+    for (auto &s : st)
+      for (Instruction *i : s.ins)
+        if (live(i) && i->mark == form && i->fu.form == FusedForm::None) heads.push_back(i);
+    return heads;
+  }
+  bool isScaled(Instruction *i, uint32_t mod) const { return i->ops == MULT && i->opcode == EWE_MUL_CONST && i->hasConstant && i->mod_id == mod; }
+  // a tensor record's MAC2 operands are (P, S, R, T) = (c00, c11, c01, c10); the forms list a pair as (c00, c10, c01, c11)
+  static std::vector<AddrType> pairOperands(const Instruction *i) { return {i->operandList[0], i->operandList[3], i->operandList[2], i->operandList[1]}; }
+  typedef std::array<AddrType, 3> Triple;        // d0, d1, d2 of a tensor form
+  typedef std::array<Instruction *, 3> Three;
+  static Triple tensorOutputs(const Instruction *i) { return {i->extraOutputs[0], i->OutputOperand, i->extraOutputs[1]}; }
+  // the MUL_CONST records that are the only readers of the three polynomials `of`, if all three carry one constant
+  bool scalars(Readers &rd, const Triple &of, uint32_t mod, Three &m) const {
+    for (int i = 0; i < 3; ++i) m[i] = soleReader(rd, of[i], EWE_MUL_CONST, mod);
+    return m[0] && m[1] && m[2] && m[0]->hasConstant && m[1]->hasConstant && m[2]->hasConstant && m[0]->constant == m[1]->constant &&
+           m[0]->constant == m[2]->constant;
+  }
+  // the ADD behind `sum` if that is all that reads it, and its other operand.  eitherSide: the sum may be either operand of the ADD ((5l), (5m),
+  // (5a)); otherwise only its operand a ((5c), (5p): their builders emit it there, and the passes have never taken it elsewhere)
+  Instruction *sumLink(Readers &rd, AddrType sum, uint32_t mod, bool eitherSide, AddrType &other) const {
+    Instruction *add = soleReader(rd, sum, EWE_ADD, mod);
+    if (!add) return nullptr;
+    const bool asA = add->operandList[0] == sum;
+    if (!asA && (!eitherSide || add->operandList[2] != sum)) return nullptr;
+    other = asA ? add->operandList[2] : add->operandList[0];
+    return other == sum ? nullptr : add;
+  }
+  // the MUL_CONST record that produces `a`, if `reader` is all that reads `a`.  ((5a) used to ask !fusedTensor as well: only pass (5) sets that,
+  // and only on MAC2 records)
+  Instruction *privateScaled(Readers &rd, AddrType a, Instruction *reader, uint32_t mod) const {
+    Instruction *m = producerOf(a);
+    return m && live(m) && isScaled(m, mod) && onlyReader(rd, a, reader) ? m : nullptr;
+  }
+  // the ADD_CONST record that is the only reader of `sum`
+  Instruction *constTail(Readers &rd, AddrType sum, uint32_t mod) const {
+    Instruction *k = soleReader(rd, sum, EWE_ADD_CONST, mod);
+    return k && k->hasConstant ? k : nullptr;
+  }
+  // the record `c` that absorbs others: it ends up where the last of them stood, with the outputs it is given
+  struct Absorber {
+    Planner &P;
+    Readers &rd;
+    Placement &place;
+    Instruction *c, *last;
+    Absorber(Planner &p, Readers &r, Placement &pl, Instruction *carrier) : P(p), rd(r), place(pl), c(carrier), last(carrier) {}
+    void take(Instruction *i) {
+      P.absorb(c, i);
+      if (place.after(i, last)) last = i;
+    }
+    // the same scalar behind the three polynomials d: their MUL_CONST records go in, d moves behind them
+    bool takeScalars(Triple &d, uint64_t &s) {
+      Three m;
+      if (!P.scalars(rd, d, c->mod_id, m)) return false;
+      s = m[0]->constant;
+      for (int i = 0; i < 3; ++i) { take(m[i]); d[i] = m[i]->OutputOperand; }
+      return true;
+    }
+    // ((5m), (5a)) addend after addend, up to `max`: d0 and d1 each go on through ONE ADD whose other operand is a MUL_CONST record read by nothing
+    // else, both with the same constant u (u x onto d0, u y onto d1).  An addend goes in with both its components or not at all
+    void takeAddends(AddrType &d0, AddrType &d1, uint32_t max) {
+      Fused &f = c->fu;
+      while (f.addends < max) {
+        AddrType x0 = 0, x1 = 0;
+        Instruction *a0 = P.sumLink(rd, d0, c->mod_id, true, x0), *a1 = P.sumLink(rd, d1, c->mod_id, true, x1);
+        Instruction *u0 = a0 ? P.privateScaled(rd, x0, a0, c->mod_id) : nullptr, *u1 = a1 ? P.privateScaled(rd, x1, a1, c->mod_id) : nullptr;
+        if (!u0 || !u1 || u0->constant != u1->constant) break;
+        f.reads.push_back(u0->operandList[0]);
+        f.reads.push_back(u1->operandList[0]);
+        f.scales2.push_back(u0->constant);
+        ++f.addends;
+        for (Instruction *i : {u0, a0, u1, a1}) take(i);
+        d0 = a0->OutputOperand; d1 = a1->OutputOperand;
+      }
+    }
+    // the ADD_CONST behind `sum` goes in, `sum` moves behind it
+    void takeConstant(AddrType &sum) {
+      if (Instruction *k = P.constTail(rd, sum, c->mod_id)) {
+        c->fu.hasConst = true;
+        c->fu.constant = k->constant;
+        take(k);
+        sum = k->OutputOperand;
+      }
+    }
+    // the outputs of the finished record; it is the producer of every one of them.  (The passes with one output, (5l) and (5c), used to re-point
+    // `producer` for that one only: their records have no other write, so this is the same)
+    void finish(AddrType out, const std::vector<AddrType> &extra) {
+      c->OutputOperand = out;
+      c->extraOutputs = extra;
+      for (const Write &w : recordWrites(*c)) P.producer[w.addr] = c;
+      place.moveTo(c, last);   // to where its last link stood
+    }
+    void finish(const Triple &d) { finish(d[1], {d[0], d[2]}); }
+  };
+
   void passThrough();      // 1
   void inttScale();        // 2
   void eweChains();        // 3
@@ -300,7 +398,7 @@ void Arch::Planner::productOperands() {
   }
   auto productFor = [&](AddrType a, Instruction *reader) -> Instruction * {
     Instruction *m = producerOf(a);
-    if (!m || !isMul(m, reader->mod_id) || m->fusedTensor || m->plincombHead || !onlyReader(rd, a, reader)) return nullptr;   // (a one-term hplincomb keeps its own launch: (5p))
+    if (!m || !isMul(m, reader->mod_id) || m->fusedTensor || m->mark == FusedForm::PLincomb || !onlyReader(rd, a, reader)) return nullptr;   // (a one-term hplincomb keeps its own launch: (5p))
     if (producerOf(m->operandList[0]) || producerOf(m->operandList[1])) return nullptr;
     return m;
   };
@@ -429,162 +527,120 @@ void Arch::Planner::tensor() {
     }
 }
 
-// (5d) sum of tensor products (hdot): behind a tensor record of (5) whose MAC2 is marked as pair 1 of a sum (sumHead), pair after pair, d0 and d2
+// (5d) sum of tensor products (hdot): behind a tensor record of (5) whose MAC2 is marked as pair 1 of a sum (mark TensorDot), pair after pair, d0 and d2
 //      go on through ONE MAC_ADD each (d0 += c00 c10, d2 += c01 c11) and d1 through ONE ADD of a MAC2 of the same four operands
 //      (c00 c11 + c01 c10); every intermediate is read only by the next link.  The links that agree on their four operands, pair by pair, merge
 //      WITH the tensor record into one record per limb: hm_tensor_dot sums the raw products of all pairs and stores the three final sums only.
 //      Never written: the three outputs of every pair but the last, and the per-pair MAC2.  The record takes the place of the last record it
 //      absorbs in the stage list: every operand of every pair is older, every reader of the sums comes after the chains' ends.
-//      Reads: fusedTensor / extraOutputs (5).  Sets on the tensor record: dotOperands, OutputOperand, extraOutputs.
+//      Reads: fusedTensor / extraOutputs (5).  Sets on the tensor record: fu (form TensorDot: reads, terms), OutputOperand, extraOutputs.
 void Arch::Planner::tensorDot() {
   Readers rd = readers();
   Placement place(st);
-  std::vector<Instruction *> heads;
-  for (auto &s : st)
-    for (Instruction *i : s.ins)
-      if (live(i) && i->fusedTensor && i->sumHead && i->dotOperands.empty()) heads.push_back(i);
-  for (Instruction *c : heads) {
-    // pair 1: MAC2 operands (P, S, R, T) = (c00, c11, c01, c10)
-    c->dotOperands = {c->operandList[0], c->operandList[3], c->operandList[2], c->operandList[1]};
-    AddrType d0 = c->extraOutputs[0], d1 = c->OutputOperand, d2 = c->extraOutputs[1];
-    Instruction *last = c;
-    while (c->dotOperands.size() / 4 < HM_TENSOR_DOT_MAX_TERMS) {
-      Instruction *m0 = soleReader(rd, d0, EWE_MAC_ADD, c->mod_id), *m2 = soleReader(rd, d2, EWE_MAC_ADD, c->mod_id), *add = soleReader(rd, d1, EWE_ADD, c->mod_id);
-      if (!m0 || !m2 || !add || m0->operandList[2] != d0 || m2->operandList[2] != d2) break;
-      const AddrType other = add->operandList[0] == d1 ? add->operandList[2] : add->operandList[0];
-      if ((add->operandList[0] != d1 && add->operandList[2] != d1) || other == d1) break;
+  for (Instruction *c : markedHeads(FusedForm::TensorDot)) {
+    if (!c->fusedTensor) continue;
+    Absorber ab(*this, rd, place, c);
+    Fused &f = c->fu;
+    f.form = FusedForm::TensorDot;
+    f.reads = pairOperands(c);   // pair 1
+    f.terms = 1;
+    Triple d = tensorOutputs(c);
+    while (f.terms < HM_TENSOR_DOT_MAX_TERMS) {
+      Instruction *m0 = soleReader(rd, d[0], EWE_MAC_ADD, c->mod_id), *m2 = soleReader(rd, d[2], EWE_MAC_ADD, c->mod_id);
+      AddrType other = 0;
+      Instruction *add = sumLink(rd, d[1], c->mod_id, true, other);
+      if (!m0 || !m2 || !add || m0->operandList[2] != d[0] || m2->operandList[2] != d[2]) break;
       Instruction *mac = producerOf(other);
       if (!mac || !live(mac) || mac->ops != MULT || mac->opcode != EWE_MAC2 || mac->fusedTensor || mac->mod_id != c->mod_id || !onlyReader(rd, other, add)) break;
       const AddrType c00 = m0->operandList[0], c10 = m0->operandList[1], c01 = m2->operandList[0], c11 = m2->operandList[1];
       if (mac->operandList[0] != c00 || mac->operandList[1] != c11 || mac->operandList[2] != c01 || mac->operandList[3] != c10) break;
-      c->dotOperands.insert(c->dotOperands.end(), {c00, c10, c01, c11});
-      for (Instruction *i : {m0, m2, mac, add}) {
-        absorb(c, i);
-        if (place.after(i, last)) last = i;
-      }
-      d0 = m0->OutputOperand; d1 = add->OutputOperand; d2 = m2->OutputOperand;
+      f.reads.insert(f.reads.end(), {c00, c10, c01, c11});
+      ++f.terms;
+      for (Instruction *i : {m0, m2, mac, add}) ab.take(i);
+      d = {m0->OutputOperand, add->OutputOperand, m2->OutputOperand};
     }
-    c->OutputOperand = d1;
-    c->extraOutputs = {d0, d2};
-    for (const Write &w : recordWrites(*c)) producer[w.addr] = c;
-    place.moveTo(c, last);   // to where its last link stood
+    ab.finish(d);
   }
 }
 
-// (5q) scaled square plus constant (hsquare): a tensor record of (5) that the builder marked (squareHead) and whose operand pairs coincide
+// (5q) scaled square plus constant (hsquare): a tensor record of (5) that the builder marked (mark Square) and whose operand pairs coincide
 //      (c00 == c10, c01 == c11: a ciphertext times itself) becomes a record of hm_tensor_square, which reads each polynomial once.  Behind it,
 //      the MUL_CONST records that are the only readers of its three outputs go in when all three carry the same constant (s d0, s d1, s d2), then the
 //      ADD_CONST record that is the only reader of d0 (d0 + k).  The record's outputs become the final buffers, so every later pass sees what it
 //      sees in hmult; it takes the place of the last record it absorbs.  Never written: the products in front of the scalar and of the constant.
-//      Reads: fusedTensor / extraOutputs (5).  Sets on the tensor record: sqOperands, sqHasScale, sqScale, sqHasConst, sqConst, OutputOperand,
+//      Reads: fusedTensor / extraOutputs (5).  Sets on the tensor record: fu (form Square: reads, hasScale, scales, hasConst, constant), OutputOperand,
 //      extraOutputs.
 void Arch::Planner::tensorSquare() {
   Readers rd = readers();
   Placement place(st);
-  std::vector<Instruction *> heads;
-  for (auto &s : st)
-    for (Instruction *i : s.ins)
-      if (live(i) && i->fusedTensor && i->squareHead && i->dotOperands.empty() && i->sqOperands.empty()) heads.push_back(i);
-  for (Instruction *c : heads) {
-    // MAC2 operands (P, S, R, T) = (c00, c11, c01, c10)
-    if (c->operandList[0] != c->operandList[3] || c->operandList[2] != c->operandList[1]) continue;
-    c->sqOperands = {c->operandList[0], c->operandList[2]};
-    AddrType d0 = c->extraOutputs[0], d1 = c->OutputOperand, d2 = c->extraOutputs[1];
-    Instruction *last = c;
-    auto take = [&](Instruction *i) {
-      absorb(c, i);
-      if (place.after(i, last)) last = i;
-    };
-    Instruction *m0 = soleReader(rd, d0, EWE_MUL_CONST, c->mod_id), *m1 = soleReader(rd, d1, EWE_MUL_CONST, c->mod_id), *m2 = soleReader(rd, d2, EWE_MUL_CONST, c->mod_id);
-    if (m0 && m1 && m2 && m0->hasConstant && m1->hasConstant && m2->hasConstant && m0->constant == m1->constant && m0->constant == m2->constant) {
-      c->sqHasScale = true;
-      c->sqScale = m0->constant;
-      for (Instruction *i : {m0, m1, m2}) take(i);
-      d0 = m0->OutputOperand; d1 = m1->OutputOperand; d2 = m2->OutputOperand;
-    }
-    if (Instruction *add = soleReader(rd, d0, EWE_ADD_CONST, c->mod_id)) {
-      if (add->hasConstant) {
-        c->sqHasConst = true;
-        c->sqConst = add->constant;
-        take(add);
-        d0 = add->OutputOperand;
-      }
-    }
-    c->OutputOperand = d1;
-    c->extraOutputs = {d0, d2};
-    for (const Write &w : recordWrites(*c)) producer[w.addr] = c;
-    place.moveTo(c, last);
+  for (Instruction *c : markedHeads(FusedForm::Square)) {
+    const std::vector<AddrType> pair = pairOperands(c);
+    if (!c->fusedTensor || pair[0] != pair[1] || pair[2] != pair[3]) continue;
+    Absorber ab(*this, rd, place, c);
+    Fused &f = c->fu;
+    f.form = FusedForm::Square;
+    f.reads = {pair[0], pair[2]};
+    f.scales = {1};
+    Triple d = tensorOutputs(c);
+    f.hasScale = ab.takeScalars(d, f.scales[0]);
+    ab.takeConstant(d[0]);
+    ab.finish(d);
   }
 }
 
-// (5l) sum of scaled polynomials plus constant (hlincomb): from a MUL_CONST record that the builder marked as term 1 of a sum (lincombHead), term
+// (5l) sum of scaled polynomials plus constant (hlincomb): from a MUL_CONST record that the builder marked as term 1 of a sum (mark Lincomb), term
 //      after term, the running sum goes on through ONE ADD whose other operand is a MUL_CONST record of the same modulus read by nothing else;
 //      behind the last term, ONE ADD_CONST.  Every intermediate is read only by the next link.  The links merge into the marked record:
 //      hm_lincomb sums the raw products s_t x_t of all terms, adds the constant and stores the final sum only.  Never written: the T scaled
 //      polynomials and the T - 1 partial sums (and the sum in front of the constant).  The record takes the place of the last record it absorbs.
 //      Only the builder of HLINCOMB sets the mark: the pass matches nothing in any other op.
-//      Sets on the marked record: lcOperands, lcScales, lcHasConst, lcConst, OutputOperand.
+//      Sets on the marked record: fu (form Lincomb: reads, scales, terms, hasConst, constant), OutputOperand.
 void Arch::Planner::linearCombination() {
   Readers rd = readers();
   Placement place(st);
-  std::vector<Instruction *> heads;
-  for (auto &s : st)
-    for (Instruction *i : s.ins)
-      if (live(i) && i->lincombHead && i->ops == MULT && i->opcode == EWE_MUL_CONST && i->hasConstant && i->lcOperands.empty()) heads.push_back(i);
-  for (Instruction *c : heads) {
-    c->lcOperands = {c->operandList[0]};
-    c->lcScales = {c->constant};
+  for (Instruction *c : markedHeads(FusedForm::Lincomb)) {
+    if (!isScaled(c, c->mod_id)) continue;
+    Absorber ab(*this, rd, place, c);
+    Fused &f = c->fu;
+    f.form = FusedForm::Lincomb;
+    f.reads = {c->operandList[0]};
+    f.scales = {c->constant};
+    f.terms = 1;
     AddrType sum = c->OutputOperand;
-    Instruction *last = c;
-    auto take = [&](Instruction *i) {
-      absorb(c, i);
-      if (place.after(i, last)) last = i;
-    };
-    while (c->lcOperands.size() < HM_LINCOMB_MAX_TERMS) {
-      Instruction *add = soleReader(rd, sum, EWE_ADD, c->mod_id);
-      if (!add) break;
-      const AddrType other = add->operandList[0] == sum ? add->operandList[2] : add->operandList[0];
-      if ((add->operandList[0] != sum && add->operandList[2] != sum) || other == sum) break;
-      Instruction *mul = producerOf(other);
-      if (!mul || !live(mul) || mul->ops != MULT || mul->opcode != EWE_MUL_CONST || !mul->hasConstant || mul->mod_id != c->mod_id || mul->lincombHead ||
-          !onlyReader(rd, other, add))
-        break;
-      c->lcOperands.push_back(mul->operandList[0]);
-      c->lcScales.push_back(mul->constant);
-      take(mul);
-      take(add);
+    while (f.terms < HM_LINCOMB_MAX_TERMS) {
+      AddrType other = 0;
+      Instruction *add = sumLink(rd, sum, c->mod_id, true, other);
+      Instruction *mul = add ? privateScaled(rd, other, add, c->mod_id) : nullptr;
+      if (!mul || mul->mark == FusedForm::Lincomb) break;
+      f.reads.push_back(mul->operandList[0]);
+      f.scales.push_back(mul->constant);
+      ++f.terms;
+      ab.take(mul);
+      ab.take(add);
       sum = add->OutputOperand;
     }
-    if (Instruction *add = soleReader(rd, sum, EWE_ADD_CONST, c->mod_id)) {
-      if (add->hasConstant) {
-        c->lcHasConst = true;
-        c->lcConst = add->constant;
-        take(add);
-        sum = add->OutputOperand;
-      }
-    }
-    c->OutputOperand = sum;
-    producer[sum] = c;
-    place.moveTo(c, last);   // to where its last link stood
+    ab.takeConstant(sum);
+    ab.finish(sum, {});
   }
 }
 
-// (5L) several sums of scaled polynomials over the same inputs (hmlincomb): the live (5l) records of one modulus whose lcOperands are the same list
+// (5L) several sums of scaled polynomials over the same inputs (hmlincomb): the live (5l) records of one modulus whose reads (fu.reads) are the same list
 //      in the same order merge, up to HM_LINCOMB_MULTI_MAX_OUT at a time, into the first of them: hm_lincomb_multi loads every input once per
 //      tile of outputs and stores every sum once.  The merged record carries the outputs, the scalar rows and the constants in the order the sums
 //      stand in the stages, the refInstructions of everything it absorbs, and takes the place of the last record it absorbs: every input is
 //      produced in front of the first of them, and nothing reads an output in front of the last (the builder emits every sum before anything that
 //      reads one).  Only HMLINCOMB produces several (5l) records over one operand list: the pass matches nothing in any other op.
-//      Sets on the first record: mlScales, mlConsts, mlHasConst, OutputOperand (unchanged), extraOutputs.
+//      Sets on the first record: fu (form LincombMulti: rowScales, rowConsts, hasConst), OutputOperand (unchanged), extraOutputs.
 void Arch::Planner::multiCombination() {
+  Readers rd;   // (no link is followed)
   Placement place(st);
   typedef std::pair<uint32_t, std::vector<AddrType>> Key;
   std::map<Key, std::vector<Instruction *>> members;
   std::vector<Key> order;   // first appearance
   for (auto &s : st)
     for (Instruction *i : s.ins)
-      if (live(i) && !i->lcOperands.empty() && i->mlScales.empty() && i->extraOutputs.empty()) {
-        const Key k{i->mod_id, i->lcOperands};
+      if (live(i) && i->fu.form == FusedForm::Lincomb && i->extraOutputs.empty()) {
+        const Key k{i->mod_id, i->fu.reads};
         if (!members.count(k)) order.push_back(k);
         members[k].push_back(i);
       }
@@ -593,23 +649,24 @@ void Arch::Planner::multiCombination() {
     for (size_t b = 0; b < mem.size(); b += HM_LINCOMB_MULTI_MAX_OUT) {
       const size_t e = std::min(mem.size(), b + (size_t)HM_LINCOMB_MULTI_MAX_OUT);
       if (e - b < 2) continue;   // one sum: (5l)'s record and launch
-      Instruction *c = mem[b], *last = c;
+      Absorber ab(*this, rd, place, mem[b]);
+      Fused &f = ab.c->fu;
+      std::vector<AddrType> further;
       for (size_t m = b; m < e; ++m) {
-        Instruction *i = mem[m];
-        c->mlScales.push_back(i->lcScales);
-        c->mlConsts.push_back(i->lcHasConst ? i->lcConst : 0);
-        c->mlHasConst = c->mlHasConst || i->lcHasConst;
-        if (i != c) c->extraOutputs.push_back(i->OutputOperand);
-        absorb(c, i);
-        if (place.after(i, last)) last = i;
+        const Fused &g = mem[m]->fu;   // (m == b: the record's own)
+        f.rowScales.push_back(g.scales);
+        f.rowConsts.push_back(g.hasConst ? g.constant : 0);
+        f.hasConst = f.hasConst || g.hasConst;
+        if (m > b) further.push_back(mem[m]->OutputOperand);
+        ab.take(mem[m]);
       }
-      for (const Write &w : recordWrites(*c)) producer[w.addr] = c;
-      place.moveTo(c, last);
+      f.form = FusedForm::LincombMulti;
+      ab.finish(ab.c->OutputOperand, further);
     }
   }
 }
 
-// (5m) scaled tensor product plus scaled addends plus constant (hmuladd): a tensor record of (5) that the builder marked (muladdHead) becomes a
+// (5m) scaled tensor product plus scaled addends plus constant (hmuladd): a tensor record of (5) that the builder marked (mark MulAdd) becomes a
 //      record of hm_tensor_muladd.  Behind it, the MUL_CONST records that are the only readers of its three outputs go in when all three carry the
 //      same constant (s d0, s d1, s d2).  Then, addend after addend, d0 and d1 each go on through ONE ADD whose other operand is a MUL_CONST record
 //      of the same modulus read by nothing else, both with the same constant u_t (u_t x_t onto d0, u_t y_t onto d1): an addend goes in with both
@@ -617,65 +674,27 @@ void Arch::Planner::multiCombination() {
 //      record's reads become the four product operands plus the 2A addend operands, its outputs the final buffers, so every later pass sees what
 //      it sees in hmult; it takes the place of the last record it absorbs.  Never written: the products in front of the scalar, the 2A scaled
 //      addends and the partial sums.  Only the builder of HMULADD sets the mark: the pass matches nothing in any other op.
-//      Reads: fusedTensor / extraOutputs (5).  Sets on the tensor record: maOperands, maAddScales, maHasScale, maScale, maHasConst, maConst,
+//      Reads: fusedTensor / extraOutputs (5).  Sets on the tensor record: fu (form MulAdd: reads, addends, scales, scales2, hasScale, hasConst, constant),
 //      OutputOperand, extraOutputs.
 void Arch::Planner::tensorMulAdd() {
   Readers rd = readers();
   Placement place(st);
-  std::vector<Instruction *> heads;
-  for (auto &s : st)
-    for (Instruction *i : s.ins)
-      if (live(i) && i->fusedTensor && i->muladdHead && i->dotOperands.empty() && i->sqOperands.empty() && i->maOperands.empty()) heads.push_back(i);
-  for (Instruction *c : heads) {
-    // MAC2 operands (P, S, R, T) = (c00, c11, c01, c10); maOperands = (a, b, c, d) = (c00, c10, c01, c11)
-    c->maOperands = {c->operandList[0], c->operandList[3], c->operandList[2], c->operandList[1]};
-    AddrType d0 = c->extraOutputs[0], d1 = c->OutputOperand, d2 = c->extraOutputs[1];
-    Instruction *last = c;
-    auto take = [&](Instruction *i) {
-      absorb(c, i);
-      if (place.after(i, last)) last = i;
-    };
-    Instruction *m0 = soleReader(rd, d0, EWE_MUL_CONST, c->mod_id), *m1 = soleReader(rd, d1, EWE_MUL_CONST, c->mod_id), *m2 = soleReader(rd, d2, EWE_MUL_CONST, c->mod_id);
-    if (m0 && m1 && m2 && m0->hasConstant && m1->hasConstant && m2->hasConstant && m0->constant == m1->constant && m0->constant == m2->constant) {
-      c->maHasScale = true;
-      c->maScale = m0->constant;
-      for (Instruction *i : {m0, m1, m2}) take(i);
-      d0 = m0->OutputOperand; d1 = m1->OutputOperand; d2 = m2->OutputOperand;
-    }
-    // the ADD behind `sum` and the MUL_CONST that feeds it, if that is all that reads them
-    auto link = [&](AddrType sum, Instruction *&add, Instruction *&mul) {
-      add = soleReader(rd, sum, EWE_ADD, c->mod_id);
-      if (!add) return false;
-      const AddrType other = add->operandList[0] == sum ? add->operandList[2] : add->operandList[0];
-      if ((add->operandList[0] != sum && add->operandList[2] != sum) || other == sum) return false;
-      mul = producerOf(other);
-      return mul && live(mul) && mul->ops == MULT && mul->opcode == EWE_MUL_CONST && mul->hasConstant && mul->mod_id == c->mod_id && onlyReader(rd, other, add);
-    };
-    while (c->maAddScales.size() < HM_TENSOR_MULADD_MAX_ADDENDS) {
-      Instruction *a0 = nullptr, *u0 = nullptr, *a1 = nullptr, *u1 = nullptr;
-      if (!link(d0, a0, u0) || !link(d1, a1, u1) || u0->constant != u1->constant) break;
-      c->maOperands.push_back(u0->operandList[0]);
-      c->maOperands.push_back(u1->operandList[0]);
-      c->maAddScales.push_back(u0->constant);
-      for (Instruction *i : {u0, a0, u1, a1}) take(i);
-      d0 = a0->OutputOperand; d1 = a1->OutputOperand;
-    }
-    if (Instruction *add = soleReader(rd, d0, EWE_ADD_CONST, c->mod_id)) {
-      if (add->hasConstant) {
-        c->maHasConst = true;
-        c->maConst = add->constant;
-        take(add);
-        d0 = add->OutputOperand;
-      }
-    }
-    c->OutputOperand = d1;
-    c->extraOutputs = {d0, d2};
-    for (const Write &w : recordWrites(*c)) producer[w.addr] = c;
-    place.moveTo(c, last);
+  for (Instruction *c : markedHeads(FusedForm::MulAdd)) {
+    if (!c->fusedTensor) continue;
+    Absorber ab(*this, rd, place, c);
+    Fused &f = c->fu;
+    f.form = FusedForm::MulAdd;
+    f.reads = pairOperands(c);
+    f.scales = {1};
+    Triple d = tensorOutputs(c);
+    f.hasScale = ab.takeScalars(d, f.scales[0]);
+    ab.takeAddends(d[0], d[1], HM_TENSOR_MULADD_MAX_ADDENDS);
+    ab.takeConstant(d[0]);
+    ab.finish(d);
   }
 }
 
-// (5a) scaled sum of tensor products plus scaled addends plus constant (hdotadd): a tensor record of (5) that the builder marked (dotaddHead) becomes
+// (5a) scaled sum of tensor products plus scaled addends plus constant (hdotadd): a tensor record of (5) that the builder marked (mark DotAdd) becomes
 //      a record of hm_tensor_dotadd.  It absorbs, in this order:
 //        its three sole-reader MUL_CONST records when all three carry the same constant (s_1 d0, s_1 d1, s_1 d2);
 //        pair after pair, the three ADD records that are the only readers of the running d0, d1, d2 and whose other operands are the three
@@ -687,137 +706,74 @@ void Arch::Planner::tensorMulAdd() {
 //      sees what it sees in hmult; it takes the place of the last record it absorbs and keeps fusedTensor, so pass (6) stays off it.  Never
 //      written: the 3T products, their scaled copies, the 2A scaled addends and the partial sums.  Only the builder of HDOTADD sets the mark: the
 //      pass matches nothing in any other op.
-//      Reads: fusedTensor / extraOutputs (5).  Sets on the marked record: daOperands, daScales, daAddScales, daHasScale, daHasConst, daConst,
+//      Reads: fusedTensor / extraOutputs (5).  Sets on the marked record: fu (form DotAdd: reads, terms, addends, scales, scales2, hasScale, hasConst, constant),
 //      OutputOperand, extraOutputs.
 void Arch::Planner::tensorDotAdd() {
   Readers rd = readers();
   Placement place(st);
-  std::vector<Instruction *> heads;
-  for (auto &s : st)
-    for (Instruction *i : s.ins)
-      if (live(i) && i->fusedTensor && i->dotaddHead && i->dotOperands.empty() && i->sqOperands.empty() && i->maOperands.empty() && i->daOperands.empty())
-        heads.push_back(i);
-  for (Instruction *c : heads) {
-    // MAC2 operands (P, S, R, T) = (c00, c11, c01, c10); daOperands = (a, b, c, d) = (c00, c10, c01, c11) per pair
-    c->daOperands = {c->operandList[0], c->operandList[3], c->operandList[2], c->operandList[1]};
-    std::array<AddrType, 3> d = {c->extraOutputs[0], c->OutputOperand, c->extraOutputs[1]};
-    Instruction *last = c;
-    auto take = [&](Instruction *i) {
-      absorb(c, i);
-      if (place.after(i, last)) last = i;
-    };
-    // the MUL_CONST records that are the only readers of the three polynomials `of`, if all three carry one constant
-    typedef std::array<Instruction *, 3> Three;
-    auto scalars = [&](const std::array<AddrType, 3> &of, Three &m) {
-      for (int i = 0; i < 3; ++i) m[i] = soleReader(rd, of[i], EWE_MUL_CONST, c->mod_id);
-      return m[0] && m[1] && m[2] && m[0]->hasConstant && m[1]->hasConstant && m[2]->hasConstant && m[0]->constant == m[1]->constant &&
-             m[0]->constant == m[2]->constant;
-    };
-    Three m;
-    uint64_t s1 = 1;
-    if (scalars(d, m)) {
-      c->daHasScale = true;
-      s1 = m[0]->constant;
-      for (int i = 0; i < 3; ++i) { take(m[i]); d[i] = m[i]->OutputOperand; }
-    }
-    c->daScales.push_back(s1);
-    // the ADD behind `sum` if that is all that reads it, and its other operand
-    auto sumLink = [&](AddrType sum, AddrType &other) -> Instruction * {
-      Instruction *add = soleReader(rd, sum, EWE_ADD, c->mod_id);
-      if (!add) return nullptr;
-      other = add->operandList[0] == sum ? add->operandList[2] : add->operandList[0];
-      if ((add->operandList[0] != sum && add->operandList[2] != sum) || other == sum) return nullptr;
-      return add;
-    };
-    while (c->daScales.size() < HM_TENSOR_DOTADD_MAX_TERMS) {
-      Three add, mul = {nullptr, nullptr, nullptr};
-      std::array<AddrType, 3> src;
+  for (Instruction *c : markedHeads(FusedForm::DotAdd)) {
+    if (!c->fusedTensor) continue;
+    Absorber ab(*this, rd, place, c);
+    Fused &f = c->fu;
+    f.form = FusedForm::DotAdd;
+    f.reads = pairOperands(c);
+    f.scales = {1};
+    f.terms = 1;
+    Triple d = tensorOutputs(c);
+    f.hasScale = ab.takeScalars(d, f.scales[0]);
+    while (f.terms < HM_TENSOR_DOTADD_MAX_TERMS) {
+      Three add, mul;
+      Triple src;
       bool ok = true;
-      for (int i = 0; i < 3 && ok; ++i) ok = (add[i] = sumLink(d[i], src[i])) != nullptr;
+      for (int i = 0; i < 3 && ok; ++i) ok = (add[i] = sumLink(rd, d[i], c->mod_id, true, src[i])) != nullptr;
       if (!ok) break;
       // through the pair's MUL_CONST records, all three or none
       int scaledOps = 0;
-      for (int i = 0; i < 3; ++i) {
-        Instruction *p = producerOf(src[i]);
-        if (p && live(p) && p->ops == MULT && p->opcode == EWE_MUL_CONST && !p->fusedTensor && p->hasConstant && p->mod_id == c->mod_id && onlyReader(rd, src[i], add[i])) {
-          mul[i] = p;
-          ++scaledOps;
-        }
-      }
+      for (int i = 0; i < 3; ++i)
+        if ((mul[i] = privateScaled(rd, src[i], add[i], c->mod_id))) ++scaledOps;
       if (scaledOps != 0 && scaledOps != 3) break;
-      std::array<AddrType, 3> prod = src;
+      Triple prod = src;
       if (scaledOps == 3) {
         if (mul[0]->constant != mul[1]->constant || mul[0]->constant != mul[2]->constant) break;
         for (int i = 0; i < 3; ++i) prod[i] = mul[i]->operandList[0];
       }
-      // the three products are the outputs of one unmarked tensor record, each read by its link only
+      // the three products are the outputs of one unmarked tensor record that no pass has taken, each read by its link only
       Instruction *x = producerOf(prod[1]);
-      if (!x || x == c || !live(x) || !x->fusedTensor || x->dotaddHead || x->mod_id != c->mod_id || !x->dotOperands.empty() || !x->sqOperands.empty() ||
-          !x->maOperands.empty() || !x->daOperands.empty() || x->OutputOperand != prod[1] || x->extraOutputs.size() != 2 ||
-          x->extraOutputs[0] != prod[0] || x->extraOutputs[1] != prod[2])
+      if (!x || x == c || !live(x) || !x->fusedTensor || x->mark == FusedForm::DotAdd || x->mod_id != c->mod_id || x->fu.form != FusedForm::None ||
+          x->extraOutputs.size() != 2 || tensorOutputs(x) != prod)
         break;
       for (int i = 0; i < 3 && ok; ++i) ok = onlyReader(rd, prod[i], scaledOps ? mul[i] : add[i]);
       if (!ok) break;
-      c->daOperands.insert(c->daOperands.end(), {x->operandList[0], x->operandList[3], x->operandList[2], x->operandList[1]});
-      c->daScales.push_back(scaledOps ? mul[0]->constant : 1);
-      if (scaledOps) c->daHasScale = true;
-      take(x);
+      const std::vector<AddrType> pair = pairOperands(x);
+      f.reads.insert(f.reads.end(), pair.begin(), pair.end());
+      f.scales.push_back(scaledOps ? mul[0]->constant : 1);
+      ++f.terms;
+      if (scaledOps) f.hasScale = true;
+      ab.take(x);
       for (int i = 0; i < 3; ++i) {
-        if (mul[i]) take(mul[i]);
-        take(add[i]);
+        if (mul[i]) ab.take(mul[i]);
+        ab.take(add[i]);
         d[i] = add[i]->OutputOperand;
       }
     }
-    // the addends: (5m)'s links
-    auto link = [&](AddrType sum, Instruction *&add, Instruction *&mul) {
-      AddrType other = 0;
-      add = sumLink(sum, other);
-      if (!add) return false;
-      mul = producerOf(other);
-      return mul && live(mul) && mul->ops == MULT && mul->opcode == EWE_MUL_CONST && !mul->fusedTensor && mul->hasConstant && mul->mod_id == c->mod_id &&
-             onlyReader(rd, other, add);
-    };
-    std::vector<AddrType> addends;
-    while (c->daAddScales.size() < HM_TENSOR_DOTADD_MAX_ADDENDS) {
-      Instruction *a0 = nullptr, *u0 = nullptr, *a1 = nullptr, *u1 = nullptr;
-      if (!link(d[0], a0, u0) || !link(d[1], a1, u1) || u0->constant != u1->constant) break;
-      addends.push_back(u0->operandList[0]);
-      addends.push_back(u1->operandList[0]);
-      c->daAddScales.push_back(u0->constant);
-      for (Instruction *i : {u0, a0, u1, a1}) take(i);
-      d[0] = a0->OutputOperand; d[1] = a1->OutputOperand;
-    }
-    c->daOperands.insert(c->daOperands.end(), addends.begin(), addends.end());
-    if (Instruction *add = soleReader(rd, d[0], EWE_ADD_CONST, c->mod_id)) {
-      if (add->hasConstant) {
-        c->daHasConst = true;
-        c->daConst = add->constant;
-        take(add);
-        d[0] = add->OutputOperand;
-      }
-    }
-    c->OutputOperand = d[1];
-    c->extraOutputs = {d[0], d[2]};
-    for (const Write &w : recordWrites(*c)) producer[w.addr] = c;
-    place.moveTo(c, last);
+    ab.takeAddends(d[0], d[1], HM_TENSOR_DOTADD_MAX_ADDENDS);   // the addends and the constant: (5m)'s
+    ab.takeConstant(d[0]);
+    ab.finish(d);
   }
 }
 
-// (5r) real and imaginary parts (hreim): from an ADD record x + y that the builder marked (reimHead), with x an op input's limb and y the limb of
+// (5r) real and imaginary parts (hreim): from an ADD record x + y that the builder marked (mark ReIm), with x an op input's limb and y the limb of
 //      its conjugate: the ONE live SUB record x - y of the same two operands, in this order, and modulus, whose output is read by ONE MUL record
 //      only, the difference its operand a and its operand b a limb that nothing produces (the stored evaluation form of -X^(N/2)).  The three
 //      merge into the marked record: hm_reim_split reads x and y once and stores the sum and the product; the factor is derived by the back-end
 //      from its roots, so the fused record does not read the stored one.  Never written: the difference.  The record takes the place of the last
 //      record it absorbs.  Only the builder of HREIM sets the mark: the pass matches nothing in any other op.
-//      Sets on the marked record: reimOperands, extraOutputs.
+//      Sets on the marked record: fu (form ReIm: reads), extraOutputs.
 void Arch::Planner::realImaginary() {
   Readers rd = readers();
   Placement place(st);
-  std::vector<Instruction *> heads;
-  for (auto &s : st)
-    for (Instruction *i : s.ins)
-      if (live(i) && i->reimHead && i->ops == MULT && i->opcode == EWE_ADD && i->reimOperands.empty() && i->extraOutputs.empty()) heads.push_back(i);
-  for (Instruction *c : heads) {
+  for (Instruction *c : markedHeads(FusedForm::ReIm)) {
+    if (c->ops != MULT || c->opcode != EWE_ADD || !c->extraOutputs.empty()) continue;
     const AddrType x = c->operandList[0], y = c->operandList[2];
     Instruction *sub = nullptr;
     size_t subs = 0;
@@ -826,20 +782,17 @@ void Arch::Planner::realImaginary() {
     if (subs != 1) continue;
     Instruction *mul = soleReader(rd, sub->OutputOperand, EWE_MUL, c->mod_id);
     if (!mul || mul->operandList[0] != sub->OutputOperand || mul->operandList[1] == sub->OutputOperand || producerOf(mul->operandList[1])) continue;
-    c->reimOperands = {x, y};
-    c->extraOutputs = {mul->OutputOperand};
-    Instruction *last = c;
-    for (Instruction *i : {sub, mul}) {
-      absorb(c, i);
-      if (place.after(i, last)) last = i;
-    }
-    producer[mul->OutputOperand] = c;
-    place.moveTo(c, last);   // to where its last link stood
+    Absorber ab(*this, rd, place, c);
+    c->fu.form = FusedForm::ReIm;
+    c->fu.reads = {x, y};
+    ab.take(sub);
+    ab.take(mul);
+    ab.finish(c->OutputOperand, {mul->OutputOperand});   // (the sum stays the record's own output)
   }
 }
 
 // (5c) sum of polynomials times a + b X^(N/2) plus constant (hclincomb): from a MUL_CONST record a_1 x_1 that the builder marked as term 1 of such a
-//      sum (clincombHead).  A term is the ADD of two MUL_CONST records of the same modulus, each read by nothing else: the real part a_t x_t, and
+//      sum (mark CLincomb).  A term is the ADD of two MUL_CONST records of the same modulus, each read by nothing else: the real part a_t x_t, and
 //      the monomial part whose operand is the output, read by nothing else, of a MUL record of the SAME x_t by a limb that nothing produces (the
 //      stored evaluation form of -X^(N/2)); its constant is q - b_t.  Term 1 is the ADD that reads the marked record; term after term, the running
 //      sum goes on through ONE ADD whose other operand is such a term, read by nothing else; behind the last term, ONE ADD_CONST.  The links merge
@@ -847,27 +800,20 @@ void Arch::Planner::realImaginary() {
 //      sum only; the factor is derived by the back-end from its roots, so the fused record does not read the stored one.  Never written: the 4T
 //      parts and the T - 1 partial sums (and the sum in front of the constant).  The record takes the place of the last record it absorbs.
 //      Only the builder of HCLINCOMB sets the mark: the pass matches nothing in any other op.
-//      Sets on the marked record: clOperands, clScalesRe, clScalesIm, clHasConst, clConst, OutputOperand.
+//      Sets on the marked record: fu (form CLincomb: reads, scales, scales2, terms, hasConst, constant), OutputOperand.
 void Arch::Planner::complexCombination() {
   Readers rd = readers();
   Placement place(st);
-  std::vector<Instruction *> heads;
-  for (auto &s : st)
-    for (Instruction *i : s.ins)
-      if (live(i) && i->clincombHead && i->ops == MULT && i->opcode == EWE_MUL_CONST && i->hasConstant && i->clOperands.empty()) heads.push_back(i);
-  for (Instruction *c : heads) {
+  for (Instruction *c : markedHeads(FusedForm::CLincomb)) {
+    if (!isScaled(c, c->mod_id)) continue;
     const uint64_t q = A.modulus(c->mod_id);
-    // the records of one term behind its ADD `term`, with `re` one of its operands' producers (null: either): re, rot, im, or none
+    // the records of one term behind its ADD `term`: re, rot, im, or none
     struct Term { Instruction *re = nullptr, *rot = nullptr, *im = nullptr; };
-    auto scaled = [&](AddrType a, Instruction *reader) -> Instruction * {
-      Instruction *m = producerOf(a);
-      return m && live(m) && m->ops == MULT && m->opcode == EWE_MUL_CONST && m->hasConstant && m->mod_id == c->mod_id && onlyReader(rd, a, reader) ? m : nullptr;
-    };
     auto termOf = [&](Instruction *term, Term &t) {
       if (term->operandList[0] == term->operandList[2]) return false;
-      t.re = scaled(term->operandList[0], term);
-      t.im = scaled(term->operandList[2], term);
-      if (!t.re || !t.im || t.im->clincombHead || (t.re->clincombHead && t.re != c)) return false;
+      t.re = privateScaled(rd, term->operandList[0], term, c->mod_id);
+      t.im = privateScaled(rd, term->operandList[2], term, c->mod_id);
+      if (!t.re || !t.im || t.im->mark == FusedForm::CLincomb || (t.re->mark == FusedForm::CLincomb && t.re != c)) return false;
       t.rot = producerOf(t.im->operandList[0]);
       return t.rot && isMul(t.rot, c->mod_id) && !t.rot->fusedTensor && onlyReader(rd, t.rot->OutputOperand, t.im) &&
              t.rot->operandList[0] == t.re->operandList[0] && t.rot->operandList[1] != t.rot->operandList[0] && !producerOf(t.rot->operandList[1]);
@@ -875,51 +821,39 @@ void Arch::Planner::complexCombination() {
     Instruction *first = soleReader(rd, c->OutputOperand, EWE_ADD, c->mod_id);
     Term t1;
     if (!first || first->operandList[0] != c->OutputOperand || !termOf(first, t1) || t1.re != c) continue;
-    Instruction *last = c;
-    auto take = [&](Instruction *i) {
-      absorb(c, i);
-      if (place.after(i, last)) last = i;
-    };
+    Absorber ab(*this, rd, place, c);
+    Fused &f = c->fu;
+    f.form = FusedForm::CLincomb;
     auto add = [&](const Term &t) {
-      c->clOperands.push_back(t.re->operandList[0]);
-      c->clScalesRe.push_back(t.re->constant);
-      c->clScalesIm.push_back(t.im->constant ? q - t.im->constant : 0);
-      take(t.re); take(t.rot); take(t.im);
+      f.reads.push_back(t.re->operandList[0]);
+      f.scales.push_back(t.re->constant);
+      f.scales2.push_back(t.im->constant ? q - t.im->constant : 0);
+      ++f.terms;
+      ab.take(t.re); ab.take(t.rot); ab.take(t.im);
     };
-    // (the marked record's own fields are read by add() before anything overwrites them: re == c, absorb(c, c) does nothing)
-    add(t1);
-    take(first);
+    add(t1);   // (re == c: absorbing itself does nothing)
+    ab.take(first);
     AddrType sum = first->OutputOperand;
-    while (c->clOperands.size() < HM_CLINCOMB_MAX_TERMS) {
-      Instruction *link = soleReader(rd, sum, EWE_ADD, c->mod_id);
-      if (!link || link->operandList[0] != sum || link->operandList[2] == sum) break;
-      const AddrType other = link->operandList[2];
-      Instruction *term = producerOf(other);
+    while (f.terms < HM_CLINCOMB_MAX_TERMS) {
+      AddrType other = 0;
+      Instruction *link = sumLink(rd, sum, c->mod_id, false, other);
+      Instruction *term = link ? producerOf(other) : nullptr;
       Term t;
       if (!term || !live(term) || term->ops != MULT || term->opcode != EWE_ADD || term->mod_id != c->mod_id || term->fusedTensor || !onlyReader(rd, other, link) ||
           !termOf(term, t))
         break;
       add(t);
-      take(term);
-      take(link);
+      ab.take(term);
+      ab.take(link);
       sum = link->OutputOperand;
     }
-    if (Instruction *k = soleReader(rd, sum, EWE_ADD_CONST, c->mod_id)) {
-      if (k->hasConstant) {
-        c->clHasConst = true;
-        c->clConst = k->constant;
-        take(k);
-        sum = k->OutputOperand;
-      }
-    }
-    c->OutputOperand = sum;
-    producer[sum] = c;
-    place.moveTo(c, last);   // to where its last link stood
+    ab.takeConstant(sum);
+    ab.finish(sum, {});
   }
 }
 
 // (5p) sum of ciphertexts times plaintexts plus a plaintext on c0 (hplincomb): from a MUL record p_1 (.) x_1 that the builder marked as term 1 of
-//      one component's sum (plincombHead).  A chain is that record followed, term after term, by ONE MAC_ADD record of the same modulus whose
+//      one component's sum (mark PLincomb).  A chain is that record followed, term after term, by ONE MAC_ADD record of the same modulus whose
 //      operand c is the running sum, read by nothing else; behind the last term, ONE marked ADD of the sum (operand a) and a limb that nothing
 //      produces (the plaintext addend).  Two chains of one modulus whose plaintext limbs (operand b) coincide term by term are the two components
 //      of one output limb: they merge into the marked record of the chain that carries the addend, or of the earlier one if neither does.
@@ -927,7 +861,7 @@ void Arch::Planner::complexCombination() {
 //      addend to c0's and stores the two final sums only.  A chain without a partner stays as it is.  Never written: the 2 (T - 1) partial sums
 //      and the sum in front of the addend.  The record takes the place of the last record it absorbs.
 //      Only the builder of HPLINCOMB sets the mark: the pass matches nothing in any other op.
-//      Sets on the marked record: plOperands, plHasAddend, plAddend, OutputOperand, extraOutputs.
+//      Sets on the marked record: fu (form PLincomb: reads, terms, hasAddend), OutputOperand, extraOutputs.
 void Arch::Planner::plaintextCombination() {
   Readers rd = readers();
   Placement place(st);
@@ -935,54 +869,44 @@ void Arch::Planner::plaintextCombination() {
   typedef std::pair<uint32_t, std::vector<AddrType>> Key;   // modulus, the plaintext limb of every term
   std::map<Key, std::vector<Sum>> byPlain;
   std::vector<Key> order;   // first appearance
-  for (auto &s : st)
-    for (Instruction *i : s.ins) {
-      if (!live(i) || !i->plincombHead || !isMul(i, i->mod_id) || i->fusedTensor || !i->plOperands.empty()) continue;
-      Sum c;
-      c.terms = {i};
-      while (c.terms.size() < HM_PLINCOMB_MAX_TERMS) {
-        Instruction *next = soleReader(rd, c.terms.back()->OutputOperand, EWE_MAC_ADD, i->mod_id);
-        if (!next || next->operandList[2] != c.terms.back()->OutputOperand || next->operandList[0] == next->operandList[2] ||
-            next->operandList[1] == next->operandList[2])
-          break;
-        c.terms.push_back(next);
-      }
-      const AddrType sum = c.terms.back()->OutputOperand;
-      Instruction *add = soleReader(rd, sum, EWE_ADD, i->mod_id);
-      if (add && add->plincombHead && add->operandList[0] == sum && add->operandList[2] != sum && !producerOf(add->operandList[2])) c.add = add;
-      Key key{i->mod_id, {}};
-      for (Instruction *t : c.terms) key.second.push_back(t->operandList[1]);
-      if (!byPlain.count(key)) order.push_back(key);
-      byPlain[key].push_back(c);
+  for (Instruction *i : markedHeads(FusedForm::PLincomb)) {
+    if (!isMul(i, i->mod_id) || i->fusedTensor) continue;   // (the marked ADD of the addend is no head)
+    Sum c;
+    c.terms = {i};
+    while (c.terms.size() < HM_PLINCOMB_MAX_TERMS) {
+      Instruction *next = soleReader(rd, c.terms.back()->OutputOperand, EWE_MAC_ADD, i->mod_id);
+      if (!next || next->operandList[2] != c.terms.back()->OutputOperand || next->operandList[0] == next->operandList[2] ||
+          next->operandList[1] == next->operandList[2])
+        break;
+      c.terms.push_back(next);
     }
+    AddrType addend = 0;
+    Instruction *add = sumLink(rd, c.terms.back()->OutputOperand, i->mod_id, false, addend);
+    if (add && add->mark == FusedForm::PLincomb && !producerOf(addend)) c.add = add;
+    Key key{i->mod_id, {}};
+    for (Instruction *t : c.terms) key.second.push_back(t->operandList[1]);
+    if (!byPlain.count(key)) order.push_back(key);
+    byPlain[key].push_back(c);
+  }
   for (const Key &key : order) {
     std::vector<Sum> &sums = byPlain[key];
     if (sums.size() != 2 || (sums[0].add && sums[1].add)) continue;
     const Sum &s0 = sums[1].add ? sums[1] : sums[0], &s1 = sums[1].add ? sums[0] : sums[1];
-    Instruction *c = s0.terms[0];
-    for (size_t t = 0; t < s0.terms.size(); ++t) {
-      c->plOperands.push_back(s0.terms[t]->operandList[1]);
-      c->plOperands.push_back(s0.terms[t]->operandList[0]);
-      c->plOperands.push_back(s1.terms[t]->operandList[0]);
-    }
-    Instruction *last = c;
-    auto take = [&](Instruction *i) {
-      absorb(c, i);
-      if (place.after(i, last)) last = i;
-    };
-    for (Instruction *i : s0.terms) take(i);
-    for (Instruction *i : s1.terms) take(i);
+    Absorber ab(*this, rd, place, s0.terms[0]);
+    Fused &f = ab.c->fu;
+    f.form = FusedForm::PLincomb;
+    f.terms = (uint32_t)s0.terms.size();
+    for (size_t t = 0; t < s0.terms.size(); ++t) f.reads.insert(f.reads.end(), {s0.terms[t]->operandList[1], s0.terms[t]->operandList[0], s1.terms[t]->operandList[0]});
+    for (Instruction *i : s0.terms) ab.take(i);
+    for (Instruction *i : s1.terms) ab.take(i);
     AddrType out0 = s0.terms.back()->OutputOperand;
     if (s0.add) {
-      c->plHasAddend = true;
-      c->plAddend = s0.add->operandList[2];
-      take(s0.add);
+      f.hasAddend = true;
+      f.reads.push_back(s0.add->operandList[2]);
+      ab.take(s0.add);
       out0 = s0.add->OutputOperand;
     }
-    c->OutputOperand = out0;
-    c->extraOutputs = {s1.terms.back()->OutputOperand};
-    for (const Write &w : recordWrites(*c)) producer[w.addr] = c;
-    place.moveTo(c, last);   // to where its last link stood
+    ab.finish(out0, {s1.terms.back()->OutputOperand});
   }
 }
 

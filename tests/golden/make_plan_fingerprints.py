@@ -46,6 +46,20 @@ SUM_OPS = [("hlintrans", [{"rotations": r} for r in (1, 4, 16)], "fuse_lintrans"
            ("hbsgs", [{"rotations": r, "giants": g} for r, g in ((1, 2), (4, 4), (16, 2), (3, 16))], "fuse_bsgs")]
 BSGS_SWITCHES = [{"fuse_rotsum": 0}, {"fuse_lintrans": 0, "fuse_bsgs": 0}, {"fuse_hoist": 0, "fuse_lintrans": 0, "fuse_bsgs": 0}]
 BSGS_TOP_BATCH = 5   # headline point only: the largest batch of hbsgs's bench shape (limb-polys are addressed by 16-bit indices)
+# the fused element-wise ops (passes 5q, 5l, 5L, 5m, 5r, 5c, 5p, 5a): (op, variants, the op's own planner switch).  Each runs fused, unfused and
+# with its own switch off, at EW_POINTS
+_01 = (0, 1)
+EW_OPS = [("hsquare", [{"sq_scale": s, "sq_const": c} for s in _01 for c in _01], "fuse_square"),
+          ("hlincomb", [{"terms": t, "lc_const": c, "rescale": r} for t in (1, 4, 16) for c in _01 for r in _01], "fuse_lincomb"),
+          ("hmlincomb", [{"terms": t, "outputs": m, "ml_const": c, "rescale": r}
+                         for t, m in ((1, 1), (4, 4), (16, 16), (3, 5)) for c in _01 for r in _01], "fuse_mlincomb"),
+          ("hmuladd", [{"addends": a, "ma_scale": s, "ma_const": c} for a in (0, 1, 8) for s in _01 for c in _01], "fuse_muladd"),
+          ("hreim", [{}], "fuse_reim"),
+          ("hclincomb", [{"terms": t, "cl_const": c, "rescale": r} for t in (1, 4, 16) for c in _01 for r in _01], "fuse_clincomb"),
+          ("hplincomb", [{"terms": t, "pl_addend": a, "rescale": r} for t in (1, 4, 16) for a in _01 for r in _01], "fuse_plincomb"),
+          ("hdotadd", [{"terms": t, "addends": a, "da_scale": s, "da_const": c}
+                       for t, a in ((1, 0), (2, 1), (4, 2), (16, 8)) for s in _01 for c in _01], "fuse_dotadd")]
+EW_POINTS = [HEADLINE, ("config_4_N15.cfg", 16, 10, 4), ("config_4.cfg", 8, 8, 8)]
 
 
 def param_points(op):
@@ -85,6 +99,11 @@ def grid():
                     for b in BATCHES + ([BSGS_TOP_BATCH] if op == "hbsgs" and (cfg, L, ell, alpha) == HEADLINE else []):
                         pts.append((cfg, L, ell, alpha, op, dict(variant, **sw, batch=b)))
             g[" ".join([op] + [f"{k}={v}" for k, v in variant.items()])] = pts
+    for op, variants, own in EW_OPS:
+        for variant in variants:
+            g[" ".join([op] + [f"{k}={v}" for k, v in variant.items()])] = [
+                (cfg, L, ell, alpha, op, dict(variant, **sw, batch=b))
+                for cfg, L, ell, alpha in EW_POINTS for sw in ({}, {"fuse": 0}, {own: 0}) for b in BATCHES]
     for cfg, L, ell, alpha in (HEADLINE, SET_C):
         for op in ("hmult", "hrotate"):
             for world in (2, 4, 8, 16):
